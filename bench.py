@@ -152,12 +152,36 @@ WARM_NOTE = ("one launch per step for the whole batch (lpx_group_fused: update o
 LEGS = ("bnb", "bnb_warm", "bnb_prune", "bnb_prune_mid", "knapsack", "roofline", "config2", "revised", "cpu")
 
 
+def dump_outputs(out_dir, dt, status, st):
+    """What the last timed headline step handed its caller, as float64 .npy files in out_dir (< 64 MB in all): the solve's
+    status and pivot count, the pivot trace, the basis, the objective row and rhs column of the final tableau whole, and a
+    fixed, seeded sample of its entries with their flat indices (the whole tableau when it has at most 2**20 entries)."""
+    import numpy as np
+    T, basis = dt.download()
+    R, C = T.shape
+    k = min(R * C, 1 << 20)
+    idx = np.arange(k, dtype=np.int64) if k == R * C else np.sort(np.random.default_rng(0).integers(0, R * C, size=k))
+    arrays = {
+        "status": np.array([status, st["pivots"]], dtype=np.float64),
+        "trace": dt.trace().astype(np.float64),
+        "basis": basis.astype(np.float64),
+        "objective_row": T[-1, :],
+        "rhs": T[:, -1],
+        "tableau_sample_index": idx.astype(np.float64),
+        "tableau_sample": T.reshape(-1)[idx],
+    }
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--launch-check", action="store_true", help="every rank prints its launch environment as JSON and exits")
     ap.add_argument("--only", default="", help="comma-separated subset of the extra legs: " + ",".join(LEGS))
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps of the headline workload (at least 1)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--m", type=int, default=4096)
     ap.add_argument("--n", type=int, default=8192)
@@ -182,7 +206,11 @@ def main():
     ap.add_argument("--bnb-warm-concurrent", type=int, default=256)
     ap.add_argument("--knap-nodes", type=int, default=1000000, help="pop budget per rank (config 5 leg)")
     ap.add_argument("--revised-iters", type=int, default=300)
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last headline step computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     only = set(x for x in args.only.split(",") if x)
     if only - set(LEGS):
         ap.error(f"--only: unknown leg(s) {sorted(only - set(LEGS))}")
@@ -319,7 +347,7 @@ def main():
         assert status == 0 or st["pivots"] == args.pivots_per_step, f"cap reached after {st['pivots']} pivots"
         assert not (rank == 0 and (m, n) == (4096, 8192) and args.pivots_per_step <= 50000) or st["pivots"] == args.pivots_per_step, \
             f"the headline LP stopped after {st['pivots']} pivots with status {status}"
-        return st
+        return status, st
 
     progress(f"headline solves ({R}x{C}, {args.pivots_per_step} pivots per step)")
     for _ in range(args.warmup):
@@ -329,13 +357,15 @@ def main():
     pivots = 0
     loop_ms = 0.0
     for _ in range(args.steps):
-        st = step()
+        status, st = step()
         pivots += st["pivots"]
         loop_ms += st["loop_ms"]
     barrier()
     dt_s = time.perf_counter() - t0
     total_pivots, wall = reduce_sum_max(pivots, dt_s)
     per_rank_pivots = gather_list(pivots)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dt, status, st)
 
     out = {
         "metric": METRIC,
