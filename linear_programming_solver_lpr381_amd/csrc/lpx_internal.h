@@ -73,10 +73,20 @@ struct FusedParams {
     double* T1; double* prow1; double* rhs1;
     DevState* rec;       // two state records: a launch reads rec[par] and writes rec[1 - par]; pad[2] = launch count, pad[3] = tableau buffer
     int par;             // set per launch by launch_pivot_fused
+    // deferred pivots of the single-tableau run (run_fused; the group step leaves them alone): ring slots of 2 * defer pending
+    // pivots -- normalised pivot row [ld], factor column [R capacity], pivot row index -- and the launch's slot
+    double* pring; double* fring; int32_t* rring;
+    int defer;           // pivots per sweep (LPX_PIVOT_DEFER)
+    int lm;              // set per launch by launch_pivot_fused: launch number mod 2 * defer
 };
 int fused_policy(int ld, int R);             // 0 = default cache policy (lpx_pivot_fused_c), 2 = streaming mix, 1 = all nt
+int pivot_defer_max();                       // deepest deferral the sweep kernels are built for
 hipError_t launch_fused_init(const FusedParams& f, hipStream_t s);
-hipError_t launch_pivot_fused(const FusedParams& f, int par, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// launch L of a run (0: the prologue's): a sweep applying f.defer pending pivots when L is a positive multiple of f.defer,
+// else select-only
+hipError_t launch_pivot_fused(const FusedParams& f, long long L, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// the n pivots a finished run left pending (its last record: buffer, count, oldest slot), applied into buffer 0
+hipError_t launch_pivot_flush(const FusedParams& f, int buf, int n, int slot0, hipStream_t s);
 // fused group step (lpx_group_fused / _c): one launch per step for a whole group of node LPs, see lpx_kernels.hip
 hipError_t launch_group_fused_init(const FusedParams* arr, const int* fresh, int nfresh, const DevState* init, hipStream_t s);
 hipError_t launch_group_fused_gather(const FusedParams* arr, int count, DevState* out, int* cur, hipStream_t s);
@@ -184,6 +194,7 @@ struct LoopCtx {
     std::function<int(hipStream_t)> prologue;                               // once, before the loop
     int launches_per_iter = 2;
     bool profile_maps = true;          // pivot k of a batch == k-th enqueued iteration
+    std::function<bool(long long)> sweep_launch;   // profile: k-th launch of the loop proper streams the tableau (empty: every one)
     int start_iter = 0;                // pivots already done on this tableau by another path (resident loop hand-over)
 };
 // graph executables parked for `owner` (the address of a handle's gexec slot): destroyed with the handle, or when its buffers change
@@ -216,6 +227,7 @@ private:
     lpx_pivot_cb cb_ = nullptr; void* user_ = nullptr;
     lpx_stats local_{}; int batch_ = 64; bool graph_ = false;
     int fired_ = 0, iter_before_ = 0, status_ = LPX_RUNNING, init_phase_ = 2;
+    long long batch_first_ = 0;     // loop-proper index of the first launch of the batch in flight (profile mode)
     double t0_ = 0;
 };
 

@@ -1079,14 +1079,15 @@ hipError_t launch_build_node(const double* T0, int ld0, int R0, int C0, double* 
 // Smaller tableaux gain more (tools/probe_fused_mid.py: 1.03-1.42x from 129 x 385 to 308 MB); cache policy: fused_policy below.
 //
 // Nothing is read and written inside one launch: everything a launch reads carries the index `c` of the CURRENT state
-// record (pivot row, factor column, RHS column) or is the source tableau; everything it writes carries 1 - c or is the
-// destination tableau -- the state records included: a launch reads record `par` and writes record 1 - par, and `par` is a
-// launch argument that alternates (graph batches are even, so a replay starts where the capture did).  Which buffer holds
-// T_k is part of the record (pad[3]); pad[2] counts launches, for the host to find the last record written.
-//   record c:  (r, q) = pivot k, selected but NOT yet applied ("pending"; r < 0: none)   qn = entering column of pivot k+1
-//   prow[c] = T_k[r,:] / T_k[r,q]     col[c] = T_k[:,q]     rhs[c] = T_k[:,C-1]
-// P.st is the host's copy of the current record, written by the first update workgroup: one launch behind.
-// A terminal status is found by select(k+1) in the launch that applies pivot k, so the tableau is complete when it shows.
+// record (RHS column) or a ring slot of a pending pivot, or is the source tableau; everything it writes carries 1 - c, its own
+// ring slot, or is the destination tableau -- the state records included: a launch reads record `par` and writes record
+// 1 - par, and `par` (like the ring slot) is a launch argument (graph batches are multiples of 2d, so a replay starts where the
+// capture did).  Which buffer holds the stored tableau is part of the record (pad[3], with the pending count: fp_rec below);
+// pad[2] counts launches, for the host to find the last record written.
+//   record c:  (r, q) = pivot k, the newest selected but not yet applied    qn = entering column of pivot k+1
+//   ring slot of pivot k: T_k[r,:] / T_k[r,q],  T_k[:,q],  r        rhs[c] = T_k[:,C-1]
+// P.st is the host's copy of the current record, written by select's first workgroup: one launch behind.
+// A terminal status can be found with pivots still pending: the host applies them (lpx_pivot_flush) before the run returns.
 // ------------------------------------------------------------------------------------------------
 static constexpr int FP_NT = 256;
 
@@ -1120,135 +1121,109 @@ __global__ __launch_bounds__(SEL_NT) void lpx_fused_init(FusedParams F)
     }
 }
 
-// waves_per_eu(6): 78 VGPRs, no spills (86 without the hint = 5 waves per SIMD: 8.46 k pivots/s against 8.57 k; 64 VGPRs with 7 spills: 8.55 k)
-// NT: nontemporal loads and (mixmod permitting) stores -- the streaming forms; false: default policy throughout, for a pair of
-// buffers that lives in the Infinity Cache together (lpx_pivot_fused_c)
-template <bool NT>
-__device__ __forceinline__ void lpx_pivot_fused_body(const FusedParams& F, int ncw, int nunits, int mixmod)
+// Deferred pivots (LPX_PIVOT_DEFER = d, run_fused).  A sweep moves the whole tableau however many pivots it applies, and
+// select(k+1) needs only column q, the RHS column, row r and the objective row of T_{k+1} -- each of them the stored tableau
+// with the pending pivots applied on the fly.  So launch L of a run (L = 0: the prologue's) is
+//   L % d != 0 or L == 0: select-only (nsel workgroups): pivot L from the stored tableau + the n = L % d pending pivots
+//   otherwise:            sweep: applies pending pivots L-d .. L-1 out of place (oldest first, the very mul-then-sub of d
+//                         single sweeps: every element's value is bit-identical) beside select of pivot L from the source
+// Pivot L's normalised row, factor column and row go to ring slot L % 2d (`lm`, a launch argument): a launch reads the slots of
+// the n <= d pivots before it and writes its own, never one it reads.  d = 1 is the one-pivot-per-sweep kernel of r02 / r03.
+// Record field pad[3] (fp_rec): bit 0 = buffer of the stored tableau, bits 1-5 = pivots pending after the launch, bits 8- =
+// ring slot of the oldest -- the host flushes them (lpx_pivot_flush) when the run is over.
+static constexpr int FP_DMAX = 16;
+// rows per sweep wave: each pending pivot row a lane loads (from L2) serves ROWS rows of the stream; three rows as in r03 while
+// one or two pivots are applied, eight beyond (at three rows the pivot-row reads grew the d = 8 sweep from 118 to 162 us; at
+// eight, 140 us).  Twelve and sixteen rows spill 12-96 VGPRs inside the 80 the select half leaves (waves_per_eu(6) below).
+__host__ __device__ constexpr int fp_rows(int D) { return D <= 2 ? UPDS_ROWS : 8; }
+__host__ __device__ constexpr int fp_rec(int buf, int npend, int slot0) { return buf | (npend << 1) | (slot0 << 8); }
+// ring slot of pending pivot s (0 = oldest) of n before the launch with ring index lm
+__device__ __forceinline__ int fp_slot(int lm, int n, int s, int ring) { const int k = lm - n + s; return k < 0 ? k + ring : k; }
+
+// select(k+1): the first nsel workgroups of a sweep launch, the whole of a select-only launch.  `sweeps`: this launch applies
+// its n pending pivots too (the stored tableau changes buffer).  U: rows in flight per lane in the column pass (the sweep
+// kernels' register budget of waves_per_eu(6) holds U = 4 with two spilled VGPRs, U = 6 spilled 19; the select-only kernel has no such budget).
+template <int U, int SU, int NC = 0>
+__device__ __forceinline__ void fused_select(const FusedParams& F, int n_, bool sweeps)
 {
+    const int n = NC > 0 ? NC : n_;                          // NC: the count known at compile time (d = 1: r03's select)
+    __shared__ double s_fs;
     const SelParams& P = F.P;
-    const int t = threadIdx.x;
-    // Which record is current comes with the LAUNCH (F.par, alternating; run_fused), not from the records: the workgroups of a
-    // launch start over its whole duration, and one that started after workgroup 0 had written the next record must not
-    // take that for the current one.  (A first form compared sequence numbers on the device; it passed every test because
-    // select finishes late and the scalar cache kept serving the old line -- and broke when a second process shared the GPU.)
-    const int c = F.par & 1;
-    const DevState curv = F.rec[c];
-    const DevState* cur = &curv;
+    const int t = threadIdx.x, b = blockIdx.x;
+    const int lm = F.lm, ring = 2 * F.defer;
+    // Which record is current comes with the LAUNCH (lm's parity), not from the records: the workgroups of a launch start over
+    // its whole duration, and one that started after workgroup 0 had written the next record must not take that for the
+    // current one.  (A first form compared sequence numbers on the device; it passed every test because select finishes late
+    // and the scalar cache kept serving the old line -- and broke when a second process shared the GPU.)
+    const int c = lm & 1;
+    const DevState cur = F.rec[c];
     DevState* nxt = F.rec + (c ^ 1);
-    const int status = cur->status;
-    const int pr = cur->r;                                   // pending pivot row (-1: nothing to apply)
-    const int seq = cur->pad[2], buf = cur->pad[3];
+    const int status = cur.status, seq = cur.pad[2], buf = cur.pad[3] & 1;
+    const int nbuf = sweeps ? (buf ^ 1) : buf;               // where the stored tableau lives once this launch is over
     const int nsel = P.nblk;
-    const int R = P.shape ? P.shape[0] : P.R, C = P.shape ? P.shape[1] : P.C;
-    const size_t ld = (size_t)P.ld;
-    const double* __restrict__ src = buf ? F.T1 : P.T;
-    double* __restrict__ dst = buf ? P.T : F.T1;
-    const double* __restrict__ prowc = c ? F.prow1 : P.prow;
-    const double* __restrict__ facc = c ? P.col1 : P.col0;
-
-    if ((int)blockIdx.x >= nsel) {
-        // ---------------- update(k): T_{k+1} = T_k - fac (x) prow, row r replaced by the normalised pivot row ----------------
-        if ((int)blockIdx.x == nsel && t == 0) *P.st = *cur;
-        if (status != LPX_RUNNING || pr < 0) return;
-        const int lane = t & 63;
-        const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-        const int unit = ((int)blockIdx.x - nsel) * (FP_NT / 64) + wave;
-        if (unit >= nunits) return;
-        const int cw = unit % ncw, rb = unit / ncw;
-        const int col = cw * 128 + lane * 2;
-        if (col >= P.ld) return;
-        const int row0 = rb * UPDS_ROWS;
-        if (row0 >= R) return;
-        const double2 p = *reinterpret_cast<const double2*>(prowc + col);
-        const double* sb = src + (size_t)row0 * ld + col;
-        double* db = dst + (size_t)row0 * ld + col;
-        if (row0 + UPDS_ROWS <= R && (pr < row0 || pr >= row0 + UPDS_ROWS)) {
-            double2 v[UPDS_ROWS];
-            double f[UPDS_ROWS];
-#pragma unroll
-            for (int k = 0; k < UPDS_ROWS; ++k) v[k] = upd_load<NT>(sb + (size_t)k * ld);
-#pragma unroll
-            for (int k = 0; k < UPDS_ROWS; ++k) f[k] = facc[row0 + k];
-#pragma unroll
-            for (int k = 0; k < UPDS_ROWS; ++k) {
-                v[k].x = v[k].x - f[k] * p.x;       // mul, then sub: contraction is off
-                v[k].y = v[k].y - f[k] * p.y;
-            }
-            // store policies as in lpx_update_mb_m / _s (two spelled-out sequences, checked in the ISA)
-            if (NT && mixmod > 0 && (mixmod == 1 || rb % mixmod == 0)) {
-#pragma unroll
-                for (int k = 0; k < UPDS_ROWS - 1; ++k) upd_store<true>(db + (size_t)k * ld, v[k]);
-                upd_store<false>(db + (size_t)(UPDS_ROWS - 1) * ld, v[UPDS_ROWS - 1]);
-            } else {
-#pragma unroll
-                for (int k = 0; k < UPDS_ROWS; ++k) upd_store<NT>(db + (size_t)k * ld, v[k]);
-            }
-            return;
-        }
-#pragma unroll 1
-        for (int k = 0; k < UPDS_ROWS; ++k) {
-            const int i = row0 + k;
-            if (i >= R) break;
-            double2 o = p;                                   // row r: the normalised pivot row
-            if (i != pr) {
-                const double2 v = upd_load<NT>(sb + (size_t)k * ld);
-                const double f = facc[i];
-                o.x = v.x - f * p.x;
-                o.y = v.y - f * p.y;
-            }
-            upd_store<NT>(db + (size_t)k * ld, o);
-        }
-        return;
-    }
-
-    // ---------------- select(k+1) on T_{k+1}, read as T_k with pivot k's correction ----------------
-    const int b = blockIdx.x;
-    const int nbuf = pr >= 0 ? (buf ^ 1) : buf;              // where T_{k+1} lives once this launch is over
+    if (b == 0 && t == 0) *P.st = cur;                        // the host's copy: one launch behind
     if (status != LPX_RUNNING) {
-        if (b == 0 && t == 0) { DevState x = *cur; x.pad[2] = seq + 1; *nxt = x; }
+        if (b == 0 && t == 0) { DevState x = cur; x.pad[2] = seq + 1; *nxt = x; }
         return;
     }
-    double* __restrict__ prown = c ? P.prow : F.prow1;
-    double* __restrict__ facn = c ? P.col0 : P.col1;
+    const int R = P.shape ? P.shape[0] : P.R, C = P.shape ? P.shape[1] : P.C;
+    const size_t ld = (size_t)P.ld, fld = (size_t)P.R;
+    const double* __restrict__ src = buf ? F.T1 : P.T;
+    double* __restrict__ prown = F.pring + (size_t)lm * ld;
+    double* __restrict__ facn = F.fring + (size_t)lm * fld;
     const double* __restrict__ rhsc = c ? F.rhs1 : P.rhsbuf;
     double* __restrict__ rhsn = c ? P.rhsbuf : F.rhs1;
     const int m = R - 1;
-    const int iter = cur->iter, primal_count = cur->primal_count;
-    const int q = cur->qn;
+    const int iter = cur.iter, primal_count = cur.primal_count;
+    const int q = cur.qn;
     int final_status = LPX_RUNNING, r = -1;
     // loop head, Models/PrimalSimplex.cs:95-106
     if (primal_count >= P.max_iter) final_status = LPX_ITER_LIMIT;
     else if (q < 0) final_status = LPX_OPTIMAL;
-    double pq = 0.0, prhs = 0.0, fs = 0.0;
+    double fs = 0.0;
     if (final_status == LPX_RUNNING) {
-        if (pr >= 0) { pq = prowc[q]; prhs = prowc[C - 1]; }
-        // T_{k+1}[i,q] and T_{k+1}[i,C-1] as the update stores them (mul, then sub; row r: the normalised pivot row)
-        auto den_of = [&](int i, double v, double f) { const double u = v - f * pq; return pr < 0 ? v : (i == pr ? pq : u); };
-        auto num_of = [&](int i, double h, double f) { const double u = h - f * prhs; return pr < 0 ? h : (i == pr ? prhs : u); };
+        // T_{k+1}[i,q] and T_{k+1}[i,C-1] as the sweep stores them: the column through every pending pivot (row r_s: the
+        // normalised pivot row), the RHS column kept current in rhsc up to the newest pending pivot, which is applied here.
+        // The pending pivots' scalars are uniform loads beside the column's (staging them in LDS behind a barrier cost the
+        // 25 MB tableau's loop 14 %: two more round trips per pivot)
+        const int sn = fp_slot(lm, n, n - 1, ring);
+        const int rl = n ? cur.r : -1;                       // the newest pending pivot is the record's
+        const double prhs = n ? F.pring[(size_t)sn * ld + (C - 1)] : 0.0;
         double* rat = P.ws + (size_t)b * (size_t)(P.R > P.C ? P.R : P.C);
-        constexpr int U = 6;                                 // rows in flight per lane: three batches of loads at m = 4096
         for (int i0 = 0; i0 < R; i0 += U * FP_NT) {
-            double v[U], f[U], h[U];
+            double v[U], h[U], fl[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int i = min(R - 1, i0 + u * FP_NT + t);    // clamped, not guarded: a guarded load waits for its own branch
-                v[u] = src[(size_t)i * ld + q]; f[u] = facc[i]; h[u] = rhsc[i];
+                v[u] = src[(size_t)i * ld + q]; h[u] = rhsc[i];
+            }
+            // oldest first; the newest pivot's factors are kept for the RHS correction
+#pragma unroll SU
+            for (int s = 0; s < n; ++s) {
+                const int sl = fp_slot(lm, n, s, ring);
+                const double* __restrict__ fac = F.fring + (size_t)sl * fld;
+                const double pq = F.pring[(size_t)sl * ld + q];
+                const int rs = s == n - 1 ? rl : F.rring[sl];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int i = min(R - 1, i0 + u * FP_NT + t);
+                    fl[u] = fac[i];
+                    const double nv = v[u] - fl[u] * pq;     // mul, then sub: contraction is off
+                    v[u] = i == rs ? pq : nv;
+                }
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int i = i0 + u * FP_NT + t;
                 if (i < R) {
-                    const double dn = den_of(i, v[u], f[u]), nm = num_of(i, h[u], f[u]);
+                    const double dn = v[u];
+                    const double nm = n == 0 ? h[u] : (i == rl ? prhs : h[u] - fl[u] * prhs);
                     rat[i] = dn > P.eps ? nm / dn : __builtin_inf();     // ChooseLeaving's ratio, :229-241
                     if (b == 0) { facn[i] = dn; rhsn[i] = nm; }          // factors of pivot k+1, numerators of the test after it
-                    if (i == m) fs = dn;                                 // T_{k+1}[m,q]
+                    if (i == m) s_fs = dn;                               // T_{k+1}[m,q]: row m belongs to exactly one lane
                 }
             }
         }
-        // every lane needs fs: row m belongs to exactly one lane of the last batch
-        __shared__ double s_fs;
-        if (((m % (U * FP_NT)) % FP_NT) == t) s_fs = fs;
         __syncthreads();                                     // the slice of ratios is complete (and visible: same CU)
         fs = s_fs;
         r = block_hysteresis_segments<FP_NT / 64>(m, P.tol_primal, CompactRatio{rat});
@@ -1256,8 +1231,9 @@ __device__ __forceinline__ void lpx_pivot_fused_body(const FusedParams& F, int n
     }
     if (final_status != LPX_RUNNING) {
         if (b == 0 && t == 0) {
-            DevState x = *cur;
-            x.status = final_status; x.r = -1; x.q = -1; x.qn = -1; x.pad[2] = seq + 1; x.pad[3] = nbuf;
+            DevState x = cur;
+            x.status = final_status; x.r = -1; x.q = -1; x.qn = -1; x.pad[2] = seq + 1;
+            x.pad[3] = fp_rec(nbuf, sweeps ? 0 : n, fp_slot(lm, n, 0, ring));
             *nxt = x;
         }
         return;
@@ -1266,20 +1242,32 @@ __device__ __forceinline__ void lpx_pivot_fused_body(const FusedParams& F, int n
     ScanRule rule; rule.forced = 0; rule.eps = P.eps; rule.thresh = P.fthresh; rule.C = C; rule.c0 = 0;
     const int per = (C + nsel - 1) / nsel;
     const int j0 = b * per, j1 = min(C, j0 + per);
-    const double fr = facc[r], fm = facc[m];
     const double* trow = src + (size_t)r * ld;
     const double* orow = src + (size_t)m * ld;
-    const double pv = trow[q];
-    const double piv = pr < 0 ? pv : (r == pr ? pq : pv - fr * pq);      // T_{k+1}[r,q]
+    auto pslot = [&](int s) { return fp_slot(lm, n, s, ring); };
+    auto prs = [&](int s) { return s == n - 1 ? cur.r : F.rring[pslot(s)]; };     // the newest: the record's
+    auto pfr = [&](int s) { return F.fring[(size_t)pslot(s) * fld + r]; };
+    auto pfm = [&](int s) { return F.fring[(size_t)pslot(s) * fld + m]; };
+    double piv = trow[q];                                    // T_{k+1}[r,q], the column's own chain
+    for (int s = 0; s < n; ++s) {
+        const double pq = F.pring[(size_t)pslot(s) * ld + q];
+        const double nv = piv - pfr(s) * pq;
+        piv = r == prs(s) ? pq : nv;
+    }
     MinIdx best; rule_init(rule, best);
 #pragma unroll 2
     for (int j = j0 + t; j < j1; j += FP_NT) {
-        const double pc = prowc[j], tv = trow[j], ov = orow[j];
-        const double tu = tv - fr * pc, ou = ov - fm * pc;
-        const double tr = pr < 0 ? tv : (r == pr ? pc : tu);     // T_{k+1}[r,j]
+        double tr = trow[j], ov = orow[j];                   // -> T_{k+1}[r,j], T_{k+1}[m,j] (m is never a pivot row)
+#pragma unroll SU
+        for (int s = 0; s < n; ++s) {
+            const double pc = F.pring[(size_t)pslot(s) * ld + j];
+            const double nt = tr - pfr(s) * pc;
+            tr = r == prs(s) ? pc : nt;
+            ov = ov - pfm(s) * pc;
+        }
         const double p = tr / piv;                               // true division, :250
         prown[j] = p;
-        const double u = (pr < 0 ? ov : ou) - fs * p;            // what update(k+1) will store at T[m,j]
+        const double u = ov - fs * p;                            // what the sweep of pivot k+1 will store at T[m,j]
         rule_feed(rule, best, j, u);
     }
     best = wave_min_idx(best);
@@ -1318,17 +1306,141 @@ __device__ __forceinline__ void lpx_pivot_fused_body(const FusedParams& F, int n
     if (b == 0 && t == 0) {
         P.basis[r] = q;                                          // basis[leaving] = entering, :110
         if (iter < P.trace_cap) { P.trace[2 * iter] = r; P.trace[2 * iter + 1] = q; }
+        F.rring[lm] = r;
         nxt->status = LPX_RUNNING; nxt->iter = iter + 1; nxt->r = r; nxt->q = q;
-        nxt->phase = cur->phase; nxt->fdf_count = cur->fdf_count; nxt->dual_iter = cur->dual_iter;
-        nxt->primal_count = primal_count + 1; nxt->forced_k = cur->forced_k; nxt->c0n = 0; nxt->qn_valid = 0;
-        nxt->pad[0] = cur->pad[0]; nxt->pad[1] = cur->pad[1]; nxt->pad[2] = seq + 1; nxt->pad[3] = nbuf;
+        nxt->phase = cur.phase; nxt->fdf_count = cur.fdf_count; nxt->dual_iter = cur.dual_iter;
+        nxt->primal_count = primal_count + 1; nxt->forced_k = cur.forced_k; nxt->c0n = 0; nxt->qn_valid = 0;
+        nxt->pad[0] = cur.pad[0]; nxt->pad[1] = cur.pad[1]; nxt->pad[2] = seq + 1;
+        nxt->pad[3] = sweeps ? fp_rec(nbuf, 1, lm) : fp_rec(nbuf, n + 1, fp_slot(lm, n, 0, ring));
     }
 }
 
+// The sweep: T_{k+1} = T_{k+1-D} with pending pivots k+1-D .. k applied, out of place, oldest first.  Each lane keeps the
+// D pivot-row pairs of its two columns in VGPRs; the factors of a wave's three rows are scalar loads.
+// NT: nontemporal loads and (mixmod permitting) stores -- the streaming forms; false: default policy throughout, for a pair of
+// buffers that lives in the Infinity Cache together (lpx_pivot_fused_c)
+template <bool NT, int D, int ROWS = fp_rows(D)>
+__device__ __forceinline__ void fused_sweep(const FusedParams& F, int ncw, int nunits, int mixmod)
+{
+    const SelParams& P = F.P;
+    const int t = threadIdx.x;
+    const int lm = F.lm;
+    constexpr int ring = 2 * D;
+    const DevState& cur = F.rec[lm & 1];
+    const int status = cur.status, buf = cur.pad[3] & 1, rnew = cur.r;     // rnew: the newest pending pivot's row
+    const int nsel = P.nblk;
+    const int R = P.shape ? P.shape[0] : P.R;
+    const size_t ld = (size_t)P.ld, fld = (size_t)P.R;
+    const double* __restrict__ src = buf ? F.T1 : P.T;
+    double* __restrict__ dst = buf ? P.T : F.T1;
+    const int lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int unit = ((int)blockIdx.x - nsel) * (FP_NT / 64) + wave;
+    if (unit >= nunits) return;
+    const int cw = unit % ncw, rb = unit / ncw;
+    const int col = cw * 128 + lane * 2;
+    if (col >= P.ld) return;
+    const int row0 = rb * ROWS;
+    if (row0 >= R) return;
+    bool hit = false;                                        // a pending pivot row in this wave's rows: the row-wise path
+#pragma unroll
+    for (int s = 0; s < D; ++s) hit |= (unsigned)((s == D - 1 ? rnew : F.rring[fp_slot(lm, D, s, ring)]) - row0) < (unsigned)ROWS;
+    if (status != LPX_RUNNING) return;                       // a run that is over leaves its pending pivots to lpx_pivot_flush
+    const double* sb = src + (size_t)row0 * ld + col;
+    double* db = dst + (size_t)row0 * ld + col;
+    if (row0 + ROWS <= R && !hit) {
+        double2 v[ROWS];
+#pragma unroll
+        for (int k = 0; k < ROWS; ++k) v[k] = upd_load<NT>(sb + (size_t)k * ld);
+#pragma unroll
+        for (int s = 0; s < D; ++s) {
+            const int sl = fp_slot(lm, D, s, ring);
+            const double2 p = *reinterpret_cast<const double2*>(F.pring + (size_t)sl * ld + col);
+            const double* fac = F.fring + (size_t)sl * fld + row0;
+#pragma unroll
+            for (int k = 0; k < ROWS; ++k) {
+                const double f = fac[k];
+                v[k].x = v[k].x - f * p.x;          // mul, then sub: contraction is off
+                v[k].y = v[k].y - f * p.y;
+            }
+        }
+        // store policies as in lpx_update_mb_m / _s (two spelled-out sequences, checked in the ISA)
+        if (NT && mixmod > 0 && (mixmod == 1 || rb % mixmod == 0)) {
+#pragma unroll
+            for (int k = 0; k < ROWS - 1; ++k) upd_store<true>(db + (size_t)k * ld, v[k]);
+            upd_store<false>(db + (size_t)(ROWS - 1) * ld, v[ROWS - 1]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < ROWS; ++k) upd_store<NT>(db + (size_t)k * ld, v[k]);
+        }
+        return;
+    }
+#pragma unroll 1
+    for (int k = 0; k < ROWS; ++k) {
+        const int i = row0 + k;
+        if (i >= R) break;
+        double2 o = upd_load<NT>(sb + (size_t)k * ld);
+#pragma unroll 1
+        for (int s = 0; s < D; ++s) {
+            const int sl = fp_slot(lm, D, s, ring);
+            const double2 p = *reinterpret_cast<const double2*>(F.pring + (size_t)sl * ld + col);
+            const double f = F.fring[(size_t)sl * fld + i];
+            double2 u;
+            u.x = o.x - f * p.x;
+            u.y = o.y - f * p.y;
+            o = i == F.rring[sl] ? p : u;                    // row r_s: the normalised pivot row
+        }
+        upd_store<NT>(db + (size_t)k * ld, o);
+    }
+}
+
+// waves_per_eu(6): 80 VGPRs.  The sweep half alone needs 28 (D = 1) to 64 (D = 16); the select half sets the budget and spills
+// (code-object metadata): 2 VGPRs in every streaming form but D = 10 (14) and D = 15 (6), 2-4 in _c<1..8>, 8-14 in _c<9..16>
+// -- the defaults run lpx_pivot_fused<12> (2) at 403 MB and lpx_pivot_fused_c<4> (2) at 25 MB; _c<12> (14) serves 64-152 MB.
+// Without the hint the r03 kernel took 86 VGPRs = 5 waves per SIMD (8.46 k pivots/s against 8.57 k at 6).
+template <int D>
 __global__ __launch_bounds__(FP_NT) __attribute__((amdgpu_waves_per_eu(6))) void lpx_pivot_fused(FusedParams F, int ncw, int nunits, int mixmod)
-{ lpx_pivot_fused_body<true>(F, ncw, nunits, mixmod); }
+{
+    if ((int)blockIdx.x < F.P.nblk) {
+        if (D == 1) fused_select<4, 1, 1>(F, 1, true);
+        else fused_select<4, 1>(F, F.defer, true);           // == D; a run-time count keeps its loops rolled
+    } else fused_sweep<true, D>(F, ncw, nunits, mixmod);
+}
+template <int D>
 __global__ __launch_bounds__(FP_NT) __attribute__((amdgpu_waves_per_eu(6))) void lpx_pivot_fused_c(FusedParams F, int ncw, int nunits, int mixmod)
-{ lpx_pivot_fused_body<false>(F, ncw, nunits, mixmod); }
+{
+    if ((int)blockIdx.x < F.P.nblk) {
+        if (D == 1) fused_select<4, 1, 1>(F, 1, true);
+        else fused_select<4, 1>(F, F.defer, true);
+    } else fused_sweep<false, D>(F, ncw, nunits, mixmod);
+}
+// select-only launch: the L % d pending pivots stay where they are
+__global__ __launch_bounds__(FP_NT) void lpx_pivot_select(FusedParams F)
+{
+    fused_select<6, 4>(F, F.lm % F.defer, false);
+}
+
+// End of a run: the n pivots still pending (record: buffer, count, oldest slot) applied to the stored tableau, written to
+// buffer 0 (in place when it is already there: every element is read and written by one lane).
+__global__ __launch_bounds__(256) void lpx_pivot_flush(FusedParams F, int buf, int n, int slot0)
+{
+    const SelParams& P = F.P;
+    const int R = P.shape ? P.shape[0] : P.R;
+    const int i = blockIdx.y;
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (i >= R || j >= P.ld) return;
+    const size_t ld = (size_t)P.ld, fld = (size_t)P.R;
+    const int ring = 2 * F.defer;
+    const double* src = buf ? F.T1 : P.T;
+    double v = src[(size_t)i * ld + j];
+    for (int s = 0; s < n; ++s) {
+        const int sl = slot0 + s < ring ? slot0 + s : slot0 + s - ring;
+        const double pc = F.pring[(size_t)sl * ld + j];
+        const double nv = v - F.fring[(size_t)sl * fld + i] * pc;
+        v = i == F.rring[sl] ? pc : nv;
+    }
+    P.T[(size_t)i * ld + j] = v;
+}
 
 // ------------------------------------------------------------------------------------------------
 // Fused GROUP step (K4g): the dual path's three-phase state machine (ForceDualFeasibility Models/DualSimplex.cs:195-228, dual
@@ -1917,19 +2029,53 @@ hipError_t launch_fused_init(const FusedParams& f, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t launch_pivot_fused(const FusedParams& f0, int par, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+using FusedKernel = void (*)(FusedParams, int, int, int);
+template <int... Ds> struct FusedTable {
+    static constexpr FusedKernel nt[] = { lpx_pivot_fused<Ds>... };
+    static constexpr FusedKernel c[] = { lpx_pivot_fused_c<Ds>... };
+};
+using FusedKernels = FusedTable<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>;
+static_assert(sizeof(FusedKernels::nt) / sizeof(FusedKernel) == FP_DMAX, "one sweep kernel per depth");
+
+int pivot_defer_max() { return FP_DMAX; }
+
+hipError_t launch_pivot_fused(const FusedParams& f0, long long L, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
 {
-    FusedParams f = f0; f.par = par & 1;
+    FusedParams f = f0;
+    const int d = f.defer;
+    if (d < 1 || d > FP_DMAX) return hipErrorInvalidValue;
+    f.lm = (int)(L % (2 * d)); f.par = f.lm & 1;
+    const bool sweep = L > 0 && L % d == 0;
     const int ld = f.P.ld, R = f.P.R;
-    const int ncw = (ld + 127) / 128, nunits = ncw * ((R + UPDS_ROWS - 1) / UPDS_ROWS);
+    if (!sweep) {
+        if (e0 && e1)
+            hipExtLaunchKernelGGL(lpx_pivot_select, dim3(f.P.nblk), dim3(FP_NT), 0, s, e0, e1, 0, f);
+        else
+            hipLaunchKernelGGL(lpx_pivot_select, dim3(f.P.nblk), dim3(FP_NT), 0, s, f);
+        return hipGetLastError();
+    }
+    const int rows = fp_rows(d);
+    const int ncw = (ld + 127) / 128, nunits = ncw * ((R + rows - 1) / rows);
     const int nblocks = f.P.nblk + (nunits + (FP_NT / 64) - 1) / (FP_NT / 64);
     const int pol = fused_policy(ld, R);
-    const int mixmod = pol == 2 ? update_mixmod(ld, R) : 0;      // 0: every store nontemporal
-    auto kern = pol == 0 ? lpx_pivot_fused_c : lpx_pivot_fused;  // both buffers at home in the Infinity Cache: default policy
+    int mixmod = pol == 2 ? update_mixmod(ld, R) : 0;            // 0: every store nontemporal
+    // the stored-through row is the last of every mixmod-th block: at `rows` per block the block period shrinks in proportion so
+    // that about the same share of BLOCKS keeps a row in the cache.  mixmod = 1 (the 403 MB headline) stays 1: one row in eight
+    // instead of one in three goes through the cache at eight rows per block -- the sweep's PMC traffic stays 1.029x of
+    // 16 R C; the other share was not measured
+    if (mixmod > 1) mixmod = std::max(1, mixmod * UPDS_ROWS / rows);
+    const FusedKernel kern = pol == 0 ? FusedKernels::c[d - 1] : FusedKernels::nt[d - 1];   // both buffers in the Infinity Cache: default policy
     if (e0 && e1)
         hipExtLaunchKernelGGL(kern, dim3(nblocks), dim3(FP_NT), 0, s, e0, e1, 0, f, ncw, nunits, mixmod);
     else
         hipLaunchKernelGGL(kern, dim3(nblocks), dim3(FP_NT), 0, s, f, ncw, nunits, mixmod);
+    return hipGetLastError();
+}
+
+hipError_t launch_pivot_flush(const FusedParams& f, int buf, int n, int slot0, hipStream_t s)
+{
+    const int R = f.P.R, ld = f.P.ld;
+    hipLaunchKernelGGL(lpx_pivot_flush, dim3((ld + 255) / 256, R), dim3(256), 0, s, f, buf, n, slot0);
     return hipGetLastError();
 }
 

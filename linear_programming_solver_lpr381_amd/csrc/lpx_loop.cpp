@@ -169,6 +169,7 @@ int LoopRun::begin(const LoopCtx& c, const DevState& init, const lpx_run_opts* o
 int LoopRun::submit()
 {
     iter_before_ = fired_;
+    batch_first_ = enq_;
     if (graph_) {
         LPX_HIP_TRY(hipGraphLaunch(*c_.gexec, c_.stream));
     } else {
@@ -203,9 +204,10 @@ int LoopRun::complete()
     status_ = c_.hst->status;
     const int done = c_.hst->iter;
     if (o_.profile && c_.profile_maps) {
-        // the first (done - iter_before) iterations of this batch each ran one full update
+        // the first (done - iter_before) iterations of this batch each ran one full update (deferred pivots: the sweeps among them)
         const int full = done - iter_before_;
         for (int i = 0; i < full && i < batch_; ++i) {
+            if (c_.sweep_launch && !c_.sweep_launch(batch_first_ + i)) continue;
             float ms = 0.f;
             LPX_HIP_TRY(hipEventElapsedTime(&ms, (*c_.events)[2 * i], (*c_.events)[2 * i + 1]));
             local_.update_ms_sum += ms;

@@ -56,6 +56,7 @@ struct lpx_tableau {
     // fused pivot (lpx_pivot_fused): second tableau buffer and the index-1 copies of the small per-pivot vectors, on first use
     double* fT = nullptr; char* fslab = nullptr;
     double* fprow = nullptr; double* frhs = nullptr; DevState* frec = nullptr;
+    char* dring = nullptr; int dring_slots = 0;   // deferred pivots of run_fused: ring of pivot rows, factor columns, row indices
     bool fused_off = false;         // the second buffer did not fit: stay on the two-launch path
     bool suspended2 = false;        // ... by the two-launch group kernels (it must continue there: no pending pivot, state in *hst)
     bool fsuspended = false; int frec_cur = 0;   // fused group run left unfinished: its records (latest: index frec_cur) are in place
@@ -192,7 +193,7 @@ void lpx_tableau_destroy(lpx_tableau* t)
     for (hipEvent_t e : t->events) hipEventDestroy(e);
     hipFree(t->T); hipFree(t->slab); hipFree(t->snapT); hipFree(t->snapBasis);
     hipFree(t->frows); hipFree(t->fcols); hipFree(t->fchosen); hipFree(t->cutbuf);
-    hipFree(t->fT); hipFree(t->fslab);
+    hipFree(t->fT); hipFree(t->fslab); hipFree(t->dring);
     hipFree(t->xr); hipFree(t->xp); hipFree(t->xgen); hipFree(t->xbasis); hipFree(t->xT); hipFree(t->xc); hipFree(t->xq);
     if (t->hslab) hipHostFree(t->hslab);
     if (t->cutbuf_h) hipHostFree(t->cutbuf_h);
@@ -408,36 +409,76 @@ static bool fused_buffers(lpx_tableau* t)
     return true;
 }
 
-// Primal loop with ONE launch per pivot (lpx_pivot_fused): update(k) out of place beside select(k+1).  The state record the
-// host polls is one launch behind the device's, so the loop gets a few iterations of slack; when it ends the tableau may sit
-// in the second buffer and is brought home (a device-to-device copy of the live rows, ~0.1 ms per 400 MB, once per solve).
+// measured on MI355X: 4097 x 12289 (403 MB) 118.9 us per pivot at d = 1, 34.9 at 12, 35.2 at 16 (the sweep 150
+// against 164 us); 1025 x 3073 (25 MB) 66 k pivots/s at d = 1, 79 k at 2, 82 k at 4, 80 k at 8
+static constexpr int PIVOT_DEFER_LARGE = 12, PIVOT_DEFER_SMALL = 4;
+static constexpr size_t PIVOT_DEFER_LARGE_BYTES = (size_t)64 << 20;
+// Pivots per sweep of run_fused (LPX_PIVOT_DEFER=d, read once; DESIGN.md 4.1 has the measured table behind the default).
+static int pivot_defer(int ld, int R)
+{
+    static const int forced = [] { const char* e = std::getenv("LPX_PIVOT_DEFER"); return e ? std::atoi(e) : 0; }();
+    if (forced > 0) return std::min(forced, pivot_defer_max());
+    const size_t bytes = sizeof(double) * (size_t)ld * (size_t)R;
+    return bytes > PIVOT_DEFER_LARGE_BYTES ? PIVOT_DEFER_LARGE : PIVOT_DEFER_SMALL;
+}
+
+// Ring of the pending pivots (2 * d slots), on first use.
+static int defer_ring(lpx_tableau* t, int d)
+{
+    if (t->dring_slots >= 2 * d) return 0;
+    hipFree(t->dring); t->dring = nullptr; t->dring_slots = 0;
+    const size_t slots = 2 * (size_t)d;
+    const size_t bytes = slots * sizeof(double) * ((size_t)t->ld + (size_t)t->Rcap) + slots * sizeof(int32_t);
+    LPX_HIP_TRY(malloc_retry((void**)&t->dring, bytes));
+    LPX_HIP_TRY(hipMemsetAsync(t->dring, 0, bytes, t->stream));
+    t->dring_slots = (int)slots;
+    return 0;
+}
+
+// Primal loop with ONE launch per pivot: launch L selects pivot L; every d-th one (a positive multiple of d) is also the
+// sweep that applies the d pivots selected before it, out of place (lpx_pivot_fused<d>), the others select only
+// (lpx_pivot_select).  The state record the host polls is one launch behind the device's, so the loop gets a few iterations
+// of slack; when it ends, the pivots still pending are applied (lpx_pivot_flush, into buffer 0), or the tableau, when none
+// are, may sit in the second buffer and is brought home (a device-to-device copy of the live rows, ~0.1 ms per 400 MB).
 static int run_fused(lpx_tableau* t, const SelParams& p, const lpx_run_opts* o, lpx_stats* stats, int start_iter)
 {
+    const int d = pivot_defer(t->ld, t->Rcap);
+    { int rc = defer_ring(t, d); if (rc) return rc; }
     FusedParams f; std::memset(&f, 0, sizeof(f));
     f.P = p; f.T1 = t->fT; f.prow1 = t->fprow; f.rhs1 = t->frhs; f.rec = t->frec;
+    f.pring = (double*)t->dring;
+    f.fring = f.pring + (size_t)t->dring_slots * t->ld;
+    f.rring = (int32_t*)(f.fring + (size_t)t->dring_slots * t->Rcap);
+    f.defer = d;
     LoopCtx c; DevState init;
     make_ctx(t, p, c, init);
     c.key.assign(reinterpret_cast<const char*>(&f), sizeof(f));
-    // A launch reads state record `par` and writes the other one; par alternates from launch to launch.  The prologue's launch is
-    // number 0, so the loop proper starts at 1 -- in the captured graph too (it is captured before the prologue runs, hence the
-    // counter is preset), and a graph batch is made even so that every replay starts at the parity the capture started at.
+    // A launch reads state record L % 2 and writes the other one, and ring slot L % 2d is its own.  The prologue's launch is
+    // number 0, so the loop proper starts at 1 -- in the captured graph too (it is captured before the prologue runs, hence
+    // the counter is preset), and a graph batch is a multiple of 2d so that every replay starts where the capture did.
     auto count = std::make_shared<long long>(1);
     c.enqueue_iter = [f, count](hipStream_t s, hipEvent_t e0, hipEvent_t e1) -> int {
-        LPX_HIP_TRY(launch_pivot_fused(f, (int)(*count & 1), s, e0, e1)); ++*count; return 0; };
-    // the prologue also selects the first pivot, so that every launch of the loop proper has a pivot to apply
+        LPX_HIP_TRY(launch_pivot_fused(f, *count, s, e0, e1)); ++*count; return 0; };
+    // the prologue also selects the first pivot, so that every launch of the loop proper has a pivot before it
     c.prologue = [f, count](hipStream_t s) -> int {
         LPX_HIP_TRY(launch_fused_init(f, s)); LPX_HIP_TRY(launch_pivot_fused(f, 0, s)); *count = 1; return 0; };
     c.launches_per_iter = 1;
+    c.sweep_launch = [d](long long k) { return (k + 1) % d == 0; };      // k-th launch of the loop proper is launch k + 1
     c.start_iter = start_iter;
     lpx_run_opts oe = *o;
-    { const int b = oe.batch > 0 ? oe.batch : 64; oe.batch = (b + 1) & ~1; }
+    { const int b = oe.batch > 0 ? oe.batch : 64; oe.batch = (b + 2 * d - 1) / (2 * d) * (2 * d); }
     o = &oe;
     const int rc = run_device_loop(c, init, o, (long long)o->max_iter + 4, nullptr, nullptr, stats);
     LPX_HIP_TRY(hipStreamSynchronize(t->stream));
     DevState recs[2];
     LPX_HIP_TRY(hipMemcpy(recs, t->frec, sizeof(recs), hipMemcpyDeviceToHost));
     const DevState& last = recs[1].pad[2] > recs[0].pad[2] ? recs[1] : recs[0];
-    if (last.pad[3] == 1) {
+    const int buf = last.pad[3] & 1, npend = (last.pad[3] >> 1) & 31, slot0 = last.pad[3] >> 8;
+    if (npend > 0) {
+        LPX_HIP_TRY(launch_pivot_flush(f, buf, npend, slot0, t->stream));
+        LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+        if (stats) stats->launches += 1;
+    } else if (buf == 1) {
         LPX_HIP_TRY(hipMemcpyAsync(t->T, t->fT, sizeof(double) * (size_t)t->R * t->ld, hipMemcpyDeviceToDevice, t->stream));
         LPX_HIP_TRY(hipStreamSynchronize(t->stream));
     }
