@@ -238,9 +238,9 @@ int lpx_tableau_snapshot(lpx_tableau* t)
 {
     if (!t) return LPX_EINVAL;
     const size_t tb = sizeof(double) * (size_t)t->R * t->ld;
-    if (!t->snapT) {
-        LPX_HIP_TRY(hipMalloc((void**)&t->snapT, tb));
-        LPX_HIP_TRY(hipMalloc((void**)&t->snapBasis, sizeof(int32_t) * (t->R > 1 ? t->R - 1 : 1)));
+    if (!t->snapT) {            // sized for the capacity: a later set_shape may grow the live rows
+        LPX_HIP_TRY(hipMalloc((void**)&t->snapT, sizeof(double) * (size_t)t->Rcap * t->ld));
+        LPX_HIP_TRY(hipMalloc((void**)&t->snapBasis, sizeof(int32_t) * (t->Rcap > 1 ? t->Rcap - 1 : 1)));
     }
     LPX_HIP_TRY(hipMemcpyAsync(t->snapT, t->T, tb, hipMemcpyDeviceToDevice, t->stream));
     LPX_HIP_TRY(hipMemcpyAsync(t->snapBasis, t->basis, sizeof(int32_t) * (t->R > 1 ? t->R - 1 : 1),

@@ -4,7 +4,10 @@ applied on the fly.  Each element goes through the same multiplies and subtracti
 pivot, so the tableau is bit-identical to the oracle's for every d -- including runs that end with fewer than d pivots pending
 (the cap not a multiple of d, optimal, unbounded), which the host flushes before anything reads the tableau.
 
-The knob is read once per process, hence one child process per setting."""
+The knob is read once per process, hence one child process per setting.  These are spot checks on the bench LP and on small
+LPs; tests/test_gpu_deferred_matrix.py pins every depth 1 .. 16 in both sweep forms, every flush length and ring half, chained
+runs without restore(), graph replay against eager launches, handle reuse through set_shape, long degenerate columns and
+profile runs to the oracle."""
 import hashlib
 import json
 import os
@@ -118,7 +121,7 @@ def small_ref(oracle):
 
 
 @pytest.mark.parametrize("policy", ["0", "2"], ids=["cached", "streaming-mix"])
-@pytest.mark.parametrize("d", [2, 5, 16])
+@pytest.mark.parametrize("d", [1, 2, 4, 5, 12, 16])
 def test_small_lps_to_the_end_vs_oracle(small_ref, d, policy):
     """Small LPs run to their end (optimal, unbounded, the cap at the optimum's pivot count and one before it) on the streaming
     kernels (resident kernels off), both cache-policy forms of the sweep: status, trace, basis and tableau bits as the oracle's."""
