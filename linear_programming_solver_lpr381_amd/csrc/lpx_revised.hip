@@ -116,11 +116,6 @@ __global__ __launch_bounds__(RV_NT) void rv_price_pick(RvParams P)
     DevState* st = P.st;
     if (st->status != LPX_RUNNING) return;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (st->iter >= st->dual_iter) {                    // :66 / :144 -- the cap travels in the state record (DevState::dual_iter is
-                                                        //   unused by this path), so the captured graph serves every segment of a run
-        if (t == 0) { st->status = LPX_ITER_LIMIT; st->r = -1; }
-        return;
-    }
     const double* pi = P.W + (size_t)P.m * P.ldw;
     Cand best; best.v = -P.eps; best.key = INT_MAX; best.col = -1;
     for (int j = t; j < P.n; j += RV_NT) {
@@ -132,6 +127,13 @@ __global__ __launch_bounds__(RV_NT) void rv_price_pick(RvParams P)
         const double rs = k >= 0 ? 0.0 - pi[s] : __builtin_inf();
         P.rc[P.n + s] = rs;                             // kept for lpx_revised_iteration_view (report text)
         if (k >= 0) { Cand c; c.v = rs; c.key = k; c.col = P.n + s; if (c.v < -P.eps) best = cand_pick(best, c); }
+    }
+    // the slack prices above are written before the cap check, as rv_price does in the fused path: a run that ends on its
+    // cap leaves every rc of lpx_revised_iteration_view from the same (last) pricing
+    if (st->iter >= st->dual_iter) {                    // :66 / :144 -- the cap travels in the state record (DevState::dual_iter is
+                                                        //   unused by this path), so the captured graph serves every segment of a run
+        if (t == 0) { st->status = LPX_ITER_LIMIT; st->r = -1; }
+        return;
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
@@ -439,7 +441,9 @@ __global__ __launch_bounds__(SEL_NT) void rv_select2(RvParams P)
     const int q = st->q;
     const int r = block_hysteresis_segments<SEL_NW, RowRatio, true>(m, P.tol, RowRatio{P.fac, 1, P.rhsbuf, 1, P.eps});
     if (r < 0) {                                                    // :113-118
-        if (t == 0) { st->status = LPX_UNBOUNDED; st->r = -1; }
+        // rv_upd_ftran of this iteration has already applied the pending update of the previous pivot (and overwritten fac
+        // with this iteration's d): nothing is pending any more, or rv_flush would apply it a second time with the new d
+        if (t == 0) { st->status = LPX_UNBOUNDED; st->r = -1; st->pad[2] = 0; }
         return;
     }
     const double piv = P.fac[r];
