@@ -427,6 +427,42 @@ int lpx_sensitivity_shadow_prices(const lpx_problem* p, const double* T, int R, 
 int lpx_sensitivity_solve_duality(const lpx_problem* p, const double* T, int R, int C, const int32_t* basis,
                                   const lpx_solve_opts* o, lpx_result* out);
 
+/* ---- ranging of a solved tableau on the device (not in the reference; csrc/lpx_ranging.hip) -------
+ * On the handle's current R x C window (m = R-1, objective row last, RHS column last), b_r = T[r,C-1], d_j = T[m,j],
+ * b+ = (b > 0 ? b : 0.0), d+ likewise, N = columns j < C-1 not in basis[0..m):
+ *   col_inc[j] = min over r < m with T[r,j] < -eps of b+_r / -T[r,j]   (j < C-1, basic columns included)
+ *   col_dec[j] = min over r < m with T[r,j] >  eps of b+_r /  T[r,j]
+ *   row_inc[r] = min over j in N with T[r,j] < -eps of d+_j / -T[r,j]  (r < m)
+ *   row_dec[r] = min over j in N with T[r,j] >  eps of d+_j /  T[r,j]
+ *   *min_rhs = min over r < m of b_r, *min_dj = min over j in N of d_j
+ * Strict minimum, ties to the lowest index; an empty set gives +inf and index -1; *_at is the row (col_*) or column
+ * (row_*) attaining it.  One read of the tableau; T, basis, snapshot, trace and captured graphs are left untouched.
+ * Any output pointer may be NULL.  eps < 0: LPX_EINVAL; no device: LPX_EDEVICE (checked before the handle). */
+int lpx_tableau_ranging(lpx_tableau* t, double eps,
+                        double* col_inc, int32_t* col_inc_at, double* col_dec, int32_t* col_dec_at,  /* [C-1] or NULL */
+                        double* row_inc, int32_t* row_inc_at, double* row_dec, int32_t* row_dec_at,  /* [R-1] or NULL */
+                        double* min_rhs, double* min_dj);
+/* The column ratio test along g_r = T[r,a[k]] - T[r,b[k]] (one IEEE subtraction) for K column pairs (equality rows). */
+int lpx_tableau_ranging_pairs(lpx_tableau* t, double eps, int K, const int32_t* a, const int32_t* b,
+                              double* inc, int32_t* inc_at, double* dec, int32_t* dec_at);   /* [K] or NULL */
+
+/* Ranging report of a solved model in user terms.  *_at: tableau column (x1..xn = 0..n-1, then the slacks) or -1;
+ * cost_*_at names the column that enters at that end, rhs_*_at the basic variable that leaves.  valid = 1 only when the
+ * solve is OPTIMAL and min_rhs >= -1e-9 and min_dj >= -1e-9; otherwise every array holds NaN / -1. */
+typedef struct lpx_ranging {
+    int n, m, valid;
+    double min_rhs, min_dj;                          /* of the final tableau (+inf when no tableau was ranged) */
+    double* cost_lo; double* cost_hi; int32_t* cost_lo_at; int32_t* cost_hi_at;
+    double* reduced_cost;                            /* [n] d(optimal objective) / d(lower bound of x_j) */
+    double* rhs_lo; double* rhs_hi; int32_t* rhs_lo_at; int32_t* rhs_hi_at;
+    double* dual;                                    /* [m] d(optimal objective) / d(b_i) */
+} lpx_ranging;
+/* lpx_solve plus the ranging report, computed on the solve's own device tableau before its handle is released.  `out` is
+ * what lpx_solve returns for the same inputs.  Primal Simplex and Dual Simplex (and their aliases) only: any other
+ * algorithm is LPX_EINVAL.  Free with lpx_ranging_free (and `out` with lpx_result_free). */
+int  lpx_solve_ranging(const lpx_problem* p, const char* algorithm, const lpx_solve_opts* o, lpx_result* out, lpx_ranging* rg);
+void lpx_ranging_free(lpx_ranging* rg);
+
 #ifdef __cplusplus
 }
 #endif

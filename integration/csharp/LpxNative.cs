@@ -60,6 +60,17 @@ namespace Linear_Programming_Solver.Native
         public int n_cuts; public double* cuts;
     }
 
+    [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct LpxRanging              // lpx_ranging  (lpx_solve_ranging; no counterpart in the reference)
+    {
+        public int n, m, valid;
+        public double min_rhs, min_dj;
+        public double* cost_lo; public double* cost_hi; public int* cost_lo_at; public int* cost_hi_at;
+        public double* reduced_cost;
+        public double* rhs_lo; public double* rhs_hi; public int* rhs_lo_at; public int* rhs_hi_at;
+        public double* dual;
+    }
+
     public static unsafe class Lpx
     {
         const string Lib = "lpx";                // liblpx.so (Linux) next to the executable / on LD_LIBRARY_PATH
@@ -114,6 +125,19 @@ namespace Linear_Programming_Solver.Native
         public static extern int lpx_solve(ref LpxProblem p, [MarshalAs(UnmanagedType.LPUTF8Str)] string algorithm,
                                            ref LpxSolveOpts o, out LpxResult result);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern void lpx_result_free(ref LpxResult r);
+
+        // ---- ranging of the final tableau (Primal / Dual Simplex), include/lpx.h; free both records afterwards ----
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_ranging(ref LpxProblem p, [MarshalAs(UnmanagedType.LPUTF8Str)] string algorithm,
+                                                   ref LpxSolveOpts o, out LpxResult result, out LpxRanging ranging);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern void lpx_ranging_free(ref LpxRanging r);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_tableau_ranging(IntPtr t, double eps, double* colInc, int* colIncAt, double* colDec, int* colDecAt,
+                                                     double* rowInc, int* rowIncAt, double* rowDec, int* rowDecAt,
+                                                     double* minRhs, double* minDj);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_tableau_ranging_pairs(IntPtr t, double eps, int K, int* a, int* b,
+                                                           double* inc, int* incAt, double* dec, int* decAt);
 
         public static string LastError()
         {

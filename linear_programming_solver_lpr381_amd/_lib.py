@@ -79,6 +79,13 @@ class Result(C.Structure):
                 ("node_z", dp), ("aux", C.c_double * 4), ("stats", Stats), ("n_cuts", C.c_int), ("cuts", dp)]
 
 
+class Ranging(C.Structure):
+    """lpx_ranging: the report of lpx_solve_ranging in user terms (freed by lpx_ranging_free)."""
+    _fields_ = [("n", C.c_int), ("m", C.c_int), ("valid", C.c_int), ("min_rhs", C.c_double), ("min_dj", C.c_double),
+                ("cost_lo", dp), ("cost_hi", dp), ("cost_lo_at", ip), ("cost_hi_at", ip), ("reduced_cost", dp),
+                ("rhs_lo", dp), ("rhs_hi", dp), ("rhs_lo_at", ip), ("rhs_hi_at", ip), ("dual", dp)]
+
+
 class Parsed(C.Structure):
     _fields_ = [("sense", C.c_int), ("n", C.c_int), ("m", C.c_int), ("c", dp), ("A", dp), ("rel", ip),
                 ("b", dp), ("ragged", C.c_int)]
@@ -202,6 +209,11 @@ def lib() -> C.CDLL:
     L.lpx_solve.argtypes = [C.POINTER(Problem), C.c_char_p, C.POINTER(SolveOpts), C.POINTER(Result)]
     L.lpx_result_free.argtypes = [C.POINTER(Result)]
     L.lpx_result_free.restype = None
+    L.lpx_tableau_ranging.argtypes = [vp, C.c_double, dp, ip, dp, ip, dp, ip, dp, ip, dp, dp]
+    L.lpx_tableau_ranging_pairs.argtypes = [vp, C.c_double, C.c_int, ip, ip, dp, ip, dp, ip]
+    L.lpx_solve_ranging.argtypes = [C.POINTER(Problem), C.c_char_p, C.POINTER(SolveOpts), C.POINTER(Result), C.POINTER(Ranging)]
+    L.lpx_ranging_free.argtypes = [C.POINTER(Ranging)]
+    L.lpx_ranging_free.restype = None
     L.lpx_parse_text.argtypes = [C.c_char_p, C.POINTER(Parsed)]
     L.lpx_parsed_free.argtypes = [C.POINTER(Parsed)]
     L.lpx_parsed_free.restype = None

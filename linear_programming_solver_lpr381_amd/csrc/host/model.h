@@ -87,6 +87,9 @@ struct EngineOptions {
     int bnb_dive = 0;                // sharded searches: 1 = depth-first-K pool policy
     bool quiet = false;              // internal solves whose Report nobody reads (B&B nodes): skip the canonical-form text,
                                      // hundreds of thousands of formatted numbers for a config-4 model
+    // lpx_solve_ranging: called by the primal / dual mirrors with the solve's device tableau and final status after the loop,
+    // before the handle goes back to the cache (the tableau has been downloaded already; the hook must not modify it)
+    std::function<void(::lpx_tableau* t, int status)> on_final_tableau;
     // test seams (see include/lpx_test.h); never set by product code
     int64_t test_fail_after_nodes = 0;
     std::function<int(double* T, int R, int C, int32_t* basis, int dual, int repaired, int max_iter, int nvars,
@@ -217,6 +220,9 @@ void BuildTableauPrimal(const LPProblem& expanded, std::vector<double>& T, int& 
                         std::vector<int32_t>& basis, std::vector<std::string>& varNames);
 LPProblem ExpandEqualitiesToInequalities(const LPProblem& model);
 LPProblem PrepareForTableauDual(const LPProblem& original, bool fix_d1);
+// Expanded rows of the tableau PrimalSimplex (dual = false) / DualSimplex builds from `original`: row k comes from constraint
+// row_of[k], multiplied by sign[k] (+1 / -1) -- the sign preparation actually applied, defect D1 included (fix_d1 = false).
+void PreparedRows(const LPProblem& original, bool dual, bool fix_d1, std::vector<int>& row_of, std::vector<int>& sign);
 
 // Handles of whole-model solves and of the B&B root templates, kept from one solve to the next (creating a handle costs ~4 ms of device
 // and pinned allocations, destroying it ~3 ms: two root solves and two templates were 25-30 ms of every search).  Exact shapes only --

@@ -230,6 +230,24 @@ LPProblem PrepareForTableauDual(const LPProblem& original, bool fix_d1)
     return expanded;
 }
 
+void PreparedRows(const LPProblem& original, bool dual, bool fix_d1, std::vector<int>& row_of, std::vector<int>& sign)
+{
+    const double Eps = 1e-9;
+    row_of.clear(); sign.clear();
+    for (int i = 0; i < (int)original.Constraints.size(); ++i) {
+        const Constraint& cons = original.Constraints[i];
+        if (cons.Relation == Rel::EQ) {                 // ExpandEqualitiesToInequalities / PrepareForTableau: (A, b), (-A, -b)
+            row_of.push_back(i); sign.push_back(1);
+            row_of.push_back(i); sign.push_back(-1);
+            continue;
+        }
+        int s = 1; double B = cons.B;
+        if (dual && cons.Relation == Rel::GE) { s = -1; B = -B; }
+        if (dual && !fix_d1 && B < -Eps) s = -s;        // the second flip of PrepareForTableauDual (defect D1)
+        row_of.push_back(i); sign.push_back(s);
+    }
+}
+
 static void fill_solution(SimplexResult& res, std::vector<double>&& T, int R, int C, std::vector<int32_t>&& basis,
                           std::vector<std::string>&& varNames, std::vector<double>& x, double& z)
 {
@@ -296,6 +314,7 @@ SimplexResult PrimalSimplex::Solve(const LPProblem& original, UpdatePivot update
     res.Trace = fetch_trace(th.h);
     rc = lpx_tableau_download(th.h, T.data(), basis.data());
     if (rc) throw_lib(rc);
+    if (opt.on_final_tableau) opt.on_final_tableau(th.h, st);
     if (st == LPX_UNBOUNDED) report += "UNBOUNDED\n";                                   // :104
     std::vector<double> x; double z;
     fill_solution(res, std::move(T), R, C, std::move(basis), std::move(varNames), x, z);
@@ -333,6 +352,7 @@ SimplexResult DualSimplex::Solve(const LPProblem& original, UpdatePivot updatePi
         res.Trace = fetch_trace(th.h);
         rc = lpx_tableau_download(th.h, T.data(), basis.data());
         if (rc) throw_lib(rc);
+        if (opt.on_final_tableau) opt.on_final_tableau(th.h, st);
     }
     if (st == LPX_INFEASIBLE) report += "INFEASIBLE (no entering column found)\n";      // :94
     SimplexResult full;

@@ -176,6 +176,16 @@ hipError_t launch_resident_primal_col(double* T, int ld, int R, int C, int grid,
                                       unsigned long long* xc, unsigned long long* xq, unsigned* xgen,
                                       double eps, double tol, int max_iter, int chunk, hipStream_t s);
 
+// What the ranging kernels (lpx_ranging.hip) need of a tableau handle: live shape, buffers, stream, and a workspace the
+// handle owns (grown on demand, freed with the handle).
+struct TableauView {
+    const double* T; int ld, R, C;
+    const int32_t* basis;
+    hipStream_t stream;
+    char** ws; size_t* ws_bytes;
+};
+void tableau_view(lpx_tableau* t, TableauView* v);
+
 void set_error(const std::string& msg);
 // Device memory the library keeps for reuse after its owner is gone (the chunk cache of destroyed parent stores, lpx_tableau.cpp):
 // trim_device_caches() gives all of it back; malloc_retry() is hipMalloc that does so and tries once more before it reports

@@ -248,6 +248,116 @@ int lpx_sensitivity_solve_duality(const lpx_problem* p, const double* T, int R, 
     });
 }
 
+int lpx_solve_ranging(const lpx_problem* p, const char* algorithm, const lpx_solve_opts* o, lpx_result* out, lpx_ranging* rg)
+{
+    if (!p || !algorithm || !out || !rg) { set_error("lpx_solve_ranging: null argument"); return LPX_EINVAL; }
+    std::memset(out, 0, sizeof(*out));
+    std::memset(rg, 0, sizeof(*rg));
+    bool dual = false;
+    {
+        std::string key;
+        try { key = LPSolver::NormalizeAlgorithmKey(algorithm); } catch (const std::exception&) {}
+        if (key == "dual simplex" || key == "dual") dual = true;
+        else if (!(key == "primal simplex" || key == "primal")) {
+            set_error(std::string("lpx_solve_ranging: algorithm '") + algorithm + "' has no tableau to range; supported: Primal Simplex, Dual Simplex");
+            return LPX_EINVAL;
+        }
+    }
+    if (int rc = ensure_device()) return rc;
+    lpx_solve_opts d; if (!o) { lpx_default_solve_opts(&d); o = &d; }
+    const int n = p->n, m = p->m;
+    const double nan = std::nan(""), inf = HUGE_VAL;
+    auto alloc = [](int k, auto fill) { using V = decltype(fill); V* a = (V*)std::malloc(sizeof(V) * (k > 0 ? k : 1)); for (int i = 0; i < k; ++i) a[i] = fill; return a; };
+    rg->n = n; rg->m = m; rg->valid = 0; rg->min_rhs = inf; rg->min_dj = inf;
+    rg->cost_lo = alloc(n, nan); rg->cost_hi = alloc(n, nan); rg->cost_lo_at = alloc(n, (int32_t)-1); rg->cost_hi_at = alloc(n, (int32_t)-1);
+    rg->reduced_cost = alloc(n, nan);
+    rg->rhs_lo = alloc(m, nan); rg->rhs_hi = alloc(m, nan); rg->rhs_lo_at = alloc(m, (int32_t)-1); rg->rhs_hi_at = alloc(m, (int32_t)-1);
+    rg->dual = alloc(m, nan);
+    const int rc = guarded("lpx_solve_ranging", [&]() -> int {
+        EngineOptions e = to_engine(o);
+        UpdatePivot cb = to_callback(o);
+        LPProblem q = to_problem(p);
+        std::vector<int> row_of, sign;
+        PreparedRows(q, dual, (o->dual_flags & LPX_DUAL_FIX_D1) != 0, row_of, sign);
+        const int mx = (int)row_of.size();
+        // raw ranging of the final tableau (R = mx + 1, C = n + mx + 1)
+        std::vector<double> ci(n + mx), cd(n + mx), ri(mx), rd(mx), dj(n + mx), pi, pd;
+        std::vector<int32_t> cia(n + mx), cda(n + mx), ria(mx), rda(mx), basis(mx), pia, pda, pa, pb;
+        std::vector<int> pair_of(m, -1);
+        for (int k = 0; k + 1 < mx; ++k)
+            if (row_of[k] == row_of[k + 1]) { pair_of[row_of[k]] = (int)pa.size(); pa.push_back(n + k); pb.push_back(n + k + 1); ++k; }
+        int status = -1; double min_rhs = inf, min_dj = inf;
+        e.on_final_tableau = [&](lpx_tableau* t, int st) {
+            status = st;
+            if (st != LPX_OPTIMAL) return;
+            auto chk = [](int rc) { if (rc) { char b[1024]; lpx_last_error(b, sizeof b); throw LpxException(rc, std::string("liblpx: ") + b); } };
+            chk(lpx_tableau_ranging(t, 1e-9, ci.data(), cia.data(), cd.data(), cda.data(), ri.data(), ria.data(), rd.data(), rda.data(),
+                                    &min_rhs, &min_dj));
+            const int K = (int)pa.size();
+            pi.resize(K); pd.resize(K); pia.resize(K); pda.resize(K);
+            chk(lpx_tableau_ranging_pairs(t, 1e-9, K, pa.data(), pb.data(), pi.data(), pia.data(), pd.data(), pda.data()));
+            chk(lpx_tableau_basis(t, basis.data()));
+            void* dT = nullptr; int ld = 0;
+            chk(lpx_tableau_device_ptr(t, &dT, &ld));
+            if (hipMemcpy(dj.data(), (const double*)dT + (size_t)mx * ld, sizeof(double) * (n + mx), hipMemcpyDeviceToHost) != hipSuccess)
+                throw LpxException(LPX_EDEVICE, "lpx_solve_ranging: objective row download failed");
+        };
+        SimplexResult r = LPSolver(e).Solve(q, algorithm, cb);
+        fill_result(out, r, p->n);
+        rg->min_rhs = min_rhs; rg->min_dj = min_dj;
+        if (!(status == LPX_OPTIMAL && min_rhs >= -1e-9 && min_dj >= -1e-9)) return 0;
+        rg->valid = 1;
+        const double sigma = q.ObjectiveSense == Sense::Min ? -1.0 : 1.0;
+        std::vector<int> row_of_var(n, -1);
+        for (int k = 0; k < mx; ++k) if (basis[k] >= 0 && basis[k] < n) row_of_var[basis[k]] = k;
+        for (int j = 0; j < n; ++j) {
+            const double c = q.C[j];
+            const int k = row_of_var[j];
+            if (k < 0) {
+                const double dp = dj[j] > 0 ? dj[j] : 0.0;
+                if (sigma > 0) { rg->cost_lo[j] = -inf; rg->cost_hi[j] = c + dp; rg->cost_hi_at[j] = j; }
+                else           { rg->cost_lo[j] = c - dp; rg->cost_hi[j] = inf; rg->cost_lo_at[j] = j; }
+                rg->reduced_cost[j] = -sigma * dj[j];
+            } else {
+                const double up = sigma > 0 ? ri[k] : rd[k], dn = sigma > 0 ? rd[k] : ri[k];
+                rg->cost_lo[j] = c - dn; rg->cost_hi[j] = c + up;
+                rg->cost_lo_at[j] = sigma > 0 ? rda[k] : ria[k];
+                rg->cost_hi_at[j] = sigma > 0 ? ria[k] : rda[k];
+                rg->reduced_cost[j] = 0.0;
+            }
+        }
+        auto leaving = [&](int32_t r) { return r >= 0 ? basis[r] : (int32_t)-1; };
+        for (int k = 0; k < mx; ++k) {
+            const int i = row_of[k];
+            const double b = q.Constraints[i].B;
+            if (pair_of[i] >= 0) {
+                if (sign[k] < 0) continue;
+                const int h = pair_of[i], s1 = pa[h], s2 = pb[h];
+                rg->rhs_lo[i] = b - pd[h]; rg->rhs_hi[i] = b + pi[h];
+                rg->rhs_lo_at[i] = leaving(pda[h]); rg->rhs_hi_at[i] = leaving(pia[h]);
+                rg->dual[i] = sigma * (dj[s1] - dj[s2]);
+            } else {
+                const int s = n + k;
+                const bool pos = sign[k] > 0;
+                rg->rhs_lo[i] = b - (pos ? cd[s] : ci[s]); rg->rhs_hi[i] = b + (pos ? ci[s] : cd[s]);
+                rg->rhs_lo_at[i] = leaving(pos ? cda[s] : cia[s]); rg->rhs_hi_at[i] = leaving(pos ? cia[s] : cda[s]);
+                rg->dual[i] = sigma * sign[k] * dj[s];
+            }
+        }
+        return 0;
+    });
+    if (rc != 0) lpx_ranging_free(rg);
+    return rc;
+}
+
+void lpx_ranging_free(lpx_ranging* rg)
+{
+    if (!rg) return;
+    std::free(rg->cost_lo); std::free(rg->cost_hi); std::free(rg->cost_lo_at); std::free(rg->cost_hi_at); std::free(rg->reduced_cost);
+    std::free(rg->rhs_lo); std::free(rg->rhs_hi); std::free(rg->rhs_lo_at); std::free(rg->rhs_hi_at); std::free(rg->dual);
+    std::memset(rg, 0, sizeof(*rg));
+}
+
 void lpx_result_free(lpx_result* r)
 {
     if (!r) return;

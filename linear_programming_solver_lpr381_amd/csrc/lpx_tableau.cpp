@@ -60,7 +60,15 @@ struct lpx_tableau {
     bool fused_off = false;         // the second buffer did not fit: stay on the two-launch path
     bool suspended2 = false;        // ... by the two-launch group kernels (it must continue there: no pending pivot, state in *hst)
     bool fsuspended = false; int frec_cur = 0;   // fused group run left unfinished: its records (latest: index frec_cur) are in place
+    char* rgws = nullptr; size_t rgws_bytes = 0;  // lpx_tableau_ranging's partial slabs and outputs, on first use
 };
+
+void lpx::tableau_view(lpx_tableau* t, TableauView* v)
+{
+    v->T = t->T; v->ld = t->ld; v->R = t->R; v->C = t->C;
+    v->basis = t->basis; v->stream = t->stream;
+    v->ws = &t->rgws; v->ws_bytes = &t->rgws_bytes;
+}
 
 static constexpr int LPX_RESIDENT_RETRY = -1000;     // internal: first resident launch timed out, state untouched
 
@@ -194,6 +202,7 @@ void lpx_tableau_destroy(lpx_tableau* t)
     hipFree(t->T); hipFree(t->slab); hipFree(t->snapT); hipFree(t->snapBasis);
     hipFree(t->frows); hipFree(t->fcols); hipFree(t->fchosen); hipFree(t->cutbuf);
     hipFree(t->fT); hipFree(t->fslab); hipFree(t->dring);
+    hipFree(t->rgws);
     hipFree(t->xr); hipFree(t->xp); hipFree(t->xgen); hipFree(t->xbasis); hipFree(t->xT); hipFree(t->xc); hipFree(t->xq);
     if (t->hslab) hipHostFree(t->hslab);
     if (t->cutbuf_h) hipHostFree(t->cutbuf_h);

@@ -69,6 +69,24 @@ class SimplexResult:        # Models/PrimalSimplex.cs:38-49 (+ engine extras aft
     Stats: Optional[dict] = None
     Extra: Optional[np.ndarray] = None      # revised / knapsack: numbers the reference only prints
     Cuts: Optional[np.ndarray] = None       # cutting plane: rows (A[0..n), B) in the order added
+    Ranging: Optional["RangingReport"] = None   # LPSolver.SolveRanged only
+
+
+@dataclass
+class RangingReport:        # lpx_ranging (include/lpx.h): ranges of the solved model in user terms
+    valid: bool
+    cost_lo: np.ndarray
+    cost_hi: np.ndarray
+    cost_lo_at: np.ndarray      # tableau column entering at that end (x1..xn = 0..n-1, then the slacks), -1 = none
+    cost_hi_at: np.ndarray
+    reduced_cost: np.ndarray    # d(optimal objective) / d(lower bound of x_j)
+    rhs_lo: np.ndarray
+    rhs_hi: np.ndarray
+    rhs_lo_at: np.ndarray       # basic variable leaving at that end, -1 = none
+    rhs_hi_at: np.ndarray
+    dual: np.ndarray            # d(optimal objective) / d(b_i)
+    min_rhs: float
+    min_dj: float
 
 
 class SolverException(Exception):
@@ -198,6 +216,33 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         if rc != 0:
             raise SolverException(rc, _lib.last_error())
         res = _take_result(r, problem.NumVars)
+        self.FinalTableau = res.Tableau
+        return res
+
+    def SolveRanged(self, problem: LPProblem, algorithm: str) -> SimplexResult:
+        """Solve (Primal Simplex or Dual Simplex) plus the ranging report of the final tableau, computed on the
+        device tableau of the solve itself (lpx_solve_ranging); the result is otherwise what Solve returns."""
+        L = lib()
+        o, keep = _solve_opts(self.engine)
+        ps, hold = _problem_struct(problem)
+        r, g = _lib.Result(), _lib.Ranging()
+        rc = L.lpx_solve_ranging(C.byref(ps), algorithm.encode() if algorithm is not None else b"", C.byref(o),
+                                 C.byref(r), C.byref(g))
+        if rc != 0:
+            raise SolverException(rc, _lib.last_error())
+        try:
+            rep = RangingReport(
+                valid=bool(g.valid),
+                cost_lo=_arr(g.cost_lo, g.n, np.float64), cost_hi=_arr(g.cost_hi, g.n, np.float64),
+                cost_lo_at=_arr(g.cost_lo_at, g.n, np.int32), cost_hi_at=_arr(g.cost_hi_at, g.n, np.int32),
+                reduced_cost=_arr(g.reduced_cost, g.n, np.float64),
+                rhs_lo=_arr(g.rhs_lo, g.m, np.float64), rhs_hi=_arr(g.rhs_hi, g.m, np.float64),
+                rhs_lo_at=_arr(g.rhs_lo_at, g.m, np.int32), rhs_hi_at=_arr(g.rhs_hi_at, g.m, np.int32),
+                dual=_arr(g.dual, g.m, np.float64), min_rhs=g.min_rhs, min_dj=g.min_dj)
+        finally:
+            L.lpx_ranging_free(C.byref(g))
+        res = _take_result(r, problem.NumVars)
+        res.Ranging = rep
         self.FinalTableau = res.Tableau
         return res
 

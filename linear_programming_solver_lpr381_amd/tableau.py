@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from typing import Callable, Optional, Tuple
 
 import numpy as np
@@ -16,6 +17,23 @@ def _wrap_cb(cb: Optional[PivotCallback]):
     if cb is None:
         return _lib.NULL_CB
     return _lib.PIVOT_CB(lambda _user, it, r, q: cb(it, r, q))
+
+
+@dataclass
+class TableauRanging:
+    """lpx_tableau_ranging of a device tableau (include/lpx.h): the column ratio test along the RHS column for every
+    column j < C-1 (col_*), the row ratio test along the objective row over the nonbasic columns for every row r < m
+    (row_*), and the two scalars that tell whether the basis is primal / dual feasible.  *_at: -1 where the set is empty."""
+    col_inc: np.ndarray
+    col_inc_at: np.ndarray
+    col_dec: np.ndarray
+    col_dec_at: np.ndarray
+    row_inc: np.ndarray
+    row_inc_at: np.ndarray
+    row_dec: np.ndarray
+    row_dec_at: np.ndarray
+    min_rhs: float
+    min_dj: float
 
 
 class DeviceTableau:
@@ -90,6 +108,31 @@ class DeviceTableau:
         tr = np.zeros((max(n.value, 1), 2), dtype=np.int32)
         check(lib().lpx_tableau_trace(self._h, tr.ctypes.data_as(ip), n.value, C.byref(n)))
         return tr[: n.value].copy()
+
+    def ranging(self, eps: float = 1e-9) -> TableauRanging:
+        """Ranging of the current shape in one device pass; the tableau, basis and trace are left as they are."""
+        R, C_ = C.c_int(), C.c_int()
+        check(lib().lpx_tableau_shape(self._h, C.byref(R), C.byref(C_), None))
+        n, m = C_.value - 1, R.value - 1
+        out = [np.empty(k, dtype=t) for k, t in ((n, np.float64), (n, np.int32), (n, np.float64), (n, np.int32),
+                                                  (m, np.float64), (m, np.int32), (m, np.float64), (m, np.int32))]
+        ptrs = [a.ctypes.data_as(dp if a.dtype == np.float64 else ip) for a in out]
+        lo, dj = C.c_double(), C.c_double()
+        check(lib().lpx_tableau_ranging(self._h, float(eps), *ptrs, C.byref(lo), C.byref(dj)))
+        return TableauRanging(*out, min_rhs=lo.value, min_dj=dj.value)
+
+    def ranging_pairs(self, a, b, eps: float = 1e-9) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """The column ratio test along T[:,a[k]] - T[:,b[k]] (equality rows). Returns (inc, inc_at, dec, dec_at)."""
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        b = np.ascontiguousarray(b, dtype=np.int32)
+        assert a.shape == b.shape and a.ndim == 1
+        K = len(a)
+        inc, dec = np.empty(K), np.empty(K)
+        inc_at, dec_at = np.empty(K, dtype=np.int32), np.empty(K, dtype=np.int32)
+        check(lib().lpx_tableau_ranging_pairs(self._h, float(eps), K, a.ctypes.data_as(ip), b.ctypes.data_as(ip),
+                                              inc.ctypes.data_as(dp), inc_at.ctypes.data_as(ip),
+                                              dec.ctypes.data_as(dp), dec_at.ctypes.data_as(ip)))
+        return inc, inc_at, dec, dec_at
 
     def primal_run(self, opts: Optional[RunOpts] = None, cb: Optional[PivotCallback] = None,
                    **kw) -> Tuple[int, dict]:

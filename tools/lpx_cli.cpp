@@ -1,12 +1,13 @@
 // lpx_cli -- Linux stand-in for the reference's WinForms host (Form1.cs), over the C ABI of liblpx.so only.
 //
-//   lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--export FILE] INPUT.txt
+//   lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--export FILE] INPUT.txt
 //
 // Does what Form1 does around the solvers: reads the model text (Import, Form1.cs:284-296), parses it with the LPParser
 // grammar (lpx_parse_text, Models/LPParser.cs:9-79), runs the algorithm chosen by its dropdown name (btnSolve_Click,
 // Form1.cs:231-279), shows the iteration text followed by "Final Report:" and "Summary:" (:277-278), and can write the
 // export file layout of BtnExport_Click (:308-315).  C only touches include/lpx.h: this is also the link test of the
-// boundary from a compiled host.  There is no CPU fallback: without a gfx950 device the solve fails with LPX_EDEVICE.
+// boundary from a compiled host.  --ranging (Primal / Dual Simplex) solves through lpx_solve_ranging and prints the ranging
+// report of the final tableau after the summary.  There is no CPU fallback: without a gfx950 device the solve fails with LPX_EDEVICE.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,20 +20,52 @@
 static std::string g_iterations;
 static void on_text(void*, const char* text, const uint8_t*, int, int) { g_iterations += text; }
 
+// Column names as BuildTableau gives them (x1..xn, then c1.. for the slacks); -1 = none.
+static std::string col_name(int j, int n) { return j < 0 ? "-" : (j < n ? "x" : "c") + std::to_string(j < n ? j + 1 : j - n + 1); }
+
+static std::string ranging_table(const lpx_ranging& g)
+{
+    std::string s = "\n\nRanging:\n";
+    if (!g.valid) {
+        char b[160];
+        std::snprintf(b, sizeof b, "  not available: the final tableau is not optimal and feasible (min rhs %.17g, min d_j %.17g)\n", g.min_rhs, g.min_dj);
+        return s + b;
+    }
+    char b[256];
+    std::snprintf(b, sizeof b, "  %-8s %24s %24s %8s %8s %24s\n", "variable", "cost low", "cost high", "enters", "enters", "reduced cost");
+    s += b;
+    for (int j = 0; j < g.n; ++j) {
+        std::snprintf(b, sizeof b, "  %-8s %24.17g %24.17g %8s %8s %24.17g\n", col_name(j, g.n).c_str(), g.cost_lo[j], g.cost_hi[j],
+                      col_name(g.cost_lo_at[j], g.n).c_str(), col_name(g.cost_hi_at[j], g.n).c_str(), g.reduced_cost[j]);
+        s += b;
+    }
+    std::snprintf(b, sizeof b, "  %-8s %24s %24s %8s %8s %24s\n", "row", "rhs low", "rhs high", "leaves", "leaves", "dual");
+    s += b;
+    for (int i = 0; i < g.m; ++i) {
+        std::snprintf(b, sizeof b, "  %-8s %24.17g %24.17g %8s %8s %24.17g\n", ("b" + std::to_string(i + 1)).c_str(), g.rhs_lo[i], g.rhs_hi[i],
+                      col_name(g.rhs_lo_at[i], g.n).c_str(), col_name(g.rhs_hi_at[i], g.n).c_str(), g.dual[i]);
+        s += b;
+    }
+    return s;
+}
+
 int main(int argc, char** argv)
 {
     std::string algorithm = "Primal Simplex", input, exportPath;
-    bool repaired = false, iterations = false;
+    bool repaired = false, iterations = false, ranging = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--algorithm" && i + 1 < argc) algorithm = argv[++i];
         else if (a == "--repaired") repaired = true;
         else if (a == "--iterations") iterations = true;
+        else if (a == "--ranging") ranging = true;
         else if (a == "--export" && i + 1 < argc) exportPath = argv[++i];
         else if (a == "--help" || a == "-h") {
-            std::printf("usage: lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--export FILE] INPUT.txt\n"
+            std::printf("usage: lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--export FILE] INPUT.txt\n"
                         "  NAME: Primal Simplex | Revised Primal Simplex | Dual Simplex | Branch and Bound |\n"
-                        "        Revised Branch and Bound | Branch and Bound Knapsack | Cutting Plane | Revised Cutting Plane\n");
+                        "        Revised Branch and Bound | Branch and Bound Knapsack | Cutting Plane | Revised Cutting Plane\n"
+                        "  --ranging: after the summary, the cost / RHS ranges, reduced costs and duals of the final tableau\n"
+                        "             (Primal Simplex and Dual Simplex only)\n");
             return 0;
         } else input = a;
     }
@@ -51,17 +84,20 @@ int main(int argc, char** argv)
     o.render_iterations = iterations ? 1 : 0;
     if (repaired) { o.dual_flags = 7; o.bnb_mode = 1; }
     lpx_result r;
-    const int rc = lpx_solve(&prob, algorithm.c_str(), &o, &r);
+    lpx_ranging rg;
+    const int rc = ranging ? lpx_solve_ranging(&prob, algorithm.c_str(), &o, &r, &rg) : lpx_solve(&prob, algorithm.c_str(), &o, &r);
     lpx_parsed_free(&p);
     if (rc != 0) { lpx_last_error(err, sizeof err); std::fprintf(stderr, "%s\n", err); return rc == LPX_EDEVICE ? 69 : 70; }
     std::string shown = g_iterations;
     shown += "\n\nFinal Report:\n"; shown += r.report ? r.report : "";
     shown += "\n\nSummary:\n"; shown += r.summary ? r.summary : "";
+    if (ranging) shown += ranging_table(rg);
     std::fputs(shown.c_str(), stdout); std::fputc('\n', stdout);
     if (!exportPath.empty()) {
         std::ofstream w(exportPath);
         w << "Linear Program:\n" << text << "\n\nIterations:\n" << shown << "\n";
     }
     lpx_result_free(&r);
+    if (ranging) lpx_ranging_free(&rg);
     return 0;
 }
