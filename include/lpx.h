@@ -34,7 +34,8 @@ enum {
     LPX_INFEASIBLE = 2,   /* "INFEASIBLE" Models/DualSimplex.cs:92-96 */
     LPX_ITER_LIMIT = 3,   /* exception "Iteration limit exceeded." Models/PrimalSimplex.cs:95-96 */
     LPX_RUNNING    = 4,   /* internal: loop not finished */
-    /* outcomes of the cutting-plane consumers (lpx_result.status for "Cutting Plane" / "Revised Cutting Plane") */
+    /* outcomes of the cutting-plane consumers (lpx_result.status for "Cutting Plane" / "Revised Cutting Plane";
+       LPX_CUT_INTEGER / LPX_CUT_INCOMPLETE also for "GMI Cutting Plane", lpx_solve_cuts) */
     LPX_CUT_INTEGER     = 0,  /* "Status: OPTIMAL INTEGER" Models/CuttingPlane.cs:91-104, CuttingPlaneRevised.cs:49-57 */
     LPX_CUT_INCOMPLETE  = 10, /* 50 iterations used up, Models/CuttingPlane.cs:132-137, CuttingPlaneRevised.cs:70-77 */
     LPX_CUT_ERROR       = 11, /* "Error: ..." summaries, Models/CuttingPlane.cs:42-74,116-124 */
@@ -462,6 +463,59 @@ typedef struct lpx_ranging {
  * algorithm is LPX_EINVAL.  Free with lpx_ranging_free (and `out` with lpx_result_free). */
 int  lpx_solve_ranging(const lpx_problem* p, const char* algorithm, const lpx_solve_opts* o, lpx_result* out, lpx_ranging* rg);
 void lpx_ranging_free(lpx_ranging* rg);
+
+/* ---- GMI cutting planes on the device (not in the reference; csrc/lpx_cuts.hip) ---------------
+ * On the handle's live R x C window (m = R-1 rows, objective row last, RHS column last), b_r = T[r,C-1], basic columns from
+ * the device basis.  Column j is integer iff j < min(n_mask, first_cut_col) and is_int[j] != 0; every other column (cut
+ * slacks included) is continuous.  frac(v) = v - floor(v) (IEEE floor, one subtraction).
+ *   Source rows: row r < m is a candidate when basis[r] is integer and f0 = frac(b_r) lies in [away, 1 - away].  Candidates
+ *   are ranked by |f0 - 0.5| ascending, ties to the lower r; the first K whose cut passes the dynamism filter are taken,
+ *   K = min(cuts_per_round, free capacity after purging) where free capacity = min(Rcap - (R - P), Ccap - (C - P)).
+ *   Cut of row r (Gomory mixed-integer): sum over nonbasic j < C-1 of alpha_j x_j >= 1, alpha_j = 0 for basic j; a = T[r,j]:
+ *     integer j:    f = frac(a); alpha = 0 if f <= coef_eps or f >= 1 - coef_eps, else f / f0 if f <= f0, else (1 - f) / (1 - f0)
+ *     continuous j: alpha = 0 if |a| <= coef_eps, else a / f0 if a > 0, else -a / (1 - f0)
+ *   Dynamism filter: reject when max alpha > max_dynamism * (min nonzero alpha); a row with no nonzero alpha passes (its
+ *   cut 0 >= 1 proves the IP infeasible).
+ *   Appended row: -alpha.x + s = -1 with s basic in it: entries (alpha_j == 0 ? +0.0 : -alpha_j), 1.0 in s's column, -1.0 in
+ *   the RHS.  The objective row is unchanged and every new slack has d = 0: the tableau stays dual feasible.
+ *   Purge (purge != 0, before appending): a cut is inactive when its slack column (a column in [first_cut_col, C-1)) is
+ *   basic in a row r with b_r > purge_tol; that row and that column are deleted (the column is the unit vector e_r, so this
+ *   is exact).  Remaining rows and columns keep their order; basis indices are renumbered.
+ *   New shape: R' = R - P + K, C' = C - P + K; the cut rows go just above the objective row in selection order, their
+ *   slacks just before the RHS column.
+ * The basis is updated and the loop state reset (as lpx_tableau_build_child does); snapshot, trace and captured graphs are
+ * left alone.  With K = P = 0 nothing is touched. */
+typedef struct lpx_cut_opts {
+    int    cuts_per_round;   /* K, default 8, 1..64 */
+    int    max_rounds;       /* default 50 (the reference's cap, Models/CuttingPlane.cs:19) */
+    int    max_active;       /* cut rows alive at once = capacity reserved by lpx_solve_cuts, default 64 */
+    int    purge;            /* default 1 */
+    double away, coef_eps, max_dynamism, purge_tol, int_tol;   /* 1e-3, 1e-9, 1e6, 1e-9, 1e-6 */
+} lpx_cut_opts;
+void lpx_default_cut_opts(lpx_cut_opts* o);
+/* One round on a handle, which needs capacity for the result shape.  src_rows gets the K source rows in selection order
+ * (row indices of the tableau before the round; K <= cuts_per_round), purged_cols the P purged columns ascending (column
+ * indices before the round).  P can be as large as the number of cut columns before the round, C-1 - first_cut_col: it is
+ * not bounded by max_active (that option only sizes lpx_solve_cuts' handle), so size purged_cols by that number.
+ * Argument errors return LPX_EINVAL before any device check, with the tableau untouched: o outside its ranges
+ * (cuts_per_round 1..64, max_rounds >= 0, max_active >= 1, 0 < away <= 0.5, 0 <= coef_eps < 0.5, max_dynamism >= 1,
+ * purge_tol not NaN, int_tol >= 0), n_mask < 0, is_int NULL with n_mask > 0, a NULL handle, first_cut_col outside [1, C-1], more than
+ * 2048 cut columns, a handle wider than 131072 columns, R < 2.  No device: LPX_EDEVICE. */
+int  lpx_tableau_gmi_round(lpx_tableau* t, const uint8_t* is_int, int n_mask, int first_cut_col,
+                           const lpx_cut_opts* o, int* n_added, int32_t* src_rows /* [K] or NULL */,
+                           int* n_purged, int32_t* purged_cols /* [C-1 - first_cut_col] or NULL */);
+/* The whole solver with explicit options; lpx_solve(p, "GMI Cutting Plane" or "gmi", ...) is this with defaults.  Every
+ * structural variable is integer; the model is prepared as Dual Simplex prepares it with defect D1 fixed (Min/Max, <=, >=,
+ * =); the slack of a prepared row is integer iff its coefficients and RHS are integral.  Root LP: lpx_primal_run when every
+ * prepared RHS is >= 0, else the repaired dual (fdf_guard = max_iter, cleanup = 1).  Each round: integer basics within
+ * int_tol of integral -> LPX_CUT_INTEGER; else lpx_tableau_gmi_round; 0 cuts added -> LPX_CUT_INCOMPLETE (stalled); else
+ * lpx_dual_run (fdf_guard = 0, cleanup = 1), LPX_INFEASIBLE there -> the IP is infeasible (LPX_INFEASIBLE); max_rounds
+ * used up -> LPX_CUT_INCOMPLETE.  The root LP's own LPX_UNBOUNDED / LPX_INFEASIBLE are returned as such.
+ * out: optimal_value = final LP bound in the user's sense; x, T, basis of the final tableau; trace = the pivots of the root
+ * LP and of every round, in order; lp_solves = 1 + rounds; aux = {rounds, cuts added, cuts purged, root LP bound};
+ * node_log = (round, source row, slack column) per added cut with node_z = the LP bound after that round; cuts = every cut
+ * ever added, in x-space as LE rows (A[0..n), B).  Argument errors as lpx_tableau_gmi_round (co NULL = defaults). */
+int  lpx_solve_cuts(const lpx_problem* p, const lpx_solve_opts* o, const lpx_cut_opts* co, lpx_result* out);
 
 #ifdef __cplusplus
 }

@@ -107,4 +107,6 @@ namespace Linear_Programming_Solver.Models
     public sealed class BranchAndBoundKnapsackLpx : LpxAlgorithm { public BranchAndBoundKnapsackLpx() : base("Branch and Bound Knapsack") { } }
     public sealed class CuttingPlaneLpx : LpxAlgorithm { public CuttingPlaneLpx() : base("Cutting Plane") { } }
     public sealed class CuttingPlaneRevisedLpx : LpxAlgorithm { public CuttingPlaneRevisedLpx() : base("Revised Cutting Plane") { } }
+    // not in the reference: the GMI cutting-plane loop on the device with its default options (Lpx.lpx_solve_cuts takes explicit ones)
+    public sealed class GmiCuttingPlaneLpx : LpxAlgorithm { public GmiCuttingPlaneLpx() : base("GMI Cutting Plane") { } }
 }

@@ -71,6 +71,13 @@ namespace Linear_Programming_Solver.Native
         public double* dual;
     }
 
+    [StructLayout(LayoutKind.Sequential)]
+    public struct LpxCutOpts                     // lpx_cut_opts  (lpx_solve_cuts / lpx_tableau_gmi_round; not in the reference)
+    {
+        public int cuts_per_round, max_rounds, max_active, purge;
+        public double away, coef_eps, max_dynamism, purge_tol, int_tol;
+    }
+
     public static unsafe class Lpx
     {
         const string Lib = "lpx";                // liblpx.so (Linux) next to the executable / on LD_LIBRARY_PATH
@@ -138,6 +145,15 @@ namespace Linear_Programming_Solver.Native
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_tableau_ranging_pairs(IntPtr t, double eps, int K, int* a, int* b,
                                                            double* inc, int* incAt, double* dec, int* decAt);
+
+        // ---- GMI cutting planes on the device (not in the reference), include/lpx.h ----
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern void lpx_default_cut_opts(out LpxCutOpts o);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_cuts(ref LpxProblem p, ref LpxSolveOpts o, ref LpxCutOpts co, out LpxResult result);
+        // srcRows: [cuts_per_round] or null; purgedCols: [C-1 - firstCutCol] (the cut columns before the round, NOT max_active) or null
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_tableau_gmi_round(IntPtr t, byte* isInt, int nMask, int firstCutCol, ref LpxCutOpts o,
+                                                       out int nAdded, int* srcRows, out int nPurged, int* purgedCols);
 
         public static string LastError()
         {

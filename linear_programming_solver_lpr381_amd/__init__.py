@@ -8,12 +8,12 @@ from . import comm
 from ._lib import LpxError, default_opts
 from .tableau import DeviceTableau, TableauRanging, primal_tableau, dual_tableau, multi_run
 from .revised import DeviceRevised, invert
-from .solver import (BranchAndBound, BranchAndBoundKnapsack, BranchAndBoundRevised, Constraint, CuttingPlane,
-                     CuttingPlaneRevised, DeviceKnapsack, DualSimplex, LPProblem, SensitivityAnalysis,
+from .solver import (BranchAndBound, BranchAndBoundKnapsack, BranchAndBoundRevised, Constraint, CutOpts, CuttingPlane,
+                     CuttingPlaneRevised, DeviceKnapsack, DualSimplex, GmiCuttingPlane, LPProblem, SensitivityAnalysis,
                      LPSolver, ParseFromText, PrimalSimplex, RangingReport, Rel, RevisedPrimalSimplex, Sense, SimplexResult,
                      SolverException)
 
 __all__ = ["_lib", "comm", "LpxError", "default_opts", "DeviceTableau", "TableauRanging", "primal_tableau", "dual_tableau", "multi_run", "DeviceRevised", "invert", "LPSolver", "LPProblem", "Constraint", "Sense", "Rel",
            "SimplexResult", "RangingReport", "SolverException", "PrimalSimplex", "RevisedPrimalSimplex", "DualSimplex",
            "BranchAndBound", "BranchAndBoundKnapsack", "BranchAndBoundRevised", "ParseFromText", "DeviceKnapsack",
-           "CuttingPlane", "CuttingPlaneRevised", "SensitivityAnalysis"]
+           "CuttingPlane", "CuttingPlaneRevised", "SensitivityAnalysis", "CutOpts", "GmiCuttingPlane"]

@@ -86,6 +86,13 @@ class Ranging(C.Structure):
                 ("rhs_lo", dp), ("rhs_hi", dp), ("rhs_lo_at", ip), ("rhs_hi_at", ip), ("dual", dp)]
 
 
+class CutOpts(C.Structure):
+    """lpx_cut_opts (include/lpx.h): options of the GMI cut round and loop."""
+    _fields_ = [("cuts_per_round", C.c_int), ("max_rounds", C.c_int), ("max_active", C.c_int), ("purge", C.c_int),
+                ("away", C.c_double), ("coef_eps", C.c_double), ("max_dynamism", C.c_double), ("purge_tol", C.c_double),
+                ("int_tol", C.c_double)]
+
+
 class Parsed(C.Structure):
     _fields_ = [("sense", C.c_int), ("n", C.c_int), ("m", C.c_int), ("c", dp), ("A", dp), ("rel", ip),
                 ("b", dp), ("ragged", C.c_int)]
@@ -214,6 +221,11 @@ def lib() -> C.CDLL:
     L.lpx_solve_ranging.argtypes = [C.POINTER(Problem), C.c_char_p, C.POINTER(SolveOpts), C.POINTER(Result), C.POINTER(Ranging)]
     L.lpx_ranging_free.argtypes = [C.POINTER(Ranging)]
     L.lpx_ranging_free.restype = None
+    L.lpx_default_cut_opts.argtypes = [C.POINTER(CutOpts)]
+    L.lpx_default_cut_opts.restype = None
+    L.lpx_tableau_gmi_round.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.POINTER(CutOpts), C.POINTER(C.c_int), ip,
+                                        C.POINTER(C.c_int), ip]
+    L.lpx_solve_cuts.argtypes = [C.POINTER(Problem), C.POINTER(SolveOpts), C.POINTER(CutOpts), C.POINTER(Result)]
     L.lpx_parse_text.argtypes = [C.c_char_p, C.POINTER(Parsed)]
     L.lpx_parsed_free.argtypes = [C.POINTER(Parsed)]
     L.lpx_parsed_free.restype = None
@@ -241,6 +253,17 @@ def default_opts(dual: bool = False, **kw) -> RunOpts:
     for k, v in kw.items():
         if not hasattr(o, k):
             raise TypeError(f"unknown run option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def cut_opts(**kw) -> CutOpts:
+    """lpx_default_cut_opts with keyword overrides."""
+    o = CutOpts()
+    lib().lpx_default_cut_opts(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError(f"unknown cut option {k!r}")
         setattr(o, k, v)
     return o
 

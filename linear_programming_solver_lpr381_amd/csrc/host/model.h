@@ -166,6 +166,17 @@ private:
     EngineOptions opt;
 };
 
+// GMI cutting-plane loop on the device (not in the reference; lpx_solve_cuts in include/lpx.h defines it): the root LP and
+// every re-optimisation run on one handle with capacity for max_active cut rows, the cut rounds are lpx_tableau_gmi_round.
+class GmiCuttingPlane : public ILPAlgorithm {
+public:
+    GmiCuttingPlane(const EngineOptions& o, const lpx_cut_opts& co) : opt(o), cut(co) {}
+    explicit GmiCuttingPlane(const EngineOptions& o = {}) : opt(o) { lpx_default_cut_opts(&cut); }
+    SimplexResult Solve(const LPProblem& problem, UpdatePivot updatePivot = nullptr) override;
+private:
+    EngineOptions opt; lpx_cut_opts cut;
+};
+
 // Models/SensitivityAnalysis.cs:11-297.  `problem` is mutated by ApplyChange, as in the
 // reference; `result` must carry Tableau/Basis/VarNames (the constructor checks, :24-43).
 class SensitivityAnalysis {

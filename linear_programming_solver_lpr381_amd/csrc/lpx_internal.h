@@ -186,6 +186,17 @@ struct TableauView {
 };
 void tableau_view(lpx_tableau* t, TableauView* v);
 
+// What the cut round (lpx_cuts.hip) needs beyond that: the capacity, the writable basis and loop state, and the second tableau
+// buffer of the fused primal loop (allocated on first use when need_second; T2 = nullptr when it does not fit the device).
+struct CutView {
+    double* T; double* T2; int ld, R, C, Rcap, Ccap;
+    int32_t* basis; DevState* st;
+    hipStream_t stream;
+    char** ws; size_t* ws_bytes;
+};
+void tableau_cut_view(lpx_tableau* t, CutView* v, bool need_second);
+int check_cut_opts(const lpx_cut_opts* o, const char* what);   // LPX_EINVAL (message set) when o is outside its ranges
+
 void set_error(const std::string& msg);
 // Device memory the library keeps for reuse after its owner is gone (the chunk cache of destroyed parent stores, lpx_tableau.cpp):
 // trim_device_caches() gives all of it back; malloc_retry() is hipMalloc that does so and tries once more before it reports

@@ -170,6 +170,8 @@ int lpx_solve(const lpx_problem* p, const char* algorithm, const lpx_solve_opts*
         const std::string key = LPSolver::NormalizeAlgorithmKey(algorithm);
         if (key == "cutting plane") r = CuttingPlane(e).Solve(q, cb);
         else if (key == "revised cutting plane" || key == "cutting plane revised") r = CuttingPlaneRevised(e).Solve(q, cb);
+        // not in the reference: the device GMI loop (lpx_solve_cuts) with default options
+        else if (key == "gmi cutting plane" || key == "gmi") r = GmiCuttingPlane(e).Solve(q, cb);
         else r = LPSolver(e).Solve(q, algorithm, cb);
         fill_result(out, r, p->n);
         return 0;
@@ -348,6 +350,21 @@ int lpx_solve_ranging(const lpx_problem* p, const char* algorithm, const lpx_sol
     });
     if (rc != 0) lpx_ranging_free(rg);
     return rc;
+}
+
+int lpx_solve_cuts(const lpx_problem* p, const lpx_solve_opts* o, const lpx_cut_opts* co, lpx_result* out)
+{
+    if (!p || !out) { set_error("lpx_solve_cuts: null argument"); return LPX_EINVAL; }
+    std::memset(out, 0, sizeof(*out));
+    lpx_cut_opts dc; if (!co) { lpx_default_cut_opts(&dc); co = &dc; }
+    if (int rc = check_cut_opts(co, "lpx_solve_cuts")) return rc;
+    if (int rc = ensure_device()) return rc;
+    lpx_solve_opts d; if (!o) { lpx_default_solve_opts(&d); o = &d; }
+    return guarded("lpx_solve_cuts", [&]() -> int {
+        SimplexResult r = GmiCuttingPlane(to_engine(o), *co).Solve(to_problem(p), to_callback(o));
+        fill_result(out, r, p->n);
+        return 0;
+    });
 }
 
 void lpx_ranging_free(lpx_ranging* rg)

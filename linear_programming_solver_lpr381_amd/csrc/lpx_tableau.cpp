@@ -60,13 +60,22 @@ struct lpx_tableau {
     bool fused_off = false;         // the second buffer did not fit: stay on the two-launch path
     bool suspended2 = false;        // ... by the two-launch group kernels (it must continue there: no pending pivot, state in *hst)
     bool fsuspended = false; int frec_cur = 0;   // fused group run left unfinished: its records (latest: index frec_cur) are in place
-    char* rgws = nullptr; size_t rgws_bytes = 0;  // lpx_tableau_ranging's partial slabs and outputs, on first use
+    char* rgws = nullptr; size_t rgws_bytes = 0;  // lpx_tableau_ranging's partial slabs and outputs / the cut round's plan, on first use
 };
 
 void lpx::tableau_view(lpx_tableau* t, TableauView* v)
 {
     v->T = t->T; v->ld = t->ld; v->R = t->R; v->C = t->C;
     v->basis = t->basis; v->stream = t->stream;
+    v->ws = &t->rgws; v->ws_bytes = &t->rgws_bytes;
+}
+
+namespace { static bool fused_buffers(lpx_tableau* t); }   // below
+void lpx::tableau_cut_view(lpx_tableau* t, CutView* v, bool need_second)
+{
+    v->T = t->T; v->T2 = need_second && fused_buffers(t) ? t->fT : nullptr;
+    v->ld = t->ld; v->R = t->R; v->C = t->C; v->Rcap = t->Rcap; v->Ccap = t->Ccap;
+    v->basis = t->basis; v->st = t->st; v->stream = t->stream;
     v->ws = &t->rgws; v->ws_bytes = &t->rgws_bytes;
 }
 

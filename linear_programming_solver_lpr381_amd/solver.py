@@ -89,6 +89,25 @@ class RangingReport:        # lpx_ranging (include/lpx.h): ranges of the solved 
     min_dj: float
 
 
+@dataclass
+class CutOpts:              # lpx_cut_opts (include/lpx.h): the GMI cut round and loop
+    cuts_per_round: int = 8
+    max_rounds: int = 50
+    max_active: int = 64
+    purge: int = 1
+    away: float = 1e-3
+    coef_eps: float = 1e-9
+    max_dynamism: float = 1e6
+    purge_tol: float = 1e-9
+    int_tol: float = 1e-6
+
+    def to_c(self) -> "_lib.CutOpts":
+        o = _lib.CutOpts()
+        for k, _ in o._fields_:
+            setattr(o, k, getattr(self, k))
+        return o
+
+
 class SolverException(Exception):
     """The reference's `throw new Exception(message)`; `.code` is the LPX_E_* of include/lpx.h."""
 
@@ -216,6 +235,8 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         if rc != 0:
             raise SolverException(rc, _lib.last_error())
         res = _take_result(r, problem.NumVars)
+        if algorithm is not None and _algorithm_key(algorithm) in ("gmi cutting plane", "gmi"):
+            _gmi_names(res, problem)
         self.FinalTableau = res.Tableau
         return res
 
@@ -245,6 +266,41 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         res.Ranging = rep
         self.FinalTableau = res.Tableau
         return res
+
+
+    def SolveCuts(self, problem: LPProblem, opts: Optional[CutOpts] = None, **cut_opts) -> SimplexResult:
+        """The GMI cutting-plane loop on the device (lpx_solve_cuts) with explicit options (CutOpts fields as keywords);
+        Solve(problem, "GMI Cutting Plane") is this with the defaults.  Status: CUT_INTEGER, CUT_INCOMPLETE, INFEASIBLE
+        or UNBOUNDED; NodeLog rows are (round, source row, slack column) per cut; Cuts are x-space LE rows (A, B)."""
+        co = opts if opts is not None else CutOpts(**cut_opts)
+        o, keep = _solve_opts(self.engine)
+        ps, hold = _problem_struct(problem)
+        r = _lib.Result()
+        c = co.to_c()
+        rc = lib().lpx_solve_cuts(C.byref(ps), C.byref(o), C.byref(c), C.byref(r))
+        if rc != 0:
+            raise SolverException(rc, _lib.last_error())
+        res = _take_result(r, problem.NumVars)
+        _gmi_names(res, problem)
+        self.FinalTableau = res.Tableau
+        return res
+
+
+def _algorithm_key(name: str) -> str:
+    """The key lpx_solve matches algorithm names by (LPSolver.NormalizeAlgorithmKey, Models/LPSolver.cs:61-76): lower case,
+    every "algorithm" removed, white space collapsed."""
+    return " ".join(name.lower().replace("algorithm", "").split())
+
+
+def _gmi_names(res: "SimplexResult", problem: LPProblem):
+    """VarNames of a GMI result: x1..xn, the slacks of the prepared rows c1.., then the live cut slacks g1.. in column order."""
+    if res.Tableau is None:
+        return
+    n = problem.NumVars
+    ms = sum(2 if int(k.Relation) == int(Rel.EQ) else 1 for k in problem.Constraints)
+    ncol = res.Tableau.shape[1] - 1
+    res.VarNames = ([f"x{j + 1}" for j in range(n)] + [f"c{j + 1}" for j in range(ms)] +
+                    [f"g{k + 1}" for k in range(ncol - n - ms)])
 
 
 class _Algo:                # ILPAlgorithm, Models/IPLAlgorithm.cs:5-8
@@ -287,6 +343,10 @@ class CuttingPlane(_Algo):              # Models/CuttingPlane.cs:9 (built by For
 
 class CuttingPlaneRevised(_Algo):       # Models/CuttingPlaneRevised.cs:9 (Form1.cs:258)
     NAME = "Revised Cutting Plane"
+
+
+class GmiCuttingPlane(_Algo):           # not in the reference: the device GMI loop (lpx_solve_cuts)
+    NAME = "GMI Cutting Plane"
 
 
 class SensitivityAnalysis:

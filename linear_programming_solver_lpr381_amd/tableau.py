@@ -55,6 +55,19 @@ class DeviceTableau:
         t.upload(T, basis)
         return t
 
+    @classmethod
+    def with_capacity(cls, T: np.ndarray, basis: Optional[np.ndarray], Rcap: int, Ccap: int) -> "DeviceTableau":
+        """A handle of capacity (Rcap, Ccap) holding the smaller tableau T (lpx_tableau_set_shape + upload)."""
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        t = cls(Rcap, Ccap)
+        t.set_shape(*T.shape)
+        t.upload(T, basis)
+        return t
+
+    def set_shape(self, R: int, C_: int):
+        check(lib().lpx_tableau_set_shape(self._h, int(R), int(C_)))
+        self.R, self.C = int(R), int(C_)
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             lib().lpx_tableau_destroy(self._h)
@@ -133,6 +146,22 @@ class DeviceTableau:
                                               inc.ctypes.data_as(dp), inc_at.ctypes.data_as(ip),
                                               dec.ctypes.data_as(dp), dec_at.ctypes.data_as(ip)))
         return inc, inc_at, dec, dec_at
+
+    def gmi_round(self, is_int, first_cut_col: int, opts=None, **kw) -> Tuple[np.ndarray, np.ndarray]:
+        """One GMI cut round on the device (lpx_tableau_gmi_round): is_int[j] marks the integer columns j < len(is_int);
+        opts is an lpx_cut_opts (None: defaults with keyword overrides).  The handle takes the new shape.
+        Returns (source rows, purged columns)."""
+        o = opts if opts is not None else _lib.cut_opts(**kw)
+        mask = np.ascontiguousarray(np.asarray(is_int) != 0, dtype=np.uint8)
+        src = np.zeros(max(o.cuts_per_round, 1), dtype=np.int32)
+        pcol = np.zeros(max(self.C, 1), dtype=np.int32)
+        k, p = C.c_int(), C.c_int()
+        check(lib().lpx_tableau_gmi_round(self._h, mask.ctypes.data_as(C.POINTER(C.c_uint8)), len(mask), int(first_cut_col),
+                                          C.byref(o), C.byref(k), src.ctypes.data_as(ip), C.byref(p), pcol.ctypes.data_as(ip)))
+        R, C_ = C.c_int(), C.c_int()
+        check(lib().lpx_tableau_shape(self._h, C.byref(R), C.byref(C_), None))
+        self.R, self.C = R.value, C_.value
+        return src[: k.value].copy(), pcol[: p.value].copy()
 
     def primal_run(self, opts: Optional[RunOpts] = None, cb: Optional[PivotCallback] = None,
                    **kw) -> Tuple[int, dict]:

@@ -1,15 +1,18 @@
 // lpx_cli -- Linux stand-in for the reference's WinForms host (Form1.cs), over the C ABI of liblpx.so only.
 //
-//   lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--export FILE] INPUT.txt
+//   lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]
+//           [--export FILE] INPUT.txt
 //
 // Does what Form1 does around the solvers: reads the model text (Import, Form1.cs:284-296), parses it with the LPParser
 // grammar (lpx_parse_text, Models/LPParser.cs:9-79), runs the algorithm chosen by its dropdown name (btnSolve_Click,
 // Form1.cs:231-279), shows the iteration text followed by "Final Report:" and "Summary:" (:277-278), and can write the
 // export file layout of BtnExport_Click (:308-315).  C only touches include/lpx.h: this is also the link test of the
 // boundary from a compiled host.  --ranging (Primal / Dual Simplex) solves through lpx_solve_ranging and prints the ranging
-// report of the final tableau after the summary.  There is no CPU fallback: without a gfx950 device the solve fails with LPX_EDEVICE.
+// report of the final tableau after the summary.  --cuts-per-round / --cut-rounds (GMI Cutting Plane) solve through
+// lpx_solve_cuts with those options.  There is no CPU fallback: without a gfx950 device the solve fails with LPX_EDEVICE.
 #include <cstdio>
 #include <cstdlib>
+#include <cctype>
 #include <cstring>
 #include <fstream>
 #include <sstream>
@@ -49,25 +52,52 @@ static std::string ranging_table(const lpx_ranging& g)
     return s;
 }
 
+// The key lpx_solve matches algorithm names by (LPSolver.NormalizeAlgorithmKey, Models/LPSolver.cs:61-76): lower case, every
+// "algorithm" removed, runs of white space collapsed to one blank, none at either end.
+static std::string algorithm_key(const std::string& name)
+{
+    std::string low;
+    for (char ch : name) low += (char)std::tolower((unsigned char)ch);
+    for (size_t p; (p = low.find("algorithm")) != std::string::npos;) low.erase(p, 9);
+    std::string key; bool sp = false;
+    for (char ch : low) {
+        if (std::isspace((unsigned char)ch)) { sp = true; continue; }
+        if (sp && !key.empty()) key += ' ';
+        sp = false; key += ch;
+    }
+    return key;
+}
+
 int main(int argc, char** argv)
 {
     std::string algorithm = "Primal Simplex", input, exportPath;
-    bool repaired = false, iterations = false, ranging = false;
+    bool repaired = false, iterations = false, ranging = false, cut_set = false;
+    lpx_cut_opts co; lpx_default_cut_opts(&co);
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--algorithm" && i + 1 < argc) algorithm = argv[++i];
         else if (a == "--repaired") repaired = true;
         else if (a == "--iterations") iterations = true;
         else if (a == "--ranging") ranging = true;
+        else if (a == "--cuts-per-round" && i + 1 < argc) { co.cuts_per_round = std::atoi(argv[++i]); cut_set = true; }
+        else if (a == "--cut-rounds" && i + 1 < argc) { co.max_rounds = std::atoi(argv[++i]); cut_set = true; }
         else if (a == "--export" && i + 1 < argc) exportPath = argv[++i];
         else if (a == "--help" || a == "-h") {
-            std::printf("usage: lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--export FILE] INPUT.txt\n"
+            std::printf("usage: lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]\n"
+                        "               [--export FILE] INPUT.txt\n"
                         "  NAME: Primal Simplex | Revised Primal Simplex | Dual Simplex | Branch and Bound |\n"
-                        "        Revised Branch and Bound | Branch and Bound Knapsack | Cutting Plane | Revised Cutting Plane\n"
+                        "        Revised Branch and Bound | Branch and Bound Knapsack | Cutting Plane | Revised Cutting Plane |\n"
+                        "        GMI Cutting Plane (gmi)\n"
                         "  --ranging: after the summary, the cost / RHS ranges, reduced costs and duals of the final tableau\n"
-                        "             (Primal Simplex and Dual Simplex only)\n");
+                        "             (Primal Simplex and Dual Simplex only)\n"
+                        "  --cuts-per-round K, --cut-rounds N: GMI Cutting Plane options (defaults 8 and 50)\n");
             return 0;
         } else input = a;
+    }
+    if (cut_set) {
+        const std::string key = algorithm_key(algorithm);
+        if (key != "gmi cutting plane" && key != "gmi") { std::fprintf(stderr, "lpx_cli: --cuts-per-round / --cut-rounds need --algorithm \"GMI Cutting Plane\"\n"); return 64; }
+        if (ranging) { std::fprintf(stderr, "lpx_cli: --ranging does not combine with --cuts-per-round / --cut-rounds\n"); return 64; }
     }
     if (input.empty()) { std::fprintf(stderr, "lpx_cli: no input file (try --help)\n"); return 64; }
     std::ifstream f(input);
@@ -85,7 +115,8 @@ int main(int argc, char** argv)
     if (repaired) { o.dual_flags = 7; o.bnb_mode = 1; }
     lpx_result r;
     lpx_ranging rg;
-    const int rc = ranging ? lpx_solve_ranging(&prob, algorithm.c_str(), &o, &r, &rg) : lpx_solve(&prob, algorithm.c_str(), &o, &r);
+    const int rc = ranging ? lpx_solve_ranging(&prob, algorithm.c_str(), &o, &r, &rg)
+                 : cut_set ? lpx_solve_cuts(&prob, &o, &co, &r) : lpx_solve(&prob, algorithm.c_str(), &o, &r);
     lpx_parsed_free(&p);
     if (rc != 0) { lpx_last_error(err, sizeof err); std::fprintf(stderr, "%s\n", err); return rc == LPX_EDEVICE ? 69 : 70; }
     std::string shown = g_iterations;
