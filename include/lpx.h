@@ -517,6 +517,82 @@ int  lpx_tableau_gmi_round(lpx_tableau* t, const uint8_t* is_int, int n_mask, in
  * ever added, in x-space as LE rows (A[0..n), B).  Argument errors as lpx_tableau_gmi_round (co NULL = defaults). */
 int  lpx_solve_cuts(const lpx_problem* p, const lpx_solve_opts* o, const lpx_cut_opts* co, lpx_result* out);
 
+/* ---- post-optimal edits on the device (not in the reference; csrc/lpx_postopt.hip) ------------
+ * On the handle's live R x C window (m = R-1, objective row last, RHS column last, Cm = C-1), basic columns from the device
+ * basis.  Every edit is one of two combinations, each with a fixed summation order:
+ *   column combination  out[i] = base[i] (+) sum_k v[k] * T[i, cols[k]]      for i in [0, R)
+ *   row combination     out[j] = base[j] (+) sum_k w[k] * T[rows[k], j]      for the columns j of the output
+ * where "(+) sum" means: the K terms are cut into segments of LPX_POSTOPT_SEG consecutive terms (k = 0 .. SEG-1, SEG ..
+ * 2 SEG-1, ...); each term is one IEEE multiply; each segment is summed sequentially in term order starting from +0.0;
+ * out = base, then out = out + (segment sum) for the segments in ascending order.  No FMA.  K = 0 gives out = base.  The
+ * bits do not depend on the launch geometry or on the handle's capacity.
+ *
+ * lpx_tableau_rhs_update:  column combination with base = T[:, Cm], written back into T[:, Cm] (row m included: z moves by
+ *   y.delta).  cols[k] in [0, Cm).
+ * lpx_tableau_add_column:  column combination with base[i] = +0.0 for i < m and base[m] = obj (= -c' for a new column of cost
+ *   c'); the RHS column moves to index C and the result becomes column Cm; the new shape is R x (C+1).  Needs Ccap > C.
+ * lpx_tableau_objective_update:  base[j] = T[m, j], then base[dcols[k]] = base[dcols[k]] - dd[k] (one IEEE subtraction per
+ *   touched column; dcols distinct, in [0, Cm)); row combination over j in [0, C) with rows[k] in [0, m); every basic column
+ *   of the output is written as +0.0; the result replaces row m.
+ * lpx_tableau_add_row:  base holds C+1 entries in the NEW shape: [0, Cm) the prepared row's old columns, Cm its own slack
+ *   (1.0 for a fresh slack), C its RHS.  Row combination with rows[k] in [0, m): output column j < Cm reads column j, output
+ *   column Cm (the new slack) is base[Cm] unchanged, output column C reads the old RHS column Cm; every basic column is +0.0.
+ *   The result goes in as row m, the objective row moves to m+1, every old row gets +0.0 in the new slack column Cm and its
+ *   RHS moved to column C; basis[m] = Cm.  The new shape is (R+1) x (C+1).  Needs Rcap > R and Ccap > C.
+ * After each edit the live shape is (re)set and the loop state reset as lpx_tableau_build_child does; the basis is unchanged
+ * but for the appended row's slack.  Snapshot, trace buffer and captured graphs are left alone: a later lpx_tableau_restore
+ * brings back the tableau as it was snapshotted, with its own shape's contents, and does not undo or redo the edit.
+ * Argument errors return LPX_EINVAL before any device check, with the tableau untouched: a NULL handle, R < 2, K < 0 or
+ * Kd < 0, NULL term arrays with K > 0, an index outside its range, repeated dcols, a NULL base, no spare capacity.  No
+ * device: LPX_EDEVICE. */
+#define LPX_POSTOPT_SEG 64
+int lpx_tableau_rhs_update(lpx_tableau* t, int K, const int32_t* cols, const double* v);
+int lpx_tableau_objective_update(lpx_tableau* t, int K, const int32_t* rows, const double* w, int Kd, const int32_t* dcols,
+                                 const double* dd);
+int lpx_tableau_add_column(lpx_tableau* t, int K, const int32_t* cols, const double* v, double obj);
+int lpx_tableau_add_row(lpx_tableau* t, int K, const int32_t* rows, const double* w, const double* base /* [C+1] */);
+
+/* A model-level warm session: one handle holds the solved model and takes edits, each re-optimised on the device from the
+ * current basis.  The model is prepared as lpx_solve_cuts prepares its root (Dual Simplex preparation with defect D1 fixed:
+ * Min -> Max with c negated, >= rows negated, = rows as the pair (a, b), (-a, -b)); prepared row k comes from constraint
+ * row_of[k] with sign[k] = +-1 and owns slack column `slack_col[k]`.  lpx_session_open: lpx_primal_run when every prepared
+ * b >= 0, else the repaired dual (fdf_guard = max_iter, cleanup = 1); for an all-<= model with b >= 0 this is the trace, basis
+ * and objective of lpx_solve(p, "Primal Simplex").  The first dual run of a handle pays a one-time setup: when the open
+ * solve ended OPTIMAL, open pays it with one dual run (fdf_guard = 0, cleanup = 1) on the solved tableau, which is primal and
+ * dual feasible and takes no pivot, after res has been filled, and reports its host wall in res->aux[1] (milliseconds).
+ * Edits (each fills `res` for the edited model; res->trace / res->stats cover this edit's pivots only; res->aux[0] = 1 for a
+ * warm edit, 0 when the session was not optimal and the edited model was rebuilt and solved cold on the same handle):
+ *   set_rhs(K, cons, b):  delta_k = sign_k * (b_new - b_old) on every prepared row k of each constraint, through
+ *                         lpx_tableau_rhs_update over the slack columns; then lpx_dual_run (fdf_guard = 0, cleanup = 1) when
+ *                         min_i b_i < -1e-9, else no pivot.
+ *   set_cost(K, vars, c): delta' = sigma * (c_new - c_old) (sigma = -1 for Min); basic variables become row weights, nonbasic
+ *                         ones sparse deltas of lpx_tableau_objective_update; then lpx_primal_run.
+ *   add_variable(c, a):   a'_k = sign_k * a[row_of[k]] over the slack columns (lpx_tableau_add_column, obj = -sigma c); the
+ *                         new column goes just before the RHS; then lpx_primal_run.
+ *   add_constraint(a, rel, b): 1 prepared row for <= / >=, 2 for = (lpx_tableau_add_row each; weights -a' of the basic
+ *                         structural variables); then lpx_dual_run as set_rhs.
+ * res->x covers the original variables, then the added ones in order; res->T is filled only with opts.want_tableau.
+ * Running out of capacity returns LPX_EINVAL with the session unchanged.  lpx_session_ranging ranges the current basis as
+ * lpx_solve_ranging does (columns in *_at are the session tableau's). */
+typedef struct lpx_session lpx_session;
+typedef struct lpx_session_opts {
+    int extra_rows;        /* spare prepared rows for added constraints, default 16 */
+    int extra_cols;        /* spare columns for added variables and constraint slacks, default 16 */
+    int max_iter;          /* 0 = 10000 */
+    int batch;             /* 0 = default */
+    int want_tableau;      /* 1 = download the tableau into res->T after every call (R x C of the live window) */
+} lpx_session_opts;
+void lpx_default_session_opts(lpx_session_opts* o);
+int  lpx_session_open(const lpx_problem* p, const lpx_session_opts* o, lpx_session** s, lpx_result* res);
+int  lpx_session_set_rhs(lpx_session* s, int K, const int32_t* cons, const double* b, lpx_result* res);
+int  lpx_session_set_cost(lpx_session* s, int K, const int32_t* vars, const double* c, lpx_result* res);
+int  lpx_session_add_variable(lpx_session* s, double c, const double* a /* [m_user] */, lpx_result* res);
+int  lpx_session_add_constraint(lpx_session* s, const double* a /* [n_cur] */, int rel, double b, lpx_result* res);
+int  lpx_session_ranging(lpx_session* s, lpx_ranging* rg);
+/* current user-level shape: variables (original + added) and constraints (original + added); any pointer may be NULL */
+int  lpx_session_shape(const lpx_session* s, int* n_vars, int* n_cons);
+void lpx_session_close(lpx_session* s);
+
 #ifdef __cplusplus
 }
 #endif

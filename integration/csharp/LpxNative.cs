@@ -72,6 +72,12 @@ namespace Linear_Programming_Solver.Native
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public struct LpxSessionOpts                 // lpx_session_opts  (lpx_session_open; not in the reference)
+    {
+        public int extra_rows, extra_cols, max_iter, batch, want_tableau;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public struct LpxCutOpts                     // lpx_cut_opts  (lpx_solve_cuts / lpx_tableau_gmi_round; not in the reference)
     {
         public int cuts_per_round, max_rounds, max_active, purge;
@@ -154,6 +160,34 @@ namespace Linear_Programming_Solver.Native
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_tableau_gmi_round(IntPtr t, byte* isInt, int nMask, int firstCutCol, ref LpxCutOpts o,
                                                        out int nAdded, int* srcRows, out int nPurged, int* purgedCols);
+
+        // warm post-optimal edits of a device tableau (include/lpx.h, lpx_postopt.hip; not in the reference)
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_tableau_rhs_update(IntPtr t, int K, int* cols, double* v);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_tableau_objective_update(IntPtr t, int K, int* rows, double* w, int Kd, int* dcols, double* dd);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_tableau_add_column(IntPtr t, int K, int* cols, double* v, double obj);
+        // baseRow: [C+1] in the new shape
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_tableau_add_row(IntPtr t, int K, int* rows, double* w, double* baseRow);
+        // the model-level session: what SensitivityAnalysis.ApplyChange (Models/SensitivityAnalysis.cs:78-107) leaves to a re-solve
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern void lpx_default_session_opts(out LpxSessionOpts o);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_session_open(ref LpxProblem p, ref LpxSessionOpts o, out IntPtr session, out LpxResult result);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_session_set_rhs(IntPtr s, int K, int* cons, double* b, out LpxResult result);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_session_set_cost(IntPtr s, int K, int* vars, double* c, out LpxResult result);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_session_add_variable(IntPtr s, double c, double* a, out LpxResult result);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_session_add_constraint(IntPtr s, double* a, int rel, double b, out LpxResult result);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_session_ranging(IntPtr s, out LpxRanging rg);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_session_shape(IntPtr s, out int nVars, out int nCons);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern void lpx_session_close(IntPtr s);
 
         public static string LastError()
         {

@@ -93,6 +93,12 @@ class CutOpts(C.Structure):
                 ("int_tol", C.c_double)]
 
 
+class SessionOpts(C.Structure):
+    """lpx_session_opts (include/lpx.h): capacity and run options of a warm post-optimal session."""
+    _fields_ = [("extra_rows", C.c_int), ("extra_cols", C.c_int), ("max_iter", C.c_int), ("batch", C.c_int),
+                ("want_tableau", C.c_int)]
+
+
 class Parsed(C.Structure):
     _fields_ = [("sense", C.c_int), ("n", C.c_int), ("m", C.c_int), ("c", dp), ("A", dp), ("rel", ip),
                 ("b", dp), ("ragged", C.c_int)]
@@ -226,6 +232,21 @@ def lib() -> C.CDLL:
     L.lpx_tableau_gmi_round.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.POINTER(CutOpts), C.POINTER(C.c_int), ip,
                                         C.POINTER(C.c_int), ip]
     L.lpx_solve_cuts.argtypes = [C.POINTER(Problem), C.POINTER(SolveOpts), C.POINTER(CutOpts), C.POINTER(Result)]
+    L.lpx_tableau_rhs_update.argtypes = [vp, C.c_int, ip, dp]
+    L.lpx_tableau_objective_update.argtypes = [vp, C.c_int, ip, dp, C.c_int, ip, dp]
+    L.lpx_tableau_add_column.argtypes = [vp, C.c_int, ip, dp, C.c_double]
+    L.lpx_tableau_add_row.argtypes = [vp, C.c_int, ip, dp, dp]
+    L.lpx_default_session_opts.argtypes = [C.POINTER(SessionOpts)]
+    L.lpx_default_session_opts.restype = None
+    L.lpx_session_open.argtypes = [C.POINTER(Problem), C.POINTER(SessionOpts), C.POINTER(vp), C.POINTER(Result)]
+    L.lpx_session_set_rhs.argtypes = [vp, C.c_int, ip, dp, C.POINTER(Result)]
+    L.lpx_session_set_cost.argtypes = [vp, C.c_int, ip, dp, C.POINTER(Result)]
+    L.lpx_session_add_variable.argtypes = [vp, C.c_double, dp, C.POINTER(Result)]
+    L.lpx_session_add_constraint.argtypes = [vp, dp, C.c_int, C.c_double, C.POINTER(Result)]
+    L.lpx_session_ranging.argtypes = [vp, C.POINTER(Ranging)]
+    L.lpx_session_shape.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.lpx_session_close.argtypes = [vp]
+    L.lpx_session_close.restype = None
     L.lpx_parse_text.argtypes = [C.c_char_p, C.POINTER(Parsed)]
     L.lpx_parsed_free.argtypes = [C.POINTER(Parsed)]
     L.lpx_parsed_free.restype = None

@@ -242,5 +242,21 @@ void PreparedRows(const LPProblem& original, bool dual, bool fix_d1, std::vector
 ::lpx_tableau* acquire_exact_handle(int R, int C);
 void release_exact_handle(::lpx_tableau* t, int R, int C);
 
+// Ranging of a solved device tableau in user terms (lpx_solve_ranging, lpx_session_ranging).  Prepared row k comes from constraint
+// row_of[k] with sign[k] and owns slack column slack_col[k]; user variable j is tableau column var_col[j].
+struct RangingMap {
+    const LPProblem* q = nullptr;
+    std::vector<int> row_of, sign, slack_col, var_col;
+};
+struct RawRanging {                     // lpx_tableau_ranging / _pairs of the final tableau, its basis and objective row
+    std::vector<double> ci, cd, ri, rd, dj, pi, pd;
+    std::vector<int32_t> cia, cda, ria, rda, basis, pia, pda, pa, pb;
+    std::vector<int> pair_of;
+    double min_rhs = 1.0 / 0.0, min_dj = 1.0 / 0.0;
+};
+void RangingAlloc(lpx_ranging* rg, int n, int m);                  // every array NaN / -1, valid = 0
+void RangeTableau(::lpx_tableau* t, const RangingMap& map, RawRanging& raw);
+void RangingToUser(const RangingMap& map, const RawRanging& raw, int status, lpx_ranging* rg);
+
 }
 }  // namespace lpx::host

@@ -13,6 +13,7 @@
 //              K cut rows at that column (it reads old row m before it writes cut row 0 over it); one thread per old row
 //              owns that row's tail (K new zero slack entries and the moved RHS), one thread the tails of the new rows.
 //              With purges: one compacting pass into the handle's second tableau buffer, copied back by the host.
+#include "lpx_append.h"
 #include "lpx_block.h"
 
 #include <cmath>
@@ -257,6 +258,22 @@ __global__ __launch_bounds__(GP_NT) void gmi_pick(int m, int Cm, int Rcap, int C
     }
 }
 
+// the K cut rows of a round as append_rows_inplace (lpx_append.h) writes them: -alpha over the old columns, the unit
+// vector of the row's own slack, -1 in the RHS
+struct GmiNewRows {
+    const double* T; int ld;
+    const int32_t* src; const double* f0;       // LDS copies of the plan
+    const uint8_t* nbm; const uint8_t* isint; double ce;
+    __device__ double body(int k, int j) const
+    {
+        const double a = T[(size_t)src[k] * ld + j];
+        const double al = nbm[j] ? gmi_alpha(a, isint[j] != 0, f0[k], ce) : 0.0;
+        return al == 0.0 ? 0.0 : -al;
+    }
+    __device__ double slack(int k, int i) const { return i == k ? 1.0 : 0.0; }
+    __device__ double rhs(int) const { return -1.0; }
+};
+
 // In place (no purge): blocks [0, ncb) own the columns j < Cm of the new rows, the rest the tails and the basis.
 __global__ __launch_bounds__(GA_NT) void gmi_apply_inplace(double* __restrict__ T, int ld, int m, int Cm, int ncb,
                                                            const GmiPlan* __restrict__ plan, const uint8_t* __restrict__ nbm,
@@ -269,36 +286,10 @@ __global__ __launch_bounds__(GA_NT) void gmi_apply_inplace(double* __restrict__ 
     if ((int)blockIdx.x < ncb) {
         for (int k = threadIdx.x; k < K; k += GA_NT) { s_src[k] = plan->src[k]; s_f0[k] = plan->f0[k]; }
         __syncthreads();
-        const int j = blockIdx.x * GA_NT + threadIdx.x;
-        if (j >= Cm) return;
-        const double obj = T[(size_t)m * ld + j];       // read before cut row 0 overwrites it
-        T[(size_t)(m + K) * ld + j] = obj;
-        const bool nb = nbm[j] != 0, ii = isint[j] != 0;
-        for (int k = 0; k < K; ++k) {
-            const double a = T[(size_t)s_src[k] * ld + j];
-            const double al = nb ? gmi_alpha(a, ii, s_f0[k], ce) : 0.0;
-            T[(size_t)(m + k) * ld + j] = al == 0.0 ? 0.0 : -al;
-        }
-        return;
     }
-    const int r = (blockIdx.x - ncb) * GA_NT + threadIdx.x;
-    if (r < m) {
-        double* row = T + (size_t)r * ld;
-        const double bv = row[Cm];
-        for (int k = 0; k < K; ++k) row[Cm + k] = 0.0;
-        row[Cm + K] = bv;
-    } else if (r == m) {
-        const double bv = T[(size_t)m * ld + Cm];
-        double* obj = T + (size_t)(m + K) * ld;
-        for (int k = 0; k < K; ++k) obj[Cm + k] = 0.0;
-        obj[Cm + K] = bv;
-        for (int k = 0; k < K; ++k) {
-            double* row = T + (size_t)(m + k) * ld;
-            for (int i = 0; i < K; ++i) row[Cm + i] = i == k ? 1.0 : 0.0;
-            row[Cm + K] = -1.0;
-        }
-    }
-    if (r < m + K) basis[r] = nbasis[r];
+    const GmiNewRows rows{T, ld, s_src, s_f0, nbm, isint, ce};
+    const int r = append_rows_inplace(T, ld, m, Cm, K, ncb, GA_NT, rows);
+    if (r >= 0 && r < m + K) basis[r] = nbasis[r];
 }
 
 // With purges: the new R2 x C2 tableau gathered into T2 (blockIdx.y strides the rows), the new basis from the plan.

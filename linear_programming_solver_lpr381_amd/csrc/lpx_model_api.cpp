@@ -147,6 +147,99 @@ template <class F> int guarded(const char* what, F&& f)
 }
 }  // namespace
 
+// ---- ranging in user terms, shared by lpx_solve_ranging and lpx_session_ranging -----------------------------------------
+namespace lpx { namespace host {
+
+void RangingAlloc(lpx_ranging* rg, int n, int m)
+{
+    const double nan = std::nan(""), inf = HUGE_VAL;
+    auto alloc = [](int k, auto fill) { using V = decltype(fill); V* a = (V*)std::malloc(sizeof(V) * (k > 0 ? k : 1)); for (int i = 0; i < k; ++i) a[i] = fill; return a; };
+    rg->n = n; rg->m = m; rg->valid = 0; rg->min_rhs = inf; rg->min_dj = inf;
+    rg->cost_lo = alloc(n, nan); rg->cost_hi = alloc(n, nan); rg->cost_lo_at = alloc(n, (int32_t)-1); rg->cost_hi_at = alloc(n, (int32_t)-1);
+    rg->reduced_cost = alloc(n, nan);
+    rg->rhs_lo = alloc(m, nan); rg->rhs_hi = alloc(m, nan); rg->rhs_lo_at = alloc(m, (int32_t)-1); rg->rhs_hi_at = alloc(m, (int32_t)-1);
+    rg->dual = alloc(m, nan);
+}
+
+void RangeTableau(lpx_tableau* t, const RangingMap& map, RawRanging& raw)
+{
+    auto chk = [](int rc) { if (rc) { char b[1024]; lpx_last_error(b, sizeof b); throw LpxException(rc, std::string("liblpx: ") + b); } };
+    int R = 0, C = 0;
+    chk(lpx_tableau_shape(t, &R, &C, nullptr));
+    const int mx = R - 1, Cm = C - 1;
+    raw.ci.resize(Cm); raw.cd.resize(Cm); raw.cia.resize(Cm); raw.cda.resize(Cm); raw.dj.resize(Cm);
+    raw.ri.resize(mx); raw.rd.resize(mx); raw.ria.resize(mx); raw.rda.resize(mx); raw.basis.resize(mx);
+    raw.pa.clear(); raw.pb.clear();
+    raw.pair_of.assign(map.q->Constraints.size(), -1);
+    const int nk = (int)map.row_of.size();
+    for (int k = 0; k + 1 < nk; ++k)
+        if (map.row_of[k] == map.row_of[k + 1]) {
+            raw.pair_of[map.row_of[k]] = (int)raw.pa.size();
+            raw.pa.push_back(map.slack_col[k]); raw.pb.push_back(map.slack_col[k + 1]); ++k;
+        }
+    chk(lpx_tableau_ranging(t, 1e-9, raw.ci.data(), raw.cia.data(), raw.cd.data(), raw.cda.data(), raw.ri.data(), raw.ria.data(),
+                            raw.rd.data(), raw.rda.data(), &raw.min_rhs, &raw.min_dj));
+    const int K = (int)raw.pa.size();
+    raw.pi.resize(K); raw.pd.resize(K); raw.pia.resize(K); raw.pda.resize(K);
+    chk(lpx_tableau_ranging_pairs(t, 1e-9, K, raw.pa.data(), raw.pb.data(), raw.pi.data(), raw.pia.data(), raw.pd.data(), raw.pda.data()));
+    chk(lpx_tableau_basis(t, raw.basis.data()));
+    void* dT = nullptr; int ld = 0;
+    chk(lpx_tableau_device_ptr(t, &dT, &ld));
+    if (hipMemcpy(raw.dj.data(), (const double*)dT + (size_t)mx * ld, sizeof(double) * Cm, hipMemcpyDeviceToHost) != hipSuccess)
+        throw LpxException(LPX_EDEVICE, "ranging: objective row download failed");
+}
+
+void RangingToUser(const RangingMap& map, const RawRanging& raw, int status, lpx_ranging* rg)
+{
+    const double inf = HUGE_VAL;
+    rg->min_rhs = raw.min_rhs; rg->min_dj = raw.min_dj;
+    if (!(status == LPX_OPTIMAL && raw.min_rhs >= -1e-9 && raw.min_dj >= -1e-9)) return;
+    rg->valid = 1;
+    const LPProblem& q = *map.q;
+    const int n = (int)map.var_col.size(), mx = (int)map.row_of.size();
+    const double sigma = q.ObjectiveSense == Sense::Min ? -1.0 : 1.0;
+    const std::vector<double>& dj = raw.dj; const std::vector<int32_t>& basis = raw.basis;
+    std::vector<int> var_of_col(dj.size(), -1), row_of_var(n, -1);
+    for (int j = 0; j < n; ++j) var_of_col[map.var_col[j]] = j;
+    for (int k = 0; k < mx; ++k) if (basis[k] >= 0 && basis[k] < (int)dj.size() && var_of_col[basis[k]] >= 0) row_of_var[var_of_col[basis[k]]] = k;
+    for (int j = 0; j < n; ++j) {
+        const double c = q.C[j];
+        const int k = row_of_var[j], col = map.var_col[j];
+        if (k < 0) {
+            const double dp = dj[col] > 0 ? dj[col] : 0.0;
+            if (sigma > 0) { rg->cost_lo[j] = -inf; rg->cost_hi[j] = c + dp; rg->cost_hi_at[j] = col; }
+            else           { rg->cost_lo[j] = c - dp; rg->cost_hi[j] = inf; rg->cost_lo_at[j] = col; }
+            rg->reduced_cost[j] = -sigma * dj[col];
+        } else {
+            const double up = sigma > 0 ? raw.ri[k] : raw.rd[k], dn = sigma > 0 ? raw.rd[k] : raw.ri[k];
+            rg->cost_lo[j] = c - dn; rg->cost_hi[j] = c + up;
+            rg->cost_lo_at[j] = sigma > 0 ? raw.rda[k] : raw.ria[k];
+            rg->cost_hi_at[j] = sigma > 0 ? raw.ria[k] : raw.rda[k];
+            rg->reduced_cost[j] = 0.0;
+        }
+    }
+    auto leaving = [&](int32_t r) { return r >= 0 ? basis[r] : (int32_t)-1; };
+    for (int k = 0; k < mx; ++k) {
+        const int i = map.row_of[k];
+        const double b = q.Constraints[i].B;
+        if (raw.pair_of[i] >= 0) {
+            if (map.sign[k] < 0) continue;
+            const int h = raw.pair_of[i], s1 = raw.pa[h], s2 = raw.pb[h];
+            rg->rhs_lo[i] = b - raw.pd[h]; rg->rhs_hi[i] = b + raw.pi[h];
+            rg->rhs_lo_at[i] = leaving(raw.pda[h]); rg->rhs_hi_at[i] = leaving(raw.pia[h]);
+            rg->dual[i] = sigma * (dj[s1] - dj[s2]);
+        } else {
+            const int s = map.slack_col[k];
+            const bool pos = map.sign[k] > 0;
+            rg->rhs_lo[i] = b - (pos ? raw.cd[s] : raw.ci[s]); rg->rhs_hi[i] = b + (pos ? raw.ci[s] : raw.cd[s]);
+            rg->rhs_lo_at[i] = leaving(pos ? raw.cda[s] : raw.cia[s]); rg->rhs_hi_at[i] = leaving(pos ? raw.cia[s] : raw.cda[s]);
+            rg->dual[i] = sigma * map.sign[k] * dj[s];
+        }
+    }
+}
+
+}}  // namespace lpx::host
+
 extern "C" {
 
 void lpx_default_solve_opts(lpx_solve_opts* o)
@@ -267,14 +360,8 @@ int lpx_solve_ranging(const lpx_problem* p, const char* algorithm, const lpx_sol
     }
     if (int rc = ensure_device()) return rc;
     lpx_solve_opts d; if (!o) { lpx_default_solve_opts(&d); o = &d; }
-    const int n = p->n, m = p->m;
-    const double nan = std::nan(""), inf = HUGE_VAL;
-    auto alloc = [](int k, auto fill) { using V = decltype(fill); V* a = (V*)std::malloc(sizeof(V) * (k > 0 ? k : 1)); for (int i = 0; i < k; ++i) a[i] = fill; return a; };
-    rg->n = n; rg->m = m; rg->valid = 0; rg->min_rhs = inf; rg->min_dj = inf;
-    rg->cost_lo = alloc(n, nan); rg->cost_hi = alloc(n, nan); rg->cost_lo_at = alloc(n, (int32_t)-1); rg->cost_hi_at = alloc(n, (int32_t)-1);
-    rg->reduced_cost = alloc(n, nan);
-    rg->rhs_lo = alloc(m, nan); rg->rhs_hi = alloc(m, nan); rg->rhs_lo_at = alloc(m, (int32_t)-1); rg->rhs_hi_at = alloc(m, (int32_t)-1);
-    rg->dual = alloc(m, nan);
+    const int n = p->n;
+    RangingAlloc(rg, n, p->m);
     const int rc = guarded("lpx_solve_ranging", [&]() -> int {
         EngineOptions e = to_engine(o);
         UpdatePivot cb = to_callback(o);
@@ -282,70 +369,20 @@ int lpx_solve_ranging(const lpx_problem* p, const char* algorithm, const lpx_sol
         std::vector<int> row_of, sign;
         PreparedRows(q, dual, (o->dual_flags & LPX_DUAL_FIX_D1) != 0, row_of, sign);
         const int mx = (int)row_of.size();
-        // raw ranging of the final tableau (R = mx + 1, C = n + mx + 1)
-        std::vector<double> ci(n + mx), cd(n + mx), ri(mx), rd(mx), dj(n + mx), pi, pd;
-        std::vector<int32_t> cia(n + mx), cda(n + mx), ria(mx), rda(mx), basis(mx), pia, pda, pa, pb;
-        std::vector<int> pair_of(m, -1);
-        for (int k = 0; k + 1 < mx; ++k)
-            if (row_of[k] == row_of[k + 1]) { pair_of[row_of[k]] = (int)pa.size(); pa.push_back(n + k); pb.push_back(n + k + 1); ++k; }
-        int status = -1; double min_rhs = inf, min_dj = inf;
+        RangingMap map;
+        map.q = &q; map.row_of = row_of; map.sign = sign;
+        for (int j = 0; j < n; ++j) map.var_col.push_back(j);
+        for (int k = 0; k < mx; ++k) map.slack_col.push_back(n + k);
+        RawRanging raw;
+        int status = -1;
         e.on_final_tableau = [&](lpx_tableau* t, int st) {
             status = st;
             if (st != LPX_OPTIMAL) return;
-            auto chk = [](int rc) { if (rc) { char b[1024]; lpx_last_error(b, sizeof b); throw LpxException(rc, std::string("liblpx: ") + b); } };
-            chk(lpx_tableau_ranging(t, 1e-9, ci.data(), cia.data(), cd.data(), cda.data(), ri.data(), ria.data(), rd.data(), rda.data(),
-                                    &min_rhs, &min_dj));
-            const int K = (int)pa.size();
-            pi.resize(K); pd.resize(K); pia.resize(K); pda.resize(K);
-            chk(lpx_tableau_ranging_pairs(t, 1e-9, K, pa.data(), pb.data(), pi.data(), pia.data(), pd.data(), pda.data()));
-            chk(lpx_tableau_basis(t, basis.data()));
-            void* dT = nullptr; int ld = 0;
-            chk(lpx_tableau_device_ptr(t, &dT, &ld));
-            if (hipMemcpy(dj.data(), (const double*)dT + (size_t)mx * ld, sizeof(double) * (n + mx), hipMemcpyDeviceToHost) != hipSuccess)
-                throw LpxException(LPX_EDEVICE, "lpx_solve_ranging: objective row download failed");
+            RangeTableau(t, map, raw);
         };
         SimplexResult r = LPSolver(e).Solve(q, algorithm, cb);
         fill_result(out, r, p->n);
-        rg->min_rhs = min_rhs; rg->min_dj = min_dj;
-        if (!(status == LPX_OPTIMAL && min_rhs >= -1e-9 && min_dj >= -1e-9)) return 0;
-        rg->valid = 1;
-        const double sigma = q.ObjectiveSense == Sense::Min ? -1.0 : 1.0;
-        std::vector<int> row_of_var(n, -1);
-        for (int k = 0; k < mx; ++k) if (basis[k] >= 0 && basis[k] < n) row_of_var[basis[k]] = k;
-        for (int j = 0; j < n; ++j) {
-            const double c = q.C[j];
-            const int k = row_of_var[j];
-            if (k < 0) {
-                const double dp = dj[j] > 0 ? dj[j] : 0.0;
-                if (sigma > 0) { rg->cost_lo[j] = -inf; rg->cost_hi[j] = c + dp; rg->cost_hi_at[j] = j; }
-                else           { rg->cost_lo[j] = c - dp; rg->cost_hi[j] = inf; rg->cost_lo_at[j] = j; }
-                rg->reduced_cost[j] = -sigma * dj[j];
-            } else {
-                const double up = sigma > 0 ? ri[k] : rd[k], dn = sigma > 0 ? rd[k] : ri[k];
-                rg->cost_lo[j] = c - dn; rg->cost_hi[j] = c + up;
-                rg->cost_lo_at[j] = sigma > 0 ? rda[k] : ria[k];
-                rg->cost_hi_at[j] = sigma > 0 ? ria[k] : rda[k];
-                rg->reduced_cost[j] = 0.0;
-            }
-        }
-        auto leaving = [&](int32_t r) { return r >= 0 ? basis[r] : (int32_t)-1; };
-        for (int k = 0; k < mx; ++k) {
-            const int i = row_of[k];
-            const double b = q.Constraints[i].B;
-            if (pair_of[i] >= 0) {
-                if (sign[k] < 0) continue;
-                const int h = pair_of[i], s1 = pa[h], s2 = pb[h];
-                rg->rhs_lo[i] = b - pd[h]; rg->rhs_hi[i] = b + pi[h];
-                rg->rhs_lo_at[i] = leaving(pda[h]); rg->rhs_hi_at[i] = leaving(pia[h]);
-                rg->dual[i] = sigma * (dj[s1] - dj[s2]);
-            } else {
-                const int s = n + k;
-                const bool pos = sign[k] > 0;
-                rg->rhs_lo[i] = b - (pos ? cd[s] : ci[s]); rg->rhs_hi[i] = b + (pos ? ci[s] : cd[s]);
-                rg->rhs_lo_at[i] = leaving(pos ? cda[s] : cia[s]); rg->rhs_hi_at[i] = leaving(pos ? cia[s] : cda[s]);
-                rg->dual[i] = sigma * sign[k] * dj[s];
-            }
-        }
+        RangingToUser(map, raw, status, rg);
         return 0;
     });
     if (rc != 0) lpx_ranging_free(rg);

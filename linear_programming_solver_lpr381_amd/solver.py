@@ -285,6 +285,135 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         self.FinalTableau = res.Tableau
         return res
 
+    def Open(self, problem: LPProblem, **opts) -> "ModelSession":
+        """A warm post-optimal session on the device (lpx_session_open): the model is solved once, then ChangeRHS /
+        ChangeCost / AddActivity / AddConstraint each re-optimise from the current basis.  opts: extra_rows, extra_cols,
+        max_iter, batch, want_tableau (lpx_session_opts)."""
+        return ModelSession(problem, **opts)
+
+
+class ModelSession:         # lpx_session (include/lpx.h): warm re-optimisation after model edits
+    def __init__(self, problem: LPProblem, **opts):
+        L = lib()
+        o = _lib.SessionOpts()
+        L.lpx_default_session_opts(C.byref(o))
+        for k, v in opts.items():
+            if not hasattr(o, k):
+                raise TypeError(f"unknown session option {k!r}")
+            setattr(o, k, int(v))
+        self._want_T = bool(o.want_tableau)
+        self.Problem = LPProblem(ObjectiveSense=problem.ObjectiveSense, C=list(problem.C),
+                                 Constraints=[Constraint(A=list(k.A), Relation=k.Relation, B=k.B) for k in problem.Constraints])
+        ps, hold = _problem_struct(problem)
+        h = C.c_void_p()
+        r = _lib.Result()
+        rc = L.lpx_session_open(C.byref(ps), C.byref(o), C.byref(h), C.byref(r))
+        if rc != 0:
+            raise SolverException(rc, _lib.last_error())
+        self._h = h
+        self.Result = self._take(r)
+
+    def _take(self, r) -> SimplexResult:
+        n = r.n
+        has_T = bool(r.T) and self._want_T
+        T = _arr(r.T, r.R * r.C, np.float64).reshape(r.R, r.C) if has_T else None
+        try:
+            res = SimplexResult(
+                Report=(r.report or b"").decode(errors="replace"), Summary=(r.summary or b"").decode(errors="replace"),
+                OptimalValue=r.optimal_value, Solution=_arr(r.x, n, np.float64), Tableau=T,
+                Basis=_arr(r.basis, max(r.R - 1, 0), np.int32), VarNames=None, Status=r.status,
+                Trace=_arr(r.trace, 2 * r.n_pivots, np.int32).reshape(-1, 2), LpSolves=r.lp_solves, Nodes=r.nodes,
+                Aux=list(r.aux), Stats=r.stats.as_dict())
+        finally:
+            lib().lpx_result_free(C.byref(r))
+        return res
+
+    def _call(self, fn, *args) -> SimplexResult:
+        if self._h is None:
+            raise SolverException(_lib.EINVAL, "session is closed")
+        r = _lib.Result()
+        rc = fn(self._h, *args, C.byref(r))
+        if rc != 0:
+            raise SolverException(rc, _lib.last_error())
+        self.Result = self._take(r)
+        return self.Result
+
+    def ChangeRHS(self, i, value) -> SimplexResult:
+        """b_i = value (i and value may be sequences: one edit of several right-hand sides)."""
+        idx = np.atleast_1d(np.asarray(i, dtype=np.int32))
+        val = np.atleast_1d(np.asarray(value, dtype=np.float64))
+        res = self._call(lib().lpx_session_set_rhs, len(idx), idx.ctypes.data_as(_lib.ip), val.ctypes.data_as(_lib.dp))
+        for k, v in zip(idx, val):
+            self.Problem.Constraints[int(k)].B = float(v)
+        return res
+
+    def ChangeCost(self, j, value) -> SimplexResult:
+        """c_j = value (j and value may be sequences)."""
+        idx = np.atleast_1d(np.asarray(j, dtype=np.int32))
+        val = np.atleast_1d(np.asarray(value, dtype=np.float64))
+        res = self._call(lib().lpx_session_set_cost, len(idx), idx.ctypes.data_as(_lib.ip), val.ctypes.data_as(_lib.dp))
+        for k, v in zip(idx, val):
+            self.Problem.C[int(k)] = float(v)
+        return res
+
+    def AddActivity(self, c: float, column) -> SimplexResult:
+        """A new variable with cost c and constraint coefficients `column` (one per constraint)."""
+        col = np.ascontiguousarray(column, dtype=np.float64)
+        if col.shape != (len(self.Problem.Constraints),):
+            raise SolverException(_lib.EINVAL, "column needs one coefficient per constraint")
+        res = self._call(lib().lpx_session_add_variable, float(c), col.ctypes.data_as(_lib.dp))
+        self.Problem.C.append(float(c))
+        for k, a in zip(self.Problem.Constraints, col):
+            k.A.append(float(a))
+        return res
+
+    def AddConstraint(self, coeffs, rel, b: float) -> SimplexResult:
+        """A new constraint coeffs . x (rel) b over every current variable."""
+        a = np.ascontiguousarray(coeffs, dtype=np.float64)
+        if a.shape != (self.Problem.NumVars,):
+            raise SolverException(_lib.EINVAL, "coeffs needs one coefficient per variable")
+        res = self._call(lib().lpx_session_add_constraint, a.ctypes.data_as(_lib.dp), int(rel), float(b))
+        self.Problem.Constraints.append(Constraint(A=[float(v) for v in a], Relation=Rel(int(rel)), B=float(b)))
+        return res
+
+    def Ranging(self) -> RangingReport:
+        """Ranging of the current basis in user terms (lpx_session_ranging); *_at name columns of the session tableau."""
+        if self._h is None:
+            raise SolverException(_lib.EINVAL, "session is closed")
+        L = lib()
+        g = _lib.Ranging()
+        rc = L.lpx_session_ranging(self._h, C.byref(g))
+        if rc != 0:
+            raise SolverException(rc, _lib.last_error())
+        try:
+            return RangingReport(
+                valid=bool(g.valid),
+                cost_lo=_arr(g.cost_lo, g.n, np.float64), cost_hi=_arr(g.cost_hi, g.n, np.float64),
+                cost_lo_at=_arr(g.cost_lo_at, g.n, np.int32), cost_hi_at=_arr(g.cost_hi_at, g.n, np.int32),
+                reduced_cost=_arr(g.reduced_cost, g.n, np.float64),
+                rhs_lo=_arr(g.rhs_lo, g.m, np.float64), rhs_hi=_arr(g.rhs_hi, g.m, np.float64),
+                rhs_lo_at=_arr(g.rhs_lo_at, g.m, np.int32), rhs_hi_at=_arr(g.rhs_hi_at, g.m, np.int32),
+                dual=_arr(g.dual, g.m, np.float64), min_rhs=g.min_rhs, min_dj=g.min_dj)
+        finally:
+            L.lpx_ranging_free(C.byref(g))
+
+    def Close(self):
+        if self._h is not None:
+            lib().lpx_session_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.Close()
+
+    def __del__(self):
+        try:
+            self.Close()
+        except Exception:
+            pass
+
 
 def _algorithm_key(name: str) -> str:
     """The key lpx_solve matches algorithm names by (LPSolver.NormalizeAlgorithmKey, Models/LPSolver.cs:61-76): lower case,

@@ -163,6 +163,49 @@ class DeviceTableau:
         self.R, self.C = R.value, C_.value
         return src[: k.value].copy(), pcol[: p.value].copy()
 
+    def _shape(self):
+        R, C_ = C.c_int(), C.c_int()
+        check(lib().lpx_tableau_shape(self._h, C.byref(R), C.byref(C_), None))
+        self.R, self.C = R.value, C_.value
+
+    def rhs_update(self, cols, v):
+        """RHS column += the column combination sum_k v[k] T[:, cols[k]] (lpx_tableau_rhs_update, segment order of
+        include/lpx.h)."""
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        assert cols.shape == v.shape
+        check(lib().lpx_tableau_rhs_update(self._h, len(cols), cols.ctypes.data_as(ip), v.ctypes.data_as(dp)))
+
+    def objective_update(self, rows, w, dcols=(), dd=()):
+        """Objective row minus the sparse deltas dd at dcols, plus the row combination sum_k w[k] T[rows[k], :], basic
+        columns +0.0 (lpx_tableau_objective_update)."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        dcols = np.ascontiguousarray(dcols, dtype=np.int32)
+        dd = np.ascontiguousarray(dd, dtype=np.float64)
+        assert rows.shape == w.shape and dcols.shape == dd.shape
+        check(lib().lpx_tableau_objective_update(self._h, len(rows), rows.ctypes.data_as(ip), w.ctypes.data_as(dp),
+                                                 len(dcols), dcols.ctypes.data_as(ip), dd.ctypes.data_as(dp)))
+
+    def add_column(self, cols, v, obj: float):
+        """New column C-1 = the column combination with base (0, ..., 0, obj); the RHS moves right (lpx_tableau_add_column)."""
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        assert cols.shape == v.shape
+        check(lib().lpx_tableau_add_column(self._h, len(cols), cols.ctypes.data_as(ip), v.ctypes.data_as(dp), float(obj)))
+        self._shape()
+
+    def add_row(self, rows, w, base):
+        """New row m = base (C+1 entries, new shape) plus the row combination, basic columns +0.0; its slack becomes basic
+        (lpx_tableau_add_row)."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        base = np.ascontiguousarray(base, dtype=np.float64)
+        assert rows.shape == w.shape and base.shape == (self.C + 1,)
+        check(lib().lpx_tableau_add_row(self._h, len(rows), rows.ctypes.data_as(ip), w.ctypes.data_as(dp),
+                                        base.ctypes.data_as(dp)))
+        self._shape()
+
     def primal_run(self, opts: Optional[RunOpts] = None, cb: Optional[PivotCallback] = None,
                    **kw) -> Tuple[int, dict]:
         """PrimalSimplex loop (Models/PrimalSimplex.cs:92-124). Returns (status, stats)."""

@@ -1,7 +1,7 @@
 // lpx_cli -- Linux stand-in for the reference's WinForms host (Form1.cs), over the C ABI of liblpx.so only.
 //
 //   lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]
-//           [--export FILE] INPUT.txt
+//           [--set-rhs I=V]... [--set-cost J=V]... [--export FILE] INPUT.txt
 //
 // Does what Form1 does around the solvers: reads the model text (Import, Form1.cs:284-296), parses it with the LPParser
 // grammar (lpx_parse_text, Models/LPParser.cs:9-79), runs the algorithm chosen by its dropdown name (btnSolve_Click,
@@ -9,7 +9,9 @@
 // export file layout of BtnExport_Click (:308-315).  C only touches include/lpx.h: this is also the link test of the
 // boundary from a compiled host.  --ranging (Primal / Dual Simplex) solves through lpx_solve_ranging and prints the ranging
 // report of the final tableau after the summary.  --cuts-per-round / --cut-rounds (GMI Cutting Plane) solve through
-// lpx_solve_cuts with those options.  There is no CPU fallback: without a gfx950 device the solve fails with LPX_EDEVICE.
+// lpx_solve_cuts with those options.  --set-rhs I=V (b_I = V) and --set-cost J=V (c_J = V), 1-based and repeatable, are
+// applied in the order given after the solve, each as a warm edit of one lpx_session (re-optimised on the device from the
+// previous basis), and each re-solve's summary is printed.  There is no CPU fallback: without a gfx950 device the solve fails with LPX_EDEVICE.
 #include <cstdio>
 #include <cstdlib>
 #include <cctype>
@@ -17,6 +19,7 @@
 #include <fstream>
 #include <sstream>
 #include <string>
+#include <vector>
 
 #include "../include/lpx.h"
 
@@ -73,6 +76,8 @@ int main(int argc, char** argv)
     std::string algorithm = "Primal Simplex", input, exportPath;
     bool repaired = false, iterations = false, ranging = false, cut_set = false;
     lpx_cut_opts co; lpx_default_cut_opts(&co);
+    struct Edit { bool rhs; int index; double value; std::string text; };
+    std::vector<Edit> edits;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--algorithm" && i + 1 < argc) algorithm = argv[++i];
@@ -81,6 +86,20 @@ int main(int argc, char** argv)
         else if (a == "--ranging") ranging = true;
         else if (a == "--cuts-per-round" && i + 1 < argc) { co.cuts_per_round = std::atoi(argv[++i]); cut_set = true; }
         else if (a == "--cut-rounds" && i + 1 < argc) { co.max_rounds = std::atoi(argv[++i]); cut_set = true; }
+        else if ((a == "--set-rhs" || a == "--set-cost") && i + 1 < argc) {
+            const std::string v = argv[++i];
+            const size_t eq = v.find('=');
+            char* end = nullptr;
+            const long idx = eq == std::string::npos ? 0 : std::strtol(v.c_str(), &end, 10);
+            if (eq == std::string::npos || end != v.c_str() + eq || idx < 1) {
+                std::fprintf(stderr, "lpx_cli: %s takes INDEX=VALUE with a 1-based index, got '%s'\n", a.c_str(), v.c_str());
+                return 64;
+            }
+            const char* val = v.c_str() + eq + 1;
+            const double x = std::strtod(val, &end);
+            if (end == val || *end) { std::fprintf(stderr, "lpx_cli: bad value in %s %s\n", a.c_str(), v.c_str()); return 64; }
+            edits.push_back({a == "--set-rhs", (int)idx - 1, x, a + " " + v});
+        }
         else if (a == "--export" && i + 1 < argc) exportPath = argv[++i];
         else if (a == "--help" || a == "-h") {
             std::printf("usage: lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]\n"
@@ -90,7 +109,9 @@ int main(int argc, char** argv)
                         "        GMI Cutting Plane (gmi)\n"
                         "  --ranging: after the summary, the cost / RHS ranges, reduced costs and duals of the final tableau\n"
                         "             (Primal Simplex and Dual Simplex only)\n"
-                        "  --cuts-per-round K, --cut-rounds N: GMI Cutting Plane options (defaults 8 and 50)\n");
+                        "  --cuts-per-round K, --cut-rounds N: GMI Cutting Plane options (defaults 8 and 50)\n"
+                        "  --set-rhs I=V, --set-cost J=V: after the solve, b_I = V / c_J = V (1-based, repeatable), applied in order,\n"
+                        "             each re-optimised warm on the device from the previous basis; each re-solve's summary is printed\n");
             return 0;
         } else input = a;
     }
@@ -117,12 +138,42 @@ int main(int argc, char** argv)
     lpx_ranging rg;
     const int rc = ranging ? lpx_solve_ranging(&prob, algorithm.c_str(), &o, &r, &rg)
                  : cut_set ? lpx_solve_cuts(&prob, &o, &co, &r) : lpx_solve(&prob, algorithm.c_str(), &o, &r);
-    lpx_parsed_free(&p);
-    if (rc != 0) { lpx_last_error(err, sizeof err); std::fprintf(stderr, "%s\n", err); return rc == LPX_EDEVICE ? 69 : 70; }
+    if (rc != 0) { lpx_parsed_free(&p); lpx_last_error(err, sizeof err); std::fprintf(stderr, "%s\n", err); return rc == LPX_EDEVICE ? 69 : 70; }
     std::string shown = g_iterations;
     shown += "\n\nFinal Report:\n"; shown += r.report ? r.report : "";
     shown += "\n\nSummary:\n"; shown += r.summary ? r.summary : "";
     if (ranging) shown += ranging_table(rg);
+    if (!edits.empty()) {
+        lpx_session* ses = nullptr;
+        lpx_result sr;
+        int src = lpx_session_open(&prob, nullptr, &ses, &sr);
+        if (src == 0) lpx_result_free(&sr);
+        for (size_t e = 0; src == 0 && e < edits.size(); ++e) {
+            const Edit& ed = edits[e];
+            const int32_t idx = ed.index;
+            if ((ed.rhs && idx >= p.m) || (!ed.rhs && idx >= p.n)) {
+                std::fprintf(stderr, "lpx_cli: %s: index out of range\n", ed.text.c_str());
+                lpx_session_close(ses); lpx_parsed_free(&p); lpx_result_free(&r);
+                if (ranging) lpx_ranging_free(&rg);
+                return 64;
+            }
+            src = ed.rhs ? lpx_session_set_rhs(ses, 1, &idx, &ed.value, &sr) : lpx_session_set_cost(ses, 1, &idx, &ed.value, &sr);
+            if (src != 0) break;
+            char head[256];
+            std::snprintf(head, sizeof head, "\n\nRe-solve after %s (%s, %d pivots):\n", ed.text.c_str(), sr.aux[0] != 0 ? "warm" : "cold",
+                          sr.n_pivots);
+            shown += head; shown += sr.summary ? sr.summary : "";
+            lpx_result_free(&sr);
+        }
+        lpx_session_close(ses);
+        if (src != 0) {
+            lpx_last_error(err, sizeof err); std::fprintf(stderr, "%s\n", err);
+            lpx_parsed_free(&p); lpx_result_free(&r);
+            if (ranging) lpx_ranging_free(&rg);
+            return src == LPX_EDEVICE ? 69 : 70;
+        }
+    }
+    lpx_parsed_free(&p);
     std::fputs(shown.c_str(), stdout); std::fputc('\n', stdout);
     if (!exportPath.empty()) {
         std::ofstream w(exportPath);
