@@ -18,3 +18,9 @@ for name in ("Primal Simplex", "Revised Primal Simplex", "Branch and Bound"):
     x = None if res.Solution is None else [float(v) for v in res.Solution]
     print(f"{name}: status {res.Status}, z = {res.OptimalValue}, x = {x}")
     print(res.Summary.strip().splitlines()[-1] if res.Summary else "")
+
+# Bounds without rows (not in the reference): the same model with every x_j <= 2 kept beside the tableau by the
+# bounded-variable primal simplex; the tableau keeps the shape of the model without the bounds.
+res = solver.SolveBounded(problem, upper=2.0)
+print(f"Bounded Primal Simplex (x <= 2): status {res.Status}, z = {res.OptimalValue}, x = {[float(v) for v in res.Solution]}, "
+      f"at upper bound {[int(v) for v in res.AtUpper]}, events (to zero, to upper, flips) {res.BoundCounts}")

@@ -593,6 +593,82 @@ int  lpx_session_ranging(lpx_session* s, lpx_ranging* rg);
 int  lpx_session_shape(const lpx_session* s, int* n_vars, int* n_cons);
 void lpx_session_close(lpx_session* s);
 
+/* ---- bounded-variable primal simplex on the device (not in the reference; csrc/lpx_bounded.hip) --
+ * A primal simplex loop on the handle's live R x C window (m = R-1 rows, objective row last, RHS column last, Cm = C-1) in
+ * which every column j < Cm has an upper bound ub[j] in [0, +inf] kept BESIDE the tableau, with a one-byte state flip[j]:
+ * flip[j] = 1 means that column j currently stands for u_j - x_j.  Invariant: every nonbasic column is at 0 in its current
+ * representation; a basic value lies in [0, ub[basis[i]]].  A 0/1 variable costs no row and no slack column.
+ * All arithmetic is IEEE double, no FMA, true division.  One EVENT per iteration:
+ *   1. Entering column q: ChooseEntering exactly as lpx_primal_run (first index of the strict minimum of T[m, 0..Cm) below
+ *      -eps).  None: LPX_OPTIMAL.
+ *   2. Ratio scan, rows i = 0..m-1 in ascending order, a = T[i,q], b_i = T[i,Cm], p = basis[i]:
+ *        a >  eps:                     rho = b_i / a,                kind 0 (the basic variable goes to zero)
+ *        a < -eps and ub[p] < +inf:    rho = (ub[p] - b_i) / (-a),   kind 1 (the basic variable goes to its upper bound;
+ *                                      one subtraction, one negation, one division)
+ *        otherwise the row does not take part.
+ *      A row is accepted iff rho < best - ratio_tol (the sequential hysteresis of ChooseLeaving; best starts at +inf); the
+ *      last accepted row is r, with its kind.
+ *   3. Decision:
+ *        ub[q] < +inf and ub[q] <= best: BOUND FLIP (ties go to the flip; it moves no other column).  For every row i in
+ *          [0, R), the objective row included: T[i,Cm] = T[i,Cm] - ub[q] * T[i,q] (one multiply, one subtract), then
+ *          T[i,q] = -T[i,q]; flip[q] ^= 1.  Basis unchanged.  Trace entry (-1, q).
+ *        else no accepted row: LPX_UNBOUNDED.
+ *        else kind 1: ROW COMPLEMENT of row r first, p = basis[r]: T[r,j] = -T[r,j] for every j < Cm, j != p (T[r,p] stays,
+ *          it is the 1.0 of a basic column); T[r,Cm] = ub[p] - T[r,Cm]; flip[p] ^= 1.  Then the ordinary pivot on (r, q).
+ *          Trace entry (-2 - r, q).
+ *        else kind 0: the ordinary pivot on (r, q).  Trace entry (r, q).
+ *      The ordinary pivot is Pivot (Models/PrimalSimplex.cs:245-257): row r divided by the pivot, every other row
+ *      T[i,:] -= T[i,q] * T[r,:] with separate multiply and subtract, basis[r] = q.
+ *   4. Before step 1, events done >= max_iter (flips and pivots alike) is LPX_ITER_LIMIT, tested where lpx_primal_run tests
+ *      its pivot count.  The per-pivot callback receives (iter, row, col) with the trace's encoding.
+ * With every ub = +inf the loop is lpx_primal_run bit for bit (same trace, same tableau).  The result depends on nothing but
+ * the tableau, basis, ub and the options: not on the batch length, on graph replay, or on how many flips share a launch.
+ * Tableaux of any m are accepted: the ratios of a tableau with more than 4096 rows go through global scratch instead of LDS.
+ *
+ * lpx_tableau_set_bounds: ncols must be the live C-1; every ub[j] in [0, +inf]; clears every flip.  ub == NULL with
+ *   ncols == 0 removes the bounds.  Bounds belong to the live shape they were set for.
+ *   lpx_tableau_upload leaves ub and flip as they are (a host may download a tableau with its flags and bring it back): set the
+ *   bounds again after uploading another model.
+ * lpx_tableau_bound_flags: flip[C-1] (all zero for a handle without bounds).
+ * lpx_bounded_run: options eps, ratio_tol, max_iter, batch, use_graph, profile as lpx_primal_run reads them (profile runs
+ *   eager launches; update_ms_sum is not collected, a launch here does not map to one update); resident = 1 is LPX_EINVAL (there
+ *   is no resident form).  A handle without bounds runs with every ub = +inf.  If the live C has changed since
+ *   lpx_tableau_set_bounds the run is LPX_EINVAL.  lpx_stats.pivots counts kind-0 and kind-1 pivots; lpx_tableau_trace
+ *   returns the events.  lpx_bounded_counts: events of the last run: kind 0, kind 1, flips.
+ * lpx_tableau_snapshot / lpx_tableau_restore carry ub and flip with the tableau; restoring a snapshot taken before the handle
+ *   had bounds clears every flip.  lpx_tableau_ranging, lpx_tableau_gmi_round and the post-optimal edits on a handle with
+ *   flips set see the internal representation (flipped columns stand for u_j - x_j); they are not bound-aware.
+ * lpx_tableau_bounded_solution: v_j = RHS of the row where j is basic, else +0.0; x[j] = flip[j] ? ub[j] - v_j : v_j (one
+ *   subtraction); *z = T[m,Cm]; at_upper[j] = 1 iff j is nonbasic and flipped.  nvars <= C-1.
+ * Argument errors return LPX_EINVAL before any device check, with the handle untouched: a NULL handle, ncols not the live
+ * C-1, a negative or NaN bound, R < 2, resident = 1.  No device: LPX_EDEVICE. */
+int lpx_tableau_set_bounds(lpx_tableau* t, int ncols, const double* ub);
+int lpx_tableau_bound_flags(lpx_tableau* t, uint8_t* flip /* [C-1] */);
+int lpx_bounded_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, void* user, lpx_stats* st);
+int lpx_bounded_counts(lpx_tableau* t, int64_t counts[3]);
+int lpx_tableau_bounded_solution(lpx_tableau* t, int nvars, double* x, double* z, uint8_t* at_upper /* [nvars] or NULL */);
+
+/* The model level: lower[j] <= x_j <= upper[j] without a row per bound.  Preparation as PrimalSimplex.Solve prepares (Min
+ * negates c; a >= row is LPX_E_GE_PRESENT; = rows become the <= pair), then the shift x = l + x': b'_i = b_i - sum_j A_ij l_j
+ * with j ascending, one multiply and one subtract per nonzero l_j; u'_j = u_j - l_j; any b'_i < -1e-9 is LPX_E_NEG_RHS with
+ * the reference's message.  lower[j] must be finite and upper[j] must be +inf or >= lower[j]: a NaN, an infinite lower bound
+ * or upper[j] < lower[j] is LPX_EINVAL (checked first, before any device check).  Slack columns get +inf.
+ * out: x in the user's variables (l_j added back), optimal_value in the user's sense including the constant c.l, T / basis
+ * the final internal tableau, trace the events, stats, aux = {kind-0 pivots, kind-1 pivots, flips, constant c.l}, report and
+ * summary in the Primal Simplex layout with one added line naming the variables at their upper bound.  info (or NULL):
+ * ncols = C-1, flip[ncols], ub[ncols] (shifted), n, lower[n]; free with lpx_bounded_info_free.  With lower == upper == NULL
+ * the result equals lpx_solve(p, "Primal Simplex") in trace, basis, tableau bits, x and, for Max models, optimal_value.
+ * lpx_solve(p, "Bounded Primal Simplex", ...) is this call without bounds. */
+typedef struct lpx_bounded_info {
+    int ncols, n;
+    uint8_t* flip;         /* [ncols] */
+    double* ub;            /* [ncols] shifted upper bounds, +inf for slacks */
+    double* lower;         /* [n] */
+} lpx_bounded_info;
+int  lpx_solve_bounded(const lpx_problem* p, const double* lower /* [n] or NULL = 0 */, const double* upper /* [n] or NULL = +inf */,
+                       const lpx_solve_opts* o, lpx_result* out, lpx_bounded_info* info /* or NULL */);
+void lpx_bounded_info_free(lpx_bounded_info* info);
+
 #ifdef __cplusplus
 }
 #endif

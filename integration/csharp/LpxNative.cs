@@ -84,6 +84,15 @@ namespace Linear_Programming_Solver.Native
         public double away, coef_eps, max_dynamism, purge_tol, int_tol;
     }
 
+    [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct LpxBoundedInfo          // lpx_bounded_info  (lpx_solve_bounded; free with lpx_bounded_info_free)
+    {
+        public int ncols, n;
+        public byte* flip;
+        public double* ub;
+        public double* lower;
+    }
+
     public static unsafe class Lpx
     {
         const string Lib = "lpx";                // liblpx.so (Linux) next to the executable / on LD_LIBRARY_PATH
@@ -188,6 +197,22 @@ namespace Linear_Programming_Solver.Native
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_session_shape(IntPtr s, out int nVars, out int nCons);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern void lpx_session_close(IntPtr s);
+
+        // ---- bounded-variable primal simplex (not in the reference), include/lpx.h: bounds beside the tableau, no bound rows ----
+        // lower / upper: [n] or null (0 / +inf); info: receives flip / ub / lower of the final tableau
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_bounded(ref LpxProblem p, double* lower, double* upper, ref LpxSolveOpts o,
+                                                   out LpxResult result, out LpxBoundedInfo info);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern void lpx_bounded_info_free(ref LpxBoundedInfo info);
+        // ub: [C-1], +inf = unbounded; null with ncols = 0 removes the bounds
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int lpx_tableau_set_bounds(IntPtr t, int ncols, double* ub);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int lpx_tableau_bound_flags(IntPtr t, byte* flip);
+        // opts: an lpx_run_opts or IntPtr.Zero for the defaults; trace rows: (r, q) pivot, (-2 - r, q) pivot to the upper bound, (-1, q) flip
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_bounded_run(IntPtr t, IntPtr opts, LpxPivotCb cb, IntPtr user, out LpxStats st);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int lpx_bounded_counts(IntPtr t, long* counts);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_tableau_bounded_solution(IntPtr t, int nvars, double* x, out double z, byte* atUpper);
 
         public static string LastError()
         {

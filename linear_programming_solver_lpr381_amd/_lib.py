@@ -99,6 +99,11 @@ class SessionOpts(C.Structure):
                 ("want_tableau", C.c_int)]
 
 
+class BoundedInfo(C.Structure):
+    """lpx_bounded_info (include/lpx.h): bound states of lpx_solve_bounded's final tableau (freed by lpx_bounded_info_free)."""
+    _fields_ = [("ncols", C.c_int), ("n", C.c_int), ("flip", C.POINTER(C.c_uint8)), ("ub", dp), ("lower", dp)]
+
+
 class Parsed(C.Structure):
     _fields_ = [("sense", C.c_int), ("n", C.c_int), ("m", C.c_int), ("c", dp), ("A", dp), ("rel", ip),
                 ("b", dp), ("ragged", C.c_int)]
@@ -247,6 +252,14 @@ def lib() -> C.CDLL:
     L.lpx_session_shape.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lpx_session_close.argtypes = [vp]
     L.lpx_session_close.restype = None
+    L.lpx_tableau_set_bounds.argtypes = [vp, C.c_int, dp]
+    L.lpx_tableau_bound_flags.argtypes = [vp, u8p]
+    L.lpx_bounded_run.argtypes = [vp, C.POINTER(RunOpts), PIVOT_CB, vp, C.POINTER(Stats)]
+    L.lpx_bounded_counts.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.lpx_tableau_bounded_solution.argtypes = [vp, C.c_int, dp, dp, u8p]
+    L.lpx_solve_bounded.argtypes = [C.POINTER(Problem), dp, dp, C.POINTER(SolveOpts), C.POINTER(Result), C.POINTER(BoundedInfo)]
+    L.lpx_bounded_info_free.argtypes = [C.POINTER(BoundedInfo)]
+    L.lpx_bounded_info_free.restype = None
     L.lpx_parse_text.argtypes = [C.c_char_p, C.POINTER(Parsed)]
     L.lpx_parsed_free.argtypes = [C.POINTER(Parsed)]
     L.lpx_parsed_free.restype = None

@@ -1,0 +1,135 @@
+// host/bounded.cpp -- the bounded-variable primal simplex at the model level (lpx_solve_bounded, include/lpx.h): preparation as
+// PrimalSimplex.Solve (Models/PrimalSimplex.cs:57-90), lower bounds shifted away on the host, upper bounds handed to the device
+// loop (lpx_bounded_run) beside the tableau instead of as rows.
+#include "model.h"
+
+#include <cmath>
+#include <cstring>
+
+namespace lpx { namespace host {
+
+namespace {
+
+[[noreturn]] void throw_lib(int rc)
+{
+    char buf[1024];
+    lpx_last_error(buf, sizeof(buf));
+    throw LpxException(rc, std::string("liblpx: ") + buf);
+}
+
+struct BoundedHandle {
+    lpx_tableau* h = nullptr; int R, C;
+    BoundedHandle(int R_, int C_) : R(R_), C(C_) { h = acquire_exact_handle(R, C); }
+    // the handle goes back to a cache shared with the other solvers: without its bounds
+    ~BoundedHandle() { if (h) lpx_tableau_set_bounds(h, 0, nullptr); release_exact_handle(h, R, C); }
+    BoundedHandle(const BoundedHandle&) = delete;
+};
+
+struct EventCtx { UpdatePivot cb; const std::vector<std::string>* names; };
+
+void bounded_event(void* user, int iter, int row, int col)
+{
+    EventCtx* c = static_cast<EventCtx*>(user);
+    if (!c->cb) return;
+    const std::string head = "BOUNDED TABLEAU Iteration " + std::to_string(iter) + ": ";
+    const std::string& v = (*c->names)[col];
+    if (row == -1) c->cb(head + "bound flip of " + v + "\n", nullptr);
+    else if (row < -1) c->cb(head + "leaving row " + std::to_string(-2 - row) + " at its upper bound, entering " + v + "\n", nullptr);
+    else c->cb(head + "leaving row " + std::to_string(row) + ", entering " + v + "\n", nullptr);
+}
+
+}  // namespace
+
+SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
+                           const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info)
+{
+    const int n = original.NumVars();
+    if ((!lower.empty() && (int)lower.size() != n) || (!upper.empty() && (int)upper.size() != n))
+        throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: lower / upper need one entry per variable");
+    for (int j = 0; j < n; ++j) {
+        const double l = lower.empty() ? 0.0 : lower[j], u = upper.empty() ? 1.0 / 0.0 : upper[j];
+        if (!std::isfinite(l)) throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: lower bound of x" + std::to_string(j + 1) + " is not finite");
+        if (!(u >= l)) throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: upper bound of x" + std::to_string(j + 1) + " is below its lower bound or NaN");
+    }
+    LPProblem model = original.Clone();
+    if (model.ObjectiveSense == Sense::Min) for (double& c : model.C) c = -c;          // :62-63
+    for (const Constraint& cons : model.Constraints)
+        if ((int)cons.A.size() < n) throw LpxException(LPX_EINVAL, "Index was outside the bounds of the array.");
+    // x = l + x': b' = b - A l, one multiply and one subtract per nonzero l_j, j ascending
+    if (!lower.empty())
+        for (Constraint& cons : model.Constraints)
+            for (int j = 0; j < n; ++j)
+                if (lower[j] != 0.0) { const double prod = cons.A[j] * lower[j]; cons.B = cons.B - prod; }
+    for (const Constraint& cons : model.Constraints) {                                  // :66-77
+        if (cons.Relation == Rel::GE)
+            throw LpxException(LPX_E_GE_PRESENT, "Constraint contains '>=' sign. The Primal Simplex method cannot handle this. Please try the Dual Simplex algorithm instead.");
+        if (cons.B < -1e-9)
+            throw LpxException(LPX_E_NEG_RHS, "Constraint has a negative RHS value. The Primal Simplex method cannot handle this. Please try the Dual Simplex algorithm instead.");
+    }
+    double constant = 0.0;          // c.l in the user's sense
+    bool shifted = false;
+    if (!lower.empty())
+        for (int j = 0; j < n; ++j)
+            if (lower[j] != 0.0) { const double prod = original.C[j] * lower[j]; constant = constant + prod; shifted = true; }
+
+    LPProblem tableauModel = ExpandEqualitiesToInequalities(model);                     // :80
+    std::string report = opt.quiet ? std::string() : AppendCanonicalForm(tableauModel); // :82
+    std::vector<double> T; int R, C; std::vector<int32_t> basis; std::vector<std::string> varNames;
+    BuildTableauPrimal(tableauModel, T, R, C, basis, varNames);                         // :85
+    if (R < 2) throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: the model has no constraints");
+    if (updatePivot) updatePivot(AppendTableau("TABLEAU Iteration", T.data(), R, C, basis, varNames, 0), nullptr);
+    const int Cm = C - 1;
+    std::vector<double> ub((size_t)Cm, 1.0 / 0.0);
+    const bool bounded = !upper.empty() || !lower.empty();
+    if (!upper.empty()) for (int j = 0; j < n; ++j) ub[j] = std::isinf(upper[j]) ? upper[j] : upper[j] - (lower.empty() ? 0.0 : lower[j]);
+
+    SimplexResult res;
+    BoundedHandle th(R, C);
+    int rc = lpx_tableau_upload(th.h, T.data(), basis.data());
+    if (rc) throw_lib(rc);
+    if (bounded) { rc = lpx_tableau_set_bounds(th.h, Cm, ub.data()); if (rc) throw_lib(rc); }
+    lpx_run_opts o; lpx_default_opts(&o, 0);
+    o.max_iter = opt.max_iter;
+    o.batch = opt.batch;
+    EventCtx ctx{updatePivot, &varNames};
+    const int st = lpx_bounded_run(th.h, &o, updatePivot ? bounded_event : nullptr, &ctx, &res.Stats);
+    if (st < 0) throw_lib(st);
+    if (st == LPX_ITER_LIMIT) throw LpxException(LPX_ITER_LIMIT, "Iteration limit exceeded.");      // :95-96
+    int nev = 0;
+    rc = lpx_tableau_trace(th.h, nullptr, 0, &nev); if (rc) throw_lib(rc);
+    res.Trace.resize(2 * (size_t)(nev > 0 ? nev : 1));
+    rc = lpx_tableau_trace(th.h, res.Trace.data(), nev, &nev); if (rc) throw_lib(rc);
+    res.Trace.resize(2 * (size_t)nev);
+    rc = lpx_tableau_download(th.h, T.data(), basis.data());
+    if (rc) throw_lib(rc);
+    std::vector<double> x((size_t)n, 0.0); double z = 0.0;
+    std::vector<uint8_t> at_upper((size_t)n, 0), flip((size_t)Cm, 0);
+    rc = lpx_tableau_bounded_solution(th.h, n, x.data(), &z, at_upper.data()); if (rc) throw_lib(rc);
+    rc = lpx_tableau_bound_flags(th.h, flip.data()); if (rc) throw_lib(rc);
+    int64_t counts[3] = {0, 0, 0};
+    lpx_bounded_counts(th.h, counts);
+    if (opt.on_final_tableau) opt.on_final_tableau(th.h, st);
+
+    if (!lower.empty()) for (int j = 0; j < n; ++j) x[j] = x[j] + lower[j];
+    // the tableau maximises; the user's optimum is -z for a Min model, plus the constant the shift took out
+    double value = z;
+    if (shifted || original.ObjectiveSense == Sense::Min) {
+        value = original.ObjectiveSense == Sense::Min ? -z : z;
+        if (shifted) value = value + constant;
+    }
+    if (st == LPX_UNBOUNDED) report += "UNBOUNDED\n";                                   // :104
+    FinalizeText(report, res.Summary, x, value, st);
+    std::string at = "  at upper bound:";
+    bool any = false;
+    for (int j = 0; j < n; ++j) if (at_upper[j]) { at += std::string(any ? "," : "") + " x" + std::to_string(j + 1); any = true; }
+    if (!any) at += " none";
+    report += at + "\n";
+    res.Summary += at.substr(2) + "\n";
+    res.Report = report; res.OptimalValue = value; res.Solution = x; res.HasSolution = true; res.Status = st;
+    res.Tableau = std::move(T); res.R = R; res.C = C; res.Basis = std::move(basis); res.VarNames = std::move(varNames);
+    res.Aux = {(double)counts[0], (double)counts[1], (double)counts[2], constant};
+    if (info) { info->flip = flip; info->ub = ub; info->lower = lower.empty() ? std::vector<double>((size_t)n, 0.0) : lower; }
+    return res;
+}
+
+}}  // namespace lpx::host

@@ -208,6 +208,12 @@ private:
     EngineOptions opt;
 };
 
+// Bounded-variable primal simplex at the model level (lpx_solve_bounded, include/lpx.h; bounded.cpp): lower / upper are empty
+// (0 / +inf) or hold one entry per variable.
+struct BoundedInfo { std::vector<uint8_t> flip; std::vector<double> ub, lower; };
+SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
+                           const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info);
+
 // LPParser.ParseFromText, Models/LPParser.cs:9-79.  Throws LpxException(LPX_E_PARSE, message).
 LPProblem ParseFromText(const std::string& input);
 
@@ -227,6 +233,8 @@ std::string BuildIterationBlock(int iter, const std::vector<int32_t>& Bidx, cons
                                 int entering, const std::vector<double>* d, double bestTheta, double eps);
 
 // helpers shared by the solver mirrors (solvers.cpp)
+// FinalizeReport, Models/PrimalSimplex.cs:130-159: status line, x, z* appended to the report and the summary
+void FinalizeText(std::string& report, std::string& summary, const std::vector<double>& x, double z, int status);
 void BuildTableauPrimal(const LPProblem& expanded, std::vector<double>& T, int& R, int& C,
                         std::vector<int32_t>& basis, std::vector<std::string>& varNames);
 LPProblem ExpandEqualitiesToInequalities(const LPProblem& model);

@@ -153,6 +153,11 @@ void check_row_lengths(const LPProblem& p)
 
 }  // namespace
 
+void FinalizeText(std::string& report, std::string& summary, const std::vector<double>& x, double z, int status)
+{
+    finalize_text(report, summary, x, z, status_text(status));
+}
+
 // ExpandEqualitiesToInequalities, Models/PrimalSimplex.cs:161-177
 LPProblem ExpandEqualitiesToInequalities(const LPProblem& model)
 {
@@ -493,6 +498,17 @@ std::string LPSolver::NormalizeAlgorithmKey(const std::string& algorithm)
     return out;
 }
 
+namespace {
+// "Bounded Primal Simplex" through the dispatcher: the bounded loop with no bound given (lpx_solve_bounded carries them)
+class BoundedPrimalNoBounds : public ILPAlgorithm {
+public:
+    explicit BoundedPrimalNoBounds(const EngineOptions& o) : opt(o) {}
+    SimplexResult Solve(const LPProblem& problem, UpdatePivot updatePivot) override { return SolveBounded(problem, {}, {}, opt, updatePivot, nullptr); }
+private:
+    EngineOptions opt;
+};
+}  // namespace
+
 SimplexResult LPSolver::Solve(const LPProblem& problem, const std::string& algorithm, UpdatePivot updatePivot)
 {
     const std::string key = NormalizeAlgorithmKey(algorithm);
@@ -500,6 +516,8 @@ SimplexResult LPSolver::Solve(const LPProblem& problem, const std::string& algor
     if (key == "primal simplex" || key == "primal") algo.reset(new PrimalSimplex(opt));
     else if (key == "revised primal simplex" || key == "revised primal") algo.reset(new RevisedPrimalSimplex(opt));
     else if (key == "dual simplex" || key == "dual") algo.reset(new DualSimplex(opt));
+    // not in the reference: the bounded-variable primal loop without bounds (lpx_solve_bounded carries them)
+    else if (key == "bounded primal simplex") algo.reset(new BoundedPrimalNoBounds(opt));
     else if (key == "branch and bound simplex" || key == "branch and bound" || key == "bnb") algo.reset(new BranchAndBound(opt));
     // not reachable through the reference's LPSolver (it is never instantiated there);
     // offered under its menu name so the knapsack path has an entry point

@@ -25,7 +25,7 @@ struct DevState {
     int pad[4];          // pad[0]: revised path's Nidx order counter; pad[1]: resident loop abort flag
 };
 
-enum { MODE_PRIMAL = 0, MODE_DUAL = 1, MODE_FORCED = 2 };
+enum { MODE_PRIMAL = 0, MODE_DUAL = 1, MODE_FORCED = 2, MODE_BOUNDED = 3 };
 
 struct SelParams {
     double* T; int ld; int R; int C;    // R, C: CAPACITY of the handle (grid sizing)
@@ -51,6 +51,14 @@ struct SelParams {
     double* ws;          // [max(R,C)] global scratch for ratios when they do not fit LDS
     int rcap;            // doubles of dynamic LDS available for ratios (0 = use ws)
 };
+
+// bounded-variable primal loop (lpx_bounded.hip): the select parameters plus the bounds kept beside the tableau
+struct BndParams {
+    SelParams P;
+    const double* ub;    // [C-1 capacity] upper bound of every column, +inf = none
+    uint8_t* flip;       // [C-1 capacity] 1 = the column stands for u_j - x_j
+};
+hipError_t launch_bounded_select(const BndParams& b, hipStream_t s);
 
 // launchers (lpx_kernels.hip)
 hipError_t launch_select(const SelParams& p, hipStream_t s);       // gather-based (dual path)

@@ -277,6 +277,44 @@ int lpx_solve(const lpx_problem* p, const char* algorithm, const lpx_solve_opts*
     }
 }
 
+int lpx_solve_bounded(const lpx_problem* p, const double* lower, const double* upper, const lpx_solve_opts* o, lpx_result* out,
+                      lpx_bounded_info* info)
+{
+    if (!p || !out) { set_error("lpx_solve_bounded: null argument"); return LPX_EINVAL; }
+    std::memset(out, 0, sizeof(*out));
+    if (info) std::memset(info, 0, sizeof(*info));
+    lpx_solve_opts d; if (!o) { lpx_default_solve_opts(&d); o = &d; }
+    try {
+        EngineOptions e = to_engine(o);
+        UpdatePivot cb = to_callback(o);
+        LPProblem q = to_problem(p);
+        std::vector<double> lo, up;
+        if (lower) lo.assign(lower, lower + p->n);
+        if (upper) up.assign(upper, upper + p->n);
+        BoundedInfo bi;
+        SimplexResult r = SolveBounded(q, lo, up, e, cb, &bi);
+        fill_result(out, r, p->n);
+        if (info) {
+            info->ncols = (int)bi.ub.size(); info->n = p->n;
+            info->flip = dup_vec(bi.flip); info->ub = dup_vec(bi.ub); info->lower = dup_vec(bi.lower);
+        }
+        return 0;
+    } catch (const LpxException& ex) {
+        set_error(ex.what());
+        return ex.code;
+    } catch (const std::exception& ex) {
+        set_error(std::string("lpx_solve_bounded: ") + ex.what());
+        return LPX_EINVAL;
+    }
+}
+
+void lpx_bounded_info_free(lpx_bounded_info* info)
+{
+    if (!info) return;
+    std::free(info->flip); std::free(info->ub); std::free(info->lower);
+    std::memset(info, 0, sizeof(*info));
+}
+
 int lpx_sensitivity_range_report(const lpx_problem* p, const double* T, int R, int C, const int32_t* basis,
                                  const char* target, char* buf, int len)
 {

@@ -61,6 +61,11 @@ struct lpx_tableau {
     bool suspended2 = false;        // ... by the two-launch group kernels (it must continue there: no pending pivot, state in *hst)
     bool fsuspended = false; int frec_cur = 0;   // fused group run left unfinished: its records (latest: index frec_cur) are in place
     char* rgws = nullptr; size_t rgws_bytes = 0;  // lpx_tableau_ranging's partial slabs and outputs / the cut round's plan, on first use
+    // bounded-variable primal loop (lpx_bounded.hip): upper bounds and flip states beside the tableau, on first use
+    double* ub = nullptr; uint8_t* flip = nullptr;          // [Ccap] each
+    bool bounds_set = false; int bounds_C = 0;              // live C the bounds were set for
+    double* snapUb = nullptr; uint8_t* snapFlip = nullptr; bool snap_bounds = false; int snap_bounds_C = 0;
+    int64_t bcounts[3] = {0, 0, 0};                         // events of the last lpx_bounded_run: kind 0, kind 1, flips
 };
 
 void lpx::tableau_view(lpx_tableau* t, TableauView* v)
@@ -212,6 +217,7 @@ void lpx_tableau_destroy(lpx_tableau* t)
     hipFree(t->frows); hipFree(t->fcols); hipFree(t->fchosen); hipFree(t->cutbuf);
     hipFree(t->fT); hipFree(t->fslab); hipFree(t->dring);
     hipFree(t->rgws);
+    hipFree(t->ub); hipFree(t->flip); hipFree(t->snapUb); hipFree(t->snapFlip);
     hipFree(t->xr); hipFree(t->xp); hipFree(t->xgen); hipFree(t->xbasis); hipFree(t->xT); hipFree(t->xc); hipFree(t->xq);
     if (t->hslab) hipHostFree(t->hslab);
     if (t->cutbuf_h) hipHostFree(t->cutbuf_h);
@@ -263,6 +269,15 @@ int lpx_tableau_snapshot(lpx_tableau* t)
     LPX_HIP_TRY(hipMemcpyAsync(t->snapT, t->T, tb, hipMemcpyDeviceToDevice, t->stream));
     LPX_HIP_TRY(hipMemcpyAsync(t->snapBasis, t->basis, sizeof(int32_t) * (t->R > 1 ? t->R - 1 : 1),
                                hipMemcpyDeviceToDevice, t->stream));
+    t->snap_bounds = t->bounds_set; t->snap_bounds_C = t->bounds_C;
+    if (t->bounds_set) {        // the bounds and the flip states belong to the tableau they describe
+        if (!t->snapUb) {
+            LPX_HIP_TRY(hipMalloc((void**)&t->snapUb, sizeof(double) * t->Ccap));
+            LPX_HIP_TRY(hipMalloc((void**)&t->snapFlip, t->Ccap));
+        }
+        LPX_HIP_TRY(hipMemcpyAsync(t->snapUb, t->ub, sizeof(double) * t->Ccap, hipMemcpyDeviceToDevice, t->stream));
+        LPX_HIP_TRY(hipMemcpyAsync(t->snapFlip, t->flip, t->Ccap, hipMemcpyDeviceToDevice, t->stream));
+    }
     LPX_HIP_TRY(hipStreamSynchronize(t->stream));
     return 0;
 }
@@ -275,6 +290,13 @@ int lpx_tableau_restore(lpx_tableau* t)
     LPX_HIP_TRY(hipMemcpyAsync(t->T, t->snapT, tb, hipMemcpyDeviceToDevice, t->stream));
     LPX_HIP_TRY(hipMemcpyAsync(t->basis, t->snapBasis, sizeof(int32_t) * (t->R > 1 ? t->R - 1 : 1),
                                hipMemcpyDeviceToDevice, t->stream));
+    if (t->snap_bounds) {
+        LPX_HIP_TRY(hipMemcpyAsync(t->ub, t->snapUb, sizeof(double) * t->Ccap, hipMemcpyDeviceToDevice, t->stream));
+        LPX_HIP_TRY(hipMemcpyAsync(t->flip, t->snapFlip, t->Ccap, hipMemcpyDeviceToDevice, t->stream));
+        t->bounds_set = true; t->bounds_C = t->snap_bounds_C;
+    } else if (t->bounds_set) {     // snapshotted before it had bounds: that tableau had no column flipped
+        LPX_HIP_TRY(hipMemsetAsync(t->flip, 0, t->Ccap, t->stream));
+    }
     LPX_HIP_TRY(hipMemsetAsync(t->st, 0, sizeof(DevState), t->stream));
     LPX_HIP_TRY(hipStreamSynchronize(t->stream));
     return 0;
@@ -1280,6 +1302,136 @@ static int multi_run_batched(lpx_tableau** ts, const int* dual, int count, const
     }
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------
+// bounded-variable primal simplex (include/lpx.h; select kernel in lpx_bounded.hip, update = lpx_update)
+// ---------------------------------------------------------------------------------------------------
+namespace {
+
+int bound_buffers(lpx_tableau* t)
+{
+    if (t->ub) return 0;
+    LPX_HIP_TRY(hipMalloc((void**)&t->ub, sizeof(double) * t->Ccap));
+    LPX_HIP_TRY(hipMalloc((void**)&t->flip, t->Ccap));
+    return 0;
+}
+
+// every live column unbounded and unflipped (a handle without bounds)
+int bounds_fill_inf(lpx_tableau* t)
+{
+    std::vector<double> inf((size_t)t->Ccap, 1.0 / 0.0);
+    LPX_HIP_TRY(hipMemcpyAsync(t->ub, inf.data(), sizeof(double) * t->Ccap, hipMemcpyHostToDevice, t->stream));
+    LPX_HIP_TRY(hipMemsetAsync(t->flip, 0, t->Ccap, t->stream));
+    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lpx_tableau_set_bounds(lpx_tableau* t, int ncols, const double* ub)
+{
+    if (!t) { set_error("lpx_tableau_set_bounds: null handle"); return LPX_EINVAL; }
+    if (!ub && ncols == 0) { t->bounds_set = false; t->bounds_C = 0; return 0; }
+    if (!ub || ncols != t->C - 1) { set_error("lpx_tableau_set_bounds: ncols must be the live C - 1 and ub non-null"); return LPX_EINVAL; }
+    for (int j = 0; j < ncols; ++j)
+        if (!(ub[j] >= 0.0)) { set_error("lpx_tableau_set_bounds: ub[" + std::to_string(j) + "] is negative or NaN"); return LPX_EINVAL; }
+    int rc = ensure_device(); if (rc) return rc;
+    rc = bound_buffers(t); if (rc) return rc;
+    rc = bounds_fill_inf(t); if (rc) return rc;            // columns beyond the live shape: unbounded; every flip cleared
+    LPX_HIP_TRY(hipMemcpy(t->ub, ub, sizeof(double) * ncols, hipMemcpyHostToDevice));
+    t->bounds_set = true; t->bounds_C = t->C;
+    return 0;
+}
+
+int lpx_tableau_bound_flags(lpx_tableau* t, uint8_t* flip)
+{
+    if (!t || !flip) { set_error("lpx_tableau_bound_flags: null argument"); return LPX_EINVAL; }
+    const int n = t->C - 1;
+    if (!t->bounds_set || !t->flip) { std::memset(flip, 0, n); return 0; }
+    if (t->bounds_C != t->C) { set_error("lpx_tableau_bound_flags: the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
+    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+    LPX_HIP_TRY(hipMemcpy(flip, t->flip, n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int lpx_bounded_counts(lpx_tableau* t, int64_t counts[3])
+{
+    if (!t || !counts) { set_error("lpx_bounded_counts: null argument"); return LPX_EINVAL; }
+    for (int k = 0; k < 3; ++k) counts[k] = t->bcounts[k];
+    return 0;
+}
+
+int lpx_bounded_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, void* user, lpx_stats* st)
+{
+    if (!t) { set_error("lpx_bounded_run: null tableau"); return LPX_EINVAL; }
+    lpx_run_opts d; if (!o) { lpx_default_opts(&d, 0); o = &d; }
+    if (t->R < 2) { set_error("lpx_bounded_run: tableau needs at least one constraint row"); return LPX_EINVAL; }
+    if (o->resident > 0) { set_error("lpx_bounded_run: there is no resident form of the bounded loop"); return LPX_EINVAL; }
+    if (t->bounds_set && t->bounds_C != t->C) { set_error("lpx_bounded_run: the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
+    int rc = ensure_device(); if (rc) return rc;
+    rc = bound_buffers(t); if (rc) return rc;
+    if (!t->bounds_set) { rc = bounds_fill_inf(t); if (rc) return rc; }
+    BndParams b; std::memset(&b, 0, sizeof(b));
+    b.P = base_params(t, o, MODE_BOUNDED);
+    b.P.us = nullptr; b.P.part_v = nullptr; b.P.part_i = nullptr; b.P.nblk = 0; b.P.qsel = 0;   // single-workgroup select
+    b.ub = t->ub; b.flip = t->flip;
+    LoopCtx c; DevState init;
+    c.stream = t->stream; c.st = t->st; c.hst = t->hst; c.trace = t->trace; c.trace_cap = t->trace_cap;
+    c.events = &t->events; c.gexec = &t->gexec; c.g_batch = &t->g_batch; c.g_key = &t->g_key;
+    c.key.assign(reinterpret_cast<const char*>(&b), sizeof(b));
+    c.enqueue_iter = [t, b](hipStream_t s, hipEvent_t e0, hipEvent_t e1) -> int {
+        LPX_HIP_TRY(launch_bounded_select(b, s));
+        // a launch that ended on a flip or on a final status leaves nothing to update: lpx_update returns at once
+        LPX_HIP_TRY(launch_update(t->T, t->ld, t->Rcap, t->Ccap, t->shape, t->prow, t->pcol, t->pcol, t->rhsbuf, t->st, s, e0, e1));
+        return 0;
+    };
+    const SelParams p = b.P;
+    c.prologue = [p](hipStream_t s) -> int { LPX_HIP_TRY(launch_rhs_init(p, s)); return 0; };
+    c.launches_per_iter = 2;
+    c.profile_maps = false;             // a launch may hold several events, or none that updates
+    std::memset(&init, 0, sizeof(init));
+    init.status = LPX_RUNNING; init.r = -1; init.q = -1; init.qn = -1; init.phase = 2;
+    lpx_stats local; std::memset(&local, 0, sizeof(local));
+    t->bcounts[0] = t->bcounts[1] = t->bcounts[2] = 0;
+    rc = run_device_loop(c, init, o, (long long)o->max_iter + 2, cb, user, &local);
+    if (rc < 0) return rc;
+    // the select kernel counts the pivots per kind in the two counters the dual path uses for its phases
+    t->bcounts[0] = t->hst->fdf_count; t->bcounts[1] = t->hst->dual_iter;
+    t->bcounts[2] = (int64_t)t->hst->iter - t->bcounts[0] - t->bcounts[1];
+    local.pivots = t->bcounts[0] + t->bcounts[1]; local.fdf_pivots = 0; local.cleanup_pivots = 0;
+    if (st) { const double h2d = st->h2d_ms, d2h = st->d2h_ms; *st = local; st->h2d_ms = h2d; st->d2h_ms = d2h; }
+    return rc;
+}
+
+int lpx_tableau_bounded_solution(lpx_tableau* t, int nvars, double* x, double* z, uint8_t* at_upper)
+{
+    if (!t || nvars < 0 || nvars > t->C - 1 || (nvars > 0 && !x)) { set_error("lpx_tableau_bounded_solution: bad argument"); return LPX_EINVAL; }
+    if (t->bounds_set && t->bounds_C != t->C) { set_error("lpx_tableau_bounded_solution: the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
+    const int m = t->R - 1, Cm = t->C - 1;
+    std::vector<double> rhs(t->R), ub(Cm, 1.0 / 0.0);
+    std::vector<int32_t> basis(m > 0 ? m : 1);
+    std::vector<uint8_t> flip(Cm, 0);
+    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+    LPX_HIP_TRY(hipMemcpy2D(rhs.data(), sizeof(double), t->T + Cm, sizeof(double) * t->ld, sizeof(double), t->R, hipMemcpyDeviceToHost));
+    if (m > 0) LPX_HIP_TRY(hipMemcpy(basis.data(), t->basis, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
+    if (t->bounds_set && Cm > 0) {
+        LPX_HIP_TRY(hipMemcpy(ub.data(), t->ub, sizeof(double) * Cm, hipMemcpyDeviceToHost));
+        LPX_HIP_TRY(hipMemcpy(flip.data(), t->flip, Cm, hipMemcpyDeviceToHost));
+    }
+    std::vector<double> v(Cm, 0.0);
+    std::vector<uint8_t> basic(Cm, 0);
+    for (int i = 0; i < m; ++i) if (basis[i] >= 0 && basis[i] < Cm) { v[basis[i]] = rhs[i]; basic[basis[i]] = 1; }
+    for (int j = 0; j < nvars; ++j) {
+        x[j] = flip[j] ? ub[j] - v[j] : v[j];
+        if (at_upper) at_upper[j] = (flip[j] && !basic[j]) ? 1 : 0;
+    }
+    if (z) *z = rhs[m];
+    return 0;
+}
+
+}  // extern "C"
 
 extern "C" {
 

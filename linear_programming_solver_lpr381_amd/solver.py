@@ -70,6 +70,9 @@ class SimplexResult:        # Models/PrimalSimplex.cs:38-49 (+ engine extras aft
     Extra: Optional[np.ndarray] = None      # revised / knapsack: numbers the reference only prints
     Cuts: Optional[np.ndarray] = None       # cutting plane: rows (A[0..n), B) in the order added
     Ranging: Optional["RangingReport"] = None   # LPSolver.SolveRanged only
+    AtUpper: Optional[np.ndarray] = None    # LPSolver.SolveBounded only: 1 = x_j is nonbasic at its upper bound
+    Flips: Optional[np.ndarray] = None      # ... flip state of every tableau column (1 = the column stands for u_j - x_j)
+    BoundCounts: Optional[tuple] = None     # ... events: (pivots to zero, pivots to the upper bound, bound flips)
 
 
 @dataclass
@@ -282,6 +285,40 @@ class LPSolver:             # Models/LPSolver.cs:6-77
             raise SolverException(rc, _lib.last_error())
         res = _take_result(r, problem.NumVars)
         _gmi_names(res, problem)
+        self.FinalTableau = res.Tableau
+        return res
+
+    def SolveBounded(self, problem: LPProblem, upper=None, lower=None) -> SimplexResult:
+        """The bounded-variable primal simplex on the device (lpx_solve_bounded): lower[j] <= x_j <= upper[j] without a row
+        per bound (None: 0 / +inf).  Status, Solution (user variables), OptimalValue (user's sense), Tableau / Basis (the final
+        internal tableau), Trace (events: (r, q) pivot, (-2 - r, q) pivot to the upper bound, (-1, q) bound flip), AtUpper,
+        Flips, BoundCounts.  Solve(problem, "Bounded Primal Simplex") is this without bounds."""
+        n = problem.NumVars
+        o, keep = _solve_opts(self.engine)
+        ps, hold = _problem_struct(problem)
+
+        def _vec(v):
+            if v is None:
+                return None, None
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)))
+            return a, a.ctypes.data_as(_lib.dp)
+        lo, lop = _vec(lower)
+        up, upp = _vec(upper)
+        r, info = _lib.Result(), _lib.BoundedInfo()
+        rc = lib().lpx_solve_bounded(C.byref(ps), lop, upp, C.byref(o), C.byref(r), C.byref(info))
+        if rc != 0:
+            raise SolverException(rc, _lib.last_error())
+        try:
+            flips = _arr(info.flip, info.ncols, np.uint8)
+        finally:
+            lib().lpx_bounded_info_free(C.byref(info))
+        res = _take_result(r, n)
+        res.Flips = flips
+        basic = np.zeros(len(flips), dtype=bool)
+        if res.Basis is not None:
+            basic[res.Basis[(res.Basis >= 0) & (res.Basis < len(flips))]] = True
+        res.AtUpper = ((flips[:n] != 0) & ~basic[:n]).astype(np.uint8)
+        res.BoundCounts = (int(res.Aux[0]), int(res.Aux[1]), int(res.Aux[2]))
         self.FinalTableau = res.Tableau
         return res
 

@@ -224,6 +224,47 @@ class DeviceTableau:
         rc = check(lib().lpx_dual_run(self._h, C.byref(o), c, None, C.byref(st)))
         return rc, st.as_dict()
 
+    def set_bounds(self, ub):
+        """Upper bounds of the columns j < C-1, kept beside the tableau (lpx_tableau_set_bounds); clears every flip.
+        None removes the bounds."""
+        if ub is None:
+            check(lib().lpx_tableau_set_bounds(self._h, 0, None))
+            return
+        ub = np.ascontiguousarray(ub, dtype=np.float64)
+        assert ub.ndim == 1
+        check(lib().lpx_tableau_set_bounds(self._h, len(ub), ub.ctypes.data_as(dp)))
+
+    def bound_flags(self) -> np.ndarray:
+        """flip[j] = 1: column j currently stands for u_j - x_j (lpx_tableau_bound_flags)."""
+        f = np.zeros(max(self.C - 1, 1), dtype=np.uint8)
+        check(lib().lpx_tableau_bound_flags(self._h, f.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return f[: self.C - 1]
+
+    def bounded_run(self, opts: Optional[RunOpts] = None, cb: Optional[PivotCallback] = None,
+                    **kw) -> Tuple[int, dict]:
+        """Bounded-variable primal loop (lpx_bounded_run): one event per iteration -- a pivot (r, q), a pivot whose leaving
+        variable goes to its upper bound (-2 - r, q), or a bound flip (-1, q).  Returns (status, stats)."""
+        o = opts if opts is not None else default_opts(False, **kw)
+        st = Stats()
+        c = _wrap_cb(cb)
+        rc = check(lib().lpx_bounded_run(self._h, C.byref(o), c, None, C.byref(st)))
+        return rc, st.as_dict()
+
+    def bounded_counts(self) -> Tuple[int, int, int]:
+        """Events of the last bounded_run: (pivots to zero, pivots to the upper bound, bound flips)."""
+        k = (C.c_int64 * 3)()
+        check(lib().lpx_bounded_counts(self._h, k))
+        return int(k[0]), int(k[1]), int(k[2])
+
+    def bounded_solution(self, nvars: int) -> Tuple[np.ndarray, float, np.ndarray]:
+        """(x[nvars], z, at_upper[nvars]) of the current tableau with its flips undone (lpx_tableau_bounded_solution)."""
+        x = np.zeros(max(nvars, 1))
+        up = np.zeros(max(nvars, 1), dtype=np.uint8)
+        z = C.c_double()
+        check(lib().lpx_tableau_bounded_solution(self._h, int(nvars), x.ctypes.data_as(dp), C.byref(z),
+                                                 up.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return x[:nvars], z.value, up[:nvars]
+
     def forced_pivots(self, rows, cols, thresh: float = 0.1, opts: Optional[RunOpts] = None,
                       **kw) -> Tuple[np.ndarray, dict]:
         """Gauss-Jordan pivots (Models/PrimalSimplex.cs:245-257) at caller-chosen positions."""

@@ -1,7 +1,7 @@
 // lpx_cli -- Linux stand-in for the reference's WinForms host (Form1.cs), over the C ABI of liblpx.so only.
 //
 //   lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]
-//           [--set-rhs I=V]... [--set-cost J=V]... [--export FILE] INPUT.txt
+//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--export FILE] INPUT.txt
 //
 // Does what Form1 does around the solvers: reads the model text (Import, Form1.cs:284-296), parses it with the LPParser
 // grammar (lpx_parse_text, Models/LPParser.cs:9-79), runs the algorithm chosen by its dropdown name (btnSolve_Click,
@@ -11,7 +11,8 @@
 // report of the final tableau after the summary.  --cuts-per-round / --cut-rounds (GMI Cutting Plane) solve through
 // lpx_solve_cuts with those options.  --set-rhs I=V (b_I = V) and --set-cost J=V (c_J = V), 1-based and repeatable, are
 // applied in the order given after the solve, each as a warm edit of one lpx_session (re-optimised on the device from the
-// previous basis), and each re-solve's summary is printed.  There is no CPU fallback: without a gfx950 device the solve fails with LPX_EDEVICE.
+// previous basis), and each re-solve's summary is printed.  --upper J=V / --lower J=V (bounds of x_J, 1-based, repeatable) and
+// --binary (every u_j = 1) select the bounded-variable primal simplex (lpx_solve_bounded): the bounds cost no rows.  There is no CPU fallback: without a gfx950 device the solve fails with LPX_EDEVICE.
 #include <cstdio>
 #include <cstdlib>
 #include <cctype>
@@ -74,13 +75,30 @@ static std::string algorithm_key(const std::string& name)
 int main(int argc, char** argv)
 {
     std::string algorithm = "Primal Simplex", input, exportPath;
-    bool repaired = false, iterations = false, ranging = false, cut_set = false;
+    bool repaired = false, iterations = false, ranging = false, cut_set = false, algo_set = false, binary = false;
+    struct Bound { bool upper; int index; double value; std::string text; };
+    std::vector<Bound> bounds;
     lpx_cut_opts co; lpx_default_cut_opts(&co);
     struct Edit { bool rhs; int index; double value; std::string text; };
     std::vector<Edit> edits;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
-        if (a == "--algorithm" && i + 1 < argc) algorithm = argv[++i];
+        if (a == "--algorithm" && i + 1 < argc) { algorithm = argv[++i]; algo_set = true; }
+        else if (a == "--binary") binary = true;
+        else if ((a == "--upper" || a == "--lower") && i + 1 < argc) {
+            const std::string v = argv[++i];
+            const size_t eq = v.find('=');
+            char* end = nullptr;
+            const long idx = eq == std::string::npos ? 0 : std::strtol(v.c_str(), &end, 10);
+            if (eq == std::string::npos || end != v.c_str() + eq || idx < 1) {
+                std::fprintf(stderr, "lpx_cli: %s takes INDEX=VALUE with a 1-based index, got '%s'\n", a.c_str(), v.c_str());
+                return 64;
+            }
+            const char* val = v.c_str() + eq + 1;
+            const double x = std::strtod(val, &end);
+            if (end == val || *end) { std::fprintf(stderr, "lpx_cli: bad value in %s %s\n", a.c_str(), v.c_str()); return 64; }
+            bounds.push_back({a == "--upper", (int)idx - 1, x, a + " " + v});
+        }
         else if (a == "--repaired") repaired = true;
         else if (a == "--iterations") iterations = true;
         else if (a == "--ranging") ranging = true;
@@ -103,13 +121,15 @@ int main(int argc, char** argv)
         else if (a == "--export" && i + 1 < argc) exportPath = argv[++i];
         else if (a == "--help" || a == "-h") {
             std::printf("usage: lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]\n"
-                        "               [--export FILE] INPUT.txt\n"
+                        "               [--upper J=V]... [--lower J=V]... [--binary] [--export FILE] INPUT.txt\n"
                         "  NAME: Primal Simplex | Revised Primal Simplex | Dual Simplex | Branch and Bound |\n"
                         "        Revised Branch and Bound | Branch and Bound Knapsack | Cutting Plane | Revised Cutting Plane |\n"
-                        "        GMI Cutting Plane (gmi)\n"
+                        "        GMI Cutting Plane (gmi) | Bounded Primal Simplex\n"
                         "  --ranging: after the summary, the cost / RHS ranges, reduced costs and duals of the final tableau\n"
                         "             (Primal Simplex and Dual Simplex only)\n"
                         "  --cuts-per-round K, --cut-rounds N: GMI Cutting Plane options (defaults 8 and 50)\n"
+                        "  --upper J=V, --lower J=V, --binary: bounds of x_J (1-based, repeatable) / every u_j = 1, kept beside the tableau\n"
+                        "             by the Bounded Primal Simplex (no rows are added); not with --ranging, the cut options or another algorithm\n"
                         "  --set-rhs I=V, --set-cost J=V: after the solve, b_I = V / c_J = V (1-based, repeatable), applied in order,\n"
                         "             each re-optimised warm on the device from the previous basis; each re-solve's summary is printed\n");
             return 0;
@@ -119,6 +139,15 @@ int main(int argc, char** argv)
         const std::string key = algorithm_key(algorithm);
         if (key != "gmi cutting plane" && key != "gmi") { std::fprintf(stderr, "lpx_cli: --cuts-per-round / --cut-rounds need --algorithm \"GMI Cutting Plane\"\n"); return 64; }
         if (ranging) { std::fprintf(stderr, "lpx_cli: --ranging does not combine with --cuts-per-round / --cut-rounds\n"); return 64; }
+    }
+    const bool bounded = binary || !bounds.empty();
+    if (bounded) {
+        if (ranging) { std::fprintf(stderr, "lpx_cli: --upper / --lower / --binary do not combine with --ranging\n"); return 64; }
+        if (cut_set) { std::fprintf(stderr, "lpx_cli: --upper / --lower / --binary do not combine with --cuts-per-round / --cut-rounds\n"); return 64; }
+        if (algo_set && algorithm_key(algorithm) != "bounded primal simplex") {
+            std::fprintf(stderr, "lpx_cli: --upper / --lower / --binary select the Bounded Primal Simplex, not --algorithm \"%s\"\n", algorithm.c_str());
+            return 64;
+        }
     }
     if (input.empty()) { std::fprintf(stderr, "lpx_cli: no input file (try --help)\n"); return 64; }
     std::ifstream f(input);
@@ -136,7 +165,12 @@ int main(int argc, char** argv)
     if (repaired) { o.dual_flags = 7; o.bnb_mode = 1; }
     lpx_result r;
     lpx_ranging rg;
-    const int rc = ranging ? lpx_solve_ranging(&prob, algorithm.c_str(), &o, &r, &rg)
+    std::vector<double> lo((size_t)(p.n > 0 ? p.n : 1), 0.0), up((size_t)(p.n > 0 ? p.n : 1), binary ? 1.0 : 1.0 / 0.0);
+    for (const Bound& bd : bounds) {
+        if (bd.index >= p.n) { std::fprintf(stderr, "lpx_cli: %s: index out of range\n", bd.text.c_str()); lpx_parsed_free(&p); return 64; }
+        (bd.upper ? up : lo)[bd.index] = bd.value;
+    }
+    const int rc = bounded ? lpx_solve_bounded(&prob, lo.data(), up.data(), &o, &r, nullptr) : ranging ? lpx_solve_ranging(&prob, algorithm.c_str(), &o, &r, &rg)
                  : cut_set ? lpx_solve_cuts(&prob, &o, &co, &r) : lpx_solve(&prob, algorithm.c_str(), &o, &r);
     if (rc != 0) { lpx_parsed_free(&p); lpx_last_error(err, sizeof err); std::fprintf(stderr, "%s\n", err); return rc == LPX_EDEVICE ? 69 : 70; }
     std::string shown = g_iterations;
