@@ -69,6 +69,8 @@ hipError_t launch_la_init(const SelParams& p, hipStream_t s);
 hipError_t launch_update(double* T, int ld, int R, int C, const int32_t* shape, const double* prow, double* fac0, double* fac1,
                          double* rhsbuf, const DevState* st, hipStream_t s,
                          hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// the same for the tableau a parameter record describes (T, ld, capacity, shape, pivot row, RHS column, state record)
+hipError_t launch_update(const SelParams& p, double* fac0, double* fac1, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 // multi-workgroup protocol: select_mb (nblk workgroups) + update_mb (reduces the partials, commits `us`)
 hipError_t launch_select_mb(const SelParams& p, hipStream_t s);
 hipError_t launch_update_mb(const SelParams& p, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);

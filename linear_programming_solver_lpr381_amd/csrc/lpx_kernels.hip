@@ -374,6 +374,43 @@ static constexpr size_t UPD_MIXED_BYTES = (size_t)8192 << 20;
 static constexpr size_t UPD_MIX_STEP_BYTES = (size_t)768 << 20;
 static constexpr size_t FUSED_CACHED_BYTES = (size_t)152 << 20;   // fused (out-of-place) forms: both buffers at home in the Infinity Cache, see fused_policy
 
+// LPX_UPDATE_POLICY=0|1|2 forces one form (diagnostic: tools/probe_policy.py measures the three on one tableau), LPX_UPDATE_MIXMOD=n
+// the period of the mixed form; both read once per process.  -1 / 0: not forced.
+static int forced_policy()
+{
+    static const int forced = [] { const char* e = std::getenv("LPX_UPDATE_POLICY"); return (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : -1; }();
+    return forced;
+}
+static int forced_mixmod()
+{
+    static const int forced = [] { const char* e = std::getenv("LPX_UPDATE_MIXMOD"); return e ? std::atoi(e) : 0; }();
+    return forced;
+}
+// which form `bytes` of tableau take: 0 = default policy (they live in the Infinity Cache: up to `cached`), 2 = mixed store policy, 1 = all nt
+static int policy_for(size_t bytes, size_t cached)
+{
+    if (forced_policy() >= 0) return forced_policy();
+    if (bytes <= cached) return 0;
+    return bytes <= UPD_MIXED_BYTES ? 2 : 1;
+}
+// every `mixmod`-th row block of the mixed form keeps one row in three in the cache: about a cache-full of the tableau in all
+// (256 MiB at 768 MiB -> every block up to there, every second block up to 1.5 GiB, ...)
+static int mixmod_for(size_t bytes)
+{
+    if (forced_mixmod() > 0) return forced_mixmod();
+    return (int)((bytes + UPD_MIX_STEP_BYTES - 1) / UPD_MIX_STEP_BYTES);
+}
+static size_t tableau_bytes(int ld, int R) { return sizeof(double) * (size_t)ld * (size_t)R; }
+
+// One launch; e0/e1 non-null: bracketed by HIP events bound to the kernel.
+template <typename... KA, typename... A>
+static hipError_t launch_k(void (*kern)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t s, hipEvent_t e0, hipEvent_t e1, A... args)
+{
+    if (e0 && e1) hipExtLaunchKernelGGL(kern, grid, block, lds, s, e0, e1, 0, static_cast<KA>(args)...);
+    else hipLaunchKernelGGL(kern, grid, block, lds, s, static_cast<KA>(args)...);
+    return hipGetLastError();
+}
+
 typedef double lpx_d2 __attribute__((ext_vector_type(2)));
 // __builtin_nontemporal_load / _store lower to global_load_dwordx4 / global_store_dwordx4 ... nt on gfx950 and stay inside
 // hipcc's s_waitcnt bookkeeping (an inline-asm load would not: cdna_hip_programming.md 5.7).
@@ -400,18 +437,142 @@ template <bool STREAM> __device__ __forceinline__ void upd_store(double* p, doub
 // batched group kernels) sees generic pointers and would issue flat_load / flat_store, which count against both the vector-memory
 // and the LDS counter; casting to address space 1 gives global_load_dwordx4 / global_store_dwordx4 as in the single-tableau kernels.
 #define LPX_GLOBAL __attribute__((address_space(1)))
-template <bool STREAM> __device__ __forceinline__ double2 upd_load_g(const LPX_GLOBAL double* p)
+template <bool STREAM> __device__ __forceinline__ double2 upd_load(const LPX_GLOBAL double* p)
 {
     const LPX_GLOBAL lpx_d2* q = (const LPX_GLOBAL lpx_d2*)p;
     lpx_d2 v;
     if constexpr (STREAM) v = __builtin_nontemporal_load(q); else v = *q;
     return make_double2(v.x, v.y);
 }
-template <bool STREAM> __device__ __forceinline__ void upd_store_g(LPX_GLOBAL double* p, double2 o)
+template <bool STREAM> __device__ __forceinline__ void upd_store(LPX_GLOBAL double* p, double2 o)
 {
-    lpx_d2 v; v.x = o.x; v.y = o.y;
-    LPX_GLOBAL lpx_d2* q = (LPX_GLOBAL lpx_d2*)p;
-    if constexpr (STREAM) __builtin_nontemporal_store(v, q); else *q = v;
+    // The default-policy store is written as two aligned doubles, which the backend's store merging turns into one
+    // global_store_dwordx4 (lpx_group_fused_c: 4 of them, as before): as a vector store it would be the nontemporal one but
+    // for its metadata, and where a tile spells out both (tile_store) the compiler hoists such a pair out of the branch as ONE
+    // store that has lost the policy (seen in lpx_group_fused).  Both facts are the compiler's doing: after a change here or
+    // a new toolchain, tools/isa_table.py against the previous build counts the stores per policy and width.
+    if constexpr (STREAM) {
+        lpx_d2 v; v.x = o.x; v.y = o.y;
+        __builtin_nontemporal_store(v, (LPX_GLOBAL lpx_d2*)p);
+    } else {
+        LPX_GLOBAL double* q = (LPX_GLOBAL double*)__builtin_assume_aligned((void*)p, 16);
+        q[0] = o.x; q[1] = o.y;
+    }
+}
+
+// The straight-line tile every streaming form ends in: a wave's ROWS x 128 block, all rows live, none of them a pivot row,
+// nothing to capture.  Loads, arithmetic and stores follow each other without a branch, so the wait counts stay exact (with
+// a branch per row the compiler waits for EVERYTHING, the previous row's store acknowledgement included, before each store).
+// Three pieces, so that the deferred sweep can apply its D pending pivots between the loads and the stores; P: `double*` or
+// `LPX_GLOBAL double*`, const or not.
+template <int ROWS, bool NT, typename P>
+__device__ __forceinline__ void tile_load(double2 (&v)[ROWS], P sb, size_t ld)
+{
+#pragma unroll
+    for (int k = 0; k < ROWS; ++k) v[k] = upd_load<NT>(sb + (size_t)k * ld);
+}
+// one pivot: `p` the lane's pair of the normalised pivot row, fac[i0 + k] the factor of the tile's row k
+template <int ROWS, typename P>
+__device__ __forceinline__ void tile_pivot(double2 (&v)[ROWS], double2 p, P fac, int i0)
+{
+    double f[ROWS];
+#pragma unroll
+    for (int k = 0; k < ROWS; ++k) f[k] = fac[i0 + k];
+#pragma unroll
+    for (int k = 0; k < ROWS; ++k) {
+        v[k].x = v[k].x - f[k] * p.x;           // mul, then sub: contraction is off
+        v[k].y = v[k].y - f[k] * p.y;
+    }
+}
+// Mixed form: the LAST row of the wave goes through the Infinity Cache (default policy) in every `mixmod`-th row block,
+// everything else is non-temporal; two spelled-out sequences so that no store loses its policy when the compiler merges code
+// (checked in the ISA, tools/isa_table.py: hipcc keeps `nt` as metadata only).  MIX: 0 = no mixed form, MIX_INPLACE = the
+// in-place kernels' argument (always >= 1), MIX_SWEEP = the out-of-place kernels' (0: no block mixes) -- two spellings of
+// the test because each compiles to the code its kernels were measured with.
+enum { MIX_NONE = 0, MIX_INPLACE = 1, MIX_SWEEP = 2 };
+template <int ROWS, bool NT, int MIX, typename P>
+__device__ __forceinline__ void tile_store(P db, size_t ld, const double2 (&v)[ROWS], int rb, int mixmod)
+{
+    if ((MIX == MIX_INPLACE && (mixmod <= 1 || rb % mixmod == 0)) ||
+        (MIX == MIX_SWEEP && mixmod > 0 && (mixmod == 1 || rb % mixmod == 0))) {
+#pragma unroll
+        for (int k = 0; k < ROWS - 1; ++k) upd_store<true>(db + (size_t)k * ld, v[k]);
+        upd_store<false>(db + (size_t)(ROWS - 1) * ld, v[ROWS - 1]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < ROWS; ++k) upd_store<NT>(db + (size_t)k * ld, v[k]);
+    }
+}
+// the whole tile for one pivot (in place: sb == db)
+template <int ROWS, bool NT, int MIX, typename SP, typename DP, typename FP>
+__device__ __forceinline__ void upd_plain_tile(SP sb, DP db, size_t ld, double2 p, FP fac, int i0, int rb, int mixmod)
+{
+    double2 v[ROWS];
+    tile_load<ROWS, NT>(v, sb, ld);
+    tile_pivot<ROWS>(v, p, fac, i0);
+    tile_store<ROWS, NT, MIX>(db, ld, v, rb, mixmod);
+}
+
+// The in-place walker behind lpx_update* and lpx_update_mb*: unit -> tile, the straight-line tile for almost every wave,
+// row by row for the rest.  MB: the multi-workgroup protocol captures row r too (it already holds the normalised pivot row, so
+// nxt[r] and rhsbuf[r] are written); without it row r is skipped ENTIRELY (lpx_bounded.hip, the dual select and the revised
+// path's exact inverse rely on that) and rhsbuf may be null (the exact inverse has no RHS column to capture).
+// `lane` comes from the header: lpx_update_mb_body has it for its reduction, and taking it from there keeps that kernel's code.
+// POLICY: 0 = default cache policy (tableau at home in the Infinity Cache), 1 = nontemporal loads and stores, 2 =
+// nontemporal loads, the wave's LAST row stored with the default policy and the others nontemporal (see UPDM above).
+template <int ROWS, int NTH, int POLICY, bool MB>
+__device__ __forceinline__ void upd_inplace_tiles(double* T, int ld, int R, int C, const double* prow, const double* fac, double* nxt,
+                                                  double* rhsbuf, int r, int qn, int lane, int ncw, int nunits, int mixmod)
+{
+    constexpr bool NT = POLICY != 0;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int unit = blockIdx.x * (NTH / 64) + wave;
+    if (unit >= nunits) return;
+    const int cw = unit % ncw;
+    const int rb = unit / ncw;
+    const int col = cw * 128 + lane * 2;
+    if (col >= ld) return;                      // ld is a multiple of 16, so col+1 < ld too
+    const int row0 = rb * ROWS;
+    if (row0 >= R) return;                      // capacity-sized grid: rows beyond the live shape
+    const double2 p = *reinterpret_cast<const double2*>(prow + col);
+    double* base = T + (size_t)row0 * ld + col;
+    const int c0 = cw * 128;
+    const bool plain_wave = row0 + ROWS <= R && (r < row0 || r >= row0 + ROWS) &&
+                            !(qn >= c0 && qn < c0 + 128) && !((MB || rhsbuf != nullptr) && C - 1 >= c0 && C - 1 < c0 + 128);
+    if (NT && plain_wave) {
+        upd_plain_tile<ROWS, NT, POLICY == 2 ? MIX_INPLACE : MIX_NONE>(base, base, (size_t)ld, p, fac, row0, rb, mixmod);
+        return;
+    }
+    // every other wave -- and every wave of the cache-resident form (8 rows x 256 lanes, default policy), which measured
+    // FASTER with the per-row branches (lpx_update_b 53 vs 74 us, config 2's update 9.1 vs 16.4 us): all loads, then per row
+    const bool wq = (qn >= 0) && ((qn & ~1) == col);              // this lane owns column qn
+    const bool wr = (MB || rhsbuf != nullptr) && (((C - 1) & ~1) == col);   // this lane owns the RHS column
+    double2 v[ROWS];
+    double f[ROWS];
+#pragma unroll
+    for (int k = 0; k < ROWS; ++k) {
+        const int i = row0 + k;
+        if (i < R) {
+            v[k] = upd_load<NT>(base + (size_t)k * ld);
+            f[k] = fac[i];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < ROWS; ++k) {
+        const int i = row0 + k;
+        if (i < R && (MB || i != r)) {
+            double2 o;
+            if (!MB || i != r) {
+                o.x = v[k].x - f[k] * p.x;      // mul, then sub: contraction is off
+                o.y = v[k].y - f[k] * p.y;
+                upd_store<NT>(base + (size_t)k * ld, o);
+            } else {
+                o = p;                          // row r already holds the normalised pivot row
+            }
+            if (wq) nxt[i] = (qn & 1) ? o.y : o.x;
+            if (wr) rhsbuf[i] = ((C - 1) & 1) ? o.y : o.x;
+        }
+    }
 }
 
 template <int ROWS = UPD_ROWS, int NTH = UPD_NT, int POLICY = 0>
@@ -428,77 +589,9 @@ __device__ __forceinline__ void lpx_update_body(double* __restrict__ T, int ld, 
     if (r < 0) return;
     const int R = shape ? shape[0] : Rcap, C = shape ? shape[1] : Ccap;
     const int par = (st->iter - 1) & 1;                   // parity of the pivot being applied
-    const double* __restrict__ fac = par ? fac1 : fac0;   // pivot column snapshot (factors)
-    double* __restrict__ nxt = par ? fac0 : fac1;         // by-product: next pivot's column
-    const int qn = st->qn;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const int unit = blockIdx.x * (NTH / 64) + wave;
-    if (unit >= nunits) return;
-    const int cw = unit % ncw;
-    const int rb = unit / ncw;
-    const int col = cw * 128 + lane * 2;
-    if (col >= ld) return;                      // ld is a multiple of 16, so col+1 < ld too
-    const double2 p = *reinterpret_cast<const double2*>(prow + col);
-    const int row0 = rb * ROWS;
-    if (row0 >= R) return;
-    double* base = T + (size_t)row0 * ld + col;
-    constexpr bool NT = POLICY != 0;
-    const int c0 = cw * 128;
-    // straight-line path of almost every wave (see lpx_update_mb_body): all rows live, no pivot row, no column to capture
-    const bool plain_wave = row0 + ROWS <= R && (r < row0 || r >= row0 + ROWS) &&
-                            !(qn >= c0 && qn < c0 + 128) && !(rhsbuf != nullptr && C - 1 >= c0 && C - 1 < c0 + 128);
-    if (NT && plain_wave) {
-        double2 v[ROWS];
-        double f[ROWS];
-#pragma unroll
-        for (int k = 0; k < ROWS; ++k) v[k] = upd_load<NT>(base + (size_t)k * ld);
-#pragma unroll
-        for (int k = 0; k < ROWS; ++k) f[k] = fac[row0 + k];
-#pragma unroll
-        for (int k = 0; k < ROWS; ++k) {
-            v[k].x = v[k].x - f[k] * p.x;       // mul, then sub: contraction is off
-            v[k].y = v[k].y - f[k] * p.y;
-        }
-        // mixed form: the LAST row of the wave goes through the Infinity Cache (default policy) in every `mixmod`-th row
-        // block, everything else is non-temporal; two spelled-out sequences so that no store loses its policy when the
-        // compiler merges code (checked in the ISA: hipcc keeps `nt` as metadata only)
-        if (POLICY == 2 && (mixmod <= 1 || rb % mixmod == 0)) {
-#pragma unroll
-            for (int k = 0; k < ROWS - 1; ++k) upd_store<true>(base + (size_t)k * ld, v[k]);
-            upd_store<false>(base + (size_t)(ROWS - 1) * ld, v[ROWS - 1]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < ROWS; ++k) upd_store<NT>(base + (size_t)k * ld, v[k]);
-        }
-        return;
-    }
-    // every other wave -- and every wave of the cache-resident form (8 rows x 256 lanes, default policy), which measured
-    // FASTER with the per-row branches (lpx_update_b 53 vs 74 us, config 2's update 9.1 vs 16.4 us): all loads, then per row
-    const bool wq = (qn >= 0) && ((qn & ~1) == col);              // this lane owns column qn
-    const bool wr = (rhsbuf != nullptr) && (((C - 1) & ~1) == col);   // this lane owns the RHS column
-    double2 v[ROWS];
-    double f[ROWS];
-#pragma unroll
-    for (int k = 0; k < ROWS; ++k) {
-        const int i = row0 + k;
-        if (i < R) {
-            v[k] = upd_load<NT>(base + (size_t)k * ld);
-            f[k] = fac[i];
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < ROWS; ++k) {
-        const int i = row0 + k;
-        if (i < R && i != r) {
-            double2 o;
-            o.x = v[k].x - f[k] * p.x;          // mul, then sub: contraction is off
-            o.y = v[k].y - f[k] * p.y;
-            upd_store<NT>(base + (size_t)k * ld, o);
-            if (wq) nxt[i] = (qn & 1) ? o.y : o.x;
-            if (wr) rhsbuf[i] = ((C - 1) & 1) ? o.y : o.x;
-        }
-    }
+    // fac: pivot column snapshot (factors); the other one takes the by-product, the next pivot's column
+    upd_inplace_tiles<ROWS, NTH, POLICY, false>(T, ld, R, C, prow, par ? fac1 : fac0, par ? fac0 : fac1, rhsbuf, r, st->qn,
+                                                threadIdx.x & 63, ncw, nunits, mixmod);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -666,8 +759,6 @@ __device__ __forceinline__ void lpx_select_mb_body(const SelParams& P)
 
 // lpx_update for the multi-workgroup protocol: same streaming body; the next entering column comes from
 // the select workgroups' partials, and workgroup 0 commits the state record `us` for the next select.
-// POLICY: 0 = default cache policy (tableau at home in the Infinity Cache), 1 = nontemporal loads and stores, 2 =
-// nontemporal loads, the wave's FIRST row stored with the default policy and the others nontemporal (see UPDM below).
 template <int ROWS = UPD_ROWS, int NTH = UPD_NT, int POLICY = 0>
 __device__ __forceinline__ void lpx_update_mb_body(double* __restrict__ T, int ld, int Rcap, int Ccap,
                                                    const int32_t* __restrict__ shape,
@@ -679,7 +770,6 @@ __device__ __forceinline__ void lpx_update_mb_body(double* __restrict__ T, int l
                                                    const int32_t* __restrict__ part_i, int nblk,
                                                    int forced, int ncw, int nunits, int mixmod = 1)
 {
-    constexpr bool NT = POLICY != 0;
     // The state record is read FIRST: a launch that finds the loop finished (tail of a batch, finished node
     // of a B&B group) must not stream the tableau.
     const int status = st->status;
@@ -716,80 +806,8 @@ __device__ __forceinline__ void lpx_update_mb_body(double* __restrict__ T, int l
     }
     if (r < 0) return;                                   // skipped pivot: nothing to update
     const int par = (st->iter - 1) & 1;
-    const double* __restrict__ fac = par ? fac1 : fac0;
-    double* __restrict__ nxt = par ? fac0 : fac1;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int unit = blockIdx.x * (NTH / 64) + wave;
-    if (unit >= nunits) return;
-    const int cw = unit % ncw;
-    const int rb = unit / ncw;
-    const int col = cw * 128 + lane * 2;
-    if (col >= ld) return;
-    const int row0 = rb * ROWS;
-    if (row0 >= R) return;                                // capacity-sized grid: rows beyond the live shape
-    const double2 p = *reinterpret_cast<const double2*>(prow + col);
-    double* base = T + (size_t)row0 * ld + col;
-    const int c0 = cw * 128;
-    // Almost every wave takes the straight-line path: all ROWS rows live, none of them the pivot row, no column to
-    // capture.  Loads, arithmetic and stores follow each other without a branch, so the wait counts stay exact (with
-    // a branch per row the compiler waits for EVERYTHING, the previous row's store acknowledgement included, before
-    // each store).
-    const bool plain_wave = row0 + ROWS <= R && (r < row0 || r >= row0 + ROWS) &&
-                            !(qn >= c0 && qn < c0 + 128) && !(C - 1 >= c0 && C - 1 < c0 + 128);
-    if (NT && plain_wave) {
-        double2 v[ROWS];
-        double f[ROWS];
-#pragma unroll
-        for (int k = 0; k < ROWS; ++k) v[k] = upd_load<NT>(base + (size_t)k * ld);
-#pragma unroll
-        for (int k = 0; k < ROWS; ++k) f[k] = fac[row0 + k];
-#pragma unroll
-        for (int k = 0; k < ROWS; ++k) {
-            v[k].x = v[k].x - f[k] * p.x;       // mul, then sub: contraction is off
-            v[k].y = v[k].y - f[k] * p.y;
-        }
-        // mixed form: the LAST row of the wave goes through the Infinity Cache (default policy) in every `mixmod`-th row
-        // block, everything else is non-temporal; two spelled-out sequences so that no store loses its policy when the
-        // compiler merges code (checked in the ISA: hipcc keeps `nt` as metadata only)
-        if (POLICY == 2 && (mixmod <= 1 || rb % mixmod == 0)) {
-#pragma unroll
-            for (int k = 0; k < ROWS - 1; ++k) upd_store<true>(base + (size_t)k * ld, v[k]);
-            upd_store<false>(base + (size_t)(ROWS - 1) * ld, v[ROWS - 1]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < ROWS; ++k) upd_store<NT>(base + (size_t)k * ld, v[k]);
-        }
-        return;
-    }
-    // every other wave, and every wave of the cache-resident form (which measured faster with the per-row branches)
-    const bool wq = (qn >= 0) && ((qn & ~1) == col);
-    const bool wr = (((C - 1) & ~1) == col);
-    double2 v[ROWS];
-    double f[ROWS];
-#pragma unroll
-    for (int k = 0; k < ROWS; ++k) {
-        const int i = row0 + k;
-        if (i < R) {
-            v[k] = upd_load<NT>(base + (size_t)k * ld);
-            f[k] = fac[i];
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < ROWS; ++k) {
-        const int i = row0 + k;
-        if (i < R) {
-            double2 o;
-            if (i != r) {
-                o.x = v[k].x - f[k] * p.x;      // mul, then sub: contraction is off
-                o.y = v[k].y - f[k] * p.y;
-                upd_store<NT>(base + (size_t)k * ld, o);
-            } else {
-                o = p;                          // row r already holds the normalised pivot row
-            }
-            if (wq) nxt[i] = (qn & 1) ? o.y : o.x;
-            if (wr) rhsbuf[i] = ((C - 1) & 1) ? o.y : o.x;
-        }
-    }
+    upd_inplace_tiles<ROWS, NTH, POLICY, true>(T, ld, R, C, prow, par ? fac1 : fac0, par ? fac0 : fac1, rhsbuf, r, qn,
+                                               lane, ncw, nunits, mixmod);
 }
 
 // single-tableau and batched (blockIdx.y = node of a branch-and-bound group) entry points
@@ -1350,29 +1368,14 @@ __device__ __forceinline__ void fused_sweep(const FusedParams& F, int ncw, int n
     double* db = dst + (size_t)row0 * ld + col;
     if (row0 + ROWS <= R && !hit) {
         double2 v[ROWS];
-#pragma unroll
-        for (int k = 0; k < ROWS; ++k) v[k] = upd_load<NT>(sb + (size_t)k * ld);
+        tile_load<ROWS, NT>(v, sb, ld);
 #pragma unroll
         for (int s = 0; s < D; ++s) {
             const int sl = fp_slot(lm, D, s, ring);
             const double2 p = *reinterpret_cast<const double2*>(F.pring + (size_t)sl * ld + col);
-            const double* fac = F.fring + (size_t)sl * fld + row0;
-#pragma unroll
-            for (int k = 0; k < ROWS; ++k) {
-                const double f = fac[k];
-                v[k].x = v[k].x - f * p.x;          // mul, then sub: contraction is off
-                v[k].y = v[k].y - f * p.y;
-            }
+            tile_pivot<ROWS>(v, p, F.fring + (size_t)sl * fld + row0, 0);
         }
-        // store policies as in lpx_update_mb_m / _s (two spelled-out sequences, checked in the ISA)
-        if (NT && mixmod > 0 && (mixmod == 1 || rb % mixmod == 0)) {
-#pragma unroll
-            for (int k = 0; k < ROWS - 1; ++k) upd_store<true>(db + (size_t)k * ld, v[k]);
-            upd_store<false>(db + (size_t)(ROWS - 1) * ld, v[ROWS - 1]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < ROWS; ++k) upd_store<NT>(db + (size_t)k * ld, v[k]);
-        }
+        tile_store<ROWS, NT, NT ? MIX_SWEEP : MIX_NONE>(db, ld, v, rb, mixmod);
         return;
     }
 #pragma unroll 1
@@ -1556,29 +1559,11 @@ __device__ __forceinline__ void lpx_group_fused_body(const FusedParams* __restri
         const int row0 = rb * UPDS_ROWS;
         const LPX_GLOBAL double* gprow = (const LPX_GLOBAL double*)prowc;
         const LPX_GLOBAL double* gfac = (const LPX_GLOBAL double*)facc;
-        const double2 p = upd_load_g<false>(gprow + col);
+        const double2 p = upd_load<false>(gprow + col);
         const LPX_GLOBAL double* sb = (const LPX_GLOBAL double*)src + (size_t)row0 * ld + col;
         LPX_GLOBAL double* db = (LPX_GLOBAL double*)dst + (size_t)row0 * ld + col;
         if (row0 + UPDS_ROWS <= R && (pr < row0 || pr >= row0 + UPDS_ROWS)) {
-            double2 v[UPDS_ROWS];
-            double f[UPDS_ROWS];
-#pragma unroll
-            for (int k = 0; k < UPDS_ROWS; ++k) v[k] = upd_load_g<NT>(sb + (size_t)k * ld);
-#pragma unroll
-            for (int k = 0; k < UPDS_ROWS; ++k) f[k] = gfac[row0 + k];
-#pragma unroll
-            for (int k = 0; k < UPDS_ROWS; ++k) {
-                v[k].x = v[k].x - f[k] * p.x;       // mul, then sub: contraction is off
-                v[k].y = v[k].y - f[k] * p.y;
-            }
-            if (NT && mixmod > 0 && (mixmod == 1 || rb % mixmod == 0)) {
-#pragma unroll
-                for (int k = 0; k < UPDS_ROWS - 1; ++k) upd_store_g<true>(db + (size_t)k * ld, v[k]);
-                upd_store_g<false>(db + (size_t)(UPDS_ROWS - 1) * ld, v[UPDS_ROWS - 1]);
-            } else {
-#pragma unroll
-                for (int k = 0; k < UPDS_ROWS; ++k) upd_store_g<NT>(db + (size_t)k * ld, v[k]);
-            }
+            upd_plain_tile<UPDS_ROWS, NT, NT ? MIX_SWEEP : MIX_NONE>(sb, db, ld, p, gfac, row0, rb, mixmod);
             return;
         }
 #pragma unroll 1
@@ -1587,12 +1572,12 @@ __device__ __forceinline__ void lpx_group_fused_body(const FusedParams* __restri
             if (i >= R) break;
             double2 o = p;                                   // row r: the normalised pivot row
             if (i != pr) {
-                const double2 v = upd_load_g<NT>(sb + (size_t)k * ld);
+                const double2 v = upd_load<NT>(sb + (size_t)k * ld);
                 const double f = gfac[i];
                 o.x = v.x - f * p.x;
                 o.y = v.y - f * p.y;
             }
-            upd_store_g<NT>(db + (size_t)k * ld, o);
+            upd_store<NT>(db + (size_t)k * ld, o);      // default policy: two doubles the backend merges into one dwordx4 (upd_store)
         }
         return;
     }
@@ -1786,17 +1771,12 @@ hipError_t launch_group_fused(const FusedParams* arr, const int* live, int nlive
                               int* comp, int cap, hipEvent_t e0, hipEvent_t e1)
 {
     if (nlive <= 0) return hipSuccess;
-    static const int forced = [] { const char* e = std::getenv("LPX_UPDATE_POLICY"); return (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : -1; }();
-    int pol = live_bytes <= FUSED_CACHED_BYTES ? 0 : (live_bytes <= UPD_MIXED_BYTES ? 2 : 1);
-    if (forced >= 0) pol = forced;
-    static const int mm_forced = [] { const char* e = std::getenv("LPX_UPDATE_MIXMOD"); return e ? std::atoi(e) : 0; }();
-    const int mixmod = pol == 2 ? (mm_forced > 0 ? mm_forced : (int)((live_bytes + UPD_MIX_STEP_BYTES - 1) / UPD_MIX_STEP_BYTES)) : 0;
+    const int pol = policy_for(live_bytes, FUSED_CACHED_BYTES);
+    const int mixmod = pol == 2 ? mixmod_for(live_bytes) : 0;
     auto kern = pol == 0 ? lpx_group_fused_c : lpx_group_fused;
     const unsigned nblocks = (unsigned)nlive * (unsigned)(1 + per_node);
     const int* comp_rd = comp + (lpar & 1) * fg_comp_region(cap);
-    if (e0 && e1) hipExtLaunchKernelGGL(kern, dim3(nblocks), dim3(FG_NT), 0, s, e0, e1, 0, arr, live, nlive, per_node, lpar & 1, mixmod, comp_rd, comp, cap);
-    else hipLaunchKernelGGL(kern, dim3(nblocks), dim3(FG_NT), 0, s, arr, live, nlive, per_node, lpar & 1, mixmod, comp_rd, comp, cap);
-    return hipGetLastError();
+    return launch_k(kern, dim3(nblocks), dim3(FG_NT), 0, s, e0, e1, arr, live, nlive, per_node, lpar & 1, mixmod, comp_rd, comp, cap);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1854,56 +1834,35 @@ hipError_t launch_select_mb(const SelParams& p, hipStream_t s)
     return hipGetLastError();
 }
 
-// which streaming form a tableau of `bytes` takes: 0 = none (it lives in the Infinity Cache), 2 = mixed store policy, 1 = all nt
-int update_policy(int ld, int R)
+// which form the in-place update of a tableau takes: 0 = cache-resident, 2 = mixed-store streaming, 1 = all-nt streaming
+int update_policy(int ld, int R) { return policy_for(tableau_bytes(ld, R), UPD_STREAM_BYTES); }
+static int update_mixmod(int ld, int R) { return mixmod_for(tableau_bytes(ld, R)); }
+
+// launch geometry of the in-place forms: 8 rows x 256 lanes (pol 0) or 3 rows x 64 lanes per workgroup, units flattened
+struct UpdGeom { int nth, ncw, nunits, nblocks; };
+static UpdGeom update_geom(int ld, int R, int pol)
 {
-    // LPX_UPDATE_POLICY=0|1|2 forces one form (diagnostic: tools/probe_policy.py measures the three on one tableau)
-    static const int forced = [] { const char* e = std::getenv("LPX_UPDATE_POLICY"); return (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : -1; }();
-    if (forced >= 0) return forced;
-    const size_t bytes = sizeof(double) * (size_t)ld * (size_t)R;
-    if (bytes <= UPD_STREAM_BYTES) return 0;
-    return bytes <= UPD_MIXED_BYTES ? 2 : 1;
+    const int rows = pol ? UPDS_ROWS : UPD_ROWS;
+    UpdGeom g;
+    g.nth = pol ? UPDS_NT : UPD_NT;
+    g.ncw = (ld + 127) / 128;
+    g.nunits = g.ncw * ((R + rows - 1) / rows);
+    g.nblocks = (g.nunits + (g.nth / 64) - 1) / (g.nth / 64);
+    return g;
 }
-// every `mixmod`-th row block of the mixed form keeps one row in three in the cache: about a cache-full of the tableau in all
-// (256 MiB at 768 MiB -> every block up to there, every second block up to 1.5 GiB, ...)
-static int update_mixmod(int ld, int R)
-{
-    static const int forced = [] { const char* e = std::getenv("LPX_UPDATE_MIXMOD"); return e ? std::atoi(e) : 0; }();   // diagnostic
-    if (forced > 0) return forced;
-    const size_t bytes = sizeof(double) * (size_t)ld * (size_t)R;
-    return (int)((bytes + UPD_MIX_STEP_BYTES - 1) / UPD_MIX_STEP_BYTES);
-}
+int update_blocks(int ld, int R) { return update_geom(ld, R, 0).nblocks; }
 
 hipError_t launch_update_mb(const SelParams& p, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
 {
     // the streaming forms read the entering column select's last workgroup reduced: both sides follow SelParams::qsel
     const int pol = !p.qsel ? 0 : (update_policy(p.ld, p.R) == 2 ? 2 : 1);
-    const int rows = pol ? UPDS_ROWS : UPD_ROWS, nth = pol ? UPDS_NT : UPD_NT;
-    const int ncw = (p.ld + 127) / 128, nunits = ncw * ((p.R + rows - 1) / rows);
-    const int nblocks = (nunits + (nth / 64) - 1) / (nth / 64);
+    const UpdGeom g = update_geom(p.ld, p.R, pol);
     const int forced = p.mode == MODE_FORCED ? 1 : 0;
-    if (pol == 0) {
-        if (e0 && e1)
-            hipExtLaunchKernelGGL(lpx_update_mb, dim3(nblocks), dim3(nth), 0, s, e0, e1, 0, p.T, p.ld, p.R, p.C, p.shape,
-                                  (const double*)p.prow, p.col0, p.col1, p.rhsbuf, (const DevState*)p.st, p.us,
-                                  (const double*)p.part_v, (const int32_t*)p.part_i, p.nblk, forced, ncw, nunits);
-        else
-            hipLaunchKernelGGL(lpx_update_mb, dim3(nblocks), dim3(nth), 0, s, p.T, p.ld, p.R, p.C, p.shape,
-                               (const double*)p.prow, p.col0, p.col1, p.rhsbuf, (const DevState*)p.st, p.us,
-                               (const double*)p.part_v, (const int32_t*)p.part_i, p.nblk, forced, ncw, nunits);
-        return hipGetLastError();
-    }
-    auto kern = pol == 2 ? lpx_update_mb_m : lpx_update_mb_s;
-    const int mixmod = update_mixmod(p.ld, p.R);
-    if (e0 && e1)
-        hipExtLaunchKernelGGL(kern, dim3(nblocks), dim3(nth), 0, s, e0, e1, 0, p.T, p.ld, p.R, p.C, p.shape,
-                              (const double*)p.prow, p.col0, p.col1, p.rhsbuf, (const DevState*)p.st, p.us,
-                              (const double*)p.part_v, (const int32_t*)p.part_i, p.nblk, forced, ncw, nunits, mixmod);
-    else
-        hipLaunchKernelGGL(kern, dim3(nblocks), dim3(nth), 0, s, p.T, p.ld, p.R, p.C, p.shape,
-                           (const double*)p.prow, p.col0, p.col1, p.rhsbuf, (const DevState*)p.st, p.us,
-                           (const double*)p.part_v, (const int32_t*)p.part_i, p.nblk, forced, ncw, nunits, mixmod);
-    return hipGetLastError();
+    if (pol == 0)
+        return launch_k(lpx_update_mb, dim3(g.nblocks), dim3(g.nth), 0, s, e0, e1, p.T, p.ld, p.R, p.C, p.shape, p.prow, p.col0, p.col1,
+                        p.rhsbuf, p.st, p.us, p.part_v, p.part_i, p.nblk, forced, g.ncw, g.nunits);
+    return launch_k(pol == 2 ? lpx_update_mb_m : lpx_update_mb_s, dim3(g.nblocks), dim3(g.nth), 0, s, e0, e1, p.T, p.ld, p.R, p.C, p.shape,
+                    p.prow, p.col0, p.col1, p.rhsbuf, p.st, p.us, p.part_v, p.part_i, p.nblk, forced, g.ncw, g.nunits, update_mixmod(p.ld, p.R));
 }
 
 // one iteration of a whole group: `arr` holds `count` parameter records in device memory
@@ -1974,12 +1933,6 @@ hipError_t launch_rhs_init(const SelParams& p, hipStream_t s)
     hipLaunchKernelGGL(lpx_rhs_init, dim3(1), dim3(SEL_NT), 0, s, p);
     return hipGetLastError();
 }
-int update_blocks(int ld, int R)
-{
-    const int nunits = ((ld + 127) / 128) * ((R + UPD_ROWS - 1) / UPD_ROWS);
-    return (nunits + (UPD_NT / 64) - 1) / (UPD_NT / 64);
-}
-
 hipError_t launch_la_init(const SelParams& p, hipStream_t s)
 {
     hipLaunchKernelGGL(lpx_la_init, dim3(1), dim3(SEL_NT), 0, s, p);
@@ -1990,23 +1943,15 @@ hipError_t launch_update(double* T, int ld, int R, int C, const int32_t* shape, 
                          double* rhsbuf, const DevState* st, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
 {
     const int pol = update_policy(ld, R);
-    const int rows = pol ? UPDS_ROWS : UPD_ROWS, nth = pol ? UPDS_NT : UPD_NT;
-    const int ncw = (ld + 127) / 128, nunits = ncw * ((R + rows - 1) / rows);
-    const int nblocks = (nunits + (nth / 64) - 1) / (nth / 64);
-    if (pol == 0) {
-        if (e0 && e1)
-            hipExtLaunchKernelGGL(lpx_update, dim3(nblocks), dim3(nth), 0, s, e0, e1, 0, T, ld, R, C, shape, prow, fac0, fac1, rhsbuf, st, ncw, nunits);
-        else
-            hipLaunchKernelGGL(lpx_update, dim3(nblocks), dim3(nth), 0, s, T, ld, R, C, shape, prow, fac0, fac1, rhsbuf, st, ncw, nunits);
-        return hipGetLastError();
-    }
-    auto kern = pol == 2 ? lpx_update_m : lpx_update_s;
-    const int mixmod = update_mixmod(ld, R);
-    if (e0 && e1)
-        hipExtLaunchKernelGGL(kern, dim3(nblocks), dim3(nth), 0, s, e0, e1, 0, T, ld, R, C, shape, prow, fac0, fac1, rhsbuf, st, ncw, nunits, mixmod);
-    else
-        hipLaunchKernelGGL(kern, dim3(nblocks), dim3(nth), 0, s, T, ld, R, C, shape, prow, fac0, fac1, rhsbuf, st, ncw, nunits, mixmod);
-    return hipGetLastError();
+    const UpdGeom g = update_geom(ld, R, pol);
+    if (pol == 0)
+        return launch_k(lpx_update, dim3(g.nblocks), dim3(g.nth), 0, s, e0, e1, T, ld, R, C, shape, prow, fac0, fac1, rhsbuf, st, g.ncw, g.nunits);
+    return launch_k(pol == 2 ? lpx_update_m : lpx_update_s, dim3(g.nblocks), dim3(g.nth), 0, s, e0, e1, T, ld, R, C, shape, prow, fac0, fac1,
+                    rhsbuf, st, g.ncw, g.nunits, update_mixmod(ld, R));
+}
+hipError_t launch_update(const SelParams& p, double* fac0, double* fac1, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    return launch_update(p.T, p.ld, p.R, p.C, p.shape, p.prow, fac0, fac1, p.rhsbuf, p.st, s, e0, e1);
 }
 
 // Cache policy of the fused launch.  Two buffers share the Infinity Cache, so the default policy only pays while BOTH fit with
@@ -2014,14 +1959,7 @@ hipError_t launch_update(double* T, int ld, int R, int C, const int32_t* shape, 
 // (tools/probe_fused_mid.py, us per pivot, two-launch in place / fused default policy / fused streaming mix):
 //    57 MB 24.1 / 21.4 / 22.8     101 MB 37.8 / 30.5 / 34.3     157 MB 53.5 / 49.2 / 49.1     190 MB 64.5 / 65.5 / 58.3
 //   227 MB 73.1 / 77.2 / 69.0     266 MB 86.1 / 91.1 / 80.3     308 MB 102.7 / 92.4 / 92.2    403 MB 128.3 / 120.0 / 120.2
-int fused_policy(int ld, int R)
-{
-    static const int forced = [] { const char* e = std::getenv("LPX_UPDATE_POLICY"); return (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : -1; }();
-    if (forced >= 0) return forced;
-    const size_t bytes = sizeof(double) * (size_t)ld * (size_t)R;
-    if (bytes <= FUSED_CACHED_BYTES) return 0;
-    return bytes <= UPD_MIXED_BYTES ? 2 : 1;
-}
+int fused_policy(int ld, int R) { return policy_for(tableau_bytes(ld, R), FUSED_CACHED_BYTES); }
 
 hipError_t launch_fused_init(const FusedParams& f, hipStream_t s)
 {
@@ -2047,13 +1985,7 @@ hipError_t launch_pivot_fused(const FusedParams& f0, long long L, hipStream_t s,
     f.lm = (int)(L % (2 * d)); f.par = f.lm & 1;
     const bool sweep = L > 0 && L % d == 0;
     const int ld = f.P.ld, R = f.P.R;
-    if (!sweep) {
-        if (e0 && e1)
-            hipExtLaunchKernelGGL(lpx_pivot_select, dim3(f.P.nblk), dim3(FP_NT), 0, s, e0, e1, 0, f);
-        else
-            hipLaunchKernelGGL(lpx_pivot_select, dim3(f.P.nblk), dim3(FP_NT), 0, s, f);
-        return hipGetLastError();
-    }
+    if (!sweep) return launch_k(lpx_pivot_select, dim3(f.P.nblk), dim3(FP_NT), 0, s, e0, e1, f);
     const int rows = fp_rows(d);
     const int ncw = (ld + 127) / 128, nunits = ncw * ((R + rows - 1) / rows);
     const int nblocks = f.P.nblk + (nunits + (FP_NT / 64) - 1) / (FP_NT / 64);
@@ -2065,11 +1997,7 @@ hipError_t launch_pivot_fused(const FusedParams& f0, long long L, hipStream_t s,
     // 16 R C; the other share was not measured
     if (mixmod > 1) mixmod = std::max(1, mixmod * UPDS_ROWS / rows);
     const FusedKernel kern = pol == 0 ? FusedKernels::c[d - 1] : FusedKernels::nt[d - 1];   // both buffers in the Infinity Cache: default policy
-    if (e0 && e1)
-        hipExtLaunchKernelGGL(kern, dim3(nblocks), dim3(FP_NT), 0, s, e0, e1, 0, f, ncw, nunits, mixmod);
-    else
-        hipLaunchKernelGGL(kern, dim3(nblocks), dim3(FP_NT), 0, s, f, ncw, nunits, mixmod);
-    return hipGetLastError();
+    return launch_k(kern, dim3(nblocks), dim3(FP_NT), 0, s, e0, e1, f, ncw, nunits, mixmod);
 }
 
 hipError_t launch_pivot_flush(const FusedParams& f, int buf, int n, int slot0, hipStream_t s)

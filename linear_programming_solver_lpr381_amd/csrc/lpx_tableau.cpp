@@ -367,36 +367,47 @@ int lpx_tableau_trace(lpx_tableau* t, int32_t* trace, int cap, int* n)
 // ---------------------------------------------------------------------------------------------------
 namespace {
 
-int enqueue_pair(lpx_tableau* t, const SelParams& p, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr)
+int enqueue_pair(const SelParams& p, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr)
 {
     if (p.mode == MODE_DUAL) {
         LPX_HIP_TRY(launch_select(p, s));
-        LPX_HIP_TRY(launch_update(t->T, t->ld, t->Rcap, t->Ccap, t->shape, t->prow, t->pcol, t->pcol, t->rhsbuf, t->st, s, e0, e1));
+        LPX_HIP_TRY(launch_update(p, p.pcol, p.pcol, s, e0, e1));
     } else if (p.us) {
         LPX_HIP_TRY(launch_select_mb(p, s));
         LPX_HIP_TRY(launch_update_mb(p, s, e0, e1));
     } else {
         LPX_HIP_TRY(launch_select_la(p, s));
-        LPX_HIP_TRY(launch_update(t->T, t->ld, t->Rcap, t->Ccap, t->shape, t->prow, t->col0, t->col1, t->rhsbuf, t->st, s, e0, e1));
+        LPX_HIP_TRY(launch_update(p, p.col0, p.col1, s, e0, e1));
     }
     return 0;
 }
 
-void make_ctx(lpx_tableau* t, const SelParams& p, LoopCtx& c, DevState& init)
+// The loop context every tableau loop shares: the handle's stream, records and graph cache, two launches per iteration, a
+// fresh state record.  What differs comes in: the bytes that key the captured graph (the loop's parameter record) and the
+// per-iteration enqueue; prologue and profile mapping follow p.mode.
+template <typename Params, typename Enqueue>
+void make_ctx(lpx_tableau* t, const SelParams& p, const Params& key, Enqueue enqueue, LoopCtx& c, DevState& init)
 {
+    const bool lookahead = p.mode != MODE_DUAL && p.mode != MODE_BOUNDED;
     c.stream = t->stream; c.st = t->st; c.hst = t->hst; c.trace = t->trace; c.trace_cap = t->trace_cap;
     c.events = &t->events; c.gexec = &t->gexec; c.g_batch = &t->g_batch; c.g_key = &t->g_key;
-    c.key.assign(reinterpret_cast<const char*>(&p), sizeof(p));
-    c.enqueue_iter = [t, p](hipStream_t s, hipEvent_t e0, hipEvent_t e1) -> int { return enqueue_pair(t, p, s, e0, e1); };
-    if (p.mode != MODE_DUAL)           // lookahead path: first entering column + its gather, once
+    c.key.assign(reinterpret_cast<const char*>(&key), sizeof(key));
+    c.enqueue_iter = enqueue;
+    if (lookahead)                                       // lookahead path: first entering column + its gather, once
         c.prologue = [p](hipStream_t s) -> int { LPX_HIP_TRY(launch_la_init(p, s)); return 0; };
-    else                               // dual path: contiguous copy of the RHS column, once
+    else                                                 // dual and bounded paths: contiguous copy of the RHS column, once
         c.prologue = [p](hipStream_t s) -> int { LPX_HIP_TRY(launch_rhs_init(p, s)); return 0; };
     c.launches_per_iter = 2;
-    c.profile_maps = (p.mode != MODE_DUAL);     // phase hops make the mapping ambiguous in dual mode
+    // one profiled update launch = one pivot: not in dual mode (phase hops make the mapping ambiguous) nor in the bounded loop
+    // (a launch may hold several events, or none that updates)
+    c.profile_maps = lookahead;
     std::memset(&init, 0, sizeof(init));
     init.status = LPX_RUNNING; init.r = -1; init.q = -1; init.qn = -1;
     init.phase = (p.mode == MODE_DUAL) ? 0 : 2;
+}
+void make_ctx(lpx_tableau* t, const SelParams& p, LoopCtx& c, DevState& init)
+{
+    make_ctx(t, p, p, [p](hipStream_t s, hipEvent_t e0, hipEvent_t e1) -> int { return enqueue_pair(p, s, e0, e1); }, c, init);
 }
 
 int run_loop(lpx_tableau* t, SelParams p, const lpx_run_opts* o, long long budget,
@@ -1378,21 +1389,12 @@ int lpx_bounded_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, void
     b.P.us = nullptr; b.P.part_v = nullptr; b.P.part_i = nullptr; b.P.nblk = 0; b.P.qsel = 0;   // single-workgroup select
     b.ub = t->ub; b.flip = t->flip;
     LoopCtx c; DevState init;
-    c.stream = t->stream; c.st = t->st; c.hst = t->hst; c.trace = t->trace; c.trace_cap = t->trace_cap;
-    c.events = &t->events; c.gexec = &t->gexec; c.g_batch = &t->g_batch; c.g_key = &t->g_key;
-    c.key.assign(reinterpret_cast<const char*>(&b), sizeof(b));
-    c.enqueue_iter = [t, b](hipStream_t s, hipEvent_t e0, hipEvent_t e1) -> int {
+    make_ctx(t, b.P, b, [b](hipStream_t s, hipEvent_t e0, hipEvent_t e1) -> int {
         LPX_HIP_TRY(launch_bounded_select(b, s));
         // a launch that ended on a flip or on a final status leaves nothing to update: lpx_update returns at once
-        LPX_HIP_TRY(launch_update(t->T, t->ld, t->Rcap, t->Ccap, t->shape, t->prow, t->pcol, t->pcol, t->rhsbuf, t->st, s, e0, e1));
+        LPX_HIP_TRY(launch_update(b.P, b.P.pcol, b.P.pcol, s, e0, e1));
         return 0;
-    };
-    const SelParams p = b.P;
-    c.prologue = [p](hipStream_t s) -> int { LPX_HIP_TRY(launch_rhs_init(p, s)); return 0; };
-    c.launches_per_iter = 2;
-    c.profile_maps = false;             // a launch may hold several events, or none that updates
-    std::memset(&init, 0, sizeof(init));
-    init.status = LPX_RUNNING; init.r = -1; init.q = -1; init.qn = -1; init.phase = 2;
+    }, c, init);
     lpx_stats local; std::memset(&local, 0, sizeof(local));
     t->bcounts[0] = t->bcounts[1] = t->bcounts[2] = 0;
     rc = run_device_loop(c, init, o, (long long)o->max_iter + 2, cb, user, &local);

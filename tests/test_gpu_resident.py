@@ -393,7 +393,8 @@ def test_column_owning_resident_kernel_is_bit_identical(oracle):
 
 def test_register_group_forms_agree_bit_for_bit(oracle):
     """lpx_resident_group_r in its forms -- three columns per lane with rows in the LDS beside the registers (default), without the LDS
-    rows, two columns per lane -- against the LDS-resident group kernel and the streaming kernels: the same config-4 node LPs (root
+    rows, two columns per lane -- against the LDS-resident group kernel and the streaming kernels (the fused group step and the
+    two-launch lpx_select_b + lpx_update_b): the same config-4 node LPs (root
     shape 770x1282 and deeper levels: the tile's padding columns differ), final tableaux, bases, pivot counts and statuses bitwise.
     The environment switches are read once per process, hence one child process per form."""
     import subprocess, sys, os, textwrap
@@ -422,7 +423,8 @@ def test_register_group_forms_agree_bit_for_bit(oracle):
     ''')
     base = dict(os.environ, PYTHONPATH=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     forms = {"default": {}, "no LDS rows": {"LPX_RESIDENT_REGS_LDS": "0"}, "two columns": {"LPX_RESIDENT_REGS_KC": "2"},
-             "LDS form": {"LPX_RESIDENT_REGS": "0"}, "streaming": {"LPX_RESIDENT_GROUP": "0"}}
+             "LDS form": {"LPX_RESIDENT_REGS": "0"}, "streaming": {"LPX_RESIDENT_GROUP": "0"},
+             "two-launch": {"LPX_RESIDENT_GROUP": "0", "LPX_GROUP_FUSED": "0"}}
     seen = {}
     for name, extra in forms.items():
         r = subprocess.run([sys.executable, "-c", code], env=dict(base, **extra), capture_output=True, text=True, timeout=300)
