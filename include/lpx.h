@@ -669,6 +669,78 @@ int  lpx_solve_bounded(const lpx_problem* p, const double* lower /* [n] or NULL 
                        const lpx_solve_opts* o, lpx_result* out, lpx_bounded_info* info /* or NULL */);
 void lpx_bounded_info_free(lpx_bounded_info* info);
 
+/* ---- bounded dual simplex and bound changes on a solved tableau (not in the reference; csrc/lpx_bounded_dual.hip, DESIGN.md
+ * section 4.14) --
+ * The representation of the bounded primal loop above, plus a LOWER SHIFT lo[j] (double) for every column j < Cm: internal
+ * column j stands for x_j - lo[j] when flip[j] = 0 and for ub[j] - (x_j - lo[j]) when flip[j] = 1.  lpx_tableau_set_bounds sets
+ * every lo[j] to +0.0; lpx_tableau_snapshot / _restore carry lo with ub and flip; lpx_tableau_upload leaves it alone.
+ * lpx_tableau_bounded_solution adds lo[j] to x[j] (one addition, after the subtraction of a flipped column), but only on a
+ * handle where a change has stored a non-zero lo since the last lpx_tableau_set_bounds; on every other handle its output is
+ * what it was without this section.  lpx_tableau_bound_state: lo, ub, flip of the live C-1 columns, each array [C-1] or NULL;
+ * a handle without bounds reports lo = 0, ub = +inf, flip = 0.
+ *
+ * lpx_tableau_change_bounds(t, K, cols, lower, upper): new ABSOLUTE bounds lower[k] <= x_cols[k] <= upper[k] on a handle that
+ * has bounds, in place on the live window (R rows, the objective row included, Cm = C-1).  IEEE double, no FMA; the bits do not
+ * depend on launch geometry or capacity.  For k = 0..K-1 in order, j = cols[k]:
+ *   1. l' = lower[k] - lo[j], u' = upper[k] - lo[j] (one subtraction each; +inf stays +inf).
+ *   2. s = flip[j] ? ub[j] - u' : l'.
+ *   3. For every row i in [0, R): T[i,Cm] = T[i,Cm] - s * T[i,j] (one multiply, one subtract) -- for a basic column too, where
+ *      only its own row really moves.  The whole pass is skipped when s == 0.0.
+ *   4. ub[j] = upper[k] - lower[k]; lo[j] = lower[k].
+ * Flips, basis and every column other than the RHS stay as they were, and so does the objective row apart from its RHS: a
+ * dual-feasible tableau stays dual feasible (a basic value may now lie below 0 or above its bound: lpx_bounded_dual_run
+ * repairs that).  The loop state is reset as lpx_tableau_build_child resets it.
+ * LPX_EINVAL before any device check, nothing touched: a NULL handle, K < 0, NULL arrays with K > 0, a column outside
+ * [0, Cm), a repeated column, a NaN bound, an infinite lower, upper < lower, a handle without bounds or whose live C changed
+ * since lpx_tableau_set_bounds.  upper = +inf on a column whose flip is set is LPX_EINVAL too (after the device check, the flip
+ * lives on the device; the handle is untouched): unflipping is not part of this edit.  No device: LPX_EDEVICE.
+ *
+ * lpx_bounded_dual_run: a dual simplex on this representation.  Precondition, not checked: every nonbasic column has
+ * T[m,j] >= -eps.  One EVENT per iteration; IEEE double, no FMA, true division:
+ *   1. Events done >= max_iter: LPX_ITER_LIMIT (tested where lpx_bounded_run tests its limit, before anything else).
+ *   2. Leaving row, rows i = 0..m-1 in ascending order, b = T[i,Cm], p = basis[i]:
+ *        b < -eps:                 w_i = b,           kind 0 (the basic variable is below zero)
+ *        else ub[p] < +inf:        w_i = ub[p] - b,   kind 1 (one subtraction; negative when the variable is above its bound)
+ *        otherwise the row does not take part.
+ *      r = first index of the strict minimum of w below -eps (the `v < mostNeg` scan of lpx_dual_run, mostNeg starting at
+ *      -eps).  No such row: LPX_OPTIMAL.
+ *   3. Kind 1: the ROW COMPLEMENT of row r as defined above for the primal loop, p = basis[r]: T[r,j] = -T[r,j] for every
+ *      j < Cm, j != p; T[r,Cm] = ub[p] - T[r,Cm]; flip[p] ^= 1.  The row's RHS is now below -eps.
+ *   4. Entering column, columns j = 0..Cm-1 in ascending order, a = T[r,j] (after the complement): a column takes part iff
+ *      a < -eps, ratio = T[m,j] / (-a), accepted iff ratio < best - ratio_tol (best starts at +inf); the last accepted column
+ *      is q -- the entering rule of lpx_dual_run.  No column: LPX_INFEASIBLE; a complement applied in step 3 stays applied (the
+ *      tableau is still a valid representation), no event is recorded.
+ *   5. The ordinary pivot on (r, q), basis[r] = q.  Trace entry (r, q) for kind 0, (-2 - r, q) for kind 1; the per-pivot
+ *      callback receives the same encoding.
+ * Options eps, ratio_tol, max_iter, batch, use_graph, profile as lpx_bounded_run reads them; fdf_guard and cleanup are not read;
+ * resident = 1 is LPX_EINVAL.  o == NULL: lpx_default_opts(o, 1), the dual loop's defaults.  lpx_stats.pivots = events;
+ * lpx_bounded_counts returns {kind 0, kind 1, 0}.  A handle without bounds runs with every ub = +inf and is then
+ * lpx_dual_run(fdf_guard = 0, cleanup = 0) bit for bit.  The result depends on nothing but the tableau, basis, ub, flip and the
+ * options: not on the batch length, on graph replay or on the callback.  Any m and Cm: w and the ratios are held on chip up to
+ * 4096 entries each and go through global scratch beyond that. */
+int lpx_tableau_bound_state(lpx_tableau* t, double* lo /* [C-1] or NULL */, double* ub /* [C-1] or NULL */, uint8_t* flip /* [C-1] or NULL */);
+int lpx_tableau_change_bounds(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper);
+int lpx_bounded_dual_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, void* user, lpx_stats* st);
+
+/* The model level: a bounded session.  lpx_bounded_open is lpx_solve_bounded that keeps its handle: same validation, same
+ * messages, res equal to lpx_solve_bounded's for the same inputs.  lpx_bounded_set_bounds takes the user's ABSOLUTE bounds
+ * lower[k] <= x_vars[k] <= upper[k] of original variables (0-based), applies them with lpx_tableau_change_bounds and
+ * re-optimises with lpx_bounded_dual_run from the tableau as it stands.  res: x in the user's variables, optimal_value in the
+ * user's sense with the constant of open included, T / basis the internal tableau, trace / stats of this edit only,
+ * aux = {kind-0 events, kind-1 events, 1, constant}, status LPX_OPTIMAL or LPX_INFEASIBLE (x and optimal_value then describe
+ * the tableau as it stands); LPX_ITER_LIMIT is the return value, as elsewhere.  A session left INFEASIBLE stays usable:
+ * loosening the bounds continues from the tableau as it stands.  A session whose open solve was not LPX_OPTIMAL returns
+ * LPX_EINVAL with a message.  Validation (before any device check): a NULL session or res, K < 0, NULL arrays with K > 0, a
+ * variable outside [0, n), a repeated variable, a lower bound that is not finite, an upper bound below its lower bound or NaN
+ * -- the last two with lpx_solve_bounded's messages.  upper = +inf on a variable whose column is flipped is LPX_EINVAL, as in
+ * lpx_tableau_change_bounds. */
+typedef struct lpx_bounded_session lpx_bounded_session;
+int  lpx_bounded_open(const lpx_problem* p, const double* lower /* [n] or NULL = 0 */, const double* upper /* [n] or NULL = +inf */,
+                      const lpx_solve_opts* o, lpx_bounded_session** session, lpx_result* res);
+int  lpx_bounded_set_bounds(lpx_bounded_session* s, int K, const int32_t* vars, const double* lower, const double* upper,
+                            lpx_result* res);
+void lpx_bounded_close(lpx_bounded_session* s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -214,6 +214,23 @@ namespace Linear_Programming_Solver.Native
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_tableau_bounded_solution(IntPtr t, int nvars, double* x, out double z, byte* atUpper);
 
+        // ---- bounded dual simplex and bound changes on a solved tableau (not in the reference), include/lpx.h ----
+        // lo / ub / flip: [C-1] each or null
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int lpx_tableau_bound_state(IntPtr t, double* lo, double* ub, byte* flip);
+        // new absolute bounds lower[k] <= x_cols[k] <= upper[k], in place: only the RHS column moves
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_tableau_change_bounds(IntPtr t, int K, int* cols, double* lower, double* upper);
+        // trace rows: (r, q) basic variable below zero, (-2 - r, q) basic variable above its upper bound
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_bounded_dual_run(IntPtr t, IntPtr opts, LpxPivotCb cb, IntPtr user, out LpxStats st);
+        // a bounded session: lpx_solve_bounded that keeps its handle, then bound edits of original variables (0-based)
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_bounded_open(ref LpxProblem p, double* lower, double* upper, ref LpxSolveOpts o,
+                                                  out IntPtr session, out LpxResult result);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_bounded_set_bounds(IntPtr s, int K, int* vars, double* lower, double* upper, out LpxResult result);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern void lpx_bounded_close(IntPtr s);
+
         public static string LastError()
         {
             var b = new byte[1024];

@@ -8,7 +8,7 @@ from . import comm
 from ._lib import LpxError, default_opts
 from .tableau import DeviceTableau, TableauRanging, primal_tableau, dual_tableau, multi_run
 from .revised import DeviceRevised, invert
-from .solver import (BranchAndBound, BranchAndBoundKnapsack, BranchAndBoundRevised, Constraint, CutOpts, CuttingPlane,
+from .solver import (BoundedSession, BranchAndBound, BranchAndBoundKnapsack, BranchAndBoundRevised, Constraint, CutOpts, CuttingPlane,
                      CuttingPlaneRevised, DeviceKnapsack, DualSimplex, GmiCuttingPlane, LPProblem, SensitivityAnalysis,
                      LPSolver, ModelSession, ParseFromText, PrimalSimplex, RangingReport, Rel, RevisedPrimalSimplex, Sense, SimplexResult,
                      SolverException)
@@ -16,4 +16,5 @@ from .solver import (BranchAndBound, BranchAndBoundKnapsack, BranchAndBoundRevis
 __all__ = ["_lib", "comm", "LpxError", "default_opts", "DeviceTableau", "TableauRanging", "primal_tableau", "dual_tableau", "multi_run", "DeviceRevised", "invert", "LPSolver", "LPProblem", "Constraint", "Sense", "Rel",
            "SimplexResult", "RangingReport", "SolverException", "PrimalSimplex", "RevisedPrimalSimplex", "DualSimplex",
            "BranchAndBound", "BranchAndBoundKnapsack", "BranchAndBoundRevised", "ParseFromText", "DeviceKnapsack",
-           "CuttingPlane", "CuttingPlaneRevised", "SensitivityAnalysis", "CutOpts", "GmiCuttingPlane", "ModelSession"]
+           "CuttingPlane", "CuttingPlaneRevised", "SensitivityAnalysis", "CutOpts", "GmiCuttingPlane", "ModelSession",
+           "BoundedSession"]

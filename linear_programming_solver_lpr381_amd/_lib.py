@@ -260,6 +260,13 @@ def lib() -> C.CDLL:
     L.lpx_solve_bounded.argtypes = [C.POINTER(Problem), dp, dp, C.POINTER(SolveOpts), C.POINTER(Result), C.POINTER(BoundedInfo)]
     L.lpx_bounded_info_free.argtypes = [C.POINTER(BoundedInfo)]
     L.lpx_bounded_info_free.restype = None
+    L.lpx_tableau_bound_state.argtypes = [vp, dp, dp, u8p]
+    L.lpx_tableau_change_bounds.argtypes = [vp, C.c_int, ip, dp, dp]
+    L.lpx_bounded_dual_run.argtypes = [vp, C.POINTER(RunOpts), PIVOT_CB, vp, C.POINTER(Stats)]
+    L.lpx_bounded_open.argtypes = [C.POINTER(Problem), dp, dp, C.POINTER(SolveOpts), C.POINTER(vp), C.POINTER(Result)]
+    L.lpx_bounded_set_bounds.argtypes = [vp, C.c_int, ip, dp, dp, C.POINTER(Result)]
+    L.lpx_bounded_close.argtypes = [vp]
+    L.lpx_bounded_close.restype = None
     L.lpx_parse_text.argtypes = [C.c_char_p, C.POINTER(Parsed)]
     L.lpx_parsed_free.argtypes = [C.POINTER(Parsed)]
     L.lpx_parsed_free.restype = None

@@ -1,6 +1,7 @@
 // host/bounded.cpp -- the bounded-variable primal simplex at the model level (lpx_solve_bounded, include/lpx.h): preparation as
 // PrimalSimplex.Solve (Models/PrimalSimplex.cs:57-90), lower bounds shifted away on the host, upper bounds handed to the device
-// loop (lpx_bounded_run) beside the tableau instead of as rows.
+// loop (lpx_bounded_run) beside the tableau instead of as rows.  A bounded session (lpx_bounded_open) is the same solve that
+// keeps its handle; its bound edits are lpx_tableau_change_bounds + lpx_bounded_dual_run on that handle.
 #include "model.h"
 
 #include <cmath>
@@ -21,7 +22,8 @@ struct BoundedHandle {
     lpx_tableau* h = nullptr; int R, C;
     BoundedHandle(int R_, int C_) : R(R_), C(C_) { h = acquire_exact_handle(R, C); }
     // the handle goes back to a cache shared with the other solvers: without its bounds
-    ~BoundedHandle() { if (h) lpx_tableau_set_bounds(h, 0, nullptr); release_exact_handle(h, R, C); }
+    ~BoundedHandle() { if (!h) return; lpx_tableau_set_bounds(h, 0, nullptr); release_exact_handle(h, R, C); }
+    lpx_tableau* take() { lpx_tableau* k = h; h = nullptr; return k; }          // a session keeps it
     BoundedHandle(const BoundedHandle&) = delete;
 };
 
@@ -38,10 +40,55 @@ void bounded_event(void* user, int iter, int row, int col)
     else c->cb(head + "leaving row " + std::to_string(row) + ", entering " + v + "\n", nullptr);
 }
 
+// What a finished loop left on the handle, in the user's terms: events, tableau, x (lower bounds of open added back), the
+// optimum in the user's sense plus the constant the shift took out, the report with its at-upper line.
+void collect(lpx_tableau* h, int st, int n, int R, int C, const std::vector<double>& lower, bool min, bool shifted, double constant,
+             std::string report, SimplexResult& res, std::vector<uint8_t>* flip_out)
+{
+    const int Cm = C - 1;
+    int nev = 0;
+    int rc = lpx_tableau_trace(h, nullptr, 0, &nev); if (rc) throw_lib(rc);
+    res.Trace.resize(2 * (size_t)(nev > 0 ? nev : 1));
+    rc = lpx_tableau_trace(h, res.Trace.data(), nev, &nev); if (rc) throw_lib(rc);
+    res.Trace.resize(2 * (size_t)nev);
+    std::vector<double> T((size_t)R * C); std::vector<int32_t> basis((size_t)(R - 1));
+    rc = lpx_tableau_download(h, T.data(), basis.data());
+    if (rc) throw_lib(rc);
+    std::vector<double> x((size_t)n, 0.0); double z = 0.0;
+    std::vector<uint8_t> at_upper((size_t)n, 0), flip((size_t)Cm, 0);
+    rc = lpx_tableau_bounded_solution(h, n, x.data(), &z, at_upper.data()); if (rc) throw_lib(rc);
+    rc = lpx_tableau_bound_flags(h, flip.data()); if (rc) throw_lib(rc);
+    if (!lower.empty()) for (int j = 0; j < n; ++j) x[j] = x[j] + lower[j];
+    // the tableau maximises; the user's optimum is -z for a Min model, plus the constant the shift took out
+    double value = z;
+    if (shifted || min) {
+        value = min ? -z : z;
+        if (shifted) value = value + constant;
+    }
+    if (st == LPX_UNBOUNDED) report += "UNBOUNDED\n";                                   // :104
+    FinalizeText(report, res.Summary, x, value, st);
+    std::string at = "  at upper bound:";
+    bool any = false;
+    for (int j = 0; j < n; ++j) if (at_upper[j]) { at += std::string(any ? "," : "") + " x" + std::to_string(j + 1); any = true; }
+    if (!any) at += " none";
+    report += at + "\n";
+    res.Summary += at.substr(2) + "\n";
+    res.Report = report; res.OptimalValue = value; res.Solution = x; res.HasSolution = true; res.Status = st;
+    res.Tableau = std::move(T); res.R = R; res.C = C; res.Basis = std::move(basis);
+    if (flip_out) *flip_out = flip;
+}
+
 }  // namespace
 
+BoundedSession::~BoundedSession()
+{
+    if (!h) return;
+    lpx_tableau_set_bounds(h, 0, nullptr);          // the handle goes back to the shared cache without its bounds
+    release_exact_handle(h, R, C);
+}
+
 SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
-                           const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info)
+                           const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info, BoundedSession* keep)
 {
     const int n = original.NumVars();
     if ((!lower.empty() && (int)lower.size() != n) || (!upper.empty() && (int)upper.size() != n))
@@ -80,7 +127,7 @@ SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>&
     if (updatePivot) updatePivot(AppendTableau("TABLEAU Iteration", T.data(), R, C, basis, varNames, 0), nullptr);
     const int Cm = C - 1;
     std::vector<double> ub((size_t)Cm, 1.0 / 0.0);
-    const bool bounded = !upper.empty() || !lower.empty();
+    const bool bounded = !upper.empty() || !lower.empty() || keep;       // a session edits bounds later: its handle always has them
     if (!upper.empty()) for (int j = 0; j < n; ++j) ub[j] = std::isinf(upper[j]) ? upper[j] : upper[j] - (lower.empty() ? 0.0 : lower[j]);
 
     SimplexResult res;
@@ -95,40 +142,58 @@ SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>&
     const int st = lpx_bounded_run(th.h, &o, updatePivot ? bounded_event : nullptr, &ctx, &res.Stats);
     if (st < 0) throw_lib(st);
     if (st == LPX_ITER_LIMIT) throw LpxException(LPX_ITER_LIMIT, "Iteration limit exceeded.");      // :95-96
-    int nev = 0;
-    rc = lpx_tableau_trace(th.h, nullptr, 0, &nev); if (rc) throw_lib(rc);
-    res.Trace.resize(2 * (size_t)(nev > 0 ? nev : 1));
-    rc = lpx_tableau_trace(th.h, res.Trace.data(), nev, &nev); if (rc) throw_lib(rc);
-    res.Trace.resize(2 * (size_t)nev);
-    rc = lpx_tableau_download(th.h, T.data(), basis.data());
-    if (rc) throw_lib(rc);
-    std::vector<double> x((size_t)n, 0.0); double z = 0.0;
-    std::vector<uint8_t> at_upper((size_t)n, 0), flip((size_t)Cm, 0);
-    rc = lpx_tableau_bounded_solution(th.h, n, x.data(), &z, at_upper.data()); if (rc) throw_lib(rc);
-    rc = lpx_tableau_bound_flags(th.h, flip.data()); if (rc) throw_lib(rc);
     int64_t counts[3] = {0, 0, 0};
     lpx_bounded_counts(th.h, counts);
+    std::vector<uint8_t> flip;
+    collect(th.h, st, n, R, C, lower, original.ObjectiveSense == Sense::Min, shifted, constant, report, res, &flip);
     if (opt.on_final_tableau) opt.on_final_tableau(th.h, st);
-
-    if (!lower.empty()) for (int j = 0; j < n; ++j) x[j] = x[j] + lower[j];
-    // the tableau maximises; the user's optimum is -z for a Min model, plus the constant the shift took out
-    double value = z;
-    if (shifted || original.ObjectiveSense == Sense::Min) {
-        value = original.ObjectiveSense == Sense::Min ? -z : z;
-        if (shifted) value = value + constant;
-    }
-    if (st == LPX_UNBOUNDED) report += "UNBOUNDED\n";                                   // :104
-    FinalizeText(report, res.Summary, x, value, st);
-    std::string at = "  at upper bound:";
-    bool any = false;
-    for (int j = 0; j < n; ++j) if (at_upper[j]) { at += std::string(any ? "," : "") + " x" + std::to_string(j + 1); any = true; }
-    if (!any) at += " none";
-    report += at + "\n";
-    res.Summary += at.substr(2) + "\n";
-    res.Report = report; res.OptimalValue = value; res.Solution = x; res.HasSolution = true; res.Status = st;
-    res.Tableau = std::move(T); res.R = R; res.C = C; res.Basis = std::move(basis); res.VarNames = std::move(varNames);
+    res.VarNames = varNames;
     res.Aux = {(double)counts[0], (double)counts[1], (double)counts[2], constant};
     if (info) { info->flip = flip; info->ub = ub; info->lower = lower.empty() ? std::vector<double>((size_t)n, 0.0) : lower; }
+    if (keep) {
+        keep->h = th.take(); keep->R = R; keep->C = C; keep->n = n;
+        keep->min = original.ObjectiveSense == Sense::Min; keep->shifted = shifted; keep->constant = constant;
+        keep->lower = lower; keep->open_status = st; keep->opt = opt; keep->varNames = varNames;
+    }
+    return res;
+}
+
+SimplexResult BoundedSetBounds(BoundedSession& s, int K, const int32_t* vars, const double* lower, const double* upper)
+{
+    const char* what = "Bounded session: ";
+    if (K < 0) throw LpxException(LPX_EINVAL, std::string(what) + "K is negative");
+    if (K > 0 && (!vars || !lower || !upper)) throw LpxException(LPX_EINVAL, std::string(what) + "null array");
+    std::vector<uint8_t> seen((size_t)(s.n > 0 ? s.n : 1), 0);
+    for (int k = 0; k < K; ++k) {
+        if (vars[k] < 0 || vars[k] >= s.n) throw LpxException(LPX_EINVAL, std::string(what) + "variable index " + std::to_string(vars[k]) + " is outside the model");
+        const std::string v = "x" + std::to_string(vars[k] + 1);
+        if (seen[vars[k]]) throw LpxException(LPX_EINVAL, std::string(what) + v + " is listed twice");
+        seen[vars[k]] = 1;
+        if (!std::isfinite(lower[k])) throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: lower bound of " + v + " is not finite");
+        if (!(upper[k] >= lower[k])) throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: upper bound of " + v + " is below its lower bound or NaN");
+    }
+    if (s.open_status != LPX_OPTIMAL) throw LpxException(LPX_EINVAL, std::string(what) + "the open solve did not end OPTIMAL, there is no tableau to continue from");
+    // the handle's columns stand for x - l(open): the user's absolute bounds move by that shift, one subtraction each
+    std::vector<double> lo((size_t)K), up((size_t)K);
+    for (int k = 0; k < K; ++k) {
+        const double l0 = s.lower.empty() ? 0.0 : s.lower[vars[k]];
+        lo[k] = s.lower.empty() ? lower[k] : lower[k] - l0;
+        up[k] = s.lower.empty() ? upper[k] : upper[k] - l0;
+    }
+    int rc = lpx_tableau_change_bounds(s.h, K, vars, lo.data(), up.data());
+    if (rc) throw_lib(rc);
+    SimplexResult res;
+    lpx_run_opts o; lpx_default_opts(&o, 1);
+    o.max_iter = s.opt.max_iter;
+    o.batch = s.opt.batch;
+    const int st = lpx_bounded_dual_run(s.h, &o, nullptr, nullptr, &res.Stats);
+    if (st < 0) throw_lib(st);
+    if (st == LPX_ITER_LIMIT) throw LpxException(LPX_ITER_LIMIT, "Iteration limit exceeded.");
+    int64_t counts[3] = {0, 0, 0};
+    lpx_bounded_counts(s.h, counts);
+    collect(s.h, st, s.n, s.R, s.C, s.lower, s.min, s.shifted, s.constant, std::string(), res, nullptr);
+    res.VarNames = s.varNames;
+    res.Aux = {(double)counts[0], (double)counts[1], 1.0, s.constant};
     return res;
 }
 

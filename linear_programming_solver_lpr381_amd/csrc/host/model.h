@@ -211,8 +211,21 @@ private:
 // Bounded-variable primal simplex at the model level (lpx_solve_bounded, include/lpx.h; bounded.cpp): lower / upper are empty
 // (0 / +inf) or hold one entry per variable.
 struct BoundedInfo { std::vector<uint8_t> flip; std::vector<double> ub, lower; };
+// A bounded session (lpx_bounded_open): the handle SolveBounded solved on, kept with what turns its tableau back into the
+// user's terms.  The destructor hands the handle back.
+struct BoundedSession {
+    ::lpx_tableau* h = nullptr; int R = 0, C = 0, n = 0;
+    bool min = false, shifted = false; double constant = 0.0;      // objective sense, and the constant c.l of open's shift
+    std::vector<double> lower;                                      // open's lower bounds (empty = none): the host-side shift
+    int open_status = -1; EngineOptions opt; std::vector<std::string> varNames;
+    BoundedSession() = default;
+    BoundedSession(const BoundedSession&) = delete;
+    ~BoundedSession();
+};
 SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
-                           const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info);
+                           const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info, BoundedSession* keep = nullptr);
+// new absolute bounds of user variables vars[k] on a session: lpx_tableau_change_bounds + lpx_bounded_dual_run (lpx_bounded_set_bounds)
+SimplexResult BoundedSetBounds(BoundedSession& s, int K, const int32_t* vars, const double* lower, const double* upper);
 
 // LPParser.ParseFromText, Models/LPParser.cs:9-79.  Throws LpxException(LPX_E_PARSE, message).
 LPProblem ParseFromText(const std::string& input);

@@ -57,8 +57,14 @@ struct BndParams {
     SelParams P;
     const double* ub;    // [C-1 capacity] upper bound of every column, +inf = none
     uint8_t* flip;       // [C-1 capacity] 1 = the column stands for u_j - x_j
+    int dual;            // 1 = the record of lpx_bounded_dual_run (read by no kernel: it keeps the two loops' cached graphs apart)
 };
 hipError_t launch_bounded_select(const BndParams& b, hipStream_t s);
+// bounded dual simplex and the bound change on a solved tableau (lpx_bounded_dual.hip)
+hipError_t launch_bounded_dual_select(const BndParams& b, hipStream_t s);
+// shift[k] from the old lo / ub / flip of cols[k], new ub / lo stored; then T[:,Cm] and rhsbuf shifted, k in order (R rows)
+hipError_t launch_change_bounds(double* T, int ld, int R, int Cm, int K, const int32_t* cols, const double* lower, const double* upper,
+                                double* ub, double* lo, const uint8_t* flip, double* shift, double* rhsbuf, hipStream_t s);
 
 // launchers (lpx_kernels.hip)
 hipError_t launch_select(const SelParams& p, hipStream_t s);       // gather-based (dual path)

@@ -315,6 +315,46 @@ void lpx_bounded_info_free(lpx_bounded_info* info)
     std::memset(info, 0, sizeof(*info));
 }
 
+// ---- bounded session: lpx_solve_bounded that keeps its handle, then bound edits re-optimised by the bounded dual loop ------
+struct lpx_bounded_session { BoundedSession s; };
+
+int lpx_bounded_open(const lpx_problem* p, const double* lower, const double* upper, const lpx_solve_opts* o,
+                     lpx_bounded_session** session, lpx_result* out)
+{
+    if (session) *session = nullptr;
+    if (!p || !session || !out) { set_error("lpx_bounded_open: null argument"); return LPX_EINVAL; }
+    std::memset(out, 0, sizeof(*out));
+    lpx_solve_opts d; if (!o) { lpx_default_solve_opts(&d); o = &d; }
+    lpx_bounded_session* ses = new lpx_bounded_session();
+    const int rc = guarded("lpx_bounded_open", [&]() -> int {
+        EngineOptions e = to_engine(o);
+        UpdatePivot cb = to_callback(o);
+        LPProblem q = to_problem(p);
+        std::vector<double> lo, up;
+        if (lower) lo.assign(lower, lower + p->n);
+        if (upper) up.assign(upper, upper + p->n);
+        SimplexResult r = SolveBounded(q, lo, up, e, cb, nullptr, &ses->s);
+        fill_result(out, r, p->n);
+        return 0;
+    });
+    if (rc != 0) { delete ses; return rc; }
+    *session = ses;
+    return 0;
+}
+
+int lpx_bounded_set_bounds(lpx_bounded_session* s, int K, const int32_t* vars, const double* lower, const double* upper, lpx_result* out)
+{
+    if (!s || !out) { set_error("lpx_bounded_set_bounds: null argument"); return LPX_EINVAL; }
+    std::memset(out, 0, sizeof(*out));
+    return guarded("lpx_bounded_set_bounds", [&]() -> int {
+        SimplexResult r = BoundedSetBounds(s->s, K, vars, lower, upper);
+        fill_result(out, r, s->s.n);
+        return 0;
+    });
+}
+
+void lpx_bounded_close(lpx_bounded_session* s) { delete s; }
+
 int lpx_sensitivity_range_report(const lpx_problem* p, const double* T, int R, int C, const int32_t* basis,
                                  const char* target, char* buf, int len)
 {

@@ -66,6 +66,10 @@ struct lpx_tableau {
     bool bounds_set = false; int bounds_C = 0;              // live C the bounds were set for
     double* snapUb = nullptr; uint8_t* snapFlip = nullptr; bool snap_bounds = false; int snap_bounds_C = 0;
     int64_t bcounts[3] = {0, 0, 0};                         // events of the last lpx_bounded_run: kind 0, kind 1, flips
+    // lower shift of every column (lpx_tableau_change_bounds): internal column j stands for x_j - lo[j]; allocated with ub
+    double* lo = nullptr; double* snapLo = nullptr;         // [Ccap] each
+    bool lo_used = false, snap_lo_used = false;             // some change has stored a non-zero lo
+    char* chg = nullptr; size_t chg_bytes = 0;              // staging of one lpx_tableau_change_bounds: lower, upper, shift, cols
 };
 
 void lpx::tableau_view(lpx_tableau* t, TableauView* v)
@@ -218,6 +222,7 @@ void lpx_tableau_destroy(lpx_tableau* t)
     hipFree(t->fT); hipFree(t->fslab); hipFree(t->dring);
     hipFree(t->rgws);
     hipFree(t->ub); hipFree(t->flip); hipFree(t->snapUb); hipFree(t->snapFlip);
+    hipFree(t->lo); hipFree(t->snapLo); hipFree(t->chg);
     hipFree(t->xr); hipFree(t->xp); hipFree(t->xgen); hipFree(t->xbasis); hipFree(t->xT); hipFree(t->xc); hipFree(t->xq);
     if (t->hslab) hipHostFree(t->hslab);
     if (t->cutbuf_h) hipHostFree(t->cutbuf_h);
@@ -274,7 +279,10 @@ int lpx_tableau_snapshot(lpx_tableau* t)
         if (!t->snapUb) {
             LPX_HIP_TRY(hipMalloc((void**)&t->snapUb, sizeof(double) * t->Ccap));
             LPX_HIP_TRY(hipMalloc((void**)&t->snapFlip, t->Ccap));
+            LPX_HIP_TRY(hipMalloc((void**)&t->snapLo, sizeof(double) * t->Ccap));
         }
+        LPX_HIP_TRY(hipMemcpyAsync(t->snapLo, t->lo, sizeof(double) * t->Ccap, hipMemcpyDeviceToDevice, t->stream));
+        t->snap_lo_used = t->lo_used;
         LPX_HIP_TRY(hipMemcpyAsync(t->snapUb, t->ub, sizeof(double) * t->Ccap, hipMemcpyDeviceToDevice, t->stream));
         LPX_HIP_TRY(hipMemcpyAsync(t->snapFlip, t->flip, t->Ccap, hipMemcpyDeviceToDevice, t->stream));
     }
@@ -293,9 +301,12 @@ int lpx_tableau_restore(lpx_tableau* t)
     if (t->snap_bounds) {
         LPX_HIP_TRY(hipMemcpyAsync(t->ub, t->snapUb, sizeof(double) * t->Ccap, hipMemcpyDeviceToDevice, t->stream));
         LPX_HIP_TRY(hipMemcpyAsync(t->flip, t->snapFlip, t->Ccap, hipMemcpyDeviceToDevice, t->stream));
-        t->bounds_set = true; t->bounds_C = t->snap_bounds_C;
-    } else if (t->bounds_set) {     // snapshotted before it had bounds: that tableau had no column flipped
+        LPX_HIP_TRY(hipMemcpyAsync(t->lo, t->snapLo, sizeof(double) * t->Ccap, hipMemcpyDeviceToDevice, t->stream));
+        t->bounds_set = true; t->bounds_C = t->snap_bounds_C; t->lo_used = t->snap_lo_used;
+    } else if (t->bounds_set) {     // snapshotted before it had bounds: that tableau had no column flipped or shifted
         LPX_HIP_TRY(hipMemsetAsync(t->flip, 0, t->Ccap, t->stream));
+        LPX_HIP_TRY(hipMemsetAsync(t->lo, 0, sizeof(double) * t->Ccap, t->stream));
+        t->lo_used = false;
     }
     LPX_HIP_TRY(hipMemsetAsync(t->st, 0, sizeof(DevState), t->stream));
     LPX_HIP_TRY(hipStreamSynchronize(t->stream));
@@ -1324,16 +1335,19 @@ int bound_buffers(lpx_tableau* t)
     if (t->ub) return 0;
     LPX_HIP_TRY(hipMalloc((void**)&t->ub, sizeof(double) * t->Ccap));
     LPX_HIP_TRY(hipMalloc((void**)&t->flip, t->Ccap));
+    LPX_HIP_TRY(hipMalloc((void**)&t->lo, sizeof(double) * t->Ccap));
     return 0;
 }
 
-// every live column unbounded and unflipped (a handle without bounds)
+// every live column unbounded, unflipped and unshifted (a handle without bounds)
 int bounds_fill_inf(lpx_tableau* t)
 {
     std::vector<double> inf((size_t)t->Ccap, 1.0 / 0.0);
     LPX_HIP_TRY(hipMemcpyAsync(t->ub, inf.data(), sizeof(double) * t->Ccap, hipMemcpyHostToDevice, t->stream));
     LPX_HIP_TRY(hipMemsetAsync(t->flip, 0, t->Ccap, t->stream));
+    LPX_HIP_TRY(hipMemsetAsync(t->lo, 0, sizeof(double) * t->Ccap, t->stream));      // +0.0
     LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+    t->lo_used = false;
     return 0;
 }
 
@@ -1422,15 +1436,123 @@ int lpx_tableau_bounded_solution(lpx_tableau* t, int nvars, double* x, double* z
         LPX_HIP_TRY(hipMemcpy(ub.data(), t->ub, sizeof(double) * Cm, hipMemcpyDeviceToHost));
         LPX_HIP_TRY(hipMemcpy(flip.data(), t->flip, Cm, hipMemcpyDeviceToHost));
     }
+    std::vector<double> lo;                             // only where a bound change has stored a non-zero lower shift
+    if (t->bounds_set && t->lo_used && Cm > 0) {
+        lo.resize(Cm);
+        LPX_HIP_TRY(hipMemcpy(lo.data(), t->lo, sizeof(double) * Cm, hipMemcpyDeviceToHost));
+    }
     std::vector<double> v(Cm, 0.0);
     std::vector<uint8_t> basic(Cm, 0);
     for (int i = 0; i < m; ++i) if (basis[i] >= 0 && basis[i] < Cm) { v[basis[i]] = rhs[i]; basic[basis[i]] = 1; }
     for (int j = 0; j < nvars; ++j) {
         x[j] = flip[j] ? ub[j] - v[j] : v[j];
+        if (!lo.empty()) x[j] = x[j] + lo[j];
         if (at_upper) at_upper[j] = (flip[j] && !basic[j]) ? 1 : 0;
     }
     if (z) *z = rhs[m];
     return 0;
+}
+
+int lpx_tableau_bound_state(lpx_tableau* t, double* lo, double* ub, uint8_t* flip)
+{
+    if (!t) { set_error("lpx_tableau_bound_state: null handle"); return LPX_EINVAL; }
+    const int n = t->C - 1;
+    if (!t->bounds_set || !t->ub) {
+        for (int j = 0; j < n; ++j) { if (lo) lo[j] = 0.0; if (ub) ub[j] = 1.0 / 0.0; if (flip) flip[j] = 0; }
+        return 0;
+    }
+    if (t->bounds_C != t->C) { set_error("lpx_tableau_bound_state: the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
+    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+    if (lo && n > 0) LPX_HIP_TRY(hipMemcpy(lo, t->lo, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (ub && n > 0) LPX_HIP_TRY(hipMemcpy(ub, t->ub, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (flip && n > 0) LPX_HIP_TRY(hipMemcpy(flip, t->flip, n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int lpx_tableau_change_bounds(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper)
+{
+    if (!t) { set_error("lpx_tableau_change_bounds: null handle"); return LPX_EINVAL; }
+    if (K < 0) { set_error("lpx_tableau_change_bounds: K is negative"); return LPX_EINVAL; }
+    if (K > 0 && (!cols || !lower || !upper)) { set_error("lpx_tableau_change_bounds: null array"); return LPX_EINVAL; }
+    const int Cm = t->C - 1;
+    {
+        std::vector<uint8_t> seen((size_t)(Cm > 0 ? Cm : 1), 0);
+        for (int k = 0; k < K; ++k) {
+            const std::string at = "[" + std::to_string(k) + "]";
+            if (cols[k] < 0 || cols[k] >= Cm) { set_error("lpx_tableau_change_bounds: cols" + at + " is outside [0, C-1)"); return LPX_EINVAL; }
+            if (seen[cols[k]]) { set_error("lpx_tableau_change_bounds: cols" + at + " repeats a column"); return LPX_EINVAL; }
+            seen[cols[k]] = 1;
+            if (lower[k] != lower[k] || upper[k] != upper[k]) { set_error("lpx_tableau_change_bounds: bound" + at + " is NaN"); return LPX_EINVAL; }
+            if (lower[k] == 1.0 / 0.0 || lower[k] == -1.0 / 0.0) { set_error("lpx_tableau_change_bounds: lower" + at + " is not finite"); return LPX_EINVAL; }
+            if (upper[k] < lower[k]) { set_error("lpx_tableau_change_bounds: upper" + at + " is below lower" + at); return LPX_EINVAL; }
+        }
+    }
+    if (!t->bounds_set) { set_error("lpx_tableau_change_bounds: the handle has no bounds (lpx_tableau_set_bounds first)"); return LPX_EINVAL; }
+    if (t->bounds_C != t->C) { set_error("lpx_tableau_change_bounds: the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
+    int rc = ensure_device(); if (rc) return rc;
+    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+    bool any_inf = false, any_lo = false;
+    for (int k = 0; k < K; ++k) { if (upper[k] == 1.0 / 0.0) any_inf = true; if (lower[k] != 0.0) any_lo = true; }
+    if (any_inf) {          // the flip lives on the device; unflipping is not part of this edit
+        std::vector<uint8_t> flip((size_t)Cm);
+        LPX_HIP_TRY(hipMemcpy(flip.data(), t->flip, Cm, hipMemcpyDeviceToHost));
+        for (int k = 0; k < K; ++k)
+            if (upper[k] == 1.0 / 0.0 && flip[cols[k]]) {
+                set_error("lpx_tableau_change_bounds: upper[" + std::to_string(k) + "] = +inf on a flipped column");
+                return LPX_EINVAL;
+            }
+    }
+    t->suspended = t->suspended2 = t->fsuspended = false;
+    if (K > 0) {
+        const size_t need = (size_t)K * (3 * sizeof(double) + sizeof(int32_t));
+        if (need > t->chg_bytes) {
+            hipFree(t->chg); t->chg = nullptr; t->chg_bytes = 0;
+            LPX_HIP_TRY(hipMalloc((void**)&t->chg, 2 * need));
+            t->chg_bytes = 2 * need;
+        }
+        double* d_lower = reinterpret_cast<double*>(t->chg);
+        double* d_upper = d_lower + K;
+        double* d_shift = d_upper + K;
+        int32_t* d_cols = reinterpret_cast<int32_t*>(d_shift + K);
+        LPX_HIP_TRY(hipMemcpyAsync(d_lower, lower, sizeof(double) * K, hipMemcpyHostToDevice, t->stream));
+        LPX_HIP_TRY(hipMemcpyAsync(d_upper, upper, sizeof(double) * K, hipMemcpyHostToDevice, t->stream));
+        LPX_HIP_TRY(hipMemcpyAsync(d_cols, cols, sizeof(int32_t) * K, hipMemcpyHostToDevice, t->stream));
+        LPX_HIP_TRY(launch_change_bounds(t->T, t->ld, t->R, Cm, K, d_cols, d_lower, d_upper, t->ub, t->lo, t->flip, d_shift, t->rhsbuf, t->stream));
+        if (any_lo) t->lo_used = true;
+    }
+    LPX_HIP_TRY(hipMemsetAsync(t->st, 0, sizeof(DevState), t->stream));      // the loop state, as lpx_tableau_build_child resets it
+    LPX_HIP_TRY(hipStreamSynchronize(t->stream));                            // the caller's arrays are free again
+    return 0;
+}
+
+int lpx_bounded_dual_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, void* user, lpx_stats* st)
+{
+    if (!t) { set_error("lpx_bounded_dual_run: null tableau"); return LPX_EINVAL; }
+    lpx_run_opts d; if (!o) { lpx_default_opts(&d, 1); o = &d; }
+    if (t->R < 2) { set_error("lpx_bounded_dual_run: tableau needs at least one constraint row"); return LPX_EINVAL; }
+    if (o->resident > 0) { set_error("lpx_bounded_dual_run: there is no resident form of the bounded dual loop"); return LPX_EINVAL; }
+    if (t->bounds_set && t->bounds_C != t->C) { set_error("lpx_bounded_dual_run: the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
+    int rc = ensure_device(); if (rc) return rc;
+    rc = bound_buffers(t); if (rc) return rc;
+    if (!t->bounds_set) { rc = bounds_fill_inf(t); if (rc) return rc; }
+    BndParams b; std::memset(&b, 0, sizeof(b));
+    b.P = base_params(t, o, MODE_BOUNDED);
+    b.P.us = nullptr; b.P.part_v = nullptr; b.P.part_i = nullptr; b.P.nblk = 0; b.P.qsel = 0;   // single-workgroup select
+    b.ub = t->ub; b.flip = t->flip; b.dual = 1;
+    LoopCtx c; DevState init;
+    make_ctx(t, b.P, b, [b](hipStream_t s, hipEvent_t e0, hipEvent_t e1) -> int {
+        LPX_HIP_TRY(launch_bounded_dual_select(b, s));
+        LPX_HIP_TRY(launch_update(b.P, b.P.pcol, b.P.pcol, s, e0, e1));       // a final status leaves nothing to update
+        return 0;
+    }, c, init);
+    lpx_stats local; std::memset(&local, 0, sizeof(local));
+    t->bcounts[0] = t->bcounts[1] = t->bcounts[2] = 0;
+    rc = run_device_loop(c, init, o, (long long)o->max_iter + 2, cb, user, &local);
+    if (rc < 0) return rc;
+    t->bcounts[0] = t->hst->fdf_count; t->bcounts[1] = t->hst->dual_iter;     // per-kind counts, as lpx_bounded_run keeps them
+    local.pivots = t->bcounts[0] + t->bcounts[1]; local.fdf_pivots = 0; local.cleanup_pivots = 0;
+    if (st) { const double h2d = st->h2d_ms, d2h = st->d2h_ms; *st = local; st->h2d_ms = h2d; st->d2h_ms = d2h; }
+    return rc;
 }
 
 }  // extern "C"

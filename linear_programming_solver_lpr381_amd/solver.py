@@ -322,11 +322,78 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         self.FinalTableau = res.Tableau
         return res
 
+    def OpenBounded(self, problem: LPProblem, upper=None, lower=None) -> "BoundedSession":
+        """SolveBounded that keeps its device tableau (lpx_bounded_open): .result is SolveBounded's result, then
+        .set_bounds(vars, lower, upper) tightens, fixes or loosens bounds and re-optimises with the bounded dual simplex."""
+        return BoundedSession(problem, upper=upper, lower=lower, **self.engine)
+
     def Open(self, problem: LPProblem, **opts) -> "ModelSession":
         """A warm post-optimal session on the device (lpx_session_open): the model is solved once, then ChangeRHS /
         ChangeCost / AddActivity / AddConstraint each re-optimise from the current basis.  opts: extra_rows, extra_cols,
         max_iter, batch, want_tableau (lpx_session_opts)."""
         return ModelSession(problem, **opts)
+
+
+class BoundedSession:       # lpx_bounded_session (include/lpx.h): bound edits re-optimised from the solved tableau
+    def __init__(self, problem: LPProblem, upper=None, lower=None, **engine):
+        n = problem.NumVars
+        self.n = n
+        o, keep = _solve_opts(engine)
+        ps, hold = _problem_struct(problem)
+
+        def _vec(v):
+            if v is None:
+                return None, None
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)))
+            return a, a.ctypes.data_as(_lib.dp)
+        lo, lop = _vec(lower)
+        up, upp = _vec(upper)
+        h = C.c_void_p()
+        r = _lib.Result()
+        self._h = None
+        rc = lib().lpx_bounded_open(C.byref(ps), lop, upp, C.byref(o), C.byref(h), C.byref(r))
+        if rc != 0:
+            raise SolverException(rc, _lib.last_error())
+        self._h = h
+        self.result = self._take(r)
+
+    def _take(self, r) -> SimplexResult:
+        res = _take_result(r, self.n)
+        res.BoundCounts = (int(res.Aux[0]), int(res.Aux[1]), int(res.Aux[2]))
+        return res
+
+    def set_bounds(self, vars, lower, upper) -> SimplexResult:
+        """lower[k] <= x_vars[k] <= upper[k] (the user's absolute bounds; scalars broadcast), then the bounded dual simplex from
+        the tableau as it stands.  Status OPTIMAL or INFEASIBLE; Trace / Stats are this edit's; BoundCounts = (kind 0, kind 1, 1)."""
+        if self._h is None:
+            raise SolverException(_lib.EINVAL, "session is closed")
+        idx = np.ascontiguousarray(np.atleast_1d(vars), dtype=np.int32)
+        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lower, dtype=np.float64), idx.shape))
+        up = np.ascontiguousarray(np.broadcast_to(np.asarray(upper, dtype=np.float64), idx.shape))
+        r = _lib.Result()
+        rc = lib().lpx_bounded_set_bounds(self._h, len(idx), idx.ctypes.data_as(_lib.ip), lo.ctypes.data_as(_lib.dp),
+                                          up.ctypes.data_as(_lib.dp), C.byref(r))
+        if rc != 0:
+            raise SolverException(rc, _lib.last_error())
+        self.result = self._take(r)
+        return self.result
+
+    def close(self):
+        if self._h is not None:
+            lib().lpx_bounded_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class ModelSession:         # lpx_session (include/lpx.h): warm re-optimisation after model edits

@@ -265,6 +265,34 @@ class DeviceTableau:
                                                  up.ctypes.data_as(C.POINTER(C.c_uint8))))
         return x[:nvars], z.value, up[:nvars]
 
+    def bound_state(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(lo, ub, flip) of the columns j < C-1 (lpx_tableau_bound_state); 0 / +inf / 0 on a handle without bounds."""
+        n = max(self.C - 1, 1)
+        lo, ub, flip = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.uint8)
+        check(lib().lpx_tableau_bound_state(self._h, lo.ctypes.data_as(dp), ub.ctypes.data_as(dp),
+                                            flip.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return lo[: self.C - 1], ub[: self.C - 1], flip[: self.C - 1]
+
+    def change_bounds(self, cols, lower, upper):
+        """New absolute bounds lower[k] <= x_cols[k] <= upper[k] on a solved tableau, in place (lpx_tableau_change_bounds):
+        only the RHS column moves, flips and basis stay; re-optimise with bounded_dual_run."""
+        cols = np.ascontiguousarray(np.atleast_1d(cols), dtype=np.int32)
+        lower = np.ascontiguousarray(np.broadcast_to(np.asarray(lower, dtype=np.float64), cols.shape))
+        upper = np.ascontiguousarray(np.broadcast_to(np.asarray(upper, dtype=np.float64), cols.shape))
+        check(lib().lpx_tableau_change_bounds(self._h, len(cols), cols.ctypes.data_as(ip), lower.ctypes.data_as(dp),
+                                              upper.ctypes.data_as(dp)))
+
+    def bounded_dual_run(self, opts: Optional[RunOpts] = None, cb: Optional[PivotCallback] = None,
+                         **kw) -> Tuple[int, dict]:
+        """Bounded dual simplex (lpx_bounded_dual_run): one event per iteration -- a pivot (r, q) on a row whose basic
+        variable is below zero, or (-2 - r, q) on a row whose basic variable is above its upper bound.  Returns
+        (status, stats)."""
+        o = opts if opts is not None else default_opts(True, **kw)
+        st = Stats()
+        c = _wrap_cb(cb)
+        rc = check(lib().lpx_bounded_dual_run(self._h, C.byref(o), c, None, C.byref(st)))
+        return rc, st.as_dict()
+
     def forced_pivots(self, rows, cols, thresh: float = 0.1, opts: Optional[RunOpts] = None,
                       **kw) -> Tuple[np.ndarray, dict]:
         """Gauss-Jordan pivots (Models/PrimalSimplex.cs:245-257) at caller-chosen positions."""
