@@ -24,3 +24,7 @@ for name in ("Primal Simplex", "Revised Primal Simplex", "Branch and Bound"):
 res = solver.SolveBounded(problem, upper=2.0)
 print(f"Bounded Primal Simplex (x <= 2): status {res.Status}, z = {res.OptimalValue}, x = {[float(v) for v in res.Solution]}, "
       f"at upper bound {[int(v) for v in res.AtUpper]}, events (to zero, to upper, flips) {res.BoundCounts}")
+
+# Branch and bound by bound changes (not in the reference): the integer program 0 <= x_j <= 2 on that one tableau.
+res = solver.SolveBnbBounded(problem, upper=2.0)
+print(f"Bounded Branch and Bound (x <= 2, integer): status {res.Status}, z = {res.OptimalValue}, x = {[float(v) for v in res.Solution]}, counters {res.BnbInfo}")

@@ -741,6 +741,109 @@ int  lpx_bounded_set_bounds(lpx_bounded_session* s, int K, const int32_t* vars, 
                             lpx_result* res);
 void lpx_bounded_close(lpx_bounded_session* s);
 
+/* ---- branch and bound by bound changes on one device tableau (not in the reference; csrc/lpx_bnb_bounded.hip,
+ * csrc/host/bnb_bounded.cpp) --
+ * A node of the search is a list of (column, lower, upper) triples applied to ONE handle whose shape never changes: the bound
+ * change of the section above, a repair of dual feasibility by bound flips, a dual loop in which fixed columns do not enter,
+ * and the pick of the branching variable.  No tableau is copied, parked or reshaped.  All arithmetic is IEEE double, no FMA,
+ * true division; no result depends on launch geometry, capacity, batch length or graph replay.
+ *
+ * lpx_tableau_dualize(t, eps, counts): dual-feasibility flips on the live window (R rows, Cm = C-1).  J is the ascending list of
+ * the columns j < Cm with T[m,j] < -eps and 0 < ub[j] < +inf.  For j in J in that order and every row i in [0, R), the
+ * objective row included:
+ *   1. T[i,Cm] = T[i,Cm] - ub[j] * T[i,j] (one multiply, one subtract),
+ *   2. T[i,j] = -T[i,j],
+ * and flip[j] ^= 1 -- the arithmetic of the BOUND FLIP of lpx_bounded_run.  The contiguous RHS copy the loops read is kept
+ * current.  A column with T[m,j] < -eps and ub[j] = +inf cannot be repaired: it is left alone and counted.  A column with
+ * ub[j] == 0 is left alone and not counted (its reduced cost may stay negative: it does not enter the flagged loop below).
+ * Basic columns have reduced cost exactly 0 after a pivot, so the test needs no basis lookup.  counts = {flips, unrepairable}.
+ * Why it is needed: a fixed column that stayed out of the flagged loop may carry a negative reduced cost; when a later node
+ * relaxes its bound, the flip puts the column at its other bound, where its reduced cost is the negation.
+ * LPX_EINVAL before any device check: a NULL handle or counts, eps negative or NaN, a handle without bounds or whose live C
+ * changed since lpx_tableau_set_bounds.
+ *
+ * lpx_bounded_dual_run2(t, o, flags, cb, user, st): lpx_bounded_dual_run with flags.  flags = 0 is lpx_bounded_dual_run bit for
+ * bit.  LPX_BDUAL_SKIP_FIXED: in step 4 of the dual contract a column takes part iff a < -eps AND ub[j] > 0.0; everything else
+ * is lpx_bounded_dual_run.  Precondition of the flagged form, not checked: every nonbasic column with ub[j] > 0 has
+ * T[m,j] >= -eps (lpx_tableau_dualize establishes it).  Why: on branch-and-bound nodes the unflagged rule cycles through
+ * degenerate pivots on fixed columns (ub = 0), which can never change the point; kept out, they cost nothing.  Any other flag
+ * bit is LPX_EINVAL.  The cached graphs of the two forms on one handle are kept apart.
+ *
+ * lpx_tableau_branch_pick(t, nint, is_int, tol, out): for j < nint, x_j is exactly the value lpx_tableau_bounded_solution
+ * returns (v_j = RHS of the row where j is basic, else +0.0; x_j = flip[j] ? ub[j] - v_j : v_j; + lo[j] on a handle that has
+ * stored a non-zero lower shift).  f = x_j - floor(x_j).  j is a candidate iff is_int[j] != 0 (is_int == NULL: every j) and
+ * f > tol and (1 - f) > tol (one subtraction).  dist = |f - 0.5|.  The pick is the candidate of least dist, ties to the lowest
+ * index: the rule of Models/Branch&Bound.cs:197-213.  out = {var or -1, candidates, x_var (0.0 without a pick), z = T[m,Cm]}.
+ * LPX_EINVAL before any device check: a NULL handle or out, nint outside [0, Cm], tol not in [0, 0.5), a handle whose live C
+ * changed since lpx_tableau_set_bounds.  A handle without bounds is read with ub = +inf, flip = 0, lo = 0.
+ *
+ * lpx_bounded_node(t, K, cols, lower, upper, o, nint, is_int, tol, out): one node in one call --
+ * lpx_tableau_change_bounds(t, K, cols, lower, upper), lpx_tableau_dualize(t, o->eps), lpx_bounded_dual_run2(t, o,
+ * LPX_BDUAL_SKIP_FIXED), and on LPX_OPTIMAL lpx_tableau_branch_pick(t, nint, is_int, tol); the bits are those of the four calls
+ * in a row.  o == NULL: lpx_default_opts(o, 1).  The return value is the loop's status (or an error);
+ * out = {status, events, kind-0 events, kind-1 events, dual-feasibility flips, unrepairable, pick}; without LPX_OPTIMAL the
+ * pick is {-1, 0, 0.0, T[m,Cm] as it stands}.  K = 0 is allowed.  A column that would be unrepairable after the change is
+ * LPX_EINVAL with a message, found before the tableau is touched: ub and lo are put back and the handle is as it was.
+ * Argument errors are those of lpx_tableau_change_bounds, plus nint outside [0, Cm], tol not in [0, 0.5), a NULL out and
+ * resident = 1; they are checked before any device check and leave the handle untouched.  No device: LPX_EDEVICE. */
+#define LPX_BDUAL_SKIP_FIXED 1
+typedef struct lpx_branch_pick {
+    int32_t var;           /* branching column, -1 = none (every integer column is integral within tol) */
+    int32_t candidates;    /* fractional integer columns */
+    double x_var;          /* value of the pick */
+    double z;              /* T[m,Cm] */
+} lpx_branch_pick;
+typedef struct lpx_node_record {
+    int32_t status;        /* LPX_OPTIMAL / LPX_INFEASIBLE / LPX_ITER_LIMIT */
+    int32_t events;        /* events of the dual loop */
+    int64_t kind0, kind1;  /* ... per kind */
+    int64_t flips;         /* dual-feasibility flips */
+    int64_t unrepairable;
+    lpx_branch_pick pick;
+} lpx_node_record;
+int lpx_tableau_dualize(lpx_tableau* t, double eps, int64_t counts[2]);
+int lpx_bounded_dual_run2(lpx_tableau* t, const lpx_run_opts* o, int flags, lpx_pivot_cb cb, void* user, lpx_stats* st);
+int lpx_tableau_branch_pick(lpx_tableau* t, int nint, const uint8_t* is_int /* [nint] or NULL = all */, double tol, lpx_branch_pick* out);
+int lpx_bounded_node(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const lpx_run_opts* o,
+                     int nint, const uint8_t* is_int /* [nint] or NULL = all */, double tol, lpx_node_record* out);
+
+/* The model level: max / min c.x, A x <= b, lower <= x <= upper, x_j integer where is_int[j] != 0 (NULL: every variable).
+ * Validation and preparation are those of lpx_solve_bounded (same messages, same lower shift); additionally every integer
+ * variable needs finite, integral lower and upper bounds, else LPX_EINVAL with a message naming the variable -- which is why
+ * a column never has to be unflipped to +inf.  The handle's columns stand for x' = x - lower; the search works on x'.
+ *   Root: lpx_bounded_run.  UNBOUNDED is reported as that.  Then a depth-first stack on the root's handle; node 0 is the root
+ *   itself (K = 0).  A node is its path of (var, lower', upper') overrides of the root bounds.
+ *   Entering a node: the node's bounds are compared with the bounds now on the device and ONE lpx_bounded_node call carries the
+ *   differing columns in ascending column order (the order is part of the contract: the RHS bits depend on it); o->max_iter is
+ *   the event limit of a node, tol = 1e-6 and nint = n.
+ *   INFEASIBLE: pruned.  z <= best + 1e-6 (EPS, Models/Branch&Bound.cs:182; z = T[m,Cm], best starts at -inf): pruned by bound.
+ *   pick.var < 0: a new incumbent, best = z; x' is read once with lpx_tableau_bounded_solution and its integer entries are
+ *   rounded as BestSolution is (:192, Math.Round: half to even).  Otherwise the children are [ceil(x'_var), U'] and
+ *   [L', floor(x'_var)] on var; the ceil child is explored first (:253-257).
+ * The reference's IsFeasible re-check of an incumbent is not mirrored: the dual loop ends primal feasible by construction.
+ * A node that reaches max_iter ends the solve with return value LPX_ITER_LIMIT and a message naming the node; there is no
+ * fallback.  Reaching max_nodes (0 = none) returns LPX_ITER_LIMIT too.  In both cases out holds the incumbent so far.
+ * out: status LPX_OPTIMAL or LPX_INFEASIBLE (no incumbent) or the root's LPX_UNBOUNDED; x in the user's variables (lower
+ * added back); optimal_value in the user's sense (-z for Min) plus the constant c.lower, as lpx_solve_bounded; nodes;
+ * lp_solves = nodes + 1; aux = {nodes, dual events, dual-feasibility flips, incumbents found}; T / basis and stats are the root
+ * solve's (the internal tableau after lpx_bounded_run), the trace is empty; the summary ends with a line of the counters.
+ * info (or NULL): counters {pruned by bound, pruned infeasible, largest K, constant} and one log record per node in the order
+ * visited; free with lpx_bnb_bounded_info_free. */
+typedef struct lpx_bnb_node_log {
+    int32_t depth, K, status, events, flips, var;     /* var: branching variable, -1 = none */
+    double z;                                         /* T[m,Cm] after the node's loop */
+} lpx_bnb_node_log;
+typedef struct lpx_bnb_bounded_info {
+    int64_t nodes, events, flips, incumbents, pruned_bound, pruned_infeasible, max_K;
+    double constant;
+    int64_t n_log;
+    lpx_bnb_node_log* log;   /* [n_log] */
+} lpx_bnb_bounded_info;
+int  lpx_solve_bnb_bounded(const lpx_problem* p, const double* lower /* [n] or NULL = 0 */, const double* upper /* [n] */,
+                           const uint8_t* is_int /* [n] or NULL = all */, const lpx_solve_opts* o, int64_t max_nodes /* 0 = none */,
+                           lpx_result* out, lpx_bnb_bounded_info* info /* or NULL */);
+void lpx_bnb_bounded_info_free(lpx_bnb_bounded_info* info);
+
 #ifdef __cplusplus
 }
 #endif

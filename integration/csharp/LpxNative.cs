@@ -85,6 +85,37 @@ namespace Linear_Programming_Solver.Native
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public struct LpxBranchPick                  // lpx_branch_pick  (lpx_tableau_branch_pick)
+    {
+        public int var, candidates;
+        public double x_var, z;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct LpxNodeRecord                  // lpx_node_record  (lpx_bounded_node)
+    {
+        public int status, events;
+        public long kind0, kind1, flips, unrepairable;
+        public LpxBranchPick pick;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct LpxBnbNodeLog                  // lpx_bnb_node_log  (one node of lpx_solve_bnb_bounded)
+    {
+        public int depth, K, status, events, flips, var;
+        public double z;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct LpxBnbBoundedInfo       // lpx_bnb_bounded_info  (free with lpx_bnb_bounded_info_free)
+    {
+        public long nodes, events, flips, incumbents, pruned_bound, pruned_infeasible, max_K;
+        public double constant;
+        public long n_log;
+        public LpxBnbNodeLog* log;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public unsafe struct LpxBoundedInfo          // lpx_bounded_info  (lpx_solve_bounded; free with lpx_bounded_info_free)
     {
         public int ncols, n;
@@ -230,6 +261,22 @@ namespace Linear_Programming_Solver.Native
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_bounded_set_bounds(IntPtr s, int K, int* vars, double* lower, double* upper, out LpxResult result);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern void lpx_bounded_close(IntPtr s);
+        // branch and bound by bound changes on one device tableau (LPX_BDUAL_SKIP_FIXED = 1: fixed columns do not enter)
+        public const int LPX_BDUAL_SKIP_FIXED = 1;
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_tableau_dualize(IntPtr t, double eps, long* counts);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_bounded_dual_run2(IntPtr t, IntPtr opts, int flags, LpxPivotCb cb, IntPtr user, out LpxStats st);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_tableau_branch_pick(IntPtr t, int nint, byte* is_int, double tol, out LpxBranchPick pick);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_bounded_node(IntPtr t, int K, int* cols, double* lower, double* upper, IntPtr opts,
+                                                  int nint, byte* is_int, double tol, out LpxNodeRecord record);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_bnb_bounded(ref LpxProblem p, double* lower, double* upper, byte* is_int, ref LpxSolveOpts o,
+                                                       long max_nodes, out LpxResult result, out LpxBnbBoundedInfo info);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern void lpx_bnb_bounded_info_free(ref LpxBnbBoundedInfo info);
 
         public static string LastError()
         {

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("LPX_LIB_PATH") or os.path.join(_PKG, "liblpx.so")
 OPTIMAL, UNBOUNDED, INFEASIBLE, ITER_LIMIT, RUNNING = 0, 1, 2, 3, 4
 CUT_INTEGER, CUT_INCOMPLETE, CUT_ERROR, CUT_NOT_OPTIMAL = 0, 10, 11, 12
 EINVAL, EDEVICE, ENOMEM = -1, -2, -3
+BDUAL_SKIP_FIXED = 1        # LPX_BDUAL_SKIP_FIXED (lpx_bounded_dual_run2)
 E_GE_PRESENT, E_NEG_RHS, E_REVISED_PRECOND, E_SINGULAR, E_KNAP_SHAPE, E_UNKNOWN_ALGO, E_PARSE = (
     -10, -11, -12, -13, -14, -15, -16)
 
@@ -102,6 +103,30 @@ class SessionOpts(C.Structure):
 class BoundedInfo(C.Structure):
     """lpx_bounded_info (include/lpx.h): bound states of lpx_solve_bounded's final tableau (freed by lpx_bounded_info_free)."""
     _fields_ = [("ncols", C.c_int), ("n", C.c_int), ("flip", C.POINTER(C.c_uint8)), ("ub", dp), ("lower", dp)]
+
+
+class BranchPick(C.Structure):
+    """lpx_branch_pick (include/lpx.h): the branching variable of a solved bounded tableau."""
+    _fields_ = [("var", C.c_int32), ("candidates", C.c_int32), ("x_var", C.c_double), ("z", C.c_double)]
+
+
+class NodeRecord(C.Structure):
+    """lpx_node_record (include/lpx.h): what one lpx_bounded_node call did."""
+    _fields_ = [("status", C.c_int32), ("events", C.c_int32), ("kind0", C.c_int64), ("kind1", C.c_int64),
+                ("flips", C.c_int64), ("unrepairable", C.c_int64), ("pick", BranchPick)]
+
+
+class BnbNodeLog(C.Structure):
+    """lpx_bnb_node_log (include/lpx.h): one node of lpx_solve_bnb_bounded."""
+    _fields_ = [("depth", C.c_int32), ("K", C.c_int32), ("status", C.c_int32), ("events", C.c_int32),
+                ("flips", C.c_int32), ("var", C.c_int32), ("z", C.c_double)]
+
+
+class BnbBoundedInfo(C.Structure):
+    """lpx_bnb_bounded_info (include/lpx.h): counters and node log of lpx_solve_bnb_bounded (freed by lpx_bnb_bounded_info_free)."""
+    _fields_ = [("nodes", C.c_int64), ("events", C.c_int64), ("flips", C.c_int64), ("incumbents", C.c_int64),
+                ("pruned_bound", C.c_int64), ("pruned_infeasible", C.c_int64), ("max_K", C.c_int64),
+                ("constant", C.c_double), ("n_log", C.c_int64), ("log", C.POINTER(BnbNodeLog))]
 
 
 class Parsed(C.Structure):
@@ -267,6 +292,14 @@ def lib() -> C.CDLL:
     L.lpx_bounded_set_bounds.argtypes = [vp, C.c_int, ip, dp, dp, C.POINTER(Result)]
     L.lpx_bounded_close.argtypes = [vp]
     L.lpx_bounded_close.restype = None
+    L.lpx_tableau_dualize.argtypes = [vp, C.c_double, C.POINTER(C.c_int64)]
+    L.lpx_bounded_dual_run2.argtypes = [vp, C.POINTER(RunOpts), C.c_int, PIVOT_CB, vp, C.POINTER(Stats)]
+    L.lpx_tableau_branch_pick.argtypes = [vp, C.c_int, u8p, C.c_double, C.POINTER(BranchPick)]
+    L.lpx_bounded_node.argtypes = [vp, C.c_int, ip, dp, dp, C.POINTER(RunOpts), C.c_int, u8p, C.c_double, C.POINTER(NodeRecord)]
+    L.lpx_solve_bnb_bounded.argtypes = [C.POINTER(Problem), dp, dp, u8p, C.POINTER(SolveOpts), C.c_int64, C.POINTER(Result),
+                                        C.POINTER(BnbBoundedInfo)]
+    L.lpx_bnb_bounded_info_free.argtypes = [C.POINTER(BnbBoundedInfo)]
+    L.lpx_bnb_bounded_info_free.restype = None
     L.lpx_parse_text.argtypes = [C.c_char_p, C.POINTER(Parsed)]
     L.lpx_parsed_free.argtypes = [C.POINTER(Parsed)]
     L.lpx_parsed_free.restype = None

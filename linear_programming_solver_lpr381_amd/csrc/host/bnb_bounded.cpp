@@ -1,0 +1,147 @@
+// host/bnb_bounded.cpp -- branch and bound by bound changes (lpx_solve_bnb_bounded, include/lpx.h): the root is SolveBounded
+// keeping its handle, and every node after it is ONE lpx_bounded_node call on that handle -- the columns whose bounds differ
+// from the bounds now on the device, in ascending order.  A node is its path of (var, lower, upper) overrides: no tableau is
+// copied, parked or reshaped, and the node store is a few bytes per node.  Search order and pruning are those of
+// Models/Branch&Bound.cs (depth first, ceil child first :253-257, prune at z <= best + EPS :182, branch on the fraction closest
+// to 0.5 :197-213).  Its IsFeasible re-check of an incumbent is not mirrored: the dual loop ends primal feasible by construction.
+#include "model.h"
+
+#include <cmath>
+#include <cstring>
+
+namespace lpx { namespace host {
+
+namespace {
+
+constexpr double EPS = 1e-6;      // Models/Branch&Bound.cs:24
+
+[[noreturn]] void throw_lib(int rc)
+{
+    char buf[1024];
+    lpx_last_error(buf, sizeof(buf));
+    throw LpxException(rc, std::string("liblpx: ") + buf);
+}
+
+struct Override { int var; double lo, ub; };
+struct Node { int depth; std::vector<Override> path; };
+
+}  // namespace
+
+SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
+                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info)
+{
+    const int n = original.NumVars();
+    if ((!lower.empty() && (int)lower.size() != n) || (!upper.empty() && (int)upper.size() != n))
+        throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: lower / upper need one entry per variable");
+    if (!is_int.empty() && (int)is_int.size() != n)
+        throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: the integer mask needs one entry per variable");
+    for (int j = 0; j < n; ++j) {       // the checks of SolveBounded, with its messages, in front of the integer ones
+        const double l = lower.empty() ? 0.0 : lower[j], u = upper.empty() ? 1.0 / 0.0 : upper[j];
+        if (!std::isfinite(l)) throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: lower bound of x" + std::to_string(j + 1) + " is not finite");
+        if (!(u >= l)) throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: upper bound of x" + std::to_string(j + 1) + " is below its lower bound or NaN");
+    }
+    for (int j = 0; j < n; ++j) {
+        if (!is_int.empty() && !is_int[j]) continue;
+        const double l = lower.empty() ? 0.0 : lower[j], u = upper.empty() ? 1.0 / 0.0 : upper[j];
+        if (!std::isfinite(u) || std::floor(l) != l || std::floor(u) != u)
+            throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: integer variable x" + std::to_string(j + 1) +
+                                           " needs finite, integral lower and upper bounds");
+    }
+    if (max_nodes < 0) throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: max_nodes is negative");
+
+    EngineOptions ropt = opt; ropt.quiet = true;
+    BoundedSession ses;
+    BoundedInfo binfo;
+    SimplexResult res = SolveBounded(original, lower, upper, ropt, nullptr, &binfo, &ses);
+    info = BnbBoundedInfo();
+    info.constant = ses.constant;
+    res.Nodes = 0; res.LpSolves = 1;
+    res.Aux = {0.0, 0.0, 0.0, 0.0};
+    if (res.Status != LPX_OPTIMAL) return res;            // an unbounded root is reported as that
+
+    // the handle's columns stand for x' = x - lower: root bounds [0, ub'] of every variable
+    std::vector<double> root_lo((size_t)n, 0.0), root_ub(binfo.ub.begin(), binfo.ub.begin() + n);
+    std::vector<double> cur_lo = root_lo, cur_ub = root_ub, nb_lo, nb_ub;
+    lpx_run_opts o; lpx_default_opts(&o, 1);
+    o.max_iter = opt.max_iter;
+    o.batch = opt.batch > 0 ? opt.batch : 16;             // a node takes a handful of events: short batches, same bits
+    const uint8_t* mask = is_int.empty() ? nullptr : is_int.data();
+
+    double best = -1.0 / 0.0;
+    std::vector<double> best_x;
+    std::vector<Node> stack;
+    stack.push_back(Node{0, {}});
+    std::vector<int32_t> cols; std::vector<double> clo, cub;
+    while (!stack.empty()) {
+        if (max_nodes > 0 && info.nodes >= max_nodes) {
+            info.limit_rc = LPX_ITER_LIMIT;
+            info.limit_msg = "Bounded Branch and Bound: node limit of " + std::to_string(max_nodes) + " reached";
+            break;
+        }
+        Node node = std::move(stack.back());
+        stack.pop_back();
+        const int64_t index = info.nodes++;
+        nb_lo = root_lo; nb_ub = root_ub;
+        for (const Override& v : node.path) { nb_lo[v.var] = v.lo; nb_ub[v.var] = v.ub; }
+        cols.clear(); clo.clear(); cub.clear();
+        for (int j = 0; j < n; ++j)
+            if (nb_lo[j] != cur_lo[j] || nb_ub[j] != cur_ub[j]) { cols.push_back(j); clo.push_back(nb_lo[j]); cub.push_back(nb_ub[j]); }
+        const int K = (int)cols.size();
+        lpx_node_record rec;
+        const int rc = lpx_bounded_node(ses.h, K, cols.data(), clo.data(), cub.data(), &o, n, mask, EPS, &rec);
+        if (rc < 0) throw_lib(rc);
+        cur_lo = nb_lo; cur_ub = nb_ub;
+        info.events += rec.events; info.flips += rec.flips;
+        if (K > info.max_K) info.max_K = K;
+        lpx_bnb_node_log lg;
+        lg.depth = node.depth; lg.K = K; lg.status = rec.status; lg.events = rec.events; lg.flips = (int32_t)rec.flips;
+        lg.var = rec.pick.var; lg.z = rec.pick.z;
+        info.log.push_back(lg);
+        if (rec.status == LPX_ITER_LIMIT) {
+            info.limit_rc = LPX_ITER_LIMIT;
+            info.limit_msg = "Bounded Branch and Bound: node " + std::to_string(index) + " (depth " + std::to_string(node.depth) +
+                             ") reached the iteration limit of " + std::to_string(o.max_iter) + " events";
+            break;
+        }
+        if (rec.status == LPX_INFEASIBLE) { info.pruned_infeasible++; continue; }
+        const double z = rec.pick.z;
+        if (z <= best + EPS) { info.pruned_bound++; continue; }                      // :182
+        if (rec.pick.var < 0) {                                                     // :189-195
+            std::vector<double> x((size_t)n, 0.0);
+            const int rs = lpx_tableau_bounded_solution(ses.h, n, x.data(), nullptr, nullptr);
+            if (rs) throw_lib(rs);
+            for (int j = 0; j < n; ++j) if (is_int.empty() || is_int[j]) x[j] = std::nearbyint(x[j]);
+            best = z; best_x = std::move(x);
+            info.incumbents++;
+            continue;
+        }
+        const int v = rec.pick.var;
+        Node fl{node.depth + 1, node.path}, ce{node.depth + 1, node.path};
+        fl.path.push_back(Override{v, nb_lo[v], std::floor(rec.pick.x_var)});
+        ce.path.push_back(Override{v, std::ceil(rec.pick.x_var), nb_ub[v]});
+        stack.push_back(std::move(fl));
+        stack.push_back(std::move(ce));                                             // explored first (:256)
+    }
+
+    res.Nodes = info.nodes; res.LpSolves = info.nodes + 1;
+    res.Aux = {(double)info.nodes, (double)info.events, (double)info.flips, (double)info.incumbents};
+    res.Trace.clear();
+    if (best_x.empty()) {
+        res.Status = LPX_INFEASIBLE; res.HasSolution = false; res.OptimalValue = 0.0;
+        res.Solution.assign((size_t)n, 0.0);
+        res.Summary = "INFEASIBLE\n"; res.Report = res.Summary;
+        return res;
+    }
+    if (!ses.lower.empty()) for (int j = 0; j < n; ++j) best_x[j] = best_x[j] + ses.lower[j];
+    double value = ses.min ? -best : best;
+    if (ses.shifted) value = value + ses.constant;
+    res.Status = LPX_OPTIMAL; res.HasSolution = true; res.OptimalValue = value; res.Solution = best_x;
+    std::string report;
+    FinalizeText(report, res.Summary, best_x, value, LPX_OPTIMAL);
+    const std::string tail = "  nodes: " + std::to_string(info.nodes) + ", dual events: " + std::to_string(info.events) +
+                             ", dual-feasibility flips: " + std::to_string(info.flips) + "\n";
+    res.Report = report + tail; res.Summary += tail.substr(2);
+    return res;
+}
+
+}}  // namespace lpx::host

@@ -227,6 +227,17 @@ SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>&
 // new absolute bounds of user variables vars[k] on a session: lpx_tableau_change_bounds + lpx_bounded_dual_run (lpx_bounded_set_bounds)
 SimplexResult BoundedSetBounds(BoundedSession& s, int K, const int32_t* vars, const double* lower, const double* upper);
 
+// Branch and bound by bound changes on the root's handle (lpx_solve_bnb_bounded, host/bnb_bounded.cpp).  limit_rc: 0, or
+// LPX_ITER_LIMIT with limit_msg when a node reached max_iter or the search reached max_nodes (the result holds the incumbent so far).
+struct BnbBoundedInfo {
+    int64_t nodes = 0, events = 0, flips = 0, incumbents = 0, pruned_bound = 0, pruned_infeasible = 0, max_K = 0;
+    double constant = 0.0;
+    std::vector<lpx_bnb_node_log> log;
+    int limit_rc = 0; std::string limit_msg;
+};
+SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
+                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info);
+
 // LPParser.ParseFromText, Models/LPParser.cs:9-79.  Throws LpxException(LPX_E_PARSE, message).
 LPProblem ParseFromText(const std::string& input);
 

@@ -19,6 +19,9 @@ namespace lpx {
 
 static constexpr int BDD_LDS_DOUBLES = 4096;
 
+// SKIP_FIXED (lpx_bounded_dual_run2 with LPX_BDUAL_SKIP_FIXED): a column with ub[j] == 0 does not enter.  The unflagged
+// instantiation is the kernel of lpx_bounded_dual_run, unchanged.
+template <bool SKIP_FIXED>
 __global__ __launch_bounds__(SEL_NT) void lpx_bounded_dual_select(BndParams B)
 {
     __shared__ double s_buf[BDD_LDS_DOUBLES];
@@ -74,7 +77,9 @@ __global__ __launch_bounds__(SEL_NT) void lpx_bounded_dual_select(BndParams B)
         for (int j = t; j < rhs; j += SEL_NT) {
             double a = trow[j];
             if (kind && j != p) a = -a;
-            ratios[j] = a < -P.eps ? zrow[j] / (-a) : inf;
+            bool part = a < -P.eps;
+            if constexpr (SKIP_FIXED) part = part && B.ub[j] > 0.0;
+            ratios[j] = part ? zrow[j] / (-a) : inf;
         }
     }
     __syncthreads();
@@ -123,7 +128,8 @@ __global__ __launch_bounds__(SEL_NT) void lpx_bounded_dual_select(BndParams B)
 
 hipError_t launch_bounded_dual_select(const BndParams& b, hipStream_t s)
 {
-    hipLaunchKernelGGL(lpx_bounded_dual_select, dim3(1), dim3(SEL_NT), 0, s, b);
+    if (b.dual == 2) hipLaunchKernelGGL(lpx_bounded_dual_select<true>, dim3(1), dim3(SEL_NT), 0, s, b);
+    else hipLaunchKernelGGL(lpx_bounded_dual_select<false>, dim3(1), dim3(SEL_NT), 0, s, b);
     return hipGetLastError();
 }
 
@@ -168,14 +174,26 @@ __global__ __launch_bounds__(CHG_NT) void lpx_bounds_apply(double* __restrict__ 
     rhsbuf[i] = b;
 }
 
+hipError_t launch_bounds_shift(int K, const int32_t* cols, const double* lower, const double* upper, double* ub, double* lo,
+                               const uint8_t* flip, double* shift, hipStream_t s)
+{
+    hipLaunchKernelGGL(lpx_bounds_shift, dim3((K + CHG_NT - 1) / CHG_NT), dim3(CHG_NT), 0, s, K, cols, lower, upper, ub, lo, flip, shift);
+    return hipGetLastError();
+}
+
+hipError_t launch_bounds_apply(double* T, int ld, int R, int Cm, int K, const int32_t* cols, const double* shift, double* rhsbuf,
+                               hipStream_t s)
+{
+    hipLaunchKernelGGL(lpx_bounds_apply, dim3((R + CHG_NT - 1) / CHG_NT), dim3(CHG_NT), 0, s, T, ld, R, Cm, K, cols, shift, rhsbuf);
+    return hipGetLastError();
+}
+
 hipError_t launch_change_bounds(double* T, int ld, int R, int Cm, int K, const int32_t* cols, const double* lower, const double* upper,
                                 double* ub, double* lo, const uint8_t* flip, double* shift, double* rhsbuf, hipStream_t s)
 {
-    hipLaunchKernelGGL(lpx_bounds_shift, dim3((K + CHG_NT - 1) / CHG_NT), dim3(CHG_NT), 0, s, K, cols, lower, upper, ub, lo, flip, shift);
-    hipError_t e = hipGetLastError();
+    hipError_t e = launch_bounds_shift(K, cols, lower, upper, ub, lo, flip, shift, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(lpx_bounds_apply, dim3((R + CHG_NT - 1) / CHG_NT), dim3(CHG_NT), 0, s, T, ld, R, Cm, K, cols, shift, rhsbuf);
-    return hipGetLastError();
+    return launch_bounds_apply(T, ld, R, Cm, K, cols, shift, rhsbuf, s);
 }
 
 }  // namespace lpx

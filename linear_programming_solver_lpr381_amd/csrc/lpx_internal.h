@@ -57,7 +57,8 @@ struct BndParams {
     SelParams P;
     const double* ub;    // [C-1 capacity] upper bound of every column, +inf = none
     uint8_t* flip;       // [C-1 capacity] 1 = the column stands for u_j - x_j
-    int dual;            // 1 = the record of lpx_bounded_dual_run (read by no kernel: it keeps the two loops' cached graphs apart)
+    int dual;            // 1 = the record of lpx_bounded_dual_run (it keeps the two loops' cached graphs apart), 2 = the record of
+                         // lpx_bounded_dual_run2 with LPX_BDUAL_SKIP_FIXED (the launcher picks the flagged instantiation by it)
 };
 hipError_t launch_bounded_select(const BndParams& b, hipStream_t s);
 // bounded dual simplex and the bound change on a solved tableau (lpx_bounded_dual.hip)
@@ -65,6 +66,29 @@ hipError_t launch_bounded_dual_select(const BndParams& b, hipStream_t s);
 // shift[k] from the old lo / ub / flip of cols[k], new ub / lo stored; then T[:,Cm] and rhsbuf shifted, k in order (R rows)
 hipError_t launch_change_bounds(double* T, int ld, int R, int Cm, int K, const int32_t* cols, const double* lower, const double* upper,
                                 double* ub, double* lo, const uint8_t* flip, double* shift, double* rhsbuf, hipStream_t s);
+
+// branch and bound by bound changes (lpx_bnb_bounded.hip)
+// list[0..count) = ascending columns j < Cm with T[m,j] < -eps and 0 < ub[j] < +inf; cnt = {count, unrepairable}
+hipError_t launch_dualize_list(const double* T, int ld, int R, int Cm, const double* ub, double eps, int32_t* list, int32_t* cnt,
+                               hipStream_t s);
+// every row: RHS -= ub[j] * T[i,j] for j of the list in order, T[i,j] negated; flip[j] ^= 1; rhsbuf kept current
+hipError_t launch_dualize_apply(double* T, int ld, int R, int Cm, const double* ub, uint8_t* flip, const int32_t* list,
+                                const int32_t* cnt, double* rhsbuf, hipStream_t s);
+// ub / lo of cols[0..K) into save[2K] (restore = 0) or back from it (restore = 1)
+hipError_t launch_bounds_save(int K, const int32_t* cols, double* ub, double* lo, double* save, int restore, hipStream_t s);
+// lpx_bounds_shift alone / lpx_bounds_apply alone (launch_change_bounds is the two in a row)
+hipError_t launch_bounds_shift(int K, const int32_t* cols, const double* lower, const double* upper, double* ub, double* lo,
+                               const uint8_t* flip, double* shift, hipStream_t s);
+hipError_t launch_bounds_apply(double* T, int ld, int R, int Cm, int K, const int32_t* cols, const double* shift, double* rhsbuf,
+                               hipStream_t s);
+struct PickParams {
+    const double* T; int ld, R, Cm;
+    const int32_t* basis; const double* ub; const uint8_t* flip; const double* lo;   // lo = nullptr: no lower shift stored
+    int nint; const uint8_t* is_int; double tol;
+    double* ws;          // [nint] values when nint is above the on-chip array
+    lpx_branch_pick* out;
+};
+hipError_t launch_branch_pick(const PickParams& p, hipStream_t s);
 
 // launchers (lpx_kernels.hip)
 hipError_t launch_select(const SelParams& p, hipStream_t s);       // gather-based (dual path)

@@ -355,6 +355,43 @@ int lpx_bounded_set_bounds(lpx_bounded_session* s, int K, const int32_t* vars, c
 
 void lpx_bounded_close(lpx_bounded_session* s) { delete s; }
 
+// ---- branch and bound by bound changes on the root's handle (host/bnb_bounded.cpp) ------------------------------------------
+int lpx_solve_bnb_bounded(const lpx_problem* p, const double* lower, const double* upper, const uint8_t* is_int,
+                          const lpx_solve_opts* o, int64_t max_nodes, lpx_result* out, lpx_bnb_bounded_info* info)
+{
+    if (!p || !out) { set_error("lpx_solve_bnb_bounded: null argument"); return LPX_EINVAL; }
+    std::memset(out, 0, sizeof(*out));
+    if (info) std::memset(info, 0, sizeof(*info));
+    lpx_solve_opts d; if (!o) { lpx_default_solve_opts(&d); o = &d; }
+    return guarded("lpx_solve_bnb_bounded", [&]() -> int {
+        EngineOptions e = to_engine(o);
+        LPProblem q = to_problem(p);
+        std::vector<double> lo, up;
+        std::vector<uint8_t> mask;
+        if (lower) lo.assign(lower, lower + p->n);
+        if (upper) up.assign(upper, upper + p->n);
+        if (is_int) mask.assign(is_int, is_int + p->n);
+        BnbBoundedInfo bi;
+        SimplexResult r = SolveBnbBounded(q, lo, up, mask, e, max_nodes, bi);
+        fill_result(out, r, p->n);
+        if (info) {
+            info->nodes = bi.nodes; info->events = bi.events; info->flips = bi.flips; info->incumbents = bi.incumbents;
+            info->pruned_bound = bi.pruned_bound; info->pruned_infeasible = bi.pruned_infeasible; info->max_K = bi.max_K;
+            info->constant = bi.constant;
+            info->n_log = (int64_t)bi.log.size(); info->log = dup_vec(bi.log);
+        }
+        if (bi.limit_rc) { set_error(bi.limit_msg); return bi.limit_rc; }
+        return 0;
+    });
+}
+
+void lpx_bnb_bounded_info_free(lpx_bnb_bounded_info* info)
+{
+    if (!info) return;
+    std::free(info->log);
+    std::memset(info, 0, sizeof(*info));
+}
+
 int lpx_sensitivity_range_report(const lpx_problem* p, const double* T, int R, int C, const int32_t* basis,
                                  const char* target, char* buf, int len)
 {

@@ -70,6 +70,9 @@ struct lpx_tableau {
     double* lo = nullptr; double* snapLo = nullptr;         // [Ccap] each
     bool lo_used = false, snap_lo_used = false;             // some change has stored a non-zero lo
     char* chg = nullptr; size_t chg_bytes = 0;              // staging of one lpx_tableau_change_bounds: lower, upper, shift, cols
+    // branch and bound by bound changes (lpx_bnb_bounded.hip), on first use: the column list of lpx_tableau_dualize with its two
+    // counts behind it, the device record of lpx_tableau_branch_pick, the integer mask, and the pinned slab the records come back through
+    int32_t* dzl = nullptr; lpx_branch_pick* pickrec = nullptr; uint8_t* pickmask = nullptr; char* nodeslab = nullptr;
 };
 
 void lpx::tableau_view(lpx_tableau* t, TableauView* v)
@@ -223,6 +226,7 @@ void lpx_tableau_destroy(lpx_tableau* t)
     hipFree(t->rgws);
     hipFree(t->ub); hipFree(t->flip); hipFree(t->snapUb); hipFree(t->snapFlip);
     hipFree(t->lo); hipFree(t->snapLo); hipFree(t->chg);
+    hipFree(t->dzl); hipFree(t->pickrec); hipFree(t->pickmask); if (t->nodeslab) hipHostFree(t->nodeslab);
     hipFree(t->xr); hipFree(t->xp); hipFree(t->xgen); hipFree(t->xbasis); hipFree(t->xT); hipFree(t->xc); hipFree(t->xq);
     if (t->hslab) hipHostFree(t->hslab);
     if (t->cutbuf_h) hipHostFree(t->cutbuf_h);
@@ -1339,6 +1343,31 @@ int bound_buffers(lpx_tableau* t)
     return 0;
 }
 
+// the argument checks of lpx_tableau_change_bounds (lpx_bounded_node makes the same ones): LPX_EINVAL with `what` in front
+int check_change_args(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const char* what)
+{
+    const std::string w = what;
+    if (!t) { set_error(w + ": null handle"); return LPX_EINVAL; }
+    if (K < 0) { set_error(w + ": K is negative"); return LPX_EINVAL; }
+    if (K > 0 && (!cols || !lower || !upper)) { set_error(w + ": null array"); return LPX_EINVAL; }
+    const int Cm = t->C - 1;
+    {
+        std::vector<uint8_t> seen((size_t)(Cm > 0 ? Cm : 1), 0);
+        for (int k = 0; k < K; ++k) {
+            const std::string at = "[" + std::to_string(k) + "]";
+            if (cols[k] < 0 || cols[k] >= Cm) { set_error(w + ": cols" + at + " is outside [0, C-1)"); return LPX_EINVAL; }
+            if (seen[cols[k]]) { set_error(w + ": cols" + at + " repeats a column"); return LPX_EINVAL; }
+            seen[cols[k]] = 1;
+            if (lower[k] != lower[k] || upper[k] != upper[k]) { set_error(w + ": bound" + at + " is NaN"); return LPX_EINVAL; }
+            if (lower[k] == 1.0 / 0.0 || lower[k] == -1.0 / 0.0) { set_error(w + ": lower" + at + " is not finite"); return LPX_EINVAL; }
+            if (upper[k] < lower[k]) { set_error(w + ": upper" + at + " is below lower" + at); return LPX_EINVAL; }
+        }
+    }
+    if (!t->bounds_set) { set_error(w + ": the handle has no bounds (lpx_tableau_set_bounds first)"); return LPX_EINVAL; }
+    if (t->bounds_C != t->C) { set_error(w + ": the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
+    return 0;
+}
+
 // every live column unbounded, unflipped and unshifted (a handle without bounds)
 int bounds_fill_inf(lpx_tableau* t)
 {
@@ -1471,25 +1500,9 @@ int lpx_tableau_bound_state(lpx_tableau* t, double* lo, double* ub, uint8_t* fli
 
 int lpx_tableau_change_bounds(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper)
 {
-    if (!t) { set_error("lpx_tableau_change_bounds: null handle"); return LPX_EINVAL; }
-    if (K < 0) { set_error("lpx_tableau_change_bounds: K is negative"); return LPX_EINVAL; }
-    if (K > 0 && (!cols || !lower || !upper)) { set_error("lpx_tableau_change_bounds: null array"); return LPX_EINVAL; }
+    int rc = check_change_args(t, K, cols, lower, upper, "lpx_tableau_change_bounds"); if (rc) return rc;
     const int Cm = t->C - 1;
-    {
-        std::vector<uint8_t> seen((size_t)(Cm > 0 ? Cm : 1), 0);
-        for (int k = 0; k < K; ++k) {
-            const std::string at = "[" + std::to_string(k) + "]";
-            if (cols[k] < 0 || cols[k] >= Cm) { set_error("lpx_tableau_change_bounds: cols" + at + " is outside [0, C-1)"); return LPX_EINVAL; }
-            if (seen[cols[k]]) { set_error("lpx_tableau_change_bounds: cols" + at + " repeats a column"); return LPX_EINVAL; }
-            seen[cols[k]] = 1;
-            if (lower[k] != lower[k] || upper[k] != upper[k]) { set_error("lpx_tableau_change_bounds: bound" + at + " is NaN"); return LPX_EINVAL; }
-            if (lower[k] == 1.0 / 0.0 || lower[k] == -1.0 / 0.0) { set_error("lpx_tableau_change_bounds: lower" + at + " is not finite"); return LPX_EINVAL; }
-            if (upper[k] < lower[k]) { set_error("lpx_tableau_change_bounds: upper" + at + " is below lower" + at); return LPX_EINVAL; }
-        }
-    }
-    if (!t->bounds_set) { set_error("lpx_tableau_change_bounds: the handle has no bounds (lpx_tableau_set_bounds first)"); return LPX_EINVAL; }
-    if (t->bounds_C != t->C) { set_error("lpx_tableau_change_bounds: the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
-    int rc = ensure_device(); if (rc) return rc;
+    rc = ensure_device(); if (rc) return rc;
     LPX_HIP_TRY(hipStreamSynchronize(t->stream));
     bool any_inf = false, any_lo = false;
     for (int k = 0; k < K; ++k) { if (upper[k] == 1.0 / 0.0) any_inf = true; if (lower[k] != 0.0) any_lo = true; }
@@ -1525,7 +1538,11 @@ int lpx_tableau_change_bounds(lpx_tableau* t, int K, const int32_t* cols, const 
     return 0;
 }
 
-int lpx_bounded_dual_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, void* user, lpx_stats* st)
+}  // extern "C"
+
+// lpx_bounded_dual_run (skip_fixed = false) and its flagged form: one body, two parameter records (b.dual = 1 / 2), so that the
+// two forms select their own instantiation of the kernel and key their own cached graph
+static int bounded_dual_run_impl(lpx_tableau* t, const lpx_run_opts* o, bool skip_fixed, lpx_pivot_cb cb, void* user, lpx_stats* st)
 {
     if (!t) { set_error("lpx_bounded_dual_run: null tableau"); return LPX_EINVAL; }
     lpx_run_opts d; if (!o) { lpx_default_opts(&d, 1); o = &d; }
@@ -1538,7 +1555,7 @@ int lpx_bounded_dual_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb,
     BndParams b; std::memset(&b, 0, sizeof(b));
     b.P = base_params(t, o, MODE_BOUNDED);
     b.P.us = nullptr; b.P.part_v = nullptr; b.P.part_i = nullptr; b.P.nblk = 0; b.P.qsel = 0;   // single-workgroup select
-    b.ub = t->ub; b.flip = t->flip; b.dual = 1;
+    b.ub = t->ub; b.flip = t->flip; b.dual = skip_fixed ? 2 : 1;
     LoopCtx c; DevState init;
     make_ctx(t, b.P, b, [b](hipStream_t s, hipEvent_t e0, hipEvent_t e1) -> int {
         LPX_HIP_TRY(launch_bounded_dual_select(b, s));
@@ -1553,6 +1570,197 @@ int lpx_bounded_dual_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb,
     local.pivots = t->bcounts[0] + t->bcounts[1]; local.fdf_pivots = 0; local.cleanup_pivots = 0;
     if (st) { const double h2d = st->h2d_ms, d2h = st->d2h_ms; *st = local; st->h2d_ms = h2d; st->d2h_ms = d2h; }
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// branch and bound by bound changes (include/lpx.h; kernels in lpx_bnb_bounded.hip)
+// ---------------------------------------------------------------------------------------------------
+namespace {
+
+// pinned slab: {int32 cnt[2], pad} at 0, lpx_branch_pick at 16
+struct NodeSlab { int32_t cnt[4]; lpx_branch_pick pick; };
+
+int node_buffers(lpx_tableau* t)
+{
+    if (t->dzl) return 0;
+    LPX_HIP_TRY(hipMalloc((void**)&t->dzl, sizeof(int32_t) * ((size_t)t->Ccap + 4)));
+    LPX_HIP_TRY(hipMalloc((void**)&t->pickrec, sizeof(lpx_branch_pick)));
+    LPX_HIP_TRY(hipMalloc((void**)&t->pickmask, (size_t)t->Ccap));
+    LPX_HIP_TRY(hipHostMalloc((void**)&t->nodeslab, sizeof(NodeSlab)));
+    return 0;
+}
+
+int bounded_ready(lpx_tableau* t)
+{
+    int rc = ensure_device(); if (rc) return rc;
+    rc = bound_buffers(t); if (rc) return rc;
+    if (!t->bounds_set) { rc = bounds_fill_inf(t); if (rc) return rc; }
+    return node_buffers(t);
+}
+
+int check_pick_args(lpx_tableau* t, int nint, double tol, const void* out, const char* what)
+{
+    const std::string w = what;
+    if (!t) { set_error(w + ": null handle"); return LPX_EINVAL; }
+    if (!out) { set_error(w + ": null out"); return LPX_EINVAL; }
+    if (nint < 0 || nint > t->C - 1) { set_error(w + ": nint is outside [0, C-1]"); return LPX_EINVAL; }
+    if (!(tol >= 0.0 && tol < 0.5)) { set_error(w + ": tol is not in [0, 0.5)"); return LPX_EINVAL; }
+    return 0;
+}
+
+// the two dualize launches; the counts stay on the device behind the list
+int enqueue_dualize_list(lpx_tableau* t, double eps)
+{
+    LPX_HIP_TRY(launch_dualize_list(t->T, t->ld, t->R, t->C - 1, t->ub, eps, t->dzl + 4, t->dzl, t->stream));
+    return 0;
+}
+int enqueue_dualize_apply(lpx_tableau* t)
+{
+    LPX_HIP_TRY(launch_dualize_apply(t->T, t->ld, t->R, t->C - 1, t->ub, t->flip, t->dzl + 4, t->dzl, t->rhsbuf, t->stream));
+    return 0;
+}
+
+// the pick launch and the copy of its record into the pinned slab (the caller waits)
+int enqueue_pick(lpx_tableau* t, int nint, const uint8_t* is_int, double tol)
+{
+    if (is_int && nint > 0) LPX_HIP_TRY(hipMemcpyAsync(t->pickmask, is_int, (size_t)nint, hipMemcpyHostToDevice, t->stream));
+    PickParams p; std::memset(&p, 0, sizeof(p));
+    p.T = t->T; p.ld = t->ld; p.R = t->R; p.Cm = t->C - 1;
+    p.basis = t->basis; p.ub = t->ub; p.flip = t->flip; p.lo = t->lo_used ? t->lo : nullptr;
+    p.nint = nint; p.is_int = (is_int && nint > 0) ? t->pickmask : nullptr; p.tol = tol;
+    p.ws = t->ws; p.out = t->pickrec;
+    LPX_HIP_TRY(launch_branch_pick(p, t->stream));
+    NodeSlab* slab = reinterpret_cast<NodeSlab*>(t->nodeslab);
+    LPX_HIP_TRY(hipMemcpyAsync(&slab->pick, t->pickrec, sizeof(lpx_branch_pick), hipMemcpyDeviceToHost, t->stream));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lpx_bounded_dual_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, void* user, lpx_stats* st)
+{
+    return bounded_dual_run_impl(t, o, false, cb, user, st);
+}
+
+int lpx_bounded_dual_run2(lpx_tableau* t, const lpx_run_opts* o, int flags, lpx_pivot_cb cb, void* user, lpx_stats* st)
+{
+    if (flags & ~LPX_BDUAL_SKIP_FIXED) { set_error("lpx_bounded_dual_run2: unknown flag"); return LPX_EINVAL; }
+    return bounded_dual_run_impl(t, o, (flags & LPX_BDUAL_SKIP_FIXED) != 0, cb, user, st);
+}
+
+int lpx_tableau_dualize(lpx_tableau* t, double eps, int64_t counts[2])
+{
+    if (!t) { set_error("lpx_tableau_dualize: null handle"); return LPX_EINVAL; }
+    if (!counts) { set_error("lpx_tableau_dualize: null counts"); return LPX_EINVAL; }
+    if (!(eps >= 0.0)) { set_error("lpx_tableau_dualize: eps is negative or NaN"); return LPX_EINVAL; }
+    if (!t->bounds_set) { set_error("lpx_tableau_dualize: the handle has no bounds (lpx_tableau_set_bounds first)"); return LPX_EINVAL; }
+    if (t->bounds_C != t->C) { set_error("lpx_tableau_dualize: the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
+    if (t->R < 1 || t->C < 1) { set_error("lpx_tableau_dualize: empty tableau"); return LPX_EINVAL; }
+    int rc = bounded_ready(t); if (rc) return rc;
+    t->suspended = t->suspended2 = t->fsuspended = false;
+    rc = enqueue_dualize_list(t, eps); if (rc) return rc;
+    rc = enqueue_dualize_apply(t); if (rc) return rc;
+    NodeSlab* slab = reinterpret_cast<NodeSlab*>(t->nodeslab);
+    LPX_HIP_TRY(hipMemcpyAsync(slab->cnt, t->dzl, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
+    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+    counts[0] = slab->cnt[0]; counts[1] = slab->cnt[1];
+    return 0;
+}
+
+int lpx_tableau_branch_pick(lpx_tableau* t, int nint, const uint8_t* is_int, double tol, lpx_branch_pick* out)
+{
+    int rc = check_pick_args(t, nint, tol, out, "lpx_tableau_branch_pick"); if (rc) return rc;
+    if (t->bounds_set && t->bounds_C != t->C) { set_error("lpx_tableau_branch_pick: the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
+    if (t->R < 1 || t->C < 1) { set_error("lpx_tableau_branch_pick: empty tableau"); return LPX_EINVAL; }
+    rc = bounded_ready(t); if (rc) return rc;
+    rc = enqueue_pick(t, nint, is_int, tol); if (rc) return rc;
+    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+    *out = reinterpret_cast<NodeSlab*>(t->nodeslab)->pick;
+    return 0;
+}
+
+int lpx_bounded_node(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const lpx_run_opts* o,
+                     int nint, const uint8_t* is_int, double tol, lpx_node_record* out)
+{
+    int rc = check_change_args(t, K, cols, lower, upper, "lpx_bounded_node"); if (rc) return rc;
+    rc = check_pick_args(t, nint, tol, out, "lpx_bounded_node"); if (rc) return rc;
+    lpx_run_opts d; if (!o) { lpx_default_opts(&d, 1); o = &d; }
+    if (t->R < 2) { set_error("lpx_bounded_node: tableau needs at least one constraint row"); return LPX_EINVAL; }
+    if (o->resident > 0) { set_error("lpx_bounded_node: there is no resident form of the bounded dual loop"); return LPX_EINVAL; }
+    if (!(o->eps >= 0.0)) { set_error("lpx_bounded_node: eps is negative or NaN"); return LPX_EINVAL; }
+    const int Cm = t->C - 1;
+    rc = bounded_ready(t); if (rc) return rc;
+    std::memset(out, 0, sizeof(*out));
+    out->pick.var = -1;
+    bool any_inf = false, any_lo = false;
+    for (int k = 0; k < K; ++k) { if (upper[k] == 1.0 / 0.0) any_inf = true; if (lower[k] != 0.0) any_lo = true; }
+    if (any_inf) {          // as lpx_tableau_change_bounds: unflipping is not part of the edit
+        std::vector<uint8_t> flip((size_t)Cm);
+        LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+        LPX_HIP_TRY(hipMemcpy(flip.data(), t->flip, Cm, hipMemcpyDeviceToHost));
+        for (int k = 0; k < K; ++k)
+            if (upper[k] == 1.0 / 0.0 && flip[cols[k]]) {
+                set_error("lpx_bounded_node: upper[" + std::to_string(k) + "] = +inf on a flipped column");
+                return LPX_EINVAL;
+            }
+    }
+    // staging of the edit: lower, upper, shift, the saved (ub, lo) pairs, cols
+    double *d_lower = nullptr, *d_upper = nullptr, *d_shift = nullptr, *d_save = nullptr; int32_t* d_cols = nullptr;
+    if (K > 0) {
+        const size_t need = (size_t)K * (5 * sizeof(double) + sizeof(int32_t));
+        if (need > t->chg_bytes) {
+            LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+            hipFree(t->chg); t->chg = nullptr; t->chg_bytes = 0;
+            LPX_HIP_TRY(hipMalloc((void**)&t->chg, 2 * need));
+            t->chg_bytes = 2 * need;
+        }
+        d_lower = reinterpret_cast<double*>(t->chg);
+        d_upper = d_lower + K; d_shift = d_upper + K; d_save = d_shift + K;
+        d_cols = reinterpret_cast<int32_t*>(d_save + 2 * (size_t)K);
+        LPX_HIP_TRY(hipMemcpyAsync(d_lower, lower, sizeof(double) * K, hipMemcpyHostToDevice, t->stream));
+        LPX_HIP_TRY(hipMemcpyAsync(d_upper, upper, sizeof(double) * K, hipMemcpyHostToDevice, t->stream));
+        LPX_HIP_TRY(hipMemcpyAsync(d_cols, cols, sizeof(int32_t) * K, hipMemcpyHostToDevice, t->stream));
+        // the new ub and lo first (small arrays only): the list of the flips needs them, and the tableau is still untouched
+        LPX_HIP_TRY(launch_bounds_save(K, d_cols, t->ub, t->lo, d_save, 0, t->stream));
+        LPX_HIP_TRY(launch_bounds_shift(K, d_cols, d_lower, d_upper, t->ub, t->lo, t->flip, d_shift, t->stream));
+    }
+    // the list reads the objective row left of the RHS, which the RHS shift of the edit does not write: listing before that
+    // shift gives the list of listing after it, and an unrepairable column is found with the tableau as it was
+    rc = enqueue_dualize_list(t, o->eps); if (rc) return rc;
+    NodeSlab* slab = reinterpret_cast<NodeSlab*>(t->nodeslab);
+    LPX_HIP_TRY(hipMemcpyAsync(slab->cnt, t->dzl, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
+    // wait 1: the counts (the caller's arrays are free again)
+    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+    out->flips = slab->cnt[0]; out->unrepairable = slab->cnt[1];
+    if (out->unrepairable > 0) {
+        LPX_HIP_TRY(launch_bounds_save(K, d_cols, t->ub, t->lo, d_save, 1, t->stream));     // ub and lo as they were
+        LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+        out->flips = 0;
+        set_error("lpx_bounded_node: " + std::to_string(out->unrepairable) + " column(s) with a negative reduced cost and no upper "
+                  "bound: a bound flip cannot restore dual feasibility");
+        return LPX_EINVAL;
+    }
+    t->suspended = t->suspended2 = t->fsuspended = false;
+    if (any_lo) t->lo_used = true;
+    if (K > 0) LPX_HIP_TRY(launch_bounds_apply(t->T, t->ld, t->R, Cm, K, d_cols, d_shift, t->rhsbuf, t->stream));
+    rc = enqueue_dualize_apply(t); if (rc) return rc;
+    // the loop (it resets the state record itself and waits once per batch)
+    const int status = bounded_dual_run_impl(t, o, true, nullptr, nullptr, nullptr);
+    if (status < 0) return status;
+    out->status = status; out->events = t->hst->iter; out->kind0 = t->bcounts[0]; out->kind1 = t->bcounts[1];
+    if (status == LPX_OPTIMAL) {
+        rc = enqueue_pick(t, nint, is_int, tol); if (rc) return rc;
+        LPX_HIP_TRY(hipStreamSynchronize(t->stream));                                    // last wait: the pick record
+        out->pick = slab->pick;
+    } else {
+        // no pick: z as the tableau stands, through the same slab
+        LPX_HIP_TRY(hipMemcpyAsync(&slab->pick.z, t->T + (size_t)(t->R - 1) * t->ld + Cm, sizeof(double), hipMemcpyDeviceToHost, t->stream));
+        LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+        out->pick.var = -1; out->pick.candidates = 0; out->pick.x_var = 0.0; out->pick.z = slab->pick.z;
+    }
+    return status;
 }
 
 }  // extern "C"

@@ -201,6 +201,11 @@ def _take_result(r, n: int) -> "SimplexResult":
     return res
 
 
+# lpx_bnb_node_log as a NumPy record
+BNB_LOG_DTYPE = np.dtype([("depth", "<i4"), ("K", "<i4"), ("status", "<i4"), ("events", "<i4"), ("flips", "<i4"),
+                          ("var", "<i4"), ("z", "<f8")])
+
+
 class LPSolver:             # Models/LPSolver.cs:6-77
     def __init__(self, **engine):
         self.engine = engine
@@ -320,6 +325,48 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         res.AtUpper = ((flips[:n] != 0) & ~basic[:n]).astype(np.uint8)
         res.BoundCounts = (int(res.Aux[0]), int(res.Aux[1]), int(res.Aux[2]))
         self.FinalTableau = res.Tableau
+        return res
+
+    def SolveBnbBounded(self, problem: LPProblem, upper, lower=None, integer=None, max_nodes: int = 0) -> SimplexResult:
+        """Branch and bound by bound changes on one device tableau (lpx_solve_bnb_bounded): lower <= x <= upper, x_j integer
+        where integer[j] (None: every variable); integer variables need finite, integral bounds.  Status OPTIMAL or INFEASIBLE,
+        Solution, OptimalValue (user's sense), Nodes, BnbInfo (counters) and BnbLog, a structured array with one record per node
+        (depth, K, status, events, flips, var, z).  A node or search limit raises SolverException(ITER_LIMIT) whose .result
+        holds the incumbent so far."""
+        n = problem.NumVars
+        o, keep = _solve_opts(self.engine)
+        ps, hold = _problem_struct(problem)
+
+        def _vec(v):
+            if v is None:
+                return None, None
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)))
+            return a, a.ctypes.data_as(_lib.dp)
+        lo, lop = _vec(lower)
+        up, upp = _vec(upper)
+        mask, mp = None, None
+        if integer is not None:
+            mask = np.ascontiguousarray(np.broadcast_to(np.asarray(integer, dtype=np.uint8), (n,)))
+            mp = mask.ctypes.data_as(C.POINTER(C.c_uint8))
+        r, info = _lib.Result(), _lib.BnbBoundedInfo()
+        rc = lib().lpx_solve_bnb_bounded(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), C.byref(r), C.byref(info))
+        if rc != 0 and rc != _lib.ITER_LIMIT:
+            raise SolverException(rc, _lib.last_error())
+        msg = _lib.last_error() if rc else ""
+        try:
+            log = np.zeros(info.n_log, dtype=BNB_LOG_DTYPE)
+            if info.n_log:
+                C.memmove(log.ctypes.data, info.log, info.n_log * C.sizeof(_lib.BnbNodeLog))
+            counters = {k: getattr(info, k) for k in ("nodes", "events", "flips", "incumbents", "pruned_bound",
+                                                      "pruned_infeasible", "max_K", "constant")}
+        finally:
+            lib().lpx_bnb_bounded_info_free(C.byref(info))
+        res = _take_result(r, n)
+        res.BnbLog, res.BnbInfo = log, counters
+        if rc != 0:
+            e = SolverException(rc, msg)
+            e.result = res
+            raise e
         return res
 
     def OpenBounded(self, problem: LPProblem, upper=None, lower=None) -> "BoundedSession":

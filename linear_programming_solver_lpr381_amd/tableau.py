@@ -283,15 +283,57 @@ class DeviceTableau:
                                               upper.ctypes.data_as(dp)))
 
     def bounded_dual_run(self, opts: Optional[RunOpts] = None, cb: Optional[PivotCallback] = None,
-                         **kw) -> Tuple[int, dict]:
+                         skip_fixed: bool = False, **kw) -> Tuple[int, dict]:
         """Bounded dual simplex (lpx_bounded_dual_run): one event per iteration -- a pivot (r, q) on a row whose basic
-        variable is below zero, or (-2 - r, q) on a row whose basic variable is above its upper bound.  Returns
-        (status, stats)."""
+        variable is below zero, or (-2 - r, q) on a row whose basic variable is above its upper bound.  skip_fixed=True is
+        lpx_bounded_dual_run2 with LPX_BDUAL_SKIP_FIXED: a column with ub = 0 does not enter.  Returns (status, stats)."""
         o = opts if opts is not None else default_opts(True, **kw)
         st = Stats()
         c = _wrap_cb(cb)
-        rc = check(lib().lpx_bounded_dual_run(self._h, C.byref(o), c, None, C.byref(st)))
+        if skip_fixed:
+            rc = check(lib().lpx_bounded_dual_run2(self._h, C.byref(o), _lib.BDUAL_SKIP_FIXED, c, None, C.byref(st)))
+        else:
+            rc = check(lib().lpx_bounded_dual_run(self._h, C.byref(o), c, None, C.byref(st)))
         return rc, st.as_dict()
+
+    def dualize(self, eps: float = 1e-9) -> Tuple[int, int]:
+        """Dual-feasibility flips (lpx_tableau_dualize): every column with a reduced cost below -eps and a finite, positive
+        upper bound is flipped to its other bound, in ascending order.  Returns (flips, unrepairable)."""
+        k = (C.c_int64 * 2)()
+        check(lib().lpx_tableau_dualize(self._h, float(eps), k))
+        return int(k[0]), int(k[1])
+
+    @staticmethod
+    def _mask(is_int, nint):
+        if is_int is None:
+            return None, None
+        a = np.ascontiguousarray(is_int, dtype=np.uint8)
+        assert a.shape == (nint,)
+        return a, a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+    def branch_pick(self, nint: int, is_int=None, tol: float = 1e-6) -> dict:
+        """The branching variable of the tableau as it stands (lpx_tableau_branch_pick): the integer column j < nint whose
+        fraction is closest to 0.5, lowest index on ties.  Returns {var (-1: none), candidates, x_var, z}."""
+        keep, mp = self._mask(is_int, int(nint))
+        out = _lib.BranchPick()
+        check(lib().lpx_tableau_branch_pick(self._h, int(nint), mp, float(tol), C.byref(out)))
+        return {"var": out.var, "candidates": out.candidates, "x_var": out.x_var, "z": out.z}
+
+    def bounded_node(self, cols, lower, upper, nint: int, is_int=None, tol: float = 1e-6,
+                     opts: Optional[RunOpts] = None, **kw) -> dict:
+        """One branch-and-bound node in one call (lpx_bounded_node): change_bounds, dualize, the dual loop in which fixed
+        columns do not enter, and on OPTIMAL the branch pick.  Returns the node record as a dict."""
+        cols = np.ascontiguousarray(np.atleast_1d(cols), dtype=np.int32).reshape(-1)
+        lower = np.ascontiguousarray(np.broadcast_to(np.asarray(lower, dtype=np.float64), cols.shape))
+        upper = np.ascontiguousarray(np.broadcast_to(np.asarray(upper, dtype=np.float64), cols.shape))
+        o = opts if opts is not None else default_opts(True, **kw)
+        keep, mp = self._mask(is_int, int(nint))
+        rec = _lib.NodeRecord()
+        check(lib().lpx_bounded_node(self._h, len(cols), cols.ctypes.data_as(ip), lower.ctypes.data_as(dp),
+                                     upper.ctypes.data_as(dp), C.byref(o), int(nint), mp, float(tol), C.byref(rec)))
+        return {"status": rec.status, "events": rec.events, "kind0": rec.kind0, "kind1": rec.kind1, "flips": rec.flips,
+                "unrepairable": rec.unrepairable, "var": rec.pick.var, "candidates": rec.pick.candidates,
+                "x_var": rec.pick.x_var, "z": rec.pick.z}
 
     def forced_pivots(self, rows, cols, thresh: float = 0.1, opts: Optional[RunOpts] = None,
                       **kw) -> Tuple[np.ndarray, dict]:

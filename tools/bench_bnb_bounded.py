@@ -1,0 +1,133 @@
+"""Branch and bound to optimality, two ways on the device, on random 0/1 programs.
+
+For each model -- synth.binary_ip(60, 12) and synth.binary_ip(128, 64) --
+  (a) rows:    the bounds as explicit rows; the warm engine search BranchAndBound(bnb_mode=1, bnb_search=2, bnb_dive=1,
+               concurrent_nodes=128): a new row and slack column per node, children assembled from parked parent tableaux
+  (b) bounded: the bounds beside the tableau; LPSolver().SolveBnbBounded: one handle whose shape never changes, a node is a
+               list of (column, lower, upper) triples (lpx_bounded_node)
+Profiler off, both sides warm (two untimed solves each), the sides alternating, REPS timed solves.  A timed solve is the whole
+call, model preparation and root solve included.  Prints one JSON line: per side the median / min / max milliseconds to
+optimality and nodes/s, node counts and optima (the two searches must reach the same optimum; they follow different paths
+through alternative optima, so the node counts may differ); for (b) the mean events per node, the wall microseconds per node,
+and the wall microseconds of a K = 0 node call on the solved root -- the fixed cost of a node outside its events: five small
+launches, one batch of the loop and three waits (host time outside the kernels proper needs a kernel trace and is not
+collected here); and the device memory each side added (hipMemGetInfo through torch, read before the first solve and after
+each side's first solve; handle caches keep what they allocated, so the reading after a solve is that side's peak).
+
+`--model NAME` keeps one of the two models (bip_60x12, bip_128x64); `--max-nodes N` bounds both searches (then neither
+reaches optimality and the optima are incumbents so far).
+
+usage: bench_bnb_bounded.py [--model NAME] [--max-nodes N] [REPS]"""
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import linear_programming_solver_lpr381_amd as L
+from linear_programming_solver_lpr381_amd import synth
+
+
+def models():
+    yield "bip_60x12", 60, 12
+    yield "bip_128x64", 128, 64
+
+
+def stats(ts):
+    return {"median": statistics.median(ts), "min": min(ts), "max": max(ts), "samples": len(ts)} if ts else None
+
+
+def device_used_mb():
+    try:
+        import torch
+        free, total = torch.cuda.mem_get_info()
+        return (total - free) / 2 ** 20
+    except Exception:
+        return None
+
+
+def main():
+    args = sys.argv[1:]
+    only, max_nodes = None, 0
+    for flag in ("--model", "--max-nodes"):
+        if flag in args:
+            k = args.index(flag)
+            if flag == "--model":
+                only = args[k + 1]
+            else:
+                max_nodes = int(args[k + 1])
+            del args[k:k + 2]
+    reps = int(args[0]) if args else 7
+    lib = L._lib.lib()
+    L._lib.check(lib.lpx_init(0))
+    out = {}
+    for name, n, m in models():
+        if only is not None and name != only:
+            continue
+        c, A, rel, b = synth.binary_ip(n, m)
+        rows_p = L.LPProblem.from_arrays(0, c, A, rel, b)
+        bnd_p = L.LPProblem.from_arrays(0, c, A[:m], rel[:m], b[:m])
+        rec = {"n": n, "m": m, "rows_shape": [m + n + 1, 2 * n + m + 1], "bounded_shape": [m + 1, n + m + 1]}
+
+        def run_rows():
+            t0 = time.perf_counter()
+            r = L.BranchAndBound(bnb_mode=1, bnb_search=2, bnb_dive=1, concurrent_nodes=128, max_nodes=max_nodes).Solve(rows_p)
+            return 1e3 * (time.perf_counter() - t0), r
+
+        def run_bounded():
+            t0 = time.perf_counter()
+            try:
+                r = L.LPSolver().SolveBnbBounded(bnd_p, 1.0, max_nodes=max_nodes)
+            except L.SolverException as e:
+                if e.code != L._lib.ITER_LIMIT or not max_nodes:
+                    raise
+                r = e.result
+            return 1e3 * (time.perf_counter() - t0), r
+
+        base = device_used_mb()
+        ta, tb, na, nb = [], [], [], []
+        peak_a = peak_b = None
+        for i in range(reps + 2):
+            ms, ra = run_rows()
+            if i == 0:
+                peak_a = device_used_mb()
+            if i >= 2:
+                ta.append(ms); na.append(ra.LpSolves / (ms / 1e3))
+            ms, rb = run_bounded()
+            if i == 0:
+                peak_b = device_used_mb()
+            if i >= 2:
+                tb.append(ms); nb.append(rb.Nodes / (ms / 1e3))
+        rec["rows"] = {"ms": stats(ta), "nodes_per_s": stats(na), "lp_solves": int(ra.LpSolves), "nodes": int(ra.Nodes),
+                       "optimum": ra.OptimalValue}
+        info = rb.BnbInfo
+        rec["bounded"] = {"ms": stats(tb), "nodes_per_s": stats(nb), "nodes": int(rb.Nodes), "optimum": rb.OptimalValue,
+                          "events": info["events"], "flips": info["flips"], "max_K": info["max_K"],
+                          "events_per_node": info["events"] / max(1, rb.Nodes),
+                          "wall_us_per_node": 1e3 * statistics.median(tb) / max(1, rb.Nodes)}
+        rec["same_optimum"] = bool(abs(ra.OptimalValue - rb.OptimalValue) <= 1e-9 * max(1.0, abs(ra.OptimalValue)))
+        if base is not None:
+            # (a) ran first: its reading is its own footprint; (b)'s is what it added on top (caches of (a) stay allocated)
+            rec["device_mb"] = {"before": base, "after_rows_first_solve": peak_a, "after_bounded_first_solve": peak_b,
+                                "rows_added": peak_a - base, "bounded_added": peak_b - peak_a}
+        # the fixed cost of a node: a K = 0 node call on a solved root (no event, no flip)
+        T, basis = synth.primal_tableau_from(c, A[:m], b[:m])
+        ub = np.full(T.shape[1] - 1, np.inf); ub[:n] = 1.0
+        with L.DeviceTableau.from_host(T, basis) as dt:
+            dt.set_bounds(ub)
+            dt.bounded_run()
+            for _ in range(20):
+                dt.bounded_node([], [], [], n, batch=16)
+            t0 = time.perf_counter()
+            for _ in range(200):
+                dt.bounded_node([], [], [], n, batch=16)
+            rec["bounded"]["empty_node_us"] = 1e6 * (time.perf_counter() - t0) / 200
+        out[name] = rec
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
