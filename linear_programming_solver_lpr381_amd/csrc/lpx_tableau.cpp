@@ -475,8 +475,10 @@ static bool fused_buffers(lpx_tableau* t)
     return true;
 }
 
-// measured on MI355X: 4097 x 12289 (403 MB) 118.9 us per pivot at d = 1, 34.9 at 12, 35.2 at 16 (the sweep 150
-// against 164 us); 1025 x 3073 (25 MB) 66 k pivots/s at d = 1, 79 k at 2, 82 k at 4, 80 k at 8
+// measured on MI355X with the select-only launch at 24.3 us: 4097 x 12289 (403 MB) 118.9 us per pivot at d = 1,
+// 34.9 at 12, 35.2 at 16 (the sweep 150 against 164 us); 1025 x 3073 (25 MB) 66 k pivots/s at d = 1, 79 k at 2, 82 k at 4, 80 k
+// at 8.  With the launch at 22.3 us (lpx_pivot_select in one pass of 9 rows per lane, handles above 64 MB) d = 12 ran 33.2 us per
+// pivot; the other depths, and every depth with that kernel in passes of 3 rows per lane as it stands: not measured.  Up to 64 MB the select-only kernel is the one these figures were taken with
 static constexpr int PIVOT_DEFER_LARGE = 12, PIVOT_DEFER_SMALL = 4;
 static constexpr size_t PIVOT_DEFER_LARGE_BYTES = (size_t)64 << 20;
 // Pivots per sweep of run_fused (LPX_PIVOT_DEFER=d, read once; DESIGN.md 4.1 has the measured table behind the default).
