@@ -188,12 +188,4 @@ hipError_t launch_bounds_apply(double* T, int ld, int R, int Cm, int K, const in
     return hipGetLastError();
 }
 
-hipError_t launch_change_bounds(double* T, int ld, int R, int Cm, int K, const int32_t* cols, const double* lower, const double* upper,
-                                double* ub, double* lo, const uint8_t* flip, double* shift, double* rhsbuf, hipStream_t s)
-{
-    hipError_t e = launch_bounds_shift(K, cols, lower, upper, ub, lo, flip, shift, s);
-    if (e != hipSuccess) return e;
-    return launch_bounds_apply(T, ld, R, Cm, K, cols, shift, rhsbuf, s);
-}
-
 }  // namespace lpx

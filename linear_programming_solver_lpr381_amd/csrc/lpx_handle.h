@@ -1,0 +1,123 @@
+// lpx_handle.h -- the tableau handle and the host helpers its translation units share (lpx_tableau.cpp, lpx_tableau_bounded.cpp,
+// lpx_tableau_nodes.cpp).  Host .cpp files of this directory only: kernels and launchers see lpx_internal.h, never the struct.
+#pragma once
+#include "lpx_internal.h"
+
+#include <cstring>
+
+struct lpx_tableau {
+    int R = 0, C = 0, ld = 0;   // live shape (<= capacity) and leading dimension (from the capacity)
+    int Rcap = 0, Ccap = 0;
+    char* slab = nullptr;       // device slab holding every small buffer below (all but T)
+    char* hslab = nullptr;      // pinned slab holding hst and shape_h
+    int32_t* shape = nullptr;   // device record {R, C} read by the kernels
+    int32_t* shape_h = nullptr; // pinned staging
+    double* T = nullptr;        // [R*ld]
+    double* snapT = nullptr;    // snapshot
+    double* prow = nullptr;     // [ld]
+    double* pcol = nullptr;     // [R]
+    double* col0 = nullptr;     // [R] lookahead column buffers (ping-pong)
+    double* col1 = nullptr;
+    double* rhsbuf = nullptr;   // [R]
+    double* ws = nullptr;       // [MB_MAXB * max(R,C)]
+    double* part_v = nullptr; int32_t* part_i = nullptr;   // [64] partial argmins of the multi-workgroup select
+    lpx::DevState* us = nullptr;    // state record written by the update kernel (multi-workgroup protocol)
+    int use_mb = 1;
+    int32_t* basis = nullptr;   // [R-1]
+    int32_t* snapBasis = nullptr;
+    int32_t* trace = nullptr;   // [2*trace_cap]
+    int trace_cap = 0;
+    lpx::DevState* st = nullptr;    // device
+    lpx::DevState* hst = nullptr;   // pinned host mirror
+    bool suspended = false;     // lpx_multi_run_some left this run unfinished: *hst is where it continues
+    int32_t* frows = nullptr; int32_t* fcols = nullptr; int32_t* fchosen = nullptr; int fcap = 0;
+    char* cutbuf = nullptr; char* cutbuf_h = nullptr; int cutcap = 0;   // staging of branching-row descriptors
+    hipStream_t stream = nullptr;
+    // cached graph of `g_batch` (select, update) pairs
+    hipGraphExec_t gexec = nullptr;
+    int g_batch = 0;
+    std::string g_key;
+    std::vector<hipEvent_t> events;
+    // resident primal loop: exchange buffers (tagged granules) and the generation counter
+    unsigned long long* xr = nullptr; unsigned long long* xp = nullptr; unsigned* xgen = nullptr;
+    int32_t* xbasis = nullptr;      // basis as it was when the current resident launch started
+    double* xT = nullptr;           // tableau as it was when the current resident launch started (put back if the launch aborts)
+    unsigned long long* xc = nullptr; unsigned long long* xq = nullptr;   // column-owning resident kernel: candidates / candidate columns
+    size_t xc_bytes = 0, xq_bytes = 0;
+    bool resident_off = false;      // a resident launch could not get its workgroups co-resident: stay on the streaming path
+    // fused pivot (lpx_pivot_fused): second tableau buffer and the index-1 copies of the small per-pivot vectors, on first use
+    double* fT = nullptr; char* fslab = nullptr;
+    double* fprow = nullptr; double* frhs = nullptr; lpx::DevState* frec = nullptr;
+    char* dring = nullptr; int dring_slots = 0;   // deferred pivots of run_fused: ring of pivot rows, factor columns, row indices
+    bool fused_off = false;         // the second buffer did not fit: stay on the two-launch path
+    bool suspended2 = false;        // ... by the two-launch group kernels (it must continue there: no pending pivot, state in *hst)
+    bool fsuspended = false; int frec_cur = 0;   // fused group run left unfinished: its records (latest: index frec_cur) are in place
+    char* rgws = nullptr; size_t rgws_bytes = 0;  // lpx_tableau_ranging's partial slabs and outputs / the cut round's plan, on first use
+    // Bounded-variable family (lpx_tableau_bounded.cpp): everything it keeps beside the tableau, on first use.
+    struct __attribute__((visibility("hidden"))) Bounds {
+        // bounded-variable loops (lpx_bounded.hip, lpx_bounded_dual.hip): upper bounds and flip states
+        double* ub = nullptr; uint8_t* flip = nullptr;          // [Ccap] each
+        bool bounds_set = false; int bounds_C = 0;              // live C the bounds were set for
+        double* snapUb = nullptr; uint8_t* snapFlip = nullptr; bool snap_bounds = false; int snap_bounds_C = 0;
+        int64_t bcounts[3] = {0, 0, 0};                         // events of the last bounded run: kind 0, kind 1, flips
+        // lower shift of every column (lpx_tableau_change_bounds): internal column j stands for x_j - lo[j]; allocated with ub
+        double* lo = nullptr; double* snapLo = nullptr;         // [Ccap] each
+        bool lo_used = false, snap_lo_used = false;             // some change has stored a non-zero lo
+        char* chg = nullptr; size_t chg_bytes = 0;              // staging of one bound edit: lower, upper, shift, saved (ub, lo), cols
+        // branch and bound by bound changes (lpx_bnb_bounded.hip): the column list of lpx_tableau_dualize with its two counts
+        // behind it, the device record of lpx_tableau_branch_pick, the integer mask, and the pinned slab the records come back through
+        int32_t* dzl = nullptr; lpx_branch_pick* pickrec = nullptr; uint8_t* pickmask = nullptr; char* nodeslab = nullptr;
+
+        void free()
+        {
+            hipFree(ub); hipFree(flip); hipFree(snapUb); hipFree(snapFlip);
+            hipFree(lo); hipFree(snapLo); hipFree(chg);
+            hipFree(dzl); hipFree(pickrec); hipFree(pickmask); if (nodeslab) hipHostFree(nodeslab);
+        }
+    } bnd;
+};
+
+#pragma GCC visibility push(hidden)       // private to liblpx.so
+namespace lpx {
+
+// The bounds and the flip states belong to the tableau they describe: lpx_tableau_snapshot / _restore take them along
+// (enqueued on the handle's stream; the caller waits).
+int bounds_snapshot(lpx_tableau* t);
+int bounds_restore(lpx_tableau* t);
+
+static constexpr int LPX_RESIDENT_RETRY = -1000;     // internal: first resident launch timed out, state untouched
+
+void drop_graph(lpx_tableau* t);
+// Fused pivot: buffers on first use.  Returns false (and remembers it) when the second tableau does not fit the device.
+bool fused_buffers(lpx_tableau* t);
+SelParams base_params(lpx_tableau* t, const lpx_run_opts* o, int mode);
+
+// The loop context every tableau loop shares: the handle's stream, records and graph cache, two launches per iteration, a
+// fresh state record.  What differs comes in: the bytes that key the captured graph (the loop's parameter record) and the
+// per-iteration enqueue; prologue and profile mapping follow p.mode.
+template <typename Params, typename Enqueue>
+void make_ctx(lpx_tableau* t, const SelParams& p, const Params& key, Enqueue enqueue, LoopCtx& c, DevState& init)
+{
+    const bool lookahead = p.mode != MODE_DUAL && p.mode != MODE_BOUNDED;
+    c.stream = t->stream; c.st = t->st; c.hst = t->hst; c.trace = t->trace; c.trace_cap = t->trace_cap;
+    c.events = &t->events; c.gexec = &t->gexec; c.g_batch = &t->g_batch; c.g_key = &t->g_key;
+    c.key.assign(reinterpret_cast<const char*>(&key), sizeof(key));
+    c.enqueue_iter = enqueue;
+    if (lookahead)                                       // lookahead path: first entering column + its gather, once
+        c.prologue = [p](hipStream_t s) -> int { LPX_HIP_TRY(launch_la_init(p, s)); return 0; };
+    else                                                 // dual and bounded paths: contiguous copy of the RHS column, once
+        c.prologue = [p](hipStream_t s) -> int { LPX_HIP_TRY(launch_rhs_init(p, s)); return 0; };
+    c.launches_per_iter = 2;
+    // one profiled update launch = one pivot: not in dual mode (phase hops make the mapping ambiguous) nor in the bounded loop
+    // (a launch may hold several events, or none that updates)
+    c.profile_maps = lookahead;
+    std::memset(&init, 0, sizeof(init));
+    init.status = LPX_RUNNING; init.r = -1; init.q = -1; init.qn = -1;
+    init.phase = (p.mode == MODE_DUAL) ? 0 : 2;
+}
+void make_ctx(lpx_tableau* t, const SelParams& p, LoopCtx& c, DevState& init);      // the (select, update) pair of p.mode
+int run_loop(lpx_tableau* t, SelParams p, const lpx_run_opts* o, long long budget,
+             lpx_pivot_cb cb, void* user, lpx_stats* stats, int start_iter = 0);
+
+}  // namespace lpx
+#pragma GCC visibility pop

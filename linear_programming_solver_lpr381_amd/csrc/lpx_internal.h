@@ -1,4 +1,4 @@
-// lpx_internal.h -- shared between the HIP kernels and the host-side C ABI of liblpx.so.
+// lpx_internal.h -- shared between the HIP kernels and the host-side C ABI of liblpx.so (the handle itself: lpx_handle.h, host only).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -63,9 +63,6 @@ struct BndParams {
 hipError_t launch_bounded_select(const BndParams& b, hipStream_t s);
 // bounded dual simplex and the bound change on a solved tableau (lpx_bounded_dual.hip)
 hipError_t launch_bounded_dual_select(const BndParams& b, hipStream_t s);
-// shift[k] from the old lo / ub / flip of cols[k], new ub / lo stored; then T[:,Cm] and rhsbuf shifted, k in order (R rows)
-hipError_t launch_change_bounds(double* T, int ld, int R, int Cm, int K, const int32_t* cols, const double* lower, const double* upper,
-                                double* ub, double* lo, const uint8_t* flip, double* shift, double* rhsbuf, hipStream_t s);
 
 // branch and bound by bound changes (lpx_bnb_bounded.hip)
 // list[0..count) = ascending columns j < Cm with T[m,j] < -eps and 0 < ub[j] < +inf; cnt = {count, unrepairable}
@@ -76,7 +73,8 @@ hipError_t launch_dualize_apply(double* T, int ld, int R, int Cm, const double* 
                                 const int32_t* cnt, double* rhsbuf, hipStream_t s);
 // ub / lo of cols[0..K) into save[2K] (restore = 0) or back from it (restore = 1)
 hipError_t launch_bounds_save(int K, const int32_t* cols, double* ub, double* lo, double* save, int restore, hipStream_t s);
-// lpx_bounds_shift alone / lpx_bounds_apply alone (launch_change_bounds is the two in a row)
+// the two launches of a bound change: shift[k] from the old lo / ub / flip of cols[k], new ub / lo stored; then T[:,Cm] and rhsbuf
+// shifted, k in order (R rows)
 hipError_t launch_bounds_shift(int K, const int32_t* cols, const double* lower, const double* upper, double* ub, double* lo,
                                const uint8_t* flip, double* shift, hipStream_t s);
 hipError_t launch_bounds_apply(double* T, int ld, int R, int Cm, int K, const int32_t* cols, const double* shift, double* rhsbuf,
@@ -238,7 +236,7 @@ void tableau_cut_view(lpx_tableau* t, CutView* v, bool need_second);
 int check_cut_opts(const lpx_cut_opts* o, const char* what);   // LPX_EINVAL (message set) when o is outside its ranges
 
 void set_error(const std::string& msg);
-// Device memory the library keeps for reuse after its owner is gone (the chunk cache of destroyed parent stores, lpx_tableau.cpp):
+// Device memory the library keeps for reuse after its owner is gone (the chunk cache of destroyed parent stores, lpx_tableau_nodes.cpp):
 // trim_device_caches() gives all of it back; malloc_retry() is hipMalloc that does so and tries once more before it reports
 // hipErrorOutOfMemory -- every large allocation of the library goes through it.
 void trim_device_caches();

@@ -1,79 +1,16 @@
-// lpx_tableau.cpp -- device-resident tableau handle and the host side of the simplex loops
-// (C ABI of include/lpx.h).  Host code only: kernels live in lpx_kernels.hip.
-#include "lpx_internal.h"
+// lpx_tableau.cpp -- device-resident tableau handle (lifecycle, transfers, snapshot) and the host side of the simplex loops:
+// single-LP loops, resident and group runs (C ABI of include/lpx.h).  The bounded-variable family is in lpx_tableau_bounded.cpp,
+// node assembly and the parent store in lpx_tableau_nodes.cpp.  Host code only: kernels live in lpx_kernels.hip.
+#include "lpx_handle.h"
 
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <memory>
-#include <mutex>
 #include <vector>
 
 namespace lpx { const std::string& get_error(); extern int g_device; }
 
 using namespace lpx;
-
-struct lpx_tableau {
-    int R = 0, C = 0, ld = 0;   // live shape (<= capacity) and leading dimension (from the capacity)
-    int Rcap = 0, Ccap = 0;
-    char* slab = nullptr;       // device slab holding every small buffer below (all but T)
-    char* hslab = nullptr;      // pinned slab holding hst and shape_h
-    int32_t* shape = nullptr;   // device record {R, C} read by the kernels
-    int32_t* shape_h = nullptr; // pinned staging
-    double* T = nullptr;        // [R*ld]
-    double* snapT = nullptr;    // snapshot
-    double* prow = nullptr;     // [ld]
-    double* pcol = nullptr;     // [R]
-    double* col0 = nullptr;     // [R] lookahead column buffers (ping-pong)
-    double* col1 = nullptr;
-    double* rhsbuf = nullptr;   // [R]
-    double* ws = nullptr;       // [MB_MAXB * max(R,C)]
-    double* part_v = nullptr; int32_t* part_i = nullptr;   // [64] partial argmins of the multi-workgroup select
-    DevState* us = nullptr;     // state record written by the update kernel (multi-workgroup protocol)
-    int use_mb = 1;
-    int32_t* basis = nullptr;   // [R-1]
-    int32_t* snapBasis = nullptr;
-    int32_t* trace = nullptr;   // [2*trace_cap]
-    int trace_cap = 0;
-    DevState* st = nullptr;     // device
-    DevState* hst = nullptr;    // pinned host mirror
-    bool suspended = false;     // lpx_multi_run_some left this run unfinished: *hst is where it continues
-    int32_t* frows = nullptr; int32_t* fcols = nullptr; int32_t* fchosen = nullptr; int fcap = 0;
-    char* cutbuf = nullptr; char* cutbuf_h = nullptr; int cutcap = 0;   // staging of branching-row descriptors
-    hipStream_t stream = nullptr;
-    // cached graph of `g_batch` (select, update) pairs
-    hipGraphExec_t gexec = nullptr;
-    int g_batch = 0;
-    std::string g_key;
-    std::vector<hipEvent_t> events;
-    // resident primal loop: exchange buffers (tagged granules) and the generation counter
-    unsigned long long* xr = nullptr; unsigned long long* xp = nullptr; unsigned* xgen = nullptr;
-    int32_t* xbasis = nullptr;      // basis as it was when the current resident launch started
-    double* xT = nullptr;           // tableau as it was when the current resident launch started (put back if the launch aborts)
-    unsigned long long* xc = nullptr; unsigned long long* xq = nullptr;   // column-owning resident kernel: candidates / candidate columns
-    size_t xc_bytes = 0, xq_bytes = 0;
-    bool resident_off = false;      // a resident launch could not get its workgroups co-resident: stay on the streaming path
-    // fused pivot (lpx_pivot_fused): second tableau buffer and the index-1 copies of the small per-pivot vectors, on first use
-    double* fT = nullptr; char* fslab = nullptr;
-    double* fprow = nullptr; double* frhs = nullptr; DevState* frec = nullptr;
-    char* dring = nullptr; int dring_slots = 0;   // deferred pivots of run_fused: ring of pivot rows, factor columns, row indices
-    bool fused_off = false;         // the second buffer did not fit: stay on the two-launch path
-    bool suspended2 = false;        // ... by the two-launch group kernels (it must continue there: no pending pivot, state in *hst)
-    bool fsuspended = false; int frec_cur = 0;   // fused group run left unfinished: its records (latest: index frec_cur) are in place
-    char* rgws = nullptr; size_t rgws_bytes = 0;  // lpx_tableau_ranging's partial slabs and outputs / the cut round's plan, on first use
-    // bounded-variable primal loop (lpx_bounded.hip): upper bounds and flip states beside the tableau, on first use
-    double* ub = nullptr; uint8_t* flip = nullptr;          // [Ccap] each
-    bool bounds_set = false; int bounds_C = 0;              // live C the bounds were set for
-    double* snapUb = nullptr; uint8_t* snapFlip = nullptr; bool snap_bounds = false; int snap_bounds_C = 0;
-    int64_t bcounts[3] = {0, 0, 0};                         // events of the last lpx_bounded_run: kind 0, kind 1, flips
-    // lower shift of every column (lpx_tableau_change_bounds): internal column j stands for x_j - lo[j]; allocated with ub
-    double* lo = nullptr; double* snapLo = nullptr;         // [Ccap] each
-    bool lo_used = false, snap_lo_used = false;             // some change has stored a non-zero lo
-    char* chg = nullptr; size_t chg_bytes = 0;              // staging of one lpx_tableau_change_bounds: lower, upper, shift, cols
-    // branch and bound by bound changes (lpx_bnb_bounded.hip), on first use: the column list of lpx_tableau_dualize with its two
-    // counts behind it, the device record of lpx_tableau_branch_pick, the integer mask, and the pinned slab the records come back through
-    int32_t* dzl = nullptr; lpx_branch_pick* pickrec = nullptr; uint8_t* pickmask = nullptr; char* nodeslab = nullptr;
-};
 
 void lpx::tableau_view(lpx_tableau* t, TableauView* v)
 {
@@ -82,7 +19,6 @@ void lpx::tableau_view(lpx_tableau* t, TableauView* v)
     v->ws = &t->rgws; v->ws_bytes = &t->rgws_bytes;
 }
 
-namespace { static bool fused_buffers(lpx_tableau* t); }   // below
 void lpx::tableau_cut_view(lpx_tableau* t, CutView* v, bool need_second)
 {
     v->T = t->T; v->T2 = need_second && fused_buffers(t) ? t->fT : nullptr;
@@ -91,9 +27,7 @@ void lpx::tableau_cut_view(lpx_tableau* t, CutView* v, bool need_second)
     v->ws = &t->rgws; v->ws_bytes = &t->rgws_bytes;
 }
 
-static constexpr int LPX_RESIDENT_RETRY = -1000;     // internal: first resident launch timed out, state untouched
-
-static void drop_graph(lpx_tableau* t)
+void lpx::drop_graph(lpx_tableau* t)
 {
     if (t->gexec) { hipGraphExecDestroy(t->gexec); t->gexec = nullptr; t->g_batch = 0; }
     graph_cache_drop_owner(&t->gexec);          // the parked ones captured the same buffers
@@ -224,9 +158,7 @@ void lpx_tableau_destroy(lpx_tableau* t)
     hipFree(t->frows); hipFree(t->fcols); hipFree(t->fchosen); hipFree(t->cutbuf);
     hipFree(t->fT); hipFree(t->fslab); hipFree(t->dring);
     hipFree(t->rgws);
-    hipFree(t->ub); hipFree(t->flip); hipFree(t->snapUb); hipFree(t->snapFlip);
-    hipFree(t->lo); hipFree(t->snapLo); hipFree(t->chg);
-    hipFree(t->dzl); hipFree(t->pickrec); hipFree(t->pickmask); if (t->nodeslab) hipHostFree(t->nodeslab);
+    t->bnd.free();
     hipFree(t->xr); hipFree(t->xp); hipFree(t->xgen); hipFree(t->xbasis); hipFree(t->xT); hipFree(t->xc); hipFree(t->xq);
     if (t->hslab) hipHostFree(t->hslab);
     if (t->cutbuf_h) hipHostFree(t->cutbuf_h);
@@ -278,18 +210,7 @@ int lpx_tableau_snapshot(lpx_tableau* t)
     LPX_HIP_TRY(hipMemcpyAsync(t->snapT, t->T, tb, hipMemcpyDeviceToDevice, t->stream));
     LPX_HIP_TRY(hipMemcpyAsync(t->snapBasis, t->basis, sizeof(int32_t) * (t->R > 1 ? t->R - 1 : 1),
                                hipMemcpyDeviceToDevice, t->stream));
-    t->snap_bounds = t->bounds_set; t->snap_bounds_C = t->bounds_C;
-    if (t->bounds_set) {        // the bounds and the flip states belong to the tableau they describe
-        if (!t->snapUb) {
-            LPX_HIP_TRY(hipMalloc((void**)&t->snapUb, sizeof(double) * t->Ccap));
-            LPX_HIP_TRY(hipMalloc((void**)&t->snapFlip, t->Ccap));
-            LPX_HIP_TRY(hipMalloc((void**)&t->snapLo, sizeof(double) * t->Ccap));
-        }
-        LPX_HIP_TRY(hipMemcpyAsync(t->snapLo, t->lo, sizeof(double) * t->Ccap, hipMemcpyDeviceToDevice, t->stream));
-        t->snap_lo_used = t->lo_used;
-        LPX_HIP_TRY(hipMemcpyAsync(t->snapUb, t->ub, sizeof(double) * t->Ccap, hipMemcpyDeviceToDevice, t->stream));
-        LPX_HIP_TRY(hipMemcpyAsync(t->snapFlip, t->flip, t->Ccap, hipMemcpyDeviceToDevice, t->stream));
-    }
+    { int rc = bounds_snapshot(t); if (rc) return rc; }
     LPX_HIP_TRY(hipStreamSynchronize(t->stream));
     return 0;
 }
@@ -302,16 +223,7 @@ int lpx_tableau_restore(lpx_tableau* t)
     LPX_HIP_TRY(hipMemcpyAsync(t->T, t->snapT, tb, hipMemcpyDeviceToDevice, t->stream));
     LPX_HIP_TRY(hipMemcpyAsync(t->basis, t->snapBasis, sizeof(int32_t) * (t->R > 1 ? t->R - 1 : 1),
                                hipMemcpyDeviceToDevice, t->stream));
-    if (t->snap_bounds) {
-        LPX_HIP_TRY(hipMemcpyAsync(t->ub, t->snapUb, sizeof(double) * t->Ccap, hipMemcpyDeviceToDevice, t->stream));
-        LPX_HIP_TRY(hipMemcpyAsync(t->flip, t->snapFlip, t->Ccap, hipMemcpyDeviceToDevice, t->stream));
-        LPX_HIP_TRY(hipMemcpyAsync(t->lo, t->snapLo, sizeof(double) * t->Ccap, hipMemcpyDeviceToDevice, t->stream));
-        t->bounds_set = true; t->bounds_C = t->snap_bounds_C; t->lo_used = t->snap_lo_used;
-    } else if (t->bounds_set) {     // snapshotted before it had bounds: that tableau had no column flipped or shifted
-        LPX_HIP_TRY(hipMemsetAsync(t->flip, 0, t->Ccap, t->stream));
-        LPX_HIP_TRY(hipMemsetAsync(t->lo, 0, sizeof(double) * t->Ccap, t->stream));
-        t->lo_used = false;
-    }
+    { int rc = bounds_restore(t); if (rc) return rc; }
     LPX_HIP_TRY(hipMemsetAsync(t->st, 0, sizeof(DevState), t->stream));
     LPX_HIP_TRY(hipStreamSynchronize(t->stream));
     return 0;
@@ -326,38 +238,19 @@ int lpx_tableau_device_ptr(lpx_tableau* t, void** dptr, int* ld)
 }
 
 #ifdef LPX_STAMPS
-int lpx_debug_resident_col(lpx_tableau* t, unsigned long long* out, int n, int clear)
+static int debug_stamps(void* src, unsigned long long* out, int n, int clear)        // n stamps out, cleared behind the copy
 {
-    if (!t->xc) return LPX_EINVAL;
-    LPX_HIP_TRY(hipMemcpy(out, t->xc + 2 * 256 * 2 * 2, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
-    if (clear) LPX_HIP_TRY(hipMemset(t->xc + 2 * 256 * 2 * 2, 0, sizeof(unsigned long long) * n));
-    return 0;
-}
-int lpx_debug_resident_group(lpx_tableau* t, unsigned long long* out, int n, int clear)
-{
-    if (!t->xp) return LPX_EINVAL;
-    LPX_HIP_TRY(hipMemcpy(out, t->xp + 4 * ((size_t)t->ld + 8), sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
-    if (clear) LPX_HIP_TRY(hipMemset(t->xp + 4 * ((size_t)t->ld + 8), 0, sizeof(unsigned long long) * n));
-    return 0;
-}
-int lpx_debug_resident(lpx_tableau* t, unsigned long long* out, int n, int clear)
-{
-    if (!t->xp) return LPX_EINVAL;
-    LPX_HIP_TRY(hipMemcpy(out, t->xp + 4 * (size_t)t->ld, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
-    if (clear) LPX_HIP_TRY(hipMemset(t->xp + 4 * (size_t)t->ld, 0, sizeof(unsigned long long) * n));
-    return 0;
-}
-#endif
-#ifdef LPX_STAMPS
-extern "C++" { namespace lpx { hipError_t debug_copy_stamps(unsigned long long* out, int clear); } }
-int lpx_debug_hs(unsigned long long* out, int clear) { LPX_HIP_TRY(lpx::debug_copy_stamps(out, clear)); return 0; }
-int lpx_debug_ws(lpx_tableau* t, unsigned long long* out, int n, int clear)
-{
-    double* src = t->us ? t->part_v + 128 : t->ws;
+    if (!src) return LPX_EINVAL;
     LPX_HIP_TRY(hipMemcpy(out, src, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
     if (clear) LPX_HIP_TRY(hipMemset(src, 0, sizeof(unsigned long long) * n));
     return 0;
 }
+int lpx_debug_resident_col(lpx_tableau* t, unsigned long long* out, int n, int clear) { return debug_stamps(t->xc ? t->xc + 2 * 256 * 2 * 2 : nullptr, out, n, clear); }
+int lpx_debug_resident_group(lpx_tableau* t, unsigned long long* out, int n, int clear) { return debug_stamps(t->xp ? t->xp + 4 * ((size_t)t->ld + 8) : nullptr, out, n, clear); }
+int lpx_debug_resident(lpx_tableau* t, unsigned long long* out, int n, int clear) { return debug_stamps(t->xp ? t->xp + 4 * (size_t)t->ld : nullptr, out, n, clear); }
+extern "C++" { namespace lpx { hipError_t debug_copy_stamps(unsigned long long* out, int clear); } }
+int lpx_debug_hs(unsigned long long* out, int clear) { LPX_HIP_TRY(lpx::debug_copy_stamps(out, clear)); return 0; }
+int lpx_debug_ws(lpx_tableau* t, unsigned long long* out, int n, int clear) { return debug_stamps(t->us ? t->part_v + 128 : t->ws, out, n, clear); }
 #endif
 
 int lpx_tableau_trace(lpx_tableau* t, int32_t* trace, int cap, int* n)
@@ -397,36 +290,15 @@ int enqueue_pair(const SelParams& p, hipStream_t s, hipEvent_t e0 = nullptr, hip
     return 0;
 }
 
-// The loop context every tableau loop shares: the handle's stream, records and graph cache, two launches per iteration, a
-// fresh state record.  What differs comes in: the bytes that key the captured graph (the loop's parameter record) and the
-// per-iteration enqueue; prologue and profile mapping follow p.mode.
-template <typename Params, typename Enqueue>
-void make_ctx(lpx_tableau* t, const SelParams& p, const Params& key, Enqueue enqueue, LoopCtx& c, DevState& init)
-{
-    const bool lookahead = p.mode != MODE_DUAL && p.mode != MODE_BOUNDED;
-    c.stream = t->stream; c.st = t->st; c.hst = t->hst; c.trace = t->trace; c.trace_cap = t->trace_cap;
-    c.events = &t->events; c.gexec = &t->gexec; c.g_batch = &t->g_batch; c.g_key = &t->g_key;
-    c.key.assign(reinterpret_cast<const char*>(&key), sizeof(key));
-    c.enqueue_iter = enqueue;
-    if (lookahead)                                       // lookahead path: first entering column + its gather, once
-        c.prologue = [p](hipStream_t s) -> int { LPX_HIP_TRY(launch_la_init(p, s)); return 0; };
-    else                                                 // dual and bounded paths: contiguous copy of the RHS column, once
-        c.prologue = [p](hipStream_t s) -> int { LPX_HIP_TRY(launch_rhs_init(p, s)); return 0; };
-    c.launches_per_iter = 2;
-    // one profiled update launch = one pivot: not in dual mode (phase hops make the mapping ambiguous) nor in the bounded loop
-    // (a launch may hold several events, or none that updates)
-    c.profile_maps = lookahead;
-    std::memset(&init, 0, sizeof(init));
-    init.status = LPX_RUNNING; init.r = -1; init.q = -1; init.qn = -1;
-    init.phase = (p.mode == MODE_DUAL) ? 0 : 2;
-}
-void make_ctx(lpx_tableau* t, const SelParams& p, LoopCtx& c, DevState& init)
+}  // namespace
+
+void lpx::make_ctx(lpx_tableau* t, const SelParams& p, LoopCtx& c, DevState& init)
 {
     make_ctx(t, p, p, [p](hipStream_t s, hipEvent_t e0, hipEvent_t e1) -> int { return enqueue_pair(p, s, e0, e1); }, c, init);
 }
 
-int run_loop(lpx_tableau* t, SelParams p, const lpx_run_opts* o, long long budget,
-             lpx_pivot_cb cb, void* user, lpx_stats* stats, int start_iter = 0)
+int lpx::run_loop(lpx_tableau* t, SelParams p, const lpx_run_opts* o, long long budget,
+                  lpx_pivot_cb cb, void* user, lpx_stats* stats, int start_iter)
 {
     LoopCtx c; DevState init;
     make_ctx(t, p, c, init);
@@ -434,7 +306,7 @@ int run_loop(lpx_tableau* t, SelParams p, const lpx_run_opts* o, long long budge
     return run_device_loop(c, init, o, budget, cb, user, stats);
 }
 
-SelParams base_params(lpx_tableau* t, const lpx_run_opts* o, int mode)
+SelParams lpx::base_params(lpx_tableau* t, const lpx_run_opts* o, int mode)
 {
     SelParams p; std::memset(&p, 0, sizeof(p));
     p.T = t->T; p.ld = t->ld; p.R = t->Rcap; p.C = t->Ccap; p.shape = t->shape;
@@ -453,8 +325,7 @@ SelParams base_params(lpx_tableau* t, const lpx_run_opts* o, int mode)
     return p;
 }
 
-// Fused pivot: buffers on first use.  Returns false (and remembers it) when the second tableau does not fit the device.
-static bool fused_buffers(lpx_tableau* t)
+bool lpx::fused_buffers(lpx_tableau* t)
 {
     if (t->fT) return true;
     if (t->fused_off) return false;
@@ -474,6 +345,8 @@ static bool fused_buffers(lpx_tableau* t)
     hipMemsetAsync(t->fslab, 0, sz[0] + sz[1] + sz[2], t->stream);
     return true;
 }
+
+namespace {
 
 // measured on MI355X with the select-only launch at 24.3 us: 4097 x 12289 (403 MB) 118.9 us per pivot at d = 1,
 // 34.9 at 12, 35.2 at 16 (the sweep 150 against 164 us); 1025 x 3073 (25 MB) 66 k pivots/s at d = 1, 79 k at 2, 82 k at 4, 80 k
@@ -1284,9 +1157,6 @@ int lpx_multi_run_end(int slot, int* statuses, lpx_stats* stats)
 
 }  // extern "C"
 
-namespace {
-}  // namespace
-
 static int multi_run_batched(lpx_tableau** ts, const int* dual, int count, const lpx_run_opts* popts,
                              const lpx_run_opts* dopts, int* statuses, lpx_stats* stats, const DevState* inits = nullptr, int min_active = 0)
 {
@@ -1330,442 +1200,6 @@ static int multi_run_batched(lpx_tableau** ts, const int* dual, int count, const
     }
     return 0;
 }
-
-// ---------------------------------------------------------------------------------------------------
-// bounded-variable primal simplex (include/lpx.h; select kernel in lpx_bounded.hip, update = lpx_update)
-// ---------------------------------------------------------------------------------------------------
-namespace {
-
-int bound_buffers(lpx_tableau* t)
-{
-    if (t->ub) return 0;
-    LPX_HIP_TRY(hipMalloc((void**)&t->ub, sizeof(double) * t->Ccap));
-    LPX_HIP_TRY(hipMalloc((void**)&t->flip, t->Ccap));
-    LPX_HIP_TRY(hipMalloc((void**)&t->lo, sizeof(double) * t->Ccap));
-    return 0;
-}
-
-// the argument checks of lpx_tableau_change_bounds (lpx_bounded_node makes the same ones): LPX_EINVAL with `what` in front
-int check_change_args(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const char* what)
-{
-    const std::string w = what;
-    if (!t) { set_error(w + ": null handle"); return LPX_EINVAL; }
-    if (K < 0) { set_error(w + ": K is negative"); return LPX_EINVAL; }
-    if (K > 0 && (!cols || !lower || !upper)) { set_error(w + ": null array"); return LPX_EINVAL; }
-    const int Cm = t->C - 1;
-    {
-        std::vector<uint8_t> seen((size_t)(Cm > 0 ? Cm : 1), 0);
-        for (int k = 0; k < K; ++k) {
-            const std::string at = "[" + std::to_string(k) + "]";
-            if (cols[k] < 0 || cols[k] >= Cm) { set_error(w + ": cols" + at + " is outside [0, C-1)"); return LPX_EINVAL; }
-            if (seen[cols[k]]) { set_error(w + ": cols" + at + " repeats a column"); return LPX_EINVAL; }
-            seen[cols[k]] = 1;
-            if (lower[k] != lower[k] || upper[k] != upper[k]) { set_error(w + ": bound" + at + " is NaN"); return LPX_EINVAL; }
-            if (lower[k] == 1.0 / 0.0 || lower[k] == -1.0 / 0.0) { set_error(w + ": lower" + at + " is not finite"); return LPX_EINVAL; }
-            if (upper[k] < lower[k]) { set_error(w + ": upper" + at + " is below lower" + at); return LPX_EINVAL; }
-        }
-    }
-    if (!t->bounds_set) { set_error(w + ": the handle has no bounds (lpx_tableau_set_bounds first)"); return LPX_EINVAL; }
-    if (t->bounds_C != t->C) { set_error(w + ": the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
-    return 0;
-}
-
-// every live column unbounded, unflipped and unshifted (a handle without bounds)
-int bounds_fill_inf(lpx_tableau* t)
-{
-    std::vector<double> inf((size_t)t->Ccap, 1.0 / 0.0);
-    LPX_HIP_TRY(hipMemcpyAsync(t->ub, inf.data(), sizeof(double) * t->Ccap, hipMemcpyHostToDevice, t->stream));
-    LPX_HIP_TRY(hipMemsetAsync(t->flip, 0, t->Ccap, t->stream));
-    LPX_HIP_TRY(hipMemsetAsync(t->lo, 0, sizeof(double) * t->Ccap, t->stream));      // +0.0
-    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
-    t->lo_used = false;
-    return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int lpx_tableau_set_bounds(lpx_tableau* t, int ncols, const double* ub)
-{
-    if (!t) { set_error("lpx_tableau_set_bounds: null handle"); return LPX_EINVAL; }
-    if (!ub && ncols == 0) { t->bounds_set = false; t->bounds_C = 0; return 0; }
-    if (!ub || ncols != t->C - 1) { set_error("lpx_tableau_set_bounds: ncols must be the live C - 1 and ub non-null"); return LPX_EINVAL; }
-    for (int j = 0; j < ncols; ++j)
-        if (!(ub[j] >= 0.0)) { set_error("lpx_tableau_set_bounds: ub[" + std::to_string(j) + "] is negative or NaN"); return LPX_EINVAL; }
-    int rc = ensure_device(); if (rc) return rc;
-    rc = bound_buffers(t); if (rc) return rc;
-    rc = bounds_fill_inf(t); if (rc) return rc;            // columns beyond the live shape: unbounded; every flip cleared
-    LPX_HIP_TRY(hipMemcpy(t->ub, ub, sizeof(double) * ncols, hipMemcpyHostToDevice));
-    t->bounds_set = true; t->bounds_C = t->C;
-    return 0;
-}
-
-int lpx_tableau_bound_flags(lpx_tableau* t, uint8_t* flip)
-{
-    if (!t || !flip) { set_error("lpx_tableau_bound_flags: null argument"); return LPX_EINVAL; }
-    const int n = t->C - 1;
-    if (!t->bounds_set || !t->flip) { std::memset(flip, 0, n); return 0; }
-    if (t->bounds_C != t->C) { set_error("lpx_tableau_bound_flags: the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
-    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
-    LPX_HIP_TRY(hipMemcpy(flip, t->flip, n, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-int lpx_bounded_counts(lpx_tableau* t, int64_t counts[3])
-{
-    if (!t || !counts) { set_error("lpx_bounded_counts: null argument"); return LPX_EINVAL; }
-    for (int k = 0; k < 3; ++k) counts[k] = t->bcounts[k];
-    return 0;
-}
-
-int lpx_bounded_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, void* user, lpx_stats* st)
-{
-    if (!t) { set_error("lpx_bounded_run: null tableau"); return LPX_EINVAL; }
-    lpx_run_opts d; if (!o) { lpx_default_opts(&d, 0); o = &d; }
-    if (t->R < 2) { set_error("lpx_bounded_run: tableau needs at least one constraint row"); return LPX_EINVAL; }
-    if (o->resident > 0) { set_error("lpx_bounded_run: there is no resident form of the bounded loop"); return LPX_EINVAL; }
-    if (t->bounds_set && t->bounds_C != t->C) { set_error("lpx_bounded_run: the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
-    int rc = ensure_device(); if (rc) return rc;
-    rc = bound_buffers(t); if (rc) return rc;
-    if (!t->bounds_set) { rc = bounds_fill_inf(t); if (rc) return rc; }
-    BndParams b; std::memset(&b, 0, sizeof(b));
-    b.P = base_params(t, o, MODE_BOUNDED);
-    b.P.us = nullptr; b.P.part_v = nullptr; b.P.part_i = nullptr; b.P.nblk = 0; b.P.qsel = 0;   // single-workgroup select
-    b.ub = t->ub; b.flip = t->flip;
-    LoopCtx c; DevState init;
-    make_ctx(t, b.P, b, [b](hipStream_t s, hipEvent_t e0, hipEvent_t e1) -> int {
-        LPX_HIP_TRY(launch_bounded_select(b, s));
-        // a launch that ended on a flip or on a final status leaves nothing to update: lpx_update returns at once
-        LPX_HIP_TRY(launch_update(b.P, b.P.pcol, b.P.pcol, s, e0, e1));
-        return 0;
-    }, c, init);
-    lpx_stats local; std::memset(&local, 0, sizeof(local));
-    t->bcounts[0] = t->bcounts[1] = t->bcounts[2] = 0;
-    rc = run_device_loop(c, init, o, (long long)o->max_iter + 2, cb, user, &local);
-    if (rc < 0) return rc;
-    // the select kernel counts the pivots per kind in the two counters the dual path uses for its phases
-    t->bcounts[0] = t->hst->fdf_count; t->bcounts[1] = t->hst->dual_iter;
-    t->bcounts[2] = (int64_t)t->hst->iter - t->bcounts[0] - t->bcounts[1];
-    local.pivots = t->bcounts[0] + t->bcounts[1]; local.fdf_pivots = 0; local.cleanup_pivots = 0;
-    if (st) { const double h2d = st->h2d_ms, d2h = st->d2h_ms; *st = local; st->h2d_ms = h2d; st->d2h_ms = d2h; }
-    return rc;
-}
-
-int lpx_tableau_bounded_solution(lpx_tableau* t, int nvars, double* x, double* z, uint8_t* at_upper)
-{
-    if (!t || nvars < 0 || nvars > t->C - 1 || (nvars > 0 && !x)) { set_error("lpx_tableau_bounded_solution: bad argument"); return LPX_EINVAL; }
-    if (t->bounds_set && t->bounds_C != t->C) { set_error("lpx_tableau_bounded_solution: the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
-    const int m = t->R - 1, Cm = t->C - 1;
-    std::vector<double> rhs(t->R), ub(Cm, 1.0 / 0.0);
-    std::vector<int32_t> basis(m > 0 ? m : 1);
-    std::vector<uint8_t> flip(Cm, 0);
-    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
-    LPX_HIP_TRY(hipMemcpy2D(rhs.data(), sizeof(double), t->T + Cm, sizeof(double) * t->ld, sizeof(double), t->R, hipMemcpyDeviceToHost));
-    if (m > 0) LPX_HIP_TRY(hipMemcpy(basis.data(), t->basis, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
-    if (t->bounds_set && Cm > 0) {
-        LPX_HIP_TRY(hipMemcpy(ub.data(), t->ub, sizeof(double) * Cm, hipMemcpyDeviceToHost));
-        LPX_HIP_TRY(hipMemcpy(flip.data(), t->flip, Cm, hipMemcpyDeviceToHost));
-    }
-    std::vector<double> lo;                             // only where a bound change has stored a non-zero lower shift
-    if (t->bounds_set && t->lo_used && Cm > 0) {
-        lo.resize(Cm);
-        LPX_HIP_TRY(hipMemcpy(lo.data(), t->lo, sizeof(double) * Cm, hipMemcpyDeviceToHost));
-    }
-    std::vector<double> v(Cm, 0.0);
-    std::vector<uint8_t> basic(Cm, 0);
-    for (int i = 0; i < m; ++i) if (basis[i] >= 0 && basis[i] < Cm) { v[basis[i]] = rhs[i]; basic[basis[i]] = 1; }
-    for (int j = 0; j < nvars; ++j) {
-        x[j] = flip[j] ? ub[j] - v[j] : v[j];
-        if (!lo.empty()) x[j] = x[j] + lo[j];
-        if (at_upper) at_upper[j] = (flip[j] && !basic[j]) ? 1 : 0;
-    }
-    if (z) *z = rhs[m];
-    return 0;
-}
-
-int lpx_tableau_bound_state(lpx_tableau* t, double* lo, double* ub, uint8_t* flip)
-{
-    if (!t) { set_error("lpx_tableau_bound_state: null handle"); return LPX_EINVAL; }
-    const int n = t->C - 1;
-    if (!t->bounds_set || !t->ub) {
-        for (int j = 0; j < n; ++j) { if (lo) lo[j] = 0.0; if (ub) ub[j] = 1.0 / 0.0; if (flip) flip[j] = 0; }
-        return 0;
-    }
-    if (t->bounds_C != t->C) { set_error("lpx_tableau_bound_state: the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
-    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
-    if (lo && n > 0) LPX_HIP_TRY(hipMemcpy(lo, t->lo, sizeof(double) * n, hipMemcpyDeviceToHost));
-    if (ub && n > 0) LPX_HIP_TRY(hipMemcpy(ub, t->ub, sizeof(double) * n, hipMemcpyDeviceToHost));
-    if (flip && n > 0) LPX_HIP_TRY(hipMemcpy(flip, t->flip, n, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-int lpx_tableau_change_bounds(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper)
-{
-    int rc = check_change_args(t, K, cols, lower, upper, "lpx_tableau_change_bounds"); if (rc) return rc;
-    const int Cm = t->C - 1;
-    rc = ensure_device(); if (rc) return rc;
-    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
-    bool any_inf = false, any_lo = false;
-    for (int k = 0; k < K; ++k) { if (upper[k] == 1.0 / 0.0) any_inf = true; if (lower[k] != 0.0) any_lo = true; }
-    if (any_inf) {          // the flip lives on the device; unflipping is not part of this edit
-        std::vector<uint8_t> flip((size_t)Cm);
-        LPX_HIP_TRY(hipMemcpy(flip.data(), t->flip, Cm, hipMemcpyDeviceToHost));
-        for (int k = 0; k < K; ++k)
-            if (upper[k] == 1.0 / 0.0 && flip[cols[k]]) {
-                set_error("lpx_tableau_change_bounds: upper[" + std::to_string(k) + "] = +inf on a flipped column");
-                return LPX_EINVAL;
-            }
-    }
-    t->suspended = t->suspended2 = t->fsuspended = false;
-    if (K > 0) {
-        const size_t need = (size_t)K * (3 * sizeof(double) + sizeof(int32_t));
-        if (need > t->chg_bytes) {
-            hipFree(t->chg); t->chg = nullptr; t->chg_bytes = 0;
-            LPX_HIP_TRY(hipMalloc((void**)&t->chg, 2 * need));
-            t->chg_bytes = 2 * need;
-        }
-        double* d_lower = reinterpret_cast<double*>(t->chg);
-        double* d_upper = d_lower + K;
-        double* d_shift = d_upper + K;
-        int32_t* d_cols = reinterpret_cast<int32_t*>(d_shift + K);
-        LPX_HIP_TRY(hipMemcpyAsync(d_lower, lower, sizeof(double) * K, hipMemcpyHostToDevice, t->stream));
-        LPX_HIP_TRY(hipMemcpyAsync(d_upper, upper, sizeof(double) * K, hipMemcpyHostToDevice, t->stream));
-        LPX_HIP_TRY(hipMemcpyAsync(d_cols, cols, sizeof(int32_t) * K, hipMemcpyHostToDevice, t->stream));
-        LPX_HIP_TRY(launch_change_bounds(t->T, t->ld, t->R, Cm, K, d_cols, d_lower, d_upper, t->ub, t->lo, t->flip, d_shift, t->rhsbuf, t->stream));
-        if (any_lo) t->lo_used = true;
-    }
-    LPX_HIP_TRY(hipMemsetAsync(t->st, 0, sizeof(DevState), t->stream));      // the loop state, as lpx_tableau_build_child resets it
-    LPX_HIP_TRY(hipStreamSynchronize(t->stream));                            // the caller's arrays are free again
-    return 0;
-}
-
-}  // extern "C"
-
-// lpx_bounded_dual_run (skip_fixed = false) and its flagged form: one body, two parameter records (b.dual = 1 / 2), so that the
-// two forms select their own instantiation of the kernel and key their own cached graph
-static int bounded_dual_run_impl(lpx_tableau* t, const lpx_run_opts* o, bool skip_fixed, lpx_pivot_cb cb, void* user, lpx_stats* st)
-{
-    if (!t) { set_error("lpx_bounded_dual_run: null tableau"); return LPX_EINVAL; }
-    lpx_run_opts d; if (!o) { lpx_default_opts(&d, 1); o = &d; }
-    if (t->R < 2) { set_error("lpx_bounded_dual_run: tableau needs at least one constraint row"); return LPX_EINVAL; }
-    if (o->resident > 0) { set_error("lpx_bounded_dual_run: there is no resident form of the bounded dual loop"); return LPX_EINVAL; }
-    if (t->bounds_set && t->bounds_C != t->C) { set_error("lpx_bounded_dual_run: the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
-    int rc = ensure_device(); if (rc) return rc;
-    rc = bound_buffers(t); if (rc) return rc;
-    if (!t->bounds_set) { rc = bounds_fill_inf(t); if (rc) return rc; }
-    BndParams b; std::memset(&b, 0, sizeof(b));
-    b.P = base_params(t, o, MODE_BOUNDED);
-    b.P.us = nullptr; b.P.part_v = nullptr; b.P.part_i = nullptr; b.P.nblk = 0; b.P.qsel = 0;   // single-workgroup select
-    b.ub = t->ub; b.flip = t->flip; b.dual = skip_fixed ? 2 : 1;
-    LoopCtx c; DevState init;
-    make_ctx(t, b.P, b, [b](hipStream_t s, hipEvent_t e0, hipEvent_t e1) -> int {
-        LPX_HIP_TRY(launch_bounded_dual_select(b, s));
-        LPX_HIP_TRY(launch_update(b.P, b.P.pcol, b.P.pcol, s, e0, e1));       // a final status leaves nothing to update
-        return 0;
-    }, c, init);
-    lpx_stats local; std::memset(&local, 0, sizeof(local));
-    t->bcounts[0] = t->bcounts[1] = t->bcounts[2] = 0;
-    rc = run_device_loop(c, init, o, (long long)o->max_iter + 2, cb, user, &local);
-    if (rc < 0) return rc;
-    t->bcounts[0] = t->hst->fdf_count; t->bcounts[1] = t->hst->dual_iter;     // per-kind counts, as lpx_bounded_run keeps them
-    local.pivots = t->bcounts[0] + t->bcounts[1]; local.fdf_pivots = 0; local.cleanup_pivots = 0;
-    if (st) { const double h2d = st->h2d_ms, d2h = st->d2h_ms; *st = local; st->h2d_ms = h2d; st->d2h_ms = d2h; }
-    return rc;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// branch and bound by bound changes (include/lpx.h; kernels in lpx_bnb_bounded.hip)
-// ---------------------------------------------------------------------------------------------------
-namespace {
-
-// pinned slab: {int32 cnt[2], pad} at 0, lpx_branch_pick at 16
-struct NodeSlab { int32_t cnt[4]; lpx_branch_pick pick; };
-
-int node_buffers(lpx_tableau* t)
-{
-    if (t->dzl) return 0;
-    LPX_HIP_TRY(hipMalloc((void**)&t->dzl, sizeof(int32_t) * ((size_t)t->Ccap + 4)));
-    LPX_HIP_TRY(hipMalloc((void**)&t->pickrec, sizeof(lpx_branch_pick)));
-    LPX_HIP_TRY(hipMalloc((void**)&t->pickmask, (size_t)t->Ccap));
-    LPX_HIP_TRY(hipHostMalloc((void**)&t->nodeslab, sizeof(NodeSlab)));
-    return 0;
-}
-
-int bounded_ready(lpx_tableau* t)
-{
-    int rc = ensure_device(); if (rc) return rc;
-    rc = bound_buffers(t); if (rc) return rc;
-    if (!t->bounds_set) { rc = bounds_fill_inf(t); if (rc) return rc; }
-    return node_buffers(t);
-}
-
-int check_pick_args(lpx_tableau* t, int nint, double tol, const void* out, const char* what)
-{
-    const std::string w = what;
-    if (!t) { set_error(w + ": null handle"); return LPX_EINVAL; }
-    if (!out) { set_error(w + ": null out"); return LPX_EINVAL; }
-    if (nint < 0 || nint > t->C - 1) { set_error(w + ": nint is outside [0, C-1]"); return LPX_EINVAL; }
-    if (!(tol >= 0.0 && tol < 0.5)) { set_error(w + ": tol is not in [0, 0.5)"); return LPX_EINVAL; }
-    return 0;
-}
-
-// the two dualize launches; the counts stay on the device behind the list
-int enqueue_dualize_list(lpx_tableau* t, double eps)
-{
-    LPX_HIP_TRY(launch_dualize_list(t->T, t->ld, t->R, t->C - 1, t->ub, eps, t->dzl + 4, t->dzl, t->stream));
-    return 0;
-}
-int enqueue_dualize_apply(lpx_tableau* t)
-{
-    LPX_HIP_TRY(launch_dualize_apply(t->T, t->ld, t->R, t->C - 1, t->ub, t->flip, t->dzl + 4, t->dzl, t->rhsbuf, t->stream));
-    return 0;
-}
-
-// the pick launch and the copy of its record into the pinned slab (the caller waits)
-int enqueue_pick(lpx_tableau* t, int nint, const uint8_t* is_int, double tol)
-{
-    if (is_int && nint > 0) LPX_HIP_TRY(hipMemcpyAsync(t->pickmask, is_int, (size_t)nint, hipMemcpyHostToDevice, t->stream));
-    PickParams p; std::memset(&p, 0, sizeof(p));
-    p.T = t->T; p.ld = t->ld; p.R = t->R; p.Cm = t->C - 1;
-    p.basis = t->basis; p.ub = t->ub; p.flip = t->flip; p.lo = t->lo_used ? t->lo : nullptr;
-    p.nint = nint; p.is_int = (is_int && nint > 0) ? t->pickmask : nullptr; p.tol = tol;
-    p.ws = t->ws; p.out = t->pickrec;
-    LPX_HIP_TRY(launch_branch_pick(p, t->stream));
-    NodeSlab* slab = reinterpret_cast<NodeSlab*>(t->nodeslab);
-    LPX_HIP_TRY(hipMemcpyAsync(&slab->pick, t->pickrec, sizeof(lpx_branch_pick), hipMemcpyDeviceToHost, t->stream));
-    return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int lpx_bounded_dual_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, void* user, lpx_stats* st)
-{
-    return bounded_dual_run_impl(t, o, false, cb, user, st);
-}
-
-int lpx_bounded_dual_run2(lpx_tableau* t, const lpx_run_opts* o, int flags, lpx_pivot_cb cb, void* user, lpx_stats* st)
-{
-    if (flags & ~LPX_BDUAL_SKIP_FIXED) { set_error("lpx_bounded_dual_run2: unknown flag"); return LPX_EINVAL; }
-    return bounded_dual_run_impl(t, o, (flags & LPX_BDUAL_SKIP_FIXED) != 0, cb, user, st);
-}
-
-int lpx_tableau_dualize(lpx_tableau* t, double eps, int64_t counts[2])
-{
-    if (!t) { set_error("lpx_tableau_dualize: null handle"); return LPX_EINVAL; }
-    if (!counts) { set_error("lpx_tableau_dualize: null counts"); return LPX_EINVAL; }
-    if (!(eps >= 0.0)) { set_error("lpx_tableau_dualize: eps is negative or NaN"); return LPX_EINVAL; }
-    if (!t->bounds_set) { set_error("lpx_tableau_dualize: the handle has no bounds (lpx_tableau_set_bounds first)"); return LPX_EINVAL; }
-    if (t->bounds_C != t->C) { set_error("lpx_tableau_dualize: the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
-    if (t->R < 1 || t->C < 1) { set_error("lpx_tableau_dualize: empty tableau"); return LPX_EINVAL; }
-    int rc = bounded_ready(t); if (rc) return rc;
-    t->suspended = t->suspended2 = t->fsuspended = false;
-    rc = enqueue_dualize_list(t, eps); if (rc) return rc;
-    rc = enqueue_dualize_apply(t); if (rc) return rc;
-    NodeSlab* slab = reinterpret_cast<NodeSlab*>(t->nodeslab);
-    LPX_HIP_TRY(hipMemcpyAsync(slab->cnt, t->dzl, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
-    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
-    counts[0] = slab->cnt[0]; counts[1] = slab->cnt[1];
-    return 0;
-}
-
-int lpx_tableau_branch_pick(lpx_tableau* t, int nint, const uint8_t* is_int, double tol, lpx_branch_pick* out)
-{
-    int rc = check_pick_args(t, nint, tol, out, "lpx_tableau_branch_pick"); if (rc) return rc;
-    if (t->bounds_set && t->bounds_C != t->C) { set_error("lpx_tableau_branch_pick: the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
-    if (t->R < 1 || t->C < 1) { set_error("lpx_tableau_branch_pick: empty tableau"); return LPX_EINVAL; }
-    rc = bounded_ready(t); if (rc) return rc;
-    rc = enqueue_pick(t, nint, is_int, tol); if (rc) return rc;
-    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
-    *out = reinterpret_cast<NodeSlab*>(t->nodeslab)->pick;
-    return 0;
-}
-
-int lpx_bounded_node(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const lpx_run_opts* o,
-                     int nint, const uint8_t* is_int, double tol, lpx_node_record* out)
-{
-    int rc = check_change_args(t, K, cols, lower, upper, "lpx_bounded_node"); if (rc) return rc;
-    rc = check_pick_args(t, nint, tol, out, "lpx_bounded_node"); if (rc) return rc;
-    lpx_run_opts d; if (!o) { lpx_default_opts(&d, 1); o = &d; }
-    if (t->R < 2) { set_error("lpx_bounded_node: tableau needs at least one constraint row"); return LPX_EINVAL; }
-    if (o->resident > 0) { set_error("lpx_bounded_node: there is no resident form of the bounded dual loop"); return LPX_EINVAL; }
-    if (!(o->eps >= 0.0)) { set_error("lpx_bounded_node: eps is negative or NaN"); return LPX_EINVAL; }
-    const int Cm = t->C - 1;
-    rc = bounded_ready(t); if (rc) return rc;
-    std::memset(out, 0, sizeof(*out));
-    out->pick.var = -1;
-    bool any_inf = false, any_lo = false;
-    for (int k = 0; k < K; ++k) { if (upper[k] == 1.0 / 0.0) any_inf = true; if (lower[k] != 0.0) any_lo = true; }
-    if (any_inf) {          // as lpx_tableau_change_bounds: unflipping is not part of the edit
-        std::vector<uint8_t> flip((size_t)Cm);
-        LPX_HIP_TRY(hipStreamSynchronize(t->stream));
-        LPX_HIP_TRY(hipMemcpy(flip.data(), t->flip, Cm, hipMemcpyDeviceToHost));
-        for (int k = 0; k < K; ++k)
-            if (upper[k] == 1.0 / 0.0 && flip[cols[k]]) {
-                set_error("lpx_bounded_node: upper[" + std::to_string(k) + "] = +inf on a flipped column");
-                return LPX_EINVAL;
-            }
-    }
-    // staging of the edit: lower, upper, shift, the saved (ub, lo) pairs, cols
-    double *d_lower = nullptr, *d_upper = nullptr, *d_shift = nullptr, *d_save = nullptr; int32_t* d_cols = nullptr;
-    if (K > 0) {
-        const size_t need = (size_t)K * (5 * sizeof(double) + sizeof(int32_t));
-        if (need > t->chg_bytes) {
-            LPX_HIP_TRY(hipStreamSynchronize(t->stream));
-            hipFree(t->chg); t->chg = nullptr; t->chg_bytes = 0;
-            LPX_HIP_TRY(hipMalloc((void**)&t->chg, 2 * need));
-            t->chg_bytes = 2 * need;
-        }
-        d_lower = reinterpret_cast<double*>(t->chg);
-        d_upper = d_lower + K; d_shift = d_upper + K; d_save = d_shift + K;
-        d_cols = reinterpret_cast<int32_t*>(d_save + 2 * (size_t)K);
-        LPX_HIP_TRY(hipMemcpyAsync(d_lower, lower, sizeof(double) * K, hipMemcpyHostToDevice, t->stream));
-        LPX_HIP_TRY(hipMemcpyAsync(d_upper, upper, sizeof(double) * K, hipMemcpyHostToDevice, t->stream));
-        LPX_HIP_TRY(hipMemcpyAsync(d_cols, cols, sizeof(int32_t) * K, hipMemcpyHostToDevice, t->stream));
-        // the new ub and lo first (small arrays only): the list of the flips needs them, and the tableau is still untouched
-        LPX_HIP_TRY(launch_bounds_save(K, d_cols, t->ub, t->lo, d_save, 0, t->stream));
-        LPX_HIP_TRY(launch_bounds_shift(K, d_cols, d_lower, d_upper, t->ub, t->lo, t->flip, d_shift, t->stream));
-    }
-    // the list reads the objective row left of the RHS, which the RHS shift of the edit does not write: listing before that
-    // shift gives the list of listing after it, and an unrepairable column is found with the tableau as it was
-    rc = enqueue_dualize_list(t, o->eps); if (rc) return rc;
-    NodeSlab* slab = reinterpret_cast<NodeSlab*>(t->nodeslab);
-    LPX_HIP_TRY(hipMemcpyAsync(slab->cnt, t->dzl, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
-    // wait 1: the counts (the caller's arrays are free again)
-    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
-    out->flips = slab->cnt[0]; out->unrepairable = slab->cnt[1];
-    if (out->unrepairable > 0) {
-        LPX_HIP_TRY(launch_bounds_save(K, d_cols, t->ub, t->lo, d_save, 1, t->stream));     // ub and lo as they were
-        LPX_HIP_TRY(hipStreamSynchronize(t->stream));
-        out->flips = 0;
-        set_error("lpx_bounded_node: " + std::to_string(out->unrepairable) + " column(s) with a negative reduced cost and no upper "
-                  "bound: a bound flip cannot restore dual feasibility");
-        return LPX_EINVAL;
-    }
-    t->suspended = t->suspended2 = t->fsuspended = false;
-    if (any_lo) t->lo_used = true;
-    if (K > 0) LPX_HIP_TRY(launch_bounds_apply(t->T, t->ld, t->R, Cm, K, d_cols, d_shift, t->rhsbuf, t->stream));
-    rc = enqueue_dualize_apply(t); if (rc) return rc;
-    // the loop (it resets the state record itself and waits once per batch)
-    const int status = bounded_dual_run_impl(t, o, true, nullptr, nullptr, nullptr);
-    if (status < 0) return status;
-    out->status = status; out->events = t->hst->iter; out->kind0 = t->bcounts[0]; out->kind1 = t->bcounts[1];
-    if (status == LPX_OPTIMAL) {
-        rc = enqueue_pick(t, nint, is_int, tol); if (rc) return rc;
-        LPX_HIP_TRY(hipStreamSynchronize(t->stream));                                    // last wait: the pick record
-        out->pick = slab->pick;
-    } else {
-        // no pick: z as the tableau stands, through the same slab
-        LPX_HIP_TRY(hipMemcpyAsync(&slab->pick.z, t->T + (size_t)(t->R - 1) * t->ld + Cm, sizeof(double), hipMemcpyDeviceToHost, t->stream));
-        LPX_HIP_TRY(hipStreamSynchronize(t->stream));
-        out->pick.var = -1; out->pick.candidates = 0; out->pick.x_var = 0.0; out->pick.z = slab->pick.z;
-    }
-    return status;
-}
-
-}  // extern "C"
 
 extern "C" {
 
@@ -1887,443 +1321,6 @@ static int one_shot(double* T, int R, int C, int32_t* basis, const lpx_run_opts*
     lpx_tableau_destroy(t);
     if (st) *st = local;
     return rc ? rc : status;
-}
-
-int lpx_tableau_set_shape(lpx_tableau* t, int R, int C)
-{
-    if (!t || R < 1 || C < 2 || R > t->Rcap || C > t->Ccap) { set_error("lpx_tableau_set_shape: shape outside the handle's capacity"); return LPX_EINVAL; }
-    LPX_HIP_TRY(hipStreamSynchronize(t->stream));          // the pinned staging word may still be in flight
-    t->R = R; t->C = C; t->suspended = t->suspended2 = t->fsuspended = false;               // a new tableau is coming: nothing to continue
-    t->shape_h[0] = R; t->shape_h[1] = C;
-    LPX_HIP_TRY(hipMemcpyAsync(t->shape, t->shape_h, sizeof(int32_t) * 2, hipMemcpyHostToDevice, t->stream));
-    return 0;
-}
-
-int lpx_tableau_build_node(lpx_tableau* node, const lpx_tableau* root, int ncuts, const int32_t* var,
-                           const double* coef, const double* zero, const double* rhs)
-{
-    if (!node || !root || ncuts < 0 || (ncuts > 0 && (!var || !coef || !zero || !rhs))) { set_error("lpx_tableau_build_node: bad argument"); return LPX_EINVAL; }
-    if (root->R + ncuts > node->Rcap || root->C + ncuts > node->Ccap) { set_error("lpx_tableau_build_node: root shape + ncuts exceeds the node handle's capacity"); return LPX_EINVAL; }
-    { int rc = lpx_tableau_set_shape(node, root->R + ncuts, root->C + ncuts); if (rc) return rc; }
-    const int n = root->C - root->R;
-    for (int k = 0; k < ncuts; ++k) if (var[k] < 0 || var[k] >= n) { set_error("lpx_tableau_build_node: branching variable out of range"); return LPX_EINVAL; }
-    const int need = ncuts > 0 ? ncuts : 1;
-    if (need > node->cutcap) {
-        hipFree(node->cutbuf); if (node->cutbuf_h) hipHostFree(node->cutbuf_h);
-        node->cutbuf = nullptr; node->cutbuf_h = nullptr; node->cutcap = 0;
-        const int c = need + 64;
-        LPX_HIP_TRY(hipMalloc((void**)&node->cutbuf, (size_t)c * 32));
-        LPX_HIP_TRY(hipHostMalloc((void**)&node->cutbuf_h, (size_t)c * 32));
-        node->cutcap = c;
-    }
-    const size_t cap = (size_t)node->cutcap;
-    double* hc = reinterpret_cast<double*>(node->cutbuf_h);          // [coef | zero | rhs | var(int32, padded)]
-    for (int k = 0; k < ncuts; ++k) { hc[k] = coef[k]; hc[cap + k] = zero[k]; hc[2 * cap + k] = rhs[k]; }
-    int32_t* hv = reinterpret_cast<int32_t*>(hc + 3 * cap);
-    for (int k = 0; k < ncuts; ++k) hv[k] = var[k];
-    LPX_HIP_TRY(hipMemcpyAsync(node->cutbuf, node->cutbuf_h, cap * 32, hipMemcpyHostToDevice, node->stream));
-    const double* dc = reinterpret_cast<const double*>(node->cutbuf);
-    const double* T0 = root->snapT ? root->snapT : root->T;          // the pristine root tableau
-    LPX_HIP_TRY(launch_build_node(T0, root->ld, root->R, root->C, node->T, node->ld, node->R, node->C,
-                                  reinterpret_cast<const int32_t*>(dc + 3 * cap), dc, dc + cap, dc + 2 * cap,
-                                  node->basis, node->stream));
-    LPX_HIP_TRY(hipMemsetAsync(node->st, 0, sizeof(DevState), node->stream));
-    return 0;   // stream-ordered: the run that follows on node->stream sees the finished tableau
-}
-
-// lpx_tableau_build_node for a group of nodes in one launch: node i gets the cuts [cut_off[i], cut_off[i + 1]) of the
-// flattened arrays.  One H2D copy of the packed descriptors and cuts, one kernel, one wait.
-int lpx_tableau_build_nodes(lpx_tableau** nodes, const lpx_tableau* root, int count, const int32_t* cut_off,
-                            const int32_t* var, const double* coef, const double* zero, const double* rhs)
-{
-    if (!nodes || !root || count < 0 || !cut_off) { set_error("lpx_tableau_build_nodes: bad argument"); return LPX_EINVAL; }
-    if (count == 0) return 0;
-    const int total = cut_off[count];
-    if (cut_off[0] != 0 || total < 0 || (total > 0 && (!var || !coef || !zero || !rhs))) { set_error("lpx_tableau_build_nodes: bad cut arrays"); return LPX_EINVAL; }
-    const int n = root->C - root->R;
-    int maxld = 16, maxR = 1;
-    for (int i = 0; i < count; ++i) {
-        lpx_tableau* t = nodes[i];
-        const int nc = cut_off[i + 1] - cut_off[i];
-        if (!t || nc < 0) { set_error("lpx_tableau_build_nodes: null node or negative cut count"); return LPX_EINVAL; }
-        if (root->R + nc > t->Rcap || root->C + nc > t->Ccap) { set_error("lpx_tableau_build_nodes: root shape + ncuts exceeds a node handle's capacity"); return LPX_EINVAL; }
-        maxld = std::max(maxld, t->ld); maxR = std::max(maxR, root->R + nc);
-    }
-    for (int k = 0; k < total; ++k) if (var[k] < 0 || var[k] >= n) { set_error("lpx_tableau_build_nodes: branching variable out of range"); return LPX_EINVAL; }
-    struct Scratch { char* h = nullptr; char* d = nullptr; size_t cap = 0; };
-    static thread_local Scratch sc;             // never freed: the HIP runtime may be gone when thread-locals are torn down
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t tn = (size_t)(total > 0 ? total : 1);
-    const size_t o_desc = 0, o_coef = up16(sizeof(BuildDesc) * (size_t)count), o_zero = o_coef + up16(8 * tn), o_rhs = o_zero + up16(8 * tn),
-                 o_var = o_rhs + up16(8 * tn), need = o_var + up16(4 * tn);
-    if (need > sc.cap) {
-        if (sc.h) hipHostFree(sc.h);
-        hipFree(sc.d);
-        sc.h = nullptr; sc.d = nullptr; sc.cap = 0;
-        LPX_HIP_TRY(hipHostMalloc((void**)&sc.h, 2 * need));
-        LPX_HIP_TRY(hipMalloc((void**)&sc.d, 2 * need));
-        sc.cap = 2 * need;
-    }
-    hipStream_t s = nodes[0]->stream;
-    // every node's own stream has to be idle before another stream writes its tableau (and before the scratch is reused)
-    for (int i = 0; i < count; ++i) {
-        bool seen = false; for (int j = 0; j < i; ++j) if (nodes[j]->stream == nodes[i]->stream) { seen = true; break; }
-        if (!seen) LPX_HIP_TRY(hipStreamSynchronize(nodes[i]->stream));
-    }
-    BuildDesc* d = reinterpret_cast<BuildDesc*>(sc.h + o_desc);
-    for (int i = 0; i < count; ++i) {
-        lpx_tableau* t = nodes[i];
-        const int nc = cut_off[i + 1] - cut_off[i];
-        t->R = root->R + nc; t->C = root->C + nc; t->suspended = t->suspended2 = t->fsuspended = false;
-        t->shape_h[0] = t->R; t->shape_h[1] = t->C;
-        d[i].T = t->T; d[i].basis = t->basis; d[i].shape = t->shape; d[i].st = t->st; d[i].ld = t->ld; d[i].R = t->R; d[i].C = t->C; d[i].cut0 = cut_off[i];
-    }
-    if (total > 0) {
-        std::memcpy(sc.h + o_coef, coef, 8 * (size_t)total); std::memcpy(sc.h + o_zero, zero, 8 * (size_t)total);
-        std::memcpy(sc.h + o_rhs, rhs, 8 * (size_t)total); std::memcpy(sc.h + o_var, var, 4 * (size_t)total);
-    }
-    LPX_HIP_TRY(hipMemcpyAsync(sc.d, sc.h, need, hipMemcpyHostToDevice, s));
-    const double* T0 = root->snapT ? root->snapT : root->T;          // the pristine root tableau
-    LPX_HIP_TRY(launch_build_nodes(T0, root->ld, root->R, root->C, reinterpret_cast<const BuildDesc*>(sc.d + o_desc), count, maxld, maxR,
-                                   reinterpret_cast<const int32_t*>(sc.d + o_var), reinterpret_cast<const double*>(sc.d + o_coef),
-                                   reinterpret_cast<const double*>(sc.d + o_zero), reinterpret_cast<const double*>(sc.d + o_rhs), s));
-    LPX_HIP_TRY(hipStreamSynchronize(s));       // the runs that follow use other streams
-    return 0;
-}
-
-// ---- parent store: final tableaux of solved nodes parked in slab slots (warm-started B&B children) ----------
-// Chunks of a destroyed store are kept for the next one (per process, up to LPX_STORE_CACHE_GB, default 64): a warm-started
-// search parks thousands of parent tableaux and grows its store by 1 GB allocations, which cost a search that follows other
-// GPU work on the same box up to half its time (bench.py's warm B&B leg right after the GPU test suite: 4.5-4.8 k nodes/s
-// against 6.8-7.2 k; hipMalloc of memory another process has just released).
-namespace {
-std::mutex g_chunk_mu;
-std::multimap<size_t, void*> g_chunk_cache;
-size_t g_chunk_cached = 0;
-size_t chunk_cache_max()
-{
-    // LPX_STORE_CACHE_GB (clamped to >= 0; default 64).  Whatever the cap, a chunk is only kept while a quarter of the device's memory
-    // stays free without it (chunk_release): several ranks sharing one GPU, or a big tableau allocated next, must not find the
-    // memory sitting idle in here -- and every large allocation of the library retries once after lpx::trim_device_caches().
-    static const size_t v = [] { const char* e = std::getenv("LPX_STORE_CACHE_GB"); long g = e ? std::atol(e) : 64; if (g < 0) g = 0; if (g > 4096) g = 4096; return (size_t)g << 30; }();
-    return v;
-}
-void chunk_cache_drop_all()
-{
-    std::lock_guard<std::mutex> lk(g_chunk_mu);
-    for (auto& kv : g_chunk_cache) hipFree(kv.second);
-    g_chunk_cache.clear(); g_chunk_cached = 0;
-}
-hipError_t chunk_alloc(void** p, size_t bytes)
-{
-    {
-        std::lock_guard<std::mutex> lk(g_chunk_mu);
-        auto it = g_chunk_cache.find(bytes);
-        if (it != g_chunk_cache.end()) { *p = it->second; g_chunk_cache.erase(it); g_chunk_cached -= bytes; return hipSuccess; }
-    }
-    hipError_t e = hipMalloc(p, bytes);
-    if (e == hipSuccess) return e;
-    // out of memory with chunks of other sizes in the cache: give them back and try once more
-    (void)hipGetLastError();
-    chunk_cache_drop_all();
-    return hipMalloc(p, bytes);
-}
-void chunk_release(void* p, size_t bytes)
-{
-    if (!p) return;
-    {
-        std::lock_guard<std::mutex> lk(g_chunk_mu);
-        size_t free_b = 0, total_b = 0;
-        const bool roomy = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= total_b / 4;
-        if (roomy && g_chunk_cached + bytes <= chunk_cache_max()) { g_chunk_cache.emplace(bytes, p); g_chunk_cached += bytes; return; }
-    }
-    hipFree(p);
-}
-}  // namespace
-
-extern "C++" {
-namespace lpx {
-void trim_device_caches() { chunk_cache_drop_all(); }
-hipError_t malloc_retry(void** p, size_t bytes)
-{
-    hipError_t e = hipMalloc(p, bytes);
-    if (e == hipSuccess) return e;
-    (void)hipGetLastError();
-    trim_device_caches();
-    return hipMalloc(p, bytes);
-}
-}  // namespace lpx
-}  // extern "C++"
-
-struct lpx_store {
-    int Rcap = 0, Ccap = 0, ld = 0, per_chunk = 128;
-    size_t slot_doubles = 0;                 // Rcap * ld
-    std::vector<double*> chunks_T; std::vector<int32_t*> chunks_b;
-    std::vector<int> R, C;                   // live shape per slot
-    std::vector<int> free_slots;
-};
-
-int lpx_store_create(int Rcap, int Ccap, lpx_store** out)
-{
-    if (!out || Rcap < 2 || Ccap < 2) { set_error("lpx_store_create: bad shape"); return LPX_EINVAL; }
-    int rc = ensure_device(); if (rc) return rc;
-    lpx_store* s = new lpx_store();
-    s->Rcap = Rcap; s->Ccap = Ccap; s->ld = (Ccap + 15) / 16 * 16;
-    s->slot_doubles = (size_t)Rcap * s->ld;
-    *out = s;
-    return 0;
-}
-
-void lpx_store_destroy(lpx_store* s)
-{
-    if (!s) return;
-    // a chunk that enters the cache may be handed to another store at once: nothing (a parking copy, a child assembly reading a
-    // parked parent -- they run on the handles' streams) may still be using it.  hipFree used to give this wait for free.
-    if (!s->chunks_T.empty()) (void)hipDeviceSynchronize();
-    for (double* p : s->chunks_T) chunk_release(p, sizeof(double) * s->slot_doubles * s->per_chunk);
-    for (int32_t* p : s->chunks_b) chunk_release(p, sizeof(int32_t) * (size_t)s->Rcap * s->per_chunk);
-    delete s;
-}
-
-static double* store_T(lpx_store* s, int slot) { return s->chunks_T[slot / s->per_chunk] + (size_t)(slot % s->per_chunk) * s->slot_doubles; }
-static int32_t* store_b(lpx_store* s, int slot) { return s->chunks_b[slot / s->per_chunk] + (size_t)(slot % s->per_chunk) * s->Rcap; }
-
-int lpx_store_save(lpx_store* s, lpx_tableau* t, int* slot_out)
-{
-    if (!s || !t || !slot_out) { set_error("lpx_store_save: null argument"); return LPX_EINVAL; }
-    if (t->ld != s->ld || t->R > s->Rcap) { set_error("lpx_store_save: tableau does not match the store's capacity class"); return LPX_EINVAL; }
-    if (s->free_slots.empty()) {
-        double* Tc = nullptr; int32_t* bc = nullptr;
-        LPX_HIP_TRY(chunk_alloc((void**)&Tc, sizeof(double) * s->slot_doubles * s->per_chunk));
-        hipError_t e = chunk_alloc((void**)&bc, sizeof(int32_t) * (size_t)s->Rcap * s->per_chunk);
-        if (e != hipSuccess) { hipFree(Tc); set_error("lpx_store_save: out of device memory"); return LPX_ENOMEM; }
-        const int base = (int)s->chunks_T.size() * s->per_chunk;
-        s->chunks_T.push_back(Tc); s->chunks_b.push_back(bc);
-        s->R.resize(base + s->per_chunk, 0); s->C.resize(base + s->per_chunk, 0);
-        for (int k = s->per_chunk - 1; k >= 0; --k) s->free_slots.push_back(base + k);
-    }
-    const int slot = s->free_slots.back(); s->free_slots.pop_back();
-    LPX_HIP_TRY(hipMemcpyAsync(store_T(s, slot), t->T, sizeof(double) * (size_t)t->R * t->ld, hipMemcpyDeviceToDevice, t->stream));
-    LPX_HIP_TRY(hipMemcpyAsync(store_b(s, slot), t->basis, sizeof(int32_t) * (t->R - 1), hipMemcpyDeviceToDevice, t->stream));
-    LPX_HIP_TRY(hipStreamSynchronize(t->stream));       // the handle may be reused by the caller right away
-    s->R[slot] = t->R; s->C[slot] = t->C;
-    *slot_out = slot;
-    return 0;
-}
-
-int lpx_store_release(lpx_store* s, int slot)
-{
-    if (!s || slot < 0 || slot >= (int)s->R.size()) return LPX_EINVAL;
-    s->free_slots.push_back(slot);
-    return 0;
-}
-
-int lpx_tableau_build_child_from_store(lpx_tableau* child, lpx_store* s, int slot, int var, int row_of_var, int is_ge, double bound)
-{
-    if (!child || !s || slot < 0 || slot >= (int)s->R.size()) { set_error("lpx_tableau_build_child_from_store: bad argument"); return LPX_EINVAL; }
-    const int Rp = s->R[slot], Cp = s->C[slot];
-    if (var < 0 || var >= Cp - 1 || row_of_var < 0 || row_of_var >= Rp - 1) { set_error("lpx_tableau_build_child_from_store: variable / row out of range"); return LPX_EINVAL; }
-    if (Rp + 1 > child->Rcap || Cp + 1 > child->Ccap) { set_error("lpx_tableau_build_child_from_store: child handle too small"); return LPX_EINVAL; }
-    { int rc = lpx_tableau_set_shape(child, Rp + 1, Cp + 1); if (rc) return rc; }
-    LPX_HIP_TRY(launch_build_child(store_T(s, slot), s->ld, Rp, Cp, store_b(s, slot), child->T, child->ld,
-                                   var, row_of_var, is_ge ? 1 : 0, bound, child->basis, child->stream));
-    LPX_HIP_TRY(hipMemsetAsync(child->st, 0, sizeof(DevState), child->stream));
-    return 0;
-}
-
-// lpx_tableau_build_child_from_store for a group of children in one launch (child i from stores[i] / slots[i]).
-int lpx_tableau_build_children_from_store(lpx_tableau** children, lpx_store** stores, const int* slots, int count,
-                                          const int32_t* var, const int32_t* row_of_var, const int32_t* is_ge, const double* bound)
-{
-    if (!children || !stores || !slots || count < 0 || (count > 0 && (!var || !row_of_var || !is_ge || !bound))) { set_error("lpx_tableau_build_children_from_store: bad argument"); return LPX_EINVAL; }
-    if (count == 0) return 0;
-    struct Scratch { char* h = nullptr; char* d = nullptr; size_t cap = 0; };
-    static thread_local Scratch sc;             // never freed (see lpx_tableau_build_nodes)
-    const size_t need = sizeof(ChildDesc) * (size_t)count;
-    if (need > sc.cap) {
-        if (sc.h) hipHostFree(sc.h);
-        hipFree(sc.d);
-        sc.h = nullptr; sc.d = nullptr; sc.cap = 0;
-        LPX_HIP_TRY(hipHostMalloc((void**)&sc.h, 2 * need));
-        LPX_HIP_TRY(hipMalloc((void**)&sc.d, 2 * need));
-        sc.cap = 2 * need;
-    }
-    int maxld = 16, maxR = 1;
-    for (int i = 0; i < count; ++i) {
-        lpx_tableau* ch = children[i]; lpx_store* s = stores[i]; const int slot = slots[i];
-        if (!ch || !s || slot < 0 || slot >= (int)s->R.size()) { set_error("lpx_tableau_build_children_from_store: bad child / store / slot"); return LPX_EINVAL; }
-        const int Rp = s->R[slot], Cp = s->C[slot];
-        if (var[i] < 0 || var[i] >= Cp - 1 || row_of_var[i] < 0 || row_of_var[i] >= Rp - 1) { set_error("lpx_tableau_build_children_from_store: variable / row out of range"); return LPX_EINVAL; }
-        if (Rp + 1 > ch->Rcap || Cp + 1 > ch->Ccap) { set_error("lpx_tableau_build_children_from_store: child handle too small"); return LPX_EINVAL; }
-        maxld = std::max(maxld, ch->ld); maxR = std::max(maxR, Rp + 1);
-    }
-    for (int i = 0; i < count; ++i) {           // every child's own stream has to be idle before another stream writes its tableau
-        bool seen = false; for (int j = 0; j < i; ++j) if (children[j]->stream == children[i]->stream) { seen = true; break; }
-        if (!seen) LPX_HIP_TRY(hipStreamSynchronize(children[i]->stream));
-    }
-    ChildDesc* d = reinterpret_cast<ChildDesc*>(sc.h);
-    for (int i = 0; i < count; ++i) {
-        lpx_tableau* ch = children[i]; lpx_store* s = stores[i]; const int slot = slots[i];
-        const int Rp = s->R[slot], Cp = s->C[slot];
-        ch->R = Rp + 1; ch->C = Cp + 1; ch->suspended = ch->suspended2 = ch->fsuspended = false; ch->shape_h[0] = ch->R; ch->shape_h[1] = ch->C;
-        d[i].Tp = store_T(s, slot); d[i].basis_p = store_b(s, slot); d[i].T = ch->T; d[i].basis = ch->basis; d[i].shape = ch->shape; d[i].st = ch->st;
-        d[i].ldp = s->ld; d[i].Rp = Rp; d[i].Cp = Cp; d[i].ld = ch->ld; d[i].var = var[i]; d[i].ik = row_of_var[i]; d[i].is_ge = is_ge[i] ? 1 : 0; d[i].pad = 0;
-        d[i].bound = bound[i];
-    }
-    hipStream_t st = children[0]->stream;
-    LPX_HIP_TRY(hipMemcpyAsync(sc.d, sc.h, need, hipMemcpyHostToDevice, st));
-    LPX_HIP_TRY(launch_build_children(reinterpret_cast<const ChildDesc*>(sc.d), count, maxld, maxR, st));
-    LPX_HIP_TRY(hipStreamSynchronize(st));      // the runs that follow use other streams
-    return 0;
-}
-
-int lpx_tableau_build_child(lpx_tableau* child, lpx_tableau* parent, int var, int row_of_var, int is_ge, double bound)
-{
-    if (!child || !parent || child == parent) { set_error("lpx_tableau_build_child: bad argument"); return LPX_EINVAL; }
-    if (var < 0 || var >= parent->C - 1 || row_of_var < 0 || row_of_var >= parent->R - 1) { set_error("lpx_tableau_build_child: variable / row out of range"); return LPX_EINVAL; }
-    if (parent->R + 1 > child->Rcap || parent->C + 1 > child->Ccap) { set_error("lpx_tableau_build_child: child handle too small"); return LPX_EINVAL; }
-    LPX_HIP_TRY(hipStreamSynchronize(parent->stream));              // the parent's final tableau must be complete
-    { int rc = lpx_tableau_set_shape(child, parent->R + 1, parent->C + 1); if (rc) return rc; }
-    LPX_HIP_TRY(launch_build_child(parent->T, parent->ld, parent->R, parent->C, parent->basis, child->T, child->ld,
-                                   var, row_of_var, is_ge ? 1 : 0, bound, child->basis, child->stream));
-    LPX_HIP_TRY(hipMemsetAsync(child->st, 0, sizeof(DevState), child->stream));
-    return 0;
-}
-
-int lpx_tableau_basis(lpx_tableau* t, int32_t* basis)
-{
-    if (!t || !basis) return LPX_EINVAL;
-    if (t->R > 1) LPX_HIP_TRY(hipMemcpyAsync(basis, t->basis, sizeof(int32_t) * (t->R - 1), hipMemcpyDeviceToHost, t->stream));
-    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
-    return 0;
-}
-
-int lpx_tableau_solution2(lpx_tableau* t, int nvars, double* x, double* z, int32_t* basis_out);
-int lpx_tableau_solution(lpx_tableau* t, int nvars, double* x, double* z) { return lpx_tableau_solution2(t, nvars, x, z, nullptr); }
-
-int lpx_tableau_solution2(lpx_tableau* t, int nvars, double* x, double* z, int32_t* basis_out)
-{
-    if (!t || nvars < 0) { set_error("lpx_tableau_solution: bad argument"); return LPX_EINVAL; }
-    const int m = t->R - 1;
-    std::vector<double> rhs(t->R);
-    std::vector<int32_t> basis(m > 0 ? m : 1);
-    LPX_HIP_TRY(hipMemcpy2DAsync(rhs.data(), sizeof(double), t->T + (t->C - 1), sizeof(double) * t->ld,
-                                 sizeof(double), t->R, hipMemcpyDeviceToHost, t->stream));
-    if (m > 0) LPX_HIP_TRY(hipMemcpyAsync(basis.data(), t->basis, sizeof(int32_t) * m, hipMemcpyDeviceToHost, t->stream));
-    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
-    if (x) {
-        for (int j = 0; j < nvars; ++j) x[j] = 0.0;
-        for (int i = 0; i < m; ++i) if (basis[i] >= 0 && basis[i] < nvars) x[basis[i]] = rhs[i];   // FinalizeReport :135-136
-    }
-    if (z) *z = rhs[m];                                                                           // :138
-    if (basis_out && m > 0) std::memcpy(basis_out, basis.data(), sizeof(int32_t) * m);
-    return 0;
-}
-
-// lpx_tableau_solution2 for a batch: x is count x nvars, z has count entries, basis_out (optional) count x basis_stride.
-int lpx_multi_solution(lpx_tableau** ts, int count, int nvars, double* x, double* z, int32_t* basis_out, int basis_stride)
-{
-    if (!ts || count < 0 || nvars < 0) { set_error("lpx_multi_solution: bad argument"); return LPX_EINVAL; }
-    if (count == 0) return 0;
-    struct Scratch { char* h = nullptr; size_t cap = 0; ~Scratch() { if (h) hipHostFree(h); } };
-    static thread_local Scratch sc;
-    size_t rows = 0;
-    for (int i = 0; i < count; ++i) {
-        if (!ts[i] || ts[i]->R < 1) { set_error("lpx_multi_solution: null or empty tableau"); return LPX_EINVAL; }
-        if (basis_out && basis_stride < ts[i]->R - 1) { set_error("lpx_multi_solution: basis_stride too small"); return LPX_EINVAL; }
-        rows += (size_t)ts[i]->R;
-    }
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_desc = 0, o_rhs = up16(sizeof(GatherDesc) * (size_t)count), o_bas = o_rhs + up16(sizeof(double) * rows);
-    const size_t need = o_bas + up16(sizeof(int32_t) * rows);
-    if (need > sc.cap) {
-        if (sc.h) hipHostFree(sc.h);
-        sc.h = nullptr; sc.cap = 0;
-        LPX_HIP_TRY(hipHostMalloc((void**)&sc.h, 2 * need));
-        sc.cap = 2 * need;
-    }
-    GatherDesc* d = reinterpret_cast<GatherDesc*>(sc.h + o_desc);
-    double* rhs = reinterpret_cast<double*>(sc.h + o_rhs);
-    int32_t* bas = reinterpret_cast<int32_t*>(sc.h + o_bas);
-    size_t off = 0;
-    for (int i = 0; i < count; ++i) {
-        d[i].T = ts[i]->T; d[i].basis = ts[i]->basis; d[i].ld = ts[i]->ld; d[i].R = ts[i]->R; d[i].C = ts[i]->C; d[i].off = (int)off;
-        off += (size_t)ts[i]->R;
-    }
-    // every handle's own stream has to be idle before another stream reads its tableau
-    for (int i = 0; i < count; ++i) {
-        bool seen = false; for (int j = 0; j < i; ++j) if (ts[j]->stream == ts[i]->stream) { seen = true; break; }
-        if (!seen) LPX_HIP_TRY(hipStreamSynchronize(ts[i]->stream));
-    }
-    hipStream_t s = ts[0]->stream;
-    LPX_HIP_TRY(launch_gather_solution(d, count, rhs, bas, s));
-    LPX_HIP_TRY(hipStreamSynchronize(s));
-    for (int i = 0; i < count; ++i) {
-        const int m = ts[i]->R - 1;
-        const double* r = rhs + d[i].off; const int32_t* b = bas + d[i].off;
-        if (x) {
-            double* xi = x + (size_t)i * nvars;
-            for (int j = 0; j < nvars; ++j) xi[j] = 0.0;
-            for (int k = 0; k < m; ++k) if (b[k] >= 0 && b[k] < nvars) xi[b[k]] = r[k];       // FinalizeReport :135-136
-        }
-        if (z) z[i] = r[m];                                                                 // :138
-        if (basis_out && m > 0) std::memcpy(basis_out + (size_t)i * basis_stride, b, sizeof(int32_t) * m);
-    }
-    return 0;
-}
-
-// lpx_store_save for a batch: all copies are enqueued first, each stream is waited for once.
-int lpx_store_save_multi(lpx_store** ss, lpx_tableau** ts, int count, int* slots)
-{
-    if (!ss || !ts || !slots || count < 0) { set_error("lpx_store_save_multi: bad argument"); return LPX_EINVAL; }
-    if (count == 0) return 0;
-    for (int i = 0; i < count; ++i) {
-        lpx_store* s = ss[i]; lpx_tableau* t = ts[i];
-        if (!s || !t) { set_error("lpx_store_save_multi: null argument"); return LPX_EINVAL; }
-        if (t->ld != s->ld || t->R > s->Rcap) { set_error("lpx_store_save_multi: tableau does not match the store's capacity class"); return LPX_EINVAL; }
-    }
-    struct Scratch { char* h = nullptr; char* d = nullptr; size_t cap = 0; };
-    static thread_local Scratch sc;             // never freed (see lpx_tableau_build_nodes)
-    const size_t need = sizeof(ParkDesc) * (size_t)count;
-    if (need > sc.cap) {
-        if (sc.h) hipHostFree(sc.h);
-        hipFree(sc.d);
-        sc.h = nullptr; sc.d = nullptr; sc.cap = 0;
-        LPX_HIP_TRY(hipHostMalloc((void**)&sc.h, 2 * need));
-        LPX_HIP_TRY(hipMalloc((void**)&sc.d, 2 * need));
-        sc.cap = 2 * need;
-    }
-    for (int i = 0; i < count; ++i) {           // the finished runs used the group's stream; the nodes' own streams are idle, make sure
-        bool seen = false; for (int j = 0; j < i; ++j) if (ts[j]->stream == ts[i]->stream) { seen = true; break; }
-        if (!seen) LPX_HIP_TRY(hipStreamSynchronize(ts[i]->stream));
-    }
-    ParkDesc* d = reinterpret_cast<ParkDesc*>(sc.h);
-    size_t maxd = 0;
-    for (int i = 0; i < count; ++i) {
-        lpx_store* s = ss[i]; lpx_tableau* t = ts[i];
-        if (s->free_slots.empty()) {
-            double* Tc = nullptr; int32_t* bc = nullptr;
-            LPX_HIP_TRY(chunk_alloc((void**)&Tc, sizeof(double) * s->slot_doubles * s->per_chunk));
-            hipError_t e = chunk_alloc((void**)&bc, sizeof(int32_t) * (size_t)s->Rcap * s->per_chunk);
-            if (e != hipSuccess) { hipFree(Tc); set_error("lpx_store_save_multi: out of device memory"); return LPX_ENOMEM; }
-            const int base = (int)s->chunks_T.size() * s->per_chunk;
-            s->chunks_T.push_back(Tc); s->chunks_b.push_back(bc);
-            s->R.resize(base + s->per_chunk, 0); s->C.resize(base + s->per_chunk, 0);
-            for (int k = s->per_chunk - 1; k >= 0; --k) s->free_slots.push_back(base + k);
-        }
-        const int slot = s->free_slots.back(); s->free_slots.pop_back();
-        s->R[slot] = t->R; s->C[slot] = t->C;
-        slots[i] = slot;
-        d[i].srcT = t->T; d[i].dstT = store_T(s, slot); d[i].srcB = t->basis; d[i].dstB = store_b(s, slot);
-        d[i].doubles = (size_t)t->R * t->ld; d[i].m = t->R - 1; d[i].pad = 0;
-        maxd = std::max(maxd, d[i].doubles);
-    }
-    hipStream_t st = ts[0]->stream;
-    LPX_HIP_TRY(hipMemcpyAsync(sc.d, sc.h, need, hipMemcpyHostToDevice, st));
-    const int bpn = (int)std::min<size_t>(256, std::max<size_t>(1, maxd / 2 / 256 / 4));        // ~4 double2 per lane at least
-    LPX_HIP_TRY(launch_park_many(reinterpret_cast<const ParkDesc*>(sc.d), count, bpn, st));
-    LPX_HIP_TRY(hipStreamSynchronize(st));      // the handles may be reused, the slots read, right away
-    return 0;
 }
 
 int lpx_multi_run(lpx_tableau** ts, const int* dual, int count, const lpx_run_opts* popts,

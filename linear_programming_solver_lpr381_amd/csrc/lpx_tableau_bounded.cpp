@@ -1,0 +1,435 @@
+// lpx_tableau_bounded.cpp -- host side of the bounded-variable family on a tableau handle (C ABI of include/lpx.h): bounds beside
+// the tableau, the bounded primal and dual loops, bound changes on a solved tableau, branch and bound by bound changes.
+// Kernels: lpx_bounded.hip, lpx_bounded_dual.hip, lpx_bnb_bounded.hip; the update is lpx_update.
+#include "lpx_handle.h"
+
+#include <cstring>
+#include <vector>
+
+using namespace lpx;
+
+int lpx::bounds_snapshot(lpx_tableau* t)
+{
+    lpx_tableau::Bounds& b = t->bnd;
+    b.snap_bounds = b.bounds_set; b.snap_bounds_C = b.bounds_C;
+    if (!b.bounds_set) return 0;
+    if (!b.snapUb) {
+        LPX_HIP_TRY(hipMalloc((void**)&b.snapUb, sizeof(double) * t->Ccap));
+        LPX_HIP_TRY(hipMalloc((void**)&b.snapFlip, t->Ccap));
+        LPX_HIP_TRY(hipMalloc((void**)&b.snapLo, sizeof(double) * t->Ccap));
+    }
+    LPX_HIP_TRY(hipMemcpyAsync(b.snapLo, b.lo, sizeof(double) * t->Ccap, hipMemcpyDeviceToDevice, t->stream));
+    b.snap_lo_used = b.lo_used;
+    LPX_HIP_TRY(hipMemcpyAsync(b.snapUb, b.ub, sizeof(double) * t->Ccap, hipMemcpyDeviceToDevice, t->stream));
+    LPX_HIP_TRY(hipMemcpyAsync(b.snapFlip, b.flip, t->Ccap, hipMemcpyDeviceToDevice, t->stream));
+    return 0;
+}
+
+int lpx::bounds_restore(lpx_tableau* t)
+{
+    lpx_tableau::Bounds& b = t->bnd;
+    if (b.snap_bounds) {
+        LPX_HIP_TRY(hipMemcpyAsync(b.ub, b.snapUb, sizeof(double) * t->Ccap, hipMemcpyDeviceToDevice, t->stream));
+        LPX_HIP_TRY(hipMemcpyAsync(b.flip, b.snapFlip, t->Ccap, hipMemcpyDeviceToDevice, t->stream));
+        LPX_HIP_TRY(hipMemcpyAsync(b.lo, b.snapLo, sizeof(double) * t->Ccap, hipMemcpyDeviceToDevice, t->stream));
+        b.bounds_set = true; b.bounds_C = b.snap_bounds_C; b.lo_used = b.snap_lo_used;
+    } else if (b.bounds_set) {      // snapshotted before it had bounds: that tableau had no column flipped or shifted
+        LPX_HIP_TRY(hipMemsetAsync(b.flip, 0, t->Ccap, t->stream));
+        LPX_HIP_TRY(hipMemsetAsync(b.lo, 0, sizeof(double) * t->Ccap, t->stream));
+        b.lo_used = false;
+    }
+    return 0;
+}
+
+namespace {
+
+// pinned slab: {int32 cnt[2], pad} at 0, lpx_branch_pick at 16
+struct NodeSlab { int32_t cnt[4]; lpx_branch_pick pick; };
+
+int bound_buffers(lpx_tableau* t)
+{
+    if (t->bnd.ub) return 0;
+    LPX_HIP_TRY(hipMalloc((void**)&t->bnd.ub, sizeof(double) * t->Ccap));
+    LPX_HIP_TRY(hipMalloc((void**)&t->bnd.flip, t->Ccap));
+    LPX_HIP_TRY(hipMalloc((void**)&t->bnd.lo, sizeof(double) * t->Ccap));
+    return 0;
+}
+
+int node_buffers(lpx_tableau* t)
+{
+    if (t->bnd.dzl) return 0;
+    LPX_HIP_TRY(hipMalloc((void**)&t->bnd.dzl, sizeof(int32_t) * ((size_t)t->Ccap + 4)));
+    LPX_HIP_TRY(hipMalloc((void**)&t->bnd.pickrec, sizeof(lpx_branch_pick)));
+    LPX_HIP_TRY(hipMalloc((void**)&t->bnd.pickmask, (size_t)t->Ccap));
+    LPX_HIP_TRY(hipHostMalloc((void**)&t->bnd.nodeslab, sizeof(NodeSlab)));
+    return 0;
+}
+
+// every live column unbounded, unflipped and unshifted (a handle without bounds)
+int bounds_fill_inf(lpx_tableau* t)
+{
+    std::vector<double> inf((size_t)t->Ccap, 1.0 / 0.0);
+    LPX_HIP_TRY(hipMemcpyAsync(t->bnd.ub, inf.data(), sizeof(double) * t->Ccap, hipMemcpyHostToDevice, t->stream));
+    LPX_HIP_TRY(hipMemsetAsync(t->bnd.flip, 0, t->Ccap, t->stream));
+    LPX_HIP_TRY(hipMemsetAsync(t->bnd.lo, 0, sizeof(double) * t->Ccap, t->stream));      // +0.0
+    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+    t->bnd.lo_used = false;
+    return 0;
+}
+
+// the device, the bound arrays the loops read (without bounds: every column unbounded) and, with node, the buffers of dualize / pick / node
+int bounded_ready(lpx_tableau* t, bool node)
+{
+    int rc = ensure_device(); if (rc) return rc;
+    rc = bound_buffers(t); if (rc) return rc;
+    if (!t->bnd.bounds_set) { rc = bounds_fill_inf(t); if (rc) return rc; }
+    return node ? node_buffers(t) : 0;
+}
+
+// bounds present (unless the entry point runs without them) and set for the live shape: LPX_EINVAL with `what` in front otherwise
+int check_bounds(const lpx_tableau* t, const char* what, bool required)
+{
+    const std::string w = what;
+    if (!t->bnd.bounds_set && !required) return 0;
+    if (!t->bnd.bounds_set) { set_error(w + ": the handle has no bounds (lpx_tableau_set_bounds first)"); return LPX_EINVAL; }
+    if (t->bnd.bounds_C != t->C) { set_error(w + ": the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
+    return 0;
+}
+
+// the argument checks of lpx_tableau_change_bounds (lpx_bounded_node makes the same ones): LPX_EINVAL with `what` in front
+int check_change_args(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const char* what)
+{
+    const std::string w = what;
+    if (!t) { set_error(w + ": null handle"); return LPX_EINVAL; }
+    if (K < 0) { set_error(w + ": K is negative"); return LPX_EINVAL; }
+    if (K > 0 && (!cols || !lower || !upper)) { set_error(w + ": null array"); return LPX_EINVAL; }
+    const int Cm = t->C - 1;
+    std::vector<uint8_t> seen((size_t)(Cm > 0 ? Cm : 1), 0);
+    for (int k = 0; k < K; ++k) {
+        const std::string at = "[" + std::to_string(k) + "]";
+        if (cols[k] < 0 || cols[k] >= Cm) { set_error(w + ": cols" + at + " is outside [0, C-1)"); return LPX_EINVAL; }
+        if (seen[cols[k]]) { set_error(w + ": cols" + at + " repeats a column"); return LPX_EINVAL; }
+        seen[cols[k]] = 1;
+        if (lower[k] != lower[k] || upper[k] != upper[k]) { set_error(w + ": bound" + at + " is NaN"); return LPX_EINVAL; }
+        if (lower[k] == 1.0 / 0.0 || lower[k] == -1.0 / 0.0) { set_error(w + ": lower" + at + " is not finite"); return LPX_EINVAL; }
+        if (upper[k] < lower[k]) { set_error(w + ": upper" + at + " is below lower" + at); return LPX_EINVAL; }
+    }
+    return check_bounds(t, what, true);
+}
+
+int check_pick_args(lpx_tableau* t, int nint, double tol, const void* out, const char* what)
+{
+    const std::string w = what;
+    if (!t) { set_error(w + ": null handle"); return LPX_EINVAL; }
+    if (!out) { set_error(w + ": null out"); return LPX_EINVAL; }
+    if (nint < 0 || nint > t->C - 1) { set_error(w + ": nint is outside [0, C-1]"); return LPX_EINVAL; }
+    if (!(tol >= 0.0 && tol < 0.5)) { set_error(w + ": tol is not in [0, 0.5)"); return LPX_EINVAL; }
+    return 0;
+}
+
+// One bound edit staged on the device: the caller's arrays in the handle's staging buffer, one layout for every entry point --
+// lower, upper, shift, the saved (ub, lo) pairs, cols ([K] each, save [2K]; lpx_tableau_change_bounds leaves the save area unused).
+struct BoundEdit { double *lower = nullptr, *upper = nullptr, *shift = nullptr, *save = nullptr; int32_t* cols = nullptr; bool any_lo = false; };
+
+// Refuses +inf on a flipped column (the flip lives on the device; unflipping is not part of an edit), grows the staging buffer
+// and enqueues the three copies.  It waits for the handle's stream only before it reads the flips or frees the old buffer.
+int stage_bound_edit(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const char* what, BoundEdit* e)
+{
+    const int Cm = t->C - 1;
+    bool any_inf = false;
+    for (int k = 0; k < K; ++k) { if (upper[k] == 1.0 / 0.0) any_inf = true; if (lower[k] != 0.0) e->any_lo = true; }
+    if (any_inf) {
+        std::vector<uint8_t> flip((size_t)Cm);
+        LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+        LPX_HIP_TRY(hipMemcpy(flip.data(), t->bnd.flip, Cm, hipMemcpyDeviceToHost));
+        for (int k = 0; k < K; ++k)
+            if (upper[k] == 1.0 / 0.0 && flip[cols[k]]) {
+                set_error(std::string(what) + ": upper[" + std::to_string(k) + "] = +inf on a flipped column");
+                return LPX_EINVAL;
+            }
+    }
+    if (K == 0) return 0;
+    const size_t need = (size_t)K * (5 * sizeof(double) + sizeof(int32_t));
+    if (need > t->bnd.chg_bytes) {
+        LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+        hipFree(t->bnd.chg); t->bnd.chg = nullptr; t->bnd.chg_bytes = 0;
+        LPX_HIP_TRY(hipMalloc((void**)&t->bnd.chg, 2 * need));
+        t->bnd.chg_bytes = 2 * need;
+    }
+    e->lower = reinterpret_cast<double*>(t->bnd.chg);
+    e->upper = e->lower + K; e->shift = e->upper + K; e->save = e->shift + K;
+    e->cols = reinterpret_cast<int32_t*>(e->save + 2 * (size_t)K);
+    LPX_HIP_TRY(hipMemcpyAsync(e->lower, lower, sizeof(double) * K, hipMemcpyHostToDevice, t->stream));
+    LPX_HIP_TRY(hipMemcpyAsync(e->upper, upper, sizeof(double) * K, hipMemcpyHostToDevice, t->stream));
+    LPX_HIP_TRY(hipMemcpyAsync(e->cols, cols, sizeof(int32_t) * K, hipMemcpyHostToDevice, t->stream));
+    return 0;
+}
+
+// The three bounded loops in one body: dual = 0 is lpx_bounded_run, 1 lpx_bounded_dual_run, 2 its form that skips fixed columns.
+// The value goes into the parameter record, so that every form selects its own kernel and keys its own cached graph.
+int bounded_run(lpx_tableau* t, const lpx_run_opts* o, int dual, lpx_pivot_cb cb, void* user, lpx_stats* st)
+{
+    const std::string w = dual ? "lpx_bounded_dual_run" : "lpx_bounded_run";
+    if (!t) { set_error(w + ": null tableau"); return LPX_EINVAL; }
+    lpx_run_opts d; if (!o) { lpx_default_opts(&d, dual ? 1 : 0); o = &d; }
+    if (t->R < 2) { set_error(w + ": tableau needs at least one constraint row"); return LPX_EINVAL; }
+    if (o->resident > 0) { set_error(w + ": there is no resident form of the bounded " + (dual ? "dual loop" : "loop")); return LPX_EINVAL; }
+    int rc = check_bounds(t, w.c_str(), false); if (rc) return rc;
+    rc = bounded_ready(t, false); if (rc) return rc;
+    BndParams b; std::memset(&b, 0, sizeof(b));
+    b.P = base_params(t, o, MODE_BOUNDED);
+    b.P.us = nullptr; b.P.part_v = nullptr; b.P.part_i = nullptr; b.P.nblk = 0; b.P.qsel = 0;   // single-workgroup select
+    b.ub = t->bnd.ub; b.flip = t->bnd.flip; b.dual = dual;
+    LoopCtx c; DevState init;
+    make_ctx(t, b.P, b, [b](hipStream_t s, hipEvent_t e0, hipEvent_t e1) -> int {
+        if (b.dual) LPX_HIP_TRY(launch_bounded_dual_select(b, s));
+        else LPX_HIP_TRY(launch_bounded_select(b, s));
+        // a launch that ended on a flip or on a final status leaves nothing to update: lpx_update returns at once
+        LPX_HIP_TRY(launch_update(b.P, b.P.pcol, b.P.pcol, s, e0, e1));
+        return 0;
+    }, c, init);
+    lpx_stats local; std::memset(&local, 0, sizeof(local));
+    int64_t* n = t->bnd.bcounts;
+    n[0] = n[1] = n[2] = 0;
+    rc = run_device_loop(c, init, o, (long long)o->max_iter + 2, cb, user, &local);
+    if (rc < 0) return rc;
+    // the select kernel counts the pivots per kind in the two counters the dual path uses for its phases; only the primal loop flips
+    n[0] = t->hst->fdf_count; n[1] = t->hst->dual_iter;
+    if (!dual) n[2] = (int64_t)t->hst->iter - n[0] - n[1];
+    local.pivots = n[0] + n[1]; local.fdf_pivots = 0; local.cleanup_pivots = 0;
+    if (st) { const double h2d = st->h2d_ms, d2h = st->d2h_ms; *st = local; st->h2d_ms = h2d; st->d2h_ms = d2h; }
+    return rc;
+}
+
+// the two dualize launches; the counts stay on the device behind the list
+int enqueue_dualize_list(lpx_tableau* t, double eps)
+{
+    LPX_HIP_TRY(launch_dualize_list(t->T, t->ld, t->R, t->C - 1, t->bnd.ub, eps, t->bnd.dzl + 4, t->bnd.dzl, t->stream));
+    return 0;
+}
+int enqueue_dualize_apply(lpx_tableau* t)
+{
+    LPX_HIP_TRY(launch_dualize_apply(t->T, t->ld, t->R, t->C - 1, t->bnd.ub, t->bnd.flip, t->bnd.dzl + 4, t->bnd.dzl, t->rhsbuf, t->stream));
+    return 0;
+}
+
+// the pick launch and the copy of its record into the pinned slab (the caller waits)
+int enqueue_pick(lpx_tableau* t, int nint, const uint8_t* is_int, double tol)
+{
+    if (is_int && nint > 0) LPX_HIP_TRY(hipMemcpyAsync(t->bnd.pickmask, is_int, (size_t)nint, hipMemcpyHostToDevice, t->stream));
+    PickParams p; std::memset(&p, 0, sizeof(p));
+    p.T = t->T; p.ld = t->ld; p.R = t->R; p.Cm = t->C - 1;
+    p.basis = t->basis; p.ub = t->bnd.ub; p.flip = t->bnd.flip; p.lo = t->bnd.lo_used ? t->bnd.lo : nullptr;
+    p.nint = nint; p.is_int = (is_int && nint > 0) ? t->bnd.pickmask : nullptr; p.tol = tol;
+    p.ws = t->ws; p.out = t->bnd.pickrec;
+    LPX_HIP_TRY(launch_branch_pick(p, t->stream));
+    NodeSlab* slab = reinterpret_cast<NodeSlab*>(t->bnd.nodeslab);
+    LPX_HIP_TRY(hipMemcpyAsync(&slab->pick, t->bnd.pickrec, sizeof(lpx_branch_pick), hipMemcpyDeviceToHost, t->stream));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- bounded-variable primal and dual simplex (select kernels in lpx_bounded.hip / lpx_bounded_dual.hip, update = lpx_update) ----
+int lpx_tableau_set_bounds(lpx_tableau* t, int ncols, const double* ub)
+{
+    if (!t) { set_error("lpx_tableau_set_bounds: null handle"); return LPX_EINVAL; }
+    if (!ub && ncols == 0) { t->bnd.bounds_set = false; t->bnd.bounds_C = 0; return 0; }
+    if (!ub || ncols != t->C - 1) { set_error("lpx_tableau_set_bounds: ncols must be the live C - 1 and ub non-null"); return LPX_EINVAL; }
+    for (int j = 0; j < ncols; ++j)
+        if (!(ub[j] >= 0.0)) { set_error("lpx_tableau_set_bounds: ub[" + std::to_string(j) + "] is negative or NaN"); return LPX_EINVAL; }
+    int rc = ensure_device(); if (rc) return rc;
+    rc = bound_buffers(t); if (rc) return rc;
+    rc = bounds_fill_inf(t); if (rc) return rc;            // columns beyond the live shape: unbounded; every flip cleared
+    LPX_HIP_TRY(hipMemcpy(t->bnd.ub, ub, sizeof(double) * ncols, hipMemcpyHostToDevice));
+    t->bnd.bounds_set = true; t->bnd.bounds_C = t->C;
+    return 0;
+}
+
+int lpx_bounded_counts(lpx_tableau* t, int64_t counts[3])
+{
+    if (!t || !counts) { set_error("lpx_bounded_counts: null argument"); return LPX_EINVAL; }
+    for (int k = 0; k < 3; ++k) counts[k] = t->bnd.bcounts[k];
+    return 0;
+}
+
+int lpx_bounded_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, void* user, lpx_stats* st) { return bounded_run(t, o, 0, cb, user, st); }
+int lpx_bounded_dual_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, void* user, lpx_stats* st) { return bounded_run(t, o, 1, cb, user, st); }
+
+int lpx_bounded_dual_run2(lpx_tableau* t, const lpx_run_opts* o, int flags, lpx_pivot_cb cb, void* user, lpx_stats* st)
+{
+    if (flags & ~LPX_BDUAL_SKIP_FIXED) { set_error("lpx_bounded_dual_run2: unknown flag"); return LPX_EINVAL; }
+    return bounded_run(t, o, (flags & LPX_BDUAL_SKIP_FIXED) ? 2 : 1, cb, user, st);
+}
+
+int lpx_tableau_bounded_solution(lpx_tableau* t, int nvars, double* x, double* z, uint8_t* at_upper)
+{
+    if (!t || nvars < 0 || nvars > t->C - 1 || (nvars > 0 && !x)) { set_error("lpx_tableau_bounded_solution: bad argument"); return LPX_EINVAL; }
+    { int rc = check_bounds(t, "lpx_tableau_bounded_solution", false); if (rc) return rc; }
+    const int m = t->R - 1, Cm = t->C - 1;
+    std::vector<double> rhs(t->R), ub(Cm, 1.0 / 0.0);
+    std::vector<int32_t> basis(m > 0 ? m : 1);
+    std::vector<uint8_t> flip(Cm, 0);
+    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+    LPX_HIP_TRY(hipMemcpy2D(rhs.data(), sizeof(double), t->T + Cm, sizeof(double) * t->ld, sizeof(double), t->R, hipMemcpyDeviceToHost));
+    if (m > 0) LPX_HIP_TRY(hipMemcpy(basis.data(), t->basis, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
+    if (t->bnd.bounds_set && Cm > 0) {
+        LPX_HIP_TRY(hipMemcpy(ub.data(), t->bnd.ub, sizeof(double) * Cm, hipMemcpyDeviceToHost));
+        LPX_HIP_TRY(hipMemcpy(flip.data(), t->bnd.flip, Cm, hipMemcpyDeviceToHost));
+    }
+    std::vector<double> lo;                             // only where a bound change has stored a non-zero lower shift
+    if (t->bnd.bounds_set && t->bnd.lo_used && Cm > 0) {
+        lo.resize(Cm);
+        LPX_HIP_TRY(hipMemcpy(lo.data(), t->bnd.lo, sizeof(double) * Cm, hipMemcpyDeviceToHost));
+    }
+    std::vector<double> v(Cm, 0.0);
+    std::vector<uint8_t> basic(Cm, 0);
+    for (int i = 0; i < m; ++i) if (basis[i] >= 0 && basis[i] < Cm) { v[basis[i]] = rhs[i]; basic[basis[i]] = 1; }
+    for (int j = 0; j < nvars; ++j) {
+        x[j] = flip[j] ? ub[j] - v[j] : v[j];
+        if (!lo.empty()) x[j] = x[j] + lo[j];
+        if (at_upper) at_upper[j] = (flip[j] && !basic[j]) ? 1 : 0;
+    }
+    if (z) *z = rhs[m];
+    return 0;
+}
+
+// lo, ub and flip of the live columns (each optional); a handle without bounds: unshifted, unbounded, unflipped
+static int bound_state(lpx_tableau* t, double* lo, double* ub, uint8_t* flip, const char* what)
+{
+    const int n = t->C - 1;
+    if (!t->bnd.bounds_set || !t->bnd.ub) {
+        for (int j = 0; j < n; ++j) { if (lo) lo[j] = 0.0; if (ub) ub[j] = 1.0 / 0.0; if (flip) flip[j] = 0; }
+        return 0;
+    }
+    { int rc = check_bounds(t, what, false); if (rc) return rc; }
+    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+    if (lo && n > 0) LPX_HIP_TRY(hipMemcpy(lo, t->bnd.lo, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (ub && n > 0) LPX_HIP_TRY(hipMemcpy(ub, t->bnd.ub, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (flip && n > 0) LPX_HIP_TRY(hipMemcpy(flip, t->bnd.flip, n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int lpx_tableau_bound_state(lpx_tableau* t, double* lo, double* ub, uint8_t* flip)
+{
+    if (!t) { set_error("lpx_tableau_bound_state: null handle"); return LPX_EINVAL; }
+    return bound_state(t, lo, ub, flip, "lpx_tableau_bound_state");
+}
+
+int lpx_tableau_bound_flags(lpx_tableau* t, uint8_t* flip)
+{
+    if (!t || !flip) { set_error("lpx_tableau_bound_flags: null argument"); return LPX_EINVAL; }
+    return bound_state(t, nullptr, nullptr, flip, "lpx_tableau_bound_flags");
+}
+
+int lpx_tableau_change_bounds(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper)
+{
+    int rc = check_change_args(t, K, cols, lower, upper, "lpx_tableau_change_bounds"); if (rc) return rc;
+    const int Cm = t->C - 1;
+    rc = ensure_device(); if (rc) return rc;
+    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+    BoundEdit e;
+    rc = stage_bound_edit(t, K, cols, lower, upper, "lpx_tableau_change_bounds", &e); if (rc) return rc;
+    t->suspended = t->suspended2 = t->fsuspended = false;
+    if (K > 0) {
+        // shift[k] from the old lo / ub / flip of cols[k], new ub / lo stored; then T[:,Cm] and rhsbuf shifted, k in order
+        LPX_HIP_TRY(launch_bounds_shift(K, e.cols, e.lower, e.upper, t->bnd.ub, t->bnd.lo, t->bnd.flip, e.shift, t->stream));
+        LPX_HIP_TRY(launch_bounds_apply(t->T, t->ld, t->R, Cm, K, e.cols, e.shift, t->rhsbuf, t->stream));
+        if (e.any_lo) t->bnd.lo_used = true;
+    }
+    LPX_HIP_TRY(hipMemsetAsync(t->st, 0, sizeof(DevState), t->stream));      // the loop state, as lpx_tableau_build_child resets it
+    LPX_HIP_TRY(hipStreamSynchronize(t->stream));                            // the caller's arrays are free again
+    return 0;
+}
+
+// ---- branch and bound by bound changes (kernels in lpx_bnb_bounded.hip) ----
+int lpx_tableau_dualize(lpx_tableau* t, double eps, int64_t counts[2])
+{
+    if (!t) { set_error("lpx_tableau_dualize: null handle"); return LPX_EINVAL; }
+    if (!counts) { set_error("lpx_tableau_dualize: null counts"); return LPX_EINVAL; }
+    if (!(eps >= 0.0)) { set_error("lpx_tableau_dualize: eps is negative or NaN"); return LPX_EINVAL; }
+    int rc = check_bounds(t, "lpx_tableau_dualize", true); if (rc) return rc;
+    if (t->R < 1 || t->C < 1) { set_error("lpx_tableau_dualize: empty tableau"); return LPX_EINVAL; }
+    rc = bounded_ready(t, true); if (rc) return rc;
+    t->suspended = t->suspended2 = t->fsuspended = false;
+    rc = enqueue_dualize_list(t, eps); if (rc) return rc;
+    rc = enqueue_dualize_apply(t); if (rc) return rc;
+    NodeSlab* slab = reinterpret_cast<NodeSlab*>(t->bnd.nodeslab);
+    LPX_HIP_TRY(hipMemcpyAsync(slab->cnt, t->bnd.dzl, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
+    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+    counts[0] = slab->cnt[0]; counts[1] = slab->cnt[1];
+    return 0;
+}
+
+int lpx_tableau_branch_pick(lpx_tableau* t, int nint, const uint8_t* is_int, double tol, lpx_branch_pick* out)
+{
+    int rc = check_pick_args(t, nint, tol, out, "lpx_tableau_branch_pick"); if (rc) return rc;
+    rc = check_bounds(t, "lpx_tableau_branch_pick", false); if (rc) return rc;
+    if (t->R < 1 || t->C < 1) { set_error("lpx_tableau_branch_pick: empty tableau"); return LPX_EINVAL; }
+    rc = bounded_ready(t, true); if (rc) return rc;
+    rc = enqueue_pick(t, nint, is_int, tol); if (rc) return rc;
+    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+    *out = reinterpret_cast<NodeSlab*>(t->bnd.nodeslab)->pick;
+    return 0;
+}
+
+int lpx_bounded_node(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const lpx_run_opts* o,
+                     int nint, const uint8_t* is_int, double tol, lpx_node_record* out)
+{
+    int rc = check_change_args(t, K, cols, lower, upper, "lpx_bounded_node"); if (rc) return rc;
+    rc = check_pick_args(t, nint, tol, out, "lpx_bounded_node"); if (rc) return rc;
+    lpx_run_opts d; if (!o) { lpx_default_opts(&d, 1); o = &d; }
+    if (t->R < 2) { set_error("lpx_bounded_node: tableau needs at least one constraint row"); return LPX_EINVAL; }
+    if (o->resident > 0) { set_error("lpx_bounded_node: there is no resident form of the bounded dual loop"); return LPX_EINVAL; }
+    if (!(o->eps >= 0.0)) { set_error("lpx_bounded_node: eps is negative or NaN"); return LPX_EINVAL; }
+    const int Cm = t->C - 1;
+    rc = bounded_ready(t, true); if (rc) return rc;
+    std::memset(out, 0, sizeof(*out));
+    out->pick.var = -1;
+    BoundEdit e;
+    rc = stage_bound_edit(t, K, cols, lower, upper, "lpx_bounded_node", &e); if (rc) return rc;
+    if (K > 0) {
+        // the new ub and lo first (small arrays only): the list of the flips needs them, and the tableau is still untouched
+        LPX_HIP_TRY(launch_bounds_save(K, e.cols, t->bnd.ub, t->bnd.lo, e.save, 0, t->stream));
+        LPX_HIP_TRY(launch_bounds_shift(K, e.cols, e.lower, e.upper, t->bnd.ub, t->bnd.lo, t->bnd.flip, e.shift, t->stream));
+    }
+    // the list reads the objective row left of the RHS, which the RHS shift of the edit does not write: listing before that
+    // shift gives the list of listing after it, and an unrepairable column is found with the tableau as it was
+    rc = enqueue_dualize_list(t, o->eps); if (rc) return rc;
+    NodeSlab* slab = reinterpret_cast<NodeSlab*>(t->bnd.nodeslab);
+    LPX_HIP_TRY(hipMemcpyAsync(slab->cnt, t->bnd.dzl, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
+    // wait 1: the counts (the caller's arrays are free again)
+    LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+    out->flips = slab->cnt[0]; out->unrepairable = slab->cnt[1];
+    if (out->unrepairable > 0) {
+        LPX_HIP_TRY(launch_bounds_save(K, e.cols, t->bnd.ub, t->bnd.lo, e.save, 1, t->stream));     // ub and lo as they were
+        LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+        out->flips = 0;
+        set_error("lpx_bounded_node: " + std::to_string(out->unrepairable) + " column(s) with a negative reduced cost and no upper "
+                  "bound: a bound flip cannot restore dual feasibility");
+        return LPX_EINVAL;
+    }
+    t->suspended = t->suspended2 = t->fsuspended = false;
+    if (e.any_lo) t->bnd.lo_used = true;
+    if (K > 0) LPX_HIP_TRY(launch_bounds_apply(t->T, t->ld, t->R, Cm, K, e.cols, e.shift, t->rhsbuf, t->stream));
+    rc = enqueue_dualize_apply(t); if (rc) return rc;
+    // the loop (it resets the state record itself and waits once per batch)
+    const int status = bounded_run(t, o, 2, nullptr, nullptr, nullptr);
+    if (status < 0) return status;
+    out->status = status; out->events = t->hst->iter; out->kind0 = t->bnd.bcounts[0]; out->kind1 = t->bnd.bcounts[1];
+    if (status == LPX_OPTIMAL) {
+        rc = enqueue_pick(t, nint, is_int, tol); if (rc) return rc;
+        LPX_HIP_TRY(hipStreamSynchronize(t->stream));                                    // last wait: the pick record
+        out->pick = slab->pick;
+    } else {
+        // no pick: z as the tableau stands, through the same slab
+        LPX_HIP_TRY(hipMemcpyAsync(&slab->pick.z, t->T + (size_t)(t->R - 1) * t->ld + Cm, sizeof(double), hipMemcpyDeviceToHost, t->stream));
+        LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+        out->pick.var = -1; out->pick.candidates = 0; out->pick.x_var = 0.0; out->pick.z = slab->pick.z;
+    }
+    return status;
+}
+
+}  // extern "C"

@@ -394,6 +394,42 @@ def test_node_refuses_an_unrepairable_column_and_leaves_the_handle_alone(gpu):
         _same_state(dt, T, basis, ub, np.zeros(len(ub)), np.zeros(len(ub), dtype=np.uint8), "after argument errors")
 
 
+def test_change_bounds_and_node_share_one_staging_buffer_across_regrowth(gpu):
+    """lpx_tableau_change_bounds and lpx_bounded_node stage their edits in one buffer of the handle, with one layout (lower, upper,
+    shift, saved (ub, lo), cols: 44 bytes per column, grown to twice the need).  K = 1 sizes it (88 bytes), K = 3 regrows it (264),
+    the refused K = 6 fills those 264 bytes to the last one and restores ub / lo from the save area, K = 2 and K = 0 then run on the
+    larger buffer.  The seed is one for which the restatement accepts every step but the third and finds that one unrepairable
+    (chosen on the CPU: steps two and five end OPTIMAL after 5 events each, the fifth with one flip)."""
+    n, m, seed = 10, 4, 2
+    dt, root = _solved_handle(gpu, n, m, seed)
+    p = np.random.default_rng(seed).permutation(n)
+    with dt:
+        h = N.Handle(*root)
+
+        def change(cols, lower, upper, what):
+            dt.change_bounds(cols, lower, upper)
+            h.T, h.ub, h.lo = D.change_bounds(h.T, h.ub, h.lo, h.flip, cols, lower, upper)
+            _same_state(dt, h.T, h.basis, h.ub, h.lo, h.flip, what)
+
+        change(p[:1], [1.0], [1.0], "after change_bounds with K = 1")
+        got = _node_both(dt, h, np.sort(p[1:4]), [0.0, 1.0, 0.0], [0.0, 1.0, 0.0], n)            # K = 3
+        assert got["status"] == N.OPTIMAL and got["events"] > 0
+        # K = 6: the four edited columns and two more relaxed, to +inf where the column is not flipped (+inf on a flipped one is an
+        # argument error, not this refusal); a fixed column the loop left with a negative reduced cost is then beyond repair
+        cols = np.sort(p[:6])
+        upper = np.where(h.flip[cols] != 0, 1.0, INF)
+        before = (h.T.copy(), h.basis.copy(), h.ub.copy(), h.lo.copy(), h.flip.copy())
+        want = h.node(cols, np.zeros(6), upper, n)
+        assert want["status"] is None and want["unrepairable"] > 0 and np.isinf(upper).any()
+        with pytest.raises(gpu.LpxError) as e:
+            dt.bounded_node(cols, np.zeros(6), upper, n)
+        assert e.value.code == gpu._lib.EINVAL and "%d column(s)" % want["unrepairable"] in str(e.value)
+        _same_state(dt, *before, "after the refused node")
+        change(np.sort(p[[0, 2]]), [0.0, 0.0], [1.0, 1.0], "after change_bounds with K = 2")
+        got = _node_both(dt, h, [], [], [], n)                                                   # K = 0
+        assert got["status"] == N.OPTIMAL and got["flips"] > 0
+
+
 # ---- the driver --------------------------------------------------------------------------------------------------------
 def _problem(lpx, c, A, rel, b, sense=0):
     return lpx.LPProblem.from_arrays(sense, c, A, rel, b)
