@@ -15,6 +15,17 @@ static constexpr int MB_NT = 256;            // lanes of one workgroup of the mu
 static constexpr int MB_QREC = 128;
 static constexpr int MB_CNT = 160;
 static constexpr int MB_MAXB = 64;           // at most this many workgroups (partials fit one wave)
+// deferred pivots of the one-launch primal loop and its latency-shaped select-only kernel (lpx_pivot_fused.hip: lpx_pivot_select)
+static constexpr int FP_DMAX = 16;           // deepest deferral: pivots applied per sweep
+static constexpr int SELP_NT = 512;
+static constexpr int SELP_U = 3;
+static constexpr int SELP_PASS_ROWS = 1536;                  // rows of one pass over the column
+static constexpr int SELP_SB = 8;                            // pending pivots whose factor loads are issued together
+static constexpr int SELP_LDS_ROWS = 10240;                  // row cap of this form: 80 KB of ratios in LDS
+static constexpr int SELP_MIN_MB = 64;                       // handles of at most this many MB keep the old form (see launch_pivot_fused)
+static constexpr int SELP_PMAX = FP_DMAX - 1;                // most pending pivots of a select-only launch
+static_assert(SELP_PASS_ROWS == SELP_NT * SELP_U, "rows of a pass: SELP_U per lane");
+static_assert(SELP_PMAX <= 64 && SELP_PMAX <= 2 * SELP_SB, "pending scalars: one lane each; row prefetch: two groups");
 
 // ------------------------------------------------------------------------------------------------
 // workgroup primitives (wave64)

@@ -88,7 +88,7 @@ struct PickParams {
 };
 hipError_t launch_branch_pick(const PickParams& p, hipStream_t s);
 
-// launchers (lpx_kernels.hip)
+// ---- lpx_kernels.hip: the two-launch select and update paths
 hipError_t launch_select(const SelParams& p, hipStream_t s);       // gather-based (dual path)
 hipError_t launch_select_la(const SelParams& p, hipStream_t s);    // lookahead (primal / forced)
 hipError_t launch_la_init(const SelParams& p, hipStream_t s);
@@ -103,7 +103,36 @@ hipError_t launch_update(const SelParams& p, double* fac0, double* fac1, hipStre
 hipError_t launch_select_mb(const SelParams& p, hipStream_t s);
 hipError_t launch_update_mb(const SelParams& p, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 int select_mb_blocks(int C);
-// Fused pivot (primal loop without a per-pivot callback, lpx_pivot_fused / _c in lpx_kernels.hip): ONE launch applies pivot k
+hipError_t launch_group_iter(const SelParams* arr, int count, int dual, int max_nblk, int max_upd_blocks, hipStream_t s,
+                             int maxR, int maxC);       // capacity of the largest node: sizes the dual select's LDS
+hipError_t launch_group_init(const SelParams* arr, int count, hipStream_t s);
+hipError_t launch_group_rhs_init(const SelParams* arr, int count, hipStream_t s);     // dual groups: contiguous RHS copy
+hipError_t launch_rhs_init(const SelParams& p, hipStream_t s);
+int update_blocks(int ld, int R);
+int update_policy(int ld, int R);            // 0 = cache-resident update kernel, 1 = all-nt streaming, 2 = mixed-store streaming
+hipError_t kernels_init();          // one-time function attributes
+
+// ---- lpx_nodes.hip: branch-and-bound node assembly (K9)
+struct BuildDesc { double* T; int32_t* basis; int32_t* shape; DevState* st; int ld, R, C, cut0; };
+hipError_t launch_build_nodes(const double* T0, int ld0, int R0, int C0, const BuildDesc* descs, int count, int maxld, int maxR,
+                              const int32_t* cvar, const double* ccoef, const double* czero, const double* crhs, hipStream_t s);
+struct ChildDesc { const double* Tp; const int32_t* basis_p; double* T; int32_t* basis; int32_t* shape; DevState* st;
+                   int ldp, Rp, Cp, ld, var, ik, is_ge, pad; double bound; };
+hipError_t launch_build_children(const ChildDesc* descs, int count, int maxld, int maxR, hipStream_t s);
+struct ParkDesc { const double* srcT; double* dstT; const int32_t* srcB; int32_t* dstB; size_t doubles; int m, pad; };
+hipError_t launch_park_many(const ParkDesc* descs, int count, int blocks_per_node, hipStream_t s);
+struct GatherDesc { const double* T; const int32_t* basis; int ld, R, C, off; };
+hipError_t launch_gather_solution(const GatherDesc* descs, int count, double* out_rhs, int32_t* out_basis, hipStream_t s);
+hipError_t launch_build_child(const double* Tp, int ldp, int Rp, int Cp, const int32_t* basis_p, double* T, int ld,
+                              int var, int ik, int is_ge, double bound, int32_t* basis, hipStream_t s);
+hipError_t launch_build_node(const double* T0, int ld0, int R0, int C0, double* T, int ld, int R, int C,
+                             const int32_t* cvar, const double* ccoef, const double* czero, const double* crhs,
+                             int32_t* basis, hipStream_t s);
+hipError_t launch_states_scatter(const SelParams* arr, const DevState* src_pinned, int count, hipStream_t s);
+hipError_t launch_states_gather(const SelParams* arr, DevState* dst_pinned, int count, hipStream_t s);
+
+// ---- lpx_pivot_fused.hip: the one-launch primal pivot (K4f) and its deferred pivots
+// Fused pivot (primal loop without a per-pivot callback, lpx_pivot_fused / _c): ONE launch applies pivot k
 // out of place (buffer b -> buffer 1 - b) and, in its first `nblk` workgroups, selects pivot k + 1 from the tableau it reads.
 // P.T / P.prow / P.rhsbuf are the buffers of index 0, the members below those of index 1; P.col0 / P.col1 the factor columns.
 struct FusedParams {
@@ -125,7 +154,9 @@ hipError_t launch_fused_init(const FusedParams& f, hipStream_t s);
 hipError_t launch_pivot_fused(const FusedParams& f, long long L, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 // the n pivots a finished run left pending (its last record: buffer, count, oldest slot), applied into buffer 0
 hipError_t launch_pivot_flush(const FusedParams& f, int buf, int n, int slot0, hipStream_t s);
-// fused group step (lpx_group_fused / _c): one launch per step for a whole group of node LPs, see lpx_kernels.hip
+hipError_t pivot_fused_init();      // one-time function attribute of lpx_pivot_select
+
+// ---- lpx_group_fused.hip: the fused group step (K4g), one launch per step for a whole group of node LPs
 hipError_t launch_group_fused_init(const FusedParams* arr, const int* fresh, int nfresh, const DevState* init, hipStream_t s);
 hipError_t launch_group_fused_gather(const FusedParams* arr, int count, DevState* out, int* cur, hipStream_t s);
 int group_fused_blocks(int ld, int R);
@@ -135,31 +166,7 @@ int group_fused_comp_ints(int cap);
 int group_fused_comp_hdr();     // ints in front of the list of a parity region: {count, padding}
 hipError_t launch_group_fused(const FusedParams* arr, const int* live, int nlive, int per_node, int lpar, size_t live_bytes, hipStream_t s,
                               int* comp, int cap, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
-hipError_t launch_states_scatter(const SelParams* arr, const DevState* src_pinned, int count, hipStream_t s);
-hipError_t launch_states_gather(const SelParams* arr, DevState* dst_pinned, int count, hipStream_t s);
-hipError_t launch_group_iter(const SelParams* arr, int count, int dual, int max_nblk, int max_upd_blocks, hipStream_t s,
-                             int maxR, int maxC);       // capacity of the largest node: sizes the dual select's LDS
-hipError_t launch_group_init(const SelParams* arr, int count, hipStream_t s);
-hipError_t launch_group_rhs_init(const SelParams* arr, int count, hipStream_t s);     // dual groups: contiguous RHS copy
-hipError_t launch_rhs_init(const SelParams& p, hipStream_t s);
-int update_blocks(int ld, int R);
-struct BuildDesc { double* T; int32_t* basis; int32_t* shape; DevState* st; int ld, R, C, cut0; };
-hipError_t launch_build_nodes(const double* T0, int ld0, int R0, int C0, const BuildDesc* descs, int count, int maxld, int maxR,
-                              const int32_t* cvar, const double* ccoef, const double* czero, const double* crhs, hipStream_t s);
-struct ChildDesc { const double* Tp; const int32_t* basis_p; double* T; int32_t* basis; int32_t* shape; DevState* st;
-                   int ldp, Rp, Cp, ld, var, ik, is_ge, pad; double bound; };
-hipError_t launch_build_children(const ChildDesc* descs, int count, int maxld, int maxR, hipStream_t s);
-struct ParkDesc { const double* srcT; double* dstT; const int32_t* srcB; int32_t* dstB; size_t doubles; int m, pad; };
-hipError_t launch_park_many(const ParkDesc* descs, int count, int blocks_per_node, hipStream_t s);
-struct GatherDesc { const double* T; const int32_t* basis; int ld, R, C, off; };
-int update_policy(int ld, int R);            // 0 = cache-resident update kernel, 1 = all-nt streaming, 2 = mixed-store streaming
-hipError_t launch_gather_solution(const GatherDesc* descs, int count, double* out_rhs, int32_t* out_basis, hipStream_t s);
-hipError_t launch_build_child(const double* Tp, int ldp, int Rp, int Cp, const int32_t* basis_p, double* T, int ld,
-                              int var, int ik, int is_ge, double bound, int32_t* basis, hipStream_t s);
-hipError_t launch_build_node(const double* T0, int ld0, int R0, int C0, double* T, int ld, int R, int C,
-                             const int32_t* cvar, const double* ccoef, const double* czero, const double* crhs,
-                             int32_t* basis, hipStream_t s);
-hipError_t kernels_init();          // one-time function attributes
+
 // FP64 matrix-core GEMM (lpx_mfma.hip): C = I - A*B (mode 0, max |C_ij| -> *absmax as double bits) or C = D + A*B (mode 1)
 hipError_t launch_dgemm_mfma(const double* A, int lda, const double* B, int ldb, double* C, int ldc, const double* D, int ldd,
                              int M, int N, int K, int mode, unsigned long long* absmax, hipStream_t s);

@@ -28,7 +28,8 @@ int ensure_device()
         g_device = 0;
         LPX_HIP_TRY(hipSetDevice(0));
     }
-    std::call_once(g_init_once, [] { g_init_err = kernels_init(); if (g_init_err == hipSuccess) g_init_err = resident_init();
+    std::call_once(g_init_once, [] { g_init_err = kernels_init(); if (g_init_err == hipSuccess) g_init_err = pivot_fused_init();
+                                     if (g_init_err == hipSuccess) g_init_err = resident_init();
                                      if (g_init_err == hipSuccess) g_init_err = resident_group_init();
                                      if (g_init_err == hipSuccess) g_init_err = resident_regs_init();
                                      if (g_init_err == hipSuccess) g_init_err = resident_col_init(); });

@@ -1,0 +1,728 @@
+// lpx_pivot_fused.hip -- the one-launch primal pivot (K4f) and its deferred pivots: sweep kernels of every depth,
+// the two select-only kernels, the flush and their launchers.  Built with -ffp-contract=off like every tile (lpx_kernels.hip).
+#include <algorithm>
+#include "lpx_scan.h"
+#include "lpx_tile.h"
+
+namespace lpx {
+
+// ------------------------------------------------------------------------------------------------
+// Fused pivot (primal loop without a per-pivot callback, any size): update(k) OUT OF PLACE + select(k+1), one launch.
+//
+// With the update in place, select(k+1) has to wait for update(k): it reads column q', row r' and the objective row of
+// T_{k+1}.  All three are rank-1 corrections of the same parts of T_k with data select(k) already produced (the factor
+// column and the normalised pivot row of pivot k) -- so if update(k) writes T_{k+1} into a SECOND buffer and leaves T_k
+// alone, select(k+1) depends on nothing update(k) produces and runs beside it: the first `nblk` workgroups of this grid are
+// lpx_select_mb's workgroups reading T_k through the correction `T_k[i,j] - fac_k[i] * prow_k[j]` (the very mul-then-sub
+// the update stores, so every value is bit-identical to what the two-launch path reads back from memory), the others are
+// the streaming update's waves.  A pivot then costs the sweep alone (117.7 us at 4097 x 12289 against 117.4 + 10.0);
+// tools/kbench/oop.hip measured the shape first: a ping-pong sweep is as fast as the in-place one (115.5 vs 116.0 us),
+// 256-lane workgroups cost it 1.6 us, and 32 select-shaped workgroups at the head of the grid another 0.5 us.
+// Smaller tableaux gain more (tools/probe_fused_mid.py: 1.03-1.42x from 129 x 385 to 308 MB); cache policy: fused_policy below.
+//
+// Nothing is read and written inside one launch: everything a launch reads carries the index `c` of the CURRENT state
+// record (RHS column) or a ring slot of a pending pivot, or is the source tableau; everything it writes carries 1 - c, its own
+// ring slot, or is the destination tableau -- the state records included: a launch reads record `par` and writes record
+// 1 - par, and `par` (like the ring slot) is a launch argument (graph batches are multiples of 2d, so a replay starts where the
+// capture did).  Which buffer holds the stored tableau is part of the record (pad[3], with the pending count: fp_rec below);
+// pad[2] counts launches, for the host to find the last record written.
+//   record c:  (r, q) = pivot k, the newest selected but not yet applied    qn = entering column of pivot k+1
+//   ring slot of pivot k: T_k[r,:] / T_k[r,q],  T_k[:,q],  r        rhs[c] = T_k[:,C-1]
+// P.st is the host's copy of the current record, written by select's first workgroup: one launch behind.
+// A terminal status can be found with pivots still pending: the host applies them (lpx_pivot_flush) before the run returns.
+// ------------------------------------------------------------------------------------------------
+static constexpr int FP_NT = 256;
+
+__global__ __launch_bounds__(SEL_NT) void lpx_fused_init(FusedParams F)
+{
+    __shared__ double s_v[SEL_NW];
+    __shared__ int s_i[SEL_NW];
+    const SelParams& P = F.P;
+    const int R = P.shape ? P.shape[0] : P.R, C = P.shape ? P.shape[1] : P.C;
+    ScanRule rule; rule.forced = 0; rule.eps = P.eps; rule.thresh = P.fthresh; rule.C = C; rule.c0 = 0;
+    // first entering column (ChooseEntering on the objective row as it stands) and the RHS column of record 0
+    int qn = -1;
+    if (P.st->status == LPX_RUNNING) qn = la_prepare_from_T(P, R, C, P.col0, R - 1, rule, s_v, s_i);
+    if (threadIdx.x == 0) {
+        DevState x = *P.st;
+        x.qn = qn; x.r = -1; x.q = -1; x.pad[2] = 1; x.pad[3] = 0;
+        F.rec[0] = x;
+        x.pad[2] = 0;
+        F.rec[1] = x;
+        P.part_i[MB_CNT] = 0;
+    }
+}
+
+// Deferred pivots (LPX_PIVOT_DEFER = d, run_fused).  A sweep moves the whole tableau however many pivots it applies, and
+// select(k+1) needs only column q, the RHS column, row r and the objective row of T_{k+1} -- each of them the stored tableau
+// with the pending pivots applied on the fly.  So launch L of a run (L = 0: the prologue's) is
+//   L % d != 0 or L == 0: select-only (nsel workgroups): pivot L from the stored tableau + the n = L % d pending pivots
+//   otherwise:            sweep: applies pending pivots L-d .. L-1 out of place (oldest first, the very mul-then-sub of d
+//                         single sweeps: every element's value is bit-identical) beside select of pivot L from the source
+// Pivot L's normalised row, factor column and row go to ring slot L % 2d (`lm`, a launch argument): a launch reads the slots of
+// the n <= d pivots before it and writes its own, never one it reads.  d = 1 is the one-pivot-per-sweep kernel of r02 / r03.
+// Record field pad[3] (fp_rec): bit 0 = buffer of the stored tableau, bits 1-5 = pivots pending after the launch, bits 8- =
+// ring slot of the oldest -- the host flushes them (lpx_pivot_flush) when the run is over.
+// (deepest deferral FP_DMAX: lpx_block.h)
+// rows per sweep wave: each pending pivot row a lane loads (from L2) serves ROWS rows of the stream; three rows as in r03 while
+// one or two pivots are applied, eight beyond (at three rows the pivot-row reads grew the d = 8 sweep from 118 to 162 us; at
+// eight, 140 us).  Twelve and sixteen rows spill 12-96 VGPRs inside the 80 the select half leaves (waves_per_eu(6) below).
+__host__ __device__ constexpr int fp_rows(int D) { return D <= 2 ? UPDS_ROWS : 8; }
+__host__ __device__ constexpr int fp_rec(int buf, int npend, int slot0) { return buf | (npend << 1) | (slot0 << 8); }
+// ring slot of pending pivot s (0 = oldest) of n before the launch with ring index lm
+__device__ __forceinline__ int fp_slot(int lm, int n, int s, int ring) { const int k = lm - n + s; return k < 0 ? k + ring : k; }
+
+#ifdef LPX_STAMPS
+// Diagnostic build only: phase stamps of the select-only launch (tools/diag_pivot_select_stamps.py).  Workgroup 0's lane 0 keeps
+// the s_memtime deltas in registers and adds them to lpx_g_stamps[8 + slot] when the launch ends (a store per stamp would put
+// its own round trip into the next phase).  LPX_FS_W first waits for wave 0's loads, so that a phase which only issues loads
+// owns their latency; that serialises phases the shipped kernel overlaps, so the phases' sum exceeds the unstamped duration
+// (slot 20 has the launch's own s_memrealtime span).  Slots: 0 record load and branch, 1 column gather, 2 pending chain,
+// 3 ratio store and barrier, 4 scan, 5 piv chain, 6 row loop, 7 wave and hand-off reduction, 8 tail stores, 9 gather trips,
+// 10-12 gather per trip (the third and later trips together), 20 realtime, 21 launches, 22 pending pivots summed.
+#define LPX_FS_BEGIN(on) const bool fs_on_ = (on) && blockIdx.x == 0 && threadIdx.x == 0; unsigned long long fs_acc_[13] = {0}; \
+    unsigned long long fs_prev_ = __builtin_amdgcn_s_memtime(); const unsigned long long fs_rt0_ = __builtin_amdgcn_s_memrealtime();
+#define LPX_FS(slot) do { if (fs_on_) { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); fs_acc_[(slot)] += n_ - fs_prev_; fs_prev_ = n_; } } while (0)
+#define LPX_FS_W(slot) do { if (fs_on_) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); } LPX_FS(slot); } while (0)
+#define LPX_FS_TRIP(trip) do { if (fs_on_) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); \
+    const unsigned long long n_ = __builtin_amdgcn_s_memtime(), d_ = n_ - fs_prev_; fs_prev_ = n_; fs_acc_[1] += d_; fs_acc_[9] += 1; \
+    if ((trip) == 0) fs_acc_[10] += d_; else if ((trip) == 1) fs_acc_[11] += d_; else fs_acc_[12] += d_; } } while (0)
+#define LPX_FS_END(npend) do { if (fs_on_) { _Pragma("unroll") for (int k_ = 0; k_ < 13; ++k_) lpx_g_stamps[8 + k_] += fs_acc_[k_]; \
+    lpx_g_stamps[28] += __builtin_amdgcn_s_memrealtime() - fs_rt0_; lpx_g_stamps[29] += 1; lpx_g_stamps[30] += (unsigned long long)(npend); } } while (0)
+#else
+#define LPX_FS_BEGIN(on)
+#define LPX_FS(slot) do {} while (0)
+#define LPX_FS_W(slot) do {} while (0)
+#define LPX_FS_TRIP(trip) do {} while (0)
+#define LPX_FS_END(npend) do {} while (0)
+#endif
+
+// select(k+1): the first nsel workgroups of a sweep launch, the whole of a select-only launch.  `sweeps`: this launch applies
+// its n pending pivots too (the stored tableau changes buffer).  U: rows in flight per lane in the column pass (the sweep
+// kernels' register budget of waves_per_eu(6) holds U = 4 with two spilled VGPRs, U = 6 spilled 19; the select-only kernel has no such budget).
+template <int U, int SU, int NC = 0>
+__device__ __forceinline__ void fused_select(const FusedParams& F, int n_, bool sweeps)
+{
+    const int n = NC > 0 ? NC : n_;                          // NC: the count known at compile time (d = 1: r03's select)
+    __shared__ double s_fs;
+    const SelParams& P = F.P;
+    const int t = threadIdx.x, b = blockIdx.x;
+    const int lm = F.lm, ring = 2 * F.defer;
+    // Which record is current comes with the LAUNCH (lm's parity), not from the records: the workgroups of a launch start over
+    // its whole duration, and one that started after workgroup 0 had written the next record must not take that for the
+    // current one.  (A first form compared sequence numbers on the device; it passed every test because select finishes late
+    // and the scalar cache kept serving the old line -- and broke when a second process shared the GPU.)
+    const int c = lm & 1;
+    LPX_FS_BEGIN(!sweeps)
+    const DevState cur = F.rec[c];
+    DevState* nxt = F.rec + (c ^ 1);
+    const int status = cur.status, seq = cur.pad[2], buf = cur.pad[3] & 1;
+    const int nbuf = sweeps ? (buf ^ 1) : buf;               // where the stored tableau lives once this launch is over
+    const int nsel = P.nblk;
+    if (b == 0 && t == 0) *P.st = cur;                        // the host's copy: one launch behind
+    LPX_FS_W(0);
+    if (status != LPX_RUNNING) {
+        if (b == 0 && t == 0) { DevState x = cur; x.pad[2] = seq + 1; *nxt = x; }
+        return;
+    }
+    const int R = P.shape ? P.shape[0] : P.R, C = P.shape ? P.shape[1] : P.C;
+    const size_t ld = (size_t)P.ld, fld = (size_t)P.R;
+    const double* __restrict__ src = buf ? F.T1 : P.T;
+    double* __restrict__ prown = F.pring + (size_t)lm * ld;
+    double* __restrict__ facn = F.fring + (size_t)lm * fld;
+    const double* __restrict__ rhsc = c ? F.rhs1 : P.rhsbuf;
+    double* __restrict__ rhsn = c ? P.rhsbuf : F.rhs1;
+    const int m = R - 1;
+    const int iter = cur.iter, primal_count = cur.primal_count;
+    const int q = cur.qn;
+    int final_status = LPX_RUNNING, r = -1;
+    // loop head, Models/PrimalSimplex.cs:95-106
+    if (primal_count >= P.max_iter) final_status = LPX_ITER_LIMIT;
+    else if (q < 0) final_status = LPX_OPTIMAL;
+    double fs = 0.0;
+    if (final_status == LPX_RUNNING) {
+        // T_{k+1}[i,q] and T_{k+1}[i,C-1] as the sweep stores them: the column through every pending pivot (row r_s: the
+        // normalised pivot row), the RHS column kept current in rhsc up to the newest pending pivot, which is applied here.
+        // The pending pivots' scalars are uniform loads beside the column's (staging them in LDS behind a barrier cost the
+        // 25 MB tableau's loop 14 %: two more round trips per pivot)
+        const int sn = fp_slot(lm, n, n - 1, ring);
+        const int rl = n ? cur.r : -1;                       // the newest pending pivot is the record's
+        const double prhs = n ? F.pring[(size_t)sn * ld + (C - 1)] : 0.0;
+        double* rat = P.ws + (size_t)b * (size_t)(P.R > P.C ? P.R : P.C);
+        for (int i0 = 0; i0 < R; i0 += U * FP_NT) {
+            double v[U], h[U], fl[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int i = min(R - 1, i0 + u * FP_NT + t);    // clamped, not guarded: a guarded load waits for its own branch
+                v[u] = src[(size_t)i * ld + q]; h[u] = rhsc[i];
+            }
+            LPX_FS_TRIP(i0 / (U * FP_NT));
+            // oldest first; the newest pivot's factors are kept for the RHS correction
+#pragma unroll SU
+            for (int s = 0; s < n; ++s) {
+                const int sl = fp_slot(lm, n, s, ring);
+                const double* __restrict__ fac = F.fring + (size_t)sl * fld;
+                const double pq = F.pring[(size_t)sl * ld + q];
+                const int rs = s == n - 1 ? rl : F.rring[sl];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int i = min(R - 1, i0 + u * FP_NT + t);
+                    fl[u] = fac[i];
+                    const double nv = v[u] - fl[u] * pq;     // mul, then sub: contraction is off
+                    v[u] = i == rs ? pq : nv;
+                }
+            }
+            LPX_FS_W(2);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int i = i0 + u * FP_NT + t;
+                if (i < R) {
+                    const double dn = v[u];
+                    const double nm = n == 0 ? h[u] : (i == rl ? prhs : h[u] - fl[u] * prhs);
+                    rat[i] = dn > P.eps ? nm / dn : __builtin_inf();     // ChooseLeaving's ratio, :229-241
+                    if (b == 0) { facn[i] = dn; rhsn[i] = nm; }          // factors of pivot k+1, numerators of the test after it
+                    if (i == m) s_fs = dn;                               // T_{k+1}[m,q]: row m belongs to exactly one lane
+                }
+            }
+            LPX_FS(3);
+        }
+        __syncthreads();                                     // the slice of ratios is complete (and visible: same CU)
+        LPX_FS(3);
+        fs = s_fs;
+        r = block_hysteresis_segments<FP_NT / 64>(m, P.tol_primal, CompactRatio{rat});
+        LPX_FS(4);
+        if (r < 0) final_status = LPX_UNBOUNDED;
+    }
+    if (final_status != LPX_RUNNING) {
+        if (b == 0 && t == 0) {
+            DevState x = cur;
+            x.status = final_status; x.r = -1; x.q = -1; x.qn = -1; x.pad[2] = seq + 1;
+            x.pad[3] = fp_rec(nbuf, sweeps ? 0 : n, fp_slot(lm, n, 0, ring));
+            *nxt = x;
+        }
+        return;
+    }
+
+    ScanRule rule; rule.forced = 0; rule.eps = P.eps; rule.thresh = P.fthresh; rule.C = C; rule.c0 = 0;
+    const int per = (C + nsel - 1) / nsel;
+    const int j0 = b * per, j1 = min(C, j0 + per);
+    const double* trow = src + (size_t)r * ld;
+    const double* orow = src + (size_t)m * ld;
+    auto pslot = [&](int s) { return fp_slot(lm, n, s, ring); };
+    auto prs = [&](int s) { return s == n - 1 ? cur.r : F.rring[pslot(s)]; };     // the newest: the record's
+    auto pfr = [&](int s) { return F.fring[(size_t)pslot(s) * fld + r]; };
+    auto pfm = [&](int s) { return F.fring[(size_t)pslot(s) * fld + m]; };
+    double piv = trow[q];                                    // T_{k+1}[r,q], the column's own chain
+    for (int s = 0; s < n; ++s) {
+        const double pq = F.pring[(size_t)pslot(s) * ld + q];
+        const double nv = piv - pfr(s) * pq;
+        piv = r == prs(s) ? pq : nv;
+    }
+    LPX_FS_W(5);
+    MinIdx best; rule_init(rule, best);
+#pragma unroll 2
+    for (int j = j0 + t; j < j1; j += FP_NT) {
+        double tr = trow[j], ov = orow[j];                   // -> T_{k+1}[r,j], T_{k+1}[m,j] (m is never a pivot row)
+#pragma unroll SU
+        for (int s = 0; s < n; ++s) {
+            const double pc = F.pring[(size_t)pslot(s) * ld + j];
+            const double nt = tr - pfr(s) * pc;
+            tr = r == prs(s) ? pc : nt;
+            ov = ov - pfm(s) * pc;
+        }
+        const double p = tr / piv;                               // true division, :250
+        prown[j] = p;
+        const double u = ov - fs * p;                            // what the sweep of pivot k+1 will store at T[m,j]
+        rule_feed(rule, best, j, u);
+    }
+    LPX_FS_W(6);
+    best = wave_min_idx(best);
+    // last-workgroup reduction of the partial argmins: the hand-off of lpx_select_mb (agent-scope stores, wait, barrier, one add)
+    if ((t & 63) == 0) {
+        const int slot = b * (FP_NT / 64) + (t >> 6);
+        __hip_atomic_store(&P.part_v[slot], best.v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&P.part_i[slot], best.i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (t < 64) {
+        int last = 0;
+        if (t == 0) last = (__hip_atomic_fetch_add(&P.part_i[MB_CNT], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nsel - 1) ? 1 : 0;
+        last = __builtin_amdgcn_readfirstlane(last);
+        if (last) {
+            MinIdx x; x.v = __builtin_inf(); x.i = INT_MAX;
+            const int npart = nsel * (FP_NT / 64);               // <= 128
+            if (t < npart) {
+                x.v = __hip_atomic_load(&P.part_v[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                x.i = __hip_atomic_load(&P.part_i[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            if (t + 64 < npart) {
+                MinIdx y;
+                y.v = __hip_atomic_load(&P.part_v[t + 64], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                y.i = __hip_atomic_load(&P.part_i[t + 64], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                x = mi_pick(x, y);
+            }
+            x = wave_min_idx(x);
+            if (t == 0) {
+                nxt->qn = (x.i == INT_MAX) ? -1 : x.i;           // the one field of the record this workgroup writes
+                __hip_atomic_store(&P.part_i[MB_CNT], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+    LPX_FS_W(7);
+    if (b == 0 && t == 0) {
+        P.basis[r] = q;                                          // basis[leaving] = entering, :110
+        if (iter < P.trace_cap) { P.trace[2 * iter] = r; P.trace[2 * iter + 1] = q; }
+        F.rring[lm] = r;
+        nxt->status = LPX_RUNNING; nxt->iter = iter + 1; nxt->r = r; nxt->q = q;
+        nxt->phase = cur.phase; nxt->fdf_count = cur.fdf_count; nxt->dual_iter = cur.dual_iter;
+        nxt->primal_count = primal_count + 1; nxt->forced_k = cur.forced_k; nxt->c0n = 0; nxt->qn_valid = 0;
+        nxt->pad[0] = cur.pad[0]; nxt->pad[1] = cur.pad[1]; nxt->pad[2] = seq + 1;
+        nxt->pad[3] = sweeps ? fp_rec(nbuf, 1, lm) : fp_rec(nbuf, n + 1, fp_slot(lm, n, 0, ring));
+    }
+    LPX_FS_W(8);
+    LPX_FS_END(n);
+}
+
+// The sweep: T_{k+1} = T_{k+1-D} with pending pivots k+1-D .. k applied, out of place, oldest first.  Each lane keeps the
+// D pivot-row pairs of its two columns in VGPRs; the factors of a wave's three rows are scalar loads.
+// NT: nontemporal loads and (mixmod permitting) stores -- the streaming forms; false: default policy throughout, for a pair of
+// buffers that lives in the Infinity Cache together (lpx_pivot_fused_c)
+template <bool NT, int D, int ROWS = fp_rows(D)>
+__device__ __forceinline__ void fused_sweep(const FusedParams& F, int ncw, int nunits, int mixmod)
+{
+    const SelParams& P = F.P;
+    const int t = threadIdx.x;
+    const int lm = F.lm;
+    constexpr int ring = 2 * D;
+    const DevState& cur = F.rec[lm & 1];
+    const int status = cur.status, buf = cur.pad[3] & 1, rnew = cur.r;     // rnew: the newest pending pivot's row
+    const int nsel = P.nblk;
+    const int R = P.shape ? P.shape[0] : P.R;
+    const size_t ld = (size_t)P.ld, fld = (size_t)P.R;
+    const double* __restrict__ src = buf ? F.T1 : P.T;
+    double* __restrict__ dst = buf ? P.T : F.T1;
+    const int lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int unit = ((int)blockIdx.x - nsel) * (FP_NT / 64) + wave;
+    if (unit >= nunits) return;
+    const int cw = unit % ncw, rb = unit / ncw;
+    const int col = cw * 128 + lane * 2;
+    if (col >= P.ld) return;
+    const int row0 = rb * ROWS;
+    if (row0 >= R) return;
+    bool hit = false;                                        // a pending pivot row in this wave's rows: the row-wise path
+#pragma unroll
+    for (int s = 0; s < D; ++s) hit |= (unsigned)((s == D - 1 ? rnew : F.rring[fp_slot(lm, D, s, ring)]) - row0) < (unsigned)ROWS;
+    if (status != LPX_RUNNING) return;                       // a run that is over leaves its pending pivots to lpx_pivot_flush
+    const double* sb = src + (size_t)row0 * ld + col;
+    double* db = dst + (size_t)row0 * ld + col;
+    if (row0 + ROWS <= R && !hit) {
+        double2 v[ROWS];
+        tile_load<ROWS, NT>(v, sb, ld);
+#pragma unroll
+        for (int s = 0; s < D; ++s) {
+            const int sl = fp_slot(lm, D, s, ring);
+            const double2 p = *reinterpret_cast<const double2*>(F.pring + (size_t)sl * ld + col);
+            tile_pivot<ROWS>(v, p, F.fring + (size_t)sl * fld + row0, 0);
+        }
+        tile_store<ROWS, NT, NT ? MIX_SWEEP : MIX_NONE>(db, ld, v, rb, mixmod);
+        return;
+    }
+#pragma unroll 1
+    for (int k = 0; k < ROWS; ++k) {
+        const int i = row0 + k;
+        if (i >= R) break;
+        double2 o = upd_load<NT>(sb + (size_t)k * ld);
+#pragma unroll 1
+        for (int s = 0; s < D; ++s) {
+            const int sl = fp_slot(lm, D, s, ring);
+            const double2 p = *reinterpret_cast<const double2*>(F.pring + (size_t)sl * ld + col);
+            const double f = F.fring[(size_t)sl * fld + i];
+            double2 u;
+            u.x = o.x - f * p.x;
+            u.y = o.y - f * p.y;
+            o = i == F.rring[sl] ? p : u;                    // row r_s: the normalised pivot row
+        }
+        upd_store<NT>(db + (size_t)k * ld, o);
+    }
+}
+
+// waves_per_eu(6): 80 VGPRs.  The sweep half alone needs 28 (D = 1) to 64 (D = 16); the select half sets the budget and spills
+// (code-object metadata): 2 VGPRs in every streaming form but D = 10 (14) and D = 15 (6), 2-4 in _c<1..8>, 8-14 in _c<9..16>
+// -- the defaults run lpx_pivot_fused<12> (2) at 403 MB and lpx_pivot_fused_c<4> (2) at 25 MB; _c<12> (14) serves 64-152 MB.
+// Without the hint the r03 kernel took 86 VGPRs = 5 waves per SIMD (8.46 k pivots/s against 8.57 k at 6).
+template <int D>
+__global__ __launch_bounds__(FP_NT) __attribute__((amdgpu_waves_per_eu(6))) void lpx_pivot_fused(FusedParams F, int ncw, int nunits, int mixmod)
+{
+    if ((int)blockIdx.x < F.P.nblk) {
+        if (D == 1) fused_select<4, 1, 1>(F, 1, true);
+        else fused_select<4, 1>(F, F.defer, true);           // == D; a run-time count keeps its loops rolled
+    } else fused_sweep<true, D>(F, ncw, nunits, mixmod);
+}
+template <int D>
+__global__ __launch_bounds__(FP_NT) __attribute__((amdgpu_waves_per_eu(6))) void lpx_pivot_fused_c(FusedParams F, int ncw, int nunits, int mixmod)
+{
+    if ((int)blockIdx.x < F.P.nblk) {
+        if (D == 1) fused_select<4, 1, 1>(F, 1, true);
+        else fused_select<4, 1>(F, F.defer, true);
+    } else fused_sweep<false, D>(F, ncw, nunits, mixmod);
+}
+// select-only launch: the L % d pending pivots stay where they are.  This form (ratios through the workgroup's slice of P.ws,
+// the column in trips of U x 256 rows) serves tableaux of more than SELP_LDS_ROWS rows; lpx_pivot_select below serves the others.
+template <int U, int SU>
+__global__ __launch_bounds__(FP_NT) void lpx_pivot_select_ws(FusedParams F)
+{
+    fused_select<U, SU>(F, F.lm % F.defer, false);
+}
+
+// The select-only launch shaped for latency.  It runs alone on the device, at most 32 workgroups, and moves no tableau: what it
+// costs is the length of its chain of dependent memory round trips, so the same loads of the same values and the same
+// arithmetic as fused_select<.., ..>(F, n, false) are issued in as few rounds as they allow:
+//   round 1  the record
+//   round 2  column q and the RHS column in passes of SELP_PASS_ROWS rows (SELP_U rows per lane; the headline's 4097 rows take
+//            three: a single pass of 9 rows per lane gathered slower, 6.6 against 5.4 us, and cost 237 VGPRs -- DESIGN.md 10),
+//            the pending pivots' scalars (one vector load per wave: lane k holds pq, r and the objective-row factor of pending
+//            pivot k, read back with v_readlane) and the factor columns of SELP_SB pending pivots at a time, whatever n is (past
+//            the newest: its factors again) -- the chain then runs in registers
+//   round 3  the pending pivot rows and the objective row of the workgroup's columns, in flight while the ratios are scanned
+//            out of LDS (dynamic, 8 R bytes: no store to global memory, drain and reload)
+//   round 4  once r is known: row r, the pivot element and the n factors of row r together
+//   round 5  the hand-off: one partial per workgroup (block_min_idx first: 8 waves x 32 workgroups would overflow the 128 entries)
+// 512 lanes at 2 waves per SIMD; the 3 + 3 + 8 x 3 doubles of round 2 fit 116 VGPRs.  The record bookkeeping and the
+// hand-off are copies of fused_select's: shared helpers moved instructions in all 32 sweep kernels.
+// (SELP_*: lpx_block.h, beside the other select kernels' launch constants)
+
+__device__ __forceinline__ double lane_f64(double x, int k)
+{
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), k), __builtin_amdgcn_readlane(__double2loint(x), k));
+}
+
+__global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F)
+{
+    extern __shared__ double sp_rat[];                       // the ratios of the test, one per live row
+    __shared__ double s_fs;
+    __shared__ double s_v[SELP_NT / 64];
+    __shared__ int s_i[SELP_NT / 64];
+    const SelParams& P = F.P;
+    const int t = threadIdx.x, b = blockIdx.x, lane = t & 63;
+    const int lm = F.lm, ring = 2 * F.defer;
+    const int n = lm % F.defer;
+    const int c = lm & 1;                                    // the current record comes with the launch: see fused_select
+    LPX_FS_BEGIN(true)
+    // the live shape beside the record, before the kernel's first store: one round for both
+    int R = P.R, C = P.C;
+    if (P.shape) { R = P.shape[0]; C = P.shape[1]; }
+    const DevState cur = F.rec[c];
+    DevState* nxt = F.rec + (c ^ 1);
+    const int status = cur.status, seq = cur.pad[2], buf = cur.pad[3] & 1;
+    const int nsel = P.nblk;
+    if (b == 0 && t == 0) *P.st = cur;                        // the host's copy: one launch behind
+    LPX_FS_W(0);
+    if (status != LPX_RUNNING) {
+        if (b == 0 && t == 0) { DevState x = cur; x.pad[2] = seq + 1; *nxt = x; }
+        return;
+    }
+    const size_t ld = (size_t)P.ld, fld = (size_t)P.R;
+    const double* __restrict__ src = buf ? F.T1 : P.T;
+    double* __restrict__ prown = F.pring + (size_t)lm * ld;
+    double* __restrict__ facn = F.fring + (size_t)lm * fld;
+    const double* __restrict__ rhsc = c ? F.rhs1 : P.rhsbuf;
+    double* __restrict__ rhsn = c ? P.rhsbuf : F.rhs1;
+    const int m = R - 1;
+    const int iter = cur.iter, primal_count = cur.primal_count;
+    const int q = cur.qn;
+    int final_status = LPX_RUNNING, r = -1;
+    // loop head, Models/PrimalSimplex.cs:95-106
+    if (primal_count >= P.max_iter) final_status = LPX_ITER_LIMIT;
+    else if (q < 0) final_status = LPX_OPTIMAL;
+    // lane k of every wave: pending pivot k (0 = oldest; lanes past the newest repeat it).  n = 0 (the prologue's launch) reads
+    // no slot: its own is the only one it could name
+    const int ks = min(lane, max(n - 1, 0));
+    const size_t kslot = (size_t)fp_slot(lm, n, ks, ring);
+    auto pslot = [&](int s) { return (size_t)fp_slot(lm, n, min(s, n - 1), ring); };
+    int rsv = -1;                                            // pending pivot `ks`: its row as the ring has it
+    auto prs = [&](int s) { return s == n - 1 ? cur.r : __builtin_amdgcn_readlane(rsv, s); };     // the newest: the record's
+    const double* __restrict__ orow = src + (size_t)m * ld;
+    const int per = (C + nsel - 1) / nsel;
+    const int j0 = b * per, j1 = min(C, j0 + per);
+    double fs = 0.0;
+    double pqv = 0.0, pfmv = 0.0;                            // T_s[r_s,q] / pivot and T_s[m,q_s] of pending pivot `ks`
+    double ov0 = 0.0, pc0[SELP_PMAX];                        // objective row and pending pivot rows at this lane's first column
+#pragma unroll
+    for (int k = 0; k < SELP_PMAX; ++k) pc0[k] = 0.0;
+    if (final_status == LPX_RUNNING) {
+        // T_{k+1}[i,q] and T_{k+1}[i,C-1] as the sweep stores them: the column through every pending pivot (row r_s: the
+        // normalised pivot row), the RHS column kept current in rhsc up to the newest pending pivot, which is applied here
+        const int sn = fp_slot(lm, n, n - 1, ring);
+        const int rl = n ? cur.r : -1;                       // the newest pending pivot is the record's
+        const double prhs = n ? F.pring[(size_t)sn * ld + (C - 1)] : 0.0;
+        if (n > 0) {
+            pqv = F.pring[kslot * ld + q];
+            pfmv = F.fring[kslot * fld + m];
+            rsv = F.rring[kslot];
+        }
+        for (int i0 = 0; i0 < R; i0 += SELP_PASS_ROWS) {
+            double v[SELP_U], h[SELP_U], fl[SELP_U];
+#pragma unroll
+            for (int u = 0; u < SELP_U; ++u) {
+                const int i = min(R - 1, i0 + u * SELP_NT + t);  // clamped, not guarded: a guarded load waits for its own branch
+                v[u] = src[(size_t)i * ld + q]; h[u] = rhsc[i]; fl[u] = 0.0;
+            }
+            LPX_FS_TRIP(i0 / SELP_PASS_ROWS);
+            // oldest first, SELP_SB pivots' factors in flight together (past the newest: its factors again, unused); the newest
+            // pivot's factors are kept for the RHS correction
+            for (int s0 = 0; s0 < n; s0 += SELP_SB) {
+                double f[SELP_SB][SELP_U];
+#pragma unroll
+                for (int k = 0; k < SELP_SB; ++k) {
+                    const double* __restrict__ fac = F.fring + pslot(s0 + k) * fld;
+#pragma unroll
+                    for (int u = 0; u < SELP_U; ++u) f[k][u] = fac[min(R - 1, i0 + u * SELP_NT + t)];
+                }
+#pragma unroll
+                for (int k = 0; k < SELP_SB; ++k) {
+                    if (s0 + k < n) {
+                        const double pq = lane_f64(pqv, s0 + k);
+                        const int rs = prs(s0 + k);
+#pragma unroll
+                        for (int u = 0; u < SELP_U; ++u) {
+                            const int i = min(R - 1, i0 + u * SELP_NT + t);
+                            fl[u] = f[k][u];
+                            const double nv = v[u] - fl[u] * pq;     // mul, then sub: contraction is off
+                            v[u] = i == rs ? pq : nv;
+                        }
+                    }
+                }
+            }
+            LPX_FS_W(2);
+#pragma unroll
+            for (int u = 0; u < SELP_U; ++u) {
+                const int i = i0 + u * SELP_NT + t;
+                if (i < R) {
+                    const double dn = v[u];
+                    const double nm = n == 0 ? h[u] : (i == rl ? prhs : h[u] - fl[u] * prhs);
+                    sp_rat[i] = dn > P.eps ? nm / dn : __builtin_inf();  // ChooseLeaving's ratio, :229-241
+                    if (b == 0) { facn[i] = dn; rhsn[i] = nm; }          // factors of pivot k+1, numerators of the test after it
+                    if (i == m) s_fs = dn;                               // T_{k+1}[m,q]: row m belongs to exactly one lane
+                }
+            }
+            LPX_FS(3);
+        }
+        // the row phase's operands that do not depend on r, in flight behind the scan
+        {
+            const int jc = min(j0 + t, C - 1);
+            ov0 = orow[jc];
+            if (n > 0) {
+#pragma unroll
+                for (int k = 0; k < SELP_SB; ++k) pc0[k] = F.pring[pslot(k) * ld + jc];
+            }
+            if (n > SELP_SB) {
+#pragma unroll
+                for (int k = SELP_SB; k < SELP_PMAX; ++k) pc0[k] = F.pring[pslot(k) * ld + jc];
+            }
+        }
+        __syncthreads();                                     // the ratios are complete
+        LPX_FS(3);
+        fs = s_fs;
+        r = block_hysteresis_segments<SELP_NT / 64>(m, P.tol_primal, CompactRatio{sp_rat});
+        LPX_FS(4);
+        if (r < 0) final_status = LPX_UNBOUNDED;
+    }
+    if (final_status != LPX_RUNNING) {
+        if (b == 0 && t == 0) {
+            DevState x = cur;
+            x.status = final_status; x.r = -1; x.q = -1; x.qn = -1; x.pad[2] = seq + 1;
+            x.pad[3] = fp_rec(buf, n, fp_slot(lm, n, 0, ring));
+            *nxt = x;
+        }
+        return;
+    }
+
+    ScanRule rule; rule.forced = 0; rule.eps = P.eps; rule.thresh = P.fthresh; rule.C = C; rule.c0 = 0;
+    const double* __restrict__ trow = src + (size_t)r * ld;
+    // row r's factors of the pending pivots (lane k: pivot k) and the pivot element T_{k+1}[r,q], the column's own chain
+    double pfrv = 0.0;
+    if (n > 0) pfrv = F.fring[kslot * fld + r];
+    double piv = trow[q];
+    double tr0 = trow[min(j0 + t, C - 1)];
+    for (int s = 0; s < n; ++s) {
+        const double pq = lane_f64(pqv, s);
+        const double nv = piv - lane_f64(pfrv, s) * pq;
+        piv = r == prs(s) ? pq : nv;
+    }
+    LPX_FS_W(5);
+    MinIdx best; rule_init(rule, best);
+    for (int jb = j0; jb < j1; jb += SELP_NT) {
+        const int j = jb + t, jc = min(j, C - 1);
+        double tr = tr0, ov = ov0, pc[SELP_PMAX];
+#pragma unroll
+        for (int k = 0; k < SELP_PMAX; ++k) pc[k] = pc0[k];
+        if (jb != j0) {                                      // more columns than lanes: the later ones are loaded here
+            tr = trow[jc]; ov = orow[jc];
+            if (n > 0) {
+#pragma unroll
+                for (int k = 0; k < SELP_SB; ++k) pc[k] = F.pring[pslot(k) * ld + jc];
+            }
+            if (n > SELP_SB) {
+#pragma unroll
+                for (int k = SELP_SB; k < SELP_PMAX; ++k) pc[k] = F.pring[pslot(k) * ld + jc];
+            }
+        }
+        // -> T_{k+1}[r,j], T_{k+1}[m,j] (m is never a pivot row)
+#pragma unroll
+        for (int k = 0; k < SELP_PMAX; ++k) {
+            if (k < n) {
+                const double nt = tr - lane_f64(pfrv, k) * pc[k];
+                tr = r == prs(k) ? pc[k] : nt;
+                ov = ov - lane_f64(pfmv, k) * pc[k];
+            }
+        }
+        if (j < j1) {
+            const double p = tr / piv;                           // true division, :250
+            prown[j] = p;
+            const double u = ov - fs * p;                        // what the sweep of pivot k+1 will store at T[m,j]
+            rule_feed(rule, best, j, u);
+        }
+    }
+    LPX_FS_W(6);
+    // one partial per workgroup, then the last-workgroup reduction of fused_select (agent-scope stores, wait, one add)
+    best = block_min_idx<SELP_NT>(best, s_v, s_i);
+    if (t < 64) {
+        if (t == 0) {
+            __hip_atomic_store(&P.part_v[b], best.v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&P.part_i[b], best.i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        int last = 0;
+        if (t == 0) last = (__hip_atomic_fetch_add(&P.part_i[MB_CNT], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nsel - 1) ? 1 : 0;
+        last = __builtin_amdgcn_readfirstlane(last);
+        if (last) {
+            MinIdx x; x.v = __builtin_inf(); x.i = INT_MAX;
+            if (t < nsel) {                                      // nsel <= MB_MAXB = 64 partials
+                x.v = __hip_atomic_load(&P.part_v[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                x.i = __hip_atomic_load(&P.part_i[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            x = wave_min_idx(x);
+            if (t == 0) {
+                nxt->qn = (x.i == INT_MAX) ? -1 : x.i;           // the one field of the record this workgroup writes
+                __hip_atomic_store(&P.part_i[MB_CNT], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+    LPX_FS_W(7);
+    if (b == 0 && t == 0) {
+        P.basis[r] = q;                                          // basis[leaving] = entering, :110
+        if (iter < P.trace_cap) { P.trace[2 * iter] = r; P.trace[2 * iter + 1] = q; }
+        F.rring[lm] = r;
+        nxt->status = LPX_RUNNING; nxt->iter = iter + 1; nxt->r = r; nxt->q = q;
+        nxt->phase = cur.phase; nxt->fdf_count = cur.fdf_count; nxt->dual_iter = cur.dual_iter;
+        nxt->primal_count = primal_count + 1; nxt->forced_k = cur.forced_k; nxt->c0n = 0; nxt->qn_valid = 0;
+        nxt->pad[0] = cur.pad[0]; nxt->pad[1] = cur.pad[1]; nxt->pad[2] = seq + 1;
+        nxt->pad[3] = fp_rec(buf, n + 1, fp_slot(lm, n, 0, ring));
+    }
+    LPX_FS_W(8);
+    LPX_FS_END(n);
+}
+
+// End of a run: the n pivots still pending (record: buffer, count, oldest slot) applied to the stored tableau, written to
+// buffer 0 (in place when it is already there: every element is read and written by one lane).
+__global__ __launch_bounds__(256) void lpx_pivot_flush(FusedParams F, int buf, int n, int slot0)
+{
+    const SelParams& P = F.P;
+    const int R = P.shape ? P.shape[0] : P.R;
+    const int i = blockIdx.y;
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (i >= R || j >= P.ld) return;
+    const size_t ld = (size_t)P.ld, fld = (size_t)P.R;
+    const int ring = 2 * F.defer;
+    const double* src = buf ? F.T1 : P.T;
+    double v = src[(size_t)i * ld + j];
+    for (int s = 0; s < n; ++s) {
+        const int sl = slot0 + s < ring ? slot0 + s : slot0 + s - ring;
+        const double pc = F.pring[(size_t)sl * ld + j];
+        const double nv = v - F.fring[(size_t)sl * fld + i] * pc;
+        v = i == F.rring[sl] ? pc : nv;
+    }
+    P.T[(size_t)i * ld + j] = v;
+}
+
+// Cache policy of the fused launch.  Two buffers share the Infinity Cache, so the default policy only pays while BOTH fit with
+// room to spare; beyond that the streaming mix wins at every size, well below the in-place kernels' own crossover
+// (tools/probe_fused_mid.py, us per pivot, two-launch in place / fused default policy / fused streaming mix):
+//    57 MB 24.1 / 21.4 / 22.8     101 MB 37.8 / 30.5 / 34.3     157 MB 53.5 / 49.2 / 49.1     190 MB 64.5 / 65.5 / 58.3
+//   227 MB 73.1 / 77.2 / 69.0     266 MB 86.1 / 91.1 / 80.3     308 MB 102.7 / 92.4 / 92.2    403 MB 128.3 / 120.0 / 120.2
+int fused_policy(int ld, int R) { return policy_for(tableau_bytes(ld, R), FUSED_CACHED_BYTES); }
+
+hipError_t launch_fused_init(const FusedParams& f, hipStream_t s)
+{
+    hipLaunchKernelGGL(lpx_fused_init, dim3(1), dim3(SEL_NT), 0, s, f);
+    return hipGetLastError();
+}
+
+using FusedKernel = void (*)(FusedParams, int, int, int);
+template <int... Ds> struct FusedTable {
+    static constexpr FusedKernel nt[] = { lpx_pivot_fused<Ds>... };
+    static constexpr FusedKernel c[] = { lpx_pivot_fused_c<Ds>... };
+};
+using FusedKernels = FusedTable<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>;
+static_assert(sizeof(FusedKernels::nt) / sizeof(FusedKernel) == FP_DMAX, "one sweep kernel per depth");
+
+int pivot_defer_max() { return FP_DMAX; }
+
+static hipError_t launch_pivot_select_ws(const FusedParams& f, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    return launch_k(lpx_pivot_select_ws<6, 4>, dim3(f.P.nblk), dim3(FP_NT), 0, s, e0, e1, f);
+}
+
+hipError_t launch_pivot_fused(const FusedParams& f0, long long L, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    FusedParams f = f0;
+    const int d = f.defer;
+    if (d < 1 || d > FP_DMAX) return hipErrorInvalidValue;
+    f.lm = (int)(L % (2 * d)); f.par = f.lm & 1;
+    const bool sweep = L > 0 && L % d == 0;
+    const int ld = f.P.ld, R = f.P.R;
+    if (!sweep) {
+        // Ratios in LDS while the handle's rows fit the cap, through the workspace beyond it -- and at small sizes: measured on
+        // MI355X with one pass of 9 rows per lane, the LDS form ran the 403 MB headline 5 % faster (select-only launch 24.3 ->
+        // 22.3 us) and config 2's 25 MB streaming loop (d = 4, 1 to 3 pivots pending, 1025 rows) 22 % slower (82.4 k -> 64.0 k
+        // pivots/s: it fetches SELP_SB factor columns whatever n is).  64 MB is not a measured crossover: nothing between 25 and
+        // 403 MB was run, so the switch sits where the depth default changes (PIVOT_DEFER_LARGE_BYTES, lpx_tableau.cpp) and up to
+        // 64 MB a handle runs exactly what it ran before.  The form pays by its pending count, not by size: at d = 2 (one pivot
+        // pending) the stamped launch on the 403 MB LP was 14 % longer than the old form's, so a handle above 64 MB run with
+        // LPX_PIVOT_DEFER = 2 to 4 is probably slower than it was; the default there is 12.
+        if (R <= SELP_LDS_ROWS && tableau_bytes(ld, R) > ((size_t)SELP_MIN_MB << 20)) return launch_k(lpx_pivot_select, dim3(f.P.nblk), dim3(SELP_NT), sizeof(double) * (size_t)R, s, e0, e1, f);
+        return launch_pivot_select_ws(f, s, e0, e1);
+    }
+    const int rows = fp_rows(d);
+    const int ncw = (ld + 127) / 128, nunits = ncw * ((R + rows - 1) / rows);
+    const int nblocks = f.P.nblk + (nunits + (FP_NT / 64) - 1) / (FP_NT / 64);
+    const int pol = fused_policy(ld, R);
+    int mixmod = pol == 2 ? mixmod_for(tableau_bytes(ld, R)) : 0;            // 0: every store nontemporal
+    // the stored-through row is the last of every mixmod-th block: at `rows` per block the block period shrinks in proportion so
+    // that about the same share of BLOCKS keeps a row in the cache.  mixmod = 1 (the 403 MB headline) stays 1: one row in eight
+    // instead of one in three goes through the cache at eight rows per block -- the sweep's PMC traffic stays 1.029x of
+    // 16 R C; the other share was not measured
+    if (mixmod > 1) mixmod = std::max(1, mixmod * UPDS_ROWS / rows);
+    const FusedKernel kern = pol == 0 ? FusedKernels::c[d - 1] : FusedKernels::nt[d - 1];   // both buffers in the Infinity Cache: default policy
+    return launch_k(kern, dim3(nblocks), dim3(FP_NT), 0, s, e0, e1, f, ncw, nunits, mixmod);
+}
+
+hipError_t launch_pivot_flush(const FusedParams& f, int buf, int n, int slot0, hipStream_t s)
+{
+    const int R = f.P.R, ld = f.P.ld;
+    hipLaunchKernelGGL(lpx_pivot_flush, dim3((ld + 255) / 256, R), dim3(256), 0, s, f, buf, n, slot0);
+    return hipGetLastError();
+}
+
+// once per process (ensure_device): the dynamic LDS lpx_pivot_select may ask for
+hipError_t pivot_fused_init()
+{
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(lpx_pivot_select), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * SELP_LDS_ROWS);
+}
+#ifdef LPX_STAMPS
+hipError_t pivot_fused_stamps(unsigned long long* acc, int clear) { return stamps_take(acc, clear); }
+#endif
+
+}  // namespace lpx

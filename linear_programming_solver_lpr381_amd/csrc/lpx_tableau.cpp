@@ -1,6 +1,6 @@
 // lpx_tableau.cpp -- device-resident tableau handle (lifecycle, transfers, snapshot) and the host side of the simplex loops:
 // single-LP loops, resident and group runs (C ABI of include/lpx.h).  The bounded-variable family is in lpx_tableau_bounded.cpp,
-// node assembly and the parent store in lpx_tableau_nodes.cpp.  Host code only: kernels live in lpx_kernels.hip.
+// node assembly and the parent store in lpx_tableau_nodes.cpp.  Host code only: kernels live in lpx_kernels.hip (two-launch paths), lpx_pivot_fused.hip and lpx_group_fused.hip.
 #include "lpx_handle.h"
 
 #include <cstdlib>
@@ -913,7 +913,7 @@ struct FusedGroupBuf {
     DevState* hs = nullptr;                                  // pinned: initial states in, latest records out
     DevState* ds = nullptr;                                  // device copy of the initial states
     int* live_d = nullptr; int* live_h = nullptr;            // live list (two halves: launches of window w read half w & 1)
-    int* comp_d = nullptr; int* comp_h = nullptr;            // device-side compaction record (lpx_kernels.hip FG_COMP_*) and its pinned staging
+    int* comp_d = nullptr; int* comp_h = nullptr;            // device-side compaction record (lpx_group_fused.hip FG_COMP_*) and its pinned staging
     int* fresh_d = nullptr; int* fresh_h = nullptr;
     int* cur_h = nullptr;                                    // pinned: index of every node's latest record
     int cap = 0;

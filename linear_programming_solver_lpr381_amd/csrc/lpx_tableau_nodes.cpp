@@ -1,5 +1,5 @@
 // lpx_tableau_nodes.cpp -- host side of node and child assembly on tableau handles, the parent store with its chunk cache, and
-// the solution read-backs (C ABI of include/lpx.h).  Kernels: lpx_kernels.hip.
+// the solution read-backs (C ABI of include/lpx.h).  Kernels: lpx_nodes.hip.
 #include "lpx_handle.h"
 
 #include <cstdlib>

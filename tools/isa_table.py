@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
-"""Compare the pivot-update kernels of two device assemblies of csrc/lpx_kernels.hip, kernel by kernel.
+"""Compare the pivot-update kernels of two builds of the csrc/*.hip kernel files, kernel by kernel.
 
     hipcc -O3 -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 --cuda-device-only -S lpx_kernels.hip -o X.s
     python tools/isa_table.py PARENT.s BRANCH.s > profiles/rNN_tile_isa.md
+    python tools/isa_table.py --parent A.s [B.s ...] --branch C.s [D.s ...] > profiles/rNN_tile_isa.md
     python tools/isa_table.py --diff PARENT.s BRANCH.s > profiles/rNN_tile_isa_diffs.txt
 
+Each side is the device assembly of one or several files (one .s per .hip file); a kernel is found by name, whichever file
+holds it.  --all: every kernel of the assemblies instead of the pivot-update kernels of the KERNELS pattern.
 --diff: instead of the table, a unified diff of the two instruction streams (register numbers and labels blanked) of every
-kernel whose streams are not the same text.
+kernel whose streams are not the same text.  "The same text" leaves out the function number of .LBB<f>_<n> labels, which
+counts the functions in front of the kernel in its file: a kernel that changed file or place keeps its text.
 
 Per kernel: registers, scratch, LDS and occupancy from the code-object metadata, a histogram of the mnemonics that matter to a
 streaming FP64 kernel (loads and stores split by `nt`), and whether the two instruction streams are the same text, the same
@@ -61,7 +65,18 @@ def normalise(line):
     return re.sub(r"\.LBB\d+_\d+", ".L", line)
 
 
-def parse(path):
+def parse_all(paths, every):
+    out = {}
+    for path in paths:
+        one = parse(path, every)
+        dup = set(out) & set(one)
+        if dup:
+            sys.exit("kernel in two files of one side: " + ", ".join(sorted(dup)))
+        out.update(one)
+    return out
+
+
+def parse(path, every=False):
     text = open(path).read().split("\n")
     meta, rec = {}, None
     for ln in text[text.index("amdhsa.kernels:"):]:     # the metadata at the end of the file: one "  - " record per kernel
@@ -78,7 +93,7 @@ def parse(path):
     out = {}
     for mangled, rec in meta.items():
         nice = names[mangled]
-        if not KERNELS.search(nice):
+        if not every and not KERNELS.search(nice):
             continue
         start = next(i for i, ln in enumerate(text) if ln.startswith(mangled + ":"))
         body, occ = [], None
@@ -92,7 +107,7 @@ def parse(path):
                         break
                 break
             if s and not s.startswith(".") and not s.endswith(":"):
-                body.append(s)
+                body.append(re.sub(r"\.LBB\d+_", ".LBB_", s))      # the function number: the kernel's place in its file
         short = re.sub(r"^lpx::", "", nice.split("(")[0])
         out[short] = {"meta": rec, "occ": occ, "body": body, "hist": Counter(filter(None, map(classify, body)))}
     return out
@@ -104,10 +119,18 @@ def order(name):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a != "--diff"]
-    if len(args) != 2:
+    sides, cur = {"pos": [], "--parent": [], "--branch": []}, "pos"
+    for a in sys.argv[1:]:
+        if a in ("--parent", "--branch"):
+            cur = a
+        elif a not in ("--diff", "--all"):
+            sides[cur].append(a)
+    if len(sides["pos"]) == 2 and not sides["--parent"] and not sides["--branch"]:
+        sides["--parent"], sides["--branch"] = sides["pos"][:1], sides["pos"][1:]
+    elif sides["pos"] or not sides["--parent"] or not sides["--branch"]:
         sys.exit(__doc__)
-    A, B = parse(args[0]), parse(args[1])
+    every = "--all" in sys.argv[1:]
+    A, B = parse_all(sides["--parent"], every), parse_all(sides["--branch"], every)
     if "--diff" in sys.argv[1:]:
         for k in sorted(set(A) & set(B), key=order):
             a, b = [normalise(x) for x in A[k]["body"]], [normalise(x) for x in B[k]["body"]]
