@@ -34,6 +34,8 @@ enum {
     LPX_INFEASIBLE = 2,   /* "INFEASIBLE" Models/DualSimplex.cs:92-96 */
     LPX_ITER_LIMIT = 3,   /* exception "Iteration limit exceeded." Models/PrimalSimplex.cs:95-96 */
     LPX_RUNNING    = 4,   /* internal: loop not finished */
+    LPX_CUTOFF     = 5,   /* "CUTOFF": lpx_bounded_dual_run3 / _node2 with LPX_BDUAL_CUTOFF stopped at T[m,Cm] <= cutoff; no other
+                             entry point returns it */
     /* outcomes of the cutting-plane consumers (lpx_result.status for "Cutting Plane" / "Revised Cutting Plane";
        LPX_CUT_INTEGER / LPX_CUT_INCOMPLETE also for "GMI Cutting Plane", lpx_solve_cuts) */
     LPX_CUT_INTEGER     = 0,  /* "Status: OPTIMAL INTEGER" Models/CuttingPlane.cs:91-104, CuttingPlaneRevised.cs:49-57 */
@@ -843,6 +845,69 @@ int  lpx_solve_bnb_bounded(const lpx_problem* p, const double* lower /* [n] or N
                            const uint8_t* is_int /* [n] or NULL = all */, const lpx_solve_opts* o, int64_t max_nodes /* 0 = none */,
                            lpx_result* out, lpx_bnb_bounded_info* info /* or NULL */);
 void lpx_bnb_bounded_info_free(lpx_bnb_bounded_info* info);
+
+/* ---- long-step ratio test, objective cutoff and dual start (not in the reference; csrc/lpx_bounded_long.hip,
+ * csrc/host/bounded.cpp, csrc/host/bnb_bounded.cpp) --
+ * lpx_bounded_dual_run3(t, o, flags, cutoff, cb, user, st): lpx_bounded_dual_run2 with two more flags.  flags with neither
+ * LPX_BDUAL_LONG_STEP nor LPX_BDUAL_CUTOFF is lpx_bounded_dual_run2(flags) bit for bit (same kernels, same cached graphs).  All
+ * arithmetic is IEEE double, no FMA, true division.  The steps are those of lpx_bounded_dual_run, with these changes:
+ *   1b. (LPX_BDUAL_CUTOFF only) After the iteration-limit test of step 1 and before the leaving row: T[m,Cm] <= cutoff is
+ *       LPX_CUTOFF.  Nothing is touched and no event is recorded.  In the dual loop T[m,Cm] only falls, so LPX_OPTIMAL implies
+ *       T[m,Cm] > cutoff.  cutoff = -inf never fires; NaN is LPX_EINVAL.  Without the flag the value is not read.
+ *   3.  The complement of a kind-1 row is applied before step 4, as in lpx_bounded_dual_run; every pass below works on the
+ *       complemented row (this decides the bits of T[r,Cm]).
+ *   4.  (LPX_BDUAL_LONG_STEP only) The ratios rho[j] are formed ONCE, exactly as in step 4 of lpx_bounded_dual_run (+inf = the
+ *       column does not take part; with LPX_BDUAL_SKIP_FIXED a column takes part iff a < -eps and ub[j] > 0).  Then repeat:
+ *         4.1 q = the last column accepted by the sequential scan rho[j] < best - ratio_tol, j ascending, best from +inf.
+ *         4.2 No q: LPX_INFEASIBLE.  Passes already made stay applied and stay in the trace (the tableau is still a valid
+ *             representation, with row r below zero and no column left that can raise it).
+ *         4.3 If ub[q] < +inf: nb = T[r,Cm] - ub[q] * T[r,q] (one multiply, one subtract).
+ *         4.4 If ub[q] < +inf and nb < -eps, column q PASSES -- the BOUND FLIP of lpx_bounded_run on column q: for every row i
+ *             in [0, R), the objective row included, T[i,Cm] = T[i,Cm] - ub[q] * T[i,q] (one multiply, one subtract), then
+ *             T[i,q] = -T[i,q]; flip[q] ^= 1; the contiguous RHS copy is kept current.  Trace entry (-1, q); the pass counts as
+ *             an event.  rho[q] = +inf, back to 4.1.
+ *         4.5 Otherwise q enters: step 5 as in lpx_bounded_dual_run.
+ *       A column passes at most once per pivot (at most Cm passes per launch).  The iteration limit is tested in step 1 only, so
+ *       a run ends with at most max_iter + Cm events.  Trace entries beyond the trace capacity are dropped, as elsewhere.
+ * lpx_bounded_counts returns {kind 0, kind 1, passes}; lpx_stats.pivots = kind 0 + kind 1; the per-pivot callback sees the
+ * passes with the trace's encoding.  The result depends on nothing but the tableau, basis, ub, flip, the options, flags and
+ * cutoff: not on the batch length, on graph replay, on the callback or on launch geometry.  The cutoff is not part of what keys
+ * the cached graph of a loop: two runs with equal options and different cutoffs each obey their own.  Any m and Cm, with the
+ * LDS-or-scratch rule of lpx_bounded_dual_run at 4096.  The cached graphs of all flag sets on one handle are kept apart.
+ * LPX_EINVAL before any device check: a flag bit outside the three ("unknown flag"), a NaN cutoff with LPX_BDUAL_CUTOFF, a NULL
+ * handle, and the argument errors of lpx_bounded_dual_run.
+ *
+ * lpx_bounded_node2(t, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out): lpx_bounded_node with the loop's flags and
+ * cutoff passed through to lpx_bounded_dual_run3.  flags = LPX_BDUAL_SKIP_FIXED is lpx_bounded_node bit for bit.  out->status may
+ * be LPX_CUTOFF; the pick is then {-1, 0, 0.0, T[m,Cm] as it stands}.  The record is unchanged: passes = events - kind0 - kind1.
+ *
+ * lpx_solve_bnb_bounded2(p, lower, upper, is_int, o, max_nodes, search_flags, out, info): lpx_solve_bnb_bounded whose nodes are
+ * lpx_bounded_node2 calls with flags = LPX_BDUAL_SKIP_FIXED | search_flags; search_flags is a subset of {LPX_BDUAL_LONG_STEP,
+ * LPX_BDUAL_CUTOFF}, anything else is LPX_EINVAL.  search_flags = 0 is lpx_solve_bnb_bounded with a bit-equal node log.  With
+ * LPX_BDUAL_CUTOFF every node call carries cutoff = best + 1e-6 (the driver's own addition; -inf before the first incumbent).  A
+ * node that ends LPX_CUTOFF is counted in pruned_bound and its log record carries status LPX_CUTOFF and z as it stood.
+ *
+ * lpx_solve_bounded_dual(p, lower, upper, flags, o, out, info): the dual start -- the bounded dual loop as the root solver of the
+ * models lpx_solve_bounded refuses.  Preparation is that of lpx_solve_bounded (same validation, same messages, same lower shift)
+ * with two differences: a >= row is negated into a <= row (every coefficient and the RHS negated, which is exact), and a negative
+ * shifted RHS is accepted.  Precheck, on the host before any device check: a variable whose internal objective-row entry (-c_j
+ * for Max, c_j for Min) is below -1e-9 and whose upper bound is +inf cannot be made dual feasible -- LPX_EINVAL with a message
+ * naming the first such variable.  Solve: slack basis, lpx_tableau_set_bounds, lpx_tableau_dualize(1e-9),
+ * lpx_bounded_dual_run3(flags, cutoff unused: LPX_BDUAL_CUTOFF in flags is LPX_EINVAL here, as is any unknown bit).
+ * out and info are laid out as lpx_solve_bounded's; aux = {kind-0 pivots, kind-1 pivots, passes, constant c.l}; the summary ends
+ * with a line of the dualize flips and the passes.  Status is LPX_OPTIMAL or LPX_INFEASIBLE (x and optimal_value then describe the
+ * tableau as it stands); LPX_ITER_LIMIT is the return value, as in lpx_solve_bounded. */
+#define LPX_BDUAL_LONG_STEP 2
+#define LPX_BDUAL_CUTOFF 4
+int lpx_bounded_dual_run3(lpx_tableau* t, const lpx_run_opts* o, int flags, double cutoff, lpx_pivot_cb cb, void* user, lpx_stats* st);
+int lpx_bounded_node2(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const lpx_run_opts* o,
+                      int flags, double cutoff, int nint, const uint8_t* is_int /* [nint] or NULL = all */, double tol,
+                      lpx_node_record* out);
+int lpx_solve_bnb_bounded2(const lpx_problem* p, const double* lower /* [n] or NULL = 0 */, const double* upper /* [n] */,
+                           const uint8_t* is_int /* [n] or NULL = all */, const lpx_solve_opts* o, int64_t max_nodes /* 0 = none */,
+                           int search_flags, lpx_result* out, lpx_bnb_bounded_info* info /* or NULL */);
+int lpx_solve_bounded_dual(const lpx_problem* p, const double* lower /* [n] or NULL = 0 */, const double* upper /* [n] or NULL = +inf */,
+                           int flags, const lpx_solve_opts* o, lpx_result* out, lpx_bounded_info* info /* or NULL */);
 
 #ifdef __cplusplus
 }

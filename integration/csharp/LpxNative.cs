@@ -129,6 +129,7 @@ namespace Linear_Programming_Solver.Native
         const string Lib = "lpx";                // liblpx.so (Linux) next to the executable / on LD_LIBRARY_PATH
 
         public const int OPTIMAL = 0, UNBOUNDED = 1, INFEASIBLE = 2, ITER_LIMIT = 3;
+        public const int CUTOFF = 5;             // "CUTOFF": lpx_bounded_dual_run3 / lpx_bounded_node2 with LPX_BDUAL_CUTOFF only
         public const int E_GE_PRESENT = -10, E_NEG_RHS = -11, E_REVISED_PRECOND = -12, E_SINGULAR = -13,
                          E_KNAP_SHAPE = -14, E_UNKNOWN_ALGO = -15, E_PARSE = -16;
 
@@ -277,6 +278,20 @@ namespace Linear_Programming_Solver.Native
                                                        long max_nodes, out LpxResult result, out LpxBnbBoundedInfo info);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern void lpx_bnb_bounded_info_free(ref LpxBnbBoundedInfo info);
+        // long-step ratio test, objective cutoff and dual start (flags of lpx_bounded_dual_run3; search_flags of lpx_solve_bnb_bounded2)
+        public const int LPX_BDUAL_LONG_STEP = 2;
+        public const int LPX_BDUAL_CUTOFF = 4;
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_bounded_dual_run3(IntPtr t, IntPtr opts, int flags, double cutoff, LpxPivotCb cb, IntPtr user, out LpxStats st);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_bounded_node2(IntPtr t, int K, int* cols, double* lower, double* upper, IntPtr opts, int flags, double cutoff,
+                                                   int nint, byte* is_int, double tol, out LpxNodeRecord record);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_bnb_bounded2(ref LpxProblem p, double* lower, double* upper, byte* is_int, ref LpxSolveOpts o,
+                                                        long max_nodes, int search_flags, out LpxResult result, out LpxBnbBoundedInfo info);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_bounded_dual(ref LpxProblem p, double* lower, double* upper, int flags, ref LpxSolveOpts o,
+                                                        out LpxResult result, out LpxBoundedInfo info);
 
         public static string LastError()
         {

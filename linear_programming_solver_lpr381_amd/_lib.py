@@ -13,15 +13,16 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LPX_LIB_PATH") or os.path.join(_PKG, "liblpx.so")
 
 # status / error codes (include/lpx.h)
-OPTIMAL, UNBOUNDED, INFEASIBLE, ITER_LIMIT, RUNNING = 0, 1, 2, 3, 4
+OPTIMAL, UNBOUNDED, INFEASIBLE, ITER_LIMIT, RUNNING, CUTOFF = 0, 1, 2, 3, 4, 5
 CUT_INTEGER, CUT_INCOMPLETE, CUT_ERROR, CUT_NOT_OPTIMAL = 0, 10, 11, 12
 EINVAL, EDEVICE, ENOMEM = -1, -2, -3
 BDUAL_SKIP_FIXED = 1        # LPX_BDUAL_SKIP_FIXED (lpx_bounded_dual_run2)
+BDUAL_LONG_STEP, BDUAL_CUTOFF = 2, 4        # LPX_BDUAL_LONG_STEP, LPX_BDUAL_CUTOFF (lpx_bounded_dual_run3)
 E_GE_PRESENT, E_NEG_RHS, E_REVISED_PRECOND, E_SINGULAR, E_KNAP_SHAPE, E_UNKNOWN_ALGO, E_PARSE = (
     -10, -11, -12, -13, -14, -15, -16)
 
 STATUS_NAMES = {OPTIMAL: "OPTIMAL", UNBOUNDED: "UNBOUNDED", INFEASIBLE: "INFEASIBLE",
-                ITER_LIMIT: "ITER_LIMIT"}
+                ITER_LIMIT: "ITER_LIMIT", CUTOFF: "CUTOFF"}
 
 dp = C.POINTER(C.c_double)
 ip = C.POINTER(C.c_int32)
@@ -300,6 +301,13 @@ def lib() -> C.CDLL:
                                         C.POINTER(BnbBoundedInfo)]
     L.lpx_bnb_bounded_info_free.argtypes = [C.POINTER(BnbBoundedInfo)]
     L.lpx_bnb_bounded_info_free.restype = None
+    L.lpx_bounded_dual_run3.argtypes = [vp, C.POINTER(RunOpts), C.c_int, C.c_double, PIVOT_CB, vp, C.POINTER(Stats)]
+    L.lpx_bounded_node2.argtypes = [vp, C.c_int, ip, dp, dp, C.POINTER(RunOpts), C.c_int, C.c_double, C.c_int, u8p, C.c_double,
+                                    C.POINTER(NodeRecord)]
+    L.lpx_solve_bnb_bounded2.argtypes = [C.POINTER(Problem), dp, dp, u8p, C.POINTER(SolveOpts), C.c_int64, C.c_int, C.POINTER(Result),
+                                         C.POINTER(BnbBoundedInfo)]
+    L.lpx_solve_bounded_dual.argtypes = [C.POINTER(Problem), dp, dp, C.c_int, C.POINTER(SolveOpts), C.POINTER(Result),
+                                         C.POINTER(BoundedInfo)]
     L.lpx_parse_text.argtypes = [C.c_char_p, C.POINTER(Parsed)]
     L.lpx_parsed_free.argtypes = [C.POINTER(Parsed)]
     L.lpx_parsed_free.restype = None

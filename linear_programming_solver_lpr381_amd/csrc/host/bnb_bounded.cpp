@@ -1,5 +1,5 @@
-// host/bnb_bounded.cpp -- branch and bound by bound changes (lpx_solve_bnb_bounded, include/lpx.h): the root is SolveBounded
-// keeping its handle, and every node after it is ONE lpx_bounded_node call on that handle -- the columns whose bounds differ
+// host/bnb_bounded.cpp -- branch and bound by bound changes (lpx_solve_bnb_bounded / _bounded2, include/lpx.h): the root is SolveBounded
+// keeping its handle, and every node after it is ONE lpx_bounded_node (flagged search: lpx_bounded_node2) call on that handle -- the columns whose bounds differ
 // from the bounds now on the device, in ascending order.  A node is its path of (var, lower, upper) overrides: no tableau is
 // copied, parked or reshaped, and the node store is a few bytes per node.  Search order and pruning are those of
 // Models/Branch&Bound.cs (depth first, ceil child first :253-257, prune at z <= best + EPS :182, branch on the fraction closest
@@ -28,7 +28,8 @@ struct Node { int depth; std::vector<Override> path; };
 }  // namespace
 
 SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
-                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info)
+                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
+                              int search_flags)
 {
     const int n = original.NumVars();
     if ((!lower.empty() && (int)lower.size() != n) || (!upper.empty() && (int)upper.size() != n))
@@ -48,6 +49,8 @@ SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<doubl
                                            " needs finite, integral lower and upper bounds");
     }
     if (max_nodes < 0) throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: max_nodes is negative");
+    if (search_flags & ~(LPX_BDUAL_LONG_STEP | LPX_BDUAL_CUTOFF))
+        throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: search_flags holds a bit other than LPX_BDUAL_LONG_STEP and LPX_BDUAL_CUTOFF");
 
     EngineOptions ropt = opt; ropt.quiet = true;
     BoundedSession ses;
@@ -88,7 +91,12 @@ SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<doubl
             if (nb_lo[j] != cur_lo[j] || nb_ub[j] != cur_ub[j]) { cols.push_back(j); clo.push_back(nb_lo[j]); cub.push_back(nb_ub[j]); }
         const int K = (int)cols.size();
         lpx_node_record rec;
-        const int rc = lpx_bounded_node(ses.h, K, cols.data(), clo.data(), cub.data(), &o, n, mask, EPS, &rec);
+        // with CUTOFF the loop stops where this node would be pruned by bound anyway; search_flags = 0 stays the old call, messages included
+        const double cutoff = (search_flags & LPX_BDUAL_CUTOFF) ? best + EPS : 0.0;
+        const int rc = search_flags == 0
+            ? lpx_bounded_node(ses.h, K, cols.data(), clo.data(), cub.data(), &o, n, mask, EPS, &rec)
+            : lpx_bounded_node2(ses.h, K, cols.data(), clo.data(), cub.data(), &o, LPX_BDUAL_SKIP_FIXED | search_flags, cutoff,
+                                n, mask, EPS, &rec);
         if (rc < 0) throw_lib(rc);
         cur_lo = nb_lo; cur_ub = nb_ub;
         info.events += rec.events; info.flips += rec.flips;
@@ -105,7 +113,7 @@ SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<doubl
         }
         if (rec.status == LPX_INFEASIBLE) { info.pruned_infeasible++; continue; }
         const double z = rec.pick.z;
-        if (z <= best + EPS) { info.pruned_bound++; continue; }                      // :182
+        if (rec.status == LPX_CUTOFF || z <= best + EPS) { info.pruned_bound++; continue; }     // :182
         if (rec.pick.var < 0) {                                                     // :189-195
             std::vector<double> x((size_t)n, 0.0);
             const int rs = lpx_tableau_bounded_solution(ses.h, n, x.data(), nullptr, nullptr);

@@ -1,7 +1,8 @@
 // host/bounded.cpp -- the bounded-variable primal simplex at the model level (lpx_solve_bounded, include/lpx.h): preparation as
 // PrimalSimplex.Solve (Models/PrimalSimplex.cs:57-90), lower bounds shifted away on the host, upper bounds handed to the device
 // loop (lpx_bounded_run) beside the tableau instead of as rows.  A bounded session (lpx_bounded_open) is the same solve that
-// keeps its handle; its bound edits are lpx_tableau_change_bounds + lpx_bounded_dual_run on that handle.
+// keeps its handle; its bound edits are lpx_tableau_change_bounds + lpx_bounded_dual_run on that handle.  The dual start
+// (lpx_solve_bounded_dual) shares the preparation and solves from the slack basis with lpx_bounded_dual_run3.
 #include "model.h"
 
 #include <cmath>
@@ -87,9 +88,20 @@ BoundedSession::~BoundedSession()
     release_exact_handle(h, R, C);
 }
 
-SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
-                           const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info, BoundedSession* keep)
+namespace {
+
+// The model as the loops see it: internal tableau with its slack basis, shifted upper bounds, and what the lower shift took out.
+struct Prepared {
+    std::vector<double> T; int R = 0, C = 0; std::vector<int32_t> basis; std::vector<std::string> varNames;
+    std::vector<double> ub; double constant = 0.0; bool shifted = false; std::string report;
+};
+
+// dual_start = false: the preparation of lpx_solve_bounded.  true: that of lpx_solve_bounded_dual -- a >= row is negated into a <=
+// row instead of being refused, a negative shifted RHS is accepted, and an improving variable without an upper bound is refused.
+Prepared prepare_bounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
+                         const EngineOptions& opt, UpdatePivot updatePivot, bool dual_start)
 {
+    Prepared P;
     const int n = original.NumVars();
     if ((!lower.empty() && (int)lower.size() != n) || (!upper.empty() && (int)upper.size() != n))
         throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: lower / upper need one entry per variable");
@@ -107,28 +119,53 @@ SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>&
         for (Constraint& cons : model.Constraints)
             for (int j = 0; j < n; ++j)
                 if (lower[j] != 0.0) { const double prod = cons.A[j] * lower[j]; cons.B = cons.B - prod; }
-    for (const Constraint& cons : model.Constraints) {                                  // :66-77
+    if (dual_start)
+        for (Constraint& cons : model.Constraints)
+            if (cons.Relation == Rel::GE) {                                             // exact: only signs change
+                for (double& a : cons.A) a = -a;
+                cons.B = -cons.B; cons.Relation = Rel::LE;
+            }
+    if (!dual_start) for (const Constraint& cons : model.Constraints) {                 // :66-77
         if (cons.Relation == Rel::GE)
             throw LpxException(LPX_E_GE_PRESENT, "Constraint contains '>=' sign. The Primal Simplex method cannot handle this. Please try the Dual Simplex algorithm instead.");
         if (cons.B < -1e-9)
             throw LpxException(LPX_E_NEG_RHS, "Constraint has a negative RHS value. The Primal Simplex method cannot handle this. Please try the Dual Simplex algorithm instead.");
     }
-    double constant = 0.0;          // c.l in the user's sense
-    bool shifted = false;
+    double& constant = P.constant;  // c.l in the user's sense
+    bool& shifted = P.shifted;
     if (!lower.empty())
         for (int j = 0; j < n; ++j)
             if (lower[j] != 0.0) { const double prod = original.C[j] * lower[j]; constant = constant + prod; shifted = true; }
 
     LPProblem tableauModel = ExpandEqualitiesToInequalities(model);                     // :80
-    std::string report = opt.quiet ? std::string() : AppendCanonicalForm(tableauModel); // :82
-    std::vector<double> T; int R, C; std::vector<int32_t> basis; std::vector<std::string> varNames;
+    P.report = opt.quiet ? std::string() : AppendCanonicalForm(tableauModel);           // :82
+    std::vector<double>& T = P.T; int& R = P.R; int& C = P.C; std::vector<int32_t>& basis = P.basis;
+    std::vector<std::string>& varNames = P.varNames;
     BuildTableauPrimal(tableauModel, T, R, C, basis, varNames);                         // :85
     if (R < 2) throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: the model has no constraints");
     if (updatePivot) updatePivot(AppendTableau("TABLEAU Iteration", T.data(), R, C, basis, varNames, 0), nullptr);
     const int Cm = C - 1;
-    std::vector<double> ub((size_t)Cm, 1.0 / 0.0);
+    P.ub.assign((size_t)Cm, 1.0 / 0.0);
+    if (!upper.empty()) for (int j = 0; j < n; ++j) P.ub[j] = std::isinf(upper[j]) ? upper[j] : upper[j] - (lower.empty() ? 0.0 : lower[j]);
+    if (dual_start)
+        for (int j = 0; j < n; ++j)
+            if (T[(size_t)(R - 1) * C + j] < -1e-9 && std::isinf(P.ub[j]))
+                throw LpxException(LPX_EINVAL, "Bounded Dual Simplex: x" + std::to_string(j + 1) + " improves the objective and has no upper "
+                                               "bound: a bound flip cannot make it dual feasible");
+    return P;
+}
+
+}  // namespace
+
+SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
+                           const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info, BoundedSession* keep)
+{
+    const int n = original.NumVars();
+    Prepared P = prepare_bounded(original, lower, upper, opt, updatePivot, false);
+    std::vector<double>& T = P.T; const int R = P.R, C = P.C, Cm = C - 1; std::vector<int32_t>& basis = P.basis;
+    const std::vector<std::string>& varNames = P.varNames; const std::vector<double>& ub = P.ub;
+    const double constant = P.constant; const bool shifted = P.shifted; const std::string& report = P.report;
     const bool bounded = !upper.empty() || !lower.empty() || keep;       // a session edits bounds later: its handle always has them
-    if (!upper.empty()) for (int j = 0; j < n; ++j) ub[j] = std::isinf(upper[j]) ? upper[j] : upper[j] - (lower.empty() ? 0.0 : lower[j]);
 
     SimplexResult res;
     BoundedHandle th(R, C);
@@ -155,6 +192,42 @@ SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>&
         keep->min = original.ObjectiveSense == Sense::Min; keep->shifted = shifted; keep->constant = constant;
         keep->lower = lower; keep->open_status = st; keep->opt = opt; keep->varNames = varNames;
     }
+    return res;
+}
+
+SimplexResult SolveBoundedDual(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper, int flags,
+                               const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info)
+{
+    if (flags & ~(LPX_BDUAL_SKIP_FIXED | LPX_BDUAL_LONG_STEP))
+        throw LpxException(LPX_EINVAL, "Bounded Dual Simplex: flags holds a bit other than LPX_BDUAL_SKIP_FIXED and LPX_BDUAL_LONG_STEP");
+    const int n = original.NumVars();
+    Prepared P = prepare_bounded(original, lower, upper, opt, updatePivot, true);
+    const int R = P.R, C = P.C, Cm = C - 1;
+
+    SimplexResult res;
+    BoundedHandle th(R, C);
+    int rc = lpx_tableau_upload(th.h, P.T.data(), P.basis.data());
+    if (rc) throw_lib(rc);
+    rc = lpx_tableau_set_bounds(th.h, Cm, P.ub.data()); if (rc) throw_lib(rc);
+    int64_t dz[2] = {0, 0};
+    rc = lpx_tableau_dualize(th.h, 1e-9, dz); if (rc) throw_lib(rc);       // every improving column to its other bound
+    lpx_run_opts o; lpx_default_opts(&o, 1);
+    o.max_iter = opt.max_iter;
+    o.batch = opt.batch;
+    EventCtx ctx{updatePivot, &P.varNames};
+    const int st = lpx_bounded_dual_run3(th.h, &o, flags, 0.0, updatePivot ? bounded_event : nullptr, &ctx, &res.Stats);
+    if (st < 0) throw_lib(st);
+    if (st == LPX_ITER_LIMIT) throw LpxException(LPX_ITER_LIMIT, "Iteration limit exceeded.");
+    int64_t counts[3] = {0, 0, 0};
+    lpx_bounded_counts(th.h, counts);
+    std::vector<uint8_t> flip;
+    collect(th.h, st, n, R, C, lower, original.ObjectiveSense == Sense::Min, P.shifted, P.constant, P.report, res, &flip);
+    const std::string tail = "  dual start: " + std::to_string(dz[0]) + " dual-feasibility flips, " + std::to_string(counts[2]) + " passes\n";
+    res.Report += tail; res.Summary += tail.substr(2);
+    if (opt.on_final_tableau) opt.on_final_tableau(th.h, st);
+    res.VarNames = P.varNames;
+    res.Aux = {(double)counts[0], (double)counts[1], (double)counts[2], P.constant};
+    if (info) { info->flip = flip; info->ub = P.ub; info->lower = lower.empty() ? std::vector<double>((size_t)n, 0.0) : lower; }
     return res;
 }
 

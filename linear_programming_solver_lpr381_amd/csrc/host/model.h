@@ -224,6 +224,9 @@ struct BoundedSession {
 };
 SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
                            const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info, BoundedSession* keep = nullptr);
+// The dual start (lpx_solve_bounded_dual): >= rows and negative right-hand sides accepted, slack basis, dualize, lpx_bounded_dual_run3(flags)
+SimplexResult SolveBoundedDual(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper, int flags,
+                               const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info);
 // new absolute bounds of user variables vars[k] on a session: lpx_tableau_change_bounds + lpx_bounded_dual_run (lpx_bounded_set_bounds)
 SimplexResult BoundedSetBounds(BoundedSession& s, int K, const int32_t* vars, const double* lower, const double* upper);
 
@@ -236,7 +239,8 @@ struct BnbBoundedInfo {
     int limit_rc = 0; std::string limit_msg;
 };
 SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
-                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info);
+                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
+                              int search_flags = 0);      // lpx_solve_bnb_bounded2: LPX_BDUAL_LONG_STEP / LPX_BDUAL_CUTOFF on every node
 
 // LPParser.ParseFromText, Models/LPParser.cs:9-79.  Throws LpxException(LPX_E_PARSE, message).
 LPProblem ParseFromText(const std::string& input);

@@ -67,12 +67,14 @@ struct lpx_tableau {
         // branch and bound by bound changes (lpx_bnb_bounded.hip): the column list of lpx_tableau_dualize with its two counts
         // behind it, the device record of lpx_tableau_branch_pick, the integer mask, and the pinned slab the records come back through
         int32_t* dzl = nullptr; lpx_branch_pick* pickrec = nullptr; uint8_t* pickmask = nullptr; char* nodeslab = nullptr;
+        // lpx_bounded_dual_run3: the objective cutoff the select kernel reads, and the host value its copy is made from
+        double* cutoff = nullptr; double cutoff_h = 0.0;
 
         void free()
         {
             hipFree(ub); hipFree(flip); hipFree(snapUb); hipFree(snapFlip);
             hipFree(lo); hipFree(snapLo); hipFree(chg);
-            hipFree(dzl); hipFree(pickrec); hipFree(pickmask); if (nodeslab) hipHostFree(nodeslab);
+            hipFree(dzl); hipFree(pickrec); hipFree(pickmask); if (nodeslab) hipHostFree(nodeslab); hipFree(cutoff);
         }
     } bnd;
 };

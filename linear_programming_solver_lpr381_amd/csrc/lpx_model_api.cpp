@@ -277,10 +277,11 @@ int lpx_solve(const lpx_problem* p, const char* algorithm, const lpx_solve_opts*
     }
 }
 
-int lpx_solve_bounded(const lpx_problem* p, const double* lower, const double* upper, const lpx_solve_opts* o, lpx_result* out,
-                      lpx_bounded_info* info)
+// lpx_solve_bounded (dual_start = false) and lpx_solve_bounded_dual (true, with the dual loop's flags) in one body
+static int solve_bounded(const lpx_problem* p, const double* lower, const double* upper, bool dual_start, int flags, const lpx_solve_opts* o,
+                         lpx_result* out, lpx_bounded_info* info, const char* what)
 {
-    if (!p || !out) { set_error("lpx_solve_bounded: null argument"); return LPX_EINVAL; }
+    if (!p || !out) { set_error(std::string(what) + ": null argument"); return LPX_EINVAL; }
     std::memset(out, 0, sizeof(*out));
     if (info) std::memset(info, 0, sizeof(*info));
     lpx_solve_opts d; if (!o) { lpx_default_solve_opts(&d); o = &d; }
@@ -292,7 +293,7 @@ int lpx_solve_bounded(const lpx_problem* p, const double* lower, const double* u
         if (lower) lo.assign(lower, lower + p->n);
         if (upper) up.assign(upper, upper + p->n);
         BoundedInfo bi;
-        SimplexResult r = SolveBounded(q, lo, up, e, cb, &bi);
+        SimplexResult r = dual_start ? SolveBoundedDual(q, lo, up, flags, e, cb, &bi) : SolveBounded(q, lo, up, e, cb, &bi);
         fill_result(out, r, p->n);
         if (info) {
             info->ncols = (int)bi.ub.size(); info->n = p->n;
@@ -303,9 +304,21 @@ int lpx_solve_bounded(const lpx_problem* p, const double* lower, const double* u
         set_error(ex.what());
         return ex.code;
     } catch (const std::exception& ex) {
-        set_error(std::string("lpx_solve_bounded: ") + ex.what());
+        set_error(std::string(what) + ": " + ex.what());
         return LPX_EINVAL;
     }
+}
+
+int lpx_solve_bounded(const lpx_problem* p, const double* lower, const double* upper, const lpx_solve_opts* o, lpx_result* out,
+                      lpx_bounded_info* info)
+{
+    return solve_bounded(p, lower, upper, false, 0, o, out, info, "lpx_solve_bounded");
+}
+
+int lpx_solve_bounded_dual(const lpx_problem* p, const double* lower, const double* upper, int flags, const lpx_solve_opts* o,
+                           lpx_result* out, lpx_bounded_info* info)
+{
+    return solve_bounded(p, lower, upper, true, flags, o, out, info, "lpx_solve_bounded_dual");
 }
 
 void lpx_bounded_info_free(lpx_bounded_info* info)
@@ -356,14 +369,14 @@ int lpx_bounded_set_bounds(lpx_bounded_session* s, int K, const int32_t* vars, c
 void lpx_bounded_close(lpx_bounded_session* s) { delete s; }
 
 // ---- branch and bound by bound changes on the root's handle (host/bnb_bounded.cpp) ------------------------------------------
-int lpx_solve_bnb_bounded(const lpx_problem* p, const double* lower, const double* upper, const uint8_t* is_int,
-                          const lpx_solve_opts* o, int64_t max_nodes, lpx_result* out, lpx_bnb_bounded_info* info)
+static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const double* upper, const uint8_t* is_int, const lpx_solve_opts* o,
+                            int64_t max_nodes, int search_flags, lpx_result* out, lpx_bnb_bounded_info* info, const char* what)
 {
-    if (!p || !out) { set_error("lpx_solve_bnb_bounded: null argument"); return LPX_EINVAL; }
+    if (!p || !out) { set_error(std::string(what) + ": null argument"); return LPX_EINVAL; }
     std::memset(out, 0, sizeof(*out));
     if (info) std::memset(info, 0, sizeof(*info));
     lpx_solve_opts d; if (!o) { lpx_default_solve_opts(&d); o = &d; }
-    return guarded("lpx_solve_bnb_bounded", [&]() -> int {
+    return guarded(what, [&]() -> int {
         EngineOptions e = to_engine(o);
         LPProblem q = to_problem(p);
         std::vector<double> lo, up;
@@ -372,7 +385,7 @@ int lpx_solve_bnb_bounded(const lpx_problem* p, const double* lower, const doubl
         if (upper) up.assign(upper, upper + p->n);
         if (is_int) mask.assign(is_int, is_int + p->n);
         BnbBoundedInfo bi;
-        SimplexResult r = SolveBnbBounded(q, lo, up, mask, e, max_nodes, bi);
+        SimplexResult r = SolveBnbBounded(q, lo, up, mask, e, max_nodes, bi, search_flags);
         fill_result(out, r, p->n);
         if (info) {
             info->nodes = bi.nodes; info->events = bi.events; info->flips = bi.flips; info->incumbents = bi.incumbents;
@@ -383,6 +396,18 @@ int lpx_solve_bnb_bounded(const lpx_problem* p, const double* lower, const doubl
         if (bi.limit_rc) { set_error(bi.limit_msg); return bi.limit_rc; }
         return 0;
     });
+}
+
+int lpx_solve_bnb_bounded(const lpx_problem* p, const double* lower, const double* upper, const uint8_t* is_int,
+                          const lpx_solve_opts* o, int64_t max_nodes, lpx_result* out, lpx_bnb_bounded_info* info)
+{
+    return solve_bnb_bounded(p, lower, upper, is_int, o, max_nodes, 0, out, info, "lpx_solve_bnb_bounded");
+}
+
+int lpx_solve_bnb_bounded2(const lpx_problem* p, const double* lower, const double* upper, const uint8_t* is_int,
+                           const lpx_solve_opts* o, int64_t max_nodes, int search_flags, lpx_result* out, lpx_bnb_bounded_info* info)
+{
+    return solve_bnb_bounded(p, lower, upper, is_int, o, max_nodes, search_flags, out, info, "lpx_solve_bnb_bounded2");
 }
 
 void lpx_bnb_bounded_info_free(lpx_bnb_bounded_info* info)

@@ -1,6 +1,6 @@
 // lpx_tableau_bounded.cpp -- host side of the bounded-variable family on a tableau handle (C ABI of include/lpx.h): bounds beside
 // the tableau, the bounded primal and dual loops, bound changes on a solved tableau, branch and bound by bound changes.
-// Kernels: lpx_bounded.hip, lpx_bounded_dual.hip, lpx_bnb_bounded.hip; the update is lpx_update.
+// Kernels: lpx_bounded.hip, lpx_bounded_dual.hip, lpx_bounded_long.hip, lpx_bnb_bounded.hip; the update is lpx_update.
 #include "lpx_handle.h"
 
 #include <cstring>
@@ -165,11 +165,20 @@ int stage_bound_edit(lpx_tableau* t, int K, const int32_t* cols, const double* l
     return 0;
 }
 
-// The three bounded loops in one body: dual = 0 is lpx_bounded_run, 1 lpx_bounded_dual_run, 2 its form that skips fixed columns.
-// The value goes into the parameter record, so that every form selects its own kernel and keys its own cached graph.
-int bounded_run(lpx_tableau* t, const lpx_run_opts* o, int dual, lpx_pivot_cb cb, void* user, lpx_stats* st)
+// the `dual` word of a flag set of the dual loop: the two old forms keep their values, every set with a new bit gets its own
+int dual_form(int flags)
 {
-    const std::string w = dual ? "lpx_bounded_dual_run" : "lpx_bounded_run";
+    if (flags & (LPX_BDUAL_LONG_STEP | LPX_BDUAL_CUTOFF)) return BDUAL_FORM_BASE + flags;
+    return (flags & LPX_BDUAL_SKIP_FIXED) ? 2 : 1;
+}
+
+// The bounded loops in one body: dual = 0 is lpx_bounded_run, 1 lpx_bounded_dual_run, 2 its form that skips fixed columns,
+// BDUAL_FORM_BASE + flags a form of lpx_bounded_dual_run3 with the long step or the cutoff (kernel: lpx_bounded_long.hip).
+// The value goes into the parameter record, so that every form selects its own kernel and keys its own cached graph.
+int bounded_run(lpx_tableau* t, const lpx_run_opts* o, int dual, lpx_pivot_cb cb, void* user, lpx_stats* st, double cutoff = 0.0)
+{
+    const bool lng = dual >= BDUAL_FORM_BASE;
+    const std::string w = lng ? "lpx_bounded_dual_run3" : dual ? "lpx_bounded_dual_run" : "lpx_bounded_run";
     if (!t) { set_error(w + ": null tableau"); return LPX_EINVAL; }
     lpx_run_opts d; if (!o) { lpx_default_opts(&d, dual ? 1 : 0); o = &d; }
     if (t->R < 2) { set_error(w + ": tableau needs at least one constraint row"); return LPX_EINVAL; }
@@ -180,9 +189,17 @@ int bounded_run(lpx_tableau* t, const lpx_run_opts* o, int dual, lpx_pivot_cb cb
     b.P = base_params(t, o, MODE_BOUNDED);
     b.P.us = nullptr; b.P.part_v = nullptr; b.P.part_i = nullptr; b.P.nblk = 0; b.P.qsel = 0;   // single-workgroup select
     b.ub = t->bnd.ub; b.flip = t->bnd.flip; b.dual = dual;
+    if (lng && ((dual - BDUAL_FORM_BASE) & LPX_BDUAL_CUTOFF)) {
+        // the value travels beside the parameter record: copied on the handle's stream in front of the run, read through a pointer
+        if (!t->bnd.cutoff) LPX_HIP_TRY(hipMalloc((void**)&t->bnd.cutoff, sizeof(double)));
+        t->bnd.cutoff_h = cutoff;
+        LPX_HIP_TRY(hipMemcpyAsync(t->bnd.cutoff, &t->bnd.cutoff_h, sizeof(double), hipMemcpyHostToDevice, t->stream));
+        b.cutoff = t->bnd.cutoff;
+    }
     LoopCtx c; DevState init;
     make_ctx(t, b.P, b, [b](hipStream_t s, hipEvent_t e0, hipEvent_t e1) -> int {
-        if (b.dual) LPX_HIP_TRY(launch_bounded_dual_select(b, s));
+        if (b.dual >= BDUAL_FORM_BASE) LPX_HIP_TRY(launch_bounded_long_select(b, s));
+        else if (b.dual) LPX_HIP_TRY(launch_bounded_dual_select(b, s));
         else LPX_HIP_TRY(launch_bounded_select(b, s));
         // a launch that ended on a flip or on a final status leaves nothing to update: lpx_update returns at once
         LPX_HIP_TRY(launch_update(b.P, b.P.pcol, b.P.pcol, s, e0, e1));
@@ -193,9 +210,10 @@ int bounded_run(lpx_tableau* t, const lpx_run_opts* o, int dual, lpx_pivot_cb cb
     n[0] = n[1] = n[2] = 0;
     rc = run_device_loop(c, init, o, (long long)o->max_iter + 2, cb, user, &local);
     if (rc < 0) return rc;
-    // the select kernel counts the pivots per kind in the two counters the dual path uses for its phases; only the primal loop flips
+    // the select kernel counts the pivots per kind in the two counters the dual path uses for its phases; the other events are the
+    // flips of the primal loop and the passes of the long step
     n[0] = t->hst->fdf_count; n[1] = t->hst->dual_iter;
-    if (!dual) n[2] = (int64_t)t->hst->iter - n[0] - n[1];
+    if (!dual || lng) n[2] = (int64_t)t->hst->iter - n[0] - n[1];
     local.pivots = n[0] + n[1]; local.fdf_pivots = 0; local.cleanup_pivots = 0;
     if (st) { const double h2d = st->h2d_ms, d2h = st->d2h_ms; *st = local; st->h2d_ms = h2d; st->d2h_ms = d2h; }
     return rc;
@@ -375,21 +393,23 @@ int lpx_tableau_branch_pick(lpx_tableau* t, int nint, const uint8_t* is_int, dou
     return 0;
 }
 
-int lpx_bounded_node(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const lpx_run_opts* o,
-                     int nint, const uint8_t* is_int, double tol, lpx_node_record* out)
+// lpx_bounded_node (flags = LPX_BDUAL_SKIP_FIXED) and lpx_bounded_node2 in one body; `what` is the entry point's name
+static int bounded_node(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const lpx_run_opts* o,
+                        int flags, double cutoff, int nint, const uint8_t* is_int, double tol, lpx_node_record* out, const char* what)
 {
-    int rc = check_change_args(t, K, cols, lower, upper, "lpx_bounded_node"); if (rc) return rc;
-    rc = check_pick_args(t, nint, tol, out, "lpx_bounded_node"); if (rc) return rc;
+    const std::string w = what;
+    int rc = check_change_args(t, K, cols, lower, upper, what); if (rc) return rc;
+    rc = check_pick_args(t, nint, tol, out, what); if (rc) return rc;
     lpx_run_opts d; if (!o) { lpx_default_opts(&d, 1); o = &d; }
-    if (t->R < 2) { set_error("lpx_bounded_node: tableau needs at least one constraint row"); return LPX_EINVAL; }
-    if (o->resident > 0) { set_error("lpx_bounded_node: there is no resident form of the bounded dual loop"); return LPX_EINVAL; }
-    if (!(o->eps >= 0.0)) { set_error("lpx_bounded_node: eps is negative or NaN"); return LPX_EINVAL; }
+    if (t->R < 2) { set_error(w + ": tableau needs at least one constraint row"); return LPX_EINVAL; }
+    if (o->resident > 0) { set_error(w + ": there is no resident form of the bounded dual loop"); return LPX_EINVAL; }
+    if (!(o->eps >= 0.0)) { set_error(w + ": eps is negative or NaN"); return LPX_EINVAL; }
     const int Cm = t->C - 1;
     rc = bounded_ready(t, true); if (rc) return rc;
     std::memset(out, 0, sizeof(*out));
     out->pick.var = -1;
     BoundEdit e;
-    rc = stage_bound_edit(t, K, cols, lower, upper, "lpx_bounded_node", &e); if (rc) return rc;
+    rc = stage_bound_edit(t, K, cols, lower, upper, what, &e); if (rc) return rc;
     if (K > 0) {
         // the new ub and lo first (small arrays only): the list of the flips needs them, and the tableau is still untouched
         LPX_HIP_TRY(launch_bounds_save(K, e.cols, t->bnd.ub, t->bnd.lo, e.save, 0, t->stream));
@@ -407,7 +427,7 @@ int lpx_bounded_node(lpx_tableau* t, int K, const int32_t* cols, const double* l
         LPX_HIP_TRY(launch_bounds_save(K, e.cols, t->bnd.ub, t->bnd.lo, e.save, 1, t->stream));     // ub and lo as they were
         LPX_HIP_TRY(hipStreamSynchronize(t->stream));
         out->flips = 0;
-        set_error("lpx_bounded_node: " + std::to_string(out->unrepairable) + " column(s) with a negative reduced cost and no upper "
+        set_error(w + ": " + std::to_string(out->unrepairable) + " column(s) with a negative reduced cost and no upper "
                   "bound: a bound flip cannot restore dual feasibility");
         return LPX_EINVAL;
     }
@@ -416,7 +436,7 @@ int lpx_bounded_node(lpx_tableau* t, int K, const int32_t* cols, const double* l
     if (K > 0) LPX_HIP_TRY(launch_bounds_apply(t->T, t->ld, t->R, Cm, K, e.cols, e.shift, t->rhsbuf, t->stream));
     rc = enqueue_dualize_apply(t); if (rc) return rc;
     // the loop (it resets the state record itself and waits once per batch)
-    const int status = bounded_run(t, o, 2, nullptr, nullptr, nullptr);
+    const int status = bounded_run(t, o, dual_form(flags), nullptr, nullptr, nullptr, cutoff);
     if (status < 0) return status;
     out->status = status; out->events = t->hst->iter; out->kind0 = t->bnd.bcounts[0]; out->kind1 = t->bnd.bcounts[1];
     if (status == LPX_OPTIMAL) {
@@ -430,6 +450,34 @@ int lpx_bounded_node(lpx_tableau* t, int K, const int32_t* cols, const double* l
         out->pick.var = -1; out->pick.candidates = 0; out->pick.x_var = 0.0; out->pick.z = slab->pick.z;
     }
     return status;
+}
+
+int lpx_bounded_node(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const lpx_run_opts* o,
+                     int nint, const uint8_t* is_int, double tol, lpx_node_record* out)
+{
+    return bounded_node(t, K, cols, lower, upper, o, LPX_BDUAL_SKIP_FIXED, 0.0, nint, is_int, tol, out, "lpx_bounded_node");
+}
+
+// ---- long-step ratio test and objective cutoff (select kernel in lpx_bounded_long.hip) ----
+static int check_long_flags(int flags, double cutoff, const char* what)
+{
+    if (flags & ~(LPX_BDUAL_SKIP_FIXED | LPX_BDUAL_LONG_STEP | LPX_BDUAL_CUTOFF)) { set_error(std::string(what) + ": unknown flag"); return LPX_EINVAL; }
+    if ((flags & LPX_BDUAL_CUTOFF) && cutoff != cutoff) { set_error(std::string(what) + ": cutoff is NaN"); return LPX_EINVAL; }
+    return 0;
+}
+
+int lpx_bounded_dual_run3(lpx_tableau* t, const lpx_run_opts* o, int flags, double cutoff, lpx_pivot_cb cb, void* user, lpx_stats* st)
+{
+    const int rc = check_long_flags(flags, cutoff, "lpx_bounded_dual_run3"); if (rc) return rc;
+    if (!t) { set_error("lpx_bounded_dual_run3: null tableau"); return LPX_EINVAL; }
+    return bounded_run(t, o, dual_form(flags), cb, user, st, cutoff);
+}
+
+int lpx_bounded_node2(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const lpx_run_opts* o,
+                      int flags, double cutoff, int nint, const uint8_t* is_int, double tol, lpx_node_record* out)
+{
+    const int rc = check_long_flags(flags, cutoff, "lpx_bounded_node2"); if (rc) return rc;
+    return bounded_node(t, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, "lpx_bounded_node2");
 }
 
 }  // extern "C"

@@ -293,11 +293,22 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         self.FinalTableau = res.Tableau
         return res
 
+    def SolveBoundedDual(self, problem: LPProblem, upper, lower=None, long_step: bool = True) -> SimplexResult:
+        """The dual start (lpx_solve_bounded_dual): the bounded dual simplex from the slack basis, for the models SolveBounded
+        refuses -- >= rows and negative right-hand sides are accepted; every variable that improves the objective needs a
+        finite upper bound.  long_step: the bound-flipping ratio test (LPX_BDUAL_LONG_STEP).  Status OPTIMAL or INFEASIBLE; the
+        result is laid out as SolveBounded's, BoundCounts = (kind-0 pivots, kind-1 pivots, passes)."""
+        return self._solve_bounded(problem, upper, lower, _lib.BDUAL_LONG_STEP if long_step else 0)
+
     def SolveBounded(self, problem: LPProblem, upper=None, lower=None) -> SimplexResult:
         """The bounded-variable primal simplex on the device (lpx_solve_bounded): lower[j] <= x_j <= upper[j] without a row
         per bound (None: 0 / +inf).  Status, Solution (user variables), OptimalValue (user's sense), Tableau / Basis (the final
         internal tableau), Trace (events: (r, q) pivot, (-2 - r, q) pivot to the upper bound, (-1, q) bound flip), AtUpper,
         Flips, BoundCounts.  Solve(problem, "Bounded Primal Simplex") is this without bounds."""
+        return self._solve_bounded(problem, upper, lower, None)
+
+    def _solve_bounded(self, problem: LPProblem, upper, lower, dual_flags) -> SimplexResult:
+        """lpx_solve_bounded (dual_flags None) or lpx_solve_bounded_dual: the same call shape and result layout."""
         n = problem.NumVars
         o, keep = _solve_opts(self.engine)
         ps, hold = _problem_struct(problem)
@@ -310,7 +321,10 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         lo, lop = _vec(lower)
         up, upp = _vec(upper)
         r, info = _lib.Result(), _lib.BoundedInfo()
-        rc = lib().lpx_solve_bounded(C.byref(ps), lop, upp, C.byref(o), C.byref(r), C.byref(info))
+        if dual_flags is None:
+            rc = lib().lpx_solve_bounded(C.byref(ps), lop, upp, C.byref(o), C.byref(r), C.byref(info))
+        else:
+            rc = lib().lpx_solve_bounded_dual(C.byref(ps), lop, upp, int(dual_flags), C.byref(o), C.byref(r), C.byref(info))
         if rc != 0:
             raise SolverException(rc, _lib.last_error())
         try:
@@ -327,12 +341,15 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         self.FinalTableau = res.Tableau
         return res
 
-    def SolveBnbBounded(self, problem: LPProblem, upper, lower=None, integer=None, max_nodes: int = 0) -> SimplexResult:
+    def SolveBnbBounded(self, problem: LPProblem, upper, lower=None, integer=None, max_nodes: int = 0,
+                        long_step: bool = False, cutoff: bool = False) -> SimplexResult:
         """Branch and bound by bound changes on one device tableau (lpx_solve_bnb_bounded): lower <= x <= upper, x_j integer
         where integer[j] (None: every variable); integer variables need finite, integral bounds.  Status OPTIMAL or INFEASIBLE,
         Solution, OptimalValue (user's sense), Nodes, BnbInfo (counters) and BnbLog, a structured array with one record per node
         (depth, K, status, events, flips, var, z).  A node or search limit raises SolverException(ITER_LIMIT) whose .result
-        holds the incumbent so far."""
+        holds the incumbent so far.  long_step / cutoff (lpx_solve_bnb_bounded2): every node's dual loop runs with the
+        long-step ratio test / stops as soon as its objective has fallen to the incumbent + 1e-6 (such a node is logged with
+        status CUTOFF and counted as pruned by bound); both off is lpx_solve_bnb_bounded."""
         n = problem.NumVars
         o, keep = _solve_opts(self.engine)
         ps, hold = _problem_struct(problem)
@@ -349,7 +366,11 @@ class LPSolver:             # Models/LPSolver.cs:6-77
             mask = np.ascontiguousarray(np.broadcast_to(np.asarray(integer, dtype=np.uint8), (n,)))
             mp = mask.ctypes.data_as(C.POINTER(C.c_uint8))
         r, info = _lib.Result(), _lib.BnbBoundedInfo()
-        rc = lib().lpx_solve_bnb_bounded(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), C.byref(r), C.byref(info))
+        flags = (_lib.BDUAL_LONG_STEP if long_step else 0) | (_lib.BDUAL_CUTOFF if cutoff else 0)
+        if flags:
+            rc = lib().lpx_solve_bnb_bounded2(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), flags, C.byref(r), C.byref(info))
+        else:
+            rc = lib().lpx_solve_bnb_bounded(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), C.byref(r), C.byref(info))
         if rc != 0 and rc != _lib.ITER_LIMIT:
             raise SolverException(rc, _lib.last_error())
         msg = _lib.last_error() if rc else ""

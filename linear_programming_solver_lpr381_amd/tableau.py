@@ -283,14 +283,22 @@ class DeviceTableau:
                                               upper.ctypes.data_as(dp)))
 
     def bounded_dual_run(self, opts: Optional[RunOpts] = None, cb: Optional[PivotCallback] = None,
-                         skip_fixed: bool = False, **kw) -> Tuple[int, dict]:
+                         skip_fixed: bool = False, long_step: bool = False, cutoff: Optional[float] = None,
+                         **kw) -> Tuple[int, dict]:
         """Bounded dual simplex (lpx_bounded_dual_run): one event per iteration -- a pivot (r, q) on a row whose basic
         variable is below zero, or (-2 - r, q) on a row whose basic variable is above its upper bound.  skip_fixed=True is
-        lpx_bounded_dual_run2 with LPX_BDUAL_SKIP_FIXED: a column with ub = 0 does not enter.  Returns (status, stats)."""
+        lpx_bounded_dual_run2 with LPX_BDUAL_SKIP_FIXED: a column with ub = 0 does not enter.  long_step=True or a cutoff is
+        lpx_bounded_dual_run3: boxed candidates that leave the row infeasible pass by a bound flip (-1, q) instead of
+        entering; the loop ends with status CUTOFF once z <= cutoff.  Returns (status, stats)."""
         o = opts if opts is not None else default_opts(True, **kw)
         st = Stats()
         c = _wrap_cb(cb)
-        if skip_fixed:
+        if long_step or cutoff is not None:
+            flags = ((_lib.BDUAL_SKIP_FIXED if skip_fixed else 0) | (_lib.BDUAL_LONG_STEP if long_step else 0)
+                     | (_lib.BDUAL_CUTOFF if cutoff is not None else 0))
+            rc = check(lib().lpx_bounded_dual_run3(self._h, C.byref(o), flags, float(cutoff if cutoff is not None else 0.0), c,
+                                                   None, C.byref(st)))
+        elif skip_fixed:
             rc = check(lib().lpx_bounded_dual_run2(self._h, C.byref(o), _lib.BDUAL_SKIP_FIXED, c, None, C.byref(st)))
         else:
             rc = check(lib().lpx_bounded_dual_run(self._h, C.byref(o), c, None, C.byref(st)))
@@ -320,17 +328,25 @@ class DeviceTableau:
         return {"var": out.var, "candidates": out.candidates, "x_var": out.x_var, "z": out.z}
 
     def bounded_node(self, cols, lower, upper, nint: int, is_int=None, tol: float = 1e-6,
-                     opts: Optional[RunOpts] = None, **kw) -> dict:
+                     opts: Optional[RunOpts] = None, long_step: bool = False, cutoff: Optional[float] = None, **kw) -> dict:
         """One branch-and-bound node in one call (lpx_bounded_node): change_bounds, dualize, the dual loop in which fixed
-        columns do not enter, and on OPTIMAL the branch pick.  Returns the node record as a dict."""
+        columns do not enter, and on OPTIMAL the branch pick.  long_step=True or a cutoff is lpx_bounded_node2: the loop runs
+        with those flags and may end with status CUTOFF (no pick).  Returns the node record as a dict."""
         cols = np.ascontiguousarray(np.atleast_1d(cols), dtype=np.int32).reshape(-1)
         lower = np.ascontiguousarray(np.broadcast_to(np.asarray(lower, dtype=np.float64), cols.shape))
         upper = np.ascontiguousarray(np.broadcast_to(np.asarray(upper, dtype=np.float64), cols.shape))
         o = opts if opts is not None else default_opts(True, **kw)
         keep, mp = self._mask(is_int, int(nint))
         rec = _lib.NodeRecord()
-        check(lib().lpx_bounded_node(self._h, len(cols), cols.ctypes.data_as(ip), lower.ctypes.data_as(dp),
-                                     upper.ctypes.data_as(dp), C.byref(o), int(nint), mp, float(tol), C.byref(rec)))
+        if long_step or cutoff is not None:
+            flags = (_lib.BDUAL_SKIP_FIXED | (_lib.BDUAL_LONG_STEP if long_step else 0)
+                     | (_lib.BDUAL_CUTOFF if cutoff is not None else 0))
+            check(lib().lpx_bounded_node2(self._h, len(cols), cols.ctypes.data_as(ip), lower.ctypes.data_as(dp),
+                                          upper.ctypes.data_as(dp), C.byref(o), flags, float(cutoff if cutoff is not None else 0.0),
+                                          int(nint), mp, float(tol), C.byref(rec)))
+        else:
+            check(lib().lpx_bounded_node(self._h, len(cols), cols.ctypes.data_as(ip), lower.ctypes.data_as(dp),
+                                         upper.ctypes.data_as(dp), C.byref(o), int(nint), mp, float(tol), C.byref(rec)))
         return {"status": rec.status, "events": rec.events, "kind0": rec.kind0, "kind1": rec.kind1, "flips": rec.flips,
                 "unrepairable": rec.unrepairable, "var": rec.pick.var, "candidates": rec.pick.candidates,
                 "x_var": rec.pick.x_var, "z": rec.pick.z}

@@ -1,7 +1,7 @@
 // lpx_cli -- Linux stand-in for the reference's WinForms host (Form1.cs), over the C ABI of liblpx.so only.
 //
 //   lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]
-//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded] [--export FILE] INPUT.txt
+//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff]] [--export FILE] INPUT.txt
 //
 // Does what Form1 does around the solvers: reads the model text (Import, Form1.cs:284-296), parses it with the LPParser
 // grammar (lpx_parse_text, Models/LPParser.cs:9-79), runs the algorithm chosen by its dropdown name (btnSolve_Click,
@@ -76,6 +76,7 @@ int main(int argc, char** argv)
 {
     std::string algorithm = "Primal Simplex", input, exportPath;
     bool repaired = false, iterations = false, ranging = false, cut_set = false, algo_set = false, binary = false, bnb_bounded = false;
+    int search_flags = 0;       // --long-step / --cutoff beside --bnb-bounded
     struct Bound { bool upper; int index; double value; std::string text; };
     std::vector<Bound> bounds;
     lpx_cut_opts co; lpx_default_cut_opts(&co);
@@ -86,6 +87,8 @@ int main(int argc, char** argv)
         if (a == "--algorithm" && i + 1 < argc) { algorithm = argv[++i]; algo_set = true; }
         else if (a == "--binary") binary = true;
         else if (a == "--bnb-bounded") bnb_bounded = true;
+        else if (a == "--long-step") search_flags |= LPX_BDUAL_LONG_STEP;
+        else if (a == "--cutoff") search_flags |= LPX_BDUAL_CUTOFF;
         else if ((a == "--upper" || a == "--lower") && i + 1 < argc) {
             const std::string v = argv[++i];
             const size_t eq = v.find('=');
@@ -122,7 +125,8 @@ int main(int argc, char** argv)
         else if (a == "--export" && i + 1 < argc) exportPath = argv[++i];
         else if (a == "--help" || a == "-h") {
             std::printf("usage: lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]\n"
-                        "               [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded] [--export FILE] INPUT.txt\n"
+                        "               [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff]]\n"
+                        "               [--export FILE] INPUT.txt\n"
                         "  NAME: Primal Simplex | Revised Primal Simplex | Dual Simplex | Branch and Bound |\n"
                         "        Revised Branch and Bound | Branch and Bound Knapsack | Cutting Plane | Revised Cutting Plane |\n"
                         "        GMI Cutting Plane (gmi) | Bounded Primal Simplex\n"
@@ -133,6 +137,8 @@ int main(int argc, char** argv)
                         "             by the Bounded Primal Simplex (no rows are added); not with --ranging, the cut options or another algorithm\n"
                         "  --bnb-bounded: with --binary / --upper / --lower, every variable integer: branch and bound by bound changes on the\n"
                         "             root's device tableau (every variable needs a finite, integral upper bound)\n"
+                        "  --long-step, --cutoff: with --bnb-bounded, every node's dual loop uses the long-step (bound-flipping) ratio test /\n"
+                        "             stops as soon as its objective has fallen to the incumbent (lpx_solve_bnb_bounded2)\n"
                         "  --set-rhs I=V, --set-cost J=V: after the solve, b_I = V / c_J = V (1-based, repeatable), applied in order,\n"
                         "             each re-optimised warm on the device from the previous basis; each re-solve's summary is printed\n");
             return 0;
@@ -145,6 +151,7 @@ int main(int argc, char** argv)
     }
     const bool bounded = binary || !bounds.empty();
     if (bnb_bounded && !bounded) { std::fprintf(stderr, "lpx_cli: --bnb-bounded needs --binary or --upper bounds\n"); return 64; }
+    if (search_flags && !bnb_bounded) { std::fprintf(stderr, "lpx_cli: --long-step / --cutoff need --bnb-bounded\n"); return 64; }
     if (bounded) {
         if (ranging) { std::fprintf(stderr, "lpx_cli: --upper / --lower / --binary do not combine with --ranging\n"); return 64; }
         if (cut_set) { std::fprintf(stderr, "lpx_cli: --upper / --lower / --binary do not combine with --cuts-per-round / --cut-rounds\n"); return 64; }
@@ -174,7 +181,8 @@ int main(int argc, char** argv)
         if (bd.index >= p.n) { std::fprintf(stderr, "lpx_cli: %s: index out of range\n", bd.text.c_str()); lpx_parsed_free(&p); return 64; }
         (bd.upper ? up : lo)[bd.index] = bd.value;
     }
-    const int rc = bnb_bounded ? lpx_solve_bnb_bounded(&prob, lo.data(), up.data(), nullptr, &o, 0, &r, nullptr)
+    const int rc = bnb_bounded && search_flags ? lpx_solve_bnb_bounded2(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, &r, nullptr)
+                 : bnb_bounded ? lpx_solve_bnb_bounded(&prob, lo.data(), up.data(), nullptr, &o, 0, &r, nullptr)
                  : bounded ? lpx_solve_bounded(&prob, lo.data(), up.data(), &o, &r, nullptr) : ranging ? lpx_solve_ranging(&prob, algorithm.c_str(), &o, &r, &rg)
                  : cut_set ? lpx_solve_cuts(&prob, &o, &co, &r) : lpx_solve(&prob, algorithm.c_str(), &o, &r);
     if (rc != 0) { lpx_parsed_free(&p); lpx_last_error(err, sizeof err); std::fprintf(stderr, "%s\n", err); return rc == LPX_EDEVICE ? 69 : 70; }
