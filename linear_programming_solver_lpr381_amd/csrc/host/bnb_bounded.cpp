@@ -15,13 +15,6 @@ namespace {
 
 constexpr double EPS = 1e-6;      // Models/Branch&Bound.cs:24
 
-[[noreturn]] void throw_lib(int rc)
-{
-    char buf[1024];
-    lpx_last_error(buf, sizeof(buf));
-    throw LpxException(rc, std::string("liblpx: ") + buf);
-}
-
 struct Override { int var; double lo, ub; };
 struct Node { int depth; std::vector<Override> path; };
 
@@ -36,11 +29,8 @@ SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<doubl
         throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: lower / upper need one entry per variable");
     if (!is_int.empty() && (int)is_int.size() != n)
         throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: the integer mask needs one entry per variable");
-    for (int j = 0; j < n; ++j) {       // the checks of SolveBounded, with its messages, in front of the integer ones
-        const double l = lower.empty() ? 0.0 : lower[j], u = upper.empty() ? 1.0 / 0.0 : upper[j];
-        if (!std::isfinite(l)) throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: lower bound of x" + std::to_string(j + 1) + " is not finite");
-        if (!(u >= l)) throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: upper bound of x" + std::to_string(j + 1) + " is below its lower bound or NaN");
-    }
+    for (int j = 0; j < n; ++j)         // the checks of SolveBounded, with its messages, in front of the integer ones
+        CheckVarBounds("x" + std::to_string(j + 1), lower.empty() ? 0.0 : lower[j], upper.empty() ? 1.0 / 0.0 : upper[j]);
     for (int j = 0; j < n; ++j) {
         if (!is_int.empty() && !is_int[j]) continue;
         const double l = lower.empty() ? 0.0 : lower[j], u = upper.empty() ? 1.0 / 0.0 : upper[j];

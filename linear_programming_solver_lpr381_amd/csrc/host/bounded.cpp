@@ -10,14 +10,13 @@
 
 namespace lpx { namespace host {
 
-namespace {
-
-[[noreturn]] void throw_lib(int rc)
+void CheckVarBounds(const std::string& var, double lower, double upper)
 {
-    char buf[1024];
-    lpx_last_error(buf, sizeof(buf));
-    throw LpxException(rc, std::string("liblpx: ") + buf);
+    if (!std::isfinite(lower)) throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: lower bound of " + var + " is not finite");
+    if (!(upper >= lower)) throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: upper bound of " + var + " is below its lower bound or NaN");
 }
+
+namespace {
 
 struct BoundedHandle {
     lpx_tableau* h = nullptr; int R, C;
@@ -105,11 +104,8 @@ Prepared prepare_bounded(const LPProblem& original, const std::vector<double>& l
     const int n = original.NumVars();
     if ((!lower.empty() && (int)lower.size() != n) || (!upper.empty() && (int)upper.size() != n))
         throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: lower / upper need one entry per variable");
-    for (int j = 0; j < n; ++j) {
-        const double l = lower.empty() ? 0.0 : lower[j], u = upper.empty() ? 1.0 / 0.0 : upper[j];
-        if (!std::isfinite(l)) throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: lower bound of x" + std::to_string(j + 1) + " is not finite");
-        if (!(u >= l)) throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: upper bound of x" + std::to_string(j + 1) + " is below its lower bound or NaN");
-    }
+    for (int j = 0; j < n; ++j)
+        CheckVarBounds("x" + std::to_string(j + 1), lower.empty() ? 0.0 : lower[j], upper.empty() ? 1.0 / 0.0 : upper[j]);
     LPProblem model = original.Clone();
     if (model.ObjectiveSense == Sense::Min) for (double& c : model.C) c = -c;          // :62-63
     for (const Constraint& cons : model.Constraints)
@@ -155,6 +151,26 @@ Prepared prepare_bounded(const LPProblem& original, const std::vector<double>& l
     return P;
 }
 
+// The tail that SolveBounded and SolveBoundedDual share, from the status of the finished loop to the result: the iteration-limit
+// throw, the counts, collect, the caller's own report lines (`tail`, given the counts; may be empty), on_final_tableau, names,
+// Aux and info.
+void finish_solve(lpx_tableau* h, int st, const LPProblem& original, const std::vector<double>& lower, const Prepared& P,
+                  const EngineOptions& opt, const std::function<std::string(const int64_t*)>& tail, SimplexResult& res, BoundedInfo* info)
+{
+    const int n = original.NumVars();
+    if (st < 0) throw_lib(st);
+    if (st == LPX_ITER_LIMIT) throw LpxException(LPX_ITER_LIMIT, "Iteration limit exceeded.");      // :95-96
+    int64_t counts[3] = {0, 0, 0};
+    lpx_bounded_counts(h, counts);
+    std::vector<uint8_t> flip;
+    collect(h, st, n, P.R, P.C, lower, original.ObjectiveSense == Sense::Min, P.shifted, P.constant, P.report, res, &flip);
+    if (tail) { const std::string lines = tail(counts); res.Report += lines; res.Summary += lines.substr(2); }
+    if (opt.on_final_tableau) opt.on_final_tableau(h, st);
+    res.VarNames = P.varNames;
+    res.Aux = {(double)counts[0], (double)counts[1], (double)counts[2], P.constant};
+    if (info) { info->flip = flip; info->ub = P.ub; info->lower = lower.empty() ? std::vector<double>((size_t)n, 0.0) : lower; }
+}
+
 }  // namespace
 
 SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
@@ -162,35 +178,24 @@ SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>&
 {
     const int n = original.NumVars();
     Prepared P = prepare_bounded(original, lower, upper, opt, updatePivot, false);
-    std::vector<double>& T = P.T; const int R = P.R, C = P.C, Cm = C - 1; std::vector<int32_t>& basis = P.basis;
-    const std::vector<std::string>& varNames = P.varNames; const std::vector<double>& ub = P.ub;
-    const double constant = P.constant; const bool shifted = P.shifted; const std::string& report = P.report;
+    const int R = P.R, C = P.C;
     const bool bounded = !upper.empty() || !lower.empty() || keep;       // a session edits bounds later: its handle always has them
 
     SimplexResult res;
     BoundedHandle th(R, C);
-    int rc = lpx_tableau_upload(th.h, T.data(), basis.data());
+    int rc = lpx_tableau_upload(th.h, P.T.data(), P.basis.data());
     if (rc) throw_lib(rc);
-    if (bounded) { rc = lpx_tableau_set_bounds(th.h, Cm, ub.data()); if (rc) throw_lib(rc); }
+    if (bounded) { rc = lpx_tableau_set_bounds(th.h, C - 1, P.ub.data()); if (rc) throw_lib(rc); }
     lpx_run_opts o; lpx_default_opts(&o, 0);
     o.max_iter = opt.max_iter;
     o.batch = opt.batch;
-    EventCtx ctx{updatePivot, &varNames};
+    EventCtx ctx{updatePivot, &P.varNames};
     const int st = lpx_bounded_run(th.h, &o, updatePivot ? bounded_event : nullptr, &ctx, &res.Stats);
-    if (st < 0) throw_lib(st);
-    if (st == LPX_ITER_LIMIT) throw LpxException(LPX_ITER_LIMIT, "Iteration limit exceeded.");      // :95-96
-    int64_t counts[3] = {0, 0, 0};
-    lpx_bounded_counts(th.h, counts);
-    std::vector<uint8_t> flip;
-    collect(th.h, st, n, R, C, lower, original.ObjectiveSense == Sense::Min, shifted, constant, report, res, &flip);
-    if (opt.on_final_tableau) opt.on_final_tableau(th.h, st);
-    res.VarNames = varNames;
-    res.Aux = {(double)counts[0], (double)counts[1], (double)counts[2], constant};
-    if (info) { info->flip = flip; info->ub = ub; info->lower = lower.empty() ? std::vector<double>((size_t)n, 0.0) : lower; }
+    finish_solve(th.h, st, original, lower, P, opt, nullptr, res, info);
     if (keep) {
         keep->h = th.take(); keep->R = R; keep->C = C; keep->n = n;
-        keep->min = original.ObjectiveSense == Sense::Min; keep->shifted = shifted; keep->constant = constant;
-        keep->lower = lower; keep->open_status = st; keep->opt = opt; keep->varNames = varNames;
+        keep->min = original.ObjectiveSense == Sense::Min; keep->shifted = P.shifted; keep->constant = P.constant;
+        keep->lower = lower; keep->open_status = st; keep->opt = opt; keep->varNames = P.varNames;
     }
     return res;
 }
@@ -200,7 +205,6 @@ SimplexResult SolveBoundedDual(const LPProblem& original, const std::vector<doub
 {
     if (flags & ~(LPX_BDUAL_SKIP_FIXED | LPX_BDUAL_LONG_STEP))
         throw LpxException(LPX_EINVAL, "Bounded Dual Simplex: flags holds a bit other than LPX_BDUAL_SKIP_FIXED and LPX_BDUAL_LONG_STEP");
-    const int n = original.NumVars();
     Prepared P = prepare_bounded(original, lower, upper, opt, updatePivot, true);
     const int R = P.R, C = P.C, Cm = C - 1;
 
@@ -216,18 +220,9 @@ SimplexResult SolveBoundedDual(const LPProblem& original, const std::vector<doub
     o.batch = opt.batch;
     EventCtx ctx{updatePivot, &P.varNames};
     const int st = lpx_bounded_dual_run3(th.h, &o, flags, 0.0, updatePivot ? bounded_event : nullptr, &ctx, &res.Stats);
-    if (st < 0) throw_lib(st);
-    if (st == LPX_ITER_LIMIT) throw LpxException(LPX_ITER_LIMIT, "Iteration limit exceeded.");
-    int64_t counts[3] = {0, 0, 0};
-    lpx_bounded_counts(th.h, counts);
-    std::vector<uint8_t> flip;
-    collect(th.h, st, n, R, C, lower, original.ObjectiveSense == Sense::Min, P.shifted, P.constant, P.report, res, &flip);
-    const std::string tail = "  dual start: " + std::to_string(dz[0]) + " dual-feasibility flips, " + std::to_string(counts[2]) + " passes\n";
-    res.Report += tail; res.Summary += tail.substr(2);
-    if (opt.on_final_tableau) opt.on_final_tableau(th.h, st);
-    res.VarNames = P.varNames;
-    res.Aux = {(double)counts[0], (double)counts[1], (double)counts[2], P.constant};
-    if (info) { info->flip = flip; info->ub = P.ub; info->lower = lower.empty() ? std::vector<double>((size_t)n, 0.0) : lower; }
+    finish_solve(th.h, st, original, lower, P, opt, [&dz](const int64_t* counts) {
+        return "  dual start: " + std::to_string(dz[0]) + " dual-feasibility flips, " + std::to_string(counts[2]) + " passes\n";
+    }, res, info);
     return res;
 }
 
@@ -242,8 +237,7 @@ SimplexResult BoundedSetBounds(BoundedSession& s, int K, const int32_t* vars, co
         const std::string v = "x" + std::to_string(vars[k] + 1);
         if (seen[vars[k]]) throw LpxException(LPX_EINVAL, std::string(what) + v + " is listed twice");
         seen[vars[k]] = 1;
-        if (!std::isfinite(lower[k])) throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: lower bound of " + v + " is not finite");
-        if (!(upper[k] >= lower[k])) throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: upper bound of " + v + " is below its lower bound or NaN");
+        CheckVarBounds(v, lower[k], upper[k]);
     }
     if (s.open_status != LPX_OPTIMAL) throw LpxException(LPX_EINVAL, std::string(what) + "the open solve did not end OPTIMAL, there is no tableau to continue from");
     // the handle's columns stand for x - l(open): the user's absolute bounds move by that shift, one subtraction each

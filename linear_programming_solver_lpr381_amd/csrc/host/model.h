@@ -208,9 +208,14 @@ private:
     EngineOptions opt;
 };
 
+// a failed call of the C ABI as the exception of the model level: LpxException(rc, "liblpx: " + the library's last error) (solvers.cpp)
+[[noreturn]] void throw_lib(int rc);
+
 // Bounded-variable primal simplex at the model level (lpx_solve_bounded, include/lpx.h; bounded.cpp): lower / upper are empty
 // (0 / +inf) or hold one entry per variable.
 struct BoundedInfo { std::vector<uint8_t> flip; std::vector<double> ub, lower; };
+// the (lower, upper) pair of the variable called `var` ("x3"): lower finite, upper >= lower; LpxException(LPX_EINVAL) otherwise
+void CheckVarBounds(const std::string& var, double lower, double upper);
 // A bounded session (lpx_bounded_open): the handle SolveBounded solved on, kept with what turns its tableau back into the
 // user's terms.  The destructor hands the handle back.
 struct BoundedSession {

@@ -50,16 +50,14 @@ void release_exact_handle(lpx_tableau* t, int R, int C)
     lpx_tableau_destroy(t);
 }
 
-namespace {
-
-std::string last_error()
+[[noreturn]] void throw_lib(int rc)
 {
     char buf[1024];
     lpx_last_error(buf, sizeof(buf));
-    return buf;
+    throw LpxException(rc, std::string("liblpx: ") + buf);
 }
 
-[[noreturn]] void throw_lib(int rc) { throw LpxException(rc, "liblpx: " + last_error()); }
+namespace {
 
 struct TableauHandle {
     lpx_tableau* h = nullptr; int R_, C_;

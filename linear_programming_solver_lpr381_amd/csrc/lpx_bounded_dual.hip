@@ -1,30 +1,28 @@
 // lpx_bounded_dual.hip -- the dual side of the bounded-variable simplex, gfx950 (CDNA4, wave64): the select kernel of
-// lpx_bounded_dual_run and the two kernels of lpx_tableau_change_bounds.
+// lpx_bounded_dual_run / _run2 and the two kernels of lpx_tableau_change_bounds.
 //
 // The representation is the one of lpx_bounded.hip: ub[j] in [0, +inf] and flip[j] beside the tableau, plus the lower shift
 // lo[j] (internal column j stands for x_j - lo[j], or ub[j] - (x_j - lo[j]) when flipped).  The arithmetic contract is in
 // include/lpx.h ("bounded dual simplex"); DESIGN.md section 4.14 has the launch shape.  Built with -ffp-contract=off.
 //
-// One launch of lpx_bounded_dual_select (1 workgroup x 1024 lanes, the mould of lpx_bounded_select) decides ONE event:
-//   w_i of every row into `buf` (LDS, or global scratch)       -> r  (block_first_min_below: first strict minimum below -eps)
+// One launch of lpx_bounded_dual_select (1 workgroup x 1024 lanes) decides ONE event; the steps it shares with the other two
+// select kernels are the pieces of lpx_bounded.h:
+//   w_i of every row into `buf` (LDS, or global scratch)       -> r  (bnd_leaving_row)
 //   kind 1 (the basic variable of row r is above its bound): row r is complemented, on the fly
 //   column ratios of the (complemented) row r into `buf`        -> q  (rs_hysteresis: the exact chain of lpx_select's dual loop)
-//   pivot prep (column snapshot -> pcol, row r complemented and normalised -> prow and T[r,:]); the rank-1 update is the
-//   lpx_update launch that follows.
+//   no q: LPX_INFEASIBLE, with the complement of a kind-1 row applied in place (bnd_complement_row)
+//   pivot prep (bnd_pivot_prep, complement on the fly); the rank-1 update is the lpx_update launch that follows.
 // w and the ratios are never alive together, so they share one array: 4096 doubles of LDS, and the handle's scratch `ws` for
-// whichever of them is longer than that.
-#include "lpx_resident.h"      // rs_hysteresis (also pulls in lpx_block.h)
+// whichever of them is longer than that.  The kernel is launched from lpx_bounded_long.hip (launch_bounded_dual_select).
+#include "lpx_bounded.h"       // the pieces shared with the other two kernels: view, exit, leaving row, complement, pivot prep
 
 namespace lpx {
 
-static constexpr int BDD_LDS_DOUBLES = 4096;
-
-// SKIP_FIXED (lpx_bounded_dual_run2 with LPX_BDUAL_SKIP_FIXED): a column with ub[j] == 0 does not enter.  The unflagged
-// instantiation is the kernel of lpx_bounded_dual_run, unchanged.
+// SKIP_FIXED (LPX_BDUAL_SKIP_FIXED): a column with ub[j] == 0 does not enter.
 template <bool SKIP_FIXED>
 __global__ __launch_bounds__(SEL_NT) void lpx_bounded_dual_select(BndParams B)
 {
-    __shared__ double s_buf[BDD_LDS_DOUBLES];
+    __shared__ double s_buf[BND_LDS_DOUBLES];
     __shared__ int s_out;
     __shared__ double s_v[SEL_NW];
     __shared__ int s_i[SEL_NW];
@@ -33,47 +31,23 @@ __global__ __launch_bounds__(SEL_NT) void lpx_bounded_dual_select(BndParams B)
     DevState* st = P.st;
     if (st->status != LPX_RUNNING) return;              // uniform: loop already finished
 
-    const int t = threadIdx.x;
-    const int R = P.shape ? P.shape[0] : P.R, C = P.shape ? P.shape[1] : P.C;
-    const int m = R - 1;
-    const int rhs = C - 1;
-    const size_t ld = (size_t)P.ld;
-    double* T = P.T;
-    double* rhsb = P.rhsbuf;                            // contiguous copy of the RHS column, kept current by lpx_update
-    double* wbuf = (m <= BDD_LDS_DOUBLES) ? s_buf : P.ws;
-    double* ratios = (rhs <= BDD_LDS_DOUBLES) ? s_buf : P.ws;
+    const BndView V(P);
+    const int t = V.t, m = V.m, rhs = V.rhs;
+    double* ratios = bnd_buf(rhs, s_buf, P.ws);
     const double inf = __builtin_inf();
 
     const int iter = st->iter;                          // events so far
-    if (iter >= P.max_iter) {
-        if (t == 0) { st->status = LPX_ITER_LIMIT; st->r = -1; st->q = -1; }
-        return;
-    }
+    if (iter >= P.max_iter) { bnd_exit(st, t, LPX_ITER_LIMIT); return; }
 
-    // ---- leaving row: infeasibility of every row, below zero (kind 0) or above the basic variable's bound (kind 1)
-    for (int i = t; i < m; i += SEL_NT) {
-        const double b = rhsb[i];
-        const int pb = P.basis[i];
-        const double u = (unsigned)pb < (unsigned)rhs ? B.ub[pb] : inf;   // gather from a small array: L2
-        double w = inf;                                                  // the row does not take part
-        if (b < -P.eps) w = b;
-        else if (u < inf) w = u - b;
-        wbuf[i] = w;
-    }
-    __syncthreads();
-    const int r = block_first_min_below(wbuf, 1, m, P.eps, s_v, s_i);    // every lane is past its reads of wbuf on return
-    if (r < 0) {
-        if (t == 0) { st->status = LPX_OPTIMAL; st->r = -1; st->q = -1; }
-        return;
-    }
-    const int kind = rhsb[r] < -P.eps ? 0 : 1;          // one address for the whole workgroup: a broadcast load
+    const int r = bnd_leaving_row(V, B, bnd_buf(m, s_buf, P.ws), s_v, s_i);
+    if (r < 0) { bnd_exit(st, t, LPX_OPTIMAL); return; }
+    const int kind = V.rhsb[r] < -P.eps ? 0 : 1;        // one address for the whole workgroup: a broadcast load
     const int p = P.basis[r];
-    double* trow = T + (size_t)r * ld;
 
-    // ---- entering column over row r.  kind 1: the row is complemented first -- every entry but the basic column's 1.0
-    // negated, RHS = ub[p] - RHS.  Negation is exact, so it is applied on the fly in front of the division.
+    // ---- entering column over row r.  kind 1: the row is complemented first, on the fly (see bnd_complement)
     {
-        const double* zrow = T + (size_t)m * ld;
+        const double* trow = V.row(r);
+        const double* zrow = V.row(m);
         for (int j = t; j < rhs; j += SEL_NT) {
             double a = trow[j];
             if (kind && j != p) a = -a;
@@ -84,54 +58,17 @@ __global__ __launch_bounds__(SEL_NT) void lpx_bounded_dual_select(BndParams B)
     }
     __syncthreads();
     const int q = rs_hysteresis(rhs, P.tol_dual, ratios, s_v, s_i, &s_out);
-    const double up = kind ? B.ub[p] : 0.0;
     if (q < 0) {
         // no entering column: the LP is infeasible.  The complement of a kind-1 row stays applied (a valid representation).
-        if (kind) {
-            for (int j = t; j < C; j += SEL_NT) {
-                const double v = trow[j];
-                const double n = (j == rhs) ? up - v : (j == p ? v : -v);
-                trow[j] = n;
-                if (j == rhs) rhsb[r] = n;
-            }
-        }
-        if (t == 0) {
-            if (kind) B.flip[p] ^= 1;
-            st->status = LPX_INFEASIBLE; st->r = -1; st->q = -1;
-        }
+        if (kind) bnd_complement_row(V, B, r, p, B.ub[p]);
+        bnd_exit(st, t, LPX_INFEASIBLE);
         return;
     }
-
-    // ---- pivot prep, as lpx_bounded_select: the complement in front of the division
-    const double a = trow[q];                           // broadcast load
-    const double piv = kind ? -a : a;
-    for (int i = t; i < R; i += SEL_NT)
-        P.pcol[i] = (i == r) ? 0.0 : T[(size_t)i * ld + q];
-    __syncthreads();                                   // pivot, basis[r] and column read before anything is rewritten
-    for (int j = t; j < C; j += SEL_NT) {
-        double v = trow[j];
-        if (kind) v = (j == rhs) ? up - v : (j == p ? v : -v);
-        const double n = v / piv;
-        trow[j] = n;
-        P.prow[j] = n;
-        if (j == rhs) rhsb[r] = n;                     // lpx_update leaves row r alone
-    }
-    if (t == 0) {
-        if (kind) B.flip[p] ^= 1;
-        P.basis[r] = q;
-        if (iter < P.trace_cap) { P.trace[2 * iter] = kind ? -2 - r : r; P.trace[2 * iter + 1] = q; }
-        st->iter = iter + 1; st->primal_count = iter + 1;
-        st->r = r; st->q = q; st->qn = -1;
-        if (kind) st->dual_iter += 1; else st->fdf_count += 1;      // per-kind event counts (lpx_bounded_counts)
-    }
+    bnd_pivot_prep(V, B, r, q, p, iter, kind, kind);
 }
 
-hipError_t launch_bounded_dual_select(const BndParams& b, hipStream_t s)
-{
-    if (b.dual == 2) hipLaunchKernelGGL(lpx_bounded_dual_select<true>, dim3(1), dim3(SEL_NT), 0, s, b);
-    else hipLaunchKernelGGL(lpx_bounded_dual_select<false>, dim3(1), dim3(SEL_NT), 0, s, b);
-    return hipGetLastError();
-}
+template __global__ void lpx_bounded_dual_select<false>(BndParams);     // launched by launch_bounded_dual_select in
+template __global__ void lpx_bounded_dual_select<true>(BndParams);      // lpx_bounded_long.hip, which sees all eight forms
 
 // ---- lpx_tableau_change_bounds: two launches, neither reads what it writes ------------------------------------------------------
 // Launch 1: the shift of every changed column from the OLD lo / ub / flip, then the new ub and lo.  The columns are distinct

@@ -52,23 +52,21 @@ struct SelParams {
     int rcap;            // doubles of dynamic LDS available for ratios (0 = use ws)
 };
 
-// bounded-variable primal loop (lpx_bounded.hip): the select parameters plus the bounds kept beside the tableau
+// the bounded-variable loops (lpx_bounded.hip, lpx_bounded_dual.hip, lpx_bounded_long.hip; shared device pieces in lpx_bounded.h):
+// the select parameters plus the bounds kept beside the tableau
 struct BndParams {
     SelParams P;
     const double* ub;    // [C-1 capacity] upper bound of every column, +inf = none
     uint8_t* flip;       // [C-1 capacity] 1 = the column stands for u_j - x_j
-    int dual;            // 1 = the record of lpx_bounded_dual_run (it keeps the two loops' cached graphs apart), 2 = the record of
-                         // lpx_bounded_dual_run2 with LPX_BDUAL_SKIP_FIXED (the launcher picks the flagged instantiation by it),
-                         // BDUAL_FORM_BASE + flags = the record of lpx_bounded_dual_run3 with LONG_STEP or CUTOFF among its flags
-    const double* cutoff;   // lpx_bounded_dual_run3 with LPX_BDUAL_CUTOFF: the handle's device double (a pointer, never the value:
+    int dual;            // the form word: 0 = the primal loop, 1 + flags (LPX_BDUAL_*) = the dual loop with that flag set.  It
+                         // picks the kernel instantiation in the launcher, and as part of the record it keeps the cached
+                         // graphs of the forms apart.  lpx_bounded_dual_run is 1, _run2 with LPX_BDUAL_SKIP_FIXED is 2.
+    const double* cutoff;   // dual loop with LPX_BDUAL_CUTOFF: the handle's device double (a pointer, never the value:
                             // the record keys the cached graph and a driver moves the cutoff at every incumbent); else nullptr
 };
-static constexpr int BDUAL_FORM_BASE = 8;
 hipError_t launch_bounded_select(const BndParams& b, hipStream_t s);
-// bounded dual simplex and the bound change on a solved tableau (lpx_bounded_dual.hip)
+// every form of the dual loop, picked by b.dual (lpx_bounded_long.hip); hipErrorInvalidValue for a word that is no form
 hipError_t launch_bounded_dual_select(const BndParams& b, hipStream_t s);
-// its long-step / cutoff forms (lpx_bounded_long.hip)
-hipError_t launch_bounded_long_select(const BndParams& b, hipStream_t s);
 
 // branch and bound by bound changes (lpx_bnb_bounded.hip)
 // list[0..count) = ascending columns j < Cm with T[m,j] < -eps and 0 < ub[j] < +inf; cnt = {count, unrepairable}

@@ -1,6 +1,7 @@
 // lpx_tableau_bounded.cpp -- host side of the bounded-variable family on a tableau handle (C ABI of include/lpx.h): bounds beside
 // the tableau, the bounded primal and dual loops, bound changes on a solved tableau, branch and bound by bound changes.
-// Kernels: lpx_bounded.hip, lpx_bounded_dual.hip, lpx_bounded_long.hip, lpx_bnb_bounded.hip; the update is lpx_update.
+// Kernels: lpx_bounded.hip, lpx_bounded_dual.hip, lpx_bounded_long.hip (their shared pieces: lpx_bounded.h), lpx_bnb_bounded.hip;
+// the update is lpx_update.
 #include "lpx_handle.h"
 
 #include <cstring>
@@ -165,19 +166,13 @@ int stage_bound_edit(lpx_tableau* t, int K, const int32_t* cols, const double* l
     return 0;
 }
 
-// the `dual` word of a flag set of the dual loop: the two old forms keep their values, every set with a new bit gets its own
-int dual_form(int flags)
-{
-    if (flags & (LPX_BDUAL_LONG_STEP | LPX_BDUAL_CUTOFF)) return BDUAL_FORM_BASE + flags;
-    return (flags & LPX_BDUAL_SKIP_FIXED) ? 2 : 1;
-}
-
-// The bounded loops in one body: dual = 0 is lpx_bounded_run, 1 lpx_bounded_dual_run, 2 its form that skips fixed columns,
-// BDUAL_FORM_BASE + flags a form of lpx_bounded_dual_run3 with the long step or the cutoff (kernel: lpx_bounded_long.hip).
-// The value goes into the parameter record, so that every form selects its own kernel and keys its own cached graph.
+// The bounded loops in one body: dual = 0 is lpx_bounded_run, 1 + flags the dual loop with that set of LPX_BDUAL_* flags
+// (lpx_bounded_dual_run is 1).  The value goes into the parameter record (BndParams::dual), so that every form selects its own
+// kernel and keys its own cached graph.
 int bounded_run(lpx_tableau* t, const lpx_run_opts* o, int dual, lpx_pivot_cb cb, void* user, lpx_stats* st, double cutoff = 0.0)
 {
-    const bool lng = dual >= BDUAL_FORM_BASE;
+    const int flags = dual ? dual - 1 : 0;
+    const bool lng = flags & (LPX_BDUAL_LONG_STEP | LPX_BDUAL_CUTOFF);      // passes and LPX_CUTOFF exist only in these forms
     const std::string w = lng ? "lpx_bounded_dual_run3" : dual ? "lpx_bounded_dual_run" : "lpx_bounded_run";
     if (!t) { set_error(w + ": null tableau"); return LPX_EINVAL; }
     lpx_run_opts d; if (!o) { lpx_default_opts(&d, dual ? 1 : 0); o = &d; }
@@ -189,7 +184,7 @@ int bounded_run(lpx_tableau* t, const lpx_run_opts* o, int dual, lpx_pivot_cb cb
     b.P = base_params(t, o, MODE_BOUNDED);
     b.P.us = nullptr; b.P.part_v = nullptr; b.P.part_i = nullptr; b.P.nblk = 0; b.P.qsel = 0;   // single-workgroup select
     b.ub = t->bnd.ub; b.flip = t->bnd.flip; b.dual = dual;
-    if (lng && ((dual - BDUAL_FORM_BASE) & LPX_BDUAL_CUTOFF)) {
+    if (flags & LPX_BDUAL_CUTOFF) {
         // the value travels beside the parameter record: copied on the handle's stream in front of the run, read through a pointer
         if (!t->bnd.cutoff) LPX_HIP_TRY(hipMalloc((void**)&t->bnd.cutoff, sizeof(double)));
         t->bnd.cutoff_h = cutoff;
@@ -198,8 +193,7 @@ int bounded_run(lpx_tableau* t, const lpx_run_opts* o, int dual, lpx_pivot_cb cb
     }
     LoopCtx c; DevState init;
     make_ctx(t, b.P, b, [b](hipStream_t s, hipEvent_t e0, hipEvent_t e1) -> int {
-        if (b.dual >= BDUAL_FORM_BASE) LPX_HIP_TRY(launch_bounded_long_select(b, s));
-        else if (b.dual) LPX_HIP_TRY(launch_bounded_dual_select(b, s));
+        if (b.dual) LPX_HIP_TRY(launch_bounded_dual_select(b, s));
         else LPX_HIP_TRY(launch_bounded_select(b, s));
         // a launch that ended on a flip or on a final status leaves nothing to update: lpx_update returns at once
         LPX_HIP_TRY(launch_update(b.P, b.P.pcol, b.P.pcol, s, e0, e1));
@@ -250,7 +244,7 @@ int enqueue_pick(lpx_tableau* t, int nint, const uint8_t* is_int, double tol)
 
 extern "C" {
 
-// ---- bounded-variable primal and dual simplex (select kernels in lpx_bounded.hip / lpx_bounded_dual.hip, update = lpx_update) ----
+// ---- bounded-variable primal and dual simplex (select kernels in lpx_bounded.hip / lpx_bounded_dual.hip / lpx_bounded_long.hip, update = lpx_update) ----
 int lpx_tableau_set_bounds(lpx_tableau* t, int ncols, const double* ub)
 {
     if (!t) { set_error("lpx_tableau_set_bounds: null handle"); return LPX_EINVAL; }
@@ -279,7 +273,7 @@ int lpx_bounded_dual_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb,
 int lpx_bounded_dual_run2(lpx_tableau* t, const lpx_run_opts* o, int flags, lpx_pivot_cb cb, void* user, lpx_stats* st)
 {
     if (flags & ~LPX_BDUAL_SKIP_FIXED) { set_error("lpx_bounded_dual_run2: unknown flag"); return LPX_EINVAL; }
-    return bounded_run(t, o, (flags & LPX_BDUAL_SKIP_FIXED) ? 2 : 1, cb, user, st);
+    return bounded_run(t, o, 1 + flags, cb, user, st);
 }
 
 int lpx_tableau_bounded_solution(lpx_tableau* t, int nvars, double* x, double* z, uint8_t* at_upper)
@@ -436,7 +430,7 @@ static int bounded_node(lpx_tableau* t, int K, const int32_t* cols, const double
     if (K > 0) LPX_HIP_TRY(launch_bounds_apply(t->T, t->ld, t->R, Cm, K, e.cols, e.shift, t->rhsbuf, t->stream));
     rc = enqueue_dualize_apply(t); if (rc) return rc;
     // the loop (it resets the state record itself and waits once per batch)
-    const int status = bounded_run(t, o, dual_form(flags), nullptr, nullptr, nullptr, cutoff);
+    const int status = bounded_run(t, o, 1 + flags, nullptr, nullptr, nullptr, cutoff);
     if (status < 0) return status;
     out->status = status; out->events = t->hst->iter; out->kind0 = t->bnd.bcounts[0]; out->kind1 = t->bnd.bcounts[1];
     if (status == LPX_OPTIMAL) {
@@ -458,7 +452,7 @@ int lpx_bounded_node(lpx_tableau* t, int K, const int32_t* cols, const double* l
     return bounded_node(t, K, cols, lower, upper, o, LPX_BDUAL_SKIP_FIXED, 0.0, nint, is_int, tol, out, "lpx_bounded_node");
 }
 
-// ---- long-step ratio test and objective cutoff (select kernel in lpx_bounded_long.hip) ----
+// ---- long-step ratio test and objective cutoff (the dual loop's forms with a flag beyond LPX_BDUAL_SKIP_FIXED) ----
 static int check_long_flags(int flags, double cutoff, const char* what)
 {
     if (flags & ~(LPX_BDUAL_SKIP_FIXED | LPX_BDUAL_LONG_STEP | LPX_BDUAL_CUTOFF)) { set_error(std::string(what) + ": unknown flag"); return LPX_EINVAL; }
@@ -470,7 +464,7 @@ int lpx_bounded_dual_run3(lpx_tableau* t, const lpx_run_opts* o, int flags, doub
 {
     const int rc = check_long_flags(flags, cutoff, "lpx_bounded_dual_run3"); if (rc) return rc;
     if (!t) { set_error("lpx_bounded_dual_run3: null tableau"); return LPX_EINVAL; }
-    return bounded_run(t, o, dual_form(flags), cb, user, st, cutoff);
+    return bounded_run(t, o, 1 + flags, cb, user, st, cutoff);
 }
 
 int lpx_bounded_node2(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const lpx_run_opts* o,

@@ -152,6 +152,19 @@ def test_every_candidate_passes_and_the_event_ends_infeasible(gpu):
     assert ref[1][0].tolist() == [1.0, 1.0, 1.0, -1.0] and ref[3].tolist() == [1, 1, 0]      # the passes stay applied
 
 
+@pytest.mark.parametrize("flags", [LONG, LONG | SKIP, CUT, CUT | LONG, CUT | LONG | SKIP])
+def test_kind1_row_without_an_entering_column_stays_complemented(gpu, flags):
+    """The tableau of test_gpu_bounded_dual.test_infeasible_after_a_complement_leaves_it_in_place: columns x0, x1, s0 (u = 1, basic
+    in row 0 at 3), s1, RHS.  Row 0 is complemented in place in every form, has no negative entry afterwards, and stays so."""
+    T = np.array([[-1, -2, 1, 0, 3], [1, 1, 0, 1, 2], [1, 1, 0, 0, 0]], dtype=np.float64)
+    basis = np.array([2, 3], dtype=np.int32)
+    ref = _long(gpu, T, basis, np.array([INF, INF, 1.0, INF]), flags=flags, cutoff=-INF)
+    assert ref[0] == L.INFEASIBLE and len(ref[4]) == 0 and ref[5] == (0, 0, 0)
+    assert np.array_equal(_u64(ref[1][0]), _u64(np.array([1.0, 2.0, 1.0, -0.0, -2.0])))      # the sign of the zero is part of the bits
+    assert ref[3].tolist() == [0, 0, 1, 0]
+    assert np.array_equal(_u64(ref[1][1:]), _u64(T[1:])) and ref[2].tolist() == [2, 3]
+
+
 def test_an_unbounded_column_stops_the_chain(gpu):
     T, basis, ub = _hand([1.0, 2.0, 3.0], [-1.0, -1.0, -1.0], -3.5, [1.0, INF, 1.0])
     ref = _long(gpu, T, basis, ub)
