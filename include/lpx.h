@@ -307,7 +307,9 @@ int  lpx_revised_solve(const double* A, int m, int n, const double* c, const dou
  * workgroup per node.  Node k is the list of its fixed decisions fix_idx[off[k]..off[k+1]) (ORIGINAL
  * item indices, ascending) with values fix_val (0/1) -- the reference's int[n] Assigned (:25) without
  * the undecided entries.  Outputs per node: profit (= bound), weight, the fractional item's position in
- * ratio order (-1 if none) and its fraction. */
+ * ratio order (-1 if none) and its fraction.  With non-negative weights a node costs one wave and a search over prefix
+ * sums; a negative weight selects the scan kernel (one workgroup reads all n items per node) without any switch, as
+ * LPX_KNAP_SCAN=1 does for any data (tests/test_gpu_knapsack_edges.py covers it). */
 typedef struct lpx_knapsack lpx_knapsack;
 int  lpx_knapsack_create(const double* profit, const double* weight, int n, double cap, lpx_knapsack** out);
 void lpx_knapsack_destroy(lpx_knapsack* k);

@@ -145,7 +145,34 @@ __device__ __forceinline__ double wave_sum_f64(double x)
     return __hiloint2double(hi, lo);
 }
 
-struct KnPrefix { const double* PW; const double* PP; };
+// PWl / PPl: what the running sums PW / PP lost to rounding (double-double tails, zero for integer data)
+struct KnPrefix { const double* PW; const double* PP; const double* PWl; const double* PPl; };
+
+// Error-free sums for the closing arithmetic of knap_relax_prefix.  The probes only compare, but the totals in front of the
+// break are PW[t] minus the fixed weight, two numbers of the size of the instance total: in plain doubles a node that leaves
+// almost nothing undecided loses its relative accuracy.  Tails are zero and the heads unchanged whenever the sums are exact.
+__device__ __forceinline__ void two_sum(double a, double b, double& s, double& e)
+{
+    s = a + b;
+    const double bb = s - a;
+    e = (a - (s - bb)) + (b - bb);
+}
+__device__ __forceinline__ void dd_add(double& hi, double& lo, double x)
+{
+    double s, e;
+    two_sum(hi, x, s, e);
+    hi = s; lo += e;
+}
+__device__ __forceinline__ void wave_sum_dd(double& hi, double& lo)     // the same pair in every lane
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const double oh = __shfl_xor(hi, d, 64), ol = __shfl_xor(lo, d, 64);
+        double s, e;
+        two_sum(hi, oh, s, e);
+        hi = s; lo = (lo + ol) + e;
+    }
+}
 
 static constexpr int KP_CACHE = 4;        // fixed entries cached in registers per lane (depth <= 256)
 
@@ -205,18 +232,33 @@ __global__ __launch_bounds__(256) void knap_relax_prefix(KnParams P, KnPrefix X)
             fixed_before(mid, fw, fp);
             if (W1 + (X.PW[mid] - fw) > P.cap + KEPS) hi = mid; else lo = mid + 1;
         }
-        double fw, fp;
+        // undecided weight / profit in front of position t, error-free
+        auto undecided = [&](int t, double& uw, double& up) {
+            double ah = 0.0, al = 0.0, bh = 0.0, bl = 0.0;
+#pragma unroll
+            for (int k = 0; k < KP_CACHE; ++k) if (cpos[k] < t) { dd_add(ah, al, cw[k]); dd_add(bh, bl, cp[k]); }
+            for (int e = lane + 64 * KP_CACHE; e < d; e += 64) {
+                const int i = P.fidx[f0 + e];
+                if (P.pos[i] < t) { dd_add(ah, al, P.w0[i]); dd_add(bh, bl, P.p0[i]); }
+            }
+            wave_sum_dd(ah, al); wave_sum_dd(bh, bl);
+            if (xpos < t) { dd_add(ah, al, xw); dd_add(bh, bl, xp); }
+            double s, e;
+            two_sum(X.PW[t], -ah, s, e); uw = s + (e + (X.PWl[t] - al));
+            two_sum(X.PP[t], -bh, s, e); up = s + (e + (X.PPl[t] - bl));
+        };
+        double uw, up;
         if (lo == n + 1) {                                              // everything undecided fits
-            fixed_before(n, fw, fp);
+            undecided(n, uw, up);
             if (lane == 0) {
-                P.out_profit[slot] = P1 + (X.PP[n] - fp); P.out_weight[slot] = W1 + (X.PW[n] - fw);
+                P.out_profit[slot] = P1 + up; P.out_weight[slot] = W1 + uw;
                 P.out_frac[slot] = -1; P.out_fracval[slot] = 0.0;
             }
             return -1;
         }
         const int j = lo - 1;                                           // first undecided item that does not fit
-        fixed_before(j, fw, fp);
-        double w = W1 + (X.PW[j] - fw), p = P1 + (X.PP[j] - fp);
+        undecided(j, uw, up);
+        double w = W1 + uw, p = P1 + up;
         int frac = -1; double fv = 0.0;
         const double wi = P.ws[j];
         const double remain = P.cap - w;
@@ -532,7 +574,7 @@ __global__ __launch_bounds__(256) void knap_expand_w(KnParams P, KnPrefix X, con
 using namespace lpx;
 
 struct lpx_knapsack {
-    double *PW = nullptr, *PP = nullptr; bool prefix_ok = false;
+    double *PW = nullptr, *PP = nullptr, *PWl = nullptr, *PPl = nullptr; bool prefix_ok = false;
     int n = 0; double cap = 0;
     double *ws = nullptr, *ps = nullptr, *w0 = nullptr, *p0 = nullptr;
     int32_t* pos = nullptr;
@@ -561,7 +603,7 @@ void lpx_knapsack_destroy(lpx_knapsack* k)
 {
     if (!k) return;
     if (k->stream) hipStreamSynchronize(k->stream);
-    hipFree(k->ws); hipFree(k->ps); hipFree(k->w0); hipFree(k->p0); hipFree(k->pos); hipFree(k->PW); hipFree(k->PP);
+    hipFree(k->ws); hipFree(k->ps); hipFree(k->w0); hipFree(k->p0); hipFree(k->pos); hipFree(k->PW); hipFree(k->PP); hipFree(k->PWl); hipFree(k->PPl);
     hipFree(k->d_off); hipFree(k->d_fidx); hipFree(k->d_frac); hipFree(k->d_fval);
     hipFree(k->d_profit); hipFree(k->d_weight); hipFree(k->d_fracval);
     hipFree(k->d_in); hipFree(k->d_out); hipFree(k->d_jobs);
@@ -608,11 +650,18 @@ int lpx_knapsack_create(const double* profit, const double* weight, int n, doubl
     up((void**)&k->pos, pos.data(), sizeof(int32_t) * n);
     { const char* ev = std::getenv("LPX_KNAP_WIDE"); k->wide = !(ev && ev[0] == '0'); }
     // running sums in ratio order (left-to-right, as the reference accumulates) for the prefix-sum kernel
-    std::vector<double> PW(n + 1, 0.0), PP(n + 1, 0.0);
+    // PWl / PPl: the rounding errors of those additions, summed (zero for integer data); PW / PP themselves are unchanged
+    std::vector<double> PW(n + 1, 0.0), PP(n + 1, 0.0), PWl(n + 1, 0.0), PPl(n + 1, 0.0);
     bool nonneg = true;
-    for (int s = 0; s < n; ++s) { PW[s + 1] = PW[s] + ws[s]; PP[s + 1] = PP[s] + ps[s]; if (!(ws[s] >= 0.0)) nonneg = false; }
+    auto lost = [](double a, double b, double s) { const double bb = s - a; return (a - (s - bb)) + (b - bb); };
+    for (int s = 0; s < n; ++s) {
+        PW[s + 1] = PW[s] + ws[s]; PP[s + 1] = PP[s] + ps[s];
+        PWl[s + 1] = PWl[s] + lost(PW[s], ws[s], PW[s + 1]); PPl[s + 1] = PPl[s] + lost(PP[s], ps[s], PP[s + 1]);
+        if (!(ws[s] >= 0.0)) nonneg = false;
+    }
     k->prefix_ok = nonneg;
     up((void**)&k->PW, PW.data(), sizeof(double) * (n + 1)); up((void**)&k->PP, PP.data(), sizeof(double) * (n + 1));
+    up((void**)&k->PWl, PWl.data(), sizeof(double) * (n + 1)); up((void**)&k->PPl, PPl.data(), sizeof(double) * (n + 1));
     if (e == hipSuccess && (k->stream = borrow_stream()) == nullptr) e = hipErrorUnknown;
     if (e != hipSuccess) { set_error(std::string("lpx_knapsack_create: ") + hipGetErrorString(e)); lpx_knapsack_destroy(k); return LPX_EDEVICE; }
     *out = k;
@@ -671,7 +720,7 @@ static int relax_batch_impl(lpx_knapsack* k, int count, const int32_t* off, cons
     P.out_fracval = reinterpret_cast<double*>(k->d_out + o_fv); P.out_frac = reinterpret_cast<int32_t*>(k->d_out + o_fr);
     static const bool force_scan = [] { const char* e = std::getenv("LPX_KNAP_SCAN"); return e && e[0] == '1'; }();
     if (k->prefix_ok && !force_scan) {
-        KnPrefix X; X.PW = k->PW; X.PP = k->PP;
+        KnPrefix X; X.PW = k->PW; X.PP = k->PP; X.PWl = k->PWl; X.PPl = k->PPl;
         if (depth2) hipLaunchKernelGGL(knap_relax_prefix<true>, dim3((count + 3) / 4), dim3(256), 0, s, P, X);
         else hipLaunchKernelGGL(knap_relax_prefix<false>, dim3((count + 3) / 4), dim3(256), 0, s, P, X);
     } else if (depth2) {
@@ -776,7 +825,7 @@ int lpx_knapsack_expand_begin(lpx_knapsack* k, int count, const int64_t* parent,
     P.count = count; P.off = nullptr; P.fidx = nullptr; P.fval = nullptr;
     P.out_profit = reinterpret_cast<double*>(k->h_out + o_p); P.out_weight = reinterpret_cast<double*>(k->h_out + o_w);
     P.out_fracval = reinterpret_cast<double*>(k->h_out + o_fv); P.out_frac = reinterpret_cast<int32_t*>(k->h_out + o_fr);
-    KnPrefix X; X.PW = k->PW; X.PP = k->PP;
+    KnPrefix X; X.PW = k->PW; X.PP = k->PP; X.PWl = k->PWl; X.PPl = k->PPl;
     // every node of the batch within the wide kernel's list capacity -> 64 probes per round; deeper nodes -> one probe per step
     if (maxdepth <= KW_CAP && k->wide)
         hipLaunchKernelGGL(knap_expand_w, dim3((count + 3) / 4), dim3(256), 0, s, P, X, reinterpret_cast<const KnJob*>(k->h_jobs));
