@@ -1,5 +1,5 @@
-// lpx_handle.h -- the tableau handle and the host helpers its translation units share (lpx_tableau.cpp, lpx_tableau_bounded.cpp,
-// lpx_tableau_nodes.cpp).  Host .cpp files of this directory only: kernels and launchers see lpx_internal.h, never the struct.
+// lpx_handle.h -- the tableau handle and the host helpers its translation units share (lpx_tableau.cpp, lpx_tableau_resident.cpp,
+// lpx_tableau_groups.cpp, lpx_tableau_bounded.cpp, lpx_tableau_nodes.cpp).  Host .cpp files of this directory only: kernels and launchers see lpx_internal.h, never the struct.
 #pragma once
 #include "lpx_internal.h"
 
@@ -22,7 +22,6 @@ struct lpx_tableau {
     double* ws = nullptr;       // [MB_MAXB * max(R,C)]
     double* part_v = nullptr; int32_t* part_i = nullptr;   // [64] partial argmins of the multi-workgroup select
     lpx::DevState* us = nullptr;    // state record written by the update kernel (multi-workgroup protocol)
-    int use_mb = 1;
     int32_t* basis = nullptr;   // [R-1]
     int32_t* snapBasis = nullptr;
     int32_t* trace = nullptr;   // [2*trace_cap]
@@ -94,6 +93,35 @@ void drop_graph(lpx_tableau* t);
 bool fused_buffers(lpx_tableau* t);
 SelParams base_params(lpx_tableau* t, const lpx_run_opts* o, int mode);
 
+// The record every run starts from.
+inline DevState fresh_state(bool dual)
+{
+    DevState init; std::memset(&init, 0, sizeof(init));
+    init.status = LPX_RUNNING; init.r = -1; init.q = -1; init.qn = -1; init.phase = dual ? 0 : 2;
+    return init;
+}
+// Continue where another path stopped: pivot count, phase and counters of `at` (a primal run has one phase).
+inline void resume_from(DevState& init, const DevState& at, bool dual)
+{
+    init.iter = at.iter; init.phase = dual ? at.phase : 2;
+    init.fdf_count = at.fdf_count; init.dual_iter = at.dual_iter; init.primal_count = at.primal_count;
+}
+// Iterations a run may need: each one pivots, changes phase or terminates.  Every loop adds the slack of its own poll lag.
+inline long long pivot_budget(const lpx_run_opts* o, bool dual)
+{
+    return dual ? (long long)o->fdf_guard + 2LL * o->max_iter : (long long)o->max_iter;
+}
+// What a finished (or suspended) state record reports; keep_transfers: the one-shot entry points keep their transfer times in s.
+inline void stats_from_state(lpx_stats& s, const DevState& d, bool dual, double loop_ms, long long launches, bool keep_transfers)
+{
+    const double h2d = s.h2d_ms, d2h = s.d2h_ms;
+    std::memset(&s, 0, sizeof(s));
+    if (keep_transfers) { s.h2d_ms = h2d; s.d2h_ms = d2h; }
+    s.pivots = d.iter; s.fdf_pivots = d.fdf_count;
+    s.cleanup_pivots = dual ? d.primal_count : 0;
+    s.loop_ms = loop_ms; s.launches = launches;
+}
+
 // The loop context every tableau loop shares: the handle's stream, records and graph cache, two launches per iteration, a
 // fresh state record.  What differs comes in: the bytes that key the captured graph (the loop's parameter record) and the
 // per-iteration enqueue; prologue and profile mapping follow p.mode.
@@ -113,13 +141,32 @@ void make_ctx(lpx_tableau* t, const SelParams& p, const Params& key, Enqueue enq
     // one profiled update launch = one pivot: not in dual mode (phase hops make the mapping ambiguous) nor in the bounded loop
     // (a launch may hold several events, or none that updates)
     c.profile_maps = lookahead;
-    std::memset(&init, 0, sizeof(init));
-    init.status = LPX_RUNNING; init.r = -1; init.q = -1; init.qn = -1;
-    init.phase = (p.mode == MODE_DUAL) ? 0 : 2;
+    init = fresh_state(p.mode == MODE_DUAL);
 }
 void make_ctx(lpx_tableau* t, const SelParams& p, LoopCtx& c, DevState& init);      // the (select, update) pair of p.mode
 int run_loop(lpx_tableau* t, SelParams p, const lpx_run_opts* o, long long budget,
              lpx_pivot_cb cb, void* user, lpx_stats* stats, int start_iter = 0);
+// One LP handed to its streaming loop at the pivot another path had reached (`at`: the record that path left).
+int continue_streaming(lpx_tableau* t, const lpx_run_opts* o, bool dual, const DevState& at, lpx_pivot_cb cb, void* user, lpx_stats* st);
+
+// Resident runs (lpx_tableau_resident.cpp).  run_resident: the primal loop of one LP with the tableau in LDS; grid / rpw / lds from
+// resident_plan or, col, resident_col_plan.  LPX_RESIDENT_RETRY: the launch was lost, the tableau is the one of its start and the
+// streaming kernels continue at pivot *resume_iter.
+int run_resident(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, void* user, lpx_stats* stats,
+                 int grid, int rpw, size_t lds, int* resume_iter, bool col = false);
+// How a group goes onto the chip: workgroups per node, nodes at a time, LDS per workgroup; nt == 0: rows in LDS
+// (lpx_resident_group), else the configuration of the register-resident kernel (lpx_resident_group_r) and the rows a workgroup
+// may hold.  slots == 0: the group does not fit.
+struct ResGroupPlan { int grid = 0, slots = 0; size_t lds = 0; int nt = 0, rt = 0; };
+ResGroupPlan resident_group_plan(lpx_tableau** ts, int count);
+// LPX_RESIDENT_RETRY: a launch was lost; statuses mark the unfinished nodes LPX_RUNNING and resume[i] is where node i stands.
+int run_resident_group(lpx_tableau** ts, const int* dual, int count, const lpx_run_opts* popts, const lpx_run_opts* dopts,
+                       int* statuses, lpx_stats* stats, const ResGroupPlan& plan, lpx_pivot_cb cb, void* user,
+                       DevState* resume = nullptr);
+// Fused group run (lpx_tableau_groups.cpp): one launch per step for the whole group.  LPX_RESIDENT_RETRY: the group cannot take
+// this path (nothing has been touched then).
+int multi_run_fused(lpx_tableau** ts, const int* dual, int count, const lpx_run_opts* popts, const lpx_run_opts* dopts,
+                    int* statuses, lpx_stats* stats, const DevState* inits, int min_active);
 
 }  // namespace lpx
 #pragma GCC visibility pop

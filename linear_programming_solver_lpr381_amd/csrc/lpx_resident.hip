@@ -23,7 +23,7 @@
 // Every wait is bounded (RS_SPIN_MAX polls); on expiry the workgroup raises the abort flag in the state
 // record and leaves without writing its rows back.  A workgroup that was scheduled late may still have finished a
 // short launch and written its rows, so the host keeps a copy of the tableau as it was when the launch started and
-// puts it back whenever the flag is up (lpx_tableau.cpp, run_resident); the streaming kernels continue from there.
+// puts it back whenever the flag is up (lpx_tableau_resident.cpp, run_resident); the streaming kernels continue from there.
 #include "lpx_resident.h"
 #include <cstdlib>
 
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(RS_NT, 1) void lpx_resident_primal(ResParams P)
     const int t = threadIdx.x, w = blockIdx.x;
     if ((P.mute == 1 || (P.mute == 2 && st->iter > 0)) && w == (int)gridDim.x - 1) return;   // 2: from the second launch on
     // A workgroup that starts after another one of this launch has given up cannot finish either: leave at once (the host
-    // restores the tableau of the launch's start whatever was written back, lpx_tableau.cpp run_resident).
+    // restores the tableau of the launch's start whatever was written back, lpx_tableau_resident.cpp run_resident).
     if (rs_abort_raised(st)) return;
     if (P.mute == 3 && w == (int)gridDim.x - 1) rs_wait_for_abort(st);                        // 3: a LATE workgroup
     const int ld = P.ld, C = P.C, m = P.R - 1, rpw = P.rpw;

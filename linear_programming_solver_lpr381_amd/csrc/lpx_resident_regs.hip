@@ -19,7 +19,7 @@
 //     rows: +1.5 us per step): 26 + 11 rows -> 21 workgroups per node -> TWELVE nodes in flight: 1170-1180 nodes/s (24-26 register rows
 //     alike; 27: 1046, 28: 1024 -- the loop's own registers spill).
 //   and with the update of pivot k DEFERRED into round k+1's wait for the pivot row (template parameter DEFER, the round loop's
-//     comment): +8 % again.  A group of more nodes than the chip holds is ONE launch (lpx_tableau.cpp, run_resident_group): the hardware
+//     comment): +8 % again.  A group of more nodes than the chip holds is ONE launch (lpx_tableau_resident.cpp, run_resident_group): the hardware
 //     starts the next node's workgroups as an earlier node's leave (+11 %: 1.31 k nodes/s on the cold config-4 search).
 // Everything else -- the tagged-granule
 // exchanges, the replicated state machine of the dual path, the lookahead, the bounded waits, the arithmetic per element -- is that of

@@ -1,6 +1,7 @@
-// lpx_tableau.cpp -- device-resident tableau handle (lifecycle, transfers, snapshot) and the host side of the simplex loops:
-// single-LP loops, resident and group runs (C ABI of include/lpx.h).  The bounded-variable family is in lpx_tableau_bounded.cpp,
-// node assembly and the parent store in lpx_tableau_nodes.cpp.  Host code only: kernels live in lpx_kernels.hip (two-launch paths), lpx_pivot_fused.hip and lpx_group_fused.hip.
+// lpx_tableau.cpp -- device-resident tableau handle (lifecycle, transfers, snapshot) and the host side of the single-LP simplex
+// loops (C ABI of include/lpx.h).  The resident runs are in lpx_tableau_resident.cpp, the group runs and lpx_multi_run* in
+// lpx_tableau_groups.cpp, the bounded-variable family in lpx_tableau_bounded.cpp, node assembly and the parent store in
+// lpx_tableau_nodes.cpp.  Host code only: kernels live in lpx_kernels.hip (two-launch paths) and lpx_pivot_fused.hip.
 #include "lpx_handle.h"
 
 #include <cstdlib>
@@ -306,6 +307,17 @@ int lpx::run_loop(lpx_tableau* t, SelParams p, const lpx_run_opts* o, long long 
     return run_device_loop(c, init, o, budget, cb, user, stats);
 }
 
+// init.iter carries the pivot count, so LoopRun numbers callbacks and reads the trace from there; LoopCtx::start_iter has nothing
+// to add (it only acts on a record whose iter is 0, and equals at.iter wherever a caller would set it).
+int lpx::continue_streaming(lpx_tableau* t, const lpx_run_opts* o, bool dual, const DevState& at, lpx_pivot_cb cb, void* user, lpx_stats* st)
+{
+    SelParams p = base_params(t, o, dual ? MODE_DUAL : MODE_PRIMAL);
+    LoopCtx c; DevState init;
+    make_ctx(t, p, c, init);
+    resume_from(init, at, dual);
+    return run_device_loop(c, init, o, pivot_budget(o, dual) + (dual ? 8 : 2), cb, user, st);
+}
+
 SelParams lpx::base_params(lpx_tableau* t, const lpx_run_opts* o, int mode)
 {
     SelParams p; std::memset(&p, 0, sizeof(p));
@@ -319,7 +331,7 @@ SelParams lpx::base_params(lpx_tableau* t, const lpx_run_opts* o, int mode)
     p.ws = t->ws;
     p.rcap = 0;
     static const bool mb_env = [] { const char* e = std::getenv("LPX_SELECT_MB"); return !(e && e[0] == '0'); }();
-    if (mode != MODE_DUAL && mb_env && t->use_mb) {
+    if (mode != MODE_DUAL && mb_env) {
         p.us = t->us; p.part_v = t->part_v; p.part_i = t->part_i; p.nblk = select_mb_blocks(t->Ccap); p.qsel = update_policy(t->ld, t->Rcap) != 0 ? 1 : 0;
     }
     return p;
@@ -409,7 +421,7 @@ static int run_fused(lpx_tableau* t, const SelParams& p, const lpx_run_opts* o, 
     lpx_run_opts oe = *o;
     { const int b = oe.batch > 0 ? oe.batch : 64; oe.batch = (b + 2 * d - 1) / (2 * d) * (2 * d); }
     o = &oe;
-    const int rc = run_device_loop(c, init, o, (long long)o->max_iter + 4, nullptr, nullptr, stats);
+    const int rc = run_device_loop(c, init, o, pivot_budget(o, false) + 4, nullptr, nullptr, stats);
     LPX_HIP_TRY(hipStreamSynchronize(t->stream));
     DevState recs[2];
     LPX_HIP_TRY(hipMemcpy(recs, t->frec, sizeof(recs), hipMemcpyDeviceToHost));
@@ -426,780 +438,8 @@ static int run_fused(lpx_tableau* t, const SelParams& p, const lpx_run_opts* o, 
     return rc;
 }
 
-// Exchange buffers of the resident kernels (sized for both of them) and the basis snapshot, allocated on first use.
-static size_t xr_bytes(const lpx_tableau* t) { return sizeof(unsigned long long) * 8 * (size_t)t->Rcap; }
-static size_t xp_bytes(const lpx_tableau* t) { return sizeof(unsigned long long) * (4 * ((size_t)t->ld + 8) + 64); }   // + diagnostic stamps
-static int resident_buffers(lpx_tableau* t)
-{
-    if (t->xr) return 0;
-    LPX_HIP_TRY(hipMalloc((void**)&t->xr, xr_bytes(t)));
-    LPX_HIP_TRY(hipMalloc((void**)&t->xp, xp_bytes(t)));
-    LPX_HIP_TRY(hipMalloc((void**)&t->xgen, sizeof(unsigned)));
-    LPX_HIP_TRY(hipMalloc((void**)&t->xbasis, sizeof(int32_t) * (size_t)t->Rcap));
-    LPX_HIP_TRY(malloc_retry((void**)&t->xT, sizeof(double) * (size_t)t->Rcap * t->ld));
-    LPX_HIP_TRY(hipMemsetAsync(t->xr, 0, xr_bytes(t), t->stream));
-    LPX_HIP_TRY(hipMemsetAsync(t->xp, 0, xp_bytes(t), t->stream));
-    LPX_HIP_TRY(hipMemsetAsync(t->xgen, 0, sizeof(unsigned), t->stream));
-    return 0;
-}
-// exchange buffers of the column-owning kernel, sized for the handle's capacity and every grid up to the CU count
-static int resident_col_buffers(lpx_tableau* t, int grid)
-{
-    const size_t xcb = resident_col_xc_bytes(grid > 256 ? grid : 256), xqb = resident_col_xq_bytes(grid > 256 ? grid : 256, t->Rcap);
-    if (t->xc && t->xc_bytes >= xcb && t->xq_bytes >= xqb) return 0;
-    hipFree(t->xc); hipFree(t->xq); t->xc = nullptr; t->xq = nullptr;
-    LPX_HIP_TRY(hipMalloc((void**)&t->xc, xcb));
-    LPX_HIP_TRY(hipMalloc((void**)&t->xq, xqb));
-    t->xc_bytes = xcb; t->xq_bytes = xqb;
-    LPX_HIP_TRY(hipMemsetAsync(t->xc, 0, xcb, t->stream));
-    LPX_HIP_TRY(hipMemsetAsync(t->xq, 0, xqb, t->stream));
-    return 0;
-}
-static void resident_buffers_clear(lpx_tableau* t)
-{
-    if (t->xc) { hipMemsetAsync(t->xc, 0, t->xc_bytes, t->stream); hipMemsetAsync(t->xq, 0, t->xq_bytes, t->stream); }
-    hipMemsetAsync(t->xr, 0, xr_bytes(t), t->stream);
-    hipMemsetAsync(t->xp, 0, xp_bytes(t), t->stream);
-    hipStreamSynchronize(t->stream);
-}
-
-// Resident primal loop: one launch runs up to `chunk` pivots with the tableau in LDS; the host only polls the
-// 64-byte state record between launches (and fires the pivot callbacks from the trace).
-// col: the column-owning kernel (lpx_resident_col.hip; grid / cpw / lds from resident_col_plan), else the row-owning one
-int run_resident(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, void* user, lpx_stats* stats,
-                 int grid, int rpw, size_t lds, int* resume_iter, bool col = false)
-{
-    const int mcap = t->Rcap;
-    { int rc = resident_buffers(t); if (rc) return rc; }
-    if (col) { int rc = resident_col_buffers(t, grid); if (rc) return rc; }
-    DevState init; std::memset(&init, 0, sizeof(init));
-    init.status = LPX_RUNNING; init.r = -1; init.q = -1; init.qn = -1; init.phase = 2;
-    *t->hst = init;
-    LPX_HIP_TRY(hipMemcpyAsync(t->st, t->hst, sizeof(DevState), hipMemcpyHostToDevice, t->stream));
-    const int chunk = cb ? (o->batch > 0 ? o->batch : 256) : (1 << 30);
-    lpx_stats local; std::memset(&local, 0, sizeof(local));
-    const double t0 = now_ms();
-    int fired = 0, status = LPX_RUNNING;
-    for (long long launches = 0; status == LPX_RUNNING; ++launches) {
-        if (launches > (long long)o->max_iter + 4) { set_error("resident loop: launch budget exhausted while still running"); return LPX_ITER_LIMIT; }
-        // Tableau and basis as of the start of this launch.  A launch that cannot finish normally writes nothing back, but
-        // a workgroup that was scheduled late (after the others gave up) may complete a short launch and store its rows:
-        // whenever the abort flag is up the host puts this copy back, so the hand-over never sees a half-pivoted tableau.
-        LPX_HIP_TRY(hipMemcpyAsync(t->xbasis, t->basis, sizeof(int32_t) * (size_t)(t->R - 1), hipMemcpyDeviceToDevice, t->stream));
-        LPX_HIP_TRY(hipMemcpyAsync(t->xT, t->T, sizeof(double) * (size_t)t->R * t->ld, hipMemcpyDeviceToDevice, t->stream));
-        if (o->profile) {
-            while (t->events.size() < 2) { hipEvent_t e; LPX_HIP_TRY(hipEventCreate(&e)); t->events.push_back(e); }
-            LPX_HIP_TRY(hipEventRecord(t->events[0], t->stream));
-        }
-        if (col)
-            LPX_HIP_TRY(launch_resident_primal_col(t->T, t->ld, t->R, t->C, grid, rpw, lds, t->basis, t->trace, t->trace_cap,
-                                                   t->st, t->xc, t->xq, t->xgen, o->eps, o->ratio_tol, o->max_iter, chunk, t->stream));
-        else
-        LPX_HIP_TRY(launch_resident_primal(t->T, t->ld, t->R, t->C, grid, rpw, lds, mcap, t->basis, t->trace, t->trace_cap,
-                                           t->st, t->xr, t->xp, t->xgen, o->eps, o->ratio_tol, o->max_iter, chunk, t->stream));
-        if (o->profile) LPX_HIP_TRY(hipEventRecord(t->events[1], t->stream));
-        local.launches++;
-        LPX_HIP_TRY(hipMemcpyAsync(t->hst, t->st, sizeof(DevState), hipMemcpyDeviceToHost, t->stream));
-        LPX_HIP_TRY(hipStreamSynchronize(t->stream));
-        if (o->profile) {       // HIP events on the library stream around the persistent kernel: its duration
-            float ms = 0.f;
-            LPX_HIP_TRY(hipEventElapsedTime(&ms, t->events[0], t->events[1]));
-            local.update_ms_sum += ms;
-            local.update_launches++;
-        }
-        if (t->hst->pad[1]) {
-            // a bounded wait expired: some workgroup was not resident or died; rows in HBM are those of the last
-            // completed launch.  Clear the exchange buffers so that no stale generation can ever match.
-            resident_buffers_clear(t);
-            set_error("resident loop: an exchange wait expired (workgroups not co-resident?)");
-            // Put the tableau and the basis of the launch's start back (late workgroups may have stored rows of a
-            // pivot the others never made) and hand over to the streaming kernels, which continue from pivot
-            // `resume_iter`.
-            LPX_HIP_TRY(hipMemcpy(t->T, t->xT, sizeof(double) * (size_t)t->R * t->ld, hipMemcpyDeviceToDevice));
-            LPX_HIP_TRY(hipMemcpy(t->basis, t->xbasis, sizeof(int32_t) * (size_t)(t->R - 1), hipMemcpyDeviceToDevice));
-            t->resident_off = true;
-            *resume_iter = fired;
-            return LPX_RESIDENT_RETRY;
-        }
-        status = t->hst->status;
-        const int done = t->hst->iter;
-        if (cb && done > fired) {
-            const int lo = fired, hi = done < t->trace_cap ? done : t->trace_cap;
-            if (hi > lo) {
-                std::vector<int32_t> tr(2 * (size_t)(hi - lo));
-                LPX_HIP_TRY(hipMemcpy(tr.data(), t->trace + 2 * lo, sizeof(int32_t) * 2 * (hi - lo), hipMemcpyDeviceToHost));
-                for (int k = lo; k < hi; ++k) cb(user, k + 1, tr[2 * (k - lo)], tr[2 * (k - lo) + 1]);
-            }
-        }
-        fired = done;
-    }
-    local.loop_ms = now_ms() - t0;
-    local.pivots = t->hst->iter;
-    if (stats) { const double h2d = stats->h2d_ms, d2h = stats->d2h_ms; *stats = local; stats->h2d_ms = h2d; stats->d2h_ms = d2h; }
-    return status;
-}
-
-// Resident group run: the nodes of a batch are solved a few at a time, each resident in the LDS of its own slice
-// of the chip (lpx_resident_group.hip).  Launches are `chunk` pivots long; after each one finished nodes leave and
-// waiting ones take their place, so the slices stay busy until the batch is done.
-struct ResGroupBuf { ResNode* d = nullptr; ResNode* h = nullptr; DevState* hs = nullptr; int cap = 0; hipStream_t stream = nullptr;
-                     ParkDesc* pd_d = nullptr; ParkDesc* pd_h = nullptr; };   // pd: descriptors of the snapshot copies (one launch for a whole group)
-ResGroupBuf g_resgroup;
-
-// which kernel the last resident_group_plan chose: 0 = rows in LDS (lpx_resident_group), else the workgroup size of the
-// register-resident variant (lpx_resident_group_r); read by run_resident_group right after (handles are used from one thread)
-static thread_local int tl_plan_nt = 0, tl_plan_rt = 0;     // register-resident kernel: configuration, rows a workgroup may hold
-
-// The register-resident variant (node rows in VGPRs): more nodes per launch when a node is wide enough to need many CUs' LDS.
-// Returns the nodes per launch it would give (0 = not applicable) and fills grid / lds / nt.
-static int resident_regs_plan(lpx_tableau** ts, int count, int cus, int* grid, size_t* lds, int* nt, int* rt)
-{
-    static const bool enabled = [] { const char* e = std::getenv("LPX_RESIDENT_REGS"); return !(e && e[0] == '0'); }();
-    if (!enabled) return 0;
-    int maxC = 2, mmax = 1, mmin = 1 << 30, min_ld = 1 << 30;
-    for (int i = 0; i < count; ++i) { maxC = std::max(maxC, ts[i]->C); mmax = std::max(mmax, ts[i]->R - 1); mmin = std::min(mmin, ts[i]->R - 1); min_ld = std::min(min_ld, ts[i]->ld); }
-    int rpw_max = 0;
-    const int n = resident_regs_shape(maxC, min_ld, mmax, &rpw_max); // the kernel configuration
-    if (!n) return 0;
-    int g = (mmax + rpw_max - 1) / rpw_max;                 // workgroups per node: every node's rows per workgroup <= rpw_max
-    if (g > mmin || g > cus) return 0;
-    { const int rpw = (mmax + g - 1) / g; g = (mmax + rpw - 1) / rpw; }          // no idle workgroups for the tallest node
-    size_t need = 0;
-    for (int i = 0; i < count; ++i) need = std::max(need, resident_regs_lds(ts[i]->R, ts[i]->C, rpw_max, n));
-    if (need > resident_regs_lds_budget()) return 0;
-    *grid = g; *lds = need; *nt = n; *rt = rpw_max;
-    return cus / g;
-}
-
-int resident_group_plan(lpx_tableau** ts, int count, int* grid, int* slots, size_t* lds)
-{
-    tl_plan_nt = 0;
-    hipDeviceProp_t prop; int dev = 0;
-    static int cus = 0;
-    if (!cus) { if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0; cus = prop.multiProcessorCount; }
-    const size_t lds_max = 160 * 1024 - 1024;
-    // As many nodes per launch as fit: a node takes cus / n workgroups, down to ONE (small node LPs: 240 of them side by side,
-    // each in the LDS of one CU).  r01 / early r02 stopped at 8 nodes per launch; a 60-variable 0/1 program went from 7.2 k to
-    // 21 k nodes/s when the limit fell (tools/probe_slots.py), node logs and pivot counts unchanged.  LPX_GROUP_SLOTS caps it.
-    static const int max_slots = [] { const char* e = std::getenv("LPX_GROUP_SLOTS"); const int v = e ? std::atoi(e) : 0; return v > 0 ? v : 1 << 20; }();
-    // (never more nodes than CUs: a node needs at least one workgroup -- a group of more than 256 nodes divided by zero here before r03)
-    for (int n = std::min(std::min(count, max_slots), cus); n >= 1; --n) {
-        int g = cus / n;
-        size_t need = 0;
-        for (int i = 0; i < count; ++i) {
-            const int m = ts[i]->R - 1;
-            const int gi = g < m ? g : m;
-            const size_t b = resident_group_lds(ts[i]->R, ts[i]->C, ts[i]->ld, gi);
-            if (b > need) need = b;
-        }
-        int mmin = 1 << 30;
-        for (int i = 0; i < count; ++i) if (ts[i]->R - 1 < mmin) mmin = ts[i]->R - 1;
-        if (g > mmin) g = mmin;                       // at most one workgroup per row of the smallest node
-        if (g < 1) continue;
-        {   // no idle workgroups: the fewest that keep the same rows-per-workgroup for the tallest node
-            int mmax = 1;
-            for (int i = 0; i < count; ++i) if (ts[i]->R - 1 > mmax) mmax = ts[i]->R - 1;
-            const int rpw = (mmax + g - 1) / g;
-            g = (mmax + rpw - 1) / rpw;
-        }
-        need = 0;
-        for (int i = 0; i < count; ++i) { const size_t b = resident_group_lds(ts[i]->R, ts[i]->C, ts[i]->ld, g); if (b > need) need = b; }
-        if (need <= lds_max) {
-            *grid = g; *slots = n; *lds = need;
-            // rows in registers instead, when that puts more nodes on the chip at once (and there are enough nodes to use them)
-            int rg = 0, rnt = 0, rrt = 0; size_t rlds = 0;
-            const int rslots = resident_regs_plan(ts, count, cus, &rg, &rlds, &rnt, &rrt);
-            static const bool force_regs = [] { const char* e = std::getenv("LPX_RESIDENT_REGS"); return e && e[0] == '2'; }();   // diagnostic: whenever it applies
-            if (rslots >= 1 && (force_regs || (rslots > n && count > n))) { *grid = rg; *slots = std::min(rslots, std::min(count, max_slots)); *lds = rlds; tl_plan_nt = rnt; tl_plan_rt = rrt; }
-            return 1;
-        }
-    }
-    {   // nothing fits the LDS form: the register form alone
-        int rg = 0, rnt = 0, rrt = 0; size_t rlds = 0;
-        const int rslots = resident_regs_plan(ts, count, cus, &rg, &rlds, &rnt, &rrt);
-        if (rslots >= 1) { *grid = rg; *slots = std::min(rslots, std::min(count, max_slots)); *lds = rlds; tl_plan_nt = rnt; tl_plan_rt = rrt; return 1; }
-    }
-    return 0;
-}
-
-int run_resident_group(lpx_tableau** ts, const int* dual, int count, const lpx_run_opts* popts, const lpx_run_opts* dopts,
-                       int* statuses, lpx_stats* stats, int grid, int slots, size_t lds, lpx_pivot_cb cb, void* user,
-                       DevState* resume = nullptr)
-{
-    ResGroupBuf& g = g_resgroup;
-    const int plan_nt = tl_plan_nt, plan_rt = tl_plan_rt;   // 0: rows in LDS; else the configuration of the register-resident kernel
-    if (!g.stream) LPX_HIP_TRY(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
-    if (g.cap < count) {
-        hipFree(g.d); if (g.h) hipHostFree(g.h); if (g.hs) hipHostFree(g.hs);
-        hipFree(g.pd_d); if (g.pd_h) hipHostFree(g.pd_h);
-        g.d = nullptr; g.h = nullptr; g.hs = nullptr; g.pd_d = nullptr; g.pd_h = nullptr; g.cap = 0;
-        const int c = count + 16;
-        LPX_HIP_TRY(hipMalloc((void**)&g.d, sizeof(ResNode) * c));
-        LPX_HIP_TRY(hipHostMalloc((void**)&g.h, sizeof(ResNode) * c));
-        LPX_HIP_TRY(hipHostMalloc((void**)&g.hs, sizeof(DevState) * c));
-        LPX_HIP_TRY(hipMalloc((void**)&g.pd_d, sizeof(ParkDesc) * c));
-        LPX_HIP_TRY(hipHostMalloc((void**)&g.pd_h, sizeof(ParkDesc) * c));
-        g.cap = c;
-    }
-    const double t0 = now_ms();
-    std::vector<ResNode> node(count);
-    // Per-node host work adds up when a group is a whole B&B level (8000 warm-started nodes: 0.24 s of stream waits, state uploads and
-    // snapshot copies in front of 0.3 s of kernel): every distinct stream is waited for once, the state records go up in one launch,
-    // the snapshots of a launch are one multi-copy launch.
-    std::vector<hipStream_t> waited;
-    auto wait_once = [&](hipStream_t st) -> int {
-        for (hipStream_t w : waited) if (w == st) return 0;
-        LPX_HIP_TRY(hipStreamSynchronize(st));
-        waited.push_back(st);
-        return 0;
-    };
-    for (int i = 0; i < count; ++i) {
-        lpx_tableau* t = ts[i];
-        { int rc = wait_once(t->stream); if (rc) return rc; }          // node assembly ran on the node's own stream
-        if (!t->xr) {
-            { int rc = resident_buffers(t); if (rc) return rc; }
-            LPX_HIP_TRY(hipStreamSynchronize(t->stream));
-        }
-        const lpx_run_opts* o = dual[i] ? dopts : popts;
-        ResNode& n = node[i];
-        n.T = t->T; n.ld = t->ld; n.R = t->R; n.C = t->C; n.basis = t->basis; n.trace = t->trace; n.trace_cap = t->trace_cap;
-        n.st = t->st; n.xr = t->xr; n.xp = t->xp; n.xgen = t->xgen; n.mcap = t->Rcap; n.dual = dual[i] ? 1 : 0;
-        n.eps = o->eps; n.tol_fdf = o->ratio_tol; n.tol_dual = o->ratio_tol; n.tol_primal = dual[i] ? o->eps : o->ratio_tol;
-        n.max_iter = o->max_iter; n.fdf_guard = o->fdf_guard; n.cleanup = o->cleanup;
-        DevState init; std::memset(&init, 0, sizeof(init));
-        init.status = LPX_RUNNING; init.r = -1; init.q = -1; init.qn = -1; init.phase = dual[i] ? 0 : 2;
-        g.hs[i] = init;
-        n.st_host = &g.hs[i];
-    }
-    // every node's initial state record: one launch reading the pinned array (node i <-> g.hs[i])
-    std::memcpy(g.h, node.data(), sizeof(ResNode) * (size_t)count);
-    LPX_HIP_TRY(hipMemcpyAsync(g.d, g.h, sizeof(ResNode) * (size_t)count, hipMemcpyHostToDevice, g.stream));
-    LPX_HIP_TRY(launch_resnode_states_scatter(g.d, g.hs, count, g.stream));
-    LPX_HIP_TRY(hipStreamSynchronize(g.stream));                        // g.h / g.d are rewritten per launch below
-    // launch length: long enough to hide the launch + reload (~30 us), short enough that a node finishing inside a
-    // launch does not leave its slice idle for long
-    const lpx_run_opts* o0 = dual[0] ? dopts : popts;
-    static const int chunk_env = [] { const char* e = std::getenv("LPX_GROUP_CHUNK"); return e ? std::atoi(e) : 0; }();   // diagnostic
-    // A group larger than the chip holds at a time goes out as ONE launch all the same (r03): the hardware hands workgroups to compute
-    // units in launch order, so the workgroups of node `slots` + k start as those of an earlier node leave -- a finished node's
-    // successor starts at once instead of at the next launch boundary, where the chip used to wait for the host (9 % of the cold
-    // config-4 search) and for the slowest node of the launch (6 %).  The earliest incomplete node is first in line for every unit
-    // that frees up, so it always completes its set; its early workgroups poll meanwhile (bounded waits of ~0.6 s against node
-    // run times of milliseconds).  LPX_GROUP_WALK=0: launches of `slots` nodes and 96 pivots, refilled by the host in between.
-    static const bool walk_env = [] { const char* e = std::getenv("LPX_GROUP_WALK"); return !(e && e[0] == '0'); }();
-    const bool walk = walk_env && cb == nullptr && count > slots;
-    const int chunk = cb ? (o0->batch > 0 ? o0->batch : 256) : (walk ? (1 << 20) : (count > slots ? (chunk_env > 0 ? chunk_env : 96) : 1024));
-    std::vector<int> live(count);
-    for (int i = 0; i < count; ++i) live[i] = i;
-    std::vector<int> fired(count, 0);
-    std::vector<DevState> before(count);
-    std::vector<char> snapped(count, 0);
-    // What an aborted launch goes back to: with a pivot callback the state at the START OF THAT LAUNCH (the callbacks of the
-    // earlier launches have fired), snapshot per launch; without one (B&B batches) the node's state at its FIRST launch --
-    // one snapshot per node instead of one per launch (a node of config 4 takes eight launches), the rare restart repeats
-    // the node's pivots on the streaming kernels and ends in the same tableau.
-    const bool snap_each_launch = cb != nullptr;
-    long long launches = 0;
-    while (!live.empty()) {
-        const int n = walk ? (int)std::min<size_t>(live.size(), 65535) : ((int)live.size() < slots ? (int)live.size() : slots);   // gridDim.y <= 65535
-        int nsnap = 0; size_t maxd = 2;
-        for (int k = 0; k < n; ++k) {
-            g.h[k] = node[live[k]];
-            lpx_tableau* t = ts[live[k]];
-            if (snap_each_launch || !snapped[live[k]]) {
-                before[live[k]] = g.hs[live[k]];
-                ParkDesc& d = g.pd_h[nsnap++];
-                d.srcT = t->T; d.dstT = t->xT; d.srcB = t->basis; d.dstB = t->xbasis;
-                d.doubles = (size_t)t->R * t->ld; d.m = t->R - 1; d.pad = 0;
-                maxd = std::max(maxd, d.doubles);
-                snapped[live[k]] = 1;
-            }
-        }
-        if (nsnap > 0) {                        // the snapshots of this launch: one multi-copy launch (lpx_park_many)
-            LPX_HIP_TRY(hipMemcpyAsync(g.pd_d, g.pd_h, sizeof(ParkDesc) * (size_t)nsnap, hipMemcpyHostToDevice, g.stream));
-            const int bpn = (int)std::min<size_t>(256, std::max<size_t>(1, maxd / 2 / 256 / 4));
-            LPX_HIP_TRY(launch_park_many(g.pd_d, nsnap, bpn, g.stream));
-        }
-        // the kernel writes each node's new state into the pinned mirror (ResNode::st_host): nothing is copied back
-        LPX_HIP_TRY(hipMemcpyAsync(g.d, g.h, sizeof(ResNode) * n, hipMemcpyHostToDevice, g.stream));
-        if (plan_nt) LPX_HIP_TRY(launch_resident_regs(g.d, n, grid, plan_nt, plan_rt, lds, chunk, g.stream));
-        else LPX_HIP_TRY(launch_resident_group(g.d, n, grid, lds, chunk, g.stream));
-        LPX_HIP_TRY(hipStreamSynchronize(g.stream));
-        bool aborted = false;
-        for (int k = 0; k < n; ++k) if (g.hs[live[k]].pad[1]) aborted = true;
-        if (aborted) {
-            for (int k = 0; k < n; ++k) resident_buffers_clear(ts[live[k]]);
-            set_error("resident group loop: an exchange wait expired (workgroups not co-resident?)");
-            // A node whose launch aborted goes back to the state of the launch's start (tableau, basis, counters: a late
-            // workgroup may have stored rows of a pivot the others never made); the other nodes of the launch finished it
-            // normally and keep what they wrote.  The caller finishes every unfinished node on the streaming kernels.
-            for (int k = 0; k < n; ++k) {
-                if (!g.hs[live[k]].pad[1]) continue;
-                lpx_tableau* t = ts[live[k]];
-                LPX_HIP_TRY(hipMemcpy(t->T, t->xT, sizeof(double) * (size_t)t->R * t->ld, hipMemcpyDeviceToDevice));
-                LPX_HIP_TRY(hipMemcpy(t->basis, t->xbasis, sizeof(int32_t) * (size_t)(t->R - 1), hipMemcpyDeviceToDevice));
-                g.hs[live[k]] = before[live[k]];
-                g.hs[live[k]].pad[1] = 0;
-                LPX_HIP_TRY(hipMemcpy(t->st, &g.hs[live[k]], sizeof(DevState), hipMemcpyHostToDevice));
-            }
-            for (int i = 0; i < count; ++i) statuses[i] = g.hs[i].status;      // LPX_RUNNING marks the unfinished ones
-            if (resume) std::memcpy(resume, g.hs, sizeof(DevState) * count);
-            return LPX_RESIDENT_RETRY;
-        }
-        ++launches;
-        if (launches > 4LL * count * ((long long)popts->max_iter + dopts->max_iter + dopts->fdf_guard) / chunk + 64) {
-            set_error("resident group loop: launch budget exhausted while still running"); return LPX_ITER_LIMIT; }
-        std::vector<int> next;
-        for (int k = 0; k < n; ++k) {
-            const int i = live[k];
-            const DevState& s = g.hs[i];
-            if (cb && s.iter > fired[i]) {
-                lpx_tableau* t = ts[i];
-                const int lo = fired[i], hi = s.iter < t->trace_cap ? s.iter : t->trace_cap;
-                if (hi > lo) {
-                    std::vector<int32_t> tr(2 * (size_t)(hi - lo));
-                    LPX_HIP_TRY(hipMemcpy(tr.data(), t->trace + 2 * lo, sizeof(int32_t) * 2 * (hi - lo), hipMemcpyDeviceToHost));
-                    for (int z = lo; z < hi; ++z) cb(user, z + 1, tr[2 * (z - lo)], tr[2 * (z - lo) + 1]);
-                }
-                fired[i] = s.iter;
-            }
-            if (s.status == LPX_RUNNING) next.push_back(i);
-        }
-        for (size_t k = (size_t)n; k < live.size(); ++k) next.push_back(live[k]);
-        live.swap(next);
-    }
-    const double ms = now_ms() - t0;
-    for (int i = 0; i < count; ++i) {
-        const DevState& s = g.hs[i];
-        *ts[i]->hst = s;
-        statuses[i] = s.status;
-        if (stats) {
-            std::memset(&stats[i], 0, sizeof(lpx_stats));
-            stats[i].pivots = s.iter; stats[i].fdf_pivots = s.fdf_count;
-            stats[i].cleanup_pivots = dual[i] ? s.primal_count : 0;
-            stats[i].loop_ms = ms / (double)count;
-            stats[i].launches = launches;
-        }
-    }
-    return 0;
-}
 
 }  // namespace
-
-// ---------------------------------------------------------------------------------------------------
-// Batched group run (K9): all tableaux of a group advance one pivot per launch pair (blockIdx.y = node),
-// so many small node LPs fill the chip from ONE stream instead of competing for a few hardware queues.
-// ---------------------------------------------------------------------------------------------------
-namespace {
-
-struct GroupBuf {
-    SelParams* d = nullptr; SelParams* h = nullptr; DevState* hs = nullptr; int cap = 0;
-    hipStream_t stream = nullptr;
-    hipGraphExec_t gexec = nullptr; std::string gkey;
-};
-GroupBuf g_groups[2];        // [primal, dual]; lpx handles are used from one thread per process
-
-int group_reserve(GroupBuf& g, int count)
-{
-    if (!g.stream) LPX_HIP_TRY(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
-    if (count <= g.cap) return 0;
-    if (g.gexec) { hipGraphExecDestroy(g.gexec); g.gexec = nullptr; g.gkey.clear(); }
-    hipFree(g.d); if (g.h) hipHostFree(g.h); if (g.hs) hipHostFree(g.hs);
-    g.d = nullptr; g.h = nullptr; g.hs = nullptr; g.cap = 0;
-    const int c = count + 16;
-    LPX_HIP_TRY(hipMalloc((void**)&g.d, sizeof(SelParams) * c));
-    LPX_HIP_TRY(hipHostMalloc((void**)&g.h, sizeof(SelParams) * c));
-    LPX_HIP_TRY(hipHostMalloc((void**)&g.hs, sizeof(DevState) * c));
-    g.cap = c;
-    return 0;
-}
-
-struct GroupRun {
-    GroupBuf* g = nullptr; std::vector<int> idx; int dual = 0; int batch = 64; long long budget = 0, enq = 0;
-    int max_nblk = 1, max_blocks = 1, maxR = 2, maxC = 2; bool done = true;
-    int min_active = 0; bool suspended_exit = false;     // stop (without exhausting the budget) once this few nodes are still running
-};
-
-int group_begin(GroupRun& r, lpx_tableau** ts, const lpx_run_opts* o, const DevState* inits = nullptr)
-{
-    GroupBuf& g = *r.g;
-    const int K = (int)r.idx.size();
-    int rc = group_reserve(g, K); if (rc) return rc;
-    r.batch = o->batch > 0 ? o->batch : 64;
-    r.budget = r.dual ? (long long)o->fdf_guard + 2LL * o->max_iter + 8 : (long long)o->max_iter + 2;
-    r.max_nblk = 1; r.max_blocks = 1; r.maxR = 2; r.maxC = 2;
-    for (int k = 0; k < K; ++k) {
-        lpx_tableau* t = ts[r.idx[k]];
-        LPX_HIP_TRY(hipStreamSynchronize(t->stream));               // node assembly ran on the node's own stream
-        SelParams p = base_params(t, o, r.dual ? MODE_DUAL : MODE_PRIMAL);
-        if (!r.dual && !p.us) { set_error("batched primal run needs the multi-workgroup select"); return LPX_EINVAL; }
-        g.h[k] = p;
-        if (p.nblk > r.max_nblk) r.max_nblk = p.nblk;
-        const int ub = update_blocks(t->ld, t->Rcap);
-        if (ub > r.max_blocks) r.max_blocks = ub;
-        if (t->Rcap > r.maxR) r.maxR = t->Rcap;
-        if (t->Ccap > r.maxC) r.maxC = t->Ccap;
-        DevState init; std::memset(&init, 0, sizeof(init));
-        init.status = LPX_RUNNING; init.r = -1; init.q = -1; init.qn = -1; init.phase = r.dual ? 0 : 2;
-        if (inits) {                                // continue where another path stopped (pivot count, phase, counters)
-            const DevState& s0 = inits[r.idx[k]];
-            init.iter = s0.iter; init.phase = r.dual ? s0.phase : 2;
-            init.fdf_count = s0.fdf_count; init.dual_iter = s0.dual_iter; init.primal_count = s0.primal_count;
-        }
-        g.hs[k] = init;
-    }
-    LPX_HIP_TRY(hipMemcpyAsync(g.d, g.h, sizeof(SelParams) * K, hipMemcpyHostToDevice, g.stream));
-    LPX_HIP_TRY(launch_states_scatter(g.d, g.hs, K, g.stream));      // every node's initial state record, one launch
-    if (!r.dual) LPX_HIP_TRY(launch_group_init(g.d, K, g.stream));
-    else LPX_HIP_TRY(launch_group_rhs_init(g.d, K, g.stream));
-    // graph of `batch` iterations, keyed by everything baked into the launches
-    char keybuf[160];
-    std::snprintf(keybuf, sizeof(keybuf), "%p/%d/%d/%d/%d/%d/%d/%d", (void*)g.d, K, r.dual, r.max_nblk, r.max_blocks, r.batch, r.maxR, r.maxC);
-    if (o->use_graph && g.gkey != keybuf) {
-        if (g.gexec) { hipGraphExecDestroy(g.gexec); g.gexec = nullptr; }
-        LPX_HIP_TRY(hipStreamSynchronize(g.stream));
-        hipGraph_t graph = nullptr;
-        LPX_HIP_TRY(hipStreamBeginCapture(g.stream, hipStreamCaptureModeThreadLocal));
-        for (int i = 0; i < r.batch; ++i) {
-            hipError_t e = launch_group_iter(g.d, K, r.dual, r.max_nblk, r.max_blocks, g.stream, r.maxR, r.maxC);
-            if (e != hipSuccess) { hipStreamEndCapture(g.stream, &graph); if (graph) hipGraphDestroy(graph); set_error("group capture failed"); return LPX_EDEVICE; }
-        }
-        LPX_HIP_TRY(hipStreamEndCapture(g.stream, &graph));
-        hipError_t e = hipGraphInstantiate(&g.gexec, graph, nullptr, nullptr, 0);
-        hipGraphDestroy(graph);
-        if (e != hipSuccess) { g.gexec = nullptr; set_error("group graph instantiate failed"); return LPX_EDEVICE; }
-        g.gkey = keybuf;
-    }
-    r.enq = 0; r.done = false;
-    return 0;
-}
-
-int group_submit(GroupRun& r, lpx_tableau** ts, const lpx_run_opts* o)
-{
-    GroupBuf& g = *r.g;
-    const int K = (int)r.idx.size();
-    if (o->use_graph && g.gexec) LPX_HIP_TRY(hipGraphLaunch(g.gexec, g.stream));
-    else for (int i = 0; i < r.batch; ++i) LPX_HIP_TRY(launch_group_iter(g.d, K, r.dual, r.max_nblk, r.max_blocks, g.stream, r.maxR, r.maxC));
-    r.enq += r.batch;
-    (void)ts;
-    LPX_HIP_TRY(launch_states_gather(g.d, g.hs, K, g.stream));       // every node's state record into the pinned array, one launch
-    return 0;
-}
-
-int group_complete(GroupRun& r)
-{
-    GroupBuf& g = *r.g;
-    LPX_HIP_TRY(hipStreamSynchronize(g.stream));
-    int running = 0;
-    for (size_t k = 0; k < r.idx.size(); ++k) if (g.hs[k].status == LPX_RUNNING) ++running;
-    r.done = running == 0 || r.enq >= r.budget;
-    if (!r.done && r.min_active > 0 && running <= r.min_active) { r.done = true; r.suspended_exit = true; }
-    return 0;
-}
-
-}  // namespace
-
-// ---------------------------------------------------------------------------------------------------
-// Fused group run (K4g, lpx_group_fused): ONE launch per step for the whole group -- update(k) of every live node out of place
-// beside select(k+1) of every live node -- and a live list instead of early-exit workgroups: between polls the host drops the
-// finished nodes from the grid.  Launches are eager (a launch costs the host ~5 us against a step of tens of microseconds on
-// the device, and the grid changes from poll to poll).  Every node needs its second tableau buffer (fused_buffers); a group in
-// which one does not get it runs on the two-launch kernels below.  LPX_GROUP_FUSED=0: never (diagnostic).
-// ---------------------------------------------------------------------------------------------------
-namespace {
-
-struct FusedGroupBuf {
-    FusedParams* d = nullptr; FusedParams* h = nullptr;     // parameter records: device / pinned
-    DevState* hs = nullptr;                                  // pinned: initial states in, latest records out
-    DevState* ds = nullptr;                                  // device copy of the initial states
-    int* live_d = nullptr; int* live_h = nullptr;            // live list (two halves: launches of window w read half w & 1)
-    int* comp_d = nullptr; int* comp_h = nullptr;            // device-side compaction record (lpx_group_fused.hip FG_COMP_*) and its pinned staging
-    int* fresh_d = nullptr; int* fresh_h = nullptr;
-    int* cur_h = nullptr;                                    // pinned: index of every node's latest record
-    int cap = 0;
-    hipStream_t stream = nullptr;
-    std::vector<hipEvent_t> ev;
-};
-
-static constexpr int kAsyncSlots = 4;           // rolling batches a host may keep in flight (lpx_multi_run_begin / _end)
-extern FusedGroupBuf g_fgroups[kAsyncSlots + 1];
-int fused_group_reserve(FusedGroupBuf& g, int count)
-{
-    static const bool one_stream = [] { const char* e = std::getenv("LPX_ROLL_ONE_STREAM"); return e && e[0] == '1'; }();   // experiment
-    if (!g.stream && one_stream && &g >= &g_fgroups[0] && &g < &g_fgroups[kAsyncSlots])
-        for (int k = 0; k < kAsyncSlots && !g.stream; ++k) if (g_fgroups[k].stream) g.stream = g_fgroups[k].stream;
-    if (!g.stream) {
-        // LOWEST priority: a window is a dozen chip-filling launches in a row; the small launches the host needs answered while the
-        // other batch pivots (solution read-back, parking, child assembly: other streams, default priority) must get their
-        // workgroups in as slots free up instead of queueing behind the window (measured: they waited 1-2 ms each without this)
-        int least = 0, greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { (void)hipGetLastError(); least = 0; }
-        if (hipStreamCreateWithPriority(&g.stream, hipStreamNonBlocking, least) != hipSuccess) {
-            (void)hipGetLastError();
-            LPX_HIP_TRY(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
-        }
-    }
-    if (count <= g.cap) return 0;
-    hipFree(g.d); hipFree(g.ds); hipFree(g.live_d); hipFree(g.fresh_d); hipFree(g.comp_d);
-    if (g.comp_h) hipHostFree(g.comp_h);
-    if (g.h) hipHostFree(g.h); if (g.hs) hipHostFree(g.hs); if (g.live_h) hipHostFree(g.live_h);
-    if (g.fresh_h) hipHostFree(g.fresh_h); if (g.cur_h) hipHostFree(g.cur_h);
-    { hipStream_t st = g.stream; std::vector<hipEvent_t> ev = std::move(g.ev); g = FusedGroupBuf{}; g.stream = st; g.ev = std::move(ev); }
-    const int c = count + 16;
-    LPX_HIP_TRY(hipMalloc((void**)&g.d, sizeof(FusedParams) * c));
-    LPX_HIP_TRY(hipMalloc((void**)&g.ds, sizeof(DevState) * c));
-    LPX_HIP_TRY(hipMalloc((void**)&g.live_d, sizeof(int) * 2 * c));
-    LPX_HIP_TRY(hipMalloc((void**)&g.fresh_d, sizeof(int) * c));
-    LPX_HIP_TRY(hipHostMalloc((void**)&g.h, sizeof(FusedParams) * c));
-    LPX_HIP_TRY(hipHostMalloc((void**)&g.hs, sizeof(DevState) * c));
-    LPX_HIP_TRY(hipHostMalloc((void**)&g.live_h, sizeof(int) * 2 * c));
-    LPX_HIP_TRY(hipHostMalloc((void**)&g.fresh_h, sizeof(int) * c));
-    LPX_HIP_TRY(hipHostMalloc((void**)&g.cur_h, sizeof(int) * c));
-    LPX_HIP_TRY(hipMalloc((void**)&g.comp_d, sizeof(int) * group_fused_comp_ints(c)));
-    LPX_HIP_TRY(hipHostMalloc((void**)&g.comp_h, sizeof(int) * 2 * (32 + c)));       // two windows' worth of {counts, list of parity 0}
-    LPX_HIP_TRY(hipMemsetAsync(g.comp_d, 0, sizeof(int) * group_fused_comp_ints(c), g.stream));
-    g.cap = c;
-    return 0;
-}
-
-FusedGroupBuf g_fgroups[kAsyncSlots + 1];   // [0 .. kAsyncSlots): the asynchronous batches (lpx_multi_run_begin / _end), [kAsyncSlots]: the synchronous runs
-
-// parameter records, initial states and the init launch of a group; returns LPX_RESIDENT_RETRY when the group cannot take the
-// fused path (nothing has been touched then)
-int fused_prepare(FusedGroupBuf& g, lpx_tableau** ts, const int* dual, int count, const lpx_run_opts* popts, const lpx_run_opts* dopts,
-                  const DevState* inits, int* per_node_out, int* batch_out, long long* budget_out)
-{
-    static const bool enabled = [] { const char* e = std::getenv("LPX_GROUP_FUSED"); return !(e && e[0] == '0'); }();
-    if (!enabled || count < 1) return LPX_RESIDENT_RETRY;
-    for (int i = 0; i < count; ++i) if (ts[i]->fused_off) return LPX_RESIDENT_RETRY;
-    for (int i = 0; i < count; ++i) if (!fused_buffers(ts[i])) return LPX_RESIDENT_RETRY;
-    { int rc = fused_group_reserve(g, count); if (rc) return rc; }
-    int per_node = 1, nfresh = 0, batch = 64;
-    long long budget = 0;
-    for (int k = 0; k < count; ++k) {
-        lpx_tableau* t = ts[k];
-        LPX_HIP_TRY(hipStreamSynchronize(t->stream));               // node assembly ran on the node's own stream
-        const lpx_run_opts* o = dual[k] ? dopts : popts;
-        FusedParams f; std::memset(&f, 0, sizeof(f));
-        f.P = base_params(t, o, dual[k] ? MODE_DUAL : MODE_PRIMAL);
-        f.T1 = t->fT; f.prow1 = t->fprow; f.rhs1 = t->frhs; f.rec = t->frec;
-        const bool cont = t->fsuspended;                            // continues a fused run: its records are in place
-        f.par = cont ? (t->frec_cur & 1) : 0;
-        g.h[k] = f;
-        DevState init; std::memset(&init, 0, sizeof(init));
-        init.status = LPX_RUNNING; init.r = -1; init.q = -1; init.qn = -1; init.phase = dual[k] ? 0 : 2;
-        if (inits) {                                                // continue where another path stopped (pivot count, phase, counters)
-            const DevState& s0 = inits[k];
-            init.iter = s0.iter; init.phase = dual[k] ? s0.phase : 2;
-            init.fdf_count = s0.fdf_count; init.dual_iter = s0.dual_iter; init.primal_count = s0.primal_count;
-        }
-        g.hs[k] = init;
-        if (!cont) g.fresh_h[nfresh++] = k;
-        t->fsuspended = false;
-        per_node = std::max(per_node, group_fused_blocks(t->ld, t->Rcap));
-        batch = o->batch > 0 ? o->batch : 64;
-        budget = std::max(budget, dual[k] ? (long long)o->fdf_guard + 2LL * o->max_iter + 12 : (long long)o->max_iter + 6);
-    }
-    batch = (batch + 1) & ~1;           // launches alternate between the two record indices: a window ends where it started
-    LPX_HIP_TRY(hipMemcpyAsync(g.d, g.h, sizeof(FusedParams) * count, hipMemcpyHostToDevice, g.stream));
-    if (nfresh > 0) {
-        LPX_HIP_TRY(hipMemcpyAsync(g.ds, g.hs, sizeof(DevState) * count, hipMemcpyHostToDevice, g.stream));
-        LPX_HIP_TRY(hipMemcpyAsync(g.fresh_d, g.fresh_h, sizeof(int) * nfresh, hipMemcpyHostToDevice, g.stream));
-        LPX_HIP_TRY(launch_group_fused_init(g.d, g.fresh_d, nfresh, g.ds, g.stream));
-    }
-    *per_node_out = per_node; *batch_out = batch; *budget_out = budget;
-    return 0;
-}
-
-// what a run leaves on its handles and reports: latest records in g.hs / g.cur_h
-void fused_finish(FusedGroupBuf& g, lpx_tableau** ts, const int* dual, int count, bool unfinished_is_suspended, double ms, long long enq,
-                  int* statuses, lpx_stats* stats, double prof_ms, long long prof_n)
-{
-    for (int k = 0; k < count; ++k) {
-        lpx_tableau* t = ts[k];
-        const DevState& s = g.hs[k];
-        *t->hst = s;
-        const bool running = s.status == LPX_RUNNING;
-        statuses[k] = running ? (unfinished_is_suspended ? LPX_RUNNING : LPX_ITER_LIMIT) : s.status;
-        t->suspended = statuses[k] == LPX_RUNNING;
-        t->fsuspended = t->suspended;
-        t->frec_cur = g.cur_h[k];
-        // a finished node whose last pivot landed in the second buffer: the buffers trade places (every consumer -- solution
-        // read-back, parking, child assembly, download -- goes through t->T); an unfinished one keeps its pending pivot where it is
-        if (!running && s.pad[3] == 1) { std::swap(t->T, t->fT); drop_graph(t); }
-        if (stats) {
-            const double h2d = stats[k].h2d_ms, d2h = stats[k].d2h_ms;      // one-shot entry points keep their transfer times here
-            std::memset(&stats[k], 0, sizeof(lpx_stats));
-            stats[k].h2d_ms = h2d; stats[k].d2h_ms = d2h;
-            stats[k].pivots = s.iter; stats[k].fdf_pivots = s.fdf_count;
-            stats[k].cleanup_pivots = dual[k] ? s.primal_count : 0;
-            stats[k].loop_ms = ms / (double)count;
-            stats[k].launches = enq / (long long)count + 1;
-            if (k == 0) { stats[k].update_ms_sum = prof_ms; stats[k].update_launches = prof_n; }   // group-level figures
-        }
-    }
-}
-
-int multi_run_fused(lpx_tableau** ts, const int* dual, int count, const lpx_run_opts* popts, const lpx_run_opts* dopts,
-                    int* statuses, lpx_stats* stats, const DevState* inits, int min_active)
-{
-    FusedGroupBuf& g = g_fgroups[kAsyncSlots];
-    const double t0 = now_ms();
-    int per_node = 1, batch = 64; long long budget = 0;
-    { const int rc = fused_prepare(g, ts, dual, count, popts, dopts, inits, &per_node, &batch, &budget); if (rc) return rc; }
-    std::vector<int> live(count);
-    for (int k = 0; k < count; ++k) live[k] = k;
-    long long enq = 0; int window = 0; bool suspended_exit = false;
-    const bool profile = popts->profile || dopts->profile;      // every launch bracketed by HIP events bound to the dispatch
-    double prof_ms = 0.0; long long prof_n = 0;
-    if (profile) while ((int)g.ev.size() < 2 * batch) { hipEvent_t e; LPX_HIP_TRY(hipEventCreate(&e)); g.ev.push_back(e); }
-    while (!live.empty() && enq < budget) {
-        // this window's live list (its own half of the buffer: the previous window's launches may still be reading theirs -- they
-        // are not, the poll below waits, but the copy stays safe if the loop ever runs ahead)
-        int* lh = g.live_h + (window & 1) * g.cap; int* ld_ = g.live_d + (window & 1) * g.cap;
-        size_t live_bytes = 0;
-        for (size_t k = 0; k < live.size(); ++k) { lh[k] = live[k]; const lpx_tableau* t = ts[live[k]]; live_bytes += sizeof(double) * (size_t)t->R * t->ld; }
-        LPX_HIP_TRY(hipMemcpyAsync(ld_, lh, sizeof(int) * live.size(), hipMemcpyHostToDevice, g.stream));
-        {   // the device's own live list starts the window equal to the host's (parity 0: windows are even)
-            const int hdr = group_fused_comp_hdr();
-            int* ch = g.comp_h + (window & 1) * (32 + g.cap);
-            std::memset(ch, 0, sizeof(int) * hdr);
-            ch[0] = (int)live.size();
-            for (size_t k = 0; k < live.size(); ++k) ch[hdr + k] = live[k];
-            LPX_HIP_TRY(hipMemcpyAsync(g.comp_d, ch, sizeof(int) * (hdr + live.size()), hipMemcpyHostToDevice, g.stream));
-        }
-        for (int i = 0; i < batch; ++i)
-            LPX_HIP_TRY(launch_group_fused(g.d, ld_, (int)live.size(), per_node, (int)((enq + i) & 1), live_bytes, g.stream, g.comp_d, g.cap,
-                                           profile ? g.ev[2 * i] : nullptr, profile ? g.ev[2 * i + 1] : nullptr));
-        enq += batch;
-        LPX_HIP_TRY(launch_group_fused_gather(g.d, count, g.hs, g.cur_h, g.stream));
-        LPX_HIP_TRY(hipStreamSynchronize(g.stream));
-        if (profile) {
-            // launches that applied a pivot of at least one node: those up to the largest pivot count of the window's live nodes
-            int full = 0;
-            for (int k : live) full = std::max(full, g.hs[k].iter);
-            const long long first = enq - batch;                   // launch l applies pivot l (the first launch of a run applies none)
-            for (int i = 0; i < batch; ++i) {
-                if (first + i < 1 || first + i > full) continue;
-                float msf = 0.f;
-                LPX_HIP_TRY(hipEventElapsedTime(&msf, g.ev[2 * i], g.ev[2 * i + 1]));
-                prof_ms += msf; ++prof_n;
-            }
-        }
-        ++window;
-        std::vector<int> next;
-        for (int k : live) if (g.hs[k].status == LPX_RUNNING) next.push_back(k);
-        live.swap(next);
-        if (!live.empty() && min_active > 0 && (int)live.size() <= min_active) { suspended_exit = true; break; }
-    }
-    fused_finish(g, ts, dual, count, suspended_exit, now_ms() - t0, enq, statuses, stats, prof_ms, prof_n);
-    return 0;
-}
-
-// ---- the same in two halves: one window of `steps` pivots of every run of a batch, enqueued and collected separately, so that the
-//      host can work on one batch (read-back, parking, assembly of the next nodes) while the other one pivots ----
-struct FusedAsync { bool active = false; std::vector<lpx_tableau*> ts; std::vector<int> dual; double t0 = 0; long long enq = 0; hipEvent_t done = nullptr; };
-FusedAsync g_fasync[kAsyncSlots];
-
-}  // namespace
-
-extern "C" {
-
-int lpx_multi_run_begin(int slot, lpx_tableau** ts, const int* dual, int count, const lpx_run_opts* popts, const lpx_run_opts* dopts, int steps)
-{
-    if (slot < 0 || slot >= kAsyncSlots || !ts || !dual || count < 1 || steps < 1) { set_error("lpx_multi_run_begin: bad argument"); return LPX_EINVAL; }
-    FusedAsync& a = g_fasync[slot];
-    if (a.active) { set_error("lpx_multi_run_begin: this slot has a batch in flight (lpx_multi_run_end first)"); return LPX_EINVAL; }
-    lpx_run_opts pd, dd;
-    if (!popts) { lpx_default_opts(&pd, 0); popts = &pd; }
-    if (!dopts) { lpx_default_opts(&dd, 1); dopts = &dd; }
-    for (int i = 0; i < count; ++i) {
-        if (!ts[i] || ts[i]->R < 2) { set_error("lpx_multi_run_begin: null or empty tableau"); return LPX_EINVAL; }
-        if (ts[i]->suspended2) { set_error("lpx_multi_run_begin: a run suspended on the two-launch kernels cannot continue here"); return LPX_EINVAL; }
-    }
-    if (popts->profile || dopts->profile) return 1;
-    FusedGroupBuf& g = g_fgroups[slot];
-    int per_node = 1, batch = 64; long long budget = 0;
-    const double t0 = now_ms();
-    {
-        const int rc = fused_prepare(g, ts, dual, count, popts, dopts, nullptr, &per_node, &batch, &budget);
-        if (rc == LPX_RESIDENT_RETRY) return 1;                 // not available for this batch: the caller takes lpx_multi_run_some
-        if (rc) return rc;
-    }
-    steps = (steps + 1) & ~1;
-    size_t live_bytes = 0;
-    for (int k = 0; k < count; ++k) { g.live_h[k] = k; live_bytes += sizeof(double) * (size_t)ts[k]->R * ts[k]->ld; }
-    LPX_HIP_TRY(hipMemcpyAsync(g.live_d, g.live_h, sizeof(int) * count, hipMemcpyHostToDevice, g.stream));
-    { const int hdr = group_fused_comp_hdr();
-      std::memset(g.comp_h, 0, sizeof(int) * hdr);
-      g.comp_h[0] = count;
-      for (int k = 0; k < count; ++k) g.comp_h[hdr + k] = k;
-      LPX_HIP_TRY(hipMemcpyAsync(g.comp_d, g.comp_h, sizeof(int) * (hdr + count), hipMemcpyHostToDevice, g.stream)); }
-    for (int i = 0; i < steps; ++i) LPX_HIP_TRY(launch_group_fused(g.d, g.live_d, count, per_node, i & 1, live_bytes, g.stream, g.comp_d, g.cap));
-    LPX_HIP_TRY(launch_group_fused_gather(g.d, count, g.hs, g.cur_h, g.stream));
-    if (!a.done) LPX_HIP_TRY(hipEventCreateWithFlags(&a.done, hipEventDisableTiming));
-    LPX_HIP_TRY(hipEventRecord(a.done, g.stream));              // the two slots may share a stream: wait for THIS window, not for the stream
-    a.active = true; a.ts.assign(ts, ts + count); a.dual.assign(dual, dual + count); a.t0 = t0; a.enq = steps;
-    return 0;
-}
-
-int lpx_multi_run_end(int slot, int* statuses, lpx_stats* stats)
-{
-    if (slot < 0 || slot >= kAsyncSlots || !statuses) { set_error("lpx_multi_run_end: bad argument"); return LPX_EINVAL; }
-    FusedAsync& a = g_fasync[slot];
-    if (!a.active) { set_error("lpx_multi_run_end: no batch in flight in this slot"); return LPX_EINVAL; }
-    FusedGroupBuf& g = g_fgroups[slot];
-    a.active = false;
-    LPX_HIP_TRY(hipEventSynchronize(a.done));
-    fused_finish(g, a.ts.data(), a.dual.data(), (int)a.ts.size(), true, now_ms() - a.t0, a.enq, statuses, stats, 0.0, 0);
-    return 0;
-}
-
-}  // extern "C"
-
-static int multi_run_batched(lpx_tableau** ts, const int* dual, int count, const lpx_run_opts* popts,
-                             const lpx_run_opts* dopts, int* statuses, lpx_stats* stats, const DevState* inits = nullptr, int min_active = 0)
-{
-    {   // one launch per step when every node has its second buffer (and none is in the middle of a two-launch run)
-        bool any_two_launch = false;
-        for (int i = 0; i < count; ++i) if (ts[i]->suspended2) any_two_launch = true;
-        if (!any_two_launch) {
-            const int rc = multi_run_fused(ts, dual, count, popts, dopts, statuses, stats, inits, min_active);
-            if (rc != LPX_RESIDENT_RETRY) return rc;
-        }
-    }
-    GroupRun runs[2];
-    for (int w = 0; w < 2; ++w) { runs[w].g = &g_groups[w]; runs[w].dual = w; runs[w].min_active = min_active; }
-    for (int i = 0; i < count; ++i) runs[dual[i] ? 1 : 0].idx.push_back(i);
-    const double t0 = now_ms();
-    for (int w = 0; w < 2; ++w) if (!runs[w].idx.empty()) { int rc = group_begin(runs[w], ts, w ? dopts : popts, inits); if (rc) return rc; }
-    for (;;) {
-        bool any = false;
-        for (int w = 0; w < 2; ++w) if (!runs[w].done) { int rc = group_submit(runs[w], ts, w ? dopts : popts); if (rc) return rc; any = true; }
-        if (!any) break;
-        for (int w = 0; w < 2; ++w) if (!runs[w].idx.empty() && runs[w].enq > 0 && !runs[w].done) { int rc = group_complete(runs[w]); if (rc) return rc; }
-    }
-    const double ms = now_ms() - t0;
-    for (int w = 0; w < 2; ++w) {
-        GroupRun& r = runs[w];
-        for (size_t k = 0; k < r.idx.size(); ++k) {
-            const DevState& s = r.g->hs[k];
-            const int i = r.idx[k];
-            *ts[i]->hst = s;
-            statuses[i] = s.status == LPX_RUNNING ? (r.suspended_exit ? LPX_RUNNING : LPX_ITER_LIMIT) : s.status;
-            ts[i]->suspended = statuses[i] == LPX_RUNNING;          // continues from *hst in the next lpx_multi_run_some
-            ts[i]->suspended2 = ts[i]->suspended;
-            if (stats) {
-                std::memset(&stats[i], 0, sizeof(lpx_stats));
-                stats[i].pivots = s.iter; stats[i].fdf_pivots = s.fdf_count;
-                stats[i].cleanup_pivots = w ? s.primal_count : 0;
-                stats[i].loop_ms = ms / (double)count;
-                stats[i].launches = 2 * r.enq / (long long)(r.idx.size() ? r.idx.size() : 1);
-            }
-        }
-    }
-    return 0;
-}
 
 extern "C" {
 
@@ -1230,7 +470,7 @@ int lpx_primal_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, void*
     // without a per-pivot callback: one fused launch per pivot (LPX_FUSED_PIVOT=0: the two-launch in-place kernels)
     static const bool fused_env = [] { const char* e = std::getenv("LPX_FUSED_PIVOT"); return !(e && e[0] == '0'); }();
     if (fused_env && p.us && !cb && fused_buffers(t)) return run_fused(t, p, o, st, resume);
-    return run_loop(t, p, o, (long long)o->max_iter + 2, cb, user, st, resume);
+    return run_loop(t, p, o, pivot_budget(o, false) + 2, cb, user, st, resume);
 }
 
 int lpx_dual_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, void* user, lpx_stats* st)
@@ -1240,22 +480,17 @@ int lpx_dual_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, void* u
     if (t->R < 2) { set_error("lpx_dual_run: tableau needs at least one constraint row"); return LPX_EINVAL; }
     static const bool res_env = [] { const char* e = std::getenv("LPX_RESIDENT"); return !(e && e[0] == '0'); }();
     if (o->resident > 0 || (o->resident == 0 && res_env && !o->profile && (o->batch == 0 || o->batch >= 32))) {
-        int grid = 0, slots = 0; size_t lds = 0; int isdual = 1, status = 0;
-        if (!t->resident_off && resident_group_plan(&t, 1, &grid, &slots, &lds)) {
+        int isdual = 1, status = 0;
+        const ResGroupPlan plan = t->resident_off ? ResGroupPlan{} : resident_group_plan(&t, 1);
+        if (plan.slots) {
             DevState resume;
-            const int rc = run_resident_group(&t, &isdual, 1, o, o, &status, st, grid, slots, lds, cb, user, &resume);
+            const int rc = run_resident_group(&t, &isdual, 1, o, o, &status, st, plan, cb, user, &resume);
             if (rc == 0) return status;
             if (rc != LPX_RESIDENT_RETRY) return rc;
             t->resident_off = true;
             if (o->resident > 0) return LPX_EDEVICE;
             // hand over to the streaming kernels at the pivot the resident loop had reached
-            SelParams p = base_params(t, o, MODE_DUAL);
-            LoopCtx c; DevState init;
-            make_ctx(t, p, c, init);
-            init.iter = resume.iter; init.phase = resume.phase;
-            init.fdf_count = resume.fdf_count; init.dual_iter = resume.dual_iter; init.primal_count = resume.primal_count;
-            c.start_iter = resume.iter;
-            return run_device_loop(c, init, o, (long long)o->fdf_guard + 2LL * o->max_iter + 8, cb, user, st);
+            return continue_streaming(t, o, true, resume, cb, user, st);
         } else
         if (o->resident > 0) { set_error("lpx_dual_run: resident = 1 but the tableau does not fit the chip's LDS"); return LPX_EINVAL; }
     }
@@ -1265,8 +500,7 @@ int lpx_dual_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, void* u
         if (rc != LPX_RESIDENT_RETRY) return rc ? rc : status;
     }
     SelParams p = base_params(t, o, MODE_DUAL);
-    long long budget = (long long)o->fdf_guard + 2LL * o->max_iter + 8;
-    return run_loop(t, p, o, budget, cb, user, st);
+    return run_loop(t, p, o, pivot_budget(o, true) + 8, cb, user, st);
 }
 
 int lpx_forced_pivots_run(lpx_tableau* t, const int32_t* rows, const int32_t* cols, int count,
@@ -1321,127 +555,6 @@ static int one_shot(double* T, int R, int C, int32_t* basis, const lpx_run_opts*
     lpx_tableau_destroy(t);
     if (st) *st = local;
     return rc ? rc : status;
-}
-
-int lpx_multi_run(lpx_tableau** ts, const int* dual, int count, const lpx_run_opts* popts,
-                  const lpx_run_opts* dopts, int* statuses, lpx_stats* stats)
-{
-    if (!ts || !dual || count < 0 || !statuses) { set_error("lpx_multi_run: bad argument"); return LPX_EINVAL; }
-    lpx_run_opts pd, dd;
-    if (!popts) { lpx_default_opts(&pd, 0); popts = &pd; }
-    if (!dopts) { lpx_default_opts(&dd, 1); dopts = &dd; }
-    // Nodes small enough to live on chip a few at a time (lpx_resident_group.hip): four 8 MB nodes of config 4 run side by
-    // side, 25 % faster than 32 of them streaming through HBM.  LPX_RESIDENT_GROUP=0 keeps the batched streaming run.
-    static const bool resgroup_env = [] { const char* e = std::getenv("LPX_RESIDENT_GROUP"); return !(e && e[0] == '0'); }();
-    if (resgroup_env && count >= 1 && !popts->profile && !dopts->profile && popts->resident >= 0 && dopts->resident >= 0) {
-        bool ok = true;
-        for (int i = 0; i < count; ++i) if (!ts[i] || ts[i]->R < 2 || ts[i]->resident_off || (!dual[i] && !ts[i]->us)) ok = false;
-        int grid = 0, slots = 0; size_t lds = 0;
-        if (ok && resident_group_plan(ts, count, &grid, &slots, &lds)) {
-            std::vector<DevState> resume(count);
-            const int rc = run_resident_group(ts, dual, count, popts, dopts, statuses, stats, grid, slots, lds, nullptr, nullptr, resume.data());
-            if (rc != LPX_RESIDENT_RETRY) return rc;
-            // some workgroup could not take part (GPU shared with another process?): finish the unfinished nodes on the
-            // batched streaming kernels, from the pivot each of them had reached
-            std::vector<lpx_tableau*> sub; std::vector<int> sdual, sidx; std::vector<DevState> sinit;
-            for (int i = 0; i < count; ++i) {
-                ts[i]->resident_off = true;
-                if (statuses[i] == LPX_RUNNING) { sub.push_back(ts[i]); sdual.push_back(dual[i]); sidx.push_back(i); sinit.push_back(resume[i]); }
-                else if (stats) { std::memset(&stats[i], 0, sizeof(lpx_stats)); stats[i].pivots = resume[i].iter; stats[i].fdf_pivots = resume[i].fdf_count; stats[i].cleanup_pivots = dual[i] ? resume[i].primal_count : 0; *ts[i]->hst = resume[i]; }
-            }
-            if (!sub.empty()) {
-                std::vector<int> sst(sub.size()); std::vector<lpx_stats> sss(sub.size());
-                int rc2;
-                if (sub.size() >= 2) rc2 = multi_run_batched(sub.data(), sdual.data(), (int)sub.size(), popts, dopts, sst.data(), sss.data(), sinit.data());
-                else {
-                    // a single straggler: its own streaming loop, continuing at its pivot count
-                    lpx_tableau* t = sub[0];
-                    const lpx_run_opts* o = sdual[0] ? dopts : popts;
-                    SelParams p = base_params(t, o, sdual[0] ? MODE_DUAL : MODE_PRIMAL);
-                    LoopCtx c; DevState init;
-                    make_ctx(t, p, c, init);
-                    init.iter = sinit[0].iter; init.phase = sdual[0] ? sinit[0].phase : 2;
-                    init.fdf_count = sinit[0].fdf_count; init.dual_iter = sinit[0].dual_iter; init.primal_count = sinit[0].primal_count;
-                    const long long budget = sdual[0] ? (long long)o->fdf_guard + 2LL * o->max_iter + 8 : (long long)o->max_iter + 2;
-                    rc2 = run_device_loop(c, init, o, budget, nullptr, nullptr, &sss[0]);
-                    if (rc2 >= 0) { sst[0] = rc2; rc2 = 0; }
-                }
-                if (rc2) return rc2;
-                for (size_t k = 0; k < sub.size(); ++k) { statuses[sidx[k]] = sst[k]; if (stats) stats[sidx[k]] = sss[k]; }
-            }
-            return 0;
-        }
-    }
-    static const bool batched_env = [] { const char* e = std::getenv("LPX_BATCHED"); return !(e && e[0] == '0'); }();
-    if (batched_env && count >= 1 && (popts->profile || dopts->profile)) {
-        // profile mode: the fused group launch bracketed by HIP events (stats[0].update_ms_sum / update_launches are the group's)
-        bool ok = true;
-        for (int i = 0; i < count; ++i) if (!ts[i] || ts[i]->R < 2) ok = false;
-        if (ok) { const int rc = multi_run_fused(ts, dual, count, popts, dopts, statuses, stats, nullptr, 0); if (rc != LPX_RESIDENT_RETRY) return rc; }
-    }
-    if (batched_env && count >= 2 && !popts->profile && !dopts->profile) {
-        bool ok = true;
-        for (int i = 0; i < count; ++i) if (!ts[i] || ts[i]->R < 2 || (!dual[i] && !ts[i]->us)) ok = false;
-        if (ok) return multi_run_batched(ts, dual, count, popts, dopts, statuses, stats);
-    }
-    std::vector<LoopRun> runs(count);
-    std::vector<char> active(count, 0);
-    for (int i = 0; i < count; ++i) {
-        lpx_tableau* t = ts[i];
-        if (!t || t->R < 2) { set_error("lpx_multi_run: null or empty tableau"); return LPX_EINVAL; }
-        const lpx_run_opts* o = dual[i] ? dopts : popts;
-        SelParams p = base_params(t, o, dual[i] ? MODE_DUAL : MODE_PRIMAL);
-        LoopCtx c; DevState init;
-        make_ctx(t, p, c, init);
-        long long budget = dual[i] ? (long long)o->fdf_guard + 2LL * o->max_iter + 8 : (long long)o->max_iter + 2;
-        int rc = runs[i].begin(c, init, o, budget, nullptr, nullptr);
-        if (rc) return rc;
-        active[i] = 1;
-    }
-    int remaining = count;
-    while (remaining > 0) {
-        for (int i = 0; i < count; ++i) if (active[i]) { int rc = runs[i].submit(); if (rc) return rc; }
-        for (int i = 0; i < count; ++i) if (active[i]) {
-            int rc = runs[i].complete(); if (rc) return rc;
-            if (runs[i].done()) {
-                statuses[i] = runs[i].finish(stats ? &stats[i] : nullptr);
-                active[i] = 0; --remaining;
-            }
-        }
-    }
-    return 0;
-}
-
-// lpx_multi_run for a ROLLING batch (warm-started B&B children need a few dozen pivots each, a few of them hundreds): the run
-// stops as soon as at most `min_active` nodes are still running and reports them as LPX_RUNNING; the caller hands them in again
-// together with fresh nodes and they continue where they stopped (pivot count, phase, counters: the handle remembers).  Without
-// it a batch of 64 runs as long as its slowest node while the device idles at the per-step latency floor.  Streaming batched
-// kernels only (callers that want the resident group kernel use lpx_multi_run); min_active = 0 runs everything to the end.
-int lpx_multi_run_some(lpx_tableau** ts, const int* dual, int count, const lpx_run_opts* popts, const lpx_run_opts* dopts,
-                       int* statuses, lpx_stats* stats, int min_active)
-{
-    if (!ts || !dual || count < 0 || !statuses) { set_error("lpx_multi_run_some: bad argument"); return LPX_EINVAL; }
-    lpx_run_opts pd, dd;
-    if (!popts) { lpx_default_opts(&pd, 0); popts = &pd; }
-    if (!dopts) { lpx_default_opts(&dd, 1); dopts = &dd; }
-    bool ok = count >= 1 && !popts->profile && !dopts->profile, resumed = false;
-    for (int i = 0; i < count; ++i) {
-        if (!ts[i] || ts[i]->R < 2) { set_error("lpx_multi_run_some: null or empty tableau"); return LPX_EINVAL; }
-        if (!dual[i] && !ts[i]->us) ok = false;
-        if (ts[i]->suspended) resumed = true;
-    }
-    if (!ok) {
-        if (resumed) { set_error("lpx_multi_run_some: a suspended run cannot continue on this path"); return LPX_EINVAL; }
-        return lpx_multi_run(ts, dual, count, popts, dopts, statuses, stats);
-    }
-    std::vector<DevState> inits(count);
-    for (int i = 0; i < count; ++i) {
-        DevState z; std::memset(&z, 0, sizeof(z));
-        z.status = LPX_RUNNING; z.phase = dual[i] ? 0 : 2;
-        inits[i] = ts[i]->suspended ? *ts[i]->hst : z;
-        ts[i]->suspended = false;
-    }
-    return multi_run_batched(ts, dual, count, popts, dopts, statuses, stats, inits.data(), min_active < count ? min_active : 0);
 }
 
 int lpx_primal_tableau(double* T, int R, int C, int32_t* basis, double eps, int max_iter,

@@ -294,7 +294,7 @@ def test_late_workgroup_cannot_leave_a_half_pivoted_tableau(oracle):
     """LPX_RESIDENT_TEST_MUTE=3: the last workgroup gets its CU only AFTER the others have given up (the real
     non-co-residency case).  It still finds their first ratios, owns the pivot row, completes the only pivot of a
     max_iter=1 launch and stores its rows -- a pivot the other workgroups never made.  The host must put the tableau
-    of the launch's start back before the streaming kernels take over (lpx_tableau.cpp run_resident /
+    of the launch's start back before the streaming kernels take over (lpx_tableau_resident.cpp run_resident /
     run_resident_group): result bit-identical to the oracle, not a tableau with one row pivoted twice."""
     import subprocess, sys, os, textwrap
     code = textwrap.dedent('''
