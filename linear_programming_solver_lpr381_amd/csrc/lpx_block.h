@@ -15,17 +15,23 @@ static constexpr int MB_NT = 256;            // lanes of one workgroup of the mu
 static constexpr int MB_QREC = 128;
 static constexpr int MB_CNT = 160;
 static constexpr int MB_MAXB = 64;           // at most this many workgroups (partials fit one wave)
-// deferred pivots of the one-launch primal loop and its latency-shaped select-only kernel (lpx_pivot_fused.hip: lpx_pivot_select)
+// deferred pivots of the one-launch primal loop and its select-only pair (lpx_pivot_fused.hip: lpx_pivot_ratio, lpx_pivot_select)
 static constexpr int FP_DMAX = 16;           // deepest deferral: pivots applied per sweep
-static constexpr int SELP_NT = 512;
+static constexpr int SELC_ROWS = 256;                        // column launch (lpx_pivot_ratio): rows = lanes of a workgroup, one row per lane
+static constexpr int SELP_NT = 512;                          // row launch (lpx_pivot_select): lanes of a workgroup
+static constexpr int SELP_RU = 10;                           // ratios a lane of the row launch has in flight per pass over the ratio buffer
+// SELP_U and SELP_PASS_ROWS shaped the column passes of the one-launch form (the column now has a launch of its own) and shape
+// no kernel any more; tests/test_gpu_select_only.py places its cases by them, so they keep their values.
 static constexpr int SELP_U = 3;
-static constexpr int SELP_PASS_ROWS = 1536;                  // rows of one pass over the column
-static constexpr int SELP_SB = 8;                            // pending pivots whose factor loads are issued together
+static constexpr int SELP_PASS_ROWS = 1536;
+static constexpr int SELP_SB = 8;                            // row launch: pending pivot rows prefetched in groups of this many
 static constexpr int SELP_LDS_ROWS = 10240;                  // row cap of this form: 80 KB of ratios in LDS
 static constexpr int SELP_MIN_MB = 64;                       // handles of at most this many MB keep the old form (see launch_pivot_fused)
 static constexpr int SELP_PMAX = FP_DMAX - 1;                // most pending pivots of a select-only launch
-static_assert(SELP_PASS_ROWS == SELP_NT * SELP_U, "rows of a pass: SELP_U per lane");
+static_assert(SELP_PASS_ROWS == SELP_NT * SELP_U, "kept for the tests that read them");
 static_assert(SELP_PMAX <= 64 && SELP_PMAX <= 2 * SELP_SB, "pending scalars: one lane each; row prefetch: two groups");
+static_assert(SELC_ROWS % 64 == 0 && SELC_ROWS <= 1024, "column launch: whole waves, one workgroup");
+static_assert(SELP_LDS_ROWS <= 2 * SELP_RU * SELP_NT, "row launch: the ratio buffer in at most two passes");
 
 // ------------------------------------------------------------------------------------------------
 // workgroup primitives (wave64)

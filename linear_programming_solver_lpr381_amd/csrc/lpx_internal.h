@@ -154,11 +154,13 @@ int fused_policy(int ld, int R);             // 0 = default cache policy (lpx_pi
 int pivot_defer_max();                       // deepest deferral the sweep kernels are built for
 hipError_t launch_fused_init(const FusedParams& f, hipStream_t s);
 // launch L of a run (0: the prologue's): a sweep applying f.defer pending pivots when L is a positive multiple of f.defer,
-// else select-only
-hipError_t launch_pivot_fused(const FusedParams& f, long long L, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// else select-only -- one kernel, or two (column launch, row launch) where pivot_select_is_pair(ld, capacity rows).
+// rat: the handle's ratio buffer (capacity rows + 1 doubles), which only the pair uses
+bool pivot_select_is_pair(int ld, int R);
+hipError_t launch_pivot_fused(const FusedParams& f, double* rat, long long L, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 // the n pivots a finished run left pending (its last record: buffer, count, oldest slot), applied into buffer 0
 hipError_t launch_pivot_flush(const FusedParams& f, int buf, int n, int slot0, hipStream_t s);
-hipError_t pivot_fused_init();      // one-time function attribute of lpx_pivot_select
+hipError_t pivot_fused_init();      // one-time function attribute of lpx_pivot_select (the row launch)
 
 // ---- lpx_group_fused.hip: the fused group step (K4g), one launch per step for a whole group of node LPs
 hipError_t launch_group_fused_init(const FusedParams* arr, const int* fresh, int nfresh, const DevState* init, hipStream_t s);

@@ -1,5 +1,5 @@
 // lpx_pivot_fused.hip -- the one-launch primal pivot (K4f) and its deferred pivots: sweep kernels of every depth,
-// the two select-only kernels, the flush and their launchers.  Built with -ffp-contract=off like every tile (lpx_kernels.hip).
+// the select-only kernels (one launch through the workspace; the column and row launches of the pair), the flush and their launchers.  Built with -ffp-contract=off like every tile (lpx_kernels.hip).
 #include <algorithm>
 #include "lpx_scan.h"
 #include "lpx_tile.h"
@@ -73,13 +73,15 @@ __host__ __device__ constexpr int fp_rec(int buf, int npend, int slot0) { return
 __device__ __forceinline__ int fp_slot(int lm, int n, int s, int ring) { const int k = lm - n + s; return k < 0 ? k + ring : k; }
 
 #ifdef LPX_STAMPS
-// Diagnostic build only: phase stamps of the select-only launch (tools/diag_pivot_select_stamps.py).  Workgroup 0's lane 0 keeps
+// Diagnostic build only: phase stamps of the select-only launches (tools/diag_pivot_select_stamps.py).  Workgroup 0's lane 0 keeps
 // the s_memtime deltas in registers and adds them to lpx_g_stamps[8 + slot] when the launch ends (a store per stamp would put
 // its own round trip into the next phase).  LPX_FS_W first waits for wave 0's loads, so that a phase which only issues loads
 // owns their latency; that serialises phases the shipped kernel overlaps, so the phases' sum exceeds the unstamped duration
-// (slot 20 has the launch's own s_memrealtime span).  Slots: 0 record load and branch, 1 column gather, 2 pending chain,
-// 3 ratio store and barrier, 4 scan, 5 piv chain, 6 row loop, 7 wave and hand-off reduction, 8 tail stores, 9 gather trips,
-// 10-12 gather per trip (the third and later trips together), 20 realtime, 21 launches, 22 pending pivots summed.
+// (slot 20 has the launch's own s_memrealtime span).  Slots of the one-launch form (lpx_pivot_select_ws): 0 record load and
+// branch, 1 column gather, 2 pending chain, 3 ratio store and barrier, 4 scan, 5 piv chain, 6 row loop, 7 wave and hand-off
+// reduction, 8 tail stores, 9 gather trips, 10-12 gather per trip (the third and later trips together), 20 realtime, 21 launches,
+// 22 pending pivots summed.  The row launch of the pair (lpx_pivot_select) uses the same range: 0 record, shape and ratios into
+// LDS, 1 issue of round 2, 3 barrier, 4 - 8 and 20 - 22 as above; the column launch has its own (LPX_FC_*, below).
 #define LPX_FS_BEGIN(on) const bool fs_on_ = (on) && blockIdx.x == 0 && threadIdx.x == 0; unsigned long long fs_acc_[13] = {0}; \
     unsigned long long fs_prev_ = __builtin_amdgcn_s_memtime(); const unsigned long long fs_rt0_ = __builtin_amdgcn_s_memrealtime();
 #define LPX_FS(slot) do { if (fs_on_) { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); fs_acc_[(slot)] += n_ - fs_prev_; fs_prev_ = n_; } } while (0)
@@ -369,39 +371,151 @@ __global__ __launch_bounds__(FP_NT) __attribute__((amdgpu_waves_per_eu(6))) void
     } else fused_sweep<false, D>(F, ncw, nunits, mixmod);
 }
 // select-only launch: the L % d pending pivots stay where they are.  This form (ratios through the workgroup's slice of P.ws,
-// the column in trips of U x 256 rows) serves tableaux of more than SELP_LDS_ROWS rows; lpx_pivot_select below serves the others.
+// the column in trips of U x 256 rows) serves tableaux of more than SELP_LDS_ROWS rows and handles of at most SELP_MIN_MB; the pair
+// lpx_pivot_ratio + lpx_pivot_select below serves the others.
 template <int U, int SU>
 __global__ __launch_bounds__(FP_NT) void lpx_pivot_select_ws(FusedParams F)
 {
     fused_select<U, SU>(F, F.lm % F.defer, false);
 }
 
-// The select-only launch shaped for latency.  It runs alone on the device, at most 32 workgroups, and moves no tableau: what it
-// costs is the length of its chain of dependent memory round trips, so the same loads of the same values and the same
-// arithmetic as fused_select<.., ..>(F, n, false) are issued in as few rounds as they allow:
-//   round 1  the record
-//   round 2  column q and the RHS column in passes of SELP_PASS_ROWS rows (SELP_U rows per lane; the headline's 4097 rows take
-//            three: a single pass of 9 rows per lane gathered slower, 6.6 against 5.4 us, and cost 237 VGPRs -- DESIGN.md 10),
-//            the pending pivots' scalars (one vector load per wave: lane k holds pq, r and the objective-row factor of pending
-//            pivot k, read back with v_readlane) and the factor columns of SELP_SB pending pivots at a time, whatever n is (past
-//            the newest: its factors again) -- the chain then runs in registers
-//   round 3  the pending pivot rows and the objective row of the workgroup's columns, in flight while the ratios are scanned
-//            out of LDS (dynamic, 8 R bytes: no store to global memory, drain and reload)
-//   round 4  once r is known: row r, the pivot element and the n factors of row r together
-//   round 5  the hand-off: one partial per workgroup (block_min_idx first: 8 waves x 32 workgroups would overflow the 128 entries)
-// 512 lanes at 2 waves per SIMD; the 3 + 3 + 8 x 3 doubles of round 2 fit 116 VGPRs.  The record bookkeeping and the
-// hand-off are copies of fused_select's: shared helpers moved instructions in all 32 sweep kernels.
-// (SELP_*: lpx_block.h, beside the other select kernels' launch constants)
+// The select-only step shaped for latency: two launches, cut where the work changes shape.  Neither moves any tableau; what they
+// cost is the length of their chains of dependent memory round trips.  In one launch (the form before this one) each of the 32
+// workgroups pulled all R lines of column q and the factor columns of the pending pivots through its own compute unit, only to
+// find the same row r as the 31 others: two thirds of that launch.  Now
+//   lpx_pivot_ratio  (column launch)  ceil(Rcap / SELC_ROWS) workgroups, one row per lane: T_{k+1}[i,q] through the n pending
+//                    pivots, the RHS correction and the ratio of row i -> facn, rhsn and the handle's ratio buffer (Rcap + 1
+//                    doubles; the last one is T_{k+1}[m,q])
+//   lpx_pivot_select (row launch)     the nsel workgroups of every select: the ratio buffer into LDS, the scan, row r and the
+//                    objective row through the pending pivots, the hand-off of the partial argmins, the next record
+// The kernel boundary between them publishes the column launch's plain stores; a hand-off inside one launch would need a spin
+// wait on workgroups that HIP does not promise to be co-resident.  Same loads of the same values and the same
+// arithmetic as fused_select<.., ..>(F, n, false).  Rounds of the column launch:
+//   round 1  the record and the live shape (leaves: status not running, iteration cap met, no entering column -- the row launch
+//            alone decides terminal states and writes the next record; workgroups past the live rows)
+//   round 2  T[i,q], rhs[i], the factor columns of the n live pending pivots (one instantiation per n) and the pending pivots'
+//            scalars (one vector load per wave: lane k holds pq and r of pending pivot k, read back with v_readlane), all in
+//            flight together -- the chain then runs in registers
+// and of the row launch:
+//   round 1  the record, the live shape and the ratio buffer (its address does not depend on the record) -> LDS (dynamic)
+//   round 2  the pending pivots' scalars, the pending pivot rows and the objective row of the workgroup's columns, in flight
+//            while the ratios are scanned out of LDS
+//   round 3  once r is known: row r, the pivot element and the n factors of row r together
+//   round 4  the hand-off: one partial per workgroup (block_min_idx first: 8 waves x 32 workgroups would overflow the 128 entries)
+// The record bookkeeping and the hand-off are copies of fused_select's: shared helpers moved instructions in all 32 sweep
+// kernels.  (SELC_*, SELP_*: lpx_block.h, beside the other select kernels' launch constants)
 
 __device__ __forceinline__ double lane_f64(double x, int k)
 {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), k), __builtin_amdgcn_readlane(__double2loint(x), k));
 }
 
-__global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F)
+#ifdef LPX_STAMPS
+// The column launch's stamps, first wave of workgroup 0, lpx_g_stamps[21 ..]: 21 record load and leave tests, 22 round 2 (every
+// load waited for), 23 chain and stores, 24 realtime span, 25 launches, 26 pending pivots summed.
+#define LPX_FC_BEGIN() const bool fc_on_ = blockIdx.x == 0 && threadIdx.x == 0; unsigned long long fc_acc_[3] = {0}; \
+    unsigned long long fc_prev_ = __builtin_amdgcn_s_memtime(); const unsigned long long fc_rt0_ = __builtin_amdgcn_s_memrealtime();
+#define LPX_FC_W(slot) do { if (fc_on_) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); \
+    const unsigned long long n_ = __builtin_amdgcn_s_memtime(); fc_acc_[(slot)] += n_ - fc_prev_; fc_prev_ = n_; } } while (0)
+#define LPX_FC_END(npend) do { if (fc_on_) { _Pragma("unroll") for (int k_ = 0; k_ < 3; ++k_) lpx_g_stamps[21 + k_] += fc_acc_[k_]; \
+    lpx_g_stamps[24] += __builtin_amdgcn_s_memrealtime() - fc_rt0_; lpx_g_stamps[25] += 1; lpx_g_stamps[26] += (unsigned long long)(npend); } } while (0)
+#else
+#define LPX_FC_BEGIN()
+#define LPX_FC_W(slot) do {} while (0)
+#define LPX_FC_END(npend) do {} while (0)
+#endif
+
+// the column launch through N pending pivots (N known at compile time: exactly N factor columns in flight)
+template <int N>
+__device__ __forceinline__ void pivot_ratio_rows(const FusedParams& F, double* __restrict__ rat)
 {
-    extern __shared__ double sp_rat[];                       // the ratios of the test, one per live row
-    __shared__ double s_fs;
+    const SelParams& P = F.P;
+    const int t = threadIdx.x;
+    const int lm = F.lm, ring = 2 * F.defer, c = lm & 1;     // the current record comes with the launch: see fused_select
+    LPX_FC_BEGIN()
+    // round 1: the live shape beside the record
+    int R = P.R, C = P.C;
+    if (P.shape) { R = P.shape[0]; C = P.shape[1]; }
+    const DevState cur = F.rec[c];
+    const int status = cur.status, primal_count = cur.primal_count, q = cur.qn, rnew = cur.r, buf = cur.pad[3] & 1;
+    if (status != LPX_RUNNING || primal_count >= P.max_iter || q < 0) return;     // the row launch writes the record of a run that is over
+    if ((int)blockIdx.x * SELC_ROWS >= R) return;            // the grid follows the capacity
+    LPX_FC_W(0);
+    const size_t ld = (size_t)P.ld, fld = (size_t)P.R;
+    const double* __restrict__ src = buf ? F.T1 : P.T;
+    double* __restrict__ facn = F.fring + (size_t)lm * fld;
+    const double* __restrict__ rhsc = c ? F.rhs1 : P.rhsbuf;
+    double* __restrict__ rhsn = c ? P.rhsbuf : F.rhs1;
+    const int m = R - 1;
+    const int i = blockIdx.x * SELC_ROWS + t;
+    const int ic = min(i, m);                                // clamped, not guarded: a guarded load waits for its own branch
+    // round 2: the column, the RHS column, the N factor columns and, last (the wave waits for them in issue order, so the chain's
+    // first v_readlane waits for the whole round), the pending pivots' scalars: lane k of every wave holds pq and r of pending
+    // pivot k (0 = oldest; lanes past the newest repeat it)
+    const double v0 = src[(size_t)ic * ld + q], h = rhsc[ic];
+    double f[N > 0 ? N : 1], pqv = 0.0, prhs = 0.0;
+    int rsv = -1;
+    if (N > 0) {
+#pragma unroll
+        for (int s = 0; s < N; ++s) f[s] = F.fring[(size_t)fp_slot(lm, N, s, ring) * fld + ic];
+        prhs = F.pring[(size_t)fp_slot(lm, N, N - 1, ring) * ld + (C - 1)];
+        const size_t kslot = (size_t)fp_slot(lm, N, min(t & 63, N - 1), ring);
+        pqv = F.pring[kslot * ld + q];
+        rsv = F.rring[kslot];
+    }
+    LPX_FC_W(1);
+    // T_{k+1}[i,q] and T_{k+1}[i,C-1] as the sweep stores them: the column through every pending pivot, oldest first (row r_s: the
+    // normalised pivot row), the RHS column kept current in rhsc up to the newest pending pivot, which is applied here
+    double v = v0;
+#pragma unroll
+    for (int s = 0; s < N; ++s) {
+        const double pq = lane_f64(pqv, s);
+        const int rs = s == N - 1 ? rnew : __builtin_amdgcn_readlane(rsv, s);     // the newest: the record's
+        const double nv = v - f[s] * pq;                     // mul, then sub: contraction is off
+        v = ic == rs ? pq : nv;
+    }
+    const double dn = v;
+    const double nm = N == 0 ? h : (ic == rnew ? prhs : h - f[N > 0 ? N - 1 : 0] * prhs);
+    double ratio = dn > P.eps ? nm / dn : __builtin_inf();   // ChooseLeaving's ratio, :229-241
+    // every lane computes (the clamped ones their copy of row m); only the stores are guarded.  The empty asm keeps it so: with
+    // the arithmetic sunk into the guarded block, the loads go with it and the v_readlane above, which cannot, waits for its own
+    // round first
+    asm volatile("" : "+v"(ratio));
+    if (i < R) {
+        rat[i] = ratio;
+        facn[i] = dn; rhsn[i] = nm;                          // factors of pivot k+1, numerators of the test after it
+        if (i == m) rat[P.R] = dn;                           // T_{k+1}[m,q]: row m belongs to exactly one lane
+    }
+    LPX_FC_W(2);
+    LPX_FC_END(N);
+}
+
+__global__ __launch_bounds__(SELC_ROWS) void lpx_pivot_ratio(FusedParams F, double* __restrict__ rat)
+{
+    switch (F.lm % F.defer) {                                // pending pivots: the launch's own argument, no load
+    case 0: pivot_ratio_rows<0>(F, rat); break;
+    case 1: pivot_ratio_rows<1>(F, rat); break;
+    case 2: pivot_ratio_rows<2>(F, rat); break;
+    case 3: pivot_ratio_rows<3>(F, rat); break;
+    case 4: pivot_ratio_rows<4>(F, rat); break;
+    case 5: pivot_ratio_rows<5>(F, rat); break;
+    case 6: pivot_ratio_rows<6>(F, rat); break;
+    case 7: pivot_ratio_rows<7>(F, rat); break;
+    case 8: pivot_ratio_rows<8>(F, rat); break;
+    case 9: pivot_ratio_rows<9>(F, rat); break;
+    case 10: pivot_ratio_rows<10>(F, rat); break;
+    case 11: pivot_ratio_rows<11>(F, rat); break;
+    case 12: pivot_ratio_rows<12>(F, rat); break;
+    case 13: pivot_ratio_rows<13>(F, rat); break;
+    case 14: pivot_ratio_rows<14>(F, rat); break;
+    default: pivot_ratio_rows<SELP_PMAX>(F, rat); break;
+    }
+}
+static_assert(SELP_PMAX == 15, "lpx_pivot_ratio: one case per pending count");
+
+__global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const double* __restrict__ rat)
+{
+    extern __shared__ double sp_rat[];                       // the ratios of the test, one per row of the handle
     __shared__ double s_v[SELP_NT / 64];
     __shared__ int s_i[SELP_NT / 64];
     const SelParams& P = F.P;
@@ -410,11 +524,34 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F)
     const int n = lm % F.defer;
     const int c = lm & 1;                                    // the current record comes with the launch: see fused_select
     LPX_FS_BEGIN(true)
-    // the live shape beside the record, before the kernel's first store: one round for both
+    // round 1: the ratios, the live shape and the record together, before the kernel's first store.  The ratio passes follow the
+    // capacity (a launch argument) and are issued first, so that no load waits for another: SELP_RU x SELP_NT rows per pass,
+    // the headline's 4097 in one
+    double x0[SELP_RU];
+#pragma unroll
+    for (int u = 0; u < SELP_RU; ++u) x0[u] = rat[min(P.R, u * SELP_NT + t)];
+    const double fs = rat[P.R];                              // T_{k+1}[m,q]
     int R = P.R, C = P.C;
     if (P.shape) { R = P.shape[0]; C = P.shape[1]; }
     const DevState cur = F.rec[c];
     DevState* nxt = F.rec + (c ^ 1);
+    // the record's loads stay here, in flight beside the ratios: left alone, the compiler sinks them behind the LDS stores
+    asm volatile("" :: "s"(cur.status), "s"(cur.qn), "s"(cur.pad[3]), "s"(R) : "memory");
+#pragma unroll
+    for (int u = 0; u < SELP_RU; ++u) {
+        const int i = u * SELP_NT + t;
+        if (i < P.R) sp_rat[i] = x0[u];
+    }
+    for (int i0 = SELP_RU * SELP_NT; i0 < P.R; i0 += SELP_RU * SELP_NT) {
+        double x[SELP_RU];
+#pragma unroll
+        for (int u = 0; u < SELP_RU; ++u) x[u] = rat[min(P.R, i0 + u * SELP_NT + t)];
+#pragma unroll
+        for (int u = 0; u < SELP_RU; ++u) {
+            const int i = i0 + u * SELP_NT + t;
+            if (i < P.R) sp_rat[i] = x[u];
+        }
+    }
     const int status = cur.status, seq = cur.pad[2], buf = cur.pad[3] & 1;
     const int nsel = P.nblk;
     if (b == 0 && t == 0) *P.st = cur;                        // the host's copy: one launch behind
@@ -426,9 +563,6 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F)
     const size_t ld = (size_t)P.ld, fld = (size_t)P.R;
     const double* __restrict__ src = buf ? F.T1 : P.T;
     double* __restrict__ prown = F.pring + (size_t)lm * ld;
-    double* __restrict__ facn = F.fring + (size_t)lm * fld;
-    const double* __restrict__ rhsc = c ? F.rhs1 : P.rhsbuf;
-    double* __restrict__ rhsn = c ? P.rhsbuf : F.rhs1;
     const int m = R - 1;
     const int iter = cur.iter, primal_count = cur.primal_count;
     const int q = cur.qn;
@@ -446,70 +580,17 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F)
     const double* __restrict__ orow = src + (size_t)m * ld;
     const int per = (C + nsel - 1) / nsel;
     const int j0 = b * per, j1 = min(C, j0 + per);
-    double fs = 0.0;
     double pqv = 0.0, pfmv = 0.0;                            // T_s[r_s,q] / pivot and T_s[m,q_s] of pending pivot `ks`
     double ov0 = 0.0, pc0[SELP_PMAX];                        // objective row and pending pivot rows at this lane's first column
 #pragma unroll
     for (int k = 0; k < SELP_PMAX; ++k) pc0[k] = 0.0;
     if (final_status == LPX_RUNNING) {
-        // T_{k+1}[i,q] and T_{k+1}[i,C-1] as the sweep stores them: the column through every pending pivot (row r_s: the
-        // normalised pivot row), the RHS column kept current in rhsc up to the newest pending pivot, which is applied here
-        const int sn = fp_slot(lm, n, n - 1, ring);
-        const int rl = n ? cur.r : -1;                       // the newest pending pivot is the record's
-        const double prhs = n ? F.pring[(size_t)sn * ld + (C - 1)] : 0.0;
+        // round 2: the row phase's operands that do not depend on r, in flight behind the scan
         if (n > 0) {
             pqv = F.pring[kslot * ld + q];
             pfmv = F.fring[kslot * fld + m];
             rsv = F.rring[kslot];
         }
-        for (int i0 = 0; i0 < R; i0 += SELP_PASS_ROWS) {
-            double v[SELP_U], h[SELP_U], fl[SELP_U];
-#pragma unroll
-            for (int u = 0; u < SELP_U; ++u) {
-                const int i = min(R - 1, i0 + u * SELP_NT + t);  // clamped, not guarded: a guarded load waits for its own branch
-                v[u] = src[(size_t)i * ld + q]; h[u] = rhsc[i]; fl[u] = 0.0;
-            }
-            LPX_FS_TRIP(i0 / SELP_PASS_ROWS);
-            // oldest first, SELP_SB pivots' factors in flight together (past the newest: its factors again, unused); the newest
-            // pivot's factors are kept for the RHS correction
-            for (int s0 = 0; s0 < n; s0 += SELP_SB) {
-                double f[SELP_SB][SELP_U];
-#pragma unroll
-                for (int k = 0; k < SELP_SB; ++k) {
-                    const double* __restrict__ fac = F.fring + pslot(s0 + k) * fld;
-#pragma unroll
-                    for (int u = 0; u < SELP_U; ++u) f[k][u] = fac[min(R - 1, i0 + u * SELP_NT + t)];
-                }
-#pragma unroll
-                for (int k = 0; k < SELP_SB; ++k) {
-                    if (s0 + k < n) {
-                        const double pq = lane_f64(pqv, s0 + k);
-                        const int rs = prs(s0 + k);
-#pragma unroll
-                        for (int u = 0; u < SELP_U; ++u) {
-                            const int i = min(R - 1, i0 + u * SELP_NT + t);
-                            fl[u] = f[k][u];
-                            const double nv = v[u] - fl[u] * pq;     // mul, then sub: contraction is off
-                            v[u] = i == rs ? pq : nv;
-                        }
-                    }
-                }
-            }
-            LPX_FS_W(2);
-#pragma unroll
-            for (int u = 0; u < SELP_U; ++u) {
-                const int i = i0 + u * SELP_NT + t;
-                if (i < R) {
-                    const double dn = v[u];
-                    const double nm = n == 0 ? h[u] : (i == rl ? prhs : h[u] - fl[u] * prhs);
-                    sp_rat[i] = dn > P.eps ? nm / dn : __builtin_inf();  // ChooseLeaving's ratio, :229-241
-                    if (b == 0) { facn[i] = dn; rhsn[i] = nm; }          // factors of pivot k+1, numerators of the test after it
-                    if (i == m) s_fs = dn;                               // T_{k+1}[m,q]: row m belongs to exactly one lane
-                }
-            }
-            LPX_FS(3);
-        }
-        // the row phase's operands that do not depend on r, in flight behind the scan
         {
             const int jc = min(j0 + t, C - 1);
             ov0 = orow[jc];
@@ -522,9 +603,9 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F)
                 for (int k = SELP_SB; k < SELP_PMAX; ++k) pc0[k] = F.pring[pslot(k) * ld + jc];
             }
         }
-        __syncthreads();                                     // the ratios are complete
+        LPX_FS(1);
+        __syncthreads();                                     // the ratios are in LDS
         LPX_FS(3);
-        fs = s_fs;
         r = block_hysteresis_segments<SELP_NT / 64>(m, P.tol_primal, CompactRatio{sp_rat});
         LPX_FS(4);
         if (r < 0) final_status = LPX_UNBOUNDED;
@@ -675,7 +756,25 @@ static hipError_t launch_pivot_select_ws(const FusedParams& f, hipStream_t s, hi
     return launch_k(lpx_pivot_select_ws<6, 4>, dim3(f.P.nblk), dim3(FP_NT), 0, s, e0, e1, f);
 }
 
-hipError_t launch_pivot_fused(const FusedParams& f0, long long L, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+// The select-only step of handles above SELP_MIN_MB with at most SELP_LDS_ROWS rows: the column launch, then the row launch.  An
+// event pair brackets both (e0 in front of the first, e1 behind the second).
+static hipError_t launch_pivot_select_pair(const FusedParams& f, double* rat, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    const dim3 gc((f.P.R + SELC_ROWS - 1) / SELC_ROWS), gr(f.P.nblk);        // the column grid follows the capacity
+    const size_t lds = sizeof(double) * (size_t)f.P.R;
+    if (e0 && e1) {
+        hipExtLaunchKernelGGL(lpx_pivot_ratio, gc, dim3(SELC_ROWS), 0, s, e0, nullptr, 0, f, rat);
+        hipExtLaunchKernelGGL(lpx_pivot_select, gr, dim3(SELP_NT), lds, s, nullptr, e1, 0, f, (const double*)rat);
+    } else {
+        hipLaunchKernelGGL(lpx_pivot_ratio, gc, dim3(SELC_ROWS), 0, s, f, rat);
+        hipLaunchKernelGGL(lpx_pivot_select, gr, dim3(SELP_NT), lds, s, f, (const double*)rat);
+    }
+    return hipGetLastError();
+}
+
+bool pivot_select_is_pair(int ld, int R) { return R <= SELP_LDS_ROWS && tableau_bytes(ld, R) > ((size_t)SELP_MIN_MB << 20); }
+
+hipError_t launch_pivot_fused(const FusedParams& f0, double* rat, long long L, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
 {
     FusedParams f = f0;
     const int d = f.defer;
@@ -684,15 +783,14 @@ hipError_t launch_pivot_fused(const FusedParams& f0, long long L, hipStream_t s,
     const bool sweep = L > 0 && L % d == 0;
     const int ld = f.P.ld, R = f.P.R;
     if (!sweep) {
-        // Ratios in LDS while the handle's rows fit the cap, through the workspace beyond it -- and at small sizes: measured on
-        // MI355X with one pass of 9 rows per lane, the LDS form ran the 403 MB headline 5 % faster (select-only launch 24.3 ->
-        // 22.3 us) and config 2's 25 MB streaming loop (d = 4, 1 to 3 pivots pending, 1025 rows) 22 % slower (82.4 k -> 64.0 k
-        // pivots/s: it fetches SELP_SB factor columns whatever n is).  64 MB is not a measured crossover: nothing between 25 and
-        // 403 MB was run, so the switch sits where the depth default changes (PIVOT_DEFER_LARGE_BYTES, lpx_tableau.cpp) and up to
-        // 64 MB a handle runs exactly what it ran before.  The form pays by its pending count, not by size: at d = 2 (one pivot
-        // pending) the stamped launch on the 403 MB LP was 14 % longer than the old form's, so a handle above 64 MB run with
-        // LPX_PIVOT_DEFER = 2 to 4 is probably slower than it was; the default there is 12.
-        if (R <= SELP_LDS_ROWS && tableau_bytes(ld, R) > ((size_t)SELP_MIN_MB << 20)) return launch_k(lpx_pivot_select, dim3(f.P.nblk), dim3(SELP_NT), sizeof(double) * (size_t)R, s, e0, e1, f);
+        // The pair (ratios through the handle's ratio buffer into LDS) while the handle's rows fit the cap, the one-launch form
+        // through the workspace beyond it -- and at small sizes: the pair's predecessor (one launch, ratios in LDS, SELP_SB factor
+        // columns fetched whatever n is) ran the 403 MB headline 5 % faster than the workspace form and config 2's 25 MB streaming
+        // loop (d = 4, 1 to 3 pivots pending, 1025 rows) 22 % slower (82.4 k -> 64.0 k pivots/s).  64 MB is not a measured
+        // crossover: nothing between 25 and 403 MB was run, so the switch sits where the depth default changes
+        // (PIVOT_DEFER_LARGE_BYTES, lpx_tableau.cpp) and up to 64 MB a handle runs exactly what it ran before.  Whether the pair,
+        // which fetches only the n live factor columns and costs a kernel boundary, would serve the small handles too was not run.
+        if (pivot_select_is_pair(ld, R)) return rat ? launch_pivot_select_pair(f, rat, s, e0, e1) : hipErrorInvalidValue;
         return launch_pivot_select_ws(f, s, e0, e1);
     }
     const int rows = fp_rows(d);
@@ -716,7 +814,7 @@ hipError_t launch_pivot_flush(const FusedParams& f, int buf, int n, int slot0, h
     return hipGetLastError();
 }
 
-// once per process (ensure_device): the dynamic LDS lpx_pivot_select may ask for
+// once per process (ensure_device): the dynamic LDS lpx_pivot_select (the row launch) may ask for
 hipError_t pivot_fused_init()
 {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(lpx_pivot_select), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * SELP_LDS_ROWS);

@@ -343,8 +343,9 @@ bool lpx::fused_buffers(lpx_tableau* t)
     if (t->fused_off) return false;
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t tb = sizeof(double) * (size_t)t->Rcap * t->ld;
-    const size_t sz[] = { up(sizeof(double) * t->ld), up(sizeof(double) * t->Rcap), up(2 * sizeof(DevState)) };
-    if (malloc_retry((void**)&t->fT, tb) != hipSuccess || malloc_retry((void**)&t->fslab, sz[0] + sz[1] + sz[2]) != hipSuccess) {
+    const size_t sz[] = { up(sizeof(double) * t->ld), up(sizeof(double) * t->Rcap), up(2 * sizeof(DevState)),
+                          up(sizeof(double) * ((size_t)t->Rcap + 1)) };
+    if (malloc_retry((void**)&t->fT, tb) != hipSuccess || malloc_retry((void**)&t->fslab, sz[0] + sz[1] + sz[2] + sz[3]) != hipSuccess) {
         (void)hipGetLastError();
         hipFree(t->fT); hipFree(t->fslab);
         t->fT = nullptr; t->fslab = nullptr; t->fused_off = true;
@@ -353,17 +354,19 @@ bool lpx::fused_buffers(lpx_tableau* t)
     t->fprow = (double*)t->fslab;
     t->frhs = (double*)(t->fslab + sz[0]);
     t->frec = (DevState*)(t->fslab + sz[0] + sz[1]);
+    t->frat = (double*)(t->fslab + sz[0] + sz[1] + sz[2]);
     hipMemsetAsync(t->fT, 0, tb, t->stream);
-    hipMemsetAsync(t->fslab, 0, sz[0] + sz[1] + sz[2], t->stream);
+    hipMemsetAsync(t->fslab, 0, sz[0] + sz[1] + sz[2] + sz[3], t->stream);
     return true;
 }
 
 namespace {
 
-// measured on MI355X with the select-only launch at 24.3 us: 4097 x 12289 (403 MB) 118.9 us per pivot at d = 1,
-// 34.9 at 12, 35.2 at 16 (the sweep 150 against 164 us); 1025 x 3073 (25 MB) 66 k pivots/s at d = 1, 79 k at 2, 82 k at 4, 80 k
-// at 8.  With the launch at 22.3 us (lpx_pivot_select in one pass of 9 rows per lane, handles above 64 MB) d = 12 ran 33.2 us per
-// pivot; the other depths, and every depth with that kernel in passes of 3 rows per lane as it stands: not measured.  Up to 64 MB the select-only kernel is the one these figures were taken with
+// measured on MI355X with the select-only launch in one kernel at 24.3 us: 4097 x 12289 (403 MB) 118.9 us per
+// pivot at d = 1, 34.9 at 12, 35.2 at 16 (the sweep 150 against 164 us); 1025 x 3073 (25 MB) 66 k pivots/s at d = 1, 79 k at 2,
+// 82 k at 4, 80 k at 8.  With the select-only step of handles above 64 MB in two launches (lpx_pivot_ratio + lpx_pivot_select,
+// 14.2 us together): 28.4 us per pivot at d = 8, 24.5 at 12, 23.0 at 16 -- d = 16 measured once, 6 % ahead; the default stays 12
+// until it has alternating runs of its own.  Up to 64 MB the select-only kernel is the one the 25 MB figures were taken with
 static constexpr int PIVOT_DEFER_LARGE = 12, PIVOT_DEFER_SMALL = 4;
 static constexpr size_t PIVOT_DEFER_LARGE_BYTES = (size_t)64 << 20;
 // Pivots per sweep of run_fused (LPX_PIVOT_DEFER=d, read once; DESIGN.md 4.1 has the measured table behind the default).
@@ -388,9 +391,10 @@ static int defer_ring(lpx_tableau* t, int d)
     return 0;
 }
 
-// Primal loop with ONE launch per pivot: launch L selects pivot L; every d-th one (a positive multiple of d) is also the
+// Primal loop with ONE step per pivot: step L selects pivot L; every d-th one (a positive multiple of d) is also the
 // sweep that applies the d pivots selected before it, out of place (lpx_pivot_fused<d>), the others select only
-// (lpx_pivot_select).  The state record the host polls is one launch behind the device's, so the loop gets a few iterations
+// (lpx_pivot_ratio + lpx_pivot_select, two kernels, on handles above 64 MB; lpx_pivot_select_ws, one, on the others --
+// lpx_stats.launches counts steps either way).  The state record the host polls is one launch behind the device's, so the loop gets a few iterations
 // of slack; when it ends, the pivots still pending are applied (lpx_pivot_flush, into buffer 0), or the tableau, when none
 // are, may sit in the second buffer and is brought home (a device-to-device copy of the live rows, ~0.1 ms per 400 MB).
 static int run_fused(lpx_tableau* t, const SelParams& p, const lpx_run_opts* o, lpx_stats* stats, int start_iter)
@@ -410,11 +414,12 @@ static int run_fused(lpx_tableau* t, const SelParams& p, const lpx_run_opts* o, 
     // number 0, so the loop proper starts at 1 -- in the captured graph too (it is captured before the prologue runs, hence
     // the counter is preset), and a graph batch is a multiple of 2d so that every replay starts where the capture did.
     auto count = std::make_shared<long long>(1);
-    c.enqueue_iter = [f, count](hipStream_t s, hipEvent_t e0, hipEvent_t e1) -> int {
-        LPX_HIP_TRY(launch_pivot_fused(f, *count, s, e0, e1)); ++*count; return 0; };
+    double* rat = t->frat;
+    c.enqueue_iter = [f, rat, count](hipStream_t s, hipEvent_t e0, hipEvent_t e1) -> int {
+        LPX_HIP_TRY(launch_pivot_fused(f, rat, *count, s, e0, e1)); ++*count; return 0; };
     // the prologue also selects the first pivot, so that every launch of the loop proper has a pivot before it
-    c.prologue = [f, count](hipStream_t s) -> int {
-        LPX_HIP_TRY(launch_fused_init(f, s)); LPX_HIP_TRY(launch_pivot_fused(f, 0, s)); *count = 1; return 0; };
+    c.prologue = [f, rat, count](hipStream_t s) -> int {
+        LPX_HIP_TRY(launch_fused_init(f, s)); LPX_HIP_TRY(launch_pivot_fused(f, rat, 0, s)); *count = 1; return 0; };
     c.launches_per_iter = 1;
     c.sweep_launch = [d](long long k) { return (k + 1) % d == 0; };      // k-th launch of the loop proper is launch k + 1
     c.start_iter = start_iter;

@@ -1,11 +1,12 @@
-"""Diagnostic (not part of the product): where does the select-only launch of the deferred-pivot primal loop (lpx_pivot_select,
-run_fused) spend its cycles?  Needs the -DLPX_STAMPS build (make -C linear_programming_solver_lpr381_amd/csrc stamps):
+"""Diagnostic (not part of the product): where do the two launches of the select-only step of the deferred-pivot primal loop
+(lpx_pivot_ratio, the column launch, and lpx_pivot_select, the row launch; run_fused) spend their cycles?  Needs the -DLPX_STAMPS build (make -C linear_programming_solver_lpr381_amd/csrc stamps):
 
     LPX_LIB_PATH=.../csrc/build/liblpx_stamps.so python tools/diag_pivot_select_stamps.py [m n [pivots [depths]]]
 
 Runs the bench LP (m = 4096, n = 8192: tableau 4097 x 12289) for `pivots` pivots (default 600) after a warm-up run of the same
 length, once per depth (default 12 and 2; LPX_PIVOT_DEFER is read once per process, so each depth is a child process), and
-prints cycles and microseconds per phase of workgroup 0's first wave.  The stamps wait for that wave's loads at the end of the
+prints cycles and microseconds per phase of workgroup 0's first wave, one table per kernel, each with the kernel's own
+s_memrealtime span.  The stamps wait for that wave's loads at the end of the
 phases that only issue loads, which serialises what the shipped kernel overlaps: the phases add up to more than the unstamped
 launch takes (the kernel trace has that figure); they say where the time is, not how long the launch is.
 
@@ -19,8 +20,12 @@ import os
 import subprocess
 import sys
 
-NAMES = ["record load and branch", "column gather (all trips)", "pending chain", "ratio store and barrier", "scan (with reload)",
-         "piv chain", "row loop", "wave and hand-off reduction", "tail stores"]
+# row launch (and, above SELP_LDS_ROWS rows, the one-launch form lpx_pivot_select_ws, whose slots 1 - 3 are the column gather, the
+# pending chain and the ratio store): lpx_g_stamps[8 + k]
+NAMES = ["record, shape, ratios -> LDS", "round 2 issue (row operands)", "(one-launch form only)", "barrier", "scan (from LDS)",
+         "piv chain", "row loop", "block and hand-off reduction", "tail stores"]
+# column launch: lpx_g_stamps[21 + k]
+COL_NAMES = ["record load and leave tests", "round 2 (column, RHS, factors, scalars)", "chain, ratio and stores"]
 
 
 def child(m, n, pivots):
@@ -45,7 +50,7 @@ def child(m, n, pivots):
     v = list(hs)[8:]
     calls, rt, npend = v[21], v[20], v[22]
     d = os.environ.get("LPX_PIVOT_DEFER", "default")
-    print(f"d = {d}: {T.shape[0]} x {T.shape[1]}, pivots={st['pivots']} launches={st['launches']} select-only launches stamped={calls} "
+    print(f"d = {d}: {T.shape[0]} x {T.shape[1]}, pivots={st['pivots']} launches={st['launches']} row launches stamped={calls} "
           f"(mean pending pivots {npend / max(calls, 1):.2f})  loop {1e3 * st['loop_ms'] / max(st['pivots'], 1):.2f} us/pivot (stamped build)")
     if not calls:
         print("  no stamps: is LPX_LIB_PATH the -DLPX_STAMPS library?")
@@ -55,8 +60,19 @@ def child(m, n, pivots):
     print(f"  in-kernel clock ~{clk:.2f} GHz; stamped {tot / calls:.0f} cycles = {rt / calls / 100:.2f} us per launch, wave 0 of workgroup 0")
     for nm, x in zip(NAMES, v[:9]):
         print(f"  {nm:30s} {x / calls:9.0f} cycles {x / calls / clk / 1e3 if clk else 0:7.2f} us {100 * x / tot:5.1f}%")
-    trips = v[9] / calls
-    print(f"  gather trips per launch {trips:.2f}: first {v[10] / calls:.0f}, second {v[11] / calls:.0f}, later {v[12] / calls:.0f} cycles")
+    if v[9]:
+        print(f"  gather trips per launch {v[9] / calls:.2f}: first {v[10] / calls:.0f}, second {v[11] / calls:.0f}, later {v[12] / calls:.0f} cycles")
+    w = list(hs)[21:27]
+    ccalls, crt, cpend = w[4], w[3], w[5]
+    if not ccalls:
+        print("  column launch: no stamps (the one-launch form ran)")
+        return
+    ctot = sum(w[:3])
+    cclk = ctot / (crt / 100e6) / 1e9 if crt else 0.0
+    print(f"  column launch (lpx_pivot_ratio): stamped launches={ccalls} (mean pending pivots {cpend / ccalls:.2f}); in-kernel clock ~{cclk:.2f} GHz; "
+          f"stamped {ctot / ccalls:.0f} cycles = {crt / ccalls / 100:.2f} us per launch, wave 0 of workgroup 0")
+    for nm, x in zip(COL_NAMES, w[:3]):
+        print(f"  {nm:40s} {x / ccalls:9.0f} cycles {x / ccalls / cclk / 1e3 if cclk else 0:7.2f} us {100 * x / ctot:5.1f}%")
 
 
 def plain_run(pivots, m=4096, n=8192, reps=1, prof=0):

@@ -14,7 +14,7 @@ counts the functions in front of the kernel in its file: a kernel that changed f
 
 Per kernel: registers, scratch, LDS and occupancy from the code-object metadata, a histogram of the mnemonics that matter to a
 streaming FP64 kernel (loads and stores split by `nt`), and whether the two instruction streams are the same text, the same
-up to register numbers and labels, or different.  Exit status 1 when a figure that admits no exception moved (VGPRs, scratch,
+up to register numbers and labels, or different; a kernel that only one side has gets one row of its own figures.  Exit status 1 when a figure that admits no exception moved (VGPRs, scratch,
 LDS, occupancy, FP64 counts -- v_fma_f64 among them -- and load and store counts per policy against the first file, or any
 v_fma_f64 in a kernel without a division: with one, only the equal count says that the tile got none).
 """
@@ -168,6 +168,10 @@ def main():
                 bad.append("%s: %s %d -> %d" % (k, c, a["hist"][c], b["hist"][c]))
         if b["hist"]["v_fma_f64"] and not b["hist"]["v_div"]:      # a division's expansion is the one place an FMA belongs
             bad.append("%s: v_fma_f64 present" % k)
+    for k in sorted(set(A) ^ set(B), key=order):                   # a kernel only one side has: its own figures, nothing to compare
+        side, r = ("parent", A[k]) if k in A else ("branch", B[k])
+        row = [k, side] + [str(r["meta"].get(f, 0)) for f in META] + [str(r["occ"])] + [str(r["hist"][c]) for c in COLS]
+        print("| " + " | ".join(row) + " | %d | %s only |" % (len(r["body"]), side))
     print()
     print("strict figures (VGPR, AGPR, scratch, LDS, occupancy, loads and stores per policy, FP64 counts, no FMA beside a division): " +
           ("all equal" if not bad else "MOVED"))
