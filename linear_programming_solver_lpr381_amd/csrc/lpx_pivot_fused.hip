@@ -67,6 +67,11 @@ __global__ __launch_bounds__(SEL_NT) void lpx_fused_init(FusedParams F)
 // rows per sweep wave: each pending pivot row a lane loads (from L2) serves ROWS rows of the stream; three rows as in r03 while
 // one or two pivots are applied, eight beyond (at three rows the pivot-row reads grew the d = 8 sweep from 118 to 162 us; at
 // eight, 140 us).  Twelve and sixteen rows spill 12-96 VGPRs inside the 80 the select half leaves (waves_per_eu(6) below).
+// tools/kbench/deferred_sweep.hip (profiles/r14_kbench_deferred_sweep.txt) confirmed those reads as what a pending pivot costs:
+// with the pairs out of a register this tile runs 130 us at d = 8, 12 and 16 alike (shipped: 134-138, 144, 156 us).  The pending
+// rows staged in LDS once per workgroup (4 rows x 4 waves on one column window) ran 123 / 126 / 132 us there and 128 / 135 /
+// 144-147 us in this kernel, 9-12 % under this tile at equal depth -- and 2.6-3.8 % on the headline at d = 16, short of the 5 %
+// a change of this loop is held to, so the tile stays (DESIGN.md 4.1 and 9.9 have the numbers and what is left to try).
 __host__ __device__ constexpr int fp_rows(int D) { return D <= 2 ? UPDS_ROWS : 8; }
 __host__ __device__ constexpr int fp_rec(int buf, int npend, int slot0) { return buf | (npend << 1) | (slot0 << 8); }
 // ring slot of pending pivot s (0 = oldest) of n before the launch with ring index lm
@@ -352,7 +357,8 @@ __device__ __forceinline__ void fused_sweep(const FusedParams& F, int ncw, int n
 
 // waves_per_eu(6): 80 VGPRs.  The sweep half alone needs 28 (D = 1) to 64 (D = 16); the select half sets the budget and spills
 // (code-object metadata): 2 VGPRs in every streaming form but D = 10 (14) and D = 15 (6), 2-4 in _c<1..8>, 8-14 in _c<9..16>
-// -- the defaults run lpx_pivot_fused<12> (2) at 403 MB and lpx_pivot_fused_c<4> (2) at 25 MB; _c<12> (14) serves 64-152 MB.
+// -- the defaults run lpx_pivot_fused<16> (2) above 292 MiB (the 403 MB headline), lpx_pivot_fused<12> (2) from 152 MB to there,
+// _c<12> (14) from 64 to 152 MB and lpx_pivot_fused_c<4> (2) up to 64 MB (config 2's 25 MB).
 // Without the hint the r03 kernel took 86 VGPRs = 5 waves per SIMD (8.46 k pivots/s against 8.57 k at 6).
 template <int D>
 __global__ __launch_bounds__(FP_NT) __attribute__((amdgpu_waves_per_eu(6))) void lpx_pivot_fused(FusedParams F, int ncw, int nunits, int mixmod)
@@ -772,6 +778,7 @@ static hipError_t launch_pivot_select_pair(const FusedParams& f, double* rat, hi
     return hipGetLastError();
 }
 
+size_t pivot_stream_bytes() { return UPD_STREAM_BYTES; }
 bool pivot_select_is_pair(int ld, int R) { return R <= SELP_LDS_ROWS && tableau_bytes(ld, R) > ((size_t)SELP_MIN_MB << 20); }
 
 hipError_t launch_pivot_fused(const FusedParams& f0, double* rat, long long L, hipStream_t s, hipEvent_t e0, hipEvent_t e1)

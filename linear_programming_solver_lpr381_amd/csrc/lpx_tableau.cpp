@@ -365,9 +365,12 @@ namespace {
 // measured on MI355X with the select-only launch in one kernel at 24.3 us: 4097 x 12289 (403 MB) 118.9 us per
 // pivot at d = 1, 34.9 at 12, 35.2 at 16 (the sweep 150 against 164 us); 1025 x 3073 (25 MB) 66 k pivots/s at d = 1, 79 k at 2,
 // 82 k at 4, 80 k at 8.  With the select-only step of handles above 64 MB in two launches (lpx_pivot_ratio + lpx_pivot_select,
-// 14.2 us together): 28.4 us per pivot at d = 8, 24.5 at 12, 23.0 at 16 -- d = 16 measured once, 6 % ahead; the default stays 12
-// until it has alternating runs of its own.  Up to 64 MB the select-only kernel is the one the 25 MB figures were taken with
-static constexpr int PIVOT_DEFER_LARGE = 12, PIVOT_DEFER_SMALL = 4;
+// 14.2 us together): 28.4 us per pivot at d = 8, 24.5 at 12, 23.0 at 16.  d = 16 against d = 12 in alternating runs of the bench
+// (profiles/r14_sweep_bench.txt, three each, one call): 43.04-43.13 k against 39.97-40.24 k pivots/s, slowest against fastest
+// +7.0 % (a second call: 42.89-43.23 k) -- so handles that cannot live in the Infinity Cache (above UPD_STREAM_BYTES, 292 MiB)
+// run d = 16.  Between 64 MB and 292 MiB the depth stays 12: d = 16 on a handle of that size was not measured.  Up to 64 MB the
+// select-only kernel is the one the 25 MB figures were taken with
+static constexpr int PIVOT_DEFER_STREAM = 16, PIVOT_DEFER_LARGE = 12, PIVOT_DEFER_SMALL = 4;
 static constexpr size_t PIVOT_DEFER_LARGE_BYTES = (size_t)64 << 20;
 // Pivots per sweep of run_fused (LPX_PIVOT_DEFER=d, read once; DESIGN.md 4.1 has the measured table behind the default).
 static int pivot_defer(int ld, int R)
@@ -375,6 +378,7 @@ static int pivot_defer(int ld, int R)
     static const int forced = [] { const char* e = std::getenv("LPX_PIVOT_DEFER"); return e ? std::atoi(e) : 0; }();
     if (forced > 0) return std::min(forced, pivot_defer_max());
     const size_t bytes = sizeof(double) * (size_t)ld * (size_t)R;
+    if (bytes > pivot_stream_bytes()) return PIVOT_DEFER_STREAM;
     return bytes > PIVOT_DEFER_LARGE_BYTES ? PIVOT_DEFER_LARGE : PIVOT_DEFER_SMALL;
 }
 

@@ -1,0 +1,257 @@
+// Microbenchmark (diagnostic, not product code): what does a pending pivot cost the deferred sweep (lpx_pivot_fused<D>,
+// DESIGN.md 4.1), and does staging the pending pivot rows in LDS once per workgroup give it back?  The sweep alone: two
+// R x ld buffers, ping-pong, a synthetic ring of D normalised pivot rows and D factor columns, nontemporal loads, the mixed
+// store policy as shipped at 403 MB (the last row of a wave's tile through the cache, the others nontemporal); no select half.
+//   baseline     every wave a tile of its own (H rows x 128 columns), its D pairs loaded from the ring: H = 8 as shipped, H = 3
+//   diagnostic   one suspect removed each (they compute other values and never ship): (a) pairs from a kernel argument instead
+//                of a load, (b) factors from a kernel argument instead of scalar loads, (c) the arithmetic contracted to FMA
+//   candidates   the W waves of a workgroup on ONE 128-column window and W x H consecutive rows; the D x 128 doubles of the
+//                pending rows go to LDS once per workgroup (global_load_dwordx4 + ds_write_b128, in front of the tile's own loads),
+//                every wave reads its pairs back with ds_read_b128; factors by scalar loads or staged too
+// Every kernel is built for 6 waves per SIMD like the product's (whose select half sets that budget) and, the candidates, for 8.
+// Each non-diagnostic variant's output of one sweep is compared with the shipped tile's through a checksum; a row that
+// DIFFERS makes the exit status 1.
+// hipcc --offload-arch=gfx950 -O3 -ffp-contract=off deferred_sweep.hip -o deferred_sweep ; ./deferred_sweep [R C reps]
+#include <hip/hip_runtime.h>
+#include <cstdio>
+#include <cstdlib>
+#include <functional>
+#include <string>
+#include <vector>
+
+#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); exit(1); } } while (0)
+
+typedef double d2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ d2 ld_nt(const double* p) { return __builtin_nontemporal_load(reinterpret_cast<const d2*>(p)); }
+__device__ __forceinline__ void st_nt(double* p, d2 v) { __builtin_nontemporal_store(v, reinterpret_cast<d2*>(p)); }
+// default policy, as the product spells it (two aligned doubles that the backend merges: a vector store next to nontemporal
+// ones can lose or gain the policy when the compiler merges code)
+__device__ __forceinline__ void st_df(double* p, d2 v) { double* q = (double*)__builtin_assume_aligned((void*)p, 16); q[0] = v.x; q[1] = v.y; }
+
+enum { PAIR_GLOBAL = 0, PAIR_CONST = 1, PAIR_LDS = 2 };
+enum { FAC_SCALAR = 0, FAC_CONST = 1, FAC_LDS = 2 };
+
+struct Args {
+    const double* src; double* dst; const double* pring; const double* fring;
+    int ld, R, ncw, nunits;
+    double cp, cf;           // the diagnostic variants' constants
+};
+
+template <int D, int H, bool FMA>
+__device__ __forceinline__ void apply(d2 (&v)[H], d2 p, const double (&f)[H])
+{
+#pragma unroll
+    for (int k = 0; k < H; ++k) {
+        if (FMA) { v[k].x = __builtin_fma(-f[k], p.x, v[k].x); v[k].y = __builtin_fma(-f[k], p.y, v[k].y); }
+        else { v[k].x = v[k].x - f[k] * p.x; v[k].y = v[k].y - f[k] * p.y; }      // mul, then sub: contraction is off
+    }
+}
+template <int H>
+__device__ __forceinline__ void store_mixed(double* db, size_t ld, const d2 (&v)[H])
+{
+#pragma unroll
+    for (int k = 0; k < H - 1; ++k) st_nt(db + (size_t)k * ld, v[k]);
+    st_df(db + (size_t)(H - 1) * ld, v[H - 1]);
+}
+// rows of a tile that runs past R, one at a time
+template <int D, int H>
+__device__ __forceinline__ void rowwise(const Args& a, int row0, int col)
+{
+    const size_t ld = (size_t)a.ld;
+#pragma unroll 1
+    for (int k = 0; k < H; ++k) {
+        const int i = row0 + k;
+        if (i >= a.R) break;
+        d2 o = ld_nt(a.src + (size_t)i * ld + col);
+#pragma unroll 1
+        for (int s = 0; s < D; ++s) {
+            const d2 p = *reinterpret_cast<const d2*>(a.pring + (size_t)s * ld + col);
+            const double f = a.fring[(size_t)s * a.R + i];
+            o.x = o.x - f * p.x; o.y = o.y - f * p.y;
+        }
+        st_nt(a.dst + (size_t)i * ld + col, o);
+    }
+}
+
+// every wave a tile of its own: the shipped shape (W = 4 waves per workgroup, units in dispatch order, column window fastest)
+template <int D, int H, int W, int PAIR, int FACM, bool FMA>
+__device__ __forceinline__ void sweep_own(const Args& a)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int unit = (int)blockIdx.x * W + wave;
+    if (unit >= a.nunits) return;
+    const int cw = unit % a.ncw, rb = unit / a.ncw;
+    const int col = cw * 128 + lane * 2;
+    if (col >= a.ld) return;
+    const int row0 = rb * H;
+    if (row0 >= a.R) return;
+    const size_t ld = (size_t)a.ld;
+    if (row0 + H > a.R) { rowwise<D, H>(a, row0, col); return; }
+    d2 v[H];
+#pragma unroll
+    for (int k = 0; k < H; ++k) v[k] = ld_nt(a.src + (size_t)(row0 + k) * ld + col);
+#pragma unroll
+    for (int s = 0; s < D; ++s) {
+        d2 p; double f[H];
+        if (PAIR == PAIR_CONST) { p.x = a.cp; p.y = a.cp; } else p = *reinterpret_cast<const d2*>(a.pring + (size_t)s * ld + col);
+#pragma unroll
+        for (int k = 0; k < H; ++k) f[k] = FACM == FAC_CONST ? a.cf : a.fring[(size_t)s * a.R + row0 + k];
+        apply<D, H, FMA>(v, p, f);
+    }
+    store_mixed<H>(a.dst + (size_t)row0 * ld + col, ld, v);
+}
+
+// the W waves of a workgroup on one column window, W x H consecutive rows; the pending rows' window through LDS
+template <int D, int H, int W, int FACM>
+__device__ __forceinline__ void sweep_staged(const Args& a)
+{
+    constexpr int NST = (D + W - 1) / W;                     // pending rows a wave stages (the last ones may be repeats: no branch)
+    __shared__ d2 s_p[NST * W * 64];
+    __shared__ double s_f[FACM == FAC_LDS ? D * W * H : 1];
+    const int t = threadIdx.x, lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int cw = (int)blockIdx.x % a.ncw, rbw = (int)blockIdx.x / a.ncw;     // the grid is exactly ncw x row blocks
+    const int col = cw * 128 + lane * 2;
+    const int colc = min(col, a.ld - 2);                     // clamped, not guarded: every lane loads, only the stores are guarded
+    const int row0 = (rbw * W + wave) * H;
+    const size_t ld = (size_t)a.ld;
+    const bool full = row0 + H <= a.R;                       // wave-uniform
+    // staging: wave w fetches pending rows w, w + W, ... (from L2, issued first so that the LDS stores need not wait for the
+    // tile's HBM loads behind them); every wave of the workgroup reaches the barrier
+    d2 st[NST];
+#pragma unroll
+    for (int j = 0; j < NST; ++j) st[j] = *reinterpret_cast<const d2*>(a.pring + (size_t)min(j * W + wave, D - 1) * ld + colc);
+    d2 v[H];                                                 // rows clamped too: straight-line code up to the barrier, exact wait counts
+#pragma unroll
+    for (int k = 0; k < H; ++k) v[k] = ld_nt(a.src + (size_t)min(row0 + k, a.R - 1) * ld + colc);
+#pragma unroll
+    for (int j = 0; j < NST; ++j) s_p[(j * W + wave) * 64 + lane] = st[j];
+    if (FACM == FAC_LDS) {
+        for (int e = t; e < D * W * H; e += W * 64) {
+            const int s = e / (W * H), i = min(rbw * W * H + e % (W * H), a.R - 1);
+            s_f[e] = a.fring[(size_t)s * a.R + i];
+        }
+    }
+    __syncthreads();
+    if (col >= a.ld || row0 >= a.R) return;
+    if (!full) { rowwise<D, H>(a, row0, col); return; }
+#pragma unroll
+    for (int s = 0; s < D; ++s) {
+        const d2 p = s_p[s * 64 + lane];
+        double f[H];
+#pragma unroll
+        for (int k = 0; k < H; ++k) f[k] = FACM == FAC_LDS ? s_f[s * W * H + wave * H + k] : a.fring[(size_t)s * a.R + row0 + k];
+        apply<D, H, false>(v, p, f);
+    }
+    store_mixed<H>(a.dst + (size_t)row0 * ld + col, ld, v);
+}
+
+template <int D, int H, int W, int PAIR, int FACM, bool FMA>
+__global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_own(Args a) { sweep_own<D, H, W, PAIR, FACM, FMA>(a); }
+template <int D, int H, int W, int FACM>
+__global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_staged6(Args a) { sweep_staged<D, H, W, FACM>(a); }
+template <int D, int H, int W, int FACM>
+__global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_staged8(Args a) { sweep_staged<D, H, W, FACM>(a); }
+
+__global__ void k_checksum(const unsigned long long* x, size_t n, unsigned long long* out)
+{
+    unsigned long long acc = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) acc += x[i] * (2 * i + 1);
+    atomicAdd(out, acc);
+}
+
+struct Variant { std::string name; int H, W; bool staged, ships; std::function<void(const Args&, dim3, hipStream_t)> launch; };
+
+template <int D>
+static void variants(std::vector<Variant>& vs)
+{
+    const std::string d = "d=" + std::to_string(D) + " ";
+#define OWN(H, PAIR, FACM, FMA, SHIPS, LABEL) vs.push_back({d + LABEL, H, 4, false, SHIPS, [](const Args& a, dim3 g, hipStream_t s) { hipLaunchKernelGGL((k_own<D, H, 4, PAIR, FACM, FMA>), g, dim3(256), 0, s, a); }})
+#define STG(K, H, W, FACM, LABEL) vs.push_back({d + LABEL, H, W, true, true, [](const Args& a, dim3 g, hipStream_t s) { hipLaunchKernelGGL((K<D, H, W, FACM>), g, dim3(W * 64), 0, s, a); }})
+    OWN(8, PAIR_GLOBAL, FAC_SCALAR, false, true, "baseline 8 rows, pairs from global (shipped)");
+    OWN(3, PAIR_GLOBAL, FAC_SCALAR, false, true, "baseline 3 rows, pairs from global");
+    OWN(8, PAIR_CONST, FAC_SCALAR, false, false, "diag (a) 8 rows, pairs constant");
+    OWN(8, PAIR_GLOBAL, FAC_CONST, false, false, "diag (b) 8 rows, factors constant");
+    OWN(8, PAIR_GLOBAL, FAC_SCALAR, true, false, "diag (c) 8 rows, FMA");
+    OWN(3, PAIR_CONST, FAC_SCALAR, false, false, "diag (a) 3 rows, pairs constant");
+    OWN(3, PAIR_GLOBAL, FAC_SCALAR, true, false, "diag (c) 3 rows, FMA");
+    STG(k_staged6, 3, 4, FAC_SCALAR, "staged H=3 W=4");
+    STG(k_staged6, 4, 4, FAC_SCALAR, "staged H=4 W=4");
+    STG(k_staged6, 8, 4, FAC_SCALAR, "staged H=8 W=4");
+    STG(k_staged6, 3, 8, FAC_SCALAR, "staged H=3 W=8");
+    STG(k_staged6, 4, 8, FAC_SCALAR, "staged H=4 W=8");
+    STG(k_staged6, 8, 8, FAC_SCALAR, "staged H=8 W=8");
+    STG(k_staged6, 3, 4, FAC_LDS, "staged H=3 W=4, factors staged");
+    STG(k_staged6, 4, 4, FAC_LDS, "staged H=4 W=4, factors staged");
+    STG(k_staged6, 3, 8, FAC_LDS, "staged H=3 W=8, factors staged");
+    STG(k_staged6, 4, 8, FAC_LDS, "staged H=4 W=8, factors staged");
+    STG(k_staged8, 3, 4, FAC_SCALAR, "staged H=3 W=4, 8 waves per SIMD");
+    STG(k_staged8, 4, 4, FAC_SCALAR, "staged H=4 W=4, 8 waves per SIMD");
+    STG(k_staged8, 3, 8, FAC_SCALAR, "staged H=3 W=8, 8 waves per SIMD");
+    STG(k_staged8, 4, 8, FAC_SCALAR, "staged H=4 W=8, 8 waves per SIMD");
+#undef OWN
+#undef STG
+}
+
+int main(int argc, char** argv)
+{
+    const int R = argc > 1 ? atoi(argv[1]) : 4097, C = argc > 2 ? atoi(argv[2]) : 12289, reps = argc > 3 ? atoi(argv[3]) : 40;
+    const int ld = (C + 15) / 16 * 16;
+    const size_t n = (size_t)R * ld;
+    constexpr int DMAX = 16;
+    double *A, *B, *A0, *pring, *fring; unsigned long long* sum;
+    CK(hipMalloc(&A, n * 8)); CK(hipMalloc(&B, n * 8)); CK(hipMalloc(&A0, n * 8));
+    CK(hipMalloc(&pring, (size_t)DMAX * ld * 8)); CK(hipMalloc(&fring, (size_t)DMAX * R * 8)); CK(hipMalloc(&sum, 8));
+    {
+        std::vector<double> h(n); for (size_t i = 0; i < n; ++i) h[i] = (double)((i * 2654435761u) % 1000) / 1000.0;
+        CK(hipMemcpy(A0, h.data(), n * 8, hipMemcpyHostToDevice));
+        std::vector<double> hp((size_t)DMAX * ld), hf((size_t)DMAX * R);
+        for (size_t i = 0; i < hp.size(); ++i) hp[i] = 1e-3 * (double)((i * 40503u) % 997) / 997.0;
+        for (size_t i = 0; i < hf.size(); ++i) hf[i] = 1e-3 * (double)((i * 9973u) % 991) / 991.0;
+        CK(hipMemcpy(pring, hp.data(), hp.size() * 8, hipMemcpyHostToDevice)); CK(hipMemcpy(fring, hf.data(), hf.size() * 8, hipMemcpyHostToDevice));
+    }
+    hipStream_t s; CK(hipStreamCreate(&s));
+    hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    const int ncw = (ld + 127) / 128;
+    const double bytes = 16.0 * R * C;
+    printf("R=%d C=%d ld=%d  tableau %.1f MB, algorithmic bytes per sweep %.1f MB, %d reps; checksum: one sweep against the shipped tile's\n", R, C, ld, 8.0 * R * ld / 1e6, bytes / 1e6, reps);
+    std::vector<Variant> vs;
+    variants<8>(vs); variants<12>(vs); variants<16>(vs);
+    int differs = 0;                                         // a shipping candidate whose sweep is not the shipped tile's: exit status 1
+    for (int pass = 0; pass < 2; ++pass) {
+        unsigned long long base = 0;
+        for (size_t vi = 0; vi < vs.size(); ++vi) {
+            const Variant& v = vs[vi];
+            Args a{}; a.pring = pring; a.fring = fring; a.ld = ld; a.R = R; a.ncw = ncw; a.cp = 1e-4; a.cf = 1e-4;
+            dim3 grid;
+            if (v.staged) { const int nrbw = (R + v.W * v.H - 1) / (v.W * v.H); a.nunits = ncw * nrbw; grid = dim3(ncw * nrbw); }
+            else { a.nunits = ncw * ((R + v.H - 1) / v.H); grid = dim3((a.nunits + v.W - 1) / v.W); }
+            CK(hipMemcpyAsync(A, A0, n * 8, hipMemcpyDeviceToDevice, s));
+            int it = 0;
+            auto launch = [&] { a.src = (it & 1) ? B : A; a.dst = (it & 1) ? A : B; v.launch(a, grid, s); ++it; };
+            launch();
+            CK(hipMemsetAsync(sum, 0, 8, s));
+            hipLaunchKernelGGL(k_checksum, dim3(2048), dim3(256), 0, s, (const unsigned long long*)B, n, sum);
+            unsigned long long got = 0;
+            CK(hipMemcpyAsync(&got, sum, 8, hipMemcpyDeviceToHost, s));
+            for (int i = 0; i < 3; ++i) launch();
+            CK(hipStreamSynchronize(s));
+            CK(hipEventRecord(e0, s));
+            for (int i = 0; i < reps; ++i) launch();
+            CK(hipEventRecord(e1, s));
+            CK(hipStreamSynchronize(s));
+            CK(hipGetLastError());
+            float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+            const double us = 1e3 * ms / reps;
+            if (v.name.find("(shipped)") != std::string::npos) base = got;
+            const char* ok = !v.ships ? "diagnostic" : (got == base ? "same bits" : "DIFFERS");
+            if (v.ships && got != base) ++differs;
+            printf("pass %d  %-52s %8.2f us  %7.1f GB/s  (%.3f of 8 TB/s)  %s\n", pass, v.name.c_str(), us, bytes / us / 1e3, bytes / us / 1e3 / 8000.0, ok);
+            fflush(stdout);
+        }
+    }
+    if (differs) printf("%d rows DIFFER from the shipped tile\n", differs);
+    return differs ? 1 : 0;
+}
