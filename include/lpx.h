@@ -911,6 +911,40 @@ int lpx_solve_bnb_bounded2(const lpx_problem* p, const double* lower /* [n] or N
 int lpx_solve_bounded_dual(const lpx_problem* p, const double* lower /* [n] or NULL = 0 */, const double* upper /* [n] or NULL = +inf */,
                            int flags, const lpx_solve_opts* o, lpx_result* out, lpx_bounded_info* info /* or NULL */);
 
+/* ---- the on-chip form of a node (not in the reference; csrc/lpx_bounded_node.hip) --
+ * lpx_bounded_node3(t, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, form, out): lpx_bounded_node2 with a choice of
+ * how the node is evaluated.  form = LPX_NODE_LAUNCHES is lpx_bounded_node2, bit for bit.  LPX_NODE_ONCHIP evaluates the whole
+ * node -- the bound edit, the dual-feasibility flips, the flagged dual loop with its rank-1 updates, the branch pick -- in ONE
+ * kernel launch of one workgroup with the live window in the LDS of one compute unit; the host makes one launch and one wait.
+ * Every output is bit-equal to the launches form on the same inputs: the record, the trace, the tableau, basis, flip, ub, lo,
+ * lpx_bounded_counts and the status (LPX_OPTIMAL, LPX_INFEASIBLE, LPX_ITER_LIMIT, LPX_CUTOFF), and so is everything read from the
+ * handle afterwards (lpx_tableau_download / _trace / _bound_state / _bounded_solution / _snapshot / _restore, a following node of
+ * either form).  LPX_NODE_AUTO is LPX_NODE_ONCHIP iff lpx_bounded_node_fits(R, C) for the live shape, else LPX_NODE_LAUNCHES.
+ * lpx_bounded_node_fits(R, C): pure host arithmetic, no device check.  1 iff R >= 2, C >= 1 and
+ *   8 * (R * (C | 1) + C + max(R, C)) <= 160 KiB - 2 KiB
+ * (the tile with an odd row stride, the bounds, one array shared by the ratios, the pivot column, the flip list and the pick; 2 KiB
+ * are kept for the kernel's reduction scratch).  It holds whenever R >= 2 and R*C + 2*(R + C) <= 18000.
+ * Argument errors are those of lpx_bounded_node2 with the new name in front, plus an unknown form; all are checked before any
+ * device check and leave the handle untouched, and so is LPX_NODE_ONCHIP on a shape that does not fit ("does not fit").  An
+ * unrepairable column and upper = +inf on a flipped column are found by the kernel, before it has touched the tableau: LPX_EINVAL
+ * with the messages of lpx_bounded_node2, the handle as it was.  resident = 1 stays LPX_EINVAL; batch, use_graph and profile are
+ * not read by the on-chip form.
+ *
+ * lpx_solve_bnb_bounded3(p, lower, upper, is_int, o, max_nodes, search_flags, node_form, out, info): lpx_solve_bnb_bounded2 whose
+ * nodes are lpx_bounded_node3(form = node_form) calls.  node_form = LPX_NODE_LAUNCHES is the existing driver with a bit-equal
+ * log; the other forms give the same log too.  An unknown node_form is LPX_EINVAL before any device check; LPX_NODE_ONCHIP with a
+ * root that does not fit is LPX_EINVAL with a message before the search starts. */
+#define LPX_NODE_LAUNCHES 0
+#define LPX_NODE_ONCHIP 1
+#define LPX_NODE_AUTO 2
+int lpx_bounded_node_fits(int R, int C);
+int lpx_bounded_node3(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const lpx_run_opts* o,
+                      int flags, double cutoff, int nint, const uint8_t* is_int /* [nint] or NULL = all */, double tol,
+                      int form, lpx_node_record* out);
+int lpx_solve_bnb_bounded3(const lpx_problem* p, const double* lower /* [n] or NULL = 0 */, const double* upper /* [n] */,
+                           const uint8_t* is_int /* [n] or NULL = all */, const lpx_solve_opts* o, int64_t max_nodes /* 0 = none */,
+                           int search_flags, int node_form, lpx_result* out, lpx_bnb_bounded_info* info /* or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -289,6 +289,17 @@ namespace Linear_Programming_Solver.Native
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_solve_bnb_bounded2(ref LpxProblem p, double* lower, double* upper, byte* is_int, ref LpxSolveOpts o,
                                                         long max_nodes, int search_flags, out LpxResult result, out LpxBnbBoundedInfo info);
+        // the on-chip form of a node: one launch per node with the tableau in LDS (form of lpx_bounded_node3; node_form of lpx_solve_bnb_bounded3)
+        public const int LPX_NODE_LAUNCHES = 0;
+        public const int LPX_NODE_ONCHIP = 1;
+        public const int LPX_NODE_AUTO = 2;
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int lpx_bounded_node_fits(int R, int C);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_bounded_node3(IntPtr t, int K, int* cols, double* lower, double* upper, IntPtr opts, int flags, double cutoff,
+                                                   int nint, byte* is_int, double tol, int form, out LpxNodeRecord record);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_bnb_bounded3(ref LpxProblem p, double* lower, double* upper, byte* is_int, ref LpxSolveOpts o,
+                                                        long max_nodes, int search_flags, int node_form, out LpxResult result, out LpxBnbBoundedInfo info);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_solve_bounded_dual(ref LpxProblem p, double* lower, double* upper, int flags, ref LpxSolveOpts o,
                                                         out LpxResult result, out LpxBoundedInfo info);

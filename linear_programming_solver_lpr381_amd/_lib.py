@@ -18,6 +18,8 @@ CUT_INTEGER, CUT_INCOMPLETE, CUT_ERROR, CUT_NOT_OPTIMAL = 0, 10, 11, 12
 EINVAL, EDEVICE, ENOMEM = -1, -2, -3
 BDUAL_SKIP_FIXED = 1        # LPX_BDUAL_SKIP_FIXED (lpx_bounded_dual_run2)
 BDUAL_LONG_STEP, BDUAL_CUTOFF = 2, 4        # LPX_BDUAL_LONG_STEP, LPX_BDUAL_CUTOFF (lpx_bounded_dual_run3)
+NODE_LAUNCHES, NODE_ONCHIP, NODE_AUTO = 0, 1, 2     # LPX_NODE_* (lpx_bounded_node3, lpx_solve_bnb_bounded3)
+NODE_FORMS = {"launches": NODE_LAUNCHES, "onchip": NODE_ONCHIP, "auto": NODE_AUTO}
 E_GE_PRESENT, E_NEG_RHS, E_REVISED_PRECOND, E_SINGULAR, E_KNAP_SHAPE, E_UNKNOWN_ALGO, E_PARSE = (
     -10, -11, -12, -13, -14, -15, -16)
 
@@ -306,6 +308,11 @@ def lib() -> C.CDLL:
                                     C.POINTER(NodeRecord)]
     L.lpx_solve_bnb_bounded2.argtypes = [C.POINTER(Problem), dp, dp, u8p, C.POINTER(SolveOpts), C.c_int64, C.c_int, C.POINTER(Result),
                                          C.POINTER(BnbBoundedInfo)]
+    L.lpx_bounded_node_fits.argtypes = [C.c_int, C.c_int]
+    L.lpx_bounded_node3.argtypes = [vp, C.c_int, ip, dp, dp, C.POINTER(RunOpts), C.c_int, C.c_double, C.c_int, u8p, C.c_double,
+                                    C.c_int, C.POINTER(NodeRecord)]
+    L.lpx_solve_bnb_bounded3.argtypes = [C.POINTER(Problem), dp, dp, u8p, C.POINTER(SolveOpts), C.c_int64, C.c_int, C.c_int,
+                                         C.POINTER(Result), C.POINTER(BnbBoundedInfo)]
     L.lpx_solve_bounded_dual.argtypes = [C.POINTER(Problem), dp, dp, C.c_int, C.POINTER(SolveOpts), C.POINTER(Result),
                                          C.POINTER(BoundedInfo)]
     L.lpx_parse_text.argtypes = [C.c_char_p, C.POINTER(Parsed)]

@@ -22,7 +22,7 @@ struct Node { int depth; std::vector<Override> path; };
 
 SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
                               const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
-                              int search_flags)
+                              int search_flags, int node_form)
 {
     const int n = original.NumVars();
     if ((!lower.empty() && (int)lower.size() != n) || (!upper.empty() && (int)upper.size() != n))
@@ -41,6 +41,8 @@ SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<doubl
     if (max_nodes < 0) throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: max_nodes is negative");
     if (search_flags & ~(LPX_BDUAL_LONG_STEP | LPX_BDUAL_CUTOFF))
         throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: search_flags holds a bit other than LPX_BDUAL_LONG_STEP and LPX_BDUAL_CUTOFF");
+    if (node_form != -1 && node_form != LPX_NODE_LAUNCHES && node_form != LPX_NODE_ONCHIP && node_form != LPX_NODE_AUTO)
+        throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: node_form is none of LPX_NODE_LAUNCHES, LPX_NODE_ONCHIP and LPX_NODE_AUTO");
 
     EngineOptions ropt = opt; ropt.quiet = true;
     BoundedSession ses;
@@ -51,6 +53,13 @@ SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<doubl
     res.Nodes = 0; res.LpSolves = 1;
     res.Aux = {0.0, 0.0, 0.0, 0.0};
     if (res.Status != LPX_OPTIMAL) return res;            // an unbounded root is reported as that
+    if (node_form == LPX_NODE_ONCHIP) {                   // the shape never changes: the root decides for every node
+        int R = 0, C = 0;
+        lpx_tableau_shape(ses.h, &R, &C, nullptr);
+        if (!lpx_bounded_node_fits(R, C))
+            throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: the root tableau (" + std::to_string(R) + " x " + std::to_string(C) +
+                                           ") does not fit the on-chip form of the node (lpx_bounded_node_fits)");
+    }
 
     // the handle's columns stand for x' = x - lower: root bounds [0, ub'] of every variable
     std::vector<double> root_lo((size_t)n, 0.0), root_ub(binfo.ub.begin(), binfo.ub.begin() + n);
@@ -83,7 +92,10 @@ SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<doubl
         lpx_node_record rec;
         // with CUTOFF the loop stops where this node would be pruned by bound anyway; search_flags = 0 stays the old call, messages included
         const double cutoff = (search_flags & LPX_BDUAL_CUTOFF) ? best + EPS : 0.0;
-        const int rc = search_flags == 0
+        const int rc = node_form > LPX_NODE_LAUNCHES      // LPX_NODE_LAUNCHES (and -1) stay the old calls, messages included
+            ? lpx_bounded_node3(ses.h, K, cols.data(), clo.data(), cub.data(), &o, LPX_BDUAL_SKIP_FIXED | search_flags, cutoff,
+                                n, mask, EPS, node_form, &rec)
+            : search_flags == 0
             ? lpx_bounded_node(ses.h, K, cols.data(), clo.data(), cub.data(), &o, n, mask, EPS, &rec)
             : lpx_bounded_node2(ses.h, K, cols.data(), clo.data(), cub.data(), &o, LPX_BDUAL_SKIP_FIXED | search_flags, cutoff,
                                 n, mask, EPS, &rec);

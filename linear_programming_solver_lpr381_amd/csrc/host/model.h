@@ -245,7 +245,8 @@ struct BnbBoundedInfo {
 };
 SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
                               const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
-                              int search_flags = 0);      // lpx_solve_bnb_bounded2: LPX_BDUAL_LONG_STEP / LPX_BDUAL_CUTOFF on every node
+                              int search_flags = 0,       // lpx_solve_bnb_bounded2: LPX_BDUAL_LONG_STEP / LPX_BDUAL_CUTOFF on every node
+                              int node_form = -1);        // lpx_solve_bnb_bounded3: LPX_NODE_* of every node call; -1: the calls of _bounded / _bounded2
 
 // LPParser.ParseFromText, Models/LPParser.cs:9-79.  Throws LpxException(LPX_E_PARSE, message).
 LPProblem ParseFromText(const std::string& input);

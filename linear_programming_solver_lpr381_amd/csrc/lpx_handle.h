@@ -69,12 +69,17 @@ struct lpx_tableau {
         int32_t* dzl = nullptr; lpx_branch_pick* pickrec = nullptr; uint8_t* pickmask = nullptr; char* nodeslab = nullptr;
         // lpx_bounded_dual_run3: the objective cutoff the select kernel reads, and the host value its copy is made from
         double* cutoff = nullptr; double cutoff_h = 0.0;
+        // the on-chip node (lpx_bounded_node3, lpx_bounded_node.hip): the pinned slab its inputs and its record travel through,
+        // and the host copy of the integer mask now in pickmask (mask_n bytes; -1: pickmask holds something else)
+        char* nodeio = nullptr; size_t nodeio_bytes = 0;
+        std::vector<uint8_t> mask_h; int mask_n = -1;
 
         void free()
         {
             hipFree(ub); hipFree(flip); hipFree(snapUb); hipFree(snapFlip);
             hipFree(lo); hipFree(snapLo); hipFree(chg);
             hipFree(dzl); hipFree(pickrec); hipFree(pickmask); if (nodeslab) hipHostFree(nodeslab); hipFree(cutoff);
+            if (nodeio) hipHostFree(nodeio);
         }
     } bnd;
 };

@@ -92,6 +92,32 @@ struct PickParams {
 };
 hipError_t launch_branch_pick(const PickParams& p, hipStream_t s);
 
+// the on-chip node (lpx_bounded_node.hip): one launch of one workgroup evaluates a whole node with the tableau in LDS
+// What a node call sends: this header and behind it lower[K], upper[K] (double) and cols[K] (int32), in the handle's pinned slab.
+struct NodeIn {
+    int32_t K, flags, nint, has_mask, max_iter, lo_used, pad[2];       // lo_used: the handle has stored a lower shift (this edit included)
+    double eps, ratio_tol, cutoff, tol;
+};
+static_assert(sizeof(NodeIn) == 64, "the arrays behind the header start on a double");
+// What it gets back, written by the kernel into the same slab.  status -1: the edit was refused and the handle is as it was --
+// inf_k >= 0: upper[inf_k] = +inf on a flipped column; else `unrepairable` columns that no flip can make dual feasible.
+struct NodeOut {
+    int32_t status, events, kind0, kind1, flips, unrepairable, inf_k, var, candidates, pad;
+    double x_var, z;
+};
+struct NodeParams {
+    double* T; int ld, R, C;             // R, C: the LIVE shape
+    double* rhsbuf; int32_t* basis; int32_t* trace; int trace_cap; DevState* st;
+    double* ub; double* lo; uint8_t* flip;
+    double* edit;                        // device staging of the edit, in the layout of BoundEdit: 5 K doubles and K int32
+    const uint8_t* mask;                 // [nint] device copy of the integer mask (read when NodeIn::has_mask)
+    const NodeIn* in; NodeOut* out;
+};
+size_t bounded_node_lds_bytes(int R, int C);        // dynamic LDS of the launch for a live R x C window
+int bounded_node_fits(int R, int C);                // pure host arithmetic: 1 iff that and the kernel's statics fit one compute unit
+hipError_t bounded_node_init();                     // one-time function attribute
+hipError_t launch_bounded_node_onchip(const NodeParams& n, hipStream_t s);
+
 // ---- lpx_kernels.hip: the two-launch select and update paths
 hipError_t launch_select(const SelParams& p, hipStream_t s);       // gather-based (dual path)
 hipError_t launch_select_la(const SelParams& p, hipStream_t s);    // lookahead (primal / forced)

@@ -370,7 +370,8 @@ void lpx_bounded_close(lpx_bounded_session* s) { delete s; }
 
 // ---- branch and bound by bound changes on the root's handle (host/bnb_bounded.cpp) ------------------------------------------
 static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const double* upper, const uint8_t* is_int, const lpx_solve_opts* o,
-                            int64_t max_nodes, int search_flags, lpx_result* out, lpx_bnb_bounded_info* info, const char* what)
+                            int64_t max_nodes, int search_flags, lpx_result* out, lpx_bnb_bounded_info* info, const char* what,
+                            int node_form = -1)
 {
     if (!p || !out) { set_error(std::string(what) + ": null argument"); return LPX_EINVAL; }
     std::memset(out, 0, sizeof(*out));
@@ -385,7 +386,7 @@ static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const do
         if (upper) up.assign(upper, upper + p->n);
         if (is_int) mask.assign(is_int, is_int + p->n);
         BnbBoundedInfo bi;
-        SimplexResult r = SolveBnbBounded(q, lo, up, mask, e, max_nodes, bi, search_flags);
+        SimplexResult r = SolveBnbBounded(q, lo, up, mask, e, max_nodes, bi, search_flags, node_form);
         fill_result(out, r, p->n);
         if (info) {
             info->nodes = bi.nodes; info->events = bi.events; info->flips = bi.flips; info->incumbents = bi.incumbents;
@@ -408,6 +409,17 @@ int lpx_solve_bnb_bounded2(const lpx_problem* p, const double* lower, const doub
                            const lpx_solve_opts* o, int64_t max_nodes, int search_flags, lpx_result* out, lpx_bnb_bounded_info* info)
 {
     return solve_bnb_bounded(p, lower, upper, is_int, o, max_nodes, search_flags, out, info, "lpx_solve_bnb_bounded2");
+}
+
+int lpx_solve_bnb_bounded3(const lpx_problem* p, const double* lower, const double* upper, const uint8_t* is_int,
+                           const lpx_solve_opts* o, int64_t max_nodes, int search_flags, int node_form, lpx_result* out,
+                           lpx_bnb_bounded_info* info)
+{
+    if (node_form != LPX_NODE_LAUNCHES && node_form != LPX_NODE_ONCHIP && node_form != LPX_NODE_AUTO) {
+        set_error("lpx_solve_bnb_bounded3: unknown node_form");
+        return LPX_EINVAL;
+    }
+    return solve_bnb_bounded(p, lower, upper, is_int, o, max_nodes, search_flags, out, info, "lpx_solve_bnb_bounded3", node_form);
 }
 
 void lpx_bnb_bounded_info_free(lpx_bnb_bounded_info* info)

@@ -5,6 +5,7 @@
 #include "lpx_handle.h"
 
 #include <cstring>
+#include <mutex>
 #include <vector>
 
 using namespace lpx;
@@ -228,7 +229,10 @@ int enqueue_dualize_apply(lpx_tableau* t)
 // the pick launch and the copy of its record into the pinned slab (the caller waits)
 int enqueue_pick(lpx_tableau* t, int nint, const uint8_t* is_int, double tol)
 {
-    if (is_int && nint > 0) LPX_HIP_TRY(hipMemcpyAsync(t->bnd.pickmask, is_int, (size_t)nint, hipMemcpyHostToDevice, t->stream));
+    if (is_int && nint > 0) {
+        LPX_HIP_TRY(hipMemcpyAsync(t->bnd.pickmask, is_int, (size_t)nint, hipMemcpyHostToDevice, t->stream));
+        t->bnd.mask_n = -1;                                  // the on-chip node's cached mask is gone
+    }
     PickParams p; std::memset(&p, 0, sizeof(p));
     p.T = t->T; p.ld = t->ld; p.R = t->R; p.Cm = t->C - 1;
     p.basis = t->basis; p.ub = t->bnd.ub; p.flip = t->bnd.flip; p.lo = t->bnd.lo_used ? t->bnd.lo : nullptr;
@@ -472,6 +476,109 @@ int lpx_bounded_node2(lpx_tableau* t, int K, const int32_t* cols, const double* 
 {
     const int rc = check_long_flags(flags, cutoff, "lpx_bounded_node2"); if (rc) return rc;
     return bounded_node(t, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, "lpx_bounded_node2");
+}
+
+// ---- the on-chip form of the node (kernel in lpx_bounded_node.hip): one launch, one wait ----
+int lpx_bounded_node_fits(int R, int C) { return bounded_node_fits(R, C); }
+
+// The steady state of a call: the inputs written into the handle's pinned slab, one kernel launch, one wait, the record read
+// from the same slab.  Allocations and the copy of the integer mask happen only when K outgrows the slab or the mask's bytes change.
+static int bounded_node_onchip(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const lpx_run_opts* o,
+                               int flags, double cutoff, int nint, const uint8_t* is_int, double tol, lpx_node_record* out, const char* what)
+{
+    const std::string w = what;
+    int rc = bounded_ready(t, true); if (rc) return rc;
+    static std::once_flag once; static hipError_t init_err = hipSuccess;
+    std::call_once(once, [] { init_err = bounded_node_init(); });
+    if (init_err != hipSuccess) { set_error(w + ": kernel attribute setup failed: " + hipGetErrorString(init_err)); return LPX_EDEVICE; }
+    lpx_tableau::Bounds& b = t->bnd;
+    std::memset(out, 0, sizeof(*out));
+    out->pick.var = -1;
+    constexpr size_t kOut = 64, kHdr = kOut + sizeof(NodeIn);
+    static_assert(sizeof(NodeOut) <= kOut, "slab layout");
+    const size_t need = kHdr + (size_t)K * (2 * sizeof(double) + sizeof(int32_t));
+    if (need > b.nodeio_bytes) {
+        LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+        if (b.nodeio) hipHostFree(b.nodeio);
+        b.nodeio = nullptr; b.nodeio_bytes = 0;
+        LPX_HIP_TRY(hipHostMalloc((void**)&b.nodeio, 2 * need));
+        b.nodeio_bytes = 2 * need;
+    }
+    const size_t stage = (size_t)K * (5 * sizeof(double) + sizeof(int32_t));     // the layout of BoundEdit
+    if (stage > b.chg_bytes) {
+        LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+        hipFree(b.chg); b.chg = nullptr; b.chg_bytes = 0;
+        LPX_HIP_TRY(hipMalloc((void**)&b.chg, 2 * stage));
+        b.chg_bytes = 2 * stage;
+    }
+    const bool has_mask = is_int && nint > 0;
+    if (has_mask && !(b.mask_n == nint && std::memcmp(b.mask_h.data(), is_int, (size_t)nint) == 0)) {
+        LPX_HIP_TRY(hipStreamSynchronize(t->stream));                            // an earlier copy may still read mask_h
+        b.mask_h.assign(is_int, is_int + nint);
+        LPX_HIP_TRY(hipMemcpyAsync(b.pickmask, b.mask_h.data(), (size_t)nint, hipMemcpyHostToDevice, t->stream));
+        b.mask_n = nint;
+    }
+    bool any_lo = false;
+    for (int k = 0; k < K; ++k) if (lower[k] != 0.0) any_lo = true;
+    NodeOut* rec = reinterpret_cast<NodeOut*>(b.nodeio);
+    NodeIn* in = reinterpret_cast<NodeIn*>(b.nodeio + kOut);
+    std::memset(in, 0, sizeof(*in));
+    in->K = K; in->flags = flags; in->nint = nint; in->has_mask = has_mask ? 1 : 0; in->max_iter = o->max_iter;
+    in->lo_used = (b.lo_used || any_lo) ? 1 : 0;
+    in->eps = o->eps; in->ratio_tol = o->ratio_tol; in->cutoff = cutoff; in->tol = tol;
+    if (K > 0) {
+        double* a = reinterpret_cast<double*>(in + 1);
+        std::memcpy(a, lower, sizeof(double) * K);
+        std::memcpy(a + K, upper, sizeof(double) * K);
+        std::memcpy(a + 2 * (size_t)K, cols, sizeof(int32_t) * K);
+    }
+    NodeParams n; std::memset(&n, 0, sizeof(n));
+    n.T = t->T; n.ld = t->ld; n.R = t->R; n.C = t->C;
+    n.rhsbuf = t->rhsbuf; n.basis = t->basis; n.trace = t->trace; n.trace_cap = t->trace_cap; n.st = t->st;
+    n.ub = b.ub; n.lo = b.lo; n.flip = b.flip; n.edit = reinterpret_cast<double*>(b.chg); n.mask = b.pickmask;
+    n.in = in; n.out = rec;
+    LPX_HIP_TRY(launch_bounded_node_onchip(n, t->stream));
+    LPX_HIP_TRY(hipStreamSynchronize(t->stream));                                // the one wait: the record is in the slab
+    if (rec->status < 0) {                                                       // refused by the kernel: the handle is as it was
+        if (rec->inf_k >= 0) { set_error(w + ": upper[" + std::to_string(rec->inf_k) + "] = +inf on a flipped column"); return LPX_EINVAL; }
+        out->unrepairable = rec->unrepairable;
+        set_error(w + ": " + std::to_string(out->unrepairable) + " column(s) with a negative reduced cost and no upper "
+                  "bound: a bound flip cannot restore dual feasibility");
+        return LPX_EINVAL;
+    }
+    t->suspended = t->suspended2 = t->fsuspended = false;
+    if (any_lo) b.lo_used = true;
+    DevState h = fresh_state(false);                                             // the host mirror, as the loop of the launches form leaves it
+    h.status = rec->status; h.iter = rec->events; h.fdf_count = rec->kind0; h.dual_iter = rec->kind1; h.primal_count = rec->events;
+    *t->hst = h;
+    b.bcounts[0] = rec->kind0; b.bcounts[1] = rec->kind1; b.bcounts[2] = (int64_t)rec->events - rec->kind0 - rec->kind1;
+    out->status = rec->status; out->events = rec->events; out->kind0 = rec->kind0; out->kind1 = rec->kind1; out->flips = rec->flips;
+    out->pick.z = rec->z;
+    if (rec->status == LPX_OPTIMAL) { out->pick.var = rec->var; out->pick.candidates = rec->candidates; out->pick.x_var = rec->x_var; }
+    return rec->status;
+}
+
+int lpx_bounded_node3(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const lpx_run_opts* o,
+                      int flags, double cutoff, int nint, const uint8_t* is_int, double tol, int form, lpx_node_record* out)
+{
+    const char* what = "lpx_bounded_node3";
+    const std::string w = what;
+    int rc = check_long_flags(flags, cutoff, what); if (rc) return rc;
+    if (form != LPX_NODE_LAUNCHES && form != LPX_NODE_ONCHIP && form != LPX_NODE_AUTO) { set_error(w + ": unknown form"); return LPX_EINVAL; }
+    if (form == LPX_NODE_LAUNCHES || (form == LPX_NODE_AUTO && t && !bounded_node_fits(t->R, t->C)))
+        return bounded_node(t, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, what);
+    rc = check_change_args(t, K, cols, lower, upper, what); if (rc) return rc;
+    rc = check_pick_args(t, nint, tol, out, what); if (rc) return rc;
+    lpx_run_opts d; if (!o) { lpx_default_opts(&d, 1); o = &d; }
+    if (t->R < 2) { set_error(w + ": tableau needs at least one constraint row"); return LPX_EINVAL; }
+    if (o->resident > 0) { set_error(w + ": there is no resident form of the bounded dual loop"); return LPX_EINVAL; }
+    if (!(o->eps >= 0.0)) { set_error(w + ": eps is negative or NaN"); return LPX_EINVAL; }
+    if (!bounded_node_fits(t->R, t->C)) {
+        set_error(w + ": the live " + std::to_string(t->R) + " x " + std::to_string(t->C) + " window does not fit the on-chip form "
+                  "(lpx_bounded_node_fits)");
+        return LPX_EINVAL;
+    }
+    return bounded_node_onchip(t, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, what);
 }
 
 }  // extern "C"

@@ -342,14 +342,18 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         return res
 
     def SolveBnbBounded(self, problem: LPProblem, upper, lower=None, integer=None, max_nodes: int = 0,
-                        long_step: bool = False, cutoff: bool = False) -> SimplexResult:
+                        long_step: bool = False, cutoff: bool = False, node_form: str = "launches") -> SimplexResult:
         """Branch and bound by bound changes on one device tableau (lpx_solve_bnb_bounded): lower <= x <= upper, x_j integer
         where integer[j] (None: every variable); integer variables need finite, integral bounds.  Status OPTIMAL or INFEASIBLE,
         Solution, OptimalValue (user's sense), Nodes, BnbInfo (counters) and BnbLog, a structured array with one record per node
         (depth, K, status, events, flips, var, z).  A node or search limit raises SolverException(ITER_LIMIT) whose .result
         holds the incumbent so far.  long_step / cutoff (lpx_solve_bnb_bounded2): every node's dual loop runs with the
         long-step ratio test / stops as soon as its objective has fallen to the incumbent + 1e-6 (such a node is logged with
-        status CUTOFF and counted as pruned by bound); both off is lpx_solve_bnb_bounded."""
+        status CUTOFF and counted as pruned by bound); both off is lpx_solve_bnb_bounded.  node_form "onchip" | "auto"
+        (lpx_solve_bnb_bounded3): every node is one kernel launch with the tableau in LDS ("auto": iff the root fits); the node
+        log is bit-equal to "launches", the default."""
+        if node_form not in _lib.NODE_FORMS:
+            raise ValueError(f"unknown node form {node_form!r}")
         n = problem.NumVars
         o, keep = _solve_opts(self.engine)
         ps, hold = _problem_struct(problem)
@@ -367,7 +371,10 @@ class LPSolver:             # Models/LPSolver.cs:6-77
             mp = mask.ctypes.data_as(C.POINTER(C.c_uint8))
         r, info = _lib.Result(), _lib.BnbBoundedInfo()
         flags = (_lib.BDUAL_LONG_STEP if long_step else 0) | (_lib.BDUAL_CUTOFF if cutoff else 0)
-        if flags:
+        if node_form != "launches":
+            rc = lib().lpx_solve_bnb_bounded3(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), flags, _lib.NODE_FORMS[node_form],
+                                              C.byref(r), C.byref(info))
+        elif flags:
             rc = lib().lpx_solve_bnb_bounded2(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), flags, C.byref(r), C.byref(info))
         else:
             rc = lib().lpx_solve_bnb_bounded(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), C.byref(r), C.byref(info))

@@ -328,17 +328,28 @@ class DeviceTableau:
         return {"var": out.var, "candidates": out.candidates, "x_var": out.x_var, "z": out.z}
 
     def bounded_node(self, cols, lower, upper, nint: int, is_int=None, tol: float = 1e-6,
-                     opts: Optional[RunOpts] = None, long_step: bool = False, cutoff: Optional[float] = None, **kw) -> dict:
+                     opts: Optional[RunOpts] = None, long_step: bool = False, cutoff: Optional[float] = None,
+                     form: Optional[str] = None, **kw) -> dict:
         """One branch-and-bound node in one call (lpx_bounded_node): change_bounds, dualize, the dual loop in which fixed
         columns do not enter, and on OPTIMAL the branch pick.  long_step=True or a cutoff is lpx_bounded_node2: the loop runs
-        with those flags and may end with status CUTOFF (no pick).  Returns the node record as a dict."""
+        with those flags and may end with status CUTOFF (no pick).  form "launches" | "onchip" | "auto" is lpx_bounded_node3:
+        "onchip" evaluates the whole node in one kernel launch with the tableau in LDS (LpxError when bounded_node_fits() is
+        False), "auto" does so iff it fits; the results are bit-equal in every form.  Returns the node record as a dict."""
         cols = np.ascontiguousarray(np.atleast_1d(cols), dtype=np.int32).reshape(-1)
         lower = np.ascontiguousarray(np.broadcast_to(np.asarray(lower, dtype=np.float64), cols.shape))
         upper = np.ascontiguousarray(np.broadcast_to(np.asarray(upper, dtype=np.float64), cols.shape))
         o = opts if opts is not None else default_opts(True, **kw)
         keep, mp = self._mask(is_int, int(nint))
         rec = _lib.NodeRecord()
-        if long_step or cutoff is not None:
+        if form is not None:
+            if form not in _lib.NODE_FORMS:
+                raise ValueError(f"unknown node form {form!r}")
+            flags = (_lib.BDUAL_SKIP_FIXED | (_lib.BDUAL_LONG_STEP if long_step else 0)
+                     | (_lib.BDUAL_CUTOFF if cutoff is not None else 0))
+            check(lib().lpx_bounded_node3(self._h, len(cols), cols.ctypes.data_as(ip), lower.ctypes.data_as(dp),
+                                          upper.ctypes.data_as(dp), C.byref(o), flags, float(cutoff if cutoff is not None else 0.0),
+                                          int(nint), mp, float(tol), _lib.NODE_FORMS[form], C.byref(rec)))
+        elif long_step or cutoff is not None:
             flags = (_lib.BDUAL_SKIP_FIXED | (_lib.BDUAL_LONG_STEP if long_step else 0)
                      | (_lib.BDUAL_CUTOFF if cutoff is not None else 0))
             check(lib().lpx_bounded_node2(self._h, len(cols), cols.ctypes.data_as(ip), lower.ctypes.data_as(dp),
@@ -350,6 +361,10 @@ class DeviceTableau:
         return {"status": rec.status, "events": rec.events, "kind0": rec.kind0, "kind1": rec.kind1, "flips": rec.flips,
                 "unrepairable": rec.unrepairable, "var": rec.pick.var, "candidates": rec.pick.candidates,
                 "x_var": rec.pick.x_var, "z": rec.pick.z}
+
+    def bounded_node_fits(self) -> bool:
+        """True iff the on-chip form of bounded_node accepts the live shape (lpx_bounded_node_fits: host arithmetic only)."""
+        return bool(lib().lpx_bounded_node_fits(self.R, self.C))
 
     def forced_pivots(self, rows, cols, thresh: float = 0.1, opts: Optional[RunOpts] = None,
                       **kw) -> Tuple[np.ndarray, dict]:

@@ -15,9 +15,17 @@ collected here); and the device memory each side added (hipMemGetInfo through to
 each side's first solve; handle caches keep what they allocated, so the reading after a solve is that side's peak).
 
 `--model NAME` keeps one of the two models (bip_60x12, bip_128x64); `--max-nodes N` bounds both searches (then neither
-reaches optimality and the optima are incumbents so far).
+reaches optimality and the optima are incumbents so far).  `--node-form launches|onchip|auto` is the node form of side (b)
+and of its K = 0 node call (lpx_bounded_node3 / lpx_solve_bnb_bounded3; default launches).
 
-usage: bench_bnb_bounded.py [--model NAME] [--max-nodes N] [REPS]"""
+`--compare-forms` measures the two node forms against each other instead: per model the wall of a K = 0
+node call on the solved root and of the root's first child (200 calls a sample, REPS samples, the forms alternating), the
+child's events, and the driver to optimality under `--flag-sets` (comma-separated out of plain,long_step,cutoff,both; default
+all four) in both forms, alternating, REPS timed solves after one untimed solve of 2000 nodes each (`--flag-sets none`: no driver runs); counts must
+be equal across forms.
+`--trace-only` runs one solve of side (b) and nothing else (for a kernel trace of the node form given).
+
+usage: bench_bnb_bounded.py [--model NAME] [--max-nodes N] [--node-form F] [--compare-forms [--flag-sets LIST]] [--trace-only] [REPS]"""
 import json
 import os
 import statistics
@@ -49,21 +57,108 @@ def device_used_mb():
         return None
 
 
+FORMS = ("launches", "onchip")
+FLAG_SETS = {"plain": {}, "long_step": {"long_step": True}, "cutoff": {"cutoff": True}, "both": {"long_step": True, "cutoff": True}}
+
+
+def compare_forms(n, m, reps, max_nodes, flag_sets):
+    """The two node forms against each other on binary_ip(n, m): node call wall and the driver (see the module docstring)."""
+    c, A, rel, b = synth.binary_ip(n, m)
+    bnd_p = L.LPProblem.from_arrays(0, c, A[:m], rel[:m], b[:m])
+    rec = {"n": n, "m": m, "bounded_shape": [m + 1, n + m + 1], "node_call_us": {}, "driver": {}}
+    T, basis = synth.primal_tableau_from(c, A[:m], b[:m])
+    ub = np.full(T.shape[1] - 1, np.inf); ub[:n] = 1.0
+    calls = 200
+    with L.DeviceTableau.from_host(T, basis) as dt:
+        dt.set_bounds(ub)
+        dt.bounded_run()
+        dt.snapshot()
+        rec["fits"] = dt.bounded_node_fits()
+        root = dt.bounded_node([], [], [], n, batch=16)
+        j = root["var"]
+        child = None
+        for what, edit in (("empty", ([], [], [])), ("child", ([j], [1.0], [1.0]))):
+            ts = {f: [] for f in FORMS}
+            for i in range(reps + 1):
+                for f in FORMS:
+                    total = 0.0
+                    for _ in range(calls):
+                        if what == "child":
+                            dt.restore()
+                        t0 = time.perf_counter()
+                        got = dt.bounded_node(*edit, n, batch=16, form=f)
+                        total += time.perf_counter() - t0
+                    if what == "child":
+                        assert child is None or child == got, "the forms disagree on the child"
+                        child = got
+                    if i >= 1:
+                        ts[f].append(1e6 * total / calls)
+            rec["node_call_us"][what] = {f: stats(ts[f]) for f in FORMS}
+        rec["child"] = {"var": j, "events": child["events"], "status": child["status"]}
+        ev = max(1, child["events"])
+        rec["us_per_event"] = {f: (rec["node_call_us"]["child"][f]["median"] - rec["node_call_us"]["empty"][f]["median"]) / ev for f in FORMS}
+
+    def solve(f, kw, limit=None):
+        limit = max_nodes if limit is None else limit
+        t0 = time.perf_counter()
+        try:
+            r = L.LPSolver().SolveBnbBounded(bnd_p, 1.0, max_nodes=limit, node_form=f, **kw)
+        except L.SolverException as e:
+            if e.code != L._lib.ITER_LIMIT or not limit:
+                raise
+            r = e.result
+        return 1e3 * (time.perf_counter() - t0), r
+
+    for fs in flag_sets:
+        kw = FLAG_SETS[fs]
+        ts = {f: [] for f in FORMS}
+        last = {}
+        for i in range(reps + 1):
+            for f in FORMS:
+                if i == 0:          # the untimed solve: what a first solve pays once is paid within its first nodes
+                    solve(f, kw, max_nodes if max_nodes else 2000)
+                    continue
+                ms, r = solve(f, kw)
+                last[f] = r
+                ts[f].append(ms)
+        a, o = last["launches"], last["onchip"]
+        d = {f: {"ms": stats(ts[f]), "nodes_per_s": a.Nodes / (statistics.median(ts[f]) / 1e3)} for f in FORMS}
+        d.update(nodes=int(a.Nodes), events=a.BnbInfo["events"], pruned_bound=a.BnbInfo["pruned_bound"],
+                 counts_equal=bool(a.BnbLog.tobytes() == o.BnbLog.tobytes() and a.BnbInfo == o.BnbInfo),
+                 onchip_wins=bool(d["onchip"]["ms"]["median"] < d["launches"]["ms"]["min"]),
+                 launches_wins=bool(d["launches"]["ms"]["median"] < d["onchip"]["ms"]["min"]))
+        rec["driver"][fs] = d
+    return rec
+
+
 def main():
     args = sys.argv[1:]
-    only, max_nodes = None, 0
-    for flag in ("--model", "--max-nodes"):
+    only, max_nodes, node_form, flag_sets = None, 0, "launches", "plain,long_step,cutoff,both"
+    for flag in ("--model", "--max-nodes", "--node-form", "--flag-sets"):
         if flag in args:
             k = args.index(flag)
             if flag == "--model":
                 only = args[k + 1]
+            elif flag == "--node-form":
+                node_form = args[k + 1]
+            elif flag == "--flag-sets":
+                flag_sets = args[k + 1]
             else:
                 max_nodes = int(args[k + 1])
             del args[k:k + 2]
+    compare = "--compare-forms" in args
+    trace_only = "--trace-only" in args
+    args = [a for a in args if a not in ("--compare-forms", "--trace-only")]
     reps = int(args[0]) if args else 7
     lib = L._lib.lib()
     L._lib.check(lib.lpx_init(0))
     out = {}
+    if compare:
+        for name, n, m in models():
+            if only is None or name == only:
+                out[name] = compare_forms(n, m, reps, max_nodes, [f for f in flag_sets.split(",") if f and f != "none"])
+        print(json.dumps(out))
+        return
     for name, n, m in models():
         if only is not None and name != only:
             continue
@@ -80,13 +175,17 @@ def main():
         def run_bounded():
             t0 = time.perf_counter()
             try:
-                r = L.LPSolver().SolveBnbBounded(bnd_p, 1.0, max_nodes=max_nodes)
+                r = L.LPSolver().SolveBnbBounded(bnd_p, 1.0, max_nodes=max_nodes, node_form=node_form)
             except L.SolverException as e:
                 if e.code != L._lib.ITER_LIMIT or not max_nodes:
                     raise
                 r = e.result
             return 1e3 * (time.perf_counter() - t0), r
 
+        if trace_only:
+            ms, rb = run_bounded()
+            out[name] = {"node_form": node_form, "ms": ms, "nodes": int(rb.Nodes), "events": rb.BnbInfo["events"]}
+            continue
         base = device_used_mb()
         ta, tb, na, nb = [], [], [], []
         peak_a = peak_b = None
@@ -120,11 +219,12 @@ def main():
             dt.set_bounds(ub)
             dt.bounded_run()
             for _ in range(20):
-                dt.bounded_node([], [], [], n, batch=16)
+                dt.bounded_node([], [], [], n, batch=16, form=node_form)
             t0 = time.perf_counter()
             for _ in range(200):
-                dt.bounded_node([], [], [], n, batch=16)
+                dt.bounded_node([], [], [], n, batch=16, form=node_form)
             rec["bounded"]["empty_node_us"] = 1e6 * (time.perf_counter() - t0) / 200
+        rec["bounded"]["node_form"] = node_form
         out[name] = rec
     print(json.dumps(out))
 
