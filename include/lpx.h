@@ -945,6 +945,92 @@ int lpx_solve_bnb_bounded3(const lpx_problem* p, const double* lower /* [n] or N
                            const uint8_t* is_int /* [n] or NULL = all */, const lpx_solve_opts* o, int64_t max_nodes /* 0 = none */,
                            int search_flags, int node_form, lpx_result* out, lpx_bnb_bounded_info* info /* or NULL */);
 
+/* ---- a batch of on-chip nodes per launch, and a search by W divers (not in the reference; csrc/lpx_bounded_node.hip,
+ * csrc/lpx_node_batch.cpp, csrc/host/bnb_bounded.cpp) --
+ * lpx_tableau_clone(src, out): a new handle on the source's device with the source's capacity (at least the live window), holding
+ * device-to-device copies of the live R x C window, the basis, the contiguous RHS copy, ub / lo / flip with the lo-used mark (if
+ * the source has bounds), and the loop state record with its host mirror.  Not copied: the snapshot, the trace (lpx_tableau_trace
+ * on the clone reports no entry until the clone's first run), the cached graphs, the callbacks, the node slabs; the clone's
+ * lpx_bounded_counts are zero.  The source is left bit for bit as it was.  lpx_tableau_download / _shape / _bound_state /
+ * _bounded_solution read the same bits from both handles, and any run or node call on the clone gives the bits it gives on the
+ * source.  A source that lpx_multi_run_some left in the middle of a run is refused (LPX_EINVAL): what continues such a run is not
+ * part of the copy.  That and a NULL argument are LPX_EINVAL before any device check; no device: LPX_EDEVICE.
+ *
+ * lpx_node_batch_create(W, handles, out): a batch that BORROWS W handles (1 <= W <= 1024; they outlive the batch, and the caller
+ * destroys them).  They must be pairwise distinct and on one device, each with bounds set for its live shape and with a live shape
+ * that satisfies lpx_bounded_node_fits; the shapes may differ.  Anything else is LPX_EINVAL before any device check.  The batch
+ * owns one pinned slab (a parameter record, the node's header with its triples behind it, and the result record per entry), the
+ * device staging of the edits and one device copy of the integer mask, which is sent again only when its bytes change; the
+ * buffers grow to twice the need, never inside a call whose need they already hold.
+ *
+ * lpx_node_batch_run(b, B, slot, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, rc): ONE kernel launch of B
+ * workgroups evaluates B nodes, 1 <= B <= W; entry i runs on handles[slot[i]] with the K[i] triples that follow those of the
+ * entries before it in cols / lower / upper (sum of K entries each).  The slots are pairwise distinct.  o, flags, nint, is_int and
+ * tol are shared by all entries; cutoff[i] is read only with LPX_BDUAL_CUTOFF.
+ *   Contract: for every i, out[i] and rc[i] and everything readable from handles[slot[i]] afterwards -- tableau, basis, ub, lo,
+ *   flip, trace, lpx_bounded_counts, the solution, the host mirror of the state, a following node of any form -- are bit-equal to
+ *   what lpx_bounded_node3(handles[slot[i]], K[i], ..., cutoff[i], ..., LPX_NODE_ONCHIP, &out[i]) gives on a handle in the same
+ *   state.  The result does not depend on B, on the slot numbers, on the other entries, or on how many workgroups run at once: the
+ *   workgroups share nothing and never wait on one another, and every loop of the kernel is bounded, so a launch ends whatever B
+ *   is (B may exceed the number of compute units).  A handle not named in slot is untouched.
+ *   Steady-state host work: the slab is written, the launch is ordered behind outstanding work on the handles' streams, ONE kernel
+ *   launch, ONE wait, B records read.
+ *   Errors: every argument error of lpx_bounded_node3 is checked for every entry before anything is written; further argument
+ *   errors are a NULL slot, K, out or rc, B outside [1, W], a NULL batch, a slot out of range or repeated, a NULL cutoff with
+ *   LPX_BDUAL_CUTOFF.  All are LPX_EINVAL before any device check and touch no handle; the message of an entry's error starts
+ *   "lpx_node_batch_run: entry i:".  The two refusals the kernel finds (an unrepairable column, upper = +inf on a flipped column)
+ *   are per entry: rc[i] = LPX_EINVAL, out[i].unrepairable is set, that handle is as it was, the other entries complete, the call
+ *   returns 0 and lpx_last_error carries the lowest refused entry's message (the text of lpx_bounded_node2 behind the entry's
+ *   prefix).  Otherwise the call returns 0 and rc[i] is the entry's status.
+ *
+ * lpx_solve_bnb_bounded4(p, lower, upper, is_int, o, max_nodes, search_flags, divers, out, info, dinfo): the search of
+ * lpx_solve_bnb_bounded3 with every node on chip, by W = divers handles diving at once (1 <= W <= 1024, else LPX_EINVAL before any
+ * device check).  Validation, root solve, result record, summary and value conversion are those of lpx_solve_bnb_bounded3; a root
+ * that does not fit is LPX_EINVAL with its message, before the search.  Diver 0 is the root's handle, divers 1 .. W-1 are
+ * lpx_tableau_clone's of it taken after the root solve.  Each diver has its own current bounds and its own stack of (depth, path);
+ * diver 0 starts with the root node, the others empty; best starts at -inf.  One round, in this order (the order is part of the
+ * contract: the log depends on it):
+ *   1. Limit: max_nodes > 0 and nodes >= max_nodes ends the solve with the node-limit return of lpx_solve_bnb_bounded.
+ *   2. Steal: for d = 0 .. W-1 in order with diver d's stack empty: v = the diver with the longest stack, ties to the lowest
+ *      index, lengths as they stand now; if that stack holds at least 2 entries its bottom (oldest) entry moves to d and steals++;
+ *      otherwise d sits the round out.
+ *   3. Pop: for d ascending, each diver with a non-empty stack pops its top while nodes + popped < max_nodes (or no limit).  The
+ *      node's columns are those whose bounds differ from diver d's current bounds, in ascending column order.
+ *   4. Evaluate: one lpx_node_batch_run over the popped nodes, flags = LPX_BDUAL_SKIP_FIXED | search_flags, every entry with
+ *      cutoff = best + 1e-6 as best stood at the start of the round.  largest_batch is the largest B seen.
+ *   5. Decide: the records in ascending diver order, each exactly as lpx_solve_bnb_bounded treats a node: nodes++, the counters,
+ *      the log record with round[] and diver[]; LPX_ITER_LIMIT ends the solve at that record (later records of the round are
+ *      dropped); infeasible; LPX_CUTOFF or z <= best + 1e-6 against best as updated by lower-index divers of the same round;
+ *      incumbent (x from lpx_tableau_bounded_solution on that diver's handle); otherwise the floor child, then the ceil child, go
+ *      onto diver d's own stack.
+ *   6. Repeat while any stack is non-empty.
+ * divers = 1 is lpx_solve_bnb_bounded3(..., LPX_NODE_ONCHIP, ...) with a bit-equal log.  The result is a function of the model, the
+ * options, the flags and W alone; it does not depend on timing.  Another W visits other nodes, and the plain dual loop
+ * (search_flags without LPX_BDUAL_LONG_STEP) can meet a node on which it makes max_iter events, which ends the solve with
+ * LPX_ITER_LIMIT as in lpx_solve_bnb_bounded: measured on binary_ip(128, 64), where W = 4, 64 and 256 end that way and W = 1 and 16
+ * do not; with LPX_BDUAL_LONG_STEP no search measured did.  Set the long step with divers on models of
+ * that size.  dinfo (or NULL): rounds, steals, largest_batch and, per log
+ * record, the round and the diver that evaluated it ([info->n_log] each); free with lpx_bnb_divers_info_free. */
+typedef struct lpx_node_batch lpx_node_batch;
+typedef struct lpx_bnb_divers_info {
+    int64_t rounds, steals, largest_batch;
+    int32_t* round;          /* [n_log of the lpx_bnb_bounded_info] */
+    int32_t* diver;          /* [n_log] */
+} lpx_bnb_divers_info;
+int  lpx_tableau_clone(const lpx_tableau* src, lpx_tableau** out);
+int  lpx_node_batch_create(int W, lpx_tableau* const* handles, lpx_node_batch** out);
+void lpx_node_batch_destroy(lpx_node_batch* b);
+int  lpx_node_batch_run(lpx_node_batch* b, int B, const int32_t* slot /* [B] */, const int32_t* K /* [B] */,
+                        const int32_t* cols, const double* lower, const double* upper /* concatenated, sum of K */,
+                        const lpx_run_opts* o, int flags, const double* cutoff /* [B]; read only with LPX_BDUAL_CUTOFF */,
+                        int nint, const uint8_t* is_int /* [nint] or NULL = all */, double tol,
+                        lpx_node_record* out /* [B] */, int32_t* rc /* [B] */);
+int  lpx_solve_bnb_bounded4(const lpx_problem* p, const double* lower /* [n] or NULL = 0 */, const double* upper /* [n] */,
+                            const uint8_t* is_int /* [n] or NULL = all */, const lpx_solve_opts* o, int64_t max_nodes /* 0 = none */,
+                            int search_flags, int divers /* W, 1..1024 */, lpx_result* out, lpx_bnb_bounded_info* info /* or NULL */,
+                            lpx_bnb_divers_info* dinfo /* or NULL */);
+void lpx_bnb_divers_info_free(lpx_bnb_divers_info* dinfo);
+
 #ifdef __cplusplus
 }
 #endif

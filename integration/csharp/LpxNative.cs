@@ -116,6 +116,13 @@ namespace Linear_Programming_Solver.Native
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct LpxBnbDiversInfo        // lpx_bnb_divers_info  (free with lpx_bnb_divers_info_free)
+    {
+        public long rounds, steals, largest_batch;
+        public int* round, diver;                // [n_log of the LpxBnbBoundedInfo] each
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public unsafe struct LpxBoundedInfo          // lpx_bounded_info  (lpx_solve_bounded; free with lpx_bounded_info_free)
     {
         public int ncols, n;
@@ -300,6 +307,18 @@ namespace Linear_Programming_Solver.Native
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_solve_bnb_bounded3(ref LpxProblem p, double* lower, double* upper, byte* is_int, ref LpxSolveOpts o,
                                                         long max_nodes, int search_flags, int node_form, out LpxResult result, out LpxBnbBoundedInfo info);
+        // a batch of on-chip nodes per launch (handles: W IntPtr of lpx_tableau_create / _clone; records: B LpxNodeRecord) and the search by W divers
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int lpx_tableau_clone(IntPtr src, out IntPtr clone);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int lpx_node_batch_create(int W, IntPtr* handles, out IntPtr batch);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern void lpx_node_batch_destroy(IntPtr batch);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_node_batch_run(IntPtr batch, int B, int* slot, int* K, int* cols, double* lower, double* upper, IntPtr opts,
+                                                    int flags, double* cutoff, int nint, byte* is_int, double tol, LpxNodeRecord* records, int* rc);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_bnb_bounded4(ref LpxProblem p, double* lower, double* upper, byte* is_int, ref LpxSolveOpts o,
+                                                        long max_nodes, int search_flags, int divers, out LpxResult result,
+                                                        out LpxBnbBoundedInfo info, out LpxBnbDiversInfo dinfo);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern void lpx_bnb_divers_info_free(ref LpxBnbDiversInfo dinfo);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_solve_bounded_dual(ref LpxProblem p, double* lower, double* upper, int flags, ref LpxSolveOpts o,
                                                         out LpxResult result, out LpxBoundedInfo info);

@@ -6,14 +6,14 @@ behind the C ABI of include/lpx.h); this package is the host-side binding and ha
 from . import _lib
 from . import comm
 from ._lib import LpxError, default_opts
-from .tableau import DeviceTableau, TableauRanging, primal_tableau, dual_tableau, multi_run
+from .tableau import DeviceTableau, NodeBatch, TableauRanging, primal_tableau, dual_tableau, multi_run
 from .revised import DeviceRevised, invert
 from .solver import (BoundedSession, BranchAndBound, BranchAndBoundKnapsack, BranchAndBoundRevised, Constraint, CutOpts, CuttingPlane,
                      CuttingPlaneRevised, DeviceKnapsack, DualSimplex, GmiCuttingPlane, LPProblem, SensitivityAnalysis,
                      LPSolver, ModelSession, ParseFromText, PrimalSimplex, RangingReport, Rel, RevisedPrimalSimplex, Sense, SimplexResult,
                      SolverException)
 
-__all__ = ["_lib", "comm", "LpxError", "default_opts", "DeviceTableau", "TableauRanging", "primal_tableau", "dual_tableau", "multi_run", "DeviceRevised", "invert", "LPSolver", "LPProblem", "Constraint", "Sense", "Rel",
+__all__ = ["_lib", "comm", "LpxError", "default_opts", "DeviceTableau", "NodeBatch", "TableauRanging", "primal_tableau", "dual_tableau", "multi_run", "DeviceRevised", "invert", "LPSolver", "LPProblem", "Constraint", "Sense", "Rel",
            "SimplexResult", "RangingReport", "SolverException", "PrimalSimplex", "RevisedPrimalSimplex", "DualSimplex",
            "BranchAndBound", "BranchAndBoundKnapsack", "BranchAndBoundRevised", "ParseFromText", "DeviceKnapsack",
            "CuttingPlane", "CuttingPlaneRevised", "SensitivityAnalysis", "CutOpts", "GmiCuttingPlane", "ModelSession",

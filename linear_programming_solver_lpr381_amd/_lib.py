@@ -132,6 +132,12 @@ class BnbBoundedInfo(C.Structure):
                 ("constant", C.c_double), ("n_log", C.c_int64), ("log", C.POINTER(BnbNodeLog))]
 
 
+class BnbDiversInfo(C.Structure):
+    """lpx_bnb_divers_info (include/lpx.h): rounds, steals and the per-node round / diver of lpx_solve_bnb_bounded4 (freed by
+    lpx_bnb_divers_info_free)."""
+    _fields_ = [("rounds", C.c_int64), ("steals", C.c_int64), ("largest_batch", C.c_int64), ("round", ip), ("diver", ip)]
+
+
 class Parsed(C.Structure):
     _fields_ = [("sense", C.c_int), ("n", C.c_int), ("m", C.c_int), ("c", dp), ("A", dp), ("rel", ip),
                 ("b", dp), ("ragged", C.c_int)]
@@ -313,6 +319,16 @@ def lib() -> C.CDLL:
                                     C.c_int, C.POINTER(NodeRecord)]
     L.lpx_solve_bnb_bounded3.argtypes = [C.POINTER(Problem), dp, dp, u8p, C.POINTER(SolveOpts), C.c_int64, C.c_int, C.c_int,
                                          C.POINTER(Result), C.POINTER(BnbBoundedInfo)]
+    L.lpx_tableau_clone.argtypes = [vp, C.POINTER(vp)]
+    L.lpx_node_batch_create.argtypes = [C.c_int, C.POINTER(vp), C.POINTER(vp)]
+    L.lpx_node_batch_destroy.argtypes = [vp]
+    L.lpx_node_batch_destroy.restype = None
+    L.lpx_node_batch_run.argtypes = [vp, C.c_int, ip, ip, ip, dp, dp, C.POINTER(RunOpts), C.c_int, dp, C.c_int, u8p, C.c_double,
+                                     C.POINTER(NodeRecord), ip]
+    L.lpx_solve_bnb_bounded4.argtypes = [C.POINTER(Problem), dp, dp, u8p, C.POINTER(SolveOpts), C.c_int64, C.c_int, C.c_int,
+                                         C.POINTER(Result), C.POINTER(BnbBoundedInfo), C.POINTER(BnbDiversInfo)]
+    L.lpx_bnb_divers_info_free.argtypes = [C.POINTER(BnbDiversInfo)]
+    L.lpx_bnb_divers_info_free.restype = None
     L.lpx_solve_bounded_dual.argtypes = [C.POINTER(Problem), dp, dp, C.c_int, C.POINTER(SolveOpts), C.POINTER(Result),
                                          C.POINTER(BoundedInfo)]
     L.lpx_parse_text.argtypes = [C.c_char_p, C.POINTER(Parsed)]

@@ -247,6 +247,11 @@ SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<doubl
                               const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
                               int search_flags = 0,       // lpx_solve_bnb_bounded2: LPX_BDUAL_LONG_STEP / LPX_BDUAL_CUTOFF on every node
                               int node_form = -1);        // lpx_solve_bnb_bounded3: LPX_NODE_* of every node call; -1: the calls of _bounded / _bounded2
+// The search by W divers (lpx_solve_bnb_bounded4): every node on chip, one lpx_node_batch_run per round.
+struct BnbDiversInfo { int64_t rounds = 0, steals = 0, largest_batch = 0; std::vector<int32_t> round, diver; };
+SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
+                             const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
+                             int search_flags, int divers, BnbDiversInfo& dinfo);
 
 // LPParser.ParseFromText, Models/LPParser.cs:9-79.  Throws LpxException(LPX_E_PARSE, message).
 LPProblem ParseFromText(const std::string& input);

@@ -1,5 +1,5 @@
 // lpx_handle.h -- the tableau handle and the host helpers its translation units share (lpx_tableau.cpp, lpx_tableau_resident.cpp,
-// lpx_tableau_groups.cpp, lpx_tableau_bounded.cpp, lpx_tableau_nodes.cpp).  Host .cpp files of this directory only: kernels and launchers see lpx_internal.h, never the struct.
+// lpx_tableau_groups.cpp, lpx_tableau_bounded.cpp, lpx_node_batch.cpp, lpx_tableau_nodes.cpp).  Host .cpp files of this directory only: kernels and launchers see lpx_internal.h, never the struct.
 #pragma once
 #include "lpx_internal.h"
 
@@ -29,6 +29,7 @@ struct lpx_tableau {
     lpx::DevState* st = nullptr;    // device
     lpx::DevState* hst = nullptr;   // pinned host mirror
     bool suspended = false;     // lpx_multi_run_some left this run unfinished: *hst is where it continues
+    bool trace_void = false;    // a clone before its first run: the state record is the source's, the trace was not copied and reads empty
     int32_t* frows = nullptr; int32_t* fcols = nullptr; int32_t* fchosen = nullptr; int fcap = 0;
     char* cutbuf = nullptr; char* cutbuf_h = nullptr; int cutcap = 0;   // staging of branching-row descriptors
     hipStream_t stream = nullptr;
@@ -91,6 +92,19 @@ namespace lpx {
 // (enqueued on the handle's stream; the caller waits).
 int bounds_snapshot(lpx_tableau* t);
 int bounds_restore(lpx_tableau* t);
+// lpx_tableau_clone's share: ub, lo, flip and the marks of src onto dst (same capacity), enqueued on dst's stream
+int bounds_clone(const lpx_tableau* src, lpx_tableau* dst);
+
+// The bounded family's checks (lpx_tableau_bounded.cpp), shared with the node batch (lpx_node_batch.cpp).
+// The checks set LPX_EINVAL's message with `what` in front and touch no device.
+int check_change_args(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const char* what);
+int check_pick_args(lpx_tableau* t, int nint, double tol, const void* out, const char* what);
+int check_long_flags(int flags, double cutoff, const char* what);
+int check_node_opts(const lpx_tableau* t, const lpx_run_opts* o, const char* what);   // R >= 2, no resident form, eps
+int check_node_fits(const lpx_tableau* t, const char* what);
+int bounded_node_ready(const char* what);       // the one-time attribute of the on-chip node kernels
+// what a finished on-chip node leaves on the host side of its handle, and the caller's record filled from the kernel's
+void node_onchip_commit(lpx_tableau* t, const NodeOut* rec, bool any_lo, lpx_node_record* out);
 
 static constexpr int LPX_RESIDENT_RETRY = -1000;     // internal: first resident launch timed out, state untouched
 
@@ -136,6 +150,7 @@ void make_ctx(lpx_tableau* t, const SelParams& p, const Params& key, Enqueue enq
 {
     const bool lookahead = p.mode != MODE_DUAL && p.mode != MODE_BOUNDED;
     c.stream = t->stream; c.st = t->st; c.hst = t->hst; c.trace = t->trace; c.trace_cap = t->trace_cap;
+    t->trace_void = false;
     c.events = &t->events; c.gexec = &t->gexec; c.g_batch = &t->g_batch; c.g_key = &t->g_key;
     c.key.assign(reinterpret_cast<const char*>(&key), sizeof(key));
     c.enqueue_iter = enqueue;

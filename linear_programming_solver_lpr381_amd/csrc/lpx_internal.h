@@ -117,6 +117,8 @@ size_t bounded_node_lds_bytes(int R, int C);        // dynamic LDS of the launch
 int bounded_node_fits(int R, int C);                // pure host arithmetic: 1 iff that and the kernel's statics fit one compute unit
 hipError_t bounded_node_init();                     // one-time function attribute
 hipError_t launch_bounded_node_onchip(const NodeParams& n, hipStream_t s);
+// the batch: workgroup b evaluates P[b] (an array the device can read); lds = the largest entry's bounded_node_lds_bytes
+hipError_t launch_bounded_nodes_onchip(const NodeParams* P, int B, size_t lds, hipStream_t s);
 
 // ---- lpx_kernels.hip: the two-launch select and update paths
 hipError_t launch_select(const SelParams& p, hipStream_t s);       // gather-based (dual path)

@@ -371,11 +371,12 @@ void lpx_bounded_close(lpx_bounded_session* s) { delete s; }
 // ---- branch and bound by bound changes on the root's handle (host/bnb_bounded.cpp) ------------------------------------------
 static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const double* upper, const uint8_t* is_int, const lpx_solve_opts* o,
                             int64_t max_nodes, int search_flags, lpx_result* out, lpx_bnb_bounded_info* info, const char* what,
-                            int node_form = -1)
+                            int node_form = -1, int divers = 0, lpx_bnb_divers_info* dinfo = nullptr)     // divers > 0: lpx_solve_bnb_bounded4
 {
     if (!p || !out) { set_error(std::string(what) + ": null argument"); return LPX_EINVAL; }
     std::memset(out, 0, sizeof(*out));
     if (info) std::memset(info, 0, sizeof(*info));
+    if (dinfo) std::memset(dinfo, 0, sizeof(*dinfo));
     lpx_solve_opts d; if (!o) { lpx_default_solve_opts(&d); o = &d; }
     return guarded(what, [&]() -> int {
         EngineOptions e = to_engine(o);
@@ -386,8 +387,14 @@ static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const do
         if (upper) up.assign(upper, upper + p->n);
         if (is_int) mask.assign(is_int, is_int + p->n);
         BnbBoundedInfo bi;
-        SimplexResult r = SolveBnbBounded(q, lo, up, mask, e, max_nodes, bi, search_flags, node_form);
+        BnbDiversInfo di;
+        SimplexResult r = divers ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di)
+                                 : SolveBnbBounded(q, lo, up, mask, e, max_nodes, bi, search_flags, node_form);
         fill_result(out, r, p->n);
+        if (dinfo) {
+            dinfo->rounds = di.rounds; dinfo->steals = di.steals; dinfo->largest_batch = di.largest_batch;
+            dinfo->round = dup_vec(di.round); dinfo->diver = dup_vec(di.diver);
+        }
         if (info) {
             info->nodes = bi.nodes; info->events = bi.events; info->flips = bi.flips; info->incumbents = bi.incumbents;
             info->pruned_bound = bi.pruned_bound; info->pruned_infeasible = bi.pruned_infeasible; info->max_K = bi.max_K;
@@ -420,6 +427,21 @@ int lpx_solve_bnb_bounded3(const lpx_problem* p, const double* lower, const doub
         return LPX_EINVAL;
     }
     return solve_bnb_bounded(p, lower, upper, is_int, o, max_nodes, search_flags, out, info, "lpx_solve_bnb_bounded3", node_form);
+}
+
+int lpx_solve_bnb_bounded4(const lpx_problem* p, const double* lower, const double* upper, const uint8_t* is_int,
+                           const lpx_solve_opts* o, int64_t max_nodes, int search_flags, int divers, lpx_result* out,
+                           lpx_bnb_bounded_info* info, lpx_bnb_divers_info* dinfo)
+{
+    if (divers < 1 || divers > 1024) { set_error("lpx_solve_bnb_bounded4: divers is outside [1, 1024]"); return LPX_EINVAL; }
+    return solve_bnb_bounded(p, lower, upper, is_int, o, max_nodes, search_flags, out, info, "lpx_solve_bnb_bounded4", -1, divers, dinfo);
+}
+
+void lpx_bnb_divers_info_free(lpx_bnb_divers_info* dinfo)
+{
+    if (!dinfo) return;
+    std::free(dinfo->round); std::free(dinfo->diver);
+    std::memset(dinfo, 0, sizeof(*dinfo));
 }
 
 void lpx_bnb_bounded_info_free(lpx_bnb_bounded_info* info)

@@ -1,0 +1,221 @@
+// lpx_node_batch.cpp -- host side of the batch of on-chip nodes (lpx_node_batch_*, C ABI of include/lpx.h): B nodes on B handles in
+// ONE launch of lpx_bounded_nodes_onchip (lpx_bounded_node.hip), one workgroup per node.  Every entry is the on-chip form of
+// lpx_bounded_node3 on its handle, bit for bit; the checks and what a finished node leaves on its handle are shared with it
+// (lpx_tableau_bounded.cpp, through lpx_handle.h).
+#include "lpx_handle.h"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+using namespace lpx;
+
+struct lpx_node_batch {
+    std::vector<lpx_tableau*> h;            // [W] borrowed
+    std::vector<hipStream_t> streams;       // the distinct streams of the handles; streams[0] carries the launch
+    char* slab = nullptr; size_t slab_bytes = 0;        // pinned: NodeParams [B], NodeOut [B] (64 bytes each), then per entry NodeIn + triples
+    char* edit = nullptr; size_t edit_bytes = 0;        // device: per entry the layout of one bound edit (5 K doubles, K int32)
+    uint8_t* mask = nullptr; size_t mask_cap = 0;       // device copy of the integer mask ...
+    std::vector<uint8_t> mask_h; int mask_n = -1;       // ... and the host bytes it was made from
+    std::vector<int32_t> seen; int32_t call = 0;        // seen[s] == call: slot s is named already in this call
+    std::vector<size_t> off_in, off_edit; std::vector<uint8_t> any_lo;      // per entry, kept to spare the steady state its allocations
+};
+
+namespace {
+
+constexpr size_t kOut = 64;
+static_assert(sizeof(NodeOut) <= kOut, "slab layout");
+size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// The launch goes behind whatever a handle's own stream still holds; in the steady state every stream is idle and this waits for
+// nothing.  settle_all looks at the distinct streams of ALL W borrowed handles (at most the 8 of the library's pool), not only at
+// those of the entries named in `slot`, and the launch always goes on streams[0], the first handle's, whether or not that handle
+// takes part.  Both are deliberate and safe: waiting for more streams than the contract names orders the launch behind a superset
+// of the work it must follow, and the host waits on streams[0] before it returns, so no handle's own stream can start later work
+// on a tableau the kernel is still writing.  Narrowing either would save nothing in the steady state.
+int settle(hipStream_t s)
+{
+    if (hipStreamQuery(s) == hipSuccess) return 0;
+    (void)hipGetLastError();
+    LPX_HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
+int settle_all(lpx_node_batch* b) { for (hipStream_t s : b->streams) { int rc = settle(s); if (rc) return rc; } return 0; }
+
+}  // namespace
+
+extern "C" {
+
+int lpx_node_batch_create(int W, lpx_tableau* const* handles, lpx_node_batch** out)
+{
+    const std::string w = "lpx_node_batch_create";
+    if (!out || !handles) { set_error(w + ": null argument"); return LPX_EINVAL; }
+    if (W < 1 || W > 1024) { set_error(w + ": W is outside [1, 1024]"); return LPX_EINVAL; }
+    for (int i = 0; i < W; ++i) {
+        const std::string at = w + ": handle " + std::to_string(i);
+        lpx_tableau* t = handles[i];
+        if (!t) { set_error(at + ": null handle"); return LPX_EINVAL; }
+        if (!t->bnd.bounds_set) { set_error(at + ": the handle has no bounds (lpx_tableau_set_bounds first)"); return LPX_EINVAL; }
+        if (t->bnd.bounds_C != t->C) { set_error(at + ": the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
+        int rc = check_node_fits(t, at.c_str()); if (rc) return rc;
+    }
+    {
+        std::vector<lpx_tableau*> sorted(handles, handles + W);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) { set_error(w + ": a handle is named twice"); return LPX_EINVAL; }
+    }
+    int rc = ensure_device(); if (rc) return rc;
+    rc = bounded_node_ready(w.c_str()); if (rc) return rc;
+    lpx_node_batch* b = new lpx_node_batch();
+    b->h.assign(handles, handles + W);
+    for (lpx_tableau* t : b->h)
+        if (std::find(b->streams.begin(), b->streams.end(), t->stream) == b->streams.end()) b->streams.push_back(t->stream);
+    b->seen.assign((size_t)W, 0);
+    b->off_in.resize((size_t)W); b->off_edit.resize((size_t)W); b->any_lo.resize((size_t)W);
+    *out = b;
+    return 0;
+}
+
+void lpx_node_batch_destroy(lpx_node_batch* b)
+{
+    if (!b) return;
+    for (hipStream_t s : b->streams) hipStreamSynchronize(s);
+    if (b->slab) hipHostFree(b->slab);
+    hipFree(b->edit); hipFree(b->mask);
+    delete b;
+}
+
+int lpx_node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const int32_t* K, const int32_t* cols, const double* lower,
+                       const double* upper, const lpx_run_opts* o, int flags, const double* cutoff, int nint, const uint8_t* is_int,
+                       double tol, lpx_node_record* out, int32_t* rc)
+{
+    const std::string w = "lpx_node_batch_run";
+    // ---- 1. every argument of every entry, before anything is written and before any device check
+    if (!slot || !K || !out || !rc) { set_error(w + ": null " + (!slot ? "slot" : !K ? "K" : !out ? "out" : "rc")); return LPX_EINVAL; }
+    if (B < 1) { set_error(w + ": B is outside [1, W]"); return LPX_EINVAL; }
+    { int r = check_long_flags(flags, 0.0, w.c_str()); if (r) return r; }
+    if (flags & LPX_BDUAL_CUTOFF) {
+        if (!cutoff) { set_error(w + ": null cutoff with LPX_BDUAL_CUTOFF"); return LPX_EINVAL; }
+        for (int i = 0; i < B; ++i) { int r = check_long_flags(flags, cutoff[i], (w + ": entry " + std::to_string(i)).c_str()); if (r) return r; }
+    }
+    if (!b) { set_error(w + ": null batch"); return LPX_EINVAL; }
+    const int W = (int)b->h.size();
+    if (B > W) { set_error(w + ": B is outside [1, W]"); return LPX_EINVAL; }
+    lpx_run_opts d; if (!o) { lpx_default_opts(&d, 1); o = &d; }
+    if (b->call == INT32_MAX) { std::fill(b->seen.begin(), b->seen.end(), 0); b->call = 0; }
+    ++b->call;
+    size_t sumK = 0, in_bytes = 0, edit_bytes = 0, lds = 0;
+    char at[48];                                                         // "lpx_node_batch_run: entry i", no allocation per entry
+    for (int i = 0; i < B; ++i) {
+        std::snprintf(at, sizeof at, "lpx_node_batch_run: entry %d", i);
+        if (slot[i] < 0 || slot[i] >= W) { set_error(std::string(at) + ": slot is outside [0, W)"); return LPX_EINVAL; }
+        if (b->seen[slot[i]] == b->call) { set_error(std::string(at) + ": slot repeats a handle"); return LPX_EINVAL; }
+        b->seen[slot[i]] = b->call;
+        lpx_tableau* t = b->h[slot[i]];
+        const int k = K[i];
+        int r = check_change_args(t, k, cols ? cols + sumK : nullptr, lower ? lower + sumK : nullptr, upper ? upper + sumK : nullptr, at);
+        if (r) return r;
+        r = check_pick_args(t, nint, tol, out, at); if (r) return r;
+        r = check_node_opts(t, o, at); if (r) return r;
+        r = check_node_fits(t, at); if (r) return r;
+        b->off_in[i] = in_bytes; b->off_edit[i] = edit_bytes;
+        in_bytes += up16(sizeof(NodeIn) + (size_t)k * (2 * sizeof(double) + sizeof(int32_t)));
+        edit_bytes += up16((size_t)k * (5 * sizeof(double) + sizeof(int32_t)));
+        lds = std::max(lds, bounded_node_lds_bytes(t->R, t->C));
+        sumK += (size_t)k;
+    }
+    int r = ensure_device(); if (r) return r;
+
+    // ---- 2. the buffers: grown to twice the need, and only when the need outgrows them
+    const size_t o_out = up16(sizeof(NodeParams) * (size_t)B), o_in = o_out + kOut * (size_t)B, need = o_in + in_bytes;
+    if (need > b->slab_bytes) {
+        r = settle_all(b); if (r) return r;
+        if (b->slab) hipHostFree(b->slab);
+        b->slab = nullptr; b->slab_bytes = 0;
+        LPX_HIP_TRY(hipHostMalloc((void**)&b->slab, 2 * need));
+        b->slab_bytes = 2 * need;
+    }
+    if (edit_bytes > b->edit_bytes) {
+        r = settle_all(b); if (r) return r;
+        hipFree(b->edit); b->edit = nullptr; b->edit_bytes = 0;
+        LPX_HIP_TRY(hipMalloc((void**)&b->edit, 2 * edit_bytes));
+        b->edit_bytes = 2 * edit_bytes;
+    }
+    hipStream_t s = b->streams[0];
+    const bool has_mask = is_int && nint > 0;
+    if (has_mask && !(b->mask_n == nint && std::memcmp(b->mask_h.data(), is_int, (size_t)nint) == 0)) {
+        r = settle(s); if (r) return r;                                  // an earlier copy may still read mask_h
+        if ((size_t)nint > b->mask_cap) {
+            hipFree(b->mask); b->mask = nullptr; b->mask_cap = 0;
+            LPX_HIP_TRY(hipMalloc((void**)&b->mask, 2 * (size_t)nint));
+            b->mask_cap = 2 * (size_t)nint;
+        }
+        b->mask_h.assign(is_int, is_int + nint);
+        LPX_HIP_TRY(hipMemcpyAsync(b->mask, b->mask_h.data(), (size_t)nint, hipMemcpyHostToDevice, s));
+        b->mask_n = nint;
+    }
+
+    // ---- 3. the slab: a parameter record, a header with its triples and a result record per entry
+    NodeParams* P = reinterpret_cast<NodeParams*>(b->slab);
+    sumK = 0;
+    for (int i = 0; i < B; ++i) {
+        lpx_tableau* t = b->h[slot[i]];
+        lpx_tableau::Bounds& bn = t->bnd;
+        const int k = K[i];
+        const double* lw = lower + sumK; const double* up = upper + sumK; const int32_t* cl = cols + sumK;
+        bool any_lo = false;
+        for (int j = 0; j < k; ++j) if (lw[j] != 0.0) any_lo = true;
+        b->any_lo[i] = any_lo ? 1 : 0;
+        NodeIn* in = reinterpret_cast<NodeIn*>(b->slab + o_in + b->off_in[i]);
+        std::memset(in, 0, sizeof(*in));
+        in->K = k; in->flags = flags; in->nint = nint; in->has_mask = has_mask ? 1 : 0; in->max_iter = o->max_iter;
+        in->lo_used = (bn.lo_used || any_lo) ? 1 : 0;
+        in->eps = o->eps; in->ratio_tol = o->ratio_tol; in->cutoff = (flags & LPX_BDUAL_CUTOFF) ? cutoff[i] : 0.0; in->tol = tol;
+        if (k > 0) {
+            double* a = reinterpret_cast<double*>(in + 1);
+            std::memcpy(a, lw, sizeof(double) * k);
+            std::memcpy(a + k, up, sizeof(double) * k);
+            std::memcpy(a + 2 * (size_t)k, cl, sizeof(int32_t) * k);
+        }
+        NodeParams& n = P[i];
+        std::memset(&n, 0, sizeof(n));
+        n.T = t->T; n.ld = t->ld; n.R = t->R; n.C = t->C;
+        n.rhsbuf = t->rhsbuf; n.basis = t->basis; n.trace = t->trace; n.trace_cap = t->trace_cap; n.st = t->st;
+        n.ub = bn.ub; n.lo = bn.lo; n.flip = bn.flip; n.edit = reinterpret_cast<double*>(b->edit + b->off_edit[i]); n.mask = b->mask;
+        n.in = in; n.out = reinterpret_cast<NodeOut*>(b->slab + o_out + kOut * (size_t)i);
+        std::memset(&out[i], 0, sizeof(out[i]));
+        out[i].pick.var = -1;
+        sumK += (size_t)k;
+    }
+
+    // ---- 4. behind the handles' own streams, ONE launch, ONE wait
+    r = settle_all(b); if (r) return r;
+    LPX_HIP_TRY(launch_bounded_nodes_onchip(P, B, lds, s));
+    LPX_HIP_TRY(hipStreamSynchronize(s));
+
+    // ---- 5. the records
+    bool refused = false;
+    for (int i = 0; i < B; ++i) {
+        lpx_tableau* t = b->h[slot[i]];
+        const NodeOut* rec = reinterpret_cast<const NodeOut*>(b->slab + o_out + kOut * (size_t)i);
+        if (rec->status < 0) {                                           // refused by the kernel: this handle is as it was
+            rc[i] = LPX_EINVAL;
+            out[i].unrepairable = rec->unrepairable;
+            if (!refused) {
+                const std::string at = w + ": entry " + std::to_string(i);
+                if (rec->inf_k >= 0) set_error(at + ": upper[" + std::to_string(rec->inf_k) + "] = +inf on a flipped column");
+                else set_error(at + ": " + std::to_string(rec->unrepairable) + " column(s) with a negative reduced cost and no upper "
+                               "bound: a bound flip cannot restore dual feasibility");
+            }
+            refused = true;
+            continue;
+        }
+        node_onchip_commit(t, rec, b->any_lo[i] != 0, &out[i]);
+        rc[i] = rec->status;
+    }
+    return 0;
+}
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 // lpx_tableau.cpp -- device-resident tableau handle (lifecycle, transfers, snapshot) and the host side of the single-LP simplex
 // loops (C ABI of include/lpx.h).  The resident runs are in lpx_tableau_resident.cpp, the group runs and lpx_multi_run* in
-// lpx_tableau_groups.cpp, the bounded-variable family in lpx_tableau_bounded.cpp, node assembly and the parent store in
-// lpx_tableau_nodes.cpp.  Host code only: kernels live in lpx_kernels.hip (two-launch paths) and lpx_pivot_fused.hip.
+// lpx_tableau_groups.cpp, the bounded-variable family in lpx_tableau_bounded.cpp (its batch of on-chip nodes in
+// lpx_node_batch.cpp), node assembly and the parent store in lpx_tableau_nodes.cpp.  Host code only: kernels live in lpx_kernels.hip (two-launch paths) and lpx_pivot_fused.hip.
 #include "lpx_handle.h"
 
 #include <cstdlib>
@@ -166,6 +166,37 @@ void lpx_tableau_destroy(lpx_tableau* t)
     delete t;                       // the stream is borrowed (borrow_stream), not owned
 }
 
+// A second handle in the state of the first (include/lpx.h): the live window, the basis, the RHS copy, the bounds and the loop
+// state.  The capacity is the source's, so that ld -- and with it every kernel's geometry -- is the same on both.
+int lpx_tableau_clone(const lpx_tableau* src, lpx_tableau** out)
+{
+    if (!src || !out) { set_error("lpx_tableau_clone: null argument"); return LPX_EINVAL; }
+    if (src->suspended || src->suspended2 || src->fsuspended) {     // what continues such a run lives beside the state record, and is not copied
+        set_error("lpx_tableau_clone: the source is in the middle of a run that lpx_multi_run_some left unfinished");
+        return LPX_EINVAL;
+    }
+    lpx_tableau* c = nullptr;
+    int rc = lpx_tableau_create(src->Rcap, src->Ccap, &c); if (rc) return rc;
+    auto fail = [&](int code) { lpx_tableau_destroy(c); return code; };
+    auto copy = [&]() -> int {
+        LPX_HIP_TRY(hipStreamSynchronize(src->stream));              // the source's last run is complete; it is only read from here on
+        c->R = src->R; c->C = src->C; c->shape_h[0] = src->R; c->shape_h[1] = src->C;
+        LPX_HIP_TRY(hipMemcpyAsync(c->shape, c->shape_h, sizeof(int32_t) * 2, hipMemcpyHostToDevice, c->stream));
+        LPX_HIP_TRY(hipMemcpyAsync(c->T, src->T, sizeof(double) * (size_t)src->R * src->ld, hipMemcpyDeviceToDevice, c->stream));
+        if (src->R > 1) LPX_HIP_TRY(hipMemcpyAsync(c->basis, src->basis, sizeof(int32_t) * (src->R - 1), hipMemcpyDeviceToDevice, c->stream));
+        LPX_HIP_TRY(hipMemcpyAsync(c->rhsbuf, src->rhsbuf, sizeof(double) * src->R, hipMemcpyDeviceToDevice, c->stream));
+        LPX_HIP_TRY(hipMemcpyAsync(c->st, src->st, sizeof(DevState), hipMemcpyDeviceToDevice, c->stream));
+        *c->hst = *src->hst;
+        c->trace_void = true;                                        // the record says how many events the source made; the trace stayed there
+        int r = bounds_clone(src, c); if (r) return r;
+        LPX_HIP_TRY(hipStreamSynchronize(c->stream));
+        return 0;
+    };
+    rc = copy(); if (rc) return fail(rc);
+    *out = c;
+    return 0;
+}
+
 int lpx_tableau_shape(const lpx_tableau* t, int* R, int* C, int* ld)
 {
     if (!t) return LPX_EINVAL;
@@ -259,7 +290,7 @@ int lpx_tableau_trace(lpx_tableau* t, int32_t* trace, int cap, int* n)
     if (!t) return LPX_EINVAL;
     LPX_HIP_TRY(hipMemcpyAsync(t->hst, t->st, sizeof(DevState), hipMemcpyDeviceToHost, t->stream));
     LPX_HIP_TRY(hipStreamSynchronize(t->stream));
-    int k = t->hst->iter;
+    int k = t->trace_void ? 0 : t->hst->iter;
     if (k > t->trace_cap) k = t->trace_cap;
     if (n) *n = k;
     if (trace && cap > 0) {
@@ -321,6 +352,7 @@ int lpx::continue_streaming(lpx_tableau* t, const lpx_run_opts* o, bool dual, co
 SelParams lpx::base_params(lpx_tableau* t, const lpx_run_opts* o, int mode)
 {
     SelParams p; std::memset(&p, 0, sizeof(p));
+    t->trace_void = false;
     p.T = t->T; p.ld = t->ld; p.R = t->Rcap; p.C = t->Ccap; p.shape = t->shape;
     p.prow = t->prow; p.pcol = t->pcol; p.col0 = t->col0; p.col1 = t->col1; p.rhsbuf = t->rhsbuf; p.basis = t->basis; p.trace = t->trace; p.trace_cap = t->trace_cap;
     p.st = t->st;

@@ -43,6 +43,21 @@ int lpx::bounds_restore(lpx_tableau* t)
     return 0;
 }
 
+int lpx::bounds_clone(const lpx_tableau* src, lpx_tableau* dst)
+{
+    const lpx_tableau::Bounds& a = src->bnd;
+    lpx_tableau::Bounds& b = dst->bnd;
+    if (!a.bounds_set) return 0;
+    LPX_HIP_TRY(hipMalloc((void**)&b.ub, sizeof(double) * dst->Ccap));
+    LPX_HIP_TRY(hipMalloc((void**)&b.flip, dst->Ccap));
+    LPX_HIP_TRY(hipMalloc((void**)&b.lo, sizeof(double) * dst->Ccap));
+    LPX_HIP_TRY(hipMemcpyAsync(b.ub, a.ub, sizeof(double) * dst->Ccap, hipMemcpyDeviceToDevice, dst->stream));
+    LPX_HIP_TRY(hipMemcpyAsync(b.flip, a.flip, dst->Ccap, hipMemcpyDeviceToDevice, dst->stream));
+    LPX_HIP_TRY(hipMemcpyAsync(b.lo, a.lo, sizeof(double) * dst->Ccap, hipMemcpyDeviceToDevice, dst->stream));
+    b.bounds_set = true; b.bounds_C = a.bounds_C; b.lo_used = a.lo_used;
+    return 0;
+}
+
 namespace {
 
 // pinned slab: {int32 cnt[2], pad} at 0, lpx_branch_pick at 16
@@ -98,8 +113,10 @@ int check_bounds(const lpx_tableau* t, const char* what, bool required)
     return 0;
 }
 
+}  // namespace
+
 // the argument checks of lpx_tableau_change_bounds (lpx_bounded_node makes the same ones): LPX_EINVAL with `what` in front
-int check_change_args(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const char* what)
+int lpx::check_change_args(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const char* what)
 {
     const std::string w = what;
     if (!t) { set_error(w + ": null handle"); return LPX_EINVAL; }
@@ -119,7 +136,7 @@ int check_change_args(lpx_tableau* t, int K, const int32_t* cols, const double* 
     return check_bounds(t, what, true);
 }
 
-int check_pick_args(lpx_tableau* t, int nint, double tol, const void* out, const char* what)
+int lpx::check_pick_args(lpx_tableau* t, int nint, double tol, const void* out, const char* what)
 {
     const std::string w = what;
     if (!t) { set_error(w + ": null handle"); return LPX_EINVAL; }
@@ -128,6 +145,8 @@ int check_pick_args(lpx_tableau* t, int nint, double tol, const void* out, const
     if (!(tol >= 0.0 && tol < 0.5)) { set_error(w + ": tol is not in [0, 0.5)"); return LPX_EINVAL; }
     return 0;
 }
+
+namespace {
 
 // One bound edit staged on the device: the caller's arrays in the handle's staging buffer, one layout for every entry point --
 // lower, upper, shift, the saved (ub, lo) pairs, cols ([K] each, save [2K]; lpx_tableau_change_bounds leaves the save area unused).
@@ -245,6 +264,54 @@ int enqueue_pick(lpx_tableau* t, int nint, const uint8_t* is_int, double tol)
 }
 
 }  // namespace
+
+int lpx::check_long_flags(int flags, double cutoff, const char* what)
+{
+    if (flags & ~(LPX_BDUAL_SKIP_FIXED | LPX_BDUAL_LONG_STEP | LPX_BDUAL_CUTOFF)) { set_error(std::string(what) + ": unknown flag"); return LPX_EINVAL; }
+    if ((flags & LPX_BDUAL_CUTOFF) && cutoff != cutoff) { set_error(std::string(what) + ": cutoff is NaN"); return LPX_EINVAL; }
+    return 0;
+}
+
+// the option checks of a node call, after its argument checks, and the fit of the on-chip form
+int lpx::check_node_opts(const lpx_tableau* t, const lpx_run_opts* o, const char* what)
+{
+    const std::string w = what;
+    if (t->R < 2) { set_error(w + ": tableau needs at least one constraint row"); return LPX_EINVAL; }
+    if (o->resident > 0) { set_error(w + ": there is no resident form of the bounded dual loop"); return LPX_EINVAL; }
+    if (!(o->eps >= 0.0)) { set_error(w + ": eps is negative or NaN"); return LPX_EINVAL; }
+    return 0;
+}
+
+int lpx::check_node_fits(const lpx_tableau* t, const char* what)
+{
+    if (bounded_node_fits(t->R, t->C)) return 0;
+    set_error(std::string(what) + ": the live " + std::to_string(t->R) + " x " + std::to_string(t->C) + " window does not fit the on-chip form "
+              "(lpx_bounded_node_fits)");
+    return LPX_EINVAL;
+}
+
+int lpx::bounded_node_ready(const char* what)
+{
+    static std::once_flag once; static hipError_t init_err = hipSuccess;
+    std::call_once(once, [] { init_err = bounded_node_init(); });
+    if (init_err != hipSuccess) { set_error(std::string(what) + ": kernel attribute setup failed: " + hipGetErrorString(init_err)); return LPX_EDEVICE; }
+    return 0;
+}
+
+void lpx::node_onchip_commit(lpx_tableau* t, const NodeOut* rec, bool any_lo, lpx_node_record* out)
+{
+    lpx_tableau::Bounds& b = t->bnd;
+    t->suspended = t->suspended2 = t->fsuspended = false;
+    t->trace_void = false;                  // the node ran and wrote its trace; a refused one leaves a clone's mark standing
+    if (any_lo) b.lo_used = true;
+    DevState h = fresh_state(false);                                             // the host mirror, as the loop of the launches form leaves it
+    h.status = rec->status; h.iter = rec->events; h.fdf_count = rec->kind0; h.dual_iter = rec->kind1; h.primal_count = rec->events;
+    *t->hst = h;
+    b.bcounts[0] = rec->kind0; b.bcounts[1] = rec->kind1; b.bcounts[2] = (int64_t)rec->events - rec->kind0 - rec->kind1;
+    out->status = rec->status; out->events = rec->events; out->kind0 = rec->kind0; out->kind1 = rec->kind1; out->flips = rec->flips;
+    out->pick.z = rec->z;
+    if (rec->status == LPX_OPTIMAL) { out->pick.var = rec->var; out->pick.candidates = rec->candidates; out->pick.x_var = rec->x_var; }
+}
 
 extern "C" {
 
@@ -457,13 +524,6 @@ int lpx_bounded_node(lpx_tableau* t, int K, const int32_t* cols, const double* l
 }
 
 // ---- long-step ratio test and objective cutoff (the dual loop's forms with a flag beyond LPX_BDUAL_SKIP_FIXED) ----
-static int check_long_flags(int flags, double cutoff, const char* what)
-{
-    if (flags & ~(LPX_BDUAL_SKIP_FIXED | LPX_BDUAL_LONG_STEP | LPX_BDUAL_CUTOFF)) { set_error(std::string(what) + ": unknown flag"); return LPX_EINVAL; }
-    if ((flags & LPX_BDUAL_CUTOFF) && cutoff != cutoff) { set_error(std::string(what) + ": cutoff is NaN"); return LPX_EINVAL; }
-    return 0;
-}
-
 int lpx_bounded_dual_run3(lpx_tableau* t, const lpx_run_opts* o, int flags, double cutoff, lpx_pivot_cb cb, void* user, lpx_stats* st)
 {
     const int rc = check_long_flags(flags, cutoff, "lpx_bounded_dual_run3"); if (rc) return rc;
@@ -488,9 +548,7 @@ static int bounded_node_onchip(lpx_tableau* t, int K, const int32_t* cols, const
 {
     const std::string w = what;
     int rc = bounded_ready(t, true); if (rc) return rc;
-    static std::once_flag once; static hipError_t init_err = hipSuccess;
-    std::call_once(once, [] { init_err = bounded_node_init(); });
-    if (init_err != hipSuccess) { set_error(w + ": kernel attribute setup failed: " + hipGetErrorString(init_err)); return LPX_EDEVICE; }
+    rc = bounded_node_ready(what); if (rc) return rc;
     lpx_tableau::Bounds& b = t->bnd;
     std::memset(out, 0, sizeof(*out));
     out->pick.var = -1;
@@ -546,15 +604,7 @@ static int bounded_node_onchip(lpx_tableau* t, int K, const int32_t* cols, const
                   "bound: a bound flip cannot restore dual feasibility");
         return LPX_EINVAL;
     }
-    t->suspended = t->suspended2 = t->fsuspended = false;
-    if (any_lo) b.lo_used = true;
-    DevState h = fresh_state(false);                                             // the host mirror, as the loop of the launches form leaves it
-    h.status = rec->status; h.iter = rec->events; h.fdf_count = rec->kind0; h.dual_iter = rec->kind1; h.primal_count = rec->events;
-    *t->hst = h;
-    b.bcounts[0] = rec->kind0; b.bcounts[1] = rec->kind1; b.bcounts[2] = (int64_t)rec->events - rec->kind0 - rec->kind1;
-    out->status = rec->status; out->events = rec->events; out->kind0 = rec->kind0; out->kind1 = rec->kind1; out->flips = rec->flips;
-    out->pick.z = rec->z;
-    if (rec->status == LPX_OPTIMAL) { out->pick.var = rec->var; out->pick.candidates = rec->candidates; out->pick.x_var = rec->x_var; }
+    node_onchip_commit(t, rec, any_lo, out);
     return rec->status;
 }
 
@@ -570,14 +620,8 @@ int lpx_bounded_node3(lpx_tableau* t, int K, const int32_t* cols, const double* 
     rc = check_change_args(t, K, cols, lower, upper, what); if (rc) return rc;
     rc = check_pick_args(t, nint, tol, out, what); if (rc) return rc;
     lpx_run_opts d; if (!o) { lpx_default_opts(&d, 1); o = &d; }
-    if (t->R < 2) { set_error(w + ": tableau needs at least one constraint row"); return LPX_EINVAL; }
-    if (o->resident > 0) { set_error(w + ": there is no resident form of the bounded dual loop"); return LPX_EINVAL; }
-    if (!(o->eps >= 0.0)) { set_error(w + ": eps is negative or NaN"); return LPX_EINVAL; }
-    if (!bounded_node_fits(t->R, t->C)) {
-        set_error(w + ": the live " + std::to_string(t->R) + " x " + std::to_string(t->C) + " window does not fit the on-chip form "
-                  "(lpx_bounded_node_fits)");
-        return LPX_EINVAL;
-    }
+    rc = check_node_opts(t, o, what); if (rc) return rc;
+    rc = check_node_fits(t, what); if (rc) return rc;
     return bounded_node_onchip(t, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, what);
 }
 

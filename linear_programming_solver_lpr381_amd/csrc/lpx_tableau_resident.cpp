@@ -81,6 +81,7 @@ int lpx::run_resident(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, vo
     { int rc = resident_buffers(t); if (rc) return rc; }
     if (col) { int rc = resident_col_buffers(t, grid); if (rc) return rc; }
     *t->hst = fresh_state(false);
+    t->trace_void = false;
     LPX_HIP_TRY(hipMemcpyAsync(t->st, t->hst, sizeof(DevState), hipMemcpyHostToDevice, t->stream));
     const int chunk = cb ? (o->batch > 0 ? o->batch : 256) : (1 << 30);
     lpx_stats local; std::memset(&local, 0, sizeof(local));
@@ -243,6 +244,7 @@ int lpx::run_resident_group(lpx_tableau** ts, const int* dual, int count, const 
     for (int i = 0; i < count; ++i) {
         lpx_tableau* t = ts[i];
         { int rc = wait_once(t->stream); if (rc) return rc; }          // node assembly ran on the node's own stream
+        t->trace_void = false;
         if (!t->xr) {
             { int rc = resident_buffers(t); if (rc) return rc; }
             LPX_HIP_TRY(hipStreamSynchronize(t->stream));

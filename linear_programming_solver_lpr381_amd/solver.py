@@ -342,7 +342,8 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         return res
 
     def SolveBnbBounded(self, problem: LPProblem, upper, lower=None, integer=None, max_nodes: int = 0,
-                        long_step: bool = False, cutoff: bool = False, node_form: str = "launches") -> SimplexResult:
+                        long_step: bool = False, cutoff: bool = False, node_form: Optional[str] = None,
+                        divers: Optional[int] = None) -> SimplexResult:
         """Branch and bound by bound changes on one device tableau (lpx_solve_bnb_bounded): lower <= x <= upper, x_j integer
         where integer[j] (None: every variable); integer variables need finite, integral bounds.  Status OPTIMAL or INFEASIBLE,
         Solution, OptimalValue (user's sense), Nodes, BnbInfo (counters) and BnbLog, a structured array with one record per node
@@ -351,7 +352,16 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         long-step ratio test / stops as soon as its objective has fallen to the incumbent + 1e-6 (such a node is logged with
         status CUTOFF and counted as pruned by bound); both off is lpx_solve_bnb_bounded.  node_form "onchip" | "auto"
         (lpx_solve_bnb_bounded3): every node is one kernel launch with the tableau in LDS ("auto": iff the root fits); the node
-        log is bit-equal to "launches", the default."""
+        log is bit-equal to "launches", the default.  divers=W (lpx_solve_bnb_bounded4): W handles dive at once, every round
+        evaluates one node per diver on chip in one kernel launch; divers=1 gives the log of node_form="onchip", any W gives a
+        log that depends on the model, the flags and W alone.  Use long_step=True with divers on larger models: another W visits
+        other nodes, and without the long step some of them make max_iter events and end the solve with ITER_LIMIT (on
+        binary_ip(128, 64), W = 4, 64 and 256 do; with the long step none measured did).  The result then carries BnbInfo["rounds" / "steals" /
+        "largest_batch"] and BnbRound / BnbDiver, the round and the diver of every log record."""
+        if divers is not None and node_form == "launches":
+            raise ValueError("divers evaluates every node on chip: it cannot be combined with node_form='launches'")
+        if node_form is None:               # not given: "launches", the default; with divers every node is on chip
+            node_form = "launches" if divers is None else "onchip"
         if node_form not in _lib.NODE_FORMS:
             raise ValueError(f"unknown node form {node_form!r}")
         n = problem.NumVars
@@ -369,9 +379,12 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         if integer is not None:
             mask = np.ascontiguousarray(np.broadcast_to(np.asarray(integer, dtype=np.uint8), (n,)))
             mp = mask.ctypes.data_as(C.POINTER(C.c_uint8))
-        r, info = _lib.Result(), _lib.BnbBoundedInfo()
+        r, info, dinfo = _lib.Result(), _lib.BnbBoundedInfo(), _lib.BnbDiversInfo()
         flags = (_lib.BDUAL_LONG_STEP if long_step else 0) | (_lib.BDUAL_CUTOFF if cutoff else 0)
-        if node_form != "launches":
+        if divers is not None:
+            rc = lib().lpx_solve_bnb_bounded4(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), flags, int(divers),
+                                              C.byref(r), C.byref(info), C.byref(dinfo))
+        elif node_form != "launches":
             rc = lib().lpx_solve_bnb_bounded3(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), flags, _lib.NODE_FORMS[node_form],
                                               C.byref(r), C.byref(info))
         elif flags:
@@ -387,10 +400,17 @@ class LPSolver:             # Models/LPSolver.cs:6-77
                 C.memmove(log.ctypes.data, info.log, info.n_log * C.sizeof(_lib.BnbNodeLog))
             counters = {k: getattr(info, k) for k in ("nodes", "events", "flips", "incumbents", "pruned_bound",
                                                       "pruned_infeasible", "max_K", "constant")}
+            if divers is not None:
+                counters.update({k: getattr(dinfo, k) for k in ("rounds", "steals", "largest_batch")})
+                rounds = np.ctypeslib.as_array(dinfo.round, (info.n_log,)).copy() if info.n_log else np.zeros(0, dtype=np.int32)
+                who = np.ctypeslib.as_array(dinfo.diver, (info.n_log,)).copy() if info.n_log else np.zeros(0, dtype=np.int32)
         finally:
             lib().lpx_bnb_bounded_info_free(C.byref(info))
+            lib().lpx_bnb_divers_info_free(C.byref(dinfo))
         res = _take_result(r, n)
         res.BnbLog, res.BnbInfo = log, counters
+        if divers is not None:
+            res.BnbRound, res.BnbDiver = rounds, who
         if rc != 0:
             e = SolverException(rc, msg)
             e.result = res

@@ -64,6 +64,15 @@ class DeviceTableau:
         t.upload(T, basis)
         return t
 
+    def clone(self) -> "DeviceTableau":
+        """A second handle in the state of this one (lpx_tableau_clone): the live window, the basis, the bounds with their flips
+        and lower shifts, and the loop state.  The snapshot and the trace stay behind; this handle is left as it was."""
+        t = object.__new__(type(self))
+        t._h = C.c_void_p()
+        check(lib().lpx_tableau_clone(self._h, C.byref(t._h)))
+        t.R, t.C = self.R, self.C
+        return t
+
     def set_shape(self, R: int, C_: int):
         check(lib().lpx_tableau_set_shape(self._h, int(R), int(C_)))
         self.R, self.C = int(R), int(C_)
@@ -358,9 +367,7 @@ class DeviceTableau:
         else:
             check(lib().lpx_bounded_node(self._h, len(cols), cols.ctypes.data_as(ip), lower.ctypes.data_as(dp),
                                          upper.ctypes.data_as(dp), C.byref(o), int(nint), mp, float(tol), C.byref(rec)))
-        return {"status": rec.status, "events": rec.events, "kind0": rec.kind0, "kind1": rec.kind1, "flips": rec.flips,
-                "unrepairable": rec.unrepairable, "var": rec.pick.var, "candidates": rec.pick.candidates,
-                "x_var": rec.pick.x_var, "z": rec.pick.z}
+        return _node_dict(rec)
 
     def bounded_node_fits(self) -> bool:
         """True iff the on-chip form of bounded_node accepts the live shape (lpx_bounded_node_fits: host arithmetic only)."""
@@ -379,6 +386,80 @@ class DeviceTableau:
                                           len(rows), float(thresh), chosen.ctypes.data_as(ip),
                                           C.byref(o), C.byref(st)))
         return chosen, st.as_dict()
+
+
+def _node_dict(rec) -> dict:
+    return {"status": rec.status, "events": rec.events, "kind0": rec.kind0, "kind1": rec.kind1, "flips": rec.flips,
+            "unrepairable": rec.unrepairable, "var": rec.pick.var, "candidates": rec.pick.candidates,
+            "x_var": rec.pick.x_var, "z": rec.pick.z}
+
+
+class NodeBatch:
+    """B branch-and-bound nodes on B handles in ONE kernel launch (lpx_node_batch_*): every entry is bit-equal to
+    DeviceTableau.bounded_node(form="onchip") on its handle.  The handles are borrowed: they must have bounds set, fit the on-chip
+    form and outlive the batch."""
+
+    def __init__(self, handles):
+        self._handles = list(handles)
+        self._W = len(self._handles)
+        self._h = C.c_void_p()
+        hs = (C.c_void_p * max(self._W, 1))(*[t._h for t in self._handles])
+        check(lib().lpx_node_batch_create(self._W, hs, C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            lib().lpx_node_batch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def run(self, slots, nodes, nint: int, is_int=None, tol: float = 1e-6, long_step: bool = False, cutoffs=None,
+            opts: Optional[RunOpts] = None, **kw) -> list:
+        """Entry i evaluates nodes[i] = (cols, lower, upper) on handles[slots[i]]; the slots are distinct.  cutoffs: one objective
+        cutoff per entry (None: no cutoff).  Returns one record dict per entry in the shape of DeviceTableau.bounded_node; an
+        entry the kernel refused (its handle is as it was) has status None, and last_error() holds the first one's message."""
+        slots = np.ascontiguousarray(np.atleast_1d(slots), dtype=np.int32).reshape(-1)
+        B = len(slots)
+        if len(nodes) != B:
+            raise ValueError(f"{B} slots but {len(nodes)} nodes")
+        if B < 1 or B > self._W:
+            raise ValueError(f"a batch of {B} entries on {self._W} handles: B must be in [1, W]")
+        cs, ls, us = [], [], []
+        for cols, lower, upper in nodes:
+            c = np.ascontiguousarray(np.atleast_1d(cols), dtype=np.int32).reshape(-1)
+            cs.append(c)
+            ls.append(np.broadcast_to(np.asarray(lower, dtype=np.float64), c.shape))
+            us.append(np.broadcast_to(np.asarray(upper, dtype=np.float64), c.shape))
+        K = np.array([len(c) for c in cs], dtype=np.int32)
+        cols = np.ascontiguousarray(np.concatenate(cs), dtype=np.int32)
+        lower = np.ascontiguousarray(np.concatenate(ls), dtype=np.float64)
+        upper = np.ascontiguousarray(np.concatenate(us), dtype=np.float64)
+        flags = (_lib.BDUAL_SKIP_FIXED | (_lib.BDUAL_LONG_STEP if long_step else 0)
+                 | (_lib.BDUAL_CUTOFF if cutoffs is not None else 0))
+        cut, cp = None, None
+        if cutoffs is not None:
+            cut = np.ascontiguousarray(np.broadcast_to(np.asarray(cutoffs, dtype=np.float64), (B,)))
+            cp = cut.ctypes.data_as(dp)
+        o = opts if opts is not None else default_opts(True, **kw)
+        keep, mp = DeviceTableau._mask(is_int, int(nint))
+        recs = (_lib.NodeRecord * B)()
+        rc = np.zeros(B, dtype=np.int32)
+        check(lib().lpx_node_batch_run(self._h, B, slots.ctypes.data_as(ip), K.ctypes.data_as(ip), cols.ctypes.data_as(ip),
+                                       lower.ctypes.data_as(dp), upper.ctypes.data_as(dp), C.byref(o), flags, cp, int(nint), mp,
+                                       float(tol), recs, rc.ctypes.data_as(ip)))
+        out = []
+        for i in range(B):
+            d = _node_dict(recs[i])
+            if rc[i] < 0:
+                d["status"] = None
+            out.append(d)
+        return out
 
 
 def primal_tableau(T: np.ndarray, basis: np.ndarray, eps: float = 1e-9, max_iter: int = 10000,

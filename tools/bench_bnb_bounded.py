@@ -23,9 +23,15 @@ node call on the solved root and of the root's first child (200 calls a sample, 
 child's events, and the driver to optimality under `--flag-sets` (comma-separated out of plain,long_step,cutoff,both; default
 all four) in both forms, alternating, REPS timed solves after one untimed solve of 2000 nodes each (`--flag-sets none`: no driver runs); counts must
 be equal across forms.
+`--compare-divers LIST` measures the search by W divers (lpx_solve_bnb_bounded4) against the single-diver
+on-chip driver: per model and flag set (`--flag-sets`, default here plain,both) the on-chip driver and each W of the
+comma-separated LIST alternate in one process, REPS timed solves each after one untimed solve; nodes, events, rounds, nodes/s
+and wall per form, and `wins`: a W wins iff its median lies below the single-diver form's minimum.
+`--divers W` makes side (b), and `--trace-only`, the search by W divers.
 `--trace-only` runs one solve of side (b) and nothing else (for a kernel trace of the node form given).
 
-usage: bench_bnb_bounded.py [--model NAME] [--max-nodes N] [--node-form F] [--compare-forms [--flag-sets LIST]] [--trace-only] [REPS]"""
+usage: bench_bnb_bounded.py [--model NAME] [--max-nodes N] [--node-form F] [--divers W] [--compare-forms [--flag-sets LIST]]
+                            [--compare-divers LIST [--flag-sets LIST]] [--trace-only] [REPS]"""
 import json
 import os
 import statistics
@@ -131,10 +137,56 @@ def compare_forms(n, m, reps, max_nodes, flag_sets):
     return rec
 
 
+def compare_divers(n, m, reps, max_nodes, flag_sets, widths):
+    """The search by W divers against the single-diver on-chip driver on binary_ip(n, m) (see the module docstring)."""
+    c, A, rel, b = synth.binary_ip(n, m)
+    bnd_p = L.LPProblem.from_arrays(0, c, A[:m], rel[:m], b[:m])
+    rec = {"n": n, "m": m, "bounded_shape": [m + 1, n + m + 1]}
+    sides = ["onchip"] + [f"W{w}" for w in widths]
+
+    def solve(side, kw, limit=None):
+        limit = max_nodes if limit is None else limit
+        how = {"node_form": "onchip"} if side == "onchip" else {"divers": int(side[1:])}
+        t0 = time.perf_counter()
+        try:
+            r = L.LPSolver().SolveBnbBounded(bnd_p, 1.0, max_nodes=limit, **how, **kw)
+            r.Limit = None
+        except L.SolverException as e:
+            if e.code != L._lib.ITER_LIMIT:
+                raise
+            r = e.result
+            r.Limit = None if limit and r.Nodes >= limit else str(e)      # a node at its event limit ends the solve: reported, not timed against
+        return 1e3 * (time.perf_counter() - t0), r
+
+    for fs in flag_sets:
+        kw = FLAG_SETS[fs]
+        ts = {s: [] for s in sides}
+        last = {}
+        for i in range(reps + 1):
+            for s in sides:
+                if i == 0:          # the untimed solve: clones, the batch's slab and the first launch are paid here
+                    solve(s, kw, max_nodes if max_nodes else 2000)
+                    continue
+                ms, r = solve(s, kw)
+                last[s] = r
+                ts[s].append(ms)
+        base = stats(ts["onchip"])
+        d = {}
+        for s in sides:
+            r = last[s]
+            st = stats(ts[s])
+            d[s] = {"ms": st, "nodes": int(r.Nodes), "events": r.BnbInfo["events"], "rounds": r.BnbInfo.get("rounds", int(r.Nodes)),
+                    "steals": r.BnbInfo.get("steals", 0), "largest_batch": r.BnbInfo.get("largest_batch", 1),
+                    "nodes_per_s": r.Nodes / (st["median"] / 1e3), "optimum": r.OptimalValue, "limit": r.Limit,
+                    "wins": bool(s != "onchip" and r.Limit is None and st["median"] < base["min"])}
+        rec[fs] = d
+    return rec
+
+
 def main():
     args = sys.argv[1:]
-    only, max_nodes, node_form, flag_sets = None, 0, "launches", "plain,long_step,cutoff,both"
-    for flag in ("--model", "--max-nodes", "--node-form", "--flag-sets"):
+    only, max_nodes, node_form, flag_sets, divers, widths = None, 0, None, None, None, None
+    for flag in ("--model", "--max-nodes", "--node-form", "--flag-sets", "--divers", "--compare-divers"):
         if flag in args:
             k = args.index(flag)
             if flag == "--model":
@@ -143,6 +195,10 @@ def main():
                 node_form = args[k + 1]
             elif flag == "--flag-sets":
                 flag_sets = args[k + 1]
+            elif flag == "--divers":
+                divers = int(args[k + 1])
+            elif flag == "--compare-divers":
+                widths = [int(w) for w in args[k + 1].split(",") if w]
             else:
                 max_nodes = int(args[k + 1])
             del args[k:k + 2]
@@ -153,6 +209,16 @@ def main():
     lib = L._lib.lib()
     L._lib.check(lib.lpx_init(0))
     out = {}
+    if flag_sets is None:
+        flag_sets = "plain,both" if widths else "plain,long_step,cutoff,both"
+    if widths:
+        for name, n, m in models():
+            if only is None or name == only:
+                out[name] = compare_divers(n, m, reps, max_nodes, [f for f in flag_sets.split(",") if f and f != "none"], widths)
+        print(json.dumps(out))
+        return
+    if node_form is None:
+        node_form = "launches" if divers is None else "onchip"
     if compare:
         for name, n, m in models():
             if only is None or name == only:
@@ -175,7 +241,7 @@ def main():
         def run_bounded():
             t0 = time.perf_counter()
             try:
-                r = L.LPSolver().SolveBnbBounded(bnd_p, 1.0, max_nodes=max_nodes, node_form=node_form)
+                r = L.LPSolver().SolveBnbBounded(bnd_p, 1.0, max_nodes=max_nodes, node_form=node_form, divers=divers)
             except L.SolverException as e:
                 if e.code != L._lib.ITER_LIMIT or not max_nodes:
                     raise
@@ -184,7 +250,8 @@ def main():
 
         if trace_only:
             ms, rb = run_bounded()
-            out[name] = {"node_form": node_form, "ms": ms, "nodes": int(rb.Nodes), "events": rb.BnbInfo["events"]}
+            out[name] = {"node_form": node_form, "divers": divers, "ms": ms, "nodes": int(rb.Nodes), "events": rb.BnbInfo["events"],
+                         "rounds": rb.BnbInfo.get("rounds")}
             continue
         base = device_used_mb()
         ta, tb, na, nb = [], [], [], []

@@ -1,7 +1,7 @@
 // lpx_cli -- Linux stand-in for the reference's WinForms host (Form1.cs), over the C ABI of liblpx.so only.
 //
 //   lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]
-//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F]] [--export FILE] INPUT.txt
+//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W]] [--export FILE] INPUT.txt
 //
 // Does what Form1 does around the solvers: reads the model text (Import, Form1.cs:284-296), parses it with the LPParser
 // grammar (lpx_parse_text, Models/LPParser.cs:9-79), runs the algorithm chosen by its dropdown name (btnSolve_Click,
@@ -78,6 +78,7 @@ int main(int argc, char** argv)
     bool repaired = false, iterations = false, ranging = false, cut_set = false, algo_set = false, binary = false, bnb_bounded = false;
     int search_flags = 0;       // --long-step / --cutoff beside --bnb-bounded
     int node_form = -1;         // --node-form beside --bnb-bounded: LPX_NODE_*; -1 = not given
+    int divers = 0;             // --divers W beside --bnb-bounded: the search by W divers (lpx_solve_bnb_bounded4); 0 = not given
     struct Bound { bool upper; int index; double value; std::string text; };
     std::vector<Bound> bounds;
     lpx_cut_opts co; lpx_default_cut_opts(&co);
@@ -94,6 +95,13 @@ int main(int argc, char** argv)
             const std::string v = argv[++i];
             node_form = v == "launches" ? LPX_NODE_LAUNCHES : v == "onchip" ? LPX_NODE_ONCHIP : v == "auto" ? LPX_NODE_AUTO : -2;
             if (node_form == -2) { std::fprintf(stderr, "lpx_cli: --node-form takes launches, onchip or auto, got '%s'\n", v.c_str()); return 64; }
+        }
+        else if (a == "--divers" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            char* end = nullptr;
+            const long w = std::strtol(v.c_str(), &end, 10);
+            if (end == v.c_str() || *end || w < 1 || w > 1024) { std::fprintf(stderr, "lpx_cli: --divers takes a count in [1, 1024], got '%s'\n", v.c_str()); return 64; }
+            divers = (int)w;
         }
         else if ((a == "--upper" || a == "--lower") && i + 1 < argc) {
             const std::string v = argv[++i];
@@ -131,7 +139,7 @@ int main(int argc, char** argv)
         else if (a == "--export" && i + 1 < argc) exportPath = argv[++i];
         else if (a == "--help" || a == "-h") {
             std::printf("usage: lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]\n"
-                        "               [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F]]\n"
+                        "               [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W]]\n"
                         "               [--export FILE] INPUT.txt\n"
                         "  NAME: Primal Simplex | Revised Primal Simplex | Dual Simplex | Branch and Bound |\n"
                         "        Revised Branch and Bound | Branch and Bound Knapsack | Cutting Plane | Revised Cutting Plane |\n"
@@ -147,6 +155,8 @@ int main(int argc, char** argv)
                         "             stops as soon as its objective has fallen to the incumbent (lpx_solve_bnb_bounded2)\n"
                         "  --node-form launches|onchip|auto: with --bnb-bounded, how a node is evaluated (lpx_solve_bnb_bounded3): by the\n"
                         "             launches of lpx_bounded_node2, in one launch with the tableau on chip, or on chip iff it fits\n"
+                        "  --divers W: with --bnb-bounded, the search by W handles diving at once, one on-chip node per diver and one kernel\n"
+                        "             launch per round (lpx_solve_bnb_bounded4); not with --node-form launches\n"
                         "  --set-rhs I=V, --set-cost J=V: after the solve, b_I = V / c_J = V (1-based, repeatable), applied in order,\n"
                         "             each re-optimised warm on the device from the previous basis; each re-solve's summary is printed\n");
             return 0;
@@ -161,6 +171,8 @@ int main(int argc, char** argv)
     if (bnb_bounded && !bounded) { std::fprintf(stderr, "lpx_cli: --bnb-bounded needs --binary or --upper bounds\n"); return 64; }
     if (search_flags && !bnb_bounded) { std::fprintf(stderr, "lpx_cli: --long-step / --cutoff need --bnb-bounded\n"); return 64; }
     if (node_form >= 0 && !bnb_bounded) { std::fprintf(stderr, "lpx_cli: --node-form needs --bnb-bounded\n"); return 64; }
+    if (divers && !bnb_bounded) { std::fprintf(stderr, "lpx_cli: --divers needs --bnb-bounded\n"); return 64; }
+    if (divers && node_form == LPX_NODE_LAUNCHES) { std::fprintf(stderr, "lpx_cli: --divers evaluates every node on chip: not with --node-form launches\n"); return 64; }
     if (bounded) {
         if (ranging) { std::fprintf(stderr, "lpx_cli: --upper / --lower / --binary do not combine with --ranging\n"); return 64; }
         if (cut_set) { std::fprintf(stderr, "lpx_cli: --upper / --lower / --binary do not combine with --cuts-per-round / --cut-rounds\n"); return 64; }
@@ -190,7 +202,8 @@ int main(int argc, char** argv)
         if (bd.index >= p.n) { std::fprintf(stderr, "lpx_cli: %s: index out of range\n", bd.text.c_str()); lpx_parsed_free(&p); return 64; }
         (bd.upper ? up : lo)[bd.index] = bd.value;
     }
-    const int rc = bnb_bounded && node_form >= 0 ? lpx_solve_bnb_bounded3(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, node_form, &r, nullptr)
+    const int rc = bnb_bounded && divers ? lpx_solve_bnb_bounded4(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, &r, nullptr, nullptr)
+                 : bnb_bounded && node_form >= 0 ? lpx_solve_bnb_bounded3(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, node_form, &r, nullptr)
                  : bnb_bounded && search_flags ? lpx_solve_bnb_bounded2(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, &r, nullptr)
                  : bnb_bounded ? lpx_solve_bnb_bounded(&prob, lo.data(), up.data(), nullptr, &o, 0, &r, nullptr)
                  : bounded ? lpx_solve_bounded(&prob, lo.data(), up.data(), &o, &r, nullptr) : ranging ? lpx_solve_ranging(&prob, algorithm.c_str(), &o, &r, &rg)
