@@ -13,6 +13,7 @@ import pytest
 import _bnb_bounded_ref as N
 import _bounded_dual_ref as D
 import _bounded_ref as B
+from _node_helpers import exact as _exact, pick_tableau as _pick_tableau
 
 pytestmark = pytest.mark.gpu
 
@@ -41,24 +42,6 @@ def _same_state(dt, T, basis, ub, lo, flip, what=""):
 
 
 # ---- branch pick -------------------------------------------------------------------------------------------------------
-FRACTIONS = np.array([0.0, 0.0, 0.0, 0.25, 0.75, 0.5, 0.125, 0.875, 1e-6, 1.0 - 1e-6, 2e-6, 0.4999, 0.3, 0.7])
-
-
-def _pick_tableau(nint, m, seed, extra=3):
-    """A synthetic solved tableau: permutation basis, chosen RHS values, zero columns otherwise (bound edits and dual-feasibility
-    flips then move the RHS of the objective row only).  Returns (T, basis, ub)."""
-    g = np.random.default_rng(seed)
-    Cm = nint + extra
-    m = min(m, Cm)
-    T = np.zeros((m + 1, Cm + 1))
-    basis = g.permutation(Cm)[:m].astype(np.int32)
-    T[np.arange(m), basis] = 1.0
-    T[:m, Cm] = g.integers(0, 3, size=m) + g.choice(FRACTIONS, size=m)
-    T[m, Cm] = 17.25
-    ub = g.choice(np.array([1.0, 2.0, 3.0, INF]), size=Cm)
-    return T, basis, ub
-
-
 def _pick_both(lpx, T, basis, ub, nint, flips=(), lo_cols=(), is_int=None, tol=1e-6):
     """The pick on the device and in the restatement; `flips`: nonbasic or basic columns with a finite bound flipped through
     lpx_tableau_dualize; lo_cols: columns given the lower bound 1 through lpx_tableau_change_bounds."""
@@ -104,20 +87,6 @@ def test_pick_at_every_edge_of_the_kernel(gpu, nint):
         again = _pick_both(gpu, T, basis, ub, nint, flips=flips, is_int=mask)
         assert again["var"] != got["var"]
     _pick_both(gpu, T, basis, ub, nint, flips=flips, is_int=np.zeros(nint, dtype=np.uint8))
-
-
-def _exact(nint, entries, m_extra=0):
-    """A tableau whose only non-integral values are `entries`: {column: value}."""
-    cols = sorted(entries)
-    m = len(cols) + m_extra
-    Cm = nint + 1 + m_extra
-    T = np.zeros((m + 1, Cm + 1))
-    basis = np.array(cols + list(range(nint + 1, nint + 1 + m_extra)), dtype=np.int32)
-    T[np.arange(m), basis] = 1.0
-    T[:len(cols), Cm] = [entries[j] for j in cols]
-    T[len(cols):m, Cm] = 2.0
-    T[m, Cm] = -3.5
-    return T, basis, np.full(Cm, INF)
 
 
 @pytest.mark.parametrize("entries,winner", [

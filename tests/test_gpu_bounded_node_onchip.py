@@ -15,6 +15,9 @@ import _bnb_bounded_ref as N
 import _bounded_dual_ref as D
 import _bounded_long_ref as L
 import _bounded_ref as B
+from _node_helpers import (bits as _bits, covering_with_fixed as _covering_with_fixed, fresh as _fresh_handle, node3 as _node3,
+                           same_record as _same_record, same_state as _same_state, slack_handle as _slack_handle, state as _state,
+                           u64 as _u64)
 
 pytestmark = pytest.mark.gpu
 
@@ -24,76 +27,12 @@ SKIP, LONG, CUT = L.SKIP_FIXED, L.LONG_STEP, L.CUTOFF_FLAG
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(ROOT, "linear_programming_solver_lpr381_amd", "lpx_cli")
 EXAMPLE = os.path.join(ROOT, "integration", "Input", "example_bounded.txt")
-REC_KEYS = ("status", "events", "kind0", "kind1", "flips", "unrepairable", "var", "candidates")
-
-
-def _u64(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def _bits(x):
-    return np.float64(x).view(np.uint64)
-
-
-def _state(dt):
-    Tg, bg = dt.download()
-    lo, ub, flip = dt.bound_state()
-    return (_u64(Tg).tolist(), bg.tolist(), flip.tolist(), _u64(ub).tolist(), _u64(lo).tolist())
-
-
-def _same_state(dt, h, what=""):
-    Tg, bg = dt.download()
-    glo, gub, gflip = dt.bound_state()
-    assert np.array_equal(_u64(Tg), _u64(h.T)), "tableau bits differ from the restatement " + what
-    assert bg.tolist() == h.basis.tolist(), what
-    assert gflip.tolist() == h.flip.tolist(), what
-    assert np.array_equal(_u64(gub), _u64(h.ub)) and np.array_equal(_u64(glo), _u64(h.lo)), what
-
-
-def _same_record(got, want):
-    assert {k: got[k] for k in REC_KEYS} == {k: want[k] for k in REC_KEYS}, (got, want)
-    assert _bits(got["x_var"]) == _bits(want["x_var"]) and _bits(got["z"]) == _bits(want["z"]), (got, want)
-
-
-def _node3(dt, h, cols, lower, upper, n, flags=0, cutoff=None, form="onchip", other=None, is_int=None, **kw):
-    """One node on the device in `form` and in the restatement: everything bit for bit.  other: a second device handle in the
-    same state, which runs the node on the launches form and must end in the same state, counts included."""
-    cols = np.atleast_1d(np.asarray(cols, dtype=np.int32))
-    lower = np.broadcast_to(np.asarray(lower, dtype=np.float64), cols.shape)
-    upper = np.broadcast_to(np.asarray(upper, dtype=np.float64), cols.shape)
-    ref_kw = {k: v for k, v in kw.items() if k in ("eps", "max_iter")}
-    want = h.node2(cols, lower, upper, n, is_int=is_int, flags=SKIP | flags | (0 if cutoff is None else CUT),
-                   cutoff=-INF if cutoff is None else cutoff, **ref_kw)
-    got = dt.bounded_node(cols, lower, upper, n, is_int=is_int, long_step=bool(flags & LONG), cutoff=cutoff, form=form, **kw)
-    _same_record(got, want)
-    assert dt.trace().tolist() == h.trace.tolist()
-    _same_state(dt, h, "after the node")
-    passes = want["events"] - want["kind0"] - want["kind1"]
-    assert dt.bounded_counts() == (want["kind0"], want["kind1"], passes)
-    if other is not None:
-        ref = other.bounded_node(cols, lower, upper, n, is_int=is_int, long_step=bool(flags & LONG), cutoff=cutoff, form="launches", **kw)
-        _same_record(got, ref)
-        assert dt.trace().tolist() == other.trace().tolist() and _state(dt) == _state(other)
-        assert dt.bounded_counts() == other.bounded_counts()
-    return got, want
-
-
-def _covering_with_fixed(m, n, seed):
-    T, basis, ub, _ = D.covering(m, n, seed)
-    g = np.random.default_rng(seed)
-    ub[:n][g.random(n) < 0.2] = 0.0                     # fixed columns: they do not enter
-    return T, basis, ub
 
 
 def _fresh(lpx, T, basis, ub):
-    dt = lpx.DeviceTableau.from_host(T, basis)
-    dt.set_bounds(ub)
+    dt = _fresh_handle(lpx, T, basis, ub)
     dt.snapshot()
     return dt
-
-
-def _slack_handle(T, basis, ub):
-    return L.Handle(T, basis, ub, np.zeros(len(ub), dtype=np.uint8))
 
 
 def _solved_handle(lpx, n, m, seed):

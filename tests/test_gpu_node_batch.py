@@ -16,6 +16,9 @@ import _bnb_divers_ref as V
 import _bounded_dual_ref as D
 import _bounded_long_ref as L
 import _bounded_ref as B
+from _node_helpers import (Pool as _Pool, bits as _bits, covering_with_fixed as _covering_with_fixed, fresh as _fresh, node as _node,
+                           reads as _reads, ref_node as _ref_node, same_record as _same_record, same_state as _same_handle,
+                           slack_handle as _slack_handle, state as _state, u64 as _u64)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,58 +28,11 @@ SKIP, LONG, CUT = L.SKIP_FIXED, L.LONG_STEP, L.CUTOFF_FLAG
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(ROOT, "linear_programming_solver_lpr381_amd", "lpx_cli")
 EXAMPLE = os.path.join(ROOT, "integration", "Input", "example_bounded.txt")
-REC_KEYS = ("status", "events", "kind0", "kind1", "flips", "unrepairable", "var", "candidates")
-
-
-def _u64(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def _bits(x):
-    return np.float64(x).view(np.uint64)
-
-
-def _state(dt):
-    Tg, bg = dt.download()
-    lo, ub, flip = dt.bound_state()
-    return (_u64(Tg).tolist(), bg.tolist(), flip.tolist(), _u64(ub).tolist(), _u64(lo).tolist())
-
-
-def _reads(dt, n):
-    """Everything the contract lets a caller read from a handle after a node."""
-    x, z, up = dt.bounded_solution(n)
-    return _state(dt) + (dt.trace().tolist(), dt.bounded_counts(), _u64(x).tolist(), int(_bits(z)), np.asarray(up).tolist())
-
-
-def _same_record(got, want):
-    assert {k: got[k] for k in REC_KEYS} == {k: want[k] for k in REC_KEYS}, (got, want)
-    assert _bits(got["x_var"]) == _bits(want["x_var"]) and _bits(got["z"]) == _bits(want["z"]), (got, want)
 
 
 def _same_state(dt, h, what=""):
-    Tg, bg = dt.download()
-    glo, gub, gflip = dt.bound_state()
-    assert np.array_equal(_u64(Tg), _u64(h.T)), "tableau bits differ from the restatement " + what
-    assert bg.tolist() == h.basis.tolist() and gflip.tolist() == h.flip.tolist(), what
-    assert np.array_equal(_u64(gub), _u64(h.ub)) and np.array_equal(_u64(glo), _u64(h.lo)), what
+    _same_handle(dt, h, what)
     assert dt.trace().tolist() == h.trace.tolist(), what
-
-
-def _covering_with_fixed(m, n, seed):
-    T, basis, ub, _ = D.covering(m, n, seed)
-    g = np.random.default_rng(seed)
-    ub[:n][g.random(n) < 0.2] = 0.0
-    return T, basis, ub
-
-
-def _fresh(lpx, T, basis, ub):
-    dt = lpx.DeviceTableau.from_host(T, basis)
-    dt.set_bounds(ub)
-    return dt
-
-
-def _slack_handle(T, basis, ub):
-    return L.Handle(T, basis, ub, np.zeros(len(ub), dtype=np.uint8))
 
 
 def _solved(lpx, n, m, seed):
@@ -85,32 +41,6 @@ def _solved(lpx, n, m, seed):
     status, _ = dt.bounded_run()
     assert status == B.OPTIMAL and np.array_equal(_u64(dt.download()[0]), _u64(Ts))
     return dt, (Ts, bs, ub, flip)
-
-
-def _node(cols=(), lower=(), upper=()):
-    return (np.asarray(cols, dtype=np.int32), np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64))
-
-
-def _ref_node(h, node, n, flags=0, cutoff=None, **kw):
-    return h.node2(*node, n, flags=SKIP | flags | (0 if cutoff is None else CUT), cutoff=-INF if cutoff is None else cutoff, **kw)
-
-
-class _Pool:
-    """Handles that are closed together."""
-
-    def __init__(self):
-        self.h = []
-
-    def add(self, dt):
-        self.h.append(dt)
-        return dt
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for dt in self.h:
-            dt.close()
 
 
 # ---- 1. clone -------------------------------------------------------------------------------------------------------------
