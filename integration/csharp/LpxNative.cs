@@ -323,6 +323,33 @@ namespace Linear_Programming_Solver.Native
         public static extern int lpx_solve_bounded_dual(ref LpxProblem p, double* lower, double* upper, int flags, ref LpxSolveOpts o,
                                                         out LpxResult result, out LpxBoundedInfo info);
 
+        // ---- branch-and-bound node and child assembly on device handles, the parent store and the batched read-back, include/lpx.h ----
+        // any of R / C / ld may be null
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int lpx_tableau_shape(IntPtr t, int* R, int* C, int* ld);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int lpx_tableau_set_shape(IntPtr t, int R, int C);
+        // the root tableau (its snapshot if one was taken) plus ncuts unit rows: coef[k] at var[k], the signed zero zero[k] elsewhere, rhs[k]
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_tableau_build_node(IntPtr node, IntPtr root, int ncuts, int* var, double* coef, double* zero, double* rhs);
+        // cutOff: [count + 1], cutOff[0] = 0; node i gets the rows [cutOff[i], cutOff[i + 1]) of the flattened arrays
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_tableau_build_nodes(IntPtr* nodes, IntPtr root, int count, int* cutOff, int* var, double* coef, double* zero, double* rhs);
+        // the parent's final tableau plus the row of x_var <= bound (isGe = 0) or x_var >= bound (isGe = 1); x_var is basic in rowOfVar
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_tableau_build_child(IntPtr child, IntPtr parent, int var, int rowOfVar, int isGe, double bound);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int lpx_store_create(int Rcap, int Ccap, out IntPtr store);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern void lpx_store_destroy(IntPtr store);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int lpx_store_save(IntPtr store, IntPtr t, out int slot);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int lpx_store_release(IntPtr store, int slot);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int lpx_store_save_multi(IntPtr* stores, IntPtr* ts, int count, int* slots);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_tableau_build_child_from_store(IntPtr child, IntPtr store, int slot, int var, int rowOfVar, int isGe, double bound);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_tableau_build_children_from_store(IntPtr* children, IntPtr* stores, int* slots, int count,
+                                                                       int* var, int* rowOfVar, int* isGe, double* bound);
+        // x: count x nvars, z: [count], basisOut: count x basisStride or null
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_multi_solution(IntPtr* ts, int count, int nvars, double* x, double* z, int* basisOut, int basisStride);
+
         public static string LastError()
         {
             var b = new byte[1024];

@@ -144,9 +144,9 @@ int lpx_tableau_build_node(lpx_tableau* node, const lpx_tableau* root, int ncuts
 {
     if (!node || !root || ncuts < 0 || (ncuts > 0 && (!var || !coef || !zero || !rhs))) { set_error("lpx_tableau_build_node: bad argument"); return LPX_EINVAL; }
     if (root->R + ncuts > node->Rcap || root->C + ncuts > node->Ccap) { set_error("lpx_tableau_build_node: root shape + ncuts exceeds the node handle's capacity"); return LPX_EINVAL; }
-    { int rc = lpx_tableau_set_shape(node, root->R + ncuts, root->C + ncuts); if (rc) return rc; }
     const int n = root->C - root->R;
     for (int k = 0; k < ncuts; ++k) if (var[k] < 0 || var[k] >= n) { set_error("lpx_tableau_build_node: branching variable out of range"); return LPX_EINVAL; }
+    { int rc = lpx_tableau_set_shape(node, root->R + ncuts, root->C + ncuts); if (rc) return rc; }   // a refused call leaves the node as it was
     const int need = ncuts > 0 ? ncuts : 1;
     if (need > node->cutcap) {
         hipFree(node->cutbuf); if (node->cutbuf_h) hipHostFree(node->cutbuf_h);
