@@ -1031,6 +1031,73 @@ int  lpx_solve_bnb_bounded4(const lpx_problem* p, const double* lower /* [n] or 
                             lpx_bnb_divers_info* dinfo /* or NULL */);
 void lpx_bnb_divers_info_free(lpx_bnb_divers_info* dinfo);
 
+/* ---- the plunge: up to D nodes per diver and launch, the tableau staying in LDS (not in the reference;
+ * csrc/lpx_bounded_plunge.hip, csrc/lpx_node_batch.cpp, csrc/host/bnb_bounded.cpp) --
+ * lpx_node_batch_plunge(b, B, slot, K, cols, lower, upper, o, flags, cutoff, prune, depth, D, nint, is_int, tol, out, steps, rc):
+ * lpx_node_batch_run whose entry i is a CHAIN of up to depth[i] nodes (1 <= depth[i] <= D <= 64) evaluated by one workgroup in ONE
+ * launch; the tile is loaded into LDS once and stored once per launch.  out is [B * D], entry-major.
+ *   The chain of entry i.  Node 0 is the entry's K[i] triples.  After node s its record is written, and the chain goes on iff
+ *   status == LPX_OPTIMAL, pick.var >= 0, !(pick.z <= prune[i]) and s + 1 < depth[i].  Node s + 1 is then the ceil child of node s:
+ *   the one triple (var, ceil(x_var), lo[var] + ub[var]) in the handle's own terms (lpx_tableau_bound_state).  The sum is the
+ *   column's current upper bound exactly when the bounds of the integer columns are finite and integral, which is why a
+ *   depth[i] > 1 is refused (LPX_EINVAL) unless every column j < nint that is_int lets in is KNOWN to the handle to have such
+ *   bounds: lpx_tableau_set_bounds and every accepted bound edit record it on the host (a clone, a snapshot and a restore carry
+ *   it), and the entry's own triples count.  prune[i] is always read (-inf: nothing is pruned); cutoff[i] only with LPX_BDUAL_CUTOFF.
+ *   Contract: for every i, out[i*D .. i*D + steps[i]), rc[i] and everything readable from handles[slot[i]] afterwards -- tableau,
+ *   basis, ub, lo, flip, trace, lpx_bounded_counts, the solution, the state's host mirror, a following node of any form -- are
+ *   bit-equal to steps[i] calls of lpx_bounded_node3(..., LPX_NODE_ONCHIP, ...) one after another on a handle in the same state:
+ *   the first with the entry's triples, each later one with the one ceil triple above, the same cutoff[i] and flags, stopped by
+ *   the rule above.  The trace is that of the last node.  rc[i] is the last node's status.  D = 1 gives lpx_node_batch_run.
+ *   Errors: those of lpx_node_batch_run under the new name, plus a NULL depth, steps or prune, D outside [1, 64], a depth[i]
+ *   outside [1, D], a NaN prune[i] and the integrality rule above; all LPX_EINVAL before any device check, an entry's message
+ *   starting "lpx_node_batch_plunge: entry i:".  A refusal the kernel finds at node 0 is lpx_node_batch_run's: rc[i] = LPX_EINVAL,
+ *   steps[i] = 0, out[i*D].unrepairable set, the handle as it was.  One found at node s + 1 (the tile is dirty by then: ub / lo of
+ *   the one column are put back and the tile is stored as node s left it) gives rc[i] = LPX_EINVAL, steps[i] = s + 1 completed
+ *   nodes, out[i*D + steps[i]].unrepairable set and the handle as after node s; the message names "node s + 1".
+ *
+ * lpx_solve_bnb_bounded5(p, lower, upper, is_int, o, max_nodes, search_flags, divers, plunge, out, info, dinfo, pinfo):
+ * lpx_solve_bnb_bounded4 whose divers plunge, 1 <= plunge = D <= 64 (else LPX_EINVAL before any device check).  Everything around
+ * the search is lpx_solve_bnb_bounded4's.  One round, in this order (the order is part of the contract):
+ *   1. Limit and 2. Steal: as lpx_solve_bnb_bounded4.
+ *   3. Pop: for d ascending, each diver with a non-empty stack gets the cap depth_d = D, or with max_nodes > 0
+ *      min(D, max_nodes - nodes - the caps handed out to lower divers in this round); the first diver whose cap would be 0 ends the
+ *      popping.  The node's columns are those whose bounds differ from the diver's current bounds, ascending.
+ *   4. Evaluate: ONE lpx_node_batch_plunge, flags = LPX_BDUAL_SKIP_FIXED | search_flags, every entry with prune = best + 1e-6 as
+ *      best stood at the start of the round, and with cutoff = that value under LPX_BDUAL_CUTOFF.  launched grows by the records
+ *      the kernel wrote, longest_chain is the longest chain seen.
+ *   5. Decide: divers ascending, each diver's records in chain order, every record exactly as lpx_solve_bnb_bounded4 treats a
+ *      node (nodes++, the counters, the log record with round[], diver[] and step[], the record's index in its chain; record s
+ *      has depth = the popped node's depth + s and K = 1 for s > 0):
+ *        LPX_ITER_LIMIT ends the solve at that record;  infeasible ends the chain;
+ *        LPX_CUTOFF or z <= best + 1e-6, best as updated by lower-index divers of this round: pruned by bound.  The kernel may
+ *          have gone on past such a record, against the older best: the later records of the chain are DROPPED -- not counted,
+ *          not logged, dropped grows by their number;
+ *        an incumbent is always the last record of its chain, so lpx_tableau_bounded_solution on the diver's handle is its x;
+ *        a branch followed by a further record pushes only the floor child: the ceil child IS that next record;
+ *        a branch that is the last record of its chain pushes the floor child, then the ceil child.
+ *      The diver's current bounds afterwards are those of the last node the kernel evaluated, dropped or not.
+ *   6. Repeat while any stack is non-empty.
+ * plunge = 1 gives lpx_solve_bnb_bounded4's log, round[] and diver[] bit for bit.  divers = 1 with any plunge gives the log of
+ * lpx_solve_bnb_bounded3(..., LPX_NODE_ONCHIP, ...) bit for bit with dropped = 0: within a chain no incumbent appears before the
+ * last record, so the sequential best is the round's.  pinfo (or NULL): launched, dropped, longest_chain and per log record its
+ * step ([info->n_log]); free with lpx_bnb_plunge_info_free. */
+typedef struct lpx_bnb_plunge_info {
+    int64_t launched, dropped, longest_chain;
+    int32_t* step;           /* [n_log of the lpx_bnb_bounded_info] */
+} lpx_bnb_plunge_info;
+int  lpx_node_batch_plunge(lpx_node_batch* b, int B, const int32_t* slot /* [B] */, const int32_t* K /* [B] */,
+                           const int32_t* cols, const double* lower, const double* upper /* concatenated, sum of K */,
+                           const lpx_run_opts* o, int flags, const double* cutoff /* [B]; read only with LPX_BDUAL_CUTOFF */,
+                           const double* prune /* [B] */, const int32_t* depth /* [B] */, int D,
+                           int nint, const uint8_t* is_int /* [nint] or NULL = all */, double tol,
+                           lpx_node_record* out /* [B*D], entry-major */, int32_t* steps /* [B] */, int32_t* rc /* [B] */);
+int  lpx_solve_bnb_bounded5(const lpx_problem* p, const double* lower /* [n] or NULL = 0 */, const double* upper /* [n] */,
+                            const uint8_t* is_int /* [n] or NULL = all */, const lpx_solve_opts* o, int64_t max_nodes /* 0 = none */,
+                            int search_flags, int divers /* W, 1..1024 */, int plunge /* D, 1..64 */, lpx_result* out,
+                            lpx_bnb_bounded_info* info /* or NULL */, lpx_bnb_divers_info* dinfo /* or NULL */,
+                            lpx_bnb_plunge_info* pinfo /* or NULL */);
+void lpx_bnb_plunge_info_free(lpx_bnb_plunge_info* pinfo);
+
 #ifdef __cplusplus
 }
 #endif

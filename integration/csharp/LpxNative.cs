@@ -123,6 +123,13 @@ namespace Linear_Programming_Solver.Native
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct LpxBnbPlungeInfo        // lpx_bnb_plunge_info  (free with lpx_bnb_plunge_info_free)
+    {
+        public long launched, dropped, longest_chain;
+        public int* step;                        // [n_log of the LpxBnbBoundedInfo]
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public unsafe struct LpxBoundedInfo          // lpx_bounded_info  (lpx_solve_bounded; free with lpx_bounded_info_free)
     {
         public int ncols, n;
@@ -319,6 +326,16 @@ namespace Linear_Programming_Solver.Native
                                                         long max_nodes, int search_flags, int divers, out LpxResult result,
                                                         out LpxBnbBoundedInfo info, out LpxBnbDiversInfo dinfo);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern void lpx_bnb_divers_info_free(ref LpxBnbDiversInfo dinfo);
+        // the plunge: records is [B * D], entry-major; steps and rc are [B]
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_node_batch_plunge(IntPtr batch, int B, int* slot, int* K, int* cols, double* lower, double* upper, IntPtr opts,
+                                                       int flags, double* cutoff, double* prune, int* depth, int D, int nint, byte* is_int,
+                                                       double tol, LpxNodeRecord* records, int* steps, int* rc);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_bnb_bounded5(ref LpxProblem p, double* lower, double* upper, byte* is_int, ref LpxSolveOpts o,
+                                                        long max_nodes, int search_flags, int divers, int plunge, out LpxResult result,
+                                                        out LpxBnbBoundedInfo info, out LpxBnbDiversInfo dinfo, out LpxBnbPlungeInfo pinfo);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern void lpx_bnb_plunge_info_free(ref LpxBnbPlungeInfo pinfo);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_solve_bounded_dual(ref LpxProblem p, double* lower, double* upper, int flags, ref LpxSolveOpts o,
                                                         out LpxResult result, out LpxBoundedInfo info);

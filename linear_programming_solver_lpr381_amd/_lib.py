@@ -138,6 +138,12 @@ class BnbDiversInfo(C.Structure):
     _fields_ = [("rounds", C.c_int64), ("steals", C.c_int64), ("largest_batch", C.c_int64), ("round", ip), ("diver", ip)]
 
 
+class BnbPlungeInfo(C.Structure):
+    """lpx_bnb_plunge_info (include/lpx.h): the records launched and dropped, the longest chain and the per-node step of
+    lpx_solve_bnb_bounded5 (freed by lpx_bnb_plunge_info_free)."""
+    _fields_ = [("launched", C.c_int64), ("dropped", C.c_int64), ("longest_chain", C.c_int64), ("step", ip)]
+
+
 class Parsed(C.Structure):
     _fields_ = [("sense", C.c_int), ("n", C.c_int), ("m", C.c_int), ("c", dp), ("A", dp), ("rel", ip),
                 ("b", dp), ("ragged", C.c_int)]
@@ -329,6 +335,13 @@ def lib() -> C.CDLL:
                                          C.POINTER(Result), C.POINTER(BnbBoundedInfo), C.POINTER(BnbDiversInfo)]
     L.lpx_bnb_divers_info_free.argtypes = [C.POINTER(BnbDiversInfo)]
     L.lpx_bnb_divers_info_free.restype = None
+    L.lpx_node_batch_plunge.argtypes = [vp, C.c_int, ip, ip, ip, dp, dp, C.POINTER(RunOpts), C.c_int, dp, dp, ip, C.c_int, C.c_int, u8p,
+                                        C.c_double, C.POINTER(NodeRecord), ip, ip]
+    L.lpx_solve_bnb_bounded5.argtypes = [C.POINTER(Problem), dp, dp, u8p, C.POINTER(SolveOpts), C.c_int64, C.c_int, C.c_int, C.c_int,
+                                         C.POINTER(Result), C.POINTER(BnbBoundedInfo), C.POINTER(BnbDiversInfo),
+                                         C.POINTER(BnbPlungeInfo)]
+    L.lpx_bnb_plunge_info_free.argtypes = [C.POINTER(BnbPlungeInfo)]
+    L.lpx_bnb_plunge_info_free.restype = None
     L.lpx_solve_bounded_dual.argtypes = [C.POINTER(Problem), dp, dp, C.c_int, C.POINTER(SolveOpts), C.POINTER(Result),
                                          C.POINTER(BoundedInfo)]
     L.lpx_parse_text.argtypes = [C.c_char_p, C.POINTER(Parsed)]

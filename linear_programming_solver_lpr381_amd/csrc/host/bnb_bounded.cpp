@@ -334,4 +334,210 @@ SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double
     return res;
 }
 
+// The search by W divers that plunge (lpx_solve_bnb_bounded5, include/lpx.h): SolveBnbDivers whose round is ONE
+// lpx_node_batch_plunge -- every diver's workgroup goes on from a node that branches into its ceil child, up to `plunge` nodes,
+// with the tableau staying on chip -- and whose decide step walks every diver's chain in order.  The validation and the result
+// tail are copies of SolveBnbDivers' (as that function's are of SolveBnbBounded's), so that the two existing drivers stay as they
+// are.  The order of the steps is part of the contract: the log is a function of the model, the options, the flags, W and D alone.
+SimplexResult SolveBnbPlunge(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
+                             const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
+                             int search_flags, int divers, int plunge, BnbDiversInfo& dinfo, BnbPlungeInfo& pinfo)
+{
+    const int n = original.NumVars();
+    if ((!lower.empty() && (int)lower.size() != n) || (!upper.empty() && (int)upper.size() != n))
+        throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: lower / upper need one entry per variable");
+    if (!is_int.empty() && (int)is_int.size() != n)
+        throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: the integer mask needs one entry per variable");
+    for (int j = 0; j < n; ++j)
+        CheckVarBounds("x" + std::to_string(j + 1), lower.empty() ? 0.0 : lower[j], upper.empty() ? 1.0 / 0.0 : upper[j]);
+    for (int j = 0; j < n; ++j) {
+        if (!is_int.empty() && !is_int[j]) continue;
+        const double l = lower.empty() ? 0.0 : lower[j], u = upper.empty() ? 1.0 / 0.0 : upper[j];
+        if (!std::isfinite(u) || std::floor(l) != l || std::floor(u) != u)
+            throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: integer variable x" + std::to_string(j + 1) +
+                                           " needs finite, integral lower and upper bounds");
+    }
+    if (max_nodes < 0) throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: max_nodes is negative");
+    if (search_flags & ~(LPX_BDUAL_LONG_STEP | LPX_BDUAL_CUTOFF))
+        throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: search_flags holds a bit other than LPX_BDUAL_LONG_STEP and LPX_BDUAL_CUTOFF");
+    if (divers < 1 || divers > 1024) throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: divers is outside [1, 1024]");
+    if (plunge < 1 || plunge > 64) throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: plunge is outside [1, 64]");
+
+    EngineOptions ropt = opt; ropt.quiet = true;
+    BoundedSession ses;
+    BoundedInfo binfo;
+    SimplexResult res = SolveBounded(original, lower, upper, ropt, nullptr, &binfo, &ses);
+    info = BnbBoundedInfo();
+    dinfo = BnbDiversInfo();
+    pinfo = BnbPlungeInfo();
+    info.constant = ses.constant;
+    res.Nodes = 0; res.LpSolves = 1;
+    res.Aux = {0.0, 0.0, 0.0, 0.0};
+    if (res.Status != LPX_OPTIMAL) return res;
+    {
+        int R = 0, C = 0;
+        lpx_tableau_shape(ses.h, &R, &C, nullptr);
+        if (!lpx_bounded_node_fits(R, C))
+            throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: the root tableau (" + std::to_string(R) + " x " + std::to_string(C) +
+                                           ") does not fit the on-chip form of the node (lpx_bounded_node_fits)");
+    }
+
+    const int W = divers, D = plunge;
+    struct Pool {
+        std::vector<lpx_tableau*> h; lpx_node_batch* batch = nullptr;
+        ~Pool() { lpx_node_batch_destroy(batch); for (size_t d = 1; d < h.size(); ++d) lpx_tableau_destroy(h[d]); }
+    } pool;
+    pool.h.push_back(ses.h);
+    for (int d = 1; d < W; ++d) {
+        lpx_tableau* c = nullptr;
+        const int rc = lpx_tableau_clone(ses.h, &c);
+        if (rc) throw_lib(rc);
+        pool.h.push_back(c);
+    }
+    { const int rc = lpx_node_batch_create(W, pool.h.data(), &pool.batch); if (rc) throw_lib(rc); }
+
+    struct Diver { std::vector<double> cur_lo, cur_ub, nb_lo, nb_ub; std::vector<Node> stack; Node node; };
+    const std::vector<double> root_lo((size_t)n, 0.0), root_ub(binfo.ub.begin(), binfo.ub.begin() + n);
+    std::vector<Diver> dv((size_t)W);
+    for (Diver& d : dv) { d.cur_lo = root_lo; d.cur_ub = root_ub; }
+    dv[0].stack.push_back(Node{0, {}});
+    lpx_run_opts o; lpx_default_opts(&o, 1);
+    o.max_iter = opt.max_iter;
+    const uint8_t* mask = is_int.empty() ? nullptr : is_int.data();
+
+    double best = -1.0 / 0.0;
+    std::vector<double> best_x;
+    std::vector<int32_t> slot, Ks, caps, cols, rcs((size_t)W), steps((size_t)W); std::vector<double> clo, cub, cutoffs, prunes;
+    std::vector<lpx_node_record> recs((size_t)W * (size_t)D);
+    auto any_open = [&] { for (const Diver& d : dv) if (!d.stack.empty()) return true; return false; };
+    bool stop = false;
+    while (!stop && any_open()) {
+        // 1. limit
+        if (max_nodes > 0 && info.nodes >= max_nodes) {
+            info.limit_rc = LPX_ITER_LIMIT;
+            info.limit_msg = "Bounded Branch and Bound: node limit of " + std::to_string(max_nodes) + " reached";
+            break;
+        }
+        // 2. steal: the oldest entry of the longest stack, lengths as they stand now
+        for (int d = 0; d < W; ++d) {
+            if (!dv[d].stack.empty()) continue;
+            int v = 0;
+            for (int k = 1; k < W; ++k) if (dv[k].stack.size() > dv[v].stack.size()) v = k;
+            if (dv[v].stack.size() < 2) continue;
+            dv[d].stack.push_back(std::move(dv[v].stack.front()));
+            dv[v].stack.erase(dv[v].stack.begin());
+            dinfo.steals++;
+        }
+        // 3. pop, each entry with its cap on nodes: plunge, or what max_nodes leaves after the caps handed out before it
+        slot.clear(); Ks.clear(); caps.clear(); cols.clear(); clo.clear(); cub.clear(); cutoffs.clear(); prunes.clear();
+        int64_t handed = 0;
+        for (int d = 0; d < W; ++d) {
+            Diver& Dv = dv[d];
+            if (Dv.stack.empty()) continue;
+            int cap = D;
+            if (max_nodes > 0) {
+                const int64_t left = max_nodes - info.nodes - handed;
+                if (left <= 0) break;
+                if (left < cap) cap = (int)left;
+            }
+            handed += cap;
+            Dv.node = std::move(Dv.stack.back());
+            Dv.stack.pop_back();
+            Dv.nb_lo = root_lo; Dv.nb_ub = root_ub;
+            for (const Override& v : Dv.node.path) { Dv.nb_lo[v.var] = v.lo; Dv.nb_ub[v.var] = v.ub; }
+            int K = 0;
+            for (int j = 0; j < n; ++j)
+                if (Dv.nb_lo[j] != Dv.cur_lo[j] || Dv.nb_ub[j] != Dv.cur_ub[j]) { cols.push_back(j); clo.push_back(Dv.nb_lo[j]); cub.push_back(Dv.nb_ub[j]); ++K; }
+            slot.push_back(d); Ks.push_back(K); caps.push_back(cap);
+            cutoffs.push_back((search_flags & LPX_BDUAL_CUTOFF) ? best + EPS : 0.0);
+            prunes.push_back(best + EPS);
+        }
+        // 4. evaluate
+        const int B = (int)slot.size();
+        const int rc = lpx_node_batch_plunge(pool.batch, B, slot.data(), Ks.data(), cols.data(), clo.data(), cub.data(), &o,
+                                             LPX_BDUAL_SKIP_FIXED | search_flags, cutoffs.data(), prunes.data(), caps.data(), D,
+                                             n, mask, EPS, recs.data(), steps.data(), rcs.data());
+        if (rc < 0) throw_lib(rc);
+        for (int i = 0; i < B; ++i) if (rcs[i] < 0) throw_lib(rcs[i]);
+        const int32_t round = (int32_t)dinfo.rounds++;
+        if (B > dinfo.largest_batch) dinfo.largest_batch = B;
+        for (int i = 0; i < B; ++i) { pinfo.launched += steps[i]; if (steps[i] > pinfo.longest_chain) pinfo.longest_chain = steps[i]; }
+        // 5. decide: divers ascending, each diver's records in chain order
+        for (int i = 0; i < B && !stop; ++i) {
+            Diver& Dv = dv[slot[i]];
+            Node node = Dv.node;                                        // the node of record s: depth and path grow along the chain
+            const int ns = steps[i];
+            for (int s = 0; s < ns; ++s) {
+                const lpx_node_record& rec = recs[(size_t)i * D + s];
+                const int K = s == 0 ? Ks[i] : 1;
+                const bool has_next = s + 1 < ns;
+                const int64_t index = info.nodes++;
+                info.events += rec.events; info.flips += rec.flips;
+                if (K > info.max_K) info.max_K = K;
+                lpx_bnb_node_log lg;
+                lg.depth = node.depth; lg.K = K; lg.status = rec.status; lg.events = rec.events; lg.flips = (int32_t)rec.flips;
+                lg.var = rec.pick.var; lg.z = rec.pick.z;
+                info.log.push_back(lg);
+                dinfo.round.push_back(round); dinfo.diver.push_back(slot[i]); pinfo.step.push_back(s);
+                if (rec.status == LPX_ITER_LIMIT) {
+                    info.limit_rc = LPX_ITER_LIMIT;
+                    info.limit_msg = "Bounded Branch and Bound: node " + std::to_string(index) + " (depth " + std::to_string(node.depth) +
+                                     ") reached the iteration limit of " + std::to_string(o.max_iter) + " events";
+                    stop = true;
+                    break;
+                }
+                if (rec.status == LPX_INFEASIBLE) { info.pruned_infeasible++; break; }
+                const double z = rec.pick.z;
+                if (rec.status == LPX_CUTOFF || z <= best + EPS) {
+                    // the kernel went on past this record against the best of the start of the round; best has moved since
+                    info.pruned_bound++;
+                    pinfo.dropped += ns - 1 - s;
+                    for (int k = s; k + 1 < ns; ++k) {                  // the handle holds the bounds of the last node evaluated
+                        const lpx_node_record& rk = recs[(size_t)i * D + k];
+                        Dv.nb_lo[rk.pick.var] = std::ceil(rk.pick.x_var);
+                    }
+                    break;
+                }
+                if (rec.pick.var < 0) {                                  // always the last record of its chain: the handle holds its x
+                    std::vector<double> x((size_t)n, 0.0);
+                    const int rs = lpx_tableau_bounded_solution(pool.h[slot[i]], n, x.data(), nullptr, nullptr);
+                    if (rs) throw_lib(rs);
+                    for (int j = 0; j < n; ++j) if (is_int.empty() || is_int[j]) x[j] = std::nearbyint(x[j]);
+                    best = z; best_x = std::move(x);
+                    info.incumbents++;
+                    break;
+                }
+                const int v = rec.pick.var;
+                Node fl{node.depth + 1, node.path}, ce{node.depth + 1, node.path};
+                fl.path.push_back(Override{v, Dv.nb_lo[v], std::floor(rec.pick.x_var)});
+                ce.path.push_back(Override{v, std::ceil(rec.pick.x_var), Dv.nb_ub[v]});
+                Dv.stack.push_back(std::move(fl));
+                if (has_next) { Dv.nb_lo[v] = std::ceil(rec.pick.x_var); node = std::move(ce); }      // the ceil child is the next record
+                else Dv.stack.push_back(std::move(ce));
+            }
+            Dv.cur_lo = Dv.nb_lo; Dv.cur_ub = Dv.nb_ub;
+        }
+    }
+
+    res.Nodes = info.nodes; res.LpSolves = info.nodes + 1;
+    res.Aux = {(double)info.nodes, (double)info.events, (double)info.flips, (double)info.incumbents};
+    res.Trace.clear();
+    if (best_x.empty()) {
+        res.Status = LPX_INFEASIBLE; res.HasSolution = false; res.OptimalValue = 0.0;
+        res.Solution.assign((size_t)n, 0.0);
+        res.Summary = "INFEASIBLE\n"; res.Report = res.Summary;
+        return res;
+    }
+    if (!ses.lower.empty()) for (int j = 0; j < n; ++j) best_x[j] = best_x[j] + ses.lower[j];
+    double value = ses.min ? -best : best;
+    if (ses.shifted) value = value + ses.constant;
+    res.Status = LPX_OPTIMAL; res.HasSolution = true; res.OptimalValue = value; res.Solution = best_x;
+    std::string report;
+    FinalizeText(report, res.Summary, best_x, value, LPX_OPTIMAL);
+    const std::string tail = "  nodes: " + std::to_string(info.nodes) + ", dual events: " + std::to_string(info.events) +
+                             ", dual-feasibility flips: " + std::to_string(info.flips) + "\n";
+    res.Report = report + tail; res.Summary += tail.substr(2);
+    return res;
+}
+
 }}  // namespace lpx::host

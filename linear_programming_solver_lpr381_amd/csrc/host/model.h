@@ -252,6 +252,11 @@ struct BnbDiversInfo { int64_t rounds = 0, steals = 0, largest_batch = 0; std::v
 SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
                              int search_flags, int divers, BnbDiversInfo& dinfo);
+// The search by W divers that plunge (lpx_solve_bnb_bounded5): one lpx_node_batch_plunge per round, up to `plunge` nodes per diver.
+struct BnbPlungeInfo { int64_t launched = 0, dropped = 0, longest_chain = 0; std::vector<int32_t> step; };
+SimplexResult SolveBnbPlunge(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
+                             const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
+                             int search_flags, int divers, int plunge, BnbDiversInfo& dinfo, BnbPlungeInfo& pinfo);
 
 // LPParser.ParseFromText, Models/LPParser.cs:9-79.  Throws LpxException(LPX_E_PARSE, message).
 LPProblem ParseFromText(const std::string& input);

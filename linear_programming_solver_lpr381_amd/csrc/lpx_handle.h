@@ -74,6 +74,9 @@ struct lpx_tableau {
         // and the host copy of the integer mask now in pickmask (mask_n bytes; -1: pickmask holds something else)
         char* nodeio = nullptr; size_t nodeio_bytes = 0;
         std::vector<uint8_t> mask_h; int mask_n = -1;
+        // the plunge (lpx_node_batch_plunge): whole[j] = 1 iff the host has seen column j's bounds and both are finite and integral
+        // (lpx_tableau_set_bounds and every accepted bound edit keep it; empty: nothing known).  Host knowledge only, no device copy.
+        std::vector<uint8_t> whole, snap_whole;
 
         void free()
         {
@@ -105,6 +108,9 @@ int check_node_fits(const lpx_tableau* t, const char* what);
 int bounded_node_ready(const char* what);       // the one-time attribute of the on-chip node kernels
 // what a finished on-chip node leaves on the host side of its handle, and the caller's record filled from the kernel's
 void node_onchip_commit(lpx_tableau* t, const NodeOut* rec, bool any_lo, lpx_node_record* out);
+// an accepted bound edit, for Bounds::whole: which of the edited columns now have finite integral bounds
+void bounds_note_edit(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper);
+int bounded_plunge_ready(const char* what);     // the one-time attribute of the plunge kernel
 
 static constexpr int LPX_RESIDENT_RETRY = -1000;     // internal: first resident launch timed out, state untouched
 

@@ -119,6 +119,11 @@ hipError_t bounded_node_init();                     // one-time function attribu
 hipError_t launch_bounded_node_onchip(const NodeParams& n, hipStream_t s);
 // the batch: workgroup b evaluates P[b] (an array the device can read); lds = the largest entry's bounded_node_lds_bytes
 hipError_t launch_bounded_nodes_onchip(const NodeParams* P, int B, size_t lds, hipStream_t s);
+// the plunge (lpx_bounded_plunge.hip): workgroup b evaluates a chain of up to P[b].depth nodes with the tile staying in LDS.
+// n.out is the first of `depth` records, 64 bytes apart; *steps = the records written; the chain stops at z <= prune.
+struct PlungeParams { NodeParams n; double prune; int32_t* steps; int32_t depth, pad; };
+hipError_t bounded_plunge_init();                   // one-time function attribute
+hipError_t launch_bounded_plunge_onchip(const PlungeParams* P, int B, size_t lds, hipStream_t s);
 
 // ---- lpx_kernels.hip: the two-launch select and update paths
 hipError_t launch_select(const SelParams& p, hipStream_t s);       // gather-based (dual path)

@@ -371,12 +371,14 @@ void lpx_bounded_close(lpx_bounded_session* s) { delete s; }
 // ---- branch and bound by bound changes on the root's handle (host/bnb_bounded.cpp) ------------------------------------------
 static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const double* upper, const uint8_t* is_int, const lpx_solve_opts* o,
                             int64_t max_nodes, int search_flags, lpx_result* out, lpx_bnb_bounded_info* info, const char* what,
-                            int node_form = -1, int divers = 0, lpx_bnb_divers_info* dinfo = nullptr)     // divers > 0: lpx_solve_bnb_bounded4
+                            int node_form = -1, int divers = 0, lpx_bnb_divers_info* dinfo = nullptr,     // divers > 0: lpx_solve_bnb_bounded4
+                            int plunge = 0, lpx_bnb_plunge_info* pinfo = nullptr)                         // plunge > 0: lpx_solve_bnb_bounded5
 {
     if (!p || !out) { set_error(std::string(what) + ": null argument"); return LPX_EINVAL; }
     std::memset(out, 0, sizeof(*out));
     if (info) std::memset(info, 0, sizeof(*info));
     if (dinfo) std::memset(dinfo, 0, sizeof(*dinfo));
+    if (pinfo) std::memset(pinfo, 0, sizeof(*pinfo));
     lpx_solve_opts d; if (!o) { lpx_default_solve_opts(&d); o = &d; }
     return guarded(what, [&]() -> int {
         EngineOptions e = to_engine(o);
@@ -388,9 +390,15 @@ static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const do
         if (is_int) mask.assign(is_int, is_int + p->n);
         BnbBoundedInfo bi;
         BnbDiversInfo di;
-        SimplexResult r = divers ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di)
+        BnbPlungeInfo pi;
+        SimplexResult r = plunge ? SolveBnbPlunge(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, plunge, di, pi)
+                        : divers ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di)
                                  : SolveBnbBounded(q, lo, up, mask, e, max_nodes, bi, search_flags, node_form);
         fill_result(out, r, p->n);
+        if (pinfo) {
+            pinfo->launched = pi.launched; pinfo->dropped = pi.dropped; pinfo->longest_chain = pi.longest_chain;
+            pinfo->step = dup_vec(pi.step);
+        }
         if (dinfo) {
             dinfo->rounds = di.rounds; dinfo->steals = di.steals; dinfo->largest_batch = di.largest_batch;
             dinfo->round = dup_vec(di.round); dinfo->diver = dup_vec(di.diver);
@@ -435,6 +443,23 @@ int lpx_solve_bnb_bounded4(const lpx_problem* p, const double* lower, const doub
 {
     if (divers < 1 || divers > 1024) { set_error("lpx_solve_bnb_bounded4: divers is outside [1, 1024]"); return LPX_EINVAL; }
     return solve_bnb_bounded(p, lower, upper, is_int, o, max_nodes, search_flags, out, info, "lpx_solve_bnb_bounded4", -1, divers, dinfo);
+}
+
+int lpx_solve_bnb_bounded5(const lpx_problem* p, const double* lower, const double* upper, const uint8_t* is_int,
+                           const lpx_solve_opts* o, int64_t max_nodes, int search_flags, int divers, int plunge, lpx_result* out,
+                           lpx_bnb_bounded_info* info, lpx_bnb_divers_info* dinfo, lpx_bnb_plunge_info* pinfo)
+{
+    if (divers < 1 || divers > 1024) { set_error("lpx_solve_bnb_bounded5: divers is outside [1, 1024]"); return LPX_EINVAL; }
+    if (plunge < 1 || plunge > 64) { set_error("lpx_solve_bnb_bounded5: plunge is outside [1, 64]"); return LPX_EINVAL; }
+    return solve_bnb_bounded(p, lower, upper, is_int, o, max_nodes, search_flags, out, info, "lpx_solve_bnb_bounded5", -1, divers, dinfo,
+                             plunge, pinfo);
+}
+
+void lpx_bnb_plunge_info_free(lpx_bnb_plunge_info* pinfo)
+{
+    if (!pinfo) return;
+    std::free(pinfo->step);
+    std::memset(pinfo, 0, sizeof(*pinfo));
 }
 
 void lpx_bnb_divers_info_free(lpx_bnb_divers_info* dinfo)

@@ -5,6 +5,7 @@
 #include "lpx_handle.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -20,6 +21,7 @@ struct lpx_node_batch {
     std::vector<uint8_t> mask_h; int mask_n = -1;       // ... and the host bytes it was made from
     std::vector<int32_t> seen; int32_t call = 0;        // seen[s] == call: slot s is named already in this call
     std::vector<size_t> off_in, off_edit; std::vector<uint8_t> any_lo;      // per entry, kept to spare the steady state its allocations
+    std::vector<size_t> off_trip; std::vector<uint8_t> colmark;             // the plunge: an entry's first triple; scratch of its integrality check
 };
 
 namespace {
@@ -73,7 +75,7 @@ int lpx_node_batch_create(int W, lpx_tableau* const* handles, lpx_node_batch** o
     for (lpx_tableau* t : b->h)
         if (std::find(b->streams.begin(), b->streams.end(), t->stream) == b->streams.end()) b->streams.push_back(t->stream);
     b->seen.assign((size_t)W, 0);
-    b->off_in.resize((size_t)W); b->off_edit.resize((size_t)W); b->any_lo.resize((size_t)W);
+    b->off_in.resize((size_t)W); b->off_edit.resize((size_t)W); b->any_lo.resize((size_t)W); b->off_trip.resize((size_t)W);
     *out = b;
     return 0;
 }
@@ -197,8 +199,11 @@ int lpx_node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const int3
 
     // ---- 5. the records
     bool refused = false;
+    sumK = 0;
     for (int i = 0; i < B; ++i) {
         lpx_tableau* t = b->h[slot[i]];
+        const size_t at0 = sumK;
+        sumK += (size_t)K[i];
         const NodeOut* rec = reinterpret_cast<const NodeOut*>(b->slab + o_out + kOut * (size_t)i);
         if (rec->status < 0) {                                           // refused by the kernel: this handle is as it was
             rc[i] = LPX_EINVAL;
@@ -213,7 +218,193 @@ int lpx_node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const int3
             continue;
         }
         node_onchip_commit(t, rec, b->any_lo[i] != 0, &out[i]);
+        if (K[i] > 0) bounds_note_edit(t, K[i], cols + at0, lower + at0, upper + at0);
         rc[i] = rec->status;
+    }
+    return 0;
+}
+
+// The plunge: lpx_node_batch_run's steps with a chain of up to depth[i] nodes per entry (kernel: lpx_bounded_plunge.hip).  The text
+// is a copy of lpx_node_batch_run's, not shared with it, as lpx_node_batch_run's was of the single node's: that function stays as it is.
+int lpx_node_batch_plunge(lpx_node_batch* b, int B, const int32_t* slot, const int32_t* K, const int32_t* cols, const double* lower,
+                          const double* upper, const lpx_run_opts* o, int flags, const double* cutoff, const double* prune,
+                          const int32_t* depth, int D, int nint, const uint8_t* is_int, double tol, lpx_node_record* out,
+                          int32_t* steps, int32_t* rc)
+{
+    const std::string w = "lpx_node_batch_plunge";
+    // ---- 1. every argument of every entry, before anything is written and before any device check
+    if (!slot || !K || !out || !rc || !depth || !steps || !prune) {
+        set_error(w + ": null " + (!slot ? "slot" : !K ? "K" : !out ? "out" : !rc ? "rc" : !depth ? "depth" : !steps ? "steps" : "prune"));
+        return LPX_EINVAL;
+    }
+    if (B < 1) { set_error(w + ": B is outside [1, W]"); return LPX_EINVAL; }
+    if (D < 1 || D > 64) { set_error(w + ": D is outside [1, 64]"); return LPX_EINVAL; }
+    { int r = check_long_flags(flags, 0.0, w.c_str()); if (r) return r; }
+    if (flags & LPX_BDUAL_CUTOFF) {
+        if (!cutoff) { set_error(w + ": null cutoff with LPX_BDUAL_CUTOFF"); return LPX_EINVAL; }
+        for (int i = 0; i < B; ++i) { int r = check_long_flags(flags, cutoff[i], (w + ": entry " + std::to_string(i)).c_str()); if (r) return r; }
+    }
+    for (int i = 0; i < B; ++i) {
+        const std::string at = w + ": entry " + std::to_string(i);
+        if (depth[i] < 1 || depth[i] > D) { set_error(at + ": depth is outside [1, D]"); return LPX_EINVAL; }
+        if (prune[i] != prune[i]) { set_error(at + ": prune is NaN"); return LPX_EINVAL; }
+    }
+    if (!b) { set_error(w + ": null batch"); return LPX_EINVAL; }
+    const int W = (int)b->h.size();
+    if (B > W) { set_error(w + ": B is outside [1, W]"); return LPX_EINVAL; }
+    lpx_run_opts d; if (!o) { lpx_default_opts(&d, 1); o = &d; }
+    if (b->call == INT32_MAX) { std::fill(b->seen.begin(), b->seen.end(), 0); b->call = 0; }
+    ++b->call;
+    size_t sumK = 0, in_bytes = 0, edit_bytes = 0, lds = 0;
+    char at[56];
+    for (int i = 0; i < B; ++i) {
+        std::snprintf(at, sizeof at, "lpx_node_batch_plunge: entry %d", i);
+        if (slot[i] < 0 || slot[i] >= W) { set_error(std::string(at) + ": slot is outside [0, W)"); return LPX_EINVAL; }
+        if (b->seen[slot[i]] == b->call) { set_error(std::string(at) + ": slot repeats a handle"); return LPX_EINVAL; }
+        b->seen[slot[i]] = b->call;
+        lpx_tableau* t = b->h[slot[i]];
+        const int k = K[i];
+        int r = check_change_args(t, k, cols ? cols + sumK : nullptr, lower ? lower + sumK : nullptr, upper ? upper + sumK : nullptr, at);
+        if (r) return r;
+        r = check_pick_args(t, nint, tol, out, at); if (r) return r;
+        r = check_node_opts(t, o, at); if (r) return r;
+        r = check_node_fits(t, at); if (r) return r;
+        if (depth[i] > 1) {
+            // a chain branches on the masked-in columns: each must be known to have finite integral bounds once this entry's own
+            // triples are in place, so that lo + ub is the upper bound exactly and the ceil child is the driver's
+            const std::vector<uint8_t>& whole = t->bnd.whole;
+            b->colmark.assign((size_t)nint, 0);
+            for (int j = 0; j < k; ++j) {
+                const int c = cols[sumK + j];
+                if (c >= nint) continue;
+                const double lw = lower[sumK + j], up = upper[sumK + j];
+                b->colmark[c] = (up < 1.0 / 0.0 && __builtin_floor(lw) == lw && __builtin_floor(up) == up) ? 1 : 2;
+            }
+            for (int j = 0; j < nint; ++j) {
+                if (is_int && !is_int[j]) continue;
+                const bool ok = b->colmark[j] ? b->colmark[j] == 1 : ((size_t)j < whole.size() && whole[j]);
+                if (!ok) {
+                    set_error(std::string(at) + ": depth > 1 needs finite integral bounds on every integer column; column " +
+                              std::to_string(j) + " is not known to have them");
+                    return LPX_EINVAL;
+                }
+            }
+        }
+        const size_t k1 = (size_t)(k > 1 ? k : 1);                       // the in-chain edit uses index 0 of the staging
+        b->off_in[i] = in_bytes; b->off_edit[i] = edit_bytes; b->off_trip[i] = sumK;
+        in_bytes += up16(sizeof(NodeIn) + (size_t)k * (2 * sizeof(double) + sizeof(int32_t)));
+        edit_bytes += up16(k1 * (5 * sizeof(double) + sizeof(int32_t)));
+        lds = std::max(lds, bounded_node_lds_bytes(t->R, t->C));
+        sumK += (size_t)k;
+    }
+    int r = ensure_device(); if (r) return r;
+    r = bounded_plunge_ready(w.c_str()); if (r) return r;
+
+    // ---- 2. the buffers: grown to twice the need, and only when the need outgrows them
+    const size_t o_out = up16(sizeof(PlungeParams) * (size_t)B), o_steps = o_out + kOut * (size_t)B * (size_t)D,
+                 o_in = o_steps + up16(sizeof(int32_t) * (size_t)B), need = o_in + in_bytes;
+    if (need > b->slab_bytes) {
+        r = settle_all(b); if (r) return r;
+        if (b->slab) hipHostFree(b->slab);
+        b->slab = nullptr; b->slab_bytes = 0;
+        LPX_HIP_TRY(hipHostMalloc((void**)&b->slab, 2 * need));
+        b->slab_bytes = 2 * need;
+    }
+    if (edit_bytes > b->edit_bytes) {
+        r = settle_all(b); if (r) return r;
+        hipFree(b->edit); b->edit = nullptr; b->edit_bytes = 0;
+        LPX_HIP_TRY(hipMalloc((void**)&b->edit, 2 * edit_bytes));
+        b->edit_bytes = 2 * edit_bytes;
+    }
+    hipStream_t s = b->streams[0];
+    const bool has_mask = is_int && nint > 0;
+    if (has_mask && !(b->mask_n == nint && std::memcmp(b->mask_h.data(), is_int, (size_t)nint) == 0)) {
+        r = settle(s); if (r) return r;                                  // an earlier copy may still read mask_h
+        if ((size_t)nint > b->mask_cap) {
+            hipFree(b->mask); b->mask = nullptr; b->mask_cap = 0;
+            LPX_HIP_TRY(hipMalloc((void**)&b->mask, 2 * (size_t)nint));
+            b->mask_cap = 2 * (size_t)nint;
+        }
+        b->mask_h.assign(is_int, is_int + nint);
+        LPX_HIP_TRY(hipMemcpyAsync(b->mask, b->mask_h.data(), (size_t)nint, hipMemcpyHostToDevice, s));
+        b->mask_n = nint;
+    }
+
+    // ---- 3. the slab: a parameter record, a header with its triples, D result records and a steps word per entry
+    PlungeParams* P = reinterpret_cast<PlungeParams*>(b->slab);
+    int32_t* nrec = reinterpret_cast<int32_t*>(b->slab + o_steps);
+    for (int i = 0; i < B; ++i) {
+        lpx_tableau* t = b->h[slot[i]];
+        lpx_tableau::Bounds& bn = t->bnd;
+        const int k = K[i];
+        const size_t at0 = b->off_trip[i];
+        bool any_lo = false;
+        for (int j = 0; j < k; ++j) if (lower[at0 + j] != 0.0) any_lo = true;
+        b->any_lo[i] = any_lo ? 1 : 0;
+        NodeIn* in = reinterpret_cast<NodeIn*>(b->slab + o_in + b->off_in[i]);
+        std::memset(in, 0, sizeof(*in));
+        in->K = k; in->flags = flags; in->nint = nint; in->has_mask = has_mask ? 1 : 0; in->max_iter = o->max_iter;
+        in->lo_used = (bn.lo_used || any_lo) ? 1 : 0;
+        in->eps = o->eps; in->ratio_tol = o->ratio_tol; in->cutoff = (flags & LPX_BDUAL_CUTOFF) ? cutoff[i] : 0.0; in->tol = tol;
+        if (k > 0) {
+            double* a = reinterpret_cast<double*>(in + 1);
+            std::memcpy(a, lower + at0, sizeof(double) * k);
+            std::memcpy(a + k, upper + at0, sizeof(double) * k);
+            std::memcpy(a + 2 * (size_t)k, cols + at0, sizeof(int32_t) * k);
+        }
+        PlungeParams& q = P[i];
+        std::memset(&q, 0, sizeof(q));
+        NodeParams& n = q.n;
+        n.T = t->T; n.ld = t->ld; n.R = t->R; n.C = t->C;
+        n.rhsbuf = t->rhsbuf; n.basis = t->basis; n.trace = t->trace; n.trace_cap = t->trace_cap; n.st = t->st;
+        n.ub = bn.ub; n.lo = bn.lo; n.flip = bn.flip; n.edit = reinterpret_cast<double*>(b->edit + b->off_edit[i]); n.mask = b->mask;
+        n.in = in; n.out = reinterpret_cast<NodeOut*>(b->slab + o_out + kOut * (size_t)i * (size_t)D);
+        q.prune = prune[i]; q.steps = nrec + i; q.depth = depth[i];
+        nrec[i] = 0;
+        for (int sx = 0; sx < D; ++sx) { std::memset(&out[(size_t)i * D + sx], 0, sizeof(out[0])); out[(size_t)i * D + sx].pick.var = -1; }
+        steps[i] = 0;
+    }
+
+    // ---- 4. behind the handles' own streams, ONE launch, ONE wait
+    r = settle_all(b); if (r) return r;
+    LPX_HIP_TRY(launch_bounded_plunge_onchip(P, B, lds, s));
+    LPX_HIP_TRY(hipStreamSynchronize(s));
+
+    // ---- 5. the records: a chain's completed nodes in order, each as a single call would have left its handle
+    bool refused = false;
+    for (int i = 0; i < B; ++i) {
+        lpx_tableau* t = b->h[slot[i]];
+        const char* base = b->slab + o_out + kOut * (size_t)i * (size_t)D;
+        int n = nrec[i];
+        if (n < 1 || n > depth[i]) { set_error(w + ": entry " + std::to_string(i) + ": the kernel left no record"); return LPX_EDEVICE; }
+        const NodeOut* last = reinterpret_cast<const NodeOut*>(base + kOut * (size_t)(n - 1));
+        const bool ref = last->status < 0;                               // refused by the kernel: the handle is as after the node before
+        const int good = ref ? n - 1 : n;
+        bool any_lo = b->any_lo[i] != 0;
+        for (int sx = 0; sx < good; ++sx) {
+            const NodeOut* rec = reinterpret_cast<const NodeOut*>(base + kOut * (size_t)sx);
+            if (sx > 0) {                                                // the ceil child's lower bound, as the kernel formed it
+                const NodeOut* prev = reinterpret_cast<const NodeOut*>(base + kOut * (size_t)(sx - 1));
+                if (std::ceil(prev->x_var) != 0.0) any_lo = true;
+            }
+            node_onchip_commit(t, rec, any_lo, &out[(size_t)i * D + sx]);
+        }
+        if (good > 0 && K[i] > 0) bounds_note_edit(t, K[i], cols + b->off_trip[i], lower + b->off_trip[i], upper + b->off_trip[i]);
+        steps[i] = good;
+        if (ref) {
+            rc[i] = LPX_EINVAL;
+            out[(size_t)i * D + good].unrepairable = last->unrepairable;
+            if (!refused) {
+                std::string at2 = w + ": entry " + std::to_string(i);
+                if (good > 0) at2 += ": node " + std::to_string(good);
+                if (last->inf_k >= 0) set_error(at2 + ": upper[" + std::to_string(last->inf_k) + "] = +inf on a flipped column");
+                else set_error(at2 + ": " + std::to_string(last->unrepairable) + " column(s) with a negative reduced cost and no upper "
+                               "bound: a bound flip cannot restore dual feasibility");
+            }
+            refused = true;
+            continue;
+        }
+        rc[i] = last->status;
     }
     return 0;
 }

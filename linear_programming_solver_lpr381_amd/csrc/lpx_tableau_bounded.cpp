@@ -21,7 +21,7 @@ int lpx::bounds_snapshot(lpx_tableau* t)
         LPX_HIP_TRY(hipMalloc((void**)&b.snapLo, sizeof(double) * t->Ccap));
     }
     LPX_HIP_TRY(hipMemcpyAsync(b.snapLo, b.lo, sizeof(double) * t->Ccap, hipMemcpyDeviceToDevice, t->stream));
-    b.snap_lo_used = b.lo_used;
+    b.snap_lo_used = b.lo_used; b.snap_whole = b.whole;
     LPX_HIP_TRY(hipMemcpyAsync(b.snapUb, b.ub, sizeof(double) * t->Ccap, hipMemcpyDeviceToDevice, t->stream));
     LPX_HIP_TRY(hipMemcpyAsync(b.snapFlip, b.flip, t->Ccap, hipMemcpyDeviceToDevice, t->stream));
     return 0;
@@ -34,11 +34,11 @@ int lpx::bounds_restore(lpx_tableau* t)
         LPX_HIP_TRY(hipMemcpyAsync(b.ub, b.snapUb, sizeof(double) * t->Ccap, hipMemcpyDeviceToDevice, t->stream));
         LPX_HIP_TRY(hipMemcpyAsync(b.flip, b.snapFlip, t->Ccap, hipMemcpyDeviceToDevice, t->stream));
         LPX_HIP_TRY(hipMemcpyAsync(b.lo, b.snapLo, sizeof(double) * t->Ccap, hipMemcpyDeviceToDevice, t->stream));
-        b.bounds_set = true; b.bounds_C = b.snap_bounds_C; b.lo_used = b.snap_lo_used;
+        b.bounds_set = true; b.bounds_C = b.snap_bounds_C; b.lo_used = b.snap_lo_used; b.whole = b.snap_whole;
     } else if (b.bounds_set) {      // snapshotted before it had bounds: that tableau had no column flipped or shifted
         LPX_HIP_TRY(hipMemsetAsync(b.flip, 0, t->Ccap, t->stream));
         LPX_HIP_TRY(hipMemsetAsync(b.lo, 0, sizeof(double) * t->Ccap, t->stream));
-        b.lo_used = false;
+        b.lo_used = false; b.whole.clear();
     }
     return 0;
 }
@@ -54,7 +54,7 @@ int lpx::bounds_clone(const lpx_tableau* src, lpx_tableau* dst)
     LPX_HIP_TRY(hipMemcpyAsync(b.ub, a.ub, sizeof(double) * dst->Ccap, hipMemcpyDeviceToDevice, dst->stream));
     LPX_HIP_TRY(hipMemcpyAsync(b.flip, a.flip, dst->Ccap, hipMemcpyDeviceToDevice, dst->stream));
     LPX_HIP_TRY(hipMemcpyAsync(b.lo, a.lo, sizeof(double) * dst->Ccap, hipMemcpyDeviceToDevice, dst->stream));
-    b.bounds_set = true; b.bounds_C = a.bounds_C; b.lo_used = a.lo_used;
+    b.bounds_set = true; b.bounds_C = a.bounds_C; b.lo_used = a.lo_used; b.whole = a.whole;
     return 0;
 }
 
@@ -90,7 +90,7 @@ int bounds_fill_inf(lpx_tableau* t)
     LPX_HIP_TRY(hipMemsetAsync(t->bnd.flip, 0, t->Ccap, t->stream));
     LPX_HIP_TRY(hipMemsetAsync(t->bnd.lo, 0, sizeof(double) * t->Ccap, t->stream));      // +0.0
     LPX_HIP_TRY(hipStreamSynchronize(t->stream));
-    t->bnd.lo_used = false;
+    t->bnd.lo_used = false; t->bnd.whole.clear();
     return 0;
 }
 
@@ -298,6 +298,23 @@ int lpx::bounded_node_ready(const char* what)
     return 0;
 }
 
+int lpx::bounded_plunge_ready(const char* what)
+{
+    static std::once_flag once; static hipError_t init_err = hipSuccess;
+    std::call_once(once, [] { init_err = bounded_plunge_init(); });
+    if (init_err != hipSuccess) { set_error(std::string(what) + ": kernel attribute setup failed: " + hipGetErrorString(init_err)); return LPX_EDEVICE; }
+    return 0;
+}
+
+void lpx::bounds_note_edit(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper)
+{
+    std::vector<uint8_t>& w = t->bnd.whole;
+    if (w.empty()) return;                  // nothing is known about this handle's columns: an edit of some of them changes nothing
+    for (int k = 0; k < K; ++k)
+        if ((size_t)cols[k] < w.size())
+            w[cols[k]] = (upper[k] < 1.0 / 0.0 && __builtin_floor(lower[k]) == lower[k] && __builtin_floor(upper[k]) == upper[k]) ? 1 : 0;
+}
+
 void lpx::node_onchip_commit(lpx_tableau* t, const NodeOut* rec, bool any_lo, lpx_node_record* out)
 {
     lpx_tableau::Bounds& b = t->bnd;
@@ -319,7 +336,7 @@ extern "C" {
 int lpx_tableau_set_bounds(lpx_tableau* t, int ncols, const double* ub)
 {
     if (!t) { set_error("lpx_tableau_set_bounds: null handle"); return LPX_EINVAL; }
-    if (!ub && ncols == 0) { t->bnd.bounds_set = false; t->bnd.bounds_C = 0; return 0; }
+    if (!ub && ncols == 0) { t->bnd.bounds_set = false; t->bnd.bounds_C = 0; t->bnd.whole.clear(); return 0; }
     if (!ub || ncols != t->C - 1) { set_error("lpx_tableau_set_bounds: ncols must be the live C - 1 and ub non-null"); return LPX_EINVAL; }
     for (int j = 0; j < ncols; ++j)
         if (!(ub[j] >= 0.0)) { set_error("lpx_tableau_set_bounds: ub[" + std::to_string(j) + "] is negative or NaN"); return LPX_EINVAL; }
@@ -328,6 +345,8 @@ int lpx_tableau_set_bounds(lpx_tableau* t, int ncols, const double* ub)
     rc = bounds_fill_inf(t); if (rc) return rc;            // columns beyond the live shape: unbounded; every flip cleared
     LPX_HIP_TRY(hipMemcpy(t->bnd.ub, ub, sizeof(double) * ncols, hipMemcpyHostToDevice));
     t->bnd.bounds_set = true; t->bnd.bounds_C = t->C;
+    t->bnd.whole.assign((size_t)ncols, 0);                 // lo is zero everywhere: a column is whole iff its ub is finite and integral
+    for (int j = 0; j < ncols; ++j) t->bnd.whole[j] = (ub[j] < 1.0 / 0.0 && __builtin_floor(ub[j]) == ub[j]) ? 1 : 0;
     return 0;
 }
 
@@ -421,6 +440,7 @@ int lpx_tableau_change_bounds(lpx_tableau* t, int K, const int32_t* cols, const 
         LPX_HIP_TRY(launch_bounds_shift(K, e.cols, e.lower, e.upper, t->bnd.ub, t->bnd.lo, t->bnd.flip, e.shift, t->stream));
         LPX_HIP_TRY(launch_bounds_apply(t->T, t->ld, t->R, Cm, K, e.cols, e.shift, t->rhsbuf, t->stream));
         if (e.any_lo) t->bnd.lo_used = true;
+        bounds_note_edit(t, K, cols, lower, upper);
     }
     LPX_HIP_TRY(hipMemsetAsync(t->st, 0, sizeof(DevState), t->stream));      // the loop state, as lpx_tableau_build_child resets it
     LPX_HIP_TRY(hipStreamSynchronize(t->stream));                            // the caller's arrays are free again
@@ -498,6 +518,7 @@ static int bounded_node(lpx_tableau* t, int K, const int32_t* cols, const double
     }
     t->suspended = t->suspended2 = t->fsuspended = false;
     if (e.any_lo) t->bnd.lo_used = true;
+    bounds_note_edit(t, K, cols, lower, upper);
     if (K > 0) LPX_HIP_TRY(launch_bounds_apply(t->T, t->ld, t->R, Cm, K, e.cols, e.shift, t->rhsbuf, t->stream));
     rc = enqueue_dualize_apply(t); if (rc) return rc;
     // the loop (it resets the state record itself and waits once per batch)
@@ -605,6 +626,7 @@ static int bounded_node_onchip(lpx_tableau* t, int K, const int32_t* cols, const
         return LPX_EINVAL;
     }
     node_onchip_commit(t, rec, any_lo, out);
+    bounds_note_edit(t, K, cols, lower, upper);
     return rec->status;
 }
 

@@ -343,7 +343,7 @@ class LPSolver:             # Models/LPSolver.cs:6-77
 
     def SolveBnbBounded(self, problem: LPProblem, upper, lower=None, integer=None, max_nodes: int = 0,
                         long_step: bool = False, cutoff: bool = False, node_form: Optional[str] = None,
-                        divers: Optional[int] = None) -> SimplexResult:
+                        divers: Optional[int] = None, plunge: Optional[int] = None) -> SimplexResult:
         """Branch and bound by bound changes on one device tableau (lpx_solve_bnb_bounded): lower <= x <= upper, x_j integer
         where integer[j] (None: every variable); integer variables need finite, integral bounds.  Status OPTIMAL or INFEASIBLE,
         Solution, OptimalValue (user's sense), Nodes, BnbInfo (counters) and BnbLog, a structured array with one record per node
@@ -357,7 +357,15 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         log that depends on the model, the flags and W alone.  Use long_step=True with divers on larger models: another W visits
         other nodes, and without the long step some of them make max_iter events and end the solve with ITER_LIMIT (on
         binary_ip(128, 64), W = 4, 64 and 256 do; with the long step none measured did).  The result then carries BnbInfo["rounds" / "steals" /
-        "largest_batch"] and BnbRound / BnbDiver, the round and the diver of every log record."""
+        "largest_batch"] and BnbRound / BnbDiver, the round and the diver of every log record.  plunge=D
+        (lpx_solve_bnb_bounded5, 1 <= D <= 64; without divers it means divers=1): a diver's workgroup goes on from a node that
+        branches into its ceil child, up to D nodes per launch with the tableau staying in LDS.  plunge=1 gives the log of
+        divers=W, divers=1 with any plunge the log of node_form="onchip".  The result then also carries BnbStep (every record's
+        index in its chain) and BnbInfo["launched" / "dropped" / "longest_chain"]."""
+        if plunge is not None and node_form == "launches":
+            raise ValueError("plunge evaluates every node on chip: it cannot be combined with node_form='launches'")
+        if plunge is not None and divers is None:
+            divers = 1
         if divers is not None and node_form == "launches":
             raise ValueError("divers evaluates every node on chip: it cannot be combined with node_form='launches'")
         if node_form is None:               # not given: "launches", the default; with divers every node is on chip
@@ -379,9 +387,12 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         if integer is not None:
             mask = np.ascontiguousarray(np.broadcast_to(np.asarray(integer, dtype=np.uint8), (n,)))
             mp = mask.ctypes.data_as(C.POINTER(C.c_uint8))
-        r, info, dinfo = _lib.Result(), _lib.BnbBoundedInfo(), _lib.BnbDiversInfo()
+        r, info, dinfo, pinfo = _lib.Result(), _lib.BnbBoundedInfo(), _lib.BnbDiversInfo(), _lib.BnbPlungeInfo()
         flags = (_lib.BDUAL_LONG_STEP if long_step else 0) | (_lib.BDUAL_CUTOFF if cutoff else 0)
-        if divers is not None:
+        if plunge is not None:
+            rc = lib().lpx_solve_bnb_bounded5(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), flags, int(divers), int(plunge),
+                                              C.byref(r), C.byref(info), C.byref(dinfo), C.byref(pinfo))
+        elif divers is not None:
             rc = lib().lpx_solve_bnb_bounded4(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), flags, int(divers),
                                               C.byref(r), C.byref(info), C.byref(dinfo))
         elif node_form != "launches":
@@ -404,13 +415,19 @@ class LPSolver:             # Models/LPSolver.cs:6-77
                 counters.update({k: getattr(dinfo, k) for k in ("rounds", "steals", "largest_batch")})
                 rounds = np.ctypeslib.as_array(dinfo.round, (info.n_log,)).copy() if info.n_log else np.zeros(0, dtype=np.int32)
                 who = np.ctypeslib.as_array(dinfo.diver, (info.n_log,)).copy() if info.n_log else np.zeros(0, dtype=np.int32)
+            if plunge is not None:
+                counters.update({k: getattr(pinfo, k) for k in ("launched", "dropped", "longest_chain")})
+                step = np.ctypeslib.as_array(pinfo.step, (info.n_log,)).copy() if info.n_log else np.zeros(0, dtype=np.int32)
         finally:
             lib().lpx_bnb_bounded_info_free(C.byref(info))
             lib().lpx_bnb_divers_info_free(C.byref(dinfo))
+            lib().lpx_bnb_plunge_info_free(C.byref(pinfo))
         res = _take_result(r, n)
         res.BnbLog, res.BnbInfo = log, counters
         if divers is not None:
             res.BnbRound, res.BnbDiver = rounds, who
+        if plunge is not None:
+            res.BnbStep = step
         if rc != 0:
             e = SolverException(rc, msg)
             e.result = res

@@ -461,6 +461,59 @@ class NodeBatch:
             out.append(d)
         return out
 
+    def plunge(self, slots, nodes, nint: int, depth, D: int, prune, is_int=None, tol: float = 1e-6, long_step: bool = False,
+               cutoffs=None, opts: Optional[RunOpts] = None, **kw) -> list:
+        """run() whose entry i is a chain of up to depth[i] <= D nodes in one launch, the tableau staying in LDS
+        (lpx_node_batch_plunge): after a node that branches with z above prune[i], the same workgroup goes on into the ceil child.
+        depth and prune are one value or one per entry (prune -inf: nothing is pruned).  Returns, per entry, the list of its
+        chain's record dicts in order; a chain the kernel refused inside ends with a dict whose status is None (an entry
+        refused at node 0 is that one dict alone)."""
+        slots = np.ascontiguousarray(np.atleast_1d(slots), dtype=np.int32).reshape(-1)
+        B = len(slots)
+        if len(nodes) != B:
+            raise ValueError(f"{B} slots but {len(nodes)} nodes")
+        if B < 1 or B > self._W:
+            raise ValueError(f"a batch of {B} entries on {self._W} handles: B must be in [1, W]")
+        D = int(D)
+        if D < 1 or D > 64:
+            raise ValueError(f"D = {D}: D must be in [1, 64]")
+        cs, ls, us = [], [], []
+        for cols, lower, upper in nodes:
+            c = np.ascontiguousarray(np.atleast_1d(cols), dtype=np.int32).reshape(-1)
+            cs.append(c)
+            ls.append(np.broadcast_to(np.asarray(lower, dtype=np.float64), c.shape))
+            us.append(np.broadcast_to(np.asarray(upper, dtype=np.float64), c.shape))
+        K = np.array([len(c) for c in cs], dtype=np.int32)
+        cols = np.ascontiguousarray(np.concatenate(cs), dtype=np.int32)
+        lower = np.ascontiguousarray(np.concatenate(ls), dtype=np.float64)
+        upper = np.ascontiguousarray(np.concatenate(us), dtype=np.float64)
+        flags = (_lib.BDUAL_SKIP_FIXED | (_lib.BDUAL_LONG_STEP if long_step else 0)
+                 | (_lib.BDUAL_CUTOFF if cutoffs is not None else 0))
+        cut, cp = None, None
+        if cutoffs is not None:
+            cut = np.ascontiguousarray(np.broadcast_to(np.asarray(cutoffs, dtype=np.float64), (B,)))
+            cp = cut.ctypes.data_as(dp)
+        pr = np.ascontiguousarray(np.broadcast_to(np.asarray(prune, dtype=np.float64), (B,)))
+        dep = np.ascontiguousarray(np.broadcast_to(np.asarray(depth, dtype=np.int32), (B,)))
+        o = opts if opts is not None else default_opts(True, **kw)
+        keep, mp = DeviceTableau._mask(is_int, int(nint))
+        recs = (_lib.NodeRecord * (B * D))()
+        rc = np.zeros(B, dtype=np.int32)
+        steps = np.zeros(B, dtype=np.int32)
+        check(lib().lpx_node_batch_plunge(self._h, B, slots.ctypes.data_as(ip), K.ctypes.data_as(ip), cols.ctypes.data_as(ip),
+                                          lower.ctypes.data_as(dp), upper.ctypes.data_as(dp), C.byref(o), flags, cp,
+                                          pr.ctypes.data_as(dp), dep.ctypes.data_as(ip), D, int(nint), mp, float(tol), recs,
+                                          steps.ctypes.data_as(ip), rc.ctypes.data_as(ip)))
+        out = []
+        for i in range(B):
+            chain = [_node_dict(recs[i * D + s]) for s in range(int(steps[i]))]
+            if rc[i] < 0:
+                d = _node_dict(recs[i * D + int(steps[i])])
+                d["status"] = None
+                chain.append(d)
+            out.append(chain)
+        return out
+
 
 def primal_tableau(T: np.ndarray, basis: np.ndarray, eps: float = 1e-9, max_iter: int = 10000,
                    cb: Optional[PivotCallback] = None):

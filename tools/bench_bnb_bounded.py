@@ -28,10 +28,18 @@ on-chip driver: per model and flag set (`--flag-sets`, default here plain,both) 
 comma-separated LIST alternate in one process, REPS timed solves each after one untimed solve; nodes, events, rounds, nodes/s
 and wall per form, and `wins`: a W wins iff its median lies below the single-diver form's minimum.
 `--divers W` makes side (b), and `--trace-only`, the search by W divers.
+`--plunge D` makes them the plunge (lpx_solve_bnb_bounded5): up to D nodes per diver and launch; without
+`--divers` it means one diver.
+`--compare-plunge LIST` measures the plunge at the W of `--divers` (default 1) against the same search without it -- divers=W,
+for W = 1 the sequential on-chip driver: per model and flag set the baseline and each D of the comma-separated LIST alternate
+in one process, REPS timed solves each after one untimed solve; nodes, events, rounds, launched, dropped and wall per form, and
+`wins`: a D wins iff its median lies below the baseline's minimum.  A search that ends at a node's event limit is reported
+(`limit`) and not timed against.
 `--trace-only` runs one solve of side (b) and nothing else (for a kernel trace of the node form given).
 
-usage: bench_bnb_bounded.py [--model NAME] [--max-nodes N] [--node-form F] [--divers W] [--compare-forms [--flag-sets LIST]]
-                            [--compare-divers LIST [--flag-sets LIST]] [--trace-only] [REPS]"""
+usage: bench_bnb_bounded.py [--model NAME] [--max-nodes N] [--node-form F] [--divers W] [--plunge D]
+                            [--compare-forms [--flag-sets LIST]] [--compare-divers LIST [--flag-sets LIST]]
+                            [--compare-plunge LIST [--flag-sets LIST]] [--trace-only] [REPS]"""
 import json
 import os
 import statistics
@@ -183,10 +191,61 @@ def compare_divers(n, m, reps, max_nodes, flag_sets, widths):
     return rec
 
 
+def compare_plunge(n, m, reps, max_nodes, flag_sets, W, depths):
+    """The plunge (lpx_solve_bnb_bounded5) at W divers against the same search without it on binary_ip(n, m): the baseline is
+    divers=W, for W = 1 the sequential on-chip driver (see the module docstring)."""
+    c, A, rel, b = synth.binary_ip(n, m)
+    bnd_p = L.LPProblem.from_arrays(0, c, A[:m], rel[:m], b[:m])
+    rec = {"n": n, "m": m, "bounded_shape": [m + 1, n + m + 1], "divers": W}
+    sides = ["base"] + [f"D{d}" for d in depths]
+
+    def solve(side, kw, limit=None):
+        limit = max_nodes if limit is None else limit
+        if side != "base":
+            how = {"divers": W, "plunge": int(side[1:])}
+        else:
+            how = {"node_form": "onchip"} if W == 1 else {"divers": W}
+        t0 = time.perf_counter()
+        try:
+            r = L.LPSolver().SolveBnbBounded(bnd_p, 1.0, max_nodes=limit, **how, **kw)
+            r.Limit = None
+        except L.SolverException as e:
+            if e.code != L._lib.ITER_LIMIT:
+                raise
+            r = e.result
+            r.Limit = None if limit and r.Nodes >= limit else str(e)      # a node at its event limit ends the solve: reported, not timed against
+        return 1e3 * (time.perf_counter() - t0), r
+
+    for fs in flag_sets:
+        kw = FLAG_SETS[fs]
+        ts = {s: [] for s in sides}
+        last = {}
+        for i in range(reps + 1):
+            for s in sides:
+                if i == 0:          # the untimed solve: clones, the batch's slab and the first launch are paid here
+                    solve(s, kw, max_nodes if max_nodes else 2000)
+                    continue
+                ms, r = solve(s, kw)
+                last[s] = r
+                ts[s].append(ms)
+        base = stats(ts["base"])
+        d = {}
+        for s in sides:
+            r = last[s]
+            st = stats(ts[s])
+            d[s] = {"ms": st, "nodes": int(r.Nodes), "events": r.BnbInfo["events"], "rounds": r.BnbInfo.get("rounds", int(r.Nodes)),
+                    "launched": r.BnbInfo.get("launched", int(r.Nodes)), "dropped": r.BnbInfo.get("dropped", 0),
+                    "longest_chain": r.BnbInfo.get("longest_chain", 1), "nodes_per_s": r.Nodes / (st["median"] / 1e3),
+                    "optimum": r.OptimalValue, "limit": r.Limit,
+                    "wins": bool(s != "base" and r.Limit is None and last["base"].Limit is None and st["median"] < base["min"])}
+        rec[fs] = d
+    return rec
+
+
 def main():
     args = sys.argv[1:]
-    only, max_nodes, node_form, flag_sets, divers, widths = None, 0, None, None, None, None
-    for flag in ("--model", "--max-nodes", "--node-form", "--flag-sets", "--divers", "--compare-divers"):
+    only, max_nodes, node_form, flag_sets, divers, widths, plunge, depths = None, 0, None, None, None, None, None, None
+    for flag in ("--model", "--max-nodes", "--node-form", "--flag-sets", "--divers", "--compare-divers", "--plunge", "--compare-plunge"):
         if flag in args:
             k = args.index(flag)
             if flag == "--model":
@@ -199,6 +258,10 @@ def main():
                 divers = int(args[k + 1])
             elif flag == "--compare-divers":
                 widths = [int(w) for w in args[k + 1].split(",") if w]
+            elif flag == "--plunge":
+                plunge = int(args[k + 1])
+            elif flag == "--compare-plunge":
+                depths = [int(w) for w in args[k + 1].split(",") if w]
             else:
                 max_nodes = int(args[k + 1])
             del args[k:k + 2]
@@ -210,7 +273,16 @@ def main():
     L._lib.check(lib.lpx_init(0))
     out = {}
     if flag_sets is None:
-        flag_sets = "plain,both" if widths else "plain,long_step,cutoff,both"
+        flag_sets = "plain,both" if widths or depths else "plain,long_step,cutoff,both"
+    if depths:
+        for name, n, m in models():
+            if only is None or name == only:
+                out[name] = compare_plunge(n, m, reps, max_nodes, [f for f in flag_sets.split(",") if f and f != "none"],
+                                           divers if divers else 1, depths)
+        print(json.dumps(out))
+        return
+    if plunge is not None and divers is None:
+        divers = 1
     if widths:
         for name, n, m in models():
             if only is None or name == only:
@@ -241,7 +313,7 @@ def main():
         def run_bounded():
             t0 = time.perf_counter()
             try:
-                r = L.LPSolver().SolveBnbBounded(bnd_p, 1.0, max_nodes=max_nodes, node_form=node_form, divers=divers)
+                r = L.LPSolver().SolveBnbBounded(bnd_p, 1.0, max_nodes=max_nodes, node_form=node_form, divers=divers, plunge=plunge)
             except L.SolverException as e:
                 if e.code != L._lib.ITER_LIMIT or not max_nodes:
                     raise
@@ -250,8 +322,9 @@ def main():
 
         if trace_only:
             ms, rb = run_bounded()
-            out[name] = {"node_form": node_form, "divers": divers, "ms": ms, "nodes": int(rb.Nodes), "events": rb.BnbInfo["events"],
-                         "rounds": rb.BnbInfo.get("rounds")}
+            out[name] = {"node_form": node_form, "divers": divers, "plunge": plunge, "ms": ms, "nodes": int(rb.Nodes),
+                         "events": rb.BnbInfo["events"], "rounds": rb.BnbInfo.get("rounds"), "launched": rb.BnbInfo.get("launched"),
+                         "dropped": rb.BnbInfo.get("dropped")}
             continue
         base = device_used_mb()
         ta, tb, na, nb = [], [], [], []

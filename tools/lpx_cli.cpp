@@ -1,7 +1,7 @@
 // lpx_cli -- Linux stand-in for the reference's WinForms host (Form1.cs), over the C ABI of liblpx.so only.
 //
 //   lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]
-//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W]] [--export FILE] INPUT.txt
+//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D]] [--export FILE] INPUT.txt
 //
 // Does what Form1 does around the solvers: reads the model text (Import, Form1.cs:284-296), parses it with the LPParser
 // grammar (lpx_parse_text, Models/LPParser.cs:9-79), runs the algorithm chosen by its dropdown name (btnSolve_Click,
@@ -79,6 +79,7 @@ int main(int argc, char** argv)
     int search_flags = 0;       // --long-step / --cutoff beside --bnb-bounded
     int node_form = -1;         // --node-form beside --bnb-bounded: LPX_NODE_*; -1 = not given
     int divers = 0;             // --divers W beside --bnb-bounded: the search by W divers (lpx_solve_bnb_bounded4); 0 = not given
+    int plunge = 0;             // --plunge D beside --bnb-bounded: up to D nodes per diver and launch (lpx_solve_bnb_bounded5); 0 = not given
     struct Bound { bool upper; int index; double value; std::string text; };
     std::vector<Bound> bounds;
     lpx_cut_opts co; lpx_default_cut_opts(&co);
@@ -102,6 +103,13 @@ int main(int argc, char** argv)
             const long w = std::strtol(v.c_str(), &end, 10);
             if (end == v.c_str() || *end || w < 1 || w > 1024) { std::fprintf(stderr, "lpx_cli: --divers takes a count in [1, 1024], got '%s'\n", v.c_str()); return 64; }
             divers = (int)w;
+        }
+        else if (a == "--plunge" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            char* end = nullptr;
+            const long d = std::strtol(v.c_str(), &end, 10);
+            if (end == v.c_str() || *end || d < 1 || d > 64) { std::fprintf(stderr, "lpx_cli: --plunge takes a depth in [1, 64], got '%s'\n", v.c_str()); return 64; }
+            plunge = (int)d;
         }
         else if ((a == "--upper" || a == "--lower") && i + 1 < argc) {
             const std::string v = argv[++i];
@@ -139,7 +147,7 @@ int main(int argc, char** argv)
         else if (a == "--export" && i + 1 < argc) exportPath = argv[++i];
         else if (a == "--help" || a == "-h") {
             std::printf("usage: lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]\n"
-                        "               [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W]]\n"
+                        "               [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D]]\n"
                         "               [--export FILE] INPUT.txt\n"
                         "  NAME: Primal Simplex | Revised Primal Simplex | Dual Simplex | Branch and Bound |\n"
                         "        Revised Branch and Bound | Branch and Bound Knapsack | Cutting Plane | Revised Cutting Plane |\n"
@@ -157,6 +165,8 @@ int main(int argc, char** argv)
                         "             launches of lpx_bounded_node2, in one launch with the tableau on chip, or on chip iff it fits\n"
                         "  --divers W: with --bnb-bounded, the search by W handles diving at once, one on-chip node per diver and one kernel\n"
                         "             launch per round (lpx_solve_bnb_bounded4); not with --node-form launches\n"
+                        "  --plunge D: with --bnb-bounded, a diver goes on from a node that branches into its ceil child, up to D nodes per\n"
+                        "             launch with the tableau staying on chip (lpx_solve_bnb_bounded5); without --divers it means --divers 1\n"
                         "  --set-rhs I=V, --set-cost J=V: after the solve, b_I = V / c_J = V (1-based, repeatable), applied in order,\n"
                         "             each re-optimised warm on the device from the previous basis; each re-solve's summary is printed\n");
             return 0;
@@ -172,6 +182,9 @@ int main(int argc, char** argv)
     if (search_flags && !bnb_bounded) { std::fprintf(stderr, "lpx_cli: --long-step / --cutoff need --bnb-bounded\n"); return 64; }
     if (node_form >= 0 && !bnb_bounded) { std::fprintf(stderr, "lpx_cli: --node-form needs --bnb-bounded\n"); return 64; }
     if (divers && !bnb_bounded) { std::fprintf(stderr, "lpx_cli: --divers needs --bnb-bounded\n"); return 64; }
+    if (plunge && !bnb_bounded) { std::fprintf(stderr, "lpx_cli: --plunge needs --bnb-bounded\n"); return 64; }
+    if (plunge && node_form == LPX_NODE_LAUNCHES) { std::fprintf(stderr, "lpx_cli: --plunge evaluates every node on chip: not with --node-form launches\n"); return 64; }
+    if (plunge && !divers) divers = 1;
     if (divers && node_form == LPX_NODE_LAUNCHES) { std::fprintf(stderr, "lpx_cli: --divers evaluates every node on chip: not with --node-form launches\n"); return 64; }
     if (bounded) {
         if (ranging) { std::fprintf(stderr, "lpx_cli: --upper / --lower / --binary do not combine with --ranging\n"); return 64; }
@@ -202,7 +215,8 @@ int main(int argc, char** argv)
         if (bd.index >= p.n) { std::fprintf(stderr, "lpx_cli: %s: index out of range\n", bd.text.c_str()); lpx_parsed_free(&p); return 64; }
         (bd.upper ? up : lo)[bd.index] = bd.value;
     }
-    const int rc = bnb_bounded && divers ? lpx_solve_bnb_bounded4(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, &r, nullptr, nullptr)
+    const int rc = bnb_bounded && plunge ? lpx_solve_bnb_bounded5(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, plunge, &r, nullptr, nullptr, nullptr)
+                 : bnb_bounded && divers ? lpx_solve_bnb_bounded4(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, &r, nullptr, nullptr)
                  : bnb_bounded && node_form >= 0 ? lpx_solve_bnb_bounded3(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, node_form, &r, nullptr)
                  : bnb_bounded && search_flags ? lpx_solve_bnb_bounded2(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, &r, nullptr)
                  : bnb_bounded ? lpx_solve_bnb_bounded(&prob, lo.data(), up.data(), nullptr, &o, 0, &r, nullptr)
