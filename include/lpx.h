@@ -1098,6 +1098,98 @@ int  lpx_solve_bnb_bounded5(const lpx_problem* p, const double* lower /* [n] or 
                             lpx_bnb_plunge_info* pinfo /* or NULL */);
 void lpx_bnb_plunge_info_free(lpx_bnb_plunge_info* pinfo);
 
+/* -- strong branching by on-chip probes (kernel: csrc/lpx_bounded_probe.hip; host: csrc/lpx_tableau_bounded.cpp,
+ * csrc/lpx_node_batch.cpp, csrc/host/bnb_bounded.cpp) --
+ * A PROBE evaluates one child of a solved node on a private copy and reports how the child ends; the handle is only read.  One
+ * launch of a grid of (2 * cand_max, B) independent workgroups probes up to cand_max candidates of B handles, both children each.
+ *
+ * lpx_bounded_probe(t, o, flags, cutoff, prune, nint, is_int, tol, cand_max, probe_iter, head, out): probes handle t AS IT STANDS,
+ * one launch and one wait.  NOTHING of the handle changes: tableau, bounds, lower shifts, flip states, basis, RHS copy, state
+ * record, trace and counts read the same before and after.  The handle must have bounds and fit the on-chip form of the node
+ * (lpx_bounded_node_fits).
+ *   Nothing to probe: head = {0, 0, T[m,Cm]} and every out[w].status = LPX_PROBE_NONE when the handle's loop state (the status
+ *   its last run or node left on the device) is not LPX_OPTIMAL, or when T[m,Cm] <= prune (prune = -inf: never).
+ *   Candidates: x_j and its fraction f for j < nint exactly as lpx_tableau_branch_pick forms them (mask, tol, lo where the handle
+ *   has stored one); the candidates are ordered by (|f - 0.5| ascending, j ascending), with comparisons only.  head.candidates
+ *   is their number, head.count = min(candidates, cand_max) of them are probed, head.z = T[m,Cm].
+ *   out[2 c + d] is the probe of candidate c (in that order), direction d: d = 0 the floor child [lo[j], floor(x_j)], d = 1 the
+ *   ceil child [ceil(x_j), lo[j] + ub[j]] (one addition).  Records with c >= count have status LPX_PROBE_NONE.
+ *   The record {status, events, kind0, kind1, flips, z} is bit-equal to what
+ *   lpx_bounded_node3(clone, 1, {var}, {lower}, {upper}, o with max_iter = probe_iter, flags, cutoff, ..., LPX_NODE_ONCHIP) reports
+ *   on an lpx_tableau_clone of the handle; var, dir, x_var, lower, upper say which call that is.  A child that call refuses
+ *   (LPX_EINVAL: upper below lower, which needs a bound that is not integral; an unrepairable column) has status -1 and zeros.  probe_iter = 0 gives LPX_ITER_LIMIT with no event.
+ *   LPX_EINVAL before any device check, the handle untouched, every message starting "lpx_bounded_probe:": a NULL t, head or out;
+ *   cand_max outside [1, 32]; probe_iter < 0; a NaN prune; an unknown flag; a NaN cutoff with LPX_BDUAL_CUTOFF; nint outside
+ *   [0, C-1]; tol outside [0, 0.5); no bounds; resident = 1; a negative or NaN eps; a shape that does not fit.  No device:
+ *   LPX_EDEVICE; there is no host fallback.
+ *
+ * lpx_node_batch_run_probe(b, B, slot, K, cols, lower, upper, o, flags, cutoff, prune, nint, is_int, tol, cand_max, probe_iter,
+ * out, head, probes, rc): the launch of lpx_node_batch_run and, behind it on the same stream, the probe launch on the same
+ * entries, with ONE wait for both.  out and rc are lpx_node_batch_run's, bit for bit, and so is every handle afterwards; head[i]
+ * and probes[i * 2 * cand_max + w] are what lpx_bounded_probe(handles[slot[i]], o, flags, cutoff[i], prune[i], ...) gives on the
+ * handle after its node.  An entry whose node the kernel refused has head {0, 0, z as it stands} and no probe.  The probes share
+ * the node's flags and o (max_iter replaced by probe_iter).  Errors: those of lpx_node_batch_run under the new name, plus a NULL
+ * prune, head or probes, cand_max outside [1, 32], probe_iter < 0 and "entry i: prune is NaN".
+ *
+ * lpx_solve_bnb_bounded6(p, lower, upper, is_int, o, max_nodes, search_flags, divers, branching, cand_max, probe_iter, out, info,
+ * dinfo, sinfo): the search of lpx_solve_bnb_bounded4 with a branching rule.  branching = LPX_BRANCH_MOST_FRACTIONAL is
+ * lpx_solve_bnb_bounded4 bit for bit, with no probe launch (cand_max and probe_iter are still checked).  branching =
+ * LPX_BRANCH_STRONG changes two steps of its round:
+ *   4. Evaluate: ONE lpx_node_batch_run_probe, every entry with prune = best + 1e-6 as best stands at the start of the round (and
+ *      cutoff = that value under LPX_BDUAL_CUTOFF), flags = LPX_BDUAL_SKIP_FIXED | search_flags for nodes and probes alike.
+ *   5. Decide: as lpx_solve_bnb_bounded4 up to the point where a node branches.  If its head.count >= 1, with z the node's z:
+ *      gain of a probe = 1e12 if it ended LPX_INFEASIBLE or LPX_CUTOFF, 1e-6 if it was refused (status -1), else
+ *      min(max(z - z_probe, 1e-6), 1e12) (LPX_ITER_LIMIT included).  score of a candidate = gain_floor * gain_ceil.  The
+ *      branching variable is the candidate of the FIRST maximum score in candidate order, x_var its value; the children are
+ *      formed from it as before.  A child is DEAD if its probe ended LPX_INFEASIBLE or LPX_CUTOFF, or ended LPX_OPTIMAL with
+ *      z_probe <= best + 1e-6, best as it stands at this decision.  A dead child is not pushed; it counts in pruned_by_probe and
+ *      not in nodes.  The live children are pushed floor first, so the ceil child is explored first.  The log's var is the
+ *      chosen variable.  head.count = 0 on a branching node: the rule of lpx_solve_bnb_bounded4.
+ *   sinfo: probe_launches (rounds with a probe launch), probes (records that ran: status != LPX_PROBE_NONE), probe_events (the sum
+ *   of their events), probe_limit (those that ended LPX_ITER_LIMIT), pruned_by_probe, changed_picks (branching nodes whose
+ *   variable differs from candidate 0, the pick of lpx_tableau_branch_pick).  Plain counters: lpx_bnb_strong_info_free zeroes it.
+ *   LPX_EINVAL before any device check: those of lpx_solve_bnb_bounded4 under the new name, branching outside {0, 1}, cand_max
+ *   outside [1, 32], probe_iter < 0.  The result is a function of the model, the options, the flags, W, cand_max and probe_iter.
+ *   The rule visits other nodes than lpx_solve_bnb_bounded4, so what that entry says about a node that makes max_iter events
+ *   holds here for other searches: binary_ip(128, 64) with both flags, W = 1, cand_max = 4 and ample probes ends that way
+ *   (DESIGN.md section 4.20). */
+#define LPX_PROBE_NONE (-2)
+#define LPX_BRANCH_MOST_FRACTIONAL 0
+#define LPX_BRANCH_STRONG 1
+typedef struct lpx_probe_head {          /* 16 bytes */
+    int32_t count;         /* candidates probed: min(candidates, cand_max); 0 = nothing was probed */
+    int32_t candidates;    /* fractional integer columns */
+    double z;              /* T[m,Cm] of the handle */
+} lpx_probe_head;
+typedef struct lpx_probe_record {        /* 64 bytes */
+    int32_t status;        /* LPX_OPTIMAL / LPX_INFEASIBLE / LPX_ITER_LIMIT / LPX_CUTOFF; -1 = refused; LPX_PROBE_NONE = no probe */
+    int32_t events, kind0, kind1;        /* events of the child's dual loop, and its pivots per kind */
+    int32_t flips;         /* dual-feasibility flips of the child */
+    int32_t var, dir;      /* column; 0 = floor child, 1 = ceil child */
+    int32_t pad;
+    double x_var;          /* value of the column at the node */
+    double lower, upper;   /* the child's bounds on it, as lpx_bounded_node3 takes them */
+    double z;              /* T[m,Cm] of the child where its loop stopped */
+} lpx_probe_record;
+typedef struct lpx_bnb_strong_info {     /* 48 bytes */
+    int64_t probe_launches, probes, probe_events, probe_limit, pruned_by_probe, changed_picks;
+} lpx_bnb_strong_info;
+int  lpx_bounded_probe(lpx_tableau* t, const lpx_run_opts* o, int flags, double cutoff, double prune,
+                       int nint, const uint8_t* is_int /* [nint] or NULL = all */, double tol, int cand_max /* 1..32 */,
+                       int probe_iter, lpx_probe_head* head, lpx_probe_record* out /* [2*cand_max] */);
+int  lpx_node_batch_run_probe(lpx_node_batch* b, int B, const int32_t* slot /* [B] */, const int32_t* K /* [B] */,
+                              const int32_t* cols, const double* lower, const double* upper /* concatenated, sum of K */,
+                              const lpx_run_opts* o, int flags, const double* cutoff /* [B]; read only with LPX_BDUAL_CUTOFF */,
+                              const double* prune /* [B] */, int nint, const uint8_t* is_int /* [nint] or NULL = all */, double tol,
+                              int cand_max /* 1..32 */, int probe_iter, lpx_node_record* out /* [B] */, lpx_probe_head* head /* [B] */,
+                              lpx_probe_record* probes /* [B*2*cand_max], entry-major */, int32_t* rc /* [B] */);
+int  lpx_solve_bnb_bounded6(const lpx_problem* p, const double* lower /* [n] or NULL = 0 */, const double* upper /* [n] */,
+                            const uint8_t* is_int /* [n] or NULL = all */, const lpx_solve_opts* o, int64_t max_nodes /* 0 = none */,
+                            int search_flags, int divers /* W, 1..1024 */, int branching, int cand_max /* 1..32 */, int probe_iter,
+                            lpx_result* out, lpx_bnb_bounded_info* info /* or NULL */, lpx_bnb_divers_info* dinfo /* or NULL */,
+                            lpx_bnb_strong_info* sinfo /* or NULL */);
+void lpx_bnb_strong_info_free(lpx_bnb_strong_info* sinfo);
+
 #ifdef __cplusplus
 }
 #endif

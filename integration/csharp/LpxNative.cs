@@ -130,6 +130,26 @@ namespace Linear_Programming_Solver.Native
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public struct LpxProbeHead                   // lpx_probe_head: 16 bytes
+    {
+        public int count, candidates;            // candidates probed (0 = nothing was probed) of how many fractional integer columns
+        public double z;                         // T[m,Cm] of the handle
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct LpxProbeRecord                 // lpx_probe_record: 64 bytes; status -1 = refused, -2 (LPX_PROBE_NONE) = no probe
+    {
+        public int status, events, kind0, kind1, flips, var, dir, pad;      // dir: 0 = floor child, 1 = ceil child
+        public double x_var, lower, upper, z;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct LpxBnbStrongInfo               // lpx_bnb_strong_info: 48 bytes of counters (lpx_bnb_strong_info_free zeroes them)
+    {
+        public long probe_launches, probes, probe_events, probe_limit, pruned_by_probe, changed_picks;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public unsafe struct LpxBoundedInfo          // lpx_bounded_info  (lpx_solve_bounded; free with lpx_bounded_info_free)
     {
         public int ncols, n;
@@ -336,6 +356,21 @@ namespace Linear_Programming_Solver.Native
                                                         long max_nodes, int search_flags, int divers, int plunge, out LpxResult result,
                                                         out LpxBnbBoundedInfo info, out LpxBnbDiversInfo dinfo, out LpxBnbPlungeInfo pinfo);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern void lpx_bnb_plunge_info_free(ref LpxBnbPlungeInfo pinfo);
+        // strong branching by probes: records is [2 * cand_max] / [B * 2 * cand_max], entry-major; branching 0 = most fractional, 1 = strong
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_bounded_probe(IntPtr tableau, IntPtr opts, int flags, double cutoff, double prune, int nint, byte* is_int,
+                                                   double tol, int cand_max, int probe_iter, out LpxProbeHead head, LpxProbeRecord* records);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_node_batch_run_probe(IntPtr batch, int B, int* slot, int* K, int* cols, double* lower, double* upper, IntPtr opts,
+                                                          int flags, double* cutoff, double* prune, int nint, byte* is_int, double tol,
+                                                          int cand_max, int probe_iter, LpxNodeRecord* records, LpxProbeHead* heads,
+                                                          LpxProbeRecord* probes, int* rc);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_bnb_bounded6(ref LpxProblem p, double* lower, double* upper, byte* is_int, ref LpxSolveOpts o,
+                                                        long max_nodes, int search_flags, int divers, int branching, int cand_max,
+                                                        int probe_iter, out LpxResult result, out LpxBnbBoundedInfo info,
+                                                        out LpxBnbDiversInfo dinfo, out LpxBnbStrongInfo sinfo);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern void lpx_bnb_strong_info_free(ref LpxBnbStrongInfo sinfo);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_solve_bounded_dual(ref LpxProblem p, double* lower, double* upper, int flags, ref LpxSolveOpts o,
                                                         out LpxResult result, out LpxBoundedInfo info);

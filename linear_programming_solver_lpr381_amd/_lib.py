@@ -144,6 +144,29 @@ class BnbPlungeInfo(C.Structure):
     _fields_ = [("launched", C.c_int64), ("dropped", C.c_int64), ("longest_chain", C.c_int64), ("step", ip)]
 
 
+PROBE_NONE = -2
+BRANCH_MOST_FRACTIONAL, BRANCH_STRONG = 0, 1
+BRANCHINGS = {"most_fractional": BRANCH_MOST_FRACTIONAL, "strong": BRANCH_STRONG}
+
+
+class ProbeHead(C.Structure):
+    """lpx_probe_head (include/lpx.h): how many candidates a probe launch evaluated on one handle, of how many, and the node's z."""
+    _fields_ = [("count", C.c_int32), ("candidates", C.c_int32), ("z", C.c_double)]
+
+
+class ProbeRecord(C.Structure):
+    """lpx_probe_record (include/lpx.h): one child of one candidate as its probe left it."""
+    _fields_ = [("status", C.c_int32), ("events", C.c_int32), ("kind0", C.c_int32), ("kind1", C.c_int32), ("flips", C.c_int32),
+                ("var", C.c_int32), ("dir", C.c_int32), ("pad", C.c_int32), ("x_var", C.c_double), ("lower", C.c_double),
+                ("upper", C.c_double), ("z", C.c_double)]
+
+
+class BnbStrongInfo(C.Structure):
+    """lpx_bnb_strong_info (include/lpx.h): the probe counters of lpx_solve_bnb_bounded6."""
+    _fields_ = [("probe_launches", C.c_int64), ("probes", C.c_int64), ("probe_events", C.c_int64), ("probe_limit", C.c_int64),
+                ("pruned_by_probe", C.c_int64), ("changed_picks", C.c_int64)]
+
+
 class Parsed(C.Structure):
     _fields_ = [("sense", C.c_int), ("n", C.c_int), ("m", C.c_int), ("c", dp), ("A", dp), ("rel", ip),
                 ("b", dp), ("ragged", C.c_int)]
@@ -342,6 +365,15 @@ def lib() -> C.CDLL:
                                          C.POINTER(BnbPlungeInfo)]
     L.lpx_bnb_plunge_info_free.argtypes = [C.POINTER(BnbPlungeInfo)]
     L.lpx_bnb_plunge_info_free.restype = None
+    L.lpx_bounded_probe.argtypes = [vp, C.POINTER(RunOpts), C.c_int, C.c_double, C.c_double, C.c_int, u8p, C.c_double, C.c_int, C.c_int,
+                                    C.POINTER(ProbeHead), C.POINTER(ProbeRecord)]
+    L.lpx_node_batch_run_probe.argtypes = [vp, C.c_int, ip, ip, ip, dp, dp, C.POINTER(RunOpts), C.c_int, dp, dp, C.c_int, u8p, C.c_double,
+                                           C.c_int, C.c_int, C.POINTER(NodeRecord), C.POINTER(ProbeHead), C.POINTER(ProbeRecord), ip]
+    L.lpx_solve_bnb_bounded6.argtypes = [C.POINTER(Problem), dp, dp, u8p, C.POINTER(SolveOpts), C.c_int64, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, C.POINTER(Result), C.POINTER(BnbBoundedInfo), C.POINTER(BnbDiversInfo),
+                                         C.POINTER(BnbStrongInfo)]
+    L.lpx_bnb_strong_info_free.argtypes = [C.POINTER(BnbStrongInfo)]
+    L.lpx_bnb_strong_info_free.restype = None
     L.lpx_solve_bounded_dual.argtypes = [C.POINTER(Problem), dp, dp, C.c_int, C.POINTER(SolveOpts), C.POINTER(Result),
                                          C.POINTER(BoundedInfo)]
     L.lpx_parse_text.argtypes = [C.c_char_p, C.POINTER(Parsed)]

@@ -7,6 +7,7 @@
 // to 0.5 :197-213).  Its IsFeasible re-check of an incumbent is not mirrored: the dual loop ends primal feasible by construction.
 #include "model.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -159,10 +160,18 @@ SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<doubl
 // current bounds and its own depth-first stack; a round steals for the idle divers, pops one node per diver, evaluates them all
 // in ONE lpx_node_batch_run and decides the records in diver order.  Everything around the search is SolveBnbBounded's.  The
 // order of the steps is part of the contract: the log is a function of the model, the options, the flags and W alone.
+// With `strong` it is the search of lpx_solve_bnb_bounded6(LPX_BRANCH_STRONG): the same rounds with probes behind the nodes.
 SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
-                             int search_flags, int divers, BnbDiversInfo& dinfo)
+                             int search_flags, int divers, BnbDiversInfo& dinfo, const BnbStrong* strong, BnbStrongInfo* sinfo)
 {
+    // strong != null (lpx_solve_bnb_bounded6 with LPX_BRANCH_STRONG): the evaluate step is ONE lpx_node_batch_run_probe and the
+    // decide step takes the variable and drops the dead children by the probes; everything else is the search below, unchanged.
+    BnbStrongInfo sdummy;
+    BnbStrongInfo& si = sinfo ? *sinfo : sdummy;
+    si = BnbStrongInfo();
+    if (strong && (strong->cand_max < 1 || strong->cand_max > 32)) throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: cand_max is outside [1, 32]");
+    if (strong && strong->probe_iter < 0) throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: probe_iter is negative");
     const int n = original.NumVars();
     if ((!lower.empty() && (int)lower.size() != n) || (!upper.empty() && (int)upper.size() != n))
         throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: lower / upper need one entry per variable");
@@ -228,6 +237,16 @@ SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double
     std::vector<double> best_x;
     std::vector<int32_t> slot, Ks, cols, rcs((size_t)W); std::vector<double> clo, cub, cutoffs;
     std::vector<lpx_node_record> recs((size_t)W);
+    std::vector<double> prunes; std::vector<lpx_probe_head> heads; std::vector<lpx_probe_record> probes;       // strong branching only
+    // the gain of a probe against its node's z, and whether the child it stands for is dead against best as it stands
+    auto gain = [](const lpx_probe_record& q, double z) {
+        if (q.status == LPX_INFEASIBLE || q.status == LPX_CUTOFF) return 1e12;
+        if (q.status < 0) return 1e-6;
+        return std::min(std::max(z - q.z, 1e-6), 1e12);
+    };
+    auto dead = [](const lpx_probe_record& q, double best_now) {
+        return q.status == LPX_INFEASIBLE || q.status == LPX_CUTOFF || (q.status == LPX_OPTIMAL && q.z <= best_now + EPS);
+    };
     auto any_open = [&] { for (const Diver& d : dv) if (!d.stack.empty()) return true; return false; };
     bool stop = false;
     while (!stop && any_open()) {
@@ -265,9 +284,25 @@ SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double
         }
         // 4. evaluate
         const int B = (int)slot.size();
-        const int rc = lpx_node_batch_run(pool.batch, B, slot.data(), Ks.data(), cols.data(), clo.data(), cub.data(), &o,
-                                          LPX_BDUAL_SKIP_FIXED | search_flags, cutoffs.data(), n, mask, EPS, recs.data(), rcs.data());
+        int rc;
+        if (strong) {
+            prunes.assign((size_t)B, best + EPS);
+            heads.resize((size_t)B); probes.resize((size_t)B * 2 * (size_t)strong->cand_max);
+            rc = lpx_node_batch_run_probe(pool.batch, B, slot.data(), Ks.data(), cols.data(), clo.data(), cub.data(), &o,
+                                          LPX_BDUAL_SKIP_FIXED | search_flags, cutoffs.data(), prunes.data(), n, mask, EPS,
+                                          strong->cand_max, strong->probe_iter, recs.data(), heads.data(), probes.data(), rcs.data());
+        } else
+            rc = lpx_node_batch_run(pool.batch, B, slot.data(), Ks.data(), cols.data(), clo.data(), cub.data(), &o,
+                                    LPX_BDUAL_SKIP_FIXED | search_flags, cutoffs.data(), n, mask, EPS, recs.data(), rcs.data());
         if (rc < 0) throw_lib(rc);
+        if (strong) {
+            si.probe_launches++;
+            for (const lpx_probe_record& q : probes) {
+                if (q.status == LPX_PROBE_NONE) continue;
+                si.probes++; si.probe_events += q.events;
+                if (q.status == LPX_ITER_LIMIT) si.probe_limit++;
+            }
+        }
         for (int i = 0; i < B; ++i) if (rcs[i] < 0) throw_lib(rcs[i]);
         const int32_t round = (int32_t)dinfo.rounds++;
         if (B > dinfo.largest_batch) dinfo.largest_batch = B;
@@ -304,12 +339,28 @@ SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double
                 info.incumbents++;
                 continue;
             }
-            const int v = rec.pick.var;
+            int v = rec.pick.var;
+            double xv = rec.pick.x_var;
+            bool push_fl = true, push_ce = true;
+            if (strong && heads[i].count >= 1) {
+                const lpx_probe_record* pr = &probes[(size_t)i * 2 * (size_t)strong->cand_max];
+                int pick = 0;
+                double top = -1.0;
+                for (int c = 0; c < heads[i].count; ++c) {
+                    const double score = gain(pr[2 * c], z) * gain(pr[2 * c + 1], z);
+                    if (score > top) { top = score; pick = c; }         // the first maximum
+                }
+                v = pr[2 * pick].var; xv = pr[2 * pick].x_var;
+                if (pick != 0) si.changed_picks++;
+                push_fl = !dead(pr[2 * pick], best); push_ce = !dead(pr[2 * pick + 1], best);
+                si.pruned_by_probe += (push_fl ? 0 : 1) + (push_ce ? 0 : 1);
+                info.log.back().var = v;
+            }
             Node fl{node.depth + 1, node.path}, ce{node.depth + 1, node.path};
-            fl.path.push_back(Override{v, D.nb_lo[v], std::floor(rec.pick.x_var)});
-            ce.path.push_back(Override{v, std::ceil(rec.pick.x_var), D.nb_ub[v]});
-            D.stack.push_back(std::move(fl));
-            D.stack.push_back(std::move(ce));
+            fl.path.push_back(Override{v, D.nb_lo[v], std::floor(xv)});
+            ce.path.push_back(Override{v, std::ceil(xv), D.nb_ub[v]});
+            if (push_fl) D.stack.push_back(std::move(fl));
+            if (push_ce) D.stack.push_back(std::move(ce));
         }
     }
 

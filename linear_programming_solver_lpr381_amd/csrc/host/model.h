@@ -249,9 +249,14 @@ SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<doubl
                               int node_form = -1);        // lpx_solve_bnb_bounded3: LPX_NODE_* of every node call; -1: the calls of _bounded / _bounded2
 // The search by W divers (lpx_solve_bnb_bounded4): every node on chip, one lpx_node_batch_run per round.
 struct BnbDiversInfo { int64_t rounds = 0, steals = 0, largest_batch = 0; std::vector<int32_t> round, diver; };
+// Strong branching (lpx_solve_bnb_bounded6 with LPX_BRANCH_STRONG): SolveBnbDivers whose round is ONE lpx_node_batch_run_probe and
+// whose decide step chooses the variable, and drops the dead children, by the probes of up to cand_max candidates.
+struct BnbStrong { int cand_max = 4, probe_iter = 0; };
+struct BnbStrongInfo { int64_t probe_launches = 0, probes = 0, probe_events = 0, probe_limit = 0, pruned_by_probe = 0, changed_picks = 0; };
 SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
-                             int search_flags, int divers, BnbDiversInfo& dinfo);
+                             int search_flags, int divers, BnbDiversInfo& dinfo, const struct BnbStrong* strong = nullptr,
+                             struct BnbStrongInfo* sinfo = nullptr);
 // The search by W divers that plunge (lpx_solve_bnb_bounded5): one lpx_node_batch_plunge per round, up to `plunge` nodes per diver.
 struct BnbPlungeInfo { int64_t launched = 0, dropped = 0, longest_chain = 0; std::vector<int32_t> step; };
 SimplexResult SolveBnbPlunge(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,

@@ -77,9 +77,14 @@ struct lpx_tableau {
         // the plunge (lpx_node_batch_plunge): whole[j] = 1 iff the host has seen column j's bounds and both are finite and integral
         // (lpx_tableau_set_bounds and every accepted bound edit keep it; empty: nothing known).  Host knowledge only, no device copy.
         std::vector<uint8_t> whole, snap_whole;
+        // the probes (lpx_bounded_probe): the device workspace of the private basis / flip copies and the pinned slab of the
+        // parameter record, the head and the records, each grown to twice the need
+        char* probews = nullptr; size_t probews_bytes = 0;
+        char* probeio = nullptr; size_t probeio_bytes = 0;
 
         void free()
         {
+            hipFree(probews); if (probeio) hipHostFree(probeio);
             hipFree(ub); hipFree(flip); hipFree(snapUb); hipFree(snapFlip);
             hipFree(lo); hipFree(snapLo); hipFree(chg);
             hipFree(dzl); hipFree(pickrec); hipFree(pickmask); if (nodeslab) hipHostFree(nodeslab); hipFree(cutoff);
@@ -111,6 +116,14 @@ void node_onchip_commit(lpx_tableau* t, const NodeOut* rec, bool any_lo, lpx_nod
 // an accepted bound edit, for Bounds::whole: which of the edited columns now have finite integral bounds
 void bounds_note_edit(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper);
 int bounded_plunge_ready(const char* what);     // the one-time attribute of the plunge kernel
+// the probes (lpx_bounded_probe.hip), shared by lpx_bounded_probe and lpx_node_batch_run_probe
+int bounded_probe_ready(const char* what);      // the one-time attribute of the probe kernel
+int check_probe_args(int cand_max, int probe_iter, const char* what);      // LPX_EINVAL with `what` in front, no device
+size_t probe_ws_bytes(const lpx_tableau* t, int cand_max);                 // the workspace of one entry: 2 * cand_max slices
+// the parameter record of one entry on handle t as it will stand when the launch runs (lo_used: then); ws: its workspace
+void probe_params(const lpx_tableau* t, const lpx_run_opts* o, int flags, double cutoff, double prune, int nint, const uint8_t* mask_dev,
+                  double tol, int cand_max, int probe_iter, bool lo_used, char* ws, const NodeOut* front, lpx_probe_head* head,
+                  lpx_probe_record* rec, ProbeParams* p);
 
 static constexpr int LPX_RESIDENT_RETRY = -1000;     // internal: first resident launch timed out, state untouched
 

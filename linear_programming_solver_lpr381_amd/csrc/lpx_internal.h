@@ -124,6 +124,23 @@ hipError_t launch_bounded_nodes_onchip(const NodeParams* P, int B, size_t lds, h
 struct PlungeParams { NodeParams n; double prune; int32_t* steps; int32_t depth, pad; };
 hipError_t bounded_plunge_init();                   // one-time function attribute
 hipError_t launch_bounded_plunge_onchip(const PlungeParams* P, int B, size_t lds, hipStream_t s);
+// the probes (lpx_bounded_probe.hip): workgroup (w, e) evaluates child w of entry P[e]'s handle as it stands and writes rec[w];
+// workgroup (0, e) writes *head.  Everything of the handle is read only.  front: the record of the node launched in front of the
+// probes on the same stream (status < 0: refused, nothing is probed), or null.  wbasis / wflip: 2 * cand_max slices of the
+// workspace, wbasis_stride int32 / wflip_stride bytes apart.
+struct ProbeParams {
+    const double* T; int ld, R, C;       // R, C: the LIVE shape
+    const int32_t* basis; const DevState* st;
+    const double* ub; const double* lo; const uint8_t* flip;
+    const uint8_t* mask;                 // [nint] device copy of the integer mask (read when has_mask)
+    const NodeOut* front;
+    int32_t* wbasis; uint8_t* wflip; int32_t wbasis_stride, wflip_stride;
+    lpx_probe_head* head; lpx_probe_record* rec;
+    double eps, ratio_tol, cutoff, tol, prune;
+    int32_t flags, nint, has_mask, lo_used, probe_iter, cand_max;
+};
+hipError_t bounded_probe_init();                    // one-time function attribute
+hipError_t launch_bounded_probe_onchip(const ProbeParams* P, int B, int cand_max, size_t lds, hipStream_t s);
 
 // ---- lpx_kernels.hip: the two-launch select and update paths
 hipError_t launch_select(const SelParams& p, hipStream_t s);       // gather-based (dual path)

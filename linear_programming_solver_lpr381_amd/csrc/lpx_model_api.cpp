@@ -372,13 +372,15 @@ void lpx_bounded_close(lpx_bounded_session* s) { delete s; }
 static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const double* upper, const uint8_t* is_int, const lpx_solve_opts* o,
                             int64_t max_nodes, int search_flags, lpx_result* out, lpx_bnb_bounded_info* info, const char* what,
                             int node_form = -1, int divers = 0, lpx_bnb_divers_info* dinfo = nullptr,     // divers > 0: lpx_solve_bnb_bounded4
-                            int plunge = 0, lpx_bnb_plunge_info* pinfo = nullptr)                         // plunge > 0: lpx_solve_bnb_bounded5
+                            int plunge = 0, lpx_bnb_plunge_info* pinfo = nullptr,                         // plunge > 0: lpx_solve_bnb_bounded5
+                            const BnbStrong* strong = nullptr, lpx_bnb_strong_info* sinfo = nullptr)      // strong: lpx_solve_bnb_bounded6, LPX_BRANCH_STRONG
 {
     if (!p || !out) { set_error(std::string(what) + ": null argument"); return LPX_EINVAL; }
     std::memset(out, 0, sizeof(*out));
     if (info) std::memset(info, 0, sizeof(*info));
     if (dinfo) std::memset(dinfo, 0, sizeof(*dinfo));
     if (pinfo) std::memset(pinfo, 0, sizeof(*pinfo));
+    if (sinfo) std::memset(sinfo, 0, sizeof(*sinfo));
     lpx_solve_opts d; if (!o) { lpx_default_solve_opts(&d); o = &d; }
     return guarded(what, [&]() -> int {
         EngineOptions e = to_engine(o);
@@ -391,10 +393,16 @@ static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const do
         BnbBoundedInfo bi;
         BnbDiversInfo di;
         BnbPlungeInfo pi;
-        SimplexResult r = plunge ? SolveBnbPlunge(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, plunge, di, pi)
+        BnbStrongInfo si;
+        SimplexResult r = strong ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di, strong, &si)
+                        : plunge ? SolveBnbPlunge(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, plunge, di, pi)
                         : divers ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di)
                                  : SolveBnbBounded(q, lo, up, mask, e, max_nodes, bi, search_flags, node_form);
         fill_result(out, r, p->n);
+        if (sinfo) {
+            sinfo->probe_launches = si.probe_launches; sinfo->probes = si.probes; sinfo->probe_events = si.probe_events;
+            sinfo->probe_limit = si.probe_limit; sinfo->pruned_by_probe = si.pruned_by_probe; sinfo->changed_picks = si.changed_picks;
+        }
         if (pinfo) {
             pinfo->launched = pi.launched; pinfo->dropped = pi.dropped; pinfo->longest_chain = pi.longest_chain;
             pinfo->step = dup_vec(pi.step);
@@ -453,6 +461,28 @@ int lpx_solve_bnb_bounded5(const lpx_problem* p, const double* lower, const doub
     if (plunge < 1 || plunge > 64) { set_error("lpx_solve_bnb_bounded5: plunge is outside [1, 64]"); return LPX_EINVAL; }
     return solve_bnb_bounded(p, lower, upper, is_int, o, max_nodes, search_flags, out, info, "lpx_solve_bnb_bounded5", -1, divers, dinfo,
                              plunge, pinfo);
+}
+
+int lpx_solve_bnb_bounded6(const lpx_problem* p, const double* lower, const double* upper, const uint8_t* is_int,
+                           const lpx_solve_opts* o, int64_t max_nodes, int search_flags, int divers, int branching, int cand_max,
+                           int probe_iter, lpx_result* out, lpx_bnb_bounded_info* info, lpx_bnb_divers_info* dinfo,
+                           lpx_bnb_strong_info* sinfo)
+{
+    if (divers < 1 || divers > 1024) { set_error("lpx_solve_bnb_bounded6: divers is outside [1, 1024]"); return LPX_EINVAL; }
+    if (branching != LPX_BRANCH_MOST_FRACTIONAL && branching != LPX_BRANCH_STRONG) {
+        set_error("lpx_solve_bnb_bounded6: branching is neither LPX_BRANCH_MOST_FRACTIONAL nor LPX_BRANCH_STRONG");
+        return LPX_EINVAL;
+    }
+    if (cand_max < 1 || cand_max > 32) { set_error("lpx_solve_bnb_bounded6: cand_max is outside [1, 32]"); return LPX_EINVAL; }
+    if (probe_iter < 0) { set_error("lpx_solve_bnb_bounded6: probe_iter is negative"); return LPX_EINVAL; }
+    BnbStrong st; st.cand_max = cand_max; st.probe_iter = probe_iter;
+    return solve_bnb_bounded(p, lower, upper, is_int, o, max_nodes, search_flags, out, info, "lpx_solve_bnb_bounded6", -1, divers, dinfo,
+                             0, nullptr, branching == LPX_BRANCH_STRONG ? &st : nullptr, sinfo);
+}
+
+void lpx_bnb_strong_info_free(lpx_bnb_strong_info* sinfo)
+{
+    if (sinfo) std::memset(sinfo, 0, sizeof(*sinfo));
 }
 
 void lpx_bnb_plunge_info_free(lpx_bnb_plunge_info* pinfo)

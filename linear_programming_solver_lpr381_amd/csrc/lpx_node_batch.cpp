@@ -1,7 +1,8 @@
 // lpx_node_batch.cpp -- host side of the batch of on-chip nodes (lpx_node_batch_*, C ABI of include/lpx.h): B nodes on B handles in
 // ONE launch of lpx_bounded_nodes_onchip (lpx_bounded_node.hip), one workgroup per node.  Every entry is the on-chip form of
 // lpx_bounded_node3 on its handle, bit for bit; the checks and what a finished node leaves on its handle are shared with it
-// (lpx_tableau_bounded.cpp, through lpx_handle.h).
+// (lpx_tableau_bounded.cpp, through lpx_handle.h).  lpx_node_batch_run_probe is the same body with the probe launch
+// (lpx_bounded_probe.hip) enqueued behind the node launch: two launches, one wait.
 #include "lpx_handle.h"
 
 #include <algorithm>
@@ -22,6 +23,7 @@ struct lpx_node_batch {
     std::vector<int32_t> seen; int32_t call = 0;        // seen[s] == call: slot s is named already in this call
     std::vector<size_t> off_in, off_edit; std::vector<uint8_t> any_lo;      // per entry, kept to spare the steady state its allocations
     std::vector<size_t> off_trip; std::vector<uint8_t> colmark;             // the plunge: an entry's first triple; scratch of its integrality check
+    char* probews = nullptr; size_t probews_bytes = 0; std::vector<size_t> off_ws;     // the probes: device workspace, an entry's share of it
 };
 
 namespace {
@@ -75,7 +77,7 @@ int lpx_node_batch_create(int W, lpx_tableau* const* handles, lpx_node_batch** o
     for (lpx_tableau* t : b->h)
         if (std::find(b->streams.begin(), b->streams.end(), t->stream) == b->streams.end()) b->streams.push_back(t->stream);
     b->seen.assign((size_t)W, 0);
-    b->off_in.resize((size_t)W); b->off_edit.resize((size_t)W); b->any_lo.resize((size_t)W); b->off_trip.resize((size_t)W);
+    b->off_in.resize((size_t)W); b->off_edit.resize((size_t)W); b->any_lo.resize((size_t)W); b->off_trip.resize((size_t)W); b->off_ws.resize((size_t)W);
     *out = b;
     return 0;
 }
@@ -85,23 +87,34 @@ void lpx_node_batch_destroy(lpx_node_batch* b)
     if (!b) return;
     for (hipStream_t s : b->streams) hipStreamSynchronize(s);
     if (b->slab) hipHostFree(b->slab);
-    hipFree(b->edit); hipFree(b->mask);
+    hipFree(b->edit); hipFree(b->mask); hipFree(b->probews);
     delete b;
 }
 
-int lpx_node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const int32_t* K, const int32_t* cols, const double* lower,
-                       const double* upper, const lpx_run_opts* o, int flags, const double* cutoff, int nint, const uint8_t* is_int,
-                       double tol, lpx_node_record* out, int32_t* rc)
+// lpx_node_batch_run (pr = null, name its own) and lpx_node_batch_run_probe in one body: with pr the probe launch goes behind the
+// node launch on the same stream and the one wait covers both.
+struct ProbeArgs { const double* prune; int cand_max, probe_iter; lpx_probe_head* head; lpx_probe_record* probes; };
+
+static int node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const int32_t* K, const int32_t* cols, const double* lower,
+                          const double* upper, const lpx_run_opts* o, int flags, const double* cutoff, int nint, const uint8_t* is_int,
+                          double tol, lpx_node_record* out, int32_t* rc, const ProbeArgs* pr, const char* name)
 {
-    const std::string w = "lpx_node_batch_run";
+    const std::string w = name;
     // ---- 1. every argument of every entry, before anything is written and before any device check
     if (!slot || !K || !out || !rc) { set_error(w + ": null " + (!slot ? "slot" : !K ? "K" : !out ? "out" : "rc")); return LPX_EINVAL; }
+    if (pr) {
+        if (!pr->prune || !pr->head || !pr->probes) { set_error(w + ": null " + (!pr->prune ? "prune" : !pr->head ? "head" : "probes")); return LPX_EINVAL; }
+        int r = check_probe_args(pr->cand_max, pr->probe_iter, name); if (r) return r;
+    }
     if (B < 1) { set_error(w + ": B is outside [1, W]"); return LPX_EINVAL; }
     { int r = check_long_flags(flags, 0.0, w.c_str()); if (r) return r; }
     if (flags & LPX_BDUAL_CUTOFF) {
         if (!cutoff) { set_error(w + ": null cutoff with LPX_BDUAL_CUTOFF"); return LPX_EINVAL; }
         for (int i = 0; i < B; ++i) { int r = check_long_flags(flags, cutoff[i], (w + ": entry " + std::to_string(i)).c_str()); if (r) return r; }
     }
+    if (pr)
+        for (int i = 0; i < B; ++i)
+            if (pr->prune[i] != pr->prune[i]) { set_error(w + ": entry " + std::to_string(i) + ": prune is NaN"); return LPX_EINVAL; }
     if (!b) { set_error(w + ": null batch"); return LPX_EINVAL; }
     const int W = (int)b->h.size();
     if (B > W) { set_error(w + ": B is outside [1, W]"); return LPX_EINVAL; }
@@ -109,9 +122,10 @@ int lpx_node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const int3
     if (b->call == INT32_MAX) { std::fill(b->seen.begin(), b->seen.end(), 0); b->call = 0; }
     ++b->call;
     size_t sumK = 0, in_bytes = 0, edit_bytes = 0, lds = 0;
-    char at[48];                                                         // "lpx_node_batch_run: entry i", no allocation per entry
+    size_t ws_bytes = 0;
+    char at[56];                                                         // "lpx_node_batch_run: entry i", no allocation per entry
     for (int i = 0; i < B; ++i) {
-        std::snprintf(at, sizeof at, "lpx_node_batch_run: entry %d", i);
+        std::snprintf(at, sizeof at, "%s: entry %d", name, i);
         if (slot[i] < 0 || slot[i] >= W) { set_error(std::string(at) + ": slot is outside [0, W)"); return LPX_EINVAL; }
         if (b->seen[slot[i]] == b->call) { set_error(std::string(at) + ": slot repeats a handle"); return LPX_EINVAL; }
         b->seen[slot[i]] = b->call;
@@ -126,12 +140,17 @@ int lpx_node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const int3
         in_bytes += up16(sizeof(NodeIn) + (size_t)k * (2 * sizeof(double) + sizeof(int32_t)));
         edit_bytes += up16((size_t)k * (5 * sizeof(double) + sizeof(int32_t)));
         lds = std::max(lds, bounded_node_lds_bytes(t->R, t->C));
+        if (pr) { b->off_ws[i] = ws_bytes; ws_bytes += probe_ws_bytes(t, pr->cand_max); }
         sumK += (size_t)k;
     }
     int r = ensure_device(); if (r) return r;
+    if (pr) { r = bounded_probe_ready(name); if (r) return r; }
 
     // ---- 2. the buffers: grown to twice the need, and only when the need outgrows them
-    const size_t o_out = up16(sizeof(NodeParams) * (size_t)B), o_in = o_out + kOut * (size_t)B, need = o_in + in_bytes;
+    const size_t nrec = pr ? 2 * (size_t)pr->cand_max : 0;
+    const size_t o_out = up16(sizeof(NodeParams) * (size_t)B), o_in = o_out + kOut * (size_t)B, o_pp = up16(o_in + in_bytes),
+                 o_head = o_pp + up16(sizeof(ProbeParams) * (size_t)B), o_prec = o_head + sizeof(lpx_probe_head) * (size_t)B,
+                 need = pr ? o_prec + sizeof(lpx_probe_record) * nrec * (size_t)B : o_in + in_bytes;
     if (need > b->slab_bytes) {
         r = settle_all(b); if (r) return r;
         if (b->slab) hipHostFree(b->slab);
@@ -144,6 +163,12 @@ int lpx_node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const int3
         hipFree(b->edit); b->edit = nullptr; b->edit_bytes = 0;
         LPX_HIP_TRY(hipMalloc((void**)&b->edit, 2 * edit_bytes));
         b->edit_bytes = 2 * edit_bytes;
+    }
+    if (ws_bytes > b->probews_bytes) {
+        r = settle_all(b); if (r) return r;
+        hipFree(b->probews); b->probews = nullptr; b->probews_bytes = 0;
+        LPX_HIP_TRY(hipMalloc((void**)&b->probews, 2 * ws_bytes));
+        b->probews_bytes = 2 * ws_bytes;
     }
     hipStream_t s = b->streams[0];
     const bool has_mask = is_int && nint > 0;
@@ -189,13 +214,23 @@ int lpx_node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const int3
         n.in = in; n.out = reinterpret_cast<NodeOut*>(b->slab + o_out + kOut * (size_t)i);
         std::memset(&out[i], 0, sizeof(out[i]));
         out[i].pick.var = -1;
+        if (pr)
+            probe_params(t, o, flags, in->cutoff, pr->prune[i], nint, has_mask ? b->mask : nullptr, tol, pr->cand_max, pr->probe_iter,
+                         in->lo_used != 0, b->probews + b->off_ws[i], n.out, reinterpret_cast<lpx_probe_head*>(b->slab + o_head) + i,
+                         reinterpret_cast<lpx_probe_record*>(b->slab + o_prec) + nrec * (size_t)i,
+                         reinterpret_cast<ProbeParams*>(b->slab + o_pp) + i);
         sumK += (size_t)k;
     }
 
-    // ---- 4. behind the handles' own streams, ONE launch, ONE wait
+    // ---- 4. behind the handles' own streams, ONE launch (with pr: the probes behind it), ONE wait
     r = settle_all(b); if (r) return r;
     LPX_HIP_TRY(launch_bounded_nodes_onchip(P, B, lds, s));
+    if (pr) LPX_HIP_TRY(launch_bounded_probe_onchip(reinterpret_cast<const ProbeParams*>(b->slab + o_pp), B, pr->cand_max, lds, s));
     LPX_HIP_TRY(hipStreamSynchronize(s));
+    if (pr) {
+        std::memcpy(pr->head, b->slab + o_head, sizeof(lpx_probe_head) * (size_t)B);
+        std::memcpy(pr->probes, b->slab + o_prec, sizeof(lpx_probe_record) * nrec * (size_t)B);
+    }
 
     // ---- 5. the records
     bool refused = false;
@@ -222,6 +257,22 @@ int lpx_node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const int3
         rc[i] = rec->status;
     }
     return 0;
+}
+
+int lpx_node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const int32_t* K, const int32_t* cols, const double* lower,
+                       const double* upper, const lpx_run_opts* o, int flags, const double* cutoff, int nint, const uint8_t* is_int,
+                       double tol, lpx_node_record* out, int32_t* rc)
+{
+    return node_batch_run(b, B, slot, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, rc, nullptr, "lpx_node_batch_run");
+}
+
+int lpx_node_batch_run_probe(lpx_node_batch* b, int B, const int32_t* slot, const int32_t* K, const int32_t* cols, const double* lower,
+                             const double* upper, const lpx_run_opts* o, int flags, const double* cutoff, const double* prune, int nint,
+                             const uint8_t* is_int, double tol, int cand_max, int probe_iter, lpx_node_record* out, lpx_probe_head* head,
+                             lpx_probe_record* probes, int32_t* rc)
+{
+    const ProbeArgs pr{prune, cand_max, probe_iter, head, probes};
+    return node_batch_run(b, B, slot, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, rc, &pr, "lpx_node_batch_run_probe");
 }
 
 // The plunge: lpx_node_batch_run's steps with a chain of up to depth[i] nodes per entry (kernel: lpx_bounded_plunge.hip).  The text

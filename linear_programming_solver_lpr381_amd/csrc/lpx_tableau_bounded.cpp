@@ -306,6 +306,50 @@ int lpx::bounded_plunge_ready(const char* what)
     return 0;
 }
 
+int lpx::bounded_probe_ready(const char* what)
+{
+    static std::once_flag once; static hipError_t init_err = hipSuccess;
+    std::call_once(once, [] { init_err = bounded_probe_init(); });
+    if (init_err != hipSuccess) { set_error(std::string(what) + ": kernel attribute setup failed: " + hipGetErrorString(init_err)); return LPX_EDEVICE; }
+    return 0;
+}
+
+int lpx::check_probe_args(int cand_max, int probe_iter, const char* what)
+{
+    if (cand_max < 1 || cand_max > 32) { set_error(std::string(what) + ": cand_max is outside [1, 32]"); return LPX_EINVAL; }
+    if (probe_iter < 0) { set_error(std::string(what) + ": probe_iter is negative"); return LPX_EINVAL; }
+    return 0;
+}
+
+namespace {
+size_t probe_basis_stride(const lpx_tableau* t) { return ((size_t)(t->R - 1) + 3) & ~(size_t)3; }       // int32 words, 16-byte slices
+size_t probe_flip_stride(const lpx_tableau* t) { return ((size_t)(t->C - 1) + 15) & ~(size_t)15; }      // bytes
+}  // namespace
+
+size_t lpx::probe_ws_bytes(const lpx_tableau* t, int cand_max)
+{
+    return 2 * (size_t)cand_max * (sizeof(int32_t) * probe_basis_stride(t) + probe_flip_stride(t));
+}
+
+void lpx::probe_params(const lpx_tableau* t, const lpx_run_opts* o, int flags, double cutoff, double prune, int nint,
+                       const uint8_t* mask_dev, double tol, int cand_max, int probe_iter, bool lo_used, char* ws, const NodeOut* front,
+                       lpx_probe_head* head, lpx_probe_record* rec, ProbeParams* p)
+{
+    std::memset(p, 0, sizeof(*p));
+    p->T = t->T; p->ld = t->ld; p->R = t->R; p->C = t->C;
+    p->basis = t->basis; p->st = t->st; p->ub = t->bnd.ub; p->lo = t->bnd.lo; p->flip = t->bnd.flip;
+    p->mask = mask_dev; p->front = front;
+    p->wbasis = reinterpret_cast<int32_t*>(ws); p->wbasis_stride = (int32_t)probe_basis_stride(t);
+    p->wflip = reinterpret_cast<uint8_t*>(ws + 2 * (size_t)cand_max * sizeof(int32_t) * probe_basis_stride(t));
+    p->wflip_stride = (int32_t)probe_flip_stride(t);
+    p->head = head; p->rec = rec;
+    p->eps = o->eps; p->ratio_tol = o->ratio_tol; p->cutoff = (flags & LPX_BDUAL_CUTOFF) ? cutoff : 0.0; p->tol = tol; p->prune = prune;
+    p->flags = flags; p->nint = nint; p->has_mask = mask_dev && nint > 0 ? 1 : 0; p->lo_used = lo_used ? 1 : 0;
+    p->probe_iter = probe_iter; p->cand_max = cand_max;
+    head->count = 0; head->candidates = 0; head->z = 0.0;
+    for (int w = 0; w < 2 * cand_max; ++w) { std::memset(&rec[w], 0, sizeof(rec[w])); rec[w].status = LPX_PROBE_NONE; rec[w].var = -1; rec[w].dir = w & 1; }
+}
+
 void lpx::bounds_note_edit(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper)
 {
     std::vector<uint8_t>& w = t->bnd.whole;
@@ -645,6 +689,62 @@ int lpx_bounded_node3(lpx_tableau* t, int K, const int32_t* cols, const double* 
     rc = check_node_opts(t, o, what); if (rc) return rc;
     rc = check_node_fits(t, what); if (rc) return rc;
     return bounded_node_onchip(t, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, what);
+}
+
+// ---- strong-branching probes of the handle as it stands (kernel in lpx_bounded_probe.hip): one launch, one wait, no write to the handle ----
+int lpx_bounded_probe(lpx_tableau* t, const lpx_run_opts* o, int flags, double cutoff, double prune, int nint, const uint8_t* is_int,
+                      double tol, int cand_max, int probe_iter, lpx_probe_head* head, lpx_probe_record* out)
+{
+    const char* what = "lpx_bounded_probe";
+    const std::string w = what;
+    // the arguments that need no handle first: they answer the same with and without a device, and without a handle
+    if (!head || !out) { set_error(w + ": null " + (!head ? "head" : "out")); return LPX_EINVAL; }
+    int rc = check_probe_args(cand_max, probe_iter, what); if (rc) return rc;
+    if (prune != prune) { set_error(w + ": prune is NaN"); return LPX_EINVAL; }
+    rc = check_long_flags(flags, cutoff, what); if (rc) return rc;
+    if (!t) { set_error(w + ": null handle"); return LPX_EINVAL; }
+    rc = check_pick_args(t, nint, tol, out, what); if (rc) return rc;
+    rc = check_bounds(t, what, true); if (rc) return rc;
+    lpx_run_opts d; if (!o) { lpx_default_opts(&d, 1); o = &d; }
+    rc = check_node_opts(t, o, what); if (rc) return rc;
+    rc = check_node_fits(t, what); if (rc) return rc;
+    rc = bounded_ready(t, true); if (rc) return rc;
+    rc = bounded_probe_ready(what); if (rc) return rc;
+    lpx_tableau::Bounds& b = t->bnd;
+    const size_t nrec = 2 * (size_t)cand_max;
+    const size_t o_head = (sizeof(ProbeParams) + 15) & ~(size_t)15, o_rec = o_head + 16, need = o_rec + sizeof(lpx_probe_record) * nrec;
+    static_assert(sizeof(lpx_probe_head) == 16 && sizeof(lpx_probe_record) == 64, "record layout of include/lpx.h");
+    if (need > b.probeio_bytes) {
+        LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+        if (b.probeio) hipHostFree(b.probeio);
+        b.probeio = nullptr; b.probeio_bytes = 0;
+        LPX_HIP_TRY(hipHostMalloc((void**)&b.probeio, 2 * need));
+        b.probeio_bytes = 2 * need;
+    }
+    const size_t ws = probe_ws_bytes(t, cand_max);
+    if (ws > b.probews_bytes) {
+        LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+        hipFree(b.probews); b.probews = nullptr; b.probews_bytes = 0;
+        LPX_HIP_TRY(hipMalloc((void**)&b.probews, 2 * ws));
+        b.probews_bytes = 2 * ws;
+    }
+    const bool has_mask = is_int && nint > 0;
+    if (has_mask && !(b.mask_n == nint && std::memcmp(b.mask_h.data(), is_int, (size_t)nint) == 0)) {
+        LPX_HIP_TRY(hipStreamSynchronize(t->stream));                            // an earlier copy may still read mask_h
+        b.mask_h.assign(is_int, is_int + nint);
+        LPX_HIP_TRY(hipMemcpyAsync(b.pickmask, b.mask_h.data(), (size_t)nint, hipMemcpyHostToDevice, t->stream));
+        b.mask_n = nint;
+    }
+    ProbeParams* P = reinterpret_cast<ProbeParams*>(b.probeio);
+    lpx_probe_head* hd = reinterpret_cast<lpx_probe_head*>(b.probeio + o_head);
+    lpx_probe_record* rec = reinterpret_cast<lpx_probe_record*>(b.probeio + o_rec);
+    probe_params(t, o, flags, cutoff, prune, nint, has_mask ? b.pickmask : nullptr, tol, cand_max, probe_iter, b.lo_used, b.probews,
+                 nullptr, hd, rec, P);
+    LPX_HIP_TRY(launch_bounded_probe_onchip(P, 1, cand_max, bounded_node_lds_bytes(t->R, t->C), t->stream));
+    LPX_HIP_TRY(hipStreamSynchronize(t->stream));                                // the one wait: head and records are in the slab
+    *head = *hd;
+    std::memcpy(out, rec, sizeof(lpx_probe_record) * nrec);
+    return 0;
 }
 
 }  // extern "C"

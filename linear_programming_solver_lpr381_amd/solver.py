@@ -343,7 +343,8 @@ class LPSolver:             # Models/LPSolver.cs:6-77
 
     def SolveBnbBounded(self, problem: LPProblem, upper, lower=None, integer=None, max_nodes: int = 0,
                         long_step: bool = False, cutoff: bool = False, node_form: Optional[str] = None,
-                        divers: Optional[int] = None, plunge: Optional[int] = None) -> SimplexResult:
+                        divers: Optional[int] = None, plunge: Optional[int] = None, branching: Optional[str] = None,
+                        candidates: int = 4, probe_iter: Optional[int] = None) -> SimplexResult:
         """Branch and bound by bound changes on one device tableau (lpx_solve_bnb_bounded): lower <= x <= upper, x_j integer
         where integer[j] (None: every variable); integer variables need finite, integral bounds.  Status OPTIMAL or INFEASIBLE,
         Solution, OptimalValue (user's sense), Nodes, BnbInfo (counters) and BnbLog, a structured array with one record per node
@@ -361,7 +362,25 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         (lpx_solve_bnb_bounded5, 1 <= D <= 64; without divers it means divers=1): a diver's workgroup goes on from a node that
         branches into its ceil child, up to D nodes per launch with the tableau staying in LDS.  plunge=1 gives the log of
         divers=W, divers=1 with any plunge the log of node_form="onchip".  The result then also carries BnbStep (every record's
-        index in its chain) and BnbInfo["launched" / "dropped" / "longest_chain"]."""
+        index in its chain) and BnbInfo["launched" / "dropped" / "longest_chain"].  branching "most_fractional" | "strong"
+        (lpx_solve_bnb_bounded6; None: the paths above, unchanged; without divers it means divers=1): "strong" probes both
+        children of up to `candidates` (1..32) fractional columns of every evaluated node in a second launch of the same round,
+        at most probe_iter events each (None: the engine's max_iter), branches on the first largest product of the two
+        objective losses and never pushes a child whose probe ended infeasible, cut off or not above the incumbent + 1e-6;
+        "most_fractional" gives the log of divers=W.  BnbInfo then carries probe_launches, probes, probe_events, probe_limit,
+        pruned_by_probe and changed_picks.  It is a rule beside the default one: it visits fewer nodes and pays for every
+        node with a second launch."""
+        if branching is not None:
+            if branching not in _lib.BRANCHINGS:
+                raise ValueError(f"unknown branching rule {branching!r}")
+            if node_form == "launches":
+                raise ValueError("branching evaluates every node on chip: it cannot be combined with node_form='launches'")
+            if plunge is not None and plunge > 1:      # a chain has no host decision between its nodes
+                raise ValueError("a branching rule decides on the host between a node and its children: it cannot be combined "
+                                 "with plunge > 1")
+            if divers is None:
+                divers = 1
+            plunge = None
         if plunge is not None and node_form == "launches":
             raise ValueError("plunge evaluates every node on chip: it cannot be combined with node_form='launches'")
         if plunge is not None and divers is None:
@@ -389,7 +408,15 @@ class LPSolver:             # Models/LPSolver.cs:6-77
             mp = mask.ctypes.data_as(C.POINTER(C.c_uint8))
         r, info, dinfo, pinfo = _lib.Result(), _lib.BnbBoundedInfo(), _lib.BnbDiversInfo(), _lib.BnbPlungeInfo()
         flags = (_lib.BDUAL_LONG_STEP if long_step else 0) | (_lib.BDUAL_CUTOFF if cutoff else 0)
-        if plunge is not None:
+        sinfo = _lib.BnbStrongInfo()
+        if branching is not None:
+            cand = int(candidates)
+            if cand < 1 or cand > 32:
+                raise ValueError(f"candidates = {cand}: candidates must be in [1, 32]")
+            rc = lib().lpx_solve_bnb_bounded6(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), flags, int(divers),
+                                              _lib.BRANCHINGS[branching], cand, int((o.max_iter or 10000) if probe_iter is None else probe_iter),
+                                              C.byref(r), C.byref(info), C.byref(dinfo), C.byref(sinfo))
+        elif plunge is not None:
             rc = lib().lpx_solve_bnb_bounded5(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), flags, int(divers), int(plunge),
                                               C.byref(r), C.byref(info), C.byref(dinfo), C.byref(pinfo))
         elif divers is not None:
@@ -415,6 +442,9 @@ class LPSolver:             # Models/LPSolver.cs:6-77
                 counters.update({k: getattr(dinfo, k) for k in ("rounds", "steals", "largest_batch")})
                 rounds = np.ctypeslib.as_array(dinfo.round, (info.n_log,)).copy() if info.n_log else np.zeros(0, dtype=np.int32)
                 who = np.ctypeslib.as_array(dinfo.diver, (info.n_log,)).copy() if info.n_log else np.zeros(0, dtype=np.int32)
+            if branching is not None:
+                counters.update({k: getattr(sinfo, k) for k in ("probe_launches", "probes", "probe_events", "probe_limit",
+                                                                "pruned_by_probe", "changed_picks")})
             if plunge is not None:
                 counters.update({k: getattr(pinfo, k) for k in ("launched", "dropped", "longest_chain")})
                 step = np.ctypeslib.as_array(pinfo.step, (info.n_log,)).copy() if info.n_log else np.zeros(0, dtype=np.int32)

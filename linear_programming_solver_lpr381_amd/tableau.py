@@ -369,6 +369,30 @@ class DeviceTableau:
                                          upper.ctypes.data_as(dp), C.byref(o), int(nint), mp, float(tol), C.byref(rec)))
         return _node_dict(rec)
 
+    def probe(self, nint: int, cand_max: int, probe_iter: Optional[int] = None, is_int=None, tol: float = 1e-6,
+              opts: Optional[RunOpts] = None, long_step: bool = False, cutoff: Optional[float] = None,
+              prune: float = -np.inf, **kw) -> dict:
+        """Strong-branching probes of the tableau as it stands (lpx_bounded_probe): up to cand_max fractional integer columns,
+        in the order (|fraction - 0.5|, column), each with its floor and its ceil child evaluated on a private copy by one
+        workgroup of ONE launch; nothing of the handle changes.  probe_iter: the event limit of a child (None: the limit of
+        opts).  Nothing is probed when the handle's last run did not end OPTIMAL or z <= prune.  Returns {count, candidates, z,
+        records, idle}: records[2 c + d] is the dict of candidate c < count, direction d (0 floor, 1 ceil), bit-equal to
+        bounded_node(var, lower, upper, form="onchip") on a clone; status None marks a child that call would refuse.  idle[w]:
+        slot w of the 2 * cand_max holds no probe (LPX_PROBE_NONE)."""
+        cand_max = int(cand_max)
+        if cand_max < 1 or cand_max > 32:
+            raise ValueError(f"cand_max = {cand_max}: cand_max must be in [1, 32]")
+        o = opts if opts is not None else default_opts(True, **kw)
+        keep, mp = self._mask(is_int, int(nint))
+        flags = (_lib.BDUAL_SKIP_FIXED | (_lib.BDUAL_LONG_STEP if long_step else 0)
+                 | (_lib.BDUAL_CUTOFF if cutoff is not None else 0))
+        head = _lib.ProbeHead()
+        recs = (_lib.ProbeRecord * (2 * cand_max))()
+        check(lib().lpx_bounded_probe(self._h, C.byref(o), flags, float(cutoff if cutoff is not None else 0.0), float(prune),
+                                      int(nint), mp, float(tol), cand_max, int(o.max_iter if probe_iter is None else probe_iter),
+                                      C.byref(head), recs))
+        return _probe_dict(head, recs, 0, cand_max)
+
     def bounded_node_fits(self) -> bool:
         """True iff the on-chip form of bounded_node accepts the live shape (lpx_bounded_node_fits: host arithmetic only)."""
         return bool(lib().lpx_bounded_node_fits(self.R, self.C))
@@ -392,6 +416,17 @@ def _node_dict(rec) -> dict:
     return {"status": rec.status, "events": rec.events, "kind0": rec.kind0, "kind1": rec.kind1, "flips": rec.flips,
             "unrepairable": rec.unrepairable, "var": rec.pick.var, "candidates": rec.pick.candidates,
             "x_var": rec.pick.x_var, "z": rec.pick.z}
+
+
+def _probe_dict(head, recs, first: int, cand_max: int) -> dict:
+    """One entry's probes: the head and the records that ran (2 * count of them), in candidate order."""
+    out = []
+    for w in range(2 * min(int(head.count), cand_max)):
+        r = recs[first + w]
+        out.append({"status": None if r.status == -1 else r.status, "events": r.events, "kind0": r.kind0, "kind1": r.kind1,
+                    "flips": r.flips, "var": r.var, "dir": r.dir, "x_var": r.x_var, "lower": r.lower, "upper": r.upper, "z": r.z})
+    return {"count": int(head.count), "candidates": int(head.candidates), "z": head.z, "records": out,
+            "idle": [recs[first + w].status == _lib.PROBE_NONE for w in range(2 * cand_max)]}
 
 
 class NodeBatch:
@@ -460,6 +495,58 @@ class NodeBatch:
                 d["status"] = None
             out.append(d)
         return out
+
+    def run_probe(self, slots, nodes, nint: int, cand_max: int, probe_iter: Optional[int] = None, prune=-np.inf, is_int=None,
+                  tol: float = 1e-6, long_step: bool = False, cutoffs=None, opts: Optional[RunOpts] = None, **kw):
+        """run(), and behind its launch on the same stream the probes of every entry's handle as the node leaves it
+        (lpx_node_batch_run_probe): two launches, ONE wait.  prune is one value or one per entry; probe_iter None is the event
+        limit of opts.  Returns (records, probes): records as run() returns them, probes[i] as DeviceTableau.probe() would
+        return it on handles[slots[i]] afterwards."""
+        slots = np.ascontiguousarray(np.atleast_1d(slots), dtype=np.int32).reshape(-1)
+        B = len(slots)
+        if len(nodes) != B:
+            raise ValueError(f"{B} slots but {len(nodes)} nodes")
+        if B < 1 or B > self._W:
+            raise ValueError(f"a batch of {B} entries on {self._W} handles: B must be in [1, W]")
+        cand_max = int(cand_max)
+        if cand_max < 1 or cand_max > 32:
+            raise ValueError(f"cand_max = {cand_max}: cand_max must be in [1, 32]")
+        cs, ls, us = [], [], []
+        for cols, lower, upper in nodes:
+            c = np.ascontiguousarray(np.atleast_1d(cols), dtype=np.int32).reshape(-1)
+            cs.append(c)
+            ls.append(np.broadcast_to(np.asarray(lower, dtype=np.float64), c.shape))
+            us.append(np.broadcast_to(np.asarray(upper, dtype=np.float64), c.shape))
+        K = np.array([len(c) for c in cs], dtype=np.int32)
+        cols = np.ascontiguousarray(np.concatenate(cs), dtype=np.int32)
+        lower = np.ascontiguousarray(np.concatenate(ls), dtype=np.float64)
+        upper = np.ascontiguousarray(np.concatenate(us), dtype=np.float64)
+        flags = (_lib.BDUAL_SKIP_FIXED | (_lib.BDUAL_LONG_STEP if long_step else 0)
+                 | (_lib.BDUAL_CUTOFF if cutoffs is not None else 0))
+        cut, cp = None, None
+        if cutoffs is not None:
+            cut = np.ascontiguousarray(np.broadcast_to(np.asarray(cutoffs, dtype=np.float64), (B,)))
+            cp = cut.ctypes.data_as(dp)
+        pr = np.ascontiguousarray(np.broadcast_to(np.asarray(prune, dtype=np.float64), (B,)))
+        o = opts if opts is not None else default_opts(True, **kw)
+        keep, mp = DeviceTableau._mask(is_int, int(nint))
+        recs = (_lib.NodeRecord * B)()
+        heads = (_lib.ProbeHead * B)()
+        probes = (_lib.ProbeRecord * (B * 2 * cand_max))()
+        rc = np.zeros(B, dtype=np.int32)
+        check(lib().lpx_node_batch_run_probe(self._h, B, slots.ctypes.data_as(ip), K.ctypes.data_as(ip), cols.ctypes.data_as(ip),
+                                             lower.ctypes.data_as(dp), upper.ctypes.data_as(dp), C.byref(o), flags, cp,
+                                             pr.ctypes.data_as(dp), int(nint), mp, float(tol), cand_max,
+                                             int(o.max_iter if probe_iter is None else probe_iter), recs, heads, probes,
+                                             rc.ctypes.data_as(ip)))
+        out, pout = [], []
+        for i in range(B):
+            d = _node_dict(recs[i])
+            if rc[i] < 0:
+                d["status"] = None
+            out.append(d)
+            pout.append(_probe_dict(heads[i], probes, i * 2 * cand_max, cand_max))
+        return out, pout
 
     def plunge(self, slots, nodes, nint: int, depth, D: int, prune, is_int=None, tol: float = 1e-6, long_step: bool = False,
                cutoffs=None, opts: Optional[RunOpts] = None, **kw) -> list:

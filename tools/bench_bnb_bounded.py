@@ -35,11 +35,18 @@ for W = 1 the sequential on-chip driver: per model and flag set the baseline and
 in one process, REPS timed solves each after one untimed solve; nodes, events, rounds, launched, dropped and wall per form, and
 `wins`: a D wins iff its median lies below the baseline's minimum.  A search that ends at a node's event limit is reported
 (`limit`) and not timed against.
+`--compare-branching LIST` measures strong branching by probes (lpx_solve_bnb_bounded6) at the W of
+`--divers` (default 1) against the most-fractional rule at the same W and flags: LIST is comma-separated settings C or C:L --
+C candidates, probes of at most L events (no L: the node's limit); per model and flag set the baseline and each setting
+alternate in one process, REPS timed solves each after one untimed solve; nodes, events, rounds, probes, probe events, children
+pruned by a probe, changed picks and wall per side, and `wins`: a setting wins iff its median lies below the baseline's minimum.
+`--branching R [--candidates C] [--probe-iter L]` makes side (b), and `--trace-only`, the search with that rule.
 `--trace-only` runs one solve of side (b) and nothing else (for a kernel trace of the node form given).
 
 usage: bench_bnb_bounded.py [--model NAME] [--max-nodes N] [--node-form F] [--divers W] [--plunge D]
                             [--compare-forms [--flag-sets LIST]] [--compare-divers LIST [--flag-sets LIST]]
-                            [--compare-plunge LIST [--flag-sets LIST]] [--trace-only] [REPS]"""
+                            [--compare-plunge LIST [--flag-sets LIST]] [--compare-branching LIST [--flag-sets LIST]]
+                            [--branching R [--candidates C] [--probe-iter L]] [--long-step] [--cutoff] [--trace-only] [REPS]"""
 import json
 import os
 import statistics
@@ -242,8 +249,75 @@ def compare_plunge(n, m, reps, max_nodes, flag_sets, W, depths):
     return rec
 
 
+def compare_branching(n, m, reps, max_nodes, flag_sets, W, settings):
+    """Strong branching (lpx_solve_bnb_bounded6) at W divers against the most-fractional rule at the same W on binary_ip(n, m)
+    (see the module docstring).  settings: (candidates, probe_iter or None)."""
+    c, A, rel, b = synth.binary_ip(n, m)
+    bnd_p = L.LPProblem.from_arrays(0, c, A[:m], rel[:m], b[:m])
+    rec = {"n": n, "m": m, "bounded_shape": [m + 1, n + m + 1], "divers": W}
+    sides = {"base": None}
+    for cand, limit in settings:
+        sides[f"C{cand}" + ("" if limit is None else f"L{limit}")] = (cand, limit)
+
+    def solve(side, kw, limit=None):
+        limit = max_nodes if limit is None else limit
+        how = {"divers": W, "branching": "most_fractional"}
+        if sides[side] is not None:
+            how = {"divers": W, "branching": "strong", "candidates": sides[side][0], "probe_iter": sides[side][1]}
+        t0 = time.perf_counter()
+        try:
+            r = L.LPSolver().SolveBnbBounded(bnd_p, 1.0, max_nodes=limit, **how, **kw)
+            r.Limit = None
+        except L.SolverException as e:
+            if e.code != L._lib.ITER_LIMIT:
+                raise
+            r = e.result
+            r.Limit = None if limit and r.Nodes >= limit else str(e)      # a node at its event limit ends the solve: reported, not timed against
+        return 1e3 * (time.perf_counter() - t0), r
+
+    for fs in flag_sets:
+        kw = FLAG_SETS[fs]
+        ts = {s: [] for s in sides}
+        last = {}
+        for i in range(reps + 1):
+            for s in sides:
+                if i == 0:          # the untimed solve: clones, the batch's slab and workspace and the first launches are paid here
+                    solve(s, kw, max_nodes if max_nodes else 2000)
+                    continue
+                ms, r = solve(s, kw)
+                last[s] = r
+                ts[s].append(ms)
+        base = stats(ts["base"])
+        d = {}
+        for s in sides:
+            r = last[s]
+            st = stats(ts[s])
+            d[s] = {"ms": st, "nodes": int(r.Nodes), "events": r.BnbInfo["events"], "rounds": r.BnbInfo["rounds"],
+                    "probes": r.BnbInfo["probes"], "probe_events": r.BnbInfo["probe_events"], "probe_limit": r.BnbInfo["probe_limit"],
+                    "pruned_by_probe": r.BnbInfo["pruned_by_probe"], "changed_picks": r.BnbInfo["changed_picks"],
+                    "nodes_per_s": r.Nodes / (st["median"] / 1e3), "optimum": r.OptimalValue, "limit": r.Limit,
+                    "wins": bool(s != "base" and r.Limit is None and last["base"].Limit is None and st["median"] < base["min"])}
+        rec[fs] = d
+    return rec
+
+
 def main():
     args = sys.argv[1:]
+    branching, candidates, probe_iter, settings = None, 4, None, None
+    for flag in ("--branching", "--candidates", "--probe-iter", "--compare-branching"):
+        if flag in args:
+            k = args.index(flag)
+            if flag == "--branching":
+                branching = args[k + 1]
+            elif flag == "--candidates":
+                candidates = int(args[k + 1])
+            elif flag == "--probe-iter":
+                probe_iter = int(args[k + 1])
+            else:
+                settings = [(int(x.split(":")[0]), int(x.split(":")[1]) if ":" in x else None) for x in args[k + 1].split(",") if x]
+            del args[k:k + 2]
+    side_flags = {"long_step": "--long-step" in args, "cutoff": "--cutoff" in args}
+    args = [a for a in args if a not in ("--long-step", "--cutoff")]
     only, max_nodes, node_form, flag_sets, divers, widths, plunge, depths = None, 0, None, None, None, None, None, None
     for flag in ("--model", "--max-nodes", "--node-form", "--flag-sets", "--divers", "--compare-divers", "--plunge", "--compare-plunge"):
         if flag in args:
@@ -273,7 +347,16 @@ def main():
     L._lib.check(lib.lpx_init(0))
     out = {}
     if flag_sets is None:
-        flag_sets = "plain,both" if widths or depths else "plain,long_step,cutoff,both"
+        flag_sets = "plain,both" if widths or depths or settings else "plain,long_step,cutoff,both"
+    if settings:
+        for name, n, m in models():
+            if only is None or name == only:
+                out[name] = compare_branching(n, m, reps, max_nodes, [f for f in flag_sets.split(",") if f and f != "none"],
+                                              divers if divers else 1, settings)
+        print(json.dumps(out))
+        return
+    if branching is not None and divers is None:
+        divers = 1
     if depths:
         for name, n, m in models():
             if only is None or name == only:
@@ -313,7 +396,9 @@ def main():
         def run_bounded():
             t0 = time.perf_counter()
             try:
-                r = L.LPSolver().SolveBnbBounded(bnd_p, 1.0, max_nodes=max_nodes, node_form=node_form, divers=divers, plunge=plunge)
+                how = {} if branching is None else {"branching": branching, "candidates": candidates, "probe_iter": probe_iter}
+                r = L.LPSolver().SolveBnbBounded(bnd_p, 1.0, max_nodes=max_nodes, node_form=node_form, divers=divers, plunge=plunge,
+                                                 **side_flags, **how)
             except L.SolverException as e:
                 if e.code != L._lib.ITER_LIMIT or not max_nodes:
                     raise
@@ -324,7 +409,8 @@ def main():
             ms, rb = run_bounded()
             out[name] = {"node_form": node_form, "divers": divers, "plunge": plunge, "ms": ms, "nodes": int(rb.Nodes),
                          "events": rb.BnbInfo["events"], "rounds": rb.BnbInfo.get("rounds"), "launched": rb.BnbInfo.get("launched"),
-                         "dropped": rb.BnbInfo.get("dropped")}
+                         "dropped": rb.BnbInfo.get("dropped"), "branching": branching, "probes": rb.BnbInfo.get("probes"),
+                         "probe_events": rb.BnbInfo.get("probe_events"), "pruned_by_probe": rb.BnbInfo.get("pruned_by_probe")}
             continue
         base = device_used_mb()
         ta, tb, na, nb = [], [], [], []

@@ -1,7 +1,7 @@
 // lpx_cli -- Linux stand-in for the reference's WinForms host (Form1.cs), over the C ABI of liblpx.so only.
 //
 //   lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]
-//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D]] [--export FILE] INPUT.txt
+//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]]] [--export FILE] INPUT.txt
 //
 // Does what Form1 does around the solvers: reads the model text (Import, Form1.cs:284-296), parses it with the LPParser
 // grammar (lpx_parse_text, Models/LPParser.cs:9-79), runs the algorithm chosen by its dropdown name (btnSolve_Click,
@@ -80,6 +80,9 @@ int main(int argc, char** argv)
     int node_form = -1;         // --node-form beside --bnb-bounded: LPX_NODE_*; -1 = not given
     int divers = 0;             // --divers W beside --bnb-bounded: the search by W divers (lpx_solve_bnb_bounded4); 0 = not given
     int plunge = 0;             // --plunge D beside --bnb-bounded: up to D nodes per diver and launch (lpx_solve_bnb_bounded5); 0 = not given
+    int branching = -1;         // --branching R beside --bnb-bounded: LPX_BRANCH_* (lpx_solve_bnb_bounded6); -1 = not given
+    int candidates = 4;         // --candidates N: the columns probed per node by --branching strong
+    int probe_iter = -1;        // --probe-iter L: the event limit of a probe; -1 = the node's
     struct Bound { bool upper; int index; double value; std::string text; };
     std::vector<Bound> bounds;
     lpx_cut_opts co; lpx_default_cut_opts(&co);
@@ -110,6 +113,23 @@ int main(int argc, char** argv)
             const long d = std::strtol(v.c_str(), &end, 10);
             if (end == v.c_str() || *end || d < 1 || d > 64) { std::fprintf(stderr, "lpx_cli: --plunge takes a depth in [1, 64], got '%s'\n", v.c_str()); return 64; }
             plunge = (int)d;
+        }
+        else if (a == "--branching" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            branching = v == "most_fractional" ? LPX_BRANCH_MOST_FRACTIONAL : v == "strong" ? LPX_BRANCH_STRONG : -2;
+            if (branching == -2) { std::fprintf(stderr, "lpx_cli: --branching takes most_fractional or strong, got '%s'\n", v.c_str()); return 64; }
+        }
+        else if ((a == "--candidates" || a == "--probe-iter") && i + 1 < argc) {
+            const std::string v = argv[++i];
+            char* end = nullptr;
+            const long x = std::strtol(v.c_str(), &end, 10);
+            const bool cand = a == "--candidates";
+            if (end == v.c_str() || *end || x < (cand ? 1 : 0) || x > (cand ? 32 : 1000000000)) {
+                std::fprintf(stderr, cand ? "lpx_cli: --candidates takes a count in [1, 32], got '%s'\n"
+                                          : "lpx_cli: --probe-iter takes a non-negative event limit, got '%s'\n", v.c_str());
+                return 64;
+            }
+            (cand ? candidates : probe_iter) = (int)x;
         }
         else if ((a == "--upper" || a == "--lower") && i + 1 < argc) {
             const std::string v = argv[++i];
@@ -147,7 +167,7 @@ int main(int argc, char** argv)
         else if (a == "--export" && i + 1 < argc) exportPath = argv[++i];
         else if (a == "--help" || a == "-h") {
             std::printf("usage: lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]\n"
-                        "               [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D]]\n"
+                        "               [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]]]\n"
                         "               [--export FILE] INPUT.txt\n"
                         "  NAME: Primal Simplex | Revised Primal Simplex | Dual Simplex | Branch and Bound |\n"
                         "        Revised Branch and Bound | Branch and Bound Knapsack | Cutting Plane | Revised Cutting Plane |\n"
@@ -167,6 +187,10 @@ int main(int argc, char** argv)
                         "             launch per round (lpx_solve_bnb_bounded4); not with --node-form launches\n"
                         "  --plunge D: with --bnb-bounded, a diver goes on from a node that branches into its ceil child, up to D nodes per\n"
                         "             launch with the tableau staying on chip (lpx_solve_bnb_bounded5); without --divers it means --divers 1\n"
+                        "  --branching most_fractional|strong: with --bnb-bounded, the branching rule (lpx_solve_bnb_bounded6; without\n"
+                        "             --divers it means --divers 1): strong probes both children of up to N = --candidates (default 4, at most 32)\n"
+                        "             fractional columns of every node on chip, --probe-iter L events each at most (default: the node's limit),\n"
+                        "             and branches on the largest product of the two objective losses; not with --plunge above 1\n"
                         "  --set-rhs I=V, --set-cost J=V: after the solve, b_I = V / c_J = V (1-based, repeatable), applied in order,\n"
                         "             each re-optimised warm on the device from the previous basis; each re-solve's summary is printed\n");
             return 0;
@@ -184,6 +208,10 @@ int main(int argc, char** argv)
     if (divers && !bnb_bounded) { std::fprintf(stderr, "lpx_cli: --divers needs --bnb-bounded\n"); return 64; }
     if (plunge && !bnb_bounded) { std::fprintf(stderr, "lpx_cli: --plunge needs --bnb-bounded\n"); return 64; }
     if (plunge && node_form == LPX_NODE_LAUNCHES) { std::fprintf(stderr, "lpx_cli: --plunge evaluates every node on chip: not with --node-form launches\n"); return 64; }
+    if (branching >= 0 && !bnb_bounded) { std::fprintf(stderr, "lpx_cli: --branching needs --bnb-bounded\n"); return 64; }
+    if (branching >= 0 && plunge > 1) { std::fprintf(stderr, "lpx_cli: --branching decides between a node and its children: not with --plunge above 1\n"); return 64; }
+    if (branching >= 0 && node_form == LPX_NODE_LAUNCHES) { std::fprintf(stderr, "lpx_cli: --branching evaluates every node on chip: not with --node-form launches\n"); return 64; }
+    if (branching >= 0) { plunge = 0; if (!divers) divers = 1; }
     if (plunge && !divers) divers = 1;
     if (divers && node_form == LPX_NODE_LAUNCHES) { std::fprintf(stderr, "lpx_cli: --divers evaluates every node on chip: not with --node-form launches\n"); return 64; }
     if (bounded) {
@@ -215,7 +243,9 @@ int main(int argc, char** argv)
         if (bd.index >= p.n) { std::fprintf(stderr, "lpx_cli: %s: index out of range\n", bd.text.c_str()); lpx_parsed_free(&p); return 64; }
         (bd.upper ? up : lo)[bd.index] = bd.value;
     }
-    const int rc = bnb_bounded && plunge ? lpx_solve_bnb_bounded5(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, plunge, &r, nullptr, nullptr, nullptr)
+    const int rc = bnb_bounded && branching >= 0 ? lpx_solve_bnb_bounded6(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, branching, candidates,
+                                                                         probe_iter >= 0 ? probe_iter : o.max_iter > 0 ? o.max_iter : 10000, &r, nullptr, nullptr, nullptr)
+                 : bnb_bounded && plunge ? lpx_solve_bnb_bounded5(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, plunge, &r, nullptr, nullptr, nullptr)
                  : bnb_bounded && divers ? lpx_solve_bnb_bounded4(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, &r, nullptr, nullptr)
                  : bnb_bounded && node_form >= 0 ? lpx_solve_bnb_bounded3(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, node_form, &r, nullptr)
                  : bnb_bounded && search_flags ? lpx_solve_bnb_bounded2(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, &r, nullptr)
