@@ -1008,8 +1008,9 @@ int lpx_solve_bnb_bounded3(const lpx_problem* p, const double* lower /* [n] or N
  * options, the flags and W alone; it does not depend on timing.  Another W visits other nodes, and the plain dual loop
  * (search_flags without LPX_BDUAL_LONG_STEP) can meet a node on which it makes max_iter events, which ends the solve with
  * LPX_ITER_LIMIT as in lpx_solve_bnb_bounded: measured on binary_ip(128, 64), where W = 4, 64 and 256 end that way and W = 1 and 16
- * do not; with LPX_BDUAL_LONG_STEP no search measured did.  Set the long step with divers on models of
- * that size.  dinfo (or NULL): rounds, steals, largest_batch and, per log
+ * do not.  LPX_BDUAL_LONG_STEP makes such a node rare, not impossible: a search with the long step ends
+ * that way under strong branching.  The cause is cycling at a dual degenerate vertex;
+ * lpx_solve_bnb_bounded7 with stall_events > 0 ends such nodes (the stall guard below).  dinfo (or NULL): rounds, steals, largest_batch and, per log
  * record, the round and the diver that evaluated it ([info->n_log] each); free with lpx_bnb_divers_info_free. */
 typedef struct lpx_node_batch lpx_node_batch;
 typedef struct lpx_bnb_divers_info {
@@ -1152,7 +1153,7 @@ void lpx_bnb_plunge_info_free(lpx_bnb_plunge_info* pinfo);
  *   outside [1, 32], probe_iter < 0.  The result is a function of the model, the options, the flags, W, cand_max and probe_iter.
  *   The rule visits other nodes than lpx_solve_bnb_bounded4, so what that entry says about a node that makes max_iter events
  *   holds here for other searches: binary_ip(128, 64) with both flags, W = 1, cand_max = 4 and ample probes ends that way
- *   (DESIGN.md section 4.20). */
+ *   (DESIGN.md section 4.20).  The stall guard below does not reach the probes or this search. */
 #define LPX_PROBE_NONE (-2)
 #define LPX_BRANCH_MOST_FRACTIONAL 0
 #define LPX_BRANCH_STRONG 1
@@ -1189,6 +1190,68 @@ int  lpx_solve_bnb_bounded6(const lpx_problem* p, const double* lower /* [n] or 
                             lpx_result* out, lpx_bnb_bounded_info* info /* or NULL */, lpx_bnb_divers_info* dinfo /* or NULL */,
                             lpx_bnb_strong_info* sinfo /* or NULL */);
 void lpx_bnb_strong_info_free(lpx_bnb_strong_info* sinfo);
+
+/* ---- the stall guard: Bland's rule once a node stops making progress (not in the reference; csrc/lpx_bounded_guard.hip,
+ * csrc/lpx_node_batch.cpp, csrc/host/bnb_bounded.cpp) --
+ * The leaving rule of lpx_bounded_dual_run (most negative infeasibility) with the hysteresis ratio test has no anti-cycling
+ * property: on a dual degenerate vertex of an integer model the loop can repeat a sequence of bases for ever, the objective
+ * standing still, until max_iter ends the node and with it the search.  The guard is an integer argument, not a flag:
+ * stall_events = S >= 0, and S = 0 gives the existing loop bit for bit.  For S > 0 the loop of lpx_bounded_dual_run3 keeps two
+ * more values per node evaluation:
+ *   z_ref   starts as T[m,Cm] as it stands when the loop is entered, after the edit and the dual-feasibility flips;
+ *   stall   starts at 0.
+ * At the top of every trip, behind step 1 and step 1b: if T[m,Cm] < z_ref - eps (one subtract, one compare), then z_ref = T[m,Cm]
+ * and stall = 0.  The trip runs in BLAND MODE iff stall >= S.  Every pivot, in either mode, adds 1 to stall; passes of the long
+ * step do not.  A trip in Bland mode differs from an ordinary trip in three places only:
+ *   2.  Leaving row: among the rows with w_i < -eps, w_i exactly as in step 2, the row whose basic column index basis[i] is
+ *       least (equal indices cannot occur in a basis; the lowest row would win).  None: LPX_OPTIMAL.  Kind and complement as ever.
+ *   4.  Entering column: the ratios rho[j] formed once, exactly as in step 4, LPX_BDUAL_SKIP_FIXED honoured.  mn = their minimum;
+ *       mn = +inf: LPX_INFEASIBLE.  Otherwise q = the lowest j with rho[j] <= mn + ratio_tol (one addition).  There is no
+ *       hysteresis scan.  (A negative ratio_tol leaves no such j; q is then the first index of the minimum.)
+ *   4.1-4.5  No passes of the long step.
+ * The pivot arithmetic, the trace entry, kind0 / kind1, the cutoff test and the event limit are unchanged.  Bland's rule cannot
+ * cycle while it is on, and it is on until the objective has moved by more than eps, so a node either makes progress every S + a
+ * bounded number of pivots or ends.  lpx_guard_record reports the pivots made in Bland mode and the event index of the first.
+ *
+ * lpx_bounded_node4(t, K, cols, lower, upper, o, flags, cutoff, stall_events, nint, is_int, tol, form, out, guard): stall_events = 0
+ * is lpx_bounded_node3 in every form, bit for bit (same kernels), guard = {0, -1}.  stall_events > 0 needs the on-chip form and
+ * runs the guarded kernel: ONE launch, ONE wait, the same LDS rule (lpx_bounded_node_fits).  LPX_EINVAL before any device check:
+ * stall_events < 0 ("stall_events is negative"); stall_events > 0 with LPX_NODE_LAUNCHES, or with LPX_NODE_AUTO on a shape that
+ * does not fit ("the stall guard has no launches form"); and the argument errors of lpx_bounded_node3 with the new name in front.
+ * guard may be NULL.  What the call leaves on the handle is what lpx_bounded_node3 leaves.
+ *
+ * lpx_node_batch_run2(b, B, slot, K, cols, lower, upper, o, flags, cutoff, stall_events, nint, is_int, tol, out, guard, rc):
+ * lpx_node_batch_run's contract word for word, with lpx_bounded_node4(..., stall_events, ..., LPX_NODE_ONCHIP, &out[i], &guard[i])
+ * as the single-node equal of entry i and "lpx_node_batch_run2" in front of the messages; stall_events is one value for the batch
+ * and a negative one is LPX_EINVAL.  stall_events = 0 is lpx_node_batch_run bit for bit.  guard ([B]) may be NULL.
+ *
+ * lpx_solve_bnb_bounded7(p, lower, upper, is_int, o, max_nodes, search_flags, divers, stall_events, out, info, dinfo, ginfo): the
+ * search of lpx_solve_bnb_bounded4 with step 4 done by lpx_node_batch_run2(stall_events).  stall_events = 0 is
+ * lpx_solve_bnb_bounded4 bit for bit.  ginfo (or NULL): guarded_nodes (nodes with a pivot in Bland mode), bland_events (those
+ * pivots) and max_events (the most events any one node made); plain counters, no free function.  LPX_EINVAL before any device
+ * check: those of lpx_solve_bnb_bounded4 under the new name and stall_events < 0.  On a search where the guard never fires the
+ * log is lpx_solve_bnb_bounded4's bit for bit.  stall_events = 50 is a reasonable value (DESIGN.md section 4.21 has counts at 20,
+ * 50 and 200).  The launches form, the plunge, the probes and strong branching have no guard. */
+typedef struct lpx_guard_record {        /* 8 bytes */
+    int32_t bland_events;  /* pivots made in Bland mode */
+    int32_t first_bland;   /* event index of the first of them, -1 = none */
+} lpx_guard_record;
+typedef struct lpx_bnb_guard_info {      /* 24 bytes */
+    int64_t guarded_nodes, bland_events, max_events;
+} lpx_bnb_guard_info;
+int  lpx_bounded_node4(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const lpx_run_opts* o,
+                       int flags, double cutoff, int stall_events, int nint, const uint8_t* is_int /* [nint] or NULL = all */, double tol,
+                       int form, lpx_node_record* out, lpx_guard_record* guard /* or NULL */);
+int  lpx_node_batch_run2(lpx_node_batch* b, int B, const int32_t* slot /* [B] */, const int32_t* K /* [B] */,
+                         const int32_t* cols, const double* lower, const double* upper /* concatenated, sum of K */,
+                         const lpx_run_opts* o, int flags, const double* cutoff /* [B]; read only with LPX_BDUAL_CUTOFF */,
+                         int stall_events, int nint, const uint8_t* is_int /* [nint] or NULL = all */, double tol,
+                         lpx_node_record* out /* [B] */, lpx_guard_record* guard /* [B] or NULL */, int32_t* rc /* [B] */);
+int  lpx_solve_bnb_bounded7(const lpx_problem* p, const double* lower /* [n] or NULL = 0 */, const double* upper /* [n] */,
+                            const uint8_t* is_int /* [n] or NULL = all */, const lpx_solve_opts* o, int64_t max_nodes /* 0 = none */,
+                            int search_flags, int divers /* W, 1..1024 */, int stall_events, lpx_result* out,
+                            lpx_bnb_bounded_info* info /* or NULL */, lpx_bnb_divers_info* dinfo /* or NULL */,
+                            lpx_bnb_guard_info* ginfo /* or NULL */);
 
 #ifdef __cplusplus
 }

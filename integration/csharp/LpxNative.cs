@@ -150,6 +150,18 @@ namespace Linear_Programming_Solver.Native
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public struct LpxGuardRecord                 // lpx_guard_record: 8 bytes
+    {
+        public int bland_events, first_bland;    // pivots made in Bland mode; event index of the first, -1 = none
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct LpxBnbGuardInfo                // lpx_bnb_guard_info: 24 bytes of counters, nothing to free
+    {
+        public long guarded_nodes, bland_events, max_events;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public unsafe struct LpxBoundedInfo          // lpx_bounded_info  (lpx_solve_bounded; free with lpx_bounded_info_free)
     {
         public int ncols, n;
@@ -371,6 +383,19 @@ namespace Linear_Programming_Solver.Native
                                                         int probe_iter, out LpxResult result, out LpxBnbBoundedInfo info,
                                                         out LpxBnbDiversInfo dinfo, out LpxBnbStrongInfo sinfo);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern void lpx_bnb_strong_info_free(ref LpxBnbStrongInfo sinfo);
+        // the stall guard: stall_events = 0 is lpx_bounded_node3 / lpx_node_batch_run / lpx_solve_bnb_bounded4; guard / guards may be null
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_bounded_node4(IntPtr tableau, int K, int* cols, double* lower, double* upper, IntPtr opts, int flags,
+                                                   double cutoff, int stall_events, int nint, byte* is_int, double tol, int form,
+                                                   out LpxNodeRecord record, LpxGuardRecord* guard);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_node_batch_run2(IntPtr batch, int B, int* slot, int* K, int* cols, double* lower, double* upper, IntPtr opts,
+                                                     int flags, double* cutoff, int stall_events, int nint, byte* is_int, double tol,
+                                                     LpxNodeRecord* records, LpxGuardRecord* guards, int* rc);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_bnb_bounded7(ref LpxProblem p, double* lower, double* upper, byte* is_int, ref LpxSolveOpts o,
+                                                        long max_nodes, int search_flags, int divers, int stall_events, out LpxResult result,
+                                                        out LpxBnbBoundedInfo info, out LpxBnbDiversInfo dinfo, out LpxBnbGuardInfo ginfo);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_solve_bounded_dual(ref LpxProblem p, double* lower, double* upper, int flags, ref LpxSolveOpts o,
                                                         out LpxResult result, out LpxBoundedInfo info);

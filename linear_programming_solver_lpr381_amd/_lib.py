@@ -167,6 +167,16 @@ class BnbStrongInfo(C.Structure):
                 ("pruned_by_probe", C.c_int64), ("changed_picks", C.c_int64)]
 
 
+class GuardRecord(C.Structure):
+    """lpx_guard_record (include/lpx.h): the pivots a node made in Bland mode and the event index of the first (-1: none)."""
+    _fields_ = [("bland_events", C.c_int32), ("first_bland", C.c_int32)]
+
+
+class BnbGuardInfo(C.Structure):
+    """lpx_bnb_guard_info (include/lpx.h): the stall-guard counters of lpx_solve_bnb_bounded7."""
+    _fields_ = [("guarded_nodes", C.c_int64), ("bland_events", C.c_int64), ("max_events", C.c_int64)]
+
+
 class Parsed(C.Structure):
     _fields_ = [("sense", C.c_int), ("n", C.c_int), ("m", C.c_int), ("c", dp), ("A", dp), ("rel", ip),
                 ("b", dp), ("ragged", C.c_int)]
@@ -374,6 +384,13 @@ def lib() -> C.CDLL:
                                          C.POINTER(BnbStrongInfo)]
     L.lpx_bnb_strong_info_free.argtypes = [C.POINTER(BnbStrongInfo)]
     L.lpx_bnb_strong_info_free.restype = None
+    L.lpx_bounded_node4.argtypes = [vp, C.c_int, ip, dp, dp, C.POINTER(RunOpts), C.c_int, C.c_double, C.c_int, C.c_int, u8p, C.c_double,
+                                    C.c_int, C.POINTER(NodeRecord), C.POINTER(GuardRecord)]
+    L.lpx_node_batch_run2.argtypes = [vp, C.c_int, ip, ip, ip, dp, dp, C.POINTER(RunOpts), C.c_int, dp, C.c_int, C.c_int, u8p, C.c_double,
+                                      C.POINTER(NodeRecord), C.POINTER(GuardRecord), ip]
+    L.lpx_solve_bnb_bounded7.argtypes = [C.POINTER(Problem), dp, dp, u8p, C.POINTER(SolveOpts), C.c_int64, C.c_int, C.c_int, C.c_int,
+                                         C.POINTER(Result), C.POINTER(BnbBoundedInfo), C.POINTER(BnbDiversInfo),
+                                         C.POINTER(BnbGuardInfo)]
     L.lpx_solve_bounded_dual.argtypes = [C.POINTER(Problem), dp, dp, C.c_int, C.POINTER(SolveOpts), C.POINTER(Result),
                                          C.POINTER(BoundedInfo)]
     L.lpx_parse_text.argtypes = [C.c_char_p, C.POINTER(Parsed)]

@@ -163,8 +163,16 @@ SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<doubl
 // With `strong` it is the search of lpx_solve_bnb_bounded6(LPX_BRANCH_STRONG): the same rounds with probes behind the nodes.
 SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
-                             int search_flags, int divers, BnbDiversInfo& dinfo, const BnbStrong* strong, BnbStrongInfo* sinfo)
+                             int search_flags, int divers, BnbDiversInfo& dinfo, const BnbStrong* strong, BnbStrongInfo* sinfo,
+                             int stall_events, BnbGuardInfo* ginfo)
 {
+    // stall_events >= 0 (lpx_solve_bnb_bounded7): the evaluate step is ONE lpx_node_batch_run2, which with 0 is lpx_node_batch_run;
+    // the guard records are counted and nothing else of the search reads them.
+    BnbGuardInfo gdummy;
+    BnbGuardInfo& gi = ginfo ? *ginfo : gdummy;
+    gi = BnbGuardInfo();
+    const bool guarded = stall_events >= 0 && !strong;
+    std::vector<lpx_guard_record> guards;
     // strong != null (lpx_solve_bnb_bounded6 with LPX_BRANCH_STRONG): the evaluate step is ONE lpx_node_batch_run_probe and the
     // decide step takes the variable and drops the dead children by the probes; everything else is the search below, unchanged.
     BnbStrongInfo sdummy;
@@ -291,6 +299,11 @@ SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double
             rc = lpx_node_batch_run_probe(pool.batch, B, slot.data(), Ks.data(), cols.data(), clo.data(), cub.data(), &o,
                                           LPX_BDUAL_SKIP_FIXED | search_flags, cutoffs.data(), prunes.data(), n, mask, EPS,
                                           strong->cand_max, strong->probe_iter, recs.data(), heads.data(), probes.data(), rcs.data());
+        } else if (guarded) {
+            guards.resize((size_t)B);
+            rc = lpx_node_batch_run2(pool.batch, B, slot.data(), Ks.data(), cols.data(), clo.data(), cub.data(), &o,
+                                     LPX_BDUAL_SKIP_FIXED | search_flags, cutoffs.data(), stall_events, n, mask, EPS, recs.data(),
+                                     guards.data(), rcs.data());
         } else
             rc = lpx_node_batch_run(pool.batch, B, slot.data(), Ks.data(), cols.data(), clo.data(), cub.data(), &o,
                                     LPX_BDUAL_SKIP_FIXED | search_flags, cutoffs.data(), n, mask, EPS, recs.data(), rcs.data());
@@ -320,6 +333,10 @@ SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double
             lg.var = rec.pick.var; lg.z = rec.pick.z;
             info.log.push_back(lg);
             dinfo.round.push_back(round); dinfo.diver.push_back(slot[i]);
+            if (guarded) {
+                if (guards[i].bland_events > 0) { gi.guarded_nodes++; gi.bland_events += guards[i].bland_events; }
+                if (rec.events > gi.max_events) gi.max_events = rec.events;
+            }
             if (rec.status == LPX_ITER_LIMIT) {
                 info.limit_rc = LPX_ITER_LIMIT;
                 info.limit_msg = "Bounded Branch and Bound: node " + std::to_string(index) + " (depth " + std::to_string(node.depth) +

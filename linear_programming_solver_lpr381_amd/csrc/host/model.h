@@ -252,11 +252,15 @@ struct BnbDiversInfo { int64_t rounds = 0, steals = 0, largest_batch = 0; std::v
 // Strong branching (lpx_solve_bnb_bounded6 with LPX_BRANCH_STRONG): SolveBnbDivers whose round is ONE lpx_node_batch_run_probe and
 // whose decide step chooses the variable, and drops the dead children, by the probes of up to cand_max candidates.
 struct BnbStrong { int cand_max = 4, probe_iter = 0; };
+// The stall guard (lpx_solve_bnb_bounded7): nodes with a pivot in Bland mode, those pivots, the most events of one node.
+struct BnbGuardInfo { int64_t guarded_nodes = 0, bland_events = 0, max_events = 0; };
 struct BnbStrongInfo { int64_t probe_launches = 0, probes = 0, probe_events = 0, probe_limit = 0, pruned_by_probe = 0, changed_picks = 0; };
 SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
                              int search_flags, int divers, BnbDiversInfo& dinfo, const struct BnbStrong* strong = nullptr,
-                             struct BnbStrongInfo* sinfo = nullptr);
+                             struct BnbStrongInfo* sinfo = nullptr,
+                             int stall_events = -1,       // lpx_solve_bnb_bounded7: >= 0, the round is ONE lpx_node_batch_run2 (never with strong)
+                             struct BnbGuardInfo* ginfo = nullptr);
 // The search by W divers that plunge (lpx_solve_bnb_bounded5): one lpx_node_batch_plunge per round, up to `plunge` nodes per diver.
 struct BnbPlungeInfo { int64_t launched = 0, dropped = 0, longest_chain = 0; std::vector<int32_t> step; };
 SimplexResult SolveBnbPlunge(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,

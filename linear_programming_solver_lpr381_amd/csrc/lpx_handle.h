@@ -116,6 +116,7 @@ void node_onchip_commit(lpx_tableau* t, const NodeOut* rec, bool any_lo, lpx_nod
 // an accepted bound edit, for Bounds::whole: which of the edited columns now have finite integral bounds
 void bounds_note_edit(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper);
 int bounded_plunge_ready(const char* what);     // the one-time attribute of the plunge kernel
+int bounded_guard_ready(const char* what);      // the one-time attribute of the guarded node kernel (lpx_bounded_guard.hip)
 // the probes (lpx_bounded_probe.hip), shared by lpx_bounded_probe and lpx_node_batch_run_probe
 int bounded_probe_ready(const char* what);      // the one-time attribute of the probe kernel
 int check_probe_args(int cand_max, int probe_iter, const char* what);      // LPX_EINVAL with `what` in front, no device

@@ -95,7 +95,8 @@ hipError_t launch_branch_pick(const PickParams& p, hipStream_t s);
 // the on-chip node (lpx_bounded_node.hip): one launch of one workgroup evaluates a whole node with the tableau in LDS
 // What a node call sends: this header and behind it lower[K], upper[K] (double) and cols[K] (int32), in the handle's pinned slab.
 struct NodeIn {
-    int32_t K, flags, nint, has_mask, max_iter, lo_used, pad[2];       // lo_used: the handle has stored a lower shift (this edit included)
+    int32_t K, flags, nint, has_mask, max_iter, lo_used;               // lo_used: the handle has stored a lower shift (this edit included)
+    int32_t stall_events, pad;                                         // stall_events: read by the guarded node alone (lpx_bounded_guard.hip)
     double eps, ratio_tol, cutoff, tol;
 };
 static_assert(sizeof(NodeIn) == 64, "the arrays behind the header start on a double");
@@ -119,6 +120,13 @@ hipError_t bounded_node_init();                     // one-time function attribu
 hipError_t launch_bounded_node_onchip(const NodeParams& n, hipStream_t s);
 // the batch: workgroup b evaluates P[b] (an array the device can read); lds = the largest entry's bounded_node_lds_bytes
 hipError_t launch_bounded_nodes_onchip(const NodeParams* P, int B, size_t lds, hipStream_t s);
+// the guarded node (lpx_bounded_guard.hip): the on-chip node with the stall guard of include/lpx.h in its dual loop, NodeIn::stall_events
+// > 0.  One batch-shaped kernel: workgroup b evaluates P[b] (an array the device can read); the single node is a batch of one.  Behind
+// each NodeOut, in the same 64-byte slot of the slab, it leaves the guard record.
+struct GuardOut { NodeOut o; int32_t bland_events, first_bland; };
+static_assert(sizeof(GuardOut) == 64, "the node record and the guard record share one 64-byte slot");
+hipError_t bounded_guard_init();                    // one-time function attribute
+hipError_t launch_bounded_guard_onchip(const NodeParams* P, int B, size_t lds, hipStream_t s);
 // the plunge (lpx_bounded_plunge.hip): workgroup b evaluates a chain of up to P[b].depth nodes with the tile staying in LDS.
 // n.out is the first of `depth` records, 64 bytes apart; *steps = the records written; the chain stops at z <= prune.
 struct PlungeParams { NodeParams n; double prune; int32_t* steps; int32_t depth, pad; };

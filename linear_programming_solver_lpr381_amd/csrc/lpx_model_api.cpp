@@ -373,7 +373,8 @@ static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const do
                             int64_t max_nodes, int search_flags, lpx_result* out, lpx_bnb_bounded_info* info, const char* what,
                             int node_form = -1, int divers = 0, lpx_bnb_divers_info* dinfo = nullptr,     // divers > 0: lpx_solve_bnb_bounded4
                             int plunge = 0, lpx_bnb_plunge_info* pinfo = nullptr,                         // plunge > 0: lpx_solve_bnb_bounded5
-                            const BnbStrong* strong = nullptr, lpx_bnb_strong_info* sinfo = nullptr)      // strong: lpx_solve_bnb_bounded6, LPX_BRANCH_STRONG
+                            const BnbStrong* strong = nullptr, lpx_bnb_strong_info* sinfo = nullptr,      // strong: lpx_solve_bnb_bounded6, LPX_BRANCH_STRONG
+                            int stall_events = -1, lpx_bnb_guard_info* ginfo = nullptr)                   // stall_events >= 0: lpx_solve_bnb_bounded7
 {
     if (!p || !out) { set_error(std::string(what) + ": null argument"); return LPX_EINVAL; }
     std::memset(out, 0, sizeof(*out));
@@ -381,6 +382,7 @@ static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const do
     if (dinfo) std::memset(dinfo, 0, sizeof(*dinfo));
     if (pinfo) std::memset(pinfo, 0, sizeof(*pinfo));
     if (sinfo) std::memset(sinfo, 0, sizeof(*sinfo));
+    if (ginfo) std::memset(ginfo, 0, sizeof(*ginfo));
     lpx_solve_opts d; if (!o) { lpx_default_solve_opts(&d); o = &d; }
     return guarded(what, [&]() -> int {
         EngineOptions e = to_engine(o);
@@ -394,11 +396,14 @@ static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const do
         BnbDiversInfo di;
         BnbPlungeInfo pi;
         BnbStrongInfo si;
-        SimplexResult r = strong ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di, strong, &si)
+        BnbGuardInfo gi;
+        SimplexResult r = stall_events >= 0 ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di, nullptr, nullptr, stall_events, &gi)
+                        : strong ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di, strong, &si)
                         : plunge ? SolveBnbPlunge(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, plunge, di, pi)
                         : divers ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di)
                                  : SolveBnbBounded(q, lo, up, mask, e, max_nodes, bi, search_flags, node_form);
         fill_result(out, r, p->n);
+        if (ginfo) { ginfo->guarded_nodes = gi.guarded_nodes; ginfo->bland_events = gi.bland_events; ginfo->max_events = gi.max_events; }
         if (sinfo) {
             sinfo->probe_launches = si.probe_launches; sinfo->probes = si.probes; sinfo->probe_events = si.probe_events;
             sinfo->probe_limit = si.probe_limit; sinfo->pruned_by_probe = si.pruned_by_probe; sinfo->changed_picks = si.changed_picks;
@@ -478,6 +483,16 @@ int lpx_solve_bnb_bounded6(const lpx_problem* p, const double* lower, const doub
     BnbStrong st; st.cand_max = cand_max; st.probe_iter = probe_iter;
     return solve_bnb_bounded(p, lower, upper, is_int, o, max_nodes, search_flags, out, info, "lpx_solve_bnb_bounded6", -1, divers, dinfo,
                              0, nullptr, branching == LPX_BRANCH_STRONG ? &st : nullptr, sinfo);
+}
+
+int lpx_solve_bnb_bounded7(const lpx_problem* p, const double* lower, const double* upper, const uint8_t* is_int,
+                           const lpx_solve_opts* o, int64_t max_nodes, int search_flags, int divers, int stall_events, lpx_result* out,
+                           lpx_bnb_bounded_info* info, lpx_bnb_divers_info* dinfo, lpx_bnb_guard_info* ginfo)
+{
+    if (divers < 1 || divers > 1024) { set_error("lpx_solve_bnb_bounded7: divers is outside [1, 1024]"); return LPX_EINVAL; }
+    if (stall_events < 0) { set_error("lpx_solve_bnb_bounded7: stall_events is negative"); return LPX_EINVAL; }
+    return solve_bnb_bounded(p, lower, upper, is_int, o, max_nodes, search_flags, out, info, "lpx_solve_bnb_bounded7", -1, divers, dinfo,
+                             0, nullptr, nullptr, nullptr, stall_events, ginfo);
 }
 
 void lpx_bnb_strong_info_free(lpx_bnb_strong_info* sinfo)

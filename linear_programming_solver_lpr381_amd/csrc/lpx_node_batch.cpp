@@ -3,6 +3,8 @@
 // lpx_bounded_node3 on its handle, bit for bit; the checks and what a finished node leaves on its handle are shared with it
 // (lpx_tableau_bounded.cpp, through lpx_handle.h).  lpx_node_batch_run_probe is the same body with the probe launch
 // (lpx_bounded_probe.hip) enqueued behind the node launch: two launches, one wait.
+// lpx_node_batch_run2 is the same body again with the stall guard (include/lpx.h): stall_events = 0 is lpx_node_batch_run's launch, above 0
+// the one launch is lpx_bounded_guard_onchip (lpx_bounded_guard.hip), which leaves a guard record behind each node record.
 #include "lpx_handle.h"
 
 #include <algorithm>
@@ -94,14 +96,20 @@ void lpx_node_batch_destroy(lpx_node_batch* b)
 // lpx_node_batch_run (pr = null, name its own) and lpx_node_batch_run_probe in one body: with pr the probe launch goes behind the
 // node launch on the same stream and the one wait covers both.
 struct ProbeArgs { const double* prune; int cand_max, probe_iter; lpx_probe_head* head; lpx_probe_record* probes; };
+// lpx_node_batch_run2 in the same body (gd non-null, never together with pr): with stall_events > 0 the one launch is the guarded
+// kernel's (lpx_bounded_guard.hip), which leaves a guard record in the 64-byte slot of each node record.
+struct GuardArgs { int stall_events; lpx_guard_record* guard; };
 
 static int node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const int32_t* K, const int32_t* cols, const double* lower,
                           const double* upper, const lpx_run_opts* o, int flags, const double* cutoff, int nint, const uint8_t* is_int,
-                          double tol, lpx_node_record* out, int32_t* rc, const ProbeArgs* pr, const char* name)
+                          double tol, lpx_node_record* out, int32_t* rc, const ProbeArgs* pr, const char* name,
+                          const GuardArgs* gd = nullptr)
 {
     const std::string w = name;
+    const int stall_events = gd ? gd->stall_events : 0;
     // ---- 1. every argument of every entry, before anything is written and before any device check
     if (!slot || !K || !out || !rc) { set_error(w + ": null " + (!slot ? "slot" : !K ? "K" : !out ? "out" : "rc")); return LPX_EINVAL; }
+    if (stall_events < 0) { set_error(w + ": stall_events is negative"); return LPX_EINVAL; }
     if (pr) {
         if (!pr->prune || !pr->head || !pr->probes) { set_error(w + ": null " + (!pr->prune ? "prune" : !pr->head ? "head" : "probes")); return LPX_EINVAL; }
         int r = check_probe_args(pr->cand_max, pr->probe_iter, name); if (r) return r;
@@ -145,6 +153,8 @@ static int node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const i
     }
     int r = ensure_device(); if (r) return r;
     if (pr) { r = bounded_probe_ready(name); if (r) return r; }
+    if (stall_events > 0) { r = bounded_guard_ready(name); if (r) return r; }
+    if (gd && gd->guard) for (int i = 0; i < B; ++i) { gd->guard[i].bland_events = 0; gd->guard[i].first_bland = -1; }
 
     // ---- 2. the buffers: grown to twice the need, and only when the need outgrows them
     const size_t nrec = pr ? 2 * (size_t)pr->cand_max : 0;
@@ -200,6 +210,7 @@ static int node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const i
         in->K = k; in->flags = flags; in->nint = nint; in->has_mask = has_mask ? 1 : 0; in->max_iter = o->max_iter;
         in->lo_used = (bn.lo_used || any_lo) ? 1 : 0;
         in->eps = o->eps; in->ratio_tol = o->ratio_tol; in->cutoff = (flags & LPX_BDUAL_CUTOFF) ? cutoff[i] : 0.0; in->tol = tol;
+        in->stall_events = stall_events;
         if (k > 0) {
             double* a = reinterpret_cast<double*>(in + 1);
             std::memcpy(a, lw, sizeof(double) * k);
@@ -224,7 +235,8 @@ static int node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const i
 
     // ---- 4. behind the handles' own streams, ONE launch (with pr: the probes behind it), ONE wait
     r = settle_all(b); if (r) return r;
-    LPX_HIP_TRY(launch_bounded_nodes_onchip(P, B, lds, s));
+    if (stall_events > 0) LPX_HIP_TRY(launch_bounded_guard_onchip(P, B, lds, s));
+    else LPX_HIP_TRY(launch_bounded_nodes_onchip(P, B, lds, s));
     if (pr) LPX_HIP_TRY(launch_bounded_probe_onchip(reinterpret_cast<const ProbeParams*>(b->slab + o_pp), B, pr->cand_max, lds, s));
     LPX_HIP_TRY(hipStreamSynchronize(s));
     if (pr) {
@@ -240,6 +252,10 @@ static int node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const i
         const size_t at0 = sumK;
         sumK += (size_t)K[i];
         const NodeOut* rec = reinterpret_cast<const NodeOut*>(b->slab + o_out + kOut * (size_t)i);
+        if (stall_events > 0 && gd->guard) {
+            const GuardOut* g = reinterpret_cast<const GuardOut*>(rec);
+            gd->guard[i].bland_events = g->bland_events; gd->guard[i].first_bland = g->first_bland;
+        }
         if (rec->status < 0) {                                           // refused by the kernel: this handle is as it was
             rc[i] = LPX_EINVAL;
             out[i].unrepairable = rec->unrepairable;
@@ -264,6 +280,14 @@ int lpx_node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const int3
                        double tol, lpx_node_record* out, int32_t* rc)
 {
     return node_batch_run(b, B, slot, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, rc, nullptr, "lpx_node_batch_run");
+}
+
+int lpx_node_batch_run2(lpx_node_batch* b, int B, const int32_t* slot, const int32_t* K, const int32_t* cols, const double* lower,
+                        const double* upper, const lpx_run_opts* o, int flags, const double* cutoff, int stall_events, int nint,
+                        const uint8_t* is_int, double tol, lpx_node_record* out, lpx_guard_record* guard, int32_t* rc)
+{
+    const GuardArgs gd{stall_events, guard};
+    return node_batch_run(b, B, slot, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, rc, nullptr, "lpx_node_batch_run2", &gd);
 }
 
 int lpx_node_batch_run_probe(lpx_node_batch* b, int B, const int32_t* slot, const int32_t* K, const int32_t* cols, const double* lower,

@@ -306,6 +306,14 @@ int lpx::bounded_plunge_ready(const char* what)
     return 0;
 }
 
+int lpx::bounded_guard_ready(const char* what)
+{
+    static std::once_flag once; static hipError_t init_err = hipSuccess;
+    std::call_once(once, [] { init_err = bounded_guard_init(); });
+    if (init_err != hipSuccess) { set_error(std::string(what) + ": kernel attribute setup failed: " + hipGetErrorString(init_err)); return LPX_EDEVICE; }
+    return 0;
+}
+
 int lpx::bounded_probe_ready(const char* what)
 {
     static std::once_flag once; static hipError_t init_err = hipSuccess;
@@ -608,18 +616,23 @@ int lpx_bounded_node_fits(int R, int C) { return bounded_node_fits(R, C); }
 
 // The steady state of a call: the inputs written into the handle's pinned slab, one kernel launch, one wait, the record read
 // from the same slab.  Allocations and the copy of the integer mask happen only when K outgrows the slab or the mask's bytes change.
+// stall_events > 0 (lpx_bounded_node4): the launch is the guarded kernel's (lpx_bounded_guard.hip) as a batch of one, its parameter
+// record in the slab behind the triples; everything else is the same call.
 static int bounded_node_onchip(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const lpx_run_opts* o,
-                               int flags, double cutoff, int nint, const uint8_t* is_int, double tol, lpx_node_record* out, const char* what)
+                               int flags, double cutoff, int nint, const uint8_t* is_int, double tol, lpx_node_record* out, const char* what,
+                               int stall_events = 0, lpx_guard_record* guard = nullptr)
 {
     const std::string w = what;
     int rc = bounded_ready(t, true); if (rc) return rc;
-    rc = bounded_node_ready(what); if (rc) return rc;
+    rc = stall_events > 0 ? bounded_guard_ready(what) : bounded_node_ready(what); if (rc) return rc;
+    if (guard) { guard->bland_events = 0; guard->first_bland = -1; }
     lpx_tableau::Bounds& b = t->bnd;
     std::memset(out, 0, sizeof(*out));
     out->pick.var = -1;
     constexpr size_t kOut = 64, kHdr = kOut + sizeof(NodeIn);
     static_assert(sizeof(NodeOut) <= kOut, "slab layout");
-    const size_t need = kHdr + (size_t)K * (2 * sizeof(double) + sizeof(int32_t));
+    const size_t o_par = (kHdr + (size_t)K * (2 * sizeof(double) + sizeof(int32_t)) + 15) & ~(size_t)15;
+    const size_t need = stall_events > 0 ? o_par + sizeof(NodeParams) : kHdr + (size_t)K * (2 * sizeof(double) + sizeof(int32_t));
     if (need > b.nodeio_bytes) {
         LPX_HIP_TRY(hipStreamSynchronize(t->stream));
         if (b.nodeio) hipHostFree(b.nodeio);
@@ -649,6 +662,7 @@ static int bounded_node_onchip(lpx_tableau* t, int K, const int32_t* cols, const
     in->K = K; in->flags = flags; in->nint = nint; in->has_mask = has_mask ? 1 : 0; in->max_iter = o->max_iter;
     in->lo_used = (b.lo_used || any_lo) ? 1 : 0;
     in->eps = o->eps; in->ratio_tol = o->ratio_tol; in->cutoff = cutoff; in->tol = tol;
+    in->stall_events = stall_events;
     if (K > 0) {
         double* a = reinterpret_cast<double*>(in + 1);
         std::memcpy(a, lower, sizeof(double) * K);
@@ -660,8 +674,17 @@ static int bounded_node_onchip(lpx_tableau* t, int K, const int32_t* cols, const
     n.rhsbuf = t->rhsbuf; n.basis = t->basis; n.trace = t->trace; n.trace_cap = t->trace_cap; n.st = t->st;
     n.ub = b.ub; n.lo = b.lo; n.flip = b.flip; n.edit = reinterpret_cast<double*>(b.chg); n.mask = b.pickmask;
     n.in = in; n.out = rec;
-    LPX_HIP_TRY(launch_bounded_node_onchip(n, t->stream));
+    if (stall_events > 0) {
+        NodeParams* P = reinterpret_cast<NodeParams*>(b.nodeio + o_par);
+        *P = n;
+        LPX_HIP_TRY(launch_bounded_guard_onchip(P, 1, bounded_node_lds_bytes(t->R, t->C), t->stream));
+    } else
+        LPX_HIP_TRY(launch_bounded_node_onchip(n, t->stream));
     LPX_HIP_TRY(hipStreamSynchronize(t->stream));                                // the one wait: the record is in the slab
+    if (stall_events > 0 && guard) {
+        const GuardOut* g = reinterpret_cast<const GuardOut*>(rec);
+        guard->bland_events = g->bland_events; guard->first_bland = g->first_bland;
+    }
     if (rec->status < 0) {                                                       // refused by the kernel: the handle is as it was
         if (rec->inf_k >= 0) { set_error(w + ": upper[" + std::to_string(rec->inf_k) + "] = +inf on a flipped column"); return LPX_EINVAL; }
         out->unrepairable = rec->unrepairable;
@@ -689,6 +712,29 @@ int lpx_bounded_node3(lpx_tableau* t, int K, const int32_t* cols, const double* 
     rc = check_node_opts(t, o, what); if (rc) return rc;
     rc = check_node_fits(t, what); if (rc) return rc;
     return bounded_node_onchip(t, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, what);
+}
+
+// The node with the stall guard (include/lpx.h, "stall guard").  stall_events = 0 is lpx_bounded_node3 in every form; above 0 only
+// the on-chip form exists (kernel in lpx_bounded_guard.hip).
+int lpx_bounded_node4(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const lpx_run_opts* o,
+                      int flags, double cutoff, int stall_events, int nint, const uint8_t* is_int, double tol, int form,
+                      lpx_node_record* out, lpx_guard_record* guard)
+{
+    const char* what = "lpx_bounded_node4";
+    const std::string w = what;
+    int rc = check_long_flags(flags, cutoff, what); if (rc) return rc;
+    if (form != LPX_NODE_LAUNCHES && form != LPX_NODE_ONCHIP && form != LPX_NODE_AUTO) { set_error(w + ": unknown form"); return LPX_EINVAL; }
+    if (stall_events < 0) { set_error(w + ": stall_events is negative"); return LPX_EINVAL; }
+    if (guard) { guard->bland_events = 0; guard->first_bland = -1; }
+    const bool launches = form == LPX_NODE_LAUNCHES || (form == LPX_NODE_AUTO && t && !bounded_node_fits(t->R, t->C));
+    if (launches && stall_events > 0) { set_error(w + ": the stall guard has no launches form"); return LPX_EINVAL; }
+    if (launches) return bounded_node(t, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, what);
+    rc = check_change_args(t, K, cols, lower, upper, what); if (rc) return rc;
+    rc = check_pick_args(t, nint, tol, out, what); if (rc) return rc;
+    lpx_run_opts d; if (!o) { lpx_default_opts(&d, 1); o = &d; }
+    rc = check_node_opts(t, o, what); if (rc) return rc;
+    rc = check_node_fits(t, what); if (rc) return rc;
+    return bounded_node_onchip(t, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, what, stall_events, guard);
 }
 
 // ---- strong-branching probes of the handle as it stands (kernel in lpx_bounded_probe.hip): one launch, one wait, no write to the handle ----

@@ -344,7 +344,8 @@ class LPSolver:             # Models/LPSolver.cs:6-77
     def SolveBnbBounded(self, problem: LPProblem, upper, lower=None, integer=None, max_nodes: int = 0,
                         long_step: bool = False, cutoff: bool = False, node_form: Optional[str] = None,
                         divers: Optional[int] = None, plunge: Optional[int] = None, branching: Optional[str] = None,
-                        candidates: int = 4, probe_iter: Optional[int] = None) -> SimplexResult:
+                        candidates: int = 4, probe_iter: Optional[int] = None,
+                        stall_events: Optional[int] = None) -> SimplexResult:
         """Branch and bound by bound changes on one device tableau (lpx_solve_bnb_bounded): lower <= x <= upper, x_j integer
         where integer[j] (None: every variable); integer variables need finite, integral bounds.  Status OPTIMAL or INFEASIBLE,
         Solution, OptimalValue (user's sense), Nodes, BnbInfo (counters) and BnbLog, a structured array with one record per node
@@ -357,7 +358,8 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         evaluates one node per diver on chip in one kernel launch; divers=1 gives the log of node_form="onchip", any W gives a
         log that depends on the model, the flags and W alone.  Use long_step=True with divers on larger models: another W visits
         other nodes, and without the long step some of them make max_iter events and end the solve with ITER_LIMIT (on
-        binary_ip(128, 64), W = 4, 64 and 256 do; with the long step none measured did).  The result then carries BnbInfo["rounds" / "steals" /
+        binary_ip(128, 64), W = 4, 64 and 256 do; the long step makes it rare, not impossible; stall_events below ends such
+        nodes).  The result then carries BnbInfo["rounds" / "steals" /
         "largest_batch"] and BnbRound / BnbDiver, the round and the diver of every log record.  plunge=D
         (lpx_solve_bnb_bounded5, 1 <= D <= 64; without divers it means divers=1): a diver's workgroup goes on from a node that
         branches into its ceil child, up to D nodes per launch with the tableau staying in LDS.  plunge=1 gives the log of
@@ -369,7 +371,24 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         objective losses and never pushes a child whose probe ended infeasible, cut off or not above the incumbent + 1e-6;
         "most_fractional" gives the log of divers=W.  BnbInfo then carries probe_launches, probes, probe_events, probe_limit,
         pruned_by_probe and changed_picks.  It is a rule beside the default one: it visits fewer nodes and pays for every
-        node with a second launch."""
+        node with a second launch.  stall_events=S (lpx_solve_bnb_bounded7; None: the paths above, unchanged; without divers
+        it means divers=1): the search by divers whose nodes run with the stall guard -- after S pivots without progress of the
+        objective a node's loop selects by Bland's rule until the objective moves again, so a node that cycles at a degenerate
+        vertex ends instead of making max_iter events.  0 gives the log of divers=W; 50 is a reasonable value.  BnbInfo then
+        carries guarded_nodes, bland_events and max_events.  It cannot be combined with node_form="launches", plunge > 1 or
+        branching: those have no guard."""
+        if stall_events is not None:
+            if int(stall_events) < 0:
+                raise ValueError(f"stall_events = {stall_events}: stall_events must not be negative")
+            if node_form == "launches":
+                raise ValueError("the stall guard has no launches form: stall_events cannot be combined with node_form='launches'")
+            if plunge is not None and plunge > 1:
+                raise ValueError("the plunge has no stall guard: stall_events cannot be combined with plunge > 1")
+            if branching is not None:
+                raise ValueError("the probes have no stall guard: stall_events cannot be combined with branching")
+            if divers is None:
+                divers = 1
+            plunge = None
         if branching is not None:
             if branching not in _lib.BRANCHINGS:
                 raise ValueError(f"unknown branching rule {branching!r}")
@@ -409,7 +428,11 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         r, info, dinfo, pinfo = _lib.Result(), _lib.BnbBoundedInfo(), _lib.BnbDiversInfo(), _lib.BnbPlungeInfo()
         flags = (_lib.BDUAL_LONG_STEP if long_step else 0) | (_lib.BDUAL_CUTOFF if cutoff else 0)
         sinfo = _lib.BnbStrongInfo()
-        if branching is not None:
+        ginfo = _lib.BnbGuardInfo()
+        if stall_events is not None:
+            rc = lib().lpx_solve_bnb_bounded7(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), flags, int(divers),
+                                              int(stall_events), C.byref(r), C.byref(info), C.byref(dinfo), C.byref(ginfo))
+        elif branching is not None:
             cand = int(candidates)
             if cand < 1 or cand > 32:
                 raise ValueError(f"candidates = {cand}: candidates must be in [1, 32]")
@@ -445,6 +468,8 @@ class LPSolver:             # Models/LPSolver.cs:6-77
             if branching is not None:
                 counters.update({k: getattr(sinfo, k) for k in ("probe_launches", "probes", "probe_events", "probe_limit",
                                                                 "pruned_by_probe", "changed_picks")})
+            if stall_events is not None:
+                counters.update({k: getattr(ginfo, k) for k in ("guarded_nodes", "bland_events", "max_events")})
             if plunge is not None:
                 counters.update({k: getattr(pinfo, k) for k in ("launched", "dropped", "longest_chain")})
                 step = np.ctypeslib.as_array(pinfo.step, (info.n_log,)).copy() if info.n_log else np.zeros(0, dtype=np.int32)

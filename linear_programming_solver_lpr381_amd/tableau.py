@@ -338,18 +338,40 @@ class DeviceTableau:
 
     def bounded_node(self, cols, lower, upper, nint: int, is_int=None, tol: float = 1e-6,
                      opts: Optional[RunOpts] = None, long_step: bool = False, cutoff: Optional[float] = None,
-                     form: Optional[str] = None, **kw) -> dict:
+                     form: Optional[str] = None, stall_events: Optional[int] = None, **kw) -> dict:
         """One branch-and-bound node in one call (lpx_bounded_node): change_bounds, dualize, the dual loop in which fixed
         columns do not enter, and on OPTIMAL the branch pick.  long_step=True or a cutoff is lpx_bounded_node2: the loop runs
         with those flags and may end with status CUTOFF (no pick).  form "launches" | "onchip" | "auto" is lpx_bounded_node3:
         "onchip" evaluates the whole node in one kernel launch with the tableau in LDS (LpxError when bounded_node_fits() is
-        False), "auto" does so iff it fits; the results are bit-equal in every form.  Returns the node record as a dict."""
+        False), "auto" does so iff it fits; the results are bit-equal in every form.  stall_events=S (lpx_bounded_node4; None:
+        the calls above): the stall guard -- after S pivots without progress of the objective the loop selects by Bland's rule
+        until the objective moves again; 0 is the node without it, above 0 needs the on-chip form (form None means "onchip"
+        then).  The record then also carries bland_events and first_bland.  Returns the node record as a dict."""
         cols = np.ascontiguousarray(np.atleast_1d(cols), dtype=np.int32).reshape(-1)
         lower = np.ascontiguousarray(np.broadcast_to(np.asarray(lower, dtype=np.float64), cols.shape))
         upper = np.ascontiguousarray(np.broadcast_to(np.asarray(upper, dtype=np.float64), cols.shape))
         o = opts if opts is not None else default_opts(True, **kw)
         keep, mp = self._mask(is_int, int(nint))
         rec = _lib.NodeRecord()
+        if stall_events is not None:
+            if int(stall_events) < 0:
+                raise ValueError(f"stall_events = {stall_events}: stall_events must not be negative")
+            if form is None:
+                form = "onchip" if int(stall_events) > 0 else "launches"
+            if form not in _lib.NODE_FORMS:
+                raise ValueError(f"unknown node form {form!r}")
+            if int(stall_events) > 0 and form == "launches":
+                raise ValueError("the stall guard has no launches form: stall_events > 0 cannot be combined with form='launches'")
+            flags = (_lib.BDUAL_SKIP_FIXED | (_lib.BDUAL_LONG_STEP if long_step else 0)
+                     | (_lib.BDUAL_CUTOFF if cutoff is not None else 0))
+            g = _lib.GuardRecord()
+            check(lib().lpx_bounded_node4(self._h, len(cols), cols.ctypes.data_as(ip), lower.ctypes.data_as(dp),
+                                          upper.ctypes.data_as(dp), C.byref(o), flags, float(cutoff if cutoff is not None else 0.0),
+                                          int(stall_events), int(nint), mp, float(tol), _lib.NODE_FORMS[form], C.byref(rec),
+                                          C.byref(g)))
+            d = _node_dict(rec)
+            d["bland_events"], d["first_bland"] = g.bland_events, g.first_bland
+            return d
         if form is not None:
             if form not in _lib.NODE_FORMS:
                 raise ValueError(f"unknown node form {form!r}")
@@ -455,10 +477,14 @@ class NodeBatch:
         self.close()
 
     def run(self, slots, nodes, nint: int, is_int=None, tol: float = 1e-6, long_step: bool = False, cutoffs=None,
-            opts: Optional[RunOpts] = None, **kw) -> list:
+            opts: Optional[RunOpts] = None, stall_events: Optional[int] = None, **kw) -> list:
         """Entry i evaluates nodes[i] = (cols, lower, upper) on handles[slots[i]]; the slots are distinct.  cutoffs: one objective
         cutoff per entry (None: no cutoff).  Returns one record dict per entry in the shape of DeviceTableau.bounded_node; an
-        entry the kernel refused (its handle is as it was) has status None, and last_error() holds the first one's message."""
+        entry the kernel refused (its handle is as it was) has status None, and last_error() holds the first one's message.
+        stall_events=S (lpx_node_batch_run2; None: lpx_node_batch_run): every entry runs with the stall guard of
+        DeviceTableau.bounded_node and its record also carries bland_events and first_bland."""
+        if stall_events is not None and int(stall_events) < 0:
+            raise ValueError(f"stall_events = {stall_events}: stall_events must not be negative")
         slots = np.ascontiguousarray(np.atleast_1d(slots), dtype=np.int32).reshape(-1)
         B = len(slots)
         if len(nodes) != B:
@@ -485,12 +511,21 @@ class NodeBatch:
         keep, mp = DeviceTableau._mask(is_int, int(nint))
         recs = (_lib.NodeRecord * B)()
         rc = np.zeros(B, dtype=np.int32)
-        check(lib().lpx_node_batch_run(self._h, B, slots.ctypes.data_as(ip), K.ctypes.data_as(ip), cols.ctypes.data_as(ip),
-                                       lower.ctypes.data_as(dp), upper.ctypes.data_as(dp), C.byref(o), flags, cp, int(nint), mp,
-                                       float(tol), recs, rc.ctypes.data_as(ip)))
+        guards = None
+        if stall_events is not None:
+            guards = (_lib.GuardRecord * B)()
+            check(lib().lpx_node_batch_run2(self._h, B, slots.ctypes.data_as(ip), K.ctypes.data_as(ip), cols.ctypes.data_as(ip),
+                                            lower.ctypes.data_as(dp), upper.ctypes.data_as(dp), C.byref(o), flags, cp,
+                                            int(stall_events), int(nint), mp, float(tol), recs, guards, rc.ctypes.data_as(ip)))
+        else:
+            check(lib().lpx_node_batch_run(self._h, B, slots.ctypes.data_as(ip), K.ctypes.data_as(ip), cols.ctypes.data_as(ip),
+                                           lower.ctypes.data_as(dp), upper.ctypes.data_as(dp), C.byref(o), flags, cp, int(nint), mp,
+                                           float(tol), recs, rc.ctypes.data_as(ip)))
         out = []
         for i in range(B):
             d = _node_dict(recs[i])
+            if guards is not None:
+                d["bland_events"], d["first_bland"] = guards[i].bland_events, guards[i].first_bland
             if rc[i] < 0:
                 d["status"] = None
             out.append(d)

@@ -41,12 +41,20 @@ C candidates, probes of at most L events (no L: the node's limit); per model and
 alternate in one process, REPS timed solves each after one untimed solve; nodes, events, rounds, probes, probe events, children
 pruned by a probe, changed picks and wall per side, and `wins`: a setting wins iff its median lies below the baseline's minimum.
 `--branching R [--candidates C] [--probe-iter L]` makes side (b), and `--trace-only`, the search with that rule.
+`--compare-guard LIST` measures the stall guard (lpx_solve_bnb_bounded7) at the W of `--divers` (default 1)
+against the same search without it: LIST is comma-separated values of stall_events; per model and flag set the baseline
+(divers=W, the kernels without the guard) and each S alternate in one process, REPS timed solves each after one untimed solve;
+nodes, events, rounds, guarded nodes, Bland pivots, the most events of one node and wall per side, `ratio` (median over the
+baseline's median) and `limit` where a search ends at a node's event limit (reported, not timed against).  Beside the two
+binary_ip models it knows bip_40x16_s6, synth.binary_ip(40, 16, seed=6), whose plain search by one diver meets a cycling node.
+`--stall-events S` makes side (b), and `--trace-only`, the search with the guard.
 `--trace-only` runs one solve of side (b) and nothing else (for a kernel trace of the node form given).
 
 usage: bench_bnb_bounded.py [--model NAME] [--max-nodes N] [--node-form F] [--divers W] [--plunge D]
                             [--compare-forms [--flag-sets LIST]] [--compare-divers LIST [--flag-sets LIST]]
                             [--compare-plunge LIST [--flag-sets LIST]] [--compare-branching LIST [--flag-sets LIST]]
-                            [--branching R [--candidates C] [--probe-iter L]] [--long-step] [--cutoff] [--trace-only] [REPS]"""
+                            [--branching R [--candidates C] [--probe-iter L]] [--compare-guard LIST [--flag-sets LIST]]
+                            [--stall-events S] [--long-step] [--cutoff] [--trace-only] [REPS]"""
 import json
 import os
 import statistics
@@ -301,8 +309,67 @@ def compare_branching(n, m, reps, max_nodes, flag_sets, W, settings):
     return rec
 
 
+def compare_guard(n, m, reps, max_nodes, flag_sets, W, stalls, seed=None):
+    """The stall guard (lpx_solve_bnb_bounded7) at W divers against the same search without it (lpx_solve_bnb_bounded4) on
+    binary_ip(n, m) (see the module docstring)."""
+    c, A, rel, b = synth.binary_ip(n, m) if seed is None else synth.binary_ip(n, m, seed)
+    bnd_p = L.LPProblem.from_arrays(0, c, A[:m], rel[:m], b[:m])
+    rec = {"n": n, "m": m, "bounded_shape": [m + 1, n + m + 1], "divers": W}
+    sides = {"base": None}
+    for S in stalls:
+        sides[f"S{S}"] = S
+
+    def solve(side, kw, limit=None):
+        limit = max_nodes if limit is None else limit
+        how = {"divers": W} if sides[side] is None else {"divers": W, "stall_events": sides[side]}
+        t0 = time.perf_counter()
+        try:
+            r = L.LPSolver().SolveBnbBounded(bnd_p, 1.0, max_nodes=limit, **how, **kw)
+            r.Limit = None
+        except L.SolverException as e:
+            if e.code != L._lib.ITER_LIMIT:
+                raise
+            r = e.result
+            r.Limit = None if limit and r.Nodes >= limit else str(e)      # a node at its event limit ends the solve: reported, not timed against
+        return 1e3 * (time.perf_counter() - t0), r
+
+    for fs in flag_sets:
+        kw = FLAG_SETS[fs]
+        ts = {s: [] for s in sides}
+        last = {}
+        for i in range(reps + 1):
+            for s in sides:
+                if i == 0:          # the untimed solve: clones, the batch's slab and the first launch of either kernel are paid here
+                    solve(s, kw, max_nodes if max_nodes else 2000)
+                    continue
+                ms, r = solve(s, kw)
+                last[s] = r
+                ts[s].append(ms)
+        base = stats(ts["base"])
+        d = {}
+        for s in sides:
+            r = last[s]
+            st = stats(ts[s])
+            d[s] = {"ms": st, "nodes": int(r.Nodes), "events": r.BnbInfo["events"], "rounds": r.BnbInfo["rounds"],
+                    "guarded_nodes": r.BnbInfo.get("guarded_nodes", 0), "bland_events": r.BnbInfo.get("bland_events", 0),
+                    "max_events": r.BnbInfo.get("max_events", int(r.BnbLog["events"].max()) if len(r.BnbLog) else 0),
+                    "nodes_per_s": r.Nodes / (st["median"] / 1e3), "optimum": r.OptimalValue, "limit": r.Limit,
+                    "ratio": None if last["base"].Limit is not None or r.Limit is not None else st["median"] / base["median"]}
+        rec[fs] = d
+    return rec
+
+
 def main():
     args = sys.argv[1:]
+    stall_events, stalls = None, None
+    for flag in ("--stall-events", "--compare-guard"):
+        if flag in args:
+            k = args.index(flag)
+            if flag == "--stall-events":
+                stall_events = int(args[k + 1])
+            else:
+                stalls = [int(x) for x in args[k + 1].split(",") if x]
+            del args[k:k + 2]
     branching, candidates, probe_iter, settings = None, 4, None, None
     for flag in ("--branching", "--candidates", "--probe-iter", "--compare-branching"):
         if flag in args:
@@ -347,7 +414,16 @@ def main():
     L._lib.check(lib.lpx_init(0))
     out = {}
     if flag_sets is None:
-        flag_sets = "plain,both" if widths or depths or settings else "plain,long_step,cutoff,both"
+        flag_sets = "plain,both" if widths or depths or settings or stalls else "plain,long_step,cutoff,both"
+    if stalls:
+        for name, n, m, seed in list((nm, n, m, None) for nm, n, m in models()) + [("bip_40x16_s6", 40, 16, 6)]:
+            if name == only or (only is None and seed is None):
+                out[name] = compare_guard(n, m, reps, max_nodes, [f for f in flag_sets.split(",") if f and f != "none"],
+                                          divers if divers else 1, stalls, seed)
+        print(json.dumps(out))
+        return
+    if stall_events is not None and divers is None:
+        divers = 1
     if settings:
         for name, n, m in models():
             if only is None or name == only:
@@ -397,6 +473,8 @@ def main():
             t0 = time.perf_counter()
             try:
                 how = {} if branching is None else {"branching": branching, "candidates": candidates, "probe_iter": probe_iter}
+                if stall_events is not None:
+                    how["stall_events"] = stall_events
                 r = L.LPSolver().SolveBnbBounded(bnd_p, 1.0, max_nodes=max_nodes, node_form=node_form, divers=divers, plunge=plunge,
                                                  **side_flags, **how)
             except L.SolverException as e:
@@ -410,7 +488,9 @@ def main():
             out[name] = {"node_form": node_form, "divers": divers, "plunge": plunge, "ms": ms, "nodes": int(rb.Nodes),
                          "events": rb.BnbInfo["events"], "rounds": rb.BnbInfo.get("rounds"), "launched": rb.BnbInfo.get("launched"),
                          "dropped": rb.BnbInfo.get("dropped"), "branching": branching, "probes": rb.BnbInfo.get("probes"),
-                         "probe_events": rb.BnbInfo.get("probe_events"), "pruned_by_probe": rb.BnbInfo.get("pruned_by_probe")}
+                         "probe_events": rb.BnbInfo.get("probe_events"), "pruned_by_probe": rb.BnbInfo.get("pruned_by_probe"),
+                         "stall_events": stall_events, "guarded_nodes": rb.BnbInfo.get("guarded_nodes"),
+                         "bland_events": rb.BnbInfo.get("bland_events")}
             continue
         base = device_used_mb()
         ta, tb, na, nb = [], [], [], []

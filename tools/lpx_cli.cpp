@@ -1,7 +1,7 @@
 // lpx_cli -- Linux stand-in for the reference's WinForms host (Form1.cs), over the C ABI of liblpx.so only.
 //
 //   lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]
-//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]]] [--export FILE] INPUT.txt
+//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S]] [--export FILE] INPUT.txt
 //
 // Does what Form1 does around the solvers: reads the model text (Import, Form1.cs:284-296), parses it with the LPParser
 // grammar (lpx_parse_text, Models/LPParser.cs:9-79), runs the algorithm chosen by its dropdown name (btnSolve_Click,
@@ -83,6 +83,7 @@ int main(int argc, char** argv)
     int branching = -1;         // --branching R beside --bnb-bounded: LPX_BRANCH_* (lpx_solve_bnb_bounded6); -1 = not given
     int candidates = 4;         // --candidates N: the columns probed per node by --branching strong
     int probe_iter = -1;        // --probe-iter L: the event limit of a probe; -1 = the node's
+    int stall_events = -1;      // --stall-events S beside --bnb-bounded: the stall guard (lpx_solve_bnb_bounded7); -1 = not given
     struct Bound { bool upper; int index; double value; std::string text; };
     std::vector<Bound> bounds;
     lpx_cut_opts co; lpx_default_cut_opts(&co);
@@ -113,6 +114,13 @@ int main(int argc, char** argv)
             const long d = std::strtol(v.c_str(), &end, 10);
             if (end == v.c_str() || *end || d < 1 || d > 64) { std::fprintf(stderr, "lpx_cli: --plunge takes a depth in [1, 64], got '%s'\n", v.c_str()); return 64; }
             plunge = (int)d;
+        }
+        else if (a == "--stall-events" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            char* end = nullptr;
+            const long x = std::strtol(v.c_str(), &end, 10);
+            if (end == v.c_str() || *end || x < 0 || x > 1000000000) { std::fprintf(stderr, "lpx_cli: --stall-events takes a non-negative pivot count, got '%s'\n", v.c_str()); return 64; }
+            stall_events = (int)x;
         }
         else if (a == "--branching" && i + 1 < argc) {
             const std::string v = argv[++i];
@@ -167,7 +175,7 @@ int main(int argc, char** argv)
         else if (a == "--export" && i + 1 < argc) exportPath = argv[++i];
         else if (a == "--help" || a == "-h") {
             std::printf("usage: lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]\n"
-                        "               [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]]]\n"
+                        "               [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S]]\n"
                         "               [--export FILE] INPUT.txt\n"
                         "  NAME: Primal Simplex | Revised Primal Simplex | Dual Simplex | Branch and Bound |\n"
                         "        Revised Branch and Bound | Branch and Bound Knapsack | Cutting Plane | Revised Cutting Plane |\n"
@@ -191,6 +199,10 @@ int main(int argc, char** argv)
                         "             --divers it means --divers 1): strong probes both children of up to N = --candidates (default 4, at most 32)\n"
                         "             fractional columns of every node on chip, --probe-iter L events each at most (default: the node's limit),\n"
                         "             and branches on the largest product of the two objective losses; not with --plunge above 1\n"
+                        "  --stall-events S: with --bnb-bounded, the stall guard (lpx_solve_bnb_bounded7; without --divers it means --divers 1):\n"
+                        "             after S pivots without progress of the objective a node selects by Bland's rule until the objective moves,\n"
+                        "             so a node that cycles ends; 0 = no guard, 50 is a reasonable value; not with --node-form launches,\n"
+                        "             --plunge above 1 or --branching\n"
                         "  --set-rhs I=V, --set-cost J=V: after the solve, b_I = V / c_J = V (1-based, repeatable), applied in order,\n"
                         "             each re-optimised warm on the device from the previous basis; each re-solve's summary is printed\n");
             return 0;
@@ -211,6 +223,11 @@ int main(int argc, char** argv)
     if (branching >= 0 && !bnb_bounded) { std::fprintf(stderr, "lpx_cli: --branching needs --bnb-bounded\n"); return 64; }
     if (branching >= 0 && plunge > 1) { std::fprintf(stderr, "lpx_cli: --branching decides between a node and its children: not with --plunge above 1\n"); return 64; }
     if (branching >= 0 && node_form == LPX_NODE_LAUNCHES) { std::fprintf(stderr, "lpx_cli: --branching evaluates every node on chip: not with --node-form launches\n"); return 64; }
+    if (stall_events >= 0 && !bnb_bounded) { std::fprintf(stderr, "lpx_cli: --stall-events needs --bnb-bounded\n"); return 64; }
+    if (stall_events >= 0 && node_form == LPX_NODE_LAUNCHES) { std::fprintf(stderr, "lpx_cli: --stall-events: the stall guard has no launches form: not with --node-form launches\n"); return 64; }
+    if (stall_events >= 0 && plunge > 1) { std::fprintf(stderr, "lpx_cli: --stall-events: the plunge has no stall guard: not with --plunge above 1\n"); return 64; }
+    if (stall_events >= 0 && branching >= 0) { std::fprintf(stderr, "lpx_cli: --stall-events: the probes have no stall guard: not with --branching\n"); return 64; }
+    if (stall_events >= 0) { plunge = 0; if (!divers) divers = 1; }
     if (branching >= 0) { plunge = 0; if (!divers) divers = 1; }
     if (plunge && !divers) divers = 1;
     if (divers && node_form == LPX_NODE_LAUNCHES) { std::fprintf(stderr, "lpx_cli: --divers evaluates every node on chip: not with --node-form launches\n"); return 64; }
@@ -243,7 +260,8 @@ int main(int argc, char** argv)
         if (bd.index >= p.n) { std::fprintf(stderr, "lpx_cli: %s: index out of range\n", bd.text.c_str()); lpx_parsed_free(&p); return 64; }
         (bd.upper ? up : lo)[bd.index] = bd.value;
     }
-    const int rc = bnb_bounded && branching >= 0 ? lpx_solve_bnb_bounded6(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, branching, candidates,
+    const int rc = bnb_bounded && stall_events >= 0 ? lpx_solve_bnb_bounded7(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, stall_events, &r, nullptr, nullptr, nullptr)
+                 : bnb_bounded && branching >= 0 ? lpx_solve_bnb_bounded6(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, branching, candidates,
                                                                          probe_iter >= 0 ? probe_iter : o.max_iter > 0 ? o.max_iter : 10000, &r, nullptr, nullptr, nullptr)
                  : bnb_bounded && plunge ? lpx_solve_bnb_bounded5(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, plunge, &r, nullptr, nullptr, nullptr)
                  : bnb_bounded && divers ? lpx_solve_bnb_bounded4(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, &r, nullptr, nullptr)
