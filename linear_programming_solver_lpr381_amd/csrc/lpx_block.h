@@ -17,6 +17,7 @@ static constexpr int MB_CNT = 160;
 static constexpr int MB_MAXB = 64;           // at most this many workgroups (partials fit one wave)
 // deferred pivots of the one-launch primal loop and its select-only pair (lpx_pivot_fused.hip: lpx_pivot_ratio, lpx_pivot_select)
 static constexpr int FP_DMAX = 16;           // deepest deferral: pivots applied per sweep
+static constexpr int FP_STRIP_BLOCKS = 2;    // row blocks (of fp_rows(d) rows) a streaming sweep wave walks with its d pivot-row pairs in registers, d >= 3
 static constexpr int SELC_ROWS = 256;                        // column launch (lpx_pivot_ratio): rows = lanes of a workgroup, one row per lane
 static constexpr int SELP_NT = 512;                          // row launch (lpx_pivot_select): lanes of a workgroup
 static constexpr int SELP_RU = 10;                           // ratios a lane of the row launch has in flight per pass over the ratio buffer

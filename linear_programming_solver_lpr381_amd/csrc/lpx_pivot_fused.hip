@@ -72,6 +72,12 @@ __global__ __launch_bounds__(SEL_NT) void lpx_fused_init(FusedParams F)
 // rows staged in LDS once per workgroup (4 rows x 4 waves on one column window) ran 123 / 126 / 132 us there and 128 / 135 /
 // 144-147 us in this kernel, 9-12 % under this tile at equal depth -- and 2.6-3.8 % on the headline at d = 16, short of the 5 %
 // a change of this loop is held to, so the tile stays (DESIGN.md 4.1 and 9.9 have the numbers and what is left to try).
+// Strips (fused_sweep_strip, the streaming kernels of d >= 3): a wave loads its D pairs ONCE and walks FP_STRIP_BLOCKS row blocks
+// of fp_rows(D) rows with them in VGPRs; the blocks keep the tile above (loads, D x (mul, sub), stores by policy).  The kbench's
+// strip rows (profiles/r15_kbench_deferred_sweep.txt, d = 16): two blocks 132.6 us at 2 waves per SIMD, 136-137 at 3, 140 at 4;
+// four blocks 136 / 145 / 146; sixteen 190 at 3 (1.04 rounds of resident waves: the tail) and 149 at 4 -- longer strips buy nothing
+// beyond the halved pair traffic.  In this kernel two blocks run 135-137 us at d = 16 and 135 at d = 12 (the tile above: 159-160 and
+// 149), the same built for 2 and for 3 waves per SIMD (141-151 VGPRs: three waves either way); for 4 it spills and runs 241 us.
 __host__ __device__ constexpr int fp_rows(int D) { return D <= 2 ? UPDS_ROWS : 8; }
 __host__ __device__ constexpr int fp_rec(int buf, int npend, int slot0) { return buf | (npend << 1) | (slot0 << 8); }
 // ring slot of pending pivot s (0 = oldest) of n before the launch with ring index lm
@@ -355,18 +361,118 @@ __device__ __forceinline__ void fused_sweep(const FusedParams& F, int ncw, int n
     }
 }
 
+// The streaming sweep of d >= 3 in strips: unit -> (strip, column window), window fastest; a strip is FP_STRIP_BLOCKS blocks of
+// fp_rows(D) rows.  The D pairs and the D pending rows are loaded once per wave; per block: the tableau loads, the factor
+// scalars and the stores of the tile above, same operations in the same order (oldest pending pivot first, mul then sub).
+//   factors    through the constant address space.  Behind the first block's stores the compiler cannot show that a plain global
+//              load is not clobbered inside the kernel and issues it as a vector load behind s_waitcnt vmcnt(0) -- one dependent
+//              round trip per pending pivot and block (210-240 us in the kbench).  No launch writes a ring slot it reads (see the
+//              head of this file), so the address space says what is true and the loads stay s_load_dwordx16.
+//   hit block  a block that holds a pending pivot's row takes a block-uniform branch: the same tile, rolled over the pivots and
+//              straight-line over the rows, row r_s taking the pair.  The pair comes from L2 again (a register array cannot be
+//              indexed by a loop counter; unrolled, the selects cost 16 VGPRs and 76-116 bytes of scratch on every block): 16
+//              dependent round trips for at most D blocks in R / 8, against 8 x D in the row-wise path.  kbench, 16 spread rows,
+//              d = 16: the tile above 157 -> 183 us, this form 137.5 -> 139 us.
+//   tail       only the block that runs past R keeps the per-row guard (the row-wise loop of fused_sweep).
+template <bool NT, int D>
+__device__ __forceinline__ void fused_sweep_strip(const FusedParams& F, int ncw, int nunits, int mixmod)
+{
+    constexpr int ROWS = fp_rows(D), S = FP_STRIP_BLOCKS, ring = 2 * D;
+    const SelParams& P = F.P;
+    const int t = threadIdx.x;
+    const int lm = F.lm;
+    const DevState& cur = F.rec[lm & 1];
+    const int status = cur.status, buf = cur.pad[3] & 1, rnew = cur.r;     // rnew: the newest pending pivot's row
+    const int nsel = P.nblk;
+    const int R = P.shape ? P.shape[0] : P.R;
+    const size_t ld = (size_t)P.ld, fld = (size_t)P.R;
+    const double* __restrict__ src = buf ? F.T1 : P.T;
+    double* __restrict__ dst = buf ? P.T : F.T1;
+    const int lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int unit = ((int)blockIdx.x - nsel) * (FP_NT / 64) + wave;
+    if (unit >= nunits) return;
+    const int cw = unit % ncw, strip = unit / ncw;
+    const int col = cw * 128 + lane * 2;
+    if (col >= P.ld) return;
+    const int row0 = strip * (S * ROWS);
+    if (row0 >= R) return;
+    int rs[D];
+#pragma unroll
+    for (int s = 0; s < D; ++s) rs[s] = s == D - 1 ? rnew : F.rring[fp_slot(lm, D, s, ring)];
+    if (status != LPX_RUNNING) return;                       // a run that is over leaves its pending pivots to lpx_pivot_flush
+    double2 p[D];
+#pragma unroll
+    for (int s = 0; s < D; ++s) p[s] = *reinterpret_cast<const double2*>(F.pring + (size_t)fp_slot(lm, D, s, ring) * ld + col);
+    const LPX_CONSTANT double* fc = (const LPX_CONSTANT double*)F.fring;
+    const int nfull = min(S, (R - row0) / ROWS);             // full blocks of this strip
+    const double* sb = src + (size_t)row0 * ld + col;
+    double* db = dst + (size_t)row0 * ld + col;
+#pragma unroll 1
+    for (int b = 0; b < nfull; ++b) {
+        const int r0 = row0 + b * ROWS;
+        bool hit = false;                                    // a pending pivot row in this block
+#pragma unroll
+        for (int s = 0; s < D; ++s) hit |= (unsigned)(rs[s] - r0) < (unsigned)ROWS;
+        double2 v[ROWS];
+        tile_load<ROWS, NT>(v, sb, ld);
+        if (!hit) {
+#pragma unroll
+            for (int s = 0; s < D; ++s) tile_pivot<ROWS>(v, p[s], fc + (size_t)fp_slot(lm, D, s, ring) * fld + r0, 0);
+        } else {
+#pragma unroll 1
+            for (int s = 0; s < D; ++s) {
+                const int sl = fp_slot(lm, D, s, ring);
+                const double2 ps = *reinterpret_cast<const double2*>(F.pring + (size_t)sl * ld + col);
+                const int r = s == D - 1 ? rnew : F.rring[sl];
+                const LPX_CONSTANT double* f = fc + (size_t)sl * fld + r0;
+#pragma unroll
+                for (int k = 0; k < ROWS; ++k) {
+                    double2 u;
+                    u.x = v[k].x - f[k] * ps.x;              // mul, then sub: contraction is off
+                    u.y = v[k].y - f[k] * ps.y;
+                    v[k] = r0 + k == r ? ps : u;             // row r_s: the normalised pivot row
+                }
+            }
+        }
+        tile_store<ROWS, NT, NT ? MIX_SWEEP : MIX_NONE>(db, ld, v, strip * S + b, mixmod);
+        sb += (size_t)ROWS * ld; db += (size_t)ROWS * ld;
+    }
+    if (nfull == S) return;
+#pragma unroll 1
+    for (int i = row0 + nfull * ROWS; i < min(R, row0 + (nfull + 1) * ROWS); ++i) {     // the block that runs past R
+        double2 o = upd_load<NT>(src + (size_t)i * ld + col);
+#pragma unroll 1
+        for (int s = 0; s < D; ++s) {
+            const int sl = fp_slot(lm, D, s, ring);
+            const double2 ps = *reinterpret_cast<const double2*>(F.pring + (size_t)sl * ld + col);
+            const double f = F.fring[(size_t)sl * fld + i];
+            double2 u;
+            u.x = o.x - f * ps.x;
+            u.y = o.y - f * ps.y;
+            o = i == F.rring[sl] ? ps : u;                   // row r_s: the normalised pivot row
+        }
+        upd_store<NT>(dst + (size_t)i * ld + col, o);
+    }
+}
+
 // waves_per_eu(6): 80 VGPRs.  The sweep half alone needs 28 (D = 1) to 64 (D = 16); the select half sets the budget and spills
-// (code-object metadata): 2 VGPRs in every streaming form but D = 10 (14) and D = 15 (6), 2-4 in _c<1..8>, 8-14 in _c<9..16>
-// -- the defaults run lpx_pivot_fused<16> (2) above 292 MiB (the 403 MB headline), lpx_pivot_fused<12> (2) from 152 MB to there,
+// (code-object metadata): 2 VGPRs in lpx_pivot_fused<1, 2>, 2-4 in _c<1..8>, 8-14 in _c<9..16>.  The strip forms (the streaming
+// kernels of d >= 3) hold D pairs and a block and are built for three waves per SIMD (fp_strip_wpe): 103 VGPRs at D = 3, 109 at
+// 8, 139 at 12, 151 at 16, no scratch -- four waves where they fit, three from D = 12.  The select half needs about 86 and spills
+// nothing there.
+// -- the defaults run lpx_pivot_fused<16> above 292 MiB (the 403 MB headline), lpx_pivot_fused<12> from 152 MB to there,
 // _c<12> (14) from 64 to 152 MB and lpx_pivot_fused_c<4> (2) up to 64 MB (config 2's 25 MB).
 // Without the hint the r03 kernel took 86 VGPRs = 5 waves per SIMD (8.46 k pivots/s against 8.57 k at 6).
+__host__ __device__ constexpr int fp_strip_wpe(int D) { return D <= 2 ? 6 : 3; }
 template <int D>
-__global__ __launch_bounds__(FP_NT) __attribute__((amdgpu_waves_per_eu(6))) void lpx_pivot_fused(FusedParams F, int ncw, int nunits, int mixmod)
+__global__ __launch_bounds__(FP_NT) __attribute__((amdgpu_waves_per_eu(fp_strip_wpe(D)))) void lpx_pivot_fused(FusedParams F, int ncw, int nunits, int mixmod)
 {
     if ((int)blockIdx.x < F.P.nblk) {
         if (D == 1) fused_select<4, 1, 1>(F, 1, true);
         else fused_select<4, 1>(F, F.defer, true);           // == D; a run-time count keeps its loops rolled
-    } else fused_sweep<true, D>(F, ncw, nunits, mixmod);
+    } else if constexpr (D <= 2) fused_sweep<true, D>(F, ncw, nunits, mixmod);
+    else fused_sweep_strip<true, D>(F, ncw, nunits, mixmod);
 }
 template <int D>
 __global__ __launch_bounds__(FP_NT) __attribute__((amdgpu_waves_per_eu(6))) void lpx_pivot_fused_c(FusedParams F, int ncw, int nunits, int mixmod)
@@ -801,9 +907,10 @@ hipError_t launch_pivot_fused(const FusedParams& f0, double* rat, long long L, h
         return launch_pivot_select_ws(f, s, e0, e1);
     }
     const int rows = fp_rows(d);
-    const int ncw = (ld + 127) / 128, nunits = ncw * ((R + rows - 1) / rows);
-    const int nblocks = f.P.nblk + (nunits + (FP_NT / 64) - 1) / (FP_NT / 64);
     const int pol = fused_policy(ld, R);
+    const int strip = (pol != 0 && d >= 3) ? FP_STRIP_BLOCKS : 1;           // the streaming kernels of d >= 3: a wave per strip of blocks
+    const int ncw = (ld + 127) / 128, nunits = ncw * (((R + rows - 1) / rows + strip - 1) / strip);
+    const int nblocks = f.P.nblk + (nunits + (FP_NT / 64) - 1) / (FP_NT / 64);
     int mixmod = pol == 2 ? mixmod_for(tableau_bytes(ld, R)) : 0;            // 0: every store nontemporal
     // the stored-through row is the last of every mixmod-th block: at `rows` per block the block period shrinks in proportion so
     // that about the same share of BLOCKS keeps a row in the cache.  mixmod = 1 (the 403 MB headline) stays 1: one row in eight

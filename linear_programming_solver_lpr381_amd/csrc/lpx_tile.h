@@ -94,6 +94,9 @@ template <bool STREAM> __device__ __forceinline__ void upd_store(double* p, doub
 // batched group kernels) sees generic pointers and would issue flat_load / flat_store, which count against both the vector-memory
 // and the LDS counter; casting to address space 1 gives global_load_dwordx4 / global_store_dwordx4 as in the single-tableau kernels.
 #define LPX_GLOBAL __attribute__((address_space(1)))
+// The constant address space, for uniform loads that must stay scalar where stores of the same kernel precede them: only for
+// memory that no lane of the launch writes (fused_sweep_strip's factor columns).
+#define LPX_CONSTANT __attribute__((address_space(4)))
 template <bool STREAM> __device__ __forceinline__ double2 upd_load(const LPX_GLOBAL double* p)
 {
     const LPX_GLOBAL lpx_d2* q = (const LPX_GLOBAL lpx_d2*)p;

@@ -8,6 +8,14 @@
 //   candidates   the W waves of a workgroup on ONE 128-column window and W x H consecutive rows; the D x 128 doubles of the
 //                pending rows go to LDS once per workgroup (global_load_dwordx4 + ds_write_b128, in front of the tile's own loads),
 //                every wave reads its pairs back with ds_read_b128; factors by scalar loads or staged too
+//   strips       a wave owns one 128-column window and S consecutive blocks of 8 rows: its D pairs are loaded ONCE and stay in VGPRs
+//                while it walks the blocks with the shipped per-block sequence (nt loads, D x (mul, sub), mixed store; factors by
+//                scalar loads).  S = 2, 3, 4, 8, 16; "pf": the next block's tableau loads issued before the current block's arithmetic
+//                (the factors of a whole block at d = 16 are 256 SGPRs and cannot be prefetched with them); built for 2 to 6
+//                waves per SIMD.  The wave count is printed against the resident slots at that occupancy.  Beside them one tile
+//                of 12 and of 16 rows with the pairs loaded as they are needed, at the occupancy whose registers hold it.
+//   hit blocks   the first D of 16 synthetic pending pivot rows spread uniformly over the rows: the shipped tile takes its row-wise
+//                path for a block that holds one, the strip the same tile rolled over the pivots with a select per row.
 // Every kernel is built for 6 waves per SIMD like the product's (whose select half sets that budget) and, the candidates, for 8.
 // Each non-diagnostic variant's output of one sweep is compared with the shipped tile's through a checksum; a row that
 // DIFFERS makes the exit status 1.
@@ -22,6 +30,7 @@
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); exit(1); } } while (0)
 
 typedef double d2 __attribute__((ext_vector_type(2)));
+#define KCONST __attribute__((address_space(4)))
 
 __device__ __forceinline__ d2 ld_nt(const double* p) { return __builtin_nontemporal_load(reinterpret_cast<const d2*>(p)); }
 __device__ __forceinline__ void st_nt(double* p, d2 v) { __builtin_nontemporal_store(v, reinterpret_cast<d2*>(p)); }
@@ -36,6 +45,7 @@ struct Args {
     const double* src; double* dst; const double* pring; const double* fring;
     int ld, R, ncw, nunits;
     double cp, cf;           // the diagnostic variants' constants
+    const int* rring;        // rows of the pending pivots (the hit-block variants)
 };
 
 template <int D, int H, bool FMA>
@@ -51,11 +61,12 @@ template <int H>
 __device__ __forceinline__ void store_mixed(double* db, size_t ld, const d2 (&v)[H])
 {
 #pragma unroll
-    for (int k = 0; k < H - 1; ++k) st_nt(db + (size_t)k * ld, v[k]);
-    st_df(db + (size_t)(H - 1) * ld, v[H - 1]);
+    for (int k = 0; k < H; ++k) {
+        if (k == H - 1 || (H > 8 && k % 8 == 7)) st_df(db + (size_t)k * ld, v[k]); else st_nt(db + (size_t)k * ld, v[k]);
+    }
 }
 // rows of a tile that runs past R, one at a time
-template <int D, int H>
+template <int D, int H, bool HITS = false>
 __device__ __forceinline__ void rowwise(const Args& a, int row0, int col)
 {
     const size_t ld = (size_t)a.ld;
@@ -69,13 +80,14 @@ __device__ __forceinline__ void rowwise(const Args& a, int row0, int col)
             const d2 p = *reinterpret_cast<const d2*>(a.pring + (size_t)s * ld + col);
             const double f = a.fring[(size_t)s * a.R + i];
             o.x = o.x - f * p.x; o.y = o.y - f * p.y;
+            if (HITS && i == a.rring[s]) o = p;               // row r_s: the normalised pivot row
         }
         st_nt(a.dst + (size_t)i * ld + col, o);
     }
 }
 
 // every wave a tile of its own: the shipped shape (W = 4 waves per workgroup, units in dispatch order, column window fastest)
-template <int D, int H, int W, int PAIR, int FACM, bool FMA>
+template <int D, int H, int W, int PAIR, int FACM, bool FMA, bool HITS = false>
 __device__ __forceinline__ void sweep_own(const Args& a)
 {
     const int lane = threadIdx.x & 63;
@@ -88,7 +100,12 @@ __device__ __forceinline__ void sweep_own(const Args& a)
     const int row0 = rb * H;
     if (row0 >= a.R) return;
     const size_t ld = (size_t)a.ld;
-    if (row0 + H > a.R) { rowwise<D, H>(a, row0, col); return; }
+    bool hit = false;                                        // as shipped: a pending pivot row among the wave's rows -> row-wise
+    if (HITS) {
+#pragma unroll
+        for (int s = 0; s < D; ++s) hit |= (unsigned)(a.rring[s] - row0) < (unsigned)H;
+    }
+    if (row0 + H > a.R || hit) { rowwise<D, H, HITS>(a, row0, col); return; }
     d2 v[H];
 #pragma unroll
     for (int k = 0; k < H; ++k) v[k] = ld_nt(a.src + (size_t)(row0 + k) * ld + col);
@@ -148,12 +165,107 @@ __device__ __forceinline__ void sweep_staged(const Args& a)
     store_mixed<H>(a.dst + (size_t)row0 * ld + col, ld, v);
 }
 
-template <int D, int H, int W, int PAIR, int FACM, bool FMA>
-__global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_own(Args a) { sweep_own<D, H, W, PAIR, FACM, FMA>(a); }
+// strips: one 128-column window, S consecutive blocks of 8 rows per wave, the D pairs kept in VGPRs (4 waves per workgroup and
+// units in dispatch order, column window fastest inside a strip index, as shipped)
+template <int D, int S, bool PF, bool HITS>
+__device__ __forceinline__ void sweep_strip(const Args& a)
+{
+    constexpr int H = 8;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int unit = (int)blockIdx.x * 4 + wave;
+    if (unit >= a.nunits) return;
+    const int cw = unit % a.ncw, strip = unit / a.ncw;
+    const int col = cw * 128 + lane * 2;
+    if (col >= a.ld) return;
+    const int row0 = strip * (S * H);
+    if (row0 >= a.R) return;
+    const size_t ld = (size_t)a.ld;
+    const int nfull = min(S, (a.R - row0) / H);              // full blocks of this strip; a block past them runs past R
+    d2 p[D];
+#pragma unroll
+    for (int s = 0; s < D; ++s) p[s] = *reinterpret_cast<const d2*>(a.pring + (size_t)s * ld + col);
+    int rs[D];
+#pragma unroll
+    for (int s = 0; s < D; ++s) rs[s] = HITS ? a.rring[s] : -1;
+    const double* sb = a.src + (size_t)row0 * ld + col;
+    double* db = a.dst + (size_t)row0 * ld + col;
+    // The factors through the constant address space: behind the first block's stores the compiler can no longer show that a
+    // plain global load is not clobbered inside the kernel and issues it as a VECTOR load (one dependent round trip per pending
+    // pivot and block, each behind s_waitcnt vmcnt(0): the first form of this kernel ran 210-240 us that way).  Nothing in a
+    // sweep writes the ring slots it reads, so the address space says what is true, and the loads stay scalar.
+    const KCONST double* fc = (const KCONST double*)a.fring;
+    d2 v[H];
+    if (PF && nfull > 0) {
+#pragma unroll
+        for (int k = 0; k < H; ++k) v[k] = ld_nt(sb + (size_t)k * ld);
+    }
+#pragma unroll 1
+    for (int b = 0; b < nfull; ++b) {
+        const int r0 = row0 + b * H;
+        d2 vn[H];
+        if (PF) {
+#pragma unroll
+            for (int k = 0; k < H; ++k) vn[k] = v[k];
+            if (b + 1 < nfull) {
+#pragma unroll
+                for (int k = 0; k < H; ++k) vn[k] = ld_nt(sb + (size_t)(H + k) * ld);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < H; ++k) v[k] = ld_nt(sb + (size_t)k * ld);
+        }
+        bool hit = false;
+        if (HITS) {
+#pragma unroll
+            for (int s = 0; s < D; ++s) hit |= (unsigned)(rs[s] - r0) < (unsigned)H;
+        }
+        if (!hit) {
+#pragma unroll
+            for (int s = 0; s < D; ++s) {
+                double f[H];
+#pragma unroll
+                for (int k = 0; k < H; ++k) f[k] = fc[(size_t)s * a.R + r0 + k];
+                apply<D, H, false>(v, p[s], f);
+            }
+        } else {
+            // the same tile with row r_s taking the normalised pivot row: rolled over the pivots, straight-line over the rows; the
+            // pair comes from L2 again (a register array cannot be indexed by a loop counter) -- 16 blocks in 513 come here
+#pragma unroll 1
+            for (int s = 0; s < D; ++s) {
+                const d2 ps = *reinterpret_cast<const d2*>(a.pring + (size_t)s * ld + col);
+                const int r = a.rring[s];
+#pragma unroll
+                for (int k = 0; k < H; ++k) {
+                    const double f = fc[(size_t)s * a.R + r0 + k];
+                    d2 u; u.x = v[k].x - f * ps.x; u.y = v[k].y - f * ps.y;
+                    v[k] = r0 + k == r ? ps : u;
+                }
+            }
+        }
+        store_mixed<H>(db, ld, v);
+        sb += (size_t)H * ld; db += (size_t)H * ld;
+        if (PF) {
+#pragma unroll
+            for (int k = 0; k < H; ++k) v[k] = vn[k];
+        }
+    }
+    if (nfull < S && row0 + nfull * H < a.R) rowwise<D, H, HITS>(a, row0 + nfull * H, col);
+}
+
+template <int D, int H, int W, int PAIR, int FACM, bool FMA, bool HITS = false>
+__global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_own(Args a) { sweep_own<D, H, W, PAIR, FACM, FMA, HITS>(a); }
 template <int D, int H, int W, int FACM>
 __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_staged6(Args a) { sweep_staged<D, H, W, FACM>(a); }
 template <int D, int H, int W, int FACM>
 __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_staged8(Args a) { sweep_staged<D, H, W, FACM>(a); }
+
+template <int WPE, int D, int S, bool PF, bool HITS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_strip(Args a) { sweep_strip<D, S, PF, HITS>(a); }
+// the shipped tile (every wave one tile, pairs from the ring as they are needed) with H = 16 rows at an occupancy whose registers
+// hold them; the store policy per 8 rows as shipped (rows 7 and 15 through the cache)
+template <int WPE, int D, int H>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_wide(Args a) { sweep_own<D, H, 4, PAIR_GLOBAL, FAC_SCALAR, false>(a); }
 
 __global__ void k_checksum(const unsigned long long* x, size_t n, unsigned long long* out)
 {
@@ -162,7 +274,7 @@ __global__ void k_checksum(const unsigned long long* x, size_t n, unsigned long 
     atomicAdd(out, acc);
 }
 
-struct Variant { std::string name; int H, W; bool staged, ships; std::function<void(const Args&, dim3, hipStream_t)> launch; };
+struct Variant { std::string name; int H, W; bool staged, ships; std::function<void(const Args&, dim3, hipStream_t)> launch; int strip = 0, wpe = 6; bool hits = false; };
 
 template <int D>
 static void variants(std::vector<Variant>& vs)
@@ -191,8 +303,34 @@ static void variants(std::vector<Variant>& vs)
     STG(k_staged8, 4, 4, FAC_SCALAR, "staged H=4 W=4, 8 waves per SIMD");
     STG(k_staged8, 3, 8, FAC_SCALAR, "staged H=3 W=8, 8 waves per SIMD");
     STG(k_staged8, 4, 8, FAC_SCALAR, "staged H=4 W=8, 8 waves per SIMD");
+#define STRIP(WPE, S, PF, HITS, LABEL) do { vs.push_back({d + LABEL, 8, 4, false, true, [](const Args& a, dim3 g, hipStream_t s) { hipLaunchKernelGGL((k_strip<WPE, D, S, PF, HITS>), g, dim3(256), 0, s, a); }}); \
+        vs.back().strip = S; vs.back().wpe = WPE; vs.back().hits = HITS; } while (0)
+#define STRIPS(WPE, W) do { STRIP(WPE, 2, false, false, "strip S=2 " W); STRIP(WPE, 3, false, false, "strip S=3 " W); STRIP(WPE, 4, false, false, "strip S=4 " W); \
+        STRIP(WPE, 8, false, false, "strip S=8 " W); STRIP(WPE, 16, false, false, "strip S=16 " W); \
+        STRIP(WPE, 2, true, false, "strip S=2 pf " W); STRIP(WPE, 3, true, false, "strip S=3 pf " W); STRIP(WPE, 4, true, false, "strip S=4 pf " W); \
+        STRIP(WPE, 8, true, false, "strip S=8 pf " W); STRIP(WPE, 16, true, false, "strip S=16 pf " W); } while (0)
+#define WIDE(WPE, H, LABEL) do { vs.push_back({d + LABEL, H, 4, false, true, [](const Args& a, dim3 g, hipStream_t s) { hipLaunchKernelGGL((k_wide<WPE, D, H>), g, dim3(256), 0, s, a); }}); \
+        vs.back().wpe = WPE; } while (0)
+    STRIPS(2, "2 waves per SIMD");
+    STRIPS(3, "3 waves per SIMD");
+    STRIPS(4, "4 waves per SIMD");
+    STRIPS(5, "5 waves per SIMD");
+    STRIPS(6, "6 waves per SIMD");
+    WIDE(4, 16, "tile 16 rows, 4 waves per SIMD");
+    WIDE(5, 16, "tile 16 rows, 5 waves per SIMD");
+    WIDE(5, 12, "tile 12 rows, 5 waves per SIMD");
+    vs.push_back({d + "baseline 8 rows, hit blocks (shipped, hits)", 8, 4, false, true, [](const Args& a, dim3 g, hipStream_t s) { hipLaunchKernelGGL((k_own<D, 8, 4, PAIR_GLOBAL, FAC_SCALAR, false, true>), g, dim3(256), 0, s, a); }});
+    vs.back().hits = true;
+    STRIP(3, 2, false, true, "strip S=2 3 waves per SIMD, hit blocks");
+    STRIP(3, 2, true, true, "strip S=2 pf 3 waves per SIMD, hit blocks");
+    STRIP(4, 2, false, true, "strip S=2 4 waves per SIMD, hit blocks");
+    STRIP(4, 4, false, true, "strip S=4 4 waves per SIMD, hit blocks");
+    STRIP(4, 16, false, true, "strip S=16 4 waves per SIMD, hit blocks");
+#undef WIDE
 #undef OWN
 #undef STG
+#undef STRIP
+#undef STRIPS
 }
 
 int main(int argc, char** argv)
@@ -201,7 +339,7 @@ int main(int argc, char** argv)
     const int ld = (C + 15) / 16 * 16;
     const size_t n = (size_t)R * ld;
     constexpr int DMAX = 16;
-    double *A, *B, *A0, *pring, *fring; unsigned long long* sum;
+    double *A, *B, *A0, *pring, *fring; unsigned long long* sum; int* rring;
     CK(hipMalloc(&A, n * 8)); CK(hipMalloc(&B, n * 8)); CK(hipMalloc(&A0, n * 8));
     CK(hipMalloc(&pring, (size_t)DMAX * ld * 8)); CK(hipMalloc(&fring, (size_t)DMAX * R * 8)); CK(hipMalloc(&sum, 8));
     {
@@ -212,6 +350,12 @@ int main(int argc, char** argv)
         for (size_t i = 0; i < hf.size(); ++i) hf[i] = 1e-3 * (double)((i * 9973u) % 991) / 991.0;
         CK(hipMemcpy(pring, hp.data(), hp.size() * 8, hipMemcpyHostToDevice)); CK(hipMemcpy(fring, hf.data(), hf.size() * 8, hipMemcpyHostToDevice));
     }
+    {
+        int hr[DMAX]; for (int k = 0; k < DMAX; ++k) hr[k] = (int)(((long long)(2 * k + 1) * (R - 1)) / (2 * DMAX));    // uniformly spread, never the last row
+        CK(hipMalloc(&rring, sizeof(hr))); CK(hipMemcpy(rring, hr, sizeof(hr), hipMemcpyHostToDevice));
+    }
+    hipDeviceProp_t prop; CK(hipGetDeviceProperties(&prop, 0));
+    const int simds = prop.multiProcessorCount * 4;
     hipStream_t s; CK(hipStreamCreate(&s));
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     const int ncw = (ld + 127) / 128;
@@ -221,12 +365,13 @@ int main(int argc, char** argv)
     variants<8>(vs); variants<12>(vs); variants<16>(vs);
     int differs = 0;                                         // a shipping candidate whose sweep is not the shipped tile's: exit status 1
     for (int pass = 0; pass < 2; ++pass) {
-        unsigned long long base = 0;
+        unsigned long long base = 0, base_hits = 0;
         for (size_t vi = 0; vi < vs.size(); ++vi) {
             const Variant& v = vs[vi];
-            Args a{}; a.pring = pring; a.fring = fring; a.ld = ld; a.R = R; a.ncw = ncw; a.cp = 1e-4; a.cf = 1e-4;
+            Args a{}; a.pring = pring; a.fring = fring; a.ld = ld; a.R = R; a.ncw = ncw; a.cp = 1e-4; a.cf = 1e-4; a.rring = rring;
             dim3 grid;
-            if (v.staged) { const int nrbw = (R + v.W * v.H - 1) / (v.W * v.H); a.nunits = ncw * nrbw; grid = dim3(ncw * nrbw); }
+            if (v.strip) { a.nunits = ncw * (((R + v.H - 1) / v.H + v.strip - 1) / v.strip); grid = dim3((a.nunits + v.W - 1) / v.W); }
+            else if (v.staged) { const int nrbw = (R + v.W * v.H - 1) / (v.W * v.H); a.nunits = ncw * nrbw; grid = dim3(ncw * nrbw); }
             else { a.nunits = ncw * ((R + v.H - 1) / v.H); grid = dim3((a.nunits + v.W - 1) / v.W); }
             CK(hipMemcpyAsync(A, A0, n * 8, hipMemcpyDeviceToDevice, s));
             int it = 0;
@@ -246,9 +391,13 @@ int main(int argc, char** argv)
             float ms; CK(hipEventElapsedTime(&ms, e0, e1));
             const double us = 1e3 * ms / reps;
             if (v.name.find("(shipped)") != std::string::npos) base = got;
-            const char* ok = !v.ships ? "diagnostic" : (got == base ? "same bits" : "DIFFERS");
-            if (v.ships && got != base) ++differs;
-            printf("pass %d  %-52s %8.2f us  %7.1f GB/s  (%.3f of 8 TB/s)  %s\n", pass, v.name.c_str(), us, bytes / us / 1e3, bytes / us / 1e3 / 8000.0, ok);
+            if (v.name.find("(shipped, hits)") != std::string::npos) base_hits = got;
+            const unsigned long long want = v.hits ? base_hits : base;
+            const char* ok = !v.ships ? "diagnostic" : (got == want ? "same bits" : "DIFFERS");
+            if (v.ships && got != want) ++differs;
+            char occ[64] = "";
+            if (v.strip) snprintf(occ, sizeof occ, "  %d waves / %d slots = %.2f", a.nunits, simds * v.wpe, (double)a.nunits / (simds * v.wpe));
+            printf("pass %d  %-60s %8.2f us  %7.1f GB/s  (%.3f of 8 TB/s)  %s%s\n", pass, v.name.c_str(), us, bytes / us / 1e3, bytes / us / 1e3 / 8000.0, ok, occ);
             fflush(stdout);
         }
     }
