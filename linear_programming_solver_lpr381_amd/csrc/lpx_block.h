@@ -33,6 +33,14 @@ static_assert(SELP_PASS_ROWS == SELP_NT * SELP_U, "kept for the tests that read 
 static_assert(SELP_PMAX <= 64 && SELP_PMAX <= 2 * SELP_SB, "pending scalars: one lane each; row prefetch: two groups");
 static_assert(SELC_ROWS % 64 == 0 && SELC_ROWS <= 1024, "column launch: whole waves, one workgroup");
 static_assert(SELP_LDS_ROWS <= 2 * SELP_RU * SELP_NT, "row launch: the ratio buffer in at most two passes");
+// Scan record of one workgroup of the column launch: what the hysteresis chain needs of its SELC_ROWS rows (see
+// block_hysteresis_segments below) -- v: the least ratio of its live constraint rows (+inf: none eligible), i: the first row of
+// that minimum, or -1 unless that row is alone in the band [v, v + tol].  They follow the ratio buffer (selc_rec_offset doubles in).
+struct alignas(16) SelcRec { double v; int i; int pad; };
+__host__ __device__ constexpr int selc_recs(int R) { return (R + SELC_ROWS - 1) / SELC_ROWS; }      // records of a handle of R rows
+__host__ __device__ constexpr size_t selc_rec_offset(int R) { return ((size_t)R + 2) & ~(size_t)1; }  // behind rat[R], 16-byte aligned
+__host__ __device__ constexpr size_t selc_ratio_bytes(int R) { return sizeof(double) * selc_rec_offset(R) + sizeof(SelcRec) * (size_t)selc_recs(R); }
+static_assert(SELP_LDS_ROWS <= 64 * SELC_ROWS, "row launch: lane k of a wave holds scan record k");
 
 // ------------------------------------------------------------------------------------------------
 // workgroup primitives (wave64)

@@ -48,7 +48,7 @@ struct lpx_tableau {
     // fused pivot (lpx_pivot_fused): second tableau buffer and the index-1 copies of the small per-pivot vectors, on first use
     double* fT = nullptr; char* fslab = nullptr;
     double* fprow = nullptr; double* frhs = nullptr; lpx::DevState* frec = nullptr;
-    double* frat = nullptr;         // [Rcap + 1] ratios of the select-only pair's column launch, then T[m,q] (lpx_pivot_ratio)
+    double* frat = nullptr;         // [Rcap + 1] ratios of the select-only pair's column launch, then T[m,q], then its scan records (lpx_pivot_ratio; pivot_ratio_bytes)
     char* dring = nullptr; int dring_slots = 0;   // deferred pivots of run_fused: ring of pivot rows, factor columns, row indices
     bool fused_off = false;         // the second buffer did not fit: stay on the two-launch path
     bool suspended2 = false;        // ... by the two-launch group kernels (it must continue there: no pending pivot, state in *hst)

@@ -213,8 +213,10 @@ int pivot_defer_max();                       // deepest deferral the sweep kerne
 hipError_t launch_fused_init(const FusedParams& f, hipStream_t s);
 // launch L of a run (0: the prologue's): a sweep applying f.defer pending pivots when L is a positive multiple of f.defer,
 // else select-only -- one kernel, or two (column launch, row launch) where pivot_select_is_pair(ld, capacity rows).
-// rat: the handle's ratio buffer (capacity rows + 1 doubles), which only the pair uses
+// rat: the handle's ratio buffer (capacity rows + 1 doubles, then the column launch's scan records: pivot_ratio_bytes(capacity rows)
+// in all), which only the pair uses
 bool pivot_select_is_pair(int ld, int R);
+size_t pivot_ratio_bytes(int R);
 size_t pivot_stream_bytes();                 // UPD_STREAM_BYTES: a handle above it cannot live in the Infinity Cache (deepest default deferral)
 hipError_t launch_pivot_fused(const FusedParams& f, double* rat, long long L, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 // the n pivots a finished run left pending (its last record: buffer, count, oldest slot), applied into buffer 0

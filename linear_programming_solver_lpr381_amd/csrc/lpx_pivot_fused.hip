@@ -91,8 +91,9 @@ __device__ __forceinline__ int fp_slot(int lm, int n, int s, int ring) { const i
 // (slot 20 has the launch's own s_memrealtime span).  Slots of the one-launch form (lpx_pivot_select_ws): 0 record load and
 // branch, 1 column gather, 2 pending chain, 3 ratio store and barrier, 4 scan, 5 piv chain, 6 row loop, 7 wave and hand-off
 // reduction, 8 tail stores, 9 gather trips, 10-12 gather per trip (the third and later trips together), 20 realtime, 21 launches,
-// 22 pending pivots summed.  The row launch of the pair (lpx_pivot_select) uses the same range: 0 record, shape and ratios into
-// LDS, 1 issue of round 2, 3 barrier, 4 - 8 and 20 - 22 as above; the column launch has its own (LPX_FC_*, below).
+// 22 pending pivots summed.  The row launch of the pair (lpx_pivot_select) uses the same range: 0 record, shape and scan records,
+// 4 the replay, 3 the exact scan behind a tie (9 counts those steps), 1 issue of round 2, 5 - 8 and 20 - 22 as above; the column
+// launch has its own (LPX_FC_*, below).
 #define LPX_FS_BEGIN(on) const bool fs_on_ = (on) && blockIdx.x == 0 && threadIdx.x == 0; unsigned long long fs_acc_[13] = {0}; \
     unsigned long long fs_prev_ = __builtin_amdgcn_s_memtime(); const unsigned long long fs_rt0_ = __builtin_amdgcn_s_memrealtime();
 #define LPX_FS(slot) do { if (fs_on_) { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); fs_acc_[(slot)] += n_ - fs_prev_; fs_prev_ = n_; } } while (0)
@@ -100,6 +101,7 @@ __device__ __forceinline__ int fp_slot(int lm, int n, int s, int ring) { const i
 #define LPX_FS_TRIP(trip) do { if (fs_on_) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); \
     const unsigned long long n_ = __builtin_amdgcn_s_memtime(), d_ = n_ - fs_prev_; fs_prev_ = n_; fs_acc_[1] += d_; fs_acc_[9] += 1; \
     if ((trip) == 0) fs_acc_[10] += d_; else if ((trip) == 1) fs_acc_[11] += d_; else fs_acc_[12] += d_; } } while (0)
+#define LPX_FS_TIE() do { if (fs_on_) fs_acc_[9] += 1; } while (0)
 #define LPX_FS_END(npend) do { if (fs_on_) { _Pragma("unroll") for (int k_ = 0; k_ < 13; ++k_) lpx_g_stamps[8 + k_] += fs_acc_[k_]; \
     lpx_g_stamps[28] += __builtin_amdgcn_s_memrealtime() - fs_rt0_; lpx_g_stamps[29] += 1; lpx_g_stamps[30] += (unsigned long long)(npend); } } while (0)
 #else
@@ -107,6 +109,7 @@ __device__ __forceinline__ int fp_slot(int lm, int n, int s, int ring) { const i
 #define LPX_FS(slot) do {} while (0)
 #define LPX_FS_W(slot) do {} while (0)
 #define LPX_FS_TRIP(trip) do {} while (0)
+#define LPX_FS_TIE() do {} while (0)
 #define LPX_FS_END(npend) do {} while (0)
 #endif
 
@@ -497,23 +500,29 @@ __global__ __launch_bounds__(FP_NT) void lpx_pivot_select_ws(FusedParams F)
 // find the same row r as the 31 others: two thirds of that launch.  Now
 //   lpx_pivot_ratio  (column launch)  ceil(Rcap / SELC_ROWS) workgroups, one row per lane: T_{k+1}[i,q] through the n pending
 //                    pivots, the RHS correction and the ratio of row i -> facn, rhsn and the handle's ratio buffer (Rcap + 1
-//                    doubles; the last one is T_{k+1}[m,q])
-//   lpx_pivot_select (row launch)     the nsel workgroups of every select: the ratio buffer into LDS, the scan, row r and the
-//                    objective row through the pending pivots, the hand-off of the partial argmins, the next record
+//                    doubles; the last one is T_{k+1}[m,q]), and one scan record per workgroup behind it (SelcRec, lpx_block.h)
+//   lpx_pivot_select (row launch)     the nsel workgroups of every select: the leaving row from the scan records (the ratios
+//                    themselves only behind a tie), row r and the objective row through the pending pivots, one partial argmin
+//                    per workgroup -- handed off to the last arriver only where the next step is not this pair -- the next record
+// Both all-to-all exchanges of a pivot (column q to every row and r back; the objective row to one argmin) cross a kernel boundary
+// anyway, so neither is paid a second time inside a launch: the column launch reduces each 256 rows to what the hysteresis chain
+// needs of them, and the entering column of 1 <= n <= d - 2 is reduced from the partials by the next column launch (n >= 2 there).
 // The kernel boundary between them publishes the column launch's plain stores; a hand-off inside one launch would need a spin
 // wait on workgroups that HIP does not promise to be co-resident.  Same loads of the same values and the same
 // arithmetic as fused_select<.., ..>(F, n, false).  Rounds of the column launch:
-//   round 1  the record and the live shape (leaves: status not running, iteration cap met, no entering column -- the row launch
-//            alone decides terminal states and writes the next record; workgroups past the live rows)
+//   round 1  the record and the live shape, for n >= 2 the partial argmins of the step before as well (leaves: status not
+//            running, iteration cap met, no entering column -- the row launch alone decides terminal states and writes the next
+//            record, the column launch only patches rec[c].qn for it; workgroups past the live rows)
 //   round 2  T[i,q], rhs[i], the factor columns of the n live pending pivots (one instantiation per n) and the pending pivots'
 //            scalars (one vector load per wave: lane k holds pq and r of pending pivot k, read back with v_readlane), all in
 //            flight together -- the chain then runs in registers
 // and of the row launch:
-//   round 1  the record, the live shape and the ratio buffer (its address does not depend on the record) -> LDS (dynamic)
-//   round 2  the pending pivots' scalars, the pending pivot rows and the objective row of the workgroup's columns, in flight
-//            while the ratios are scanned out of LDS
-//   round 3  once r is known: row r, the pivot element and the n factors of row r together
-//   round 4  the hand-off: one partial per workgroup (block_min_idx first: 8 waves x 32 workgroups would overflow the 128 entries)
+//   round 1  the record, the live shape and the scan records (their address does not depend on the record); r from the records
+//            (behind a tie: one more round, the ratio buffer -> LDS (dynamic), and the exact scan)
+//   round 2  everything else at once, r being known: the pending pivots' scalars with the n factors of row r and the pivot
+//            element, then row r, the pending pivot rows and the objective row of the workgroup's columns
+//   round 3  one partial per workgroup (block_min_idx first: 8 waves x 32 workgroups would overflow the 128 entries), with the
+//            hand-off of fused_select for n = 0 and n = d - 1
 // The record bookkeeping and the hand-off are copies of fused_select's: shared helpers moved instructions in all 32 sweep
 // kernels.  (SELC_*, SELP_*: lpx_block.h, beside the other select kernels' launch constants)
 
@@ -539,7 +548,13 @@ __device__ __forceinline__ double lane_f64(double x, int k)
 
 // the column launch through N pending pivots (N known at compile time: exactly N factor columns in flight)
 template <int N>
-__device__ __forceinline__ void pivot_ratio_rows(const FusedParams& F, double* __restrict__ rat)
+__device__ __forceinline__ void pivot_ratio_patch(const FusedParams& F, int c, int q)
+{
+    if (N >= 2 && blockIdx.x == 0 && threadIdx.x == 0) F.rec[c].qn = q;
+}
+struct SelcExchange { double v[SELC_ROWS / 64]; int i[SELC_ROWS / 64]; int n[SELC_ROWS / 64]; };      // the waves' shares of the scan record
+template <int N>
+__device__ __forceinline__ void pivot_ratio_rows(const FusedParams& F, double* __restrict__ rat, SelcExchange& X)
 {
     const SelParams& P = F.P;
     const int t = threadIdx.x;
@@ -548,9 +563,29 @@ __device__ __forceinline__ void pivot_ratio_rows(const FusedParams& F, double* _
     // round 1: the live shape beside the record
     int R = P.R, C = P.C;
     if (P.shape) { R = P.shape[0]; C = P.shape[1]; }
+    // N >= 2: the step before this one was a row launch that left without a hand-off (lpx_pivot_select: 1 <= n <= d - 2), so the
+    // entering column is still its nsel partial argmins.  Every wave loads them in this round (lane k: partial k, lanes past the
+    // last repeat it) and reduces them as the last-arriver did -- the same wave_min_idx, the same q, tie-break included.
+    MinIdx part; part.v = 0.0; part.i = 0;
+    if (N >= 2) {
+        const int k = min(t & 63, P.nblk - 1);
+        part.v = P.part_v[k]; part.i = P.part_i[k];
+    }
     const DevState cur = F.rec[c];
-    const int status = cur.status, primal_count = cur.primal_count, q = cur.qn, rnew = cur.r, buf = cur.pad[3] & 1;
-    if (status != LPX_RUNNING || primal_count >= P.max_iter || q < 0) return;     // the row launch writes the record of a run that is over
+    // the partials' loads stay in this round: left alone, they sink behind the leave tests.  The record and the shape are named so
+    // that their loads come first and keep their scalar form
+    if (N >= 2) asm volatile("" :: "s"(cur.status), "s"(cur.primal_count), "s"(cur.r), "s"(cur.pad[3]), "s"(R), "s"(C) : "memory");
+    const int status = cur.status, primal_count = cur.primal_count, rnew = cur.r, buf = cur.pad[3] & 1;
+    int q = cur.qn;
+    if (status != LPX_RUNNING || primal_count >= P.max_iter) return;     // the row launch writes the record of a run that is over
+    if (N >= 2) {
+        part = wave_min_idx(part);
+        q = part.i == INT_MAX ? -1 : part.i;
+    }
+    // N >= 2: the record gets its entering column from workgroup 0 (pivot_ratio_patch), for the row launch of this step to read
+    // behind the kernel boundary; nothing in this launch reads the field, every wave has its own q.  The store comes last, or
+    // every load behind it would lose its scalar form
+    if (q < 0) { pivot_ratio_patch<N>(F, c, q); return; }    // optimal: the row launch says so
     if ((int)blockIdx.x * SELC_ROWS >= R) return;            // the grid follows the capacity
     LPX_FC_W(0);
     const size_t ld = (size_t)P.ld, fld = (size_t)P.R;
@@ -598,34 +633,59 @@ __device__ __forceinline__ void pivot_ratio_rows(const FusedParams& F, double* _
         facn[i] = dn; rhsn[i] = nm;                          // factors of pivot k+1, numerators of the test after it
         if (i == m) rat[P.R] = dn;                           // T_{k+1}[m,q]: row m belongs to exactly one lane
     }
+    // The workgroup's scan record (SelcRec, lpx_block.h) over its live constraint rows i < m, with the expressions of
+    // block_hysteresis_segments: the minimum and its first row (wave_min_idx, then mi_pick over the waves), then the rows inside
+    // the band [v, v + tol].  Two exchanges among the waves through X; the row launch replays the chain over the records.
+    constexpr int NW = SELC_ROWS / 64;
+    const int wave = t >> 6;
+    MinIdx lmin; lmin.v = i < m ? ratio : __builtin_inf(); lmin.i = i;
+    const double rt = lmin.v;
+    lmin = wave_min_idx(lmin);
+    if ((t & 63) == 0) { X.v[wave] = lmin.v; X.i[wave] = lmin.i; }
+    __syncthreads();
+    lmin.v = X.v[0]; lmin.i = X.i[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) { MinIdx y; y.v = X.v[w]; y.i = X.i[w]; lmin = mi_pick(lmin, y); }
+    const int inband = __popcll(__ballot(i < m && (rt - P.tol_primal) <= lmin.v));
+    if ((t & 63) == 0) X.n[wave] = inband;
+    __syncthreads();
+    if (t == 0) {
+        int alone = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) alone += X.n[w];
+        SelcRec rec; rec.v = lmin.v; rec.i = alone == 1 ? lmin.i : -1; rec.pad = 0;
+        reinterpret_cast<SelcRec*>(rat + selc_rec_offset(P.R))[blockIdx.x] = rec;
+    }
+    pivot_ratio_patch<N>(F, c, q);
     LPX_FC_W(2);
     LPX_FC_END(N);
 }
 
 __global__ __launch_bounds__(SELC_ROWS) void lpx_pivot_ratio(FusedParams F, double* __restrict__ rat)
 {
+    __shared__ SelcExchange X;
     switch (F.lm % F.defer) {                                // pending pivots: the launch's own argument, no load
-    case 0: pivot_ratio_rows<0>(F, rat); break;
-    case 1: pivot_ratio_rows<1>(F, rat); break;
-    case 2: pivot_ratio_rows<2>(F, rat); break;
-    case 3: pivot_ratio_rows<3>(F, rat); break;
-    case 4: pivot_ratio_rows<4>(F, rat); break;
-    case 5: pivot_ratio_rows<5>(F, rat); break;
-    case 6: pivot_ratio_rows<6>(F, rat); break;
-    case 7: pivot_ratio_rows<7>(F, rat); break;
-    case 8: pivot_ratio_rows<8>(F, rat); break;
-    case 9: pivot_ratio_rows<9>(F, rat); break;
-    case 10: pivot_ratio_rows<10>(F, rat); break;
-    case 11: pivot_ratio_rows<11>(F, rat); break;
-    case 12: pivot_ratio_rows<12>(F, rat); break;
-    case 13: pivot_ratio_rows<13>(F, rat); break;
-    case 14: pivot_ratio_rows<14>(F, rat); break;
-    default: pivot_ratio_rows<SELP_PMAX>(F, rat); break;
+    case 0: pivot_ratio_rows<0>(F, rat, X); break;
+    case 1: pivot_ratio_rows<1>(F, rat, X); break;
+    case 2: pivot_ratio_rows<2>(F, rat, X); break;
+    case 3: pivot_ratio_rows<3>(F, rat, X); break;
+    case 4: pivot_ratio_rows<4>(F, rat, X); break;
+    case 5: pivot_ratio_rows<5>(F, rat, X); break;
+    case 6: pivot_ratio_rows<6>(F, rat, X); break;
+    case 7: pivot_ratio_rows<7>(F, rat, X); break;
+    case 8: pivot_ratio_rows<8>(F, rat, X); break;
+    case 9: pivot_ratio_rows<9>(F, rat, X); break;
+    case 10: pivot_ratio_rows<10>(F, rat, X); break;
+    case 11: pivot_ratio_rows<11>(F, rat, X); break;
+    case 12: pivot_ratio_rows<12>(F, rat, X); break;
+    case 13: pivot_ratio_rows<13>(F, rat, X); break;
+    case 14: pivot_ratio_rows<14>(F, rat, X); break;
+    default: pivot_ratio_rows<SELP_PMAX>(F, rat, X); break;
     }
 }
 static_assert(SELP_PMAX == 15, "lpx_pivot_ratio: one case per pending count");
 
-__global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const double* __restrict__ rat)
+__global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const double* __restrict__ rat, const SelcRec* recs)
 {
     extern __shared__ double sp_rat[];                       // the ratios of the test, one per row of the handle
     __shared__ double s_v[SELP_NT / 64];
@@ -636,34 +696,18 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const
     const int n = lm % F.defer;
     const int c = lm & 1;                                    // the current record comes with the launch: see fused_select
     LPX_FS_BEGIN(true)
-    // round 1: the ratios, the live shape and the record together, before the kernel's first store.  The ratio passes follow the
-    // capacity (a launch argument) and are issued first, so that no load waits for another: SELP_RU x SELP_NT rows per pass,
-    // the headline's 4097 in one
-    double x0[SELP_RU];
-#pragma unroll
-    for (int u = 0; u < SELP_RU; ++u) x0[u] = rat[min(P.R, u * SELP_NT + t)];
+    // round 1: the column launch's scan records, the live shape and the record together.  The records' address follows the capacity
+    // (a launch argument), so no load waits for another: lane k of every wave holds record k (lanes past the last repeat it)
+    // (`recs` is the ratio buffer's tail, rat + selc_rec_offset(P.R), as an argument of its own: a load through the restrict-qualified
+    // `rat` may pass the asm below and is sunk to its first use, behind the row operands' loads -- the replay then waits for all of them)
+    const SelcRec srec = recs[min(lane, selc_recs(P.R) - 1)];
     const double fs = rat[P.R];                              // T_{k+1}[m,q]
     int R = P.R, C = P.C;
     if (P.shape) { R = P.shape[0]; C = P.shape[1]; }
     const DevState cur = F.rec[c];
     DevState* nxt = F.rec + (c ^ 1);
-    // the record's loads stay here, in flight beside the ratios: left alone, the compiler sinks them behind the LDS stores
+    // the record's loads stay here, in flight beside the scan records' (which the clobber holds in place): left alone, the compiler sinks them
     asm volatile("" :: "s"(cur.status), "s"(cur.qn), "s"(cur.pad[3]), "s"(R) : "memory");
-#pragma unroll
-    for (int u = 0; u < SELP_RU; ++u) {
-        const int i = u * SELP_NT + t;
-        if (i < P.R) sp_rat[i] = x0[u];
-    }
-    for (int i0 = SELP_RU * SELP_NT; i0 < P.R; i0 += SELP_RU * SELP_NT) {
-        double x[SELP_RU];
-#pragma unroll
-        for (int u = 0; u < SELP_RU; ++u) x[u] = rat[min(P.R, i0 + u * SELP_NT + t)];
-#pragma unroll
-        for (int u = 0; u < SELP_RU; ++u) {
-            const int i = i0 + u * SELP_NT + t;
-            if (i < P.R) sp_rat[i] = x[u];
-        }
-    }
     const int status = cur.status, seq = cur.pad[2], buf = cur.pad[3] & 1;
     const int nsel = P.nblk;
     if (b == 0 && t == 0) *P.st = cur;                        // the host's copy: one launch behind
@@ -697,29 +741,49 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const
 #pragma unroll
     for (int k = 0; k < SELP_PMAX; ++k) pc0[k] = 0.0;
     if (final_status == LPX_RUNNING) {
-        // round 2: the row phase's operands that do not depend on r, in flight behind the scan
-        if (n > 0) {
-            pqv = F.pring[kslot * ld + q];
-            pfmv = F.fring[kslot * fld + m];
-            rsv = F.rring[kslot];
-        }
-        {
-            const int jc = min(j0 + t, C - 1);
-            ov0 = orow[jc];
-            if (n > 0) {
-#pragma unroll
-                for (int k = 0; k < SELP_SB; ++k) pc0[k] = F.pring[pslot(k) * ld + jc];
+        // The leaving row: the hysteresis chain of block_hysteresis_segments replayed over the S records of the live rows (S
+        // follows the live m; records past it are stale and take no part).  Every lane of every workgroup holds the same
+        // records, so a segment that would be entered through a tie sends all of them to the exact scan together.
+        // First the same short cut as wave_hysteresis_argmin's, one level up: if the least record is alone in its band among the
+        // records too, and its row alone inside its segment, the chain ends on that row whatever it accepted on the way (every
+        // earlier best is a ratio r with fl(r - tol) above the minimum; nothing behind can be lower by tol) -- a wave reduction
+        // and a ballot instead of a loop of S dependent branches (1.6 us over the headline's 16 records).
+        const int S = selc_recs(m);
+        double best = __builtin_inf();
+        int tie = -1;
+        MinIdx g; g.v = lane < S ? srec.v : __builtin_inf(); g.i = lane;
+        const double myv = g.v;
+        g = wave_min_idx(g);
+        const int gi = __builtin_amdgcn_readlane(srec.i, g.i);
+        if (g.v < __builtin_inf() && __popcll(__ballot((myv - P.tol_primal) <= g.v)) == 1 && gi >= 0) r = gi;
+        else {
+            for (int sgi = 0; sgi < S; ++sgi) {
+                const double v = lane_f64(srec.v, sgi);
+                if (!(v < best - P.tol_primal)) continue;    // nothing in this segment beats the carried best
+                const int i = __builtin_amdgcn_readlane(srec.i, sgi);
+                if (i < 0) { tie = sgi; break; }
+                best = v; r = i;
             }
-            if (n > SELP_SB) {
-#pragma unroll
-                for (int k = SELP_SB; k < SELP_PMAX; ++k) pc0[k] = F.pring[pslot(k) * ld + jc];
-            }
         }
-        LPX_FS(1);
-        __syncthreads();                                     // the ratios are in LDS
-        LPX_FS(3);
-        r = block_hysteresis_segments<SELP_NT / 64>(m, P.tol_primal, CompactRatio{sp_rat});
         LPX_FS(4);
+        if (tie >= 0) {
+            // ties: the ratios into LDS and the exact scan from that segment on, best and position carried (any start is valid
+            // there).  The passes follow the capacity: SELP_RU x SELP_NT rows each, the headline's 4097 in one
+            for (int i0 = 0; i0 < P.R; i0 += SELP_RU * SELP_NT) {
+                double x[SELP_RU];
+#pragma unroll
+                for (int u = 0; u < SELP_RU; ++u) x[u] = rat[min(P.R, i0 + u * SELP_NT + t)];
+#pragma unroll
+                for (int u = 0; u < SELP_RU; ++u) {
+                    const int i = i0 + u * SELP_NT + t;
+                    if (i < P.R) sp_rat[i] = x[u];
+                }
+            }
+            __syncthreads();                                 // the ratios are in LDS
+            LPX_FS_TIE();
+            r = wave_hysteresis_argmin(m, P.tol_primal, CompactRatio{sp_rat}, tie * SELC_ROWS, best, r);
+            LPX_FS(3);
+        }
         if (r < 0) final_status = LPX_UNBOUNDED;
     }
     if (final_status != LPX_RUNNING) {
@@ -734,11 +798,32 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const
 
     ScanRule rule; rule.forced = 0; rule.eps = P.eps; rule.thresh = P.fthresh; rule.C = C; rule.c0 = 0;
     const double* __restrict__ trow = src + (size_t)r * ld;
-    // row r's factors of the pending pivots (lane k: pivot k) and the pivot element T_{k+1}[r,q], the column's own chain
+    // round 2, all of it at once now that r is known before any of it is needed: the pending pivots' scalars with row r's factors
+    // (lane k: pivot k) and the pivot element T_{k+1}[r,q] first -- the column's own chain waits for those alone -- then row r,
+    // the objective row and the pending pivot rows of the workgroup's columns
     double pfrv = 0.0;
-    if (n > 0) pfrv = F.fring[kslot * fld + r];
+    if (n > 0) {
+        pqv = F.pring[kslot * ld + q];
+        pfrv = F.fring[kslot * fld + r];
+        pfmv = F.fring[kslot * fld + m];
+        rsv = F.rring[kslot];
+    }
     double piv = trow[q];
-    double tr0 = trow[min(j0 + t, C - 1)];
+    double tr0;
+    {
+        const int jc = min(j0 + t, C - 1);
+        tr0 = trow[jc];
+        ov0 = orow[jc];
+        if (n > 0) {
+#pragma unroll
+            for (int k = 0; k < SELP_SB; ++k) pc0[k] = F.pring[pslot(k) * ld + jc];
+        }
+        if (n > SELP_SB) {
+#pragma unroll
+            for (int k = SELP_SB; k < SELP_PMAX; ++k) pc0[k] = F.pring[pslot(k) * ld + jc];
+        }
+    }
+    LPX_FS(1);
     for (int s = 0; s < n; ++s) {
         const double pq = lane_f64(pqv, s);
         const double nv = piv - lane_f64(pfrv, s) * pq;
@@ -779,9 +864,15 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const
         }
     }
     LPX_FS_W(6);
-    // one partial per workgroup, then the last-workgroup reduction of fused_select (agent-scope stores, wait, one add)
+    // one partial per workgroup, then the last-workgroup reduction of fused_select (agent-scope stores, wait, one add) -- where
+    // the next step's consumer expects nxt->qn: the sweep's fused_select (n = d - 1) or, behind the prologue (n = 0), a column
+    // launch with one pivot pending.  With 1 <= n <= d - 2 the next step is the pair again, its column launch reduces the partials
+    // itself (pivot_ratio_rows, N >= 2) and the kernel boundary publishes them: no wait, no counter, no last arriver.  (The switch
+    // is uniform and follows the launch arguments; part_i[MB_CNT] is left at zero.)
     best = block_min_idx<SELP_NT>(best, s_v, s_i);
-    if (t < 64) {
+    if (n >= 1 && n <= F.defer - 2) {
+        if (t == 0) { P.part_v[b] = best.v; P.part_i[b] = best.i; }
+    } else if (t < 64) {
         if (t == 0) {
             __hip_atomic_store(&P.part_v[b], best.v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(&P.part_i[b], best.i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -874,17 +965,19 @@ static hipError_t launch_pivot_select_pair(const FusedParams& f, double* rat, hi
 {
     const dim3 gc((f.P.R + SELC_ROWS - 1) / SELC_ROWS), gr(f.P.nblk);        // the column grid follows the capacity
     const size_t lds = sizeof(double) * (size_t)f.P.R;
+    const SelcRec* recs = reinterpret_cast<const SelcRec*>(rat + selc_rec_offset(f.P.R));
     if (e0 && e1) {
         hipExtLaunchKernelGGL(lpx_pivot_ratio, gc, dim3(SELC_ROWS), 0, s, e0, nullptr, 0, f, rat);
-        hipExtLaunchKernelGGL(lpx_pivot_select, gr, dim3(SELP_NT), lds, s, nullptr, e1, 0, f, (const double*)rat);
+        hipExtLaunchKernelGGL(lpx_pivot_select, gr, dim3(SELP_NT), lds, s, nullptr, e1, 0, f, (const double*)rat, recs);
     } else {
         hipLaunchKernelGGL(lpx_pivot_ratio, gc, dim3(SELC_ROWS), 0, s, f, rat);
-        hipLaunchKernelGGL(lpx_pivot_select, gr, dim3(SELP_NT), lds, s, f, (const double*)rat);
+        hipLaunchKernelGGL(lpx_pivot_select, gr, dim3(SELP_NT), lds, s, f, (const double*)rat, recs);
     }
     return hipGetLastError();
 }
 
 size_t pivot_stream_bytes() { return UPD_STREAM_BYTES; }
+size_t pivot_ratio_bytes(int R) { return selc_ratio_bytes(R); }
 bool pivot_select_is_pair(int ld, int R) { return R <= SELP_LDS_ROWS && tableau_bytes(ld, R) > ((size_t)SELP_MIN_MB << 20); }
 
 hipError_t launch_pivot_fused(const FusedParams& f0, double* rat, long long L, hipStream_t s, hipEvent_t e0, hipEvent_t e1)

@@ -376,7 +376,7 @@ bool lpx::fused_buffers(lpx_tableau* t)
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t tb = sizeof(double) * (size_t)t->Rcap * t->ld;
     const size_t sz[] = { up(sizeof(double) * t->ld), up(sizeof(double) * t->Rcap), up(2 * sizeof(DevState)),
-                          up(sizeof(double) * ((size_t)t->Rcap + 1)) };
+                          up(pivot_ratio_bytes(t->Rcap)) };
     if (malloc_retry((void**)&t->fT, tb) != hipSuccess || malloc_retry((void**)&t->fslab, sz[0] + sz[1] + sz[2] + sz[3]) != hipSuccess) {
         (void)hipGetLastError();
         hipFree(t->fT); hipFree(t->fslab);

@@ -22,7 +22,9 @@ import sys
 
 # row launch (and, above SELP_LDS_ROWS rows, the one-launch form lpx_pivot_select_ws, whose slots 1 - 3 are the column gather, the
 # pending chain and the ratio store): lpx_g_stamps[8 + k]
-NAMES = ["record, shape, ratios -> LDS", "round 2 issue (row operands)", "(one-launch form only)", "barrier", "scan (from LDS)",
+# (the row launch of the pair: "barrier" is the exact scan behind a tie, ratios into LDS included, and runs only on the steps the
+# last line counts; "scan" is the replay of the chain over the column launch's records)
+NAMES = ["record, shape, scan records", "round 2 issue (row operands)", "(one-launch form only)", "barrier / tie fallback", "scan (records or LDS)",
          "piv chain", "row loop", "block and hand-off reduction", "tail stores"]
 # column launch: lpx_g_stamps[21 + k]
 COL_NAMES = ["record load and leave tests", "round 2 (column, RHS, factors, scalars)", "chain, ratio and stores"]
@@ -55,14 +57,16 @@ def child(m, n, pivots):
     if not calls:
         print("  no stamps: is LPX_LIB_PATH the -DLPX_STAMPS library?")
         return
+    w = list(hs)[21:27]                                  # the column launch's stamps (w[4]: its launches; 0 in the one-launch form)
     tot = sum(v[:9])
     clk = tot / (rt / 100e6) / 1e9 if rt else 0.0        # s_memrealtime counts at 100 MHz
     print(f"  in-kernel clock ~{clk:.2f} GHz; stamped {tot / calls:.0f} cycles = {rt / calls / 100:.2f} us per launch, wave 0 of workgroup 0")
     for nm, x in zip(NAMES, v[:9]):
         print(f"  {nm:30s} {x / calls:9.0f} cycles {x / calls / clk / 1e3 if clk else 0:7.2f} us {100 * x / tot:5.1f}%")
-    if v[9]:
+    if w[4]:
+        print(f"  steps that took the tie fallback (exact scan over the ratios): {v[9]} of {calls}")
+    elif v[9]:
         print(f"  gather trips per launch {v[9] / calls:.2f}: first {v[10] / calls:.0f}, second {v[11] / calls:.0f}, later {v[12] / calls:.0f} cycles")
-    w = list(hs)[21:27]
     ccalls, crt, cpend = w[4], w[3], w[5]
     if not ccalls:
         print("  column launch: no stamps (the one-launch form ran)")
