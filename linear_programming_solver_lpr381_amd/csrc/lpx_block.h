@@ -106,6 +106,24 @@ __device__ __forceinline__ MinIdx wave_min_idx(MinIdx x)
     return r;
 }
 
+// wave_min_idx over lanes 0 .. 7 alone (the partials of at most eight waves), in every lane: three steps of the scan, lane 7 has it
+__device__ __forceinline__ MinIdx lanes8_min_idx(MinIdx x)
+{
+    const double inf = __builtin_inf();
+    double v = x.v;
+    v = fmin_nn(v, dpp_f64<0x111, 0xf>(inf, v));     // row_shr:1
+    v = fmin_nn(v, dpp_f64<0x112, 0xf>(inf, v));     // row_shr:2
+    v = fmin_nn(v, dpp_f64<0x114, 0xf>(inf, v));     // row_shr:4
+    MinIdx r;
+    r.v = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 7), __builtin_amdgcn_readlane(__double2loint(v), 7));
+    int i = x.v == r.v ? x.i : INT_MAX;
+    i = min(i, dpp_i32<0x111, 0xf>(INT_MAX, i));
+    i = min(i, dpp_i32<0x112, 0xf>(INT_MAX, i));
+    i = min(i, dpp_i32<0x114, 0xf>(INT_MAX, i));
+    r.i = __builtin_amdgcn_readlane(i, 7);
+    return r;
+}
+
 // All NT lanes call this. Returns the block-wide winner in every lane.
 template <int NT = SEL_NT>
 __device__ inline MinIdx block_min_idx(MinIdx x, double* s_v, int* s_i)

@@ -91,8 +91,9 @@ __device__ __forceinline__ int fp_slot(int lm, int n, int s, int ring) { const i
 // (slot 20 has the launch's own s_memrealtime span).  Slots of the one-launch form (lpx_pivot_select_ws): 0 record load and
 // branch, 1 column gather, 2 pending chain, 3 ratio store and barrier, 4 scan, 5 piv chain, 6 row loop, 7 wave and hand-off
 // reduction, 8 tail stores, 9 gather trips, 10-12 gather per trip (the third and later trips together), 20 realtime, 21 launches,
-// 22 pending pivots summed.  The row launch of the pair (lpx_pivot_select) uses the same range: 0 record, shape and scan records,
-// 4 the replay, 3 the exact scan behind a tie (9 counts those steps), 1 issue of round 2, 5 - 8 and 20 - 22 as above; the column
+// 22 pending pivots summed.  The row launch of the pair (lpx_pivot_select) uses the same range: 0 record, shape and scan records
+// (and, in this build, the wait for the operands issued beside them), 4 the replay, 3 the exact scan behind a tie (9 counts those
+// steps), 1 issue of the three loads behind r and the objective row's chain, 5 - 8 and 20 - 22 as above; the column
 // launch has its own (LPX_FC_*, below).
 #define LPX_FS_BEGIN(on) const bool fs_on_ = (on) && blockIdx.x == 0 && threadIdx.x == 0; unsigned long long fs_acc_[13] = {0}; \
     unsigned long long fs_prev_ = __builtin_amdgcn_s_memtime(); const unsigned long long fs_rt0_ = __builtin_amdgcn_s_memrealtime();
@@ -518,11 +519,15 @@ __global__ __launch_bounds__(FP_NT) void lpx_pivot_select_ws(FusedParams F)
 //            flight together -- the chain then runs in registers
 // and of the row launch:
 //   round 1  the record, the live shape and the scan records (their address does not depend on the record); r from the records
-//            (behind a tie: one more round, the ratio buffer -> LDS (dynamic), and the exact scan)
-//   round 2  everything else at once, r being known: the pending pivots' scalars with the n factors of row r and the pivot
-//            element, then row r, the pending pivot rows and the objective row of the workgroup's columns
+//            (behind a tie: one more round, the ratio buffer -> LDS (dynamic), and the exact scan).  In flight behind the scan
+//            records, from the launch arguments alone: the pending pivot rows of the workgroup's columns (a share of the
+//            capacity, not of the live columns) and the pending pivots' rows; behind the record, beside the replay: the objective
+//            row, pq and the objective row's factors of the pending pivots
+//   round 2  the three loads that need r: the n factors of row r, the pivot element and row r of the workgroup's columns
 //   round 3  one partial per workgroup (block_min_idx first: 8 waves x 32 workgroups would overflow the 128 entries), with the
 //            hand-off of fused_select for n = 0 and n = d - 1
+// (The column launch with its factor columns, RHS column and pending rows issued in round 1 as well, the row clamped by the
+// capacity, and its scan record in one exchange was built and measured in r17: it did not lower the pair's time and is not here.)
 // The record bookkeeping and the hand-off are copies of fused_select's: shared helpers moved instructions in all 32 sweep
 // kernels.  (SELC_*, SELP_*: lpx_block.h, beside the other select kernels' launch constants)
 
@@ -706,17 +711,39 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const
     if (P.shape) { R = P.shape[0]; C = P.shape[1]; }
     const DevState cur = F.rec[c];
     DevState* nxt = F.rec + (c ^ 1);
+    // Still round 1, behind the scan records (vmcnt counts in issue order: the replay's wait leaves these in flight): what follows
+    // from the launch arguments alone.  The pending pivot rows at this lane's first column, in groups of SELP_SB, and the pending
+    // pivots' rows (lane k of every wave: pending pivot k, 0 = oldest; lanes past the newest repeat it; n = 0, the prologue's
+    // launch, names the slot before its own and uses nothing of it).  The live shape arrives in this same round, so a workgroup's
+    // columns follow the capacity: rows of the ring are ld doubles, the loads are in bounds, and a lane past the live columns
+    // feeds and stores nothing (below).
+    const int nsel = P.nblk;
+    const size_t ld = (size_t)P.ld, fld = (size_t)P.R;
+    const int per = (P.C + nsel - 1) / nsel;
+    const int j0 = b * per, j1c = min(P.C, j0 + per);
+    const int jc0 = min(j0 + t, P.C - 1);
+    const size_t kslot = (size_t)fp_slot(lm, n, min(lane, n - 1), ring);
+    auto pslot = [&](int s) { return (size_t)fp_slot(lm, n, min(s, n - 1), ring); };
+    asm volatile("" ::: "memory");                           // the scan records' load stays in front
+    double pc0[SELP_PMAX];                                   // pending pivot rows at this lane's first column
+#pragma unroll
+    for (int k = 0; k < SELP_SB; ++k) pc0[k] = F.pring[pslot(k) * ld + jc0];
+#pragma unroll
+    for (int k = SELP_SB; k < SELP_PMAX; ++k) pc0[k] = 0.0;
+    if (n > SELP_SB) {
+#pragma unroll
+        for (int k = SELP_SB; k < SELP_PMAX; ++k) pc0[k] = F.pring[pslot(k) * ld + jc0];
+    }
+    const int rsv = F.rring[kslot];                          // pending pivot `ks`: its row as the ring has it
     // the record's loads stay here, in flight beside the scan records' (which the clobber holds in place): left alone, the compiler sinks them
     asm volatile("" :: "s"(cur.status), "s"(cur.qn), "s"(cur.pad[3]), "s"(R) : "memory");
     const int status = cur.status, seq = cur.pad[2], buf = cur.pad[3] & 1;
-    const int nsel = P.nblk;
     if (b == 0 && t == 0) *P.st = cur;                        // the host's copy: one launch behind
     LPX_FS_W(0);
     if (status != LPX_RUNNING) {
         if (b == 0 && t == 0) { DevState x = cur; x.pad[2] = seq + 1; *nxt = x; }
         return;
     }
-    const size_t ld = (size_t)P.ld, fld = (size_t)P.R;
     const double* __restrict__ src = buf ? F.T1 : P.T;
     double* __restrict__ prown = F.pring + (size_t)lm * ld;
     const int m = R - 1;
@@ -726,21 +753,17 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const
     // loop head, Models/PrimalSimplex.cs:95-106
     if (primal_count >= P.max_iter) final_status = LPX_ITER_LIMIT;
     else if (q < 0) final_status = LPX_OPTIMAL;
-    // lane k of every wave: pending pivot k (0 = oldest; lanes past the newest repeat it).  n = 0 (the prologue's launch) reads
-    // no slot: its own is the only one it could name
-    const int ks = min(lane, max(n - 1, 0));
-    const size_t kslot = (size_t)fp_slot(lm, n, ks, ring);
-    auto pslot = [&](int s) { return (size_t)fp_slot(lm, n, min(s, n - 1), ring); };
-    int rsv = -1;                                            // pending pivot `ks`: its row as the ring has it
     auto prs = [&](int s) { return s == n - 1 ? cur.r : __builtin_amdgcn_readlane(rsv, s); };     // the newest: the record's
     const double* __restrict__ orow = src + (size_t)m * ld;
-    const int per = (C + nsel - 1) / nsel;
-    const int j0 = b * per, j1 = min(C, j0 + per);
+    const int j1 = min(j1c, C);                              // the live columns of this workgroup's share of the capacity
     double pqv = 0.0, pfmv = 0.0;                            // T_s[r_s,q] / pivot and T_s[m,q_s] of pending pivot `ks`
-    double ov0 = 0.0, pc0[SELP_PMAX];                        // objective row and pending pivot rows at this lane's first column
-#pragma unroll
-    for (int k = 0; k < SELP_PMAX; ++k) pc0[k] = 0.0;
+    double ov0 = 0.0;                                        // objective row at this lane's first column
     if (final_status == LPX_RUNNING) {
+        // behind the record, beside the replay: what needs the record (buffer, q) or the live m, but not r
+        ov0 = orow[jc0];
+        pqv = F.pring[kslot * ld + q];
+        pfmv = F.fring[kslot * fld + m];
+        asm volatile("" ::: "memory");
         // The leaving row: the hysteresis chain of block_hysteresis_segments replayed over the S records of the live rows (S
         // follows the live m; records past it are stale and take no part).  Every lane of every workgroup holds the same
         // records, so a segment that would be entered through a tie sends all of them to the exact scan together.
@@ -798,32 +821,20 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const
 
     ScanRule rule; rule.forced = 0; rule.eps = P.eps; rule.thresh = P.fthresh; rule.C = C; rule.c0 = 0;
     const double* __restrict__ trow = src + (size_t)r * ld;
-    // round 2, all of it at once now that r is known before any of it is needed: the pending pivots' scalars with row r's factors
-    // (lane k: pivot k) and the pivot element T_{k+1}[r,q] first -- the column's own chain waits for those alone -- then row r,
-    // the objective row and the pending pivot rows of the workgroup's columns
-    double pfrv = 0.0;
-    if (n > 0) {
-        pqv = F.pring[kslot * ld + q];
-        pfrv = F.fring[kslot * fld + r];
-        pfmv = F.fring[kslot * fld + m];
-        rsv = F.rring[kslot];
-    }
+    // round 2, the three loads that need r: row r's factors (lane k: pending pivot k), the pivot element T_{k+1}[r,q] -- the
+    // column's own chain waits for those -- and row r at this lane's first column.  Everything else is in flight since round 1.
+    const double pfrv = F.fring[kslot * fld + r];
     double piv = trow[q];
-    double tr0;
-    {
-        const int jc = min(j0 + t, C - 1);
-        tr0 = trow[jc];
-        ov0 = orow[jc];
-        if (n > 0) {
-#pragma unroll
-            for (int k = 0; k < SELP_SB; ++k) pc0[k] = F.pring[pslot(k) * ld + jc];
-        }
-        if (n > SELP_SB) {
-#pragma unroll
-            for (int k = SELP_SB; k < SELP_PMAX; ++k) pc0[k] = F.pring[pslot(k) * ld + jc];
-        }
-    }
+    const double tr0 = trow[jc0];
     LPX_FS(1);
+    // while those three are in flight: the objective row through the pending pivots, which needs none of them (the same
+    // mul-then-sub, oldest first, that the row loop applies to a later pass's columns)
+    double ov1 = ov0;
+#pragma unroll
+    for (int k = 0; k < SELP_PMAX; ++k) {
+        if (k < n) ov1 = ov1 - lane_f64(pfmv, k) * pc0[k];
+    }
+    asm volatile("" : "+v"(ov1));                            // in front of the chain's wait, not behind it
     for (int s = 0; s < n; ++s) {
         const double pq = lane_f64(pqv, s);
         const double nv = piv - lane_f64(pfrv, s) * pq;
@@ -833,7 +844,7 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const
     MinIdx best; rule_init(rule, best);
     for (int jb = j0; jb < j1; jb += SELP_NT) {
         const int j = jb + t, jc = min(j, C - 1);
-        double tr = tr0, ov = ov0, pc[SELP_PMAX];
+        double tr = tr0, ov = ov1, pc[SELP_PMAX];
 #pragma unroll
         for (int k = 0; k < SELP_PMAX; ++k) pc[k] = pc0[k];
         if (jb != j0) {                                      // more columns than lanes: the later ones are loaded here
@@ -846,14 +857,17 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const
 #pragma unroll
                 for (int k = SELP_SB; k < SELP_PMAX; ++k) pc[k] = F.pring[pslot(k) * ld + jc];
             }
+#pragma unroll
+            for (int k = 0; k < SELP_PMAX; ++k) {
+                if (k < n) ov = ov - lane_f64(pfmv, k) * pc[k];
+            }
         }
-        // -> T_{k+1}[r,j], T_{k+1}[m,j] (m is never a pivot row)
+        // -> T_{k+1}[r,j]; T_{k+1}[m,j] is `ov` already (m is never a pivot row)
 #pragma unroll
         for (int k = 0; k < SELP_PMAX; ++k) {
             if (k < n) {
                 const double nt = tr - lane_f64(pfrv, k) * pc[k];
                 tr = r == prs(k) ? pc[k] : nt;
-                ov = ov - lane_f64(pfmv, k) * pc[k];
             }
         }
         if (j < j1) {
@@ -869,7 +883,14 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const
     // launch with one pivot pending.  With 1 <= n <= d - 2 the next step is the pair again, its column launch reduces the partials
     // itself (pivot_ratio_rows, N >= 2) and the kernel boundary publishes them: no wait, no counter, no last arriver.  (The switch
     // is uniform and follows the launch arguments; part_i[MB_CNT] is left at zero.)
-    best = block_min_idx<SELP_NT>(best, s_v, s_i);
+    // The block's argmin with one barrier: s_v / s_i have no other user in this kernel (the exact scan behind a tie works on
+    // sp_rat), so nothing has to be protected in front of the stores, and the eight waves' entries take three steps of the scan
+    static_assert(SELP_NT / 64 == 8, "lanes8_min_idx: one entry per wave");
+    best = wave_min_idx(best);
+    if (lane == 0) { s_v[t >> 6] = best.v; s_i[t >> 6] = best.i; }
+    __syncthreads();
+    best.v = s_v[lane & 7]; best.i = s_i[lane & 7];
+    best = lanes8_min_idx(best);
     if (n >= 1 && n <= F.defer - 2) {
         if (t == 0) { P.part_v[b] = best.v; P.part_i[b] = best.i; }
     } else if (t < 64) {

@@ -23,8 +23,9 @@ import sys
 # row launch (and, above SELP_LDS_ROWS rows, the one-launch form lpx_pivot_select_ws, whose slots 1 - 3 are the column gather, the
 # pending chain and the ratio store): lpx_g_stamps[8 + k]
 # (the row launch of the pair: "barrier" is the exact scan behind a tie, ratios into LDS included, and runs only on the steps the
-# last line counts; "scan" is the replay of the chain over the column launch's records)
-NAMES = ["record, shape, scan records", "round 2 issue (row operands)", "(one-launch form only)", "barrier / tie fallback", "scan (records or LDS)",
+# last line counts; "scan" is the replay of the chain over the column launch's records.  Since r17 the operands that do not need r
+# are issued in the first phase, which waits for them in this build: the shipped kernel leaves them in flight over the replay)
+NAMES = ["record, shape, scan records (+ early operands)", "issue of the 3 loads behind r", "(one-launch form only)", "barrier / tie fallback", "scan (records or LDS)",
          "piv chain", "row loop", "block and hand-off reduction", "tail stores"]
 # column launch: lpx_g_stamps[21 + k]
 COL_NAMES = ["record load and leave tests", "round 2 (column, RHS, factors, scalars)", "chain, ratio and stores"]
