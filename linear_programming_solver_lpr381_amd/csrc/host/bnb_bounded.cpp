@@ -1,10 +1,17 @@
-// host/bnb_bounded.cpp -- branch and bound by bound changes (lpx_solve_bnb_bounded / _bounded2 / _bounded3; the search by divers of
-// lpx_solve_bnb_bounded4 is SolveBnbDivers at the end; include/lpx.h): the root is SolveBounded
-// keeping its handle, and every node after it is ONE lpx_bounded_node (flagged search: lpx_bounded_node2) call on that handle -- the columns whose bounds differ
-// from the bounds now on the device, in ascending order.  A node is its path of (var, lower, upper) overrides: no tableau is
-// copied, parked or reshaped, and the node store is a few bytes per node.  Search order and pruning are those of
-// Models/Branch&Bound.cs (depth first, ceil child first :253-257, prune at z <= best + EPS :182, branch on the fraction closest
-// to 0.5 :197-213).  Its IsFeasible re-check of an incumbent is not mirrored: the dual loop ends primal feasible by construction.
+// host/bnb_bounded.cpp -- branch and bound by bound changes (include/lpx.h): three drivers around one frame.
+//   SolveBnbBounded   lpx_solve_bnb_bounded / _bounded2 / _bounded3: the root is SolveBounded keeping its handle, and every node after
+//                     it is ONE lpx_bounded_node (flagged search: lpx_bounded_node2 / _node3) call on that handle
+//   SolveBnbDivers    lpx_solve_bnb_bounded4 / 6 / 7: W handles, a round is ONE lpx_node_batch_run (_run_probe, _run2)
+//   SolveBnbPlunge    lpx_solve_bnb_bounded5: the same rounds with ONE lpx_node_batch_plunge, chains of up to D nodes
+// A node is its path of (var, lower, upper) overrides and what a call sends are the columns whose bounds differ from the bounds now
+// on the device, in ascending order: no tableau is copied, parked or reshaped, and the node store is a few bytes per node.  Search
+// order and pruning are those of Models/Branch&Bound.cs (depth first, ceil child first :253-257, prune at z <= best + EPS :182,
+// branch on the fraction closest to 0.5 :197-213).  Its IsFeasible re-check of an incumbent is not mirrored: the dual loop ends
+// primal feasible by construction.
+// The frame stands once, in the anonymous namespace: the checks, the root step, the pool of handles, the steal step, the bounds
+// diff of a popped node, the node log, the incumbent and the result tail.  The three search loops stay three functions: their
+// decide steps differ, and the order of their steps is part of the contract (the log is a function of the model, the options, the
+// flags, W and D alone).  No helper allocates per round: the scratch vectors are the callers'.
 #include "model.h"
 
 #include <algorithm>
@@ -20,13 +27,10 @@ constexpr double EPS = 1e-6;      // Models/Branch&Bound.cs:24
 struct Override { int var; double lo, ub; };
 struct Node { int depth; std::vector<Override> path; };
 
-}  // namespace
-
-SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
-                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
-                              int search_flags, int node_form)
+// The checks every driver makes, in this order; a driver adds its own in front of or behind them where the ABI tests pin them.
+void ValidateBnbBounded(int n, const std::vector<double>& lower, const std::vector<double>& upper, const std::vector<uint8_t>& is_int,
+                        int64_t max_nodes, int search_flags)
 {
-    const int n = original.NumVars();
     if ((!lower.empty() && (int)lower.size() != n) || (!upper.empty() && (int)upper.size() != n))
         throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: lower / upper need one entry per variable");
     if (!is_int.empty() && (int)is_int.size() != n)
@@ -43,98 +47,37 @@ SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<doubl
     if (max_nodes < 0) throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: max_nodes is negative");
     if (search_flags & ~(LPX_BDUAL_LONG_STEP | LPX_BDUAL_CUTOFF))
         throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: search_flags holds a bit other than LPX_BDUAL_LONG_STEP and LPX_BDUAL_CUTOFF");
-    if (node_form != -1 && node_form != LPX_NODE_LAUNCHES && node_form != LPX_NODE_ONCHIP && node_form != LPX_NODE_AUTO)
-        throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: node_form is none of LPX_NODE_LAUNCHES, LPX_NODE_ONCHIP and LPX_NODE_AUTO");
+}
 
+// The root: SolveBounded keeping its handle, the records reset, and -- where every node is on chip -- the fit of the root's shape,
+// which never changes and so decides for every node.  False: the root ends the search (an unbounded root is reported as that).
+bool SolveRoot(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper, const EngineOptions& opt,
+               bool onchip, BoundedSession& ses, BoundedInfo& binfo, SimplexResult& res, BnbBoundedInfo& info,
+               BnbDiversInfo* dinfo = nullptr, BnbPlungeInfo* pinfo = nullptr)
+{
     EngineOptions ropt = opt; ropt.quiet = true;
-    BoundedSession ses;
-    BoundedInfo binfo;
-    SimplexResult res = SolveBounded(original, lower, upper, ropt, nullptr, &binfo, &ses);
+    res = SolveBounded(original, lower, upper, ropt, nullptr, &binfo, &ses);
     info = BnbBoundedInfo();
+    if (dinfo) *dinfo = BnbDiversInfo();
+    if (pinfo) *pinfo = BnbPlungeInfo();
     info.constant = ses.constant;
     res.Nodes = 0; res.LpSolves = 1;
     res.Aux = {0.0, 0.0, 0.0, 0.0};
-    if (res.Status != LPX_OPTIMAL) return res;            // an unbounded root is reported as that
-    if (node_form == LPX_NODE_ONCHIP) {                   // the shape never changes: the root decides for every node
+    if (res.Status != LPX_OPTIMAL) return false;
+    if (onchip) {
         int R = 0, C = 0;
         lpx_tableau_shape(ses.h, &R, &C, nullptr);
         if (!lpx_bounded_node_fits(R, C))
             throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: the root tableau (" + std::to_string(R) + " x " + std::to_string(C) +
                                            ") does not fit the on-chip form of the node (lpx_bounded_node_fits)");
     }
+    return true;
+}
 
-    // the handle's columns stand for x' = x - lower: root bounds [0, ub'] of every variable
-    std::vector<double> root_lo((size_t)n, 0.0), root_ub(binfo.ub.begin(), binfo.ub.begin() + n);
-    std::vector<double> cur_lo = root_lo, cur_ub = root_ub, nb_lo, nb_ub;
-    lpx_run_opts o; lpx_default_opts(&o, 1);
-    o.max_iter = opt.max_iter;
-    o.batch = opt.batch > 0 ? opt.batch : 16;             // a node takes a handful of events: short batches, same bits
-    const uint8_t* mask = is_int.empty() ? nullptr : is_int.data();
-
-    double best = -1.0 / 0.0;
-    std::vector<double> best_x;
-    std::vector<Node> stack;
-    stack.push_back(Node{0, {}});
-    std::vector<int32_t> cols; std::vector<double> clo, cub;
-    while (!stack.empty()) {
-        if (max_nodes > 0 && info.nodes >= max_nodes) {
-            info.limit_rc = LPX_ITER_LIMIT;
-            info.limit_msg = "Bounded Branch and Bound: node limit of " + std::to_string(max_nodes) + " reached";
-            break;
-        }
-        Node node = std::move(stack.back());
-        stack.pop_back();
-        const int64_t index = info.nodes++;
-        nb_lo = root_lo; nb_ub = root_ub;
-        for (const Override& v : node.path) { nb_lo[v.var] = v.lo; nb_ub[v.var] = v.ub; }
-        cols.clear(); clo.clear(); cub.clear();
-        for (int j = 0; j < n; ++j)
-            if (nb_lo[j] != cur_lo[j] || nb_ub[j] != cur_ub[j]) { cols.push_back(j); clo.push_back(nb_lo[j]); cub.push_back(nb_ub[j]); }
-        const int K = (int)cols.size();
-        lpx_node_record rec;
-        // with CUTOFF the loop stops where this node would be pruned by bound anyway; search_flags = 0 stays the old call, messages included
-        const double cutoff = (search_flags & LPX_BDUAL_CUTOFF) ? best + EPS : 0.0;
-        const int rc = node_form > LPX_NODE_LAUNCHES      // LPX_NODE_LAUNCHES (and -1) stay the old calls, messages included
-            ? lpx_bounded_node3(ses.h, K, cols.data(), clo.data(), cub.data(), &o, LPX_BDUAL_SKIP_FIXED | search_flags, cutoff,
-                                n, mask, EPS, node_form, &rec)
-            : search_flags == 0
-            ? lpx_bounded_node(ses.h, K, cols.data(), clo.data(), cub.data(), &o, n, mask, EPS, &rec)
-            : lpx_bounded_node2(ses.h, K, cols.data(), clo.data(), cub.data(), &o, LPX_BDUAL_SKIP_FIXED | search_flags, cutoff,
-                                n, mask, EPS, &rec);
-        if (rc < 0) throw_lib(rc);
-        cur_lo = nb_lo; cur_ub = nb_ub;
-        info.events += rec.events; info.flips += rec.flips;
-        if (K > info.max_K) info.max_K = K;
-        lpx_bnb_node_log lg;
-        lg.depth = node.depth; lg.K = K; lg.status = rec.status; lg.events = rec.events; lg.flips = (int32_t)rec.flips;
-        lg.var = rec.pick.var; lg.z = rec.pick.z;
-        info.log.push_back(lg);
-        if (rec.status == LPX_ITER_LIMIT) {
-            info.limit_rc = LPX_ITER_LIMIT;
-            info.limit_msg = "Bounded Branch and Bound: node " + std::to_string(index) + " (depth " + std::to_string(node.depth) +
-                             ") reached the iteration limit of " + std::to_string(o.max_iter) + " events";
-            break;
-        }
-        if (rec.status == LPX_INFEASIBLE) { info.pruned_infeasible++; continue; }
-        const double z = rec.pick.z;
-        if (rec.status == LPX_CUTOFF || z <= best + EPS) { info.pruned_bound++; continue; }     // :182
-        if (rec.pick.var < 0) {                                                     // :189-195
-            std::vector<double> x((size_t)n, 0.0);
-            const int rs = lpx_tableau_bounded_solution(ses.h, n, x.data(), nullptr, nullptr);
-            if (rs) throw_lib(rs);
-            for (int j = 0; j < n; ++j) if (is_int.empty() || is_int[j]) x[j] = std::nearbyint(x[j]);
-            best = z; best_x = std::move(x);
-            info.incumbents++;
-            continue;
-        }
-        const int v = rec.pick.var;
-        Node fl{node.depth + 1, node.path}, ce{node.depth + 1, node.path};
-        fl.path.push_back(Override{v, nb_lo[v], std::floor(rec.pick.x_var)});
-        ce.path.push_back(Override{v, std::ceil(rec.pick.x_var), nb_ub[v]});
-        stack.push_back(std::move(fl));
-        stack.push_back(std::move(ce));                                             // explored first (:256)
-    }
-
+// The result from `res.Nodes` to the report text
+SimplexResult FinishBnbResult(SimplexResult res, const BnbBoundedInfo& info, const BoundedSession& ses, int n, double best,
+                              std::vector<double>& best_x)
+{
     res.Nodes = info.nodes; res.LpSolves = info.nodes + 1;
     res.Aux = {(double)info.nodes, (double)info.events, (double)info.flips, (double)info.incumbents};
     res.Trace.clear();
@@ -154,6 +97,159 @@ SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<doubl
                              ", dual-feasibility flips: " + std::to_string(info.flips) + "\n";
     res.Report = report + tail; res.Summary += tail.substr(2);
     return res;
+}
+
+// The handles of the divers: diver 0 is the root's handle, the others are copies of it.  The pool hands the copies and the batch
+// back on every way out.
+struct Pool {
+    std::vector<lpx_tableau*> h; lpx_node_batch* batch = nullptr;
+    void open(lpx_tableau* root, int W)
+    {
+        h.push_back(root);
+        for (int d = 1; d < W; ++d) {
+            lpx_tableau* c = nullptr;
+            const int rc = lpx_tableau_clone(root, &c);
+            if (rc) throw_lib(rc);
+            h.push_back(c);
+        }
+        const int rc = lpx_node_batch_create(W, h.data(), &batch);
+        if (rc) throw_lib(rc);
+    }
+    ~Pool() { lpx_node_batch_destroy(batch); for (size_t d = 1; d < h.size(); ++d) lpx_tableau_destroy(h[d]); }
+};
+
+// A diver: the bounds now on its handle (cur), those of the node it holds (nb), its own depth-first stack
+struct Diver { std::vector<double> cur_lo, cur_ub, nb_lo, nb_ub; std::vector<Node> stack; Node node; };
+
+bool AnyOpen(const std::vector<Diver>& dv) { for (const Diver& d : dv) if (!d.stack.empty()) return true; return false; }
+
+// The steal step: every idle diver takes the oldest entry of the longest stack, lengths as they stand now
+void StealForIdle(std::vector<Diver>& dv, BnbDiversInfo& dinfo)
+{
+    const int W = (int)dv.size();
+    for (int d = 0; d < W; ++d) {
+        if (!dv[d].stack.empty()) continue;
+        int v = 0;
+        for (int k = 1; k < W; ++k) if (dv[k].stack.size() > dv[v].stack.size()) v = k;
+        if (dv[v].stack.size() < 2) continue;
+        dv[d].stack.push_back(std::move(dv[v].stack.front()));
+        dv[v].stack.erase(dv[v].stack.begin());
+        dinfo.steals++;
+    }
+}
+
+// The bounds of a node from its path (nb), and the columns in which they differ from the bounds now on the handle (cur) appended to
+// cols / clo / cub in ascending order; the return value is their count K
+int DiffBounds(const Node& node, const std::vector<double>& root_lo, const std::vector<double>& root_ub, const std::vector<double>& cur_lo,
+               const std::vector<double>& cur_ub, std::vector<double>& nb_lo, std::vector<double>& nb_ub, std::vector<int32_t>& cols,
+               std::vector<double>& clo, std::vector<double>& cub)
+{
+    nb_lo = root_lo; nb_ub = root_ub;
+    for (const Override& v : node.path) { nb_lo[v.var] = v.lo; nb_ub[v.var] = v.ub; }
+    int K = 0;
+    for (int j = 0; j < (int)nb_lo.size(); ++j)
+        if (nb_lo[j] != cur_lo[j] || nb_ub[j] != cur_ub[j]) { cols.push_back(j); clo.push_back(nb_lo[j]); cub.push_back(nb_ub[j]); ++K; }
+    return K;
+}
+
+bool NodeLimitReached(int64_t max_nodes, BnbBoundedInfo& info)
+{
+    if (!(max_nodes > 0 && info.nodes >= max_nodes)) return false;
+    info.limit_rc = LPX_ITER_LIMIT;
+    info.limit_msg = "Bounded Branch and Bound: node limit of " + std::to_string(max_nodes) + " reached";
+    return true;
+}
+
+// A node's record into the counts and the log; true: it reached the iteration limit, which ends the search
+bool LogNode(BnbBoundedInfo& info, int64_t index, int depth, int K, const lpx_node_record& rec, int max_iter)
+{
+    info.events += rec.events; info.flips += rec.flips;
+    if (K > info.max_K) info.max_K = K;
+    lpx_bnb_node_log lg;
+    lg.depth = depth; lg.K = K; lg.status = rec.status; lg.events = rec.events; lg.flips = (int32_t)rec.flips;
+    lg.var = rec.pick.var; lg.z = rec.pick.z;
+    info.log.push_back(lg);
+    if (rec.status != LPX_ITER_LIMIT) return false;
+    info.limit_rc = LPX_ITER_LIMIT;
+    info.limit_msg = "Bounded Branch and Bound: node " + std::to_string(index) + " (depth " + std::to_string(depth) +
+                     ") reached the iteration limit of " + std::to_string(max_iter) + " events";
+    return true;
+}
+
+// The incumbent step (:189-195): the solution the handle holds, its integer columns to the nearest integer
+void TakeIncumbent(lpx_tableau* h, int n, const std::vector<uint8_t>& is_int, double z, double& best, std::vector<double>& best_x,
+                   BnbBoundedInfo& info)
+{
+    std::vector<double> x((size_t)n, 0.0);
+    const int rs = lpx_tableau_bounded_solution(h, n, x.data(), nullptr, nullptr);
+    if (rs) throw_lib(rs);
+    for (int j = 0; j < n; ++j) if (is_int.empty() || is_int[j]) x[j] = std::nearbyint(x[j]);
+    best = z; best_x = std::move(x);
+    info.incumbents++;
+}
+
+}  // namespace
+
+SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
+                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
+                              int search_flags, int node_form)
+{
+    const int n = original.NumVars();
+    ValidateBnbBounded(n, lower, upper, is_int, max_nodes, search_flags);
+    if (node_form != -1 && node_form != LPX_NODE_LAUNCHES && node_form != LPX_NODE_ONCHIP && node_form != LPX_NODE_AUTO)
+        throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: node_form is none of LPX_NODE_LAUNCHES, LPX_NODE_ONCHIP and LPX_NODE_AUTO");
+
+    BoundedSession ses;
+    BoundedInfo binfo;
+    SimplexResult res;
+    if (!SolveRoot(original, lower, upper, opt, node_form == LPX_NODE_ONCHIP, ses, binfo, res, info)) return res;
+
+    // the handle's columns stand for x' = x - lower: root bounds [0, ub'] of every variable
+    std::vector<double> root_lo((size_t)n, 0.0), root_ub(binfo.ub.begin(), binfo.ub.begin() + n);
+    std::vector<double> cur_lo = root_lo, cur_ub = root_ub, nb_lo, nb_ub;
+    lpx_run_opts o; lpx_default_opts(&o, 1);
+    o.max_iter = opt.max_iter;
+    o.batch = opt.batch > 0 ? opt.batch : 16;             // a node takes a handful of events: short batches, same bits
+    const uint8_t* mask = is_int.empty() ? nullptr : is_int.data();
+
+    double best = -1.0 / 0.0;
+    std::vector<double> best_x;
+    std::vector<Node> stack;
+    stack.push_back(Node{0, {}});
+    std::vector<int32_t> cols; std::vector<double> clo, cub;
+    while (!stack.empty()) {
+        if (NodeLimitReached(max_nodes, info)) break;
+        Node node = std::move(stack.back());
+        stack.pop_back();
+        const int64_t index = info.nodes++;
+        cols.clear(); clo.clear(); cub.clear();
+        const int K = DiffBounds(node, root_lo, root_ub, cur_lo, cur_ub, nb_lo, nb_ub, cols, clo, cub);
+        lpx_node_record rec;
+        // with CUTOFF the loop stops where this node would be pruned by bound anyway; search_flags = 0 stays the old call, messages included
+        const double cutoff = (search_flags & LPX_BDUAL_CUTOFF) ? best + EPS : 0.0;
+        const int rc = node_form > LPX_NODE_LAUNCHES      // LPX_NODE_LAUNCHES (and -1) stay the old calls, messages included
+            ? lpx_bounded_node3(ses.h, K, cols.data(), clo.data(), cub.data(), &o, LPX_BDUAL_SKIP_FIXED | search_flags, cutoff,
+                                n, mask, EPS, node_form, &rec)
+            : search_flags == 0
+            ? lpx_bounded_node(ses.h, K, cols.data(), clo.data(), cub.data(), &o, n, mask, EPS, &rec)
+            : lpx_bounded_node2(ses.h, K, cols.data(), clo.data(), cub.data(), &o, LPX_BDUAL_SKIP_FIXED | search_flags, cutoff,
+                                n, mask, EPS, &rec);
+        if (rc < 0) throw_lib(rc);
+        cur_lo = nb_lo; cur_ub = nb_ub;
+        if (LogNode(info, index, node.depth, K, rec, o.max_iter)) break;
+        if (rec.status == LPX_INFEASIBLE) { info.pruned_infeasible++; continue; }
+        const double z = rec.pick.z;
+        if (rec.status == LPX_CUTOFF || z <= best + EPS) { info.pruned_bound++; continue; }     // :182
+        if (rec.pick.var < 0) { TakeIncumbent(ses.h, n, is_int, z, best, best_x, info); continue; }      // :189-195
+        const int v = rec.pick.var;
+        Node fl{node.depth + 1, node.path}, ce{node.depth + 1, node.path};
+        fl.path.push_back(Override{v, nb_lo[v], std::floor(rec.pick.x_var)});
+        ce.path.push_back(Override{v, std::ceil(rec.pick.x_var), nb_ub[v]});
+        stack.push_back(std::move(fl));
+        stack.push_back(std::move(ce));                                             // explored first (:256)
+    }
+
+    return FinishBnbResult(std::move(res), info, ses, n, best, best_x);
 }
 
 // The search by W divers (lpx_solve_bnb_bounded4, include/lpx.h): W handles in the state of the solved root, each with its own
@@ -181,58 +277,18 @@ SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double
     if (strong && (strong->cand_max < 1 || strong->cand_max > 32)) throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: cand_max is outside [1, 32]");
     if (strong && strong->probe_iter < 0) throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: probe_iter is negative");
     const int n = original.NumVars();
-    if ((!lower.empty() && (int)lower.size() != n) || (!upper.empty() && (int)upper.size() != n))
-        throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: lower / upper need one entry per variable");
-    if (!is_int.empty() && (int)is_int.size() != n)
-        throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: the integer mask needs one entry per variable");
-    for (int j = 0; j < n; ++j)
-        CheckVarBounds("x" + std::to_string(j + 1), lower.empty() ? 0.0 : lower[j], upper.empty() ? 1.0 / 0.0 : upper[j]);
-    for (int j = 0; j < n; ++j) {
-        if (!is_int.empty() && !is_int[j]) continue;
-        const double l = lower.empty() ? 0.0 : lower[j], u = upper.empty() ? 1.0 / 0.0 : upper[j];
-        if (!std::isfinite(u) || std::floor(l) != l || std::floor(u) != u)
-            throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: integer variable x" + std::to_string(j + 1) +
-                                           " needs finite, integral lower and upper bounds");
-    }
-    if (max_nodes < 0) throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: max_nodes is negative");
-    if (search_flags & ~(LPX_BDUAL_LONG_STEP | LPX_BDUAL_CUTOFF))
-        throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: search_flags holds a bit other than LPX_BDUAL_LONG_STEP and LPX_BDUAL_CUTOFF");
+    ValidateBnbBounded(n, lower, upper, is_int, max_nodes, search_flags);
     if (divers < 1 || divers > 1024) throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: divers is outside [1, 1024]");
 
-    EngineOptions ropt = opt; ropt.quiet = true;
     BoundedSession ses;
     BoundedInfo binfo;
-    SimplexResult res = SolveBounded(original, lower, upper, ropt, nullptr, &binfo, &ses);
-    info = BnbBoundedInfo();
-    dinfo = BnbDiversInfo();
-    info.constant = ses.constant;
-    res.Nodes = 0; res.LpSolves = 1;
-    res.Aux = {0.0, 0.0, 0.0, 0.0};
-    if (res.Status != LPX_OPTIMAL) return res;
-    {
-        int R = 0, C = 0;
-        lpx_tableau_shape(ses.h, &R, &C, nullptr);
-        if (!lpx_bounded_node_fits(R, C))
-            throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: the root tableau (" + std::to_string(R) + " x " + std::to_string(C) +
-                                           ") does not fit the on-chip form of the node (lpx_bounded_node_fits)");
-    }
+    SimplexResult res;
+    if (!SolveRoot(original, lower, upper, opt, true, ses, binfo, res, info, &dinfo)) return res;
 
-    // diver 0 is the root's handle; the others are copies of it.  The guard hands the copies and the batch back on every way out.
     const int W = divers;
-    struct Pool {
-        std::vector<lpx_tableau*> h; lpx_node_batch* batch = nullptr;
-        ~Pool() { lpx_node_batch_destroy(batch); for (size_t d = 1; d < h.size(); ++d) lpx_tableau_destroy(h[d]); }
-    } pool;
-    pool.h.push_back(ses.h);
-    for (int d = 1; d < W; ++d) {
-        lpx_tableau* c = nullptr;
-        const int rc = lpx_tableau_clone(ses.h, &c);
-        if (rc) throw_lib(rc);
-        pool.h.push_back(c);
-    }
-    { const int rc = lpx_node_batch_create(W, pool.h.data(), &pool.batch); if (rc) throw_lib(rc); }
+    Pool pool;
+    pool.open(ses.h, W);
 
-    struct Diver { std::vector<double> cur_lo, cur_ub, nb_lo, nb_ub; std::vector<Node> stack; Node node; };
     const std::vector<double> root_lo((size_t)n, 0.0), root_ub(binfo.ub.begin(), binfo.ub.begin() + n);
     std::vector<Diver> dv((size_t)W);
     for (Diver& d : dv) { d.cur_lo = root_lo; d.cur_ub = root_ub; }
@@ -255,25 +311,11 @@ SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double
     auto dead = [](const lpx_probe_record& q, double best_now) {
         return q.status == LPX_INFEASIBLE || q.status == LPX_CUTOFF || (q.status == LPX_OPTIMAL && q.z <= best_now + EPS);
     };
-    auto any_open = [&] { for (const Diver& d : dv) if (!d.stack.empty()) return true; return false; };
     bool stop = false;
-    while (!stop && any_open()) {
-        // 1. limit
-        if (max_nodes > 0 && info.nodes >= max_nodes) {
-            info.limit_rc = LPX_ITER_LIMIT;
-            info.limit_msg = "Bounded Branch and Bound: node limit of " + std::to_string(max_nodes) + " reached";
-            break;
-        }
-        // 2. steal: the oldest entry of the longest stack, lengths as they stand now
-        for (int d = 0; d < W; ++d) {
-            if (!dv[d].stack.empty()) continue;
-            int v = 0;
-            for (int k = 1; k < W; ++k) if (dv[k].stack.size() > dv[v].stack.size()) v = k;
-            if (dv[v].stack.size() < 2) continue;
-            dv[d].stack.push_back(std::move(dv[v].stack.front()));
-            dv[v].stack.erase(dv[v].stack.begin());
-            dinfo.steals++;
-        }
+    while (!stop && AnyOpen(dv)) {
+        // 1. limit, 2. steal
+        if (NodeLimitReached(max_nodes, info)) break;
+        StealForIdle(dv, dinfo);
         // 3. pop
         slot.clear(); Ks.clear(); cols.clear(); clo.clear(); cub.clear(); cutoffs.clear();
         for (int d = 0; d < W; ++d) {
@@ -282,11 +324,7 @@ SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double
             if (max_nodes > 0 && info.nodes + (int64_t)slot.size() >= max_nodes) break;
             D.node = std::move(D.stack.back());
             D.stack.pop_back();
-            D.nb_lo = root_lo; D.nb_ub = root_ub;
-            for (const Override& v : D.node.path) { D.nb_lo[v.var] = v.lo; D.nb_ub[v.var] = v.ub; }
-            int K = 0;
-            for (int j = 0; j < n; ++j)
-                if (D.nb_lo[j] != D.cur_lo[j] || D.nb_ub[j] != D.cur_ub[j]) { cols.push_back(j); clo.push_back(D.nb_lo[j]); cub.push_back(D.nb_ub[j]); ++K; }
+            const int K = DiffBounds(D.node, root_lo, root_ub, D.cur_lo, D.cur_ub, D.nb_lo, D.nb_ub, cols, clo, cub);
             slot.push_back(d); Ks.push_back(K);
             cutoffs.push_back((search_flags & LPX_BDUAL_CUTOFF) ? best + EPS : 0.0);
         }
@@ -326,36 +364,17 @@ SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double
             const Node& node = D.node;
             const int64_t index = info.nodes++;
             D.cur_lo = D.nb_lo; D.cur_ub = D.nb_ub;
-            info.events += rec.events; info.flips += rec.flips;
-            if (Ks[i] > info.max_K) info.max_K = Ks[i];
-            lpx_bnb_node_log lg;
-            lg.depth = node.depth; lg.K = Ks[i]; lg.status = rec.status; lg.events = rec.events; lg.flips = (int32_t)rec.flips;
-            lg.var = rec.pick.var; lg.z = rec.pick.z;
-            info.log.push_back(lg);
+            const bool limit = LogNode(info, index, node.depth, Ks[i], rec, o.max_iter);
             dinfo.round.push_back(round); dinfo.diver.push_back(slot[i]);
             if (guarded) {
                 if (guards[i].bland_events > 0) { gi.guarded_nodes++; gi.bland_events += guards[i].bland_events; }
                 if (rec.events > gi.max_events) gi.max_events = rec.events;
             }
-            if (rec.status == LPX_ITER_LIMIT) {
-                info.limit_rc = LPX_ITER_LIMIT;
-                info.limit_msg = "Bounded Branch and Bound: node " + std::to_string(index) + " (depth " + std::to_string(node.depth) +
-                                 ") reached the iteration limit of " + std::to_string(o.max_iter) + " events";
-                stop = true;
-                break;
-            }
+            if (limit) { stop = true; break; }
             if (rec.status == LPX_INFEASIBLE) { info.pruned_infeasible++; continue; }
             const double z = rec.pick.z;
             if (rec.status == LPX_CUTOFF || z <= best + EPS) { info.pruned_bound++; continue; }
-            if (rec.pick.var < 0) {
-                std::vector<double> x((size_t)n, 0.0);
-                const int rs = lpx_tableau_bounded_solution(pool.h[slot[i]], n, x.data(), nullptr, nullptr);
-                if (rs) throw_lib(rs);
-                for (int j = 0; j < n; ++j) if (is_int.empty() || is_int[j]) x[j] = std::nearbyint(x[j]);
-                best = z; best_x = std::move(x);
-                info.incumbents++;
-                continue;
-            }
+            if (rec.pick.var < 0) { TakeIncumbent(pool.h[slot[i]], n, is_int, z, best, best_x, info); continue; }
             int v = rec.pick.var;
             double xv = rec.pick.x_var;
             bool push_fl = true, push_ce = true;
@@ -381,90 +400,31 @@ SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double
         }
     }
 
-    res.Nodes = info.nodes; res.LpSolves = info.nodes + 1;
-    res.Aux = {(double)info.nodes, (double)info.events, (double)info.flips, (double)info.incumbents};
-    res.Trace.clear();
-    if (best_x.empty()) {
-        res.Status = LPX_INFEASIBLE; res.HasSolution = false; res.OptimalValue = 0.0;
-        res.Solution.assign((size_t)n, 0.0);
-        res.Summary = "INFEASIBLE\n"; res.Report = res.Summary;
-        return res;
-    }
-    if (!ses.lower.empty()) for (int j = 0; j < n; ++j) best_x[j] = best_x[j] + ses.lower[j];
-    double value = ses.min ? -best : best;
-    if (ses.shifted) value = value + ses.constant;
-    res.Status = LPX_OPTIMAL; res.HasSolution = true; res.OptimalValue = value; res.Solution = best_x;
-    std::string report;
-    FinalizeText(report, res.Summary, best_x, value, LPX_OPTIMAL);
-    const std::string tail = "  nodes: " + std::to_string(info.nodes) + ", dual events: " + std::to_string(info.events) +
-                             ", dual-feasibility flips: " + std::to_string(info.flips) + "\n";
-    res.Report = report + tail; res.Summary += tail.substr(2);
-    return res;
+    return FinishBnbResult(std::move(res), info, ses, n, best, best_x);
 }
 
 // The search by W divers that plunge (lpx_solve_bnb_bounded5, include/lpx.h): SolveBnbDivers whose round is ONE
 // lpx_node_batch_plunge -- every diver's workgroup goes on from a node that branches into its ceil child, up to `plunge` nodes,
-// with the tableau staying on chip -- and whose decide step walks every diver's chain in order.  The validation and the result
-// tail are copies of SolveBnbDivers' (as that function's are of SolveBnbBounded's), so that the two existing drivers stay as they
-// are.  The order of the steps is part of the contract: the log is a function of the model, the options, the flags, W and D alone.
+// with the tableau staying on chip -- and whose decide step walks every diver's chain in order.  The order of the steps is part
+// of the contract: the log is a function of the model, the options, the flags, W and D alone.
 SimplexResult SolveBnbPlunge(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
                              int search_flags, int divers, int plunge, BnbDiversInfo& dinfo, BnbPlungeInfo& pinfo)
 {
     const int n = original.NumVars();
-    if ((!lower.empty() && (int)lower.size() != n) || (!upper.empty() && (int)upper.size() != n))
-        throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: lower / upper need one entry per variable");
-    if (!is_int.empty() && (int)is_int.size() != n)
-        throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: the integer mask needs one entry per variable");
-    for (int j = 0; j < n; ++j)
-        CheckVarBounds("x" + std::to_string(j + 1), lower.empty() ? 0.0 : lower[j], upper.empty() ? 1.0 / 0.0 : upper[j]);
-    for (int j = 0; j < n; ++j) {
-        if (!is_int.empty() && !is_int[j]) continue;
-        const double l = lower.empty() ? 0.0 : lower[j], u = upper.empty() ? 1.0 / 0.0 : upper[j];
-        if (!std::isfinite(u) || std::floor(l) != l || std::floor(u) != u)
-            throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: integer variable x" + std::to_string(j + 1) +
-                                           " needs finite, integral lower and upper bounds");
-    }
-    if (max_nodes < 0) throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: max_nodes is negative");
-    if (search_flags & ~(LPX_BDUAL_LONG_STEP | LPX_BDUAL_CUTOFF))
-        throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: search_flags holds a bit other than LPX_BDUAL_LONG_STEP and LPX_BDUAL_CUTOFF");
+    ValidateBnbBounded(n, lower, upper, is_int, max_nodes, search_flags);
     if (divers < 1 || divers > 1024) throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: divers is outside [1, 1024]");
     if (plunge < 1 || plunge > 64) throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: plunge is outside [1, 64]");
 
-    EngineOptions ropt = opt; ropt.quiet = true;
     BoundedSession ses;
     BoundedInfo binfo;
-    SimplexResult res = SolveBounded(original, lower, upper, ropt, nullptr, &binfo, &ses);
-    info = BnbBoundedInfo();
-    dinfo = BnbDiversInfo();
-    pinfo = BnbPlungeInfo();
-    info.constant = ses.constant;
-    res.Nodes = 0; res.LpSolves = 1;
-    res.Aux = {0.0, 0.0, 0.0, 0.0};
-    if (res.Status != LPX_OPTIMAL) return res;
-    {
-        int R = 0, C = 0;
-        lpx_tableau_shape(ses.h, &R, &C, nullptr);
-        if (!lpx_bounded_node_fits(R, C))
-            throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: the root tableau (" + std::to_string(R) + " x " + std::to_string(C) +
-                                           ") does not fit the on-chip form of the node (lpx_bounded_node_fits)");
-    }
+    SimplexResult res;
+    if (!SolveRoot(original, lower, upper, opt, true, ses, binfo, res, info, &dinfo, &pinfo)) return res;
 
     const int W = divers, D = plunge;
-    struct Pool {
-        std::vector<lpx_tableau*> h; lpx_node_batch* batch = nullptr;
-        ~Pool() { lpx_node_batch_destroy(batch); for (size_t d = 1; d < h.size(); ++d) lpx_tableau_destroy(h[d]); }
-    } pool;
-    pool.h.push_back(ses.h);
-    for (int d = 1; d < W; ++d) {
-        lpx_tableau* c = nullptr;
-        const int rc = lpx_tableau_clone(ses.h, &c);
-        if (rc) throw_lib(rc);
-        pool.h.push_back(c);
-    }
-    { const int rc = lpx_node_batch_create(W, pool.h.data(), &pool.batch); if (rc) throw_lib(rc); }
+    Pool pool;
+    pool.open(ses.h, W);
 
-    struct Diver { std::vector<double> cur_lo, cur_ub, nb_lo, nb_ub; std::vector<Node> stack; Node node; };
     const std::vector<double> root_lo((size_t)n, 0.0), root_ub(binfo.ub.begin(), binfo.ub.begin() + n);
     std::vector<Diver> dv((size_t)W);
     for (Diver& d : dv) { d.cur_lo = root_lo; d.cur_ub = root_ub; }
@@ -477,25 +437,11 @@ SimplexResult SolveBnbPlunge(const LPProblem& original, const std::vector<double
     std::vector<double> best_x;
     std::vector<int32_t> slot, Ks, caps, cols, rcs((size_t)W), steps((size_t)W); std::vector<double> clo, cub, cutoffs, prunes;
     std::vector<lpx_node_record> recs((size_t)W * (size_t)D);
-    auto any_open = [&] { for (const Diver& d : dv) if (!d.stack.empty()) return true; return false; };
     bool stop = false;
-    while (!stop && any_open()) {
-        // 1. limit
-        if (max_nodes > 0 && info.nodes >= max_nodes) {
-            info.limit_rc = LPX_ITER_LIMIT;
-            info.limit_msg = "Bounded Branch and Bound: node limit of " + std::to_string(max_nodes) + " reached";
-            break;
-        }
-        // 2. steal: the oldest entry of the longest stack, lengths as they stand now
-        for (int d = 0; d < W; ++d) {
-            if (!dv[d].stack.empty()) continue;
-            int v = 0;
-            for (int k = 1; k < W; ++k) if (dv[k].stack.size() > dv[v].stack.size()) v = k;
-            if (dv[v].stack.size() < 2) continue;
-            dv[d].stack.push_back(std::move(dv[v].stack.front()));
-            dv[v].stack.erase(dv[v].stack.begin());
-            dinfo.steals++;
-        }
+    while (!stop && AnyOpen(dv)) {
+        // 1. limit, 2. steal
+        if (NodeLimitReached(max_nodes, info)) break;
+        StealForIdle(dv, dinfo);
         // 3. pop, each entry with its cap on nodes: plunge, or what max_nodes leaves after the caps handed out before it
         slot.clear(); Ks.clear(); caps.clear(); cols.clear(); clo.clear(); cub.clear(); cutoffs.clear(); prunes.clear();
         int64_t handed = 0;
@@ -511,11 +457,7 @@ SimplexResult SolveBnbPlunge(const LPProblem& original, const std::vector<double
             handed += cap;
             Dv.node = std::move(Dv.stack.back());
             Dv.stack.pop_back();
-            Dv.nb_lo = root_lo; Dv.nb_ub = root_ub;
-            for (const Override& v : Dv.node.path) { Dv.nb_lo[v.var] = v.lo; Dv.nb_ub[v.var] = v.ub; }
-            int K = 0;
-            for (int j = 0; j < n; ++j)
-                if (Dv.nb_lo[j] != Dv.cur_lo[j] || Dv.nb_ub[j] != Dv.cur_ub[j]) { cols.push_back(j); clo.push_back(Dv.nb_lo[j]); cub.push_back(Dv.nb_ub[j]); ++K; }
+            const int K = DiffBounds(Dv.node, root_lo, root_ub, Dv.cur_lo, Dv.cur_ub, Dv.nb_lo, Dv.nb_ub, cols, clo, cub);
             slot.push_back(d); Ks.push_back(K); caps.push_back(cap);
             cutoffs.push_back((search_flags & LPX_BDUAL_CUTOFF) ? best + EPS : 0.0);
             prunes.push_back(best + EPS);
@@ -540,20 +482,9 @@ SimplexResult SolveBnbPlunge(const LPProblem& original, const std::vector<double
                 const int K = s == 0 ? Ks[i] : 1;
                 const bool has_next = s + 1 < ns;
                 const int64_t index = info.nodes++;
-                info.events += rec.events; info.flips += rec.flips;
-                if (K > info.max_K) info.max_K = K;
-                lpx_bnb_node_log lg;
-                lg.depth = node.depth; lg.K = K; lg.status = rec.status; lg.events = rec.events; lg.flips = (int32_t)rec.flips;
-                lg.var = rec.pick.var; lg.z = rec.pick.z;
-                info.log.push_back(lg);
+                const bool limit = LogNode(info, index, node.depth, K, rec, o.max_iter);
                 dinfo.round.push_back(round); dinfo.diver.push_back(slot[i]); pinfo.step.push_back(s);
-                if (rec.status == LPX_ITER_LIMIT) {
-                    info.limit_rc = LPX_ITER_LIMIT;
-                    info.limit_msg = "Bounded Branch and Bound: node " + std::to_string(index) + " (depth " + std::to_string(node.depth) +
-                                     ") reached the iteration limit of " + std::to_string(o.max_iter) + " events";
-                    stop = true;
-                    break;
-                }
+                if (limit) { stop = true; break; }
                 if (rec.status == LPX_INFEASIBLE) { info.pruned_infeasible++; break; }
                 const double z = rec.pick.z;
                 if (rec.status == LPX_CUTOFF || z <= best + EPS) {
@@ -567,12 +498,7 @@ SimplexResult SolveBnbPlunge(const LPProblem& original, const std::vector<double
                     break;
                 }
                 if (rec.pick.var < 0) {                                  // always the last record of its chain: the handle holds its x
-                    std::vector<double> x((size_t)n, 0.0);
-                    const int rs = lpx_tableau_bounded_solution(pool.h[slot[i]], n, x.data(), nullptr, nullptr);
-                    if (rs) throw_lib(rs);
-                    for (int j = 0; j < n; ++j) if (is_int.empty() || is_int[j]) x[j] = std::nearbyint(x[j]);
-                    best = z; best_x = std::move(x);
-                    info.incumbents++;
+                    TakeIncumbent(pool.h[slot[i]], n, is_int, z, best, best_x, info);
                     break;
                 }
                 const int v = rec.pick.var;
@@ -587,25 +513,7 @@ SimplexResult SolveBnbPlunge(const LPProblem& original, const std::vector<double
         }
     }
 
-    res.Nodes = info.nodes; res.LpSolves = info.nodes + 1;
-    res.Aux = {(double)info.nodes, (double)info.events, (double)info.flips, (double)info.incumbents};
-    res.Trace.clear();
-    if (best_x.empty()) {
-        res.Status = LPX_INFEASIBLE; res.HasSolution = false; res.OptimalValue = 0.0;
-        res.Solution.assign((size_t)n, 0.0);
-        res.Summary = "INFEASIBLE\n"; res.Report = res.Summary;
-        return res;
-    }
-    if (!ses.lower.empty()) for (int j = 0; j < n; ++j) best_x[j] = best_x[j] + ses.lower[j];
-    double value = ses.min ? -best : best;
-    if (ses.shifted) value = value + ses.constant;
-    res.Status = LPX_OPTIMAL; res.HasSolution = true; res.OptimalValue = value; res.Solution = best_x;
-    std::string report;
-    FinalizeText(report, res.Summary, best_x, value, LPX_OPTIMAL);
-    const std::string tail = "  nodes: " + std::to_string(info.nodes) + ", dual events: " + std::to_string(info.events) +
-                             ", dual-feasibility flips: " + std::to_string(info.flips) + "\n";
-    res.Report = report + tail; res.Summary += tail.substr(2);
-    return res;
+    return FinishBnbResult(std::move(res), info, ses, n, best, best_x);
 }
 
 }}  // namespace lpx::host

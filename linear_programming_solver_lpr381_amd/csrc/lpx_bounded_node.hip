@@ -24,13 +24,10 @@
 //                       list of the dual-feasibility flips (int32); the values of the pick.  The leaving row needs no array.
 // basis, flip, lo, the trace and the state record stay in global memory (a gather or lane 0's few words per event); the
 // normalised pivot row is row r of the tile itself, which the update leaves alone.
-#include "lpx_bounded.h"       // bnd_complement; through lpx_resident.h rs_hysteresis, through lpx_block.h the reductions
+#define LPX_ONCHIP_GUARD 0
+#include "lpx_onchip.h"        // the launch constants, the refusal record; through lpx_bounded.h the shared device pieces
 
 namespace lpx {
-
-static constexpr int ND_NT = SEL_NT, ND_NW = SEL_NW;
-static constexpr size_t ND_LDS_TOTAL = 160 * 1024;      // one compute unit
-static constexpr size_t ND_LDS_STATIC = 2048;           // reserved for the statics of the kernel (reduction scratch, counters)
 
 size_t bounded_node_lds_bytes(int R, int C)
 {
@@ -41,21 +38,13 @@ size_t bounded_node_lds_bytes(int R, int C)
 int bounded_node_fits(int R, int C)
 {
     if (R < 2 || C < 1) return 0;
-    return bounded_node_lds_bytes(R, C) <= ND_LDS_TOTAL - ND_LDS_STATIC ? 1 : 0;
+    return bounded_node_lds_bytes(R, C) <= OC_LDS_MAX ? 1 : 0;
 }
 
-__device__ __forceinline__ void nd_refuse(const NodeParams& N, int t, int flips, int bad, int inf_k)
-{
-    if (t == 0) {
-        NodeOut* o = N.out;
-        o->status = -1; o->events = 0; o->kind0 = 0; o->kind1 = 0; o->flips = flips; o->unrepairable = bad; o->inf_k = inf_k;
-        o->var = -1; o->candidates = 0; o->x_var = 0.0; o->z = 0.0;
-    }
-}
-
-// One node on one workgroup.  The body is lpx_bounded_node_body.h, the text of both kernels (the reason is in that file): N is
-// uniform over the workgroup, and every `return` of the body is taken by all of its lanes.
-__global__ __launch_bounds__(ND_NT) void lpx_bounded_node_onchip(NodeParams N)
+// One node on one workgroup.  The body is lpx_bounded_node_body.h, the text of these two kernels and of the guarded one (the reason
+// is in that file): N is uniform over the workgroup, and every `return` of the body is taken by all of its lanes.  The stall guard
+// is off in this file; lpx_bounded_guard.hip has it on.
+__global__ __launch_bounds__(OC_NT) void lpx_bounded_node_onchip(NodeParams N)
 {
 #include "lpx_bounded_node_body.h"
 }
@@ -64,7 +53,7 @@ __global__ __launch_bounds__(ND_NT) void lpx_bounded_node_onchip(NodeParams N)
 // nothing: no wait, no flag, no atomic between them, each writes its own handle's memory and its own records only, so the result
 // of an entry does not depend on B, on its place in the grid or on how many workgroups run at once, and a refused entry's early
 // return holds nobody up.  P[b] (pinned host memory) is read once through a wave-uniform address into scalar registers.
-__global__ __launch_bounds__(ND_NT) void lpx_bounded_nodes_onchip(const NodeParams* __restrict__ P)
+__global__ __launch_bounds__(OC_NT) void lpx_bounded_nodes_onchip(const NodeParams* __restrict__ P)
 {
     const NodeParams N = P[blockIdx.x];
 #include "lpx_bounded_node_body.h"
@@ -72,24 +61,22 @@ __global__ __launch_bounds__(ND_NT) void lpx_bounded_nodes_onchip(const NodePara
 
 hipError_t bounded_node_init()
 {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lpx_bounded_node_onchip), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)(ND_LDS_TOTAL - ND_LDS_STATIC));
+    hipError_t e = oc_allow_lds(reinterpret_cast<const void*>(lpx_bounded_node_onchip));
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(lpx_bounded_nodes_onchip), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(ND_LDS_TOTAL - ND_LDS_STATIC));
+    return oc_allow_lds(reinterpret_cast<const void*>(lpx_bounded_nodes_onchip));
 }
 
 hipError_t launch_bounded_node_onchip(const NodeParams& n, hipStream_t s)
 {
     if (!bounded_node_fits(n.R, n.C)) return hipErrorInvalidValue;      // never launched beyond the LDS of one compute unit
-    hipLaunchKernelGGL(lpx_bounded_node_onchip, dim3(1), dim3(ND_NT), bounded_node_lds_bytes(n.R, n.C), s, n);
+    hipLaunchKernelGGL(lpx_bounded_node_onchip, dim3(1), dim3(OC_NT), bounded_node_lds_bytes(n.R, n.C), s, n);
     return hipGetLastError();
 }
 
 hipError_t launch_bounded_nodes_onchip(const NodeParams* P, int B, size_t lds, hipStream_t s)
 {
-    if (B < 1 || lds > ND_LDS_TOTAL - ND_LDS_STATIC) return hipErrorInvalidValue;       // the caller checks the fit of every entry
-    hipLaunchKernelGGL(lpx_bounded_nodes_onchip, dim3(B), dim3(ND_NT), lds, s, P);
+    if (B < 1 || lds > OC_LDS_MAX) return hipErrorInvalidValue;         // the caller checks the fit of every entry
+    hipLaunchKernelGGL(lpx_bounded_nodes_onchip, dim3(B), dim3(OC_NT), lds, s, P);
     return hipGetLastError();
 }
 

@@ -13,15 +13,14 @@
 //
 // The arithmetic of the child is that of lpx_bounded_node_body.h with K = 1 (the edit, the dual-feasibility flips, the dual loop
 // with the long-step passes and the cutoff where flagged), operation for operation, so that a record is bit-equal to
-// lpx_bounded_node3(..., LPX_NODE_ONCHIP) on a clone of the handle.  It has its own text because the node's text writes its handle.
-// The candidates use the arithmetic of the branch pick (lpx_branch_pick_kernel).  Dynamic LDS: that of the node
-// (bounded_node_lds_bytes): tile [R * S], ub [C], buf [max(R, C)].
-#include "lpx_bounded.h"       // bnd_complement; through lpx_resident.h rs_hysteresis, through lpx_block.h the reductions
+// lpx_bounded_node3(..., LPX_NODE_ONCHIP) on a clone of the handle.  Steps 2b, 5 and 6 ARE the node's text, the step files of
+// lpx_onchip.h: `basis` and `flip` name this workgroup's slice of the workspace there, no trace is kept and nothing is stored back.
+// The candidate passes, the child's edit and the record are this kernel's own; the candidates use the arithmetic of the branch pick
+// (lpx_branch_pick_kernel).  Dynamic LDS: that of the node (bounded_node_lds_bytes): tile [R * S], ub [C], buf [max(R, C)].
+#define LPX_ONCHIP_GUARD 0
+#include "lpx_onchip.h"        // the launch constants; through lpx_bounded.h the shared device pieces
 
 namespace lpx {
-
-static constexpr int PB_NT = SEL_NT, PB_NW = SEL_NW;
-static constexpr size_t PB_LDS_TOTAL = 160 * 1024, PB_LDS_STATIC = 2048;     // as the node: one compute unit, the statics reserved
 
 __device__ __forceinline__ void pb_record(lpx_probe_record* o, int status, int events, int k0, int k1, int flips, int var, int dir,
                                           double x_var, double lower, double upper, double z)
@@ -30,15 +29,19 @@ __device__ __forceinline__ void pb_record(lpx_probe_record* o, int status, int e
     o->x_var = x_var; o->lower = lower; o->upper = upper; o->z = z;
 }
 
-__global__ __launch_bounds__(PB_NT) void lpx_bounded_probe_onchip(const ProbeParams* __restrict__ P)
+__global__ __launch_bounds__(OC_NT) void lpx_bounded_probe_onchip(const ProbeParams* __restrict__ P)
 {
+    constexpr int stall_events = 0;                     // no stall guard here yet: this line and the file's switch are all of it
+    constexpr int trace_cap = INT_MIN;                              // no trace is kept: no event count lies below it, so the test folds away
+    int32_t* const trace = nullptr;
+    [[maybe_unused]] bool dirty = false;                            // nothing goes back to the handle
     const ProbeParams N = P[blockIdx.y];
     extern __shared__ double pb_lds[];
-    __shared__ double s_v[PB_NW];
-    __shared__ int s_i[PB_NW];
+    __shared__ double s_v[OC_NW];
+    __shared__ int s_i[OC_NW];
     __shared__ int s_out;
-    __shared__ int s_tot[PB_NW];
-    __shared__ int s_bad[PB_NW];
+    __shared__ int s_tot[OC_NW];
+    __shared__ int s_bad[OC_NW];
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int w = blockIdx.x;
@@ -68,9 +71,9 @@ __global__ __launch_bounds__(PB_NT) void lpx_bounded_probe_onchip(const ProbePar
     uint8_t* flip = N.wflip + (size_t)w * N.wflip_stride;
 
     // ---- 2. load: ub and the live window into LDS, basis and flip into the slice
-    for (int j = t; j < Cm; j += PB_NT) { ub_s[j] = N.ub[j]; flip[j] = N.flip[j]; }
-    for (int i = t; i < m; i += PB_NT) basis[i] = N.basis[i];
-    for (int i = wave; i < R; i += PB_NW) {
+    for (int j = t; j < Cm; j += OC_NT) { ub_s[j] = N.ub[j]; flip[j] = N.flip[j]; }
+    for (int i = t; i < m; i += OC_NT) basis[i] = N.basis[i];
+    for (int i = wave; i < R; i += OC_NW) {
         const double* src = N.T + (size_t)i * ld;
         double* dst = tile + (size_t)i * S;
         for (int j = lane; j < C; j += 64) dst[j] = src[j];
@@ -85,9 +88,9 @@ __global__ __launch_bounds__(PB_NT) void lpx_bounded_probe_onchip(const ProbePar
     {
         double* vals = buf;
         const bool masked = N.has_mask && nint > 0;
-        for (int j = t; j < nint; j += PB_NT) vals[j] = 0.0;
+        for (int j = t; j < nint; j += OC_NT) vals[j] = 0.0;
         __syncthreads();
-        for (int i = t; i < m; i += PB_NT) {
+        for (int i = t; i < m; i += OC_NT) {
             const int pb = basis[i];
             if ((unsigned)pb < (unsigned)nint) vals[pb] = tile[(size_t)i * S + Cm];
         }
@@ -96,7 +99,7 @@ __global__ __launch_bounds__(PB_NT) void lpx_bounded_probe_onchip(const ProbePar
         for (int pass = 0; pass <= c; ++pass) {                      // c < cand_max <= 32
             MinIdx best; best.v = inf; best.i = INT_MAX;
             int nc = 0;
-            for (int j = t; j < nint; j += PB_NT) {
+            for (int j = t; j < nint; j += OC_NT) {
                 if (masked && !N.mask[j]) continue;
                 const double v = vals[j];
                 double x = flip[j] ? ub_s[j] - v : v;
@@ -109,8 +112,8 @@ __global__ __launch_bounds__(PB_NT) void lpx_bounded_probe_onchip(const ProbePar
                     if (beyond && d < best.v) { best.v = d; best.i = j; }
                 }
             }
-            best = block_min_idx<PB_NT>(best, s_v, s_i);
-            if (pass == 0) block_excl_scan_sum<PB_NT>(nc, s_i, &total);
+            best = block_min_idx<OC_NT>(best, s_v, s_i);
+            if (pass == 0) block_excl_scan_sum<OC_NT>(nc, s_i, &total);
             if (best.i == INT_MAX) { var = -1; break; }             // fewer than c + 1 candidates
             var = best.i; last_d = best.v; last_j = best.i;
         }
@@ -146,23 +149,7 @@ __global__ __launch_bounds__(PB_NT) void lpx_bounded_probe_onchip(const ProbePar
     int nflips = 0;
     {
         const double* zrow = tile + (size_t)m * S;                  // the bits of the tableau's objective row
-        int n = 0, bad = 0;
-        for (int base = 0; base < Cm; base += PB_NT) {              // uniform trip count
-            const int j = base + t;
-            bool in_l = false, un = false;
-            if (j < Cm) {
-                const bool neg = zrow[j] < -eps;
-                const double u = ub_s[j];
-                in_l = neg && u > 0.0 && u < inf;
-                un = neg && u == inf;
-            }
-            n += __popcll(__ballot(in_l)); bad += __popcll(__ballot(un));
-        }
-        __syncthreads();
-        if (lane == 0) { s_tot[wave] = n; s_bad[wave] = bad; }
-        __syncthreads();
-        n = 0; bad = 0;
-        for (int k = 0; k < PB_NW; ++k) { n += s_tot[k]; bad += s_bad[k]; }
+#include "lpx_onchip_count.h"
         if (bad > 0) {                                              // refused, as the node refuses it
             if (t == 0) pb_record(o, -1, 0, 0, 0, 0, var, dir, x_var, lw, up, 0.0);
             return;
@@ -172,7 +159,7 @@ __global__ __launch_bounds__(PB_NT) void lpx_bounded_probe_onchip(const ProbePar
 
     // ---- the RHS shift of the edit: a lane per row
     if (shift != 0.0) {
-        for (int i = t; i < R; i += PB_NT) {
+        for (int i = t; i < R; i += OC_NT) {
             double* row = tile + (size_t)i * S;
             const double prod = shift * row[var];
             row[Cm] = row[Cm] - prod;
@@ -180,126 +167,10 @@ __global__ __launch_bounds__(PB_NT) void lpx_bounded_probe_onchip(const ProbePar
     }
     __syncthreads();
 
-    // ---- the dual-feasibility flips, j ascending (step 5 of the node)
-    if (nflips > 0) {
-        const double* zrow = tile + (size_t)m * S;
-        int n = 0;
-        for (int base = 0; base < Cm; base += PB_NT) {
-            const int j = base + t;
-            bool in_l = false;
-            if (j < Cm) { const double u = ub_s[j]; in_l = zrow[j] < -eps && u > 0.0 && u < inf; }
-            const unsigned long long mi = __ballot(in_l);
-            const int before = __popcll(mi & ((1ull << lane) - 1ull));
-            __syncthreads();
-            if (lane == 0) s_tot[wave] = __popcll(mi);
-            __syncthreads();
-            int pre = 0, tot = 0;
-            for (int k = 0; k < PB_NW; ++k) { const int y = s_tot[k]; if (k < wave) pre += y; tot += y; }
-            if (in_l) list[n + pre + before] = j;                   // n + pre + before < columns tested so far <= Cm
-            n += tot;
-        }
-        __syncthreads();
-        for (int k = t; k < n; k += PB_NT) flip[list[k]] ^= 1;
-        for (int i = t; i < R; i += PB_NT) {
-            double* row = tile + (size_t)i * S;
-            double b = row[Cm];
-            for (int k = 0; k < n; ++k) {
-                const int j = list[k];
-                const double a = row[j];
-                const double prod = ub_s[j] * a;
-                b = b - prod;
-                row[j] = -a;
-            }
-            row[Cm] = b;
-        }
-        __syncthreads();
-    }
-
-    // ---- 5. the dual loop (step 6 of the node): every trip ends the loop or makes at least one event
-    int iter = 0, k0 = 0, k1 = 0, status = LPX_ITER_LIMIT;
-    double* ratios = buf;
-    double* pcol = buf;
+    // ---- 5. the dual-feasibility flips and the dual loop (steps 5 and 6 of the node)
     double* zrow = tile + (size_t)m * S;
-    for (int trip = 0; trip <= max_iter; ++trip) {
-        if (iter >= max_iter) { status = LPX_ITER_LIMIT; break; }
-        if (cut && zrow[Cm] <= cutoff) { status = LPX_CUTOFF; break; }
-
-        MinIdx mn; mn.v = -eps; mn.i = INT_MAX;
-        for (int i = t; i < m; i += PB_NT) {
-            const double b = tile[(size_t)i * S + Cm];
-            const int pb = basis[i];
-            const double u = (unsigned)pb < (unsigned)Cm ? ub_s[pb] : inf;
-            double x = inf;
-            if (b < -eps) x = b;
-            else if (u < inf) x = u - b;
-            if (x < mn.v) { mn.v = x; mn.i = i; }
-        }
-        mn = block_min_idx<PB_NT>(mn, s_v, s_i);
-        if (mn.i == INT_MAX) { status = LPX_OPTIMAL; break; }
-        const int r = mn.i;
-        double* trow = tile + (size_t)r * S;
-        const int kind = trow[Cm] < -eps ? 0 : 1;
-        const int p = basis[r];
-
-        if (kind) {
-            const double upp = ub_s[p];
-            __syncthreads();                                        // every lane has read trow[Cm] before it is rewritten
-            for (int j = t; j < C; j += PB_NT) trow[j] = bnd_complement(trow[j], j, p, Cm, upp);
-            if (t == 0) flip[p] ^= 1;
-        }
-
-        for (int j = t; j < Cm; j += PB_NT) {
-            const double a = trow[j];
-            bool part = a < -eps;
-            if (skip_fixed) part = part && ub_s[j] > 0.0;
-            ratios[j] = part ? zrow[j] / (-a) : inf;
-        }
-        __syncthreads();
-
-        int q = rs_hysteresis(Cm, rtol, ratios, s_v, s_i, &s_out);
-        if (long_step) {
-            for (int pass = 0; pass < Cm && q >= 0; ++pass) {       // a column passes at most once: its ratio becomes +inf
-                const double uq = ub_s[q];
-                if (!(uq < inf)) break;
-                const double prod = uq * trow[q];
-                const double nb = trow[Cm] - prod;
-                if (!(nb < -eps)) break;
-                __syncthreads();
-                for (int i = t; i < R; i += PB_NT) {
-                    double* row = tile + (size_t)i * S;
-                    const double a = row[q];
-                    const double pr = uq * a;
-                    row[Cm] = row[Cm] - pr;
-                    row[q] = -a;
-                }
-                if (t == 0) { flip[q] ^= 1; ratios[q] = inf; }
-                ++iter;
-                __syncthreads();
-                q = rs_hysteresis(Cm, rtol, ratios, s_v, s_i, &s_out);
-            }
-        }
-        if (q < 0) { status = LPX_INFEASIBLE; break; }
-
-        const double piv = trow[q];
-        for (int i = t; i < R; i += PB_NT) pcol[i] = (i == r) ? 0.0 : tile[(size_t)i * S + q];      // the ratios are dead
-        __syncthreads();
-        for (int j = t; j < C; j += PB_NT) trow[j] = trow[j] / piv;
-        if (t == 0) basis[r] = q;
-        ++iter;
-        if (kind) ++k1; else ++k0;
-        __syncthreads();
-
-        for (int i = wave; i < R; i += PB_NW) {
-            if (i == r) continue;
-            const double f = pcol[i];
-            double* row = tile + (size_t)i * S;
-            for (int j = lane; j < C; j += 64) {
-                const double pr = f * trow[j];
-                row[j] = row[j] - pr;
-            }
-        }
-        __syncthreads();
-    }
+#include "lpx_onchip_flips.h"
+#include "lpx_onchip_dual.h"
 
     // ---- 6. the record (pinned host memory); nothing goes back to the handle
     if (t == 0) pb_record(o, status, iter, k0, k1, nflips, var, dir, x_var, lw, up, zrow[Cm]);
@@ -307,14 +178,13 @@ __global__ __launch_bounds__(PB_NT) void lpx_bounded_probe_onchip(const ProbePar
 
 hipError_t bounded_probe_init()
 {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(lpx_bounded_probe_onchip), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(PB_LDS_TOTAL - PB_LDS_STATIC));
+    return oc_allow_lds(reinterpret_cast<const void*>(lpx_bounded_probe_onchip));
 }
 
 hipError_t launch_bounded_probe_onchip(const ProbeParams* P, int B, int cand_max, size_t lds, hipStream_t s)
 {
-    if (B < 1 || cand_max < 1 || cand_max > 32 || lds > PB_LDS_TOTAL - PB_LDS_STATIC) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(lpx_bounded_probe_onchip, dim3(2 * cand_max, B), dim3(PB_NT), lds, s, P);
+    if (B < 1 || cand_max < 1 || cand_max > 32 || lds > OC_LDS_MAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lpx_bounded_probe_onchip, dim3(2 * cand_max, B), dim3(OC_NT), lds, s, P);
     return hipGetLastError();
 }
 

@@ -5,6 +5,9 @@
 // (lpx_bounded_probe.hip) enqueued behind the node launch: two launches, one wait.
 // lpx_node_batch_run2 is the same body again with the stall guard (include/lpx.h): stall_events = 0 is lpx_node_batch_run's launch, above 0
 // the one launch is lpx_bounded_guard_onchip (lpx_bounded_guard.hip), which leaves a guard record behind each node record.
+// lpx_node_batch_plunge (lpx_bounded_plunge.hip) has its own slab layout and its own walk over a chain's records; what it does as
+// the others do -- the checks of the flags and of an entry, the growth of the buffers, the mask, the header and the parameter
+// record of an entry, the message of a refusal -- are the sub-steps of the anonymous namespace, called from both.
 #include "lpx_handle.h"
 
 #include <algorithm>
@@ -49,6 +52,130 @@ int settle(hipStream_t s)
 }
 
 int settle_all(lpx_node_batch* b) { for (hipStream_t s : b->streams) { int rc = settle(s); if (rc) return rc; } return 0; }
+
+// ---- the sub-steps that node_batch_run and lpx_node_batch_plunge share; messages and the order of the checks are the callers'
+
+int check_flags_cutoff(const std::string& w, int B, int flags, const double* cutoff)
+{
+    { int r = check_long_flags(flags, 0.0, w.c_str()); if (r) return r; }
+    if (flags & LPX_BDUAL_CUTOFF) {
+        if (!cutoff) { set_error(w + ": null cutoff with LPX_BDUAL_CUTOFF"); return LPX_EINVAL; }
+        for (int i = 0; i < B; ++i) { int r = check_long_flags(flags, cutoff[i], (w + ": entry " + std::to_string(i)).c_str()); if (r) return r; }
+    }
+    return 0;
+}
+
+// the batch itself, B against its W, the default options, and a new number for this call's `seen` marks
+int begin_call(const std::string& w, lpx_node_batch* b, int B, const lpx_run_opts*& o, lpx_run_opts& d)
+{
+    if (!b) { set_error(w + ": null batch"); return LPX_EINVAL; }
+    if (B > (int)b->h.size()) { set_error(w + ": B is outside [1, W]"); return LPX_EINVAL; }
+    if (!o) { lpx_default_opts(&d, 1); o = &d; }
+    if (b->call == INT32_MAX) { std::fill(b->seen.begin(), b->seen.end(), 0); b->call = 0; }
+    ++b->call;
+    return 0;
+}
+
+// entry i names a handle once and is a valid node call on it; at: "name: entry i".  *t = the handle.
+int check_entry(lpx_node_batch* b, int slot, int k, const int32_t* cols, const double* lower, const double* upper, const lpx_run_opts* o,
+                int nint, double tol, const lpx_node_record* out, const char* at, lpx_tableau** t)
+{
+    if (slot < 0 || slot >= (int)b->h.size()) { set_error(std::string(at) + ": slot is outside [0, W)"); return LPX_EINVAL; }
+    if (b->seen[slot] == b->call) { set_error(std::string(at) + ": slot repeats a handle"); return LPX_EINVAL; }
+    b->seen[slot] = b->call;
+    *t = b->h[slot];
+    int r = check_change_args(*t, k, cols, lower, upper, at); if (r) return r;
+    r = check_pick_args(*t, nint, tol, out, at); if (r) return r;
+    r = check_node_opts(*t, o, at); if (r) return r;
+    return check_node_fits(*t, at);
+}
+
+// entry i's place in the slab and in the edit staging (for kedit triples), and its share of the launch's LDS
+void place_entry(lpx_node_batch* b, int i, const lpx_tableau* t, int k, int kedit, size_t& in_bytes, size_t& edit_bytes, size_t& lds)
+{
+    b->off_in[i] = in_bytes; b->off_edit[i] = edit_bytes;
+    in_bytes += up16(sizeof(NodeIn) + (size_t)k * (2 * sizeof(double) + sizeof(int32_t)));
+    edit_bytes += up16((size_t)kedit * (5 * sizeof(double) + sizeof(int32_t)));
+    lds = std::max(lds, bounded_node_lds_bytes(t->R, t->C));
+}
+
+// the buffers: grown to twice the need, and only when the need outgrows them
+int ensure_buffers(lpx_node_batch* b, size_t need, size_t edit_bytes, size_t ws_bytes)
+{
+    int r;
+    if (need > b->slab_bytes) {
+        r = settle_all(b); if (r) return r;
+        if (b->slab) hipHostFree(b->slab);
+        b->slab = nullptr; b->slab_bytes = 0;
+        LPX_HIP_TRY(hipHostMalloc((void**)&b->slab, 2 * need));
+        b->slab_bytes = 2 * need;
+    }
+    if (edit_bytes > b->edit_bytes) {
+        r = settle_all(b); if (r) return r;
+        hipFree(b->edit); b->edit = nullptr; b->edit_bytes = 0;
+        LPX_HIP_TRY(hipMalloc((void**)&b->edit, 2 * edit_bytes));
+        b->edit_bytes = 2 * edit_bytes;
+    }
+    if (ws_bytes > b->probews_bytes) {
+        r = settle_all(b); if (r) return r;
+        hipFree(b->probews); b->probews = nullptr; b->probews_bytes = 0;
+        LPX_HIP_TRY(hipMalloc((void**)&b->probews, 2 * ws_bytes));
+        b->probews_bytes = 2 * ws_bytes;
+    }
+    return 0;
+}
+
+// the device copy of the integer mask, sent again only when its bytes changed
+int ensure_mask(lpx_node_batch* b, hipStream_t s, const uint8_t* is_int, int nint)
+{
+    if (b->mask_n == nint && std::memcmp(b->mask_h.data(), is_int, (size_t)nint) == 0) return 0;
+    int r = settle(s); if (r) return r;                                  // an earlier copy may still read mask_h
+    if ((size_t)nint > b->mask_cap) {
+        hipFree(b->mask); b->mask = nullptr; b->mask_cap = 0;
+        LPX_HIP_TRY(hipMalloc((void**)&b->mask, 2 * (size_t)nint));
+        b->mask_cap = 2 * (size_t)nint;
+    }
+    b->mask_h.assign(is_int, is_int + nint);
+    LPX_HIP_TRY(hipMemcpyAsync(b->mask, b->mask_h.data(), (size_t)nint, hipMemcpyHostToDevice, s));
+    b->mask_n = nint;
+    return 0;
+}
+
+// entry i's header with its triples in the slab (*in) and its parameter record (*n); cutoff is 0 without LPX_BDUAL_CUTOFF, and the
+// caller sets n->out
+struct EntryOpts { const lpx_run_opts* o; int flags, nint, stall_events; bool has_mask; double tol; };
+void fill_entry(lpx_node_batch* b, int i, lpx_tableau* t, int k, const int32_t* cl, const double* lw, const double* up, double cutoff,
+                const EntryOpts& e, NodeIn* in, NodeParams* n)
+{
+    lpx_tableau::Bounds& bn = t->bnd;
+    bool any_lo = false;
+    for (int j = 0; j < k; ++j) if (lw[j] != 0.0) any_lo = true;
+    b->any_lo[i] = any_lo ? 1 : 0;
+    std::memset(in, 0, sizeof(*in));
+    in->K = k; in->flags = e.flags; in->nint = e.nint; in->has_mask = e.has_mask ? 1 : 0; in->max_iter = e.o->max_iter;
+    in->lo_used = (bn.lo_used || any_lo) ? 1 : 0;
+    in->eps = e.o->eps; in->ratio_tol = e.o->ratio_tol; in->cutoff = cutoff; in->tol = e.tol;
+    in->stall_events = e.stall_events;
+    if (k > 0) {
+        double* a = reinterpret_cast<double*>(in + 1);
+        std::memcpy(a, lw, sizeof(double) * k);
+        std::memcpy(a + k, up, sizeof(double) * k);
+        std::memcpy(a + 2 * (size_t)k, cl, sizeof(int32_t) * k);
+    }
+    std::memset(n, 0, sizeof(*n));
+    n->T = t->T; n->ld = t->ld; n->R = t->R; n->C = t->C;
+    n->rhsbuf = t->rhsbuf; n->basis = t->basis; n->trace = t->trace; n->trace_cap = t->trace_cap; n->st = t->st;
+    n->ub = bn.ub; n->lo = bn.lo; n->flip = bn.flip; n->edit = reinterpret_cast<double*>(b->edit + b->off_edit[i]); n->mask = b->mask;
+    n->in = in;
+}
+
+// the message of the first entry the kernel refused; at: "name: entry i" (the plunge: with the node inside the chain)
+void set_refusal(const std::string& at, const NodeOut* rec)
+{
+    if (rec->inf_k >= 0) set_error(at + ": upper[" + std::to_string(rec->inf_k) + "] = +inf on a flipped column");
+    else set_error(at + ": " + std::to_string(rec->unrepairable) + " column(s) with a negative reduced cost and no upper "
+                   "bound: a bound flip cannot restore dual feasibility");
+}
 
 }  // namespace
 
@@ -115,39 +242,23 @@ static int node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const i
         int r = check_probe_args(pr->cand_max, pr->probe_iter, name); if (r) return r;
     }
     if (B < 1) { set_error(w + ": B is outside [1, W]"); return LPX_EINVAL; }
-    { int r = check_long_flags(flags, 0.0, w.c_str()); if (r) return r; }
-    if (flags & LPX_BDUAL_CUTOFF) {
-        if (!cutoff) { set_error(w + ": null cutoff with LPX_BDUAL_CUTOFF"); return LPX_EINVAL; }
-        for (int i = 0; i < B; ++i) { int r = check_long_flags(flags, cutoff[i], (w + ": entry " + std::to_string(i)).c_str()); if (r) return r; }
-    }
+    { int r = check_flags_cutoff(w, B, flags, cutoff); if (r) return r; }
     if (pr)
         for (int i = 0; i < B; ++i)
             if (pr->prune[i] != pr->prune[i]) { set_error(w + ": entry " + std::to_string(i) + ": prune is NaN"); return LPX_EINVAL; }
-    if (!b) { set_error(w + ": null batch"); return LPX_EINVAL; }
-    const int W = (int)b->h.size();
-    if (B > W) { set_error(w + ": B is outside [1, W]"); return LPX_EINVAL; }
-    lpx_run_opts d; if (!o) { lpx_default_opts(&d, 1); o = &d; }
-    if (b->call == INT32_MAX) { std::fill(b->seen.begin(), b->seen.end(), 0); b->call = 0; }
-    ++b->call;
+    lpx_run_opts d;
+    { int r = begin_call(w, b, B, o, d); if (r) return r; }
     size_t sumK = 0, in_bytes = 0, edit_bytes = 0, lds = 0;
     size_t ws_bytes = 0;
     char at[56];                                                         // "lpx_node_batch_run: entry i", no allocation per entry
     for (int i = 0; i < B; ++i) {
         std::snprintf(at, sizeof at, "%s: entry %d", name, i);
-        if (slot[i] < 0 || slot[i] >= W) { set_error(std::string(at) + ": slot is outside [0, W)"); return LPX_EINVAL; }
-        if (b->seen[slot[i]] == b->call) { set_error(std::string(at) + ": slot repeats a handle"); return LPX_EINVAL; }
-        b->seen[slot[i]] = b->call;
-        lpx_tableau* t = b->h[slot[i]];
+        lpx_tableau* t = nullptr;
         const int k = K[i];
-        int r = check_change_args(t, k, cols ? cols + sumK : nullptr, lower ? lower + sumK : nullptr, upper ? upper + sumK : nullptr, at);
+        int r = check_entry(b, slot[i], k, cols ? cols + sumK : nullptr, lower ? lower + sumK : nullptr, upper ? upper + sumK : nullptr, o,
+                            nint, tol, out, at, &t);
         if (r) return r;
-        r = check_pick_args(t, nint, tol, out, at); if (r) return r;
-        r = check_node_opts(t, o, at); if (r) return r;
-        r = check_node_fits(t, at); if (r) return r;
-        b->off_in[i] = in_bytes; b->off_edit[i] = edit_bytes;
-        in_bytes += up16(sizeof(NodeIn) + (size_t)k * (2 * sizeof(double) + sizeof(int32_t)));
-        edit_bytes += up16((size_t)k * (5 * sizeof(double) + sizeof(int32_t)));
-        lds = std::max(lds, bounded_node_lds_bytes(t->R, t->C));
+        place_entry(b, i, t, k, k, in_bytes, edit_bytes, lds);
         if (pr) { b->off_ws[i] = ws_bytes; ws_bytes += probe_ws_bytes(t, pr->cand_max); }
         sumK += (size_t)k;
     }
@@ -161,68 +272,22 @@ static int node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const i
     const size_t o_out = up16(sizeof(NodeParams) * (size_t)B), o_in = o_out + kOut * (size_t)B, o_pp = up16(o_in + in_bytes),
                  o_head = o_pp + up16(sizeof(ProbeParams) * (size_t)B), o_prec = o_head + sizeof(lpx_probe_head) * (size_t)B,
                  need = pr ? o_prec + sizeof(lpx_probe_record) * nrec * (size_t)B : o_in + in_bytes;
-    if (need > b->slab_bytes) {
-        r = settle_all(b); if (r) return r;
-        if (b->slab) hipHostFree(b->slab);
-        b->slab = nullptr; b->slab_bytes = 0;
-        LPX_HIP_TRY(hipHostMalloc((void**)&b->slab, 2 * need));
-        b->slab_bytes = 2 * need;
-    }
-    if (edit_bytes > b->edit_bytes) {
-        r = settle_all(b); if (r) return r;
-        hipFree(b->edit); b->edit = nullptr; b->edit_bytes = 0;
-        LPX_HIP_TRY(hipMalloc((void**)&b->edit, 2 * edit_bytes));
-        b->edit_bytes = 2 * edit_bytes;
-    }
-    if (ws_bytes > b->probews_bytes) {
-        r = settle_all(b); if (r) return r;
-        hipFree(b->probews); b->probews = nullptr; b->probews_bytes = 0;
-        LPX_HIP_TRY(hipMalloc((void**)&b->probews, 2 * ws_bytes));
-        b->probews_bytes = 2 * ws_bytes;
-    }
+    r = ensure_buffers(b, need, edit_bytes, ws_bytes); if (r) return r;
     hipStream_t s = b->streams[0];
     const bool has_mask = is_int && nint > 0;
-    if (has_mask && !(b->mask_n == nint && std::memcmp(b->mask_h.data(), is_int, (size_t)nint) == 0)) {
-        r = settle(s); if (r) return r;                                  // an earlier copy may still read mask_h
-        if ((size_t)nint > b->mask_cap) {
-            hipFree(b->mask); b->mask = nullptr; b->mask_cap = 0;
-            LPX_HIP_TRY(hipMalloc((void**)&b->mask, 2 * (size_t)nint));
-            b->mask_cap = 2 * (size_t)nint;
-        }
-        b->mask_h.assign(is_int, is_int + nint);
-        LPX_HIP_TRY(hipMemcpyAsync(b->mask, b->mask_h.data(), (size_t)nint, hipMemcpyHostToDevice, s));
-        b->mask_n = nint;
-    }
+    if (has_mask) { r = ensure_mask(b, s, is_int, nint); if (r) return r; }
 
     // ---- 3. the slab: a parameter record, a header with its triples and a result record per entry
     NodeParams* P = reinterpret_cast<NodeParams*>(b->slab);
     sumK = 0;
+    const EntryOpts eo{o, flags, nint, stall_events, has_mask, tol};
     for (int i = 0; i < B; ++i) {
         lpx_tableau* t = b->h[slot[i]];
-        lpx_tableau::Bounds& bn = t->bnd;
         const int k = K[i];
-        const double* lw = lower + sumK; const double* up = upper + sumK; const int32_t* cl = cols + sumK;
-        bool any_lo = false;
-        for (int j = 0; j < k; ++j) if (lw[j] != 0.0) any_lo = true;
-        b->any_lo[i] = any_lo ? 1 : 0;
         NodeIn* in = reinterpret_cast<NodeIn*>(b->slab + o_in + b->off_in[i]);
-        std::memset(in, 0, sizeof(*in));
-        in->K = k; in->flags = flags; in->nint = nint; in->has_mask = has_mask ? 1 : 0; in->max_iter = o->max_iter;
-        in->lo_used = (bn.lo_used || any_lo) ? 1 : 0;
-        in->eps = o->eps; in->ratio_tol = o->ratio_tol; in->cutoff = (flags & LPX_BDUAL_CUTOFF) ? cutoff[i] : 0.0; in->tol = tol;
-        in->stall_events = stall_events;
-        if (k > 0) {
-            double* a = reinterpret_cast<double*>(in + 1);
-            std::memcpy(a, lw, sizeof(double) * k);
-            std::memcpy(a + k, up, sizeof(double) * k);
-            std::memcpy(a + 2 * (size_t)k, cl, sizeof(int32_t) * k);
-        }
         NodeParams& n = P[i];
-        std::memset(&n, 0, sizeof(n));
-        n.T = t->T; n.ld = t->ld; n.R = t->R; n.C = t->C;
-        n.rhsbuf = t->rhsbuf; n.basis = t->basis; n.trace = t->trace; n.trace_cap = t->trace_cap; n.st = t->st;
-        n.ub = bn.ub; n.lo = bn.lo; n.flip = bn.flip; n.edit = reinterpret_cast<double*>(b->edit + b->off_edit[i]); n.mask = b->mask;
-        n.in = in; n.out = reinterpret_cast<NodeOut*>(b->slab + o_out + kOut * (size_t)i);
+        fill_entry(b, i, t, k, cols + sumK, lower + sumK, upper + sumK, (flags & LPX_BDUAL_CUTOFF) ? cutoff[i] : 0.0, eo, in, &n);
+        n.out = reinterpret_cast<NodeOut*>(b->slab + o_out + kOut * (size_t)i);
         std::memset(&out[i], 0, sizeof(out[i]));
         out[i].pick.var = -1;
         if (pr)
@@ -259,12 +324,7 @@ static int node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const i
         if (rec->status < 0) {                                           // refused by the kernel: this handle is as it was
             rc[i] = LPX_EINVAL;
             out[i].unrepairable = rec->unrepairable;
-            if (!refused) {
-                const std::string at = w + ": entry " + std::to_string(i);
-                if (rec->inf_k >= 0) set_error(at + ": upper[" + std::to_string(rec->inf_k) + "] = +inf on a flipped column");
-                else set_error(at + ": " + std::to_string(rec->unrepairable) + " column(s) with a negative reduced cost and no upper "
-                               "bound: a bound flip cannot restore dual feasibility");
-            }
+            if (!refused) set_refusal(w + ": entry " + std::to_string(i), rec);
             refused = true;
             continue;
         }
@@ -299,8 +359,9 @@ int lpx_node_batch_run_probe(lpx_node_batch* b, int B, const int32_t* slot, cons
     return node_batch_run(b, B, slot, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, rc, &pr, "lpx_node_batch_run_probe");
 }
 
-// The plunge: lpx_node_batch_run's steps with a chain of up to depth[i] nodes per entry (kernel: lpx_bounded_plunge.hip).  The text
-// is a copy of lpx_node_batch_run's, not shared with it, as lpx_node_batch_run's was of the single node's: that function stays as it is.
+// The plunge: lpx_node_batch_run's steps with a chain of up to depth[i] nodes per entry (kernel: lpx_bounded_plunge.hip).  Its own:
+// the checks of depth, prune and the integrality marks, the staging for max(K, 1) triples, the PlungeParams around an entry's
+// parameter record, the D-strided records and `steps`.
 int lpx_node_batch_plunge(lpx_node_batch* b, int B, const int32_t* slot, const int32_t* K, const int32_t* cols, const double* lower,
                           const double* upper, const lpx_run_opts* o, int flags, const double* cutoff, const double* prune,
                           const int32_t* depth, int D, int nint, const uint8_t* is_int, double tol, lpx_node_record* out,
@@ -314,36 +375,23 @@ int lpx_node_batch_plunge(lpx_node_batch* b, int B, const int32_t* slot, const i
     }
     if (B < 1) { set_error(w + ": B is outside [1, W]"); return LPX_EINVAL; }
     if (D < 1 || D > 64) { set_error(w + ": D is outside [1, 64]"); return LPX_EINVAL; }
-    { int r = check_long_flags(flags, 0.0, w.c_str()); if (r) return r; }
-    if (flags & LPX_BDUAL_CUTOFF) {
-        if (!cutoff) { set_error(w + ": null cutoff with LPX_BDUAL_CUTOFF"); return LPX_EINVAL; }
-        for (int i = 0; i < B; ++i) { int r = check_long_flags(flags, cutoff[i], (w + ": entry " + std::to_string(i)).c_str()); if (r) return r; }
-    }
+    { int r = check_flags_cutoff(w, B, flags, cutoff); if (r) return r; }
     for (int i = 0; i < B; ++i) {
         const std::string at = w + ": entry " + std::to_string(i);
         if (depth[i] < 1 || depth[i] > D) { set_error(at + ": depth is outside [1, D]"); return LPX_EINVAL; }
         if (prune[i] != prune[i]) { set_error(at + ": prune is NaN"); return LPX_EINVAL; }
     }
-    if (!b) { set_error(w + ": null batch"); return LPX_EINVAL; }
-    const int W = (int)b->h.size();
-    if (B > W) { set_error(w + ": B is outside [1, W]"); return LPX_EINVAL; }
-    lpx_run_opts d; if (!o) { lpx_default_opts(&d, 1); o = &d; }
-    if (b->call == INT32_MAX) { std::fill(b->seen.begin(), b->seen.end(), 0); b->call = 0; }
-    ++b->call;
+    lpx_run_opts d;
+    { int r = begin_call(w, b, B, o, d); if (r) return r; }
     size_t sumK = 0, in_bytes = 0, edit_bytes = 0, lds = 0;
     char at[56];
     for (int i = 0; i < B; ++i) {
         std::snprintf(at, sizeof at, "lpx_node_batch_plunge: entry %d", i);
-        if (slot[i] < 0 || slot[i] >= W) { set_error(std::string(at) + ": slot is outside [0, W)"); return LPX_EINVAL; }
-        if (b->seen[slot[i]] == b->call) { set_error(std::string(at) + ": slot repeats a handle"); return LPX_EINVAL; }
-        b->seen[slot[i]] = b->call;
-        lpx_tableau* t = b->h[slot[i]];
+        lpx_tableau* t = nullptr;
         const int k = K[i];
-        int r = check_change_args(t, k, cols ? cols + sumK : nullptr, lower ? lower + sumK : nullptr, upper ? upper + sumK : nullptr, at);
+        int r = check_entry(b, slot[i], k, cols ? cols + sumK : nullptr, lower ? lower + sumK : nullptr, upper ? upper + sumK : nullptr, o,
+                            nint, tol, out, at, &t);
         if (r) return r;
-        r = check_pick_args(t, nint, tol, out, at); if (r) return r;
-        r = check_node_opts(t, o, at); if (r) return r;
-        r = check_node_fits(t, at); if (r) return r;
         if (depth[i] > 1) {
             // a chain branches on the masked-in columns: each must be known to have finite integral bounds once this entry's own
             // triples are in place, so that lo + ub is the upper bound exactly and the ceil child is the driver's
@@ -365,11 +413,8 @@ int lpx_node_batch_plunge(lpx_node_batch* b, int B, const int32_t* slot, const i
                 }
             }
         }
-        const size_t k1 = (size_t)(k > 1 ? k : 1);                       // the in-chain edit uses index 0 of the staging
-        b->off_in[i] = in_bytes; b->off_edit[i] = edit_bytes; b->off_trip[i] = sumK;
-        in_bytes += up16(sizeof(NodeIn) + (size_t)k * (2 * sizeof(double) + sizeof(int32_t)));
-        edit_bytes += up16(k1 * (5 * sizeof(double) + sizeof(int32_t)));
-        lds = std::max(lds, bounded_node_lds_bytes(t->R, t->C));
+        b->off_trip[i] = sumK;
+        place_entry(b, i, t, k, k > 1 ? k : 1, in_bytes, edit_bytes, lds);    // the in-chain edit uses index 0 of the staging
         sumK += (size_t)k;
     }
     int r = ensure_device(); if (r) return r;
@@ -378,62 +423,22 @@ int lpx_node_batch_plunge(lpx_node_batch* b, int B, const int32_t* slot, const i
     // ---- 2. the buffers: grown to twice the need, and only when the need outgrows them
     const size_t o_out = up16(sizeof(PlungeParams) * (size_t)B), o_steps = o_out + kOut * (size_t)B * (size_t)D,
                  o_in = o_steps + up16(sizeof(int32_t) * (size_t)B), need = o_in + in_bytes;
-    if (need > b->slab_bytes) {
-        r = settle_all(b); if (r) return r;
-        if (b->slab) hipHostFree(b->slab);
-        b->slab = nullptr; b->slab_bytes = 0;
-        LPX_HIP_TRY(hipHostMalloc((void**)&b->slab, 2 * need));
-        b->slab_bytes = 2 * need;
-    }
-    if (edit_bytes > b->edit_bytes) {
-        r = settle_all(b); if (r) return r;
-        hipFree(b->edit); b->edit = nullptr; b->edit_bytes = 0;
-        LPX_HIP_TRY(hipMalloc((void**)&b->edit, 2 * edit_bytes));
-        b->edit_bytes = 2 * edit_bytes;
-    }
+    r = ensure_buffers(b, need, edit_bytes, 0); if (r) return r;
     hipStream_t s = b->streams[0];
     const bool has_mask = is_int && nint > 0;
-    if (has_mask && !(b->mask_n == nint && std::memcmp(b->mask_h.data(), is_int, (size_t)nint) == 0)) {
-        r = settle(s); if (r) return r;                                  // an earlier copy may still read mask_h
-        if ((size_t)nint > b->mask_cap) {
-            hipFree(b->mask); b->mask = nullptr; b->mask_cap = 0;
-            LPX_HIP_TRY(hipMalloc((void**)&b->mask, 2 * (size_t)nint));
-            b->mask_cap = 2 * (size_t)nint;
-        }
-        b->mask_h.assign(is_int, is_int + nint);
-        LPX_HIP_TRY(hipMemcpyAsync(b->mask, b->mask_h.data(), (size_t)nint, hipMemcpyHostToDevice, s));
-        b->mask_n = nint;
-    }
+    if (has_mask) { r = ensure_mask(b, s, is_int, nint); if (r) return r; }
 
     // ---- 3. the slab: a parameter record, a header with its triples, D result records and a steps word per entry
     PlungeParams* P = reinterpret_cast<PlungeParams*>(b->slab);
     int32_t* nrec = reinterpret_cast<int32_t*>(b->slab + o_steps);
+    const EntryOpts eo{o, flags, nint, 0, has_mask, tol};
     for (int i = 0; i < B; ++i) {
-        lpx_tableau* t = b->h[slot[i]];
-        lpx_tableau::Bounds& bn = t->bnd;
-        const int k = K[i];
         const size_t at0 = b->off_trip[i];
-        bool any_lo = false;
-        for (int j = 0; j < k; ++j) if (lower[at0 + j] != 0.0) any_lo = true;
-        b->any_lo[i] = any_lo ? 1 : 0;
-        NodeIn* in = reinterpret_cast<NodeIn*>(b->slab + o_in + b->off_in[i]);
-        std::memset(in, 0, sizeof(*in));
-        in->K = k; in->flags = flags; in->nint = nint; in->has_mask = has_mask ? 1 : 0; in->max_iter = o->max_iter;
-        in->lo_used = (bn.lo_used || any_lo) ? 1 : 0;
-        in->eps = o->eps; in->ratio_tol = o->ratio_tol; in->cutoff = (flags & LPX_BDUAL_CUTOFF) ? cutoff[i] : 0.0; in->tol = tol;
-        if (k > 0) {
-            double* a = reinterpret_cast<double*>(in + 1);
-            std::memcpy(a, lower + at0, sizeof(double) * k);
-            std::memcpy(a + k, upper + at0, sizeof(double) * k);
-            std::memcpy(a + 2 * (size_t)k, cols + at0, sizeof(int32_t) * k);
-        }
         PlungeParams& q = P[i];
         std::memset(&q, 0, sizeof(q));
-        NodeParams& n = q.n;
-        n.T = t->T; n.ld = t->ld; n.R = t->R; n.C = t->C;
-        n.rhsbuf = t->rhsbuf; n.basis = t->basis; n.trace = t->trace; n.trace_cap = t->trace_cap; n.st = t->st;
-        n.ub = bn.ub; n.lo = bn.lo; n.flip = bn.flip; n.edit = reinterpret_cast<double*>(b->edit + b->off_edit[i]); n.mask = b->mask;
-        n.in = in; n.out = reinterpret_cast<NodeOut*>(b->slab + o_out + kOut * (size_t)i * (size_t)D);
+        fill_entry(b, i, b->h[slot[i]], K[i], cols + at0, lower + at0, upper + at0, (flags & LPX_BDUAL_CUTOFF) ? cutoff[i] : 0.0, eo,
+                   reinterpret_cast<NodeIn*>(b->slab + o_in + b->off_in[i]), &q.n);
+        q.n.out = reinterpret_cast<NodeOut*>(b->slab + o_out + kOut * (size_t)i * (size_t)D);
         q.prune = prune[i]; q.steps = nrec + i; q.depth = depth[i];
         nrec[i] = 0;
         for (int sx = 0; sx < D; ++sx) { std::memset(&out[(size_t)i * D + sx], 0, sizeof(out[0])); out[(size_t)i * D + sx].pick.var = -1; }
@@ -469,13 +474,7 @@ int lpx_node_batch_plunge(lpx_node_batch* b, int B, const int32_t* slot, const i
         if (ref) {
             rc[i] = LPX_EINVAL;
             out[(size_t)i * D + good].unrepairable = last->unrepairable;
-            if (!refused) {
-                std::string at2 = w + ": entry " + std::to_string(i);
-                if (good > 0) at2 += ": node " + std::to_string(good);
-                if (last->inf_k >= 0) set_error(at2 + ": upper[" + std::to_string(last->inf_k) + "] = +inf on a flipped column");
-                else set_error(at2 + ": " + std::to_string(last->unrepairable) + " column(s) with a negative reduced cost and no upper "
-                               "bound: a bound flip cannot restore dual feasibility");
-            }
+            if (!refused) set_refusal(w + ": entry " + std::to_string(i) + (good > 0 ? ": node " + std::to_string(good) : std::string()), last);
             refused = true;
             continue;
         }
