@@ -18,7 +18,7 @@
 // Sharded form (world > 1): the tree is expanded redundantly until the heap holds >= 4*world nodes,
 // heap[i] then belongs to rank i % world; every rank runs the same best-first loop on its own heap for
 // `round` pops, then ONE all-reduce(max) over {incumbent, have_work} (X1) and the loop continues.
-#include "model.h"
+#include "sharded.h"
 
 #include <algorithm>
 #include <chrono>
@@ -388,78 +388,57 @@ SimplexResult BranchAndBoundKnapsack::Solve(const LPProblem& problem, UpdatePivo
     pq.push(root);
     S.max_heap = 1;
 
-    const int world = std::max(1, opt.world), rank = opt.rank;
+    Sharded sh(opt, "the bounds");                                          // the rank protocol: host/sharded.h
+    const int world = sh.world;
     const int64_t cap_nodes = opt.max_nodes;
-    bool replicated = world > 1;
-    const bool sharded = (world > 1 || opt.shard_one) && (bool)opt.allreduce_max;
     const int round = 256;
-    bool failed = false; std::string fail_msg; int fail_code = 0;
-    // fingerprint of the heap as the replicated warm-up leaves it: {+h, -h} in every rank's FIRST all-reduce, max(+h) == -max(-h) iff
-    // all ranks agree -- ranks that do not (a device path whose result depends on scheduling, as in round 2's record scale7) return an
-    // error instead of waiting in collectives that no longer match (the same device as csrc/host/bnb.cpp frontier_fingerprint)
+    // what the ranks must agree on when the replicated warm-up ends: the heap as it stands, and the pops that led to it
     auto fingerprint = [&](bool handed_out) {
-        uint64_t h = 1469598103934665603ull ^ (handed_out ? 0x9e3779b97f4a7c15ull : 0ull);
-        auto mix = [&](uint64_t v) { h ^= v + 0x9e3779b97f4a7c15ull + (h << 6) + (h >> 2); };
-        mix((uint64_t)pq.d.size()); mix((uint64_t)S.popped);
-        for (const auto& e : pq.d) { int64_t b; double d = e.n->bound; std::memcpy(&b, &d, sizeof(b)); mix((uint64_t)b); mix((uint64_t)(uint32_t)e.n->item); mix((uint64_t)(uint32_t)e.n->depth); }
-        return (double)(h & ((1ull << 52) - 1));
+        Fingerprint fp(handed_out);
+        fp.mix((uint64_t)pq.d.size()); fp.mix((uint64_t)S.popped);
+        for (const auto& e : pq.d) { fp.mix_bits(e.n->bound); fp.mix((uint64_t)(uint32_t)e.n->item); fp.mix((uint64_t)(uint32_t)e.n->depth); }
+        return fp.value();
     };
-    double agree_h = -1.0; bool agree_sent = !sharded;
-    if (sharded && !replicated) agree_h = fingerprint(false);
+    if (sh.exchanging()) sh.agree(fingerprint(false));                      // a world of one: nothing is replicated
     for (;;) {
-        if (replicated && pq.d.size() >= (size_t)(4 * world)) {
-            agree_h = fingerprint(true);
+        if (sh.replicated && pq.d.size() >= (size_t)(4 * world)) {
+            sh.agree(fingerprint(true));
             Heap mine;
-            for (size_t i = 0; i < pq.d.size(); ++i) if ((int)(i % world) == rank) mine.push(pq.d[i].n);
+            for (size_t i = 0; i < pq.d.size(); ++i) if (sh.mine(i)) mine.push(pq.d[i].n);
             pq.d.swap(mine.d);
-            replicated = false;
             S.finish_jobs();
             S.reseed_leaves(pq);
-            if (rank != 0) { S.redundant_popped = S.popped; S.redundant_relax = S.relaxations; }   // rank 0 accounts for the warm-up
+            if (sh.rank != 0) { S.redundant_popped = S.popped; S.redundant_relax = S.relaxations; }   // rank 0 accounts for the warm-up
         }
         bool more = true;
         try {
             for (int it = 0; it < round && more; ++it) {
                 if (cap_nodes > 0 && S.popped >= cap_nodes) { more = false; break; }
                 more = S.step(pq);
-                if (replicated && pq.d.size() >= (size_t)(4 * world)) break;
+                if (sh.replicated && pq.d.size() >= (size_t)(4 * world)) break;
             }
         } catch (const LpxException& e) {
             // a rank that left now would leave its peers waiting in the round's all-reduce: tell them, then stop together
-            if (!sharded) throw;
-            failed = true; fail_msg = e.what(); fail_code = e.code; more = false; replicated = false;
+            if (!sh.sharded) throw;
+            sh.fail(e); more = false;
         }
-        if (sharded && replicated && (!more || pq.d.empty())) {             // ended inside the replicated warm-up: one all-reduce says every rank did
-            agree_h = fingerprint(false);
-            replicated = false;
-        }
-        if (sharded && !replicated) {
-            double vals[5] = {S.has_best ? S.best : -INFINITY, (more && !pq.d.empty()) ? 1.0 : 0.0, failed ? 1.0 : 0.0, -INFINITY, -INFINITY};
-            const bool first = !agree_sent;
-            if (first && !failed) { vals[3] = agree_h; vals[4] = -agree_h; }
-            agree_sent = true;
-            const double mine = vals[0];
-            opt.allreduce_max(vals, 5);                                     // X1: incumbent + termination (+ "someone failed", + the fingerprint once)
-            if (vals[0] > mine) { S.best = vals[0]; S.has_best = true; std::fill(S.bestX.begin(), S.bestX.end(), -1); }
-            if (vals[2] > 0.0) { if (!failed) { failed = true; fail_code = LPX_EDEVICE; fail_msg = "sharded search: a peer rank failed"; } break; }
-            if (first && vals[3] != -vals[4]) {
-                failed = true; fail_code = LPX_EDEVICE;
-                fail_msg = "sharded search: the replicated warm-up ended differently on different ranks (the bounds must be bit-identical across ranks)";
-                break;
-            }
-            if (vals[1] == 0.0) break;
-        } else if (!more || pq.d.empty()) {
-            if (cap_nodes > 0 && S.popped >= cap_nodes) break;
-            if (pq.d.empty()) break;
-        }
+        const bool have_work = more && !pq.d.empty();
+        if (sh.sharded && sh.replicated && !have_work) sh.agree(fingerprint(false));   // ended inside the replicated warm-up: one all-reduce says every rank did
+        if (sh.exchanging()) {
+            double vals[5] = {0, 0, 0, -INFINITY, -INFINITY};
+            const Sharded::Round r = sh.exchange(vals, 5, S.has_best ? S.best : -INFINITY, have_work);   // X1
+            if (r.better) { S.best = r.best; S.has_best = true; std::fill(S.bestX.begin(), S.bestX.end(), -1); }
+            if (r.verdict != Sharded::GO_ON) break;
+        } else if (!have_work) break;                                       // out of budget, or the heap ran dry
     }
-    if (failed) { try { S.finish_jobs(); } catch (const LpxException&) {} throw LpxException(fail_code ? fail_code : LPX_EDEVICE, fail_msg); }
-    if (sharded) {
-        double own = (S.has_best && !S.bestX.empty() && S.bestX[0] >= 0) ? -(double)rank : -INFINITY;
-        opt.allreduce_max(&own, 1);
+    if (sh.failed) { try { S.finish_jobs(); } catch (const LpxException&) {} sh.rethrow(); }
+    if (sh.sharded) {
+        // the solution vector: the lowest rank that holds one for the best z publishes it
+        double own = (S.has_best && !S.bestX.empty() && S.bestX[0] >= 0) ? -(double)sh.rank : -INFINITY;
+        sh.max(&own, 1);
         std::vector<double> xs(n, -INFINITY);
-        if (own == -(double)rank && S.has_best && S.bestX[0] >= 0) for (int i = 0; i < n; ++i) xs[i] = S.bestX[i];
-        if (own != -INFINITY) { opt.allreduce_max(xs.data(), n); for (int i = 0; i < n; ++i) S.bestX[i] = (int32_t)xs[i]; }
+        if (own == -(double)sh.rank && S.has_best && S.bestX[0] >= 0) for (int i = 0; i < n; ++i) xs[i] = S.bestX[i];
+        if (own != -INFINITY) { sh.max(xs.data(), n); for (int i = 0; i < n; ++i) S.bestX[i] = (int32_t)xs[i]; }
     }
 
     S.finish_jobs();                                                        // a batch evaluated ahead may still be on the device
@@ -490,7 +469,7 @@ SimplexResult BranchAndBoundKnapsack::Solve(const LPProblem& problem, UpdatePivo
     res.Solution.assign(S.bestX.begin(), S.bestX.end());
     res.HasSolution = false;
     // whole-job totals when summed over ranks: the replicated warm-up is counted by rank 0 only
-    if (world > 1 && replicated && rank != 0) { S.redundant_popped = S.popped; S.redundant_relax = S.relaxations; }
+    if (world > 1 && sh.replicated && sh.rank != 0) { S.redundant_popped = S.popped; S.redundant_relax = S.relaxations; }
     res.Nodes = S.popped - S.redundant_popped; res.LpSolves = S.relaxations - S.redundant_relax;
     res.NodeZ = {(double)(S.relaxations - S.redundant_relax), (double)(S.popped - S.redundant_popped), (double)S.expanded, (double)S.max_heap};
     res.Stats.launches = S.launches;
