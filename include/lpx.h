@@ -1253,6 +1253,73 @@ int  lpx_solve_bnb_bounded7(const lpx_problem* p, const double* lower /* [n] or 
                             lpx_bnb_bounded_info* info /* or NULL */, lpx_bnb_divers_info* dinfo /* or NULL */,
                             lpx_bnb_guard_info* ginfo /* or NULL */);
 
+/* ---- the bounded primal loop on chip: one launch per LP, a batch of LPs per launch -------------------------------------------
+ *
+ * The on-chip form of lpx_bounded_run (kernels in lpx_bounded_primal.hip): ONE launch of one workgroup runs
+ * the whole loop of the contract "bounded-variable primal simplex" above, steps 1-4 unchanged, with the live window in the LDS of
+ * one compute unit.  The LDS layout is the on-chip node's, so lpx_bounded_node_fits(R, C) is the fit rule unchanged.
+ *
+ * lpx_bounded_run2(t, o, form, cb, user, st): form is LPX_NODE_LAUNCHES, LPX_NODE_ONCHIP or LPX_NODE_AUTO.
+ *   LPX_NODE_LAUNCHES is lpx_bounded_run bit for bit: the same code path, the same cached graphs.
+ *   LPX_NODE_ONCHIP makes ONE launch and ONE wait.  Of the options eps, ratio_tol and max_iter are read; batch, use_graph and
+ *     profile are not.  st (or NULL): pivots = kind-0 + kind-1 pivots, launches = 1, loop_ms the host wall of the call's launch and
+ *     wait.  The status and everything readable from the handle afterwards are bit-equal to the launches form on a handle in the
+ *     same state: the tableau, basis, ub, lo, flip, the trace (entries beyond the trace capacity are dropped, as there),
+ *     lpx_bounded_counts, lpx_tableau_bounded_solution, snapshot and restore, a following lpx_bounded_run and a following
+ *     lpx_bounded_node* of any form.  A handle without bounds runs with every ub = +inf and is then lpx_primal_run bit for bit, as
+ *     the launches form is.
+ *   LPX_NODE_AUTO is LPX_NODE_ONCHIP iff lpx_bounded_node_fits(R, C) for the live shape and cb == NULL, else LPX_NODE_LAUNCHES.
+ *   LPX_EINVAL before any device check, the handle untouched: an unknown form ("unknown form"); LPX_NODE_ONCHIP on a shape that
+ *   does not fit ("does not fit") or with a callback ("no per-event callback": the events of one launch are not reported one by
+ *   one); resident = 1; and the argument errors of lpx_bounded_run with the new name in front.
+ *
+ * lpx_node_batch_primal(b, B, slot, o, out, rc): ONE launch of B workgroups solves B LPs on the batch's handles, 1 <= B <= W, the
+ * slots pairwise distinct.  For every i, out[i], rc[i] (the status, or a negative error) and everything readable from
+ * handles[slot[i]] are bit-equal to lpx_bounded_run2(handles[slot[i]], o, LPX_NODE_ONCHIP, NULL, NULL, NULL) on a handle in the
+ * same state.  The workgroups share nothing, so the result of an entry is independent of B, of the slot numbers and of the other
+ * entries; B may exceed the number of compute units.  Argument errors are checked for every entry before anything is written and
+ * are LPX_EINVAL before any device check with no handle touched: null batch / slot / out / rc, B outside [1, W], a slot outside
+ * [0, W), a repeated slot, resident = 1, a live shape that changed since lpx_tableau_set_bounds or does not fit.  The steady state
+ * of a call: the slab is written, one launch, one wait, B records are read. */
+typedef struct lpx_primal_record {       /* 40 bytes */
+    int32_t status;        /* LPX_OPTIMAL, LPX_UNBOUNDED or LPX_ITER_LIMIT */
+    int32_t events;        /* pivots and flips */
+    int64_t kind0, kind1;  /* pivots whose leaving variable went to zero / to its upper bound */
+    int64_t flips;         /* bound flips */
+    double  z;             /* T[m, C-1] as the loop left it */
+} lpx_primal_record;
+int  lpx_bounded_run2(lpx_tableau* t, const lpx_run_opts* o, int form, lpx_pivot_cb cb, void* user, lpx_stats* st);
+int  lpx_node_batch_primal(lpx_node_batch* b, int B, const int32_t* slot /* [B] */, const lpx_run_opts* o,
+                           lpx_primal_record* out /* [B] */, int32_t* rc /* [B] */);
+
+/* The model level.
+ * lpx_solve_bounded2(p, lower, upper, o, form, out, info): lpx_solve_bounded whose loop is lpx_bounded_run2(form).
+ *   LPX_NODE_LAUNCHES is lpx_solve_bounded with equal results.  LPX_NODE_ONCHIP gives the same out and info apart from
+ *   stats.launches (1) and the times; the shape is known on the host after preparation, so a model that does not fit ("does not
+ *   fit") and a text_cb ("no per-event callback") are LPX_EINVAL before any device check, behind lpx_solve_bounded's own
+ *   validation messages.  LPX_NODE_AUTO is on chip iff the model fits and there is no text_cb.  An unknown form is LPX_EINVAL.
+ * lpx_solve_bounded_batch(count, problems, lowers, uppers, o, outs, infos): 1 <= count <= 1024 independent models of any mix of
+ *   shapes; lowers / uppers are NULL or hold count pointers (each NULL or [n of that model]); infos is NULL or [count].  All models
+ *   are validated and prepared first (an error names the model: "model i: ...") and every one must fit the on-chip form; then the
+ *   call makes count handles, ONE lpx_node_batch_primal launch and count results, each equal to
+ *   lpx_solve_bounded2(problems[i], ..., LPX_NODE_ONCHIP, &outs[i], &infos[i]).  A model that reaches the iteration limit makes
+ *   the call return LPX_ITER_LIMIT ("model i: Iteration limit exceeded.").  On any error outs and infos come back zeroed.
+ * lpx_solve_bnb_bounded8(p, lower, upper, is_int, o, max_nodes, search_flags, divers, stall_events, root_form, out, info, dinfo,
+ *   ginfo): lpx_solve_bnb_bounded7 whose root is solved by lpx_bounded_run2(root_form).  LPX_NODE_LAUNCHES is
+ *   lpx_solve_bnb_bounded7 bit for bit; every form gives a bit-equal node log and a bit-equal result apart from the root's
+ *   stats.launches.  An unknown root_form is LPX_EINVAL before any device check ("unknown root_form"); the root's shape always
+ *   has to fit, as in lpx_solve_bnb_bounded4.  The plunge and the strong-branching drivers have no root_form. */
+int  lpx_solve_bounded2(const lpx_problem* p, const double* lower /* [n] or NULL = 0 */, const double* upper /* [n] or NULL = +inf */,
+                        const lpx_solve_opts* o, int form, lpx_result* out, lpx_bounded_info* info /* or NULL */);
+int  lpx_solve_bounded_batch(int count, const lpx_problem* const* problems, const double* const* lowers /* or NULL */,
+                             const double* const* uppers /* or NULL */, const lpx_solve_opts* o, lpx_result* outs /* [count] */,
+                             lpx_bounded_info* infos /* [count] or NULL */);
+int  lpx_solve_bnb_bounded8(const lpx_problem* p, const double* lower /* [n] or NULL = 0 */, const double* upper /* [n] */,
+                            const uint8_t* is_int /* [n] or NULL = all */, const lpx_solve_opts* o, int64_t max_nodes /* 0 = none */,
+                            int search_flags, int divers /* W, 1..1024 */, int stall_events, int root_form, lpx_result* out,
+                            lpx_bnb_bounded_info* info /* or NULL */, lpx_bnb_divers_info* dinfo /* or NULL */,
+                            lpx_bnb_guard_info* ginfo /* or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,14 @@ namespace Linear_Programming_Solver.Native
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public struct LpxPrimalRecord                // lpx_primal_record: 40 bytes, one entry of lpx_node_batch_primal
+    {
+        public int status, events;               // LPX_OPTIMAL / LPX_UNBOUNDED / LPX_ITER_LIMIT; pivots and flips
+        public long kind0, kind1, flips;
+        public double z;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public struct LpxGuardRecord                 // lpx_guard_record: 8 bytes
     {
         public int bland_events, first_bland;    // pivots made in Bland mode; event index of the first, -1 = none
@@ -399,6 +407,23 @@ namespace Linear_Programming_Solver.Native
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_solve_bounded_dual(ref LpxProblem p, double* lower, double* upper, int flags, ref LpxSolveOpts o,
                                                         out LpxResult result, out LpxBoundedInfo info);
+        // ---- the bounded primal loop on chip: one launch per LP, a batch per launch.  form / root_form: LPX_NODE_* ----
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_bounded_run2(IntPtr t, IntPtr opts, int form, LpxPivotCb cb, IntPtr user, out LpxStats st);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_node_batch_primal(IntPtr batch, int B, int* slot, IntPtr opts, LpxPrimalRecord* records, int* rc);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_bounded2(ref LpxProblem p, double* lower, double* upper, ref LpxSolveOpts o, int form,
+                                                    out LpxResult result, out LpxBoundedInfo info);
+        // problems / lowers / uppers: [count] pointers (lowers, uppers and their entries may be null); results / infos: [count]
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_bounded_batch(int count, LpxProblem** problems, double** lowers, double** uppers, ref LpxSolveOpts o,
+                                                         LpxResult* results, LpxBoundedInfo* infos);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_bnb_bounded8(ref LpxProblem p, double* lower, double* upper, byte* is_int, ref LpxSolveOpts o,
+                                                        long max_nodes, int search_flags, int divers, int stall_events, int root_form,
+                                                        out LpxResult result, out LpxBnbBoundedInfo info, out LpxBnbDiversInfo dinfo,
+                                                        out LpxBnbGuardInfo ginfo);
 
         // ---- branch-and-bound node and child assembly on device handles, the parent store and the batched read-back, include/lpx.h ----
         // any of R / C / ld may be null

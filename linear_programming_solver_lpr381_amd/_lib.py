@@ -177,6 +177,12 @@ class BnbGuardInfo(C.Structure):
     _fields_ = [("guarded_nodes", C.c_int64), ("bland_events", C.c_int64), ("max_events", C.c_int64)]
 
 
+class PrimalRecord(C.Structure):
+    """lpx_primal_record (include/lpx.h): what one entry of lpx_node_batch_primal did."""
+    _fields_ = [("status", C.c_int32), ("events", C.c_int32), ("kind0", C.c_int64), ("kind1", C.c_int64), ("flips", C.c_int64),
+                ("z", C.c_double)]
+
+
 class Parsed(C.Structure):
     _fields_ = [("sense", C.c_int), ("n", C.c_int), ("m", C.c_int), ("c", dp), ("A", dp), ("rel", ip),
                 ("b", dp), ("ragged", C.c_int)]
@@ -393,6 +399,14 @@ def lib() -> C.CDLL:
                                          C.POINTER(BnbGuardInfo)]
     L.lpx_solve_bounded_dual.argtypes = [C.POINTER(Problem), dp, dp, C.c_int, C.POINTER(SolveOpts), C.POINTER(Result),
                                          C.POINTER(BoundedInfo)]
+    L.lpx_bounded_run2.argtypes = [vp, C.POINTER(RunOpts), C.c_int, PIVOT_CB, vp, C.POINTER(Stats)]
+    L.lpx_node_batch_primal.argtypes = [vp, C.c_int, ip, C.POINTER(RunOpts), C.POINTER(PrimalRecord), ip]
+    L.lpx_solve_bounded2.argtypes = [C.POINTER(Problem), dp, dp, C.POINTER(SolveOpts), C.c_int, C.POINTER(Result), C.POINTER(BoundedInfo)]
+    L.lpx_solve_bounded_batch.argtypes = [C.c_int, C.POINTER(C.POINTER(Problem)), C.POINTER(dp), C.POINTER(dp), C.POINTER(SolveOpts),
+                                          C.POINTER(Result), C.POINTER(BoundedInfo)]
+    L.lpx_solve_bnb_bounded8.argtypes = [C.POINTER(Problem), dp, dp, u8p, C.POINTER(SolveOpts), C.c_int64, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.POINTER(Result), C.POINTER(BnbBoundedInfo), C.POINTER(BnbDiversInfo),
+                                         C.POINTER(BnbGuardInfo)]
     L.lpx_parse_text.argtypes = [C.c_char_p, C.POINTER(Parsed)]
     L.lpx_parsed_free.argtypes = [C.POINTER(Parsed)]
     L.lpx_parsed_free.restype = None

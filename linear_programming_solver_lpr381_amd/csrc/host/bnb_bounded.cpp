@@ -53,10 +53,10 @@ void ValidateBnbBounded(int n, const std::vector<double>& lower, const std::vect
 // which never changes and so decides for every node.  False: the root ends the search (an unbounded root is reported as that).
 bool SolveRoot(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper, const EngineOptions& opt,
                bool onchip, BoundedSession& ses, BoundedInfo& binfo, SimplexResult& res, BnbBoundedInfo& info,
-               BnbDiversInfo* dinfo = nullptr, BnbPlungeInfo* pinfo = nullptr)
+               BnbDiversInfo* dinfo = nullptr, BnbPlungeInfo* pinfo = nullptr, int root_form = -1)
 {
     EngineOptions ropt = opt; ropt.quiet = true;
-    res = SolveBounded(original, lower, upper, ropt, nullptr, &binfo, &ses);
+    res = SolveBounded(original, lower, upper, ropt, nullptr, &binfo, &ses, root_form);
     info = BnbBoundedInfo();
     if (dinfo) *dinfo = BnbDiversInfo();
     if (pinfo) *pinfo = BnbPlungeInfo();
@@ -260,7 +260,7 @@ SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<doubl
 SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
                              int search_flags, int divers, BnbDiversInfo& dinfo, const BnbStrong* strong, BnbStrongInfo* sinfo,
-                             int stall_events, BnbGuardInfo* ginfo)
+                             int stall_events, BnbGuardInfo* ginfo, int root_form)
 {
     // stall_events >= 0 (lpx_solve_bnb_bounded7): the evaluate step is ONE lpx_node_batch_run2, which with 0 is lpx_node_batch_run;
     // the guard records are counted and nothing else of the search reads them.
@@ -283,7 +283,7 @@ SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double
     BoundedSession ses;
     BoundedInfo binfo;
     SimplexResult res;
-    if (!SolveRoot(original, lower, upper, opt, true, ses, binfo, res, info, &dinfo)) return res;
+    if (!SolveRoot(original, lower, upper, opt, true, ses, binfo, res, info, &dinfo, nullptr, root_form)) return res;
 
     const int W = divers;
     Pool pool;

@@ -2,9 +2,11 @@
 // PrimalSimplex.Solve (Models/PrimalSimplex.cs:57-90), lower bounds shifted away on the host, upper bounds handed to the device
 // loop (lpx_bounded_run) beside the tableau instead of as rows.  A bounded session (lpx_bounded_open) is the same solve that
 // keeps its handle; its bound edits are lpx_tableau_change_bounds + lpx_bounded_dual_run on that handle.  The dual start
-// (lpx_solve_bounded_dual) shares the preparation and solves from the slack basis with lpx_bounded_dual_run3.
+// (lpx_solve_bounded_dual) shares the preparation and solves from the slack basis with lpx_bounded_dual_run3.  With a form
+// (lpx_solve_bounded2) the loop is lpx_bounded_run2; lpx_solve_bounded_batch solves many models in one lpx_node_batch_primal.
 #include "model.h"
 
+#include <chrono>
 #include <cmath>
 #include <cstring>
 
@@ -174,12 +176,23 @@ void finish_solve(lpx_tableau* h, int st, const LPProblem& original, const std::
 }  // namespace
 
 SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
-                           const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info, BoundedSession* keep)
+                           const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info, BoundedSession* keep, int form)
 {
     const int n = original.NumVars();
-    Prepared P = prepare_bounded(original, lower, upper, opt, updatePivot, false);
+    if (form != -1 && form != LPX_NODE_LAUNCHES && form != LPX_NODE_ONCHIP && form != LPX_NODE_AUTO)
+        throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: unknown form (none of LPX_NODE_LAUNCHES, LPX_NODE_ONCHIP and LPX_NODE_AUTO)");
+    // the on-chip form reports no event: with a callback it is refused below, behind the validation and without a call of it
+    Prepared P = prepare_bounded(original, lower, upper, opt, form == LPX_NODE_ONCHIP ? nullptr : updatePivot, false);
     const int R = P.R, C = P.C;
     const bool bounded = !upper.empty() || !lower.empty() || keep;       // a session edits bounds later: its handle always has them
+    // the shape is known here, on the host: the refusals of the on-chip form come before any device check
+    const bool fits = lpx_bounded_node_fits(R, C) != 0;
+    if (form == LPX_NODE_ONCHIP && updatePivot)
+        throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: the on-chip form has no per-event callback (text_cb)");
+    if (form == LPX_NODE_ONCHIP && !fits)
+        throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: the " + std::to_string(R) + " x " + std::to_string(C) +
+                                       " tableau does not fit the on-chip form (lpx_bounded_node_fits)");
+    const bool onchip = form == LPX_NODE_ONCHIP || (form == LPX_NODE_AUTO && fits && !updatePivot);
 
     SimplexResult res;
     BoundedHandle th(R, C);
@@ -190,7 +203,8 @@ SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>&
     o.max_iter = opt.max_iter;
     o.batch = opt.batch;
     EventCtx ctx{updatePivot, &P.varNames};
-    const int st = lpx_bounded_run(th.h, &o, updatePivot ? bounded_event : nullptr, &ctx, &res.Stats);
+    const int st = onchip ? lpx_bounded_run2(th.h, &o, LPX_NODE_ONCHIP, nullptr, nullptr, &res.Stats)
+                          : lpx_bounded_run(th.h, &o, updatePivot ? bounded_event : nullptr, &ctx, &res.Stats);
     finish_solve(th.h, st, original, lower, P, opt, nullptr, res, info);
     if (keep) {
         keep->h = th.take(); keep->R = R; keep->C = C; keep->n = n;
@@ -198,6 +212,54 @@ SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>&
         keep->lower = lower; keep->open_status = st; keep->opt = opt; keep->varNames = P.varNames;
     }
     return res;
+}
+
+// Many independent models in ONE launch (lpx_solve_bounded_batch): every model validated and prepared first, then a handle per
+// model, one lpx_node_batch_primal over all of them, and per model the tail of SolveBounded.
+void SolveBoundedBatch(const std::vector<const LPProblem*>& problems, const std::vector<std::vector<double>>& lowers,
+                       const std::vector<std::vector<double>>& uppers, const EngineOptions& opt, std::vector<SimplexResult>& results,
+                       std::vector<BoundedInfo>& infos)
+{
+    const int count = (int)problems.size();
+    if (count < 1 || count > 1024) throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: count is outside [1, 1024]");
+    auto named = [](int i, const LpxException& ex) { return LpxException(ex.code, "model " + std::to_string(i) + ": " + ex.what()); };
+    std::vector<Prepared> P((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        try {
+            P[i] = prepare_bounded(*problems[i], lowers[i], uppers[i], opt, nullptr, false);
+            if (!lpx_bounded_node_fits(P[i].R, P[i].C))
+                throw LpxException(LPX_EINVAL, "Bounded Primal Simplex: the " + std::to_string(P[i].R) + " x " + std::to_string(P[i].C) +
+                                               " tableau does not fit the on-chip form (lpx_bounded_node_fits)");
+        } catch (const LpxException& ex) { throw named(i, ex); }
+    }
+    std::vector<std::unique_ptr<BoundedHandle>> th;
+    std::vector<lpx_tableau*> hs;
+    for (int i = 0; i < count; ++i) {
+        th.emplace_back(new BoundedHandle(P[i].R, P[i].C));
+        lpx_tableau* h = th.back()->h;
+        int rc = lpx_tableau_upload(h, P[i].T.data(), P[i].basis.data());
+        if (rc) throw_lib(rc);
+        // a batch's handles always carry their bounds; every ub = +inf is the run without bounds, bit for bit
+        rc = lpx_tableau_set_bounds(h, P[i].C - 1, P[i].ub.data()); if (rc) throw_lib(rc);
+        hs.push_back(h);
+    }
+    lpx_run_opts o; lpx_default_opts(&o, 0);
+    o.max_iter = opt.max_iter;
+    std::vector<int32_t> slot((size_t)count), rcs((size_t)count, 0);
+    for (int i = 0; i < count; ++i) slot[i] = i;
+    std::vector<lpx_primal_record> recs((size_t)count);
+    struct Batch { lpx_node_batch* b = nullptr; ~Batch() { lpx_node_batch_destroy(b); } } nb;
+    int rc = lpx_node_batch_create(count, hs.data(), &nb.b); if (rc) throw_lib(rc);
+    const auto t0 = std::chrono::steady_clock::now();
+    rc = lpx_node_batch_primal(nb.b, count, slot.data(), &o, recs.data(), rcs.data()); if (rc) throw_lib(rc);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();   // the one launch, shared
+    results.assign((size_t)count, SimplexResult());
+    infos.assign((size_t)count, BoundedInfo());
+    for (int i = 0; i < count; ++i) {
+        results[i].Stats.pivots = recs[i].kind0 + recs[i].kind1; results[i].Stats.launches = 1; results[i].Stats.loop_ms = ms;
+        try { finish_solve(hs[i], rcs[i], *problems[i], lowers[i], P[i], opt, nullptr, results[i], &infos[i]); }
+        catch (const LpxException& ex) { results.resize((size_t)i); infos.resize((size_t)i); throw named(i, ex); }
+    }
 }
 
 SimplexResult SolveBoundedDual(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper, int flags,

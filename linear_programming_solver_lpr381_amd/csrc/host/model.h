@@ -228,7 +228,12 @@ struct BoundedSession {
     ~BoundedSession();
 };
 SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
-                           const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info, BoundedSession* keep = nullptr);
+                           const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info, BoundedSession* keep = nullptr,
+                           int form = -1);             // lpx_solve_bounded2: LPX_NODE_* of the loop (lpx_bounded_run2); -1: lpx_bounded_run
+// count independent models in ONE lpx_node_batch_primal launch (lpx_solve_bounded_batch); an error names its model ("model i: ")
+void SolveBoundedBatch(const std::vector<const LPProblem*>& problems, const std::vector<std::vector<double>>& lowers,
+                       const std::vector<std::vector<double>>& uppers, const EngineOptions& opt, std::vector<SimplexResult>& results,
+                       std::vector<BoundedInfo>& infos);
 // The dual start (lpx_solve_bounded_dual): >= rows and negative right-hand sides accepted, slack basis, dualize, lpx_bounded_dual_run3(flags)
 SimplexResult SolveBoundedDual(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper, int flags,
                                const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info);
@@ -260,7 +265,8 @@ SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double
                              int search_flags, int divers, BnbDiversInfo& dinfo, const struct BnbStrong* strong = nullptr,
                              struct BnbStrongInfo* sinfo = nullptr,
                              int stall_events = -1,       // lpx_solve_bnb_bounded7: >= 0, the round is ONE lpx_node_batch_run2 (never with strong)
-                             struct BnbGuardInfo* ginfo = nullptr);
+                             struct BnbGuardInfo* ginfo = nullptr,
+                             int root_form = -1);         // lpx_solve_bnb_bounded8: LPX_NODE_* of the root solve; -1: lpx_bounded_run
 // The search by W divers that plunge (lpx_solve_bnb_bounded5): one lpx_node_batch_plunge per round, up to `plunge` nodes per diver.
 struct BnbPlungeInfo { int64_t launched = 0, dropped = 0, longest_chain = 0; std::vector<int32_t> step; };
 SimplexResult SolveBnbPlunge(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,

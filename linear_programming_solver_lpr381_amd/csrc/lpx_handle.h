@@ -125,6 +125,11 @@ size_t probe_ws_bytes(const lpx_tableau* t, int cand_max);                 // th
 void probe_params(const lpx_tableau* t, const lpx_run_opts* o, int flags, double cutoff, double prune, int nint, const uint8_t* mask_dev,
                   double tol, int cand_max, int probe_iter, bool lo_used, char* ws, const NodeOut* front, lpx_probe_head* head,
                   lpx_probe_record* rec, ProbeParams* p);
+// the on-chip bounded primal loop (lpx_bounded_primal.hip), shared by lpx_bounded_run2 and lpx_node_batch_primal
+int bounded_primal_ready(const char* what);     // the one-time attribute of its kernels
+int bounded_primal_prepare(lpx_tableau* t);     // the device and the bound arrays the loop reads (without bounds: every ub = +inf)
+void primal_params(lpx_tableau* t, const lpx_run_opts* o, lpx_primal_record* rec, PrimalParams* n);    // the parameter record of handle t
+void primal_onchip_commit(lpx_tableau* t, const lpx_primal_record* rec);   // what a finished launch leaves on the host side of its handle
 
 static constexpr int LPX_RESIDENT_RETRY = -1000;     // internal: first resident launch timed out, state untouched
 

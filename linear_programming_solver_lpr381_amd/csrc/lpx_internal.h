@@ -149,6 +149,20 @@ struct ProbeParams {
 };
 hipError_t bounded_probe_init();                    // one-time function attribute
 hipError_t launch_bounded_probe_onchip(const ProbeParams* P, int B, int cand_max, size_t lds, hipStream_t s);
+// the on-chip bounded primal loop (lpx_bounded_primal.hip): one launch of one workgroup runs a whole LP from the basis its handle
+// holds, with the tableau in LDS.  The LDS rule is the node's (bounded_node_lds_bytes).  out: the 40-byte record of include/lpx.h
+// in pinned host memory, the records of a batch 64 bytes apart.
+struct PrimalParams {
+    double* T; int ld, R, C;             // R, C: the LIVE shape
+    double* rhsbuf; int32_t* basis; int32_t* trace; int trace_cap; DevState* st;
+    const double* ub; uint8_t* flip;
+    double eps, ratio_tol; int32_t max_iter, pad;
+    lpx_primal_record* out;
+};
+hipError_t bounded_primal_init();                   // one-time function attribute
+hipError_t launch_bounded_primal_onchip(const PrimalParams& n, hipStream_t s);
+// the batch: workgroup b solves P[b] (an array the device can read); lds = the largest entry's bounded_node_lds_bytes
+hipError_t launch_bounded_primals_onchip(const PrimalParams* P, int B, size_t lds, hipStream_t s);
 
 // ---- lpx_kernels.hip: the two-launch select and update paths
 hipError_t launch_select(const SelParams& p, hipStream_t s);       // gather-based (dual path)

@@ -279,7 +279,7 @@ int lpx_solve(const lpx_problem* p, const char* algorithm, const lpx_solve_opts*
 
 // lpx_solve_bounded (dual_start = false) and lpx_solve_bounded_dual (true, with the dual loop's flags) in one body
 static int solve_bounded(const lpx_problem* p, const double* lower, const double* upper, bool dual_start, int flags, const lpx_solve_opts* o,
-                         lpx_result* out, lpx_bounded_info* info, const char* what)
+                         lpx_result* out, lpx_bounded_info* info, const char* what, int form = -1)      // form: lpx_solve_bounded2
 {
     if (!p || !out) { set_error(std::string(what) + ": null argument"); return LPX_EINVAL; }
     std::memset(out, 0, sizeof(*out));
@@ -293,7 +293,7 @@ static int solve_bounded(const lpx_problem* p, const double* lower, const double
         if (lower) lo.assign(lower, lower + p->n);
         if (upper) up.assign(upper, upper + p->n);
         BoundedInfo bi;
-        SimplexResult r = dual_start ? SolveBoundedDual(q, lo, up, flags, e, cb, &bi) : SolveBounded(q, lo, up, e, cb, &bi);
+        SimplexResult r = dual_start ? SolveBoundedDual(q, lo, up, flags, e, cb, &bi) : SolveBounded(q, lo, up, e, cb, &bi, nullptr, form);
         fill_result(out, r, p->n);
         if (info) {
             info->ncols = (int)bi.ub.size(); info->n = p->n;
@@ -319,6 +319,50 @@ int lpx_solve_bounded_dual(const lpx_problem* p, const double* lower, const doub
                            lpx_result* out, lpx_bounded_info* info)
 {
     return solve_bounded(p, lower, upper, true, flags, o, out, info, "lpx_solve_bounded_dual");
+}
+
+// ---- the bounded primal loop with its form, and a batch of models in one launch (host/bounded.cpp) ---------------------------
+int lpx_solve_bounded2(const lpx_problem* p, const double* lower, const double* upper, const lpx_solve_opts* o, int form, lpx_result* out,
+                       lpx_bounded_info* info)
+{
+    if (form != LPX_NODE_LAUNCHES && form != LPX_NODE_ONCHIP && form != LPX_NODE_AUTO) { set_error("lpx_solve_bounded2: unknown form"); return LPX_EINVAL; }
+    return solve_bounded(p, lower, upper, false, 0, o, out, info, "lpx_solve_bounded2", form);
+}
+
+int lpx_solve_bounded_batch(int count, const lpx_problem* const* problems, const double* const* lowers, const double* const* uppers,
+                            const lpx_solve_opts* o, lpx_result* outs, lpx_bounded_info* infos)
+{
+    const char* what = "lpx_solve_bounded_batch";
+    if (count < 1 || count > 1024) { set_error(std::string(what) + ": count is outside [1, 1024]"); return LPX_EINVAL; }
+    if (!problems || !outs) { set_error(std::string(what) + ": null argument"); return LPX_EINVAL; }
+    for (int i = 0; i < count; ++i)
+        if (!problems[i]) { set_error(std::string(what) + ": model " + std::to_string(i) + ": null problem"); return LPX_EINVAL; }
+    std::memset(outs, 0, sizeof(*outs) * (size_t)count);
+    if (infos) std::memset(infos, 0, sizeof(*infos) * (size_t)count);
+    lpx_solve_opts d; if (!o) { lpx_default_solve_opts(&d); o = &d; }
+    if (o->text_cb) { set_error(std::string(what) + ": the on-chip form has no per-event callback (text_cb)"); return LPX_EINVAL; }
+    return guarded(what, [&]() -> int {
+        EngineOptions e = to_engine(o);
+        std::vector<LPProblem> qs; qs.reserve((size_t)count);
+        std::vector<const LPProblem*> qp;
+        std::vector<std::vector<double>> lo((size_t)count), up((size_t)count);
+        for (int i = 0; i < count; ++i) {
+            qs.push_back(to_problem(problems[i]));
+            if (lowers && lowers[i]) lo[i].assign(lowers[i], lowers[i] + problems[i]->n);
+            if (uppers && uppers[i]) up[i].assign(uppers[i], uppers[i] + problems[i]->n);
+        }
+        for (int i = 0; i < count; ++i) qp.push_back(&qs[i]);
+        std::vector<SimplexResult> rs; std::vector<BoundedInfo> bis;
+        SolveBoundedBatch(qp, lo, up, e, rs, bis);
+        for (int i = 0; i < count; ++i) {
+            fill_result(&outs[i], rs[i], problems[i]->n);
+            if (infos) {
+                infos[i].ncols = (int)bis[i].ub.size(); infos[i].n = problems[i]->n;
+                infos[i].flip = dup_vec(bis[i].flip); infos[i].ub = dup_vec(bis[i].ub); infos[i].lower = dup_vec(bis[i].lower);
+            }
+        }
+        return 0;
+    });
 }
 
 void lpx_bounded_info_free(lpx_bounded_info* info)
@@ -374,7 +418,8 @@ static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const do
                             int node_form = -1, int divers = 0, lpx_bnb_divers_info* dinfo = nullptr,     // divers > 0: lpx_solve_bnb_bounded4
                             int plunge = 0, lpx_bnb_plunge_info* pinfo = nullptr,                         // plunge > 0: lpx_solve_bnb_bounded5
                             const BnbStrong* strong = nullptr, lpx_bnb_strong_info* sinfo = nullptr,      // strong: lpx_solve_bnb_bounded6, LPX_BRANCH_STRONG
-                            int stall_events = -1, lpx_bnb_guard_info* ginfo = nullptr)                   // stall_events >= 0: lpx_solve_bnb_bounded7
+                            int stall_events = -1, lpx_bnb_guard_info* ginfo = nullptr,                   // stall_events >= 0: lpx_solve_bnb_bounded7
+                            int root_form = -1)                                                           // lpx_solve_bnb_bounded8: the root's form
 {
     if (!p || !out) { set_error(std::string(what) + ": null argument"); return LPX_EINVAL; }
     std::memset(out, 0, sizeof(*out));
@@ -397,7 +442,7 @@ static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const do
         BnbPlungeInfo pi;
         BnbStrongInfo si;
         BnbGuardInfo gi;
-        SimplexResult r = stall_events >= 0 ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di, nullptr, nullptr, stall_events, &gi)
+        SimplexResult r = stall_events >= 0 ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di, nullptr, nullptr, stall_events, &gi, root_form)
                         : strong ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di, strong, &si)
                         : plunge ? SolveBnbPlunge(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, plunge, di, pi)
                         : divers ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di)
@@ -493,6 +538,21 @@ int lpx_solve_bnb_bounded7(const lpx_problem* p, const double* lower, const doub
     if (stall_events < 0) { set_error("lpx_solve_bnb_bounded7: stall_events is negative"); return LPX_EINVAL; }
     return solve_bnb_bounded(p, lower, upper, is_int, o, max_nodes, search_flags, out, info, "lpx_solve_bnb_bounded7", -1, divers, dinfo,
                              0, nullptr, nullptr, nullptr, stall_events, ginfo);
+}
+
+int lpx_solve_bnb_bounded8(const lpx_problem* p, const double* lower, const double* upper, const uint8_t* is_int,
+                           const lpx_solve_opts* o, int64_t max_nodes, int search_flags, int divers, int stall_events, int root_form,
+                           lpx_result* out, lpx_bnb_bounded_info* info, lpx_bnb_divers_info* dinfo, lpx_bnb_guard_info* ginfo)
+{
+    if (divers < 1 || divers > 1024) { set_error("lpx_solve_bnb_bounded8: divers is outside [1, 1024]"); return LPX_EINVAL; }
+    if (stall_events < 0) { set_error("lpx_solve_bnb_bounded8: stall_events is negative"); return LPX_EINVAL; }
+    if (root_form != LPX_NODE_LAUNCHES && root_form != LPX_NODE_ONCHIP && root_form != LPX_NODE_AUTO) {
+        set_error("lpx_solve_bnb_bounded8: unknown root_form");
+        return LPX_EINVAL;
+    }
+    // LPX_NODE_LAUNCHES: the call of lpx_solve_bnb_bounded7 itself (the root through lpx_bounded_run)
+    return solve_bnb_bounded(p, lower, upper, is_int, o, max_nodes, search_flags, out, info, "lpx_solve_bnb_bounded8", -1, divers, dinfo,
+                             0, nullptr, nullptr, nullptr, stall_events, ginfo, root_form == LPX_NODE_LAUNCHES ? -1 : root_form);
 }
 
 void lpx_bnb_strong_info_free(lpx_bnb_strong_info* sinfo)

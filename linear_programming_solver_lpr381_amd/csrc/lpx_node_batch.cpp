@@ -5,6 +5,7 @@
 // (lpx_bounded_probe.hip) enqueued behind the node launch: two launches, one wait.
 // lpx_node_batch_run2 is the same body again with the stall guard (include/lpx.h): stall_events = 0 is lpx_node_batch_run's launch, above 0
 // the one launch is lpx_bounded_guard_onchip (lpx_bounded_guard.hip), which leaves a guard record behind each node record.
+// lpx_node_batch_primal is the batch of bounded PRIMAL solves (lpx_bounded_primal.hip): no edit, no mask, no pick, its own small slab.
 // lpx_node_batch_plunge (lpx_bounded_plunge.hip) has its own slab layout and its own walk over a chain's records; what it does as
 // the others do -- the checks of the flags and of an entry, the growth of the buffers, the mask, the header and the parameter
 // record of an entry, the message of a refusal -- are the sub-steps of the anonymous namespace, called from both.
@@ -357,6 +358,64 @@ int lpx_node_batch_run_probe(lpx_node_batch* b, int B, const int32_t* slot, cons
 {
     const ProbeArgs pr{prune, cand_max, probe_iter, head, probes};
     return node_batch_run(b, B, slot, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, rc, &pr, "lpx_node_batch_run_probe");
+}
+
+// The batch of bounded PRIMAL solves (kernel: lpx_bounded_primals_onchip, lpx_bounded_primal.hip): entry i is the on-chip form of
+// lpx_bounded_run2 on handles[slot[i]].  The steps are lpx_node_batch_run's without an edit, a mask or a pick: the slab holds a
+// parameter record and a 64-byte result slot per entry.
+int lpx_node_batch_primal(lpx_node_batch* b, int B, const int32_t* slot, const lpx_run_opts* o, lpx_primal_record* out, int32_t* rc)
+{
+    const char* name = "lpx_node_batch_primal";
+    const std::string w = name;
+    // ---- 1. every argument of every entry, before anything is written and before any device check
+    if (!slot || !out || !rc) { set_error(w + ": null " + (!slot ? "slot" : !out ? "out" : "rc")); return LPX_EINVAL; }
+    if (B < 1) { set_error(w + ": B is outside [1, W]"); return LPX_EINVAL; }
+    lpx_run_opts d;
+    if (b && !o) { lpx_default_opts(&d, 0); o = &d; }                    // the primal loop's defaults
+    { int r = begin_call(w, b, B, o, d); if (r) return r; }
+    if (o->resident > 0) { set_error(w + ": there is no resident form of the bounded loop"); return LPX_EINVAL; }
+    size_t lds = 0;
+    char at[56];
+    for (int i = 0; i < B; ++i) {
+        std::snprintf(at, sizeof at, "%s: entry %d", name, i);
+        if (slot[i] < 0 || slot[i] >= (int)b->h.size()) { set_error(std::string(at) + ": slot is outside [0, W)"); return LPX_EINVAL; }
+        if (b->seen[slot[i]] == b->call) { set_error(std::string(at) + ": slot repeats a handle"); return LPX_EINVAL; }
+        b->seen[slot[i]] = b->call;
+        const lpx_tableau* t = b->h[slot[i]];
+        if (t->R < 2) { set_error(std::string(at) + ": tableau needs at least one constraint row"); return LPX_EINVAL; }
+        if (t->bnd.bounds_set && t->bnd.bounds_C != t->C) { set_error(std::string(at) + ": the live shape changed since lpx_tableau_set_bounds"); return LPX_EINVAL; }
+        int r = check_node_fits(t, at); if (r) return r;
+        lds = std::max(lds, bounded_node_lds_bytes(t->R, t->C));
+    }
+    int r = ensure_device(); if (r) return r;
+    r = bounded_primal_ready(name); if (r) return r;
+    for (int i = 0; i < B; ++i) { r = bounded_primal_prepare(b->h[slot[i]]); if (r) return r; }     // steady state: nothing to do
+
+    // ---- 2. the slab: a parameter record and a result slot per entry
+    const size_t o_out = up16(sizeof(PrimalParams) * (size_t)B), need = o_out + kOut * (size_t)B;
+    static_assert(sizeof(lpx_primal_record) <= kOut, "slab layout");
+    r = ensure_buffers(b, need, 0, 0); if (r) return r;
+    PrimalParams* P = reinterpret_cast<PrimalParams*>(b->slab);
+    for (int i = 0; i < B; ++i) {
+        lpx_primal_record* rec = reinterpret_cast<lpx_primal_record*>(b->slab + o_out + kOut * (size_t)i);
+        std::memset(rec, 0, sizeof(*rec));
+        primal_params(b->h[slot[i]], o, rec, &P[i]);
+    }
+
+    // ---- 3. behind the handles' own streams, ONE launch, ONE wait
+    hipStream_t s = b->streams[0];
+    r = settle_all(b); if (r) return r;
+    LPX_HIP_TRY(launch_bounded_primals_onchip(P, B, lds, s));
+    LPX_HIP_TRY(hipStreamSynchronize(s));
+
+    // ---- 4. the records
+    for (int i = 0; i < B; ++i) {
+        const lpx_primal_record* rec = reinterpret_cast<const lpx_primal_record*>(b->slab + o_out + kOut * (size_t)i);
+        primal_onchip_commit(b->h[slot[i]], rec);
+        out[i] = *rec;
+        rc[i] = rec->status;
+    }
+    return 0;
 }
 
 // The plunge: lpx_node_batch_run's steps with a chain of up to depth[i] nodes per entry (kernel: lpx_bounded_plunge.hip).  Its own:

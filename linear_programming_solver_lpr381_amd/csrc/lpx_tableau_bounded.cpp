@@ -1,7 +1,8 @@
 // lpx_tableau_bounded.cpp -- host side of the bounded-variable family on a tableau handle (C ABI of include/lpx.h): bounds beside
 // the tableau, the bounded primal and dual loops, bound changes on a solved tableau, branch and bound by bound changes.
 // Kernels: lpx_bounded.hip, lpx_bounded_dual.hip, lpx_bounded_long.hip (their shared pieces: lpx_bounded.h), lpx_bnb_bounded.hip;
-// the update is lpx_update.
+// the update is lpx_update.  The on-chip forms: the node (lpx_bounded_node.hip and its siblings) and the primal loop
+// (lpx_bounded_run2, lpx_bounded_primal.hip).
 #include "lpx_handle.h"
 
 #include <cstring>
@@ -189,11 +190,12 @@ int stage_bound_edit(lpx_tableau* t, int K, const int32_t* cols, const double* l
 // The bounded loops in one body: dual = 0 is lpx_bounded_run, 1 + flags the dual loop with that set of LPX_BDUAL_* flags
 // (lpx_bounded_dual_run is 1).  The value goes into the parameter record (BndParams::dual), so that every form selects its own
 // kernel and keys its own cached graph.
-int bounded_run(lpx_tableau* t, const lpx_run_opts* o, int dual, lpx_pivot_cb cb, void* user, lpx_stats* st, double cutoff = 0.0)
+int bounded_run(lpx_tableau* t, const lpx_run_opts* o, int dual, lpx_pivot_cb cb, void* user, lpx_stats* st, double cutoff = 0.0,
+                const char* name = nullptr)         // name: the entry point in front of the messages where it is not the form's own
 {
     const int flags = dual ? dual - 1 : 0;
     const bool lng = flags & (LPX_BDUAL_LONG_STEP | LPX_BDUAL_CUTOFF);      // passes and LPX_CUTOFF exist only in these forms
-    const std::string w = lng ? "lpx_bounded_dual_run3" : dual ? "lpx_bounded_dual_run" : "lpx_bounded_run";
+    const std::string w = name ? name : lng ? "lpx_bounded_dual_run3" : dual ? "lpx_bounded_dual_run" : "lpx_bounded_run";
     if (!t) { set_error(w + ": null tableau"); return LPX_EINVAL; }
     lpx_run_opts d; if (!o) { lpx_default_opts(&d, dual ? 1 : 0); o = &d; }
     if (t->R < 2) { set_error(w + ": tableau needs at least one constraint row"); return LPX_EINVAL; }
@@ -322,6 +324,35 @@ int lpx::bounded_probe_ready(const char* what)
     return 0;
 }
 
+int lpx::bounded_primal_ready(const char* what)
+{
+    static std::once_flag once; static hipError_t init_err = hipSuccess;
+    std::call_once(once, [] { init_err = bounded_primal_init(); });
+    if (init_err != hipSuccess) { set_error(std::string(what) + ": kernel attribute setup failed: " + hipGetErrorString(init_err)); return LPX_EDEVICE; }
+    return 0;
+}
+
+int lpx::bounded_primal_prepare(lpx_tableau* t) { return bounded_ready(t, false); }
+
+void lpx::primal_params(lpx_tableau* t, const lpx_run_opts* o, lpx_primal_record* rec, PrimalParams* n)
+{
+    std::memset(n, 0, sizeof(*n));
+    n->T = t->T; n->ld = t->ld; n->R = t->R; n->C = t->C;
+    n->rhsbuf = t->rhsbuf; n->basis = t->basis; n->trace = t->trace; n->trace_cap = t->trace_cap; n->st = t->st;
+    n->ub = t->bnd.ub; n->flip = t->bnd.flip;
+    n->eps = o->eps; n->ratio_tol = o->ratio_tol; n->max_iter = o->max_iter;
+    n->out = rec;
+}
+
+void lpx::primal_onchip_commit(lpx_tableau* t, const lpx_primal_record* rec)
+{
+    t->trace_void = false;                  // the loop ran and wrote its trace
+    DevState h = fresh_state(false);        // the host mirror, as the loop of the launches form leaves it
+    h.status = rec->status; h.iter = rec->events; h.fdf_count = (int)rec->kind0; h.dual_iter = (int)rec->kind1; h.primal_count = rec->events;
+    *t->hst = h;
+    t->bnd.bcounts[0] = rec->kind0; t->bnd.bcounts[1] = rec->kind1; t->bnd.bcounts[2] = rec->flips;
+}
+
 int lpx::check_probe_args(int cand_max, int probe_iter, const char* what)
 {
     if (cand_max < 1 || cand_max > 32) { set_error(std::string(what) + ": cand_max is outside [1, 32]"); return LPX_EINVAL; }
@@ -411,6 +442,50 @@ int lpx_bounded_counts(lpx_tableau* t, int64_t counts[3])
 
 int lpx_bounded_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, void* user, lpx_stats* st) { return bounded_run(t, o, 0, cb, user, st); }
 int lpx_bounded_dual_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, void* user, lpx_stats* st) { return bounded_run(t, o, 1, cb, user, st); }
+
+// The bounded primal loop with its form (kernels of the on-chip form: lpx_bounded_primal.hip).  On chip the steady state of a
+// call is: the parameter record formed, one kernel launch, one wait, the record read from the handle's pinned slab.
+int lpx_bounded_run2(lpx_tableau* t, const lpx_run_opts* o, int form, lpx_pivot_cb cb, void* user, lpx_stats* st)
+{
+    const char* what = "lpx_bounded_run2";
+    const std::string w = what;
+    if (form != LPX_NODE_LAUNCHES && form != LPX_NODE_ONCHIP && form != LPX_NODE_AUTO) { set_error(w + ": unknown form"); return LPX_EINVAL; }
+    if (form == LPX_NODE_LAUNCHES || (form == LPX_NODE_AUTO && (!t || cb || !bounded_node_fits(t->R, t->C))))
+        return bounded_run(t, o, 0, cb, user, st, 0.0, what);
+    if (!t) { set_error(w + ": null tableau"); return LPX_EINVAL; }
+    lpx_run_opts d; if (!o) { lpx_default_opts(&d, 0); o = &d; }
+    if (t->R < 2) { set_error(w + ": tableau needs at least one constraint row"); return LPX_EINVAL; }
+    if (o->resident > 0) { set_error(w + ": there is no resident form of the bounded loop"); return LPX_EINVAL; }
+    int rc = check_bounds(t, what, false); if (rc) return rc;
+    if (cb) { set_error(w + ": the on-chip form has no per-event callback"); return LPX_EINVAL; }
+    rc = check_node_fits(t, what); if (rc) return rc;
+    rc = bounded_ready(t, false); if (rc) return rc;
+    rc = bounded_primal_ready(what); if (rc) return rc;
+    lpx_tableau::Bounds& b = t->bnd;
+    constexpr size_t kOut = 64;
+    static_assert(sizeof(lpx_primal_record) <= kOut, "slab layout");
+    if (kOut > b.nodeio_bytes) {
+        LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+        if (b.nodeio) hipHostFree(b.nodeio);
+        b.nodeio = nullptr; b.nodeio_bytes = 0;
+        LPX_HIP_TRY(hipHostMalloc((void**)&b.nodeio, 2 * kOut));
+        b.nodeio_bytes = 2 * kOut;
+    }
+    lpx_primal_record* rec = reinterpret_cast<lpx_primal_record*>(b.nodeio);
+    PrimalParams n;
+    primal_params(t, o, rec, &n);
+    const double t0 = now_ms();
+    LPX_HIP_TRY(launch_bounded_primal_onchip(n, t->stream));
+    LPX_HIP_TRY(hipStreamSynchronize(t->stream));                                // the one wait: the record is in the slab
+    primal_onchip_commit(t, rec);
+    if (st) {
+        const double h2d = st->h2d_ms, d2h = st->d2h_ms;
+        std::memset(st, 0, sizeof(*st));
+        st->h2d_ms = h2d; st->d2h_ms = d2h;
+        st->pivots = rec->kind0 + rec->kind1; st->loop_ms = now_ms() - t0; st->launches = 1;
+    }
+    return rec->status;
+}
 
 int lpx_bounded_dual_run2(lpx_tableau* t, const lpx_run_opts* o, int flags, lpx_pivot_cb cb, void* user, lpx_stats* st)
 {

@@ -300,15 +300,49 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         result is laid out as SolveBounded's, BoundCounts = (kind-0 pivots, kind-1 pivots, passes)."""
         return self._solve_bounded(problem, upper, lower, _lib.BDUAL_LONG_STEP if long_step else 0)
 
-    def SolveBounded(self, problem: LPProblem, upper=None, lower=None) -> SimplexResult:
+    def SolveBounded(self, problem: LPProblem, upper=None, lower=None, form: str = "launches") -> SimplexResult:
         """The bounded-variable primal simplex on the device (lpx_solve_bounded): lower[j] <= x_j <= upper[j] without a row
         per bound (None: 0 / +inf).  Status, Solution (user variables), OptimalValue (user's sense), Tableau / Basis (the final
         internal tableau), Trace (events: (r, q) pivot, (-2 - r, q) pivot to the upper bound, (-1, q) bound flip), AtUpper,
-        Flips, BoundCounts.  Solve(problem, "Bounded Primal Simplex") is this without bounds."""
-        return self._solve_bounded(problem, upper, lower, None)
+        Flips, BoundCounts.  Solve(problem, "Bounded Primal Simplex") is this without bounds.  form "onchip" | "auto"
+        (lpx_solve_bounded2): the whole loop in ONE kernel launch with the tableau in LDS ("auto": iff the model fits); the
+        result is that of "launches", the default, apart from the launch count."""
+        if form not in _lib.NODE_FORMS:
+            raise ValueError(f"unknown form {form!r}")
+        return self._solve_bounded(problem, upper, lower, None, form)
 
-    def _solve_bounded(self, problem: LPProblem, upper, lower, dual_flags) -> SimplexResult:
-        """lpx_solve_bounded (dual_flags None) or lpx_solve_bounded_dual: the same call shape and result layout."""
+    def SolveBoundedBatch(self, problems, uppers=None, lowers=None) -> list:
+        """Many independent bounded models in ONE kernel launch (lpx_solve_bounded_batch): 1 <= len(problems) <= 1024 models
+        of any mix of shapes, each of which must fit the on-chip form.  uppers / lowers: None or one entry (None or bounds) per
+        model.  Returns one SimplexResult per model, each equal to SolveBounded(..., form="onchip") of that model."""
+        problems = list(problems)
+        count = len(problems)
+        if count < 1 or count > 1024:
+            raise ValueError(f"{count} models: count must be in [1, 1024]")
+        for name, v in (("uppers", uppers), ("lowers", lowers)):
+            if v is not None and len(v) != count:
+                raise ValueError(f"{len(v)} {name} for {count} models")
+        o, keep = _solve_opts(self.engine)
+        structs, holds, arrs = [], [], []
+        lop, upp = (_lib.dp * count)(), (_lib.dp * count)()
+        for i, pr in enumerate(problems):
+            ps, hold = _problem_struct(pr)
+            structs.append(ps); holds.append(hold)
+            for ptrs, v in ((lop, lowers), (upp, uppers)):
+                if v is not None and v[i] is not None:
+                    a = np.ascontiguousarray(np.broadcast_to(np.asarray(v[i], dtype=np.float64), (pr.NumVars,)))
+                    arrs.append(a)
+                    ptrs[i] = a.ctypes.data_as(_lib.dp)
+        pp = (C.POINTER(_lib.Problem) * count)(*[C.pointer(ps) for ps in structs])
+        rs, infos = (_lib.Result * count)(), (_lib.BoundedInfo * count)()
+        rc = lib().lpx_solve_bounded_batch(count, pp, lop, upp, C.byref(o), rs, infos)
+        if rc != 0:
+            raise SolverException(rc, _lib.last_error())
+        return [self._bounded_result(rs[i], infos[i], problems[i].NumVars) for i in range(count)]
+
+    def _solve_bounded(self, problem: LPProblem, upper, lower, dual_flags, form: str = "launches") -> SimplexResult:
+        """lpx_solve_bounded (dual_flags None; with a form, lpx_solve_bounded2) or lpx_solve_bounded_dual: the same call shape
+        and result layout."""
         n = problem.NumVars
         o, keep = _solve_opts(self.engine)
         ps, hold = _problem_struct(problem)
@@ -321,12 +355,21 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         lo, lop = _vec(lower)
         up, upp = _vec(upper)
         r, info = _lib.Result(), _lib.BoundedInfo()
-        if dual_flags is None:
+        if dual_flags is None and form != "launches":
+            rc = lib().lpx_solve_bounded2(C.byref(ps), lop, upp, C.byref(o), _lib.NODE_FORMS[form], C.byref(r), C.byref(info))
+        elif dual_flags is None:
             rc = lib().lpx_solve_bounded(C.byref(ps), lop, upp, C.byref(o), C.byref(r), C.byref(info))
         else:
             rc = lib().lpx_solve_bounded_dual(C.byref(ps), lop, upp, int(dual_flags), C.byref(o), C.byref(r), C.byref(info))
         if rc != 0:
             raise SolverException(rc, _lib.last_error())
+        res = self._bounded_result(r, info, n)
+        self.FinalTableau = res.Tableau
+        return res
+
+    @staticmethod
+    def _bounded_result(r, info, n) -> SimplexResult:
+        """The result of a bounded solve from its lpx_result and lpx_bounded_info (which it frees)."""
         try:
             flips = _arr(info.flip, info.ncols, np.uint8)
         finally:
@@ -338,14 +381,13 @@ class LPSolver:             # Models/LPSolver.cs:6-77
             basic[res.Basis[(res.Basis >= 0) & (res.Basis < len(flips))]] = True
         res.AtUpper = ((flips[:n] != 0) & ~basic[:n]).astype(np.uint8)
         res.BoundCounts = (int(res.Aux[0]), int(res.Aux[1]), int(res.Aux[2]))
-        self.FinalTableau = res.Tableau
         return res
 
     def SolveBnbBounded(self, problem: LPProblem, upper, lower=None, integer=None, max_nodes: int = 0,
                         long_step: bool = False, cutoff: bool = False, node_form: Optional[str] = None,
                         divers: Optional[int] = None, plunge: Optional[int] = None, branching: Optional[str] = None,
                         candidates: int = 4, probe_iter: Optional[int] = None,
-                        stall_events: Optional[int] = None) -> SimplexResult:
+                        stall_events: Optional[int] = None, root_form: Optional[str] = None) -> SimplexResult:
         """Branch and bound by bound changes on one device tableau (lpx_solve_bnb_bounded): lower <= x <= upper, x_j integer
         where integer[j] (None: every variable); integer variables need finite, integral bounds.  Status OPTIMAL or INFEASIBLE,
         Solution, OptimalValue (user's sense), Nodes, BnbInfo (counters) and BnbLog, a structured array with one record per node
@@ -376,7 +418,21 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         objective a node's loop selects by Bland's rule until the objective moves again, so a node that cycles at a degenerate
         vertex ends instead of making max_iter events.  0 gives the log of divers=W; 50 is a reasonable value.  BnbInfo then
         carries guarded_nodes, bland_events and max_events.  It cannot be combined with node_form="launches", plunge > 1 or
-        branching: those have no guard."""
+        branching: those have no guard.  root_form "launches" | "onchip" | "auto" (lpx_solve_bnb_bounded8; None: the paths above,
+        unchanged; without divers it means divers=1, without stall_events stall_events=0): the search by divers whose root LP
+        is solved in that form; the node log is the same for every form.  It cannot be combined with node_form="launches",
+        plunge or branching: those drivers have no root form."""
+        if root_form is not None:
+            if root_form not in _lib.NODE_FORMS:
+                raise ValueError(f"unknown root form {root_form!r}")
+            if node_form == "launches":
+                raise ValueError("root_form belongs to the search by divers: it cannot be combined with node_form='launches'")
+            if plunge is not None:
+                raise ValueError("the plunge driver has no root form: root_form cannot be combined with plunge")
+            if branching is not None:
+                raise ValueError("the strong-branching driver has no root form: root_form cannot be combined with branching")
+            if stall_events is None:
+                stall_events = 0
         if stall_events is not None:
             if int(stall_events) < 0:
                 raise ValueError(f"stall_events = {stall_events}: stall_events must not be negative")
@@ -429,7 +485,11 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         flags = (_lib.BDUAL_LONG_STEP if long_step else 0) | (_lib.BDUAL_CUTOFF if cutoff else 0)
         sinfo = _lib.BnbStrongInfo()
         ginfo = _lib.BnbGuardInfo()
-        if stall_events is not None:
+        if root_form is not None:
+            rc = lib().lpx_solve_bnb_bounded8(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), flags, int(divers),
+                                              int(stall_events), _lib.NODE_FORMS[root_form], C.byref(r), C.byref(info), C.byref(dinfo),
+                                              C.byref(ginfo))
+        elif stall_events is not None:
             rc = lib().lpx_solve_bnb_bounded7(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), flags, int(divers),
                                               int(stall_events), C.byref(r), C.byref(info), C.byref(dinfo), C.byref(ginfo))
         elif branching is not None:

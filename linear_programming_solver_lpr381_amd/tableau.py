@@ -250,13 +250,20 @@ class DeviceTableau:
         return f[: self.C - 1]
 
     def bounded_run(self, opts: Optional[RunOpts] = None, cb: Optional[PivotCallback] = None,
-                    **kw) -> Tuple[int, dict]:
+                    form: str = "launches", **kw) -> Tuple[int, dict]:
         """Bounded-variable primal loop (lpx_bounded_run): one event per iteration -- a pivot (r, q), a pivot whose leaving
-        variable goes to its upper bound (-2 - r, q), or a bound flip (-1, q).  Returns (status, stats)."""
+        variable goes to its upper bound (-2 - r, q), or a bound flip (-1, q).  Returns (status, stats).  form "onchip" | "auto"
+        (lpx_bounded_run2): the whole loop in ONE kernel launch with the tableau in LDS ("auto": iff the live shape fits and
+        there is no callback); everything the handle holds afterwards is bit-equal to "launches", the default."""
+        if form not in _lib.NODE_FORMS:
+            raise ValueError(f"unknown form {form!r}")
         o = opts if opts is not None else default_opts(False, **kw)
         st = Stats()
         c = _wrap_cb(cb)
-        rc = check(lib().lpx_bounded_run(self._h, C.byref(o), c, None, C.byref(st)))
+        if form == "launches":
+            rc = check(lib().lpx_bounded_run(self._h, C.byref(o), c, None, C.byref(st)))
+        else:
+            rc = check(lib().lpx_bounded_run2(self._h, C.byref(o), _lib.NODE_FORMS[form], c, None, C.byref(st)))
         return rc, st.as_dict()
 
     def bounded_counts(self) -> Tuple[int, int, int]:
@@ -475,6 +482,21 @@ class NodeBatch:
 
     def __exit__(self, *exc):
         self.close()
+
+    def solve(self, slots, opts: Optional[RunOpts] = None, **kw) -> list:
+        """Entry i runs the bounded primal loop on handles[slots[i]] from the basis it holds, all in ONE kernel launch
+        (lpx_node_batch_primal); the slots are distinct.  Every entry is bit-equal to DeviceTableau.bounded_run(form="onchip")
+        on its handle.  Returns one dict per entry: status, events, kind0, kind1, flips, z."""
+        slots = np.ascontiguousarray(np.atleast_1d(slots), dtype=np.int32).reshape(-1)
+        B = len(slots)
+        if B < 1 or B > self._W:
+            raise ValueError(f"a batch of {B} entries on {self._W} handles: B must be in [1, W]")
+        o = opts if opts is not None else default_opts(False, **kw)
+        recs = (_lib.PrimalRecord * B)()
+        rc = np.zeros(B, dtype=np.int32)
+        check(lib().lpx_node_batch_primal(self._h, B, slots.ctypes.data_as(ip), C.byref(o), recs, rc.ctypes.data_as(ip)))
+        return [{"status": int(rc[i]), "events": recs[i].events, "kind0": recs[i].kind0, "kind1": recs[i].kind1,
+                 "flips": recs[i].flips, "z": recs[i].z} for i in range(B)]
 
     def run(self, slots, nodes, nint: int, is_int=None, tol: float = 1e-6, long_step: bool = False, cutoffs=None,
             opts: Optional[RunOpts] = None, stall_events: Optional[int] = None, **kw) -> list:

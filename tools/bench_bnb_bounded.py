@@ -54,7 +54,12 @@ usage: bench_bnb_bounded.py [--model NAME] [--max-nodes N] [--node-form F] [--di
                             [--compare-forms [--flag-sets LIST]] [--compare-divers LIST [--flag-sets LIST]]
                             [--compare-plunge LIST [--flag-sets LIST]] [--compare-branching LIST [--flag-sets LIST]]
                             [--branching R [--candidates C] [--probe-iter L]] [--compare-guard LIST [--flag-sets LIST]]
-                            [--stall-events S] [--long-step] [--cutoff] [--trace-only] [REPS]"""
+                            [--stall-events S] [--long-step] [--cutoff] [--trace-only] [--compare-root LIST] [REPS]
+
+`--compare-root LIST` measures the form of the root solve (lpx_solve_bnb_bounded8) at every W of LIST, with the
+long step and the cutoff: root_form "launches" against "onchip", the sides alternating, one untimed solve each first.  Beside the
+search it times the root solve alone in either form (lpx_solve_bounded / lpx_solve_bounded2) and reports its share of the search's
+wall on both sides.  A side wins iff its median lies below the other's minimum."""
 import json
 import os
 import statistics
@@ -359,8 +364,74 @@ def compare_guard(n, m, reps, max_nodes, flag_sets, W, stalls, seed=None):
     return rec
 
 
+def compare_root(n, m, reps, max_nodes, widths):
+    """The root solve's form (lpx_solve_bnb_bounded8) at W divers on binary_ip(n, m), long step and cutoff (see the module docstring)."""
+    c, A, rel, b = synth.binary_ip(n, m)
+    p = L.LPProblem.from_arrays(0, c, A[:m], rel[:m], b[:m])
+    rec = {"n": n, "m": m, "bounded_shape": [m + 1, n + m + 1]}
+    root = {f: [] for f in FORMS}
+    for i in range(reps + 2):
+        for f in FORMS:
+            t0 = time.perf_counter()
+            r = L.LPSolver().SolveBounded(p, 1.0, form=f)
+            if i >= 2:
+                root[f].append(1e3 * (time.perf_counter() - t0))
+    rec["root_alone_ms"] = {f: stats(root[f]) for f in FORMS}
+    rec["root_events"] = int(sum(r.BoundCounts))
+
+    def solve(W, f):
+        t0 = time.perf_counter()
+        try:
+            r = L.LPSolver().SolveBnbBounded(p, 1.0, max_nodes=max_nodes, divers=W, root_form=f, long_step=True, cutoff=True)
+            r.Limit = None
+        except L.SolverException as e:
+            if e.code != L._lib.ITER_LIMIT:
+                raise
+            r = e.result
+            r.Limit = str(e)
+        return 1e3 * (time.perf_counter() - t0), r
+
+    for W in widths:
+        ts = {f: [] for f in FORMS}
+        last = {}
+        for i in range(reps + 1):
+            for f in FORMS:
+                ms, r = solve(W, f)
+                if i >= 1:
+                    ts[f].append(ms)
+                last[f] = r
+        assert last["launches"].BnbLog.tobytes() == last["onchip"].BnbLog.tobytes(), "the node logs differ"
+        d = {}
+        for f in FORMS:
+            st = stats(ts[f])
+            d[f] = {"ms": st, "nodes": int(last[f].Nodes), "limit": last[f].Limit,
+                    "root_share": rec["root_alone_ms"][f]["median"] / st["median"]}
+        a, o = d["launches"]["ms"], d["onchip"]["ms"]
+        d["winner"] = "onchip" if o["median"] < a["min"] else "launches" if a["median"] < o["min"] else "tie"
+        rec[f"W{W}"] = d
+    return rec
+
+
 def main():
     args = sys.argv[1:]
+    if "--compare-root" in args:
+        k = args.index("--compare-root")
+        widths = [int(w) for w in args[k + 1].split(",") if w]
+        del args[k:k + 2]
+        only, max_nodes = None, 0
+        for flag in ("--model", "--max-nodes"):
+            if flag in args:
+                j = args.index(flag)
+                if flag == "--model":
+                    only = args[j + 1]
+                else:
+                    max_nodes = int(args[j + 1])
+                del args[j:j + 2]
+        reps = int(args[0]) if args else 7
+        L._lib.check(L._lib.lib().lpx_init(0))
+        out = {name: compare_root(n, m, reps, max_nodes, widths) for name, n, m in models() if only is None or name == only}
+        print(json.dumps(out))
+        return
     stall_events, stalls = None, None
     for flag in ("--stall-events", "--compare-guard"):
         if flag in args:

@@ -14,7 +14,15 @@ of lpx_bounded_select and of the lpx_update launches it feeds.
 
 `--model NAME` keeps one of the two models (config4_root, dense_1024x2048_u1), so that a trace covers one shape.
 
-usage: bench_bounded.py [--trace-only] [--model NAME] [REPS]"""
+`--compare-forms` measures the on-chip form of the bounded primal loop (lpx_bounded_run2 with LPX_NODE_ONCHIP)
+against the launches form (lpx_bounded_run), by the rule of DESIGN section 4.17: host wall, median with min and max, the sides
+alternating in one process, and a side wins iff its median lies below the other's minimum.  Root solves: binary_ip(60, 12),
+binary_ip(128, 64) without their bound rows and dense_lp(64, 128), every u_j = 1, one handle each, a timed run starting from a
+restored snapshot.  The batch, three ways: 256 models of 13 x 73 through lpx_solve_bounded_batch, as 256 single on-chip solves and
+as 256 launches-form solves (lpx_solve_bounded), whole calls timed.  `--forms-trace` runs one warm on-chip solve per root model and
+one batch, for a run of its own under `rocprofv3 --kernel-trace --stats`: one kernel per solve and one per batch.
+
+usage: bench_bounded.py [--trace-only] [--model NAME] [--compare-forms | --forms-trace] [REPS]"""
 import json
 import os
 import statistics
@@ -39,7 +47,133 @@ def stats(ts):
     return {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts), "reps": len(ts)}
 
 
+def form_models():
+    for n, m in ((60, 12), (128, 64)):
+        c, A, rel, b = synth.binary_ip(n, m)
+        yield "binary_bounded_%dx%d" % (n, m), c, A[:m], b[:m]
+    c, A, b = synth.dense_lp(64, 128)
+    yield "dense_unit_64x128", c, A, b
+
+
+def verdict(a, b, na, nb):
+    """The rule of DESIGN section 4.17: a side wins iff its median lies below the other's minimum."""
+    if a["median_ms"] < b["min_ms"]:
+        return na
+    if b["median_ms"] < a["min_ms"]:
+        return nb
+    return "tie"
+
+
+def batch_models(count):
+    ps = []
+    for s in range(1, count + 1):
+        c, A, rel, b = synth.binary_ip(60, 12, s)
+        ps.append(L.LPProblem.from_arrays(0, c, A[:12], [0] * 12, b[:12]))
+    return ps
+
+
+def compare_forms(reps, trace):
+    out = {}
+    for name, c, A, b in form_models():
+        m, n = A.shape
+        T, basis = synth.primal_tableau_from(c, A, b)
+        ub = np.full(T.shape[1] - 1, np.inf); ub[:n] = 1.0
+        with L.DeviceTableau.from_host(T, basis) as dt:
+            dt.set_bounds(ub)
+            dt.snapshot()
+            tl, tc = [], []
+            for i in range(1 + 2 if trace else reps + 2):
+                if not trace:
+                    dt.restore()
+                    t0 = time.perf_counter()
+                    sl, stl = dt.bounded_run()
+                    if i >= 2:
+                        tl.append(1e3 * (time.perf_counter() - t0))
+                    kl, zl = dt.bounded_counts(), dt.bounded_solution(n)[1]
+                dt.restore()
+                t0 = time.perf_counter()
+                sc, stc = dt.bounded_run(form="onchip")
+                if i >= 2:
+                    tc.append(1e3 * (time.perf_counter() - t0))
+            kc, zc = dt.bounded_counts(), dt.bounded_solution(n)[1]
+            rec = {"shape": list(T.shape), "events": sum(kc), "counts": list(kc), "status": sc, "z": zc,
+                   "onchip": dict(stats(tc), launches=stc["launches"])}
+            if not trace:
+                assert (sl, kl, zl) == (sc, kc, zc), "the forms differ"
+                rec["launches"] = dict(stats(tl), launches=stl["launches"])
+                rec["launches_over_onchip"] = rec["launches"]["median_ms"] / rec["onchip"]["median_ms"]
+                rec["winner"] = verdict(rec["launches"], rec["onchip"], "launches", "onchip")
+        out[name] = rec
+    count = 256
+    ps = batch_models(count)
+    S = L.LPSolver()
+    tb, ts, tl = [], [], []
+    for i in range(1 + 1 if trace else reps + 1):
+        t0 = time.perf_counter()
+        rb = S.SolveBoundedBatch(ps, [1.0] * count)
+        if i >= 1:
+            tb.append(1e3 * (time.perf_counter() - t0))
+        if trace:
+            continue
+        t0 = time.perf_counter()
+        rs = [S.SolveBounded(p, 1.0, form="onchip") for p in ps]
+        if i >= 1:
+            ts.append(1e3 * (time.perf_counter() - t0))
+        t0 = time.perf_counter()
+        rl = [S.SolveBounded(p, 1.0) for p in ps]
+        if i >= 1:
+            tl.append(1e3 * (time.perf_counter() - t0))
+        assert all(a.OptimalValue == b.OptimalValue == c.OptimalValue and a.BoundCounts == b.BoundCounts == c.BoundCounts
+                   for a, b, c in zip(rb, rs, rl)), "the three ways differ"
+    rec = {"count": count, "shape": [13, 73], "events": int(sum(sum(r.BoundCounts) for r in rb)), "batch": stats(tb)}
+    if not trace:
+        rec["single_onchip"] = stats(ts); rec["single_launches"] = stats(tl)
+        rec["winner_batch_vs_single_onchip"] = verdict(rec["batch"], rec["single_onchip"], "batch", "single_onchip")
+        rec["winner_batch_vs_single_launches"] = verdict(rec["batch"], rec["single_launches"], "batch", "single_launches")
+        rec["winner_single_onchip_vs_single_launches"] = verdict(rec["single_onchip"], rec["single_launches"], "single_onchip", "single_launches")
+    out["batch_256_of_13x73"] = rec
+    if not trace:
+        # the same 256 LPs on handles that exist already (tableau level): the restores are not timed, each side's runs are
+        hs = []
+        for s in range(1, count + 1):
+            c, A, rel, b = synth.binary_ip(60, 12, s)
+            T, basis = synth.primal_tableau_from(c, A[:12], b[:12])
+            ub = np.full(T.shape[1] - 1, np.inf); ub[:60] = 1.0
+            dt = L.DeviceTableau.from_host(T, basis)
+            dt.set_bounds(ub); dt.snapshot()
+            hs.append(dt)
+        sides = {"batch": [], "single_onchip": [], "single_launches": []}
+        with L.NodeBatch(hs) as nb:
+            slots = list(range(count))
+            for i in range(reps + 2):
+                for side, ts in sides.items():
+                    for dt in hs:
+                        dt.restore()
+                    for dt in hs[:16]:          # the handles borrow a few pool streams round robin: this waits for every restore
+                        dt.bound_flags()
+                    t0 = time.perf_counter()
+                    if side == "batch":
+                        recs = nb.solve(slots)
+                    else:
+                        for dt in hs:
+                            dt.bounded_run(form="onchip" if side == "single_onchip" else "launches")
+                    if i >= 2:
+                        ts.append(1e3 * (time.perf_counter() - t0))
+        for dt in hs:
+            dt.close()
+        rec = {"count": count, "shape": [13, 73], "events": int(sum(r["events"] for r in recs))}
+        rec.update({k: stats(v) for k, v in sides.items()})
+        rec["winner_batch_vs_single_onchip"] = verdict(rec["batch"], rec["single_onchip"], "batch", "single_onchip")
+        rec["winner_batch_vs_single_launches"] = verdict(rec["batch"], rec["single_launches"], "batch", "single_launches")
+        out["handles_256_of_13x73"] = rec
+    print(json.dumps(out))
+
+
 def main():
+    if "--compare-forms" in sys.argv[1:] or "--forms-trace" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a not in ("--compare-forms", "--forms-trace")]
+        L._lib.check(L._lib.lib().lpx_init(0))
+        return compare_forms(int(rest[0]) if rest else 15, "--forms-trace" in sys.argv[1:])
     args = [a for a in sys.argv[1:] if a != "--trace-only"]
     trace_only = "--trace-only" in sys.argv[1:]
     only = None

@@ -1,7 +1,7 @@
 // lpx_cli -- Linux stand-in for the reference's WinForms host (Form1.cs), over the C ABI of liblpx.so only.
 //
 //   lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]
-//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S]] [--export FILE] INPUT.txt
+//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S] [--root-form F]] [--bounded-form F] [--export FILE] INPUT.txt
 //
 // Does what Form1 does around the solvers: reads the model text (Import, Form1.cs:284-296), parses it with the LPParser
 // grammar (lpx_parse_text, Models/LPParser.cs:9-79), runs the algorithm chosen by its dropdown name (btnSolve_Click,
@@ -84,6 +84,8 @@ int main(int argc, char** argv)
     int candidates = 4;         // --candidates N: the columns probed per node by --branching strong
     int probe_iter = -1;        // --probe-iter L: the event limit of a probe; -1 = the node's
     int stall_events = -1;      // --stall-events S beside --bnb-bounded: the stall guard (lpx_solve_bnb_bounded7); -1 = not given
+    int bounded_form = -1;      // --bounded-form F: LPX_NODE_* of the bounded primal solve (lpx_solve_bounded2); -1 = not given
+    int root_form = -1;         // --root-form F beside --bnb-bounded --divers: LPX_NODE_* of the root solve (lpx_solve_bnb_bounded8); -1 = not given
     struct Bound { bool upper; int index; double value; std::string text; };
     std::vector<Bound> bounds;
     lpx_cut_opts co; lpx_default_cut_opts(&co);
@@ -100,6 +102,12 @@ int main(int argc, char** argv)
             const std::string v = argv[++i];
             node_form = v == "launches" ? LPX_NODE_LAUNCHES : v == "onchip" ? LPX_NODE_ONCHIP : v == "auto" ? LPX_NODE_AUTO : -2;
             if (node_form == -2) { std::fprintf(stderr, "lpx_cli: --node-form takes launches, onchip or auto, got '%s'\n", v.c_str()); return 64; }
+        }
+        else if ((a == "--bounded-form" || a == "--root-form") && i + 1 < argc) {
+            const std::string v = argv[++i];
+            const int f = v == "launches" ? LPX_NODE_LAUNCHES : v == "onchip" ? LPX_NODE_ONCHIP : v == "auto" ? LPX_NODE_AUTO : -2;
+            if (f == -2) { std::fprintf(stderr, "lpx_cli: %s takes launches, onchip or auto, got '%s'\n", a.c_str(), v.c_str()); return 64; }
+            (a == "--bounded-form" ? bounded_form : root_form) = f;
         }
         else if (a == "--divers" && i + 1 < argc) {
             const std::string v = argv[++i];
@@ -175,7 +183,7 @@ int main(int argc, char** argv)
         else if (a == "--export" && i + 1 < argc) exportPath = argv[++i];
         else if (a == "--help" || a == "-h") {
             std::printf("usage: lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]\n"
-                        "               [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S]]\n"
+                        "               [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S] [--root-form F]] [--bounded-form F]\n"
                         "               [--export FILE] INPUT.txt\n"
                         "  NAME: Primal Simplex | Revised Primal Simplex | Dual Simplex | Branch and Bound |\n"
                         "        Revised Branch and Bound | Branch and Bound Knapsack | Cutting Plane | Revised Cutting Plane |\n"
@@ -203,6 +211,10 @@ int main(int argc, char** argv)
                         "             after S pivots without progress of the objective a node selects by Bland's rule until the objective moves,\n"
                         "             so a node that cycles ends; 0 = no guard, 50 is a reasonable value; not with --node-form launches,\n"
                         "             --plunge above 1 or --branching\n"
+                        "  --bounded-form launches|onchip|auto: the bounded primal solve (--binary / --upper / --lower without --bnb-bounded) as\n"
+                        "             launches per pivot (the default) or in ONE kernel launch with the tableau on chip (lpx_solve_bounded2)\n"
+                        "  --root-form launches|onchip|auto: with --bnb-bounded --divers, how the root LP is solved (lpx_solve_bnb_bounded8);\n"
+                        "             the node log does not depend on it; not with --plunge or --branching\n"
                         "  --set-rhs I=V, --set-cost J=V: after the solve, b_I = V / c_J = V (1-based, repeatable), applied in order,\n"
                         "             each re-optimised warm on the device from the previous basis; each re-solve's summary is printed\n");
             return 0;
@@ -227,6 +239,10 @@ int main(int argc, char** argv)
     if (stall_events >= 0 && node_form == LPX_NODE_LAUNCHES) { std::fprintf(stderr, "lpx_cli: --stall-events: the stall guard has no launches form: not with --node-form launches\n"); return 64; }
     if (stall_events >= 0 && plunge > 1) { std::fprintf(stderr, "lpx_cli: --stall-events: the plunge has no stall guard: not with --plunge above 1\n"); return 64; }
     if (stall_events >= 0 && branching >= 0) { std::fprintf(stderr, "lpx_cli: --stall-events: the probes have no stall guard: not with --branching\n"); return 64; }
+    if (bounded_form >= 0 && (!bounded || bnb_bounded)) { std::fprintf(stderr, "lpx_cli: --bounded-form needs --binary or --upper / --lower bounds, without --bnb-bounded\n"); return 64; }
+    if (root_form >= 0 && !(bnb_bounded && divers)) { std::fprintf(stderr, "lpx_cli: --root-form needs --bnb-bounded --divers\n"); return 64; }
+    if (root_form >= 0 && (plunge || branching >= 0)) { std::fprintf(stderr, "lpx_cli: --root-form: the plunge and the strong-branching drivers have no root form\n"); return 64; }
+    if (root_form >= 0 && stall_events < 0) stall_events = 0;
     if (stall_events >= 0) { plunge = 0; if (!divers) divers = 1; }
     if (branching >= 0) { plunge = 0; if (!divers) divers = 1; }
     if (plunge && !divers) divers = 1;
@@ -252,6 +268,8 @@ int main(int argc, char** argv)
     lpx_solve_opts o; lpx_default_solve_opts(&o);
     o.text_cb = on_text;
     o.render_iterations = iterations ? 1 : 0;
+    // the on-chip form of the bounded solve reports no event: without --iterations no text is asked for, so it may be chosen
+    if (bounded_form > LPX_NODE_LAUNCHES && !iterations) o.text_cb = nullptr;
     if (repaired) { o.dual_flags = 7; o.bnb_mode = 1; }
     lpx_result r;
     lpx_ranging rg;
@@ -260,7 +278,8 @@ int main(int argc, char** argv)
         if (bd.index >= p.n) { std::fprintf(stderr, "lpx_cli: %s: index out of range\n", bd.text.c_str()); lpx_parsed_free(&p); return 64; }
         (bd.upper ? up : lo)[bd.index] = bd.value;
     }
-    const int rc = bnb_bounded && stall_events >= 0 ? lpx_solve_bnb_bounded7(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, stall_events, &r, nullptr, nullptr, nullptr)
+    const int rc = bnb_bounded && root_form >= 0 ? lpx_solve_bnb_bounded8(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, stall_events, root_form, &r, nullptr, nullptr, nullptr)
+                 : bnb_bounded && stall_events >= 0 ? lpx_solve_bnb_bounded7(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, stall_events, &r, nullptr, nullptr, nullptr)
                  : bnb_bounded && branching >= 0 ? lpx_solve_bnb_bounded6(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, branching, candidates,
                                                                          probe_iter >= 0 ? probe_iter : o.max_iter > 0 ? o.max_iter : 10000, &r, nullptr, nullptr, nullptr)
                  : bnb_bounded && plunge ? lpx_solve_bnb_bounded5(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, plunge, &r, nullptr, nullptr, nullptr)
@@ -268,6 +287,7 @@ int main(int argc, char** argv)
                  : bnb_bounded && node_form >= 0 ? lpx_solve_bnb_bounded3(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, node_form, &r, nullptr)
                  : bnb_bounded && search_flags ? lpx_solve_bnb_bounded2(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, &r, nullptr)
                  : bnb_bounded ? lpx_solve_bnb_bounded(&prob, lo.data(), up.data(), nullptr, &o, 0, &r, nullptr)
+                 : bounded && bounded_form >= 0 ? lpx_solve_bounded2(&prob, lo.data(), up.data(), &o, bounded_form, &r, nullptr)
                  : bounded ? lpx_solve_bounded(&prob, lo.data(), up.data(), &o, &r, nullptr) : ranging ? lpx_solve_ranging(&prob, algorithm.c_str(), &o, &r, &rg)
                  : cut_set ? lpx_solve_cuts(&prob, &o, &co, &r) : lpx_solve(&prob, algorithm.c_str(), &o, &r);
     if (rc != 0) { lpx_parsed_free(&p); lpx_last_error(err, sizeof err); std::fprintf(stderr, "%s\n", err); return rc == LPX_EDEVICE ? 69 : 70; }
