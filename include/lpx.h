@@ -641,7 +641,8 @@ void lpx_session_close(lpx_session* s);
  *   returns the events.  lpx_bounded_counts: events of the last run: kind 0, kind 1, flips.
  * lpx_tableau_snapshot / lpx_tableau_restore carry ub and flip with the tableau; restoring a snapshot taken before the handle
  *   had bounds clears every flip.  lpx_tableau_ranging, lpx_tableau_gmi_round and the post-optimal edits on a handle with
- *   flips set see the internal representation (flipped columns stand for u_j - x_j); they are not bound-aware.
+ *   flips set see the internal representation (flipped columns stand for u_j - x_j); they are not bound-aware
+ *   (lpx_tableau_gmi_round_bounded is the round that is, and it carries the bounds across its reshape).
  * lpx_tableau_bounded_solution: v_j = RHS of the row where j is basic, else +0.0; x[j] = flip[j] ? ub[j] - v_j : v_j (one
  *   subtraction); *z = T[m,Cm]; at_upper[j] = 1 iff j is nonbasic and flipped.  nvars <= C-1.
  * Argument errors return LPX_EINVAL before any device check, with the handle untouched: a NULL handle, ncols not the live
@@ -1319,6 +1320,103 @@ int  lpx_solve_bnb_bounded8(const lpx_problem* p, const double* lower /* [n] or 
                             int search_flags, int divers /* W, 1..1024 */, int stall_events, int root_form, lpx_result* out,
                             lpx_bnb_bounded_info* info /* or NULL */, lpx_bnb_divers_info* dinfo /* or NULL */,
                             lpx_bnb_guard_info* ginfo /* or NULL */);
+
+/* ---- GMI cuts on a handle with bounds, and the cut loop at a bounded root (csrc/lpx_cuts.hip, csrc/lpx_tableau_bounded.cpp,
+ * DESIGN.md section 4.23) --------------------------------------------------------------------------------------------------
+ * An internal column of a bounded handle stands for x'_j = x_j - lo_j, or for ub_j - (x_j - lo_j) when it is flipped; x'_j >= 0
+ * and a nonbasic column sits at 0.  A GMI cut of a row in the internal variables needs no more than that and the integrality of
+ * the x'_j it treats as integer, so the arithmetic of lpx_tableau_gmi_round is valid on the internal representation as it stands,
+ * and the appended row is an ordinary equality row that every later bound edit, dualize flip and row complement re-expresses
+ * like any other.  Cuts derived under the root's bounds hold in the whole tree below it.
+ *
+ * lpx_tableau_gmi_round_bounded(t, is_int, n_mask, first_cut_col, o, n_added, src_rows, n_purged, purged_cols): the round of
+ *   lpx_tableau_gmi_round, bit for bit on the internal representation (candidates, ranking, alphas, dynamism filter, appended
+ *   rows, purge rule, new shape, outputs), with these differences:
+ *   - Column j is integer iff j < min(n_mask, first_cut_col), is_int[j] != 0, lo[j] == floor(lo[j]) and (ub[j] == +inf or
+ *     ub[j] == floor(ub[j])), with lo / ub the handle's (lpx_tableau_bound_state); decided on the device.  A flagged column with
+ *     a fractional bound is continuous; a handle without bounds passes every flagged column.  Source rows use the same notion
+ *     for their basic column.
+ *   - The bounds follow the reshape: surviving columns keep ub, lo and flip in order, every new slack gets ub = +inf, lo = 0,
+ *     flip = 0, and the shape the bounds belong to becomes the new C.  Every bounded entry point, lpx_tableau_clone and
+ *     lpx_tableau_snapshot / _restore accept the handle afterwards; the contiguous RHS copy the bounded kernels read is rewritten.
+ *   - cuts_per_round = 0 is allowed: a purge-only call.
+ *   Argument errors as lpx_tableau_gmi_round (cuts_per_round 0..64), plus bounds that were set for another live C
+ *   ("the live shape changed since lpx_tableau_set_bounds"): LPX_EINVAL before any device check, the handle untouched.
+ *
+ * lpx_bounded_cut_loop(t, is_int, n_mask, first_cut_col, nint, node_is_int, co, ro, flags, form, rec): rounds of cuts on a
+ *   solved (OPTIMAL) bounded handle with spare capacity.  is_int / n_mask / first_cut_col are the round's; nint / node_is_int
+ *   ([nint] or NULL = all) are the pick's (lpx_tableau_branch_pick, tol = co->int_tol).  Each round:
+ *     1. the pick of the tableau as it stands (round one: lpx_tableau_branch_pick; later: the pick of the last re-optimisation)
+ *        has var < 0 -> stop LPX_CUTLOOP_INTEGRAL;
+ *     2. rounds == co->max_rounds -> stop LPX_CUTLOOP_ROUNDS;
+ *     3. lpx_tableau_gmi_round_bounded; K == 0 -> stop LPX_CUTLOOP_STALLED (its purges are counted);
+ *     4. lpx_bounded_node3 with no bound edit (K = 0), flags | LPX_BDUAL_SKIP_FIXED, cutoff -inf (given only with
+ *        LPX_BDUAL_CUTOFF in flags), tol = co->int_tol, in `form` (LPX_NODE_AUTO: decided per round by lpx_bounded_node_fits;
+ *        both forms are bit-equal).  LPX_INFEASIBLE -> the integer program is infeasible, stop LPX_CUTLOOP_INFEASIBLE;
+ *        LPX_ITER_LIMIT -> stop LPX_CUTLOOP_ITER_LIMIT; any other status but LPX_OPTIMAL -> stop LPX_CUTLOOP_STATUS.
+ *   Then, if co->purge is set and the stop is none of INFEASIBLE / ITER_LIMIT / STATUS, one purge-only call (cuts_per_round = 0);
+ *   it needs no re-optimisation, a purged row has a basic slack.
+ *   rec: rounds = re-optimisations made; added / purged = cuts over all calls; events = events of the re-optimisations;
+ *   stop; status = the last re-optimisation's (LPX_OPTIMAL when there was none); R, C = the final live shape; pick = the pick of
+ *   the final tableau (z = T[m,Cm] in every case); z_before[i] / z_after[i] (each NULL or [co->max_rounds], the caller's) =
+ *   T[m,Cm] in front of and behind round i < rounds.  Returns 0, or LPX_ITER_LIMIT with the record filled.
+ *   LPX_EINVAL before any device check, the handle untouched: everything lpx_tableau_gmi_round_bounded and lpx_bounded_node3
+ *   refuse (flags outside LPX_BDUAL_LONG_STEP | LPX_BDUAL_CUTOFF | LPX_BDUAL_SKIP_FIXED, unknown form, LPX_NODE_ONCHIP on a
+ *   shape that does not fit or whose spare capacity min(Rcap - R, Ccap - C) added to R and C does not, nint outside [0, C-1],
+ *   ...), a NULL rec, a handle without bounds. */
+#define LPX_CUTLOOP_INTEGRAL   0
+#define LPX_CUTLOOP_STALLED    1
+#define LPX_CUTLOOP_ROUNDS     2
+#define LPX_CUTLOOP_INFEASIBLE 3
+#define LPX_CUTLOOP_ITER_LIMIT 4
+#define LPX_CUTLOOP_STATUS     5
+typedef struct lpx_cut_loop_record {
+    int32_t rounds, added, purged, stop;
+    int32_t status, R, C, pad;
+    int64_t events;
+    lpx_branch_pick pick;
+    double* z_before;       /* in: NULL or [max_rounds] */
+    double* z_after;        /* in: NULL or [max_rounds] */
+} lpx_cut_loop_record;
+int  lpx_tableau_gmi_round_bounded(lpx_tableau* t, const uint8_t* is_int, int n_mask, int first_cut_col,
+                                   const lpx_cut_opts* o, int* n_added, int32_t* src_rows /* [K] or NULL */,
+                                   int* n_purged, int32_t* purged_cols /* [C-1 - first_cut_col] or NULL */);
+int  lpx_bounded_cut_loop(lpx_tableau* t, const uint8_t* is_int, int n_mask, int first_cut_col, int nint,
+                          const uint8_t* node_is_int /* [nint] or NULL */, const lpx_cut_opts* co, const lpx_run_opts* ro /* or NULL */,
+                          int flags, int form, lpx_cut_loop_record* rec);
+
+/* lpx_solve_bnb_bounded9(p, lower, upper, is_int, o, max_nodes, search_flags, divers, stall_events, root_form, root_cuts, out, info,
+ *   dinfo, ginfo, cinfo): lpx_solve_bnb_bounded8 with cut-and-branch at the root.  root_cuts = NULL is lpx_solve_bnb_bounded8 bit
+ *   for bit (cinfo comes back zeroed).  Otherwise:
+ *   - The root handle is made with `a` spare rows and columns, a = the largest value <= root_cuts->max_active for which
+ *     (R + a, C + a) still satisfies lpx_bounded_node_fits; the round's free-capacity rule then keeps every later node on chip.
+ *     a = 0 runs no round (cinfo->ran = 0, cinfo->spare = 0) and the search is that of lpx_solve_bnb_bounded8.
+ *   - The round's flags: the structural is_int as given (NULL = all); the slack of prepared row i is integer iff every
+ *     coefficient of the row is integral, its shifted RHS is integral and every variable with a non-zero coefficient in it is
+ *     integer; an = row is a pair of rows and gives two slacks, judged alike.  first_cut_col = n_mask = C - 1.
+ *   - lpx_bounded_cut_loop(root handle, flags, C-1, C-1, n, is_int, root_cuts, the node options, search_flags, LPX_NODE_AUTO).
+ *     It ends LPX_CUTLOOP_INFEASIBLE: the result is LPX_INFEASIBLE with 0 nodes.  LPX_CUTLOOP_ITER_LIMIT: the call returns
+ *     LPX_ITER_LIMIT with 0 nodes.  LPX_CUTLOOP_INTEGRAL: the search still runs; its first node is the incumbent.  Otherwise the
+ *     search by W divers runs from the final handle: the clones are made after the loop, the root bounds are the model's, and
+ *     nothing else of the driver changes (cuts derived under the root's bounds hold in the whole tree).
+ *   cinfo (or NULL): ran, spare, the loop's rounds / added / purged / events / stop / status, the shape R x C the search runs on,
+ *   and z_before / z_after [n_z = rounds] (T[m,Cm] around every round, internal sense); free with lpx_bnb_cut_info_free.
+ *   Root cuts are defined for this driver alone: the sequential driver with node_form = LPX_NODE_LAUNCHES (lpx_solve_bnb_bounded3),
+ *   the plunge (lpx_solve_bnb_bounded5) and strong branching (lpx_solve_bnb_bounded6) have no root_cuts.  LPX_EINVAL before any
+ *   device check: everything lpx_solve_bnb_bounded8 refuses, and root_cuts outside the ranges of lpx_tableau_gmi_round
+ *   (cuts_per_round 1..64). */
+typedef struct lpx_bnb_cut_info {
+    int32_t ran, spare, rounds, added, purged, stop, status, R, C, n_z;
+    int64_t events;
+    double* z_before; double* z_after;      /* [n_z] */
+} lpx_bnb_cut_info;
+int  lpx_solve_bnb_bounded9(const lpx_problem* p, const double* lower /* [n] or NULL = 0 */, const double* upper /* [n] */,
+                            const uint8_t* is_int /* [n] or NULL = all */, const lpx_solve_opts* o, int64_t max_nodes /* 0 = none */,
+                            int search_flags, int divers /* W, 1..1024 */, int stall_events, int root_form,
+                            const lpx_cut_opts* root_cuts /* or NULL */, lpx_result* out, lpx_bnb_bounded_info* info /* or NULL */,
+                            lpx_bnb_divers_info* dinfo /* or NULL */, lpx_bnb_guard_info* ginfo /* or NULL */,
+                            lpx_bnb_cut_info* cinfo /* or NULL */);
+void lpx_bnb_cut_info_free(lpx_bnb_cut_info* cinfo);
 
 #ifdef __cplusplus
 }

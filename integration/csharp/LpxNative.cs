@@ -170,6 +170,26 @@ namespace Linear_Programming_Solver.Native
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct LpxCutLoopRecord        // lpx_cut_loop_record (lpx_bounded_cut_loop); z_before / z_after: the caller's [max_rounds] or null
+    {
+        public int rounds, added, purged, stop;
+        public int status, R, C, pad;
+        public long events;
+        public LpxBranchPick pick;
+        public double* z_before;
+        public double* z_after;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct LpxBnbCutInfo           // lpx_bnb_cut_info (lpx_solve_bnb_bounded9; free with lpx_bnb_cut_info_free)
+    {
+        public int ran, spare, rounds, added, purged, stop, status, R, C, n_z;
+        public long events;
+        public double* z_before;
+        public double* z_after;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public unsafe struct LpxBoundedInfo          // lpx_bounded_info  (lpx_solve_bounded; free with lpx_bounded_info_free)
     {
         public int ncols, n;
@@ -424,6 +444,21 @@ namespace Linear_Programming_Solver.Native
                                                         long max_nodes, int search_flags, int divers, int stall_events, int root_form,
                                                         out LpxResult result, out LpxBnbBoundedInfo info, out LpxBnbDiversInfo dinfo,
                                                         out LpxBnbGuardInfo ginfo);
+
+        // GMI cuts on a handle with bounds and cut-and-branch at the bounded root (include/lpx.h; lpx_cuts.hip).  LPX_CUTLOOP_*: 0 integral,
+        // 1 stalled, 2 rounds used up, 3 infeasible, 4 iteration limit, 5 another status.  rootCuts null: lpx_solve_bnb_bounded8 bit for bit
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_tableau_gmi_round_bounded(IntPtr t, byte* isInt, int nMask, int firstCutCol, ref LpxCutOpts o,
+                                                               out int nAdded, int* srcRows, out int nPurged, int* purgedCols);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_bounded_cut_loop(IntPtr t, byte* isInt, int nMask, int firstCutCol, int nint, byte* nodeIsInt,
+                                                      ref LpxCutOpts co, IntPtr opts, int flags, int form, ref LpxCutLoopRecord rec);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_bnb_bounded9(ref LpxProblem p, double* lower, double* upper, byte* is_int, ref LpxSolveOpts o,
+                                                        long max_nodes, int search_flags, int divers, int stall_events, int root_form,
+                                                        LpxCutOpts* root_cuts, out LpxResult result, out LpxBnbBoundedInfo info,
+                                                        out LpxBnbDiversInfo dinfo, out LpxBnbGuardInfo ginfo, out LpxBnbCutInfo cinfo);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern void lpx_bnb_cut_info_free(ref LpxBnbCutInfo cinfo);
 
         // ---- branch-and-bound node and child assembly on device handles, the parent store and the batched read-back, include/lpx.h ----
         // any of R / C / ld may be null

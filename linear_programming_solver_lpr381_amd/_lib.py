@@ -119,6 +119,23 @@ class NodeRecord(C.Structure):
                 ("flips", C.c_int64), ("unrepairable", C.c_int64), ("pick", BranchPick)]
 
 
+class CutLoopRecord(C.Structure):
+    """lpx_cut_loop_record (include/lpx.h): what one lpx_bounded_cut_loop call did; z_before / z_after are the caller's arrays."""
+    _fields_ = [("rounds", C.c_int32), ("added", C.c_int32), ("purged", C.c_int32), ("stop", C.c_int32),
+                ("status", C.c_int32), ("R", C.c_int32), ("C", C.c_int32), ("pad", C.c_int32), ("events", C.c_int64),
+                ("pick", BranchPick), ("z_before", dp), ("z_after", dp)]
+
+
+class BnbCutInfo(C.Structure):
+    """lpx_bnb_cut_info (include/lpx.h): the cut loop at the root of lpx_solve_bnb_bounded9 (freed by lpx_bnb_cut_info_free)."""
+    _fields_ = [("ran", C.c_int32), ("spare", C.c_int32), ("rounds", C.c_int32), ("added", C.c_int32), ("purged", C.c_int32),
+                ("stop", C.c_int32), ("status", C.c_int32), ("R", C.c_int32), ("C", C.c_int32), ("n_z", C.c_int32),
+                ("events", C.c_int64), ("z_before", dp), ("z_after", dp)]
+
+
+CUTLOOP_STOPS = ("integral", "stalled", "rounds", "infeasible", "iter_limit", "status")     # LPX_CUTLOOP_*
+
+
 class BnbNodeLog(C.Structure):
     """lpx_bnb_node_log (include/lpx.h): one node of lpx_solve_bnb_bounded."""
     _fields_ = [("depth", C.c_int32), ("K", C.c_int32), ("status", C.c_int32), ("events", C.c_int32),
@@ -315,6 +332,9 @@ def lib() -> C.CDLL:
     L.lpx_default_cut_opts.restype = None
     L.lpx_tableau_gmi_round.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.POINTER(CutOpts), C.POINTER(C.c_int), ip,
                                         C.POINTER(C.c_int), ip]
+    L.lpx_tableau_gmi_round_bounded.argtypes = L.lpx_tableau_gmi_round.argtypes
+    L.lpx_bounded_cut_loop.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(CutOpts),
+                                       C.POINTER(RunOpts), C.c_int, C.c_int, C.POINTER(CutLoopRecord)]
     L.lpx_solve_cuts.argtypes = [C.POINTER(Problem), C.POINTER(SolveOpts), C.POINTER(CutOpts), C.POINTER(Result)]
     L.lpx_tableau_rhs_update.argtypes = [vp, C.c_int, ip, dp]
     L.lpx_tableau_objective_update.argtypes = [vp, C.c_int, ip, dp, C.c_int, ip, dp]
@@ -407,6 +427,11 @@ def lib() -> C.CDLL:
     L.lpx_solve_bnb_bounded8.argtypes = [C.POINTER(Problem), dp, dp, u8p, C.POINTER(SolveOpts), C.c_int64, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.POINTER(Result), C.POINTER(BnbBoundedInfo), C.POINTER(BnbDiversInfo),
                                          C.POINTER(BnbGuardInfo)]
+    L.lpx_solve_bnb_bounded9.argtypes = [C.POINTER(Problem), dp, dp, u8p, C.POINTER(SolveOpts), C.c_int64, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.POINTER(CutOpts), C.POINTER(Result), C.POINTER(BnbBoundedInfo),
+                                         C.POINTER(BnbDiversInfo), C.POINTER(BnbGuardInfo), C.POINTER(BnbCutInfo)]
+    L.lpx_bnb_cut_info_free.argtypes = [C.POINTER(BnbCutInfo)]
+    L.lpx_bnb_cut_info_free.restype = None
     L.lpx_parse_text.argtypes = [C.c_char_p, C.POINTER(Parsed)]
     L.lpx_parsed_free.argtypes = [C.POINTER(Parsed)]
     L.lpx_parsed_free.restype = None

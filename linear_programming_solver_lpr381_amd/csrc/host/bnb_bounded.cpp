@@ -53,10 +53,10 @@ void ValidateBnbBounded(int n, const std::vector<double>& lower, const std::vect
 // which never changes and so decides for every node.  False: the root ends the search (an unbounded root is reported as that).
 bool SolveRoot(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper, const EngineOptions& opt,
                bool onchip, BoundedSession& ses, BoundedInfo& binfo, SimplexResult& res, BnbBoundedInfo& info,
-               BnbDiversInfo* dinfo = nullptr, BnbPlungeInfo* pinfo = nullptr, int root_form = -1)
+               BnbDiversInfo* dinfo = nullptr, BnbPlungeInfo* pinfo = nullptr, int root_form = -1, int max_spare = 0)
 {
     EngineOptions ropt = opt; ropt.quiet = true;
-    res = SolveBounded(original, lower, upper, ropt, nullptr, &binfo, &ses, root_form);
+    res = SolveBounded(original, lower, upper, ropt, nullptr, &binfo, &ses, root_form, max_spare);
     info = BnbBoundedInfo();
     if (dinfo) *dinfo = BnbDiversInfo();
     if (pinfo) *pinfo = BnbPlungeInfo();
@@ -260,8 +260,13 @@ SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<doubl
 SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
                              int search_flags, int divers, BnbDiversInfo& dinfo, const BnbStrong* strong, BnbStrongInfo* sinfo,
-                             int stall_events, BnbGuardInfo* ginfo, int root_form)
+                             int stall_events, BnbGuardInfo* ginfo, int root_form, const lpx_cut_opts* root_cuts, BnbCutInfo* cinfo)
 {
+    // root_cuts != null (lpx_solve_bnb_bounded9): the root's handle gets spare capacity, lpx_bounded_cut_loop runs on it, and the
+    // divers start from the handle the loop leaves; nothing else of the search changes (the cuts hold in the whole tree).
+    BnbCutInfo cdummy;
+    BnbCutInfo& ci = cinfo ? *cinfo : cdummy;
+    ci = BnbCutInfo();
     // stall_events >= 0 (lpx_solve_bnb_bounded7): the evaluate step is ONE lpx_node_batch_run2, which with 0 is lpx_node_batch_run;
     // the guard records are counted and nothing else of the search reads them.
     BnbGuardInfo gdummy;
@@ -283,7 +288,48 @@ SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double
     BoundedSession ses;
     BoundedInfo binfo;
     SimplexResult res;
-    if (!SolveRoot(original, lower, upper, opt, true, ses, binfo, res, info, &dinfo, nullptr, root_form)) return res;
+    if (!SolveRoot(original, lower, upper, opt, true, ses, binfo, res, info, &dinfo, nullptr, root_form, root_cuts ? root_cuts->max_active : 0))
+        return res;
+
+    lpx_run_opts o; lpx_default_opts(&o, 1);
+    o.max_iter = opt.max_iter;
+    const uint8_t* mask = is_int.empty() ? nullptr : is_int.data();
+    double best = -1.0 / 0.0;
+    std::vector<double> best_x;
+
+    ci.spare = ses.spare;
+    if (root_cuts && ses.spare > 0) {
+        // the round's flags: the structural ones as given; the slack of prepared row i is integer iff its coefficients and its
+        // shifted RHS are integral and every variable with a non-zero coefficient is integer (an = pair: two rows, judged alike)
+        const int R = ses.R, C = ses.C, m = R - 1;
+        std::vector<uint8_t> flags((size_t)(C - 1), 0);
+        for (int j = 0; j < n; ++j) flags[j] = (is_int.empty() || is_int[j]) ? 1 : 0;
+        for (int i = 0; i < m; ++i) {
+            const double* row = ses.T0.data() + (size_t)i * C;
+            bool whole = std::floor(row[C - 1]) == row[C - 1];
+            for (int j = 0; j < n && whole; ++j) whole = std::floor(row[j]) == row[j] && (row[j] == 0.0 || flags[j]);
+            flags[n + i] = whole ? 1 : 0;
+        }
+        lpx_cut_loop_record rec; std::memset(&rec, 0, sizeof(rec));
+        ci.z_before.assign((size_t)std::max(root_cuts->max_rounds, 1), 0.0); ci.z_after = ci.z_before;
+        rec.z_before = ci.z_before.data(); rec.z_after = ci.z_after.data();
+        const int rc = lpx_bounded_cut_loop(ses.h, flags.data(), C - 1, C - 1, n, mask, root_cuts, &o, search_flags, LPX_NODE_AUTO, &rec);
+        if (rc < 0) throw_lib(rc);
+        ci.ran = 1; ci.rounds = rec.rounds; ci.added = rec.added; ci.purged = rec.purged; ci.stop = rec.stop; ci.status = rec.status;
+        ci.R = rec.R; ci.C = rec.C; ci.events = rec.events;
+        ci.z_before.resize((size_t)rec.rounds); ci.z_after.resize((size_t)rec.rounds);
+        if (rec.stop == LPX_CUTLOOP_ITER_LIMIT) {
+            info.limit_rc = LPX_ITER_LIMIT;
+            info.limit_msg = "Bounded Branch and Bound: cut round " + std::to_string(rec.rounds) + " at the root reached the iteration limit of " +
+                             std::to_string(o.max_iter) + " events";
+        }
+        // INFEASIBLE: a cut of the root LP's own rows leaves no point, so the integer program has none: no node is searched
+        if (rec.stop == LPX_CUTLOOP_INFEASIBLE || rec.stop == LPX_CUTLOOP_ITER_LIMIT || rec.stop == LPX_CUTLOOP_STATUS)
+            return FinishBnbResult(std::move(res), info, ses, n, best, best_x);
+    } else if (root_cuts) {
+        ci.z_before.clear(); ci.z_after.clear();
+        lpx_tableau_shape(ses.h, &ci.R, &ci.C, nullptr);
+    }
 
     const int W = divers;
     Pool pool;
@@ -293,12 +339,6 @@ SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double
     std::vector<Diver> dv((size_t)W);
     for (Diver& d : dv) { d.cur_lo = root_lo; d.cur_ub = root_ub; }
     dv[0].stack.push_back(Node{0, {}});
-    lpx_run_opts o; lpx_default_opts(&o, 1);
-    o.max_iter = opt.max_iter;
-    const uint8_t* mask = is_int.empty() ? nullptr : is_int.data();
-
-    double best = -1.0 / 0.0;
-    std::vector<double> best_x;
     std::vector<int32_t> slot, Ks, cols, rcs((size_t)W); std::vector<double> clo, cub, cutoffs;
     std::vector<lpx_node_record> recs((size_t)W);
     std::vector<double> prunes; std::vector<lpx_probe_head> heads; std::vector<lpx_probe_record> probes;       // strong branching only

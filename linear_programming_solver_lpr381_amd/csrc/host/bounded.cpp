@@ -21,10 +21,21 @@ void CheckVarBounds(const std::string& var, double lower, double upper)
 namespace {
 
 struct BoundedHandle {
-    lpx_tableau* h = nullptr; int R, C;
-    BoundedHandle(int R_, int C_) : R(R_), C(C_) { h = acquire_exact_handle(R, C); }
-    // the handle goes back to a cache shared with the other solvers: without its bounds
-    ~BoundedHandle() { if (!h) return; lpx_tableau_set_bounds(h, 0, nullptr); release_exact_handle(h, R, C); }
+    lpx_tableau* h = nullptr; int R, C, spare;  // R x C: the capacity the handle was made with
+    // spare > 0: capacity (R_ + spare, C_ + spare) around a live R_ x C_ window
+    BoundedHandle(int R_, int C_, int spare_ = 0) : R(R_ + spare_), C(C_ + spare_), spare(spare_)
+    {
+        h = acquire_exact_handle(R, C);
+        if (spare > 0) { const int rc = lpx_tableau_set_shape(h, R_, C_); if (rc) { release_exact_handle(h, R, C); h = nullptr; throw_lib(rc); } }
+    }
+    // the handle goes back to a cache shared with the other solvers: without its bounds, its live shape the capacity
+    ~BoundedHandle()
+    {
+        if (!h) return;
+        lpx_tableau_set_bounds(h, 0, nullptr);
+        if (spare > 0) lpx_tableau_set_shape(h, R, C);
+        release_exact_handle(h, R, C);
+    }
     lpx_tableau* take() { lpx_tableau* k = h; h = nullptr; return k; }          // a session keeps it
     BoundedHandle(const BoundedHandle&) = delete;
 };
@@ -86,7 +97,8 @@ BoundedSession::~BoundedSession()
 {
     if (!h) return;
     lpx_tableau_set_bounds(h, 0, nullptr);          // the handle goes back to the shared cache without its bounds
-    release_exact_handle(h, R, C);
+    if (spare > 0) lpx_tableau_set_shape(h, R + spare, C + spare);      // ... and with the shape it was made with
+    release_exact_handle(h, R + spare, C + spare);
 }
 
 namespace {
@@ -176,7 +188,7 @@ void finish_solve(lpx_tableau* h, int st, const LPProblem& original, const std::
 }  // namespace
 
 SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
-                           const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info, BoundedSession* keep, int form)
+                           const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info, BoundedSession* keep, int form, int max_spare)
 {
     const int n = original.NumVars();
     if (form != -1 && form != LPX_NODE_LAUNCHES && form != LPX_NODE_ONCHIP && form != LPX_NODE_AUTO)
@@ -194,8 +206,11 @@ SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>&
                                        " tableau does not fit the on-chip form (lpx_bounded_node_fits)");
     const bool onchip = form == LPX_NODE_ONCHIP || (form == LPX_NODE_AUTO && fits && !updatePivot);
 
+    int spare = keep ? max_spare : 0;
+    while (spare > 0 && !lpx_bounded_node_fits(R + spare, C + spare)) --spare;
+
     SimplexResult res;
-    BoundedHandle th(R, C);
+    BoundedHandle th(R, C, spare);
     int rc = lpx_tableau_upload(th.h, P.T.data(), P.basis.data());
     if (rc) throw_lib(rc);
     if (bounded) { rc = lpx_tableau_set_bounds(th.h, C - 1, P.ub.data()); if (rc) throw_lib(rc); }
@@ -210,6 +225,8 @@ SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>&
         keep->h = th.take(); keep->R = R; keep->C = C; keep->n = n;
         keep->min = original.ObjectiveSense == Sense::Min; keep->shifted = P.shifted; keep->constant = P.constant;
         keep->lower = lower; keep->open_status = st; keep->opt = opt; keep->varNames = P.varNames;
+        keep->spare = spare;
+        if (max_spare > 0) keep->T0 = P.T;
     }
     return res;
 }

@@ -223,13 +223,17 @@ struct BoundedSession {
     bool min = false, shifted = false; double constant = 0.0;      // objective sense, and the constant c.l of open's shift
     std::vector<double> lower;                                      // open's lower bounds (empty = none): the host-side shift
     int open_status = -1; EngineOptions opt; std::vector<std::string> varNames;
+    int spare = 0;                                                  // rows and columns of capacity beyond R x C (SolveBounded's max_spare)
+    std::vector<double> T0;                                         // with max_spare > 0: the prepared tableau [R * C], for the slack flags of the cut rounds
     BoundedSession() = default;
     BoundedSession(const BoundedSession&) = delete;
     ~BoundedSession();
 };
 SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
                            const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info, BoundedSession* keep = nullptr,
-                           int form = -1);             // lpx_solve_bounded2: LPX_NODE_* of the loop (lpx_bounded_run2); -1: lpx_bounded_run
+                           int form = -1,              // lpx_solve_bounded2: LPX_NODE_* of the loop (lpx_bounded_run2); -1: lpx_bounded_run
+                           int max_spare = 0);         // with keep: the handle gets the largest a <= max_spare spare rows and columns for which
+                                                       // (R + a, C + a) still satisfies lpx_bounded_node_fits (keep->spare = a)
 // count independent models in ONE lpx_node_batch_primal launch (lpx_solve_bounded_batch); an error names its model ("model i: ")
 void SolveBoundedBatch(const std::vector<const LPProblem*>& problems, const std::vector<std::vector<double>>& lowers,
                        const std::vector<std::vector<double>>& uppers, const EngineOptions& opt, std::vector<SimplexResult>& results,
@@ -259,6 +263,9 @@ struct BnbDiversInfo { int64_t rounds = 0, steals = 0, largest_batch = 0; std::v
 struct BnbStrong { int cand_max = 4, probe_iter = 0; };
 // The stall guard (lpx_solve_bnb_bounded7): nodes with a pivot in Bland mode, those pivots, the most events of one node.
 struct BnbGuardInfo { int64_t guarded_nodes = 0, bland_events = 0, max_events = 0; };
+// The cut loop at the root (lpx_solve_bnb_bounded9): the loop's record; ran = 0 with spare = 0 (no capacity that keeps the nodes on chip).
+struct BnbCutInfo { int ran = 0, spare = 0, rounds = 0, added = 0, purged = 0, stop = 0, status = 0, R = 0, C = 0; int64_t events = 0;
+                    std::vector<double> z_before, z_after; };
 struct BnbStrongInfo { int64_t probe_launches = 0, probes = 0, probe_events = 0, probe_limit = 0, pruned_by_probe = 0, changed_picks = 0; };
 SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
@@ -266,7 +273,9 @@ SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double
                              struct BnbStrongInfo* sinfo = nullptr,
                              int stall_events = -1,       // lpx_solve_bnb_bounded7: >= 0, the round is ONE lpx_node_batch_run2 (never with strong)
                              struct BnbGuardInfo* ginfo = nullptr,
-                             int root_form = -1);         // lpx_solve_bnb_bounded8: LPX_NODE_* of the root solve; -1: lpx_bounded_run
+                             int root_form = -1,          // lpx_solve_bnb_bounded8: LPX_NODE_* of the root solve; -1: lpx_bounded_run
+                             const lpx_cut_opts* root_cuts = nullptr,     // lpx_solve_bnb_bounded9: lpx_bounded_cut_loop at the root, the divers start from its handle
+                             struct BnbCutInfo* cinfo = nullptr);
 // The search by W divers that plunge (lpx_solve_bnb_bounded5): one lpx_node_batch_plunge per round, up to `plunge` nodes per diver.
 struct BnbPlungeInfo { int64_t launched = 0, dropped = 0, longest_chain = 0; std::vector<int32_t> step; };
 SimplexResult SolveBnbPlunge(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,

@@ -13,6 +13,17 @@
 //              K cut rows at that column (it reads old row m before it writes cut row 0 over it); one thread per old row
 //              owns that row's tail (K new zero slack entries and the moved RHS), one thread the tails of the new rows.
 //              With purges: one compacting pass into the handle's second tableau buffer, copied back by the host.
+//
+// The round on a handle with bounds (lpx_tableau_gmi_round_bounded) is the same three launches on the internal representation,
+// between two small ones of its own:
+//   gmi_mask_bounded   in front: the round's integer array from the caller's flags and the handle's lo / ub (a flagged column
+//                      with a fractional bound is continuous).
+//   gmi_carry_inplace  behind gmi_apply_inplace: the ub / lo / flip tails of the K new slacks and the contiguous copy of the new
+//                      RHS column (rhsbuf); it writes only entries no earlier launch of the round has read.
+//   gmi_carry_purge    behind gmi_apply_purge: ub / lo / flip gathered through the plan's column map into staging and the RHS
+//                      column of the second buffer into rhsbuf; the host copies the staging back.
+// They hold to the shared-device rules at the head of lpx_bounded_primal.hip: no workgroup waits on another, every loop is bounded
+// by R or Ccap, plain vector stores, no scratch (resource remarks: DESIGN.md section 4.23).
 #include "lpx_append.h"
 #include "lpx_block.h"
 
@@ -320,6 +331,52 @@ __global__ __launch_bounds__(GA_NT) void gmi_apply_purge(const double* __restric
     }
 }
 
+// ---- the round on a handle with bounds -----------------------------------------------------------------------------------
+// isint[j] for j < Cm: flagged (flags[j], j < nint) and both bounds of the column whole.  lo == nullptr: a handle without bounds.
+__global__ __launch_bounds__(GA_NT) void gmi_mask_bounded(int Cm, int nint, const uint8_t* __restrict__ flags,
+                                                          const double* __restrict__ lo, const double* __restrict__ ub,
+                                                          uint8_t* __restrict__ isint)
+{
+    const int j = blockIdx.x * GA_NT + threadIdx.x;
+    if (j >= Cm) return;
+    bool whole = j < nint && flags[j] != 0;
+    if (whole && lo) {
+        const double l = lo[j], u = ub[j];
+        whole = l == floor(l) && (u == __builtin_inf() || u == floor(u));
+    }
+    isint[j] = whole ? 1 : 0;
+}
+
+// In place: new slack k < K is column Cm + k (Cm + K <= Ccap - 1 by the round's capacity rule); rhsbuf[i] = new T[i, Cm + K].
+__global__ __launch_bounds__(GA_NT) void gmi_carry_inplace(const double* __restrict__ T, int ld, int R2, int Cm,
+                                                           const GmiPlan* __restrict__ plan, double* __restrict__ ub,
+                                                           double* __restrict__ lo, uint8_t* __restrict__ flip,
+                                                           double* __restrict__ rhsbuf)
+{
+    const int K = plan->K;
+    const int i = blockIdx.x * GA_NT + threadIdx.x;
+    if (i < K) { ub[Cm + i] = __builtin_inf(); lo[Cm + i] = 0.0; flip[Cm + i] = 0; }
+    if (i < R2) rhsbuf[i] = T[(size_t)i * ld + Cm + K];
+}
+
+// With purges: entry j < Ccap of the staging arrays from the column map (a new slack, the RHS column and everything beyond the
+// new live shape: unbounded, unshifted, unflipped); rhsbuf[i] = T2[i, C2 - 1].
+__global__ __launch_bounds__(GA_NT) void gmi_carry_purge(const double* __restrict__ T2, int ld, int R2, int C2, int Ccap,
+                                                         const int32_t* __restrict__ colsrc, const double* __restrict__ ub,
+                                                         const double* __restrict__ lo, const uint8_t* __restrict__ flip,
+                                                         double* __restrict__ ub2, double* __restrict__ lo2,
+                                                         uint8_t* __restrict__ flip2, double* __restrict__ rhsbuf)
+{
+    const int j = blockIdx.x * GA_NT + threadIdx.x;
+    if (j < Ccap) {
+        const int c = j < C2 - 1 ? colsrc[j] : -1;
+        ub2[j] = c >= 0 ? ub[c] : __builtin_inf();
+        lo2[j] = c >= 0 ? lo[c] : 0.0;
+        flip2[j] = c >= 0 ? flip[c] : 0;
+    }
+    if (j < R2) rhsbuf[j] = T2[(size_t)j * ld + C2 - 1];
+}
+
 namespace {
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -337,11 +394,11 @@ int gm_workspace(const CutView& v, size_t bytes, char** ws)
 }
 }  // namespace
 
-int check_cut_opts(const lpx_cut_opts* o, const char* what)
+int check_cut_opts(const lpx_cut_opts* o, const char* what, int kmin)
 {
     if (!o) { set_error(std::string(what) + ": null options"); return LPX_EINVAL; }
     const char* bad = nullptr;
-    if (o->cuts_per_round < 1 || o->cuts_per_round > GMI_KMAX) bad = "cuts_per_round must be in 1..64";
+    if (o->cuts_per_round < kmin || o->cuts_per_round > GMI_KMAX) bad = kmin ? "cuts_per_round must be in 1..64" : "cuts_per_round must be in 0..64";
     else if (o->max_rounds < 0) bad = "max_rounds must be >= 0";
     else if (o->max_active < 1) bad = "max_active must be >= 1";
     else if (!(o->away > 0 && o->away <= 0.5)) bad = "away must be in (0, 0.5]";
@@ -353,25 +410,11 @@ int check_cut_opts(const lpx_cut_opts* o, const char* what)
     return 0;
 }
 
-}  // namespace lpx
+int check_cut_opts(const lpx_cut_opts* o, const char* what) { return check_cut_opts(o, what, 1); }
 
-using namespace lpx;
-
-extern "C" {
-
-void lpx_default_cut_opts(lpx_cut_opts* o)
+int gmi_round_args(lpx_tableau* t, const uint8_t* is_int, int n_mask, int first_cut_col, const lpx_cut_opts* o, int kmin, const char* what)
 {
-    if (!o) return;
-    std::memset(o, 0, sizeof(*o));
-    o->cuts_per_round = 8; o->max_rounds = 50; o->max_active = 64; o->purge = 1;
-    o->away = 1e-3; o->coef_eps = 1e-9; o->max_dynamism = 1e6; o->purge_tol = 1e-9; o->int_tol = 1e-6;
-}
-
-int lpx_tableau_gmi_round(lpx_tableau* t, const uint8_t* is_int, int n_mask, int first_cut_col,
-                          const lpx_cut_opts* o, int* n_added, int32_t* src_rows, int* n_purged, int32_t* purged_cols)
-{
-    static const char* what = "lpx_tableau_gmi_round";
-    if (int rc = check_cut_opts(o, what)) return rc;
+    if (int rc = check_cut_opts(o, what, kmin)) return rc;
     if (n_mask < 0 || (n_mask > 0 && !is_int)) { set_error(std::string(what) + ": bad integer mask"); return LPX_EINVAL; }
     if (!t) { set_error(std::string(what) + ": null handle"); return LPX_EINVAL; }
     CutView v;
@@ -381,6 +424,18 @@ int lpx_tableau_gmi_round(lpx_tableau* t, const uint8_t* is_int, int n_mask, int
     if (first_cut_col < 1 || first_cut_col > Cm) { set_error(std::string(what) + ": first_cut_col outside [1, C-1]"); return LPX_EINVAL; }
     if (Cm - first_cut_col > GMI_PMAX) { set_error(std::string(what) + ": more than 2048 cut columns"); return LPX_EINVAL; }
     if (v.Ccap > GMI_CMAX) { set_error(std::string(what) + ": handle wider than 131072 columns"); return LPX_EINVAL; }
+    return 0;
+}
+
+// The round of both entry points behind their argument checks.  cb == nullptr: lpx_tableau_gmi_round.  Else the bounded round: the
+// integer array from cb's lo / ub (either null: a handle without bounds, every flagged column passes) and, where cb->ub is set,
+// ub / lo / flip and rhsbuf carried to the new shape.
+int gmi_round_run(lpx_tableau* t, const uint8_t* is_int, int n_mask, int first_cut_col, const lpx_cut_opts* o, int* n_added,
+                  int32_t* src_rows, int* n_purged, int32_t* purged_cols, const CutBounds* cb, const char* what)
+{
+    CutView v;
+    tableau_cut_view(t, &v, false);
+    const int m = v.R - 1, Cm = v.C - 1;
     if (int rc = ensure_device()) return rc;
     if (n_added) *n_added = 0;
     if (n_purged) *n_purged = 0;
@@ -389,7 +444,8 @@ int lpx_tableau_gmi_round(lpx_tableau* t, const uint8_t* is_int, int n_mask, int
     const size_t b_plan = up256(sizeof(GmiPlan)), b_i = up256(sizeof(int32_t) * Rc), b_d = up256(sizeof(double) * Rc);
     const size_t b_cu8 = up256(Cc), b_ci = up256(sizeof(int32_t) * Cc);
     char* ws = nullptr;
-    if (int rc = gm_workspace(v, b_plan + 3 * b_i + 4 * b_d + 2 * b_cu8 + 2 * b_ci, &ws)) return rc;
+    const size_t b_cd = up256(sizeof(double) * Cc);
+    if (int rc = gm_workspace(v, b_plan + 3 * b_i + 4 * b_d + 2 * b_cu8 + 2 * b_ci + (cb ? 2 * b_cu8 + 2 * b_cd : 0), &ws)) return rc;
     GmiPlan* plan = (GmiPlan*)ws; ws += b_plan;
     int32_t* flag = (int32_t*)ws; ws += b_i;
     int32_t* rowsrc = (int32_t*)ws; ws += b_i;
@@ -401,12 +457,19 @@ int lpx_tableau_gmi_round(lpx_tableau* t, const uint8_t* is_int, int n_mask, int
     uint8_t* isint = (uint8_t*)ws; ws += b_cu8;
     uint8_t* nbm = (uint8_t*)ws; ws += b_cu8;
     int32_t* colsrc = (int32_t*)ws; ws += b_ci;
-    int32_t* pcol = (int32_t*)ws;
+    int32_t* pcol = (int32_t*)ws; ws += b_ci;
+    uint8_t* flags = nullptr; uint8_t* flip2 = nullptr; double* ub2 = nullptr; double* lo2 = nullptr;     // the bounded round's
+    if (cb) { flags = (uint8_t*)ws; ws += b_cu8; flip2 = (uint8_t*)ws; ws += b_cu8; ub2 = (double*)ws; ws += b_cd; lo2 = (double*)ws; }
 
     const int nint = n_mask < first_cut_col ? n_mask : first_cut_col;
     std::vector<uint8_t> hint((size_t)Cm, 0);
     for (int j = 0; j < nint; ++j) hint[j] = is_int[j] ? 1 : 0;
-    LPX_HIP_TRY(hipMemcpyAsync(isint, hint.data(), (size_t)Cm, hipMemcpyHostToDevice, v.stream));
+    LPX_HIP_TRY(hipMemcpyAsync(cb ? flags : isint, hint.data(), (size_t)Cm, hipMemcpyHostToDevice, v.stream));
+    if (cb) {
+        hipLaunchKernelGGL(gmi_mask_bounded, dim3((unsigned)((Cm + GA_NT - 1) / GA_NT)), dim3(GA_NT), 0, v.stream, Cm, nint, flags,
+                           cb->ub ? cb->lo : nullptr, cb->ub, isint);
+        LPX_HIP_TRY(hipGetLastError());
+    }
 
     GmiParams g;
     g.away = o->away; g.coef_eps = o->coef_eps; g.max_dyn = o->max_dynamism; g.purge_tol = o->purge_tol;
@@ -432,6 +495,12 @@ int lpx_tableau_gmi_round(lpx_tableau* t, const uint8_t* is_int, int n_mask, int
         hipLaunchKernelGGL(gmi_apply_inplace, dim3((unsigned)(ncb + ntb)), dim3(GA_NT), 0, v.stream, v.T, v.ld, m, Cm, ncb,
                            plan, nbm, isint, nbasis, v.basis, o->coef_eps);
         LPX_HIP_TRY(hipGetLastError());
+        if (cb && cb->ub) {
+            const int n = hp.R2 > hp.K ? hp.R2 : hp.K;
+            hipLaunchKernelGGL(gmi_carry_inplace, dim3((unsigned)((n + GA_NT - 1) / GA_NT)), dim3(GA_NT), 0, v.stream, v.T, v.ld, hp.R2,
+                               Cm, plan, cb->ub, cb->lo, cb->flip, cb->rhsbuf);
+            LPX_HIP_TRY(hipGetLastError());
+        }
     } else {
         tableau_cut_view(t, &v, true);
         if (!v.T2) { set_error(std::string(what) + ": no device memory for the compacting pass"); return LPX_ENOMEM; }
@@ -440,6 +509,15 @@ int lpx_tableau_gmi_round(lpx_tableau* t, const uint8_t* is_int, int n_mask, int
         hipLaunchKernelGGL(gmi_apply_purge, dim3((unsigned)gx, (unsigned)gy), dim3(GA_NT), 0, v.stream, v.T, v.T2, v.ld, Cm,
                            hp.R2, hp.C2, plan, rowsrc, colsrc, nbm, isint, nbasis, v.basis, o->coef_eps);
         LPX_HIP_TRY(hipGetLastError());
+        if (cb && cb->ub) {
+            const int n = hp.R2 > v.Ccap ? hp.R2 : v.Ccap;
+            hipLaunchKernelGGL(gmi_carry_purge, dim3((unsigned)((n + GA_NT - 1) / GA_NT)), dim3(GA_NT), 0, v.stream, v.T2, v.ld, hp.R2,
+                               hp.C2, v.Ccap, colsrc, cb->ub, cb->lo, cb->flip, ub2, lo2, flip2, cb->rhsbuf);
+            LPX_HIP_TRY(hipGetLastError());
+            LPX_HIP_TRY(hipMemcpyAsync(cb->ub, ub2, sizeof(double) * Cc, hipMemcpyDeviceToDevice, v.stream));
+            LPX_HIP_TRY(hipMemcpyAsync(cb->lo, lo2, sizeof(double) * Cc, hipMemcpyDeviceToDevice, v.stream));
+            LPX_HIP_TRY(hipMemcpyAsync(cb->flip, flip2, Cc, hipMemcpyDeviceToDevice, v.stream));
+        }
         LPX_HIP_TRY(hipMemcpyAsync(v.T, v.T2, sizeof(double) * (size_t)hp.R2 * v.ld, hipMemcpyDeviceToDevice, v.stream));
     }
     LPX_HIP_TRY(hipStreamSynchronize(v.stream));
@@ -451,6 +529,28 @@ int lpx_tableau_gmi_round(lpx_tableau* t, const uint8_t* is_int, int n_mask, int
     if (n_purged) *n_purged = hp.P;
     if (purged_cols) for (int i = 0; i < hp.P; ++i) purged_cols[i] = hpc[i];
     return 0;
+}
+
+}  // namespace lpx
+
+using namespace lpx;
+
+extern "C" {
+
+void lpx_default_cut_opts(lpx_cut_opts* o)
+{
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->cuts_per_round = 8; o->max_rounds = 50; o->max_active = 64; o->purge = 1;
+    o->away = 1e-3; o->coef_eps = 1e-9; o->max_dynamism = 1e6; o->purge_tol = 1e-9; o->int_tol = 1e-6;
+}
+
+int lpx_tableau_gmi_round(lpx_tableau* t, const uint8_t* is_int, int n_mask, int first_cut_col,
+                          const lpx_cut_opts* o, int* n_added, int32_t* src_rows, int* n_purged, int32_t* purged_cols)
+{
+    static const char* what = "lpx_tableau_gmi_round";
+    if (int rc = gmi_round_args(t, is_int, n_mask, first_cut_col, o, 1, what)) return rc;
+    return gmi_round_run(t, is_int, n_mask, first_cut_col, o, n_added, src_rows, n_purged, purged_cols, nullptr, what);
 }
 
 }  // extern "C"

@@ -322,6 +322,14 @@ struct CutView {
 };
 void tableau_cut_view(lpx_tableau* t, CutView* v, bool need_second);
 int check_cut_opts(const lpx_cut_opts* o, const char* what);   // LPX_EINVAL (message set) when o is outside its ranges
+int check_cut_opts(const lpx_cut_opts* o, const char* what, int kmin);     // ... with cuts_per_round in kmin..64 (the call above: 1)
+// The cut round behind lpx_tableau_gmi_round and lpx_tableau_gmi_round_bounded (lpx_cuts.hip).  gmi_round_args: every argument
+// check of include/lpx.h, no device touched.  gmi_round_run: the round; cb == nullptr is the plain round, else the bounded one on
+// the handle's bound arrays (all null: a handle without bounds) and its contiguous RHS copy.
+struct CutBounds { double* ub; double* lo; uint8_t* flip; double* rhsbuf; };
+int gmi_round_args(lpx_tableau* t, const uint8_t* is_int, int n_mask, int first_cut_col, const lpx_cut_opts* o, int kmin, const char* what);
+int gmi_round_run(lpx_tableau* t, const uint8_t* is_int, int n_mask, int first_cut_col, const lpx_cut_opts* o, int* n_added,
+                  int32_t* src_rows, int* n_purged, int32_t* purged_cols, const CutBounds* cb, const char* what);
 
 void set_error(const std::string& msg);
 // Device memory the library keeps for reuse after its owner is gone (the chunk cache of destroyed parent stores, lpx_tableau_nodes.cpp):

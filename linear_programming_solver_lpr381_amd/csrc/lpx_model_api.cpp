@@ -419,7 +419,8 @@ static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const do
                             int plunge = 0, lpx_bnb_plunge_info* pinfo = nullptr,                         // plunge > 0: lpx_solve_bnb_bounded5
                             const BnbStrong* strong = nullptr, lpx_bnb_strong_info* sinfo = nullptr,      // strong: lpx_solve_bnb_bounded6, LPX_BRANCH_STRONG
                             int stall_events = -1, lpx_bnb_guard_info* ginfo = nullptr,                   // stall_events >= 0: lpx_solve_bnb_bounded7
-                            int root_form = -1)                                                           // lpx_solve_bnb_bounded8: the root's form
+                            int root_form = -1,                                                           // lpx_solve_bnb_bounded8: the root's form
+                            const lpx_cut_opts* root_cuts = nullptr, lpx_bnb_cut_info* cinfo = nullptr)   // lpx_solve_bnb_bounded9: cuts at the root
 {
     if (!p || !out) { set_error(std::string(what) + ": null argument"); return LPX_EINVAL; }
     std::memset(out, 0, sizeof(*out));
@@ -428,12 +429,14 @@ static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const do
     if (pinfo) std::memset(pinfo, 0, sizeof(*pinfo));
     if (sinfo) std::memset(sinfo, 0, sizeof(*sinfo));
     if (ginfo) std::memset(ginfo, 0, sizeof(*ginfo));
+    if (cinfo) std::memset(cinfo, 0, sizeof(*cinfo));
     lpx_solve_opts d; if (!o) { lpx_default_solve_opts(&d); o = &d; }
     return guarded(what, [&]() -> int {
         EngineOptions e = to_engine(o);
         LPProblem q = to_problem(p);
         std::vector<double> lo, up;
         std::vector<uint8_t> mask;
+        BnbCutInfo ci;
         if (lower) lo.assign(lower, lower + p->n);
         if (upper) up.assign(upper, upper + p->n);
         if (is_int) mask.assign(is_int, is_int + p->n);
@@ -442,12 +445,19 @@ static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const do
         BnbPlungeInfo pi;
         BnbStrongInfo si;
         BnbGuardInfo gi;
-        SimplexResult r = stall_events >= 0 ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di, nullptr, nullptr, stall_events, &gi, root_form)
+        SimplexResult r = stall_events >= 0 ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di, nullptr, nullptr, stall_events, &gi, root_form,
+                                                             root_cuts, &ci)
                         : strong ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di, strong, &si)
                         : plunge ? SolveBnbPlunge(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, plunge, di, pi)
                         : divers ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di)
                                  : SolveBnbBounded(q, lo, up, mask, e, max_nodes, bi, search_flags, node_form);
         fill_result(out, r, p->n);
+        if (cinfo) {
+            cinfo->ran = ci.ran; cinfo->spare = ci.spare; cinfo->rounds = ci.rounds; cinfo->added = ci.added; cinfo->purged = ci.purged;
+            cinfo->stop = ci.stop; cinfo->status = ci.status; cinfo->R = ci.R; cinfo->C = ci.C; cinfo->events = ci.events;
+            cinfo->n_z = (int32_t)ci.z_before.size();
+            cinfo->z_before = dup_vec(ci.z_before); cinfo->z_after = dup_vec(ci.z_after);
+        }
         if (ginfo) { ginfo->guarded_nodes = gi.guarded_nodes; ginfo->bland_events = gi.bland_events; ginfo->max_events = gi.max_events; }
         if (sinfo) {
             sinfo->probe_launches = si.probe_launches; sinfo->probes = si.probes; sinfo->probe_events = si.probe_events;
@@ -553,6 +563,30 @@ int lpx_solve_bnb_bounded8(const lpx_problem* p, const double* lower, const doub
     // LPX_NODE_LAUNCHES: the call of lpx_solve_bnb_bounded7 itself (the root through lpx_bounded_run)
     return solve_bnb_bounded(p, lower, upper, is_int, o, max_nodes, search_flags, out, info, "lpx_solve_bnb_bounded8", -1, divers, dinfo,
                              0, nullptr, nullptr, nullptr, stall_events, ginfo, root_form == LPX_NODE_LAUNCHES ? -1 : root_form);
+}
+
+int lpx_solve_bnb_bounded9(const lpx_problem* p, const double* lower, const double* upper, const uint8_t* is_int,
+                           const lpx_solve_opts* o, int64_t max_nodes, int search_flags, int divers, int stall_events, int root_form,
+                           const lpx_cut_opts* root_cuts, lpx_result* out, lpx_bnb_bounded_info* info, lpx_bnb_divers_info* dinfo,
+                           lpx_bnb_guard_info* ginfo, lpx_bnb_cut_info* cinfo)
+{
+    if (divers < 1 || divers > 1024) { set_error("lpx_solve_bnb_bounded9: divers is outside [1, 1024]"); return LPX_EINVAL; }
+    if (stall_events < 0) { set_error("lpx_solve_bnb_bounded9: stall_events is negative"); return LPX_EINVAL; }
+    if (root_form != LPX_NODE_LAUNCHES && root_form != LPX_NODE_ONCHIP && root_form != LPX_NODE_AUTO) {
+        set_error("lpx_solve_bnb_bounded9: unknown root_form");
+        return LPX_EINVAL;
+    }
+    if (root_cuts) if (int rc = check_cut_opts(root_cuts, "lpx_solve_bnb_bounded9")) return rc;
+    // root_cuts == NULL: the call of lpx_solve_bnb_bounded8 itself
+    return solve_bnb_bounded(p, lower, upper, is_int, o, max_nodes, search_flags, out, info, "lpx_solve_bnb_bounded9", -1, divers, dinfo,
+                             0, nullptr, nullptr, nullptr, stall_events, ginfo, root_form == LPX_NODE_LAUNCHES ? -1 : root_form, root_cuts, cinfo);
+}
+
+void lpx_bnb_cut_info_free(lpx_bnb_cut_info* cinfo)
+{
+    if (!cinfo) return;
+    std::free(cinfo->z_before); std::free(cinfo->z_after);
+    std::memset(cinfo, 0, sizeof(*cinfo));
 }
 
 void lpx_bnb_strong_info_free(lpx_bnb_strong_info* sinfo)

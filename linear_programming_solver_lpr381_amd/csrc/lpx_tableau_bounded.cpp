@@ -2,7 +2,8 @@
 // the tableau, the bounded primal and dual loops, bound changes on a solved tableau, branch and bound by bound changes.
 // Kernels: lpx_bounded.hip, lpx_bounded_dual.hip, lpx_bounded_long.hip (their shared pieces: lpx_bounded.h), lpx_bnb_bounded.hip;
 // the update is lpx_update.  The on-chip forms: the node (lpx_bounded_node.hip and its siblings) and the primal loop
-// (lpx_bounded_run2, lpx_bounded_primal.hip).
+// (lpx_bounded_run2, lpx_bounded_primal.hip).  The cut round on a handle with bounds and the cut loop at a bounded root
+// (lpx_tableau_gmi_round_bounded, lpx_bounded_cut_loop; the round and its kernels: lpx_cuts.hip).
 #include "lpx_handle.h"
 
 #include <cstring>
@@ -810,6 +811,95 @@ int lpx_bounded_node4(lpx_tableau* t, int K, const int32_t* cols, const double* 
     rc = check_node_opts(t, o, what); if (rc) return rc;
     rc = check_node_fits(t, what); if (rc) return rc;
     return bounded_node_onchip(t, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, what, stall_events, guard);
+}
+
+// ---- GMI cuts on a handle with bounds, and the cut loop at a bounded root (kernels in lpx_cuts.hip) ----
+// The round itself is gmi_round_run's; what the handle keeps beside the tableau follows the reshape here.
+static int gmi_round_bounded(lpx_tableau* t, const uint8_t* is_int, int n_mask, int first_cut_col, const lpx_cut_opts* o, int* n_added,
+                             int32_t* src_rows, int* n_purged, int32_t* purged_cols, const char* what)
+{
+    lpx_tableau::Bounds& b = t->bnd;
+    const int Cm = t->C - 1;
+    std::vector<int32_t> pc((size_t)(Cm - first_cut_col > 0 ? Cm - first_cut_col : 1));
+    int K = 0, P = 0;
+    CutBounds cb{nullptr, nullptr, nullptr, t->rhsbuf};
+    if (b.bounds_set) { cb.ub = b.ub; cb.lo = b.lo; cb.flip = b.flip; }
+    t->suspended = t->suspended2 = t->fsuspended = false;
+    const int rc = gmi_round_run(t, is_int, n_mask, first_cut_col, o, &K, src_rows, &P, pc.data(), &cb, what);
+    if (rc) return rc;
+    if (b.bounds_set && (K > 0 || P > 0)) {
+        b.bounds_C = t->C;
+        if (!b.whole.empty()) {                         // the plunge's host knowledge: purged columns leave, a new slack is not whole
+            for (int i = P - 1; i >= 0; --i) if ((size_t)pc[i] < b.whole.size()) b.whole.erase(b.whole.begin() + pc[i]);
+            b.whole.resize((size_t)(t->C - 1), 0);
+        }
+    }
+    if (n_added) *n_added = K;
+    if (n_purged) *n_purged = P;
+    if (purged_cols) for (int i = 0; i < P; ++i) purged_cols[i] = pc[i];
+    return 0;
+}
+
+int lpx_tableau_gmi_round_bounded(lpx_tableau* t, const uint8_t* is_int, int n_mask, int first_cut_col, const lpx_cut_opts* o,
+                                  int* n_added, int32_t* src_rows, int* n_purged, int32_t* purged_cols)
+{
+    const char* what = "lpx_tableau_gmi_round_bounded";
+    int rc = gmi_round_args(t, is_int, n_mask, first_cut_col, o, 0, what); if (rc) return rc;
+    rc = check_bounds(t, what, false); if (rc) return rc;
+    return gmi_round_bounded(t, is_int, n_mask, first_cut_col, o, n_added, src_rows, n_purged, purged_cols, what);
+}
+
+int lpx_bounded_cut_loop(lpx_tableau* t, const uint8_t* is_int, int n_mask, int first_cut_col, int nint, const uint8_t* node_is_int,
+                         const lpx_cut_opts* co, const lpx_run_opts* ro, int flags, int form, lpx_cut_loop_record* rec)
+{
+    const char* what = "lpx_bounded_cut_loop";
+    const std::string w = what;
+    if (!rec) { set_error(w + ": null record"); return LPX_EINVAL; }
+    int rc = gmi_round_args(t, is_int, n_mask, first_cut_col, co, 0, what); if (rc) return rc;
+    rc = check_long_flags(flags | LPX_BDUAL_SKIP_FIXED, -1.0 / 0.0, what); if (rc) return rc;
+    if (form != LPX_NODE_LAUNCHES && form != LPX_NODE_ONCHIP && form != LPX_NODE_AUTO) { set_error(w + ": unknown form"); return LPX_EINVAL; }
+    rc = check_pick_args(t, nint, co->int_tol, rec, what); if (rc) return rc;
+    rc = check_bounds(t, what, true); if (rc) return rc;
+    lpx_run_opts d; if (!ro) { lpx_default_opts(&d, 1); ro = &d; }
+    rc = check_node_opts(t, ro, what); if (rc) return rc;
+    if (form == LPX_NODE_ONCHIP) {                      // every shape the rounds can reach has to fit: they grow R and C alike
+        rc = check_node_fits(t, what); if (rc) return rc;
+        const int a = t->Rcap - t->R < t->Ccap - t->C ? t->Rcap - t->R : t->Ccap - t->C;
+        if (!bounded_node_fits(t->R + a, t->C + a)) { set_error(w + ": the handle's spare capacity does not fit the on-chip form"); return LPX_EINVAL; }
+    }
+    double* zb = rec->z_before; double* za = rec->z_after;
+    std::memset(rec, 0, sizeof(*rec));
+    rec->z_before = zb; rec->z_after = za; rec->status = LPX_OPTIMAL; rec->stop = LPX_CUTLOOP_ROUNDS; rec->pick.var = -1;
+    rec->R = t->R; rec->C = t->C;
+    const int nflags = flags | LPX_BDUAL_SKIP_FIXED;
+    const double cutoff = -1.0 / 0.0;
+    rc = lpx_tableau_branch_pick(t, nint, node_is_int, co->int_tol, &rec->pick); if (rc) return rc;
+    for (;;) {
+        if (rec->pick.var < 0) { rec->stop = LPX_CUTLOOP_INTEGRAL; break; }
+        if (rec->rounds >= co->max_rounds) { rec->stop = LPX_CUTLOOP_ROUNDS; break; }
+        int K = 0, P = 0;
+        rc = gmi_round_bounded(t, is_int, n_mask, first_cut_col, co, &K, nullptr, &P, nullptr, what); if (rc) return rc;
+        rec->purged += P; rec->R = t->R; rec->C = t->C;
+        if (K == 0) { rec->stop = LPX_CUTLOOP_STALLED; break; }
+        rec->added += K;
+        const double z0 = rec->pick.z;
+        lpx_node_record nr;
+        rc = lpx_bounded_node3(t, 0, nullptr, nullptr, nullptr, ro, nflags, cutoff, nint, node_is_int, co->int_tol, form, &nr);
+        if (rc < 0) return rc;
+        if (zb) zb[rec->rounds] = z0;
+        if (za) za[rec->rounds] = nr.pick.z;
+        rec->rounds += 1; rec->events += nr.events; rec->status = nr.status; rec->pick = nr.pick;
+        if (nr.status == LPX_INFEASIBLE) { rec->stop = LPX_CUTLOOP_INFEASIBLE; break; }
+        if (nr.status == LPX_ITER_LIMIT) { rec->stop = LPX_CUTLOOP_ITER_LIMIT; break; }
+        if (nr.status != LPX_OPTIMAL) { rec->stop = LPX_CUTLOOP_STATUS; break; }
+    }
+    if (co->purge && rec->stop <= LPX_CUTLOOP_ROUNDS) {
+        lpx_cut_opts po = *co; po.cuts_per_round = 0;
+        int K = 0, P = 0;
+        rc = gmi_round_bounded(t, is_int, n_mask, first_cut_col, &po, &K, nullptr, &P, nullptr, what); if (rc) return rc;
+        rec->purged += P; rec->R = t->R; rec->C = t->C;
+    }
+    return rec->stop == LPX_CUTLOOP_ITER_LIMIT ? LPX_ITER_LIMIT : 0;
 }
 
 // ---- strong-branching probes of the handle as it stands (kernel in lpx_bounded_probe.hip): one launch, one wait, no write to the handle ----

@@ -387,7 +387,9 @@ class LPSolver:             # Models/LPSolver.cs:6-77
                         long_step: bool = False, cutoff: bool = False, node_form: Optional[str] = None,
                         divers: Optional[int] = None, plunge: Optional[int] = None, branching: Optional[str] = None,
                         candidates: int = 4, probe_iter: Optional[int] = None,
-                        stall_events: Optional[int] = None, root_form: Optional[str] = None) -> SimplexResult:
+                        stall_events: Optional[int] = None, root_form: Optional[str] = None,
+                        root_cuts: Optional[int] = None, cuts_per_round: int = 8, max_active: int = 64,
+                        cut_opts: Optional["CutOpts"] = None) -> SimplexResult:
         """Branch and bound by bound changes on one device tableau (lpx_solve_bnb_bounded): lower <= x <= upper, x_j integer
         where integer[j] (None: every variable); integer variables need finite, integral bounds.  Status OPTIMAL or INFEASIBLE,
         Solution, OptimalValue (user's sense), Nodes, BnbInfo (counters) and BnbLog, a structured array with one record per node
@@ -421,7 +423,24 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         branching: those have no guard.  root_form "launches" | "onchip" | "auto" (lpx_solve_bnb_bounded8; None: the paths above,
         unchanged; without divers it means divers=1, without stall_events stall_events=0): the search by divers whose root LP
         is solved in that form; the node log is the same for every form.  It cannot be combined with node_form="launches",
-        plunge or branching: those drivers have no root form."""
+        plunge or branching: those drivers have no root form.  root_cuts=N (lpx_solve_bnb_bounded9; None: the paths above,
+        unchanged; without root_form it means root_form="launches"): cut-and-branch -- up to N rounds of cuts_per_round GMI cuts
+        at the solved root (lpx_bounded_cut_loop) on a handle with up to max_active spare rows and columns, then the search by
+        divers from that handle; cut_opts (a CutOpts) gives every option of the loop instead.  BnbInfo then carries cut_ran,
+        cut_spare, cut_rounds, cuts_added, cuts_purged, cut_events, cut_stop, cut_R and cut_C, and the result CutZ, an array
+        [rounds, 2] of the LP objective in front of and behind every round (internal sense).  Whether the tree shrinks depends
+        on the model.  It cannot be combined with node_form="launches", plunge or branching."""
+        if root_cuts is not None or cut_opts is not None:
+            if node_form == "launches":
+                raise ValueError("root cuts belong to the search by divers: they cannot be combined with node_form='launches'")
+            if plunge is not None:
+                raise ValueError("the plunge driver has no root cuts: root_cuts cannot be combined with plunge")
+            if branching is not None:
+                raise ValueError("the strong-branching driver has no root cuts: root_cuts cannot be combined with branching")
+            if cut_opts is None:
+                cut_opts = CutOpts(cuts_per_round=int(cuts_per_round), max_rounds=int(root_cuts), max_active=int(max_active))
+            if root_form is None:
+                root_form = "launches"
         if root_form is not None:
             if root_form not in _lib.NODE_FORMS:
                 raise ValueError(f"unknown root form {root_form!r}")
@@ -485,7 +504,13 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         flags = (_lib.BDUAL_LONG_STEP if long_step else 0) | (_lib.BDUAL_CUTOFF if cutoff else 0)
         sinfo = _lib.BnbStrongInfo()
         ginfo = _lib.BnbGuardInfo()
-        if root_form is not None:
+        cinfo = _lib.BnbCutInfo()
+        if cut_opts is not None:
+            co = cut_opts.to_c()
+            rc = lib().lpx_solve_bnb_bounded9(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), flags, int(divers),
+                                              int(stall_events), _lib.NODE_FORMS[root_form], C.byref(co), C.byref(r), C.byref(info),
+                                              C.byref(dinfo), C.byref(ginfo), C.byref(cinfo))
+        elif root_form is not None:
             rc = lib().lpx_solve_bnb_bounded8(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), flags, int(divers),
                                               int(stall_events), _lib.NODE_FORMS[root_form], C.byref(r), C.byref(info), C.byref(dinfo),
                                               C.byref(ginfo))
@@ -530,6 +555,13 @@ class LPSolver:             # Models/LPSolver.cs:6-77
                                                                 "pruned_by_probe", "changed_picks")})
             if stall_events is not None:
                 counters.update({k: getattr(ginfo, k) for k in ("guarded_nodes", "bland_events", "max_events")})
+            if cut_opts is not None:
+                counters.update(cut_ran=cinfo.ran, cut_spare=cinfo.spare, cut_rounds=cinfo.rounds, cuts_added=cinfo.added,
+                                cuts_purged=cinfo.purged, cut_events=cinfo.events, cut_stop=_lib.CUTLOOP_STOPS[cinfo.stop] if cinfo.ran else None,
+                                cut_R=cinfo.R, cut_C=cinfo.C)
+                cutz = np.zeros((cinfo.n_z, 2))
+                for i in range(cinfo.n_z):
+                    cutz[i] = cinfo.z_before[i], cinfo.z_after[i]
             if plunge is not None:
                 counters.update({k: getattr(pinfo, k) for k in ("launched", "dropped", "longest_chain")})
                 step = np.ctypeslib.as_array(pinfo.step, (info.n_log,)).copy() if info.n_log else np.zeros(0, dtype=np.int32)
@@ -537,8 +569,11 @@ class LPSolver:             # Models/LPSolver.cs:6-77
             lib().lpx_bnb_bounded_info_free(C.byref(info))
             lib().lpx_bnb_divers_info_free(C.byref(dinfo))
             lib().lpx_bnb_plunge_info_free(C.byref(pinfo))
+            lib().lpx_bnb_cut_info_free(C.byref(cinfo))
         res = _take_result(r, n)
         res.BnbLog, res.BnbInfo = log, counters
+        if cut_opts is not None:
+            res.CutZ = cutz
         if divers is not None:
             res.BnbRound, res.BnbDiver = rounds, who
         if plunge is not None:

@@ -156,21 +156,52 @@ class DeviceTableau:
                                               dec.ctypes.data_as(dp), dec_at.ctypes.data_as(ip)))
         return inc, inc_at, dec, dec_at
 
-    def gmi_round(self, is_int, first_cut_col: int, opts=None, **kw) -> Tuple[np.ndarray, np.ndarray]:
+    def gmi_round(self, is_int, first_cut_col: int, opts=None, bounded: bool = False, **kw) -> Tuple[np.ndarray, np.ndarray]:
         """One GMI cut round on the device (lpx_tableau_gmi_round): is_int[j] marks the integer columns j < len(is_int);
         opts is an lpx_cut_opts (None: defaults with keyword overrides).  The handle takes the new shape.
-        Returns (source rows, purged columns)."""
+        bounded=True is lpx_tableau_gmi_round_bounded: a flagged column counts as integer only where the handle's lo and ub are
+        whole, ub / lo / flip follow the reshape (every bounded call accepts the handle afterwards), and cuts_per_round=0 is a
+        purge-only call.  Returns (source rows, purged columns)."""
         o = opts if opts is not None else _lib.cut_opts(**kw)
         mask = np.ascontiguousarray(np.asarray(is_int) != 0, dtype=np.uint8)
         src = np.zeros(max(o.cuts_per_round, 1), dtype=np.int32)
         pcol = np.zeros(max(self.C, 1), dtype=np.int32)
         k, p = C.c_int(), C.c_int()
-        check(lib().lpx_tableau_gmi_round(self._h, mask.ctypes.data_as(C.POINTER(C.c_uint8)), len(mask), int(first_cut_col),
-                                          C.byref(o), C.byref(k), src.ctypes.data_as(ip), C.byref(p), pcol.ctypes.data_as(ip)))
+        fn = lib().lpx_tableau_gmi_round_bounded if bounded else lib().lpx_tableau_gmi_round
+        check(fn(self._h, mask.ctypes.data_as(C.POINTER(C.c_uint8)), len(mask), int(first_cut_col),
+                 C.byref(o), C.byref(k), src.ctypes.data_as(ip), C.byref(p), pcol.ctypes.data_as(ip)))
         R, C_ = C.c_int(), C.c_int()
         check(lib().lpx_tableau_shape(self._h, C.byref(R), C.byref(C_), None))
         self.R, self.C = R.value, C_.value
         return src[: k.value].copy(), pcol[: p.value].copy()
+
+    def cut_loop(self, is_int, first_cut_col: int, nint: int, node_is_int=None, opts=None, run_opts: Optional[RunOpts] = None,
+                 long_step: bool = False, cutoff: bool = False, form: str = "launches", **kw) -> dict:
+        """Rounds of GMI cuts on a solved bounded handle with spare capacity (lpx_bounded_cut_loop): pick, bounded round,
+        re-optimisation as a node without a bound edit (form "launches" | "onchip" | "auto", bit-equal), until the pick finds
+        no fractional integer column, a round adds no cut, max_rounds are used up, or the re-optimisation ends INFEASIBLE (the
+        integer program is infeasible) or at its iteration limit; then one purge-only call when opts.purge is set.  is_int /
+        first_cut_col are the round's, nint / node_is_int the pick's; long_step / cutoff set the loop's flags (the cutoff is
+        -inf).  Returns {rounds, added, purged, events, stop, status, R, C, var, candidates, x_var, z, z_before, z_after, rc}."""
+        if form not in _lib.NODE_FORMS:
+            raise ValueError(f"unknown form {form!r}")
+        o = opts if opts is not None else _lib.cut_opts(**kw)
+        mask = np.ascontiguousarray(np.asarray(is_int) != 0, dtype=np.uint8)
+        keep, mp = self._mask(node_is_int, int(nint))
+        zb, za = np.zeros(max(o.max_rounds, 1)), np.zeros(max(o.max_rounds, 1))
+        rec = _lib.CutLoopRecord()
+        rec.z_before, rec.z_after = zb.ctypes.data_as(dp), za.ctypes.data_as(dp)
+        flags = (_lib.BDUAL_LONG_STEP if long_step else 0) | (_lib.BDUAL_CUTOFF if cutoff else 0)
+        try:
+            rc = check(lib().lpx_bounded_cut_loop(self._h, mask.ctypes.data_as(C.POINTER(C.c_uint8)), len(mask), int(first_cut_col),
+                                                  int(nint), mp, C.byref(o), C.byref(run_opts) if run_opts is not None else None,
+                                                  flags, _lib.NODE_FORMS[form], C.byref(rec)))
+        finally:
+            self._shape()
+        return {"rounds": rec.rounds, "added": rec.added, "purged": rec.purged, "events": rec.events,
+                "stop": _lib.CUTLOOP_STOPS[rec.stop], "status": rec.status, "R": rec.R, "C": rec.C, "var": rec.pick.var,
+                "candidates": rec.pick.candidates, "x_var": rec.pick.x_var, "z": rec.pick.z,
+                "z_before": zb[: rec.rounds].copy(), "z_after": za[: rec.rounds].copy(), "rc": rc}
 
     def _shape(self):
         R, C_ = C.c_int(), C.c_int()

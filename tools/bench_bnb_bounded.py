@@ -54,12 +54,22 @@ usage: bench_bnb_bounded.py [--model NAME] [--max-nodes N] [--node-form F] [--di
                             [--compare-forms [--flag-sets LIST]] [--compare-divers LIST [--flag-sets LIST]]
                             [--compare-plunge LIST [--flag-sets LIST]] [--compare-branching LIST [--flag-sets LIST]]
                             [--branching R [--candidates C] [--probe-iter L]] [--compare-guard LIST [--flag-sets LIST]]
-                            [--stall-events S] [--long-step] [--cutoff] [--trace-only] [--compare-root LIST] [REPS]
+                            [--stall-events S] [--long-step] [--cutoff] [--trace-only] [--compare-root LIST]
+                            [--compare-cuts [LIST] [--rounds LIST] [--cuts-per-round K]] [REPS]
 
 `--compare-root LIST` measures the form of the root solve (lpx_solve_bnb_bounded8) at every W of LIST, with the
 long step and the cutoff: root_form "launches" against "onchip", the sides alternating, one untimed solve each first.  Beside the
 search it times the root solve alone in either form (lpx_solve_bounded / lpx_solve_bounded2) and reports its share of the search's
-wall on both sides.  A side wins iff its median lies below the other's minimum."""
+wall on both sides.  A side wins iff its median lies below the other's minimum.
+
+`--compare-cuts [LIST]` measures cut-and-branch at the root (lpx_solve_bnb_bounded9) at every W of LIST (default
+1,16,256), with the long step and the cutoff: the search with N rounds of K GMI cuts at the root, N over `--rounds` (default 2,4,8) and
+K = `--cuts-per-round` (default 8), against the same search without cuts (lpx_solve_bnb_bounded8, root_form "launches") in the same
+process, the settings alternating, one untimed solve each first.  Per setting: nodes, wall to optimality, the cut counts and the shape
+the search runs on.  A setting wins iff its median lies below the baseline's minimum, and loses iff the baseline's median lies below
+its minimum.  Beside the searches it times lpx_bounded_cut_loop alone on the solved root in both node forms (the handle is put back
+from a snapshot between the runs) and checks that the two forms leave the same record.  No ratio is expected in advance: whether the
+tree shrinks depends on the model."""
 import json
 import os
 import statistics
@@ -412,8 +422,114 @@ def compare_root(n, m, reps, max_nodes, widths):
     return rec
 
 
+def compare_cuts(n, m, reps, max_nodes, widths, rounds, K, max_active=64):
+    """Cut-and-branch at the root (lpx_solve_bnb_bounded9) against the search without cuts on binary_ip(n, m) (see the module docstring)."""
+    c, A, rel, b = synth.binary_ip(n, m)
+    p = L.LPProblem.from_arrays(0, c, A[:m], rel[:m], b[:m])
+    rec = {"n": n, "m": m, "bounded_shape": [m + 1, n + m + 1], "cuts_per_round": K, "max_active": max_active}
+
+    # the loop alone, on the solved root, in both node forms
+    T, basis = synth.primal_tableau_from(c, A[:m], b[:m])
+    R, C_ = T.shape
+    ub = np.full(C_ - 1, np.inf); ub[:n] = 1.0
+    spare = max_active
+    while spare > 0 and not L._lib.lib().lpx_bounded_node_fits(R + spare, C_ + spare):
+        spare -= 1
+    rec["spare"] = spare
+    flags = np.zeros(C_ - 1, dtype=np.uint8); flags[:n] = 1
+    for i in range(m):
+        flags[n + i] = 1 if (np.all(T[i, :n] == np.floor(T[i, :n])) and T[i, -1] == np.floor(T[i, -1])) else 0
+    loop = {}
+    if spare > 0:
+        with L.DeviceTableau.with_capacity(T, basis, R + spare, C_ + spare) as dt:
+            dt.set_bounds(ub)
+            dt.bounded_run()
+            dt.snapshot()
+            for N in rounds:
+                ts, last = {f: [] for f in FORMS}, {}
+                for i in range(reps + 1):
+                    for f in FORMS:
+                        dt.set_shape(R, C_)
+                        dt.restore()
+                        t0 = time.perf_counter()
+                        r = dt.cut_loop(flags, C_ - 1, n, cuts_per_round=K, max_rounds=N, max_active=max_active, long_step=True,
+                                        cutoff=True, form=f)
+                        if i >= 1:
+                            ts[f].append(1e3 * (time.perf_counter() - t0))
+                        last[f] = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in r.items()}
+                assert last["launches"] == last["onchip"], "the two forms of the loop leave different records"
+                loop[f"rounds{N}"] = {"ms": {f: stats(ts[f]) for f in FORMS}, "record": {k: last["onchip"][k] for k in
+                                      ("rounds", "added", "purged", "events", "stop", "R", "C")}, "z": [last["onchip"]["z_before"][:1],
+                                      last["onchip"]["z_after"]]}
+    rec["loop_alone"] = loop
+
+    def solve(W, N):
+        kw = dict(root_cuts=N, cuts_per_round=K, max_active=max_active) if N else dict(root_form="launches")
+        t0 = time.perf_counter()
+        try:
+            r = L.LPSolver().SolveBnbBounded(p, 1.0, max_nodes=max_nodes, divers=W, long_step=True, cutoff=True, **kw)
+            r.Limit = None
+        except L.SolverException as e:
+            if e.code != L._lib.ITER_LIMIT:
+                raise
+            r = e.result
+            r.Limit = str(e)
+        return 1e3 * (time.perf_counter() - t0), r
+
+    settings = [0] + [N for N in rounds if N]
+    for W in widths:
+        ts, last = {N: [] for N in settings}, {}
+        for i in range(reps + 1):
+            for N in settings:
+                ms, r = solve(W, N)
+                if i >= 1:
+                    ts[N].append(ms)
+                last[N] = r
+        d = {}
+        base = stats(ts[0])
+        for N in settings:
+            st, r = stats(ts[N]), last[N]
+            e = {"ms": st, "nodes": int(r.Nodes), "value": float(r.OptimalValue), "limit": r.Limit}
+            if N:
+                bi = r.BnbInfo
+                e.update(cut_rounds=bi["cut_rounds"], cuts_added=bi["cuts_added"], cuts_purged=bi["cuts_purged"], cut_stop=bi["cut_stop"],
+                         shape=[bi["cut_R"], bi["cut_C"]], nodes_vs_baseline=r.Nodes / max(last[0].Nodes, 1),
+                         wall_vs_baseline=st["median"] / base["median"],
+                         verdict="win" if st["median"] < base["min"] else "loss" if base["median"] < st["min"] else "tie")
+                assert r.Limit or last[0].Limit or abs(r.OptimalValue - last[0].OptimalValue) <= 1e-9 * abs(last[0].OptimalValue), "optimum differs"
+            d["baseline" if not N else f"rounds{N}"] = e
+        rec[f"W{W}"] = d
+    return rec
+
+
 def main():
     args = sys.argv[1:]
+    if "--compare-cuts" in args:
+        k = args.index("--compare-cuts")
+        widths = [1, 16, 256]
+        if k + 1 < len(args) and args[k + 1][:1].isdigit() and "," in args[k + 1]:
+            widths = [int(w) for w in args[k + 1].split(",") if w]
+            del args[k + 1]
+        del args[k]
+        only, max_nodes, rounds, K = None, 0, [2, 4, 8], 8
+        for flag in ("--model", "--max-nodes", "--rounds", "--cuts-per-round"):
+            if flag in args:
+                j = args.index(flag)
+                if flag == "--model":
+                    only = args[j + 1]
+                elif flag == "--max-nodes":
+                    max_nodes = int(args[j + 1])
+                elif flag == "--rounds":
+                    rounds = [int(w) for w in args[j + 1].split(",") if w]
+                else:
+                    K = int(args[j + 1])
+                del args[j:j + 2]
+        reps = int(args[0]) if args else None
+        L._lib.check(L._lib.lib().lpx_init(0))
+        out = {name: compare_cuts(n, m, reps if reps is not None else (3 if n >= 128 else 7), max_nodes, widths, rounds, K)
+               for name, n, m in models() if only is None or name == only}
+        print(json.dumps(out))
+        return
     if "--compare-root" in args:
         k = args.index("--compare-root")
         widths = [int(w) for w in args[k + 1].split(",") if w]
