@@ -1418,6 +1418,84 @@ int  lpx_solve_bnb_bounded9(const lpx_problem* p, const double* lower /* [n] or 
                             lpx_bnb_cut_info* cinfo /* or NULL */);
 void lpx_bnb_cut_info_free(lpx_bnb_cut_info* cinfo);
 
+/* ---- reduced-cost tightening: a node that branches shrinks the ranges of its subtree (not in the reference;
+ * csrc/lpx_bounded_fix.hip, csrc/lpx_onchip_fix.h, csrc/lpx_node_batch.cpp, csrc/host/bnb_bounded.cpp) --
+ * A node that ends LPX_OPTIMAL leaves a dual feasible objective row, and from the first incumbent on a driver has a bound to
+ * beat.  The rule works on the handle's internal variables (the search is internally a Max; z = T[m,Cm]) and is driven by one
+ * double, fix_bound; -inf turns it off.  It runs only when the node ended LPX_OPTIMAL and z > fix_bound, in the same launch,
+ * behind the branch pick (the pick sees the bounds as they were).  For every column j < nint it applies when all of these hold:
+ *   - the mask admits j (is_int NULL or is_int[j] != 0);
+ *   - j is not basic (the basic columns are marked through the basis; none is inferred from a zero);
+ *   - d = T[m,j] satisfies d > eps.
+ * With g = (z - fix_bound) / d (one subtract, one IEEE divide) and t = floor(g), column j is tightened iff t < ub[j], and then
+ * ub[j] = t.  A column with flip[j] != 0 also gets lo[j] = (lo[j] + ub_old[j]) - t, and the handle's mark that a lower shift is
+ * stored is set as a bound edit with the reported triples would set it.  Nothing beside ub and lo changes: a nonbasic column
+ * stands at 0, so its range change has a zero RHS shift; the tableau, the RHS, the basis, the flip states and the trace stay.
+ * The tightened columns are reported in ascending j, each as the absolute triple (col, lower, upper) in the handle's x' space
+ * that a bound edit would take: unflipped (j, lo[j], lo[j] + t); flipped (j, up - t, up) with up = lo[j] + ub_old[j].
+ * DEFINING PROPERTY: after the call, ub, lo, flip, the tableau and the basis are bit-equal to those of a twin handle that ran the
+ * same node with tightening off and then one more node call carrying exactly the reported triples; that call makes 0 events and
+ * 0 flips.  WHY IT IS VALID: in the internal variables z(x') = z - sum d_j x'_j over the nonbasic columns, so a point with
+ * x'_j >= t + 1 has an objective <= z - d (t + 1) <= fix_bound, which with fix_bound = best + 1e-6 is the driver's own prune
+ * test.  The admitted columns are expected to have finite ranges, as the integer columns of every driver have: on a column
+ * with ub = +inf any finite t becomes its upper bound, which is valid and harmless but with a fix_bound far below z is merely
+ * a huge number.  Integer columns only (no slack, no continuous column), and local only: the tightening holds for the subtree of the
+ * node; nothing is fixed again at the root when an incumbent improves.
+ *
+ * lpx_bounded_node5(t, K, cols, lower, upper, o, flags, cutoff, stall_events, fix_bound, nint, is_int, tol, form, out, guard, fix):
+ * fix_bound = -inf is lpx_bounded_node4 in every form, bit for bit (same kernels), fix->n = 0.  Any other fix_bound needs the
+ * on-chip form and runs lpx_bounded_fix_onchip: ONE launch, ONE wait, the same LDS rule (lpx_bounded_node_fits); that kernel
+ * carries the stall guard, and with stall_events = 0 its loop is the unguarded one bit for bit.  fix is caller-owned: cap entries
+ * in each of cols / lower / upper; n comes back, the first n entries are the triples.  LPX_EINVAL before any device check:
+ * fix_bound is NaN ("fix_bound is NaN"); fix with cap < nint ("fix->cap is below nint") or, with nint > 0, a null array; no fix
+ * with a fix_bound other than -inf ("null fix"); such a fix_bound with LPX_NODE_LAUNCHES, or with LPX_NODE_AUTO on a shape that
+ * does not fit ("reduced-cost tightening has no launches form"); and the argument errors of lpx_bounded_node4 with the new name
+ * in front.  guard and, with fix_bound = -inf, fix may be NULL.  A refused edit leaves n = 0.
+ *
+ * lpx_node_batch_run3(b, B, slot, K, cols, lower, upper, o, flags, cutoff, stall_events, fix_bound, nint, is_int, tol, out, guard,
+ * fix, rc): lpx_node_batch_run2's contract word for word, with lpx_bounded_node5(..., stall_events, fix_bound[i], ...,
+ * LPX_NODE_ONCHIP, &out[i], &guard[i], &fix[i]) as the single-node equal of entry i and "lpx_node_batch_run3" in front of the
+ * messages.  fix_bound [B] is per entry and never NULL; fix [B] may be NULL only when every fix_bound[i] is -inf.  Entries with
+ * -inf tighten nothing whatever the others do.  When every entry is -inf the launch is lpx_node_batch_run2's.
+ *
+ * lpx_solve_bnb_bounded10(p, lower, upper, is_int, o, max_nodes, search_flags, divers, stall_events, root_form, root_cuts, tighten,
+ * out, info, dinfo, ginfo, cinfo, finfo): lpx_solve_bnb_bounded9 with the flag tighten (0 or 1, anything else is LPX_EINVAL:
+ * "tighten is neither 0 nor 1").  tighten = 0 is lpx_solve_bnb_bounded9 bit for bit.  With tighten = 1 the rounds change in two
+ * steps only.  Step 4 is ONE lpx_node_batch_run3 in which every entry's fix_bound is best + 1e-6 as best stood at the start of
+ * the round, or -inf while there is no incumbent.  Step 5, for every record with reported triples: they are applied to the bounds
+ * the driver holds for that diver's handle (the kernel has applied them to the handle already), and, where the node branches,
+ * appended to both children's paths in front of the branching override.  The log stays a function of the model, the options,
+ * the flags, W and tighten.  finfo (or NULL): tightened_nodes (nodes that tightened a column), tightened_cols (their sum) and
+ * max_per_node; plain counters, no free function.  The default stays off: no speed-up is promised.
+ * The plunge, the probes with strong branching and the sequential driver of the launches form have no tightening. */
+typedef struct lpx_fix_list {            /* 32 bytes */
+    int32_t cap;           /* in: entries the three arrays hold, >= nint */
+    int32_t n;             /* out: columns tightened */
+    int32_t* cols;         /* out [n]: ascending */
+    double* lower;         /* out [n]: the triples a bound edit would take, in the handle's x' space */
+    double* upper;
+} lpx_fix_list;
+typedef struct lpx_bnb_fix_info {        /* 24 bytes */
+    int64_t tightened_nodes, tightened_cols, max_per_node;
+} lpx_bnb_fix_info;
+int  lpx_bounded_node5(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const lpx_run_opts* o,
+                       int flags, double cutoff, int stall_events, double fix_bound, int nint,
+                       const uint8_t* is_int /* [nint] or NULL = all */, double tol, int form, lpx_node_record* out,
+                       lpx_guard_record* guard /* or NULL */, lpx_fix_list* fix /* NULL only with fix_bound = -inf */);
+int  lpx_node_batch_run3(lpx_node_batch* b, int B, const int32_t* slot /* [B] */, const int32_t* K /* [B] */,
+                         const int32_t* cols, const double* lower, const double* upper /* concatenated, sum of K */,
+                         const lpx_run_opts* o, int flags, const double* cutoff /* [B]; read only with LPX_BDUAL_CUTOFF */,
+                         int stall_events, const double* fix_bound /* [B] */, int nint,
+                         const uint8_t* is_int /* [nint] or NULL = all */, double tol, lpx_node_record* out /* [B] */,
+                         lpx_guard_record* guard /* [B] or NULL */, lpx_fix_list* fix /* [B] */, int32_t* rc /* [B] */);
+int  lpx_solve_bnb_bounded10(const lpx_problem* p, const double* lower /* [n] or NULL = 0 */, const double* upper /* [n] */,
+                             const uint8_t* is_int /* [n] or NULL = all */, const lpx_solve_opts* o, int64_t max_nodes /* 0 = none */,
+                             int search_flags, int divers /* W, 1..1024 */, int stall_events, int root_form,
+                             const lpx_cut_opts* root_cuts /* or NULL */, int tighten /* 0 or 1 */, lpx_result* out,
+                             lpx_bnb_bounded_info* info /* or NULL */, lpx_bnb_divers_info* dinfo /* or NULL */,
+                             lpx_bnb_guard_info* ginfo /* or NULL */, lpx_bnb_cut_info* cinfo /* or NULL */,
+                             lpx_bnb_fix_info* finfo /* or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

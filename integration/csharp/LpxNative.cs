@@ -170,6 +170,21 @@ namespace Linear_Programming_Solver.Native
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct LpxFixList              // lpx_fix_list: 32 bytes; the caller owns the arrays (cap entries each, cap >= nint)
+    {
+        public int cap, n;                       // in: capacity; out: columns tightened
+        public int* cols;                        // out [n]: ascending
+        public double* lower;                    // out [n]: the triples a bound edit would take
+        public double* upper;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct LpxBnbFixInfo                  // lpx_bnb_fix_info: 24 bytes of counters, nothing to free
+    {
+        public long tightened_nodes, tightened_cols, max_per_node;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public unsafe struct LpxCutLoopRecord        // lpx_cut_loop_record (lpx_bounded_cut_loop); z_before / z_after: the caller's [max_rounds] or null
     {
         public int rounds, added, purged, stop;
@@ -459,6 +474,23 @@ namespace Linear_Programming_Solver.Native
                                                         LpxCutOpts* root_cuts, out LpxResult result, out LpxBnbBoundedInfo info,
                                                         out LpxBnbDiversInfo dinfo, out LpxBnbGuardInfo ginfo, out LpxBnbCutInfo cinfo);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern void lpx_bnb_cut_info_free(ref LpxBnbCutInfo cinfo);
+
+        // reduced-cost bound tightening (include/lpx.h; lpx_bounded_fix.hip).  fix_bound = -inf: lpx_bounded_node4 / lpx_node_batch_run2 bit
+        // for bit; tighten = 0: lpx_solve_bnb_bounded9 bit for bit
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_bounded_node5(IntPtr tableau, int K, int* cols, double* lower, double* upper, IntPtr opts, int flags,
+                                                   double cutoff, int stall_events, double fix_bound, int nint, byte* is_int, double tol, int form,
+                                                   out LpxNodeRecord record, LpxGuardRecord* guard, LpxFixList* fix);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_node_batch_run3(IntPtr batch, int B, int* slot, int* K, int* cols, double* lower, double* upper, IntPtr opts,
+                                                     int flags, double* cutoff, int stall_events, double* fix_bound, int nint, byte* is_int, double tol,
+                                                     LpxNodeRecord* records, LpxGuardRecord* guards, LpxFixList* fixes, int* rc);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_bnb_bounded10(ref LpxProblem p, double* lower, double* upper, byte* is_int, ref LpxSolveOpts o,
+                                                         long max_nodes, int search_flags, int divers, int stall_events, int root_form,
+                                                         LpxCutOpts* root_cuts, int tighten, out LpxResult result, out LpxBnbBoundedInfo info,
+                                                         out LpxBnbDiversInfo dinfo, out LpxBnbGuardInfo ginfo, out LpxBnbCutInfo cinfo,
+                                                         out LpxBnbFixInfo finfo);
 
         // ---- branch-and-bound node and child assembly on device handles, the parent store and the batched read-back, include/lpx.h ----
         // any of R / C / ld may be null

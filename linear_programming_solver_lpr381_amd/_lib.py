@@ -200,6 +200,16 @@ class PrimalRecord(C.Structure):
                 ("z", C.c_double)]
 
 
+class FixList(C.Structure):
+    """lpx_fix_list (include/lpx.h): the caller-owned list of the columns a node tightened, as the triples of a bound edit."""
+    _fields_ = [("cap", C.c_int32), ("n", C.c_int32), ("cols", ip), ("lower", dp), ("upper", dp)]
+
+
+class BnbFixInfo(C.Structure):
+    """lpx_bnb_fix_info (include/lpx.h): the reduced-cost tightening counters of lpx_solve_bnb_bounded10."""
+    _fields_ = [("tightened_nodes", C.c_int64), ("tightened_cols", C.c_int64), ("max_per_node", C.c_int64)]
+
+
 class Parsed(C.Structure):
     _fields_ = [("sense", C.c_int), ("n", C.c_int), ("m", C.c_int), ("c", dp), ("A", dp), ("rel", ip),
                 ("b", dp), ("ragged", C.c_int)]
@@ -432,6 +442,14 @@ def lib() -> C.CDLL:
                                          C.POINTER(BnbDiversInfo), C.POINTER(BnbGuardInfo), C.POINTER(BnbCutInfo)]
     L.lpx_bnb_cut_info_free.argtypes = [C.POINTER(BnbCutInfo)]
     L.lpx_bnb_cut_info_free.restype = None
+    L.lpx_bounded_node5.argtypes = [vp, C.c_int, ip, dp, dp, C.POINTER(RunOpts), C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, u8p,
+                                    C.c_double, C.c_int, C.POINTER(NodeRecord), C.POINTER(GuardRecord), C.POINTER(FixList)]
+    L.lpx_node_batch_run3.argtypes = [vp, C.c_int, ip, ip, ip, dp, dp, C.POINTER(RunOpts), C.c_int, dp, C.c_int, dp, C.c_int, u8p,
+                                      C.c_double, C.POINTER(NodeRecord), C.POINTER(GuardRecord), C.POINTER(FixList), ip]
+    L.lpx_solve_bnb_bounded10.argtypes = [C.POINTER(Problem), dp, dp, u8p, C.POINTER(SolveOpts), C.c_int64, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.POINTER(CutOpts), C.c_int, C.POINTER(Result), C.POINTER(BnbBoundedInfo),
+                                          C.POINTER(BnbDiversInfo), C.POINTER(BnbGuardInfo), C.POINTER(BnbCutInfo),
+                                          C.POINTER(BnbFixInfo)]
     L.lpx_parse_text.argtypes = [C.c_char_p, C.POINTER(Parsed)]
     L.lpx_parsed_free.argtypes = [C.POINTER(Parsed)]
     L.lpx_parsed_free.restype = None

@@ -1,7 +1,7 @@
 // host/bnb_bounded.cpp -- branch and bound by bound changes (include/lpx.h): three drivers around one frame.
 //   SolveBnbBounded   lpx_solve_bnb_bounded / _bounded2 / _bounded3: the root is SolveBounded keeping its handle, and every node after
 //                     it is ONE lpx_bounded_node (flagged search: lpx_bounded_node2 / _node3) call on that handle
-//   SolveBnbDivers    lpx_solve_bnb_bounded4 / 6 / 7: W handles, a round is ONE lpx_node_batch_run (_run_probe, _run2)
+//   SolveBnbDivers    lpx_solve_bnb_bounded4 / 6 / 7 / 10: W handles, a round is ONE lpx_node_batch_run (_run_probe, _run2, _run3)
 //   SolveBnbPlunge    lpx_solve_bnb_bounded5: the same rounds with ONE lpx_node_batch_plunge, chains of up to D nodes
 // A node is its path of (var, lower, upper) overrides and what a call sends are the columns whose bounds differ from the bounds now
 // on the device, in ascending order: no tableau is copied, parked or reshaped, and the node store is a few bytes per node.  Search
@@ -260,8 +260,18 @@ SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<doubl
 SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
                              int search_flags, int divers, BnbDiversInfo& dinfo, const BnbStrong* strong, BnbStrongInfo* sinfo,
-                             int stall_events, BnbGuardInfo* ginfo, int root_form, const lpx_cut_opts* root_cuts, BnbCutInfo* cinfo)
+                             int stall_events, BnbGuardInfo* ginfo, int root_form, const lpx_cut_opts* root_cuts, BnbCutInfo* cinfo,
+                             int tighten, BnbFixInfo* finfo)
 {
+    // tighten = 1 (lpx_solve_bnb_bounded10): the evaluate step is ONE lpx_node_batch_run3 whose entries carry fix_bound = best + EPS of
+    // the start of the round (-inf without an incumbent); the decide step applies the reported triples to the bounds it holds for
+    // the diver's handle -- the kernel has applied them to the handle already -- and hands them down both children's paths.  The
+    // plunge, the probes and the sequential driver have no tightening.
+    BnbFixInfo fdummy;
+    BnbFixInfo& fi = finfo ? *finfo : fdummy;
+    fi = BnbFixInfo();
+    const bool tightening = tighten == 1 && stall_events >= 0 && !strong;
+    std::vector<lpx_fix_list> fixes; std::vector<double> fix_bounds, fix_lower, fix_upper; std::vector<int32_t> fix_cols;
     // root_cuts != null (lpx_solve_bnb_bounded9): the root's handle gets spare capacity, lpx_bounded_cut_loop runs on it, and the
     // divers start from the handle the loop leaves; nothing else of the search changes (the cuts hold in the whole tree).
     BnbCutInfo cdummy;
@@ -377,6 +387,15 @@ SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double
             rc = lpx_node_batch_run_probe(pool.batch, B, slot.data(), Ks.data(), cols.data(), clo.data(), cub.data(), &o,
                                           LPX_BDUAL_SKIP_FIXED | search_flags, cutoffs.data(), prunes.data(), n, mask, EPS,
                                           strong->cand_max, strong->probe_iter, recs.data(), heads.data(), probes.data(), rcs.data());
+        } else if (tightening) {
+            guards.resize((size_t)B);
+            fix_bounds.assign((size_t)B, best + EPS);                       // -inf while there is no incumbent
+            fixes.resize((size_t)B); fix_cols.resize((size_t)B * n); fix_lower.resize((size_t)B * n); fix_upper.resize((size_t)B * n);
+            for (int i = 0; i < B; ++i)
+                fixes[i] = lpx_fix_list{n, 0, fix_cols.data() + (size_t)i * n, fix_lower.data() + (size_t)i * n, fix_upper.data() + (size_t)i * n};
+            rc = lpx_node_batch_run3(pool.batch, B, slot.data(), Ks.data(), cols.data(), clo.data(), cub.data(), &o,
+                                     LPX_BDUAL_SKIP_FIXED | search_flags, cutoffs.data(), stall_events, fix_bounds.data(), n, mask, EPS,
+                                     recs.data(), guards.data(), fixes.data(), rcs.data());
         } else if (guarded) {
             guards.resize((size_t)B);
             rc = lpx_node_batch_run2(pool.batch, B, slot.data(), Ks.data(), cols.data(), clo.data(), cub.data(), &o,
@@ -403,6 +422,9 @@ SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double
             const lpx_node_record& rec = recs[i];
             const Node& node = D.node;
             const int64_t index = info.nodes++;
+            const int nfix = tightening ? fixes[i].n : 0;
+            for (int k = 0; k < nfix; ++k) { D.nb_lo[fixes[i].cols[k]] = fixes[i].lower[k]; D.nb_ub[fixes[i].cols[k]] = fixes[i].upper[k]; }
+            if (nfix > 0) { fi.tightened_nodes++; fi.tightened_cols += nfix; if (nfix > fi.max_per_node) fi.max_per_node = nfix; }
             D.cur_lo = D.nb_lo; D.cur_ub = D.nb_ub;
             const bool limit = LogNode(info, index, node.depth, Ks[i], rec, o.max_iter);
             dinfo.round.push_back(round); dinfo.diver.push_back(slot[i]);
@@ -433,6 +455,10 @@ SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double
                 info.log.back().var = v;
             }
             Node fl{node.depth + 1, node.path}, ce{node.depth + 1, node.path};
+            for (int k = 0; k < nfix; ++k) {                            // in front of the branching override
+                const Override ov{fixes[i].cols[k], fixes[i].lower[k], fixes[i].upper[k]};
+                fl.path.push_back(ov); ce.path.push_back(ov);
+            }
             fl.path.push_back(Override{v, D.nb_lo[v], std::floor(xv)});
             ce.path.push_back(Override{v, std::ceil(xv), D.nb_ub[v]});
             if (push_fl) D.stack.push_back(std::move(fl));

@@ -266,6 +266,8 @@ struct BnbGuardInfo { int64_t guarded_nodes = 0, bland_events = 0, max_events = 
 // The cut loop at the root (lpx_solve_bnb_bounded9): the loop's record; ran = 0 with spare = 0 (no capacity that keeps the nodes on chip).
 struct BnbCutInfo { int ran = 0, spare = 0, rounds = 0, added = 0, purged = 0, stop = 0, status = 0, R = 0, C = 0; int64_t events = 0;
                     std::vector<double> z_before, z_after; };
+// Reduced-cost tightening (lpx_solve_bnb_bounded10): nodes that tightened a column, the columns, the most of one node.
+struct BnbFixInfo { int64_t tightened_nodes = 0, tightened_cols = 0, max_per_node = 0; };
 struct BnbStrongInfo { int64_t probe_launches = 0, probes = 0, probe_events = 0, probe_limit = 0, pruned_by_probe = 0, changed_picks = 0; };
 SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
@@ -275,7 +277,9 @@ SimplexResult SolveBnbDivers(const LPProblem& original, const std::vector<double
                              struct BnbGuardInfo* ginfo = nullptr,
                              int root_form = -1,          // lpx_solve_bnb_bounded8: LPX_NODE_* of the root solve; -1: lpx_bounded_run
                              const lpx_cut_opts* root_cuts = nullptr,     // lpx_solve_bnb_bounded9: lpx_bounded_cut_loop at the root, the divers start from its handle
-                             struct BnbCutInfo* cinfo = nullptr);
+                             struct BnbCutInfo* cinfo = nullptr,
+                             int tighten = 0,             // lpx_solve_bnb_bounded10: 1, the round is ONE lpx_node_batch_run3 (never with strong)
+                             struct BnbFixInfo* finfo = nullptr);
 // The search by W divers that plunge (lpx_solve_bnb_bounded5): one lpx_node_batch_plunge per round, up to `plunge` nodes per diver.
 struct BnbPlungeInfo { int64_t launched = 0, dropped = 0, longest_chain = 0; std::vector<int32_t> step; };
 SimplexResult SolveBnbPlunge(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,

@@ -8,6 +8,7 @@
 // it to the kernels of lpx_bounded_node.hip).  A file of its own because the kernel's code depends on what else its translation
 // unit holds: alone it is the code it was before the text was shared (profiles/r18_onchip_text_isa.md).
 #define LPX_ONCHIP_GUARD 1
+#define LPX_ONCHIP_FIX 0
 #include "lpx_onchip.h"
 
 namespace lpx {

@@ -1,7 +1,8 @@
-// lpx_bounded_node_body.h -- the body of the on-chip node, included as the text of ALL THREE of its kernels: lpx_bounded_node_onchip
+// lpx_bounded_node_body.h -- the body of the on-chip node, included as the text of ALL FOUR of its kernels: lpx_bounded_node_onchip
 // (one node, the record a kernel argument) and lpx_bounded_nodes_onchip (the batch, workgroup b takes P[b]) in lpx_bounded_node.hip,
-// and lpx_bounded_guard_onchip (the batch with the stall guard) in lpx_bounded_guard.hip.  Not a header in the usual sense: it is a
-// sequence of statements that expects `const NodeParams N` (or `NodeParams N`) in scope and the file's switch GUARD (lpx_onchip.h),
+// lpx_bounded_guard_onchip (the batch with the stall guard) in lpx_bounded_guard.hip, and lpx_bounded_fix_onchip (that batch with
+// reduced-cost tightening behind the pick, step 7b, under the file switch LPX_ONCHIP_FIX) in lpx_bounded_fix.hip.  Not a header in
+// the usual sense: it is a sequence of statements that expects `const NodeParams N` (or `NodeParams N`) in scope and the file's switch GUARD (lpx_onchip.h),
 // and may `return` from the kernel.  It is the sequence of its own steps 1-4, 8 and 9; steps 2b, 5, 6 and 7 are the step files that
 // the plunge and the probes include too (lpx_onchip_count.h, _flips.h, _dual.h, _pick.h), which find what differs between the
 // kernels under the names declared here: basis, flip, trace, trace_cap, dirty, lo_used, max_iter, stall_events.  There is one text
@@ -119,6 +120,12 @@
     double x_var = 0.0;
 #include "lpx_onchip_pick.h"
 
+#if LPX_ONCHIP_FIX      // ---- 7b. reduced-cost bound tightening: the text of lpx_bounded_fix_onchip alone (a preprocessor switch, so
+    // that the other kernels of this body keep their instruction text); the kernel declares fix_bound and the list's arrays
+    int nfix = 0;
+#include "lpx_onchip_fix.h"
+#endif
+
     // ---- 8. back to global memory: the tableau when it changed, the contiguous RHS copy, the state record
     if (dirty)
         for (int i = wave; i < R; i += OC_NW) {
@@ -137,4 +144,7 @@
         o->status = status; o->events = iter; o->kind0 = k0; o->kind1 = k1; o->flips = nflips; o->unrepairable = 0; o->inf_k = -1;
         o->var = var; o->candidates = total; o->x_var = x_var; o->z = zrow[Cm];
         if (GUARD) { GuardOut* g = reinterpret_cast<GuardOut*>(o); g->bland_events = bland_events; g->first_bland = first_bland; }
+#if LPX_ONCHIP_FIX
+        o->pad = nfix;                                  // the count of the tightened columns: the record's one spare word
+#endif
     }

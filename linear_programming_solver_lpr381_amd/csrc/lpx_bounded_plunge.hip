@@ -32,6 +32,7 @@
 // double 2, the saved pair at 3 and 4, the column at 5), which is what the last single call would leave there.  The host sizes the
 // staging for max(K, 1) triples.  LDS layout and fit rule: lpx_bounded_node.hip (bounded_node_lds_bytes, lpx_bounded_node_fits).
 #define LPX_ONCHIP_GUARD 0
+#define LPX_ONCHIP_FIX 0
 #include "lpx_onchip.h"        // the launch constants, the refusal record, oc_uniform; through lpx_bounded.h the shared device pieces
 
 namespace lpx {

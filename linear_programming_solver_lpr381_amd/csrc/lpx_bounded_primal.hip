@@ -23,6 +23,7 @@
 // basis, flip, the trace and the state record stay in global memory (a gather or lane 0's few words per event); the normalised
 // pivot row is row r of the tile itself, which the update leaves alone.
 #define LPX_ONCHIP_GUARD 0
+#define LPX_ONCHIP_FIX 0
 #include "lpx_onchip.h"        // the launch constants; through lpx_bounded.h bnd_complement, rs_hysteresis and the reductions
 
 namespace lpx {

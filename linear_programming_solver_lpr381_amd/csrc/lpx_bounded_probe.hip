@@ -18,6 +18,7 @@
 // The candidate passes, the child's edit and the record are this kernel's own; the candidates use the arithmetic of the branch pick
 // (lpx_branch_pick_kernel).  Dynamic LDS: that of the node (bounded_node_lds_bytes): tile [R * S], ub [C], buf [max(R, C)].
 #define LPX_ONCHIP_GUARD 0
+#define LPX_ONCHIP_FIX 0
 #include "lpx_onchip.h"        // the launch constants; through lpx_bounded.h the shared device pieces
 
 namespace lpx {

@@ -117,6 +117,14 @@ void node_onchip_commit(lpx_tableau* t, const NodeOut* rec, bool any_lo, lpx_nod
 void bounds_note_edit(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper);
 int bounded_plunge_ready(const char* what);     // the one-time attribute of the plunge kernel
 int bounded_guard_ready(const char* what);      // the one-time attribute of the guarded node kernel (lpx_bounded_guard.hip)
+// reduced-cost tightening (lpx_bounded_fix.hip), shared by lpx_bounded_node5 and lpx_node_batch_run3
+int bounded_fix_ready(const char* what);        // the one-time attribute of its kernel
+int check_fix_args(double fix_bound, const lpx_fix_list* fix, int nint, const char* what);      // LPX_EINVAL with `what` in front, no device
+size_t fix_list_bytes(int nint);                // the pinned arrays of one entry's list: upper, lower (double) and cols (int32), nint each
+void fix_list_place(char* at, int nint, FixParams* p);             // ... and their places in p
+// what the tightened columns of a finished node leave on the host side of its handle (as a bound edit with these triples would),
+// and the caller's list filled from the kernel's
+void fix_commit(lpx_tableau* t, int n, const FixParams& p, lpx_fix_list* fix);
 // the probes (lpx_bounded_probe.hip), shared by lpx_bounded_probe and lpx_node_batch_run_probe
 int bounded_probe_ready(const char* what);      // the one-time attribute of the probe kernel
 int check_probe_args(int cand_max, int probe_iter, const char* what);      // LPX_EINVAL with `what` in front, no device

@@ -127,6 +127,14 @@ struct GuardOut { NodeOut o; int32_t bland_events, first_bland; };
 static_assert(sizeof(GuardOut) == 64, "the node record and the guard record share one 64-byte slot");
 hipError_t bounded_guard_init();                    // one-time function attribute
 hipError_t launch_bounded_guard_onchip(const NodeParams* P, int B, size_t lds, hipStream_t s);
+// the node with reduced-cost tightening (lpx_bounded_fix.hip): the guarded node with step 7b (lpx_onchip_fix.h) behind its pick.
+// One batch-shaped kernel; NodeIn::stall_events = INT_MAX stands for "no guard".  fix_bound travels around the node's record, so
+// NodeIn and the records of the other kernels stay as they are.  cols / lower / upper: the entry's list of tightened columns, nint
+// entries each, in memory the host reads after its one wait; their count comes back in NodeOut::pad, the one spare word of the
+// 64-byte record slot (the guard record fills the rest), which no other kernel writes.
+struct FixParams { NodeParams n; double fix_bound; int32_t* cols; double* lower; double* upper; };
+hipError_t bounded_fix_init();                      // one-time function attribute
+hipError_t launch_bounded_fix_onchip(const FixParams* P, int B, size_t lds, hipStream_t s);
 // the plunge (lpx_bounded_plunge.hip): workgroup b evaluates a chain of up to P[b].depth nodes with the tile staying in LDS.
 // n.out is the first of `depth` records, 64 bytes apart; *steps = the records written; the chain stops at z <= prune.
 struct PlungeParams { NodeParams n; double prune; int32_t* steps; int32_t depth, pad; };

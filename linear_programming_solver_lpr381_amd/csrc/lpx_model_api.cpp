@@ -420,7 +420,8 @@ static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const do
                             const BnbStrong* strong = nullptr, lpx_bnb_strong_info* sinfo = nullptr,      // strong: lpx_solve_bnb_bounded6, LPX_BRANCH_STRONG
                             int stall_events = -1, lpx_bnb_guard_info* ginfo = nullptr,                   // stall_events >= 0: lpx_solve_bnb_bounded7
                             int root_form = -1,                                                           // lpx_solve_bnb_bounded8: the root's form
-                            const lpx_cut_opts* root_cuts = nullptr, lpx_bnb_cut_info* cinfo = nullptr)   // lpx_solve_bnb_bounded9: cuts at the root
+                            const lpx_cut_opts* root_cuts = nullptr, lpx_bnb_cut_info* cinfo = nullptr,   // lpx_solve_bnb_bounded9: cuts at the root
+                            int tighten = 0, lpx_bnb_fix_info* finfo = nullptr)                           // lpx_solve_bnb_bounded10: reduced-cost tightening
 {
     if (!p || !out) { set_error(std::string(what) + ": null argument"); return LPX_EINVAL; }
     std::memset(out, 0, sizeof(*out));
@@ -430,6 +431,7 @@ static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const do
     if (sinfo) std::memset(sinfo, 0, sizeof(*sinfo));
     if (ginfo) std::memset(ginfo, 0, sizeof(*ginfo));
     if (cinfo) std::memset(cinfo, 0, sizeof(*cinfo));
+    if (finfo) std::memset(finfo, 0, sizeof(*finfo));
     lpx_solve_opts d; if (!o) { lpx_default_solve_opts(&d); o = &d; }
     return guarded(what, [&]() -> int {
         EngineOptions e = to_engine(o);
@@ -445,8 +447,9 @@ static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const do
         BnbPlungeInfo pi;
         BnbStrongInfo si;
         BnbGuardInfo gi;
+        BnbFixInfo fi;
         SimplexResult r = stall_events >= 0 ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di, nullptr, nullptr, stall_events, &gi, root_form,
-                                                             root_cuts, &ci)
+                                                             root_cuts, &ci, tighten, &fi)
                         : strong ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di, strong, &si)
                         : plunge ? SolveBnbPlunge(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, plunge, di, pi)
                         : divers ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di)
@@ -458,6 +461,7 @@ static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const do
             cinfo->n_z = (int32_t)ci.z_before.size();
             cinfo->z_before = dup_vec(ci.z_before); cinfo->z_after = dup_vec(ci.z_after);
         }
+        if (finfo) { finfo->tightened_nodes = fi.tightened_nodes; finfo->tightened_cols = fi.tightened_cols; finfo->max_per_node = fi.max_per_node; }
         if (ginfo) { ginfo->guarded_nodes = gi.guarded_nodes; ginfo->bland_events = gi.bland_events; ginfo->max_events = gi.max_events; }
         if (sinfo) {
             sinfo->probe_launches = si.probe_launches; sinfo->probes = si.probes; sinfo->probe_events = si.probe_events;
@@ -580,6 +584,25 @@ int lpx_solve_bnb_bounded9(const lpx_problem* p, const double* lower, const doub
     // root_cuts == NULL: the call of lpx_solve_bnb_bounded8 itself
     return solve_bnb_bounded(p, lower, upper, is_int, o, max_nodes, search_flags, out, info, "lpx_solve_bnb_bounded9", -1, divers, dinfo,
                              0, nullptr, nullptr, nullptr, stall_events, ginfo, root_form == LPX_NODE_LAUNCHES ? -1 : root_form, root_cuts, cinfo);
+}
+
+int lpx_solve_bnb_bounded10(const lpx_problem* p, const double* lower, const double* upper, const uint8_t* is_int,
+                            const lpx_solve_opts* o, int64_t max_nodes, int search_flags, int divers, int stall_events, int root_form,
+                            const lpx_cut_opts* root_cuts, int tighten, lpx_result* out, lpx_bnb_bounded_info* info,
+                            lpx_bnb_divers_info* dinfo, lpx_bnb_guard_info* ginfo, lpx_bnb_cut_info* cinfo, lpx_bnb_fix_info* finfo)
+{
+    if (divers < 1 || divers > 1024) { set_error("lpx_solve_bnb_bounded10: divers is outside [1, 1024]"); return LPX_EINVAL; }
+    if (stall_events < 0) { set_error("lpx_solve_bnb_bounded10: stall_events is negative"); return LPX_EINVAL; }
+    if (root_form != LPX_NODE_LAUNCHES && root_form != LPX_NODE_ONCHIP && root_form != LPX_NODE_AUTO) {
+        set_error("lpx_solve_bnb_bounded10: unknown root_form");
+        return LPX_EINVAL;
+    }
+    if (root_cuts) if (int rc = check_cut_opts(root_cuts, "lpx_solve_bnb_bounded10")) return rc;
+    if (tighten != 0 && tighten != 1) { set_error("lpx_solve_bnb_bounded10: tighten is neither 0 nor 1"); return LPX_EINVAL; }
+    // tighten == 0: the call of lpx_solve_bnb_bounded9 itself
+    return solve_bnb_bounded(p, lower, upper, is_int, o, max_nodes, search_flags, out, info, "lpx_solve_bnb_bounded10", -1, divers, dinfo,
+                             0, nullptr, nullptr, nullptr, stall_events, ginfo, root_form == LPX_NODE_LAUNCHES ? -1 : root_form, root_cuts, cinfo,
+                             tighten, finfo);
 }
 
 void lpx_bnb_cut_info_free(lpx_bnb_cut_info* cinfo)

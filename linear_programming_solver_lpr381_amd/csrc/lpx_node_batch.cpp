@@ -5,6 +5,8 @@
 // (lpx_bounded_probe.hip) enqueued behind the node launch: two launches, one wait.
 // lpx_node_batch_run2 is the same body again with the stall guard (include/lpx.h): stall_events = 0 is lpx_node_batch_run's launch, above 0
 // the one launch is lpx_bounded_guard_onchip (lpx_bounded_guard.hip), which leaves a guard record behind each node record.
+// lpx_node_batch_run3 is that body once more with reduced-cost tightening (include/lpx.h): when some entry's fix_bound is not -inf the
+// one launch is lpx_bounded_fix_onchip (lpx_bounded_fix.hip), whose records carry each entry's fix_bound and the places of its list.
 // lpx_node_batch_primal is the batch of bounded PRIMAL solves (lpx_bounded_primal.hip): no edit, no mask, no pick, its own small slab.
 // lpx_node_batch_plunge (lpx_bounded_plunge.hip) has its own slab layout and its own walk over a chain's records; what it does as
 // the others do -- the checks of the flags and of an entry, the growth of the buffers, the mask, the header and the parameter
@@ -227,14 +229,19 @@ struct ProbeArgs { const double* prune; int cand_max, probe_iter; lpx_probe_head
 // lpx_node_batch_run2 in the same body (gd non-null, never together with pr): with stall_events > 0 the one launch is the guarded
 // kernel's (lpx_bounded_guard.hip), which leaves a guard record in the 64-byte slot of each node record.
 struct GuardArgs { int stall_events; lpx_guard_record* guard; };
+// lpx_node_batch_run3 in the same body (fx non-null, always with gd, never with pr): fix_bound per entry; when one of them is not
+// -inf the one launch is the kernel of lpx_bounded_fix.hip, which lists the columns it tightened per entry.
+struct FixArgs { const double* fix_bound; lpx_fix_list* fix; };
 
 static int node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const int32_t* K, const int32_t* cols, const double* lower,
                           const double* upper, const lpx_run_opts* o, int flags, const double* cutoff, int nint, const uint8_t* is_int,
                           double tol, lpx_node_record* out, int32_t* rc, const ProbeArgs* pr, const char* name,
-                          const GuardArgs* gd = nullptr)
+                          const GuardArgs* gd = nullptr, const FixArgs* fx = nullptr)
 {
     const std::string w = name;
     const int stall_events = gd ? gd->stall_events : 0;
+    const double ninf = -1.0 / 0.0;
+    bool fixing = false;
     // ---- 1. every argument of every entry, before anything is written and before any device check
     if (!slot || !K || !out || !rc) { set_error(w + ": null " + (!slot ? "slot" : !K ? "K" : !out ? "out" : "rc")); return LPX_EINVAL; }
     if (stall_events < 0) { set_error(w + ": stall_events is negative"); return LPX_EINVAL; }
@@ -247,6 +254,15 @@ static int node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const i
     if (pr)
         for (int i = 0; i < B; ++i)
             if (pr->prune[i] != pr->prune[i]) { set_error(w + ": entry " + std::to_string(i) + ": prune is NaN"); return LPX_EINVAL; }
+    if (fx) {
+        if (!fx->fix_bound) { set_error(w + ": null fix_bound"); return LPX_EINVAL; }
+        for (int i = 0; i < B; ++i) {
+            const lpx_fix_list* fl = fx->fix ? &fx->fix[i] : nullptr;
+            if (check_fix_args(fx->fix_bound[i], fl, nint, name))        // again with the entry in front: no string per entry in the steady state
+                return check_fix_args(fx->fix_bound[i], fl, nint, (w + ": entry " + std::to_string(i)).c_str());
+            if (fx->fix_bound[i] != ninf) fixing = true;
+        }
+    }
     lpx_run_opts d;
     { int r = begin_call(w, b, B, o, d); if (r) return r; }
     size_t sumK = 0, in_bytes = 0, edit_bytes = 0, lds = 0;
@@ -265,14 +281,18 @@ static int node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const i
     }
     int r = ensure_device(); if (r) return r;
     if (pr) { r = bounded_probe_ready(name); if (r) return r; }
-    if (stall_events > 0) { r = bounded_guard_ready(name); if (r) return r; }
+    if (fixing) { r = bounded_fix_ready(name); if (r) return r; }
+    else if (stall_events > 0) { r = bounded_guard_ready(name); if (r) return r; }
+    if (fx && fx->fix) for (int i = 0; i < B; ++i) fx->fix[i].n = 0;
     if (gd && gd->guard) for (int i = 0; i < B; ++i) { gd->guard[i].bland_events = 0; gd->guard[i].first_bland = -1; }
 
     // ---- 2. the buffers: grown to twice the need, and only when the need outgrows them
     const size_t nrec = pr ? 2 * (size_t)pr->cand_max : 0;
     const size_t o_out = up16(sizeof(NodeParams) * (size_t)B), o_in = o_out + kOut * (size_t)B, o_pp = up16(o_in + in_bytes),
                  o_head = o_pp + up16(sizeof(ProbeParams) * (size_t)B), o_prec = o_head + sizeof(lpx_probe_head) * (size_t)B,
-                 need = pr ? o_prec + sizeof(lpx_probe_record) * nrec * (size_t)B : o_in + in_bytes;
+                 o_fp = up16(o_in + in_bytes), o_list = o_fp + up16(sizeof(FixParams) * (size_t)B),     // the tightening: records, lists
+                 need = pr ? o_prec + sizeof(lpx_probe_record) * nrec * (size_t)B
+                      : fixing ? o_list + fix_list_bytes(nint) * (size_t)B : o_in + in_bytes;
     r = ensure_buffers(b, need, edit_bytes, ws_bytes); if (r) return r;
     hipStream_t s = b->streams[0];
     const bool has_mask = is_int && nint > 0;
@@ -281,7 +301,8 @@ static int node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const i
     // ---- 3. the slab: a parameter record, a header with its triples and a result record per entry
     NodeParams* P = reinterpret_cast<NodeParams*>(b->slab);
     sumK = 0;
-    const EntryOpts eo{o, flags, nint, stall_events, has_mask, tol};
+    const EntryOpts eo{o, flags, nint, fixing && stall_events == 0 ? INT32_MAX : stall_events, has_mask, tol};   // the fix kernel carries the guard: INT_MAX = never
+    FixParams* F = reinterpret_cast<FixParams*>(b->slab + o_fp);
     for (int i = 0; i < B; ++i) {
         lpx_tableau* t = b->h[slot[i]];
         const int k = K[i];
@@ -296,12 +317,18 @@ static int node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const i
                          in->lo_used != 0, b->probews + b->off_ws[i], n.out, reinterpret_cast<lpx_probe_head*>(b->slab + o_head) + i,
                          reinterpret_cast<lpx_probe_record*>(b->slab + o_prec) + nrec * (size_t)i,
                          reinterpret_cast<ProbeParams*>(b->slab + o_pp) + i);
+        if (fixing) {
+            n.out->pad = 0;                                              // a refused edit writes no count
+            F[i].n = n; F[i].fix_bound = fx->fix_bound[i];
+            fix_list_place(b->slab + o_list + fix_list_bytes(nint) * (size_t)i, nint, &F[i]);
+        }
         sumK += (size_t)k;
     }
 
     // ---- 4. behind the handles' own streams, ONE launch (with pr: the probes behind it), ONE wait
     r = settle_all(b); if (r) return r;
-    if (stall_events > 0) LPX_HIP_TRY(launch_bounded_guard_onchip(P, B, lds, s));
+    if (fixing) LPX_HIP_TRY(launch_bounded_fix_onchip(F, B, lds, s));
+    else if (stall_events > 0) LPX_HIP_TRY(launch_bounded_guard_onchip(P, B, lds, s));
     else LPX_HIP_TRY(launch_bounded_nodes_onchip(P, B, lds, s));
     if (pr) LPX_HIP_TRY(launch_bounded_probe_onchip(reinterpret_cast<const ProbeParams*>(b->slab + o_pp), B, pr->cand_max, lds, s));
     LPX_HIP_TRY(hipStreamSynchronize(s));
@@ -318,7 +345,7 @@ static int node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const i
         const size_t at0 = sumK;
         sumK += (size_t)K[i];
         const NodeOut* rec = reinterpret_cast<const NodeOut*>(b->slab + o_out + kOut * (size_t)i);
-        if (stall_events > 0 && gd->guard) {
+        if ((stall_events > 0 || fixing) && gd->guard) {
             const GuardOut* g = reinterpret_cast<const GuardOut*>(rec);
             gd->guard[i].bland_events = g->bland_events; gd->guard[i].first_bland = g->first_bland;
         }
@@ -331,6 +358,7 @@ static int node_batch_run(lpx_node_batch* b, int B, const int32_t* slot, const i
         }
         node_onchip_commit(t, rec, b->any_lo[i] != 0, &out[i]);
         if (K[i] > 0) bounds_note_edit(t, K[i], cols + at0, lower + at0, upper + at0);
+        if (fixing && fx->fix_bound[i] != ninf) fix_commit(t, rec->pad, F[i], &fx->fix[i]);
         rc[i] = rec->status;
     }
     return 0;
@@ -349,6 +377,16 @@ int lpx_node_batch_run2(lpx_node_batch* b, int B, const int32_t* slot, const int
 {
     const GuardArgs gd{stall_events, guard};
     return node_batch_run(b, B, slot, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, rc, nullptr, "lpx_node_batch_run2", &gd);
+}
+
+int lpx_node_batch_run3(lpx_node_batch* b, int B, const int32_t* slot, const int32_t* K, const int32_t* cols, const double* lower,
+                        const double* upper, const lpx_run_opts* o, int flags, const double* cutoff, int stall_events, const double* fix_bound,
+                        int nint, const uint8_t* is_int, double tol, lpx_node_record* out, lpx_guard_record* guard, lpx_fix_list* fix,
+                        int32_t* rc)
+{
+    const GuardArgs gd{stall_events, guard};
+    const FixArgs fx{fix_bound, fix};
+    return node_batch_run(b, B, slot, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, rc, nullptr, "lpx_node_batch_run3", &gd, &fx);
 }
 
 int lpx_node_batch_run_probe(lpx_node_batch* b, int B, const int32_t* slot, const int32_t* K, const int32_t* cols, const double* lower,

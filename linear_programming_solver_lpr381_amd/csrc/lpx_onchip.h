@@ -1,5 +1,6 @@
 // lpx_onchip.h -- what the on-chip forms of the bounded branch-and-bound node share as an ordinary header: lpx_bounded_node.hip (the
-// node and the batch), lpx_bounded_guard.hip (the guarded node), lpx_bounded_plunge.hip and lpx_bounded_probe.hip.  The launch constants, the refusal record
+// node and the batch), lpx_bounded_guard.hip (the guarded node), lpx_bounded_fix.hip (the node with reduced-cost tightening),
+// lpx_bounded_plunge.hip and lpx_bounded_probe.hip.  The launch constants, the refusal record
 // and the wave-uniform helpers stand here once.  The steps of a node are not functions but included text, one file per step
 // (lpx_onchip_count.h, lpx_onchip_flips.h, lpx_onchip_dual.h, lpx_onchip_pick.h; the reason is in lpx_bounded_node_body.h).  The fit
 // rule (bounded_node_lds_bytes, bounded_node_fits) is declared in lpx_internal.h, where the host files see it, and defined in
@@ -15,6 +16,13 @@ namespace lpx {
 #error "define LPX_ONCHIP_GUARD as 0 or 1 in front of lpx_onchip.h"
 #endif
 static constexpr bool GUARD = LPX_ONCHIP_GUARD != 0;
+// Whether the node body carries the reduced-cost tightening step (lpx_onchip_fix.h, between the pick and the write-back) is a
+// second switch of the same kind, LPX_ONCHIP_FIX: 1 in lpx_bounded_fix.hip alone, 0 in every other file, whose kernels keep the
+// text they had.  It is read by the preprocessor only: the body has one `#if` on it around the step and one around the count in the
+// record (the step's names do not exist in the other kernels, so a constant would not do).
+#ifndef LPX_ONCHIP_FIX
+#error "define LPX_ONCHIP_FIX as 0 or 1 in front of lpx_onchip.h"
+#endif
 
 static constexpr int OC_NT = SEL_NT, OC_NW = SEL_NW;    // one workgroup x 1024 lanes per node, 16 waves
 static constexpr size_t OC_LDS_TOTAL = 160 * 1024;      // one compute unit

@@ -317,6 +317,46 @@ int lpx::bounded_guard_ready(const char* what)
     return 0;
 }
 
+int lpx::bounded_fix_ready(const char* what)
+{
+    static std::once_flag once; static hipError_t init_err = hipSuccess;
+    std::call_once(once, [] { init_err = bounded_fix_init(); });
+    if (init_err != hipSuccess) { set_error(std::string(what) + ": kernel attribute setup failed: " + hipGetErrorString(init_err)); return LPX_EDEVICE; }
+    return 0;
+}
+
+int lpx::check_fix_args(double fix_bound, const lpx_fix_list* fix, int nint, const char* what)
+{
+    const char* msg = nullptr;                          // no string is built on the way that every call of a search takes
+    if (fix_bound != fix_bound) msg = ": fix_bound is NaN";
+    else if (!fix) { if (fix_bound != -1.0 / 0.0) msg = ": null fix"; }
+    else if (fix->cap < nint) msg = ": fix->cap is below nint";
+    else if (nint > 0 && (!fix->cols || !fix->lower || !fix->upper)) msg = ": null array in fix";
+    if (!msg) return 0;
+    set_error(std::string(what) + msg);
+    return LPX_EINVAL;
+}
+
+size_t lpx::fix_list_bytes(int nint) { return ((size_t)nint * (2 * sizeof(double) + sizeof(int32_t)) + 15) & ~(size_t)15; }
+
+void lpx::fix_list_place(char* at, int nint, FixParams* p)
+{
+    p->upper = reinterpret_cast<double*>(at);
+    p->lower = p->upper + nint;
+    p->cols = reinterpret_cast<int32_t*>(p->lower + nint);
+}
+
+void lpx::fix_commit(lpx_tableau* t, int n, const FixParams& p, lpx_fix_list* fix)
+{
+    fix->n = n;
+    if (n <= 0) return;
+    std::memcpy(fix->cols, p.cols, sizeof(int32_t) * (size_t)n);
+    std::memcpy(fix->lower, p.lower, sizeof(double) * (size_t)n);
+    std::memcpy(fix->upper, p.upper, sizeof(double) * (size_t)n);
+    for (int k = 0; k < n; ++k) if (fix->lower[k] != 0.0) t->bnd.lo_used = true;
+    bounds_note_edit(t, n, fix->cols, fix->lower, fix->upper);
+}
+
 int lpx::bounded_probe_ready(const char* what)
 {
     static std::once_flag once; static hipError_t init_err = hipSuccess;
@@ -693,22 +733,28 @@ int lpx_bounded_node_fits(int R, int C) { return bounded_node_fits(R, C); }
 // The steady state of a call: the inputs written into the handle's pinned slab, one kernel launch, one wait, the record read
 // from the same slab.  Allocations and the copy of the integer mask happen only when K outgrows the slab or the mask's bytes change.
 // stall_events > 0 (lpx_bounded_node4): the launch is the guarded kernel's (lpx_bounded_guard.hip) as a batch of one, its parameter
-// record in the slab behind the triples; everything else is the same call.
+// record in the slab behind the triples; everything else is the same call.  fix_bound > -inf (lpx_bounded_node5): the launch is that
+// of lpx_bounded_fix.hip, again a batch of one, whose record carries fix_bound and the places of the list behind it in the slab.
 static int bounded_node_onchip(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const lpx_run_opts* o,
                                int flags, double cutoff, int nint, const uint8_t* is_int, double tol, lpx_node_record* out, const char* what,
-                               int stall_events = 0, lpx_guard_record* guard = nullptr)
+                               int stall_events = 0, lpx_guard_record* guard = nullptr, double fix_bound = -1.0 / 0.0,
+                               lpx_fix_list* fix = nullptr)
 {
     const std::string w = what;
+    const bool fixing = fix_bound != -1.0 / 0.0;
     int rc = bounded_ready(t, true); if (rc) return rc;
-    rc = stall_events > 0 ? bounded_guard_ready(what) : bounded_node_ready(what); if (rc) return rc;
+    rc = fixing ? bounded_fix_ready(what) : stall_events > 0 ? bounded_guard_ready(what) : bounded_node_ready(what); if (rc) return rc;
     if (guard) { guard->bland_events = 0; guard->first_bland = -1; }
+    if (fix) fix->n = 0;
     lpx_tableau::Bounds& b = t->bnd;
     std::memset(out, 0, sizeof(*out));
     out->pick.var = -1;
     constexpr size_t kOut = 64, kHdr = kOut + sizeof(NodeIn);
     static_assert(sizeof(NodeOut) <= kOut, "slab layout");
     const size_t o_par = (kHdr + (size_t)K * (2 * sizeof(double) + sizeof(int32_t)) + 15) & ~(size_t)15;
-    const size_t need = stall_events > 0 ? o_par + sizeof(NodeParams) : kHdr + (size_t)K * (2 * sizeof(double) + sizeof(int32_t));
+    const size_t o_list = o_par + ((sizeof(FixParams) + 15) & ~(size_t)15);
+    const size_t need = fixing ? o_list + fix_list_bytes(nint)
+                      : stall_events > 0 ? o_par + sizeof(NodeParams) : kHdr + (size_t)K * (2 * sizeof(double) + sizeof(int32_t));
     if (need > b.nodeio_bytes) {
         LPX_HIP_TRY(hipStreamSynchronize(t->stream));
         if (b.nodeio) hipHostFree(b.nodeio);
@@ -738,7 +784,7 @@ static int bounded_node_onchip(lpx_tableau* t, int K, const int32_t* cols, const
     in->K = K; in->flags = flags; in->nint = nint; in->has_mask = has_mask ? 1 : 0; in->max_iter = o->max_iter;
     in->lo_used = (b.lo_used || any_lo) ? 1 : 0;
     in->eps = o->eps; in->ratio_tol = o->ratio_tol; in->cutoff = cutoff; in->tol = tol;
-    in->stall_events = stall_events;
+    in->stall_events = fixing && stall_events == 0 ? INT32_MAX : stall_events;    // the fix kernel carries the guard: INT_MAX = never
     if (K > 0) {
         double* a = reinterpret_cast<double*>(in + 1);
         std::memcpy(a, lower, sizeof(double) * K);
@@ -750,14 +796,20 @@ static int bounded_node_onchip(lpx_tableau* t, int K, const int32_t* cols, const
     n.rhsbuf = t->rhsbuf; n.basis = t->basis; n.trace = t->trace; n.trace_cap = t->trace_cap; n.st = t->st;
     n.ub = b.ub; n.lo = b.lo; n.flip = b.flip; n.edit = reinterpret_cast<double*>(b.chg); n.mask = b.pickmask;
     n.in = in; n.out = rec;
-    if (stall_events > 0) {
+    FixParams* F = reinterpret_cast<FixParams*>(b.nodeio + o_par);
+    if (fixing) {
+        F->n = n; F->fix_bound = fix_bound;
+        fix_list_place(b.nodeio + o_list, nint, F);
+        rec->pad = 0;                                                            // a refused edit writes no count
+        LPX_HIP_TRY(launch_bounded_fix_onchip(F, 1, bounded_node_lds_bytes(t->R, t->C), t->stream));
+    } else if (stall_events > 0) {
         NodeParams* P = reinterpret_cast<NodeParams*>(b.nodeio + o_par);
         *P = n;
         LPX_HIP_TRY(launch_bounded_guard_onchip(P, 1, bounded_node_lds_bytes(t->R, t->C), t->stream));
     } else
         LPX_HIP_TRY(launch_bounded_node_onchip(n, t->stream));
     LPX_HIP_TRY(hipStreamSynchronize(t->stream));                                // the one wait: the record is in the slab
-    if (stall_events > 0 && guard) {
+    if ((stall_events > 0 || fixing) && guard) {
         const GuardOut* g = reinterpret_cast<const GuardOut*>(rec);
         guard->bland_events = g->bland_events; guard->first_bland = g->first_bland;
     }
@@ -770,6 +822,7 @@ static int bounded_node_onchip(lpx_tableau* t, int K, const int32_t* cols, const
     }
     node_onchip_commit(t, rec, any_lo, out);
     bounds_note_edit(t, K, cols, lower, upper);
+    if (fixing) fix_commit(t, rec->pad, *F, fix);
     return rec->status;
 }
 
@@ -811,6 +864,33 @@ int lpx_bounded_node4(lpx_tableau* t, int K, const int32_t* cols, const double* 
     rc = check_node_opts(t, o, what); if (rc) return rc;
     rc = check_node_fits(t, what); if (rc) return rc;
     return bounded_node_onchip(t, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, what, stall_events, guard);
+}
+
+// The node with reduced-cost tightening (include/lpx.h, "reduced-cost tightening").  fix_bound = -inf is lpx_bounded_node4 in every
+// form; any other value needs the on-chip form (kernel in lpx_bounded_fix.hip).
+int lpx_bounded_node5(lpx_tableau* t, int K, const int32_t* cols, const double* lower, const double* upper, const lpx_run_opts* o,
+                      int flags, double cutoff, int stall_events, double fix_bound, int nint, const uint8_t* is_int, double tol, int form,
+                      lpx_node_record* out, lpx_guard_record* guard, lpx_fix_list* fix)
+{
+    const char* what = "lpx_bounded_node5";
+    const std::string w = what;
+    int rc = check_long_flags(flags, cutoff, what); if (rc) return rc;
+    if (form != LPX_NODE_LAUNCHES && form != LPX_NODE_ONCHIP && form != LPX_NODE_AUTO) { set_error(w + ": unknown form"); return LPX_EINVAL; }
+    if (stall_events < 0) { set_error(w + ": stall_events is negative"); return LPX_EINVAL; }
+    rc = check_fix_args(fix_bound, fix, nint, what); if (rc) return rc;
+    if (guard) { guard->bland_events = 0; guard->first_bland = -1; }
+    if (fix) fix->n = 0;
+    const bool fixing = fix_bound != -1.0 / 0.0;
+    const bool launches = form == LPX_NODE_LAUNCHES || (form == LPX_NODE_AUTO && t && !bounded_node_fits(t->R, t->C));
+    if (launches && stall_events > 0) { set_error(w + ": the stall guard has no launches form"); return LPX_EINVAL; }
+    if (launches && fixing) { set_error(w + ": reduced-cost tightening has no launches form"); return LPX_EINVAL; }
+    if (launches) return bounded_node(t, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, what);
+    rc = check_change_args(t, K, cols, lower, upper, what); if (rc) return rc;
+    rc = check_pick_args(t, nint, tol, out, what); if (rc) return rc;
+    lpx_run_opts d; if (!o) { lpx_default_opts(&d, 1); o = &d; }
+    rc = check_node_opts(t, o, what); if (rc) return rc;
+    rc = check_node_fits(t, what); if (rc) return rc;
+    return bounded_node_onchip(t, K, cols, lower, upper, o, flags, cutoff, nint, is_int, tol, out, what, stall_events, guard, fix_bound, fix);
 }
 
 // ---- GMI cuts on a handle with bounds, and the cut loop at a bounded root (kernels in lpx_cuts.hip) ----

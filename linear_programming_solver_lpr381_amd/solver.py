@@ -389,7 +389,7 @@ class LPSolver:             # Models/LPSolver.cs:6-77
                         candidates: int = 4, probe_iter: Optional[int] = None,
                         stall_events: Optional[int] = None, root_form: Optional[str] = None,
                         root_cuts: Optional[int] = None, cuts_per_round: int = 8, max_active: int = 64,
-                        cut_opts: Optional["CutOpts"] = None) -> SimplexResult:
+                        cut_opts: Optional["CutOpts"] = None, tighten: bool = False) -> SimplexResult:
         """Branch and bound by bound changes on one device tableau (lpx_solve_bnb_bounded): lower <= x <= upper, x_j integer
         where integer[j] (None: every variable); integer variables need finite, integral bounds.  Status OPTIMAL or INFEASIBLE,
         Solution, OptimalValue (user's sense), Nodes, BnbInfo (counters) and BnbLog, a structured array with one record per node
@@ -429,7 +429,22 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         divers from that handle; cut_opts (a CutOpts) gives every option of the loop instead.  BnbInfo then carries cut_ran,
         cut_spare, cut_rounds, cuts_added, cuts_purged, cut_events, cut_stop, cut_R and cut_C, and the result CutZ, an array
         [rounds, 2] of the LP objective in front of and behind every round (internal sense).  Whether the tree shrinks depends
-        on the model.  It cannot be combined with node_form="launches", plunge or branching."""
+        on the model.  It cannot be combined with node_form="launches", plunge or branching.  tighten=True
+        (lpx_solve_bnb_bounded10; False: the paths above, unchanged; without root_form it means root_form="launches"):
+        reduced-cost tightening -- from the first incumbent on, every node that ends OPTIMAL above the incumbent + 1e-6 shrinks,
+        in its own launch, the range of every nonbasic integer column whose reduced cost leaves it less room than its range,
+        and the tighter ranges hold for the node's subtree.  BnbInfo then carries tightened_nodes, tightened_cols and
+        max_per_node.  The tree usually shrinks; no speed-up is promised, and the default stays off.  It cannot be combined
+        with node_form="launches", plunge or branching: those have no tightening."""
+        if tighten:
+            if node_form == "launches":
+                raise ValueError("reduced-cost tightening has no launches form: tighten cannot be combined with node_form='launches'")
+            if plunge is not None:
+                raise ValueError("the plunge driver has no tightening: tighten cannot be combined with plunge")
+            if branching is not None:
+                raise ValueError("the strong-branching driver has no tightening: tighten cannot be combined with branching")
+            if root_form is None:
+                root_form = "launches"
         if root_cuts is not None or cut_opts is not None:
             if node_form == "launches":
                 raise ValueError("root cuts belong to the search by divers: they cannot be combined with node_form='launches'")
@@ -505,7 +520,14 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         sinfo = _lib.BnbStrongInfo()
         ginfo = _lib.BnbGuardInfo()
         cinfo = _lib.BnbCutInfo()
-        if cut_opts is not None:
+        finfo = _lib.BnbFixInfo()
+        if tighten:
+            co = cut_opts.to_c() if cut_opts is not None else None
+            rc = lib().lpx_solve_bnb_bounded10(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), flags, int(divers),
+                                               int(stall_events), _lib.NODE_FORMS[root_form], C.byref(co) if co is not None else None,
+                                               1, C.byref(r), C.byref(info), C.byref(dinfo), C.byref(ginfo), C.byref(cinfo),
+                                               C.byref(finfo))
+        elif cut_opts is not None:
             co = cut_opts.to_c()
             rc = lib().lpx_solve_bnb_bounded9(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), flags, int(divers),
                                               int(stall_events), _lib.NODE_FORMS[root_form], C.byref(co), C.byref(r), C.byref(info),
@@ -555,6 +577,8 @@ class LPSolver:             # Models/LPSolver.cs:6-77
                                                                 "pruned_by_probe", "changed_picks")})
             if stall_events is not None:
                 counters.update({k: getattr(ginfo, k) for k in ("guarded_nodes", "bland_events", "max_events")})
+            if tighten:
+                counters.update({k: getattr(finfo, k) for k in ("tightened_nodes", "tightened_cols", "max_per_node")})
             if cut_opts is not None:
                 counters.update(cut_ran=cinfo.ran, cut_spare=cinfo.spare, cut_rounds=cinfo.rounds, cuts_added=cinfo.added,
                                 cuts_purged=cinfo.purged, cut_events=cinfo.events, cut_stop=_lib.CUTLOOP_STOPS[cinfo.stop] if cinfo.ran else None,

@@ -376,7 +376,8 @@ class DeviceTableau:
 
     def bounded_node(self, cols, lower, upper, nint: int, is_int=None, tol: float = 1e-6,
                      opts: Optional[RunOpts] = None, long_step: bool = False, cutoff: Optional[float] = None,
-                     form: Optional[str] = None, stall_events: Optional[int] = None, **kw) -> dict:
+                     form: Optional[str] = None, stall_events: Optional[int] = None, fix_bound: Optional[float] = None,
+                     **kw) -> dict:
         """One branch-and-bound node in one call (lpx_bounded_node): change_bounds, dualize, the dual loop in which fixed
         columns do not enter, and on OPTIMAL the branch pick.  long_step=True or a cutoff is lpx_bounded_node2: the loop runs
         with those flags and may end with status CUTOFF (no pick).  form "launches" | "onchip" | "auto" is lpx_bounded_node3:
@@ -384,13 +385,46 @@ class DeviceTableau:
         False), "auto" does so iff it fits; the results are bit-equal in every form.  stall_events=S (lpx_bounded_node4; None:
         the calls above): the stall guard -- after S pivots without progress of the objective the loop selects by Bland's rule
         until the objective moves again; 0 is the node without it, above 0 needs the on-chip form (form None means "onchip"
-        then).  The record then also carries bland_events and first_bland.  Returns the node record as a dict."""
+        then).  The record then also carries bland_events and first_bland.  fix_bound=b (lpx_bounded_node5; None: the calls
+        above): reduced-cost tightening -- a node that ends OPTIMAL with z > b shrinks the range of every nonbasic integer
+        column whose reduced cost d leaves it floor((z - b) / d) steps, in the same launch; -inf is the node without it, any
+        other value needs the on-chip form (form None means "onchip" then; stall_events None means 0).  The record then also
+        carries fixed = (cols, lower, upper): the tightened columns, ascending, as the triples of a bound edit.  Returns the
+        node record as a dict."""
         cols = np.ascontiguousarray(np.atleast_1d(cols), dtype=np.int32).reshape(-1)
         lower = np.ascontiguousarray(np.broadcast_to(np.asarray(lower, dtype=np.float64), cols.shape))
         upper = np.ascontiguousarray(np.broadcast_to(np.asarray(upper, dtype=np.float64), cols.shape))
         o = opts if opts is not None else default_opts(True, **kw)
         keep, mp = self._mask(is_int, int(nint))
         rec = _lib.NodeRecord()
+        if fix_bound is not None:
+            fix_bound = float(fix_bound)
+            if fix_bound != fix_bound:
+                raise ValueError("fix_bound is NaN")
+            S = 0 if stall_events is None else int(stall_events)
+            if S < 0:
+                raise ValueError(f"stall_events = {stall_events}: stall_events must not be negative")
+            needs_chip = S > 0 or fix_bound != -np.inf
+            if form is None:
+                form = "onchip" if needs_chip else "launches"
+            if form not in _lib.NODE_FORMS:
+                raise ValueError(f"unknown node form {form!r}")
+            if fix_bound != -np.inf and form == "launches":
+                raise ValueError("reduced-cost tightening has no launches form: fix_bound cannot be combined with form='launches'")
+            flags = (_lib.BDUAL_SKIP_FIXED | (_lib.BDUAL_LONG_STEP if long_step else 0)
+                     | (_lib.BDUAL_CUTOFF if cutoff is not None else 0))
+            g = _lib.GuardRecord()
+            cap = max(int(nint), 0)
+            fc, fl, fu = np.zeros(cap, dtype=np.int32), np.zeros(cap), np.zeros(cap)
+            fx = _lib.FixList(cap, 0, fc.ctypes.data_as(ip), fl.ctypes.data_as(dp), fu.ctypes.data_as(dp))
+            check(lib().lpx_bounded_node5(self._h, len(cols), cols.ctypes.data_as(ip), lower.ctypes.data_as(dp),
+                                          upper.ctypes.data_as(dp), C.byref(o), flags, float(cutoff if cutoff is not None else 0.0),
+                                          S, fix_bound, int(nint), mp, float(tol), _lib.NODE_FORMS[form], C.byref(rec),
+                                          C.byref(g), C.byref(fx)))
+            d = _node_dict(rec)
+            d["bland_events"], d["first_bland"] = g.bland_events, g.first_bland
+            d["fixed"] = (fc[:fx.n].copy(), fl[:fx.n].copy(), fu[:fx.n].copy())
+            return d
         if stall_events is not None:
             if int(stall_events) < 0:
                 raise ValueError(f"stall_events = {stall_events}: stall_events must not be negative")
@@ -530,12 +564,14 @@ class NodeBatch:
                  "flips": recs[i].flips, "z": recs[i].z} for i in range(B)]
 
     def run(self, slots, nodes, nint: int, is_int=None, tol: float = 1e-6, long_step: bool = False, cutoffs=None,
-            opts: Optional[RunOpts] = None, stall_events: Optional[int] = None, **kw) -> list:
+            opts: Optional[RunOpts] = None, stall_events: Optional[int] = None, fix_bounds=None, **kw) -> list:
         """Entry i evaluates nodes[i] = (cols, lower, upper) on handles[slots[i]]; the slots are distinct.  cutoffs: one objective
         cutoff per entry (None: no cutoff).  Returns one record dict per entry in the shape of DeviceTableau.bounded_node; an
         entry the kernel refused (its handle is as it was) has status None, and last_error() holds the first one's message.
         stall_events=S (lpx_node_batch_run2; None: lpx_node_batch_run): every entry runs with the stall guard of
-        DeviceTableau.bounded_node and its record also carries bland_events and first_bland."""
+        DeviceTableau.bounded_node and its record also carries bland_events and first_bland.  fix_bounds (lpx_node_batch_run3;
+        one value or one per entry, -inf = none for that entry): every entry runs with the reduced-cost tightening of
+        DeviceTableau.bounded_node(fix_bound=) and its record also carries fixed = (cols, lower, upper)."""
         if stall_events is not None and int(stall_events) < 0:
             raise ValueError(f"stall_events = {stall_events}: stall_events must not be negative")
         slots = np.ascontiguousarray(np.atleast_1d(slots), dtype=np.int32).reshape(-1)
@@ -565,7 +601,21 @@ class NodeBatch:
         recs = (_lib.NodeRecord * B)()
         rc = np.zeros(B, dtype=np.int32)
         guards = None
-        if stall_events is not None:
+        fixes = None
+        if fix_bounds is not None:
+            fb = np.ascontiguousarray(np.broadcast_to(np.asarray(fix_bounds, dtype=np.float64), (B,)))
+            if np.isnan(fb).any():
+                raise ValueError("fix_bounds holds a NaN")
+            guards = (_lib.GuardRecord * B)()
+            cap = max(int(nint), 0)
+            fc, fl, fu = np.zeros((B, cap), dtype=np.int32), np.zeros((B, cap)), np.zeros((B, cap))
+            fixes = (_lib.FixList * B)(*[_lib.FixList(cap, 0, fc[i].ctypes.data_as(ip), fl[i].ctypes.data_as(dp),
+                                                      fu[i].ctypes.data_as(dp)) for i in range(B)])
+            check(lib().lpx_node_batch_run3(self._h, B, slots.ctypes.data_as(ip), K.ctypes.data_as(ip), cols.ctypes.data_as(ip),
+                                            lower.ctypes.data_as(dp), upper.ctypes.data_as(dp), C.byref(o), flags, cp,
+                                            int(stall_events or 0), fb.ctypes.data_as(dp), int(nint), mp, float(tol), recs, guards,
+                                            fixes, rc.ctypes.data_as(ip)))
+        elif stall_events is not None:
             guards = (_lib.GuardRecord * B)()
             check(lib().lpx_node_batch_run2(self._h, B, slots.ctypes.data_as(ip), K.ctypes.data_as(ip), cols.ctypes.data_as(ip),
                                             lower.ctypes.data_as(dp), upper.ctypes.data_as(dp), C.byref(o), flags, cp,
@@ -579,6 +629,9 @@ class NodeBatch:
             d = _node_dict(recs[i])
             if guards is not None:
                 d["bland_events"], d["first_bland"] = guards[i].bland_events, guards[i].first_bland
+            if fixes is not None:
+                k = fixes[i].n
+                d["fixed"] = (fc[i, :k].copy(), fl[i, :k].copy(), fu[i, :k].copy())
             if rc[i] < 0:
                 d["status"] = None
             out.append(d)

@@ -55,7 +55,8 @@ usage: bench_bnb_bounded.py [--model NAME] [--max-nodes N] [--node-form F] [--di
                             [--compare-plunge LIST [--flag-sets LIST]] [--compare-branching LIST [--flag-sets LIST]]
                             [--branching R [--candidates C] [--probe-iter L]] [--compare-guard LIST [--flag-sets LIST]]
                             [--stall-events S] [--long-step] [--cutoff] [--trace-only] [--compare-root LIST]
-                            [--compare-cuts [LIST] [--rounds LIST] [--cuts-per-round K]] [REPS]
+                            [--compare-cuts [LIST] [--rounds LIST] [--cuts-per-round K]]
+                            [--compare-tighten [LIST] [--flag-sets LIST]] [REPS]
 
 `--compare-root LIST` measures the form of the root solve (lpx_solve_bnb_bounded8) at every W of LIST, with the
 long step and the cutoff: root_form "launches" against "onchip", the sides alternating, one untimed solve each first.  Beside the
@@ -69,7 +70,18 @@ process, the settings alternating, one untimed solve each first.  Per setting: n
 the search runs on.  A setting wins iff its median lies below the baseline's minimum, and loses iff the baseline's median lies below
 its minimum.  Beside the searches it times lpx_bounded_cut_loop alone on the solved root in both node forms (the handle is put back
 from a snapshot between the runs) and checks that the two forms leave the same record.  No ratio is expected in advance: whether the
-tree shrinks depends on the model."""
+tree shrinks depends on the model.
+
+`--compare-tighten [LIST]` measures reduced-cost bound tightening (lpx_solve_bnb_bounded10) at every W of LIST
+(default 1,16,256) and every flag set of `--flag-sets` (default plain,both): the search with tighten=True against the same binary
+with tighten = 0 (root_form "launches", by contract lpx_solve_bnb_bounded9 without cuts), the sides alternating in one process, one
+untimed solve each first, REPS (default 7) timed solves each.  Per side: nodes, events, rounds, the three counters and wall as
+median (min-max); the tightening wins iff its median lies below the baseline's minimum and loses iff the baseline's median lies
+below its minimum.  A side that ends at a node's event limit is reported (`limit`) and not timed against.  Beside the searches it times one node call with K = 0 on the solved root in three kernels -- lpx_bounded_node4
+with stall_events = 0 (the node kernel, its record a kernel argument), with a stall_events it never reaches (the guarded kernel,
+its record read from pinned memory) and lpx_bounded_node5 with a fix_bound so far below z that the step runs and tightens nothing
+(the guarded kernel's shape plus the step).  No
+speed-up is expected in advance: at large W the tighter bounds arrive a round late."""
 import json
 import os
 import statistics
@@ -502,8 +514,103 @@ def compare_cuts(n, m, reps, max_nodes, widths, rounds, K, max_active=64):
     return rec
 
 
+def compare_tighten(n, m, reps, max_nodes, flag_sets, widths):
+    """Reduced-cost tightening (lpx_solve_bnb_bounded10) against the same search without it on binary_ip(n, m) (see the module docstring)."""
+    c, A, rel, b = synth.binary_ip(n, m)
+    p = L.LPProblem.from_arrays(0, c, A[:m], rel[:m], b[:m])
+    rec = {"n": n, "m": m, "bounded_shape": [m + 1, n + m + 1]}
+
+    # one node call with K = 0 on the solved root: the node kernel against the kernel with the step, which tightens nothing
+    T, basis = synth.primal_tableau_from(c, A[:m], b[:m])
+    ub = np.full(T.shape[1] - 1, np.inf); ub[:n] = 1.0
+    none = (np.zeros(0, dtype=np.int32), np.zeros(0), np.zeros(0))
+    with L.DeviceTableau.from_host(T, basis) as dt:
+        dt.set_bounds(ub)
+        dt.bounded_run()
+        z = dt.bounded_node(*none, n, form="onchip")["z"]
+        # node4_guard: the guarded kernel with a threshold it never reaches -- batch-shaped like the kernel with the step, its
+        # parameter record read from pinned host memory, so node5 against it is the step alone
+        calls = {"node4": dict(stall_events=0), "node4_guard": dict(stall_events=1000000), "node5": dict(fix_bound=z - 1e9)}
+        ts = {k: [] for k in calls}
+        fixed = 0
+        for i in range(40 * (reps + 1)):
+            for k, kw in calls.items():
+                t0 = time.perf_counter()
+                r = dt.bounded_node(*none, n, form="onchip", **kw)
+                if i >= 40:
+                    ts[k].append(1e6 * (time.perf_counter() - t0))
+                if k == "node5":
+                    fixed += len(r["fixed"][0])
+        assert fixed == 0, "the timed node call tightened a column"
+        rec["node_call_us"] = {k: stats(ts[k]) for k in calls}
+
+    def solve(W, side, kw):
+        how = dict(tighten=True) if side == "tighten" else dict(root_form="launches")
+        t0 = time.perf_counter()
+        try:
+            r = L.LPSolver().SolveBnbBounded(p, 1.0, max_nodes=max_nodes, divers=W, **how, **kw)
+            r.Limit = None
+        except L.SolverException as e:
+            if e.code != L._lib.ITER_LIMIT:
+                raise
+            r = e.result
+            r.Limit = None if max_nodes and r.Nodes >= max_nodes else str(e)
+        return 1e3 * (time.perf_counter() - t0), r
+
+    sides = ("base", "tighten")
+    for fs in flag_sets:
+        kw = FLAG_SETS[fs]
+        for W in widths:
+            ts, last = {s: [] for s in sides}, {}
+            for i in range(reps + 1):
+                for s in sides:
+                    ms, r = solve(W, s, kw)
+                    if i >= 1:
+                        ts[s].append(ms)
+                    last[s] = r
+            d = {}
+            for s in sides:
+                st, r = stats(ts[s]), last[s]
+                d[s] = {"ms": st, "nodes": int(r.Nodes), "events": r.BnbInfo["events"], "rounds": r.BnbInfo["rounds"],
+                        "max_K": r.BnbInfo["max_K"], "tightened_nodes": r.BnbInfo.get("tightened_nodes", 0),
+                        "tightened_cols": r.BnbInfo.get("tightened_cols", 0), "max_per_node": r.BnbInfo.get("max_per_node", 0),
+                        "optimum": float(r.OptimalValue), "limit": r.Limit}
+            a, t = d["base"]["ms"], d["tighten"]["ms"]
+            limited = last["base"].Limit is not None or last["tighten"].Limit is not None     # a side that ended at a node's event limit: reported, not timed against
+            d["ratio"] = None if limited else t["median"] / a["median"]
+            d["verdict"] = "limit" if limited else "win" if t["median"] < a["min"] else "loss" if a["median"] < t["min"] else "tie"
+            if not (last["base"].Limit or last["tighten"].Limit or max_nodes):
+                assert abs(d["base"]["optimum"] - d["tighten"]["optimum"]) <= 1e-9 * abs(d["base"]["optimum"]), "optimum differs"
+            rec[f"{fs}_W{W}"] = d
+    return rec
+
+
 def main():
     args = sys.argv[1:]
+    if "--compare-tighten" in args:
+        k = args.index("--compare-tighten")
+        widths = [1, 16, 256]
+        if k + 1 < len(args) and args[k + 1][:1].isdigit() and ("," in args[k + 1] or k + 2 < len(args) and args[k + 2][:1].isdigit()):
+            widths = [int(w) for w in args[k + 1].split(",") if w]
+            del args[k + 1]
+        del args[k]
+        only, max_nodes, flag_sets = None, 0, "plain,both"
+        for flag in ("--model", "--max-nodes", "--flag-sets"):
+            if flag in args:
+                j = args.index(flag)
+                if flag == "--model":
+                    only = args[j + 1]
+                elif flag == "--max-nodes":
+                    max_nodes = int(args[j + 1])
+                else:
+                    flag_sets = args[j + 1]
+                del args[j:j + 2]
+        reps = int(args[0]) if args else 7
+        L._lib.check(L._lib.lib().lpx_init(0))
+        out = {name: compare_tighten(n, m, reps, max_nodes, [f for f in flag_sets.split(",") if f and f != "none"], widths)
+               for name, n, m in models() if only is None or name == only}
+        print(json.dumps(out))
+        return
     if "--compare-cuts" in args:
         k = args.index("--compare-cuts")
         widths = [1, 16, 256]

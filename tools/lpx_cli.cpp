@@ -1,7 +1,7 @@
 // lpx_cli -- Linux stand-in for the reference's WinForms host (Form1.cs), over the C ABI of liblpx.so only.
 //
 //   lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]
-//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S] [--root-form F] [--root-cuts N [--cuts-per-round K]]] [--bounded-form F] [--export FILE] INPUT.txt
+//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S] [--root-form F] [--root-cuts N [--cuts-per-round K]] [--tighten]] [--bounded-form F] [--export FILE] INPUT.txt
 //
 // Does what Form1 does around the solvers: reads the model text (Import, Form1.cs:284-296), parses it with the LPParser
 // grammar (lpx_parse_text, Models/LPParser.cs:9-79), runs the algorithm chosen by its dropdown name (btnSolve_Click,
@@ -85,6 +85,7 @@ int main(int argc, char** argv)
     int probe_iter = -1;        // --probe-iter L: the event limit of a probe; -1 = the node's
     int stall_events = -1;      // --stall-events S beside --bnb-bounded: the stall guard (lpx_solve_bnb_bounded7); -1 = not given
     int bounded_form = -1;      // --bounded-form F: LPX_NODE_* of the bounded primal solve (lpx_solve_bounded2); -1 = not given
+    bool tighten = false;       // --tighten beside --bnb-bounded --divers: reduced-cost bound tightening at every node (lpx_solve_bnb_bounded10)
     int root_cuts = -1;         // --root-cuts N beside --bnb-bounded --divers: N rounds of GMI cuts at the root (lpx_solve_bnb_bounded9; K = --cuts-per-round); -1 = not given
     int root_form = -1;         // --root-form F beside --bnb-bounded --divers: LPX_NODE_* of the root solve (lpx_solve_bnb_bounded8); -1 = not given
     struct Bound { bool upper; int index; double value; std::string text; };
@@ -173,6 +174,7 @@ int main(int argc, char** argv)
             if (end == v.c_str() || *end || w < 0 || w > 1000000) { std::fprintf(stderr, "lpx_cli: --root-cuts takes a number of rounds >= 0, got '%s'\n", v.c_str()); return 64; }
             root_cuts = (int)w;
         }
+        else if (a == "--tighten") tighten = true;
         else if (a == "--cut-rounds" && i + 1 < argc) { co.max_rounds = std::atoi(argv[++i]); cut_set = true; }
         else if ((a == "--set-rhs" || a == "--set-cost") && i + 1 < argc) {
             const std::string v = argv[++i];
@@ -191,7 +193,7 @@ int main(int argc, char** argv)
         else if (a == "--export" && i + 1 < argc) exportPath = argv[++i];
         else if (a == "--help" || a == "-h") {
             std::printf("usage: lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]\n"
-                        "               [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S] [--root-form F] [--root-cuts N [--cuts-per-round K]]] [--bounded-form F]\n"
+                        "               [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S] [--root-form F] [--root-cuts N [--cuts-per-round K]] [--tighten]] [--bounded-form F]\n"
                         "               [--export FILE] INPUT.txt\n"
                         "  NAME: Primal Simplex | Revised Primal Simplex | Dual Simplex | Branch and Bound |\n"
                         "        Revised Branch and Bound | Branch and Bound Knapsack | Cutting Plane | Revised Cutting Plane |\n"
@@ -225,6 +227,9 @@ int main(int argc, char** argv)
                         "             (default 8) GMI cuts at the solved root, then the search from that tableau; not with --plunge or --branching\n"
                         "  --root-form launches|onchip|auto: with --bnb-bounded --divers, how the root LP is solved (lpx_solve_bnb_bounded8);\n"
                         "             the node log does not depend on it; not with --plunge or --branching\n"
+                        "  --tighten: with --bnb-bounded --divers, reduced-cost bound tightening (lpx_solve_bnb_bounded10): from the first incumbent\n"
+                        "             on, a node that ends optimal shrinks the range of every nonbasic integer column whose reduced cost leaves it\n"
+                        "             less room than its range, for the node's subtree; not with --node-form launches, --plunge or --branching\n"
                         "  --set-rhs I=V, --set-cost J=V: after the solve, b_I = V / c_J = V (1-based, repeatable), applied in order,\n"
                         "             each re-optimised warm on the device from the previous basis; each re-solve's summary is printed\n");
             return 0;
@@ -255,7 +260,10 @@ int main(int argc, char** argv)
     if (root_form >= 0 && (plunge || branching >= 0)) { std::fprintf(stderr, "lpx_cli: --root-form: the plunge and the strong-branching drivers have no root form\n"); return 64; }
     if (root_cuts >= 0 && !(bnb_bounded && divers)) { std::fprintf(stderr, "lpx_cli: --root-cuts needs --bnb-bounded --divers\n"); return 64; }
     if (root_cuts >= 0 && (plunge || branching >= 0)) { std::fprintf(stderr, "lpx_cli: --root-cuts: the plunge and the strong-branching drivers have no root cuts\n"); return 64; }
-    if (root_cuts >= 0 && root_form < 0) root_form = LPX_NODE_LAUNCHES;
+    if (tighten && !(bnb_bounded && divers)) { std::fprintf(stderr, "lpx_cli: --tighten needs --bnb-bounded --divers\n"); return 64; }
+    if (tighten && node_form == LPX_NODE_LAUNCHES) { std::fprintf(stderr, "lpx_cli: --tighten: reduced-cost tightening has no launches form: not with --node-form launches\n"); return 64; }
+    if (tighten && (plunge || branching >= 0)) { std::fprintf(stderr, "lpx_cli: --tighten: the plunge and the strong-branching drivers have no tightening\n"); return 64; }
+    if ((root_cuts >= 0 || tighten) && root_form < 0) root_form = LPX_NODE_LAUNCHES;
     if (root_form >= 0 && stall_events < 0) stall_events = 0;
     if (stall_events >= 0) { plunge = 0; if (!divers) divers = 1; }
     if (branching >= 0) { plunge = 0; if (!divers) divers = 1; }
@@ -293,7 +301,10 @@ int main(int argc, char** argv)
         (bd.upper ? up : lo)[bd.index] = bd.value;
     }
     lpx_bnb_cut_info cinfo; std::memset(&cinfo, 0, sizeof cinfo);
-    const int rc = bnb_bounded && root_cuts >= 0 ? lpx_solve_bnb_bounded9(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, stall_events, root_form, &co, &r, nullptr, nullptr, nullptr, &cinfo)
+    lpx_bnb_fix_info finfo; std::memset(&finfo, 0, sizeof finfo);
+    const int rc = bnb_bounded && tighten ? lpx_solve_bnb_bounded10(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, stall_events, root_form,
+                                                                    root_cuts >= 0 ? &co : nullptr, 1, &r, nullptr, nullptr, nullptr, &cinfo, &finfo)
+                 : bnb_bounded && root_cuts >= 0 ? lpx_solve_bnb_bounded9(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, stall_events, root_form, &co, &r, nullptr, nullptr, nullptr, &cinfo)
                  : bnb_bounded && root_form >= 0 ? lpx_solve_bnb_bounded8(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, stall_events, root_form, &r, nullptr, nullptr, nullptr)
                  : bnb_bounded && stall_events >= 0 ? lpx_solve_bnb_bounded7(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, stall_events, &r, nullptr, nullptr, nullptr)
                  : bnb_bounded && branching >= 0 ? lpx_solve_bnb_bounded6(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, branching, candidates,
@@ -315,6 +326,9 @@ int main(int argc, char** argv)
                  " purged, search on " + std::to_string(cinfo.R) + " x " + std::to_string(cinfo.C) + (cinfo.ran ? "\n" : " (no spare capacity on chip: no round)\n");
         lpx_bnb_cut_info_free(&cinfo);
     }
+    if (tighten)
+        shown += "tightening: " + std::to_string(finfo.tightened_cols) + " columns on " + std::to_string(finfo.tightened_nodes) + " nodes, at most " +
+                 std::to_string(finfo.max_per_node) + " on one\n";
     if (ranging) shown += ranging_table(rg);
     if (!edits.empty()) {
         lpx_session* ses = nullptr;
