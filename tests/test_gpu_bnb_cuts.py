@@ -32,11 +32,23 @@ def _model(name):
     return c, A, np.zeros(m, dtype=np.int32), b, np.ones(n), None, None, 0
 
 
+def sentinel_handle(gpu, T, basis, Rcap, Ccap, seed):
+    """A handle of capacity (Rcap, Ccap) whose whole capacity held random finite values before T went into its live window, so that
+    a test can tell a write outside that window.  Returns (handle, what the capacity held)."""
+    dead = np.random.default_rng(seed).uniform(-9.0, 9.0, size=(Rcap, Ccap))
+    dt = gpu.DeviceTableau(Rcap, Ccap)
+    dt.upload(dead)
+    dt.set_shape(*T.shape)
+    dt.upload(T, basis)
+    return dt, dead
+
+
 class Pair:
     """A device handle and the restatement's Handle in the same state: the solved root of a model, then one node whose edit
-    raises a lower bound (so the handle carries flips and a non-zero lo), with `extra` spare rows and columns."""
+    raises a lower bound (so the handle carries flips and a non-zero lo), with `extra` spare rows and columns.  root_form: the form
+    of the root solve.  sentinel (a seed): the handle is a sentinel_handle."""
 
-    def __init__(self, gpu, name, extra, edit=True, ub_override=None):
+    def __init__(self, gpu, name, extra, edit=True, ub_override=None, root_form="launches", sentinel=None):
         c, A, rel, b, upper, lower, mask, sense = _model(name)
         T0, basis0, ub0, _, _, _, _ = N.prepare(c, A, b, lower, upper, sense, rel)
         if ub_override:
@@ -49,9 +61,12 @@ class Pair:
         st, Ts, bs, flip, _, _ = B.run(T0, basis0, ub0)
         assert st == L.OPTIMAL
         self.h = L.Handle(Ts, bs, ub0, flip)
-        self.dt = gpu.DeviceTableau.with_capacity(T0, basis0, self.Rcap, self.Ccap)
+        if sentinel is None:
+            self.dt = gpu.DeviceTableau.with_capacity(T0, basis0, self.Rcap, self.Ccap)
+        else:
+            self.dt, _ = sentinel_handle(gpu, T0, basis0, self.Rcap, self.Ccap, sentinel)
         self.dt.set_bounds(ub0)
-        assert self.dt.bounded_run()[0] == L.OPTIMAL
+        assert self.dt.bounded_run(form=root_form)[0] == L.OPTIMAL
         self.flags = X.slack_mask(T0, self.n, mask)
         if edit:
             pk = N.pick(self.h.T, self.h.basis, self.h.flip, self.h.ub, self.h.lo, self.n, mask)
@@ -168,9 +183,9 @@ def test_flagged_column_with_a_fractional_upper_bound_is_continuous(gpu):
         p.close()
 
 
-def _after_rounds(gpu, name):
-    """A pair two rounds and one re-optimisation in: cut rows on the handle, bounds carried."""
-    p = Pair(gpu, name, 24)
+def _after_rounds(gpu, name, **kw):
+    """A pair two rounds and one re-optimisation in: cut rows on the handle, bounds carried.  kw: Pair's."""
+    p = Pair(gpu, name, 24, **kw)
     p.round(G.CutOpts(cuts_per_round=4))
     assert p.node([], [], [], LONG)["status"] == L.OPTIMAL
     src, _ = p.round(G.CutOpts(cuts_per_round=4))
