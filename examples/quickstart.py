@@ -25,6 +25,10 @@ res = solver.SolveBounded(problem, upper=2.0)
 print(f"Bounded Primal Simplex (x <= 2): status {res.Status}, z = {res.OptimalValue}, x = {[float(v) for v in res.Solution]}, "
       f"at upper bound {[int(v) for v in res.AtUpper]}, events (to zero, to upper, flips) {res.BoundCounts}")
 
+# Many small LPs in ONE launch (not in the reference): one model under three right-hand sides, c, A and the bounds shared.
+packed = solver.SolvePacked([3, 5, 2], [[1, 2, 2], [2, 4, 3]], [[10, 15], [11, 15], [9, 14]], upper=[4, 3, 3])
+print(f"Packed batch (3 right-hand sides, one launch): status {packed.Status.tolist()}, z = {packed.OptimalValue.tolist()}")
+
 # Branch and bound by bound changes (not in the reference): the integer program 0 <= x_j <= 2 on that one tableau.
 res = solver.SolveBnbBounded(problem, upper=2.0)
 print(f"Bounded Branch and Bound (x <= 2, integer): status {res.Status}, z = {res.OptimalValue}, x = {[float(v) for v in res.Solution]}, counters {res.BnbInfo}")

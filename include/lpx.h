@@ -1321,6 +1321,52 @@ int  lpx_solve_bnb_bounded8(const lpx_problem* p, const double* lower /* [n] or 
                             lpx_bnb_bounded_info* info /* or NULL */, lpx_bnb_divers_info* dinfo /* or NULL */,
                             lpx_bnb_guard_info* ginfo /* or NULL */);
 
+/* ---- packed batches of small bounded LPs: arrays in, ONE launch, arrays out (csrc/lpx_packed.hip) --------
+ *
+ * count models of ONE shape (m rows, every row <=; n variables) as contiguous arrays.  A call makes at most one host-to-device
+ * copy per input array, ONE kernel launch of count workgroups, one device-to-host copy and one wait, each independent of count;
+ * there is no handle, no tableau in device memory and no host work per model.  Workgroup i builds the tableau of model i in the
+ * LDS of its compute unit (the preparation of lpx_solve_bounded, bit for bit: Min negates c, b' = b - A l with j ascending and one
+ * multiply and one subtract per non-zero l_j, u' = u - l, slack basis), validates it, runs the event loop of the on-chip bounded
+ * primal form unchanged and extracts x, the optimum, the record, the basis and the at-upper flags from LDS.
+ *
+ * A stride is the number of doubles between two models of an array: the packed size (n for c, lower and upper; m*n for A; m for b)
+ * or 0, which means ONE copy that every model shares (only that copy is uploaded).  lower / upper may be NULL (0 / +inf).
+ *
+ * lpx_packed_fits(m, n) == lpx_bounded_node_fits(m + 1, n + m + 1) for m, n >= 1, else 0: pure host arithmetic.
+ *
+ * lpx_solve_packed(in, o, out, st) returns 0 once the launch ran; the outcome of model i is status[i]: LPX_OPTIMAL, LPX_UNBOUNDED,
+ * LPX_ITER_LIMIT (x, value, basis and at_upper are then the point at which the loop stopped), LPX_EINVAL (a lower bound that is
+ * not finite, or an upper bound below its lower bound or NaN) or, behind that check, LPX_E_NEG_RHS (a b'_i < -1e-9).  A model with a
+ * negative status has x, value, basis and at_upper zeroed and a record of zeros around that status; the other models are unaffected.
+ * Of o the fields eps, ratio_tol and max_iter are read; NULL is lpx_default_opts(o, 0).  st (or NULL): pivots = the kind-0 and kind-1
+ * pivots of all models, launches = 1, loop_ms the host wall of the copies, the launch and the wait.
+ *
+ * For every i, status[i], x, value, rec, basis and at_upper are bit-equal to what lpx_solve_bounded2(model i, lower_i, upper_i, o,
+ * LPX_NODE_ONCHIP, ...) returns (a negative status[i] is that call's return code), and do not depend on count, on i, on the other
+ * models or on whether an array is shared.
+ *
+ * LPX_EINVAL before any device check, the outputs untouched, every message starting "lpx_solve_packed: ": a NULL in, out, c, A, b,
+ * status, x or value; count outside [1, 65536]; m or n below 1; a sense other than LPX_MAX / LPX_MIN; a stride that is neither 0
+ * nor the packed size; a shape with lpx_packed_fits(m, n) == 0 ("R x C ... does not fit"); resident = 1; more than 1 GiB of input
+ * plus output bytes ("too large": chunking is the caller's business).  No device: LPX_EDEVICE.  The device buffers of a call are
+ * one arena that is kept for the next call and grows when needed; like the handle cache it lives as long as the process. */
+typedef struct lpx_packed_models {
+    int32_t count, m, n, sense;        /* one shape for all; every row is <= */
+    const double *c, *A, *b;           /* [count][n], [count][m][n] row-major, [count][m] */
+    const double *lower, *upper;       /* [count][n] or NULL (0 / +inf) */
+    int64_t c_stride, A_stride, b_stride, lower_stride, upper_stride;
+                                       /* doubles between models: the packed size (n, m*n, m, n, n),
+                                          or 0 = ONE copy shared by every model */
+} lpx_packed_models;
+typedef struct lpx_packed_results {    /* caller-allocated; each of the last three may be NULL */
+    int32_t* status;  double* x;  double* value;           /* [count], [count][n], [count] */
+    lpx_primal_record* rec;  int32_t* basis;  uint8_t* at_upper;   /* [count], [count][m], [count][n] */
+} lpx_packed_results;
+int lpx_packed_fits(int m, int n);
+int lpx_solve_packed(const lpx_packed_models* in, const lpx_run_opts* o /* or NULL */, const lpx_packed_results* out,
+                     lpx_stats* st /* or NULL */);
+
 /* ---- GMI cuts on a handle with bounds, and the cut loop at a bounded root (csrc/lpx_cuts.hip, csrc/lpx_tableau_bounded.cpp,
  * DESIGN.md section 4.23) --------------------------------------------------------------------------------------------------
  * An internal column of a bounded handle stands for x'_j = x_j - lo_j, or for ub_j - (x_j - lo_j) when it is flipped; x'_j >= 0

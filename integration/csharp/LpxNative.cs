@@ -158,6 +158,22 @@ namespace Linear_Programming_Solver.Native
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct LpxPackedModels         // lpx_packed_models: count models of one shape as contiguous arrays
+    {
+        public int count, m, n, sense;           // every row is <=
+        public double* c, A, b;                  // [count][n], [count][m][n] row-major, [count][m]
+        public double* lower, upper;             // [count][n] or null (0 / +inf)
+        public long c_stride, A_stride, b_stride, lower_stride, upper_stride;   // doubles between models; 0 = one shared copy
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct LpxPackedResults        // lpx_packed_results: caller-allocated; rec, basis, at_upper may be null
+    {
+        public int* status; public double* x; public double* value;
+        public LpxPrimalRecord* rec; public int* basis; public byte* at_upper;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public struct LpxGuardRecord                 // lpx_guard_record: 8 bytes
     {
         public int bland_events, first_bland;    // pivots made in Bland mode; event index of the first, -1 = none
@@ -454,6 +470,10 @@ namespace Linear_Programming_Solver.Native
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_solve_bounded_batch(int count, LpxProblem** problems, double** lowers, double** uppers, ref LpxSolveOpts o,
                                                          LpxResult* results, LpxBoundedInfo* infos);
+        // packed batches: arrays in, ONE launch, arrays out; opts: lpx_run_opts or IntPtr.Zero, st may be null
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int lpx_packed_fits(int m, int n);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_packed(ref LpxPackedModels models, IntPtr opts, ref LpxPackedResults results, LpxStats* st);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_solve_bnb_bounded8(ref LpxProblem p, double* lower, double* upper, byte* is_int, ref LpxSolveOpts o,
                                                         long max_nodes, int search_flags, int divers, int stall_events, int root_form,

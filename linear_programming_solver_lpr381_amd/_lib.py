@@ -200,6 +200,20 @@ class PrimalRecord(C.Structure):
                 ("z", C.c_double)]
 
 
+class PackedModels(C.Structure):
+    """lpx_packed_models (include/lpx.h): count models of one shape as contiguous arrays; a stride of 0 shares one copy."""
+    _fields_ = [("count", C.c_int32), ("m", C.c_int32), ("n", C.c_int32), ("sense", C.c_int32),
+                ("c", dp), ("A", dp), ("b", dp), ("lower", dp), ("upper", dp),
+                ("c_stride", C.c_int64), ("A_stride", C.c_int64), ("b_stride", C.c_int64), ("lower_stride", C.c_int64),
+                ("upper_stride", C.c_int64)]
+
+
+class PackedResults(C.Structure):
+    """lpx_packed_results (include/lpx.h): caller-allocated output arrays of lpx_solve_packed; rec, basis, at_upper may be NULL."""
+    _fields_ = [("status", ip), ("x", dp), ("value", dp), ("rec", C.POINTER(PrimalRecord)), ("basis", ip),
+                ("at_upper", C.POINTER(C.c_uint8))]
+
+
 class FixList(C.Structure):
     """lpx_fix_list (include/lpx.h): the caller-owned list of the columns a node tightened, as the triples of a bound edit."""
     _fields_ = [("cap", C.c_int32), ("n", C.c_int32), ("cols", ip), ("lower", dp), ("upper", dp)]
@@ -434,6 +448,8 @@ def lib() -> C.CDLL:
     L.lpx_solve_bounded2.argtypes = [C.POINTER(Problem), dp, dp, C.POINTER(SolveOpts), C.c_int, C.POINTER(Result), C.POINTER(BoundedInfo)]
     L.lpx_solve_bounded_batch.argtypes = [C.c_int, C.POINTER(C.POINTER(Problem)), C.POINTER(dp), C.POINTER(dp), C.POINTER(SolveOpts),
                                           C.POINTER(Result), C.POINTER(BoundedInfo)]
+    L.lpx_packed_fits.argtypes = [C.c_int, C.c_int]
+    L.lpx_solve_packed.argtypes = [C.POINTER(PackedModels), C.POINTER(RunOpts), C.POINTER(PackedResults), C.POINTER(Stats)]
     L.lpx_solve_bnb_bounded8.argtypes = [C.POINTER(Problem), dp, dp, u8p, C.POINTER(SolveOpts), C.c_int64, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.POINTER(Result), C.POINTER(BnbBoundedInfo), C.POINTER(BnbDiversInfo),
                                          C.POINTER(BnbGuardInfo)]

@@ -238,6 +238,8 @@ SimplexResult SolveBounded(const LPProblem& original, const std::vector<double>&
 void SolveBoundedBatch(const std::vector<const LPProblem*>& problems, const std::vector<std::vector<double>>& lowers,
                        const std::vector<std::vector<double>>& uppers, const EngineOptions& opt, std::vector<SimplexResult>& results,
                        std::vector<BoundedInfo>& infos);
+// the argument checks of lpx_solve_packed (LPX_EINVAL, no device, no look at any model); the call itself is lpx::packed_solve
+void CheckPacked(const lpx_packed_models* in, const lpx_run_opts* o, const lpx_packed_results* out);
 // The dual start (lpx_solve_bounded_dual): >= rows and negative right-hand sides accepted, slack basis, dualize, lpx_bounded_dual_run3(flags)
 SimplexResult SolveBoundedDual(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper, int flags,
                                const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info);

@@ -171,6 +171,18 @@ hipError_t bounded_primal_init();                   // one-time function attribu
 hipError_t launch_bounded_primal_onchip(const PrimalParams& n, hipStream_t s);
 // the batch: workgroup b solves P[b] (an array the device can read); lds = the largest entry's bounded_node_lds_bytes
 hipError_t launch_bounded_primals_onchip(const PrimalParams* P, int B, size_t lds, hipStream_t s);
+// the packed batch (lpx_packed.hip): workgroup i builds model i's tableau in LDS from the packed arrays, runs the same loop and
+// extracts its results from LDS.  Every pointer is device memory; a stride is in doubles, 0 = one copy shared by every model.
+struct PackedParams {
+    const double *c, *A, *b, *lower, *upper;            // lower / upper: or null (0 / +inf)
+    int64_t c_stride, A_stride, b_stride, lower_stride, upper_stride;
+    int32_t m, n, min, max_iter;
+    double eps, ratio_tol;
+    int32_t* status; double* x; double* value; lpx_primal_record* rec; int32_t* basis; uint8_t* at_upper;     // [count] ... as lpx_packed_results
+    uint8_t* flip; int64_t flip_stride;                 // work bytes, [count][flip_stride], flip_stride >= n + m
+};
+// lpx_solve_packed behind its argument checks: the arena, the copies, the one launch, the one wait
+int packed_solve(const lpx_packed_models* in, const lpx_run_opts* o, const lpx_packed_results* out, lpx_stats* st);
 
 // ---- lpx_kernels.hip: the two-launch select and update paths
 hipError_t launch_select(const SelParams& p, hipStream_t s);       // gather-based (dual path)

@@ -365,6 +365,21 @@ int lpx_solve_bounded_batch(int count, const lpx_problem* const* problems, const
     });
 }
 
+// ---- packed batches: arrays in, one launch, arrays out (host/bounded.cpp CheckPacked, lpx_packed.hip) -------------------------
+int lpx_packed_fits(int m, int n)
+{
+    if (m < 1 || n < 1 || m > (1 << 20) || n > (1 << 20)) return 0;
+    return lpx_bounded_node_fits(m + 1, n + m + 1);
+}
+
+int lpx_solve_packed(const lpx_packed_models* in, const lpx_run_opts* o, const lpx_packed_results* out, lpx_stats* st)
+{
+    try { CheckPacked(in, o, out); }
+    catch (const LpxException& ex) { set_error(ex.what()); return ex.code; }
+    lpx_run_opts d; if (!o) { lpx_default_opts(&d, 0); o = &d; }
+    return packed_solve(in, o, out, st);
+}
+
 void lpx_bounded_info_free(lpx_bounded_info* info)
 {
     if (!info) return;

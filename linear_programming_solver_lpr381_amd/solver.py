@@ -76,6 +76,19 @@ class SimplexResult:        # Models/PrimalSimplex.cs:38-49 (+ engine extras aft
 
 
 @dataclass
+class PackedResult:         # lpx_packed_results (include/lpx.h): LPSolver.SolvePacked, one entry per model along axis 0
+    Status: np.ndarray                      # (B,) int32: OPTIMAL, UNBOUNDED, ITER_LIMIT, or a negative LPX_E* of that model alone
+    Solution: np.ndarray                    # (B, n)
+    OptimalValue: np.ndarray                # (B,) in the user's sense
+    Events: Optional[np.ndarray] = None     # (B,) pivots and flips                                         (want "rec")
+    BoundCounts: Optional[np.ndarray] = None    # (B, 3): pivots to zero, pivots to the upper bound, flips  (want "rec")
+    Z: Optional[np.ndarray] = None          # (B,) T[m, C-1] as the loop left it                            (want "rec")
+    Basis: Optional[np.ndarray] = None      # (B, m) int32                                                  (want "basis")
+    AtUpper: Optional[np.ndarray] = None    # (B, n) uint8: 1 = x_j is nonbasic at its upper bound          (want "at_upper")
+    Stats: Optional[dict] = None
+
+
+@dataclass
 class RangingReport:        # lpx_ranging (include/lpx.h): ranges of the solved model in user terms
     valid: bool
     cost_lo: np.ndarray
@@ -339,6 +352,91 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         if rc != 0:
             raise SolverException(rc, _lib.last_error())
         return [self._bounded_result(rs[i], infos[i], problems[i].NumVars) for i in range(count)]
+
+    def SolvePacked(self, c, A, b, upper=None, lower=None, sense="max", max_iter=None,
+                    want=("rec", "basis", "at_upper")) -> PackedResult:
+        """B bounded models of ONE shape (m rows, all <=; n variables) as arrays, solved in ONE kernel launch with one upload
+        per array and one read-back (lpx_solve_packed).  c: (B, n) or (n,); A: (B, m, n) or (m, n); b: (B, m) or (m,); upper /
+        lower: the shapes of c, a scalar, or None (+inf / 0).  An array without the batch axis is shared by every model (stride
+        0) and is never tiled on the host.  B comes from whichever argument has the batch axis (none: B = 1); disagreeing axes
+        are a ValueError.  sense: "max" | "min".  Every model gets its own Status: one that is refused (LPX_EINVAL for its bounds,
+        LPX_E_NEG_RHS) or reaches the iteration limit does not fail the call.  Each entry is bit-equal to
+        SolveBounded(model, upper, lower, form="onchip").  want: which of the optional outputs to fetch."""
+        if isinstance(sense, str):
+            if sense.lower() not in ("max", "min"):
+                raise ValueError(f"unknown sense {sense!r}")
+            sense = 1 if sense.lower() == "min" else 0
+        want = tuple(want)
+        for w in want:
+            if w not in ("rec", "basis", "at_upper"):
+                raise ValueError(f"unknown output {w!r}")
+
+        def _f64(v):
+            return np.ascontiguousarray(np.asarray(v, dtype=np.float64))
+        c, A, b = _f64(c), _f64(A), _f64(b)
+        if c.ndim not in (1, 2) or A.ndim not in (2, 3) or b.ndim not in (1, 2):
+            raise ValueError("c is (B, n) or (n,), A is (B, m, n) or (m, n), b is (B, m) or (m,)")
+        m, n = A.shape[-2], A.shape[-1]
+        if c.shape[-1] != n or b.shape[-1] != m:
+            raise ValueError(f"A is {m} x {n}, but c has {c.shape[-1]} entries and b has {b.shape[-1]}")
+        batched = [("c", c, 2), ("A", A, 3), ("b", b, 2)]
+        bounds = {}
+        for name, v in (("upper", upper), ("lower", lower)):
+            if v is None:
+                bounds[name] = None
+                continue
+            if np.ndim(v) == 0:
+                v = np.full(n, float(v))                # one shared row, not one per model
+            v = _f64(v)
+            if v.ndim not in (1, 2) or v.shape[-1] != n:
+                raise ValueError(f"{name} is (B, n), (n,) or a scalar with n = {n}")
+            bounds[name] = v
+            batched.append((name, v, 2))
+        sizes = {name: v.shape[0] for name, v, nd in batched if v.ndim == nd}
+        if len(set(sizes.values())) > 1:
+            raise ValueError(f"the batch axes disagree: {sizes}")
+        B = next(iter(sizes.values())) if sizes else 1
+        if B < 1:
+            raise ValueError("an empty batch")
+
+        def _stride(v, nd, packed):
+            return packed if v.ndim == nd else 0
+        pm = _lib.PackedModels()
+        pm.count, pm.m, pm.n, pm.sense = B, m, n, int(sense)
+        pm.c, pm.A, pm.b = (v.ctypes.data_as(_lib.dp) for v in (c, A, b))
+        pm.c_stride, pm.A_stride, pm.b_stride = _stride(c, 2, n), _stride(A, 3, m * n), _stride(b, 2, m)
+        for name in ("upper", "lower"):
+            v = bounds[name]
+            if v is not None:
+                setattr(pm, name, v.ctypes.data_as(_lib.dp))
+                setattr(pm, name + "_stride", _stride(v, 2, n))
+        status = np.zeros(B, dtype=np.int32); x = np.zeros((B, n)); value = np.zeros(B)
+        pr = _lib.PackedResults()
+        pr.status, pr.x, pr.value = status.ctypes.data_as(_lib.ip), x.ctypes.data_as(_lib.dp), value.ctypes.data_as(_lib.dp)
+        recs = basis = at = None
+        if "rec" in want:
+            recs = (_lib.PrimalRecord * B)()
+            pr.rec = recs
+        if "basis" in want:
+            basis = np.zeros((B, m), dtype=np.int32)
+            pr.basis = basis.ctypes.data_as(_lib.ip)
+        if "at_upper" in want:
+            at = np.zeros((B, n), dtype=np.uint8)
+            pr.at_upper = at.ctypes.data_as(C.POINTER(C.c_uint8))
+        limit = max_iter if max_iter is not None else self.engine.get("max_iter")
+        o = _lib.default_opts(False) if limit is None else _lib.default_opts(False, max_iter=int(limit))
+        st = _lib.Stats()
+        rc = lib().lpx_solve_packed(C.byref(pm), C.byref(o), C.byref(pr), C.byref(st))
+        if rc != 0:
+            raise SolverException(rc, _lib.last_error())
+        res = PackedResult(Status=status, Solution=x, OptimalValue=value, Basis=basis, AtUpper=at, Stats=st.as_dict())
+        if recs is not None:
+            r = np.frombuffer(recs, dtype=np.dtype([("status", "<i4"), ("events", "<i4"), ("kind0", "<i8"), ("kind1", "<i8"),
+                                                    ("flips", "<i8"), ("z", "<f8")]))
+            res.Events = r["events"].copy()
+            res.BoundCounts = np.stack([r["kind0"], r["kind1"], r["flips"]], axis=1)
+            res.Z = r["z"].copy()
+        return res
 
     def _solve_bounded(self, problem: LPProblem, upper, lower, dual_flags, form: str = "launches") -> SimplexResult:
         """lpx_solve_bounded (dual_flags None; with a form, lpx_solve_bounded2) or lpx_solve_bounded_dual: the same call shape

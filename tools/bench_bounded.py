@@ -22,7 +22,13 @@ restored snapshot.  The batch, three ways: 256 models of 13 x 73 through lpx_sol
 as 256 launches-form solves (lpx_solve_bounded), whole calls timed.  `--forms-trace` runs one warm on-chip solve per root model and
 one batch, for a run of its own under `rocprofv3 --kernel-trace --stats`: one kernel per solve and one per batch.
 
-usage: bench_bounded.py [--trace-only] [--model NAME] [--compare-forms | --forms-trace] [REPS]"""
+`--compare-packed` measures the packed batch call (lpx_solve_packed) by the same rule: the 256 models of the
+batch above with u = 1 four ways, alternating in one process, whole calls timed (SolvePacked, SolveBoundedBatch, 256 single on-chip
+solves, 256 launches-form solves; equal optima and counts asserted); then SolvePacked alone on 4096 and 65536 models of that shape;
+then 4096 right-hand sides of one shared model (stride 0) against the same 4096 fully packed.  `--packed-trace` makes four packed
+calls of 256 models, for a run of its own under `rocprofv3 --kernel-trace --stats`: one kernel per call.
+
+usage: bench_bounded.py [--trace-only] [--model NAME] [--compare-forms | --forms-trace | --compare-packed | --packed-trace] [REPS]"""
 import json
 import os
 import statistics
@@ -169,7 +175,95 @@ def compare_forms(reps, trace):
     print(json.dumps(out))
 
 
+def packed_arrays(count):
+    """The models of batch_models(256) as packed arrays, repeated up to count models."""
+    cs, As, bs = [], [], []
+    for s in range(1, min(count, 256) + 1):
+        c, A, rel, b = synth.binary_ip(60, 12, s)
+        cs.append(c); As.append(A[:12]); bs.append(b[:12])
+    c, A, b = np.stack(cs), np.stack(As), np.stack(bs)
+    reps = -(-count // len(cs))
+    return tuple(np.ascontiguousarray(np.tile(v, (reps,) + (1,) * (v.ndim - 1))[:count]) for v in (c, A, b))
+
+
+def compare_packed(reps, trace):
+    """The packed call (lpx_solve_packed) against the three ways of --compare-forms on the same 256 models,
+    whole calls timed and the four alternating in one process; then the packed call alone on 4096 and 65536 models of that shape;
+    then 4096 right-hand sides of ONE shared model (stride 0) against the same 4096 fully packed."""
+    S = L.LPSolver()
+    count = 256
+    c, A, b = packed_arrays(count)
+    if trace:                                           # one warm-up call and three calls: one kernel each in the trace
+        for i in range(4):
+            r = S.SolvePacked(c, A, b, 1.0)
+        print(json.dumps({"packed_trace": {"count": count, "calls": 4, "events": int(r.Events.sum()), "launches_per_call": r.Stats["launches"]}}))
+        return
+    out = {}
+    ps = batch_models(count)
+    sides = {"packed": [], "batch": [], "single_onchip": [], "single_launches": []}
+    for i in range(reps + 1):
+        t0 = time.perf_counter()
+        rp = S.SolvePacked(c, A, b, 1.0)
+        sides["packed"].append(1e3 * (time.perf_counter() - t0))
+        t0 = time.perf_counter()
+        rb = S.SolveBoundedBatch(ps, [1.0] * count)
+        sides["batch"].append(1e3 * (time.perf_counter() - t0))
+        t0 = time.perf_counter()
+        rs = [S.SolveBounded(p, 1.0, form="onchip") for p in ps]
+        sides["single_onchip"].append(1e3 * (time.perf_counter() - t0))
+        t0 = time.perf_counter()
+        rl = [S.SolveBounded(p, 1.0) for p in ps]
+        sides["single_launches"].append(1e3 * (time.perf_counter() - t0))
+        assert all(rp.OptimalValue[k] == x.OptimalValue == y.OptimalValue == z.OptimalValue and
+                   tuple(rp.BoundCounts[k].tolist()) == x.BoundCounts == y.BoundCounts == z.BoundCounts and rp.Status[k] == x.Status
+                   for k, (x, y, z) in enumerate(zip(rb, rs, rl))), "the four ways differ"
+    rec = {"count": count, "shape": [13, 73], "events": int(rp.Events.sum()), "loop_ms_last": rp.Stats["loop_ms"],
+           "bytes_in": int(c.nbytes + A.nbytes + b.nbytes + 8 * 60), "bytes_out": int(count * (4 + 8 * 60 + 8 + 40 + 4 * 12 + 60))}
+    rec.update({k: stats(v[1:]) for k, v in sides.items()})                     # the first round is the warm-up
+    for other in ("batch", "single_onchip", "single_launches"):
+        rec["winner_packed_vs_" + other] = verdict(rec["packed"], rec[other], "packed", other)
+        rec[other + "_over_packed"] = rec[other]["median_ms"] / rec["packed"]["median_ms"]
+    out["four_ways_256_of_13x73"] = rec
+    for count in (4096, 65536):
+        c, A, b = packed_arrays(count)
+        ts, loop = [], []
+        for i in range(min(reps, 7) + 1):
+            t0 = time.perf_counter()
+            r = S.SolvePacked(c, A, b, 1.0)
+            ts.append(1e3 * (time.perf_counter() - t0)); loop.append(r.Stats["loop_ms"])
+        assert (r.Status == 0).all() and np.array_equal(r.OptimalValue[:256], rp.OptimalValue) and np.array_equal(r.OptimalValue[-256:], rp.OptimalValue)
+        out["packed_%d_of_13x73" % count] = dict(stats(ts[1:]), count=count, bytes_in=int(c.nbytes + A.nbytes + b.nbytes + 8 * 60),
+                                                 loop_ms_median=statistics.median(loop[1:]),
+                                                 us_per_model=1e3 * statistics.median(ts[1:]) / count)
+    # one shared model, 4096 right-hand sides: stride 0 for c and A against the same data tiled
+    count = 4096
+    c1, A1, b1 = packed_arrays(1)
+    g = np.random.default_rng(5)
+    bs = np.floor(b1[0] * g.uniform(0.8, 1.2, size=(count, 12)))
+    ct, At = np.ascontiguousarray(np.tile(c1, (count, 1))), np.ascontiguousarray(np.tile(A1, (count, 1, 1)))
+    sides = {"shared": [], "tiled": []}
+    for i in range(reps + 1):
+        t0 = time.perf_counter()
+        rsh = S.SolvePacked(c1[0], A1[0], bs, 1.0)
+        sides["shared"].append(1e3 * (time.perf_counter() - t0))
+        t0 = time.perf_counter()
+        rti = S.SolvePacked(ct, At, bs, 1.0)
+        sides["tiled"].append(1e3 * (time.perf_counter() - t0))
+        assert rsh.Solution.tobytes() == rti.Solution.tobytes() and rsh.OptimalValue.tobytes() == rti.OptimalValue.tobytes() and \
+            np.array_equal(rsh.BoundCounts, rti.BoundCounts) and np.array_equal(rsh.Status, rti.Status), "shared and tiled differ"
+    rec = {"count": count, "shape": [13, 73], "events": int(rsh.Events.sum()), "bytes_in_shared": int(c1[0].nbytes + A1[0].nbytes + bs.nbytes + 8 * 60),
+           "bytes_in_tiled": int(ct.nbytes + At.nbytes + bs.nbytes + 8 * 60)}
+    rec.update({k: stats(v[1:]) for k, v in sides.items()})
+    rec["winner"] = verdict(rec["shared"], rec["tiled"], "shared", "tiled")
+    out["rhs_4096_shared_vs_tiled"] = rec
+    print(json.dumps(out))
+
+
 def main():
+    if "--compare-packed" in sys.argv[1:] or "--packed-trace" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a not in ("--compare-packed", "--packed-trace")]
+        L._lib.check(L._lib.lib().lpx_init(0))
+        return compare_packed(int(rest[0]) if rest else 15, "--packed-trace" in sys.argv[1:])
     if "--compare-forms" in sys.argv[1:] or "--forms-trace" in sys.argv[1:]:
         rest = [a for a in sys.argv[1:] if a not in ("--compare-forms", "--forms-trace")]
         L._lib.check(L._lib.lib().lpx_init(0))

@@ -1,7 +1,7 @@
 // lpx_cli -- Linux stand-in for the reference's WinForms host (Form1.cs), over the C ABI of liblpx.so only.
 //
 //   lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]
-//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S] [--root-form F] [--root-cuts N [--cuts-per-round K]] [--tighten]] [--bounded-form F] [--export FILE] INPUT.txt
+//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S] [--root-form F] [--root-cuts N [--cuts-per-round K]] [--tighten]] [--bounded-form F] [--bounded [--rhs-file F]] [--export FILE] INPUT.txt
 //
 // Does what Form1 does around the solvers: reads the model text (Import, Form1.cs:284-296), parses it with the LPParser
 // grammar (lpx_parse_text, Models/LPParser.cs:9-79), runs the algorithm chosen by its dropdown name (btnSolve_Click,
@@ -12,7 +12,9 @@
 // lpx_solve_cuts with those options.  --set-rhs I=V (b_I = V) and --set-cost J=V (c_J = V), 1-based and repeatable, are
 // applied in the order given after the solve, each as a warm edit of one lpx_session (re-optimised on the device from the
 // previous basis), and each re-solve's summary is printed.  --upper J=V / --lower J=V (bounds of x_J, 1-based, repeatable) and
-// --binary (every u_j = 1) select the bounded-variable primal simplex (lpx_solve_bounded): the bounds cost no rows.  There is no CPU fallback: without a gfx950 device the solve fails with LPX_EDEVICE.
+// --binary (every u_j = 1) select the bounded-variable primal simplex (lpx_solve_bounded): the bounds cost no rows.  --bounded selects it without any bound.  --bounded --rhs-file F solves the model once per line of F (m numbers, the
+// right-hand sides of that run) as ONE packed call (lpx_solve_packed) with c, A and the bounds shared by every run, and prints one
+// line "status value x1 .. xn" per right-hand side.  There is no CPU fallback: without a gfx950 device the solve fails with LPX_EDEVICE.
 #include <cstdio>
 #include <cstdlib>
 #include <cctype>
@@ -76,6 +78,8 @@ int main(int argc, char** argv)
 {
     std::string algorithm = "Primal Simplex", input, exportPath;
     bool repaired = false, iterations = false, ranging = false, cut_set = false, algo_set = false, binary = false, bnb_bounded = false;
+    bool bounded_flag = false;  // --bounded: the bounded primal simplex even without a bound
+    std::string rhs_file;       // --rhs-file F beside --bounded: one packed call (lpx_solve_packed), a right-hand side per line of F
     int search_flags = 0;       // --long-step / --cutoff beside --bnb-bounded
     int node_form = -1;         // --node-form beside --bnb-bounded: LPX_NODE_*; -1 = not given
     int divers = 0;             // --divers W beside --bnb-bounded: the search by W divers (lpx_solve_bnb_bounded4); 0 = not given
@@ -98,6 +102,8 @@ int main(int argc, char** argv)
         if (a == "--algorithm" && i + 1 < argc) { algorithm = argv[++i]; algo_set = true; }
         else if (a == "--binary") binary = true;
         else if (a == "--bnb-bounded") bnb_bounded = true;
+        else if (a == "--bounded") bounded_flag = true;
+        else if (a == "--rhs-file" && i + 1 < argc) rhs_file = argv[++i];
         else if (a == "--long-step") search_flags |= LPX_BDUAL_LONG_STEP;
         else if (a == "--cutoff") search_flags |= LPX_BDUAL_CUTOFF;
         else if (a == "--node-form" && i + 1 < argc) {
@@ -194,7 +200,7 @@ int main(int argc, char** argv)
         else if (a == "--help" || a == "-h") {
             std::printf("usage: lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]\n"
                         "               [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S] [--root-form F] [--root-cuts N [--cuts-per-round K]] [--tighten]] [--bounded-form F]\n"
-                        "               [--export FILE] INPUT.txt\n"
+                        "               [--bounded [--rhs-file F]] [--export FILE] INPUT.txt\n"
                         "  NAME: Primal Simplex | Revised Primal Simplex | Dual Simplex | Branch and Bound |\n"
                         "        Revised Branch and Bound | Branch and Bound Knapsack | Cutting Plane | Revised Cutting Plane |\n"
                         "        GMI Cutting Plane (gmi) | Bounded Primal Simplex\n"
@@ -223,6 +229,9 @@ int main(int argc, char** argv)
                         "             --plunge above 1 or --branching\n"
                         "  --bounded-form launches|onchip|auto: the bounded primal solve (--binary / --upper / --lower without --bnb-bounded) as\n"
                         "             launches per pivot (the default) or in ONE kernel launch with the tableau on chip (lpx_solve_bounded2)\n"
+                        "  --bounded: the Bounded Primal Simplex even without a bound.  --bounded --rhs-file F: the model once per line of F (m\n"
+                        "             numbers: the right-hand sides of that run) as ONE packed call (lpx_solve_packed: one upload, one kernel\n"
+                        "             launch, one read-back; c, A and the bounds shared); prints a line \"status value x1 .. xn\" per run\n"
                         "  --root-cuts N: with --bnb-bounded --divers, cut-and-branch (lpx_solve_bnb_bounded9): up to N rounds of --cuts-per-round K\n"
                         "             (default 8) GMI cuts at the solved root, then the search from that tableau; not with --plunge or --branching\n"
                         "  --root-form launches|onchip|auto: with --bnb-bounded --divers, how the root LP is solved (lpx_solve_bnb_bounded8);\n"
@@ -241,7 +250,11 @@ int main(int argc, char** argv)
         if (key != "gmi cutting plane" && key != "gmi") { std::fprintf(stderr, "lpx_cli: --cuts-per-round / --cut-rounds need --algorithm \"GMI Cutting Plane\"\n"); return 64; }
         if (ranging) { std::fprintf(stderr, "lpx_cli: --ranging does not combine with --cuts-per-round / --cut-rounds\n"); return 64; }
     }
-    const bool bounded = binary || !bounds.empty();
+    const bool bounded = binary || !bounds.empty() || bounded_flag;
+    if (!rhs_file.empty() && (!bounded_flag || bnb_bounded || bounded_form >= 0 || iterations || !edits.empty() || !exportPath.empty())) {
+        std::fprintf(stderr, "lpx_cli: --rhs-file needs --bounded and combines only with --upper / --lower / --binary\n");
+        return 64;
+    }
     if (bnb_bounded && !bounded) { std::fprintf(stderr, "lpx_cli: --bnb-bounded needs --binary or --upper bounds\n"); return 64; }
     if (search_flags && !bnb_bounded) { std::fprintf(stderr, "lpx_cli: --long-step / --cutoff need --bnb-bounded\n"); return 64; }
     if (node_form >= 0 && !bnb_bounded) { std::fprintf(stderr, "lpx_cli: --node-form needs --bnb-bounded\n"); return 64; }
@@ -299,6 +312,45 @@ int main(int argc, char** argv)
     for (const Bound& bd : bounds) {
         if (bd.index >= p.n) { std::fprintf(stderr, "lpx_cli: %s: index out of range\n", bd.text.c_str()); lpx_parsed_free(&p); return 64; }
         (bd.upper ? up : lo)[bd.index] = bd.value;
+    }
+    if (!rhs_file.empty()) {
+        // one packed call: a right-hand side per line, everything else shared at stride 0
+        for (int i = 0; i < p.m; ++i)
+            if (p.rel[i] != LPX_LE) { std::fprintf(stderr, "lpx_cli: --rhs-file: every constraint must be <=\n"); lpx_parsed_free(&p); return 65; }
+        std::ifstream rf(rhs_file);
+        if (!rf) { std::fprintf(stderr, "Error reading file: %s\n", rhs_file.c_str()); lpx_parsed_free(&p); return 66; }
+        std::vector<double> rhs;
+        std::string line;
+        int count = 0;
+        while (std::getline(rf, line)) {
+            std::istringstream ls(line);
+            std::vector<double> row; double v;
+            while (ls >> v) row.push_back(v);
+            if (row.empty() && ls.eof()) continue;      // a blank line
+            if ((int)row.size() != p.m || !ls.eof()) {
+                std::fprintf(stderr, "lpx_cli: --rhs-file: line %d does not hold %d numbers\n", count + 1, p.m);
+                lpx_parsed_free(&p); return 65;
+            }
+            rhs.insert(rhs.end(), row.begin(), row.end()); ++count;
+        }
+        lpx_packed_models pm; std::memset(&pm, 0, sizeof pm);
+        pm.count = count; pm.m = p.m; pm.n = p.n; pm.sense = p.sense;
+        pm.c = p.c; pm.A = p.A; pm.b = rhs.data(); pm.lower = lo.data(); pm.upper = up.data();
+        pm.b_stride = p.m;                              // c, A and the bounds: stride 0, one copy for every run
+        std::vector<int32_t> status((size_t)(count > 0 ? count : 1));
+        std::vector<double> x((size_t)(count > 0 ? count : 1) * (size_t)(p.n > 0 ? p.n : 1)), value((size_t)(count > 0 ? count : 1));
+        lpx_packed_results pr; std::memset(&pr, 0, sizeof pr);
+        pr.status = status.data(); pr.x = x.data(); pr.value = value.data();
+        lpx_run_opts ro; lpx_default_opts(&ro, 0);
+        const int prc = lpx_solve_packed(&pm, &ro, &pr, nullptr);
+        if (prc != 0) { lpx_parsed_free(&p); lpx_last_error(err, sizeof err); std::fprintf(stderr, "%s\n", err); return prc == LPX_EDEVICE ? 69 : 70; }
+        for (int i = 0; i < count; ++i) {
+            std::printf("%d %.17g", status[i], value[i]);
+            for (int j = 0; j < p.n; ++j) std::printf(" %.17g", x[(size_t)i * p.n + j]);
+            std::printf("\n");
+        }
+        lpx_parsed_free(&p);
+        return 0;
     }
     lpx_bnb_cut_info cinfo; std::memset(&cinfo, 0, sizeof cinfo);
     lpx_bnb_fix_info finfo; std::memset(&finfo, 0, sizeof finfo);
