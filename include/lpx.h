@@ -129,6 +129,8 @@ int  lpx_tableau_shape(const lpx_tableau* t, int* R, int* C, int* ld);
 /* A handle created for (Rcap, Ccap) can hold any smaller tableau: the kernels read the live shape from a
  * device record, so one handle (and its captured hipGraph) serves every depth of a B&B tree. */
 int  lpx_tableau_set_shape(lpx_tableau* t, int R, int C);
+/* 1 if the last lpx_primal_run on this handle swept a compact tableau without the basic columns (streamed handles, long runs), else 0 */
+int  lpx_tableau_last_run_compact(const lpx_tableau* t);
 
 /* The hot loops.  Each iteration is two launches on one stream:
  *   select  -- ChooseEntering + ChooseLeaving (+ pivot-row normalisation and pivot-column snapshot)

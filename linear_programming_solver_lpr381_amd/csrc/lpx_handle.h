@@ -50,6 +50,8 @@ struct lpx_tableau {
     double* fprow = nullptr; double* frhs = nullptr; lpx::DevState* frec = nullptr;
     double* frat = nullptr;         // [Rcap + 1] ratios of the select-only pair's column launch, then T[m,q], then its scan records (lpx_pivot_ratio; pivot_ratio_bytes)
     char* dring = nullptr; int dring_slots = 0;   // deferred pivots of run_fused: ring of pivot rows, factor columns, row indices
+    char* cslab = nullptr;          // compact form of run_fused: its integer maps, on first use
+    bool last_compact = false;      // the last run_fused took the compact form (lpx_tableau_last_run_compact)
     bool fused_off = false;         // the second buffer did not fit: stay on the two-launch path
     bool suspended2 = false;        // ... by the two-launch group kernels (it must continue there: no pending pivot, state in *hst)
     bool fsuspended = false; int frec_cur = 0;   // fused group run left unfinished: its records (latest: index frec_cur) are in place

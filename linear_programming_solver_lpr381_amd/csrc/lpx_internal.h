@@ -241,7 +241,25 @@ struct FusedParams {
     double* pring; double* fring; int32_t* rring;
     int defer;           // pivots per sweep (LPX_PIVOT_DEFER)
     int lm;              // set per launch by launch_pivot_fused: launch number mod 2 * defer
+    // compact form of run_fused: P.T / T1 hold only the nonbasic columns and the RHS (slots), P.ld / P.C / P.shape
+    // describe that layout, and `ld_full` is the handle's own leading dimension (the launcher's policy choices follow the handle)
+    int compact, ld_full;
+    int32_t* slotvar;    // [compact ld] variable of every slot; the RHS slot holds the RHS column's index
+    int32_t* pslot;      // [128] slot of every partial argmin (the partials themselves carry the variable: ties break by variable)
+    int32_t* qring;      // [2 * defer] entering slot of every ring slot's pivot
+    int32_t* caux;       // {slot, ring slot} of a column zeroed for a pivot that was not taken (UNBOUNDED), or -1
 };
+// the compact form's entry and exit passes (lpx_pivot_fused.hip)
+struct CompactIo {
+    double* full; int ld, R, C;          // the handle's tableau: leading dimension, LIVE rows and columns
+    double* comp; int cld;               // the compact buffer and its leading dimension; C - R + 1 live slots
+    const int32_t* basis;                // [R - 1]
+    int32_t* vmap;                       // [C] scratch: slot of a nonbasic variable, -2 - row of a basic one
+    int32_t* slotvar; int32_t* flag;     // flag: set when a basic column is not a unit vector bit for bit, or the basis is not one
+};
+hipError_t launch_compact_entry(const CompactIo& io, int32_t* cshape, int32_t* caux, hipStream_t s);
+// applies the n pending pivots of the compact buffer `src` and writes the full layout (basic columns as unit vectors)
+hipError_t launch_compact_exit(const FusedParams& f, const CompactIo& io, const double* src, int n, int slot0, hipStream_t s);
 int fused_policy(int ld, int R);             // 0 = default cache policy (lpx_pivot_fused_c), 2 = streaming mix, 1 = all nt
 int pivot_defer_max();                       // deepest deferral the sweep kernels are built for
 hipError_t launch_fused_init(const FusedParams& f, hipStream_t s);
@@ -250,6 +268,7 @@ hipError_t launch_fused_init(const FusedParams& f, hipStream_t s);
 // rat: the handle's ratio buffer (capacity rows + 1 doubles, then the column launch's scan records: pivot_ratio_bytes(capacity rows)
 // in all), which only the pair uses
 bool pivot_select_is_pair(int ld, int R);
+bool pivot_compact_ok(int ld, int R, int d);   // depth d on this handle can run the compact form (the pair, a strip sweep built for d)
 size_t pivot_ratio_bytes(int R);
 size_t pivot_stream_bytes();                 // UPD_STREAM_BYTES: a handle above it cannot live in the Infinity Cache (deepest default deferral)
 hipError_t launch_pivot_fused(const FusedParams& f, double* rat, long long L, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);

@@ -1,5 +1,13 @@
 // lpx_pivot_fused.hip -- the one-launch primal pivot (K4f) and its deferred pivots: sweep kernels of every depth,
 // the select-only kernels (one launch through the workspace; the column and row launches of the pair), the flush and their launchers.  Built with -ffp-contract=off like every tile (lpx_kernels.hip).
+// Compact form (the _cm kernels, lpx_compact_*): a long run on a streamed handle sweeps a tableau of the nonbasic
+// columns and the RHS only.  A column is then a SLOT; F.slotvar names its variable.  Pivot k (entering slot s, row r): the column
+// launch stores +0.0 over the stored column s once its values are in the factor column of the ring slot (the slot holds the leaving
+// variable from here on, a unit column); the row launch takes the pivot element from that factor column, counts row r as 1.0 and the
+// objective row as +0.0 at s, writes +0.0 into the pending pivot rows at s, and the lane that owns s does the bookkeeping in
+// variables (basis, trace, slotvar).  The entering rule compares variables, the partial argmins carry the slot beside them.  A pivot
+// selected by a sweep launch is zeroed by the next column launch (or the exit pass).  Sweep bodies are untouched: they see a
+// narrower tableau.  Every other run uses the kernels without the flag, whose arithmetic and order are what they were.
 #include <algorithm>
 #include "lpx_scan.h"
 #include "lpx_tile.h"
@@ -117,7 +125,26 @@ __device__ __forceinline__ int fp_slot(int lm, int n, int s, int ring) { const i
 // select(k+1): the first nsel workgroups of a sweep launch, the whole of a select-only launch.  `sweeps`: this launch applies
 // its n pending pivots too (the stored tableau changes buffer).  U: rows in flight per lane in the column pass (the sweep
 // kernels' register budget of waves_per_eu(6) holds U = 4 with two spilled VGPRs, U = 6 spilled 19; the select-only kernel has no such budget).
-template <int U, int SU, int NC = 0>
+// Compact form (CM instantiations): columns are slots.  The entering rule compares VARIABLES (F.slotvar), so a
+// candidate carries its variable in MinIdx::i and its slot beside it; cm_feed / cm_pick / cm_wave_min are rule_feed / mi_pick /
+// wave_min_idx with the slot carried along (variables are unique, so the winner's lane is the one that holds its variable).
+__device__ __forceinline__ void cm_feed(MinIdx& m, int& mslot, int j, int var, double u)
+{
+    if (u < m.v || (u == m.v && m.i != INT_MAX && var < m.i)) { m.v = u; m.i = var; mslot = j; }      // the initial -eps is no candidate
+}
+__device__ __forceinline__ void cm_pick(MinIdx& a, int& aslot, MinIdx b, int bslot)
+{
+    if (b.v < a.v || (b.v == a.v && b.i < a.i)) { a = b; aslot = bslot; }
+}
+__device__ __forceinline__ MinIdx cm_wave_min(MinIdx x, int& slot)
+{
+    const MinIdx r = wave_min_idx(x);
+    const unsigned long long mk = __ballot(x.i == r.i);      // never empty: some lane holds the winner (or every lane INT_MAX and slot -1)
+    slot = __builtin_amdgcn_readlane(slot, __ffsll((long long)mk) - 1);
+    return r;
+}
+
+template <int U, int SU, int NC = 0, bool CM = false>
 __device__ __forceinline__ void fused_select(const FusedParams& F, int n_, bool sweeps)
 {
     const int n = NC > 0 ? NC : n_;                          // NC: the count known at compile time (d = 1: r03's select)
@@ -237,6 +264,7 @@ __device__ __forceinline__ void fused_select(const FusedParams& F, int n_, bool 
     }
     LPX_FS_W(5);
     MinIdx best; rule_init(rule, best);
+    int bslot = -1;                                          // CM: the slot of `best`, whose index is a variable
 #pragma unroll 2
     for (int j = j0 + t; j < j1; j += FP_NT) {
         double tr = trow[j], ov = orow[j];                   // -> T_{k+1}[r,j], T_{k+1}[m,j] (m is never a pivot row)
@@ -247,18 +275,38 @@ __device__ __forceinline__ void fused_select(const FusedParams& F, int n_, bool 
             tr = r == prs(s) ? pc : nt;
             ov = ov - pfm(s) * pc;
         }
+        if constexpr (CM) {
+            // slot q from here on holds the LEAVING variable: a unit column, 1.0 in row r and +0.0 in the objective row.  The lane
+            // that owns it does the pivot's bookkeeping in variables: nobody else reads basis[r] or slotvar[q] in this launch
+            int var = F.slotvar[j];
+            if (j == q) {
+                const int lv = P.basis[r];
+                tr = 1.0; ov = 0.0;
+                P.basis[r] = var;                                // basis[leaving] = entering, :110
+                if (iter < P.trace_cap) { P.trace[2 * iter] = r; P.trace[2 * iter + 1] = var; }
+                F.slotvar[j] = lv; F.qring[lm] = q;
+                var = lv;
+            }
+            const double p = tr / piv;
+            prown[j] = p;
+            const double u = ov - fs * p;
+            if (j < C - 1) cm_feed(best, bslot, j, var, u);
+        } else {
         const double p = tr / piv;                               // true division, :250
         prown[j] = p;
         const double u = ov - fs * p;                            // what the sweep of pivot k+1 will store at T[m,j]
         rule_feed(rule, best, j, u);
+        }
     }
     LPX_FS_W(6);
-    best = wave_min_idx(best);
+    if constexpr (CM) best = cm_wave_min(best, bslot);
+    else best = wave_min_idx(best);
     // last-workgroup reduction of the partial argmins: the hand-off of lpx_select_mb (agent-scope stores, wait, barrier, one add)
     if ((t & 63) == 0) {
         const int slot = b * (FP_NT / 64) + (t >> 6);
         __hip_atomic_store(&P.part_v[slot], best.v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(&P.part_i[slot], best.i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if constexpr (CM) __hip_atomic_store(&F.pslot[slot], bslot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -268,17 +316,23 @@ __device__ __forceinline__ void fused_select(const FusedParams& F, int n_, bool 
         last = __builtin_amdgcn_readfirstlane(last);
         if (last) {
             MinIdx x; x.v = __builtin_inf(); x.i = INT_MAX;
+            int xs = -1;
             const int npart = nsel * (FP_NT / 64);               // <= 128
             if (t < npart) {
                 x.v = __hip_atomic_load(&P.part_v[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 x.i = __hip_atomic_load(&P.part_i[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if constexpr (CM) xs = __hip_atomic_load(&F.pslot[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             if (t + 64 < npart) {
                 MinIdx y;
                 y.v = __hip_atomic_load(&P.part_v[t + 64], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 y.i = __hip_atomic_load(&P.part_i[t + 64], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if constexpr (CM) cm_pick(x, xs, y, __hip_atomic_load(&F.pslot[t + 64], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                else
                 x = mi_pick(x, y);
             }
+            if constexpr (CM) { x = cm_wave_min(x, xs); if (x.i != INT_MAX) x.i = xs; }     // the record's qn is a slot
+            else
             x = wave_min_idx(x);
             if (t == 0) {
                 nxt->qn = (x.i == INT_MAX) ? -1 : x.i;           // the one field of the record this workgroup writes
@@ -288,8 +342,10 @@ __device__ __forceinline__ void fused_select(const FusedParams& F, int n_, bool 
     }
     LPX_FS_W(7);
     if (b == 0 && t == 0) {
+        if constexpr (!CM) {                                     // CM: the lane that owns slot q has done these, in variables
         P.basis[r] = q;                                          // basis[leaving] = entering, :110
         if (iter < P.trace_cap) { P.trace[2 * iter] = r; P.trace[2 * iter + 1] = q; }
+        }
         F.rring[lm] = r;
         nxt->status = LPX_RUNNING; nxt->iter = iter + 1; nxt->r = r; nxt->q = q;
         nxt->phase = cur.phase; nxt->fdf_count = cur.fdf_count; nxt->dual_iter = cur.dual_iter;
@@ -478,6 +534,14 @@ __global__ __launch_bounds__(FP_NT) __attribute__((amdgpu_waves_per_eu(fp_strip_
     } else if constexpr (D <= 2) fused_sweep<true, D>(F, ncw, nunits, mixmod);
     else fused_sweep_strip<true, D>(F, ncw, nunits, mixmod);
 }
+// the compact form's sweep launch: the strip sweep as it is (a slot is a column to it), the select half in slots and variables
+template <int D>
+__global__ __launch_bounds__(FP_NT) __attribute__((amdgpu_waves_per_eu(fp_strip_wpe(D)))) void lpx_pivot_fused_cm(FusedParams F, int ncw, int nunits, int mixmod)
+{
+    static_assert(D >= 3, "the compact form runs the strip sweeps only");
+    if ((int)blockIdx.x < F.P.nblk) fused_select<4, 1, 0, true>(F, F.defer, true);
+    else fused_sweep_strip<true, D>(F, ncw, nunits, mixmod);
+}
 template <int D>
 __global__ __launch_bounds__(FP_NT) __attribute__((amdgpu_waves_per_eu(6))) void lpx_pivot_fused_c(FusedParams F, int ncw, int nunits, int mixmod)
 {
@@ -558,7 +622,7 @@ __device__ __forceinline__ void pivot_ratio_patch(const FusedParams& F, int c, i
     if (N >= 2 && blockIdx.x == 0 && threadIdx.x == 0) F.rec[c].qn = q;
 }
 struct SelcExchange { double v[SELC_ROWS / 64]; int i[SELC_ROWS / 64]; int n[SELC_ROWS / 64]; };      // the waves' shares of the scan record
-template <int N>
+template <int N, bool CM = false>
 __device__ __forceinline__ void pivot_ratio_rows(const FusedParams& F, double* __restrict__ rat, SelcExchange& X)
 {
     const SelParams& P = F.P;
@@ -572,9 +636,11 @@ __device__ __forceinline__ void pivot_ratio_rows(const FusedParams& F, double* _
     // entering column is still its nsel partial argmins.  Every wave loads them in this round (lane k: partial k, lanes past the
     // last repeat it) and reduces them as the last-arriver did -- the same wave_min_idx, the same q, tie-break included.
     MinIdx part; part.v = 0.0; part.i = 0;
+    int pslot = -1;                                          // CM: the partial's slot (its index is a variable)
     if (N >= 2) {
         const int k = min(t & 63, P.nblk - 1);
         part.v = P.part_v[k]; part.i = P.part_i[k];
+        if constexpr (CM) pslot = F.pslot[k];
     }
     const DevState cur = F.rec[c];
     // the partials' loads stay in this round: left alone, they sink behind the leave tests.  The record and the shape are named so
@@ -584,8 +650,11 @@ __device__ __forceinline__ void pivot_ratio_rows(const FusedParams& F, double* _
     int q = cur.qn;
     if (status != LPX_RUNNING || primal_count >= P.max_iter) return;     // the row launch writes the record of a run that is over
     if (N >= 2) {
+        if constexpr (CM) { part = cm_wave_min(part, pslot); q = part.i == INT_MAX ? -1 : pslot; }
+        else {
         part = wave_min_idx(part);
         q = part.i == INT_MAX ? -1 : part.i;
+        }
     }
     // N >= 2: the record gets its entering column from workgroup 0 (pivot_ratio_patch), for the row launch of this step to read
     // behind the kernel boundary; nothing in this launch reads the field, every wave has its own q.  The store comes last, or
@@ -604,7 +673,11 @@ __device__ __forceinline__ void pivot_ratio_rows(const FusedParams& F, double* _
     // round 2: the column, the RHS column, the N factor columns and, last (the wave waits for them in issue order, so the chain's
     // first v_readlane waits for the whole round), the pending pivots' scalars: lane k of every wave holds pq and r of pending
     // pivot k (0 = oldest; lanes past the newest repeat it)
-    const double v0 = src[(size_t)ic * ld + q], h = rhsc[ic];
+    // CM: the stored column is read and then zeroed by this very lane (a slot that holds a basic variable is +0.0 throughout, the
+    // objective row included), so the pointer it goes through is not the restrict-qualified one
+    double* srcw = buf ? F.T1 : P.T;
+    double v0 = CM ? srcw[(size_t)ic * ld + q] : src[(size_t)ic * ld + q];
+    const double h = rhsc[ic];
     double f[N > 0 ? N : 1], pqv = 0.0, prhs = 0.0;
     int rsv = -1;
     if (N > 0) {
@@ -618,6 +691,12 @@ __device__ __forceinline__ void pivot_ratio_rows(const FusedParams& F, double* _
     LPX_FC_W(1);
     // T_{k+1}[i,q] and T_{k+1}[i,C-1] as the sweep stores them: the column through every pending pivot, oldest first (row r_s: the
     // normalised pivot row), the RHS column kept current in rhsc up to the newest pending pivot, which is applied here
+    if constexpr (CM && N == 1) {
+        // the pending pivot may be one that a sweep launch selected: its select half could not zero the slot's column while the
+        // sweep's waves were writing it.  It is zeroed here (again, harmlessly, behind the prologue), and read as zero
+        if (q == cur.q) v0 = 0.0;
+        if (i < R) srcw[(size_t)i * ld + cur.q] = 0.0;
+    }
     double v = v0;
 #pragma unroll
     for (int s = 0; s < N; ++s) {
@@ -636,6 +715,7 @@ __device__ __forceinline__ void pivot_ratio_rows(const FusedParams& F, double* _
     if (i < R) {
         rat[i] = ratio;
         facn[i] = dn; rhsn[i] = nm;                          // factors of pivot k+1, numerators of the test after it
+        if constexpr (CM) srcw[(size_t)i * ld + q] = 0.0;    // its values live on in facn: the slot now holds the leaving variable
         if (i == m) rat[P.R] = dn;                           // T_{k+1}[m,q]: row m belongs to exactly one lane
     }
     // The workgroup's scan record (SelcRec, lpx_block.h) over its live constraint rows i < m, with the expressions of
@@ -666,6 +746,35 @@ __device__ __forceinline__ void pivot_ratio_rows(const FusedParams& F, double* _
     LPX_FC_END(N);
 }
 
+template <bool CM>
+__device__ __forceinline__ void pivot_ratio_switch(const FusedParams& F, double* __restrict__ rat, SelcExchange& X)
+{
+    switch (F.lm % F.defer) {
+    case 0: pivot_ratio_rows<0, CM>(F, rat, X); break;
+    case 1: pivot_ratio_rows<1, CM>(F, rat, X); break;
+    case 2: pivot_ratio_rows<2, CM>(F, rat, X); break;
+    case 3: pivot_ratio_rows<3, CM>(F, rat, X); break;
+    case 4: pivot_ratio_rows<4, CM>(F, rat, X); break;
+    case 5: pivot_ratio_rows<5, CM>(F, rat, X); break;
+    case 6: pivot_ratio_rows<6, CM>(F, rat, X); break;
+    case 7: pivot_ratio_rows<7, CM>(F, rat, X); break;
+    case 8: pivot_ratio_rows<8, CM>(F, rat, X); break;
+    case 9: pivot_ratio_rows<9, CM>(F, rat, X); break;
+    case 10: pivot_ratio_rows<10, CM>(F, rat, X); break;
+    case 11: pivot_ratio_rows<11, CM>(F, rat, X); break;
+    case 12: pivot_ratio_rows<12, CM>(F, rat, X); break;
+    case 13: pivot_ratio_rows<13, CM>(F, rat, X); break;
+    case 14: pivot_ratio_rows<14, CM>(F, rat, X); break;
+    default: pivot_ratio_rows<SELP_PMAX, CM>(F, rat, X); break;
+    }
+}
+// the compact form's column launch
+__global__ __launch_bounds__(SELC_ROWS) void lpx_pivot_ratio_cm(FusedParams F, double* __restrict__ rat)
+{
+    __shared__ SelcExchange X;
+    pivot_ratio_switch<true>(F, rat, X);
+}
+
 __global__ __launch_bounds__(SELC_ROWS) void lpx_pivot_ratio(FusedParams F, double* __restrict__ rat)
 {
     __shared__ SelcExchange X;
@@ -690,11 +799,13 @@ __global__ __launch_bounds__(SELC_ROWS) void lpx_pivot_ratio(FusedParams F, doub
 }
 static_assert(SELP_PMAX == 15, "lpx_pivot_ratio: one case per pending count");
 
-__global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const double* __restrict__ rat, const SelcRec* recs)
+template <bool CM>
+__device__ __forceinline__ void pivot_select_body(const FusedParams& F, const double* __restrict__ rat, const SelcRec* recs)
 {
     extern __shared__ double sp_rat[];                       // the ratios of the test, one per row of the handle
     __shared__ double s_v[SELP_NT / 64];
     __shared__ int s_i[SELP_NT / 64];
+    __shared__ int s_s[SELP_NT / 64];                        // CM: the slots of the waves' candidates
     const SelParams& P = F.P;
     const int t = threadIdx.x, b = blockIdx.x, lane = t & 63;
     const int lm = F.lm, ring = 2 * F.defer;
@@ -735,6 +846,8 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const
         for (int k = SELP_SB; k < SELP_PMAX; ++k) pc0[k] = F.pring[pslot(k) * ld + jc0];
     }
     const int rsv = F.rring[kslot];                          // pending pivot `ks`: its row as the ring has it
+    int var0 = 0;                                            // CM: the variable in this lane's first slot
+    if constexpr (CM) var0 = F.slotvar[jc0];
     // the record's loads stay here, in flight beside the scan records' (which the clobber holds in place): left alone, the compiler sinks them
     asm volatile("" :: "s"(cur.status), "s"(cur.qn), "s"(cur.pad[3]), "s"(R) : "memory");
     const int status = cur.status, seq = cur.pad[2], buf = cur.pad[3] & 1;
@@ -761,7 +874,7 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const
     if (final_status == LPX_RUNNING) {
         // behind the record, beside the replay: what needs the record (buffer, q) or the live m, but not r
         ov0 = orow[jc0];
-        pqv = F.pring[kslot * ld + q];
+        if constexpr (!CM) pqv = F.pring[kslot * ld + q];
         pfmv = F.fring[kslot * fld + m];
         asm volatile("" ::: "memory");
         // The leaving row: the hysteresis chain of block_hysteresis_segments replayed over the S records of the live rows (S
@@ -815,6 +928,8 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const
             x.status = final_status; x.r = -1; x.q = -1; x.qn = -1; x.pad[2] = seq + 1;
             x.pad[3] = fp_rec(buf, n, fp_slot(lm, n, 0, ring));
             *nxt = x;
+            // CM: the column launch has zeroed slot q for a pivot that is not taken; the exit pass puts it back from ring slot lm
+            if constexpr (CM) { if (final_status == LPX_UNBOUNDED) { F.caux[0] = q; F.caux[1] = lm; } }
         }
         return;
     }
@@ -824,8 +939,11 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const
     // round 2, the three loads that need r: row r's factors (lane k: pending pivot k), the pivot element T_{k+1}[r,q] -- the
     // column's own chain waits for those -- and row r at this lane's first column.  Everything else is in flight since round 1.
     const double pfrv = F.fring[kslot * fld + r];
-    double piv = trow[q];
+    // CM: the column launch has zeroed the stored slot q; the pivot element and its chain are that launch's facn[r], the same bits
+    double piv = CM ? F.fring[(size_t)lm * fld + r] : trow[q];
     const double tr0 = trow[jc0];
+    int lv = 0;                                              // CM: the leaving variable (used by the lane that owns slot q)
+    if constexpr (CM) lv = P.basis[r];
     LPX_FS(1);
     // while those three are in flight: the objective row through the pending pivots, which needs none of them (the same
     // mul-then-sub, oldest first, that the row loop applies to a later pass's columns)
@@ -835,15 +953,20 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const
         if (k < n) ov1 = ov1 - lane_f64(pfmv, k) * pc0[k];
     }
     asm volatile("" : "+v"(ov1));                            // in front of the chain's wait, not behind it
+    if constexpr (!CM) {
     for (int s = 0; s < n; ++s) {
         const double pq = lane_f64(pqv, s);
         const double nv = piv - lane_f64(pfrv, s) * pq;
         piv = r == prs(s) ? pq : nv;
     }
+    }
     LPX_FS_W(5);
     MinIdx best; rule_init(rule, best);
+    int bslot = -1;                                          // CM: the slot of `best`, whose index is a variable
     for (int jb = j0; jb < j1; jb += SELP_NT) {
         const int j = jb + t, jc = min(j, C - 1);
+        int var = var0;
+        if constexpr (CM) { if (jb != j0) var = F.slotvar[jc]; }
         double tr = tr0, ov = ov1, pc[SELP_PMAX];
 #pragma unroll
         for (int k = 0; k < SELP_PMAX; ++k) pc[k] = pc0[k];
@@ -870,6 +993,26 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const
                 tr = r == prs(k) ? pc[k] : nt;
             }
         }
+        if constexpr (CM) {
+            if (j < j1) {
+                // slot q from here on holds the LEAVING variable: a unit column, 1.0 in row r and +0.0 in the objective row, and +0.0
+                // in every pending pivot's row (written here: the one store into a ring slot this launch also reads -- by this lane
+                // alone, above).  The lane that owns the slot does the pivot's bookkeeping in variables: nobody else
+                // uses basis[r] or slotvar[q] in this launch
+                if (j == q) {
+                    tr = 1.0; ov = 0.0;
+                    P.basis[r] = var;                            // basis[leaving] = entering, :110
+                    if (iter < P.trace_cap) { P.trace[2 * iter] = r; P.trace[2 * iter + 1] = var; }
+                    F.slotvar[j] = lv; F.qring[lm] = q;
+                    for (int k = 0; k < n; ++k) F.pring[pslot(k) * ld + j] = 0.0;
+                    var = lv;
+                }
+                const double p = tr / piv;
+                prown[j] = p;
+                const double u = ov - fs * p;
+                if (j < C - 1) cm_feed(best, bslot, j, var, u);
+            }
+        } else
         if (j < j1) {
             const double p = tr / piv;                           // true division, :250
             prown[j] = p;
@@ -886,17 +1029,26 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const
     // The block's argmin with one barrier: s_v / s_i have no other user in this kernel (the exact scan behind a tie works on
     // sp_rat), so nothing has to be protected in front of the stores, and the eight waves' entries take three steps of the scan
     static_assert(SELP_NT / 64 == 8, "lanes8_min_idx: one entry per wave");
+    if constexpr (CM) {
+        best = cm_wave_min(best, bslot);
+        if (lane == 0) { s_v[t >> 6] = best.v; s_i[t >> 6] = best.i; s_s[t >> 6] = bslot; }
+        __syncthreads();
+        best.v = s_v[lane & 7]; best.i = s_i[lane & 7]; bslot = s_s[lane & 7];
+        best = cm_wave_min(best, bslot);                     // every entry eight times over: the minimum of the eight
+    } else {
     best = wave_min_idx(best);
     if (lane == 0) { s_v[t >> 6] = best.v; s_i[t >> 6] = best.i; }
     __syncthreads();
     best.v = s_v[lane & 7]; best.i = s_i[lane & 7];
     best = lanes8_min_idx(best);
+    }
     if (n >= 1 && n <= F.defer - 2) {
-        if (t == 0) { P.part_v[b] = best.v; P.part_i[b] = best.i; }
+        if (t == 0) { P.part_v[b] = best.v; P.part_i[b] = best.i; if constexpr (CM) F.pslot[b] = bslot; }
     } else if (t < 64) {
         if (t == 0) {
             __hip_atomic_store(&P.part_v[b], best.v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(&P.part_i[b], best.i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if constexpr (CM) __hip_atomic_store(&F.pslot[b], bslot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         int last = 0;
@@ -904,10 +1056,14 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const
         last = __builtin_amdgcn_readfirstlane(last);
         if (last) {
             MinIdx x; x.v = __builtin_inf(); x.i = INT_MAX;
+            int xs = -1;
             if (t < nsel) {                                      // nsel <= MB_MAXB = 64 partials
                 x.v = __hip_atomic_load(&P.part_v[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 x.i = __hip_atomic_load(&P.part_i[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if constexpr (CM) xs = __hip_atomic_load(&F.pslot[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
+            if constexpr (CM) { x = cm_wave_min(x, xs); if (x.i != INT_MAX) x.i = xs; }     // the record's qn is a slot
+            else
             x = wave_min_idx(x);
             if (t == 0) {
                 nxt->qn = (x.i == INT_MAX) ? -1 : x.i;           // the one field of the record this workgroup writes
@@ -917,8 +1073,10 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const
     }
     LPX_FS_W(7);
     if (b == 0 && t == 0) {
+        if constexpr (!CM) {                                     // CM: the lane that owns slot q has done these, in variables
         P.basis[r] = q;                                          // basis[leaving] = entering, :110
         if (iter < P.trace_cap) { P.trace[2 * iter] = r; P.trace[2 * iter + 1] = q; }
+        }
         F.rring[lm] = r;
         nxt->status = LPX_RUNNING; nxt->iter = iter + 1; nxt->r = r; nxt->q = q;
         nxt->phase = cur.phase; nxt->fdf_count = cur.fdf_count; nxt->dual_iter = cur.dual_iter;
@@ -928,6 +1086,15 @@ __global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const
     }
     LPX_FS_W(8);
     LPX_FS_END(n);
+}
+__global__ __launch_bounds__(SELP_NT) void lpx_pivot_select(FusedParams F, const double* __restrict__ rat, const SelcRec* recs)
+{
+    pivot_select_body<false>(F, rat, recs);
+}
+// the compact form's row launch
+__global__ __launch_bounds__(SELP_NT) void lpx_pivot_select_cm(FusedParams F, const double* __restrict__ rat, const SelcRec* recs)
+{
+    pivot_select_body<true>(F, rat, recs);
 }
 
 // End of a run: the n pivots still pending (record: buffer, count, oldest slot) applied to the stored tableau, written to
@@ -950,6 +1117,88 @@ __global__ __launch_bounds__(256) void lpx_pivot_flush(FusedParams F, int buf, i
         v = i == F.rring[sl] ? pc : nv;
     }
     P.T[(size_t)i * ld + j] = v;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Compact form: the entry and exit passes of a run.  Variables v < C - 1, slots in the order of the variables.
+// ------------------------------------------------------------------------------------------------
+static constexpr int CE_NT = 1024;
+// one workgroup: vmap[v] = slot of a nonbasic variable, -2 - row of a basic one; slotvar; the compact shape; flag on a bad basis
+__global__ __launch_bounds__(CE_NT) void lpx_compact_map(CompactIo io, int32_t* cshape, int32_t* caux)
+{
+    __shared__ int s_cnt[CE_NT];
+    const int t = threadIdx.x, nv = io.C - 1, m = io.R - 1;
+    for (int v = t; v < nv; v += CE_NT) io.vmap[v] = 0;
+    if (t == 0) { cshape[0] = io.R; cshape[1] = io.C - io.R + 1; caux[0] = -1; caux[1] = 0; }
+    __syncthreads();
+    for (int k = t; k < m; k += CE_NT) {
+        const int v = io.basis[k];
+        if (v < 0 || v >= nv || atomicCAS(&io.vmap[v], 0, -2 - k) != 0) *io.flag = 1;    // out of range, or named twice
+    }
+    __syncthreads();
+    const int per = (nv + CE_NT - 1) / CE_NT, v0 = min(nv, t * per), v1 = min(nv, v0 + per);
+    int cnt = 0;
+    for (int v = v0; v < v1; ++v) cnt += io.vmap[v] == 0;
+    s_cnt[t] = cnt;
+    __syncthreads();
+    if (t == 0) { int run = 0; for (int k = 0; k < CE_NT; ++k) { const int c = s_cnt[k]; s_cnt[k] = run; run += c; } }
+    __syncthreads();
+    int slot = s_cnt[t];
+    for (int v = v0; v < v1; ++v) {
+        if (io.vmap[v] == 0) { io.vmap[v] = slot; io.slotvar[slot] = v; ++slot; }
+    }
+    if (t == 0) { io.vmap[nv] = io.C - io.R; io.slotvar[io.C - io.R] = nv; }              // the RHS: the last slot
+}
+// vmap from slotvar and basis as a run left them (the exit pass's gather)
+__global__ __launch_bounds__(256) void lpx_compact_unmap(CompactIo io)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k <= io.C - io.R) io.vmap[io.slotvar[k]] = k;
+    if (k < io.R - 1) io.vmap[io.basis[k]] = -2 - k;
+}
+// one lane per element of the full tableau: a nonbasic column goes to its slot, a basic one is checked -- bit for bit 1.0 in its
+// row and +0.0 elsewhere, the objective row included; anything else (a -0.0, a value one ulp off) raises the flag and the run
+// takes the full path.  The lane of the RHS column also clears the padding behind the last slot.
+__global__ __launch_bounds__(256) void lpx_compact_gather(CompactIo io)
+{
+    const int i = blockIdx.y, v = blockIdx.x * 256 + threadIdx.x;
+    if (i >= io.R || v >= io.C) return;
+    const double x = io.full[(size_t)i * io.ld + v];
+    const int mp = io.vmap[v];
+    if (mp >= 0) {
+        io.comp[(size_t)i * io.cld + mp] = x;
+        if (v == io.C - 1) for (int j = mp + 1; j < io.cld; ++j) io.comp[(size_t)i * io.cld + j] = 0.0;
+    } else {
+        const double want = i == -2 - mp ? 1.0 : 0.0;
+        if (__double_as_longlong(x) != __double_as_longlong(want)) *io.flag = 1;
+    }
+}
+// End of a compact run: lpx_pivot_flush in slots (the n pending pivots applied, oldest first), scattered into the full layout with
+// the basic columns written as unit vectors and the padding as zero.  Two columns take their stored values from elsewhere: with
+// one pivot pending, its slot reads as zero (a sweep launch may have selected it: see the column launch); the slot zeroed for a
+// pivot that was not taken (UNBOUNDED, caux) comes back from that step's factor column, which is the column through all n.
+__global__ __launch_bounds__(256) void lpx_compact_exit(FusedParams F, CompactIo io, const double* src, int n, int slot0)
+{
+    const int i = blockIdx.y, v = blockIdx.x * 256 + threadIdx.x;
+    if (i >= io.R || v >= io.ld) return;
+    double x = 0.0;
+    if (v < io.C) {
+        const int mp = io.vmap[v];
+        if (mp < 0) x = i == -2 - mp ? 1.0 : 0.0;
+        else if (mp == F.caux[0]) x = F.fring[(size_t)F.caux[1] * F.P.R + i];
+        else {
+            const size_t cld = (size_t)io.cld, fld = (size_t)F.P.R;
+            const int ring = 2 * F.defer;
+            x = (n == 1 && mp == F.qring[slot0]) ? 0.0 : src[(size_t)i * cld + mp];
+            for (int s = 0; s < n; ++s) {
+                const int sl = slot0 + s < ring ? slot0 + s : slot0 + s - ring;
+                const double pc = F.pring[(size_t)sl * cld + mp];
+                const double nx = x - F.fring[(size_t)sl * fld + i] * pc;
+                x = i == F.rring[sl] ? pc : nx;
+            }
+        }
+    }
+    io.full[(size_t)i * io.ld + v] = x;
 }
 
 // Cache policy of the fused launch.  Two buffers share the Infinity Cache, so the default policy only pays while BOTH fit with
@@ -987,7 +1236,15 @@ static hipError_t launch_pivot_select_pair(const FusedParams& f, double* rat, hi
     const dim3 gc((f.P.R + SELC_ROWS - 1) / SELC_ROWS), gr(f.P.nblk);        // the column grid follows the capacity
     const size_t lds = sizeof(double) * (size_t)f.P.R;
     const SelcRec* recs = reinterpret_cast<const SelcRec*>(rat + selc_rec_offset(f.P.R));
-    if (e0 && e1) {
+    if (f.compact) {
+        if (e0 && e1) {
+            hipExtLaunchKernelGGL(lpx_pivot_ratio_cm, gc, dim3(SELC_ROWS), 0, s, e0, nullptr, 0, f, rat);
+            hipExtLaunchKernelGGL(lpx_pivot_select_cm, gr, dim3(SELP_NT), lds, s, nullptr, e1, 0, f, (const double*)rat, recs);
+        } else {
+            hipLaunchKernelGGL(lpx_pivot_ratio_cm, gc, dim3(SELC_ROWS), 0, s, f, rat);
+            hipLaunchKernelGGL(lpx_pivot_select_cm, gr, dim3(SELP_NT), lds, s, f, (const double*)rat, recs);
+        }
+    } else if (e0 && e1) {
         hipExtLaunchKernelGGL(lpx_pivot_ratio, gc, dim3(SELC_ROWS), 0, s, e0, nullptr, 0, f, rat);
         hipExtLaunchKernelGGL(lpx_pivot_select, gr, dim3(SELP_NT), lds, s, nullptr, e1, 0, f, (const double*)rat, recs);
     } else {
@@ -1001,6 +1258,24 @@ size_t pivot_stream_bytes() { return UPD_STREAM_BYTES; }
 size_t pivot_ratio_bytes(int R) { return selc_ratio_bytes(R); }
 bool pivot_select_is_pair(int ld, int R) { return R <= SELP_LDS_ROWS && tableau_bytes(ld, R) > ((size_t)SELP_MIN_MB << 20); }
 
+// The compact form's sweep kernels: the depths of the defaults and one small one; a run of another depth keeps the full layout.
+static FusedKernel compact_kernel(int d)
+{
+    switch (d) {
+    case 3: return lpx_pivot_fused_cm<3>;
+    case 4: return lpx_pivot_fused_cm<4>;
+    case 8: return lpx_pivot_fused_cm<8>;
+    case 12: return lpx_pivot_fused_cm<12>;
+    case 16: return lpx_pivot_fused_cm<16>;
+    default: return nullptr;
+    }
+}
+// a run of depth d on this handle (leading dimension, capacity rows) can take the compact form: the select-only pair and a strip sweep
+bool pivot_compact_ok(int ld, int R, int d)
+{
+    return pivot_select_is_pair(ld, R) && fused_policy(ld, R) != 0 && d >= 3 && compact_kernel(d) != nullptr;
+}
+
 hipError_t launch_pivot_fused(const FusedParams& f0, double* rat, long long L, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
 {
     FusedParams f = f0;
@@ -1008,7 +1283,9 @@ hipError_t launch_pivot_fused(const FusedParams& f0, double* rat, long long L, h
     if (d < 1 || d > FP_DMAX) return hipErrorInvalidValue;
     f.lm = (int)(L % (2 * d)); f.par = f.lm & 1;
     const bool sweep = L > 0 && L % d == 0;
-    const int ld = f.P.ld, R = f.P.R;
+    // the compact form: the handle's own leading dimension decides what runs (the pair, the policy, the store mix -- what the handle
+    // ran before), the compact one only the sweep's geometry
+    const int ld = f.compact ? f.ld_full : f.P.ld, R = f.P.R;
     if (!sweep) {
         // The pair (ratios through the handle's ratio buffer into LDS) while the handle's rows fit the cap, the one-launch form
         // through the workspace beyond it -- and at small sizes: the pair's predecessor (one launch, ratios in LDS, SELP_SB factor
@@ -1023,7 +1300,7 @@ hipError_t launch_pivot_fused(const FusedParams& f0, double* rat, long long L, h
     const int rows = fp_rows(d);
     const int pol = fused_policy(ld, R);
     const int strip = (pol != 0 && d >= 3) ? FP_STRIP_BLOCKS : 1;           // the streaming kernels of d >= 3: a wave per strip of blocks
-    const int ncw = (ld + 127) / 128, nunits = ncw * (((R + rows - 1) / rows + strip - 1) / strip);
+    const int ncw = (f.P.ld + 127) / 128, nunits = ncw * (((R + rows - 1) / rows + strip - 1) / strip);
     const int nblocks = f.P.nblk + (nunits + (FP_NT / 64) - 1) / (FP_NT / 64);
     int mixmod = pol == 2 ? mixmod_for(tableau_bytes(ld, R)) : 0;            // 0: every store nontemporal
     // the stored-through row is the last of every mixmod-th block: at `rows` per block the block period shrinks in proportion so
@@ -1031,7 +1308,8 @@ hipError_t launch_pivot_fused(const FusedParams& f0, double* rat, long long L, h
     // instead of one in three goes through the cache at eight rows per block -- the sweep's PMC traffic stays 1.029x of
     // 16 R C; the other share was not measured
     if (mixmod > 1) mixmod = std::max(1, mixmod * UPDS_ROWS / rows);
-    const FusedKernel kern = pol == 0 ? FusedKernels::c[d - 1] : FusedKernels::nt[d - 1];   // both buffers in the Infinity Cache: default policy
+    if (f.compact && !pivot_compact_ok(ld, R, d)) return hipErrorInvalidValue;
+    const FusedKernel kern = f.compact ? compact_kernel(d) : pol == 0 ? FusedKernels::c[d - 1] : FusedKernels::nt[d - 1];   // both buffers in the Infinity Cache: default policy
     return launch_k(kern, dim3(nblocks), dim3(FP_NT), 0, s, e0, e1, f, ncw, nunits, mixmod);
 }
 
@@ -1042,10 +1320,26 @@ hipError_t launch_pivot_flush(const FusedParams& f, int buf, int n, int slot0, h
     return hipGetLastError();
 }
 
+hipError_t launch_compact_entry(const CompactIo& io, int32_t* cshape, int32_t* caux, hipStream_t s)
+{
+    hipLaunchKernelGGL(lpx_compact_map, dim3(1), dim3(CE_NT), 0, s, io, cshape, caux);
+    hipLaunchKernelGGL(lpx_compact_gather, dim3((io.C + 255) / 256, io.R), dim3(256), 0, s, io);
+    return hipGetLastError();
+}
+
+hipError_t launch_compact_exit(const FusedParams& f, const CompactIo& io, const double* src, int n, int slot0, hipStream_t s)
+{
+    hipLaunchKernelGGL(lpx_compact_unmap, dim3((std::max(io.R, io.C - io.R + 1) + 255) / 256), dim3(256), 0, s, io);
+    hipLaunchKernelGGL(lpx_compact_exit, dim3((io.ld + 255) / 256, io.R), dim3(256), 0, s, f, io, src, n, slot0);
+    return hipGetLastError();
+}
+
 // once per process (ensure_device): the dynamic LDS lpx_pivot_select (the row launch) may ask for
 hipError_t pivot_fused_init()
 {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(lpx_pivot_select), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * SELP_LDS_ROWS);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lpx_pivot_select), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * SELP_LDS_ROWS);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(lpx_pivot_select_cm), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * SELP_LDS_ROWS);
 }
 #ifdef LPX_STAMPS
 hipError_t pivot_fused_stamps(unsigned long long* acc, int clear) { return stamps_take(acc, clear); }

@@ -157,7 +157,7 @@ void lpx_tableau_destroy(lpx_tableau* t)
     for (hipEvent_t e : t->events) hipEventDestroy(e);
     hipFree(t->T); hipFree(t->slab); hipFree(t->snapT); hipFree(t->snapBasis);
     hipFree(t->frows); hipFree(t->fcols); hipFree(t->fchosen); hipFree(t->cutbuf);
-    hipFree(t->fT); hipFree(t->fslab); hipFree(t->dring);
+    hipFree(t->fT); hipFree(t->fslab); hipFree(t->dring); hipFree(t->cslab);
     hipFree(t->rgws);
     t->bnd.free();
     hipFree(t->xr); hipFree(t->xp); hipFree(t->xgen); hipFree(t->xbasis); hipFree(t->xT); hipFree(t->xc); hipFree(t->xq);
@@ -433,6 +433,29 @@ static int defer_ring(lpx_tableau* t, int d)
 // lpx_stats.launches counts steps either way).  The state record the host polls is one launch behind the device's, so the loop gets a few iterations
 // of slack; when it ends, the pivots still pending are applied (lpx_pivot_flush, into buffer 0), or the tableau, when none
 // are, may sit in the second buffer and is brought home (a device-to-device copy of the live rows, ~0.1 ms per 400 MB).
+//
+// Compact form: a basic column is a unit vector before and after every pivot, so a long run leaves the R - 1 of
+// them out.  The entry pass gathers the nonbasic columns and the RHS (slots, in the order of the variables) into the second
+// buffer and checks every basic column bit for bit; the loop runs on that buffer and on the handle's own as the pair, with slot
+// coordinates in its records; the exit pass applies the pending pivots and writes the full layout back.  No tableau-sized
+// allocation: a handle pays for the maps (8 bytes per column).  LPX_PIVOT_COMPACT=0: never, =1: whatever the budget.
+// shortest budget, in sweeps, that takes the compact form.  Kernel trace at 4097 x 12289, d = 16: the entry pass 26 + 140 us,
+// the exit pass 574 us against the flush's 466, one more host round trip for the flag -- about 0.3 ms -- against 39.5 us off every sweep
+static constexpr int COMPACT_MIN_SWEEPS = 8;
+static int pivot_compact_env()
+{
+    static const int v = [] { const char* e = std::getenv("LPX_PIVOT_COMPACT"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
+    return v;
+}
+// the maps of the compact form, on first use: slotvar [ld], vmap [Ccap], partial slots [128], ring slots' entering slots, {caux, shape, flag}
+static bool compact_buffers(lpx_tableau* t)
+{
+    if (t->cslab) return true;
+    const size_t ints = (size_t)t->ld + (size_t)t->Ccap + 128 + 2 * (size_t)pivot_defer_max() + 8;
+    if (malloc_retry((void**)&t->cslab, sizeof(int32_t) * ints) != hipSuccess) { (void)hipGetLastError(); t->cslab = nullptr; return false; }
+    return true;
+}
+
 static int run_fused(lpx_tableau* t, const SelParams& p, const lpx_run_opts* o, lpx_stats* stats, int start_iter)
 {
     const int d = pivot_defer(t->ld, t->Rcap);
@@ -443,6 +466,32 @@ static int run_fused(lpx_tableau* t, const SelParams& p, const lpx_run_opts* o, 
     f.fring = f.pring + (size_t)t->dring_slots * t->ld;
     f.rring = (int32_t*)(f.fring + (size_t)t->dring_slots * t->Rcap);
     f.defer = d;
+    t->last_compact = false;
+    CompactIo io; std::memset(&io, 0, sizeof(io));
+    double pass_ms = 0.0;                            // the entry and exit passes: part of loop_ms, no part of launches
+    const int cenv = pivot_compact_env();
+    if (cenv != 0 && pivot_compact_ok(t->ld, t->Rcap, d) && t->C - t->R >= 1
+        && (cenv == 1 || pivot_budget(o, false) >= (long long)COMPACT_MIN_SWEEPS * d) && compact_buffers(t)) {
+        int32_t* ci = (int32_t*)t->cslab;
+        io.full = t->T; io.ld = t->ld; io.R = t->R; io.C = t->C;
+        io.comp = t->fT; io.cld = (t->C - t->R + 1 + 15) / 16 * 16;
+        io.basis = t->basis; io.slotvar = ci; io.vmap = ci + t->ld;
+        int32_t* pslot = io.vmap + t->Ccap; int32_t* qring = pslot + 128; int32_t* caux = qring + 2 * pivot_defer_max();
+        int32_t* cshape = caux + 2; io.flag = cshape + 2;
+        const double t0 = now_ms();
+        int32_t bad = 0;
+        LPX_HIP_TRY(hipMemsetAsync(io.flag, 0, sizeof(int32_t), t->stream));
+        LPX_HIP_TRY(launch_compact_entry(io, cshape, caux, t->stream));
+        LPX_HIP_TRY(hipMemcpyAsync(&bad, io.flag, sizeof(bad), hipMemcpyDeviceToHost, t->stream));
+        LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+        pass_ms += now_ms() - t0;
+        if (!bad) {                                  // else: the full path, silently (the handle's tableau has not been touched)
+            f.P.T = t->fT; f.T1 = t->T; f.P.ld = io.cld; f.P.C = t->C - t->R + 1; f.P.shape = cshape;
+            f.compact = 1; f.ld_full = t->ld;
+            f.slotvar = io.slotvar; f.pslot = pslot; f.qring = qring; f.caux = caux;
+            t->last_compact = true;
+        }
+    }
     LoopCtx c; DevState init;
     make_ctx(t, p, c, init);
     c.key.assign(reinterpret_cast<const char*>(&f), sizeof(f));
@@ -468,6 +517,16 @@ static int run_fused(lpx_tableau* t, const SelParams& p, const lpx_run_opts* o, 
     LPX_HIP_TRY(hipMemcpy(recs, t->frec, sizeof(recs), hipMemcpyDeviceToHost));
     const DevState& last = recs[1].pad[2] > recs[0].pad[2] ? recs[1] : recs[0];
     const int buf = last.pad[3] & 1, npend = (last.pad[3] >> 1) & 31, slot0 = last.pad[3] >> 8;
+    if (f.compact) {
+        // buffer 0 is the second buffer: its result expands straight into the handle's tableau; a result in the handle's own
+        // memory expands into the second buffer and comes home by the copy below
+        const double t0 = now_ms();
+        io.full = buf ? t->fT : t->T;
+        LPX_HIP_TRY(launch_compact_exit(f, io, buf ? t->T : t->fT, npend, slot0, t->stream));
+        if (buf) LPX_HIP_TRY(hipMemcpyAsync(t->T, t->fT, sizeof(double) * (size_t)t->R * t->ld, hipMemcpyDeviceToDevice, t->stream));
+        LPX_HIP_TRY(hipStreamSynchronize(t->stream));
+        pass_ms += now_ms() - t0;
+    } else
     if (npend > 0) {
         LPX_HIP_TRY(launch_pivot_flush(f, buf, npend, slot0, t->stream));
         LPX_HIP_TRY(hipStreamSynchronize(t->stream));
@@ -476,6 +535,7 @@ static int run_fused(lpx_tableau* t, const SelParams& p, const lpx_run_opts* o, 
         LPX_HIP_TRY(hipMemcpyAsync(t->T, t->fT, sizeof(double) * (size_t)t->R * t->ld, hipMemcpyDeviceToDevice, t->stream));
         LPX_HIP_TRY(hipStreamSynchronize(t->stream));
     }
+    if (stats) stats->loop_ms += pass_ms;            // a refused entry pass has cost its time too
     return rc;
 }
 
@@ -484,11 +544,14 @@ static int run_fused(lpx_tableau* t, const SelParams& p, const lpx_run_opts* o, 
 
 extern "C" {
 
+int lpx_tableau_last_run_compact(const lpx_tableau* t) { return t && t->last_compact ? 1 : 0; }
+
 int lpx_primal_run(lpx_tableau* t, const lpx_run_opts* o, lpx_pivot_cb cb, void* user, lpx_stats* st)
 {
     if (!t) { set_error("lpx_primal_run: null tableau"); return LPX_EINVAL; }
     lpx_run_opts d; if (!o) { lpx_default_opts(&d, 0); o = &d; }
     if (t->R < 2) { set_error("lpx_primal_run: tableau needs at least one constraint row"); return LPX_EINVAL; }
+    t->last_compact = false;
     // Tableau small enough to live on chip: persistent workgroups, no per-pivot HBM traffic (lpx_resident.hip).
     static const bool res_env = [] { const char* e = std::getenv("LPX_RESIDENT"); return !(e && e[0] == '0'); }();
     int resume = 0;
