@@ -64,6 +64,7 @@ class Compact:
         self.trace = []
         self.unb = None                                                            # (slot, factor column) of a pivot not taken
         self.events = []                                                           # what the tests assert on
+        self.sweeps = 0                                                            # sweep launches (the exit pass is none)
         self.qn = self._entering(self.T[self.m, :self.S], list(self.slotvar[:self.S]))
 
     def _entering(self, u, variables):
@@ -93,6 +94,7 @@ class Compact:
         sweeps = L > 0 and L % d == 0
         n = len(self.pend)
         assert n == (d if sweeps else L % d)
+        self.sweeps += int(sweeps)                                # every way out of a sweep launch sweeps
         if len(self.trace) >= max_iter:
             status = ITER_LIMIT
         elif self.qn < 0:
@@ -234,11 +236,17 @@ def _bad(kind):
     return T, basis
 
 
-MAIN_M, MAIN_N, MAIN_SEED = 60, 60, 21              # 66 pivots; re-entries before and across a sweep at d = 3, 12, 16
+MAIN_M, MAIN_N, MAIN_SEED = 60, 60, 21              # 66 pivots; re-entries before and across a sweep at d = 3, 4, 8, 12, 16
 TIES_M, TIES_N, TIES_SEED, TIES_PAIRS = 30, 40, 3, 6  # 39 pivots; slots 5 and 37 tie at pivot 25, the lower variable in slot 37
 TALL_SEED = 3
 EDGES = {"edge256": (40, 255, 45), "edge272": (20, 259, 8), "edge100": (50, 99, 9)}      # (m, n, seed): 26, 26 and 39 pivots
+# row edges of the _cm launches: (m, n, seed), the oracle's pivot count, and R = m + 1 as (modulus, residue).  A strip wave walks
+# two blocks of 8 rows (R % 16 == 0: both full, 1: one row into the next strip, 8: the second block empty); the column launch
+# gives one row to each lane of a workgroup of 256 (one full workgroup; one row into the second)
+ROW_EDGES = {"rows64": ((63, 60, 2), 51, (16, 0)), "rows65": ((64, 60, 3), 48, (16, 1)), "rows72": ((71, 60, 2), 54, (16, 8)),
+             "rows256": ((255, 40, 1), 70, (256, 0)), "rows257": ((256, 40, 3), 75, (256, 1))}
 MAIN, TIES, TALL = "main", "ties", "tall"
+ROW_EDGE_CAP = 17                                   # one sweep and 5 pivots pending at d = 12, five sweeps and 2 pending at d = 3
 LPS = {
     MAIN: lambda: synth.primal_tableau_from(*synth.dense_lp(MAIN_M, MAIN_N, seed=MAIN_SEED)),
     TIES: lambda: _dup_lp(TIES_M, TIES_N, TIES_SEED, TIES_PAIRS),
@@ -250,6 +258,8 @@ LPS = {
     "bad-ulp": lambda: _bad("bad-ulp"),
     "bad-basis": lambda: _bad("bad-basis"),
 }
+LPS.update({name: (lambda m=m, n=n, seed=seed: synth.primal_tableau_from(*synth.dense_lp(m, n, seed=seed)))
+            for name, ((m, n, seed), _, _) in ROW_EDGES.items()})
 
 
 @functools.lru_cache(maxsize=None)
@@ -290,6 +300,22 @@ def ending_caps(d, npiv):
     return caps
 
 
+def nothing_pending_caps(d, npiv):
+    """Caps d, 2d and 3d end a run of depth d in a sweep launch with nothing pending, after 1, 2 and 3 sweeps: the exit pass meets
+    the result once in each buffer of the pair.  d + 1 and 2d - 1 leave 1 and d - 1 pivots pending after ONE sweep (ending_caps has
+    them after two)."""
+    caps = [d, 2 * d, 3 * d, d + 1, 2 * d - 1]
+    assert npiv > max(caps)
+    return caps
+
+
+def ended(name, d, cap=10000):
+    """(pivots, sweep launches, pivots pending at the end, the newest of them chosen by a sweep launch) of the model's run."""
+    T, basis = lp(name)
+    M = compact_run(T, basis, d, cap)
+    return len(M[1]), M[4].sweeps, M[4].ended_pending, M[4].ended_on_sweep_pivot
+
+
 def reversed_tie_steps(oracle, name, d=3):
     T, basis = lp(name)
     return [e for e in compact_run(T, basis, d)[4].events if e[0] == "reversed-tie"]
@@ -316,7 +342,7 @@ def _against_oracle(oracle, name, d, cap=10000):
     return got[4]
 
 
-@pytest.mark.parametrize("d", [3, 12, 16])
+@pytest.mark.parametrize("d", [3, 4, 8, 12, 16])
 def test_endings_vs_oracle(oracle, d):
     """Runs that end with 1, 0 and d - 1 pivots pending, with the newest pending pivot selected by a sweep launch, and at the
     optimum; the trace holds re-entries inside the window before and across a sweep."""
@@ -332,7 +358,50 @@ def test_endings_vs_oracle(oracle, d):
     assert any(e[0] == "reentry-pending" for e in M.events)
 
 
-@pytest.mark.parametrize("d", [3, 12, 16])
+def test_main_and_its_caps():
+    """What the cases at d = 4 and 8 rest on."""
+    assert ending_caps(4, 66) == [1, 8, 9, 11] and ending_caps(8, 66) == [1, 16, 17, 23]
+
+
+@pytest.mark.parametrize("d", [3, 8, 16])
+def test_nothing_pending_in_either_buffer_vs_oracle(oracle, d):
+    """Caps d, 2d, 3d: the cap is met by a sweep launch, nothing is pending, and the sweep counts 1, 2, 3 put the result in one
+    buffer and in the other.  Caps d + 1 and 2d - 1: 1 (chosen by the sweep launch) and d - 1 pending after one sweep."""
+    npiv = len(oracle_trace(oracle, MAIN))
+    assert npiv == 66
+    ends = []
+    for cap in nothing_pending_caps(d, npiv):
+        M = _against_oracle(oracle, MAIN, d, cap)
+        assert len(M.trace) == cap
+        ends.append((M.sweeps, M.ended_pending, M.ended_on_sweep_pivot))
+    assert ends == [(1, 0, False), (2, 0, False), (3, 0, False), (1, 1, True), (1, d - 1, False)], ends
+    assert ends[0][0] % 2 != ends[1][0] % 2
+
+
+@pytest.mark.parametrize("name", sorted(ROW_EDGES))
+def test_row_edge_lps_vs_oracle(oracle, name):
+    """The LPs of the GPU file's row-edge cases at d = 12 (and the 257-row one at d = 3): to the end and to ROW_EDGE_CAP, which
+    leaves pivots pending after at least one sweep."""
+    (m, n, seed), pivots, (mod, res) = ROW_EDGES[name]
+    T, _ = lp(name)
+    assert T.shape == (m + 1, m + n + 1) and T.shape[0] % mod == res
+    assert len(oracle_trace(oracle, name)) == pivots
+    for d in (12, 3) if name == "rows257" else (12,):
+        M = _against_oracle(oracle, name, d)
+        assert M.sweeps == pivots // d
+        M = _against_oracle(oracle, name, d, ROW_EDGE_CAP)
+        assert M.sweeps >= 1 and M.ended_pending == ROW_EDGE_CAP % d > 0
+
+
+def test_tall_sweep_counts_tell_the_depths_apart(oracle):
+    """The GPU file reads the default depth of a handle off the number of sweep launches of TALL's run: 12 and 16 differ."""
+    p12, s12, _, _ = ended(TALL, 12)
+    p16, s16, _, _ = ended(TALL, 16)
+    assert p12 == p16 == len(oracle_trace(oracle, TALL)) == 57
+    assert (s12, s16) == (p12 // 12, p16 // 16) == (4, 3)
+
+
+@pytest.mark.parametrize("d", [3, 4, 8, 12, 16])
 def test_reversed_ties_vs_oracle(oracle, d):
     """Two slots tie on bits for the minimum while their slot order is the reverse of their variable order; the slot order got
     reversed because a variable came back into a leaving variable's slot."""

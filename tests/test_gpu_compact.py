@@ -29,7 +29,10 @@ TESTS = os.path.join(ROOT, "tests")
 STREAMING = {"LPX_UPDATE_POLICY": "2", "LPX_PIVOT_COMPACT": "1"}
 
 # One child runs a list of steps on one handle and prints one record per "run" step (the steps of test_gpu_deferred_matrix.py's
-# child; an LP is one of test_compact_ref.LPS or of the neighbouring files).  A record ends with the form the run took.
+# child; an LP is one of test_compact_ref.LPS or of the neighbouring files).  A record ends with the form the run took.  Two more
+# steps serve tests/test_gpu_compact_edges.py:
+#   ["upload", lp]               a tableau of the handle's live shape over what the last run left (no set_shape), its start kept
+#   ["dual", opts]               dual_run(resident=-1, **opts); the record ends with whether the handle's buffers traded places
 _CHILD = """
     import hashlib, json, sys, ctypes, numpy as np
     sys.path.insert(0, %r)
@@ -40,7 +43,11 @@ _CHILD = """
     lib.lpx_tableau_last_run_compact.argtypes = [ctypes.c_void_p]
     lib.lpx_tableau_last_run_compact.restype = ctypes.c_int
     h = lambda a, dt: hashlib.sha256(np.ascontiguousarray(a, dtype=dt).view(np.uint8)).hexdigest()
-    get = lambda name: CR.lp(name) if name in CR.LPS else _lp(name)
+    def get(name):
+        if name.startswith("dual:"):                # "dual:m:n:seed:n_ge": test_gpu_dual._dual_tableau
+            from test_gpu_dual import _dual_tableau
+            return _dual_tableau(*[int(v) for v in name.split(":")[1:]])
+        return CR.lp(name) if name in CR.LPS else _lp(name)
     out, dt = [], None
     for step in json.loads(sys.argv[1]):
         op = step[0]
@@ -65,6 +72,16 @@ _CHILD = """
             tr = dt.trace()
             out.append([int(status), int(st["pivots"]), int(st["launches"]), int(st["update_launches"]),
                         h(tr, np.int32), h(bg, np.int32), h(Tg, np.float64), int(lib.lpx_tableau_last_run_compact(dt._h))])
+        elif op == "upload":                        # a tableau of the handle's live shape over whatever the last run left
+            dt.upload(*get(step[1]))
+            dt.snapshot()
+        elif op == "dual":                          # dual_run; the record ends with: has the handle's tableau changed buffers
+            at = dt.device_ptr()[0]
+            status, st = dt.dual_run(L.default_opts(True, resident=-1, **step[1]))
+            Tg, bg = dt.download()
+            tr = dt.trace()
+            out.append([int(status), int(st["pivots"]), int(st["launches"]), int(st["update_launches"]),
+                        h(tr, np.int32), h(bg, np.int32), h(Tg, np.float64), int(dt.device_ptr()[0] != at)])
     dt.close()
     print(json.dumps(out))
 """ % TESTS
@@ -117,7 +134,7 @@ def _check(got, want, what, compact=1):
 # ---------------------------------------------------------------------------------------------------------------------------
 # 1. the cases of tests/test_compact_ref.py: depths, endings, re-entries, reversed ties, the tall LP
 # ---------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("d", [3, 12, 16])
+@pytest.mark.parametrize("d", [3, 4, 8, 12, 16])
 def test_endings_and_reentries_vs_oracle(ref, oracle, d):
     """CR.MAIN at depth d to the caps of CR.ending_caps: 0, 1 and d - 1 pivots pending, the newest pending pivot chosen at a sweep
     step, and to the end; its trace holds re-entries inside the window before and across a sweep (asserted)."""
@@ -133,7 +150,7 @@ def test_endings_and_reentries_vs_oracle(ref, oracle, d):
     _check(_child(plan, dict(STREAMING, LPX_PIVOT_DEFER=str(d))), want, d)
 
 
-@pytest.mark.parametrize("d", [3, 16])
+@pytest.mark.parametrize("d", [3, 4, 8, 16])
 def test_reversed_ties_vs_oracle(ref, oracle, d):
     """CR.TIES: duplicated columns whose reduced costs tie on bits while the slot order of the two variables is the reverse of
     their variable order, one of them having reached its slot by way of a leaving variable (asserted on the oracle's trace)."""
