@@ -1369,6 +1369,65 @@ int lpx_packed_fits(int m, int n);
 int lpx_solve_packed(const lpx_packed_models* in, const lpx_run_opts* o /* or NULL */, const lpx_packed_results* out,
                      lpx_stats* st /* or NULL */);
 
+/* ---- packed batches by a dual start: >= rows and negative right-hand sides (csrc/lpx_packed_dual.hip) ---
+ *
+ * lpx_solve_packed_dual(in, flags, o, out, st) is lpx_solve_packed for the models lpx_solve_bounded_dual was built for: count models
+ * of ONE shape whose rows are <= or >= (rel, [count][m] of LPX_LE / LPX_GE; rel_stride m, or 0 = one copy shared by every model;
+ * rel = NULL: every row is <=) and whose shifted right-hand sides may have either sign.  The same arena, the same stream, at most
+ * one copy per input array, ONE launch of count workgroups, one read-back and one wait.  Workgroup i
+ *   1. builds the tableau of model i in LDS: Min negates c; a >= row is negated while it is stored (every coefficient and b_i:
+ *      exact), then b' = b - A l and u' = u - l as in lpx_solve_packed, slack basis; no test of the sign of b';
+ *   2. refuses the model (LPX_EINVAL) for a lower bound that is not finite, an upper bound below its lower bound or NaN, a rel
+ *      entry that is neither LPX_LE nor LPX_GE, and, behind those, for a column whose objective-row entry is below -1e-9 while its
+ *      upper bound is +inf (the precheck of lpx_solve_bounded_dual: no bound flip can make it dual feasible);
+ *   3. makes the dual-feasibility flips of lpx_tableau_dualize(1e-9), j ascending;
+ *   4. runs the dual loop of lpx_bounded_dual_run3(flags) from the slack basis with o's eps, ratio_tol and max_iter;
+ *   5. extracts x, the optimum, the record, the basis, the at-upper flags and the duals from LDS.
+ * flags is 0 or LPX_BDUAL_LONG_STEP; any other bit is LPX_EINVAL ("unknown flag"), LPX_BDUAL_CUTOFF included, as in
+ * lpx_solve_bounded_dual.  The fit rule is lpx_packed_fits(m, n) unchanged.
+ *
+ * status[i]: LPX_OPTIMAL, LPX_INFEASIBLE, LPX_ITER_LIMIT or LPX_EINVAL.  For LPX_INFEASIBLE and LPX_ITER_LIMIT the outputs describe
+ * the tableau as the loop left it.  A refused model has every output zeroed and a record of zeros around its status; the other
+ * models are unaffected.  There is no LPX_E_NEG_RHS here.  Of o the fields eps, ratio_tol and max_iter are read; NULL is
+ * lpx_default_opts(o, 1).  st (or NULL): pivots = the kind-0 and kind-1 pivots of all models, launches = 1, loop_ms the host wall.
+ *
+ * For every i, status, x, value, basis, at_upper and the counts of the record are bit-equal to lpx_solve_bounded_dual(model i,
+ * lower_i, upper_i, flags, ...) (at the iteration limit, where that call returns an error, to the contract above), and do not depend
+ * on count, on i, on the other models or on whether an array is shared.
+ *
+ * The duals are objective-row entries with exact sign changes, in the user's sense and on the user's rows:
+ *   y[i] = T[m, n+i], negated iff exactly one of (row i is >=, the sense is Min) holds:        y_i = d value / d b_i;
+ *   d[j] = T[m, j],   negated iff (the sense is Min) == (column j is flipped):                   d_j = c_j - sum_i y_i A_ij.
+ *
+ * LPX_EINVAL before any device check, the outputs untouched, every message starting "lpx_solve_packed_dual: ": the list of
+ * lpx_solve_packed in its order (rel_stride among the strides: neither 0 nor m), then a shared rel (rel_stride 0)
+ * holding anything but LPX_LE / LPX_GE, then an unknown flag.  A per-model rel is checked by its workgroup.  No device:
+ * LPX_EDEVICE. */
+typedef struct lpx_packed_dual_models {
+    int32_t count, m, n, sense;        /* one shape for all */
+    const double *c, *A, *b;           /* [count][n], [count][m][n] row-major, [count][m] */
+    const double *lower, *upper;       /* [count][n] or NULL (0 / +inf) */
+    int64_t c_stride, A_stride, b_stride, lower_stride, upper_stride;
+                                       /* doubles between models: the packed size, or 0 = ONE shared copy */
+    const int32_t* rel;                /* [count][m] of LPX_LE / LPX_GE, or NULL = every row is <= */
+    int64_t rel_stride;                /* int32 between models: m, or 0 = ONE shared copy */
+} lpx_packed_dual_models;
+typedef struct lpx_packed_dual_record {  /* 48 bytes */
+    int32_t status;        /* LPX_OPTIMAL, LPX_INFEASIBLE, LPX_ITER_LIMIT or LPX_EINVAL */
+    int32_t events;        /* pivots and passes of the loop */
+    int64_t kind0, kind1;  /* pivots whose leaving variable went to zero / to its upper bound */
+    int64_t passes;        /* long-step passes (bound flips inside the ratio test) */
+    int64_t dualize_flips; /* dual-feasibility flips in front of the loop */
+    double  z;             /* T[m, C-1] as the loop left it */
+} lpx_packed_dual_record;
+typedef struct lpx_packed_dual_results { /* caller-allocated; each of the last five may be NULL */
+    int32_t* status;  double* x;  double* value;           /* [count], [count][n], [count] */
+    lpx_packed_dual_record* rec;  int32_t* basis;  uint8_t* at_upper;   /* [count], [count][m], [count][n] */
+    double* y;  double* d;                                 /* [count][m], [count][n] */
+} lpx_packed_dual_results;
+int lpx_solve_packed_dual(const lpx_packed_dual_models* in, int flags, const lpx_run_opts* o /* or NULL */,
+                          const lpx_packed_dual_results* out, lpx_stats* st /* or NULL */);
+
 /* ---- GMI cuts on a handle with bounds, and the cut loop at a bounded root (csrc/lpx_cuts.hip, csrc/lpx_tableau_bounded.cpp,
  * DESIGN.md section 4.23) --------------------------------------------------------------------------------------------------
  * An internal column of a bounded handle stands for x'_j = x_j - lo_j, or for ub_j - (x_j - lo_j) when it is flipped; x'_j >= 0

@@ -174,6 +174,33 @@ namespace Linear_Programming_Solver.Native
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct LpxPackedDualModels     // lpx_packed_dual_models: lpx_packed_models plus the row senses
+    {
+        public int count, m, n, sense;           // rows are <= or >=
+        public double* c, A, b;                  // [count][n], [count][m][n] row-major, [count][m]
+        public double* lower, upper;             // [count][n] or null (0 / +inf)
+        public long c_stride, A_stride, b_stride, lower_stride, upper_stride;   // doubles between models; 0 = one shared copy
+        public int* rel;                         // [count][m] of LPX_LE (0) / LPX_GE (1), or null = every row is <=
+        public long rel_stride;                  // int32 between models: m, or 0 = one shared copy
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct LpxPackedDualRecord            // lpx_packed_dual_record: 48 bytes, one model of lpx_solve_packed_dual
+    {
+        public int status, events;               // LPX_OPTIMAL / LPX_INFEASIBLE / LPX_ITER_LIMIT / LPX_EINVAL; pivots and passes
+        public long kind0, kind1, passes, dualize_flips;
+        public double z;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct LpxPackedDualResults    // lpx_packed_dual_results: caller-allocated; the last five may be null
+    {
+        public int* status; public double* x; public double* value;
+        public LpxPackedDualRecord* rec; public int* basis; public byte* at_upper;
+        public double* y; public double* d;      // [count][m] duals, [count][n] reduced costs, in the user's sense
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public struct LpxGuardRecord                 // lpx_guard_record: 8 bytes
     {
         public int bland_events, first_bland;    // pivots made in Bland mode; event index of the first, -1 = none
@@ -474,6 +501,10 @@ namespace Linear_Programming_Solver.Native
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int lpx_packed_fits(int m, int n);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_solve_packed(ref LpxPackedModels models, IntPtr opts, ref LpxPackedResults results, LpxStats* st);
+        // the same by a dual start: >= rows and negative right-hand sides; flags: 0 or LPX_BDUAL_LONG_STEP (2)
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_packed_dual(ref LpxPackedDualModels models, int flags, IntPtr opts, ref LpxPackedDualResults results,
+                                                       LpxStats* st);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_solve_bnb_bounded8(ref LpxProblem p, double* lower, double* upper, byte* is_int, ref LpxSolveOpts o,
                                                         long max_nodes, int search_flags, int divers, int stall_events, int root_form,

@@ -214,6 +214,23 @@ class PackedResults(C.Structure):
                 ("at_upper", C.POINTER(C.c_uint8))]
 
 
+class PackedDualModels(C.Structure):
+    """lpx_packed_dual_models (include/lpx.h): lpx_packed_models plus rel ([count][m] of LPX_LE / LPX_GE, or NULL) and its stride."""
+    _fields_ = PackedModels._fields_ + [("rel", ip), ("rel_stride", C.c_int64)]
+
+
+class PackedDualRecord(C.Structure):
+    """lpx_packed_dual_record (include/lpx.h): what one model of lpx_solve_packed_dual did."""
+    _fields_ = [("status", C.c_int32), ("events", C.c_int32), ("kind0", C.c_int64), ("kind1", C.c_int64), ("passes", C.c_int64),
+                ("dualize_flips", C.c_int64), ("z", C.c_double)]
+
+
+class PackedDualResults(C.Structure):
+    """lpx_packed_dual_results (include/lpx.h): caller-allocated output arrays; rec, basis, at_upper, y and d may be NULL."""
+    _fields_ = [("status", ip), ("x", dp), ("value", dp), ("rec", C.POINTER(PackedDualRecord)), ("basis", ip),
+                ("at_upper", C.POINTER(C.c_uint8)), ("y", dp), ("d", dp)]
+
+
 class FixList(C.Structure):
     """lpx_fix_list (include/lpx.h): the caller-owned list of the columns a node tightened, as the triples of a bound edit."""
     _fields_ = [("cap", C.c_int32), ("n", C.c_int32), ("cols", ip), ("lower", dp), ("upper", dp)]
@@ -450,6 +467,8 @@ def lib() -> C.CDLL:
                                           C.POINTER(Result), C.POINTER(BoundedInfo)]
     L.lpx_packed_fits.argtypes = [C.c_int, C.c_int]
     L.lpx_solve_packed.argtypes = [C.POINTER(PackedModels), C.POINTER(RunOpts), C.POINTER(PackedResults), C.POINTER(Stats)]
+    L.lpx_solve_packed_dual.argtypes = [C.POINTER(PackedDualModels), C.c_int, C.POINTER(RunOpts), C.POINTER(PackedDualResults),
+                                        C.POINTER(Stats)]
     L.lpx_solve_bnb_bounded8.argtypes = [C.POINTER(Problem), dp, dp, u8p, C.POINTER(SolveOpts), C.c_int64, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.POINTER(Result), C.POINTER(BnbBoundedInfo), C.POINTER(BnbDiversInfo),
                                          C.POINTER(BnbGuardInfo)]

@@ -313,6 +313,49 @@ void CheckPacked(const lpx_packed_models* in, const lpx_run_opts* o, const lpx_p
         throw bad("too large: " + std::to_string(bytes) + " bytes of inputs and outputs, above 1 GiB (split the batch)");
 }
 
+// The argument checks of lpx_solve_packed_dual: CheckPacked's list in its order (rel_stride among the strides), then a shared rel
+// (m reads; a per-model rel is checked by its workgroup), then the flags.
+void CheckPackedDual(const lpx_packed_dual_models* in, int flags, const lpx_run_opts* o, const lpx_packed_dual_results* out)
+{
+    auto bad = [](const std::string& msg) { return LpxException(LPX_EINVAL, "lpx_solve_packed_dual: " + msg); };
+    if (!in || !out) throw bad("null argument");
+    if (!in->c || !in->A || !in->b) throw bad("null c, A or b");
+    if (!out->status || !out->x || !out->value) throw bad("null status, x or value");
+    if (in->count < 1 || in->count > 65536) throw bad("count is outside [1, 65536]");
+    if (in->m < 1 || in->n < 1) throw bad("m and n must be at least 1");
+    if (in->sense != LPX_MAX && in->sense != LPX_MIN) throw bad("sense is neither LPX_MAX nor LPX_MIN");
+    const int64_t m = in->m, n = in->n, count = in->count;
+    const struct { const char* name; int64_t stride, packed; } strides[6] = {
+        {"c_stride", in->c_stride, n}, {"A_stride", in->A_stride, m * n}, {"b_stride", in->b_stride, m},
+        {"lower_stride", in->lower ? in->lower_stride : 0, n}, {"upper_stride", in->upper ? in->upper_stride : 0, n},
+        {"rel_stride", in->rel ? in->rel_stride : 0, m}};
+    for (const auto& s : strides)
+        if (s.stride != 0 && s.stride != s.packed)
+            throw bad(std::string(s.name) + " is neither 0 nor the packed size " + std::to_string(s.packed));
+    const int64_t R = m + 1, C = n + m + 1;
+    if (!lpx_packed_fits(in->m, in->n))
+        throw bad("the " + std::to_string(R) + " x " + std::to_string(C) + " tableau does not fit the on-chip form (lpx_packed_fits)");
+    if (o && o->resident > 0) throw bad("there is no resident form of the bounded loop (resident = 1)");
+    auto models = [&](int64_t stride) { return stride == 0 ? (int64_t)1 : count; };
+    int64_t bytes = 8 * (n * models(in->c_stride) + m * n * models(in->A_stride) + m * models(in->b_stride));
+    if (in->lower) bytes += 8 * n * models(in->lower_stride);
+    if (in->upper) bytes += 8 * n * models(in->upper_stride);
+    if (in->rel) bytes += 4 * m * models(in->rel_stride);
+    bytes += count * (4 + 8 * n + 8);
+    if (out->rec) bytes += count * (int64_t)sizeof(lpx_packed_dual_record);
+    if (out->basis) bytes += count * 4 * m;
+    if (out->at_upper) bytes += count * n;
+    if (out->y) bytes += count * 8 * m;
+    if (out->d) bytes += count * 8 * n;
+    if (bytes > ((int64_t)1 << 30))
+        throw bad("too large: " + std::to_string(bytes) + " bytes of inputs and outputs, above 1 GiB (split the batch)");
+    if (in->rel && in->rel_stride == 0)
+        for (int64_t i = 0; i < m; ++i)
+            if (in->rel[i] != LPX_LE && in->rel[i] != LPX_GE)
+                throw bad("rel[" + std::to_string(i) + "] is neither LPX_LE nor LPX_GE (an = row is passed as its pair of rows)");
+    if (flags & ~LPX_BDUAL_LONG_STEP) throw bad("unknown flag: flags holds a bit other than LPX_BDUAL_LONG_STEP");
+}
+
 SimplexResult SolveBoundedDual(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper, int flags,
                                const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info)
 {

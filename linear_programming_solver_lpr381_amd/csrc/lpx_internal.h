@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 #include <functional>
+#include <mutex>
 #include "../../include/lpx.h"
 
 namespace lpx {
@@ -183,6 +184,32 @@ struct PackedParams {
 };
 // lpx_solve_packed behind its argument checks: the arena, the copies, the one launch, the one wait
 int packed_solve(const lpx_packed_models* in, const lpx_run_opts* o, const lpx_packed_results* out, lpx_stats* st);
+// the host side of a packed call, shared by lpx_packed.hip and lpx_packed_dual.hip: one arena on the device, one pinned block for
+// the results, one stream, all under one mutex.  Never destroyed, as the handle cache: the HIP runtime may be gone by the time
+// statics are torn down.
+struct PackedArena {
+    std::mutex mu;
+    char* dev = nullptr; size_t dev_bytes = 0;
+    char* pin = nullptr; size_t pin_bytes = 0;          // the results of a call come back in ONE copy and are handed out from here
+    hipStream_t stream = nullptr;
+    bool attr = false;                                  // the function attribute of lpx_packed_primal_onchip is set
+    bool attr_dual = false;                             // ... of lpx_packed_dual_onchip
+};
+extern PackedArena g_packed;                            // defined in lpx_packed.hip
+// the packed batch by a dual start (lpx_packed_dual.hip): PackedParams plus rel (int32 [m] per model; a stride in int32, 0 = shared;
+// null = every row <=), the long-step switch and the duals
+struct PackedDualParams {
+    const double *c, *A, *b, *lower, *upper;
+    const int32_t* rel;
+    int64_t c_stride, A_stride, b_stride, lower_stride, upper_stride, rel_stride;
+    int32_t m, n, min, max_iter, long_step, pad;
+    double eps, ratio_tol;
+    int32_t* status; double* x; double* value; lpx_packed_dual_record* rec; int32_t* basis; uint8_t* at_upper;   // as lpx_packed_dual_results
+    double* y; double* d;                               // [count][m], [count][n]
+    uint8_t* flip; int64_t flip_stride;                 // work bytes, [count][flip_stride], flip_stride >= n + m
+};
+// lpx_solve_packed_dual behind its argument checks: the same arena, the copies, the one launch, the one wait
+int packed_dual_solve(const lpx_packed_dual_models* in, int flags, const lpx_run_opts* o, const lpx_packed_dual_results* out, lpx_stats* st);
 
 // ---- lpx_kernels.hip: the two-launch select and update paths
 hipError_t launch_select(const SelParams& p, hipStream_t s);       // gather-based (dual path)

@@ -380,6 +380,15 @@ int lpx_solve_packed(const lpx_packed_models* in, const lpx_run_opts* o, const l
     return packed_solve(in, o, out, st);
 }
 
+int lpx_solve_packed_dual(const lpx_packed_dual_models* in, int flags, const lpx_run_opts* o, const lpx_packed_dual_results* out,
+                          lpx_stats* st)
+{
+    try { CheckPackedDual(in, flags, o, out); }
+    catch (const LpxException& ex) { set_error(ex.what()); return ex.code; }
+    lpx_run_opts d; if (!o) { lpx_default_opts(&d, 1); o = &d; }
+    return packed_dual_solve(in, flags, o, out, st);
+}
+
 void lpx_bounded_info_free(lpx_bounded_info* info)
 {
     if (!info) return;

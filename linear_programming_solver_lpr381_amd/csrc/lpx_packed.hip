@@ -256,17 +256,11 @@ __global__ __launch_bounds__(OC_NT) void lpx_packed_primal_onchip(PackedParams N
     }
 }
 
-// ---- the host side of a call: one arena on the device, one pinned block for the results, one stream -----------------------------
-namespace {
-
-struct PackedArena {
-    std::mutex mu;
-    char* dev = nullptr; size_t dev_bytes = 0;
-    char* pin = nullptr; size_t pin_bytes = 0;          // the results of a call come back in ONE copy and are handed out from here
-    hipStream_t stream = nullptr;
-    bool attr = false;
-};
+// ---- the host side of a call: one arena on the device, one pinned block for the results, one stream (PackedArena, lpx_internal.h:
+// lpx_packed_dual.hip uses the same one) ---------------------------------------------------------------------------------------
 PackedArena g_packed;       // never destroyed, as the handle cache: the HIP runtime may be gone by the time statics are torn down
+
+namespace {
 
 size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 

@@ -89,6 +89,15 @@ class PackedResult:         # lpx_packed_results (include/lpx.h): LPSolver.Solve
 
 
 @dataclass
+class PackedDualResult(PackedResult):   # lpx_packed_dual_results (include/lpx.h): LPSolver.SolvePackedDual
+    # Status: OPTIMAL, INFEASIBLE, ITER_LIMIT or LPX_EINVAL of that model alone; BoundCounts (B, 3): kind-0 pivots, kind-1 pivots, passes
+    Duals: Optional[np.ndarray] = None          # (B, m) y_i = d value / d b_i, the user's sense and rows       (want "y")
+    ReducedCosts: Optional[np.ndarray] = None   # (B, n) d_j = c_j - sum_i y_i A_ij                              (want "d")
+    Passes: Optional[np.ndarray] = None         # (B,) long-step passes                                          (want "rec")
+    DualizeFlips: Optional[np.ndarray] = None   # (B,) dual-feasibility flips in front of the loop               (want "rec")
+
+
+@dataclass
 class RangingReport:        # lpx_ranging (include/lpx.h): ranges of the solved model in user terms
     valid: bool
     cost_lo: np.ndarray
@@ -217,6 +226,58 @@ def _take_result(r, n: int) -> "SimplexResult":
 # lpx_bnb_node_log as a NumPy record
 BNB_LOG_DTYPE = np.dtype([("depth", "<i4"), ("K", "<i4"), ("status", "<i4"), ("events", "<i4"), ("flips", "<i4"),
                           ("var", "<i4"), ("z", "<f8")])
+
+
+def _packed_inputs(c, A, b, upper, lower, sense, rel=None):
+    """The arguments SolvePacked and SolvePackedDual share, checked: (sense, c, A, b, {"upper", "lower"}, rel, B, m, n).  An array
+    without the batch axis is shared; B comes from whichever argument has the batch axis (none: B = 1).  rel (SolvePackedDual
+    only): (m,) or (B, m) of 0 / 1 or "<=" / ">=", returned as int32."""
+    if isinstance(sense, str):
+        if sense.lower() not in ("max", "min"):
+            raise ValueError(f"unknown sense {sense!r}")
+        sense = 1 if sense.lower() == "min" else 0
+
+    def _f64(v):
+        return np.ascontiguousarray(np.asarray(v, dtype=np.float64))
+    c, A, b = _f64(c), _f64(A), _f64(b)
+    if c.ndim not in (1, 2) or A.ndim not in (2, 3) or b.ndim not in (1, 2):
+        raise ValueError("c is (B, n) or (n,), A is (B, m, n) or (m, n), b is (B, m) or (m,)")
+    m, n = A.shape[-2], A.shape[-1]
+    if c.shape[-1] != n or b.shape[-1] != m:
+        raise ValueError(f"A is {m} x {n}, but c has {c.shape[-1]} entries and b has {b.shape[-1]}")
+    batched = [("c", c, 2), ("A", A, 3), ("b", b, 2)]
+    bounds = {}
+    for name, v in (("upper", upper), ("lower", lower)):
+        if v is None:
+            bounds[name] = None
+            continue
+        if np.ndim(v) == 0:
+            v = np.full(n, float(v))                # one shared row, not one per model
+        v = _f64(v)
+        if v.ndim not in (1, 2) or v.shape[-1] != n:
+            raise ValueError(f"{name} is (B, n), (n,) or a scalar with n = {n}")
+        bounds[name] = v
+        batched.append((name, v, 2))
+    if rel is not None:
+        rel = np.asarray(rel)
+        if rel.dtype.kind in "US":
+            known = np.isin(rel, ("<=", ">="))
+            if not known.all():
+                raise ValueError(f"rel holds {rel[~known].flat[0]!r}: a row is '<=' or '>=' (an = row is passed as its pair)")
+            rel = rel == ">="
+        elif rel.dtype.kind not in "biu":
+            raise ValueError("rel holds integers (0 = <=, 1 = >=) or the strings '<=' / '>='")
+        rel = np.ascontiguousarray(rel, dtype=np.int32)
+        if rel.ndim not in (1, 2) or rel.shape[-1] != m:
+            raise ValueError(f"rel is (B, m) or (m,) with m = {m}")
+        batched.append(("rel", rel, 2))
+    sizes = {name: v.shape[0] for name, v, nd in batched if v.ndim == nd}
+    if len(set(sizes.values())) > 1:
+        raise ValueError(f"the batch axes disagree: {sizes}")
+    B = next(iter(sizes.values())) if sizes else 1
+    if B < 1:
+        raise ValueError("an empty batch")
+    return sense, c, A, b, bounds, rel, B, m, n
 
 
 class LPSolver:             # Models/LPSolver.cs:6-77
@@ -362,42 +423,11 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         are a ValueError.  sense: "max" | "min".  Every model gets its own Status: one that is refused (LPX_EINVAL for its bounds,
         LPX_E_NEG_RHS) or reaches the iteration limit does not fail the call.  Each entry is bit-equal to
         SolveBounded(model, upper, lower, form="onchip").  want: which of the optional outputs to fetch."""
-        if isinstance(sense, str):
-            if sense.lower() not in ("max", "min"):
-                raise ValueError(f"unknown sense {sense!r}")
-            sense = 1 if sense.lower() == "min" else 0
         want = tuple(want)
         for w in want:
             if w not in ("rec", "basis", "at_upper"):
                 raise ValueError(f"unknown output {w!r}")
-
-        def _f64(v):
-            return np.ascontiguousarray(np.asarray(v, dtype=np.float64))
-        c, A, b = _f64(c), _f64(A), _f64(b)
-        if c.ndim not in (1, 2) or A.ndim not in (2, 3) or b.ndim not in (1, 2):
-            raise ValueError("c is (B, n) or (n,), A is (B, m, n) or (m, n), b is (B, m) or (m,)")
-        m, n = A.shape[-2], A.shape[-1]
-        if c.shape[-1] != n or b.shape[-1] != m:
-            raise ValueError(f"A is {m} x {n}, but c has {c.shape[-1]} entries and b has {b.shape[-1]}")
-        batched = [("c", c, 2), ("A", A, 3), ("b", b, 2)]
-        bounds = {}
-        for name, v in (("upper", upper), ("lower", lower)):
-            if v is None:
-                bounds[name] = None
-                continue
-            if np.ndim(v) == 0:
-                v = np.full(n, float(v))                # one shared row, not one per model
-            v = _f64(v)
-            if v.ndim not in (1, 2) or v.shape[-1] != n:
-                raise ValueError(f"{name} is (B, n), (n,) or a scalar with n = {n}")
-            bounds[name] = v
-            batched.append((name, v, 2))
-        sizes = {name: v.shape[0] for name, v, nd in batched if v.ndim == nd}
-        if len(set(sizes.values())) > 1:
-            raise ValueError(f"the batch axes disagree: {sizes}")
-        B = next(iter(sizes.values())) if sizes else 1
-        if B < 1:
-            raise ValueError("an empty batch")
+        sense, c, A, b, bounds, _, B, m, n = _packed_inputs(c, A, b, upper, lower, sense)
 
         def _stride(v, nd, packed):
             return packed if v.ndim == nd else 0
@@ -435,6 +465,72 @@ class LPSolver:             # Models/LPSolver.cs:6-77
                                                     ("flips", "<i8"), ("z", "<f8")]))
             res.Events = r["events"].copy()
             res.BoundCounts = np.stack([r["kind0"], r["kind1"], r["flips"]], axis=1)
+            res.Z = r["z"].copy()
+        return res
+
+    def SolvePackedDual(self, c, A, b, rel=None, upper=None, lower=None, sense="max", long_step: bool = True, max_iter=None,
+                        want=("rec", "basis", "at_upper", "y", "d")) -> PackedDualResult:
+        """SolvePacked by a dual start (lpx_solve_packed_dual): B models of ONE shape whose rows are <= or >= and whose right-hand
+        sides may have either sign, in ONE kernel launch -- covering models, Min c.x, A x >= b, right-hand-side sweeps across zero.
+        The arrays are SolvePacked's; rel: None (every row <=), (m,) shared by every model or (B, m), of 0 / 1 (LPX_LE / LPX_GE)
+        or the strings "<=" / ">=".  Every variable that improves the objective needs a finite upper bound.  long_step: the
+        bound-flipping ratio test (LPX_BDUAL_LONG_STEP).  Every model gets its own Status: OPTIMAL, INFEASIBLE, ITER_LIMIT, or
+        LPX_EINVAL for its bounds, a bad entry of its own rel row, or an improving variable without an upper bound.  Each entry is
+        bit-equal to SolveBoundedDual(model, upper, lower, long_step).  Duals y_i = d value / d b_i and ReducedCosts
+        d_j = c_j - sum_i y_i A_ij are in the user's sense and on the user's rows.  want: which optional outputs to fetch."""
+        want = tuple(want)
+        for w in want:
+            if w not in ("rec", "basis", "at_upper", "y", "d"):
+                raise ValueError(f"unknown output {w!r}")
+        sense, c, A, b, bounds, rel, B, m, n = _packed_inputs(c, A, b, upper, lower, sense, rel)
+
+        def _stride(v, nd, packed):
+            return packed if v.ndim == nd else 0
+        pm = _lib.PackedDualModels()
+        pm.count, pm.m, pm.n, pm.sense = B, m, n, int(sense)
+        pm.c, pm.A, pm.b = (v.ctypes.data_as(_lib.dp) for v in (c, A, b))
+        pm.c_stride, pm.A_stride, pm.b_stride = _stride(c, 2, n), _stride(A, 3, m * n), _stride(b, 2, m)
+        for name in ("upper", "lower"):
+            v = bounds[name]
+            if v is not None:
+                setattr(pm, name, v.ctypes.data_as(_lib.dp))
+                setattr(pm, name + "_stride", _stride(v, 2, n))
+        if rel is not None:
+            pm.rel, pm.rel_stride = rel.ctypes.data_as(_lib.ip), _stride(rel, 2, m)
+        status = np.zeros(B, dtype=np.int32); x = np.zeros((B, n)); value = np.zeros(B)
+        pr = _lib.PackedDualResults()
+        pr.status, pr.x, pr.value = status.ctypes.data_as(_lib.ip), x.ctypes.data_as(_lib.dp), value.ctypes.data_as(_lib.dp)
+        recs = basis = at = y = d = None
+        if "rec" in want:
+            recs = (_lib.PackedDualRecord * B)()
+            pr.rec = recs
+        if "basis" in want:
+            basis = np.zeros((B, m), dtype=np.int32)
+            pr.basis = basis.ctypes.data_as(_lib.ip)
+        if "at_upper" in want:
+            at = np.zeros((B, n), dtype=np.uint8)
+            pr.at_upper = at.ctypes.data_as(C.POINTER(C.c_uint8))
+        if "y" in want:
+            y = np.zeros((B, m))
+            pr.y = y.ctypes.data_as(_lib.dp)
+        if "d" in want:
+            d = np.zeros((B, n))
+            pr.d = d.ctypes.data_as(_lib.dp)
+        limit = max_iter if max_iter is not None else self.engine.get("max_iter")
+        o = _lib.default_opts(True) if limit is None else _lib.default_opts(True, max_iter=int(limit))
+        st = _lib.Stats()
+        rc = lib().lpx_solve_packed_dual(C.byref(pm), _lib.BDUAL_LONG_STEP if long_step else 0, C.byref(o), C.byref(pr), C.byref(st))
+        if rc != 0:
+            raise SolverException(rc, _lib.last_error())
+        res = PackedDualResult(Status=status, Solution=x, OptimalValue=value, Basis=basis, AtUpper=at, Stats=st.as_dict(),
+                               Duals=y, ReducedCosts=d)
+        if recs is not None:
+            r = np.frombuffer(recs, dtype=np.dtype([("status", "<i4"), ("events", "<i4"), ("kind0", "<i8"), ("kind1", "<i8"),
+                                                    ("passes", "<i8"), ("dualize_flips", "<i8"), ("z", "<f8")]))
+            res.Events = r["events"].copy()
+            res.BoundCounts = np.stack([r["kind0"], r["kind1"], r["passes"]], axis=1)
+            res.Passes = r["passes"].copy()
+            res.DualizeFlips = r["dualize_flips"].copy()
             res.Z = r["z"].copy()
         return res
 

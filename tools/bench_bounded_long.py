@@ -13,11 +13,21 @@ finished):
       per checkout with `--root DIR` (the tree whose package is imported; default: this one) to compare two commits on one box.
 Prints one JSON line.
 
+`--compare-packed` measures the packed call by a dual start (lpx_solve_packed_dual) instead of the legs: host
+wall of whole calls, REPS (default 15) timed rounds behind one warm-up round, the sides alternating in one process; a side wins iff
+its median lies below the other's minimum.  256 covering models covering(12, 60, seed) as Min c.x, A x >= b:
+SolvePackedDual with and without the long step against 256 SolveBoundedDual calls (statuses, optima and counts asserted equal);
+then 4096 right-hand sides of ONE shared model (stride 0 for c, A and rel), long step on against off.  With `--parent-lib
+PATH/liblpx.so` (the library of the parent commit) the existing packed primal call, lpx_solve_packed, is measured on both libraries
+in the same process, alternating, with the bits of their outputs asserted equal.  `--packed-trace` makes four packed dual calls
+and nothing else, for a run of its own under `rocprofv3 --kernel-trace --stats`.
+
 `--trace-only` runs leg (a) on the smaller model once per side (no untimed run in front), for a separate run under
 `rocprofv3 --kernel-trace --stats -- python tools/bench_bounded_long.py --trace-only`, whose kernel table gives the mean launch
 time of lpx_bounded_long_select, lpx_bounded_dual_select and the lpx_update launches they feed.
 
-usage: bench_bounded_long.py [--leg a|b|c]... [--root DIR] [--big-reps N] [--skip-big] [--trace-only] [REPS]"""
+usage: bench_bounded_long.py [--leg a|b|c]... [--root DIR] [--big-reps N] [--skip-big] [--trace-only]
+                             [--compare-packed [--parent-lib PATH] | --packed-trace] [REPS]"""
 import json
 import os
 import statistics
@@ -27,7 +37,8 @@ import time
 
 def _args():
     a = sys.argv[1:]
-    opt = {"legs": [], "root": None, "big_reps": 2, "skip_big": False, "trace_only": False, "reps": 7}
+    opt = {"legs": [], "root": None, "big_reps": 2, "skip_big": False, "trace_only": False, "reps": None, "compare_packed": False,
+           "packed_trace": False, "parent_lib": None}
     i = 0
     while i < len(a):
         if a[i] == "--leg":
@@ -40,10 +51,18 @@ def _args():
             opt["skip_big"] = True; i += 1
         elif a[i] == "--trace-only":
             opt["trace_only"] = True; i += 1
+        elif a[i] == "--compare-packed":
+            opt["compare_packed"] = True; i += 1
+        elif a[i] == "--packed-trace":
+            opt["packed_trace"] = True; i += 1
+        elif a[i] == "--parent-lib":
+            opt["parent_lib"] = a[i + 1]; i += 2
         else:
             opt["reps"] = int(a[i]); i += 1
     if not opt["legs"]:
         opt["legs"] = ["a", "b", "c"]
+    if opt["reps"] is None:
+        opt["reps"] = 15 if opt["compare_packed"] else 7
     return opt
 
 
@@ -158,9 +177,129 @@ def leg_c(reps):
     return {"root": ROOT, "binary_ip_60x12_skip_fixed_only": info}
 
 
+def verdict(a, b, na, nb):
+    """The rule of DESIGN section 4.17: a side wins iff its median lies below the other's minimum."""
+    if a["median_ms"] < b["min_ms"]:
+        return na
+    if b["median_ms"] < a["min_ms"]:
+        return nb
+    return "tie"
+
+
+def covering_models(count, m=12, n=60):
+    """covering(m, n, seed) for seeds 1..count as user models: stacked (c, A, b) of Min c.x, A x >= b, 0 <= x <= 1."""
+    cs, As, bs = [], [], []
+    for s in range(1, count + 1):
+        c, A, _ = synth.dense_lp(m, n, s)
+        A = np.abs(A)
+        cs.append(np.abs(c) + 1.0); As.append(A)
+        bs.append(A.sum(axis=1) * np.random.default_rng(s).uniform(0.2, 0.5, size=m))
+    return np.stack(cs), np.stack(As), np.stack(bs)
+
+
+def _timed(f):
+    t0 = time.perf_counter()
+    r = f()
+    return 1e3 * (time.perf_counter() - t0), r
+
+
+def packed_primal_parent(reps, parent_lib):
+    """lpx_solve_packed of this tree's library against the parent commit's, loaded beside it: the same arrays, alternating."""
+    import ctypes as C
+    Lb = L._lib
+    libs = {"tree": Lb.lib(), "parent": C.CDLL(os.path.abspath(parent_lib))}
+    libs["parent"].lpx_solve_packed.argtypes = libs["tree"].lpx_solve_packed.argtypes
+    count, m, n = 256, 12, 60
+    cs, As, bs = [], [], []
+    for s in range(1, count + 1):
+        c, A, rel, b = synth.binary_ip(n, m, s)
+        cs.append(c); As.append(A[:m]); bs.append(b[:m])
+    c, A, b = (np.ascontiguousarray(np.stack(v)) for v in (cs, As, bs))
+    up = np.ones(n)
+    pm = Lb.PackedModels(count, m, n, 0, c.ctypes.data_as(Lb.dp), A.ctypes.data_as(Lb.dp), b.ctypes.data_as(Lb.dp), None,
+                         up.ctypes.data_as(Lb.dp), n, m * n, m, 0, 0)
+    outs, t = {}, {k: [] for k in libs}
+    for k in libs:
+        status = np.zeros(count, dtype=np.int32); x = np.zeros((count, n)); value = np.zeros(count)
+        recs = (Lb.PrimalRecord * count)(); basis = np.zeros((count, m), dtype=np.int32); at = np.zeros((count, n), dtype=np.uint8)
+        pr = Lb.PackedResults(status.ctypes.data_as(Lb.ip), x.ctypes.data_as(Lb.dp), value.ctypes.data_as(Lb.dp), recs,
+                              basis.ctypes.data_as(Lb.ip), at.ctypes.data_as(C.POINTER(C.c_uint8)))
+        outs[k] = (pr, status, x, value, recs, basis, at)
+    for i in range(reps + 1):
+        for k, lib in libs.items():
+            ms, rc = _timed(lambda: lib.lpx_solve_packed(C.byref(pm), None, C.byref(outs[k][0]), None))
+            assert rc == 0, k
+            t[k].append(ms)
+    a, p = outs["tree"], outs["parent"]
+    assert all(a[j].tobytes() == p[j].tobytes() for j in (1, 2, 3, 5, 6)) and bytes(a[4]) == bytes(p[4]), "tree and parent differ"
+    rec = {k: stats(v[1:]) for k, v in t.items()}
+    rec["winner"] = verdict(rec["tree"], rec["parent"], "tree", "parent")
+    rec["equal_bits"] = True
+    return rec
+
+
+def compare_packed(reps, trace, parent_lib):
+    S = L.LPSolver()
+    count = 256
+    c, A, b = covering_models(count)
+    rel = np.ones(12, dtype=np.int32)
+    if trace:                                           # one warm-up call and three calls: one kernel each in the trace
+        for i in range(4):
+            r = S.SolvePackedDual(c, A, b, rel, 1.0, sense="min")
+        return {"packed_trace": {"count": count, "calls": 4, "events": int(r.Events.sum()), "launches_per_call": r.Stats["launches"]}}
+    out = {}
+    ps = [L.LPProblem.from_arrays(1, c[k], A[k], [1] * 12, b[k]) for k in range(count)]
+    sides = {"packed_long": [], "packed_plain": [], "single_long": [], "single_plain": []}
+    for i in range(reps + 1):
+        ms, rp = _timed(lambda: S.SolvePackedDual(c, A, b, rel, 1.0, sense="min"))
+        sides["packed_long"].append(ms)
+        ms, rq = _timed(lambda: S.SolvePackedDual(c, A, b, rel, 1.0, sense="min", long_step=False))
+        sides["packed_plain"].append(ms)
+        ms, rs = _timed(lambda: [S.SolveBoundedDual(p, 1.0) for p in ps])
+        sides["single_long"].append(ms)
+        ms, rt = _timed(lambda: [S.SolveBoundedDual(p, 1.0, long_step=False) for p in ps])
+        sides["single_plain"].append(ms)
+        for packed, singles in ((rp, rs), (rq, rt)):
+            assert all(packed.Status[k] == x.Status and packed.OptimalValue[k] == x.OptimalValue and
+                       tuple(packed.BoundCounts[k].tolist()) == x.BoundCounts for k, x in enumerate(singles)), "packed and single differ"
+    rec = {"count": count, "shape": [13, 73], "events_long": int(rp.Events.sum()), "passes_long": int(rp.Passes.sum()),
+           "events_plain": int(rq.Events.sum()), "loop_ms_last": rp.Stats["loop_ms"],
+           "bytes_in": int(c.nbytes + A.nbytes + b.nbytes + rel.nbytes + 8 * 60)}
+    rec.update({k: stats(v[1:]) for k, v in sides.items()})                     # the first round is the warm-up
+    rec["winner_packed_vs_single_long"] = verdict(rec["packed_long"], rec["single_long"], "packed", "single")
+    rec["winner_packed_vs_single_plain"] = verdict(rec["packed_plain"], rec["single_plain"], "packed", "single")
+    rec["winner_long_vs_plain_packed"] = verdict(rec["packed_long"], rec["packed_plain"], "long_step", "plain")
+    rec["single_over_packed_long"] = rec["single_long"]["median_ms"] / rec["packed_long"]["median_ms"]
+    rec["single_over_packed_plain"] = rec["single_plain"]["median_ms"] / rec["packed_plain"]["median_ms"]
+    out["covering_256_of_13x73"] = rec
+    # one shared model, 4096 right-hand sides: stride 0 for c, A and rel
+    count = 4096
+    bs = b[0] * np.random.default_rng(5).uniform(0.8, 1.2, size=(count, 12))
+    sides = {"long_step": [], "plain": []}
+    for i in range(reps + 1):
+        ms, rl = _timed(lambda: S.SolvePackedDual(c[0], A[0], bs, rel, 1.0, sense="min"))
+        sides["long_step"].append(ms)
+        ms, rn = _timed(lambda: S.SolvePackedDual(c[0], A[0], bs, rel, 1.0, sense="min", long_step=False))
+        sides["plain"].append(ms)
+        assert np.array_equal(rl.Status, rn.Status) and (rl.Status == 0).all()
+        assert np.abs(rl.OptimalValue - rn.OptimalValue).max() <= 1e-9 * np.abs(rn.OptimalValue).max()
+    rec = {"count": count, "shape": [13, 73], "events_long": int(rl.Events.sum()), "passes_long": int(rl.Passes.sum()),
+           "events_plain": int(rn.Events.sum()), "bytes_in": int(c[0].nbytes + A[0].nbytes + bs.nbytes + rel.nbytes + 8 * 60)}
+    rec.update({k: stats(v[1:]) for k, v in sides.items()})
+    rec["winner"] = verdict(rec["long_step"], rec["plain"], "long_step", "plain")
+    rec["us_per_model_long"] = 1e3 * rec["long_step"]["median_ms"] / count
+    out["rhs_4096_shared"] = rec
+    if parent_lib:
+        out["packed_primal_tree_vs_parent"] = packed_primal_parent(reps, parent_lib)
+    return out
+
+
 def main():
     L._lib.check(L._lib.lib().lpx_init(0))
     out = {}
+    if OPT["compare_packed"] or OPT["packed_trace"]:
+        print(json.dumps(compare_packed(OPT["reps"], OPT["packed_trace"], OPT["parent_lib"])))
+        return
     if OPT["trace_only"]:
         out["a"] = leg_a(1, [(256, 768)], warm=0)
     else:

@@ -1,7 +1,7 @@
 // lpx_cli -- Linux stand-in for the reference's WinForms host (Form1.cs), over the C ABI of liblpx.so only.
 //
 //   lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]
-//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S] [--root-form F] [--root-cuts N [--cuts-per-round K]] [--tighten]] [--bounded-form F] [--bounded [--rhs-file F]] [--export FILE] INPUT.txt
+//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S] [--root-form F] [--root-cuts N [--cuts-per-round K]] [--tighten]] [--bounded-form F] [--bounded [--rhs-file F]] [--bounded-dual [--long-step] --rhs-file F] [--export FILE] INPUT.txt
 //
 // Does what Form1 does around the solvers: reads the model text (Import, Form1.cs:284-296), parses it with the LPParser
 // grammar (lpx_parse_text, Models/LPParser.cs:9-79), runs the algorithm chosen by its dropdown name (btnSolve_Click,
@@ -14,7 +14,8 @@
 // previous basis), and each re-solve's summary is printed.  --upper J=V / --lower J=V (bounds of x_J, 1-based, repeatable) and
 // --binary (every u_j = 1) select the bounded-variable primal simplex (lpx_solve_bounded): the bounds cost no rows.  --bounded selects it without any bound.  --bounded --rhs-file F solves the model once per line of F (m numbers, the
 // right-hand sides of that run) as ONE packed call (lpx_solve_packed) with c, A and the bounds shared by every run, and prints one
-// line "status value x1 .. xn" per right-hand side.  There is no CPU fallback: without a gfx950 device the solve fails with LPX_EDEVICE.
+// line "status value x1 .. xn" per right-hand side.  --bounded-dual [--long-step] --rhs-file F does the same by the dual start
+// (lpx_solve_packed_dual): >= rows and negative right-hand sides are accepted, an = row is refused.  There is no CPU fallback: without a gfx950 device the solve fails with LPX_EDEVICE.
 #include <cstdio>
 #include <cstdlib>
 #include <cctype>
@@ -80,6 +81,7 @@ int main(int argc, char** argv)
     bool repaired = false, iterations = false, ranging = false, cut_set = false, algo_set = false, binary = false, bnb_bounded = false;
     bool bounded_flag = false;  // --bounded: the bounded primal simplex even without a bound
     std::string rhs_file;       // --rhs-file F beside --bounded: one packed call (lpx_solve_packed), a right-hand side per line of F
+    bool bounded_dual = false;  // --bounded-dual beside --rhs-file: that packed call by the dual start (lpx_solve_packed_dual)
     int search_flags = 0;       // --long-step / --cutoff beside --bnb-bounded
     int node_form = -1;         // --node-form beside --bnb-bounded: LPX_NODE_*; -1 = not given
     int divers = 0;             // --divers W beside --bnb-bounded: the search by W divers (lpx_solve_bnb_bounded4); 0 = not given
@@ -103,6 +105,7 @@ int main(int argc, char** argv)
         else if (a == "--binary") binary = true;
         else if (a == "--bnb-bounded") bnb_bounded = true;
         else if (a == "--bounded") bounded_flag = true;
+        else if (a == "--bounded-dual") bounded_dual = true;
         else if (a == "--rhs-file" && i + 1 < argc) rhs_file = argv[++i];
         else if (a == "--long-step") search_flags |= LPX_BDUAL_LONG_STEP;
         else if (a == "--cutoff") search_flags |= LPX_BDUAL_CUTOFF;
@@ -200,7 +203,7 @@ int main(int argc, char** argv)
         else if (a == "--help" || a == "-h") {
             std::printf("usage: lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]\n"
                         "               [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S] [--root-form F] [--root-cuts N [--cuts-per-round K]] [--tighten]] [--bounded-form F]\n"
-                        "               [--bounded [--rhs-file F]] [--export FILE] INPUT.txt\n"
+                        "               [--bounded [--rhs-file F]] [--bounded-dual [--long-step] --rhs-file F] [--export FILE] INPUT.txt\n"
                         "  NAME: Primal Simplex | Revised Primal Simplex | Dual Simplex | Branch and Bound |\n"
                         "        Revised Branch and Bound | Branch and Bound Knapsack | Cutting Plane | Revised Cutting Plane |\n"
                         "        GMI Cutting Plane (gmi) | Bounded Primal Simplex\n"
@@ -232,6 +235,8 @@ int main(int argc, char** argv)
                         "  --bounded: the Bounded Primal Simplex even without a bound.  --bounded --rhs-file F: the model once per line of F (m\n"
                         "             numbers: the right-hand sides of that run) as ONE packed call (lpx_solve_packed: one upload, one kernel\n"
                         "             launch, one read-back; c, A and the bounds shared); prints a line \"status value x1 .. xn\" per run\n"
+                        "  --bounded-dual [--long-step] --rhs-file F: the same by the dual start (lpx_solve_packed_dual): >= rows and negative\n"
+                        "             right-hand sides are accepted, an = row is refused; --long-step: the bound-flipping ratio test\n"
                         "  --root-cuts N: with --bnb-bounded --divers, cut-and-branch (lpx_solve_bnb_bounded9): up to N rounds of --cuts-per-round K\n"
                         "             (default 8) GMI cuts at the solved root, then the search from that tableau; not with --plunge or --branching\n"
                         "  --root-form launches|onchip|auto: with --bnb-bounded --divers, how the root LP is solved (lpx_solve_bnb_bounded8);\n"
@@ -250,13 +255,18 @@ int main(int argc, char** argv)
         if (key != "gmi cutting plane" && key != "gmi") { std::fprintf(stderr, "lpx_cli: --cuts-per-round / --cut-rounds need --algorithm \"GMI Cutting Plane\"\n"); return 64; }
         if (ranging) { std::fprintf(stderr, "lpx_cli: --ranging does not combine with --cuts-per-round / --cut-rounds\n"); return 64; }
     }
-    const bool bounded = binary || !bounds.empty() || bounded_flag;
-    if (!rhs_file.empty() && (!bounded_flag || bnb_bounded || bounded_form >= 0 || iterations || !edits.empty() || !exportPath.empty())) {
+    const bool bounded = binary || !bounds.empty() || bounded_flag || bounded_dual;
+    if (bounded_dual && (rhs_file.empty() || bounded_flag || bnb_bounded || bounded_form >= 0 || iterations || !edits.empty() || !exportPath.empty() ||
+                         (search_flags & ~LPX_BDUAL_LONG_STEP))) {
+        std::fprintf(stderr, "lpx_cli: --bounded-dual needs --rhs-file and combines only with --long-step and --upper / --lower / --binary\n");
+        return 64;
+    }
+    if (!bounded_dual && !rhs_file.empty() && (!bounded_flag || bnb_bounded || bounded_form >= 0 || iterations || !edits.empty() || !exportPath.empty())) {
         std::fprintf(stderr, "lpx_cli: --rhs-file needs --bounded and combines only with --upper / --lower / --binary\n");
         return 64;
     }
     if (bnb_bounded && !bounded) { std::fprintf(stderr, "lpx_cli: --bnb-bounded needs --binary or --upper bounds\n"); return 64; }
-    if (search_flags && !bnb_bounded) { std::fprintf(stderr, "lpx_cli: --long-step / --cutoff need --bnb-bounded\n"); return 64; }
+    if (search_flags && !bnb_bounded && !bounded_dual) { std::fprintf(stderr, "lpx_cli: --long-step / --cutoff need --bnb-bounded\n"); return 64; }
     if (node_form >= 0 && !bnb_bounded) { std::fprintf(stderr, "lpx_cli: --node-form needs --bnb-bounded\n"); return 64; }
     if (divers && !bnb_bounded) { std::fprintf(stderr, "lpx_cli: --divers needs --bnb-bounded\n"); return 64; }
     if (plunge && !bnb_bounded) { std::fprintf(stderr, "lpx_cli: --plunge needs --bnb-bounded\n"); return 64; }
@@ -315,8 +325,13 @@ int main(int argc, char** argv)
     }
     if (!rhs_file.empty()) {
         // one packed call: a right-hand side per line, everything else shared at stride 0
-        for (int i = 0; i < p.m; ++i)
-            if (p.rel[i] != LPX_LE) { std::fprintf(stderr, "lpx_cli: --rhs-file: every constraint must be <=\n"); lpx_parsed_free(&p); return 65; }
+        for (int i = 0; i < p.m; ++i) {
+            if (bounded_dual && p.rel[i] == LPX_EQ) {
+                std::fprintf(stderr, "lpx_cli: --bounded-dual --rhs-file: an = constraint is not accepted (pass it as its <= and >= pair)\n");
+                lpx_parsed_free(&p); return 65;
+            }
+            if (!bounded_dual && p.rel[i] != LPX_LE) { std::fprintf(stderr, "lpx_cli: --rhs-file: every constraint must be <=\n"); lpx_parsed_free(&p); return 65; }
+        }
         std::ifstream rf(rhs_file);
         if (!rf) { std::fprintf(stderr, "Error reading file: %s\n", rhs_file.c_str()); lpx_parsed_free(&p); return 66; }
         std::vector<double> rhs;
@@ -333,16 +348,28 @@ int main(int argc, char** argv)
             }
             rhs.insert(rhs.end(), row.begin(), row.end()); ++count;
         }
-        lpx_packed_models pm; std::memset(&pm, 0, sizeof pm);
-        pm.count = count; pm.m = p.m; pm.n = p.n; pm.sense = p.sense;
-        pm.c = p.c; pm.A = p.A; pm.b = rhs.data(); pm.lower = lo.data(); pm.upper = up.data();
-        pm.b_stride = p.m;                              // c, A and the bounds: stride 0, one copy for every run
         std::vector<int32_t> status((size_t)(count > 0 ? count : 1));
         std::vector<double> x((size_t)(count > 0 ? count : 1) * (size_t)(p.n > 0 ? p.n : 1)), value((size_t)(count > 0 ? count : 1));
-        lpx_packed_results pr; std::memset(&pr, 0, sizeof pr);
-        pr.status = status.data(); pr.x = x.data(); pr.value = value.data();
-        lpx_run_opts ro; lpx_default_opts(&ro, 0);
-        const int prc = lpx_solve_packed(&pm, &ro, &pr, nullptr);
+        int prc;
+        if (bounded_dual) {                             // c, A, rel and the bounds: stride 0, one copy for every run
+            lpx_packed_dual_models dm; std::memset(&dm, 0, sizeof dm);
+            dm.count = count; dm.m = p.m; dm.n = p.n; dm.sense = p.sense;
+            dm.c = p.c; dm.A = p.A; dm.b = rhs.data(); dm.lower = lo.data(); dm.upper = up.data(); dm.rel = p.rel;
+            dm.b_stride = p.m;
+            lpx_packed_dual_results dr; std::memset(&dr, 0, sizeof dr);
+            dr.status = status.data(); dr.x = x.data(); dr.value = value.data();
+            lpx_run_opts ro; lpx_default_opts(&ro, 1);
+            prc = lpx_solve_packed_dual(&dm, search_flags & LPX_BDUAL_LONG_STEP, &ro, &dr, nullptr);
+        } else {
+            lpx_packed_models pm; std::memset(&pm, 0, sizeof pm);
+            pm.count = count; pm.m = p.m; pm.n = p.n; pm.sense = p.sense;
+            pm.c = p.c; pm.A = p.A; pm.b = rhs.data(); pm.lower = lo.data(); pm.upper = up.data();
+            pm.b_stride = p.m;                          // c, A and the bounds: stride 0, one copy for every run
+            lpx_packed_results pr; std::memset(&pr, 0, sizeof pr);
+            pr.status = status.data(); pr.x = x.data(); pr.value = value.data();
+            lpx_run_opts ro; lpx_default_opts(&ro, 0);
+            prc = lpx_solve_packed(&pm, &ro, &pr, nullptr);
+        }
         if (prc != 0) { lpx_parsed_free(&p); lpx_last_error(err, sizeof err); std::fprintf(stderr, "%s\n", err); return prc == LPX_EDEVICE ? 69 : 70; }
         for (int i = 0; i < count; ++i) {
             std::printf("%d %.17g", status[i], value[i]);
