@@ -1428,6 +1428,92 @@ typedef struct lpx_packed_dual_results { /* caller-allocated; each of the last f
 int lpx_solve_packed_dual(const lpx_packed_dual_models* in, int flags, const lpx_run_opts* o /* or NULL */,
                           const lpx_packed_dual_results* out, lpx_stats* st /* or NULL */);
 
+/* ---- packed batches of small integer programs: a whole branch and bound per workgroup (csrc/lpx_packed_bnb.hip, DESIGN.md
+ * section 4.27) ---------------------------------------------------------------------------------------------------------------
+ *
+ * lpx_solve_packed_bnb(in, opt, out, st) is lpx_solve_packed for integer programs: count models of ONE shape (m rows, every row <=;
+ * n variables; is_int, [n] bytes shared by every model, or NULL = every variable is integer) as contiguous arrays with the strides
+ * of lpx_solve_packed.  The same arena, the same stream, at most one copy per input array, ONE launch of count workgroups, one
+ * read-back and one wait, whatever count and whatever the number of nodes.  Workgroup i
+ *   a. builds the tableau of model i in LDS and validates it as lpx_solve_packed does (LPX_EINVAL for a bound, LPX_E_NEG_RHS);
+ *      behind the bounds check every integer variable needs a finite upper bound and integral lower and upper bounds, else the
+ *      model is LPX_EINVAL; then the root LP runs in the on-chip bounded primal loop with eps, ratio_tol of lpx_default_opts(o, 0)
+ *      and the call's max_iter.  A root that does not end LPX_OPTIMAL ends the model with the root's status, x and value as
+ *      lpx_solve_packed gives them (stop = LPX_PBNB_ROOT);
+ *   b. runs the search of lpx_solve_bnb_bounded3(..., LPX_NODE_ONCHIP) itself, the same steps in the same order, with the tableau
+ *      never leaving LDS: the limits, the pop of the depth-first stack, the node's bounds from its path over the root bounds
+ *      [0, u'], the columns whose bounds differ from those on the tableau in ascending order, the bound edit, the dual-feasibility
+ *      flips, the dual loop with LPX_BDUAL_SKIP_FIXED | search_flags, ratio_tol of lpx_default_opts(o, 1) and, under
+ *      LPX_BDUAL_CUTOFF, cutoff = best + 1e-6, the pick (tol 1e-6, nint = n, the mask) and the decide step: LPX_INFEASIBLE prunes;
+ *      LPX_CUTOFF or z <= best + 1e-6 prunes by bound; no fractional integer variable is an incumbent (x' as
+ *      lpx_tableau_bounded_solution forms it, integer entries rounded half to even, best = z); otherwise the floor child is pushed,
+ *      then the ceil child, which is explored first;
+ *   c. finishes as lpx_solve_bnb_bounded does: x = the incumbent plus lower when a lower array was given, value = -best for Min,
+ *      plus the constant c.lower where a lower bound was non-zero.
+ * The fit rule is lpx_packed_fits(m, n) unchanged.  What the search keeps outside LDS (the handle's lower shifts and flip bytes,
+ * the bounds, the path, the stack, the incumbent) is a work slice of the arena per model.
+ *
+ * The three budgets are per model and mandatory: max_nodes and max_events at least 1, max_iter (events per node and of the root
+ * loop) at least 0; max_depth is the deepest node a model may hold (0 = n; a binary model never goes deeper than n).
+ *
+ * status[i]: LPX_OPTIMAL (the stack ran empty with an incumbent), LPX_INFEASIBLE (it ran empty without one), LPX_ITER_LIMIT (a
+ * budget stopped the search and rec[i].stop says which; x and value are the incumbent so far, or zeros while incumbents == 0), the
+ * root's LPX_UNBOUNDED / LPX_ITER_LIMIT, LPX_EINVAL / LPX_E_NEG_RHS as in lpx_solve_packed (zeros around the status), and LPX_EINVAL
+ * with stop = LPX_PBNB_REFUSED for a node edit lpx_bounded_node3 would refuse (the host driver fails with that call's error there).
+ * One model's outcome never affects another's.  stop: LPX_PBNB_DONE (the stack ran empty), _ROOT (the model ended at or in front of
+ * the root LP), _NODES (max_nodes nodes were evaluated and the stack is not empty), _NODE_ITER (a node made max_iter events), _EVENTS
+ * (the nodes evaluated so far made max_events dual events or more; tested where max_nodes is, in front of a pop, behind it),
+ * _DEPTH (a node at depth max_depth would branch), _REFUSED.
+ *
+ * For every i: status, x, value, nodes, events, flips, incumbents, pruned_bound, pruned_infeasible, max_K and the first log_cap log
+ * records are bit-equal to lpx_solve_bnb_bounded3(model i, lower_i, upper_i, is_int, max_iter, max_nodes, search_flags,
+ * LPX_NODE_ONCHIP) wherever max_events and max_depth do not bind (where that call returns LPX_ITER_LIMIT, its out holds the same
+ * incumbent), and do not depend on count, on i, on the other models or on whether an array is shared.  deepest is the largest
+ * depth of an evaluated node, root_events the events of the root loop, logged = min(nodes, log_cap), best the internal objective
+ * of the incumbent (-inf: none), constant = c.lower over the non-zero lower bounds.  The log slice of a model behind its `logged`
+ * records is zero.
+ *
+ * LPX_EINVAL before any device check, the outputs untouched, every message starting "lpx_solve_packed_bnb: ": the list of
+ * lpx_solve_packed in its order up to the fit rule; then a NULL opt, a search_flags bit outside LPX_BDUAL_LONG_STEP |
+ * LPX_BDUAL_CUTOFF ("unknown flag"), a negative max_iter; then max_nodes or max_events below 1, a negative max_depth or log_cap, log
+ * non-NULL with log_cap == 0 or log NULL with log_cap > 0; last, because it needs valid options, more than 1 GiB of inputs, outputs,
+ * log and work slices ("too large").  No device: LPX_EDEVICE.  st (or NULL): pivots = the kind-0 and kind-1 pivots of every root
+ * and node, launches = 1, loop_ms the host wall of the copies, the launch and the wait. */
+#define LPX_PBNB_DONE      0
+#define LPX_PBNB_ROOT      1
+#define LPX_PBNB_NODES     2
+#define LPX_PBNB_NODE_ITER 3
+#define LPX_PBNB_EVENTS    4
+#define LPX_PBNB_DEPTH     5
+#define LPX_PBNB_REFUSED   6
+typedef struct lpx_packed_bnb_models {  /* lpx_packed_models plus the mask */
+    int32_t count, m, n, sense;        /* one shape for all; every row is <= */
+    const double *c, *A, *b;           /* [count][n], [count][m][n] row-major, [count][m] */
+    const double *lower, *upper;       /* [count][n] or NULL (0 / +inf) */
+    int64_t c_stride, A_stride, b_stride, lower_stride, upper_stride;
+                                       /* doubles between models: the packed size, or 0 = ONE shared copy */
+    const uint8_t* is_int;             /* [n], shared by every model, or NULL = every variable is integer */
+} lpx_packed_bnb_models;
+typedef struct lpx_packed_bnb_opts {
+    int32_t search_flags;              /* subset of LPX_BDUAL_LONG_STEP | LPX_BDUAL_CUTOFF */
+    int32_t max_iter;                  /* events per node and of the root loop, >= 0 */
+    int32_t max_depth;                 /* deepest node a model may hold; 0 = n */
+    int32_t log_cap;                   /* log records kept per model, 0 = none */
+    int64_t max_nodes, max_events;     /* per model, both >= 1 */
+} lpx_packed_bnb_opts;
+typedef struct lpx_packed_bnb_record {  /* 88 bytes */
+    int32_t status, stop;              /* status[i] again; LPX_PBNB_* */
+    int64_t nodes, events, flips, incumbents, pruned_bound, pruned_infeasible;
+    int32_t max_K, deepest, root_events, logged;
+    double best, constant;             /* internal z of the incumbent (-inf: none); c.lower */
+} lpx_packed_bnb_record;
+typedef struct lpx_packed_bnb_results { /* caller-allocated; status, x, value required; rec and log may be NULL */
+    int32_t* status;  double* x;  double* value;           /* [count], [count][n], [count] */
+    lpx_packed_bnb_record* rec;  lpx_bnb_node_log* log;    /* [count], [count][log_cap] */
+} lpx_packed_bnb_results;
+int lpx_solve_packed_bnb(const lpx_packed_bnb_models* in, const lpx_packed_bnb_opts* opt, const lpx_packed_bnb_results* out,
+                         lpx_stats* st /* or NULL */);
+
 /* ---- GMI cuts on a handle with bounds, and the cut loop at a bounded root (csrc/lpx_cuts.hip, csrc/lpx_tableau_bounded.cpp,
  * DESIGN.md section 4.23) --------------------------------------------------------------------------------------------------
  * An internal column of a bounded handle stands for x'_j = x_j - lo_j, or for ub_j - (x_j - lo_j) when it is flipped; x'_j >= 0

@@ -201,6 +201,39 @@ namespace Linear_Programming_Solver.Native
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct LpxPackedBnbModels      // lpx_packed_bnb_models: lpx_packed_models plus the integer mask
+    {
+        public int count, m, n, sense;           // every row is <=
+        public double* c, A, b;                  // [count][n], [count][m][n] row-major, [count][m]
+        public double* lower, upper;             // [count][n] or null (0 / +inf)
+        public long c_stride, A_stride, b_stride, lower_stride, upper_stride;   // doubles between models; 0 = one shared copy
+        public byte* is_int;                     // [n], shared by every model, or null = every variable is integer
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct LpxPackedBnbOpts               // lpx_packed_bnb_opts: the flags and the budgets of one model's search
+    {
+        public int search_flags, max_iter, max_depth, log_cap;   // LPX_BDUAL_LONG_STEP (2) | LPX_BDUAL_CUTOFF (4); max_depth 0 = n
+        public long max_nodes, max_events;       // both at least 1
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public struct LpxPackedBnbRecord             // lpx_packed_bnb_record: 88 bytes, one model of lpx_solve_packed_bnb
+    {
+        public int status, stop;                 // stop: LPX_PBNB_* 0 done, 1 root, 2 nodes, 3 node_iter, 4 events, 5 depth, 6 refused
+        public long nodes, events, flips, incumbents, pruned_bound, pruned_infeasible;
+        public int max_K, deepest, root_events, logged;
+        public double best, constant;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct LpxPackedBnbResults     // lpx_packed_bnb_results: caller-allocated; rec and log may be null
+    {
+        public int* status; public double* x; public double* value;
+        public LpxPackedBnbRecord* rec; public LpxBnbNodeLog* log;   // [count], [count][log_cap]
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public struct LpxGuardRecord                 // lpx_guard_record: 8 bytes
     {
         public int bland_events, first_bland;    // pivots made in Bland mode; event index of the first, -1 = none
@@ -505,6 +538,10 @@ namespace Linear_Programming_Solver.Native
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_solve_packed_dual(ref LpxPackedDualModels models, int flags, IntPtr opts, ref LpxPackedDualResults results,
                                                        LpxStats* st);
+        // packed batches of small integer programs: the whole branch and bound of every model in ONE launch
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_packed_bnb(ref LpxPackedBnbModels models, ref LpxPackedBnbOpts opts, ref LpxPackedBnbResults results,
+                                                      LpxStats* st);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_solve_bnb_bounded8(ref LpxProblem p, double* lower, double* upper, byte* is_int, ref LpxSolveOpts o,
                                                         long max_nodes, int search_flags, int divers, int stall_events, int root_form,

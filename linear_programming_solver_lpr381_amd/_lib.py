@@ -231,6 +231,34 @@ class PackedDualResults(C.Structure):
                 ("at_upper", C.POINTER(C.c_uint8)), ("y", dp), ("d", dp)]
 
 
+PBNB_DONE, PBNB_ROOT, PBNB_NODES, PBNB_NODE_ITER, PBNB_EVENTS, PBNB_DEPTH, PBNB_REFUSED = range(7)    # LPX_PBNB_* (lpx_solve_packed_bnb)
+PBNB_STOPS = ("done", "root", "nodes", "node_iter", "events", "depth", "refused")
+
+
+class PackedBnbModels(C.Structure):
+    """lpx_packed_bnb_models (include/lpx.h): lpx_packed_models plus is_int ([n] bytes shared by every model, or NULL = all)."""
+    _fields_ = PackedModels._fields_ + [("is_int", C.POINTER(C.c_uint8))]
+
+
+class PackedBnbOpts(C.Structure):
+    """lpx_packed_bnb_opts (include/lpx.h): the search flags and the budgets of lpx_solve_packed_bnb, per model."""
+    _fields_ = [("search_flags", C.c_int32), ("max_iter", C.c_int32), ("max_depth", C.c_int32), ("log_cap", C.c_int32),
+                ("max_nodes", C.c_int64), ("max_events", C.c_int64)]
+
+
+class PackedBnbRecord(C.Structure):
+    """lpx_packed_bnb_record (include/lpx.h): the counters of one model's search, 88 bytes."""
+    _fields_ = [("status", C.c_int32), ("stop", C.c_int32), ("nodes", C.c_int64), ("events", C.c_int64), ("flips", C.c_int64),
+                ("incumbents", C.c_int64), ("pruned_bound", C.c_int64), ("pruned_infeasible", C.c_int64), ("max_K", C.c_int32),
+                ("deepest", C.c_int32), ("root_events", C.c_int32), ("logged", C.c_int32), ("best", C.c_double),
+                ("constant", C.c_double)]
+
+
+class PackedBnbResults(C.Structure):
+    """lpx_packed_bnb_results (include/lpx.h): caller-allocated output arrays; rec and log may be NULL."""
+    _fields_ = [("status", ip), ("x", dp), ("value", dp), ("rec", C.POINTER(PackedBnbRecord)), ("log", C.POINTER(BnbNodeLog))]
+
+
 class FixList(C.Structure):
     """lpx_fix_list (include/lpx.h): the caller-owned list of the columns a node tightened, as the triples of a bound edit."""
     _fields_ = [("cap", C.c_int32), ("n", C.c_int32), ("cols", ip), ("lower", dp), ("upper", dp)]
@@ -469,7 +497,9 @@ def lib() -> C.CDLL:
     L.lpx_solve_packed.argtypes = [C.POINTER(PackedModels), C.POINTER(RunOpts), C.POINTER(PackedResults), C.POINTER(Stats)]
     L.lpx_solve_packed_dual.argtypes = [C.POINTER(PackedDualModels), C.c_int, C.POINTER(RunOpts), C.POINTER(PackedDualResults),
                                         C.POINTER(Stats)]
-    L.lpx_solve_bnb_bounded8.argtypes = [C.POINTER(Problem), dp, dp, u8p, C.POINTER(SolveOpts), C.c_int64, C.c_int, C.c_int, C.c_int,
+    L.lpx_solve_packed_bnb.argtypes = [C.POINTER(PackedBnbModels), C.POINTER(PackedBnbOpts), C.POINTER(PackedBnbResults),
+                                       C.POINTER(Stats)]
+    L.lpx_solve_bnb_bounded8.argtypes =[C.POINTER(Problem), dp, dp, u8p, C.POINTER(SolveOpts), C.c_int64, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.POINTER(Result), C.POINTER(BnbBoundedInfo), C.POINTER(BnbDiversInfo),
                                          C.POINTER(BnbGuardInfo)]
     L.lpx_solve_bnb_bounded9.argtypes = [C.POINTER(Problem), dp, dp, u8p, C.POINTER(SolveOpts), C.c_int64, C.c_int, C.c_int, C.c_int,

@@ -242,6 +242,9 @@ void SolveBoundedBatch(const std::vector<const LPProblem*>& problems, const std:
 void CheckPacked(const lpx_packed_models* in, const lpx_run_opts* o, const lpx_packed_results* out);
 // the argument checks of lpx_solve_packed_dual, the same way; the call itself is lpx::packed_dual_solve
 void CheckPackedDual(const lpx_packed_dual_models* in, int flags, const lpx_run_opts* o, const lpx_packed_dual_results* out);
+// the argument checks of lpx_solve_packed_bnb, the same way; work_bytes is lpx::packed_bnb_work_bytes; the call itself is lpx::packed_bnb_solve
+void CheckPackedBnb(const lpx_packed_bnb_models* in, const lpx_packed_bnb_opts* opt, const lpx_packed_bnb_results* out,
+                    size_t (*work_bytes)(int count, int m, int n, int max_depth));
 // The dual start (lpx_solve_bounded_dual): >= rows and negative right-hand sides accepted, slack basis, dualize, lpx_bounded_dual_run3(flags)
 SimplexResult SolveBoundedDual(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper, int flags,
                                const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info);

@@ -389,6 +389,14 @@ int lpx_solve_packed_dual(const lpx_packed_dual_models* in, int flags, const lpx
     return packed_dual_solve(in, flags, o, out, st);
 }
 
+int lpx_solve_packed_bnb(const lpx_packed_bnb_models* in, const lpx_packed_bnb_opts* opt, const lpx_packed_bnb_results* out,
+                         lpx_stats* st)
+{
+    try { CheckPackedBnb(in, opt, out, packed_bnb_work_bytes); }
+    catch (const LpxException& ex) { set_error(ex.what()); return ex.code; }
+    return packed_bnb_solve(in, opt, out, st);
+}
+
 void lpx_bounded_info_free(lpx_bounded_info* info)
 {
     if (!info) return;

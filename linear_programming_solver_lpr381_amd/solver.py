@@ -98,7 +98,22 @@ class PackedDualResult(PackedResult):   # lpx_packed_dual_results (include/lpx.h
 
 
 @dataclass
-class RangingReport:        # lpx_ranging (include/lpx.h): ranges of the solved model in user terms
+class PackedBnbResult(PackedResult):    # lpx_packed_bnb_results (include/lpx.h): LPSolver.SolvePackedBnb
+    # Status: OPTIMAL, INFEASIBLE, ITER_LIMIT (a budget: see Stop), the root's UNBOUNDED, or LPX_EINVAL / LPX_E_NEG_RHS of that model alone
+    Stop: Optional[np.ndarray] = None           # (B,) int32 LPX_PBNB_*: done, root, nodes, node_iter, events, depth, refused (want "rec")
+    Nodes: Optional[np.ndarray] = None          # (B,) nodes evaluated                                               (want "rec")
+    Info: Optional[np.ndarray] = None           # (B,) structured: every counter of lpx_packed_bnb_record            (want "rec")
+    Log: Optional[np.ndarray] = None            # (B, log_cap) of the BnbLog dtype; zero behind Logged[i] records     (log_cap > 0)
+    Logged: Optional[np.ndarray] = None         # (B,) min(nodes, log_cap)                                            (log_cap > 0)
+
+
+PACKED_BNB_DTYPE = np.dtype([("status", "<i4"), ("stop", "<i4"), ("nodes", "<i8"), ("events", "<i8"), ("flips", "<i8"),
+                             ("incumbents", "<i8"), ("pruned_bound", "<i8"), ("pruned_infeasible", "<i8"), ("max_K", "<i4"),
+                             ("deepest", "<i4"), ("root_events", "<i4"), ("logged", "<i4"), ("best", "<f8"), ("constant", "<f8")])
+
+
+@dataclass
+class RangingReport:       # lpx_ranging (include/lpx.h): ranges of the solved model in user terms
     valid: bool
     cost_lo: np.ndarray
     cost_hi: np.ndarray
@@ -532,6 +547,74 @@ class LPSolver:             # Models/LPSolver.cs:6-77
             res.Passes = r["passes"].copy()
             res.DualizeFlips = r["dualize_flips"].copy()
             res.Z = r["z"].copy()
+        return res
+
+    def SolvePackedBnb(self, c, A, b, upper, lower=None, integer=None, sense="max", long_step: bool = False, cutoff: bool = False,
+                       max_nodes: int = 100000, max_events: int = 2000000, max_iter=None, max_depth: int = 0, log_cap: int = 0,
+                       want=("rec",)) -> PackedBnbResult:
+        """B small integer programs of ONE shape (m rows, all <=; n variables) in ONE kernel launch (lpx_solve_packed_bnb): every
+        workgroup runs the whole branch and bound of SolveBnbBounded(node_form="onchip") for its model with the tableau staying in
+        LDS.  The arrays are SolvePacked's; integer: None (every variable) or (n,) flags shared by every model; integer variables
+        need finite, integral bounds (else that model is LPX_EINVAL).  long_step / cutoff: the flags of SolveBnbBounded.  The
+        budgets are per model and mandatory: max_nodes and max_events at least 1, max_iter (events per node and of the root LP;
+        None: the engine's, else 10000), max_depth (0 = n).  Status per model: OPTIMAL, INFEASIBLE, ITER_LIMIT (a budget stopped the
+        search, Stop says which, Solution / OptimalValue are the incumbent so far or zeros), the root's UNBOUNDED, or the model's own
+        LPX_EINVAL / LPX_E_NEG_RHS.  Each entry is bit-equal to SolveBnbBounded(model, ..., node_form="onchip", max_nodes=) wherever
+        max_events and max_depth do not bind.  log_cap > 0: Log, the first log_cap node records of every model, and Logged."""
+        want = tuple(want)
+        for w in want:
+            if w not in ("rec",):
+                raise ValueError(f"unknown output {w!r}")
+        if int(max_nodes) < 1 or int(max_events) < 1:
+            raise ValueError("max_nodes and max_events must be at least 1: the budgets of a packed search are mandatory")
+        if int(max_depth) < 0 or int(log_cap) < 0:
+            raise ValueError("max_depth and log_cap must not be negative")
+        limit = max_iter if max_iter is not None else self.engine.get("max_iter")
+        limit = 10000 if limit is None else int(limit)
+        if limit < 0:
+            raise ValueError("max_iter must not be negative")
+        sense, c, A, b, bounds, _, B, m, n = _packed_inputs(c, A, b, upper, lower, sense)
+        mask = None
+        if integer is not None:
+            mask = np.ascontiguousarray(np.asarray(integer)).astype(np.uint8)
+            if mask.shape != (n,):
+                raise ValueError(f"integer is (n,) with n = {n}: one mask shared by every model")
+
+        def _stride(v, nd, packed):
+            return packed if v.ndim == nd else 0
+        pm = _lib.PackedBnbModels()
+        pm.count, pm.m, pm.n, pm.sense = B, m, n, int(sense)
+        pm.c, pm.A, pm.b = (v.ctypes.data_as(_lib.dp) for v in (c, A, b))
+        pm.c_stride, pm.A_stride, pm.b_stride = _stride(c, 2, n), _stride(A, 3, m * n), _stride(b, 2, m)
+        for name in ("upper", "lower"):
+            v = bounds[name]
+            if v is not None:
+                setattr(pm, name, v.ctypes.data_as(_lib.dp))
+                setattr(pm, name + "_stride", _stride(v, 2, n))
+        if mask is not None:
+            pm.is_int = mask.ctypes.data_as(C.POINTER(C.c_uint8))
+        po = _lib.PackedBnbOpts((_lib.BDUAL_LONG_STEP if long_step else 0) | (_lib.BDUAL_CUTOFF if cutoff else 0), limit,
+                                int(max_depth), int(log_cap), int(max_nodes), int(max_events))
+        status = np.zeros(B, dtype=np.int32); x = np.zeros((B, n)); value = np.zeros(B)
+        pr = _lib.PackedBnbResults()
+        pr.status, pr.x, pr.value = status.ctypes.data_as(_lib.ip), x.ctypes.data_as(_lib.dp), value.ctypes.data_as(_lib.dp)
+        recs = log = None
+        if "rec" in want or log_cap > 0:
+            recs = np.zeros(B, dtype=PACKED_BNB_DTYPE)
+            pr.rec = recs.ctypes.data_as(C.POINTER(_lib.PackedBnbRecord))
+        if log_cap > 0:
+            log = np.zeros((B, int(log_cap)), dtype=BNB_LOG_DTYPE)
+            pr.log = log.ctypes.data_as(C.POINTER(_lib.BnbNodeLog))
+        st = _lib.Stats()
+        rc = lib().lpx_solve_packed_bnb(C.byref(pm), C.byref(po), C.byref(pr), C.byref(st))
+        if rc != 0:
+            raise SolverException(rc, _lib.last_error())
+        res = PackedBnbResult(Status=status, Solution=x, OptimalValue=value, Stats=st.as_dict())
+        if recs is not None:
+            res.Stop, res.Nodes, res.Info = recs["stop"].copy(), recs["nodes"].copy(), recs
+            res.Events = recs["events"].copy()
+        if log is not None:
+            res.Log, res.Logged = log, recs["logged"].copy()
         return res
 
     def _solve_bounded(self, problem: LPProblem, upper, lower, dual_flags, form: str = "launches") -> SimplexResult:

@@ -81,7 +81,14 @@ below its minimum.  A side that ends at a node's event limit is reported (`limit
 with stall_events = 0 (the node kernel, its record a kernel argument), with a stall_events it never reaches (the guarded kernel,
 its record read from pinned memory) and lpx_bounded_node5 with a fix_bound so far below z that the step runs and tightens nothing
 (the guarded kernel's shape plus the step).  No
-speed-up is expected in advance: at large W the tighter bounds arrive a round late."""
+speed-up is expected in advance: at large W the tighter bounds arrive a round late.
+
+`--compare-packed [--flag-sets NAME] [REPS]` measures the packed branch and bound (lpx_solve_packed_bnb): 256
+and 4096 right-hand sides of one 9 x 29 binary model as ONE SolvePackedBnb call against the same models as single
+SolveBnbBounded(node_form="onchip") calls, host wall of whole calls, the sides alternating in one process, one untimed round first,
+REPS (default 7; 2 at 4096) timed rounds, the results asserted equal; then one model alone against the sequential driver and
+divers=4,16,64; then binary_ip(60, 12) alone against the sequential on-chip driver, as time per node.  A side wins iff its median lies
+below the other's minimum.  `--packed-trace` makes four packed calls and the binary_ip(60, 12) call for a kernel trace."""
 import json
 import os
 import statistics
@@ -585,8 +592,105 @@ def compare_tighten(n, m, reps, max_nodes, flag_sets, widths):
     return rec
 
 
+def rhs_family(n, m, count, seed=5):
+    """count right-hand sides of ONE binary model of n variables and m rows (synth.binary_ip's rows): b_i scaled by U(0.8, 1.2),
+    floored, plus 0.5 -- (c, A [m, n], bs [count, m])."""
+    c, A, _, b = synth.binary_ip(n, m, seed)
+    g = np.random.default_rng(seed)
+    bs = np.floor(b[:m] * g.uniform(0.8, 1.2, size=(count, m))) + 0.5
+    return c, np.ascontiguousarray(A[:m]), bs
+
+
+def compare_packed(reps, counts, big_reps, widths, kw_name="plain"):
+    """The packed branch and bound (lpx_solve_packed_bnb) against the same models as single
+    SolveBnbBounded(node_form="onchip") calls: host wall of whole calls, the sides alternating in one process, one untimed round
+    first.  Then, on one model, the best of divers=W; then binary_ip(60, 12) alone against the sequential on-chip driver."""
+    S = L.LPSolver()
+    kw = FLAG_SETS[kw_name]
+    out = {"flags": kw_name, "families": {}}
+    n, m = 20, 8
+    for count in counts:
+        c, A, bs = rhs_family(n, m, count)
+        probs = [L.LPProblem.from_arrays(0, c, A, [0] * m, bs[i]) for i in range(count)]
+        r = big_reps if count > 1024 else reps
+        ts = {"packed": [], "single": []}
+        for i in range(r + 1):
+            t0 = time.perf_counter()
+            pk = S.SolvePackedBnb(c, A, bs, 1.0, **kw)
+            t1 = time.perf_counter()
+            ones = [S.SolveBnbBounded(p, 1.0, node_form="onchip", **kw) for p in probs]
+            t2 = time.perf_counter()
+            if i >= 1:
+                ts["packed"].append(1e3 * (t1 - t0)); ts["single"].append(1e3 * (t2 - t1))
+        assert pk.Status.tolist() == [o.Status for o in ones] and (pk.Stop == 0).all()
+        assert pk.Nodes.tolist() == [o.Nodes for o in ones]
+        assert all(np.array_equal(pk.Solution[i], o.Solution) and pk.OptimalValue[i] == o.OptimalValue for i, o in enumerate(ones))
+        d = {k: stats(v) for k, v in ts.items()}
+        d.update(count=count, shape=[m + 1, n + m + 1], nodes=int(pk.Nodes.sum()), events=int(pk.Info["events"].sum()),
+                 max_nodes_of_a_model=int(pk.Nodes.max()), deepest=int(pk.Info["deepest"].max()),
+                 kernel_ms=pk.Stats["loop_ms"], us_per_node_packed=1e3 * statistics.median(ts["packed"]) / int(pk.Nodes.sum()),
+                 us_per_node_single=1e3 * statistics.median(ts["single"]) / int(pk.Nodes.sum()),
+                 packed_wins=bool(d["packed"]["median"] < d["single"]["min"]), single_wins=bool(d["single"]["median"] < d["packed"]["min"]))
+        out["families"][str(count)] = d
+    # one model: the packed call (count = 1) against the sequential driver and the divers
+    c, A, bs = rhs_family(n, m, 1)
+    p = L.LPProblem.from_arrays(0, c, A, [0] * m, bs[0])
+    sides = {"packed": lambda: S.SolvePackedBnb(c, A, bs, 1.0, **kw), "onchip": lambda: S.SolveBnbBounded(p, 1.0, node_form="onchip", **kw)}
+    for W in widths:
+        sides["divers=%d" % W] = (lambda W=W: S.SolveBnbBounded(p, 1.0, divers=W, **kw))
+    out["one_model"] = alternate(sides, reps)
+    # binary_ip(60, 12) alone: ONE workgroup, every node in the one launch
+    c, A, rel, b = synth.binary_ip(60, 12)
+    A12, b12 = np.ascontiguousarray(A[:12]), b[:12]
+    p = L.LPProblem.from_arrays(0, c, A12, [0] * 12, b12)
+    sides = {"packed": lambda: S.SolvePackedBnb(c, A12, b12, 1.0, max_nodes=1000000, max_events=100000000, **kw),
+             "onchip": lambda: S.SolveBnbBounded(p, 1.0, node_form="onchip", **kw)}
+    d = alternate(sides, reps)
+    pk, one = sides["packed"](), sides["onchip"]()
+    assert pk.Status[0] == one.Status and pk.Nodes[0] == one.Nodes and pk.OptimalValue[0] == one.OptimalValue
+    d.update(nodes=int(pk.Nodes[0]), events=int(pk.Info["events"][0]), deepest=int(pk.Info["deepest"][0]),
+             us_per_node_packed=1e3 * d["packed"]["median"] / int(pk.Nodes[0]), us_per_node_onchip=1e3 * d["onchip"]["median"] / int(pk.Nodes[0]))
+    out["bip_60x12"] = d
+    return out
+
+
+def alternate(sides, reps):
+    """Host wall in ms of every side, the sides alternating in one process, one untimed round first; a side wins against another iff
+    its median lies below the other's minimum."""
+    ts = {k: [] for k in sides}
+    for i in range(reps + 1):
+        for k, f in sides.items():
+            t0 = time.perf_counter()
+            f()
+            if i >= 1:
+                ts[k].append(1e3 * (time.perf_counter() - t0))
+    d = {k: stats(v) for k, v in ts.items()}
+    d["wins"] = {a: [b for b in sides if b != a and d[a]["median"] < d[b]["min"]] for a in sides}
+    return d
+
+
 def main():
     args = sys.argv[1:]
+    if "--packed-trace" in args:        # four packed calls of 256 right-hand sides and one of binary_ip(60, 12), for a kernel trace
+        L._lib.check(L._lib.lib().lpx_init(0))
+        c, A, bs = rhs_family(20, 8, 256)
+        for _ in range(4):
+            L.LPSolver().SolvePackedBnb(c, A, bs, 1.0)
+        c, A, rel, b = synth.binary_ip(60, 12)
+        r = L.LPSolver().SolvePackedBnb(c, np.ascontiguousarray(A[:12]), b[:12], 1.0, max_nodes=1000000, max_events=100000000)
+        print(json.dumps({"bip_60x12_nodes": int(r.Nodes[0]), "status": int(r.Status[0]), "loop_ms": r.Stats["loop_ms"]}))
+        return
+    if "--compare-packed" in args:
+        args.remove("--compare-packed")
+        flag_set = "plain"
+        if "--flag-sets" in args:
+            j = args.index("--flag-sets")
+            flag_set = args[j + 1]
+            del args[j:j + 2]
+        reps = int(args[0]) if args else 7
+        L._lib.check(L._lib.lib().lpx_init(0))
+        print(json.dumps(compare_packed(reps, [256, 4096], 2, [4, 16, 64], flag_set)))
+        return
     if "--compare-tighten" in args:
         k = args.index("--compare-tighten")
         widths = [1, 16, 256]

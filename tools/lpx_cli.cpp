@@ -1,7 +1,7 @@
 // lpx_cli -- Linux stand-in for the reference's WinForms host (Form1.cs), over the C ABI of liblpx.so only.
 //
 //   lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]
-//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S] [--root-form F] [--root-cuts N [--cuts-per-round K]] [--tighten]] [--bounded-form F] [--bounded [--rhs-file F]] [--bounded-dual [--long-step] --rhs-file F] [--export FILE] INPUT.txt
+//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S] [--root-form F] [--root-cuts N [--cuts-per-round K]] [--tighten]] [--bounded-form F] [--bounded [--rhs-file F]] [--bounded-dual [--long-step] --rhs-file F] [--binary --bnb-bounded [--long-step] [--cutoff] --rhs-file F] [--export FILE] INPUT.txt
 //
 // Does what Form1 does around the solvers: reads the model text (Import, Form1.cs:284-296), parses it with the LPParser
 // grammar (lpx_parse_text, Models/LPParser.cs:9-79), runs the algorithm chosen by its dropdown name (btnSolve_Click,
@@ -15,7 +15,9 @@
 // --binary (every u_j = 1) select the bounded-variable primal simplex (lpx_solve_bounded): the bounds cost no rows.  --bounded selects it without any bound.  --bounded --rhs-file F solves the model once per line of F (m numbers, the
 // right-hand sides of that run) as ONE packed call (lpx_solve_packed) with c, A and the bounds shared by every run, and prints one
 // line "status value x1 .. xn" per right-hand side.  --bounded-dual [--long-step] --rhs-file F does the same by the dual start
-// (lpx_solve_packed_dual): >= rows and negative right-hand sides are accepted, an = row is refused.  There is no CPU fallback: without a gfx950 device the solve fails with LPX_EDEVICE.
+// (lpx_solve_packed_dual): >= rows and negative right-hand sides are accepted, an = row is refused.  --bnb-bounded --rhs-file F (with
+// --binary or --upper bounds, and --long-step / --cutoff) solves the model as an integer program once per line of F as ONE packed
+// call (lpx_solve_packed_bnb): a whole branch and bound per right-hand side in one kernel launch, the same line per run.  There is no CPU fallback: without a gfx950 device the solve fails with LPX_EDEVICE.
 #include <cstdio>
 #include <cstdlib>
 #include <cctype>
@@ -204,6 +206,7 @@ int main(int argc, char** argv)
             std::printf("usage: lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]\n"
                         "               [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S] [--root-form F] [--root-cuts N [--cuts-per-round K]] [--tighten]] [--bounded-form F]\n"
                         "               [--bounded [--rhs-file F]] [--bounded-dual [--long-step] --rhs-file F] [--export FILE] INPUT.txt\n"
+                        "               [--binary --bnb-bounded [--long-step] [--cutoff] --rhs-file F]\n"
                         "  NAME: Primal Simplex | Revised Primal Simplex | Dual Simplex | Branch and Bound |\n"
                         "        Revised Branch and Bound | Branch and Bound Knapsack | Cutting Plane | Revised Cutting Plane |\n"
                         "        GMI Cutting Plane (gmi) | Bounded Primal Simplex\n"
@@ -237,6 +240,9 @@ int main(int argc, char** argv)
                         "             launch, one read-back; c, A and the bounds shared); prints a line \"status value x1 .. xn\" per run\n"
                         "  --bounded-dual [--long-step] --rhs-file F: the same by the dual start (lpx_solve_packed_dual): >= rows and negative\n"
                         "             right-hand sides are accepted, an = row is refused; --long-step: the bound-flipping ratio test\n"
+                        "  --bnb-bounded --rhs-file F: the model as an integer program once per line of F as ONE packed call (lpx_solve_packed_bnb:\n"
+                        "             a whole branch and bound per right-hand side in one kernel launch; at most 100000 nodes and 2000000 events\n"
+                        "             per run); with --binary or --upper bounds and --long-step / --cutoff; the same line per run\n"
                         "  --root-cuts N: with --bnb-bounded --divers, cut-and-branch (lpx_solve_bnb_bounded9): up to N rounds of --cuts-per-round K\n"
                         "             (default 8) GMI cuts at the solved root, then the search from that tableau; not with --plunge or --branching\n"
                         "  --root-form launches|onchip|auto: with --bnb-bounded --divers, how the root LP is solved (lpx_solve_bnb_bounded8);\n"
@@ -256,12 +262,18 @@ int main(int argc, char** argv)
         if (ranging) { std::fprintf(stderr, "lpx_cli: --ranging does not combine with --cuts-per-round / --cut-rounds\n"); return 64; }
     }
     const bool bounded = binary || !bounds.empty() || bounded_flag || bounded_dual;
+    const bool packed_bnb = bnb_bounded && !rhs_file.empty() && !bounded_dual && !bounded_flag;     // --bnb-bounded --rhs-file F
+    if (packed_bnb && (node_form >= 0 || divers || plunge || branching >= 0 || stall_events >= 0 || root_form >= 0 || root_cuts >= 0 || tighten ||
+                       bounded_form >= 0 || iterations || !edits.empty() || !exportPath.empty())) {
+        std::fprintf(stderr, "lpx_cli: --bnb-bounded --rhs-file combines only with --long-step / --cutoff and --upper / --lower / --binary\n");
+        return 64;
+    }
     if (bounded_dual && (rhs_file.empty() || bounded_flag || bnb_bounded || bounded_form >= 0 || iterations || !edits.empty() || !exportPath.empty() ||
                          (search_flags & ~LPX_BDUAL_LONG_STEP))) {
         std::fprintf(stderr, "lpx_cli: --bounded-dual needs --rhs-file and combines only with --long-step and --upper / --lower / --binary\n");
         return 64;
     }
-    if (!bounded_dual && !rhs_file.empty() && (!bounded_flag || bnb_bounded || bounded_form >= 0 || iterations || !edits.empty() || !exportPath.empty())) {
+    if (!bounded_dual && !packed_bnb && !rhs_file.empty() && (!bounded_flag || bnb_bounded || bounded_form >= 0 || iterations || !edits.empty() || !exportPath.empty())) {
         std::fprintf(stderr, "lpx_cli: --rhs-file needs --bounded and combines only with --upper / --lower / --binary\n");
         return 64;
     }
@@ -351,7 +363,20 @@ int main(int argc, char** argv)
         std::vector<int32_t> status((size_t)(count > 0 ? count : 1));
         std::vector<double> x((size_t)(count > 0 ? count : 1) * (size_t)(p.n > 0 ? p.n : 1)), value((size_t)(count > 0 ? count : 1));
         int prc;
-        if (bounded_dual) {                             // c, A, rel and the bounds: stride 0, one copy for every run
+        if (packed_bnb) {                               // c, A and the bounds: stride 0; every variable integer, as --bnb-bounded
+            lpx_packed_bnb_models bm; std::memset(&bm, 0, sizeof bm);
+            bm.count = count; bm.m = p.m; bm.n = p.n; bm.sense = p.sense;
+            bm.c = p.c; bm.A = p.A; bm.b = rhs.data(); bm.lower = lo.data(); bm.upper = up.data();
+            bm.b_stride = p.m;
+            lpx_packed_bnb_opts bo; std::memset(&bo, 0, sizeof bo);
+            lpx_run_opts ro; lpx_default_opts(&ro, 1);
+            bo.search_flags = search_flags; bo.max_iter = ro.max_iter;
+            bo.max_depth = binary && bounds.empty() ? 0 : 4 * p.n + 64;    // a general integer is branched on more than once
+            bo.max_nodes = 100000; bo.max_events = 2000000;
+            lpx_packed_bnb_results br; std::memset(&br, 0, sizeof br);
+            br.status = status.data(); br.x = x.data(); br.value = value.data();
+            prc = lpx_solve_packed_bnb(&bm, &bo, &br, nullptr);
+        } else if (bounded_dual) {                             // c, A, rel and the bounds: stride 0, one copy for every run
             lpx_packed_dual_models dm; std::memset(&dm, 0, sizeof dm);
             dm.count = count; dm.m = p.m; dm.n = p.n; dm.sense = p.sense;
             dm.c = p.c; dm.A = p.A; dm.b = rhs.data(); dm.lower = lo.data(); dm.upper = up.data(); dm.rel = p.rel;
