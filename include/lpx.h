@@ -1514,6 +1514,68 @@ typedef struct lpx_packed_bnb_results { /* caller-allocated; status, x, value re
 int lpx_solve_packed_bnb(const lpx_packed_bnb_models* in, const lpx_packed_bnb_opts* opt, const lpx_packed_bnb_results* out,
                          lpx_stats* st /* or NULL */);
 
+/* ---- integer programs with >= rows: branch and bound from a dual start, host-driven and packed (csrc/host/bnb_bounded.cpp,
+ * csrc/lpx_packed_bnb_dual.hip) -------------------------------------------------------------------------
+ *
+ * lpx_solve_bnb_bounded_dual(p, lower, upper, is_int, o, max_nodes, search_flags, node_form, out, info) is lpx_solve_bnb_bounded3
+ * with one difference: the root is the dual start of lpx_solve_bounded_dual, not lpx_solve_bounded.  So a >= row is accepted
+ * (negated into a <= row), an = row is taken as its pair, and a shifted right-hand side may be negative: covering models, models
+ * with rows of both senses and right-hand sides that cross zero.  The root runs the flips of lpx_tableau_dualize(1e-9) and then
+ * lpx_bounded_dual_run3 with lpx_default_opts(o, 1), the caller's max_iter and flags = search_flags & LPX_BDUAL_LONG_STEP (no
+ * LPX_BDUAL_SKIP_FIXED and no cutoff at the root).  Every integer variable has a finite upper bound, so on a pure integer program
+ * the precheck of the dual start always passes; it can only name a continuous variable ("improves the objective and has no upper
+ * bound", LPX_EINVAL).
+ * Order of refusals: the checks of lpx_solve_bnb_bounded (bounds, then the integer variables, max_nodes, search_flags), then an
+ * unknown node_form (LPX_NODE_LAUNCHES, LPX_NODE_ONCHIP or LPX_NODE_AUTO), then the preparation.
+ * A root that ends LPX_INFEASIBLE ends the search with the result of a search without an incumbent: status LPX_INFEASIBLE,
+ * has_solution 0, value 0, x zeros, summary "INFEASIBLE\n", nodes 0, lp_solves 1; the call returns 0.  A root at the iteration
+ * limit fails as lpx_solve_bounded_dual does.  From a solved root on the search, the info, the log and the limits are those of
+ * lpx_solve_bnb_bounded3, and LPX_NODE_LAUNCHES and LPX_NODE_ONCHIP give bit-equal node logs.  Unlike a search over <= rows this
+ * one can end LPX_INFEASIBLE with nodes > 0. */
+int lpx_solve_bnb_bounded_dual(const lpx_problem* p, const double* lower /* [n] or NULL = 0 */, const double* upper /* [n] */,
+                               const uint8_t* is_int /* [n] or NULL = all */, const lpx_solve_opts* o /* or NULL */,
+                               int64_t max_nodes /* 0 = none */, int search_flags, int node_form, lpx_result* out,
+                               lpx_bnb_bounded_info* info /* or NULL */);
+
+/* lpx_solve_packed_bnb_dual(in, opt, out, st) is lpx_solve_packed_bnb for the models above: the options, record, results, log
+ * records and stop codes of lpx_solve_packed_bnb, the rows of lpx_solve_packed_dual (rel: LPX_LE / LPX_GE per row, per model or
+ * shared).  The same arena, stream and pinned block, at most one copy per input array, ONE launch of count workgroups, one
+ * read-back and one wait.  The fit rule is lpx_packed_fits(m, n).  Workgroup i
+ *   a. builds the tableau of model i in LDS as lpx_solve_packed_dual does (Min negates c, a >= row is negated while it is stored,
+ *      b' = b - A l, u' = u - l, the slack basis) and checks, in this order, the bounds, the integer variables (a finite upper
+ *      bound, integral lower and upper bounds) and rel: LPX_EINVAL.  Then the dual-feasibility flips with eps 1e-9 (a column no
+ *      flip can repair is the precheck of lpx_solve_bounded_dual: LPX_EINVAL) and the on-chip dual loop as the root loop, with
+ *      ratio_tol of lpx_default_opts(o, 1), the call's max_iter, the long step under LPX_BDUAL_LONG_STEP, no LPX_BDUAL_SKIP_FIXED
+ *      and no cutoff.  There is no LPX_E_NEG_RHS and no LPX_UNBOUNDED on this call.  A root that ends LPX_INFEASIBLE ends the
+ *      model with x zeros, value 0, nodes 0 and root_events set (the answer of the host driver); a root at LPX_ITER_LIMIT ends it
+ *      with x and value as lpx_solve_packed_dual extracts them; both with stop = LPX_PBNB_ROOT;
+ *   b. runs the search of lpx_solve_packed_bnb part b, the same steps in the same order;
+ *   c. finishes as lpx_solve_packed_bnb does.  status LPX_INFEASIBLE with stop = LPX_PBNB_DONE (the stack ran empty without an
+ *      incumbent) can be reached on this call.
+ * root_events counts the pivots and passes of the root loop; flips, events and the log count nodes only.
+ *
+ * For every i: status, x, value, nodes, events, flips, incumbents, pruned_bound, pruned_infeasible, max_K and the first log_cap log
+ * records are bit-equal to lpx_solve_bnb_bounded_dual(model i, ..., LPX_NODE_ONCHIP) wherever max_events and max_depth do not
+ * bind, and do not depend on count, on i, on the other models or on whether an array is shared.
+ *
+ * LPX_EINVAL before any device check, the outputs untouched, every message starting "lpx_solve_packed_bnb_dual: ": the list of
+ * lpx_solve_packed_bnb in its order up to the fit rule, with rel_stride among the strides (neither 0 nor m); behind the fit rule a
+ * shared rel (rel_stride 0) holding anything but LPX_LE / LPX_GE; then the option checks and the 1 GiB rule of
+ * lpx_solve_packed_bnb, which here counts rel.  A per-model rel is checked by its workgroup.  No device: LPX_EDEVICE.  st as in
+ * lpx_solve_packed_bnb. */
+typedef struct lpx_packed_bnb_dual_models {   /* lpx_packed_dual_models plus the mask */
+    int32_t count, m, n, sense;        /* one shape for all */
+    const double *c, *A, *b;           /* [count][n], [count][m][n] row-major, [count][m] */
+    const double *lower, *upper;       /* [count][n] or NULL (0 / +inf) */
+    int64_t c_stride, A_stride, b_stride, lower_stride, upper_stride;
+                                       /* doubles between models: the packed size, or 0 = ONE shared copy */
+    const int32_t* rel;                /* [count][m] of LPX_LE / LPX_GE, or NULL = every row is <= */
+    int64_t rel_stride;                /* int32 between models: m, or 0 = ONE shared copy */
+    const uint8_t* is_int;             /* [n], shared by every model, or NULL = every variable is integer */
+} lpx_packed_bnb_dual_models;
+int lpx_solve_packed_bnb_dual(const lpx_packed_bnb_dual_models* in, const lpx_packed_bnb_opts* opt,
+                              const lpx_packed_bnb_results* out, lpx_stats* st /* or NULL */);
+
 /* ---- GMI cuts on a handle with bounds, and the cut loop at a bounded root (csrc/lpx_cuts.hip, csrc/lpx_tableau_bounded.cpp,
  * DESIGN.md section 4.23) --------------------------------------------------------------------------------------------------
  * An internal column of a bounded handle stands for x'_j = x_j - lo_j, or for ub_j - (x_j - lo_j) when it is flipped; x'_j >= 0

@@ -211,6 +211,18 @@ namespace Linear_Programming_Solver.Native
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct LpxPackedBnbDualModels  // lpx_packed_bnb_dual_models: lpx_packed_dual_models plus the integer mask
+    {
+        public int count, m, n, sense;
+        public double* c, A, b;                  // [count][n], [count][m][n] row-major, [count][m]
+        public double* lower, upper;             // [count][n] or null (0 / +inf)
+        public long c_stride, A_stride, b_stride, lower_stride, upper_stride;   // doubles between models; 0 = one shared copy
+        public int* rel;                         // [count][m] of LPX_LE (0) / LPX_GE (1), or null = every row is <=
+        public long rel_stride;                  // ints between models: m, or 0 = one shared copy
+        public byte* is_int;                     // [n], shared by every model, or null = every variable is integer
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public struct LpxPackedBnbOpts               // lpx_packed_bnb_opts: the flags and the budgets of one model's search
     {
         public int search_flags, max_iter, max_depth, log_cap;   // LPX_BDUAL_LONG_STEP (2) | LPX_BDUAL_CUTOFF (4); max_depth 0 = n
@@ -542,6 +554,13 @@ namespace Linear_Programming_Solver.Native
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_solve_packed_bnb(ref LpxPackedBnbModels models, ref LpxPackedBnbOpts opts, ref LpxPackedBnbResults results,
                                                       LpxStats* st);
+        // integer programs with >= rows: the search from a dual start, host-driven and packed (options, record and results of lpx_solve_packed_bnb)
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_bnb_bounded_dual(ref LpxProblem p, double* lower, double* upper, byte* is_int, ref LpxSolveOpts o,
+                                                            long max_nodes, int search_flags, int node_form, out LpxResult result, out LpxBnbBoundedInfo info);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_solve_packed_bnb_dual(ref LpxPackedBnbDualModels models, ref LpxPackedBnbOpts opts, ref LpxPackedBnbResults results,
+                                                           LpxStats* st);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_solve_bnb_bounded8(ref LpxProblem p, double* lower, double* upper, byte* is_int, ref LpxSolveOpts o,
                                                         long max_nodes, int search_flags, int divers, int stall_events, int root_form,

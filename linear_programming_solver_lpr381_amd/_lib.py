@@ -240,6 +240,11 @@ class PackedBnbModels(C.Structure):
     _fields_ = PackedModels._fields_ + [("is_int", C.POINTER(C.c_uint8))]
 
 
+class PackedBnbDualModels(C.Structure):
+    """lpx_packed_bnb_dual_models (include/lpx.h): lpx_packed_dual_models plus is_int ([n] bytes shared by every model, or NULL = all)."""
+    _fields_ = PackedDualModels._fields_ + [("is_int", C.POINTER(C.c_uint8))]
+
+
 class PackedBnbOpts(C.Structure):
     """lpx_packed_bnb_opts (include/lpx.h): the search flags and the budgets of lpx_solve_packed_bnb, per model."""
     _fields_ = [("search_flags", C.c_int32), ("max_iter", C.c_int32), ("max_depth", C.c_int32), ("log_cap", C.c_int32),
@@ -499,6 +504,10 @@ def lib() -> C.CDLL:
                                         C.POINTER(Stats)]
     L.lpx_solve_packed_bnb.argtypes = [C.POINTER(PackedBnbModels), C.POINTER(PackedBnbOpts), C.POINTER(PackedBnbResults),
                                        C.POINTER(Stats)]
+    L.lpx_solve_packed_bnb_dual.argtypes = [C.POINTER(PackedBnbDualModels), C.POINTER(PackedBnbOpts), C.POINTER(PackedBnbResults),
+                                            C.POINTER(Stats)]
+    L.lpx_solve_bnb_bounded_dual.argtypes = [C.POINTER(Problem), dp, dp, u8p, C.POINTER(SolveOpts), C.c_int64, C.c_int, C.c_int,
+                                             C.POINTER(Result), C.POINTER(BnbBoundedInfo)]
     L.lpx_solve_bnb_bounded8.argtypes =[C.POINTER(Problem), dp, dp, u8p, C.POINTER(SolveOpts), C.c_int64, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.POINTER(Result), C.POINTER(BnbBoundedInfo), C.POINTER(BnbDiversInfo),
                                          C.POINTER(BnbGuardInfo)]

@@ -1,6 +1,8 @@
 // host/bnb_bounded.cpp -- branch and bound by bound changes (include/lpx.h): three drivers around one frame.
 //   SolveBnbBounded   lpx_solve_bnb_bounded / _bounded2 / _bounded3: the root is SolveBounded keeping its handle, and every node after
 //                     it is ONE lpx_bounded_node (flagged search: lpx_bounded_node2 / _node3) call on that handle
+//   SolveBnbBoundedDual  lpx_solve_bnb_bounded_dual: the same search (SearchFromRoot) behind the root of SolveBoundedDual, for >= rows
+//                     and right-hand sides of either sign
 //   SolveBnbDivers    lpx_solve_bnb_bounded4 / 6 / 7 / 10: W handles, a round is ONE lpx_node_batch_run (_run_probe, _run2, _run3)
 //   SolveBnbPlunge    lpx_solve_bnb_bounded5: the same rounds with ONE lpx_node_batch_plunge, chains of up to D nodes
 // A node is its path of (var, lower, upper) overrides and what a call sends are the columns whose bounds differ from the bounds now
@@ -49,20 +51,30 @@ void ValidateBnbBounded(int n, const std::vector<double>& lower, const std::vect
         throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: search_flags holds a bit other than LPX_BDUAL_LONG_STEP and LPX_BDUAL_CUTOFF");
 }
 
+SimplexResult FinishBnbResult(SimplexResult res, const BnbBoundedInfo& info, const BoundedSession& ses, int n, double best,
+                              std::vector<double>& best_x);
+
 // The root: SolveBounded keeping its handle, the records reset, and -- where every node is on chip -- the fit of the root's shape,
 // which never changes and so decides for every node.  False: the root ends the search (an unbounded root is reported as that).
 bool SolveRoot(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper, const EngineOptions& opt,
                bool onchip, BoundedSession& ses, BoundedInfo& binfo, SimplexResult& res, BnbBoundedInfo& info,
-               BnbDiversInfo* dinfo = nullptr, BnbPlungeInfo* pinfo = nullptr, int root_form = -1, int max_spare = 0)
+               BnbDiversInfo* dinfo = nullptr, BnbPlungeInfo* pinfo = nullptr, int root_form = -1, int max_spare = 0,
+               bool dual_root = false, int search_flags = 0)   // dual_root: the root is the dual start (>= rows, any RHS sign)
 {
     EngineOptions ropt = opt; ropt.quiet = true;
-    res = SolveBounded(original, lower, upper, ropt, nullptr, &binfo, &ses, root_form, max_spare);
+    res = dual_root ? SolveBoundedDual(original, lower, upper, search_flags & LPX_BDUAL_LONG_STEP, ropt, nullptr, &binfo, &ses)
+                    : SolveBounded(original, lower, upper, ropt, nullptr, &binfo, &ses, root_form, max_spare);
     info = BnbBoundedInfo();
     if (dinfo) *dinfo = BnbDiversInfo();
     if (pinfo) *pinfo = BnbPlungeInfo();
     info.constant = ses.constant;
     res.Nodes = 0; res.LpSolves = 1;
     res.Aux = {0.0, 0.0, 0.0, 0.0};
+    if (dual_root && res.Status == LPX_INFEASIBLE) {    // the answer of a search that found no incumbent, without a node
+        std::vector<double> none;
+        res = FinishBnbResult(std::move(res), info, ses, original.NumVars(), -1.0 / 0.0, none);
+        return false;
+    }
     if (res.Status != LPX_OPTIMAL) return false;
     if (onchip) {
         int R = 0, C = 0;
@@ -188,22 +200,10 @@ void TakeIncumbent(lpx_tableau* h, int n, const std::vector<uint8_t>& is_int, do
     info.incumbents++;
 }
 
-}  // namespace
-
-SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
-                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
-                              int search_flags, int node_form)
+// The search of SolveBnbBounded and SolveBnbBoundedDual from a solved root on: one node call per popped node on the root's handle
+SimplexResult SearchFromRoot(SimplexResult res, BoundedSession& ses, const BoundedInfo& binfo, int n, const std::vector<uint8_t>& is_int,
+                             const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info, int search_flags, int node_form)
 {
-    const int n = original.NumVars();
-    ValidateBnbBounded(n, lower, upper, is_int, max_nodes, search_flags);
-    if (node_form != -1 && node_form != LPX_NODE_LAUNCHES && node_form != LPX_NODE_ONCHIP && node_form != LPX_NODE_AUTO)
-        throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: node_form is none of LPX_NODE_LAUNCHES, LPX_NODE_ONCHIP and LPX_NODE_AUTO");
-
-    BoundedSession ses;
-    BoundedInfo binfo;
-    SimplexResult res;
-    if (!SolveRoot(original, lower, upper, opt, node_form == LPX_NODE_ONCHIP, ses, binfo, res, info)) return res;
-
     // the handle's columns stand for x' = x - lower: root bounds [0, ub'] of every variable
     std::vector<double> root_lo((size_t)n, 0.0), root_ub(binfo.ub.begin(), binfo.ub.begin() + n);
     std::vector<double> cur_lo = root_lo, cur_ub = root_ub, nb_lo, nb_ub;
@@ -250,6 +250,44 @@ SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<doubl
     }
 
     return FinishBnbResult(std::move(res), info, ses, n, best, best_x);
+}
+
+}  // namespace
+
+SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
+                              const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
+                              int search_flags, int node_form)
+{
+    const int n = original.NumVars();
+    ValidateBnbBounded(n, lower, upper, is_int, max_nodes, search_flags);
+    if (node_form != -1 && node_form != LPX_NODE_LAUNCHES && node_form != LPX_NODE_ONCHIP && node_form != LPX_NODE_AUTO)
+        throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: node_form is none of LPX_NODE_LAUNCHES, LPX_NODE_ONCHIP and LPX_NODE_AUTO");
+
+    BoundedSession ses;
+    BoundedInfo binfo;
+    SimplexResult res;
+    if (!SolveRoot(original, lower, upper, opt, node_form == LPX_NODE_ONCHIP, ses, binfo, res, info)) return res;
+    return SearchFromRoot(std::move(res), ses, binfo, n, is_int, opt, max_nodes, info, search_flags, node_form);
+}
+
+// lpx_solve_bnb_bounded_dual: SolveBnbBounded whose root is the dual start of SolveBoundedDual, so >= rows, an = row as its pair and
+// right-hand sides of either sign are accepted.  A root that ends LPX_INFEASIBLE ends the search with the result of a search that
+// found no incumbent (Nodes = 0, LpSolves = 1).  From a solved root on it is SearchFromRoot unchanged.
+SimplexResult SolveBnbBoundedDual(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
+                                  const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
+                                  int search_flags, int node_form)
+{
+    const int n = original.NumVars();
+    ValidateBnbBounded(n, lower, upper, is_int, max_nodes, search_flags);
+    if (node_form != LPX_NODE_LAUNCHES && node_form != LPX_NODE_ONCHIP && node_form != LPX_NODE_AUTO)
+        throw LpxException(LPX_EINVAL, "Bounded Branch and Bound: node_form is none of LPX_NODE_LAUNCHES, LPX_NODE_ONCHIP and LPX_NODE_AUTO");
+
+    BoundedSession ses;
+    BoundedInfo binfo;
+    SimplexResult res;
+    if (!SolveRoot(original, lower, upper, opt, node_form == LPX_NODE_ONCHIP, ses, binfo, res, info, nullptr, nullptr, -1, 0, true, search_flags))
+        return res;
+    return SearchFromRoot(std::move(res), ses, binfo, n, is_int, opt, max_nodes, info, search_flags, node_form);
 }
 
 // The search by W divers (lpx_solve_bnb_bounded4, include/lpx.h): W handles in the state of the solved root, each with its own

@@ -401,8 +401,59 @@ void CheckPackedBnb(const lpx_packed_bnb_models* in, const lpx_packed_bnb_opts* 
         throw bad("too large: " + std::to_string(bytes) + " bytes of inputs, outputs, log and work slices, above 1 GiB (split the batch)");
 }
 
+// The argument checks of lpx_solve_packed_bnb_dual: CheckPackedBnb's list in its order with rel_stride among the strides, behind the
+// fit rule a shared rel (m reads; a per-model rel is checked by its workgroup), then the options and the 1 GiB rule, which counts rel.
+void CheckPackedBnbDual(const lpx_packed_bnb_dual_models* in, const lpx_packed_bnb_opts* opt, const lpx_packed_bnb_results* out,
+                        size_t (*work_bytes)(int count, int m, int n, int max_depth))
+{
+    auto bad = [](const std::string& msg) { return LpxException(LPX_EINVAL, "lpx_solve_packed_bnb_dual: " + msg); };
+    if (!in || !out) throw bad("null argument");
+    if (!in->c || !in->A || !in->b) throw bad("null c, A or b");
+    if (!out->status || !out->x || !out->value) throw bad("null status, x or value");
+    if (in->count < 1 || in->count > 65536) throw bad("count is outside [1, 65536]");
+    if (in->m < 1 || in->n < 1) throw bad("m and n must be at least 1");
+    if (in->sense != LPX_MAX && in->sense != LPX_MIN) throw bad("sense is neither LPX_MAX nor LPX_MIN");
+    const int64_t m = in->m, n = in->n, count = in->count;
+    const struct { const char* name; int64_t stride, packed; } strides[6] = {
+        {"c_stride", in->c_stride, n}, {"A_stride", in->A_stride, m * n}, {"b_stride", in->b_stride, m},
+        {"lower_stride", in->lower ? in->lower_stride : 0, n}, {"upper_stride", in->upper ? in->upper_stride : 0, n},
+        {"rel_stride", in->rel ? in->rel_stride : 0, m}};
+    for (const auto& s : strides)
+        if (s.stride != 0 && s.stride != s.packed)
+            throw bad(std::string(s.name) + " is neither 0 nor the packed size " + std::to_string(s.packed));
+    const int64_t R = m + 1, C = n + m + 1;
+    if (!lpx_packed_fits(in->m, in->n))
+        throw bad("the " + std::to_string(R) + " x " + std::to_string(C) + " tableau does not fit the on-chip form (lpx_packed_fits)");
+    if (in->rel && in->rel_stride == 0)
+        for (int64_t i = 0; i < m; ++i)
+            if (in->rel[i] != LPX_LE && in->rel[i] != LPX_GE)
+                throw bad("rel[" + std::to_string(i) + "] is neither LPX_LE nor LPX_GE (an = row is passed as its pair of rows)");
+    if (!opt) throw bad("null opts");
+    if (opt->search_flags & ~(LPX_BDUAL_LONG_STEP | LPX_BDUAL_CUTOFF))
+        throw bad("unknown flag: search_flags holds a bit other than LPX_BDUAL_LONG_STEP and LPX_BDUAL_CUTOFF");
+    if (opt->max_iter < 0) throw bad("max_iter is negative");
+    if (opt->max_nodes < 1) throw bad("max_nodes is below 1 (the budgets of a packed search are mandatory)");
+    if (opt->max_events < 1) throw bad("max_events is below 1 (the budgets of a packed search are mandatory)");
+    if (opt->max_depth < 0) throw bad("max_depth is negative");
+    if (opt->log_cap < 0) throw bad("log_cap is negative");
+    if (out->log && opt->log_cap == 0) throw bad("log is given but log_cap is 0");
+    if (!out->log && opt->log_cap > 0) throw bad("log_cap is positive but log is null");
+    auto models = [&](int64_t stride) { return stride == 0 ? (int64_t)1 : count; };
+    int64_t bytes = 8 * (n * models(in->c_stride) + m * n * models(in->A_stride) + m * models(in->b_stride));
+    if (in->lower) bytes += 8 * n * models(in->lower_stride);
+    if (in->upper) bytes += 8 * n * models(in->upper_stride);
+    if (in->rel) bytes += 4 * m * models(in->rel_stride);
+    if (in->is_int) bytes += n;
+    bytes += count * (4 + 8 * n + 8);
+    if (out->rec) bytes += count * (int64_t)sizeof(lpx_packed_bnb_record);
+    bytes += count * (int64_t)opt->log_cap * (int64_t)sizeof(lpx_bnb_node_log);
+    bytes += (int64_t)work_bytes(in->count, in->m, in->n, opt->max_depth);
+    if (bytes > ((int64_t)1 << 30))
+        throw bad("too large: " + std::to_string(bytes) + " bytes of inputs, outputs, log and work slices, above 1 GiB (split the batch)");
+}
+
 SimplexResult SolveBoundedDual(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper, int flags,
-                               const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info)
+                               const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info, BoundedSession* keep)
 {
     if (flags & ~(LPX_BDUAL_SKIP_FIXED | LPX_BDUAL_LONG_STEP))
         throw LpxException(LPX_EINVAL, "Bounded Dual Simplex: flags holds a bit other than LPX_BDUAL_SKIP_FIXED and LPX_BDUAL_LONG_STEP");
@@ -424,6 +475,12 @@ SimplexResult SolveBoundedDual(const LPProblem& original, const std::vector<doub
     finish_solve(th.h, st, original, lower, P, opt, [&dz](const int64_t* counts) {
         return "  dual start: " + std::to_string(dz[0]) + " dual-feasibility flips, " + std::to_string(counts[2]) + " passes\n";
     }, res, info);
+    if (keep) {                                      // as SolveBounded fills it; a dual start makes no spare capacity
+        keep->h = th.take(); keep->R = R; keep->C = C; keep->n = original.NumVars();
+        keep->min = original.ObjectiveSense == Sense::Min; keep->shifted = P.shifted; keep->constant = P.constant;
+        keep->lower = lower; keep->open_status = st; keep->opt = opt; keep->varNames = P.varNames;
+        keep->spare = 0;
+    }
     return res;
 }
 

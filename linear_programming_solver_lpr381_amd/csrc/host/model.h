@@ -245,9 +245,13 @@ void CheckPackedDual(const lpx_packed_dual_models* in, int flags, const lpx_run_
 // the argument checks of lpx_solve_packed_bnb, the same way; work_bytes is lpx::packed_bnb_work_bytes; the call itself is lpx::packed_bnb_solve
 void CheckPackedBnb(const lpx_packed_bnb_models* in, const lpx_packed_bnb_opts* opt, const lpx_packed_bnb_results* out,
                     size_t (*work_bytes)(int count, int m, int n, int max_depth));
+// the argument checks of lpx_solve_packed_bnb_dual, the same way (rel among them); the call itself is lpx::packed_bnb_dual_solve
+void CheckPackedBnbDual(const lpx_packed_bnb_dual_models* in, const lpx_packed_bnb_opts* opt, const lpx_packed_bnb_results* out,
+                        size_t (*work_bytes)(int count, int m, int n, int max_depth));
 // The dual start (lpx_solve_bounded_dual): >= rows and negative right-hand sides accepted, slack basis, dualize, lpx_bounded_dual_run3(flags)
 SimplexResult SolveBoundedDual(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper, int flags,
-                               const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info);
+                               const EngineOptions& opt, UpdatePivot updatePivot, BoundedInfo* info,
+                               BoundedSession* keep = nullptr);     // the handle kept as SolveBounded keeps it (no spare)
 // new absolute bounds of user variables vars[k] on a session: lpx_tableau_change_bounds + lpx_bounded_dual_run (lpx_bounded_set_bounds)
 SimplexResult BoundedSetBounds(BoundedSession& s, int K, const int32_t* vars, const double* lower, const double* upper);
 
@@ -263,6 +267,10 @@ SimplexResult SolveBnbBounded(const LPProblem& original, const std::vector<doubl
                               const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
                               int search_flags = 0,       // lpx_solve_bnb_bounded2: LPX_BDUAL_LONG_STEP / LPX_BDUAL_CUTOFF on every node
                               int node_form = -1);        // lpx_solve_bnb_bounded3: LPX_NODE_* of every node call; -1: the calls of _bounded / _bounded2
+// lpx_solve_bnb_bounded_dual: the same search behind the root of SolveBoundedDual (>= rows, right-hand sides of either sign)
+SimplexResult SolveBnbBoundedDual(const LPProblem& original, const std::vector<double>& lower, const std::vector<double>& upper,
+                                  const std::vector<uint8_t>& is_int, const EngineOptions& opt, int64_t max_nodes, BnbBoundedInfo& info,
+                                  int search_flags, int node_form);
 // The search by W divers (lpx_solve_bnb_bounded4): every node on chip, one lpx_node_batch_run per round.
 struct BnbDiversInfo { int64_t rounds = 0, steals = 0, largest_batch = 0; std::vector<int32_t> round, diver; };
 // Strong branching (lpx_solve_bnb_bounded6 with LPX_BRANCH_STRONG): SolveBnbDivers whose round is ONE lpx_node_batch_run_probe and

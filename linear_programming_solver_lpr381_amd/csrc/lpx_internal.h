@@ -195,6 +195,7 @@ struct PackedArena {
     bool attr = false;                                  // the function attribute of lpx_packed_primal_onchip is set
     bool attr_dual = false;                             // ... of lpx_packed_dual_onchip
     bool attr_bnb = false;                              // ... of lpx_packed_bnb_onchip
+    bool attr_bnb_dual = false;                         // ... of lpx_packed_bnb_dual_onchip
 };
 extern PackedArena g_packed;                            // defined in lpx_packed.hip
 // the packed batch by a dual start (lpx_packed_dual.hip): PackedParams plus rel (int32 [m] per model; a stride in int32, 0 = shared;
@@ -229,6 +230,23 @@ struct PackedBnbParams {
 int packed_bnb_solve(const lpx_packed_bnb_models* in, const lpx_packed_bnb_opts* opt, const lpx_packed_bnb_results* out, lpx_stats* st);
 // the device bytes of the work slices of such a call (host arithmetic, for the 1 GiB rule)
 size_t packed_bnb_work_bytes(int count, int m, int n, int max_depth);
+// the packed batch of integer programs by a dual start (lpx_packed_bnb_dual.hip): PackedBnbParams plus rel as PackedDualParams has it;
+// ratio_tol_root is that of the root's dual loop
+struct PackedBnbDualParams {
+    const double *c, *A, *b, *lower, *upper;
+    const int32_t* rel;
+    const uint8_t* mask;
+    int64_t c_stride, A_stride, b_stride, lower_stride, upper_stride, rel_stride;
+    int32_t m, n, min, max_iter, flags, max_depth, log_cap, pad;        // max_depth: resolved, at least 1
+    long long max_nodes, max_events;
+    double eps, ratio_tol_root, ratio_tol_node;
+    int32_t* status; double* x; double* value; lpx_packed_bnb_record* rec; lpx_bnb_node_log* log;   // as lpx_packed_bnb_results
+    long long* pivots;                                  // [count] kind-0 and kind-1 pivots of the root and of every node, for lpx_stats
+    char* work; int64_t work_stride;
+};
+// lpx_solve_packed_bnb_dual behind its argument checks: the same arena, the copies, the one launch, the one wait; its work slices
+// are those of packed_bnb_work_bytes
+int packed_bnb_dual_solve(const lpx_packed_bnb_dual_models* in, const lpx_packed_bnb_opts* opt, const lpx_packed_bnb_results* out, lpx_stats* st);
 
 // ---- lpx_kernels.hip: the two-launch select and update paths
 hipError_t launch_select(const SelParams& p, hipStream_t s);       // gather-based (dual path)

@@ -397,6 +397,14 @@ int lpx_solve_packed_bnb(const lpx_packed_bnb_models* in, const lpx_packed_bnb_o
     return packed_bnb_solve(in, opt, out, st);
 }
 
+int lpx_solve_packed_bnb_dual(const lpx_packed_bnb_dual_models* in, const lpx_packed_bnb_opts* opt, const lpx_packed_bnb_results* out,
+                              lpx_stats* st)
+{
+    try { CheckPackedBnbDual(in, opt, out, packed_bnb_work_bytes); }
+    catch (const LpxException& ex) { set_error(ex.what()); return ex.code; }
+    return packed_bnb_dual_solve(in, opt, out, st);
+}
+
 void lpx_bounded_info_free(lpx_bounded_info* info)
 {
     if (!info) return;
@@ -453,7 +461,8 @@ static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const do
                             int stall_events = -1, lpx_bnb_guard_info* ginfo = nullptr,                   // stall_events >= 0: lpx_solve_bnb_bounded7
                             int root_form = -1,                                                           // lpx_solve_bnb_bounded8: the root's form
                             const lpx_cut_opts* root_cuts = nullptr, lpx_bnb_cut_info* cinfo = nullptr,   // lpx_solve_bnb_bounded9: cuts at the root
-                            int tighten = 0, lpx_bnb_fix_info* finfo = nullptr)                           // lpx_solve_bnb_bounded10: reduced-cost tightening
+                            int tighten = 0, lpx_bnb_fix_info* finfo = nullptr,                           // lpx_solve_bnb_bounded10: reduced-cost tightening
+                            bool dual_root = false)                                                       // lpx_solve_bnb_bounded_dual: the root by the dual start
 {
     if (!p || !out) { set_error(std::string(what) + ": null argument"); return LPX_EINVAL; }
     std::memset(out, 0, sizeof(*out));
@@ -480,7 +489,8 @@ static int solve_bnb_bounded(const lpx_problem* p, const double* lower, const do
         BnbStrongInfo si;
         BnbGuardInfo gi;
         BnbFixInfo fi;
-        SimplexResult r = stall_events >= 0 ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di, nullptr, nullptr, stall_events, &gi, root_form,
+        SimplexResult r = dual_root ? SolveBnbBoundedDual(q, lo, up, mask, e, max_nodes, bi, search_flags, node_form)
+                        : stall_events >= 0 ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di, nullptr, nullptr, stall_events, &gi, root_form,
                                                              root_cuts, &ci, tighten, &fi)
                         : strong ? SolveBnbDivers(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, di, strong, &si)
                         : plunge ? SolveBnbPlunge(q, lo, up, mask, e, max_nodes, bi, search_flags, divers, plunge, di, pi)
@@ -539,6 +549,15 @@ int lpx_solve_bnb_bounded3(const lpx_problem* p, const double* lower, const doub
         return LPX_EINVAL;
     }
     return solve_bnb_bounded(p, lower, upper, is_int, o, max_nodes, search_flags, out, info, "lpx_solve_bnb_bounded3", node_form);
+}
+
+// node_form is checked by the driver, behind the bounds and the integer variables
+int lpx_solve_bnb_bounded_dual(const lpx_problem* p, const double* lower, const double* upper, const uint8_t* is_int,
+                               const lpx_solve_opts* o, int64_t max_nodes, int search_flags, int node_form, lpx_result* out,
+                               lpx_bnb_bounded_info* info)
+{
+    return solve_bnb_bounded(p, lower, upper, is_int, o, max_nodes, search_flags, out, info, "lpx_solve_bnb_bounded_dual", node_form, 0, nullptr,
+                             0, nullptr, nullptr, nullptr, -1, nullptr, -1, nullptr, nullptr, 0, nullptr, true);
 }
 
 int lpx_solve_bnb_bounded4(const lpx_problem* p, const double* lower, const double* upper, const uint8_t* is_int,

@@ -561,6 +561,26 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         search, Stop says which, Solution / OptimalValue are the incumbent so far or zeros), the root's UNBOUNDED, or the model's own
         LPX_EINVAL / LPX_E_NEG_RHS.  Each entry is bit-equal to SolveBnbBounded(model, ..., node_form="onchip", max_nodes=) wherever
         max_events and max_depth do not bind.  log_cap > 0: Log, the first log_cap node records of every model, and Logged."""
+        return self._solve_packed_bnb(False, c, A, b, None, upper, lower, integer, sense, long_step, cutoff, max_nodes, max_events,
+                                      max_iter, max_depth, log_cap, want)
+
+    def SolvePackedBnbDual(self, c, A, b, rel, upper, lower=None, integer=None, sense="max", long_step: bool = False,
+                           cutoff: bool = False, max_nodes: int = 100000, max_events: int = 2000000, max_iter=None,
+                           max_depth: int = 0, log_cap: int = 0, want=("rec",)) -> PackedBnbResult:
+        """SolvePackedBnb from a dual start (lpx_solve_packed_bnb_dual): B small integer programs of ONE shape whose rows are <= or
+        >= and whose right-hand sides may have either sign, in ONE kernel launch -- covering models, rows of both senses, an = row as
+        its pair, right-hand-side sweeps across zero.  rel: None (every row <=), (m,) shared by every model or (B, m), as
+        SolvePackedDual takes it; everything else is SolvePackedBnb's.  Status per model: OPTIMAL, INFEASIBLE (Stop "root": the root
+        LP is infeasible, Nodes 0; Stop "done": the search ran empty without an incumbent), ITER_LIMIT, or the model's own
+        LPX_EINVAL (its bounds, an integer variable's bounds, a bad entry of its own rel row, or a continuous variable that
+        improves the objective and has no upper bound).  Each entry is bit-equal to SolveBnbBoundedDual(model, ...,
+        node_form="onchip", max_nodes=) wherever max_events and max_depth do not bind."""
+        return self._solve_packed_bnb(True, c, A, b, rel, upper, lower, integer, sense, long_step, cutoff, max_nodes, max_events,
+                                      max_iter, max_depth, log_cap, want)
+
+    def _solve_packed_bnb(self, dual, c, A, b, rel, upper, lower, integer, sense, long_step, cutoff, max_nodes, max_events, max_iter,
+                          max_depth, log_cap, want) -> PackedBnbResult:
+        """lpx_solve_packed_bnb, or with dual lpx_solve_packed_bnb_dual: the same call shape plus rel."""
         want = tuple(want)
         for w in want:
             if w not in ("rec",):
@@ -573,7 +593,7 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         limit = 10000 if limit is None else int(limit)
         if limit < 0:
             raise ValueError("max_iter must not be negative")
-        sense, c, A, b, bounds, _, B, m, n = _packed_inputs(c, A, b, upper, lower, sense)
+        sense, c, A, b, bounds, rel, B, m, n = _packed_inputs(c, A, b, upper, lower, sense, rel)
         mask = None
         if integer is not None:
             mask = np.ascontiguousarray(np.asarray(integer)).astype(np.uint8)
@@ -582,7 +602,7 @@ class LPSolver:             # Models/LPSolver.cs:6-77
 
         def _stride(v, nd, packed):
             return packed if v.ndim == nd else 0
-        pm = _lib.PackedBnbModels()
+        pm = _lib.PackedBnbDualModels() if dual else _lib.PackedBnbModels()
         pm.count, pm.m, pm.n, pm.sense = B, m, n, int(sense)
         pm.c, pm.A, pm.b = (v.ctypes.data_as(_lib.dp) for v in (c, A, b))
         pm.c_stride, pm.A_stride, pm.b_stride = _stride(c, 2, n), _stride(A, 3, m * n), _stride(b, 2, m)
@@ -593,6 +613,8 @@ class LPSolver:             # Models/LPSolver.cs:6-77
                 setattr(pm, name + "_stride", _stride(v, 2, n))
         if mask is not None:
             pm.is_int = mask.ctypes.data_as(C.POINTER(C.c_uint8))
+        if dual and rel is not None:
+            pm.rel, pm.rel_stride = rel.ctypes.data_as(_lib.ip), _stride(rel, 2, m)
         po = _lib.PackedBnbOpts((_lib.BDUAL_LONG_STEP if long_step else 0) | (_lib.BDUAL_CUTOFF if cutoff else 0), limit,
                                 int(max_depth), int(log_cap), int(max_nodes), int(max_events))
         status = np.zeros(B, dtype=np.int32); x = np.zeros((B, n)); value = np.zeros(B)
@@ -606,7 +628,8 @@ class LPSolver:             # Models/LPSolver.cs:6-77
             log = np.zeros((B, int(log_cap)), dtype=BNB_LOG_DTYPE)
             pr.log = log.ctypes.data_as(C.POINTER(_lib.BnbNodeLog))
         st = _lib.Stats()
-        rc = lib().lpx_solve_packed_bnb(C.byref(pm), C.byref(po), C.byref(pr), C.byref(st))
+        call = lib().lpx_solve_packed_bnb_dual if dual else lib().lpx_solve_packed_bnb
+        rc = call(C.byref(pm), C.byref(po), C.byref(pr), C.byref(st))
         if rc != 0:
             raise SolverException(rc, _lib.last_error())
         res = PackedBnbResult(Status=status, Solution=x, OptimalValue=value, Stats=st.as_dict())
@@ -879,6 +902,55 @@ class LPSolver:             # Models/LPSolver.cs:6-77
             res.BnbRound, res.BnbDiver = rounds, who
         if plunge is not None:
             res.BnbStep = step
+        if rc != 0:
+            e = SolverException(rc, msg)
+            e.result = res
+            raise e
+        return res
+
+    def SolveBnbBoundedDual(self, problem: LPProblem, upper, lower=None, integer=None, max_nodes: int = 0, long_step: bool = False,
+                            cutoff: bool = False, node_form: Optional[str] = None) -> SimplexResult:
+        """SolveBnbBounded whose root is the dual start of SolveBoundedDual (lpx_solve_bnb_bounded_dual): >= rows, an = row as its
+        pair and right-hand sides of either sign are accepted -- covering models, rows of both senses.  The arguments, the result,
+        BnbInfo, BnbLog and the limits are SolveBnbBounded's for node_form ("launches", the default, "onchip" or "auto"; the node
+        logs of "launches" and "onchip" are bit-equal).  A root LP that is infeasible gives Status INFEASIBLE with Nodes 0; so can a
+        search that runs empty without an incumbent.  A continuous variable that improves the objective needs a finite upper bound."""
+        if node_form is None:
+            node_form = "launches"
+        if node_form not in _lib.NODE_FORMS:
+            raise ValueError(f"unknown node form {node_form!r}")
+        n = problem.NumVars
+        o, keep = _solve_opts(self.engine)
+        ps, hold = _problem_struct(problem)
+
+        def _vec(v):
+            if v is None:
+                return None, None
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)))
+            return a, a.ctypes.data_as(_lib.dp)
+        lo, lop = _vec(lower)
+        up, upp = _vec(upper)
+        mask, mp = None, None
+        if integer is not None:
+            mask = np.ascontiguousarray(np.broadcast_to(np.asarray(integer, dtype=np.uint8), (n,)))
+            mp = mask.ctypes.data_as(C.POINTER(C.c_uint8))
+        r, info = _lib.Result(), _lib.BnbBoundedInfo()
+        flags = (_lib.BDUAL_LONG_STEP if long_step else 0) | (_lib.BDUAL_CUTOFF if cutoff else 0)
+        rc = lib().lpx_solve_bnb_bounded_dual(C.byref(ps), lop, upp, mp, C.byref(o), int(max_nodes), flags, _lib.NODE_FORMS[node_form],
+                                              C.byref(r), C.byref(info))
+        if rc != 0 and rc != _lib.ITER_LIMIT:
+            raise SolverException(rc, _lib.last_error())
+        msg = _lib.last_error() if rc else ""
+        try:
+            log = np.zeros(info.n_log, dtype=BNB_LOG_DTYPE)
+            if info.n_log:
+                C.memmove(log.ctypes.data, info.log, info.n_log * C.sizeof(_lib.BnbNodeLog))
+            counters = {k: getattr(info, k) for k in ("nodes", "events", "flips", "incumbents", "pruned_bound",
+                                                      "pruned_infeasible", "max_K", "constant")}
+        finally:
+            lib().lpx_bnb_bounded_info_free(C.byref(info))
+        res = _take_result(r, n)
+        res.BnbLog, res.BnbInfo = log, counters
         if rc != 0:
             e = SolverException(rc, msg)
             e.result = res

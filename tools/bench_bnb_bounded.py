@@ -88,7 +88,13 @@ and 4096 right-hand sides of one 9 x 29 binary model as ONE SolvePackedBnb call 
 SolveBnbBounded(node_form="onchip") calls, host wall of whole calls, the sides alternating in one process, one untimed round first,
 REPS (default 7; 2 at 4096) timed rounds, the results asserted equal; then one model alone against the sequential driver and
 divers=4,16,64; then binary_ip(60, 12) alone against the sequential on-chip driver, as time per node.  A side wins iff its median lies
-below the other's minimum.  `--packed-trace` makes four packed calls and the binary_ip(60, 12) call for a kernel trace."""
+below the other's minimum.  `--packed-trace` makes four packed calls and the binary_ip(60, 12) call for a kernel trace.
+
+`--compare-packed-dual [--flag-sets NAME] [REPS]` measures the packed branch and bound from a dual start
+(lpx_solve_packed_bnb_dual) the same way: 256 and 4096 right-hand sides of one 8 x 16 covering model (Min c.x,
+A x >= b over binaries) as ONE SolvePackedBnbDual call against the same models as single SolveBnbBoundedDual(node_form="onchip")
+calls, the results asserted equal; then, on the <= family of --compare-packed, which both packed calls accept, SolvePackedBnbDual
+against SolvePackedBnb: what the dual root costs or saves where the primal one would do.  No time or ratio is promised."""
 import json
 import os
 import statistics
@@ -654,6 +660,62 @@ def compare_packed(reps, counts, big_reps, widths, kw_name="plain"):
     return out
 
 
+def cover_family(m, n, count, seed=3):
+    """count right-hand sides of ONE covering model (Min c.x, A x >= b, binaries): A = integers(1, 9), c = integers(1, 12),
+    b_i = floor(U(0.3, 0.5) rowsum) -- (c, A [m, n], bs [count, m])."""
+    g = np.random.default_rng(seed)
+    A = g.integers(1, 9, (m, n)).astype(np.float64)
+    c = g.integers(1, 12, n).astype(np.float64)
+    bs = np.floor(A.sum(axis=1) * g.uniform(0.3, 0.5, size=(count, m)))
+    return c, A, bs
+
+
+def compare_packed_dual(reps, counts, big_reps, kw_name="plain"):
+    """The packed branch and bound from a dual start (lpx_solve_packed_bnb_dual) against the same covering
+    models as single SolveBnbBoundedDual(node_form="onchip") calls, as compare_packed measures; then against SolvePackedBnb on a
+    family of <= models that both accept."""
+    S = L.LPSolver()
+    kw = FLAG_SETS[kw_name]
+    out = {"flags": kw_name, "families": {}}
+    m, n = 8, 16
+    rel = np.ones(m, dtype=np.int32)
+    for count in counts:
+        c, A, bs = cover_family(m, n, count)
+        probs = [L.LPProblem.from_arrays(1, c, A, [1] * m, bs[i]) for i in range(count)]
+        r = big_reps if count > 1024 else reps
+        ts = {"packed": [], "single": []}
+        for i in range(r + 1):
+            t0 = time.perf_counter()
+            pk = S.SolvePackedBnbDual(c, A, bs, rel, 1.0, sense="min", **kw)
+            t1 = time.perf_counter()
+            ones = [S.SolveBnbBoundedDual(p, 1.0, node_form="onchip", **kw) for p in probs]
+            t2 = time.perf_counter()
+            if i >= 1:
+                ts["packed"].append(1e3 * (t1 - t0)); ts["single"].append(1e3 * (t2 - t1))
+        assert pk.Status.tolist() == [o.Status for o in ones] and (pk.Stop <= 1).all()
+        assert pk.Nodes.tolist() == [o.Nodes for o in ones]
+        assert all(pk.OptimalValue[i] == o.OptimalValue and (o.Status != 0 or np.array_equal(pk.Solution[i], o.Solution))
+                   for i, o in enumerate(ones))
+        nodes = max(1, int(pk.Nodes.sum()))
+        d = {k: stats(v) for k, v in ts.items()}
+        d.update(count=count, shape=[m + 1, n + m + 1], nodes=int(pk.Nodes.sum()), events=int(pk.Info["events"].sum()),
+                 root_events=int(pk.Info["root_events"].sum()), infeasible=int((pk.Status == 2).sum()),
+                 max_nodes_of_a_model=int(pk.Nodes.max()), deepest=int(pk.Info["deepest"].max()), kernel_ms=pk.Stats["loop_ms"],
+                 us_per_node_packed=1e3 * statistics.median(ts["packed"]) / nodes, us_per_node_single=1e3 * statistics.median(ts["single"]) / nodes,
+                 packed_wins=bool(d["packed"]["median"] < d["single"]["min"]), single_wins=bool(d["single"]["median"] < d["packed"]["min"]))
+        out["families"][str(count)] = d
+    # a family both packed calls accept (every row <=, b >= 0): the dual root against the primal root, the searches behind them
+    c, A, bs = rhs_family(20, 8, 256)
+    sides = {"dual_root": lambda: S.SolvePackedBnbDual(c, A, bs, None, 1.0, **kw), "primal_root": lambda: S.SolvePackedBnb(c, A, bs, 1.0, **kw)}
+    d = alternate(sides, reps)
+    a, b = sides["dual_root"](), sides["primal_root"]()
+    assert a.Status.tolist() == b.Status.tolist() and np.array_equal(a.OptimalValue, b.OptimalValue)
+    d.update(count=256, nodes_dual_root=int(a.Nodes.sum()), nodes_primal_root=int(b.Nodes.sum()),
+             root_events_dual=int(a.Info["root_events"].sum()), root_events_primal=int(b.Info["root_events"].sum()))
+    out["le_family"] = d
+    return out
+
+
 def alternate(sides, reps):
     """Host wall in ms of every side, the sides alternating in one process, one untimed round first; a side wins against another iff
     its median lies below the other's minimum."""
@@ -679,6 +741,17 @@ def main():
         c, A, rel, b = synth.binary_ip(60, 12)
         r = L.LPSolver().SolvePackedBnb(c, np.ascontiguousarray(A[:12]), b[:12], 1.0, max_nodes=1000000, max_events=100000000)
         print(json.dumps({"bip_60x12_nodes": int(r.Nodes[0]), "status": int(r.Status[0]), "loop_ms": r.Stats["loop_ms"]}))
+        return
+    if "--compare-packed-dual" in args:
+        args.remove("--compare-packed-dual")
+        flag_set = "plain"
+        if "--flag-sets" in args:
+            j = args.index("--flag-sets")
+            flag_set = args[j + 1]
+            del args[j:j + 2]
+        reps = int(args[0]) if args else 7
+        L._lib.check(L._lib.lib().lpx_init(0))
+        print(json.dumps(compare_packed_dual(reps, [256, 4096], 2, flag_set)))
         return
     if "--compare-packed" in args:
         args.remove("--compare-packed")

@@ -1,7 +1,7 @@
 // lpx_cli -- Linux stand-in for the reference's WinForms host (Form1.cs), over the C ABI of liblpx.so only.
 //
 //   lpx_cli [--algorithm NAME] [--repaired] [--iterations] [--ranging] [--cuts-per-round K] [--cut-rounds N]
-//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S] [--root-form F] [--root-cuts N [--cuts-per-round K]] [--tighten]] [--bounded-form F] [--bounded [--rhs-file F]] [--bounded-dual [--long-step] --rhs-file F] [--binary --bnb-bounded [--long-step] [--cutoff] --rhs-file F] [--export FILE] INPUT.txt
+//           [--set-rhs I=V]... [--set-cost J=V]... [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S] [--root-form F] [--root-cuts N [--cuts-per-round K]] [--tighten]] [--bounded-form F] [--bounded [--rhs-file F]] [--bounded-dual [--long-step] --rhs-file F] [--binary --bnb-bounded [--long-step] [--cutoff] --rhs-file F] [--bnb-bounded --dual-root [--long-step] [--cutoff] [--node-form F | --rhs-file F]] [--export FILE] INPUT.txt
 //
 // Does what Form1 does around the solvers: reads the model text (Import, Form1.cs:284-296), parses it with the LPParser
 // grammar (lpx_parse_text, Models/LPParser.cs:9-79), runs the algorithm chosen by its dropdown name (btnSolve_Click,
@@ -17,7 +17,9 @@
 // line "status value x1 .. xn" per right-hand side.  --bounded-dual [--long-step] --rhs-file F does the same by the dual start
 // (lpx_solve_packed_dual): >= rows and negative right-hand sides are accepted, an = row is refused.  --bnb-bounded --rhs-file F (with
 // --binary or --upper bounds, and --long-step / --cutoff) solves the model as an integer program once per line of F as ONE packed
-// call (lpx_solve_packed_bnb): a whole branch and bound per right-hand side in one kernel launch, the same line per run.  There is no CPU fallback: without a gfx950 device the solve fails with LPX_EDEVICE.
+// call (lpx_solve_packed_bnb): a whole branch and bound per right-hand side in one kernel launch, the same line per run.
+// --bnb-bounded --dual-root runs the search from a dual start (lpx_solve_bnb_bounded_dual; with --rhs-file F lpx_solve_packed_bnb_dual):
+// >= rows and negative right-hand sides are accepted, an = row is refused under --rhs-file.  There is no CPU fallback: without a gfx950 device the solve fails with LPX_EDEVICE.
 #include <cstdio>
 #include <cstdlib>
 #include <cctype>
@@ -83,6 +85,7 @@ int main(int argc, char** argv)
     bool repaired = false, iterations = false, ranging = false, cut_set = false, algo_set = false, binary = false, bnb_bounded = false;
     bool bounded_flag = false;  // --bounded: the bounded primal simplex even without a bound
     std::string rhs_file;       // --rhs-file F beside --bounded: one packed call (lpx_solve_packed), a right-hand side per line of F
+    bool dual_root = false;     // --dual-root beside --bnb-bounded: the search from a dual start (lpx_solve_bnb_bounded_dual; with --rhs-file lpx_solve_packed_bnb_dual)
     bool bounded_dual = false;  // --bounded-dual beside --rhs-file: that packed call by the dual start (lpx_solve_packed_dual)
     int search_flags = 0;       // --long-step / --cutoff beside --bnb-bounded
     int node_form = -1;         // --node-form beside --bnb-bounded: LPX_NODE_*; -1 = not given
@@ -108,6 +111,7 @@ int main(int argc, char** argv)
         else if (a == "--bnb-bounded") bnb_bounded = true;
         else if (a == "--bounded") bounded_flag = true;
         else if (a == "--bounded-dual") bounded_dual = true;
+        else if (a == "--dual-root") dual_root = true;
         else if (a == "--rhs-file" && i + 1 < argc) rhs_file = argv[++i];
         else if (a == "--long-step") search_flags |= LPX_BDUAL_LONG_STEP;
         else if (a == "--cutoff") search_flags |= LPX_BDUAL_CUTOFF;
@@ -207,6 +211,7 @@ int main(int argc, char** argv)
                         "               [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S] [--root-form F] [--root-cuts N [--cuts-per-round K]] [--tighten]] [--bounded-form F]\n"
                         "               [--bounded [--rhs-file F]] [--bounded-dual [--long-step] --rhs-file F] [--export FILE] INPUT.txt\n"
                         "               [--binary --bnb-bounded [--long-step] [--cutoff] --rhs-file F]\n"
+                        "               [--bnb-bounded --dual-root [--long-step] [--cutoff] [--node-form F | --rhs-file F]]\n"
                         "  NAME: Primal Simplex | Revised Primal Simplex | Dual Simplex | Branch and Bound |\n"
                         "        Revised Branch and Bound | Branch and Bound Knapsack | Cutting Plane | Revised Cutting Plane |\n"
                         "        GMI Cutting Plane (gmi) | Bounded Primal Simplex\n"
@@ -243,6 +248,9 @@ int main(int argc, char** argv)
                         "  --bnb-bounded --rhs-file F: the model as an integer program once per line of F as ONE packed call (lpx_solve_packed_bnb:\n"
                         "             a whole branch and bound per right-hand side in one kernel launch; at most 100000 nodes and 2000000 events\n"
                         "             per run); with --binary or --upper bounds and --long-step / --cutoff; the same line per run\n"
+                        "  --dual-root: with --bnb-bounded, the search from a dual start (lpx_solve_bnb_bounded_dual): >= constraints and negative\n"
+                        "             right-hand sides are accepted; with --long-step / --cutoff / --node-form and the bound flags only.  With\n"
+                        "             --rhs-file F the packed call lpx_solve_packed_bnb_dual, a line per right-hand side; an = constraint is refused\n"
                         "  --root-cuts N: with --bnb-bounded --divers, cut-and-branch (lpx_solve_bnb_bounded9): up to N rounds of --cuts-per-round K\n"
                         "             (default 8) GMI cuts at the solved root, then the search from that tableau; not with --plunge or --branching\n"
                         "  --root-form launches|onchip|auto: with --bnb-bounded --divers, how the root LP is solved (lpx_solve_bnb_bounded8);\n"
@@ -260,6 +268,13 @@ int main(int argc, char** argv)
         const std::string key = algorithm_key(algorithm);
         if (key != "gmi cutting plane" && key != "gmi") { std::fprintf(stderr, "lpx_cli: --cuts-per-round / --cut-rounds need --algorithm \"GMI Cutting Plane\"\n"); return 64; }
         if (ranging) { std::fprintf(stderr, "lpx_cli: --ranging does not combine with --cuts-per-round / --cut-rounds\n"); return 64; }
+    }
+    if (dual_root && (!bnb_bounded || bounded_flag || bounded_dual || divers || plunge || branching >= 0 || stall_events >= 0 || root_form >= 0 ||
+                      root_cuts >= 0 || tighten || bounded_form >= 0 || iterations || ranging || repaired || cut_set || algo_set || !edits.empty() ||
+                      !exportPath.empty() || (!rhs_file.empty() && node_form >= 0))) {
+        std::fprintf(stderr, "lpx_cli: --dual-root needs --bnb-bounded and combines only with --long-step / --cutoff, --node-form (without --rhs-file), "
+                             "--rhs-file and --upper / --lower / --binary\n");
+        return 64;
     }
     const bool bounded = binary || !bounds.empty() || bounded_flag || bounded_dual;
     const bool packed_bnb = bnb_bounded && !rhs_file.empty() && !bounded_dual && !bounded_flag;     // --bnb-bounded --rhs-file F
@@ -338,6 +353,11 @@ int main(int argc, char** argv)
     if (!rhs_file.empty()) {
         // one packed call: a right-hand side per line, everything else shared at stride 0
         for (int i = 0; i < p.m; ++i) {
+            if (dual_root && p.rel[i] == LPX_EQ) {
+                std::fprintf(stderr, "lpx_cli: --dual-root --rhs-file: an = constraint is not accepted (pass it as its <= and >= pair)\n");
+                lpx_parsed_free(&p); return 65;
+            }
+            if (dual_root) continue;
             if (bounded_dual && p.rel[i] == LPX_EQ) {
                 std::fprintf(stderr, "lpx_cli: --bounded-dual --rhs-file: an = constraint is not accepted (pass it as its <= and >= pair)\n");
                 lpx_parsed_free(&p); return 65;
@@ -375,6 +395,13 @@ int main(int argc, char** argv)
             bo.max_nodes = 100000; bo.max_events = 2000000;
             lpx_packed_bnb_results br; std::memset(&br, 0, sizeof br);
             br.status = status.data(); br.x = x.data(); br.value = value.data();
+            if (dual_root) {                            // the same call from a dual start: rel too at stride 0
+                lpx_packed_bnb_dual_models dm; std::memset(&dm, 0, sizeof dm);
+                dm.count = count; dm.m = p.m; dm.n = p.n; dm.sense = p.sense;
+                dm.c = p.c; dm.A = p.A; dm.b = rhs.data(); dm.lower = lo.data(); dm.upper = up.data(); dm.rel = p.rel;
+                dm.b_stride = p.m;
+                prc = lpx_solve_packed_bnb_dual(&dm, &bo, &br, nullptr);
+            } else
             prc = lpx_solve_packed_bnb(&bm, &bo, &br, nullptr);
         } else if (bounded_dual) {                             // c, A, rel and the bounds: stride 0, one copy for every run
             lpx_packed_dual_models dm; std::memset(&dm, 0, sizeof dm);
@@ -415,6 +442,7 @@ int main(int argc, char** argv)
                                                                          probe_iter >= 0 ? probe_iter : o.max_iter > 0 ? o.max_iter : 10000, &r, nullptr, nullptr, nullptr)
                  : bnb_bounded && plunge ? lpx_solve_bnb_bounded5(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, plunge, &r, nullptr, nullptr, nullptr)
                  : bnb_bounded && divers ? lpx_solve_bnb_bounded4(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, divers, &r, nullptr, nullptr)
+                 : bnb_bounded && dual_root ? lpx_solve_bnb_bounded_dual(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, node_form >= 0 ? node_form : LPX_NODE_LAUNCHES, &r, nullptr)
                  : bnb_bounded && node_form >= 0 ? lpx_solve_bnb_bounded3(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, node_form, &r, nullptr)
                  : bnb_bounded && search_flags ? lpx_solve_bnb_bounded2(&prob, lo.data(), up.data(), nullptr, &o, 0, search_flags, &r, nullptr)
                  : bnb_bounded ? lpx_solve_bnb_bounded(&prob, lo.data(), up.data(), nullptr, &o, 0, &r, nullptr)
