@@ -1428,6 +1428,58 @@ typedef struct lpx_packed_dual_results { /* caller-allocated; each of the last f
 int lpx_solve_packed_dual(const lpx_packed_dual_models* in, int flags, const lpx_run_opts* o /* or NULL */,
                           const lpx_packed_dual_results* out, lpx_stats* st /* or NULL */);
 
+/* ---- packed right-hand-side scenarios warm-started from one solved base (csrc/lpx_packed_warm.hip) ----
+ *
+ * The commonest packed batch is count right-hand sides of ONE model.  lpx_packed_base_open solves that model once for a base
+ * right-hand side and keeps the solved tableau on the device; lpx_packed_base_solve then re-solves count right-hand sides in ONE
+ * launch, every workgroup continuing the dual loop from the base's optimal basis.  After any pivots, complements and bound flips the
+ * RHS column of a tableau is an affine function of the internal b whose linear part is the slack block (columns n .. n+m-1), so a new
+ * right-hand side costs one (m+1) x m product and leaves the objective row, and with it dual feasibility, untouched.
+ *
+ * lpx_packed_base_open(in, flags, o, base_out, &h) performs, for the base model, exactly steps 1-5 of lpx_solve_packed_dual;
+ * base_out (or NULL), the results structure of that call for count = 1, is bit-equal to lpx_solve_packed_dual with count = 1.  In an
+ * allocation that the handle owns it keeps on the device: the solved tile, the bounds ub, the basis and the flip bytes, the user's b
+ * and rel, the lower bounds and the shift constant.  The fit rule is lpx_packed_fits(m, n).  flags is 0 or LPX_BDUAL_LONG_STEP.  It
+ * returns 0 and a handle only when the base ends LPX_OPTIMAL; otherwise it returns that status (LPX_INFEASIBLE, LPX_ITER_LIMIT, or
+ * LPX_EINVAL for a model its workgroup refuses) and *h = NULL.  LPX_EINVAL before any device check, the outputs untouched (*h is set
+ * to NULL wherever h is given), every message starting "lpx_packed_base_open: ": a NULL in or h; then the list of
+ * lpx_solve_packed_dual in its order for count = 1 and shared arrays (a NULL c, A or b; with base_out given, a NULL status, x or
+ * value; m or n below 1; the sense; the fit rule; resident = 1; more than 1 GiB; a rel entry that is neither LPX_LE nor LPX_GE; an
+ * unknown flag).  No device: LPX_EDEVICE.
+ *
+ * lpx_packed_base_solve(h, count, b, flags, o, out, st) makes one upload of b ([count][m], the user's right-hand sides), ONE launch
+ * of count workgroups, one read-back and one wait, on the arena and the stream of lpx_solve_packed.  Workgroup i
+ *   1. copies the base's tile and ub into LDS, the basis and the flip bytes into its own slices;
+ *   2. forms delta_k = b_i[k] - b0[k], negated for a >= row; a b_i[k] that is not finite refuses the scenario (LPX_EINVAL: its
+ *      outputs zeroed, a record of zeros around the status);
+ *   3. updates the RHS column: for every row r = 0 .. m, the objective row included,
+ *          acc = T[r][C-1];  for k = 0 .. m-1 ascending with delta_k != 0.0:  prod = T[r][n+k] * delta_k;  acc = acc + prod
+ *      (one multiply and one add, separately rounded; no other arithmetic: an all-zero delta leaves every bit as the base left it);
+ *   4. runs the dual loop of lpx_bounded_dual_run3(flags) from the base's basis with o's eps, ratio_tol and max_iter
+ *      (NULL: lpx_default_opts(o, 1)) and this call's flags (0 or LPX_BDUAL_LONG_STEP);
+ *   5. extracts x, value, the record, the basis, at_upper, y and d exactly as lpx_solve_packed_dual does; in the record
+ *      dualize_flips = 0 and events counts this scenario's loop only.
+ * status[i]: LPX_OPTIMAL, LPX_INFEASIBLE, LPX_ITER_LIMIT (the limit is tested first, as in the loop) or LPX_EINVAL.  The results do
+ * not depend on count, on i or on the other scenarios.  The handle is only read: several solves may follow one open, and several
+ * handles may be open at once.  Per-scenario bounds or costs are not offered.  st (or NULL) as in lpx_solve_packed_dual.
+ * LPX_EINVAL before any device check, the outputs untouched, every message starting "lpx_packed_base_solve: ": a NULL h, b or out;
+ * a NULL status, x or value; count outside [1, 65536]; an unknown flag; resident = 1; more than 1 GiB of input plus output bytes.
+ * No device: LPX_EDEVICE.
+ *
+ * lpx_packed_base_close(h) frees the device allocation and the handle; NULL is allowed.  Returns 0. */
+typedef struct lpx_packed_base lpx_packed_base;            /* opaque */
+typedef struct lpx_packed_base_model {
+    int32_t m, n, sense;
+    const double *c, *A, *b;           /* [n], [m][n] row-major, [m]: b is the base right-hand side */
+    const double *lower, *upper;       /* [n] or NULL (0 / +inf) */
+    const int32_t* rel;                /* [m] of LPX_LE / LPX_GE, or NULL = every row is <= */
+} lpx_packed_base_model;
+int lpx_packed_base_open(const lpx_packed_base_model* in, int flags, const lpx_run_opts* o /* or NULL */,
+                         const lpx_packed_dual_results* base_out /* or NULL: count = 1 */, lpx_packed_base** h);
+int lpx_packed_base_solve(const lpx_packed_base* h, int32_t count, const double* b /* [count][m] */, int flags,
+                          const lpx_run_opts* o /* or NULL */, const lpx_packed_dual_results* out, lpx_stats* st /* or NULL */);
+int lpx_packed_base_close(lpx_packed_base* h);             /* NULL is allowed */
+
 /* ---- packed batches of small integer programs: a whole branch and bound per workgroup (csrc/lpx_packed_bnb.hip, DESIGN.md
  * section 4.27) ---------------------------------------------------------------------------------------------------------------
  *

@@ -201,6 +201,15 @@ namespace Linear_Programming_Solver.Native
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct LpxPackedBaseModel      // lpx_packed_base_model: the one model of lpx_packed_base_open
+    {
+        public int m, n, sense;
+        public double* c, A, b;                  // [n], [m][n] row-major, [m]: b is the base right-hand side
+        public double* lower, upper;             // [n] or null (0 / +inf)
+        public int* rel;                         // [m] of LPX_LE (0) / LPX_GE (1), or null = every row is <=
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public unsafe struct LpxPackedBnbModels      // lpx_packed_bnb_models: lpx_packed_models plus the integer mask
     {
         public int count, m, n, sense;           // every row is <=
@@ -550,6 +559,15 @@ namespace Linear_Programming_Solver.Native
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_solve_packed_dual(ref LpxPackedDualModels models, int flags, IntPtr opts, ref LpxPackedDualResults results,
                                                        LpxStats* st);
+        // right-hand-side scenarios warm-started from one solved base: open keeps the solved tableau on the device (handle: an opaque
+        // pointer, null unless the base ends LPX_OPTIMAL; baseOut may be null), solve re-solves count right-hand sides ([count][m]) in ONE launch
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_packed_base_open(ref LpxPackedBaseModel model, int flags, IntPtr opts, LpxPackedDualResults* baseOut,
+                                                      out IntPtr handle);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_packed_base_solve(IntPtr handle, int count, double* b, int flags, IntPtr opts, ref LpxPackedDualResults results,
+                                                       LpxStats* st);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int lpx_packed_base_close(IntPtr handle);
         // packed batches of small integer programs: the whole branch and bound of every model in ONE launch
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_solve_packed_bnb(ref LpxPackedBnbModels models, ref LpxPackedBnbOpts opts, ref LpxPackedBnbResults results,

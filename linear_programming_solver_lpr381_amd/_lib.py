@@ -231,6 +231,12 @@ class PackedDualResults(C.Structure):
                 ("at_upper", C.POINTER(C.c_uint8)), ("y", dp), ("d", dp)]
 
 
+class PackedBaseModel(C.Structure):
+    """lpx_packed_base_model (include/lpx.h): the one model of lpx_packed_base_open; b is the base right-hand side."""
+    _fields_ = [("m", C.c_int32), ("n", C.c_int32), ("sense", C.c_int32), ("c", dp), ("A", dp), ("b", dp), ("lower", dp), ("upper", dp),
+                ("rel", ip)]
+
+
 PBNB_DONE, PBNB_ROOT, PBNB_NODES, PBNB_NODE_ITER, PBNB_EVENTS, PBNB_DEPTH, PBNB_REFUSED = range(7)    # LPX_PBNB_* (lpx_solve_packed_bnb)
 PBNB_STOPS = ("done", "root", "nodes", "node_iter", "events", "depth", "refused")
 
@@ -502,6 +508,10 @@ def lib() -> C.CDLL:
     L.lpx_solve_packed.argtypes = [C.POINTER(PackedModels), C.POINTER(RunOpts), C.POINTER(PackedResults), C.POINTER(Stats)]
     L.lpx_solve_packed_dual.argtypes = [C.POINTER(PackedDualModels), C.c_int, C.POINTER(RunOpts), C.POINTER(PackedDualResults),
                                         C.POINTER(Stats)]
+    L.lpx_packed_base_open.argtypes = [C.POINTER(PackedBaseModel), C.c_int, C.POINTER(RunOpts), C.POINTER(PackedDualResults),
+                                       C.POINTER(vp)]
+    L.lpx_packed_base_solve.argtypes = [vp, C.c_int32, dp, C.c_int, C.POINTER(RunOpts), C.POINTER(PackedDualResults), C.POINTER(Stats)]
+    L.lpx_packed_base_close.argtypes = [vp]
     L.lpx_solve_packed_bnb.argtypes = [C.POINTER(PackedBnbModels), C.POINTER(PackedBnbOpts), C.POINTER(PackedBnbResults),
                                        C.POINTER(Stats)]
     L.lpx_solve_packed_bnb_dual.argtypes = [C.POINTER(PackedBnbDualModels), C.POINTER(PackedBnbOpts), C.POINTER(PackedBnbResults),

@@ -315,12 +315,15 @@ void CheckPacked(const lpx_packed_models* in, const lpx_run_opts* o, const lpx_p
 
 // The argument checks of lpx_solve_packed_dual: CheckPacked's list in its order (rel_stride among the strides), then a shared rel
 // (m reads; a per-model rel is checked by its workgroup), then the flags.
-void CheckPackedDual(const lpx_packed_dual_models* in, int flags, const lpx_run_opts* o, const lpx_packed_dual_results* out)
+// `what` is the prefix of every message; out_optional: a NULL out is accepted and then counts no output bytes (the base of
+// lpx_packed_base_open)
+static void check_packed_dual(const std::string& what, const lpx_packed_dual_models* in, int flags, const lpx_run_opts* o,
+                              const lpx_packed_dual_results* out, bool out_optional)
 {
-    auto bad = [](const std::string& msg) { return LpxException(LPX_EINVAL, "lpx_solve_packed_dual: " + msg); };
-    if (!in || !out) throw bad("null argument");
+    auto bad = [&](const std::string& msg) { return LpxException(LPX_EINVAL, what + msg); };
+    if (!in || (!out && !out_optional)) throw bad("null argument");
     if (!in->c || !in->A || !in->b) throw bad("null c, A or b");
-    if (!out->status || !out->x || !out->value) throw bad("null status, x or value");
+    if (out && (!out->status || !out->x || !out->value)) throw bad("null status, x or value");
     if (in->count < 1 || in->count > 65536) throw bad("count is outside [1, 65536]");
     if (in->m < 1 || in->n < 1) throw bad("m and n must be at least 1");
     if (in->sense != LPX_MAX && in->sense != LPX_MIN) throw bad("sense is neither LPX_MAX nor LPX_MIN");
@@ -341,12 +344,14 @@ void CheckPackedDual(const lpx_packed_dual_models* in, int flags, const lpx_run_
     if (in->lower) bytes += 8 * n * models(in->lower_stride);
     if (in->upper) bytes += 8 * n * models(in->upper_stride);
     if (in->rel) bytes += 4 * m * models(in->rel_stride);
-    bytes += count * (4 + 8 * n + 8);
-    if (out->rec) bytes += count * (int64_t)sizeof(lpx_packed_dual_record);
-    if (out->basis) bytes += count * 4 * m;
-    if (out->at_upper) bytes += count * n;
-    if (out->y) bytes += count * 8 * m;
-    if (out->d) bytes += count * 8 * n;
+    if (out) {
+        bytes += count * (4 + 8 * n + 8);
+        if (out->rec) bytes += count * (int64_t)sizeof(lpx_packed_dual_record);
+        if (out->basis) bytes += count * 4 * m;
+        if (out->at_upper) bytes += count * n;
+        if (out->y) bytes += count * 8 * m;
+        if (out->d) bytes += count * 8 * n;
+    }
     if (bytes > ((int64_t)1 << 30))
         throw bad("too large: " + std::to_string(bytes) + " bytes of inputs and outputs, above 1 GiB (split the batch)");
     if (in->rel && in->rel_stride == 0)
@@ -354,6 +359,46 @@ void CheckPackedDual(const lpx_packed_dual_models* in, int flags, const lpx_run_
             if (in->rel[i] != LPX_LE && in->rel[i] != LPX_GE)
                 throw bad("rel[" + std::to_string(i) + "] is neither LPX_LE nor LPX_GE (an = row is passed as its pair of rows)");
     if (flags & ~LPX_BDUAL_LONG_STEP) throw bad("unknown flag: flags holds a bit other than LPX_BDUAL_LONG_STEP");
+}
+
+void CheckPackedDual(const lpx_packed_dual_models* in, int flags, const lpx_run_opts* o, const lpx_packed_dual_results* out)
+{
+    check_packed_dual("lpx_solve_packed_dual: ", in, flags, o, out, false);
+}
+
+// The argument checks of lpx_packed_base_open: a NULL in or h, then the list of lpx_solve_packed_dual in its order for the base as
+// a batch of one whose arrays are all shared; base_out may be NULL.
+void CheckPackedBaseOpen(const lpx_packed_base_model* in, int flags, const lpx_run_opts* o, const lpx_packed_dual_results* base_out,
+                         const void* h)
+{
+    const std::string what = "lpx_packed_base_open: ";
+    if (!in || !h) throw LpxException(LPX_EINVAL, what + "null argument");
+    lpx_packed_dual_models dm;
+    std::memset(&dm, 0, sizeof dm);
+    dm.count = 1; dm.m = in->m; dm.n = in->n; dm.sense = in->sense;
+    dm.c = in->c; dm.A = in->A; dm.b = in->b; dm.lower = in->lower; dm.upper = in->upper; dm.rel = in->rel;
+    check_packed_dual(what, &dm, flags, o, base_out, true);
+}
+
+// The argument checks of lpx_packed_base_solve; m and n are the handle's (read only behind the NULL test of the handle).
+void CheckPackedBaseSolve(const void* h, int m32, int n32, int32_t count32, const double* b, int flags, const lpx_run_opts* o,
+                          const lpx_packed_dual_results* out)
+{
+    auto bad = [](const std::string& msg) { return LpxException(LPX_EINVAL, "lpx_packed_base_solve: " + msg); };
+    if (!h || !b || !out) throw bad("null argument");
+    if (!out->status || !out->x || !out->value) throw bad("null status, x or value");
+    if (count32 < 1 || count32 > 65536) throw bad("count is outside [1, 65536]");
+    if (flags & ~LPX_BDUAL_LONG_STEP) throw bad("unknown flag: flags holds a bit other than LPX_BDUAL_LONG_STEP");
+    if (o && o->resident > 0) throw bad("there is no resident form of the bounded loop (resident = 1)");
+    const int64_t m = m32, n = n32, count = count32;
+    int64_t bytes = 8 * m * count + count * (4 + 8 * n + 8);
+    if (out->rec) bytes += count * (int64_t)sizeof(lpx_packed_dual_record);
+    if (out->basis) bytes += count * 4 * m;
+    if (out->at_upper) bytes += count * n;
+    if (out->y) bytes += count * 8 * m;
+    if (out->d) bytes += count * 8 * n;
+    if (bytes > ((int64_t)1 << 30))
+        throw bad("too large: " + std::to_string(bytes) + " bytes of inputs and outputs, above 1 GiB (split the batch)");
 }
 
 // The argument checks of lpx_solve_packed_bnb: CheckPacked's list in its order up to the fit rule, then the options, and last --

@@ -242,6 +242,12 @@ void SolveBoundedBatch(const std::vector<const LPProblem*>& problems, const std:
 void CheckPacked(const lpx_packed_models* in, const lpx_run_opts* o, const lpx_packed_results* out);
 // the argument checks of lpx_solve_packed_dual, the same way; the call itself is lpx::packed_dual_solve
 void CheckPackedDual(const lpx_packed_dual_models* in, int flags, const lpx_run_opts* o, const lpx_packed_dual_results* out);
+// the argument checks of lpx_packed_base_open (h: where the handle goes) and lpx_packed_base_solve (h: the handle, m and n its
+// shape), the same way; the calls themselves are lpx::packed_base_open and lpx::packed_base_solve
+void CheckPackedBaseOpen(const lpx_packed_base_model* in, int flags, const lpx_run_opts* o, const lpx_packed_dual_results* base_out,
+                         const void* h);
+void CheckPackedBaseSolve(const void* h, int m, int n, int32_t count, const double* b, int flags, const lpx_run_opts* o,
+                          const lpx_packed_dual_results* out);
 // the argument checks of lpx_solve_packed_bnb, the same way; work_bytes is lpx::packed_bnb_work_bytes; the call itself is lpx::packed_bnb_solve
 void CheckPackedBnb(const lpx_packed_bnb_models* in, const lpx_packed_bnb_opts* opt, const lpx_packed_bnb_results* out,
                     size_t (*work_bytes)(int count, int m, int n, int max_depth));

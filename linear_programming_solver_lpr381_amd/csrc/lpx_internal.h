@@ -212,6 +212,36 @@ struct PackedDualParams {
 };
 // lpx_solve_packed_dual behind its argument checks: the same arena, the copies, the one launch, the one wait
 int packed_dual_solve(const lpx_packed_dual_models* in, int flags, const lpx_run_opts* o, const lpx_packed_dual_results* out, lpx_stats* st);
+// right-hand-side scenarios warm-started from one solved base (lpx_packed_warm.hip).  The snapshot of a base: one device allocation
+// the handle owns, every pointer into it.  tile is the solved tableau with the row stride S = C | 1 of the kernels' LDS image (a
+// padding column holds 0.0); lower and rel are null where the model has none; flip holds bit 0 only.
+struct PackedBaseSnap {
+    double* tile; double* ub; double* b0; double* lower; double* constant;     // [R * S], [C], [m], [n], [1]: c.l, what the shift took out
+    int32_t* basis; int32_t* rel; int32_t* shifted;                            // [m], [m], [1]
+    uint8_t* flip;                                                             // [C - 1]
+};
+struct PackedBase {                                     // what an lpx_packed_base holds on the host
+    int32_t m = 0, n = 0, min = 0;
+    char* dev = nullptr; size_t dev_bytes = 0;
+    PackedBaseSnap snap{};
+};
+// both kernels: the base reads c, A, upper and snap.b0 / lower / rel (uploaded there) and writes the rest of the snapshot; a
+// scenario reads the snapshot and its own b ([count][m])
+struct PackedWarmParams {
+    const double *c, *A, *upper, *b;
+    PackedBaseSnap snap;
+    int32_t m, n, min, max_iter, long_step, pad;
+    double eps, ratio_tol;
+    int32_t* status; double* x; double* value; lpx_packed_dual_record* rec; int32_t* basis; uint8_t* at_upper;   // as lpx_packed_dual_results
+    double* y; double* d;
+    uint8_t* flip; int64_t flip_stride;                 // work bytes, [count][flip_stride], flip_stride >= n + m
+};
+// lpx_packed_base_open / _solve / _close behind their argument checks.  open: the base's status (0 = LPX_OPTIMAL: *base filled) or
+// an error code; the caller frees a base it does not keep with packed_base_close
+int packed_base_open(const lpx_packed_base_model* in, int flags, const lpx_run_opts* o, const lpx_packed_dual_results* base_out, PackedBase* base);
+int packed_base_solve(const PackedBase* base, int32_t count, const double* b, int flags, const lpx_run_opts* o,
+                      const lpx_packed_dual_results* out, lpx_stats* st);
+void packed_base_close(PackedBase* base);
 // the packed batch of integer programs (lpx_packed_bnb.hip): PackedParams plus the shared integer mask ([n] bytes or null = every
 // variable), the search flags, the three budgets, both ratio tolerances (the root's primal loop, a node's dual loop), the log and
 // the work slices ([count][work_stride] bytes: what the search keeps outside LDS)

@@ -389,6 +389,40 @@ int lpx_solve_packed_dual(const lpx_packed_dual_models* in, int flags, const lpx
     return packed_dual_solve(in, flags, o, out, st);
 }
 
+// ---- right-hand-side scenarios warm-started from one solved base (host/bounded.cpp CheckPackedBase*, lpx_packed_warm.hip) -------
+struct lpx_packed_base { PackedBase s; };
+
+int lpx_packed_base_open(const lpx_packed_base_model* in, int flags, const lpx_run_opts* o, const lpx_packed_dual_results* base_out,
+                         lpx_packed_base** h)
+{
+    if (h) *h = nullptr;
+    try { CheckPackedBaseOpen(in, flags, o, base_out, h); }
+    catch (const LpxException& ex) { set_error(ex.what()); return ex.code; }
+    lpx_run_opts d; if (!o) { lpx_default_opts(&d, 1); o = &d; }
+    lpx_packed_base* base = new lpx_packed_base();
+    const int rc = packed_base_open(in, flags, o, base_out, &base->s);
+    if (rc != 0) { packed_base_close(&base->s); delete base; return rc; }     // only an optimal base is kept
+    *h = base;
+    return 0;
+}
+
+int lpx_packed_base_solve(const lpx_packed_base* h, int32_t count, const double* b, int flags, const lpx_run_opts* o,
+                          const lpx_packed_dual_results* out, lpx_stats* st)
+{
+    try { CheckPackedBaseSolve(h, h ? h->s.m : 0, h ? h->s.n : 0, count, b, flags, o, out); }
+    catch (const LpxException& ex) { set_error(ex.what()); return ex.code; }
+    lpx_run_opts d; if (!o) { lpx_default_opts(&d, 1); o = &d; }
+    return packed_base_solve(&h->s, count, b, flags, o, out, st);
+}
+
+int lpx_packed_base_close(lpx_packed_base* h)
+{
+    if (!h) return 0;
+    packed_base_close(&h->s);
+    delete h;
+    return 0;
+}
+
 int lpx_solve_packed_bnb(const lpx_packed_bnb_models* in, const lpx_packed_bnb_opts* opt, const lpx_packed_bnb_results* out,
                          lpx_stats* st)
 {

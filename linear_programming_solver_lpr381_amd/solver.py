@@ -962,11 +962,103 @@ class LPSolver:             # Models/LPSolver.cs:6-77
         .set_bounds(vars, lower, upper) tightens, fixes or loosens bounds and re-optimises with the bounded dual simplex."""
         return BoundedSession(problem, upper=upper, lower=lower, **self.engine)
 
+    def OpenPackedBase(self, c, A, b, rel=None, upper=None, lower=None, sense="max", long_step: bool = True,
+                       max_iter=None) -> "PackedBase":
+        """ONE model (c (n,), A (m, n), b (m,), rel / upper / lower as SolvePackedDual takes them without the batch axis) solved by
+        the dual start and kept on the device (lpx_packed_base_open): .Base is SolvePackedDual's result for it, and
+        .solve(b) re-solves a batch of right-hand sides of that model in ONE launch, every workgroup continuing from the base's
+        optimal basis.  A base that is not OPTIMAL raises SolverException with its status as the code."""
+        limit = max_iter if max_iter is not None else self.engine.get("max_iter")
+        return PackedBase(c, A, b, rel, upper, lower, sense, long_step, limit)
+
     def Open(self, problem: LPProblem, **opts) -> "ModelSession":
         """A warm post-optimal session on the device (lpx_session_open): the model is solved once, then ChangeRHS /
         ChangeCost / AddActivity / AddConstraint each re-optimise from the current basis.  opts: extra_rows, extra_cols,
         max_iter, batch, want_tableau (lpx_session_opts)."""
         return ModelSession(problem, **opts)
+
+
+def _packed_dual_outputs(B, m, n):
+    """Every output array of an lpx_packed_dual_results for B models, the struct over them and a function that makes the result."""
+    status = np.zeros(B, dtype=np.int32); x = np.zeros((B, n)); value = np.zeros(B)
+    recs = (_lib.PackedDualRecord * B)()
+    basis = np.zeros((B, m), dtype=np.int32); at = np.zeros((B, n), dtype=np.uint8); y = np.zeros((B, m)); d = np.zeros((B, n))
+    pr = _lib.PackedDualResults(status.ctypes.data_as(_lib.ip), x.ctypes.data_as(_lib.dp), value.ctypes.data_as(_lib.dp), recs,
+                                basis.ctypes.data_as(_lib.ip), at.ctypes.data_as(C.POINTER(C.c_uint8)), y.ctypes.data_as(_lib.dp),
+                                d.ctypes.data_as(_lib.dp))
+
+    def take(stats):
+        r = np.frombuffer(recs, dtype=np.dtype([("status", "<i4"), ("events", "<i4"), ("kind0", "<i8"), ("kind1", "<i8"),
+                                                ("passes", "<i8"), ("dualize_flips", "<i8"), ("z", "<f8")]))
+        return PackedDualResult(Status=status, Solution=x, OptimalValue=value, Basis=basis, AtUpper=at, Stats=stats, Duals=y,
+                                ReducedCosts=d, Events=r["events"].copy(), BoundCounts=np.stack([r["kind0"], r["kind1"], r["passes"]], axis=1),
+                                Passes=r["passes"].copy(), DualizeFlips=r["dualize_flips"].copy(), Z=r["z"].copy())
+    return pr, take
+
+
+class PackedBase:           # lpx_packed_base (include/lpx.h): right-hand-side scenarios warm-started from one solved model
+    def __init__(self, c, A, b, rel=None, upper=None, lower=None, sense="max", long_step: bool = True, max_iter=None):
+        self._h = None
+        sense, c, A, b, bounds, rel, B, m, n = _packed_inputs(c, A, b, upper, lower, sense, rel)
+        if c.ndim != 1 or A.ndim != 2 or b.ndim != 1 or any(v is not None and v.ndim != 1 for v in (bounds["upper"], bounds["lower"], rel)):
+            raise ValueError("the base is one model: c (n,), A (m, n), b (m,), rel (m,), upper / lower (n,) or a scalar")
+        self.m, self.n = m, n
+        pm = _lib.PackedBaseModel()
+        pm.m, pm.n, pm.sense = m, n, int(sense)
+        pm.c, pm.A, pm.b = (v.ctypes.data_as(_lib.dp) for v in (c, A, b))
+        for name in ("upper", "lower"):
+            if bounds[name] is not None:
+                setattr(pm, name, bounds[name].ctypes.data_as(_lib.dp))
+        if rel is not None:
+            pm.rel = rel.ctypes.data_as(_lib.ip)
+        pr, take = _packed_dual_outputs(1, m, n)
+        o = _lib.default_opts(True) if max_iter is None else _lib.default_opts(True, max_iter=int(max_iter))
+        h = C.c_void_p()
+        rc = lib().lpx_packed_base_open(C.byref(pm), _lib.BDUAL_LONG_STEP if long_step else 0, C.byref(o), C.byref(pr), C.byref(h))
+        if rc != 0:
+            raise SolverException(rc, _lib.last_error())
+        self._h = h
+        self._max_iter = max_iter
+        self.Base = take(None)
+
+    def solve(self, b, long_step: bool = True, max_iter=None) -> PackedDualResult:
+        """b: (B, m) or (m,) right-hand sides of the base's model, re-solved in ONE launch (lpx_packed_base_solve).  Every scenario
+        gets its own Status: OPTIMAL, INFEASIBLE, ITER_LIMIT, or LPX_EINVAL for a right-hand side that is not finite.  Events and
+        BoundCounts count the scenario's own loop; DualizeFlips is 0.  max_iter: None = the one the base was opened with."""
+        if self._h is None:
+            raise SolverException(_lib.EINVAL, "the packed base is closed")
+        b = np.ascontiguousarray(np.asarray(b, dtype=np.float64))
+        if b.ndim == 1:
+            b = b[None, :]
+        if b.ndim != 2 or b.shape[1] != self.m or b.shape[0] < 1:
+            raise ValueError(f"b is (B, m) or (m,) with m = {self.m}")
+        B = b.shape[0]
+        pr, take = _packed_dual_outputs(B, self.m, self.n)
+        limit = max_iter if max_iter is not None else self._max_iter
+        o = _lib.default_opts(True) if limit is None else _lib.default_opts(True, max_iter=int(limit))
+        st = _lib.Stats()
+        rc = lib().lpx_packed_base_solve(self._h, B, b.ctypes.data_as(_lib.dp), _lib.BDUAL_LONG_STEP if long_step else 0, C.byref(o),
+                                         C.byref(pr), C.byref(st))
+        if rc != 0:
+            raise SolverException(rc, _lib.last_error())
+        return take(st.as_dict())
+
+    def close(self):
+        if self._h is not None:
+            lib().lpx_packed_base_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class BoundedSession:       # lpx_bounded_session (include/lpx.h): bound edits re-optimised from the solved tableau

@@ -22,12 +22,22 @@ PATH/liblpx.so` (the library of the parent commit) the existing packed primal ca
 in the same process, alternating, with the bits of their outputs asserted equal.  `--packed-trace` makes four packed dual calls
 and nothing else, for a run of its own under `rocprofv3 --kernel-trace --stats`.
 
+`--compare-warm` measures the packed calls from a solved base (lpx_packed_base_open / _solve) against the
+cold packed call of the same scenarios, SolvePackedDual with c, A and rel at stride 0, in the same library and process: +-20 %
+right-hand sides of covering(12, 60, 1) (13 x 73) and of covering(110, 50, 1) (111 x 161, near the fit limit), count 256, 4096 and
+65536 (the last with BIG_REPS timed rounds), with and without the long step.  Three sides alternate in every round: cold; warm with
+the base kept open (PackedBase.solve alone is timed); warm with the open and the close inside the timed region.  Host wall of whole
+calls, the rule of section 4.17 per pair; statuses asserted equal and optima within 1e-9 relative; events per scenario of both
+sides.  `--warm-trace` makes three calls of each side at count 4096 on the 13 x 73 model with the long step and nothing else, for a
+run of its own under
+`rocprofv3 --kernel-trace --stats`.
+
 `--trace-only` runs leg (a) on the smaller model once per side (no untimed run in front), for a separate run under
 `rocprofv3 --kernel-trace --stats -- python tools/bench_bounded_long.py --trace-only`, whose kernel table gives the mean launch
 time of lpx_bounded_long_select, lpx_bounded_dual_select and the lpx_update launches they feed.
 
 usage: bench_bounded_long.py [--leg a|b|c]... [--root DIR] [--big-reps N] [--skip-big] [--trace-only]
-                             [--compare-packed [--parent-lib PATH] | --packed-trace] [REPS]"""
+                             [--compare-packed [--parent-lib PATH] | --packed-trace | --compare-warm | --warm-trace] [REPS]"""
 import json
 import os
 import statistics
@@ -38,7 +48,7 @@ import time
 def _args():
     a = sys.argv[1:]
     opt = {"legs": [], "root": None, "big_reps": 2, "skip_big": False, "trace_only": False, "reps": None, "compare_packed": False,
-           "packed_trace": False, "parent_lib": None}
+           "packed_trace": False, "parent_lib": None, "compare_warm": False, "warm_trace": False}
     i = 0
     while i < len(a):
         if a[i] == "--leg":
@@ -55,6 +65,10 @@ def _args():
             opt["compare_packed"] = True; i += 1
         elif a[i] == "--packed-trace":
             opt["packed_trace"] = True; i += 1
+        elif a[i] == "--compare-warm":
+            opt["compare_warm"] = True; i += 1
+        elif a[i] == "--warm-trace":
+            opt["warm_trace"] = True; i += 1
         elif a[i] == "--parent-lib":
             opt["parent_lib"] = a[i + 1]; i += 2
         else:
@@ -62,7 +76,7 @@ def _args():
     if not opt["legs"]:
         opt["legs"] = ["a", "b", "c"]
     if opt["reps"] is None:
-        opt["reps"] = 15 if opt["compare_packed"] else 7
+        opt["reps"] = 15 if opt["compare_packed"] else 7           # --compare-warm: 7
     return opt
 
 
@@ -294,9 +308,53 @@ def compare_packed(reps, trace, parent_lib):
     return out
 
 
+def compare_warm(reps, big_reps, trace):
+    S = L.LPSolver()
+    out = {}
+    for m, n in (((12, 60),) if trace else ((12, 60), (110, 50))):
+        assert L._lib.lib().lpx_packed_fits(m, n) == 1
+        cs, As, b0s = covering_models(1, m, n)
+        c, A, b0 = cs[0], As[0], b0s[0]
+        rel = np.ones(m, dtype=np.int32)
+        for count in ((4096,) if trace else (256, 4096, 65536)):
+            bs = b0 * np.random.default_rng(5).uniform(0.8, 1.2, size=(count, m))
+            for long_step in ((True,) if trace else (True, False)):
+                rounds = 2 if trace else (big_reps if count == 65536 else reps)
+                sides = {"cold": [], "warm_kept": [], "warm_with_open": []}
+                with S.OpenPackedBase(c, A, b0, rel, 1.0, sense="min", long_step=long_step) as kept:
+                    for i in range(rounds + 1):
+                        ms, rc = _timed(lambda: S.SolvePackedDual(c, A, bs, rel, 1.0, sense="min", long_step=long_step))
+                        sides["cold"].append(ms)
+                        ms, rw = _timed(lambda: kept.solve(bs, long_step=long_step))
+                        sides["warm_kept"].append(ms)
+
+                        def opened():
+                            with S.OpenPackedBase(c, A, b0, rel, 1.0, sense="min", long_step=long_step) as base:
+                                return base.solve(bs, long_step=long_step)
+                        ms, ro = _timed(opened)
+                        sides["warm_with_open"].append(ms)
+                        assert np.array_equal(rc.Status, rw.Status) and np.array_equal(rw.Status, ro.Status), "statuses differ"
+                        ok = rc.Status == 0
+                        assert (np.abs(rw.OptimalValue - rc.OptimalValue)[ok] <= 1e-9 * np.maximum(1.0, np.abs(rc.OptimalValue[ok]))).all()
+                        assert rw.OptimalValue.tobytes() == ro.OptimalValue.tobytes()
+                rec = {"shape": [m + 1, n + m + 1], "count": count, "long_step": long_step, "optimal": int(ok.sum()),
+                       "events_per_scenario_cold": float(rc.Events.mean()), "events_per_scenario_warm": float(rw.Events.mean()),
+                       "base_events": int(kept.Base.Events[0])}
+                if not trace:
+                    rec.update({k: stats(v[1:]) for k, v in sides.items()})     # the first round is the warm-up
+                    rec["winner_kept"] = verdict(rec["warm_kept"], rec["cold"], "warm", "cold")
+                    rec["winner_with_open"] = verdict(rec["warm_with_open"], rec["cold"], "warm", "cold")
+                    rec["cold_over_warm_kept"] = rec["cold"]["median_ms"] / rec["warm_kept"]["median_ms"]
+                out["%dx%d count %d %s" % (m + 1, n + m + 1, count, "long" if long_step else "plain")] = rec
+    return out
+
+
 def main():
     L._lib.check(L._lib.lib().lpx_init(0))
     out = {}
+    if OPT["compare_warm"] or OPT["warm_trace"]:
+        print(json.dumps(compare_warm(OPT["reps"], OPT["big_reps"], OPT["warm_trace"])))
+        return
     if OPT["compare_packed"] or OPT["packed_trace"]:
         print(json.dumps(compare_packed(OPT["reps"], OPT["packed_trace"], OPT["parent_lib"])))
         return

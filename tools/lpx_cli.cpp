@@ -15,7 +15,8 @@
 // --binary (every u_j = 1) select the bounded-variable primal simplex (lpx_solve_bounded): the bounds cost no rows.  --bounded selects it without any bound.  --bounded --rhs-file F solves the model once per line of F (m numbers, the
 // right-hand sides of that run) as ONE packed call (lpx_solve_packed) with c, A and the bounds shared by every run, and prints one
 // line "status value x1 .. xn" per right-hand side.  --bounded-dual [--long-step] --rhs-file F does the same by the dual start
-// (lpx_solve_packed_dual): >= rows and negative right-hand sides are accepted, an = row is refused.  --bnb-bounded --rhs-file F (with
+// (lpx_solve_packed_dual): >= rows and negative right-hand sides are accepted, an = row is refused; with --warm-base the input's own
+// right-hand side is solved once and every line continues from that base (lpx_packed_base_open / _solve).  --bnb-bounded --rhs-file F (with
 // --binary or --upper bounds, and --long-step / --cutoff) solves the model as an integer program once per line of F as ONE packed
 // call (lpx_solve_packed_bnb): a whole branch and bound per right-hand side in one kernel launch, the same line per run.
 // --bnb-bounded --dual-root runs the search from a dual start (lpx_solve_bnb_bounded_dual; with --rhs-file F lpx_solve_packed_bnb_dual):
@@ -87,6 +88,7 @@ int main(int argc, char** argv)
     std::string rhs_file;       // --rhs-file F beside --bounded: one packed call (lpx_solve_packed), a right-hand side per line of F
     bool dual_root = false;     // --dual-root beside --bnb-bounded: the search from a dual start (lpx_solve_bnb_bounded_dual; with --rhs-file lpx_solve_packed_bnb_dual)
     bool bounded_dual = false;  // --bounded-dual beside --rhs-file: that packed call by the dual start (lpx_solve_packed_dual)
+    bool warm_base = false;     // --warm-base beside --bounded-dual --rhs-file: the input's own right-hand side solved once, every line of F from that base (lpx_packed_base_open / _solve)
     int search_flags = 0;       // --long-step / --cutoff beside --bnb-bounded
     int node_form = -1;         // --node-form beside --bnb-bounded: LPX_NODE_*; -1 = not given
     int divers = 0;             // --divers W beside --bnb-bounded: the search by W divers (lpx_solve_bnb_bounded4); 0 = not given
@@ -111,6 +113,7 @@ int main(int argc, char** argv)
         else if (a == "--bnb-bounded") bnb_bounded = true;
         else if (a == "--bounded") bounded_flag = true;
         else if (a == "--bounded-dual") bounded_dual = true;
+        else if (a == "--warm-base") warm_base = true;
         else if (a == "--dual-root") dual_root = true;
         else if (a == "--rhs-file" && i + 1 < argc) rhs_file = argv[++i];
         else if (a == "--long-step") search_flags |= LPX_BDUAL_LONG_STEP;
@@ -211,6 +214,7 @@ int main(int argc, char** argv)
                         "               [--upper J=V]... [--lower J=V]... [--binary] [--bnb-bounded [--long-step] [--cutoff] [--node-form F] [--divers W] [--plunge D] [--branching R [--candidates N] [--probe-iter L]] [--stall-events S] [--root-form F] [--root-cuts N [--cuts-per-round K]] [--tighten]] [--bounded-form F]\n"
                         "               [--bounded [--rhs-file F]] [--bounded-dual [--long-step] --rhs-file F] [--export FILE] INPUT.txt\n"
                         "               [--binary --bnb-bounded [--long-step] [--cutoff] --rhs-file F]\n"
+                        "               [--bounded-dual [--long-step] --warm-base --rhs-file F]\n"
                         "               [--bnb-bounded --dual-root [--long-step] [--cutoff] [--node-form F | --rhs-file F]]\n"
                         "  NAME: Primal Simplex | Revised Primal Simplex | Dual Simplex | Branch and Bound |\n"
                         "        Revised Branch and Bound | Branch and Bound Knapsack | Cutting Plane | Revised Cutting Plane |\n"
@@ -245,6 +249,9 @@ int main(int argc, char** argv)
                         "             launch, one read-back; c, A and the bounds shared); prints a line \"status value x1 .. xn\" per run\n"
                         "  --bounded-dual [--long-step] --rhs-file F: the same by the dual start (lpx_solve_packed_dual): >= rows and negative\n"
                         "             right-hand sides are accepted, an = row is refused; --long-step: the bound-flipping ratio test\n"
+                        "  --bounded-dual [--long-step] --warm-base --rhs-file F: the input's own right-hand side is solved once and kept on the\n"
+                        "             device (lpx_packed_base_open); every line of F is then re-solved from that base's optimal basis in ONE kernel\n"
+                        "             launch (lpx_packed_base_solve); the same line per run\n"
                         "  --bnb-bounded --rhs-file F: the model as an integer program once per line of F as ONE packed call (lpx_solve_packed_bnb:\n"
                         "             a whole branch and bound per right-hand side in one kernel launch; at most 100000 nodes and 2000000 events\n"
                         "             per run); with --binary or --upper bounds and --long-step / --cutoff; the same line per run\n"
@@ -288,6 +295,7 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "lpx_cli: --bounded-dual needs --rhs-file and combines only with --long-step and --upper / --lower / --binary\n");
         return 64;
     }
+    if (warm_base && !bounded_dual) { std::fprintf(stderr, "lpx_cli: --warm-base needs --bounded-dual --rhs-file\n"); return 64; }
     if (!bounded_dual && !packed_bnb && !rhs_file.empty() && (!bounded_flag || bnb_bounded || bounded_form >= 0 || iterations || !edits.empty() || !exportPath.empty())) {
         std::fprintf(stderr, "lpx_cli: --rhs-file needs --bounded and combines only with --upper / --lower / --binary\n");
         return 64;
@@ -411,6 +419,15 @@ int main(int argc, char** argv)
             lpx_packed_dual_results dr; std::memset(&dr, 0, sizeof dr);
             dr.status = status.data(); dr.x = x.data(); dr.value = value.data();
             lpx_run_opts ro; lpx_default_opts(&ro, 1);
+            if (warm_base) {                            // the input's own right-hand side is the base; every line continues from it
+                lpx_packed_base_model bm; std::memset(&bm, 0, sizeof bm);
+                bm.m = p.m; bm.n = p.n; bm.sense = p.sense;
+                bm.c = p.c; bm.A = p.A; bm.b = p.b; bm.lower = lo.data(); bm.upper = up.data(); bm.rel = p.rel;
+                lpx_packed_base* base = nullptr;
+                prc = lpx_packed_base_open(&bm, search_flags & LPX_BDUAL_LONG_STEP, &ro, nullptr, &base);
+                if (prc == 0) prc = lpx_packed_base_solve(base, count, rhs.data(), search_flags & LPX_BDUAL_LONG_STEP, &ro, &dr, nullptr);
+                lpx_packed_base_close(base);
+            } else
             prc = lpx_solve_packed_dual(&dm, search_flags & LPX_BDUAL_LONG_STEP, &ro, &dr, nullptr);
         } else {
             lpx_packed_models pm; std::memset(&pm, 0, sizeof pm);
