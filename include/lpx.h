@@ -1461,7 +1461,8 @@ int lpx_solve_packed_dual(const lpx_packed_dual_models* in, int flags, const lpx
  *      dualize_flips = 0 and events counts this scenario's loop only.
  * status[i]: LPX_OPTIMAL, LPX_INFEASIBLE, LPX_ITER_LIMIT (the limit is tested first, as in the loop) or LPX_EINVAL.  The results do
  * not depend on count, on i or on the other scenarios.  The handle is only read: several solves may follow one open, and several
- * handles may be open at once.  Per-scenario bounds or costs are not offered.  st (or NULL) as in lpx_solve_packed_dual.
+ * handles may be open at once.  Per-scenario costs are lpx_packed_base_solve_costs (below); per-scenario bounds are not offered.
+ * st (or NULL) as in lpx_solve_packed_dual.
  * LPX_EINVAL before any device check, the outputs untouched, every message starting "lpx_packed_base_solve: ": a NULL h, b or out;
  * a NULL status, x or value; count outside [1, 65536]; an unknown flag; resident = 1; more than 1 GiB of input plus output bytes.
  * No device: LPX_EDEVICE.
@@ -1479,6 +1480,67 @@ int lpx_packed_base_open(const lpx_packed_base_model* in, int flags, const lpx_r
 int lpx_packed_base_solve(const lpx_packed_base* h, int32_t count, const double* b /* [count][m] */, int flags,
                           const lpx_run_opts* o /* or NULL */, const lpx_packed_dual_results* out, lpx_stats* st /* or NULL */);
 int lpx_packed_base_close(lpx_packed_base* h);             /* NULL is allowed */
+
+/* ---- packed cost and right-hand-side scenarios from the same solved base (csrc/lpx_packed_cost.hip) ------
+ *
+ * Costs are the other half of a scenario workload: price sweeps, stochastic programmes, a moving objective, pricing sub-problems.
+ * A cost change leaves the RHS column of the base's solved tableau untouched, so the base's basis stays primal feasible; only the
+ * objective row moves, by one m x C product, and the bounded PRIMAL loop continues from the base's basis.  A scenario that changes
+ * c and b is the two moves in turn: the primal loop runs to the optimum of (c_i, b0), which is dual feasible again, then the
+ * slack-block move of lpx_packed_base_solve is applied and the dual loop runs.  The handle remembers the base's c (a host copy
+ * made by lpx_packed_base_open).
+ *
+ * lpx_packed_base_solve_costs(h, count, c, b, flags, o_primal, o_dual, out, st) makes one upload of c0, c ([count][n], the user's
+ * costs) and, if given, b ([count][m]; NULL: every scenario keeps b0), ONE launch of count workgroups, one read-back and one wait,
+ * on the arena and the stream of lpx_solve_packed.  Every product and every sum below is separately rounded, in the stated order.
+ * Workgroup i
+ *   1. copies the base's tile and ub into LDS, the basis and the flip bytes into its own slices (step 1 of lpx_packed_base_solve);
+ *   2. refuses the scenario if any c_i[j], or any b_i[k] when b is given, is not finite (LPX_EINVAL: its outputs zeroed, a record
+ *      of zeros around the status);
+ *   3. moves the objective row:
+ *          delta_j = c_i[j] - c0[j], negated for a Min model;
+ *          g_j = -delta_j if bit 0 of flip[j] is set, else delta_j, for j < n;  g_j = 0 for the slack columns;
+ *          K = 0;  for j ascending over the flipped columns with delta_j != 0.0:  prod = delta_j * ub[j];  K = K + prod;
+ *          for every column j = 0 .. C-1, the RHS column included:
+ *              acc = T[m][j];
+ *              for i = 0 .. m-1 ascending with g_basis[i] != 0.0:  prod = g_basis[i] * T[i][j];  acc = acc + prod;
+ *              for j < n with g_j != 0.0:  acc = acc - g_j;
+ *              for j = C-1:  acc = acc + K;
+ *              T[m][j] = acc
+ *      and nothing else: an all-zero delta leaves every bit as the base left it.  The shift constant of the user's optimum is
+ *      re-summed from c_i: sum of c_i[j] * l_j for j ascending over l_j != 0.0, the statement the base uses;
+ *   4. runs the bounded primal loop (steps 1-4 of "bounded-variable primal simplex", the loop of lpx_solve_packed) from the base's
+ *      basis and flip bytes with o_primal's eps, ratio_tol and max_iter (NULL: lpx_default_opts(o, 0)).  LPX_UNBOUNDED or
+ *      LPX_ITER_LIMIT ends the scenario with that status; the dual loop is then not run;
+ *   5. with b only: applies steps 2-3 of lpx_packed_base_solve (the slack-block move) to the tile as the primal loop left it, then
+ *      runs the dual loop of lpx_bounded_dual_run3(flags) with o_dual's eps, ratio_tol and max_iter (NULL: lpx_default_opts(o, 1))
+ *      and this call's flags (0 or LPX_BDUAL_LONG_STEP); the loop counts its own events from 0 and tests its limit first;
+ *   6. extracts x, value, basis, at_upper, y and d exactly as lpx_packed_base_solve does, with the re-summed constant, for every
+ *      status but LPX_EINVAL.
+ * status[i]: LPX_OPTIMAL, LPX_UNBOUNDED, LPX_INFEASIBLE, LPX_ITER_LIMIT or LPX_EINVAL.  A scenario whose primal phase ends
+ * LPX_UNBOUNDED is reported LPX_UNBOUNDED even when its b_i would make it infeasible: the phases run in turn and the first one to
+ * fail ends the scenario.  The results do not depend on count, on i or on the other scenarios; the handle is only read.  st (or
+ * NULL): pivots = the sum of the four pivot counters of all scenarios, launches = 1, loop_ms the host wall.
+ * LPX_EINVAL before any device check, the outputs untouched, every message starting "lpx_packed_base_solve_costs: ": a NULL h, c or
+ * out; a NULL status, x or value; count outside [1, 65536]; an unknown flag; resident = 1 in either opts; more than 1 GiB of input
+ * plus output bytes.  No device: LPX_EDEVICE. */
+typedef struct lpx_packed_cost_record {   /* 72 bytes */
+    int32_t status;                        /* OPTIMAL, UNBOUNDED, INFEASIBLE, ITER_LIMIT or LPX_EINVAL */
+    int32_t primal_events, dual_events, pad;
+    int64_t primal_kind0, primal_kind1, primal_flips;   /* the primal loop: pivots of either kind, bound flips */
+    int64_t dual_kind0, dual_kind1, dual_passes;        /* the dual loop (all 0 without b) */
+    double  z;                             /* T[m, C-1] as the last loop left it */
+} lpx_packed_cost_record;
+typedef struct lpx_packed_cost_results {   /* lpx_packed_dual_results with this record; the last five may be NULL */
+    int32_t* status; double* x; double* value;
+    lpx_packed_cost_record* rec; int32_t* basis; uint8_t* at_upper; double* y; double* d;
+} lpx_packed_cost_results;
+int lpx_packed_base_solve_costs(const lpx_packed_base* h, int32_t count,
+                                const double* c /* [count][n] */, const double* b /* [count][m] or NULL = b0 */,
+                                int flags /* 0 or LPX_BDUAL_LONG_STEP: the dual loop */,
+                                const lpx_run_opts* o_primal /* or NULL: lpx_default_opts(.,0) */,
+                                const lpx_run_opts* o_dual   /* or NULL: lpx_default_opts(.,1) */,
+                                const lpx_packed_cost_results* out, lpx_stats* st /* or NULL */);
 
 /* ---- packed batches of small integer programs: a whole branch and bound per workgroup (csrc/lpx_packed_bnb.hip, DESIGN.md
  * section 4.27) ---------------------------------------------------------------------------------------------------------------

@@ -201,6 +201,23 @@ namespace Linear_Programming_Solver.Native
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public struct LpxPackedCostRecord            // lpx_packed_cost_record: 72 bytes, one scenario of lpx_packed_base_solve_costs
+    {
+        public int status;                       // LPX_OPTIMAL / LPX_UNBOUNDED / LPX_INFEASIBLE / LPX_ITER_LIMIT / LPX_EINVAL
+        public int primal_events, dual_events, pad;
+        public long primal_kind0, primal_kind1, primal_flips;   // the primal loop: pivots of either kind, bound flips
+        public long dual_kind0, dual_kind1, dual_passes;        // the dual loop (all 0 without b)
+        public double z;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct LpxPackedCostResults    // lpx_packed_cost_results: caller-allocated; the last five may be null
+    {
+        public int* status; public double* x; public double* value;
+        public LpxPackedCostRecord* rec; public int* basis; public byte* at_upper; public double* y; public double* d;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public unsafe struct LpxPackedBaseModel      // lpx_packed_base_model: the one model of lpx_packed_base_open
     {
         public int m, n, sense;
@@ -567,6 +584,11 @@ namespace Linear_Programming_Solver.Native
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
         public static extern int lpx_packed_base_solve(IntPtr handle, int count, double* b, int flags, IntPtr opts, ref LpxPackedDualResults results,
                                                        LpxStats* st);
+        // cost scenarios from the same base: c [count][n], b [count][m] or null (every scenario keeps the base's right-hand side);
+        // oPrimal / oDual: the options of the primal and of the dual loop, or IntPtr.Zero for each loop's defaults
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+        public static extern int lpx_packed_base_solve_costs(IntPtr handle, int count, double* c, double* b, int flags, IntPtr oPrimal, IntPtr oDual,
+                                                             ref LpxPackedCostResults results, LpxStats* st);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int lpx_packed_base_close(IntPtr handle);
         // packed batches of small integer programs: the whole branch and bound of every model in ONE launch
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]

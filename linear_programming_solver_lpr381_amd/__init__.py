@@ -10,11 +10,11 @@ from .tableau import DeviceTableau, NodeBatch, TableauRanging, primal_tableau, d
 from .revised import DeviceRevised, invert
 from .solver import (BoundedSession, BranchAndBound, BranchAndBoundKnapsack, BranchAndBoundRevised, Constraint, CutOpts, CuttingPlane,
                      CuttingPlaneRevised, DeviceKnapsack, DualSimplex, GmiCuttingPlane, LPProblem, SensitivityAnalysis,
-                     LPSolver, ModelSession, PackedBase, PackedBnbResult, PackedDualResult, PackedResult, ParseFromText, PrimalSimplex, RangingReport, Rel, RevisedPrimalSimplex, Sense, SimplexResult,
+                     LPSolver, ModelSession, PackedBase, PackedBnbResult, PackedCostResult, PackedDualResult, PackedResult, ParseFromText, PrimalSimplex, RangingReport, Rel, RevisedPrimalSimplex, Sense, SimplexResult,
                      SolverException)
 
 __all__ = ["_lib", "comm", "LpxError", "default_opts", "DeviceTableau", "NodeBatch", "TableauRanging", "primal_tableau", "dual_tableau", "multi_run", "DeviceRevised", "invert", "LPSolver", "LPProblem", "Constraint", "Sense", "Rel",
            "SimplexResult", "RangingReport", "SolverException", "PrimalSimplex", "RevisedPrimalSimplex", "DualSimplex",
            "BranchAndBound", "BranchAndBoundKnapsack", "BranchAndBoundRevised", "ParseFromText", "DeviceKnapsack",
            "CuttingPlane", "CuttingPlaneRevised", "SensitivityAnalysis", "CutOpts", "GmiCuttingPlane", "ModelSession",
-           "BoundedSession", "PackedResult", "PackedDualResult", "PackedBnbResult", "PackedBase"]
+           "BoundedSession", "PackedResult", "PackedDualResult", "PackedBnbResult", "PackedBase", "PackedCostResult"]

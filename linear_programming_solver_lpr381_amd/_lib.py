@@ -237,6 +237,19 @@ class PackedBaseModel(C.Structure):
                 ("rel", ip)]
 
 
+class PackedCostRecord(C.Structure):
+    """lpx_packed_cost_record (include/lpx.h): what one scenario of lpx_packed_base_solve_costs did, loop by loop."""
+    _fields_ = [("status", C.c_int32), ("primal_events", C.c_int32), ("dual_events", C.c_int32), ("pad", C.c_int32),
+                ("primal_kind0", C.c_int64), ("primal_kind1", C.c_int64), ("primal_flips", C.c_int64),
+                ("dual_kind0", C.c_int64), ("dual_kind1", C.c_int64), ("dual_passes", C.c_int64), ("z", C.c_double)]
+
+
+class PackedCostResults(C.Structure):
+    """lpx_packed_cost_results (include/lpx.h): caller-allocated output arrays; rec, basis, at_upper, y and d may be NULL."""
+    _fields_ = [("status", ip), ("x", dp), ("value", dp), ("rec", C.POINTER(PackedCostRecord)), ("basis", ip),
+                ("at_upper", C.POINTER(C.c_uint8)), ("y", dp), ("d", dp)]
+
+
 PBNB_DONE, PBNB_ROOT, PBNB_NODES, PBNB_NODE_ITER, PBNB_EVENTS, PBNB_DEPTH, PBNB_REFUSED = range(7)    # LPX_PBNB_* (lpx_solve_packed_bnb)
 PBNB_STOPS = ("done", "root", "nodes", "node_iter", "events", "depth", "refused")
 
@@ -511,6 +524,8 @@ def lib() -> C.CDLL:
     L.lpx_packed_base_open.argtypes = [C.POINTER(PackedBaseModel), C.c_int, C.POINTER(RunOpts), C.POINTER(PackedDualResults),
                                        C.POINTER(vp)]
     L.lpx_packed_base_solve.argtypes = [vp, C.c_int32, dp, C.c_int, C.POINTER(RunOpts), C.POINTER(PackedDualResults), C.POINTER(Stats)]
+    L.lpx_packed_base_solve_costs.argtypes = [vp, C.c_int32, dp, dp, C.c_int, C.POINTER(RunOpts), C.POINTER(RunOpts),
+                                              C.POINTER(PackedCostResults), C.POINTER(Stats)]
     L.lpx_packed_base_close.argtypes = [vp]
     L.lpx_solve_packed_bnb.argtypes = [C.POINTER(PackedBnbModels), C.POINTER(PackedBnbOpts), C.POINTER(PackedBnbResults),
                                        C.POINTER(Stats)]

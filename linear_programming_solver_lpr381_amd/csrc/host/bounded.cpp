@@ -401,6 +401,30 @@ void CheckPackedBaseSolve(const void* h, int m32, int n32, int32_t count32, cons
         throw bad("too large: " + std::to_string(bytes) + " bytes of inputs and outputs, above 1 GiB (split the batch)");
 }
 
+// The argument checks of lpx_packed_base_solve_costs: those of lpx_packed_base_solve in their order with c in the place of b (b may
+// be NULL: every scenario keeps b0), either options structure refused for resident = 1, the 1 GiB rule over c0, c, b and the outputs.
+void CheckPackedBaseSolveCosts(const void* h, int m32, int n32, int32_t count32, const double* c, const double* b, int flags,
+                               const lpx_run_opts* o_primal, const lpx_run_opts* o_dual, const lpx_packed_cost_results* out)
+{
+    auto bad = [](const std::string& msg) { return LpxException(LPX_EINVAL, "lpx_packed_base_solve_costs: " + msg); };
+    if (!h || !c || !out) throw bad("null argument");
+    if (!out->status || !out->x || !out->value) throw bad("null status, x or value");
+    if (count32 < 1 || count32 > 65536) throw bad("count is outside [1, 65536]");
+    if (flags & ~LPX_BDUAL_LONG_STEP) throw bad("unknown flag: flags holds a bit other than LPX_BDUAL_LONG_STEP");
+    if ((o_primal && o_primal->resident > 0) || (o_dual && o_dual->resident > 0))
+        throw bad("there is no resident form of the bounded loop (resident = 1)");
+    const int64_t m = m32, n = n32, count = count32;
+    int64_t bytes = 8 * n + 8 * n * count + count * (4 + 8 * n + 8);
+    if (b) bytes += 8 * m * count;
+    if (out->rec) bytes += count * (int64_t)sizeof(lpx_packed_cost_record);
+    if (out->basis) bytes += count * 4 * m;
+    if (out->at_upper) bytes += count * n;
+    if (out->y) bytes += count * 8 * m;
+    if (out->d) bytes += count * 8 * n;
+    if (bytes > ((int64_t)1 << 30))
+        throw bad("too large: " + std::to_string(bytes) + " bytes of inputs and outputs, above 1 GiB (split the batch)");
+}
+
 // The argument checks of lpx_solve_packed_bnb: CheckPacked's list in its order up to the fit rule, then the options, and last --
 // it needs valid options -- the 1 GiB rule, which counts the log and the work slices (work_bytes: lpx::packed_bnb_work_bytes).
 void CheckPackedBnb(const lpx_packed_bnb_models* in, const lpx_packed_bnb_opts* opt, const lpx_packed_bnb_results* out,

@@ -248,6 +248,9 @@ void CheckPackedBaseOpen(const lpx_packed_base_model* in, int flags, const lpx_r
                          const void* h);
 void CheckPackedBaseSolve(const void* h, int m, int n, int32_t count, const double* b, int flags, const lpx_run_opts* o,
                           const lpx_packed_dual_results* out);
+// the argument checks of lpx_packed_base_solve_costs, the same way (b may be NULL); the call itself is lpx::packed_base_solve_costs
+void CheckPackedBaseSolveCosts(const void* h, int m, int n, int32_t count, const double* c, const double* b, int flags,
+                               const lpx_run_opts* o_primal, const lpx_run_opts* o_dual, const lpx_packed_cost_results* out);
 // the argument checks of lpx_solve_packed_bnb, the same way; work_bytes is lpx::packed_bnb_work_bytes; the call itself is lpx::packed_bnb_solve
 void CheckPackedBnb(const lpx_packed_bnb_models* in, const lpx_packed_bnb_opts* opt, const lpx_packed_bnb_results* out,
                     size_t (*work_bytes)(int count, int m, int n, int max_depth));

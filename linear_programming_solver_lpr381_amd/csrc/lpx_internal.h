@@ -242,6 +242,10 @@ int packed_base_open(const lpx_packed_base_model* in, int flags, const lpx_run_o
 int packed_base_solve(const PackedBase* base, int32_t count, const double* b, int flags, const lpx_run_opts* o,
                       const lpx_packed_dual_results* out, lpx_stats* st);
 void packed_base_close(PackedBase* base);
+// lpx_packed_base_solve_costs behind its argument checks (lpx_packed_cost.hip): c0 is the host copy of the base's costs ([n]) that
+// the API-level handle keeps; b may be null (every scenario keeps b0); op and od are the primal and the dual loop's options
+int packed_base_solve_costs(const PackedBase* base, const double* c0, int32_t count, const double* c, const double* b, int flags,
+                            const lpx_run_opts* op, const lpx_run_opts* od, const lpx_packed_cost_results* out, lpx_stats* st);
 // the packed batch of integer programs (lpx_packed_bnb.hip): PackedParams plus the shared integer mask ([n] bytes or null = every
 // variable), the search flags, the three budgets, both ratio tolerances (the root's primal loop, a node's dual loop), the log and
 // the work slices ([count][work_stride] bytes: what the search keeps outside LDS)

@@ -390,7 +390,7 @@ int lpx_solve_packed_dual(const lpx_packed_dual_models* in, int flags, const lpx
 }
 
 // ---- right-hand-side scenarios warm-started from one solved base (host/bounded.cpp CheckPackedBase*, lpx_packed_warm.hip) -------
-struct lpx_packed_base { PackedBase s; };
+struct lpx_packed_base { PackedBase s; std::vector<double> c0; };     // c0: the base's costs, for lpx_packed_base_solve_costs
 
 int lpx_packed_base_open(const lpx_packed_base_model* in, int flags, const lpx_run_opts* o, const lpx_packed_dual_results* base_out,
                          lpx_packed_base** h)
@@ -402,6 +402,7 @@ int lpx_packed_base_open(const lpx_packed_base_model* in, int flags, const lpx_r
     lpx_packed_base* base = new lpx_packed_base();
     const int rc = packed_base_open(in, flags, o, base_out, &base->s);
     if (rc != 0) { packed_base_close(&base->s); delete base; return rc; }     // only an optimal base is kept
+    base->c0.assign(in->c, in->c + in->n);
     *h = base;
     return 0;
 }
@@ -413,6 +414,18 @@ int lpx_packed_base_solve(const lpx_packed_base* h, int32_t count, const double*
     catch (const LpxException& ex) { set_error(ex.what()); return ex.code; }
     lpx_run_opts d; if (!o) { lpx_default_opts(&d, 1); o = &d; }
     return packed_base_solve(&h->s, count, b, flags, o, out, st);
+}
+
+int lpx_packed_base_solve_costs(const lpx_packed_base* h, int32_t count, const double* c, const double* b, int flags,
+                                const lpx_run_opts* o_primal, const lpx_run_opts* o_dual, const lpx_packed_cost_results* out,
+                                lpx_stats* st)
+{
+    try { CheckPackedBaseSolveCosts(h, h ? h->s.m : 0, h ? h->s.n : 0, count, c, b, flags, o_primal, o_dual, out); }
+    catch (const LpxException& ex) { set_error(ex.what()); return ex.code; }
+    lpx_run_opts dp, dd;
+    if (!o_primal) { lpx_default_opts(&dp, 0); o_primal = &dp; }
+    if (!o_dual) { lpx_default_opts(&dd, 1); o_dual = &dd; }
+    return packed_base_solve_costs(&h->s, h->c0.data(), count, c, b, flags, o_primal, o_dual, out, st);
 }
 
 int lpx_packed_base_close(lpx_packed_base* h)

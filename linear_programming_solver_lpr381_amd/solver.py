@@ -98,6 +98,29 @@ class PackedDualResult(PackedResult):   # lpx_packed_dual_results (include/lpx.h
 
 
 @dataclass
+class PackedCostResult:     # lpx_packed_cost_results (include/lpx.h): PackedBase.solve_costs, one entry per scenario along axis 0
+    Status: np.ndarray                      # (B,) int32: OPTIMAL, UNBOUNDED, INFEASIBLE, ITER_LIMIT or LPX_EINVAL of that scenario alone
+    Solution: np.ndarray                    # (B, n)
+    OptimalValue: np.ndarray                # (B,) in the user's sense
+    Events: Optional[np.ndarray] = None     # (B,) PrimalEvents + DualEvents
+    Z: Optional[np.ndarray] = None          # (B,) T[m, C-1] as the last loop left it
+    Basis: Optional[np.ndarray] = None      # (B, m) int32
+    AtUpper: Optional[np.ndarray] = None    # (B, n) uint8: 1 = x_j is nonbasic at its upper bound
+    Stats: Optional[dict] = None
+    Duals: Optional[np.ndarray] = None          # (B, m) y_i = d value / d b_i, the user's sense and rows
+    ReducedCosts: Optional[np.ndarray] = None   # (B, n) d_j = c_j - sum_i y_i A_ij
+    PrimalEvents: Optional[np.ndarray] = None   # (B,) pivots and bound flips of the primal loop
+    DualEvents: Optional[np.ndarray] = None     # (B,) pivots and passes of the dual loop (0 without b)
+    PrimalCounts: Optional[np.ndarray] = None   # (B, 3): kind-0 pivots, kind-1 pivots, bound flips
+    DualCounts: Optional[np.ndarray] = None     # (B, 3): kind-0 pivots, kind-1 pivots, long-step passes
+
+
+PACKED_COST_DTYPE = np.dtype([("status", "<i4"), ("primal_events", "<i4"), ("dual_events", "<i4"), ("pad", "<i4"),
+                              ("primal_kind0", "<i8"), ("primal_kind1", "<i8"), ("primal_flips", "<i8"),
+                              ("dual_kind0", "<i8"), ("dual_kind1", "<i8"), ("dual_passes", "<i8"), ("z", "<f8")])
+
+
+@dataclass
 class PackedBnbResult(PackedResult):    # lpx_packed_bnb_results (include/lpx.h): LPSolver.SolvePackedBnb
     # Status: OPTIMAL, INFEASIBLE, ITER_LIMIT (a budget: see Stop), the root's UNBOUNDED, or LPX_EINVAL / LPX_E_NEG_RHS of that model alone
     Stop: Optional[np.ndarray] = None           # (B,) int32 LPX_PBNB_*: done, root, nodes, node_iter, events, depth, refused (want "rec")
@@ -1042,6 +1065,57 @@ class PackedBase:           # lpx_packed_base (include/lpx.h): right-hand-side s
         if rc != 0:
             raise SolverException(rc, _lib.last_error())
         return take(st.as_dict())
+
+    def solve_costs(self, c, b=None, long_step: bool = True, max_iter=None, primal_max_iter=None,
+                    dual_max_iter=None) -> PackedCostResult:
+        """c: (B, n) or (n,) cost vectors of the base's model; b: None (every scenario keeps the base's right-hand side), (B, m) or
+        (m,), broadcast against c's batch.  ONE launch (lpx_packed_base_solve_costs): every workgroup moves the objective row of
+        the base's solved tableau, continues the bounded primal loop from the base's basis and, with b, moves the RHS column and
+        continues the dual loop.  Every scenario gets its own Status: OPTIMAL, UNBOUNDED, INFEASIBLE, ITER_LIMIT, or LPX_EINVAL for
+        a cost or a right-hand side that is not finite.  max_iter: the limit of both loops; primal_max_iter / dual_max_iter: the
+        limit of one loop alone, in front of max_iter.  With none given the dual loop takes the limit the base was opened with
+        (which was a dual loop's) and the primal loop its default."""
+        if self._h is None:
+            raise SolverException(_lib.EINVAL, "the packed base is closed")
+        c = np.asarray(c, dtype=np.float64)
+        if c.ndim == 1:
+            c = c[None, :]
+        if c.ndim != 2 or c.shape[1] != self.n or c.shape[0] < 1:
+            raise ValueError(f"c is (B, n) or (n,) with n = {self.n}")
+        if b is not None:
+            b = np.asarray(b, dtype=np.float64)
+            if b.ndim == 1:
+                b = b[None, :]
+            if b.ndim != 2 or b.shape[1] != self.m or b.shape[0] < 1:
+                raise ValueError(f"b is None, (B, m) or (m,) with m = {self.m}")
+            if b.shape[0] != c.shape[0] and 1 not in (b.shape[0], c.shape[0]):
+                raise ValueError(f"c has {c.shape[0]} scenarios and b has {b.shape[0]}")
+            B = max(b.shape[0], c.shape[0])
+            b = np.ascontiguousarray(np.broadcast_to(b, (B, self.m)))
+            c = np.broadcast_to(c, (B, self.n))
+        c = np.ascontiguousarray(c)
+        B, m, n = c.shape[0], self.m, self.n
+        status = np.zeros(B, dtype=np.int32); x = np.zeros((B, n)); value = np.zeros(B)
+        recs = (_lib.PackedCostRecord * B)()
+        basis = np.zeros((B, m), dtype=np.int32); at = np.zeros((B, n), dtype=np.uint8); y = np.zeros((B, m)); d = np.zeros((B, n))
+        pr = _lib.PackedCostResults(status.ctypes.data_as(_lib.ip), x.ctypes.data_as(_lib.dp), value.ctypes.data_as(_lib.dp), recs,
+                                    basis.ctypes.data_as(_lib.ip), at.ctypes.data_as(C.POINTER(C.c_uint8)), y.ctypes.data_as(_lib.dp),
+                                    d.ctypes.data_as(_lib.dp))
+        p_limit = primal_max_iter if primal_max_iter is not None else max_iter
+        d_limit = dual_max_iter if dual_max_iter is not None else max_iter if max_iter is not None else self._max_iter
+        op, od = ((_lib.default_opts(dual) if limit is None else _lib.default_opts(dual, max_iter=int(limit)))
+                  for dual, limit in ((False, p_limit), (True, d_limit)))
+        st = _lib.Stats()
+        rc = lib().lpx_packed_base_solve_costs(self._h, B, c.ctypes.data_as(_lib.dp), None if b is None else b.ctypes.data_as(_lib.dp),
+                                               _lib.BDUAL_LONG_STEP if long_step else 0, C.byref(op), C.byref(od), C.byref(pr), C.byref(st))
+        if rc != 0:
+            raise SolverException(rc, _lib.last_error())
+        r = np.frombuffer(recs, dtype=PACKED_COST_DTYPE)
+        return PackedCostResult(Status=status, Solution=x, OptimalValue=value, Events=r["primal_events"] + r["dual_events"], Z=r["z"].copy(),
+                                Basis=basis, AtUpper=at, Stats=st.as_dict(), Duals=y, ReducedCosts=d,
+                                PrimalEvents=r["primal_events"].copy(), DualEvents=r["dual_events"].copy(),
+                                PrimalCounts=np.stack([r["primal_kind0"], r["primal_kind1"], r["primal_flips"]], axis=1),
+                                DualCounts=np.stack([r["dual_kind0"], r["dual_kind1"], r["dual_passes"]], axis=1))
 
     def close(self):
         if self._h is not None:

@@ -32,12 +32,22 @@ sides.  `--warm-trace` makes three calls of each side at count 4096 on the 13 x 
 run of its own under
 `rocprofv3 --kernel-trace --stats`.
 
+`--compare-costs` measures the packed cost scenarios from a solved base (lpx_packed_base_solve_costs) against
+the cold packed call of the same scenarios, SolvePackedDual with c at stride n and everything else at stride 0, in the same library
+and process: +-20 % costs of covering(12, 60, 1) and covering(110, 50, 1), count 256, 4096 and 65536 (the last with BIG_REPS timed
+rounds), without b and with +-20 % right-hand sides, the long step on.  Two sides alternate in every round: cold; kept =
+PackedBase.solve_costs with the base opened outside the timed region.  Host wall of whole calls, the rule of section 4.17; every
+scenario asserted OPTIMAL on both sides and optima within 1e-9 relative; events per scenario of both sides.  With `--parent-lib
+PATH/liblpx.so` the existing PackedBase.solve call (lpx_packed_base_open / _solve) is measured on both libraries in the same
+process, alternating, with the bits of their outputs asserted equal.
+
 `--trace-only` runs leg (a) on the smaller model once per side (no untimed run in front), for a separate run under
 `rocprofv3 --kernel-trace --stats -- python tools/bench_bounded_long.py --trace-only`, whose kernel table gives the mean launch
 time of lpx_bounded_long_select, lpx_bounded_dual_select and the lpx_update launches they feed.
 
 usage: bench_bounded_long.py [--leg a|b|c]... [--root DIR] [--big-reps N] [--skip-big] [--trace-only]
-                             [--compare-packed [--parent-lib PATH] | --packed-trace | --compare-warm | --warm-trace] [REPS]"""
+                             [--compare-packed [--parent-lib PATH] | --packed-trace | --compare-warm | --warm-trace |
+                              --compare-costs [--parent-lib PATH]] [REPS]"""
 import json
 import os
 import statistics
@@ -48,7 +58,7 @@ import time
 def _args():
     a = sys.argv[1:]
     opt = {"legs": [], "root": None, "big_reps": 2, "skip_big": False, "trace_only": False, "reps": None, "compare_packed": False,
-           "packed_trace": False, "parent_lib": None, "compare_warm": False, "warm_trace": False}
+           "packed_trace": False, "parent_lib": None, "compare_warm": False, "warm_trace": False, "compare_costs": False}
     i = 0
     while i < len(a):
         if a[i] == "--leg":
@@ -67,6 +77,8 @@ def _args():
             opt["packed_trace"] = True; i += 1
         elif a[i] == "--compare-warm":
             opt["compare_warm"] = True; i += 1
+        elif a[i] == "--compare-costs":
+            opt["compare_costs"] = True; i += 1
         elif a[i] == "--warm-trace":
             opt["warm_trace"] = True; i += 1
         elif a[i] == "--parent-lib":
@@ -76,7 +88,7 @@ def _args():
     if not opt["legs"]:
         opt["legs"] = ["a", "b", "c"]
     if opt["reps"] is None:
-        opt["reps"] = 15 if opt["compare_packed"] else 7           # --compare-warm: 7
+        opt["reps"] = 15 if opt["compare_packed"] else 7           # --compare-warm, --compare-costs: 7
     return opt
 
 
@@ -349,9 +361,91 @@ def compare_warm(reps, big_reps, trace):
     return out
 
 
+def packed_warm_parent(reps, parent_lib):
+    """lpx_packed_base_open / _solve of this tree's library against the parent commit's, loaded beside it: the same arrays,
+    alternating; 4096 right-hand sides of covering(12, 60, 1)."""
+    import ctypes as C
+    Lb = L._lib
+    libs = {"tree": Lb.lib(), "parent": C.CDLL(os.path.abspath(parent_lib))}
+    for f in ("lpx_packed_base_open", "lpx_packed_base_solve", "lpx_packed_base_close"):
+        getattr(libs["parent"], f).argtypes = getattr(libs["tree"], f).argtypes
+    count, m, n = 4096, 12, 60
+    cs, As, b0s = covering_models(1, m, n)
+    c, A, b0 = (np.ascontiguousarray(v[0]) for v in (cs, As, b0s))
+    rel = np.ones(m, dtype=np.int32); up = np.ones(n)
+    bs = np.ascontiguousarray(b0 * np.random.default_rng(5).uniform(0.8, 1.2, size=(count, m)))
+    pm = Lb.PackedBaseModel(m, n, 1, c.ctypes.data_as(Lb.dp), A.ctypes.data_as(Lb.dp), b0.ctypes.data_as(Lb.dp), None,
+                            up.ctypes.data_as(Lb.dp), rel.ctypes.data_as(Lb.ip))
+    outs, t, hs = {}, {k: [] for k in libs}, {}
+    for k, lib in libs.items():
+        status = np.zeros(count, dtype=np.int32); x = np.zeros((count, n)); value = np.zeros(count)
+        recs = (Lb.PackedDualRecord * count)(); basis = np.zeros((count, m), dtype=np.int32); at = np.zeros((count, n), dtype=np.uint8)
+        y = np.zeros((count, m)); d = np.zeros((count, n))
+        pr = Lb.PackedDualResults(status.ctypes.data_as(Lb.ip), x.ctypes.data_as(Lb.dp), value.ctypes.data_as(Lb.dp), recs,
+                                  basis.ctypes.data_as(Lb.ip), at.ctypes.data_as(C.POINTER(C.c_uint8)), y.ctypes.data_as(Lb.dp),
+                                  d.ctypes.data_as(Lb.dp))
+        outs[k] = (pr, status, x, value, recs, basis, at, y, d)
+        hs[k] = C.c_void_p()
+        assert lib.lpx_packed_base_open(C.byref(pm), Lb.BDUAL_LONG_STEP, None, None, C.byref(hs[k])) == 0, k
+    for i in range(reps + 1):
+        for k, lib in libs.items():
+            ms, rc = _timed(lambda: lib.lpx_packed_base_solve(hs[k], count, bs.ctypes.data_as(Lb.dp), Lb.BDUAL_LONG_STEP, None,
+                                                              C.byref(outs[k][0]), None))
+            assert rc == 0, k
+            t[k].append(ms)
+    for k, lib in libs.items():
+        lib.lpx_packed_base_close(hs[k])
+    a, p = outs["tree"], outs["parent"]
+    assert all(a[j].tobytes() == p[j].tobytes() for j in (1, 2, 3, 5, 6, 7, 8)) and bytes(a[4]) == bytes(p[4]), "tree and parent differ"
+    rec = {k: stats(v[1:]) for k, v in t.items()}
+    rec["winner"] = verdict(rec["tree"], rec["parent"], "tree", "parent")
+    rec["equal_bits"] = True
+    return rec
+
+
+def compare_costs(reps, big_reps, parent_lib):
+    S = L.LPSolver()
+    out = {}
+    for m, n in ((12, 60), (110, 50)):
+        assert L._lib.lib().lpx_packed_fits(m, n) == 1
+        cs, As, b0s = covering_models(1, m, n)
+        c0, A, b0 = cs[0], As[0], b0s[0]
+        rel = np.ones(m, dtype=np.int32)
+        for count in (256, 4096, 65536):
+            g = np.random.default_rng(7)
+            costs = c0 * g.uniform(0.8, 1.2, size=(count, n))
+            rhs = b0 * g.uniform(0.8, 1.2, size=(count, m))
+            for with_b in (False, True):
+                bs = rhs if with_b else None
+                rounds = big_reps if count == 65536 else reps
+                sides = {"cold": [], "kept": []}
+                with S.OpenPackedBase(c0, A, b0, rel, 1.0, sense="min") as kept:
+                    for i in range(rounds + 1):
+                        ms, rc = _timed(lambda: S.SolvePackedDual(costs, A, rhs if with_b else b0, rel, 1.0, sense="min"))
+                        sides["cold"].append(ms)
+                        ms, rw = _timed(lambda: kept.solve_costs(costs, bs))
+                        sides["kept"].append(ms)
+                        assert (rc.Status == 0).all() and (rw.Status == 0).all(), "a scenario is not OPTIMAL"
+                        assert (np.abs(rw.OptimalValue - rc.OptimalValue) <= 1e-9 * np.maximum(1.0, np.abs(rc.OptimalValue))).all()
+                rec = {"shape": [m + 1, n + m + 1], "count": count, "with_b": with_b,
+                       "events_per_scenario_cold": float(rc.Events.mean()), "events_per_scenario_kept": float(rw.Events.mean()),
+                       "primal_events_per_scenario": float(rw.PrimalEvents.mean()), "dual_events_per_scenario": float(rw.DualEvents.mean())}
+                rec.update({k: stats(v[1:]) for k, v in sides.items()})         # the first round is the warm-up
+                rec["winner"] = verdict(rec["kept"], rec["cold"], "kept", "cold")
+                rec["cold_over_kept"] = rec["cold"]["median_ms"] / rec["kept"]["median_ms"]
+                out["%dx%d count %d %s" % (m + 1, n + m + 1, count, "c and b" if with_b else "c")] = rec
+                print(json.dumps({"row": list(out)[-1], **rec}), file=sys.stderr, flush=True)
+    if parent_lib:
+        out["packed_base_solve_tree_vs_parent"] = packed_warm_parent(reps, parent_lib)
+    return out
+
+
 def main():
     L._lib.check(L._lib.lib().lpx_init(0))
     out = {}
+    if OPT["compare_costs"]:
+        print(json.dumps(compare_costs(OPT["reps"], OPT["big_reps"], OPT["parent_lib"])))
+        return
     if OPT["compare_warm"] or OPT["warm_trace"]:
         print(json.dumps(compare_warm(OPT["reps"], OPT["big_reps"], OPT["warm_trace"])))
         return

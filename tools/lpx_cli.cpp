@@ -16,7 +16,8 @@
 // right-hand sides of that run) as ONE packed call (lpx_solve_packed) with c, A and the bounds shared by every run, and prints one
 // line "status value x1 .. xn" per right-hand side.  --bounded-dual [--long-step] --rhs-file F does the same by the dual start
 // (lpx_solve_packed_dual): >= rows and negative right-hand sides are accepted, an = row is refused; with --warm-base the input's own
-// right-hand side is solved once and every line continues from that base (lpx_packed_base_open / _solve).  --bnb-bounded --rhs-file F (with
+// right-hand side is solved once and every line continues from that base (lpx_packed_base_open / _solve); --cost-file F [--rhs-file G] beside
+// --warm-base re-solves a cost vector per line of F (with G: and the right-hand side of the same line) from that base (lpx_packed_base_solve_costs).  --bnb-bounded --rhs-file F (with
 // --binary or --upper bounds, and --long-step / --cutoff) solves the model as an integer program once per line of F as ONE packed
 // call (lpx_solve_packed_bnb): a whole branch and bound per right-hand side in one kernel launch, the same line per run.
 // --bnb-bounded --dual-root runs the search from a dual start (lpx_solve_bnb_bounded_dual; with --rhs-file F lpx_solve_packed_bnb_dual):
@@ -80,6 +81,28 @@ static std::string algorithm_key(const std::string& name)
     return key;
 }
 
+// the lines of a scenario file (--cost-file, --rhs-file beside it): `width` numbers per line, blank lines skipped.  0, or the exit
+// code behind a message
+static int read_rows(const std::string& path, const char* option, int width, std::vector<double>& out, int& count)
+{
+    std::ifstream rf(path);
+    if (!rf) { std::fprintf(stderr, "Error reading file: %s\n", path.c_str()); return 66; }
+    std::string line;
+    count = 0;
+    while (std::getline(rf, line)) {
+        std::istringstream ls(line);
+        std::vector<double> row; double v;
+        while (ls >> v) row.push_back(v);
+        if (row.empty() && ls.eof()) continue;          // a blank line
+        if ((int)row.size() != width || !ls.eof()) {
+            std::fprintf(stderr, "lpx_cli: %s: line %d does not hold %d numbers\n", option, count + 1, width);
+            return 65;
+        }
+        out.insert(out.end(), row.begin(), row.end()); ++count;
+    }
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     std::string algorithm = "Primal Simplex", input, exportPath;
@@ -88,6 +111,7 @@ int main(int argc, char** argv)
     std::string rhs_file;       // --rhs-file F beside --bounded: one packed call (lpx_solve_packed), a right-hand side per line of F
     bool dual_root = false;     // --dual-root beside --bnb-bounded: the search from a dual start (lpx_solve_bnb_bounded_dual; with --rhs-file lpx_solve_packed_bnb_dual)
     bool bounded_dual = false;  // --bounded-dual beside --rhs-file: that packed call by the dual start (lpx_solve_packed_dual)
+    std::string cost_file;      // --cost-file F beside --bounded-dual --warm-base: a cost vector per line of F, every line re-solved from the base (lpx_packed_base_solve_costs); with --rhs-file G line k of F goes with line k of G
     bool warm_base = false;     // --warm-base beside --bounded-dual --rhs-file: the input's own right-hand side solved once, every line of F from that base (lpx_packed_base_open / _solve)
     int search_flags = 0;       // --long-step / --cutoff beside --bnb-bounded
     int node_form = -1;         // --node-form beside --bnb-bounded: LPX_NODE_*; -1 = not given
@@ -116,6 +140,7 @@ int main(int argc, char** argv)
         else if (a == "--warm-base") warm_base = true;
         else if (a == "--dual-root") dual_root = true;
         else if (a == "--rhs-file" && i + 1 < argc) rhs_file = argv[++i];
+        else if (a == "--cost-file" && i + 1 < argc) cost_file = argv[++i];
         else if (a == "--long-step") search_flags |= LPX_BDUAL_LONG_STEP;
         else if (a == "--cutoff") search_flags |= LPX_BDUAL_CUTOFF;
         else if (a == "--node-form" && i + 1 < argc) {
@@ -215,6 +240,7 @@ int main(int argc, char** argv)
                         "               [--bounded [--rhs-file F]] [--bounded-dual [--long-step] --rhs-file F] [--export FILE] INPUT.txt\n"
                         "               [--binary --bnb-bounded [--long-step] [--cutoff] --rhs-file F]\n"
                         "               [--bounded-dual [--long-step] --warm-base --rhs-file F]\n"
+                        "               [--bounded-dual [--long-step] --warm-base --cost-file F [--rhs-file G]]\n"
                         "               [--bnb-bounded --dual-root [--long-step] [--cutoff] [--node-form F | --rhs-file F]]\n"
                         "  NAME: Primal Simplex | Revised Primal Simplex | Dual Simplex | Branch and Bound |\n"
                         "        Revised Branch and Bound | Branch and Bound Knapsack | Cutting Plane | Revised Cutting Plane |\n"
@@ -252,6 +278,10 @@ int main(int argc, char** argv)
                         "  --bounded-dual [--long-step] --warm-base --rhs-file F: the input's own right-hand side is solved once and kept on the\n"
                         "             device (lpx_packed_base_open); every line of F is then re-solved from that base's optimal basis in ONE kernel\n"
                         "             launch (lpx_packed_base_solve); the same line per run\n"
+                        "  --bounded-dual [--long-step] --warm-base --cost-file F [--rhs-file G]: the input's own model is solved once and kept on\n"
+                        "             the device; every line of F (n numbers, the costs c) is re-solved from that base in ONE kernel launch\n"
+                        "             (lpx_packed_base_solve_costs): the objective row is moved and the bounded primal loop continues.  With G,\n"
+                        "             line k of F goes with line k of G (m numbers) and the dual loop follows; unequal line counts are refused\n"
                         "  --bnb-bounded --rhs-file F: the model as an integer program once per line of F as ONE packed call (lpx_solve_packed_bnb:\n"
                         "             a whole branch and bound per right-hand side in one kernel launch; at most 100000 nodes and 2000000 events\n"
                         "             per run); with --binary or --upper bounds and --long-step / --cutoff; the same line per run\n"
@@ -290,7 +320,12 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "lpx_cli: --bnb-bounded --rhs-file combines only with --long-step / --cutoff and --upper / --lower / --binary\n");
         return 64;
     }
-    if (bounded_dual && (rhs_file.empty() || bounded_flag || bnb_bounded || bounded_form >= 0 || iterations || !edits.empty() || !exportPath.empty() ||
+    if (!cost_file.empty() && !(bounded_dual && warm_base)) { std::fprintf(stderr, "lpx_cli: --cost-file needs --bounded-dual --warm-base\n"); return 64; }
+    if (bounded_dual && warm_base && rhs_file.empty() && cost_file.empty()) {
+        std::fprintf(stderr, "lpx_cli: --bounded-dual --warm-base needs --rhs-file or --cost-file\n");
+        return 64;
+    }
+    if (bounded_dual && ((rhs_file.empty() && cost_file.empty()) || bounded_flag || bnb_bounded || bounded_form >= 0 || iterations || !edits.empty() || !exportPath.empty() ||
                          (search_flags & ~LPX_BDUAL_LONG_STEP))) {
         std::fprintf(stderr, "lpx_cli: --bounded-dual needs --rhs-file and combines only with --long-step and --upper / --lower / --binary\n");
         return 64;
@@ -357,6 +392,45 @@ int main(int argc, char** argv)
     for (const Bound& bd : bounds) {
         if (bd.index >= p.n) { std::fprintf(stderr, "lpx_cli: %s: index out of range\n", bd.text.c_str()); lpx_parsed_free(&p); return 64; }
         (bd.upper ? up : lo)[bd.index] = bd.value;
+    }
+    if (!cost_file.empty()) {
+        // the input's own model is the base; a cost vector per line of F and, with --rhs-file G, a right-hand side per line of G
+        for (int i = 0; i < p.m; ++i)
+            if (p.rel[i] == LPX_EQ) {
+                std::fprintf(stderr, "lpx_cli: --bounded-dual --cost-file: an = constraint is not accepted (pass it as its <= and >= pair)\n");
+                lpx_parsed_free(&p); return 65;
+            }
+        std::vector<double> costs, rhs;
+        int count = 0, rhs_count = 0;
+        int frc = read_rows(cost_file, "--cost-file", p.n, costs, count);
+        if (frc == 0 && !rhs_file.empty()) frc = read_rows(rhs_file, "--rhs-file", p.m, rhs, rhs_count);
+        if (frc != 0) { lpx_parsed_free(&p); return frc; }
+        if (count == 0) { std::fprintf(stderr, "lpx_cli: --cost-file holds no cost vector\n"); lpx_parsed_free(&p); return 65; }
+        if (!rhs_file.empty() && rhs_count != count) {
+            std::fprintf(stderr, "lpx_cli: --cost-file holds %d lines and --rhs-file holds %d\n", count, rhs_count);
+            lpx_parsed_free(&p); return 65;
+        }
+        std::vector<int32_t> status((size_t)(count > 0 ? count : 1));
+        std::vector<double> x((size_t)(count > 0 ? count : 1) * (size_t)(p.n > 0 ? p.n : 1)), value((size_t)(count > 0 ? count : 1));
+        lpx_packed_cost_results cr; std::memset(&cr, 0, sizeof cr);
+        cr.status = status.data(); cr.x = x.data(); cr.value = value.data();
+        lpx_run_opts ro; lpx_default_opts(&ro, 1);
+        lpx_packed_base_model bm; std::memset(&bm, 0, sizeof bm);
+        bm.m = p.m; bm.n = p.n; bm.sense = p.sense;
+        bm.c = p.c; bm.A = p.A; bm.b = p.b; bm.lower = lo.data(); bm.upper = up.data(); bm.rel = p.rel;
+        lpx_packed_base* base = nullptr;
+        int prc = lpx_packed_base_open(&bm, search_flags & LPX_BDUAL_LONG_STEP, &ro, nullptr, &base);
+        if (prc == 0) prc = lpx_packed_base_solve_costs(base, count, costs.data(), rhs_file.empty() ? nullptr : rhs.data(),
+                                                        search_flags & LPX_BDUAL_LONG_STEP, nullptr, &ro, &cr, nullptr);
+        lpx_packed_base_close(base);
+        if (prc != 0) { lpx_parsed_free(&p); lpx_last_error(err, sizeof err); std::fprintf(stderr, "%s\n", err); return prc == LPX_EDEVICE ? 69 : 70; }
+        for (int i = 0; i < count; ++i) {
+            std::printf("%d %.17g", status[i], value[i]);
+            for (int j = 0; j < p.n; ++j) std::printf(" %.17g", x[(size_t)i * p.n + j]);
+            std::printf("\n");
+        }
+        lpx_parsed_free(&p);
+        return 0;
     }
     if (!rhs_file.empty()) {
         // one packed call: a right-hand side per line, everything else shared at stride 0
